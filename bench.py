@@ -495,7 +495,13 @@ def main():
                          "(the code path of N > 1 on a one-GPU box; the timed loop then includes the collective)")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic_latest.json"),
                     help="per-launch HBM bytes of the dominant kernel from a rocprofv3 --pmc run of this workload")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64): lnL [1], "
+                         "branch_gradient [2T-1] and, with --subst-gradient, parameter_gradient; the inputs depend on the arguments only, "
+                         "so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -632,13 +638,21 @@ def main():
     t0 = time.perf_counter()
     for _ in range(args.steps):
         ts = time.perf_counter()
-        lnl, bg = step()[:2]  # (ends in a device-to-host copy of the result: nothing is left in flight)
+        last = step()  # (ends in a device-to-host copy of the result: nothing is left in flight)
         step_ms.append(1e3 * (time.perf_counter() - ts))
         p = eng.profile()  # HIP-event times of this evaluation, recorded on the engine's stream
         for k in prof:
             prof[k] += p[k]
     fence()
     elapsed = time.perf_counter() - t0
+    lnl, bg = last[:2]
+    if args.dump_outputs and rank == 0:  # every rank holds the whole job's result after the all-reduce
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        dump = {"lnL": np.array([lnl]), "branch_gradient": bg}
+        if len(last) > 2:
+            dump["parameter_gradient"] = last[2]
+        for name, arr in dump.items():
+            np.save(os.path.join(args.dump_outputs, f"{name}.npy"), np.ascontiguousarray(arr, dtype=np.float64))
     rank_ms = [1e3 * elapsed / args.steps]
     if collective:
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if rehearsal else device)

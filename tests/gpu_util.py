@@ -1,7 +1,18 @@
 """Helpers shared by the GPU parity tests: build an Engine from a golden case / an oracle Problem."""
+import subprocess
+import sys
+
 import numpy as np
 
 from physher_amd.engine import Engine
+
+
+def gpu_present():
+    """torch's answer from a fresh process.  Not this one: torch brings its own HIP runtime, and once the engine has made a HIP
+    call here (phyamd_create asks for the current device even when it refuses its arguments), torch reports no GPU on a GPU
+    machine while the engine still finds it."""
+    out = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.is_available())"], capture_output=True, text=True, timeout=300)
+    return out.stdout.strip() == "True"
 
 
 def engine_from_problem(pb, rescale=2, tip_mode="states", **kw):

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -41,6 +42,23 @@ def test_bench_line_contract():
     for key in ("value", "unit", "cores", "kind", "sample"):
         assert key in c, key
     assert c["kind"] in ("reference", "port") and c["cores"] == 1 and c["value"] > 0
+
+
+def test_bench_dump_outputs_hold_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the last timed step's lnL and branch gradient as float64 .npy files; the inputs depend on the
+    arguments only, so a second run writes the same arrays"""
+    a, b = tmp_path / "a", tmp_path / "b"
+    d = _run(["--no-cpu-baseline", "--dump-outputs", str(a)])
+    lnl, g = np.load(a / "lnL.npy"), np.load(a / "branch_gradient.npy")
+    assert lnl.dtype == np.float64 and lnl.shape == (1,) and lnl[0] == d["config"]["lnL"]
+    assert g.dtype == np.float64 and g.shape == (2 * 24 - 1,) and np.isfinite(g).all() and np.abs(g).max() > 0
+    assert sorted(os.listdir(a)) == ["branch_gradient.npy", "lnL.npy"]
+    _run(["--no-cpu-baseline", "--dump-outputs", str(b)])
+    for name in ("lnL", "branch_gradient"):
+        assert np.array_equal(np.load(a / f"{name}.npy"), np.load(b / f"{name}.npy")), name
+    _run(["--no-cpu-baseline", "--subst-gradient", "--dump-outputs", str(tmp_path / "c")])
+    pg = np.load(tmp_path / "c" / "parameter_gradient.npy")
+    assert pg.dtype == np.float64 and pg.shape == (5 + 4 + 4,) and np.isfinite(pg).all()
 
 
 def test_bench_secondary_modes():

@@ -45,8 +45,8 @@ def test_preloaded_binding_forwards_untouched_objects_to_the_cpu_path(tmp_path):
 
 
 def test_requested_device_without_gpu_is_a_loud_error(tmp_path):
-    import torch
-    if torch.cuda.is_available():
+    from gpu_util import gpu_present
+    if gpu_present():
         pytest.skip("a GPU is present")
     env = dict(os.environ, LD_PRELOAD=SHIM, PHYSHER_DEVICE="1")
     out = subprocess.run([DRIVER, "dump", "spec.txt", str(tmp_path / "x.json")], cwd=os.path.join(GOLDEN, "gtr_g4_t16"), env=env, capture_output=True, text=True,
