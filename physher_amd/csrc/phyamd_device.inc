@@ -23,29 +23,15 @@ __device__ __forceinline__ void store4(double *p, const d4 &v) {
 // Once-read / once-written streams (stored partials in the tree-walk kernels and child_message): non-temporal accesses.
 // A/B at 1000 x 1e6 x 4 x 4 (two runs each): plain 49.7 / 49.8 ms per evaluation, nt loads 49.1 / 49.6, nt stores 48.9,
 // both 49.2 / 49.0 -- a per-cent, kept because these bytes are never re-read from cache
-#ifndef PHYAMD_NT_LOAD
-#define PHYAMD_NT_LOAD 1
-#endif
-#ifndef PHYAMD_NT_STORE
-#define PHYAMD_NT_STORE 1
-#endif
 typedef double dv2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ d4 load4_stream(const double *p) {
-#if PHYAMD_NT_LOAD
 	const dv2 a = __builtin_nontemporal_load(reinterpret_cast<const dv2 *>(p));
 	const dv2 b = __builtin_nontemporal_load(reinterpret_cast<const dv2 *>(p) + 1);
 	return d4{a.x, a.y, b.x, b.y};
-#else
-	return load4(p);
-#endif
 }
 __device__ __forceinline__ void store4_stream(double *p, const d4 &v) {
-#if PHYAMD_NT_STORE
 	__builtin_nontemporal_store(dv2{v.x, v.y}, reinterpret_cast<dv2 *>(p));
 	__builtin_nontemporal_store(dv2{v.z, v.w}, reinterpret_cast<dv2 *>(p) + 1);
-#else
-	store4(p, v);
-#endif
 }
 
 // tip vector from a 4-bit ambiguity mask (one-hot for a known state, 0xF for a gap: datatype.h:26-66)
@@ -239,11 +225,7 @@ struct Ctx4 {
 		if (valu_tips) return matvec4(M(t), mask4(m));
 		return load4(tiptab + (((size_t)t * C + c) * 16 + m) * 4);
 	}
-#ifdef PHYAMD_ABL_NOMAT
-	__device__ __forceinline__ cptr M(int node) const { return opaque(as_const(mats + ((size_t)(node & 1) * C + c) * 16)); }  // A/B: two matrices, always cached
-#else
 	__device__ __forceinline__ cptr M(int node) const { return opaque(as_const(mats + ((size_t)node * C + c) * 16)); }
-#endif
 };
 
 // partial of a fringe node itself (before its own branch's matrix): cherry = product of two tip messages, cherry + tip

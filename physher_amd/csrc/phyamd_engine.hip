@@ -74,17 +74,9 @@ int fail(int code, const char *fmt, ...) {
 constexpr int WAVE = 64;             // lanes per wavefront (gfx950)
 // tuning constants (A/B measured on MI355X at 1000 taxa x 1e6 patterns): pattern groups swept
 // sequentially by one workgroup, and the occupancy the pre-order kernel is compiled for
-#ifndef PHYAMD_PPT_LOWER
-#define PHYAMD_PPT_LOWER 2
-#endif
-#ifndef PHYAMD_PPT_UPPER
-#define PHYAMD_PPT_UPPER 8
-#endif
-#ifndef PHYAMD_UPPER_MIN_WAVES
-#define PHYAMD_UPPER_MIN_WAVES 6
-#endif
+constexpr int PPT_LOWER = 2, PPT_UPPER = 8;
+constexpr int UPPER_MIN_WAVES = 6;
 // patterns per thread of the tree-walk kernels are chosen per engine from the shard size (phyamd_create)
-constexpr int PPT_LOWER = PHYAMD_PPT_LOWER, PPT_UPPER = PHYAMD_PPT_UPPER;
 constexpr int MAX_WAVES = 16;        // 1024 threads
 constexpr double SCALING_THRESHOLD = 1.0e-40;  // treelikelihood.c:1121
 
@@ -115,6 +107,7 @@ struct NodeOp {
 	// upper walk, plain kernel: a parked upper whose waiting time holds no other park ("leaf park": two thirds of them in a random
 	// tree) can wait in the wave's LDS slot instead of HBM.  bit 0: the parent's upper is read from LDS; bit 1 / 2: the left /
 	// right child's upper is parked in LDS.  The HBM slot stays assigned (the rescaling and parameter variants use it).
+	// (bit 3 is no longer set by the host; k_lower4_walk still tests it)
 	int32_t lds_park;
 };
 

@@ -343,7 +343,7 @@ int run_gradient(Shard *e, int flags, bool with_params = false) {
 	}
 	bool any_explicit = false;  // explicit matrices have no eigen system: the tree-walk's eigen-basis branch term does not cover them
 	for (uint8_t x : e->explicit_host) any_explicit |= x != 0;
-	const bool walk_params = with_params && !any_explicit && !e->generic && e->walking && e->walk_upper_on && e->walk_params_on &&
+	const bool walk_params = with_params && !any_explicit && !e->generic && e->walking &&
 	                         !((flags & PHYAMD_GRAD_COMPAT_SCALED) && e->scaling_on);
 	if (with_params && !e->generic && !walk_params) e->level_upper_needed = true;
 	if ((rc = ensure_upper_storage(e))) return rc;

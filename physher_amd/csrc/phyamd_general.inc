@@ -25,27 +25,7 @@
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
-#ifndef PHYAMD_GEN_PREFETCH
-#define PHYAMD_GEN_PREFETCH 1
-#endif
-#ifndef PHYAMD_GEN_ABL
-#define PHYAMD_GEN_ABL 0  // measurement only (results are wrong): 1 = no operand loads, 2 = no matrix products, 4 = no partial stores
-#endif
-#ifndef PHYAMD_GEN_ILV
-#define PHYAMD_GEN_ILV 1  // 20 states: the two row tiles' chains of a product issued alternately (mfma_matvec); 0: A/B switch
-#endif
-#ifndef PHYAMD_GEN_QP
-#define PHYAMD_GEN_QP 1  // 20 states: the branch term of a tip child from the image of Qf P(t) (GenFuse::QP); 0: A/B switch
-#endif
-#ifndef PHYAMD_GEN_CLAMP_LOADS
-#define PHYAMD_GEN_CLAMP_LOADS 1
-#endif
-#ifndef PHYAMD_GEN_WAVES20
-#define PHYAMD_GEN_WAVES20 8
-#endif
-#ifndef PHYAMD_GEN_OCC20
-#define PHYAMD_GEN_OCC20 4
-#endif
+constexpr int GEN_WAVES20 = 8, GEN_OCC20 = 4;  // 20 states: waves per workgroup, and waves per SIMD the kernels are compiled for
 constexpr int GEN_TILES_MAX = 8;  // 16-pattern tiles per wave: chosen per level by choose_gen_tiles (phyamd_launch.inc)
 // Workgroups are 8 waves, two per SIMD, that share the LDS images: the f64 MFMA is a 64-cycle instruction issued in order, so a
 // lone wave per SIMD leaves the matrix pipe idle through every load, state sum and store (measured at 61 states with one wave per
@@ -54,8 +34,8 @@ constexpr int GEN_TILES_MAX = 8;  // 16-pattern tiles per wave: chosen per level
 // image, and B fragments are loaded right before the product that consumes them.
 template <int RT>
 struct GenGeo {
-	static constexpr int WAVES = PHYAMD_GEN_WAVES20 > 0 && RT == 2 ? PHYAMD_GEN_WAVES20 : 8;
-	static constexpr int MIN_WAVES_PER_SIMD = RT >= 4 ? 2 : PHYAMD_GEN_OCC20;
+	static constexpr int WAVES = RT == 2 ? GEN_WAVES20 : 8;
+	static constexpr int MIN_WAVES_PER_SIMD = RT >= 4 ? 2 : GEN_OCC20;
 	static constexpr int MIN_PATTERNS_PER_BLOCK = WAVES * 16;  // one tile per wave: the finest grid, which sizes the gradient slabs
 };
 // state count of a tile shape: (2, 5) = 20, (4, 15) = 60, (4, 16) = 61
@@ -65,13 +45,10 @@ struct GenStates {
 	static_assert((RT == 2 && KT == 5) || (RT == 4 && (KT == 15 || KT == 16)), "tile shapes of 20 / 60 / 61 states");
 };
 
-// 20 states (RT = 2, KT = 5): rows 16..19 go through the 4x4x4 MFMA (see mfma_matvec); PHYAMD_GEN_TAIL4 = 0: A/B switch
-#ifndef PHYAMD_GEN_TAIL4
-#define PHYAMD_GEN_TAIL4 1
-#endif
+// 20 states (RT = 2, KT = 5): rows 16..19 go through the 4x4x4 MFMA (see mfma_matvec)
 template <int RT, int KT>
 struct TailRows {
-	static constexpr bool ON = PHYAMD_GEN_TAIL4 != 0 && RT == 2 && KT == 5;
+	static constexpr bool ON = RT == 2 && KT == 5;
 };
 
 template <int RT, int KT>
@@ -143,13 +120,11 @@ __device__ __forceinline__ void stage_image(double *img, const double *__restric
 template <int RT, int KT>
 __device__ __forceinline__ void mfma_matvec(const double *img, const double (&b)[KT], f64x4 (&d)[RT]) {
 	const int lane = threadIdx.x & 63;
-	if (PHYAMD_GEN_ABL & 2) {
-#pragma unroll
-		for (int t = 0; t < RT; t++) d[t] = f64x4{b[0], b[1], b[2], b[3]} * img[lane];
-		return;
-	}
-	if (PHYAMD_GEN_ILV && TailRows<RT, KT>::ON) {
-		// 20 states: the 16-row chain and the chain of rows 16..19 advance together -- each instruction's predecessor in its own
+	if (TailRows<RT, KT>::ON) {
+		// rows 16..19 of a 20-state product: v_mfma_f64_4x4x4_4b (four 4 x 4 x 4 blocks = the tile's sixteen patterns, 19 cycles)
+		// instead of a second 16-row tile that is three quarters padding (64 cycles).  Its B layout (lane = 16 k + pattern) IS
+		// the 16x16x4 one, and its single result register is rows 16 + (lane >> 4): register 0 of the second row tile.
+		// The 16-row chain and the chain of rows 16..19 advance together -- each instruction's predecessor in its own
 		// chain is two issues back, and all ten fragments are requested before the first product
 		f64x4 acc = {0., 0., 0., 0.};
 		double acc1 = 0.0;
@@ -165,17 +140,6 @@ __device__ __forceinline__ void mfma_matvec(const double *img, const double (&b)
 	}
 #pragma unroll
 	for (int t = 0; t < RT; t++) {
-		if (TailRows<RT, KT>::ON && t == 1) {
-			// rows 16..19 of a 20-state product: v_mfma_f64_4x4x4_4b (four 4 x 4 x 4 blocks = the tile's sixteen patterns, 19 cycles)
-			// instead of a second 16-row tile that is three quarters padding (64 cycles).  Its B layout (lane = 16 k + pattern) IS
-			// the 16x16x4 one, and its single result register is rows 16 + (lane >> 4): register 0 of the second row tile.
-			double acc1 = 0.0;
-#pragma unroll
-			for (int ks = 0; ks < KT; ks++) acc1 = __builtin_amdgcn_mfma_f64_4x4x4f64(img[(KT + ks) * 64 + lane], b[ks], acc1, 0, 0, 0);
-			d[1] = f64x4{acc1, 0., 0., 0.};
-			__builtin_amdgcn_sched_barrier(0);
-			continue;
-		}
 		f64x4 acc = {0., 0., 0., 0.};
 #pragma unroll
 		for (int ks = 0; ks < KT; ks++) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(img[(t * KT + ks) * 64 + lane], b[ks], acc, 0, 0, 0);
@@ -236,29 +200,20 @@ __device__ __forceinline__ size_t opaque_stride(int Pp) {
 	return (size_t)(unsigned)v;
 }
 
-#ifndef PHYAMD_GEN_NT
-#define PHYAMD_GEN_NT 2  // partials are written once and read once or twice, launches apart: 0 = plain, 1 = non-temporal stores, 2 = also loads (cfg3 192 / 199 / 205 evals/s, cfg4 457 / 461 / 469)
-#endif
+// partials are written once and read once or twice, launches apart: non-temporal loads and stores (plain / nt stores / nt both:
+// cfg3 192 / 199 / 205 evals/s, cfg4 457 / 461 / 469)
 __device__ __forceinline__ double ld_row(const double *row, unsigned byte_off) {
-#if PHYAMD_GEN_NT >= 2
 	return __builtin_nontemporal_load(reinterpret_cast<const double *>(reinterpret_cast<const char *>(row) + byte_off));
-#else
-	return *reinterpret_cast<const double *>(reinterpret_cast<const char *>(row) + byte_off);
-#endif
 }
 __device__ __forceinline__ void st_row(double *row, unsigned byte_off, double v) {
-#if PHYAMD_GEN_NT >= 1
 	__builtin_nontemporal_store(v, reinterpret_cast<double *>(reinterpret_cast<char *>(row) + byte_off));
-#else
-	*reinterpret_cast<double *>(reinterpret_cast<char *>(row) + byte_off) = v;
-#endif
 }
 
 // B fragments of an internal node's partial: state 4ks + (lane>>4), pattern pat
 template <int RT, int KT>
 __device__ __forceinline__ void load_b(const double *__restrict__ plane0, size_t Pp, const TileAddr<RT, KT> &ta, double (&b)[KT]) {
 #pragma unroll
-	for (int ks = 0; ks < KT; ks++) b[ks] = (PHYAMD_GEN_ABL & 1) ? 0.25 + ta.off : ld_row(plane0 + (size_t)(4 * ks) * Pp, ks == KT - 1 ? ta.last : ta.off);
+	for (int ks = 0; ks < KT; ks++) b[ks] = ld_row(plane0 + (size_t)(4 * ks) * Pp, ks == KT - 1 ? ta.last : ta.off);
 }
 
 // M . tip in D layout without MFMAs: one-hot -> column `code` of M, unknown (code S) -> row sums, code S + 1 + q -> the
@@ -322,7 +277,7 @@ struct GenFuse {
 	// QP (20 states): the branch term of a TIP child, sum_i u_i (Qf P e_code)_i, takes the column of Qf P(t) from an image of that
 	// product (k_tip_rate_products, staged like the others: four more slots for the tips on either side) instead of forming
 	// Qf . (P e_code) on the matrix cores -- 200 of the 794 products of a cfg3 evaluation.  33 KB images leave no room at 60 / 61 states.
-	static constexpr bool QP = PHYAMD_GEN_QP != 0 && RT == 2;
+	static constexpr bool QP = RT == 2;
 	static constexpr int LOWER_IMAGES = ON ? 7 : 3, UPPER_IMAGES = (ON ? 8 : 4) + (QP ? 4 : 0);  // lower: the node's own, two children, four cherry tips
 };
 
@@ -359,7 +314,7 @@ __device__ __forceinline__ void store_d_tile(double *__restrict__ plane0, size_t
 #pragma unroll
 	for (int r = 0; r < 4; r++) {
 		const int base = 16 * t + 4 * r;  // a constant once the caller's loop over t is unrolled
-		if (!(PHYAMD_GEN_ABL & 4) && base < S && ta.ok && (base + 3 < S || rq < S - base)) st_row(plane0 + (size_t)base * Pp, ta.off, d[r]);
+		if (base < S && ta.ok && (base + 3 < S || rq < S - base)) st_row(plane0 + (size_t)base * Pp, ta.off, d[r]);
 	}
 }
 

@@ -146,22 +146,15 @@ void launch_lower_walk_ppt(Shard *e, size_t lds) {
 	const int nb = (e->nblk_walk_upper + PPT - 1) / PPT;  // nblk_walk_upper = workgroups at one pattern per thread
 	e->lnl_blocks = nb * PPT * e->G;  // one entry per block of 64 patterns (a trailing all-padding block adds 0)
 	e->lnl_per_block = true;
-	if (e->lds_park_on) {  // + one park slot per wave and pattern group (LPARK)
-		lds += sizeof(double) * ((size_t)(e->G & 1) + (size_t)e->G * e->C * PPT * 4 * WAVE);
-		// the chunked list: every cut subtree as workgroups of its own (blockIdx.y), then the top part with the root
-		const int subtrees = (int)e->walk_lower_chunk_off.size() - 2;
-		for (int phase = subtrees > 0 ? 0 : 1; phase < 2; phase++)
-			hipLaunchKernelGGL((k_lower4_walk<WAVES, PPT, SCALE, true>), dim3(nb, phase ? 1 : subtrees), block_dims(e), lds, e->stream, e->d_walk_lower_chunk_ops,
-			                   (int)e->walk_lower_chunk_ops.size(), e->T, e->P, e->C, e->d_tipmask, e->d_lower, e->d_mats, e->d_tiptab, e->d_lscale, e->d_freqs,
-			                   e->d_props, e->d_weights, e->d_plk, e->d_wl, e->d_lnl_part, (const int *)e->d_walk_lower_chunk_off, phase ? std::max(0, subtrees) : 0,
-			                   phase);
-		e->prof.lower_launches = subtrees > 0 ? 2 : 1;
-		return;
-	}
-	e->prof.lower_launches = 1;
-	hipLaunchKernelGGL((k_lower4_walk<WAVES, PPT, SCALE>), dim3(nb), block_dims(e), lds, e->stream, e->d_walk_lower_ops, (int)e->walk_lower_ops.size(), e->T,
-	                   e->P, e->C, e->d_tipmask, e->d_lower, e->d_mats, e->d_tiptab, e->d_lscale, e->d_freqs, e->d_props, e->d_weights, e->d_plk, e->d_wl,
-	                   e->d_lnl_part, (const int *)nullptr, 0, 1);
+	lds += sizeof(double) * ((size_t)(e->G & 1) + (size_t)e->G * e->C * PPT * 4 * WAVE);  // + one park slot per wave and pattern group (LPARK)
+	// the chunked list: every cut subtree as workgroups of its own (blockIdx.y), then the top part with the root
+	const int subtrees = (int)e->walk_lower_chunk_off.size() - 2;
+	for (int phase = subtrees > 0 ? 0 : 1; phase < 2; phase++)
+		hipLaunchKernelGGL((k_lower4_walk<WAVES, PPT, SCALE>), dim3(nb, phase ? 1 : subtrees), block_dims(e), lds, e->stream, e->d_walk_lower_chunk_ops,
+		                   (int)e->walk_lower_chunk_ops.size(), e->T, e->P, e->C, e->d_tipmask, e->d_lower, e->d_mats, e->d_tiptab, e->d_lscale, e->d_freqs,
+		                   e->d_props, e->d_weights, e->d_plk, e->d_wl, e->d_lnl_part, (const int *)e->d_walk_lower_chunk_off, phase ? std::max(0, subtrees) : 0,
+		                   phase);
+	e->prof.lower_launches = subtrees > 0 ? 2 : 1;
 }
 
 template <int WAVES, bool SCALE>
@@ -172,20 +165,17 @@ int launch_lower_walk(Shard *e) {
 	// full card, so it takes whichever needs fewer rounds of resident workgroups (a workgroup's walk takes as long whatever
 	// shares its CU): two per thread make a 125k-pattern shard ONE round of 977 workgroups instead of two of 1954 (1.9 vs 2.1 ms).
 	int ppt = 1;
-	if (!SCALE && e->ppt_walk_lower == 0) {
-		const size_t park = e->lds_park_on ? sizeof(double) * ((size_t)(e->G & 1) + (size_t)e->G * e->C * 4 * WAVE) : 0;
+	if (!SCALE) {
+		const size_t park = sizeof(double) * ((size_t)(e->G & 1) + (size_t)e->G * e->C * 4 * WAVE);
 		const int threads = e->C * e->G * WAVE;  // the block that is launched (block_dims), not the template's bound
 		if (e->lower_walk_slots[0] == 0) {  // (reset with the pattern storage: the launch shape follows G and C)
-			e->lower_walk_slots[0] = e->lds_park_on ? resident_workgroups(e, k_lower4_walk<WAVES, 1, SCALE, true>, threads, lds + park)
-			                                        : resident_workgroups(e, k_lower4_walk<WAVES, 1, SCALE>, threads, lds);
-			e->lower_walk_slots[1] = e->lds_park_on ? resident_workgroups(e, k_lower4_walk<WAVES, 2, SCALE, true>, threads, lds + 2 * park)
-			                                        : resident_workgroups(e, k_lower4_walk<WAVES, 2, SCALE>, threads, lds);
+			e->lower_walk_slots[0] = resident_workgroups(e, k_lower4_walk<WAVES, 1, SCALE>, threads, lds + park);
+			e->lower_walk_slots[1] = resident_workgroups(e, k_lower4_walk<WAVES, 2, SCALE>, threads, lds + 2 * park);
 		}
 		const long slots1 = e->lower_walk_slots[0], slots2 = e->lower_walk_slots[1];
 		const long g = e->nblk_walk_upper, r1 = (g + slots1 - 1) / slots1, r2 = 2 * (((g + 1) / 2 + slots2 - 1) / slots2);
 		ppt = (r2 <= r1 || g <= slots1) ? 2 : 1;  // (less than one round either way: two per thread measure 7 % better at 1e5 patterns)
-	} else if (!SCALE)
-		ppt = e->ppt_walk_lower;
+	}
 	if (ppt == 1) launch_lower_walk_ppt<WAVES, SCALE, 1>(e, lds);
 	else launch_lower_walk_ppt<WAVES, SCALE, 2>(e, lds);
 	HIP_TRY(hipGetLastError());
@@ -209,7 +199,7 @@ int launch_lower_w(Shard *e) {
 	}
 	e->scale_exp2 = false;  // (every other post-order kernel rescales as the reference does
 	e->stored_tform = false;  //  and stores the partials themselves)
-	if (e->walking && e->walk_lower_on && !e->incremental_pass) return e->scaling_on ? launch_lower_walk<WAVES, true>(e) : launch_lower_walk<WAVES, false>(e);
+	if (e->walking && !e->incremental_pass) return e->scaling_on ? launch_lower_walk<WAVES, true>(e) : launch_lower_walk<WAVES, false>(e);
 	return e->scaling_on ? launch_lower_levels<WAVES, true>(e) : launch_lower_levels<WAVES, false>(e);
 }
 
@@ -311,7 +301,7 @@ bool exp2_scaling(const Shard *e) { return e->scaling_on && e->exp2_on && !e->co
 bool tform_storage(const Shard *e) { return e->scaling_on ? exp2_scaling(e) : e->tform_on && !e->compat_sticky; }  // (PHYAMD_STREAM_TFORM = 0: plain evaluations only)
 
 bool lower_stream_applies(const Shard *e) {
-	return e->walking && e->walk_lower_on && e->stream_walk && e->lstream_on && e->lds_park_on && (!e->scaling_on || exp2_scaling(e) || e->C <= STREAM_WAVES) &&
+	return e->walking && e->stream_walk && e->lstream_on && (!e->scaling_on || exp2_scaling(e) || e->C <= STREAM_WAVES) &&
 	       !e->incremental_pass && !e->lstream_desc.empty();
 }
 
@@ -393,8 +383,7 @@ int launch_upper_stream(Shard *e) {
 	const bool exp2 = SCALE && e->scale_exp2;
 	if (exp2 && (rc = ensure_ints(e, &e->d_uexp, &e->uexp_alloc, std::max<size_t>(1, e->upper_alloc_slots) * e->C * e->P))) return rc;
 	const int waves = SCALE && !exp2 ? e->C : STREAM_WAVES;
-	size_t lds = (size_t)STREAM_LDS_PER_WAVE * waves + (exp2 ? (size_t)waves * STREAM_PARK_SLOTS * WAVE * sizeof(int) : SCALE ? (size_t)4 * e->C * WAVE * sizeof(double) : 0);
-	if (const char *env = std::getenv("PHYAMD_LDS_PAD")) lds += (size_t)std::atoi(env);  // A/B: fewer workgroups per CU
+	const size_t lds = (size_t)STREAM_LDS_PER_WAVE * waves + (exp2 ? (size_t)waves * STREAM_PARK_SLOTS * WAVE * sizeof(int) : SCALE ? (size_t)4 * e->C * WAVE * sizeof(double) : 0);
 	const dim3 grid_x(SCALE && !exp2 ? (unsigned)nb : (unsigned)((nb + STREAM_WAVES - 1) / STREAM_WAVES) * e->C), block(WAVE, waves);
 	hipLaunchKernelGGL(k_op_tables, dim3(nops, e->C), dim3(64), 0, e->stream, nops, e->C, (const int *)e->d_stream_op_tips, (const int *)e->d_stream_op_deep,
 	                   (const int *)e->d_stream_site_tab, e->d_mats, FOLD ? e->d_Q : e->d_Qpi, reinterpret_cast<double *>(e->d_optab));
@@ -467,7 +456,7 @@ int reduce_stream_slab(Shard *e, double *out) {
 template <int WAVES, bool FOLD, bool SCALE, bool COMPAT>
 int launch_upper_walk_v(Shard *e) {
 	const int ops = (int)e->walk_upper_ops.size(), nb = e->nblk_walk_upper * e->G;
-	if (!COMPAT && e->stream_walk && e->lds_park_on && (!SCALE || e->scale_exp2 || e->C <= STREAM_WAVES)) {
+	if (!COMPAT && e->stream_walk && (!SCALE || e->scale_exp2 || e->C <= STREAM_WAVES)) {
 		if constexpr (!COMPAT) {
 			// (pattern tiles: the mask words follow the tile's tip codes, rebuilt with every tile copy: ~0.1 ms per tile)
 			int rc1 = ensure_mask_stream(e);
@@ -481,30 +470,19 @@ int launch_upper_walk_v(Shard *e) {
 		int rc2;
 		if ((rc2 = require_reference_lowers(e))) return rc2;
 	}
-	constexpr bool LPARK = true;  // leaf parks wait in LDS (2 KB per wave behind the columns and the rescaling exchange)
-	size_t lds = sizeof(double) * ((size_t)e->G * e->C * NACC * WCOL + (SCALE ? (size_t)4 * e->G * e->C * WAVE : 0) + (e->lds_park_on ? (size_t)4 * e->G * e->C * WAVE : 0));
-	if (const char *env = std::getenv("PHYAMD_LDS_PAD")) lds += (size_t)std::atoi(env);  // A/B: fewer workgroups per CU
+	// columns, the rescaling exchange, then the leaf parks' LDS slots (LPARK: 2 KB per wave)
+	const size_t lds = sizeof(double) * ((size_t)e->G * e->C * NACC * WCOL + (SCALE ? (size_t)4 * e->G * e->C * WAVE : 0) + (size_t)4 * e->G * e->C * WAVE);
 	int rc0;
-	if (LPARK && e->lds_park_on) {
-		if ((rc0 = allow_big_lds(k_upper4_walk<WAVES, FOLD, false, SCALE, COMPAT, LPARK>, lds))) return rc0;
-		// the chunked list: the top part, then every cut subtree as workgroups of its own (blockIdx.y)
-		const int subtrees = (int)e->walk_chunk_off.size() - 2;
-		for (int phase = 0; phase < (subtrees > 0 ? 2 : 1); phase++)
-			hipLaunchKernelGGL((k_upper4_walk<WAVES, FOLD, false, SCALE, COMPAT, LPARK>), dim3(e->nblk_walk_upper, phase ? subtrees : 1), block_dims(e), lds, e->stream,
-			                   e->d_walk_chunk_ops, ops, e->T, e->P, e->C, e->d_tipmask, e->d_lower, e->d_upper, e->d_mats, e->d_tiptab, FOLD ? e->d_Q : e->d_Qpi,
-			                   e->d_freqs, e->d_wl, e->d_gpart, nb, (const double *)nullptr, (const double *)nullptr, (double *)nullptr, e->d_props, e->d_weights,
-			                   (const int *)e->d_walk_chunk_off, phase);
-		HIP_TRY(hipGetLastError());
-		e->prof.upper_launches = subtrees > 0 ? 2 : 1;
-		e->grad_blocks = nb;
-		return PHYAMD_OK;
-	}
 	if ((rc0 = allow_big_lds(k_upper4_walk<WAVES, FOLD, false, SCALE, COMPAT>, lds))) return rc0;
-	hipLaunchKernelGGL((k_upper4_walk<WAVES, FOLD, false, SCALE, COMPAT>), dim3(e->nblk_walk_upper), block_dims(e), lds, e->stream, e->d_walk_upper_ops, ops, e->T,
-	                   e->P, e->C, e->d_tipmask, e->d_lower, e->d_upper, e->d_mats, e->d_tiptab, FOLD ? e->d_Q : e->d_Qpi, e->d_freqs, e->d_wl, e->d_gpart, nb,
-	                   (const double *)nullptr, (const double *)nullptr, (double *)nullptr, e->d_props, e->d_weights, (const int *)nullptr, 0);
+	// the chunked list: the top part, then every cut subtree as workgroups of its own (blockIdx.y)
+	const int subtrees = (int)e->walk_chunk_off.size() - 2;
+	for (int phase = 0; phase < (subtrees > 0 ? 2 : 1); phase++)
+		hipLaunchKernelGGL((k_upper4_walk<WAVES, FOLD, false, SCALE, COMPAT>), dim3(e->nblk_walk_upper, phase ? subtrees : 1), block_dims(e), lds, e->stream,
+		                   e->d_walk_chunk_ops, ops, e->T, e->P, e->C, e->d_tipmask, e->d_lower, e->d_upper, e->d_mats, e->d_tiptab, FOLD ? e->d_Q : e->d_Qpi,
+		                   e->d_freqs, e->d_wl, e->d_gpart, nb, (const double *)nullptr, (const double *)nullptr, (double *)nullptr, e->d_props, e->d_weights,
+		                   (const int *)e->d_walk_chunk_off, phase);
 	HIP_TRY(hipGetLastError());
-	e->prof.upper_launches = 1;
+	e->prof.upper_launches = subtrees > 0 ? 2 : 1;
 	e->grad_blocks = nb;
 	return PHYAMD_OK;
 }
@@ -574,16 +552,11 @@ int launch_upper_walk_params(Shard *e) {
 	const int nf = e->N * e->C * 20;
 	hipLaunchKernelGGL(k_eigen_weights, dim3((nf + 255) / 256), dim3(256), 0, e->stream, e->C, e->N, e->d_model, e->d_rates, e->d_props, e->d_lengths, e->d_explicit,
 	                   e->root, e->d_Fw);
-	static const bool catblk_on = [] { const char *v = std::getenv("PHYAMD_PARAMS_CATBLK"); return !v || std::atoi(v) != 0; }();
-	bool catblk = false;
-	if constexpr (!SCALE && WAVES == 4) catblk = catblk_on;
-	if (catblk) {  // four pattern groups of one category per workgroup (see k_upper4_walk, CATBLK)
-		if constexpr (!SCALE && WAVES == 4) {
-			const size_t lds4 = sizeof(double) * (size_t)4 * 16 * WCOL;
-			hipLaunchKernelGGL((k_upper4_walk<4, false, true, false, false, false, true>), dim3((unsigned)((nb + 3) / 4) * e->C), dim3(WAVE, 1, 4), lds4, e->stream,
-			                   e->d_walk_upper_ops, ops, e->T, e->P, e->C, e->d_tipmask, e->d_lower, e->d_upper, e->d_mats, e->d_tiptab, e->d_Qpi, e->d_freqs, e->d_wl,
-			                   e->d_gpart, nb, e->d_pbuf, e->d_Fw, e->d_gacc, e->d_props, e->d_weights, (const int *)nullptr, 0);
-		}
+	if constexpr (!SCALE && WAVES == 4) {  // four pattern groups of one category per workgroup (see k_upper4_walk, CATBLK)
+		const size_t lds4 = sizeof(double) * (size_t)4 * 16 * WCOL;
+		hipLaunchKernelGGL((k_upper4_walk<4, false, true, false, false, true>), dim3((unsigned)((nb + 3) / 4) * e->C), dim3(WAVE, 1, 4), lds4, e->stream,
+		                   e->d_walk_upper_ops, ops, e->T, e->P, e->C, e->d_tipmask, e->d_lower, e->d_upper, e->d_mats, e->d_tiptab, e->d_Qpi, e->d_freqs, e->d_wl,
+		                   e->d_gpart, nb, e->d_pbuf, e->d_Fw, e->d_gacc, e->d_props, e->d_weights, (const int *)nullptr, 0);
 	} else
 		hipLaunchKernelGGL((k_upper4_walk<WAVES, false, true, SCALE, false>), dim3(e->nblk_walk_upper), block_dims(e), lds, e->stream, e->d_walk_upper_ops, ops, e->T,
 		                   e->P, e->C, e->d_tipmask, e->d_lower, e->d_upper, e->d_mats, e->d_tiptab, e->d_Qpi, e->d_freqs, e->d_wl, e->d_gpart, nb, e->d_pbuf, e->d_Fw,
@@ -601,7 +574,7 @@ template <int WAVES>
 int launch_upper_w(Shard *e, int flags) {
 	const bool fold = flags & PHYAMD_GRAD_FOLD_ROOT_FREQS, compat = (flags & PHYAMD_GRAD_COMPAT_SCALED) && e->scaling_on;
 	e->grad_blocks = e->nblk;
-	if (e->walking && e->walk_upper_on) return launch_upper_walk<WAVES>(e, fold, compat);
+	if (e->walking) return launch_upper_walk<WAVES>(e, fold, compat);
 	if (e->scaling_on) {
 		if (fold) return compat ? launch_upper_levels<WAVES, true, true, true, false>(e) : launch_upper_levels<WAVES, true, true, false, false>(e);
 		return compat ? launch_upper_levels<WAVES, true, false, true, false>(e) : launch_upper_levels<WAVES, true, false, false, false>(e);
@@ -669,14 +642,7 @@ inline int choose_gen_tiles(int P, int waves, long work, int slots, double stage
 	return best;
 }
 
-inline double gen_stage_cost(int S) {
-	static const double env = [] { const char *v = std::getenv("PHYAMD_GEN_STAGE_COST"); return v ? std::atof(v) : 0.0; }();
-	return env > 0.0 ? env : (S == 20 ? 2.0 : 0.6);
-}
-inline int gen_fixed_tiles() {  // A/B runs: PHYAMD_GEN_TILES = n pins every level to n tiles per wave
-	static const int env = [] { const char *v = std::getenv("PHYAMD_GEN_TILES"); return v ? std::atoi(v) : 0; }();
-	return env >= 1 && env <= GEN_TILES_MAX ? env : 0;
-}
+inline double gen_stage_cost(int S) { return S == 20 ? 2.0 : 0.6; }
 
 template <int RT, int KT, bool SCALE>
 int launch_lower_gen(Shard *e) {
@@ -695,7 +661,7 @@ int launch_lower_gen(Shard *e) {
 		const int off = level_off[lv], cnt = level_off[lv + 1] - off;
 		if (cnt == 0) continue;
 		launched++;
-		const int tiles = gen_fixed_tiles() ? gen_fixed_tiles() : choose_gen_tiles(e->P, WV, (long)cnt * e->C, slots, gen_stage_cost(e->S));
+		const int tiles = choose_gen_tiles(e->P, WV, (long)cnt * e->C, slots, gen_stage_cost(e->S));
 		dim3 grid((e->P + WV * 16 * tiles - 1) / (WV * 16 * tiles), cnt, e->C);
 		const bool is_root = lv == levels - 1;
 		if (is_root)
@@ -734,7 +700,7 @@ int launch_upper_gen_v(Shard *e, bool compat) {
 	for (int lv = 0; lv < levels; lv++) {
 		const int off = e->upper_level_off[lv], cnt = e->upper_level_off[lv + 1] - off;
 		if (cnt == 0) continue;
-		const int tiles = gen_fixed_tiles() ? gen_fixed_tiles() : choose_gen_tiles(e->P, WV, (long)cnt * e->C, slots, gen_stage_cost(e->S));
+		const int tiles = choose_gen_tiles(e->P, WV, (long)cnt * e->C, slots, gen_stage_cost(e->S));
 		dim3 grid((e->P + WV * 16 * tiles - 1) / (WV * 16 * tiles), cnt, e->C);
 		if (SCALE) mxu = e->d_gen_scratch + (size_t)cnt * 3 * e->C * e->P;
 		hipLaunchKernelGGL((k_upper_gen<RT, KT, FOLD, SCALE>), grid, dim3(WV * 64), lds, e->stream, e->d_upper_ops + off, e->T, e->P, e->Pp, e->C,

@@ -91,12 +91,9 @@ __global__ __launch_bounds__(WAVES *WAVE) void k_lower4(const NodeOp *__restrict
 // dynamic LDS: SCALE: 6 * G*C*64 doubles (three double-buffered exchanges); then NACC * waves * 64 doubles (reduction)
 
 constexpr int NACC = 10;  // gradient accumulators per thread: 2 children + 4 + 4 fringe branches
-#ifndef PHYAMD_RED_STRIDED
-#define PHYAMD_RED_STRIDED 1
-#endif
 // tree-walk kernel: LDS column stride.  Four lanes add a column: lane s of the four takes entries s, s + 4, s + 8, ... and the stride
 // of 68 doubles puts the 32 readers of a half-wave on 32 different bank pairs (contiguous quarters at stride 66 met two- and three-way)
-constexpr int WCOL = PHYAMD_RED_STRIDED ? WAVE + 4 : WAVE + 2;
+constexpr int WCOL = WAVE + 4;
 
 struct Grad4 {
 	cptr Q;
@@ -178,7 +175,7 @@ __device__ __forceinline__ void descend_fringe(const Ctx4 &x, const GradT &gr, i
 }
 
 template <int WAVES, bool SCALE, bool FOLD, bool COMPAT, bool PARAMS>
-__global__ __launch_bounds__(WAVES *WAVE, (WAVES == 4 && !PARAMS) ? PHYAMD_UPPER_MIN_WAVES : 1) void k_upper4(const NodeOp *__restrict__ ops, int T, int P, int C,
+__global__ __launch_bounds__(WAVES *WAVE, (WAVES == 4 && !PARAMS) ? UPPER_MIN_WAVES : 1) void k_upper4(const NodeOp *__restrict__ ops, int T, int P, int C,
                                                         const uint8_t *__restrict__ tipmask, const double *__restrict__ lower,
                                                         double *__restrict__ upper, const double *__restrict__ mats,
                                                         const double *__restrict__ tiptab, const double *__restrict__ Q,

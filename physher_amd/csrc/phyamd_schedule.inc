@@ -31,11 +31,12 @@ size_t node_partial_doubles(const Shard *e) { return (size_t)e->C * e->S * (e->g
 // Build the level schedule and the upper-slot assignment.
 // Chunked form of the pre-order walk (the launches with LDS park slots).  A workgroup's walk takes as long whatever shares its CU,
 // and the card holds 1280 of them: 15 625 workgroups (1e6 patterns) are 12.2 rounds, i.e. 13, and 1 563 (1e5 patterns) are two.
-// Cutting the op list into a top part and subtrees of at most 1 / PHYAMD_WALK_CHUNKS of the ops that run as workgroups of their own
+// Cutting the op list into a top part and subtrees of at most 1 / WALK_CHUNKS of the ops that run as workgroups of their own
 // (second launch, blockIdx.y = subtree) makes the rounds short and many, so the unfilled last one costs a fraction of a walk.
 // A cut node's upper crosses from one workgroup to another through HBM; since the subtrees of one pattern block run at the same
 // time, no HBM slot is recycled here (every HBM park has its own), and LDS parks stay inside a chunk.
 // walk_chunk_ops: [top ops | subtree 1 | subtree 2 | ...], walk_chunk_off: offsets (chunks + 1 entries)
+constexpr int WALK_CHUNKS = 3;  // (3 measured best once a re-read beside a cut subtree cost the post-order pass its write rate)
 void build_walk_chunks(Shard *e) {
 	const std::vector<NodeOp> &src = e->walk_upper_ops;
 	const int n = (int)src.size(), N = e->N;
@@ -48,9 +49,9 @@ void build_walk_chunks(Shard *e) {
 	for (int i = n - 1; i >= 0; i--)
 		for (int ch : {src[i].left, src[i].right})
 			if (opi[ch] >= 0) size[i] += size[opi[ch]];
-	const int parts = std::max(1, e->walk_chunks), target = std::max(16, (n + parts - 1) / parts);
+	const int target = std::max(16, (n + WALK_CHUNKS - 1) / WALK_CHUNKS);
 	std::vector<char> top(n, 0), cut(n, 0);
-	if (parts > 1 && n >= 32) {
+	if (n >= 32) {
 		std::vector<int> stack{0};
 		while (!stack.empty()) {
 			const int i = stack.back();
@@ -167,8 +168,8 @@ void build_lower_walk_chunks(Shard *e) {
 	for (int i = 0; i < n; i++)  // post-order: children's ops come first
 		for (int ch : {src[i].left, src[i].right})
 			if (opi[ch] >= 0) size[i] += size[opi[ch]];
-	const int parts = std::max(1, e->walk_chunks), target = std::max(16, (n + parts - 1) / parts);
-	if (parts <= 1 || n < 32) return;
+	const int target = std::max(16, (n + WALK_CHUNKS - 1) / WALK_CHUNKS);
+	if (n < 32) return;
 	std::vector<char> cut(n, 0), in_cut(n, 0);
 	std::vector<int> stack{n - 1};  // the root's op is the last one
 	while (!stack.empty()) {
@@ -379,52 +380,6 @@ void build_stream_ops(Shard *e) {
 			}
 	}
 	e->stream_R = (int)e->stream_qnode.size();
-	if (std::getenv("PHYAMD_DUMP_OPS")) {  // diagnostic: the kinds of the walk's ops (left x right), parents' upper sources, stored operands
-		static const char *kn[5] = {"TIP", "CORE", "DEEP", "CHERRY", "CHERRY_TIP"};
-		int hist[5][5] = {}, us[4] = {}, stores = 0, lparks = 0, lparks2 = 0;
-		for (int i = 0; i < n; i++) {
-			const StreamOp &s = e->stream_ops[i];
-			hist[s.flags & 7][(s.flags >> 3) & 7]++;
-			us[(s.flags >> 9) & 7]++;
-			stores += (s.slot_left >= 0) + (s.slot_right >= 0);
-			lparks += ((s.flags >> 12) & 3) != 0;
-			lparks2 += ((s.flags >> 12) & 3) != 0 && ((s.flags >> 6) & 1);
-		}
-		fprintf(stderr, "[phyamd] stream ops %d, rows %d, slab %d; upper source carry %d lds %d hbm %d root %d; hbm stores %d, lds parks %d (%d of them in the second slot)\n", n,
-		        (int)e->stream_row_entries.size() / 8, e->stream_R, us[SU_CARRY], us[SU_LDS], us[SU_U], us[SU_ROOT], stores, lparks, lparks2);
-		for (int a = 0; a < 5; a++)
-			for (int b = 0; b < 5; b++)
-				if (hist[a][b]) fprintf(stderr, "[phyamd]   %-10s x %-10s %d\n", kn[a], kn[b], hist[a][b]);
-		// how far ahead a stored operand COULD be requested: ops since the last op that used the same register set
-		int dist[3][4] = {};
-		int last[3] = {-1, -1, -1};
-		for (int i = 0; i < n; i++) {
-			const int want[3] = {want_a[i], want_b[i], want_u[i]};
-			for (int s = 0; s < 3; s++)
-				if (want[s] >= 0) {
-					const int d = last[s] < 0 ? 3 : std::min(3, i - last[s]);
-					dist[s][d]++;
-					last[s] = i;
-				}
-		}
-		for (int s = 0; s < 3; s++)
-			fprintf(stderr, "[phyamd]   register set %c: %d fetches could leave 1 op ahead, %d two, %d three or more\n", "ABU"[s], dist[s][1], dist[s][2], dist[s][3]);
-	}
-	if (const char *abl = std::getenv("PHYAMD_ABL_STREAM")) {  // TIMING-ONLY forms of the op list (results are wrong): 1 = every stored operand is
-		const int m = std::atoi(abl);                            // array 0 / slot 0 (cache-resident), 2 = every mask word is word 0, 3 = both
-		for (int i = 0; i < n; i++) {
-			if ((m & 1) && want_a[i] >= 0) want_a[i] = 0;
-			if ((m & 1) && want_b[i] >= 0) want_b[i] = 0;
-			if ((m & 1) && want_u[i] >= 0) want_u[i] = 0;
-			if ((m & 2) && first_word[i] >= 0) first_word[i] = 0;
-			if (m & 8) e->stream_ops[i].slot_left = e->stream_ops[i].slot_right = -1;  // no parked upper is stored
-			if (m & 4) {  // one matrix for everything (always in the scalar cache)
-				StreamOp &s = e->stream_ops[i];
-				s.parent = s.lnode = s.rnode = 0;
-				for (int j : {3, 0, 4, 5, 9}) s.la[j] = s.ra[j] = 0;
-			}
-		}
-	}
 	e->stream_words = (int)e->stream_row_entries.size() / 8;  // (build_lower_stream_ops appends the post-order walk's rows)
 	const int chunks = (int)e->walk_chunk_off.size() - 1;
 	for (int k = 0; k < chunks; k++) {
@@ -499,7 +454,6 @@ void build_lower_stream_ops(Shard *e) {
 	auto moff = [&](int32_t node) { return node >= 0 ? node * e->C * 128 : 0; };
 	e->lstream_desc.assign(n, LowerDesc{});
 	std::vector<int> pieces(n, 0), first_word(n, 0), last_word(n, 0), words(n, 0);
-	static const bool abl_words = [] { const char *v = std::getenv("PHYAMD_ABL_STREAM"); return v && (std::atoi(v) & 2); }();  // timing only: one hot row
 	MaskPacker packer(e->stream_row_entries);
 	for (int i = 0; i < n; i++) {
 		const NodeOp &o = e->walk_lower_chunk_ops[i];
@@ -515,7 +469,6 @@ void build_lower_stream_ops(Shard *e) {
 				d.wsh |= shift << (5 * words[i]) | (row & 3) << (10 + 2 * words[i]);  // shift 0-4 / 5-9, ring slot 10-11 / 12-13
 				words[i]++;
 			}
-		if (abl_words) words[i] = 0;  // (timing only: no row is ever fetched)
 		int fl = (u.flags & 0x3F) | (u.flags & 0x00FF0000);  // kinds and half kinds
 		d.lnode = moff(u.lnode);
 		d.rnode = moff(u.rnode);
@@ -547,7 +500,6 @@ void build_lower_stream_ops(Shard *e) {
 			fl |= src << (6 + 2 * side);
 		}
 		if (o.lds_park & 4) fl |= 1 << 10;
-		if (o.lds_park & 8) fl |= 1 << 11;
 		pieces[i] = (kinds[0] != CH_CORE ? 1 : 0) | (kinds[1] != CH_CORE ? 2 : 0);
 		d.flags = fl;
 	}
@@ -640,7 +592,7 @@ int build_schedule(Shard *e) {
 			if (l < T && r < T) kind[n] = CH_CHERRY;
 			else if (e->generic) continue;
 			else if ((l < T && kind[r] == CH_CHERRY) || (r < T && kind[l] == CH_CHERRY)) kind[n] = CH_CHERRY_TIP;
-			else if (e->deep_enabled && kind[l] != CH_CORE && kind[l] != CH_DEEP && kind[r] != CH_CORE && kind[r] != CH_DEEP)
+			else if (kind[l] != CH_CORE && kind[l] != CH_DEEP && kind[r] != CH_CORE && kind[r] != CH_DEEP)
 				kind[n] = CH_DEEP;  // both children are tips or fringe: 4-6 tips below, rebuilt in registers wherever its partial is needed
 		}
 	}
@@ -746,7 +698,7 @@ int build_schedule(Shard *e) {
 	// Depth-first op orders for the tree-walk kernels (see k_lower4_walk).  csize = core ops in the subtree.
 	e->walking = e->walk_enabled && !e->generic && !e->keep_partials;
 	// 20 states, plain evaluations: the post-order list drives k_lower_gen_walk (phyamd_genwalk.inc)
-	e->gen_walking = e->walk_enabled && e->gen_walk_on && e->generic && e->S == 20 && !e->keep_partials && !e->scaling_on;
+	e->gen_walking = e->walk_enabled && e->generic && e->S == 20 && !e->keep_partials && !e->scaling_on;
 	e->walk_lower_ops.clear();
 	e->walk_upper_ops.clear();
 	e->walk_upper_slots = 0;
@@ -798,10 +750,6 @@ int build_schedule(Shard *e) {
 					e->walk_lower_ops[lower_op_of[first]].lds_park |= 4;
 					op.lds_park |= first == l ? 1 : 2;
 				}
-				// timing-only ablation (results are wrong): PHYAMD_ABL_LOWER = 1 drops the stores of the nodes a second DEEP tier would not
-				// store (both children rebuilt from tips), 2 drops every store -- what writing less could buy the post-order walk
-				static const int abl_lower = [] { const char *v = std::getenv("PHYAMD_ABL_LOWER"); return v ? std::atoi(v) : 0; }();
-				if (abl_lower == 2 || (abl_lower == 1 && kind[l] != CH_CORE && kind[r] != CH_CORE && n != e->root)) op.lds_park |= 8;
 				lower_op_of[n] = (int)e->walk_lower_ops.size();
 				e->walk_lower_ops.push_back(op);
 				st.pop_back();
@@ -970,7 +918,7 @@ int upload_schedule(Shard *e) {
 int ensure_upper_storage(Shard *e) {
 	// the tree-walk schedule parks far fewer uppers than the level schedule keeps; parameter-gradient and inspection
 	// calls still run the level kernels, so the larger of the two is held once either has been needed
-	const bool level_path = !(e->walking && e->walk_upper_on) || e->level_upper_needed;  // (20-state walks: both, they alternate with level passes)
+	const bool level_path = !e->walking || e->level_upper_needed;  // (20-state walks: both, they alternate with level passes)
 	const size_t need = (size_t)std::max(1, level_path ? std::max(e->upper_slots, e->walk_upper_slots) : e->walk_upper_slots);
 	if (e->d_upper && e->upper_alloc_slots >= need) return PHYAMD_OK;
 	dev_free(e, &e->d_upper, e->upper_alloc_slots * node_partial_doubles(e));

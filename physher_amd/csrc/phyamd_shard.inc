@@ -10,7 +10,6 @@ struct Shard {
 	int nblk_root = 0;     // workgroups of k_root_finish (generic)
 	int nblk_lower = 0;    // pattern blocks of the post-order kernels
 	int nblk_walk = 0, nblk_walk_upper = 0;  // pattern blocks of the tree-walk kernels
-	int ppt_walk_lower = 0;  // patterns per thread of the post-order walk (0: by shard size)
 	int lower_walk_slots[2] = {0, 0};  // resident workgroups of k_lower4_walk at one / two patterns per thread
 	int gen_slots[3][2] = {};          // resident workgroups of the 20 / 60 / 61-state kernels on this engine's device: [lower, upper, upper FOLD][SCALE]
 	int lnl_blocks = 0;    // entries of d_lnl_part the last post-order pass wrote
@@ -48,12 +47,9 @@ struct Shard {
 	unsigned long schedule_epoch = 0;  // bumped whenever slots are reassigned from scratch
 	bool two_slots = false;            // d_lower / d_lscale hold 2 * core_count slots
 	bool force_root = false;           // the root's outputs (lnL_k, w_k / L_k, lnL) belong to a discarded state
-	bool walk_params_on = true;  // parameter gradients through the tree walk (PHYAMD_WALK_PARAMS = 0: level kernels)
 	bool generic_fusion = true;  // 20 states: cherries fused into their parents' ops (PHYAMD_GEN_FUSION = 0: every node stored)
-	bool lds_park_on = true;  // plain pre-order walk: leaf parks wait in LDS (PHYAMD_LDS_PARK = 0: every park goes to HBM)
-	bool walk_lower_on = true, walk_upper_on = true;  // A/B switches (PHYAMD_WALK_LOWER / PHYAMD_WALK_UPPER = 0)
 	bool walk_enabled = true, walking = false;  // tree-walk kernels (4 states, unscaled, not keep_partials)
-	bool gen_walk_on = true, gen_walking = false;  // post-order walk for 20 states (phyamd_genwalk.inc; PHYAMD_GEN_WALK = 0: level kernels)
+	bool gen_walking = false;  // post-order walk for 20 states (phyamd_genwalk.inc)
 	int *d_gen_walk_counter = nullptr;  // work-unit counter of the walk
 	int gen_walk_slots[1] = {0};  // resident workgroups of k_lower_gen_walk
 	std::vector<NodeOp> walk_lower_ops, walk_upper_ops;  // depth-first op orders
@@ -61,7 +57,7 @@ struct Shard {
 	int walk_upper_slots = 0;
 	std::vector<NodeOp> walk_chunk_ops;  // chunked form of walk_upper_ops (build_walk_chunks)
 	std::vector<int> walk_chunk_off;     // chunk offsets into walk_chunk_ops: [0] top part, then one per cut subtree
-	int walk_chunk_slots = 0, walk_chunks = 3;  // PHYAMD_WALK_CHUNKS (1: one chunk; 3 measured best once a re-read beside a cut subtree cost the post-order pass its write rate)
+	int walk_chunk_slots = 0;
 	std::vector<NodeOp> walk_lower_chunk_ops;  // chunked form of walk_lower_ops: cut subtrees, then the top part
 	std::vector<int> walk_lower_chunk_off;
 	NodeOp *d_walk_lower_chunk_ops = nullptr;
@@ -69,7 +65,7 @@ struct Shard {
 	NodeOp *d_walk_chunk_ops = nullptr;
 	int *d_walk_chunk_off = nullptr;
 	// streamed pre-order walk (phyamd_walk4s.inc): flattened ops of the chunked list, mask words in walk order, walk-order slab
-	bool stream_walk = true;             // PHYAMD_WALK_STREAM = 0: k_upper4_walk
+	bool stream_walk = true;             // false (tiling ENOMEM, T >= 2^20): k_upper4_walk
 	int xcd_map = 1;                     // PHYAMD_XCD_MAP = 0: streamed walks with consecutive workgroup ids per block group (A/B; see xcd_position)
 	std::vector<StreamOp> stream_ops;    // one per op of walk_chunk_ops
 	std::vector<StreamDesc> stream_desc; // ... as the kernel reads them (byte offsets multiplied out for stream_P patterns, stream_mstride)
@@ -80,7 +76,7 @@ struct Shard {
 	std::vector<LowerChunk> lstream_chunks;
 	LowerDesc *d_lstream_ops = nullptr;
 	LowerChunk *d_lstream_chunks = nullptr;
-	bool lstream_on = true;              // PHYAMD_LOWER_STREAM = 0: k_lower4_walk
+	bool lstream_on = true;              // false (tiling ENOMEM): k_lower4_walk
 	std::vector<int> stream_row_entries; // [rows][8] nibbles of the packed mask words (MaskPacker): the pre-order walk's rows, then the post-order walk's
 	std::vector<int> stream_site_tab;    // [ops][16] byte offset of each result lane's branch in a slab row (-1: none)
 	std::vector<int> stream_qnode;       // slab position -> node
@@ -148,7 +144,6 @@ struct Shard {
 	std::vector<int32_t> core_index;  // node -> index of its stored lower array (-1: tip or fused)
 	int core_count = 0;
 	bool fusion_enabled = true, fused = false;
-	bool deep_enabled = true;          // PHYAMD_DEEP = 0: every node above the fringe is stored
 	std::vector<DeepDesc> deep_host;   // by node id (only DEEP nodes filled)
 	int deep_count = 0;
 	// (device copy: behind the tip-message table, see Ctx4::deep)

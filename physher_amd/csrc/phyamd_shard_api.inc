@@ -64,11 +64,9 @@ int allocate_pattern_storage(Shard *e) {
 	e->nblk_lower = (e->P + WAVE * e->G * PPT_LOWER - 1) / (WAVE * e->G * PPT_LOWER);  // post-order kernel / lnL slab
 	{
 		// Tree-walk geometry.  The pre-order walk always takes one pattern per thread (see k_upper4_walk); the plain post-order walk
-		// one or two, by shard size (launch_lower_walk; PHYAMD_PPT_WALK_LOWER = 1 / 2 pins it for A/B runs), the rescaled one one.
+		// one or two, chosen per launch by shard size (launch_lower_walk), the rescaled one one.
 		const int groups = (e->P + WAVE * e->G - 1) / (WAVE * e->G);  // workgroups at one pattern per thread
-		e->ppt_walk_lower = 0;  // 0 = chosen per launch from the shard size (launch_lower_walk)
 		e->lower_walk_slots[0] = e->lower_walk_slots[1] = 0;
-		if (const char *env = std::getenv("PHYAMD_PPT_WALK_LOWER")) e->ppt_walk_lower = std::atoi(env) == 1 ? 1 : 2;
 		e->nblk_walk = groups;
 		e->nblk_walk_upper = groups;
 	}
@@ -178,20 +176,11 @@ int shard_create(const phyamd_config *cfg, Shard **out) {
 	}
 	e->scaling_on = cfg->rescale == PHYAMD_RESCALE_ALWAYS;
 	if (const char *env = std::getenv("PHYAMD_FUSE")) e->fusion_enabled = std::atoi(env) != 0;  // A/B switch for the fringe fusion
-	if (const char *env = std::getenv("PHYAMD_DEEP")) e->deep_enabled = std::atoi(env) != 0;
 	if (const char *env = std::getenv("PHYAMD_WALK")) e->walk_enabled = std::atoi(env) != 0;
-	if (const char *env = std::getenv("PHYAMD_WALK_LOWER")) e->walk_lower_on = std::atoi(env) != 0;
-	if (const char *env = std::getenv("PHYAMD_WALK_UPPER")) e->walk_upper_on = std::atoi(env) != 0;
-	if (const char *env = std::getenv("PHYAMD_WALK_PARAMS")) e->walk_params_on = std::atoi(env) != 0;
-	if (const char *env = std::getenv("PHYAMD_LDS_PARK")) e->lds_park_on = std::atoi(env) != 0;
 	if (const char *env = std::getenv("PHYAMD_GEN_FUSION")) e->generic_fusion = std::atoi(env) != 0;
-	if (const char *env = std::getenv("PHYAMD_GEN_WALK")) e->gen_walk_on = std::atoi(env) != 0;
-	if (const char *env = std::getenv("PHYAMD_LOWER_STREAM")) e->lstream_on = std::atoi(env) != 0;
-	if (const char *env = std::getenv("PHYAMD_WALK_STREAM")) e->stream_walk = std::atoi(env) != 0;
 	if (const char *env = std::getenv("PHYAMD_XCD_MAP")) e->xcd_map = std::atoi(env) != 0;
 	if (const char *env = std::getenv("PHYAMD_SCALE_EXP2")) e->exp2_on = std::atoi(env) != 0;
 	if (const char *env = std::getenv("PHYAMD_STREAM_TFORM")) e->tform_on = std::atoi(env) != 0;
-	if (const char *env = std::getenv("PHYAMD_WALK_CHUNKS")) e->walk_chunks = std::max(1, std::atoi(env));
 	e->generic = e->S != 4;
 	e->tip_set.assign(e->T, 0);
 	e->explicit_host.assign(e->N, 0);

@@ -58,20 +58,9 @@ __device__ __forceinline__ d4 child_message_hoisted(const Ctx4 &x, int kind, int
 	return half_message(x, kind, node, t0, t1, t2, inner, m);
 }
 
-#ifndef PHYAMD_LOWER_SETPRIO
-#define PHYAMD_LOWER_SETPRIO 1
-#endif
-#ifndef PHYAMD_LOWER_MIN_WAVES
-#define PHYAMD_LOWER_MIN_WAVES 7  // waves per SIMD asked of the plain one-pattern-per-thread walk (67 VGPRs): 6 -> 12.97, 7 -> 12.55, 8 (4 spilled) -> 13.25 ms
-#endif
-#ifndef PHYAMD_LOWER_HOIST
-#define PHYAMD_LOWER_HOIST 1  // A/B: 0 = mask bytes loaded where the nested child messages use them
-#endif
-#ifndef PHYAMD_LOWER_VALU_TIPS
-#define PHYAMD_LOWER_VALU_TIPS 1  // A/B: 0 = gather tip messages from the tables
-#endif
-template <int WAVES, int PPT_WALK, bool SCALE, bool LPARK = false>
-__global__ __launch_bounds__(WAVES *WAVE, (WAVES == 4 && PPT_WALK == 1 && !SCALE) ? PHYAMD_LOWER_MIN_WAVES : 1) void k_lower4_walk(const NodeOp *__restrict__ ops, int nops, int T, int P, int C,
+constexpr int LOWER_MIN_WAVES = 7;  // waves per SIMD asked of the plain one-pattern-per-thread walk (67 VGPRs): 6 -> 12.97, 7 -> 12.55, 8 (4 spilled) -> 13.25 ms
+template <int WAVES, int PPT_WALK, bool SCALE>
+__global__ __launch_bounds__(WAVES *WAVE, (WAVES == 4 && PPT_WALK == 1 && !SCALE) ? LOWER_MIN_WAVES : 1) void k_lower4_walk(const NodeOp *__restrict__ ops, int nops, int T, int P, int C,
                                                              const uint8_t *__restrict__ tipmask, double *__restrict__ lower,
                                                              const double *__restrict__ mats, const double *__restrict__ tiptab,
                                                              double *__restrict__ lscale,
@@ -108,32 +97,28 @@ __global__ __launch_bounds__(WAVES *WAVE, (WAVES == 4 && PPT_WALK == 1 && !SCALE
 	for (int i = op_begin; i < op_end; i++) {
 		const NodeOp *op = ops + i;  // wave-uniform: scalar loads
 		const int cin = op->carry_in;
-		const int lp = LPARK ? op->lds_park : 0;
+		const int lp = op->lds_park;
 		double *dst = lower + ((size_t)op->core_parent * C + c) * plane;
 #pragma unroll
 		for (int q = 0; q < PPT_WALK; q++) {
-			const Ctx4 x{tipmask, mats, tiptab, P, C, c, kq[q], T, PHYAMD_LOWER_VALU_TIPS != 0};
+			const Ctx4 x{tipmask, mats, tiptab, P, C, c, kq[q], T, true};
 			d4 a, b;
-			if (LPARK && (lp & 3)) {  // both children stored: one carried, the other from the LDS slot
+			if (lp & 3) {  // both children stored: one carried, the other from the LDS slot
 				const dv2 lo = park[q * 2 * WAVE], hi = park[(q * 2 + 1) * WAVE];
 				const d4 parked = d4{lo.x, lo.y, hi.x, hi.y};
 				a = matvec4(x.M(op->left), (lp & 1) ? parked : carry[q]);
 				b = matvec4(x.M(op->right), (lp & 2) ? parked : carry[q]);
-			} else if (!PHYAMD_LOWER_HOIST || SCALE) {  // (the rescaled walk measures 5 ms slower with the hoisted form: 21.2 vs 16.3)
+			} else if (SCALE) {  // (the rescaled walk measures 5 ms slower with the hoisted form: 21.2 vs 16.3)
 				a = cin == 1 ? matvec4(x.M(op->left), carry[q])
 				             : child_message(x, op->kind_left, op->left, op->core_left, op->lt0, op->lt1, op->lt2, op->linner, lower, plane);
 				b = cin == 2 ? matvec4(x.M(op->right), carry[q])
 				             : child_message(x, op->kind_right, op->right, op->core_right, op->rt0, op->rt1, op->rt2, op->rinner, lower, plane);
 			} else {
 				unsigned ml[6] = {0, 0, 0, 0, 0, 0}, mr[6] = {0, 0, 0, 0, 0, 0};
-#if PHYAMD_LOWER_SETPRIO
 				__builtin_amdgcn_s_setprio(3);
-#endif
 				if (cin != 1) load_child_masks(x, op->kind_left, op->left, op->lt0, op->lt1, op->lt2, ml);
 				if (cin != 2) load_child_masks(x, op->kind_right, op->right, op->rt0, op->rt1, op->rt2, mr);
-#if PHYAMD_LOWER_SETPRIO
 				__builtin_amdgcn_s_setprio(0);
-#endif
 				a = cin == 1 ? matvec4(x.M(op->left), carry[q])
 				             : child_message_hoisted(x, op->kind_left, op->left, op->core_left, op->lt0, op->lt1, op->lt2, op->linner, lower, plane, ml);
 				b = cin == 2 ? matvec4(x.M(op->right), carry[q])
@@ -156,8 +141,8 @@ __global__ __launch_bounds__(WAVES *WAVE, (WAVES == 4 && PPT_WALK == 1 && !SCALE
 				if (c == 0 && vq[q]) lscale[(size_t)op->core_parent * P + kq[q]] = sf;
 				sfc[q] = sf;
 			}
-			if (vq[q] && !(op->lds_park & 8)) store4_stream(dst + (size_t)kq[q] * 4, out);  // (bit 3: PHYAMD_ABL_LOWER, timing only)
-			if (LPARK && (lp & 4)) {
+			if (vq[q] && !(op->lds_park & 8)) store4_stream(dst + (size_t)kq[q] * 4, out);  // (bit 3: no longer set by the host)
+			if (lp & 4) {
 				park[q * 2 * WAVE] = dv2{out.x, out.y};
 				park[(q * 2 + 1) * WAVE] = dv2{out.z, out.w};
 			}
@@ -216,9 +201,6 @@ struct GradWT {
 	double w, d;  // SCALE + COMPAT: the reference divides each category's term by that category's own likelihood, which underflows
 	              // to denormals where the ratio is still finite -- quotient first there
 	__device__ __forceinline__ void add(int i, const d4 &u, const d4 &b) const {
-#ifdef PHYAMD_ABL_NOSITES
-		return;
-#endif
 		const double num = dot4(u, matvec4_opt<FENCE>(opaque(Q), b));
 		col[i * WCOL] = SCALE ? (COMPAT ? w * (num / d) : wq * num) : wl * num;
 	}
@@ -262,21 +244,8 @@ struct GradWT {
 
 // Variants for the pre-order tree walk: the mask bytes of an op's (up to six) tips are all requested at the top of the op,
 // together with the parent's upper, so the op pays one memory round trip for them instead of one per child.
-#ifdef PHYAMD_ABL_NOTIP
-__device__ __forceinline__ d4 tip_gather(const Ctx4 &x, int t, unsigned m) { return d4{0.3, 0.2, 0.1, 0.4}; }
-#else
 __device__ __forceinline__ d4 tip_gather(const Ctx4 &x, int t, unsigned m) { return load4(x.tiptab + (((size_t)t * x.C + x.c) * 16 + m) * 4); }
-#endif
 // `pre` receives the child's own partial (what the parameter gradient contracts): untouched for tips
-#ifndef PHYAMD_UPPER_SETPRIO
-#define PHYAMD_UPPER_SETPRIO 1
-#endif
-#ifndef PHYAMD_UPPER_GATHER_EARLY
-#define PHYAMD_UPPER_GATHER_EARLY 1
-#endif
-#ifndef PHYAMD_UPPER_DEEP_HOIST
-#define PHYAMD_UPPER_DEEP_HOIST 1  // A/B: 0 = a DEEP child's mask bytes are loaded one by one inside deep_partial
-#endif
 // P_half . p_half of one half of a DEEP node (a tip, a cherry or a cherry + tip), masks in m[0..2], messages from the tables
 template <bool FENCE>
 __device__ __forceinline__ d4 deep_half_m(const Ctx4 &x, int kind, int node, int t0, int t1, int t2, int inner, const unsigned *m) {
@@ -291,23 +260,15 @@ __device__ __forceinline__ d4 child_message_m(const Ctx4 &x, int kind, int node,
 	if (kind == CH_TIP) return tip_gather(x, node, m0);
 	if (kind == CH_CORE) pre = pcore;
 	else if (kind == CH_DEEP) {
-		if (PHYAMD_UPPER_DEEP_HOIST) {
-			const DeepDesc *d = x.deep(node);  // wave-uniform: scalar loads
-			pre = mul4(deep_half_m<FENCE>(x, d->kind_left, d->left, d->lt0, d->lt1, d->lt2, d->linner, dm),
-			           deep_half_m<FENCE>(x, d->kind_right, d->right, d->rt0, d->rt1, d->rt2, d->rinner, dm + 3));
-		} else
-			pre = deep_partial(x, node);
+		const DeepDesc *d = x.deep(node);  // wave-uniform: scalar loads
+		pre = mul4(deep_half_m<FENCE>(x, d->kind_left, d->left, d->lt0, d->lt1, d->lt2, d->linner, dm),
+		           deep_half_m<FENCE>(x, d->kind_right, d->right, d->rt0, d->rt1, d->rt2, d->rinner, dm + 3));
 	} else {
-#if PHYAMD_UPPER_GATHER_EARLY
 		const d4 g0 = tip_gather(x, t0, m0), g1 = tip_gather(x, t1, m1);
 		d4 g2 = d4{1., 1., 1., 1.};
 		if (kind == CH_CHERRY_TIP) g2 = tip_gather(x, t2, m2);  // requested with the other two, not behind the inner mat-vec
 		pre = mul4(g0, g1);                                                                          // cherry
 		if (kind == CH_CHERRY_TIP) pre = mul4(matvec4_opt<FENCE>(x.M(inner), pre), g2);              // cherry + tip
-#else
-		pre = mul4(tip_gather(x, t0, m0), tip_gather(x, t1, m1));                                    // cherry
-		if (kind == CH_CHERRY_TIP) pre = mul4(matvec4_opt<FENCE>(x.M(inner), pre), tip_gather(x, t2, m2));   // cherry + tip
-#endif
 	}
 	return matvec4_opt<FENCE>(x.M(node), pre);
 }
@@ -315,19 +276,13 @@ template <typename GradT>
 __device__ __forceinline__ void descend_fringe_m(const Ctx4 &x, const GradT &gr, int base, int kind, int node, int t0, int t1, int t2, int inner,
                                                  const d4 &u, unsigned m0, unsigned m1, unsigned m2) {
 	const d4 b0 = tip_gather(x, t0, m0), b1 = tip_gather(x, t1, m1);
-#if PHYAMD_UPPER_GATHER_EARLY
 	d4 b2e = d4{1., 1., 1., 1.};
 	if (kind == CH_CHERRY_TIP) b2e = tip_gather(x, t2, m2);
-#endif
 	d4 a2 = matvec4_opt<GradT::FENCE>(x.M(node), u);
 	if (kind == CH_CHERRY_TIP) {
 		const d4 pn = mul4(b0, b1);
 		const d4 bn = matvec4_opt<GradT::FENCE>(x.M(inner), pn);
-#if PHYAMD_UPPER_GATHER_EARLY
 		const d4 b2 = b2e;
-#else
-		const d4 b2 = tip_gather(x, t2, m2);
-#endif
 		const d4 un = mul4(a2, b2);
 		gr.site_vec(x, base + 2, inner, un, bn, pn);
 		gr.site_tip(x, base + 3, t2, mul4(a2, bn), b2, m2);
@@ -367,24 +322,20 @@ __device__ __forceinline__ double wave_sum16(const double (&v)[16], int lane) {
 // patterns per thread, carried uppers in LDS and accumulators in registers (126 VGPRs, 4 waves) measured 14 % slower.
 // dynamic LDS: [waves][NACC][WCOL] doubles
 // ------------------------------------------------------------------------------------------------
-#ifndef PHYAMD_WALK_UPPER_MIN_WAVES
-#define PHYAMD_WALK_UPPER_MIN_WAVES 5
-#endif
-#ifndef PHYAMD_WALK_UPPER_SCALE_WAVES
-#define PHYAMD_WALK_UPPER_SCALE_WAVES 4  // 5 spills (4-16 VGPRs) and needs the LDS park slots gone to fit: 41.0 vs 42.7 ms, not taken
-#endif
+constexpr int WALK_UPPER_MIN_WAVES = 5;
+constexpr int WALK_UPPER_SCALE_WAVES = 4;  // 5 spills (4-16 VGPRs) and needs the LDS park slots gone to fit: 41.0 vs 42.7 ms, not taken
 // PARAMS: dynamic LDS holds 16 columns per wave (the eigen-basis sums are reduced once, after the walk); pbuf = [UTpi(16) |
 // Uinv(16) | utab(64)], Fw as in ParamCtx, gacc [16][nblk] receives the per-wave sums.
 // SCALE / COMPAT: rescaled evaluations (see k_upper4): one LDS exchange per op gives every category's wave the mixture
 // denominator D_k and the maxima of the two new uppers; dynamic LDS grows by 4 * waves * 64 doubles (double-buffered).
-// LPARK (plain kernel): leaf parks (NodeOp::lds_park) wait in a per-wave LDS slot of 64 x 32 bytes behind the columns instead of
-// HBM: at 1000 taxa 94 of the 140 parked uppers, i.e. 24 of the 91 GB the walk moves, and their re-reads cost an LDS round trip
-// instead of an HBM one.
+// LPARK (every launch but the parameter walk, LPARK = !PARAMS): leaf parks (NodeOp::lds_park) wait in a per-wave LDS slot of 64 x
+// 32 bytes behind the columns instead of HBM: at 1000 taxa 94 of the 140 parked uppers, i.e. 24 of the 91 GB the walk moves, and
+// their re-reads cost an LDS round trip instead of an HBM one.
 // CATBLK (unscaled launches only): the workgroup's waves are blockDim.z pattern groups of ONE category, blockIdx.x = group block * C +
 // category -- the waves share matrices and tables in the scalar cache (the parameter sums load three 4 x 4 matrices and twenty
 // doubles per branch: with one category per wave a fifth of those scalar loads missed)
-template <int WAVES, bool FOLD, bool PARAMS, bool SCALE, bool COMPAT, bool LPARK = false, bool CATBLK = false>
-__global__ __launch_bounds__(WAVES *WAVE, WAVES == 4 ? (PARAMS ? 3 : (SCALE ? PHYAMD_WALK_UPPER_SCALE_WAVES : PHYAMD_WALK_UPPER_MIN_WAVES)) : 1) void k_upper4_walk(const NodeOp *__restrict__ ops, int nops, int T, int P, int C,
+template <int WAVES, bool FOLD, bool PARAMS, bool SCALE, bool COMPAT, bool CATBLK = false>
+__global__ __launch_bounds__(WAVES *WAVE, WAVES == 4 ? (PARAMS ? 3 : (SCALE ? WALK_UPPER_SCALE_WAVES : WALK_UPPER_MIN_WAVES)) : 1) void k_upper4_walk(const NodeOp *__restrict__ ops, int nops, int T, int P, int C,
                                                               const uint8_t *__restrict__ tipmask, const double *__restrict__ lower,
                                                               double *__restrict__ upper, const double *__restrict__ mats,
                                                               const double *__restrict__ tiptab, const double *__restrict__ Q,
@@ -395,6 +346,7 @@ __global__ __launch_bounds__(WAVES *WAVE, WAVES == 4 ? (PARAMS ? 3 : (SCALE ? PH
                                                               const int *__restrict__ chunk_off, int chunk_base) {
 	extern __shared__ double sh[];
 	constexpr int NCOL = PARAMS ? 16 : NACC;
+	constexpr bool LPARK = !PARAMS;  // (the parameter walk runs on the unchunked list, whose parks all have HBM slots)
 	static_assert(!(CATBLK && SCALE), "rescaled launches exchange across the categories of a workgroup");
 	const int lane = threadIdx.x, g = __builtin_amdgcn_readfirstlane(threadIdx.z), G = blockDim.z;
 	const int c = CATBLK ? (int)(blockIdx.x % C) : __builtin_amdgcn_readfirstlane(threadIdx.y), bx = CATBLK ? (int)(blockIdx.x / C) : (int)blockIdx.x;
@@ -432,14 +384,11 @@ __global__ __launch_bounds__(WAVES *WAVE, WAVES == 4 ? (PARAMS ? 3 : (SCALE ? PH
 		GradWT<PARAMS, SCALE, COMPAT> gr{as_const(Q), wl, col, pc, Gab, 0.0, 0.0, 1.0};  // Q is diag(pi) Q unless FOLD
 		// every tip mask byte of the op up front: all in flight together (a DEEP child's four to six bytes too: they are used
 		// once, for its message, at the top of the op)
-#if PHYAMD_UPPER_SETPRIO
 		__builtin_amdgcn_s_setprio(3);  // a wave about to request its operands goes first: the sooner they leave, the shorter its chain
-#endif
 		unsigned ml0 = 0, ml1 = 0, ml2 = 0, mr0 = 0, mr1 = 0, mr2 = 0;
 		unsigned dl[6] = {0, 0, 0, 0, 0, 0}, dr[6] = {0, 0, 0, 0, 0, 0};
-#ifndef PHYAMD_ABL_NOTIP
-		if (PHYAMD_UPPER_DEEP_HOIST && kl == CH_DEEP) load_child_masks(x, kl, op->left, -1, -1, -1, dl);
-		if (PHYAMD_UPPER_DEEP_HOIST && kr == CH_DEEP) load_child_masks(x, kr, op->right, -1, -1, -1, dr);
+		if (kl == CH_DEEP) load_child_masks(x, kl, op->left, -1, -1, -1, dl);
+		if (kr == CH_DEEP) load_child_masks(x, kr, op->right, -1, -1, -1, dr);
 		if (kl == CH_TIP) ml0 = tipmask[(size_t)op->left * P + k];
 		else if (kl >= CH_CHERRY) {
 			ml0 = tipmask[(size_t)op->lt0 * P + k];
@@ -452,11 +401,7 @@ __global__ __launch_bounds__(WAVES *WAVE, WAVES == 4 ? (PARAMS ? 3 : (SCALE ? PH
 			mr1 = tipmask[(size_t)op->rt1 * P + k];
 			if (kr == CH_CHERRY_TIP) mr2 = tipmask[(size_t)op->rt2 * P + k];
 		}
-#endif
 		d4 uin = carry;  // the parent's upper: carried in registers, or parked by an earlier op of this thread
-#ifdef PHYAMD_ABL_NOCORE
-		d4 pl = d4{0.1, 0.2, 0.3, 0.4}, pr = d4{0.4, 0.3, 0.2, 0.1};
-#else
 		if (!proot && !cin) {
 			if (LPARK && (op->lds_park & 1)) {
 				const dv2 lo = park[0], hi = park[WAVE];
@@ -467,19 +412,13 @@ __global__ __launch_bounds__(WAVES *WAVE, WAVES == 4 ? (PARAMS ? 3 : (SCALE ? PH
 		d4 pl = one, pr = one;  // stored children
 		if (kl == CH_CORE) pl = load4_stream(lower + ((size_t)op->core_left * C + c) * plane + (size_t)k * 4);
 		if (kr == CH_CORE) pr = load4_stream(lower + ((size_t)op->core_right * C + c) * plane + (size_t)k * 4);
-#endif
-#if PHYAMD_UPPER_SETPRIO == 1 || PHYAMD_UPPER_SETPRIO == 3
 		__builtin_amdgcn_s_setprio(0);
-#endif
 		d4 prel = one, prer = one;  // the children's own partials (the parameter gradient contracts them)
 		const d4 bl = child_message_m<PARAMS>(x, kl, op->left, op->core_left, op->lt0, op->lt1, op->lt2, op->linner, pl, ml0, ml1, ml2, prel, dl);
 		const d4 br = child_message_m<PARAMS>(x, kr, op->right, op->core_right, op->rt0, op->rt1, op->rt2, op->rinner, pr, mr0, mr1, mr2, prer, dr);
 		d4 a;
 		if (proot) a = FOLD ? pi : one;
 		else a = matvec4_opt<PARAMS>(x.M(op->parent), uin);
-#if PHYAMD_UPPER_SETPRIO == 2
-		__builtin_amdgcn_s_setprio(0);
-#endif
 		d4 ul = mul4(a, br), ur = mul4(a, bl);
 		double ml = 1.0, mr = 1.0;
 		if (SCALE) {
@@ -521,7 +460,6 @@ __global__ __launch_bounds__(WAVES *WAVE, WAVES == 4 ? (PARAMS ? 3 : (SCALE ? PH
 			if (ml < SCALING_THRESHOLD) ul = d4{ul.x / ml, ul.y / ml, ul.z / ml, ul.w / ml};
 			if (mr < SCALING_THRESHOLD) ur = d4{ur.x / mr, ur.y / mr, ur.z / mr, ur.w / mr};
 		}
-#ifndef PHYAMD_ABL_NOSTORE
 		if (LPARK && (op->lds_park & 6)) {
 			const d4 &v = (op->lds_park & 2) ? ul : ur;
 			park[0] = dv2{v.x, v.y};
@@ -532,30 +470,16 @@ __global__ __launch_bounds__(WAVES *WAVE, WAVES == 4 ? (PARAMS ? 3 : (SCALE ? PH
 		// lane writes measured 2.5 ms slower here (it pays in the post-order walk, whose partials are read a whole pass later)
 		if (op->upper_slot_left >= 0 && valid) store4(upper + ((size_t)op->upper_slot_left * C + c) * plane + (size_t)k * 4, ul);
 		if (op->upper_slot_right >= 0 && valid) store4(upper + ((size_t)op->upper_slot_right * C + c) * plane + (size_t)k * 4, ur);
-#endif
 		carry = cout == 1 ? ul : ur;
-#if defined(PHYAMD_ABL_NORED) || defined(PHYAMD_ABL_NOSITES)
-		continue;
-#endif
-#if PHYAMD_UPPER_SETPRIO == 3
-		__builtin_amdgcn_s_setprio(3);  // from the column sums through the next op's requests
-#endif
 		// Fixed-order sum of each column over the wave's 64 patterns: four lanes per column add 16 entries each in order,
 		// then (s0 + s1) + (s2 + s3).  Slots an op did not write hold stale values; their rows are never stored.
 		__builtin_amdgcn_wave_barrier();
 		double tot = 0.0;
 		if (my < NACC) {
-#if PHYAMD_RED_STRIDED
 			const double *src = wave_cols + my * WCOL + seg;
 			tot = src[0];
 #pragma unroll
 			for (int j = 1; j < 16; j++) tot += src[4 * j];
-#else
-			const double *src = wave_cols + my * WCOL + seg * 16;
-			tot = src[0];
-#pragma unroll
-			for (int j = 1; j < 16; j++) tot += src[j];
-#endif
 		}
 		tot = quad_swap_add<0xB1>(tot);  // s0 + s1 | s2 + s3
 		tot = quad_swap_add<0x4E>(tot);  // (s0 + s1) + (s2 + s3)
@@ -581,17 +505,10 @@ __global__ __launch_bounds__(WAVES *WAVE, WAVES == 4 ? (PARAMS ? 3 : (SCALE ? PH
 #pragma unroll
 		for (int a = 0; a < 16; a++) col[a * WCOL] = Gab[a];
 		__builtin_amdgcn_wave_barrier();
-#if PHYAMD_RED_STRIDED
 		const double *src = wave_cols + my * WCOL + seg;
 		double tot = src[0];
 #pragma unroll
 		for (int j = 1; j < 16; j++) tot += src[4 * j];
-#else
-		const double *src = wave_cols + my * WCOL + seg * 16;
-		double tot = src[0];
-#pragma unroll
-		for (int j = 1; j < 16; j++) tot += src[j];
-#endif
 		tot += __shfl_xor(tot, 1, 64);
 		tot += __shfl_xor(tot, 2, 64);
 		if (seg == 0) gacc[(size_t)my * nblk * C + slab * C + c] = tot;

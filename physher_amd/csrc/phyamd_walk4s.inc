@@ -335,12 +335,8 @@ __device__ __forceinline__ int exp2_rescale(d4 &v) {
 	return e;
 }
 
-#ifndef PHYAMD_STREAM_MIN_WAVES
-#define PHYAMD_STREAM_MIN_WAVES 4  // waves per SIMD the kernel is compiled for (<= 128 registers)
-#endif
-#ifndef PHYAMD_STREAM_MIN_WAVES_SCALE
-#define PHYAMD_STREAM_MIN_WAVES_SCALE 3  // ... its rescaled / ambiguity-code instantiations (<= 168 registers, so that nothing is spilled)
-#endif
+constexpr int STREAM_MIN_WAVES = 4;        // waves per SIMD the kernel is compiled for (<= 128 registers)
+constexpr int STREAM_MIN_WAVES_SCALE = 3;  // ... its rescaled / ambiguity-code instantiations (<= 168 registers, so that nothing is spilled)
 
 // one 1 KB piece of a table block: global -> LDS with no register in between (global_load_lds_dwordx4: LDS address = uniform base +
 // 16 * lane, source address per lane); completion is counted on vmcnt like any vector load
@@ -353,8 +349,8 @@ __device__ __forceinline__ void dma_piece(const char *gsrc, lds_cptr dst) {
 // load it tracks drew a conservative s_waitcnt vmcnt(0) behind the requests (the op waits once, explicitly, at its top).
 // The results are consumed only behind that wait -- and must not be MOVED before it either: the compiler takes them for defined
 // when the statement ends, so a spill of A / B / U across the loop edge would save registers the load has not written yet.  Every
-// instantiation is therefore compiled for an occupancy at which nothing is spilled (PHYAMD_STREAM_MIN_WAVES,
-// PHYAMD_STREAM_MIN_WAVES_SCALE; tests/test_kernel_resources.py pins the spill counts to zero).
+// instantiation is therefore compiled for an occupancy at which nothing is spilled (STREAM_MIN_WAVES,
+// STREAM_MIN_WAVES_SCALE; tests/test_kernel_resources.py pins the spill counts to zero).
 typedef double dv4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ d4 prefetch4(const char *base, unsigned lane_off, bool nt) {
 	dv2 lo, hi;
@@ -371,11 +367,8 @@ __device__ __forceinline__ unsigned prefetch1(const char *base, unsigned lane_of
 // dynamic LDS per wave: STREAM_PARK_SLOTS park slots of [2][64] x 16 bytes, then two table blocks (this op's and the next op's).
 // Slot 0 holds leaf parks (nothing else is parked while they wait), slot 1 parks whose wait holds leaf parks only -- an upper parked
 // in HBM is written and read back (7.4 GB per evaluation at the headline shape with one slot), and without those stores the pass is
-// 1.4 ms shorter (PHYAMD_ABL_STREAM=8).  8 KB per wave: four workgroups per CU use 128 KB of the 160.
-#ifndef PHYAMD_STREAM_PARK_SLOTS
-#define PHYAMD_STREAM_PARK_SLOTS 2
-#endif
-constexpr int STREAM_PARK_SLOTS = PHYAMD_STREAM_PARK_SLOTS, STREAM_PARK_BYTES = 2 * WAVE * 16;
+// 1.4 ms shorter (a timing-only ablation, since retired).  8 KB per wave: four workgroups per CU use 128 KB of the 160.
+constexpr int STREAM_PARK_SLOTS = 2, STREAM_PARK_BYTES = 2 * WAVE * 16;
 constexpr int STREAM_LDS_PER_WAVE = STREAM_PARK_SLOTS * STREAM_PARK_BYTES + 2 * OPBLK_BYTES;
 
 // Workgroup = STREAM_WAVES waves = that many consecutive blocks of 64 patterns of ONE category (blockIdx.x = block group * C + category):
@@ -423,7 +416,7 @@ __device__ __forceinline__ d4 own_registers(const d4 &v) {
 // TF: the stored children arrive as t = P p (the streamed post-order walk's TF variant stored them so: k_lower4_stream) -- a CORE
 // child's message is the stored array itself, sixteen multiply-adds and a matrix fewer per such child.
 template <bool FOLD, int SCALE, bool AMBIG = false, bool TF = false>
-__global__ __launch_bounds__(STREAM_WAVES *WAVE, (SCALE || AMBIG) ? PHYAMD_STREAM_MIN_WAVES_SCALE : PHYAMD_STREAM_MIN_WAVES) void k_upper4_stream(
+__global__ __launch_bounds__(STREAM_WAVES *WAVE, (SCALE || AMBIG) ? STREAM_MIN_WAVES_SCALE : STREAM_MIN_WAVES) void k_upper4_stream(
     const StreamDesc *__restrict__ ops, const StreamChunk *__restrict__ chunks, const int *__restrict__ chunk_off, int chunk_base, int nops, int P, int C, int nb,
     const uint32_t *__restrict__ mstream, size_t mstride, const double *__restrict__ lower, double *__restrict__ upper, const double *__restrict__ mats,
     const char *__restrict__ optab, const double *__restrict__ Q, const double *__restrict__ freqs, const double *__restrict__ w_over_L,
@@ -688,7 +681,7 @@ __global__ __launch_bounds__(STREAM_WAVES *WAVE, (SCALE || AMBIG) ? PHYAMD_STREA
 // cache and L2), no workgroup-level synchronisation; the root's sum over categories is k_root_finish64's.
 struct LowerDesc {
 	int32_t flags;     // kl 0-2 | kr 3-5 | where a stored left child comes from 6-7 (0: memory, 1: the previous op's result, 2: the parked
-	                   // partial) | same for the right child 8-9 | 10: park the result | 11: no store (PHYAMD_ABL_LOWER) | 12-13: ring slot of
+	                   // partial) | same for the right child 8-9 | 10: park the result | 11: no store (no longer set) | 12-13: ring slot of
 	                   // the first mask row to request for the NEXT op | 14-15: how many rows to request for it (0..2: the rows it reads that
 	                   // no op before it has read) | half kinds 16-23 | 24 / 25: the next op's block needs its second / first piece
 	int32_t nx_block;  // table block of the next op
@@ -707,9 +700,7 @@ struct LowerChunk {  // what the first op of a chunk wants requested before the 
 	int64_t words;
 };
 
-#ifndef PHYAMD_LSTREAM_MIN_WAVES
-#define PHYAMD_LSTREAM_MIN_WAVES 5  // (29 KB of LDS per workgroup allow five workgroups per CU: 96 registers)
-#endif
+constexpr int LSTREAM_MIN_WAVES = 5;  // (29 KB of LDS per workgroup allow five workgroups per CU: 96 registers)
 constexpr int LSTREAM_LDS_PER_WAVE = 2 * OPBLK_BYTES + 5 * WAVE * 4 + WAVE * 32;  // two table blocks, a ring of four mask rows + a scratch row, the store staging area
 
 __device__ __forceinline__ void dma_dword(const char *gsrc, lds_cptr dst) {  // one dword per lane -> LDS base + 4 * lane
@@ -728,7 +719,7 @@ __device__ __forceinline__ void dma_dword(const char *gsrc, lds_cptr dst) {  // 
 // convention BETWEEN the two streamed walks (Shard::stored_tform): every other reader of stored partials gets p_n back
 // (ensure_compat_state: the pass runs again without TF and stays so).  Never with SCALE == 1, which IS the reference's convention.
 template <bool AMBIG, int SCALE, bool TF = false>  // SCALE: 0 plain, 1 the reference's rescaling (exchange), 2 powers of two per category (lscale = int exponents [stored][C][P])
-__global__ __launch_bounds__(STREAM_WAVES *WAVE, SCALE == 1 ? 4 : PHYAMD_LSTREAM_MIN_WAVES) void k_lower4_stream(
+__global__ __launch_bounds__(STREAM_WAVES *WAVE, SCALE == 1 ? 4 : LSTREAM_MIN_WAVES) void k_lower4_stream(
     const LowerDesc *__restrict__ ops, const LowerChunk *__restrict__ chunks, const int *__restrict__ chunk_off, int chunk_base, int nblocks, int P, int C, int nb,
     const uint32_t *__restrict__ mstream, size_t mstride, double *__restrict__ lower, const double *__restrict__ mats, const char *__restrict__ optab,
     const double *__restrict__ freqs, const double *__restrict__ props, double *__restrict__ Lc, int with_root, double *__restrict__ lscale, int xcd_map,
@@ -884,7 +875,7 @@ __global__ __launch_bounds__(STREAM_WAVES *WAVE, SCALE == 1 ? 4 : PHYAMD_LSTREAM
 			sfp = sfc;
 			efp = efc;
 		}
-		have_prev = !(fl & (1 << 11));
+		have_prev = !(fl & (1 << 11));  // (the host no longer sets bit 11)
 		prev_store = op.store;
 		prev_ls = op.ls_store;
 	}

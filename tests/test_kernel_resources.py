@@ -26,7 +26,7 @@ def kernels():
 @pytest.mark.parametrize("name,max_vgpr", [("k_upper4_stream<false, 0, false, true>", 128), ("k_upper4_stream<true, 0, false, true>", 128),
                                            ("k_upper4_stream<false, 0, false, false>", 128),
                                            ("k_lower4_stream<false, 0, true>", 96), ("k_lower4_stream<false, 0, false>", 96), ("k_lower4_stream<false, 2, true>", 96),
-                                           ("k_lower4_walk<4, 1, false, true>", 72),
+                                           ("k_lower4_walk<4, 1, false>", 72),
                                            ("k_lower_gen_walk<2, 5>", 128)])
 def test_hot_kernels_keep_their_occupancy(kernels, name, max_vgpr):
     k = kernels[name]
