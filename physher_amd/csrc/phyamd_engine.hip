@@ -2,7 +2,7 @@
 //
 // One translation unit, assembled from:
 //   phyamd_device.inc / _level4 / _walk4 / _walk4s / _general / _genwalk / _patterns   device code (kernels)
-//   phyamd_shard.inc        state of one engine on one GPU (= one shard of the site patterns)
+//   phyamd_shard.inc        state of one engine on one GPU (= one shard of the site patterns), the form of its stored lowers
 //   phyamd_schedule.inc     level and tree-walk schedules, device storage
 //   phyamd_launch.inc       kernel launches per pass
 //   phyamd_eval.inc         one evaluation (incremental updates, lazy rescaling, gradients, pattern tiling)
@@ -23,7 +23,7 @@
 //     depth-first walk (20-state post-order), cherries fused (phyamd_general.inc, phyamd_genwalk.inc);
 //   * a stored node holds t_n = P_n p_n, its partial carried through its own branch: the pre-order pass reads it where it would
 //     repeat that product (20 / 60 / 61 states: always; 4 states: between the two streamed walks -- every other reader of stored
-//     partials gets p_n back, ensure_compat_state);
+//     partials gets p_n back, require_reference_form);
 //   * transition matrices are built on the device from the cached eigen system and reach the 4-state kernels through
 //     wave-uniform (scalar) loads;
 //   * the pre-order pass computes BOTH children's uppers from one read of the parent's upper and fuses the branch-length

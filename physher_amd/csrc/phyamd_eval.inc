@@ -17,10 +17,6 @@ void record(Shard *e, int i) {
 	if (e->profiling) (void)hipEventRecord(e->ev[i], e->stream);
 }
 
-// A caller needs stored partials in the reference's rescaling convention (anything but the streamed pair of walks): from now on
-// every pass uses it, and if the stored state is in the power-of-two convention the post-order pass runs again.
-int ensure_compat_state(Shard *e);
-
 // lower pass (+ lazy rescaling).  On return d_result[0] holds lnL on the device.
 // need_host_check: 1 = read lnL back and decide the lazy switch here; 2 = (gradient calls) send lnL on its way to the host and let
 // the caller decide once its pre-order pass has been LAUNCHED (finish_lazy_check): the device does not idle between the passes
@@ -38,9 +34,9 @@ int run_lower(Shard *e, int need_host_check) {
 	e->act_lower_ops = e->d_lower_ops;
 	e->incremental_pass = false;
 	bool incremental = e->lower_valid && !e->all_dirty;
-	if (incremental && ((e->scaling_on && e->scale_exp2) || e->stored_tform) && !(e->changed.empty() && !e->force_root)) {
-		// an incremental update reads stored children: they have to be the partials themselves in the reference's convention, i.e. recomputed once
-		e->compat_sticky = true;
+	if (incremental && e->lower_form != LowerForm::Reference && !(e->changed.empty() && !e->force_root)) {
+		// an incremental update reads stored children in the reference's form: this pass recomputes every node in it
+		prefer_reference_form(e);
 		incremental = false;
 	}
 	if (incremental && e->changed.empty() && !e->force_root) {  // nothing changed: d_result[0] still holds lnL
@@ -152,23 +148,7 @@ int update_parameter_matrices(Shard *e) {
 		e->ppart_alloc = need;
 	}
 	if (e->params_dirty) {
-		const double *evec = e->model.data() + S, *ivec = e->model.data() + S + S * S;
-		std::vector<double> B((size_t)np * S * S), tmp((size_t)S * S);
-		for (int th = 0; th < np; th++) {
-			const double *dQ = e->dQ_host.data() + (size_t)th * S * S;
-			for (int a = 0; a < S; a++)
-				for (int j = 0; j < S; j++) {
-					double v = 0.0;
-					for (int i = 0; i < S; i++) v += ivec[a * S + i] * dQ[i * S + j];
-					tmp[a * S + j] = v;
-				}
-			for (int a = 0; a < S; a++)
-				for (int b = 0; b < S; b++) {
-					double v = 0.0;
-					for (int j = 0; j < S; j++) v += tmp[a * S + j] * evec[j * S + b];
-					B[((size_t)th * S + a) * S + b] = v;
-				}
-		}
+		const std::vector<double> B = eigen_basis_derivatives(e);
 		HIP_TRY(hipMemcpyAsync(e->d_B, B.data(), sizeof(double) * B.size(), hipMemcpyHostToDevice, e->stream));
 		HIP_TRY(hipStreamSynchronize(e->stream));  // B is a stack-lifetime buffer
 		e->params_dirty = false;
@@ -207,24 +187,8 @@ int launch_parameters_gen(Shard *e, double *dst) {
 		HIP_TRY(hipMemcpyAsync(e->d_pg_core, e->core_index.data(), sizeof(int) * e->N, hipMemcpyHostToDevice, e->stream));
 		HIP_TRY(hipStreamSynchronize(e->stream));
 	}
-	if (e->params_dirty) {  // B_theta = U^-1 dQ_theta U
-		const double *evec = e->model.data() + S, *ivec = e->model.data() + S + S2;
-		std::vector<double> Bm((size_t)np * S2), tmp((size_t)S2);
-		for (int th = 0; th < np; th++) {
-			const double *dQ = e->dQ_host.data() + (size_t)th * S2;
-			for (int a = 0; a < S; a++)
-				for (int j = 0; j < S; j++) {
-					double v = 0.0;
-					for (int i = 0; i < S; i++) v += ivec[a * S + i] * dQ[i * S + j];
-					tmp[a * S + j] = v;
-				}
-			for (int a = 0; a < S; a++)
-				for (int b = 0; b < S; b++) {
-					double v = 0.0;
-					for (int j = 0; j < S; j++) v += tmp[a * S + j] * evec[j * S + b];
-					Bm[((size_t)th * S + a) * S + b] = v;
-				}
-		}
+	if (e->params_dirty) {
+		const std::vector<double> Bm = eigen_basis_derivatives(e);
 		HIP_TRY(hipMemcpyAsync(e->d_pg_B, Bm.data(), sizeof(double) * Bm.size(), hipMemcpyHostToDevice, e->stream));
 		HIP_TRY(hipStreamSynchronize(e->stream));
 		e->params_dirty = false;
@@ -301,24 +265,15 @@ int finish_lazy_check(Shard *e, bool *again) {
 	return PHYAMD_OK;
 }
 
-int ensure_compat_state(Shard *e) {
-	e->compat_sticky = true;
-	if (!(e->scaling_on && e->scale_exp2) && !e->stored_tform) return PHYAMD_OK;
-	e->lower_valid = false;
-	e->all_dirty = true;
-	e->upper_valid = false;
-	return run_lower(e, 1);
-}
-
 int run_gradient(Shard *e, int flags, bool with_params = false) {
 	int rc;
-	// the power-of-two rescaling convention serves the plain gradient only: parameter sums, the reference's folded / per-category
-	// arithmetic and resident uppers read stored partials with other kernels
+	// the streamed walks' own forms serve the plain gradient only: parameter sums, the reference's folded / per-category arithmetic
+	// and resident uppers read stored partials with other kernels
 	if (with_params || e->keep_partials || (e->scaling_on && (flags & PHYAMD_GRAD_COMPAT_SCALED))) {
 		if ((rc = bind_device(e))) return rc;
-		if ((rc = ensure_compat_state(e))) return rc;  // (stored lowers of an earlier call in the walks' own convention: computed again)
+		if ((rc = require_reference_form(e))) return rc;  // (stored lowers of an earlier call in another form: computed again)
 	} else if (e->scaling_on && (flags & PHYAMD_GRAD_FOLD_ROOT_FREQS))
-		e->compat_sticky = true;  // (the reference's folded arithmetic under rescaling: its convention from the next post-order pass on)
+		prefer_reference_form(e);  // (the reference's folded arithmetic under rescaling: its form from the next post-order pass on)
 	e->upper_fold = (flags & PHYAMD_GRAD_FOLD_ROOT_FREQS) != 0;
 	if (with_params) {
 		if (e->np < 1) return fail(PHYAMD_EINVAL, "phyamd_set_rate_matrix_derivatives has not been called");
@@ -341,6 +296,8 @@ int run_gradient(Shard *e, int flags, bool with_params = false) {
 		if ((rc = rebuild_schedule(e))) return rc;
 		if ((rc = run_lower(e, true))) return rc;
 	}
+	// (a tile's post-order pass decides the lazy switch itself: rescaling may have come on after the requirement above was settled)
+	if (e->scaling_on && (flags & PHYAMD_GRAD_COMPAT_SCALED) && (rc = require_reference_form(e))) return rc;
 	bool any_explicit = false;  // explicit matrices have no eigen system: the tree-walk's eigen-basis branch term does not cover them
 	for (uint8_t x : e->explicit_host) any_explicit |= x != 0;
 	const bool walk_params = with_params && !any_explicit && !e->generic && e->walking &&

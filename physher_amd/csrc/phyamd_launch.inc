@@ -1,11 +1,6 @@
 // phyamd_launch.inc -- kernel launches of the post-order and pre-order passes (4 states and 20 / 60 / 61 states)
 // (part of phyamd_engine.hip: one translation unit, internal linkage)
 
-int ensure_compat_state(Shard *e);  // (phyamd_eval.inc)
-// a pre-order kernel other than the streamed walk is about to read stored lowers: they have to be the partials themselves, in the
-// reference's rescaling convention (the post-order pass runs again if the streamed walk left them in its own)
-int require_reference_lowers(Shard *e) { return (e->stored_tform || (e->scaling_on && e->scale_exp2)) ? ensure_compat_state(e) : PHYAMD_OK; }
-
 size_t gen_image_doubles(const Shard *e) {
 	return e->S == 20 ? MatImage<2, 5>::SIZE : e->S == 60 ? MatImage<4, 15>::SIZE : MatImage<4, 16>::SIZE;
 }
@@ -197,8 +192,7 @@ int launch_lower_w(Shard *e) {
 		else if (rc) return rc;
 		else if (!e->stream_unsupported) return launch_lower_stream(e);
 	}
-	e->scale_exp2 = false;  // (every other post-order kernel rescales as the reference does
-	e->stored_tform = false;  //  and stores the partials themselves)
+	e->lower_form = LowerForm::Reference;
 	if (e->walking && !e->incremental_pass) return e->scaling_on ? launch_lower_walk<WAVES, true>(e) : launch_lower_walk<WAVES, false>(e);
 	return e->scaling_on ? launch_lower_levels<WAVES, true>(e) : launch_lower_levels<WAVES, false>(e);
 }
@@ -217,7 +211,7 @@ int launch_upper_levels(Shard *e, int p0 = 0, int pc = 0) {
 	const size_t nw = (size_t)e->G * e->C, nacc = NACC + (PARAMS ? pc : 0);
 	const size_t lds = sizeof(double) * ((SCALE ? 6 * nw * WAVE : 0) + nw * nacc * WAVE + nw * nacc);
 	int rc;
-	if ((rc = require_reference_lowers(e))) return rc;
+	if ((rc = check_reference_form(e, "k_upper4"))) return rc;
 	if ((rc = allow_big_lds(k_upper4<WAVES, SCALE, FOLD, COMPAT, PARAMS>, lds))) return rc;
 	const int op_total = (int)e->upper_ops.size();
 	const double *dpm = PARAMS ? e->d_dpm + (size_t)p0 * e->N * e->C * 16 : nullptr;
@@ -293,15 +287,8 @@ int ensure_optab(Shard *e) {
 	return PHYAMD_OK;
 }
 
-// the streamed post-order walk (k_lower4_stream): every cut subtree as workgroups of its own, then the top part with the root
-// rescaled evaluations of the streamed walks: powers of two per category unless some caller needs the reference's convention
-bool exp2_scaling(const Shard *e) { return e->scaling_on && e->exp2_on && !e->compat_sticky; }
-// what the streamed post-order walk stores: t = P p (TF) unless some caller needs the partials themselves; the reference's rescaling
-// (SCALE == 1) is by definition the compatible form; the power-of-two one is private to the two walks anyway: always TF
-bool tform_storage(const Shard *e) { return e->scaling_on ? exp2_scaling(e) : e->tform_on && !e->compat_sticky; }  // (PHYAMD_STREAM_TFORM = 0: plain evaluations only)
-
 bool lower_stream_applies(const Shard *e) {
-	return e->walking && e->stream_walk && e->lstream_on && (!e->scaling_on || exp2_scaling(e) || e->C <= STREAM_WAVES) &&
+	return e->walking && e->stream_walk && e->lstream_on && (!e->scaling_on || stream_lower_form(e) == LowerForm::CarriedExp2 || e->C <= STREAM_WAVES) &&
 	       !e->incremental_pass && !e->lstream_desc.empty();
 }
 
@@ -314,6 +301,8 @@ int ensure_ints(Shard *e, int **p, size_t *have, size_t count) {
 	if (!rc) *have = count;
 	return rc;
 }
+
+// the streamed post-order walk (k_lower4_stream): every cut subtree as workgroups of its own, then the top part with the root
 int launch_lower_stream(Shard *e) {
 	int rc;
 	const int nb = (e->P + WAVE - 1) / WAVE, nops = (int)e->stream_ops.size();
@@ -325,14 +314,15 @@ int launch_lower_stream(Shard *e) {
 	                   (const int *)e->d_stream_site_tab, e->d_mats, (const double *)nullptr, reinterpret_cast<double *>(e->d_optab));
 	// rescaled: powers of two per category (the plain workgroup shape), or the reference's maxima over categories -- workgroup = the
 	// category waves of one block + their exchange buffer
-	const bool exp2 = exp2_scaling(e), scale = e->scaling_on && !exp2;
+	const LowerForm form = stream_lower_form(e);
+	const StreamVariant v = stream_variant(form, e->scaling_on);
+	const bool exp2 = v.scale == 2, scale = v.scale == 1, tf = v.tf;
 	if (exp2) {
 		if ((rc = ensure_ints(e, &e->d_lexp, &e->lexp_alloc, e->lower_alloc_cores * (size_t)e->C * e->P))) return rc;
-		if (!e->d_Ec && ((rc = dev_alloc(e, &e->d_Ec, (size_t)e->C * e->P)) || (rc = dev_alloc(e, &e->d_Eroot, (size_t)e->P)))) return rc;
+		if (!e->d_Ec && (rc = dev_alloc(e, &e->d_Ec, (size_t)e->C * e->P))) return rc;
+		if (!e->d_Eroot && (rc = dev_alloc(e, &e->d_Eroot, (size_t)e->P))) return rc;
 	}
-	e->scale_exp2 = exp2;
-	const bool tf = tform_storage(e);
-	e->stored_tform = tf;
+	e->lower_form = form;
 	const int waves = scale ? e->C : STREAM_WAVES;
 	const size_t lds = (size_t)LSTREAM_LDS_PER_WAVE * waves + (scale ? sizeof(double) * 2 * e->C * WAVE : 0);
 	const unsigned gx = scale ? (unsigned)nb : (unsigned)((nb + STREAM_WAVES - 1) / STREAM_WAVES) * e->C;
@@ -379,8 +369,10 @@ int launch_upper_stream(Shard *e) {
 		e->oct_alloc = (size_t)8 * e->C * R;
 	}
 	// plain: workgroup = four blocks of one category; rescaled as the reference does: the C <= 4 category waves of one block + their
-	// exchange buffers; rescaled by powers of two (the stored lowers are in that convention): the plain shape + the parks' exponents
-	const bool exp2 = SCALE && e->scale_exp2;
+	// exchange buffers; rescaled by powers of two (the stored lowers are in that form): the plain shape + the parks' exponents
+	const StreamVariant v = stream_variant(e->lower_form, SCALE);  // (the stored lowers decide: they are what this walk reads)
+	if (v.scale < 0) return fail(PHYAMD_EDEVICE, "streamed walk: the stored lowers hold the %s form, which no %s post-order pass writes", form_name(e->lower_form), SCALE ? "rescaled" : "plain");
+	const bool exp2 = v.scale == 2, tf = v.tf;
 	if (exp2 && (rc = ensure_ints(e, &e->d_uexp, &e->uexp_alloc, std::max<size_t>(1, e->upper_alloc_slots) * e->C * e->P))) return rc;
 	const int waves = SCALE && !exp2 ? e->C : STREAM_WAVES;
 	const size_t lds = (size_t)STREAM_LDS_PER_WAVE * waves + (exp2 ? (size_t)waves * STREAM_PARK_SLOTS * WAVE * sizeof(int) : SCALE ? (size_t)4 * e->C * WAVE * sizeof(double) : 0);
@@ -389,12 +381,11 @@ int launch_upper_stream(Shard *e) {
 	                   (const int *)e->d_stream_site_tab, e->d_mats, FOLD ? e->d_Q : e->d_Qpi, reinterpret_cast<double *>(e->d_optab));
 	const int subtrees = (int)e->walk_chunk_off.size() - 2;
 	for (int phase = 0; phase < (subtrees > 0 ? 2 : 1); phase++) {
-		const bool amb = e->stream_ambiguous, tf = e->stored_tform;  // (the stored lowers decide: they are what this walk reads)
+		const bool amb = e->stream_ambiguous;
 		auto *kernel = exp2 ? (amb ? k_upper4_stream<FOLD, 2, true, true> : k_upper4_stream<FOLD, 2, false, true>)
 		             : SCALE ? (amb ? k_upper4_stream<FOLD, 1, true, false> : k_upper4_stream<FOLD, 1, false, false>)
 		             : tf    ? (amb ? k_upper4_stream<FOLD, 0, true, true> : k_upper4_stream<FOLD, 0, false, true>)
 		                     : (amb ? k_upper4_stream<FOLD, 0, true, false> : k_upper4_stream<FOLD, 0, false, false>);
-		if (tf != (exp2 || (!SCALE && tf))) return fail(PHYAMD_EDEVICE, "streamed walk: stored partials and rescaling convention do not match");
 		hipLaunchKernelGGL(kernel, dim3(grid_x.x, phase ? subtrees : 1), block, lds, e->stream, (const StreamDesc *)e->d_stream_ops, (const StreamChunk *)e->d_stream_chunks,
 		                   (const int *)e->d_walk_chunk_off, phase, nops, e->P, e->C, nb, (const uint32_t *)e->d_mstream, e->mstride, (const double *)e->d_lower, e->d_upper,
 		                   (const double *)e->d_mats, (const char *)e->d_optab, (const double *)(FOLD ? e->d_Q : e->d_Qpi), (const double *)e->d_freqs, (const double *)e->d_wl,
@@ -456,24 +447,21 @@ int reduce_stream_slab(Shard *e, double *out) {
 template <int WAVES, bool FOLD, bool SCALE, bool COMPAT>
 int launch_upper_walk_v(Shard *e) {
 	const int ops = (int)e->walk_upper_ops.size(), nb = e->nblk_walk_upper * e->G;
-	if (!COMPAT && e->stream_walk && (!SCALE || e->scale_exp2 || e->C <= STREAM_WAVES)) {
-		if constexpr (!COMPAT) {
+	int rc;
+	if constexpr (!COMPAT) {
+		if (e->stream_walk && (!SCALE || e->lower_form == LowerForm::CarriedExp2 || e->C <= STREAM_WAVES)) {
 			// (pattern tiles: the mask words follow the tile's tip codes, rebuilt with every tile copy: ~0.1 ms per tile)
-			int rc1 = ensure_mask_stream(e);
-			if (!rc1) rc1 = ensure_optab(e);
-			if (rc1 == PHYAMD_ENOMEM && e->cfg.max_device_bytes > 0) e->stream_walk = false;  // the cap leaves no room for the words: the table-gather walk from here on
-			else if (rc1) return rc1;
+			rc = ensure_mask_stream(e);
+			if (!rc) rc = ensure_optab(e);
+			if (rc == PHYAMD_ENOMEM && e->cfg.max_device_bytes > 0) e->stream_walk = false;  // the cap leaves no room for the words: the table-gather walk from here on
+			else if (rc) return rc;
 			else if (!e->stream_unsupported) return launch_upper_stream<FOLD, SCALE>(e);
 		}
 	}
-	{
-		int rc2;
-		if ((rc2 = require_reference_lowers(e))) return rc2;
-	}
+	if ((rc = check_reference_form(e, "k_upper4_walk"))) return rc;
 	// columns, the rescaling exchange, then the leaf parks' LDS slots (LPARK: 2 KB per wave)
 	const size_t lds = sizeof(double) * ((size_t)e->G * e->C * NACC * WCOL + (SCALE ? (size_t)4 * e->G * e->C * WAVE : 0) + (size_t)4 * e->G * e->C * WAVE);
-	int rc0;
-	if ((rc0 = allow_big_lds(k_upper4_walk<WAVES, FOLD, false, SCALE, COMPAT>, lds))) return rc0;
+	if ((rc = allow_big_lds(k_upper4_walk<WAVES, FOLD, false, SCALE, COMPAT>, lds))) return rc;
 	// the chunked list: the top part, then every cut subtree as workgroups of its own (blockIdx.y)
 	const int subtrees = (int)e->walk_chunk_off.size() - 2;
 	for (int phase = 0; phase < (subtrees > 0 ? 2 : 1); phase++)
@@ -498,13 +486,36 @@ int launch_upper_walk(Shard *e, bool fold, bool compat) {
 	return fold ? launch_upper_walk_v<WAVES, true, false, false>(e) : launch_upper_walk_v<WAVES, false, false, false>(e);
 }
 
+// B_theta = U^-1 dQ_theta U of every parameter theta, [np][S][S] (U, U^-1: the eigen system in e->model)
+std::vector<double> eigen_basis_derivatives(const Shard *e) {
+	const int S = e->S;
+	const double *evec = e->model.data() + S, *ivec = e->model.data() + S + S * S;
+	std::vector<double> B((size_t)e->np * S * S), tmp((size_t)S * S);
+	for (int th = 0; th < e->np; th++) {
+		const double *dQ = e->dQ_host.data() + (size_t)th * S * S;
+		for (int a = 0; a < S; a++)
+			for (int j = 0; j < S; j++) {
+				double v = 0.0;
+				for (int i = 0; i < S; i++) v += ivec[a * S + i] * dQ[i * S + j];
+				tmp[a * S + j] = v;
+			}
+		for (int a = 0; a < S; a++)
+			for (int b = 0; b < S; b++) {
+				double v = 0.0;
+				for (int j = 0; j < S; j++) v += tmp[a * S + j] * evec[j * S + b];
+				B[((size_t)th * S + a) * S + b] = v;
+			}
+	}
+	return B;
+}
+
 // G2 through the tree walk: B = U^-1 dQ U per parameter, the eigen-basis tables, one walk, then 16 sums and a contraction
 template <int WAVES, bool SCALE>
 int launch_upper_walk_params(Shard *e) {
 	const int ops = (int)e->walk_upper_ops.size(), nb = e->nblk_walk_upper * e->G, S = 4, np = e->np;
 	const size_t lds = sizeof(double) * ((size_t)e->G * e->C * 16 * WCOL + (SCALE ? (size_t)4 * e->G * e->C * WAVE : 0));
 	int rc;
-	if ((rc = require_reference_lowers(e))) return rc;
+	if ((rc = check_reference_form(e, "k_upper4_walk (parameters)"))) return rc;
 	if ((rc = upload_qpi(e))) return rc;
 	if ((size_t)np > e->np_alloc_B) {
 		dev_free(e, &e->d_Bw, e->np_alloc_B * 16);
@@ -517,22 +528,8 @@ int launch_upper_walk_params(Shard *e) {
 	if (!e->d_gacc && (rc = dev_alloc(e, &e->d_gacc, (size_t)16 * nb * e->C + 16))) return rc;
 	{
 		const double *evec = e->model.data() + S, *ivec = e->model.data() + S + S * S;
-		std::vector<double> B((size_t)np * 16), tmp(16), pb(96);
-		for (int th = 0; th < np; th++) {
-			const double *dQ = e->dQ_host.data() + (size_t)th * 16;
-			for (int a = 0; a < 4; a++)
-				for (int j = 0; j < 4; j++) {
-					double v = 0.0;
-					for (int i = 0; i < 4; i++) v += ivec[a * 4 + i] * dQ[i * 4 + j];
-					tmp[a * 4 + j] = v;
-				}
-			for (int a = 0; a < 4; a++)
-				for (int b = 0; b < 4; b++) {
-					double v = 0.0;
-					for (int j = 0; j < 4; j++) v += tmp[a * 4 + j] * evec[j * 4 + b];
-					B[(size_t)th * 16 + a * 4 + b] = v;
-				}
-		}
+		const std::vector<double> B = eigen_basis_derivatives(e);
+		std::vector<double> pb(96);
 		for (int a = 0; a < 4; a++)
 			for (int i = 0; i < 4; i++) {
 				pb[a * 4 + i] = evec[i * 4 + a] * e->freqs[i];  // (diag(pi) U)^T

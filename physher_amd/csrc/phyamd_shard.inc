@@ -1,5 +1,9 @@
-// phyamd_shard.inc -- state of one engine on one GPU (one pattern shard)
+// phyamd_shard.inc -- state of one engine on one GPU (one pattern shard) and the form of its stored 4-state lowers
 // (part of phyamd_engine.hip: one translation unit, internal linkage)
+
+// what a stored 4-state lower array holds: the reference's p_n (with its rescaling), or -- read by the two streamed walks only --
+// t_n = P_n p_n (their TF), unscaled or rescaled by powers of two per category (SCALE == 2)
+enum class LowerForm { Reference, Carried, CarriedExp2 };
 
 struct Shard {
 	phyamd_config cfg{};
@@ -120,17 +124,13 @@ struct Shard {
 	std::vector<uint8_t> tip_set;
 	bool matrices_dirty = true;
 	bool scaling_on = false;
-	// Rescaling by powers of two per category (phyamd_walk4s.inc, exp2_rescale): the convention of the two streamed walks when nothing
-	// else has to read the stored partials.  scale_exp2: the stored lowers ARE in that convention (set by the streamed post-order walk);
-	// compat_sticky: some caller needed the reference's convention (stored partials, single-branch evaluations, store / restore,
-	// incremental updates, parameter or reference-compatible gradients): from then on every pass uses it.
-	bool exp2_on = true, scale_exp2 = false, compat_sticky = false;  // PHYAMD_SCALE_EXP2 = 0: never
-	// The same arrangement for WHAT a stored 4-state lower array holds between the two streamed walks: t_n = P_n p_n instead of p_n
-	// (k_lower4_stream's TF variants; the pre-order walk then skips the mat-vec of every stored child).  stored_tform: the stored
-	// lowers ARE so; tform_on: PHYAMD_STREAM_TFORM = 0: never.  compat_sticky ends it like the power-of-two rescaling.
-	bool tform_on = true, stored_tform = false;
+	// the form of the stored 4-state lowers in the slots core_index points at now, and the policy that decides it (below,
+	// "what d_lower holds"): reference_form_only = some reader has needed the reference's form, every later post-order pass writes it
+	LowerForm lower_form = LowerForm::Reference;
+	bool reference_form_only = false;
+	bool exp2_on = true, tform_on = true;  // PHYAMD_SCALE_EXP2 = 0 / PHYAMD_STREAM_TFORM = 0: the streamed walks never write CarriedExp2 / Carried
 	int *d_lexp = nullptr, *d_uexp = nullptr, *d_Ec = nullptr, *d_Eroot = nullptr;  // exponents: [stored][C][P], [upper slots][C][P], [C][P], [P]
-	size_t lexp_alloc = 0, uexp_alloc = 0, ec_alloc = 0;
+	size_t lexp_alloc = 0, uexp_alloc = 0;
 	bool keep_partials = false;
 	bool profiling = false;
 	bool upper_valid = false;
@@ -212,3 +212,45 @@ struct Shard {
 	hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
 	phyamd_profile prof{};
 };
+
+// ---- what d_lower holds ----------------------------------------------------------------------------------------------------
+// Every 4-state post-order pass records the form it wrote (launch_lower_w, launch_lower_stream).  A reader other than the two
+// streamed walks settles the form before a pass is launched (require_reference_form, prefer_reference_form); launchers only check.
+
+const char *form_name(LowerForm f) { return f == LowerForm::Reference ? "Reference" : f == LowerForm::Carried ? "Carried" : "CarriedExp2"; }
+
+// the form the streamed post-order walk writes: t_n = P_n p_n -- rescaled: by powers of two per category -- unless a reader has
+// needed the reference's (the reference's own rescaling, SCALE == 1, is by definition the reference's form)
+LowerForm stream_lower_form(const Shard *e) {
+	if (e->reference_form_only) return LowerForm::Reference;
+	if (e->scaling_on) return e->exp2_on ? LowerForm::CarriedExp2 : LowerForm::Reference;
+	return e->tform_on ? LowerForm::Carried : LowerForm::Reference;
+}
+
+// the streamed walks' instantiation (k_lower4_stream, k_upper4_stream) for stored lowers of form f in a pass with or without
+// rescaling: SCALE (0: none, 1: the reference's, 2: powers of two) and TF.  scale = -1: no post-order pass writes f so
+struct StreamVariant { int scale; bool tf; };
+StreamVariant stream_variant(LowerForm f, bool scaling) {
+	if (f != LowerForm::Reference && (f == LowerForm::CarriedExp2) != scaling) return {-1, false};
+	return {f == LowerForm::CarriedExp2 ? 2 : scaling ? 1 : 0, f != LowerForm::Reference};
+}
+
+int check_reference_form(const Shard *e, const char *kernel) {  // a launcher of a kernel that reads the stored lowers as p_n
+	if (e->lower_form == LowerForm::Reference) return PHYAMD_OK;
+	return fail(PHYAMD_EDEVICE, "%s reads the stored lowers in the Reference form, they hold the %s form", kernel, form_name(e->lower_form));
+}
+
+int run_lower(Shard *e, int need_host_check);  // (phyamd_eval.inc)
+
+// a reader needs the reference's form from the next post-order pass on (for good: the streamed walks lose their own forms)
+void prefer_reference_form(Shard *e) { e->reference_form_only = true; }
+
+// a reader needs the reference's form now: the post-order pass runs again if the stored lowers are in another form
+int require_reference_form(Shard *e) {
+	prefer_reference_form(e);
+	if (e->lower_form == LowerForm::Reference) return PHYAMD_OK;
+	e->lower_valid = false;
+	e->all_dirty = true;
+	e->upper_valid = false;
+	return run_lower(e, 1);
+}

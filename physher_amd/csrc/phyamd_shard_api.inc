@@ -112,6 +112,8 @@ void free_pattern_storage(Shard *e) {
 	dev_free(e, &e->d_wl, (size_t)e->P);
 	dev_free(e, &e->d_lnl_part, e->lnl_part_alloc);
 	dev_free(e, &e->d_Lc, (size_t)e->C * e->P);
+	dev_free(e, &e->d_Ec, (size_t)e->C * e->P);
+	dev_free(e, &e->d_Eroot, (size_t)e->P);
 	dev_free(e, &e->d_gpart, (size_t)e->N * e->C * e->gpart_row);
 	dev_free(e, &e->d_mstream, e->mstream_alloc);
 	e->mstream_alloc = 0;
@@ -444,7 +446,7 @@ int shard_store(Shard *e) {
 	NOT_TILED(e, "phyamd_store");
 	int rc;
 	if ((rc = bind_device(e))) return rc;
-	if ((rc = ensure_compat_state(e))) return rc;  // (stored partials: the partials themselves, in the reference's rescaling convention)
+	if ((rc = require_reference_form(e))) return rc;  // (stored partials: the partials themselves, in the reference's form)
 	for (uint8_t x : e->explicit_host)
 		if (x) return fail(PHYAMD_EUNSUPPORTED, "phyamd_store does not cover explicit node matrices");
 	if ((rc = run_lower(e, true))) return rc;  // the state that is stored is an evaluated one (a no-op when nothing is pending)
@@ -753,7 +755,7 @@ int shard_root_frequency_term(Shard *e, double *out) {
 	if ((rc = bind_device(e))) return rc;
 	if ((rc = check_ready(e))) return rc;
 	// (the root's array is p_root in every storage convention: only a rescaled evaluation's factors have to be the reference's)
-	if (e->scaling_on && (rc = ensure_compat_state(e))) return rc;
+	if (e->scaling_on && (rc = require_reference_form(e))) return rc;
 	if (e->tiles > 1) {  // the per-tile terms were summed by the last phyamd_parameter_gradient
 		if (!e->tiled_root_term) return fail(PHYAMD_EINVAL, "with tiled patterns the root frequency term comes with phyamd_parameter_gradient: call that first");
 		HIP_TRY(hipMemcpyAsync(e->h_result, e->d_result + 1 + (size_t)e->N * e->C + e->np, sizeof(double) * e->S, hipMemcpyDeviceToHost, e->stream));
@@ -866,7 +868,7 @@ int shard_branch_log_likelihood(Shard *e, int node, double length, double *lnl, 
 	if (!e->have_eigen) return fail(PHYAMD_EINVAL, "the single-branch evaluation needs the eigen system (phyamd_set_eigen)");
 	int rc;
 	if ((rc = bind_device(e))) return rc;
-	if ((rc = ensure_compat_state(e))) return rc;  // (stored partials: the partials themselves, in the reference's rescaling convention)
+	if ((rc = require_reference_form(e))) return rc;  // (stored partials: the partials themselves, in the reference's form)
 	const size_t npd = node_partial_doubles(e);
 	// the two partials that meet on the branch: resident after a keep-partials gradient, else the upper one is rebuilt by a
 	// walk down the path from the root (pending changes are evaluated first; the result is kept until partials change)
@@ -946,7 +948,7 @@ int shard_root_invariant_term(Shard *e, double *out) {
 	int rc;
 	if ((rc = bind_device(e))) return rc;
 	if ((rc = check_ready(e))) return rc;
-	if (e->scaling_on && (rc = ensure_compat_state(e))) return rc;  // (see shard_root_frequency_term)
+	if (e->scaling_on && (rc = require_reference_form(e))) return rc;  // (see shard_root_frequency_term)
 	const double *src;
 	if (e->tiles > 1) {  // summed over the tiles by the last evaluation (one entry behind everything else in the total)
 		if (!e->tiled_eval_done) return fail(PHYAMD_EINVAL, "no evaluation has been run yet");
@@ -986,7 +988,7 @@ int shard_get_partials(Shard *e, int node, int upper, double *out) {
 	if (!out || node < 0 || node >= e->N) return fail(PHYAMD_EINVAL, "bad node %d or null out", node);
 	int rc;
 	if ((rc = bind_device(e))) return rc;
-	if ((rc = ensure_compat_state(e))) return rc;  // (stored partials: the partials themselves, in the reference's rescaling convention)
+	if ((rc = require_reference_form(e))) return rc;  // (stored partials: the partials themselves, in the reference's form)
 	const size_t np = node_partial_doubles(e);
 	if (upper) {
 		if (!e->keep_partials || !e->upper_valid) return fail(PHYAMD_EINVAL, "upper partials need shard_set_keep_partials(1) before phyamd_gradient");
@@ -1075,7 +1077,7 @@ int shard_set_keep_partials(Shard *e, int on) {
 	if (on) NOT_TILED(e, "keeping every partial");
 	const bool want = on != 0;
 	if (want == e->keep_partials) return PHYAMD_OK;
-	if (want) e->compat_sticky = true;  // (resident partials are the reference's: no power-of-two rescaling from here on)
+	if (want) prefer_reference_form(e);  // (resident partials are the reference's)
 	e->keep_partials = want;
 	e->upper_valid = false;
 	if (e->have_topology) {

@@ -325,8 +325,8 @@ __device__ __forceinline__ double fold_sites(double acc0, double acc1, double ac
 // CATEGORY'S OWN affair: with integer exponents per (node, pattern, category) a branch term is brought to the units of the site
 // likelihood by one ldexp, so the category waves of a pattern block never have to meet -- the reference's scheme (a maximum over
 // categories and states, treelikelihood.c:1790-1836: SCALE == 1) costs both walks an LDS exchange behind a barrier per op.
-// The stored partials then differ from the reference's by their scale factors: this convention lives between the two streamed
-// walks only (Shard::scale_exp2); every other consumer of stored partials gets the reference's (require_compat_scaling).
+// The stored partials then differ from the reference's by their scale factors: this form lives between the two streamed walks
+// only (LowerForm::CarriedExp2); every other reader of stored partials gets the reference's (require_reference_form).
 __device__ __forceinline__ int exp2_rescale(d4 &v) {
 	const double m = max4(v);
 	if (!(m < SCALING_THRESHOLD) || !(m > 0.0)) return 0;
@@ -716,8 +716,8 @@ __device__ __forceinline__ void dma_dword(const char *gsrc, lds_cptr dst) {  // 
 // TF: what an op hands on -- carries, parks, stores -- is t_n = P_n p_n, the partial already carried through the node's own branch
 // (the root: p_root).  The multiply-adds are the same in number (one mat-vec per op instead of one per stored child), but the
 // pre-order walk reads a stored child as its message and drops that mat-vec: 16 of ~220 vector instructions per op.  This is a
-// convention BETWEEN the two streamed walks (Shard::stored_tform): every other reader of stored partials gets p_n back
-// (ensure_compat_state: the pass runs again without TF and stays so).  Never with SCALE == 1, which IS the reference's convention.
+// form BETWEEN the two streamed walks (LowerForm::Carried): every other reader of stored partials gets p_n back
+// (require_reference_form: the pass runs again without TF and stays so).  Never with SCALE == 1, which IS the reference's form.
 template <bool AMBIG, int SCALE, bool TF = false>  // SCALE: 0 plain, 1 the reference's rescaling (exchange), 2 powers of two per category (lscale = int exponents [stored][C][P])
 __global__ __launch_bounds__(STREAM_WAVES *WAVE, SCALE == 1 ? 4 : LSTREAM_MIN_WAVES) void k_lower4_stream(
     const LowerDesc *__restrict__ ops, const LowerChunk *__restrict__ chunks, const int *__restrict__ chunk_off, int chunk_base, int nblocks, int P, int C, int nb,

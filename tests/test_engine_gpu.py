@@ -1150,6 +1150,24 @@ def test_pattern_tiling_under_a_memory_cap(S, T, P, C, rescale, shape):
         Engine(T, P, S, C, max_device_bytes=1000)  # below the smallest tile
 
 
+def test_lazy_rescaling_switch_inside_a_tile_with_the_compat_gradient():
+    """A tile's post-order pass decides the lazy switch itself, so rescaling comes on after run_gradient has settled what form the
+    stored lowers must be in.  The reference-compatible gradient reads them in the reference's form, the streamed walk has just
+    written its own: the pass runs again before the pre-order pass is launched, and the tiled result is the untiled one's."""
+    pb = random_problem(900, 3000, 4, seed=13, bl=(0.5, 1.5))
+    with engine_from_problem(pb, rescale=RESCALE_AUTO) as whole:
+        whole.gradient()  # (the streamed walks' exponent arrays are part of the working set the cap is taken from)
+        cap = int(0.45 * whole.profile()["device_bytes"])
+        l_ref, cg_ref = whole.gradient(GRAD_COMPAT_SCALED)
+        assert whole.rescaling
+    with engine_from_problem(pb, rescale=RESCALE_AUTO, max_device_bytes=cap) as e:
+        assert e.profile()["tiles"] >= 2 and not e.rescaling
+        lnl, cg = e.gradient(GRAD_COMPAT_SCALED)
+        assert e.rescaling
+        assert abs(lnl - l_ref) <= 1e-12 * abs(l_ref)
+        assert np.abs(cg - cg_ref).max() <= 1e-10 * max(1.0, np.abs(cg_ref).max())
+
+
 def test_memory_cap_is_never_exceeded_by_later_requests():
     """20 states, tiled: a substitution-parameter gradient wants every node's lower and upper partial resident (about three
     times the tile's working set).  Under an explicit cap that is refused with PHYAMD_ENOMEM instead of silently overshooting."""
