@@ -214,3 +214,16 @@ def root_frequency_term(problem: "Problem"):
     root = np.einsum("c,cks->ks", problem.cat_props, r["lower"][problem.root])
     like = root @ problem.freqs
     return (problem.weights / like) @ root
+
+
+def root_invariant_term(problem: "Problem"):
+    """d lnL / d(proportion of the invariant class) through the root partials (treelikelihood.c:2943-3008):
+    sum_k (w_k / L_k) sum_i pi_i (p_root[0][k][i] - mean_{c >= 1} p_root[c][k][i]).  The scale factors are per pattern, so they
+    cancel in the ratio: rescaled problems are served too.  Needs at least two categories."""
+    if problem.C < 2:
+        raise ValueError("the invariant-class term needs at least two categories")
+    r = problem.log_likelihood(want_lower=True)
+    root = r["lower"][problem.root]  # [C][P][S]
+    diff = (root[0] - root[1:].mean(axis=0)) @ problem.freqs
+    like = np.einsum("c,cks->ks", problem.cat_props, root) @ problem.freqs
+    return float(np.sum(problem.weights * diff / like))

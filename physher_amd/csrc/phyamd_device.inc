@@ -278,22 +278,32 @@ __global__ __launch_bounds__(64) void k_reduce_rows(const double *__restrict__ p
 // invariant class) term that needs the root partials (treelikelihood.c:2943-3008).  root: stored root partial;
 // cat_stride / pat_stride / state_stride describe its layout ([C][P][4] or planes [C][S][Pp]).  L_k is re-formed from the
 // root partial itself (scale factors are per pattern), so the expression also serves rescaled evaluations.
+// Ec: null, or the per-category exponents of a root partial in the streamed walks' power-of-two form (LowerForm::CarriedExp2,
+// [C][P]: category c is in units of 2^Ec[c][k]).  Every category is then brought to the units of the largest exponent of its
+// pattern before the categories are mixed (as k_root_finish64 forms L_k).
 __global__ __launch_bounds__(256) void k_root_invariant_term(int P, int S, int C, const double *__restrict__ root, size_t cat_stride, size_t pat_stride,
                                                             size_t state_stride, const double *__restrict__ freqs, const double *__restrict__ props,
-                                                            const double *__restrict__ weights, double *__restrict__ part) {
+                                                            const double *__restrict__ weights, const int *__restrict__ Ec, double *__restrict__ part) {
 	__shared__ double red[4];
 	const int k = blockIdx.x * 256 + threadIdx.x;
 	double acc = 0.0;
 	if (k < P) {
+		int E = 0;
+		if (Ec) {
+			E = Ec[k];
+			for (int c = 1; c < C; c++) E = max(E, Ec[(size_t)c * P + k]);
+		}
 		double s = 0.0, like = 0.0;
 		for (int i = 0; i < S; i++) {
 			const double *p = root + (size_t)k * pat_stride + (size_t)i * state_stride;
-			double others = 0.0, mix = props[0] * p[0];
+			const double p0 = Ec ? ldexp(p[0], Ec[k] - E) : p[0];
+			double others = 0.0, mix = props[0] * p0;
 			for (int c = 1; c < C; c++) {
-				others += p[(size_t)c * cat_stride];
-				mix += props[c] * p[(size_t)c * cat_stride];
+				const double v = p[(size_t)c * cat_stride], pc = Ec ? ldexp(v, Ec[(size_t)c * P + k] - E) : v;
+				others += pc;
+				mix += props[c] * pc;
 			}
-			s += freqs[i] * (p[0] - others / (C - 1));
+			s += freqs[i] * (p0 - others / (C - 1));
 			like += freqs[i] * mix;
 		}
 		acc = s * (weights[k] / like);

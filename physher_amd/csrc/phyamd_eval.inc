@@ -232,7 +232,8 @@ int launch_root_frequency_term(Shard *e, double *dst) {
 	return PHYAMD_OK;
 }
 
-// sum_k (w_k / L_k) sum_i pi_i (p_root[cat 0] - mean of p_root[cat >= 1]) of the resident root partial -> dst (device)
+// sum_k (w_k / L_k) sum_i pi_i (p_root[cat 0] - mean of p_root[cat >= 1]) of the resident root partial -> dst (device), in whatever
+// form the last post-order pass left it (CarriedExp2: with its per-category exponents)
 int launch_root_invariant_term(Shard *e, double *dst) {
 	int rc;
 	const int nb = (e->P + 255) / 256;
@@ -240,8 +241,9 @@ int launch_root_invariant_term(Shard *e, double *dst) {
 	const double *root = e->d_lower + (size_t)e->core_index[e->root] * node_partial_doubles(e);
 	const size_t cat_stride = e->generic ? (size_t)e->S * e->Pp : (size_t)e->P * e->S;
 	const size_t pat_stride = e->generic ? 1 : (size_t)e->S, state_stride = e->generic ? (size_t)e->Pp : 1;
+	const int *Ec = e->lower_form == LowerForm::CarriedExp2 ? (const int *)e->d_Ec : nullptr;
 	hipLaunchKernelGGL(k_root_invariant_term, dim3(nb), dim3(256), 0, e->stream, e->P, e->S, e->C, root, cat_stride, pat_stride, state_stride, e->d_freqs,
-	                   e->d_props, e->d_weights, e->d_inv_part);
+	                   e->d_props, e->d_weights, Ec, e->d_inv_part);
 	hipLaunchKernelGGL(k_reduce_rows, dim3(1), dim3(64), 0, e->stream, e->d_inv_part, nb, (const uint8_t *)nullptr, dst ? dst : e->d_inv_part + nb);
 	HIP_TRY(hipGetLastError());
 	return PHYAMD_OK;
@@ -375,7 +377,7 @@ int run_tiled(Shard *e, int mode, int flags) {
 		e->all_dirty = true;
 		if ((rc = mode == 0 ? run_lower(e, true) : run_gradient(e, flags, mode == 2))) return rc;
 		hipLaunchKernelGGL(k_accumulate, dim3((n + 255) / 256), dim3(256), 0, e->stream, n, e->d_result, e->d_total);
-		if (e->C >= 2) {  // the +I site-model gradient needs this tile's root partial while it is resident
+		if (e->C >= 2) {  // the +I site-model gradient needs this tile's root partial while it is resident (in the form it is in)
 			if ((rc = launch_root_invariant_term(e, nullptr))) return rc;
 			hipLaunchKernelGGL(k_accumulate, dim3(1), dim3(64), 0, e->stream, 1, e->d_inv_part + (e->P + 255) / 256, inv_total);
 		}

@@ -180,6 +180,8 @@ int launch_lower_walk(Shard *e) {
 bool lower_stream_applies(const Shard *e);
 int ensure_mask_stream(Shard *e);
 int ensure_optab(Shard *e);
+int ensure_exponent_storage(Shard *e);
+void free_exponent_storage(Shard *e);
 int launch_lower_stream(Shard *e);
 
 template <int WAVES>
@@ -190,7 +192,14 @@ int launch_lower_w(Shard *e) {
 		if (!rc && !e->d_Lc) rc = dev_alloc(e, &e->d_Lc, (size_t)e->C * e->P);  // per-category root terms for k_root_finish64
 		if (rc == PHYAMD_ENOMEM && e->cfg.max_device_bytes > 0) e->lstream_on = false;  // the cap leaves no room for the words
 		else if (rc) return rc;
-		else if (!e->stream_unsupported) return launch_lower_stream(e);
+		else if (!e->stream_unsupported) {
+			if (stream_lower_form(e) == LowerForm::CarriedExp2 && (rc = ensure_exponent_storage(e))) {
+				if (rc != PHYAMD_ENOMEM || e->cfg.max_device_bytes <= 0) return rc;
+				prefer_reference_form(e);  // the cap leaves no room for the exponents: the reference's rescaling from here on
+				free_exponent_storage(e);
+			}
+			if (lower_stream_applies(e)) return launch_lower_stream(e);
+		}
 	}
 	e->lower_form = LowerForm::Reference;
 	if (e->walking && !e->incremental_pass) return e->scaling_on ? launch_lower_walk<WAVES, true>(e) : launch_lower_walk<WAVES, false>(e);
@@ -302,6 +311,24 @@ int ensure_ints(Shard *e, int **p, size_t *have, size_t count) {
 	return rc;
 }
 
+// the exponents of the power-of-two rescaling (LowerForm::CarriedExp2), the pre-order walk's included: made before the post-order
+// pass that writes that form, so that a memory cap without room for them is met while the reference's form can still be written
+int ensure_exponent_storage(Shard *e) {
+	int rc;
+	if ((rc = ensure_ints(e, &e->d_lexp, &e->lexp_alloc, e->lower_alloc_cores * (size_t)e->C * e->P))) return rc;
+	if ((rc = ensure_ints(e, &e->d_uexp, &e->uexp_alloc, std::max(e->upper_alloc_slots, upper_slots_needed(e)) * e->C * e->P))) return rc;
+	if (!e->d_Ec && (rc = dev_alloc(e, &e->d_Ec, (size_t)e->C * e->P))) return rc;
+	if (!e->d_Eroot && (rc = dev_alloc(e, &e->d_Eroot, (size_t)e->P))) return rc;
+	return PHYAMD_OK;
+}
+void free_exponent_storage(Shard *e) {
+	dev_free(e, &e->d_lexp, e->lexp_alloc);
+	dev_free(e, &e->d_uexp, e->uexp_alloc);
+	e->lexp_alloc = e->uexp_alloc = 0;
+	dev_free(e, &e->d_Ec, (size_t)e->C * e->P);
+	dev_free(e, &e->d_Eroot, (size_t)e->P);
+}
+
 // the streamed post-order walk (k_lower4_stream): every cut subtree as workgroups of its own, then the top part with the root
 int launch_lower_stream(Shard *e) {
 	int rc;
@@ -317,11 +344,7 @@ int launch_lower_stream(Shard *e) {
 	const LowerForm form = stream_lower_form(e);
 	const StreamVariant v = stream_variant(form, e->scaling_on);
 	const bool exp2 = v.scale == 2, scale = v.scale == 1, tf = v.tf;
-	if (exp2) {
-		if ((rc = ensure_ints(e, &e->d_lexp, &e->lexp_alloc, e->lower_alloc_cores * (size_t)e->C * e->P))) return rc;
-		if (!e->d_Ec && (rc = dev_alloc(e, &e->d_Ec, (size_t)e->C * e->P))) return rc;
-		if (!e->d_Eroot && (rc = dev_alloc(e, &e->d_Eroot, (size_t)e->P))) return rc;
-	}
+	if (exp2 && (rc = ensure_exponent_storage(e))) return rc;
 	e->lower_form = form;
 	const int waves = scale ? e->C : STREAM_WAVES;
 	const size_t lds = (size_t)LSTREAM_LDS_PER_WAVE * waves + (scale ? sizeof(double) * 2 * e->C * WAVE : 0);

@@ -915,11 +915,15 @@ int upload_schedule(Shard *e) {
 	return PHYAMD_OK;
 }
 
-int ensure_upper_storage(Shard *e) {
-	// the tree-walk schedule parks far fewer uppers than the level schedule keeps; parameter-gradient and inspection
-	// calls still run the level kernels, so the larger of the two is held once either has been needed
+// the tree-walk schedule parks far fewer uppers than the level schedule keeps; parameter-gradient and inspection
+// calls still run the level kernels, so the larger of the two is held once either has been needed
+size_t upper_slots_needed(const Shard *e) {
 	const bool level_path = !e->walking || e->level_upper_needed;  // (20-state walks: both, they alternate with level passes)
-	const size_t need = (size_t)std::max(1, level_path ? std::max(e->upper_slots, e->walk_upper_slots) : e->walk_upper_slots);
+	return (size_t)std::max(1, level_path ? std::max(e->upper_slots, e->walk_upper_slots) : e->walk_upper_slots);
+}
+
+int ensure_upper_storage(Shard *e) {
+	const size_t need = upper_slots_needed(e);
 	if (e->d_upper && e->upper_alloc_slots >= need) return PHYAMD_OK;
 	dev_free(e, &e->d_upper, e->upper_alloc_slots * node_partial_doubles(e));
 	e->upper_alloc_slots = 0;

@@ -5,6 +5,9 @@
 // t_n = P_n p_n (their TF), unscaled or rescaled by powers of two per category (SCALE == 2)
 enum class LowerForm { Reference, Carried, CarriedExp2 };
 
+// schedule counts the pattern tiles are sized by (tile_working_set)
+struct ScheduleCounts { int core_count, upper_slots, widest; };
+
 struct Shard {
 	phyamd_config cfg{};
 	int T = 0, N = 0, P = 0, S = 0, C = 0, root = -1;
@@ -143,6 +146,8 @@ struct Shard {
 	int upper_slots = 0;
 	std::vector<int32_t> core_index;  // node -> index of its stored lower array (-1: tip or fused)
 	int core_count = 0;
+	ScheduleCounts scaled_counts{0, 0, 1};  // those of the schedule a lazy rescaling switch would build (have_scaled_counts)
+	bool have_scaled_counts = false;
 	bool fusion_enabled = true, fused = false;
 	std::vector<DeepDesc> deep_host;   // by node id (only DEEP nodes filled)
 	int deep_count = 0;

@@ -6,19 +6,41 @@
 // about half of the internal nodes' partials are stored (fringe / DEEP nodes are not), plus parked uppers; 20 / 60 / 61 states
 // -- every internal node's lower partial and the level schedule's uppers.  With a schedule (phyamd_set_topology) the real
 // counts: stored nodes, the upper slots either schedule may ask for, scale factors, the generic kernels' scratch, the
-// gradient slabs.  (A ladder-like tree stores twice what a random one does.)
-double tile_working_set(const Shard *e, double p, bool exact) {
+// gradient slabs.  (A ladder-like tree stores twice what a random one does.)  A 4-state engine that may rescale also holds the
+// streamed walks' power-of-two exponents: one int per (stored lower or upper slot, category, pattern), plus the root's per
+// category and per pattern (d_lexp, d_uexp, d_Ec, d_Eroot; ensure_exponent_storage).
+// the counts of the schedule the tiles must hold (ScheduleCounts: the current one's, or those of the schedule a lazy switch builds)
+ScheduleCounts schedule_counts(const Shard *e) {
+	ScheduleCounts c{e->core_count, std::max(e->upper_slots, e->walk_upper_slots), 1};
+	for (size_t i = 0; i + 1 < e->lower_level_off.size(); i++) c.widest = std::max(c.widest, e->lower_level_off[i + 1] - e->lower_level_off[i]);
+	for (size_t i = 0; i + 1 < e->upper_level_off.size(); i++) c.widest = std::max(c.widest, e->upper_level_off[i + 1] - e->upper_level_off[i]);
+	return c;
+}
+
+double tile_working_set(const Shard *e, double p, bool exact, const ScheduleCounts &k) {
 	const double pp = e->S == 4 ? p : std::ceil(p / 16.0) * 16.0, npd = (double)e->C * e->S * pp;
 	const double per_pattern = (double)e->T * p + 8.0 * p * (3.0 + (e->S == 4 ? 0.0 : (double)e->C));
-	if (!exact) return 8.0 * ((e->S == 4 ? 0.5 : 1.6) * (double)(e->N - e->T) * npd + 2.0 * npd) + per_pattern;
-	const bool may_scale = e->cfg.rescale != PHYAMD_RESCALE_NEVER;
-	int widest = 1;
-	for (size_t i = 0; i + 1 < e->lower_level_off.size(); i++) widest = std::max(widest, e->lower_level_off[i + 1] - e->lower_level_off[i]);
-	for (size_t i = 0; i + 1 < e->upper_level_off.size(); i++) widest = std::max(widest, e->upper_level_off[i + 1] - e->upper_level_off[i]);
-	double doubles = (double)(std::max(1, e->core_count) + std::max(1, std::max(e->upper_slots, e->walk_upper_slots))) * npd;
-	if (may_scale) doubles += (double)std::max(1, e->core_count) * p + (e->S == 4 ? 0.0 : 5.0 * widest * e->C * p);
+	const bool may_scale = e->cfg.rescale != PHYAMD_RESCALE_NEVER, exponents = may_scale && e->S == 4 && e->exp2_on;
+	if (!exact) return 8.0 * (exponents ? 1.125 : 1.0) * ((e->S == 4 ? 0.5 : 1.6) * (double)(e->N - e->T) * npd + 2.0 * npd) + per_pattern;
+	double doubles = (double)(std::max(1, k.core_count) + std::max(1, k.upper_slots)) * npd;
+	if (may_scale) doubles += (double)std::max(1, k.core_count) * p + (e->S == 4 ? 0.0 : 5.0 * k.widest * e->C * p);
+	if (exponents) doubles += 0.5 * ((double)(std::max(1, k.core_count) + std::max(1, k.upper_slots) + 1) * e->C * p + p);
+	if (e->S == 4) doubles += (double)e->C * p;  // the streamed post-order walk's per-category root terms (d_Lc)
 	doubles += (double)e->N * e->C * (p / (WAVE * std::max(1, 4 / e->C)) + 1.0);  // gradient slabs, one entry per wave group
 	return 8.0 * doubles + per_pattern;
+}
+
+// the larger of the working sets of the current schedule and, if a lazy switch may still replace it, of the rescaled one
+double tile_working_set(const Shard *e, double p, bool exact) {
+	const double now = tile_working_set(e, p, exact, schedule_counts(e));
+	return e->have_scaled_counts ? std::max(now, tile_working_set(e, p, exact, e->scaled_counts)) : now;
+}
+
+// buffers the 4-state walks make on demand whose size does not follow the tile (whether or not the engine may rescale): the streamed walks' table blocks ([C][ops], ops < N)
+// and the pre-order walk's per-op scratch (d_oct: 8 C R doubles, R < N).  What is held already counts in device_bytes.
+double walk_reserve(const Shard *e) {
+	if (e->S != 4) return 0.0;
+	return std::max(0.0, (double)e->N * e->C * OPBLK_BYTES - (double)e->optab_alloc) + std::max(0.0, 8.0 * (8.0 * e->C * e->N - (double)e->oct_alloc));
 }
 
 // tiles / patterns per tile for the cap (the caller's max_device_bytes, else most of what the device has free right now, so that
@@ -28,12 +50,14 @@ int choose_tiles(Shard *e, bool exact) {
 	const bool automatic = e->cfg.max_device_bytes <= 0;
 	// what this engine holds now in buffers sized by the tile (they are dropped and re-made if the tile size changes)
 	const double tile_sized = (double)e->pattern_bytes + 8.0 * ((double)(e->lower_alloc_cores + e->upper_alloc_slots) * (double)node_partial_doubles(e) +
-	                                                            (e->d_lscale ? (double)e->lower_alloc_cores * e->P : 0.0));
+	                                                            (e->d_lscale ? (double)e->lower_alloc_cores * e->P : 0.0)) +
+	                          4.0 * ((double)(e->lexp_alloc + e->uexp_alloc) + (e->d_Ec ? (double)e->C * e->P : 0.0) + (e->d_Eroot ? (double)e->P : 0.0)) +
+	                          (e->S == 4 && e->d_Lc ? 8.0 * e->C * e->P : 0.0);
 	if (automatic) {
 		size_t free_bytes = 0, total_bytes = 0;
 		cap = hipMemGetInfo(&free_bytes, &total_bytes) == hipSuccess ? 0.92 * ((double)free_bytes + tile_sized) : 0.0;
 	} else
-		cap -= (double)e->device_bytes - tile_sized + 65536.0;  // resident whatever the tile size, and small buffers made on demand
+		cap -= (double)e->device_bytes - tile_sized + 65536.0 + walk_reserve(e);  // resident whatever the tile size, and buffers made on demand
 	if (!automatic && cap <= 0)
 		return fail(PHYAMD_ENOMEM, "max_device_bytes (%lld) does not even hold what is resident whatever the tile size (%lld bytes)",
 		            (long long)e->cfg.max_device_bytes, (long long)(e->device_bytes - (int64_t)tile_sized));
@@ -90,6 +114,7 @@ int allocate_pattern_storage(Shard *e) {
 	e->lnl_part_alloc = (size_t)std::max(std::max(std::max(e->nblk, e->nblk_lower), (e->nblk_walk_upper + 2) * e->G), e->nblk_root);  // (walk: one entry per 64 patterns)
 	if ((rc = dev_alloc(e, &e->d_lnl_part, e->lnl_part_alloc))) return rc;
 	if (e->generic && (rc = dev_alloc(e, &e->d_Lc, (size_t)e->C * e->P))) return rc;
+	if (e->C >= 2 && (rc = dev_alloc(e, &e->d_inv_part, (size_t)(e->P + 255) / 256 + 1))) return rc;  // (the +I root term: held like the lnL slab)
 	e->gpart_row = (size_t)std::max(e->nblk, e->generic ? 0 : e->nblk_walk_upper * e->G);  // the tree-walk kernels write one entry per wave-group
 	if ((rc = dev_alloc(e, &e->d_gpart, (size_t)e->N * e->C * e->gpart_row))) return rc;
 	HIP_TRY(hipMemsetAsync(e->d_gpart, 0, sizeof(double) * (size_t)e->N * e->C * e->gpart_row, e->stream));
@@ -112,6 +137,7 @@ void free_pattern_storage(Shard *e) {
 	dev_free(e, &e->d_wl, (size_t)e->P);
 	dev_free(e, &e->d_lnl_part, e->lnl_part_alloc);
 	dev_free(e, &e->d_Lc, (size_t)e->C * e->P);
+	dev_free(e, &e->d_inv_part, (size_t)(e->P + 255) / 256 + 1);
 	dev_free(e, &e->d_Ec, (size_t)e->C * e->P);
 	dev_free(e, &e->d_Eroot, (size_t)e->P);
 	dev_free(e, &e->d_gpart, (size_t)e->N * e->C * e->gpart_row);
@@ -126,6 +152,9 @@ void free_pattern_storage(Shard *e) {
 	e->lower_alloc_cores = 0;
 	dev_free(e, &e->d_upper, e->upper_alloc_slots * npd);
 	e->upper_alloc_slots = 0;
+	dev_free(e, &e->d_lexp, e->lexp_alloc);
+	dev_free(e, &e->d_uexp, e->uexp_alloc);
+	e->lexp_alloc = e->uexp_alloc = 0;
 }
 
 void shard_destroy(Shard *e);
@@ -362,6 +391,17 @@ int shard_set_topology(Shard *e, const int32_t *left, const int32_t *right, int 
 		return code;
 	};
 	if ((rc = build_schedule(e))) return roll_back(rc);
+	e->have_scaled_counts = false;
+	if (e->generic && e->cfg.rescale == PHYAMD_RESCALE_AUTO && !e->scaling_on) {
+		// the lazy switch rebuilds the 20 / 60 / 61-state schedule without fringe fusion or tree walk (more stored nodes and upper
+		// slots): the tiles are sized for that schedule too, so that the switch never needs more than the cap
+		e->scaling_on = true;
+		rc = build_schedule(e);
+		if (!rc) e->scaled_counts = schedule_counts(e);
+		e->scaling_on = false;
+		if (rc || (rc = build_schedule(e))) return roll_back(rc);
+		e->have_scaled_counts = true;
+	}
 	{
 		// now that the tree is known the tile size follows its real storage needs (a ladder-like tree stores twice what the
 		// estimate of phyamd_create assumed): possible as long as no tip data or weights sit in buffers of the old tile size
@@ -948,12 +988,12 @@ int shard_root_invariant_term(Shard *e, double *out) {
 	int rc;
 	if ((rc = bind_device(e))) return rc;
 	if ((rc = check_ready(e))) return rc;
-	if (e->scaling_on && (rc = require_reference_form(e))) return rc;  // (see shard_root_frequency_term)
 	const double *src;
-	if (e->tiles > 1) {  // summed over the tiles by the last evaluation (one entry behind everything else in the total)
+	if (e->tiles > 1) {  // summed over the tiles by the last evaluation (one entry behind everything else in the total), each tile in its own form
 		if (!e->tiled_eval_done) return fail(PHYAMD_EINVAL, "no evaluation has been run yet");
 		src = e->d_total + (size_t)e->N * e->C + 2 * PHYAMD_MAX_PARAMETERS;
 	} else {
+		if (e->scaling_on && (rc = require_reference_form(e))) return rc;  // (see shard_root_frequency_term)
 		if (!e->lower_valid || e->force_root || e->core_index.empty() || e->core_index[e->root] < 0 || !e->d_lower) return fail(PHYAMD_EINVAL, "no evaluation has been run yet");
 		if ((rc = launch_root_invariant_term(e, nullptr))) return rc;
 		src = e->d_inv_part + (e->P + 255) / 256;

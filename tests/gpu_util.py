@@ -31,8 +31,9 @@ def engine_from_problem(pb, rescale=2, tip_mode="states", **kw):
     return e
 
 
-def random_problem(T, P, C, seed, S=4, shape="random", gaps=0.0, bl=(0.01, 0.1), rescale=0, **kw):
-    """Seeded synthetic problem (oracle Problem object) with a GTR-like reversible model."""
+def random_problem(T, P, C, seed, S=4, shape="random", gaps=0.0, bl=(0.01, 0.1), rescale=0, pinv=None, **kw):
+    """Seeded synthetic problem (oracle Problem object) with a GTR-like reversible model.  pinv: category 0 is an invariant
+    class (rate 0) of that proportion, the other C - 1 categories share the rest equally; the mean rate is 1 either way."""
     from oracle import phyoracle as po
     from physher_amd import synth
     from golden_util import reversible_eigen
@@ -46,8 +47,14 @@ def random_problem(T, P, C, seed, S=4, shape="random", gaps=0.0, bl=(0.01, 0.1),
     r = rng.uniform(0.5, 3.0, size=(S, S))
     r = 0.5 * (r + r.T)
     ev, U, Ui = reversible_eigen(r, freqs)
-    rates = np.sort(rng.gamma(0.5, 2.0, size=C)) + 0.05
-    props = np.full(C, 1.0 / C)
+    if pinv is None:
+        rates = np.sort(rng.gamma(0.5, 2.0, size=C)) + 0.05
+        props = np.full(C, 1.0 / C)
+    else:
+        if C < 2:
+            raise ValueError("an invariant class needs at least two categories")
+        rates = np.concatenate([[0.0], np.sort(rng.gamma(0.5, 2.0, size=C - 1)) + 0.05])
+        props = np.concatenate([[pinv], np.full(C - 1, (1.0 - pinv) / (C - 1))])
     rates = rates / (rates * props).sum()
     return po.Problem(tree.left, tree.right, tree.root, weights, ev, U, Ui, freqs, rates, props, tree.length,
                       tip_states=states, rescale=rescale, **kw)

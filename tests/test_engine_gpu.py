@@ -1130,6 +1130,8 @@ def test_pattern_tiling_under_a_memory_cap(S, T, P, C, rescale, shape):
             assert np.abs(cg - cg_ref).max() <= 1e-10 * max(1.0, np.abs(cg_ref).max())
             if C >= 2:  # the +I root term is summed over the tiles while each tile's root partial is resident
                 assert abs(e.root_invariant_term() - whole.root_invariant_term()) <= 1e-10 * max(1.0, abs(whole.root_invariant_term()))
+                term_ref = po.root_invariant_term(pb)
+                assert abs(e.root_invariant_term() - term_ref) <= 1e-10 * max(1.0, abs(term_ref))
             e.set_rate_matrix_derivatives(dQ)
             whole.set_rate_matrix_derivatives(dQ)
             if S == 4:
@@ -1293,6 +1295,9 @@ def test_root_terms_agree_between_rescaled_and_unscaled_evaluations():
         la, lb = a.log_likelihood(), b.log_likelihood()
         assert b.rescaling and abs(la - lb) <= 1e-11 * abs(la)
         assert abs(a.root_invariant_term() - b.root_invariant_term()) <= 1e-10 * max(1.0, abs(a.root_invariant_term()))
+        term_ref = po.root_invariant_term(pb)
+        for x in (a, b):
+            assert abs(x.root_invariant_term() - term_ref) <= 1e-10 * max(1.0, abs(term_ref))
         np.testing.assert_allclose(a.root_frequency_term(), b.root_frequency_term(), rtol=1e-10)
 
 

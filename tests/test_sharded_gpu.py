@@ -38,6 +38,8 @@ def test_sharded_engine_matches_oracle(S, T, P, C, n, rescale):
         np.testing.assert_allclose(bg, po.branch_gradient_from_cat(cg, pb.cat_rates, pb.cat_props), rtol=1e-13, atol=1e-13)
         if C >= 2:
             assert abs(e.root_invariant_term() - one.root_invariant_term()) <= 1e-10 * max(1.0, abs(one.root_invariant_term()))
+            term_ref = po.root_invariant_term(pb)
+            assert abs(e.root_invariant_term() - term_ref) <= 1e-10 * max(1.0, abs(term_ref))
         np.testing.assert_allclose(e.root_frequency_term(), po.root_frequency_term(pb), rtol=1e-9)
         # the optimiser's fast path: sums over patterns, shard by shard
         node = T + 1 if T + 1 != pb.root else T
