@@ -216,6 +216,22 @@ int phyamd_root_frequency_term(phyamd_engine *e, double *out /* [S] */);
  * branch" (optimizer.c:116-150) costs a path per branch, not a sweep.  Any of lnl / d1 / d2 may be NULL.  The engine's branch
  * lengths are not changed by this call. */
 int phyamd_branch_log_likelihood(phyamd_engine *e, int node, double length, double *lnl, double *d1, double *d2);
+/* lnL, and for every node n != root the exact first and second derivative of lnL in t_n:
+ *   d1[n] = sum_k w_k L'_k / L_k,   d2[n] = sum_k w_k (L''_k / L_k - (L'_k / L_k)^2),
+ *   L'_k = sum_c w_c r_c sum_i pi_i u_i (Q P_c p)_i,   L''_k = sum_c w_c r_c^2 sum_i pi_i u_i (Q Q P_c p)_i
+ * with r_c the category rates the matrices were built with (P_c = exp(Q t r_c)), u the branch's upper partial and p its lower.
+ * This is _singleTreeLikelihood_d2logP / d2lnldt2_uppper (treelikelihood.c:469-530, 2267-2335) for all branches at once: row n
+ * is what phyamd_branch_log_likelihood(e, n, t_n, ...) returns as d1 and d2, from ONE post-order and ONE pre-order pass instead
+ * of a path walk per branch -- the diagonal physher's Laplace approximations (laplace.c:102, 207, 347, 489, 579, 717), its
+ * Hessian (hessian.c:14-25) and Newton-type branch optimisers ask for.  Root row 0 (no row is zeroed for unrooted trees: that
+ * rule is the caller's epilogue, as for phyamd_gradient).  [2T-1] each; d1 may be NULL.  flags: 0 (others reserved, refused).
+ * NaN/inf lnL => all-NaN d1, d2.  Branch lengths are not changed, and later evaluations give what they would have given
+ * without this call.  Every state count, rescaling policy, tiled patterns and shards.  Needs the eigen system; refused with
+ * PHYAMD_EUNSUPPORTED: explicit node matrices (Q P, Q Q P are the derivatives of exp(Q t r) only), more than 8 categories with
+ * 4 states, a zero frequency with 20 / 60 / 61 states. */
+int phyamd_branch_hessian_diagonal(phyamd_engine *e, int flags, double *lnl, double *d1, double *d2);
+/* device-resident form for sharding: [lnL | d1[2T-1] | d2[2T-1]], sums over this engine's patterns, no host sync */
+int phyamd_branch_hessian_diagonal_device(phyamd_engine *e, int flags, double *device_out);
 int phyamd_synchronize(phyamd_engine *e);
 
 /* --- inspection (parity tests, debugging) --- */

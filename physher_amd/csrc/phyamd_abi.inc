@@ -444,6 +444,28 @@ int phyamd_branch_log_likelihood(phyamd_engine *g, int node, double length, doub
 	return PHYAMD_OK;
 }
 
+int phyamd_branch_hessian_diagonal(phyamd_engine *g, int flags, double *lnl, double *d1, double *d2) {
+	CHECK_GROUP(g);
+	if (!lnl || !d2) return fail(PHYAMD_EINVAL, "null lnl or d2");
+	const size_t n = (size_t)1 + 2 * g->N;
+	ensure_scratch(g, n);
+	std::vector<double> total(n);
+	int rc;
+	if (group_size(g) == 1) {
+		if ((rc = shard_branch_hessian_diagonal(g->shards[0], flags, total.data()))) return rc;
+	} else {
+		// per-shard sums added like the gradient's: 2 / 4 / 8 shards cut by the engine's bisection give the one-engine bits
+		if ((rc = for_shards(g, [&](Shard *s, int i) { return shard_branch_hessian_diagonal(s, flags, g->scratch[i].data()); }))) return rc;
+		sum_shards(g, n, total.data());
+		if (std::isnan(total[0]) || std::isinf(total[0]))
+			for (size_t i = 1; i < n; i++) total[i] = NAN;
+	}
+	*lnl = total[0];
+	if (d1) std::memcpy(d1, total.data() + 1, sizeof(double) * g->N);
+	std::memcpy(d2, total.data() + 1 + g->N, sizeof(double) * g->N);
+	return PHYAMD_OK;
+}
+
 // device-resident results (one process per GPU: the caller reduces them across processes with ONE RCCL all-reduce)
 int phyamd_log_likelihood_device(phyamd_engine *g, double *device_out) {
 	CHECK_GROUP(g);
@@ -459,6 +481,12 @@ int phyamd_parameter_gradient_device(phyamd_engine *g, int flags, double *device
 	CHECK_GROUP(g);
 	SINGLE_DEVICE_ONLY(g, "phyamd_parameter_gradient_device");
 	return shard_parameter_gradient_device(g->shards[0], flags, device_out);
+}
+
+int phyamd_branch_hessian_diagonal_device(phyamd_engine *g, int flags, double *device_out) {
+	CHECK_GROUP(g);
+	SINGLE_DEVICE_ONLY(g, "phyamd_branch_hessian_diagonal_device");
+	return shard_branch_hessian_diagonal_device(g->shards[0], flags, device_out);
 }
 
 // --- inspection ---------------------------------------------------------------------------------------------------

@@ -348,6 +348,52 @@ int run_gradient(Shard *e, int flags, bool with_params = false) {
 	return again ? run_gradient(e, flags, with_params) : PHYAMD_OK;
 }
 
+// Every branch's d lnL / dt and d2 lnL / dt2 (phyamd_branch_hessian_diagonal): raw sums [lnL | d1 | d2] over this engine's patterns
+// (or tile) to out.  The HESS pass reads the stored lowers in the reference's form; unlike the other readers this call does not
+// keep the engine on that form: an engine whose streamed walks store another one recomputes its lowers in that form at the next
+// evaluation, so lnL and gradients afterwards are those of an engine that never made the call.
+int run_hessian(Shard *e, double *out) {
+	int rc;
+	if ((rc = bind_device(e))) return rc;
+	const bool form_only = e->reference_form_only;
+	e->reference_form_only = true;
+	// 20 states fuse cherries into their parents' ops, which leaves their tip branches without rows: the unfused schedule for this
+	// call, the fused one again afterwards (rebuild_schedule: the next evaluation recomputes every node, as a new engine would)
+	const bool unfuse = e->generic && e->fused;
+	if (unfuse) {
+		e->fusion_enabled = false;
+		rc = rebuild_schedule(e);
+	}
+	if (!rc) rc = run_lower(e, 1);
+	if (!rc) rc = require_reference_form(e);
+	if (!rc) {
+		e->level_upper_needed = true;
+		if (!(rc = ensure_upper_storage(e)) && !(rc = ensure_hess_storage(e))) rc = launch_hess(e, out);
+	}
+	if (unfuse) {
+		e->fusion_enabled = true;
+		const int rc2 = rebuild_schedule(e);
+		if (!rc) rc = rc2;
+	}
+	e->upper_valid = false;  // (the level pass's uppers: not those a keep-partials gradient leaves)
+	if (!form_only) {
+		e->reference_form_only = false;
+		if (e->lower_form != stream_lower_form(e)) {
+			e->lower_valid = false;
+			e->all_dirty = true;
+		}
+	}
+	return rc;
+}
+
+// [lnL | d1[N] | d2[N]]: a NaN / inf lnL makes every derivative NaN (treelikelihood.c:327-332)
+__global__ void k_hess_finish(int n, double *__restrict__ v) {
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const double l = v[0];
+	if (isnan(l) || isinf(l)) v[1 + i] = NAN;
+}
+
 __global__ void k_accumulate(int n, const double *__restrict__ src, double *__restrict__ dst) {
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i < n) dst[i] += src[i];
@@ -355,12 +401,15 @@ __global__ void k_accumulate(int n, const double *__restrict__ src, double *__re
 
 // One evaluation = every tile in turn through the same partial storage; the per-tile results ([lnL | gradient rows | parameter
 // sums | root frequency term]: all of them sums over patterns) are added in tile order (fixed: reproducible).
-// mode 0: post-order pass only; 1: + pre-order pass and branch gradient; 2: + substitution-parameter sums
+// mode 0: post-order pass only; 1: + pre-order pass and branch gradient; 2: + substitution-parameter sums; 3: the HESS pass
+// ([lnL | d1 | d2] in hess_result instead of d_result)
 int run_tiled(Shard *e, int mode, int flags) {
 	int rc;
 	if ((rc = bind_device(e))) return rc;
-	const int n = mode == 0 ? 1 : 1 + e->N * e->C + (mode == 2 ? e->np + e->S : 0);
-	HIP_TRY(hipMemsetAsync(e->d_total, 0, sizeof(double) * n, e->stream));
+	if (mode == 3 && (rc = ensure_hess_storage(e))) return rc;
+	const int n = mode == 0 ? 1 : mode == 3 ? 1 + 2 * e->N : 1 + e->N * e->C + (mode == 2 ? e->np + e->S : 0);
+	double *result = mode == 3 ? hess_result(e) : e->d_result, *total = mode == 3 ? hess_total(e) : e->d_total;
+	HIP_TRY(hipMemsetAsync(total, 0, sizeof(double) * n, e->stream));
 	double *inv_total = e->d_total + (size_t)e->N * e->C + 2 * PHYAMD_MAX_PARAMETERS;  // the last entry of the allocation: the +I root term
 	HIP_TRY(hipMemsetAsync(inv_total, 0, sizeof(double), e->stream));
 	const uint8_t unknown = e->generic ? (uint8_t)e->S : (uint8_t)0xF;
@@ -375,8 +424,8 @@ int run_tiled(Shard *e, int mode, int flags) {
 			HIP_TRY(hipMemsetAsync(e->d_weights + w, 0, sizeof(double) * ((size_t)e->P - w), e->stream));
 		}
 		e->all_dirty = true;
-		if ((rc = mode == 0 ? run_lower(e, true) : run_gradient(e, flags, mode == 2))) return rc;
-		hipLaunchKernelGGL(k_accumulate, dim3((n + 255) / 256), dim3(256), 0, e->stream, n, e->d_result, e->d_total);
+		if ((rc = mode == 0 ? run_lower(e, true) : mode == 3 ? run_hessian(e, result) : run_gradient(e, flags, mode == 2))) return rc;
+		hipLaunchKernelGGL(k_accumulate, dim3((n + 255) / 256), dim3(256), 0, e->stream, n, result, total);
 		if (e->C >= 2) {  // the +I site-model gradient needs this tile's root partial while it is resident (in the form it is in)
 			if ((rc = launch_root_invariant_term(e, nullptr))) return rc;
 			hipLaunchKernelGGL(k_accumulate, dim3(1), dim3(64), 0, e->stream, 1, e->d_inv_part + (e->P + 255) / 256, inv_total);
@@ -384,7 +433,7 @@ int run_tiled(Shard *e, int mode, int flags) {
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipMemcpyAsync(e->d_plk_all + off, e->d_plk, sizeof(double) * w, hipMemcpyDeviceToDevice, e->stream));
 	}
-	HIP_TRY(hipMemcpyAsync(e->d_result, e->d_total, sizeof(double) * n, hipMemcpyDeviceToDevice, e->stream));
+	HIP_TRY(hipMemcpyAsync(result, total, sizeof(double) * n, hipMemcpyDeviceToDevice, e->stream));
 	e->tiled_root_term = mode == 2;
 	e->tiled_eval_done = true;
 	e->lower_valid = false;  // the resident partials are those of the last tile only
@@ -394,6 +443,15 @@ int run_tiled(Shard *e, int mode, int flags) {
 }
 
 int eval_lower(Shard *e) { return e->tiles > 1 ? run_tiled(e, 0, 0) : run_lower(e, true); }
+// [lnL | d1 | d2] in hess_result(e), the NaN rule applied
+int eval_hessian(Shard *e) {
+	int rc;
+	if ((rc = bind_device(e)) || (rc = ensure_hess_storage(e))) return rc;
+	if ((rc = e->tiles > 1 ? run_tiled(e, 3, 0) : run_hessian(e, hess_result(e)))) return rc;
+	hipLaunchKernelGGL(k_hess_finish, dim3((2 * e->N + 255) / 256), dim3(256), 0, e->stream, 2 * e->N, hess_result(e));
+	HIP_TRY(hipGetLastError());
+	return PHYAMD_OK;
+}
 int eval_gradient(Shard *e, int flags, bool with_params = false) {
 	return e->tiles > 1 ? run_tiled(e, with_params ? 2 : 1, flags) : run_gradient(e, flags, with_params);
 }

@@ -338,6 +338,19 @@ __device__ __forceinline__ void load_state_weights(const double *__restrict__ w,
 		}
 }
 
+// f[i] *= w[i] in the state layout of load_state_weights (padding states stay 0)
+template <int RT>
+__device__ __forceinline__ void scale_by_states(const double *__restrict__ w, int S, f64x4 (&f)[RT]) {
+	const int lane = threadIdx.x & 63;
+#pragma unroll
+	for (int t = 0; t < RT; t++)
+#pragma unroll
+		for (int r = 0; r < 4; r++) {
+			const int i = 16 * t + 4 * r + (lane >> 4);
+			f[t][r] = i < S ? f[t][r] * w[i] : 0.0;
+		}
+}
+
 // ---- post-order level: grid (pattern blocks, nodes of the level, categories) ---------------------------------
 // WHAT IS STORED for 20 / 60 / 61 states: node n at lower + core(n) * C*S*Pp holds  t_n = P_n . p_n,  its partial already carried
 // through its own branch (the root, which has no branch, holds p_root itself).  A parent forms p = t_l o t_r without a product for
@@ -514,6 +527,45 @@ __global__ __launch_bounds__(256) void k_scaled_gradient_gen(const NodeOp *__res
 	}
 }
 
+// HESS rows of one pre-order level -> the Hessian slab: per pattern D = sum_c w_c den_c, A = sum_c w_c r_c num_c,
+// B = sum_c w_c r_c^2 num2_c (the branch's units cancel in both ratios), and per workgroup the sums of w_k A / D and
+// w_k (B / D - (A / D)^2) of both children.  Workgroup x takes the 64-pattern blocks [hwg[2x], hwg[2x + 1]) like the 4-state pass,
+// so the slab does not depend on the shard count.  nd: [op][5][c][pat]; hpart: [workgroup][2 N].
+__global__ __launch_bounds__(256) void k_hess_gen(const NodeOp *__restrict__ ops, int P, int C, int N, const double *__restrict__ nd,
+                                                 const double *__restrict__ weights, const double *__restrict__ props, const double *__restrict__ rates,
+                                                 const int *__restrict__ hwg, double *__restrict__ hpart) {
+	__shared__ double red[4][4];
+	const NodeOp op = ops[blockIdx.y];
+	const double *base = nd + (size_t)blockIdx.y * 5 * C * P;
+	const int k0 = hwg[2 * blockIdx.x] * 64, k1 = min(P, hwg[2 * blockIdx.x + 1] * 64);
+	double acc[4] = {0.0, 0.0, 0.0, 0.0};  // d1_l, d1_r, d2_l, d2_r
+	for (int k = k0 + threadIdx.x; k < k1; k += 256) {
+		double D = 0.0, Al = 0.0, Ar = 0.0, Bl = 0.0, Br = 0.0;
+		for (int c = 0; c < C; c++) {
+			const double w = props[c], wr = w * rates[c], wr2 = wr * rates[c];
+			D += w * base[((size_t)2 * C + c) * P + k];
+			Al += wr * base[(size_t)c * P + k];
+			Ar += wr * base[((size_t)C + c) * P + k];
+			Bl += wr2 * base[((size_t)3 * C + c) * P + k];
+			Br += wr2 * base[((size_t)4 * C + c) * P + k];
+		}
+		const double w = weights[k], al = Al / D, ar = Ar / D;
+		acc[0] += w * al;
+		acc[1] += w * ar;
+		acc[2] += w * (Bl / D - al * al);
+		acc[3] += w * (Br / D - ar * ar);
+	}
+	for (int j = 0; j < 4; j++) {
+		const double s = wave_sum(acc[j]);
+		if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][j] = s;
+	}
+	__syncthreads();
+	if (threadIdx.x < 4) {
+		const int j = threadIdx.x, node = (j & 1) ? op.right : op.left;
+		hpart[(size_t)blockIdx.x * 2 * N + (j >> 1) * N + node] = (red[0][j] + red[1][j]) + (red[2][j] + red[3][j]);
+	}
+}
+
 // lnL_k = log sum_c Lc[c][k] (+ the root's cumulative log scale factor), w_k / L_k, and the fixed-order partial sums of
 // w_k lnL_k (treelikelihood.c:1473-1487)
 __global__ __launch_bounds__(256) void k_root_finish(int P, int C, const double *__restrict__ Lc, const double *__restrict__ weights,
@@ -584,17 +636,25 @@ __device__ __forceinline__ void cherry_gradient(const double *imgY, const double
 	g1 += wl * s1;
 }
 
-template <int RT, int KT, bool FOLD, bool SCALE>
-__global__ __launch_bounds__(GenGeo<RT>::WAVES * 64, GenGeo<RT>::MIN_WAVES_PER_SIMD) void k_upper_gen(const NodeOp *__restrict__ ops, int T, int P, int Pp_arg, int C,
+// HESS (phyamd_branch_hessian_diagonal): rows in every evaluation, rescaled or not, and two more per op:
+// nd[op][num_l, num_r, den, num2_l, num2_r][c][pat], num2 = sum_i u_i (Qf Q b)_i, formed as Qf (diag(1 / pi) (Qf b)) with the
+// Qf b the gradient term has just formed and the staged image of Qf (invf = 1 / pi; no fifth image: a 60 / 61-state one does not
+// fit next to the four in LDS).  Unfused schedules only; k_hess_gen mixes the categories.  No occupancy bound: at 61 states the
+// second product does not fit in the two-waves-per-SIMD register budget.
+template <int RT, int KT, bool FOLD, bool SCALE, bool HESS>
+__global__ __launch_bounds__(GenGeo<RT>::WAVES * 64, HESS ? 1 : GenGeo<RT>::MIN_WAVES_PER_SIMD) void k_upper_gen(const NodeOp *__restrict__ ops, int T, int P, int Pp_arg, int C,
                                                             const uint8_t *__restrict__ tipcode, const unsigned long long *__restrict__ tipsets,
                                                             const double *__restrict__ lower, double *__restrict__ upper, const double *__restrict__ mats,
                                                             const double *__restrict__ Qf, const double *__restrict__ freqs,
                                                             const double *__restrict__ w_over_L, double *__restrict__ gpart, int nblk,
-                                                            double *__restrict__ nd, double *__restrict__ mxu, int tiles, const double *__restrict__ qp) {
+                                                            double *__restrict__ nd, double *__restrict__ mxu, int tiles, const double *__restrict__ qp,
+                                                            const double *__restrict__ invf) {
+	static_assert(!HESS || !FOLD, "the Hessian variant is the reference's unfolded arithmetic");
 	extern __shared__ double sh[];
 	using Img = MatImage<RT, KT>;
 	constexpr int S = GenStates<RT, KT>::S, WV = GenGeo<RT>::WAVES, NIMG = GenFuse<RT>::UPPER_IMAGES;
-	constexpr bool FUSE = GenFuse<RT>::ON && !SCALE;  // (rescaled evaluations run the unfused schedule)
+	constexpr bool FUSE = GenFuse<RT>::ON && !SCALE && !HESS;  // (rescaled evaluations and the Hessian run the unfused schedule)
+	constexpr bool ROWS = SCALE || HESS;  // per-pattern rows instead of per-lane sums
 	const NodeOp op = ops[blockIdx.y];
 	const int c = blockIdx.z, lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 	const bool ltip = op.left < T, rtip = op.right < T, proot = op.upper_slot_parent < 0;
@@ -684,9 +744,9 @@ __global__ __launch_bounds__(GenGeo<RT>::WAVES * 64, GenGeo<RT>::MIN_WAVES_PER_S
 				b_as_d<RT, KT>(f0, br);
 			}
 		}
-		const double wl = (!SCALE && ta.ok) ? w_over_L[pat] : 0.0;
-		const size_t ndo = ((size_t)blockIdx.y * 3 * C + c) * P + pat, mxo = ((size_t)blockIdx.y * 2 * C + c) * P + pat;
-		if (SCALE) {
+		const double wl = (!ROWS && ta.ok) ? w_over_L[pat] : 0.0;
+		const size_t ndo = ((size_t)blockIdx.y * (HESS ? 5 : 3) * C + c) * P + pat, mxo = ((size_t)blockIdx.y * 2 * C + c) * P + pat;
+		if (ROWS) {
 			load_state_weights<RT>(freqs, S, FOLD, tmp);  // weights of the state sum: 1 if pi is folded into the uppers
 #pragma unroll
 			for (int t = 0; t < RT; t++) tmp[t] = tmp[t] * a[t] * bl[t] * br[t];
@@ -711,14 +771,27 @@ __global__ __launch_bounds__(GenGeo<RT>::WAVES * 64, GenGeo<RT>::MIN_WAVES_PER_S
 			sl += (m[0] + m[1]) + (m[2] + m[3]);
 			if (SCALE) mxl = fmax(mxl, fmax(fmax(u[0], u[1]), fmax(u[2], u[3])));
 		}
-		if (SCALE) {
-			const double num = lanes_sum16(sl), m = lanes_max16(mxl);
+		if (ROWS) {
+			const double num = lanes_sum16(sl), m = SCALE ? lanes_max16(mxl) : 0.0;
 			if (ta.ok && lane < 16) {
 				nd[ndo] = num;
-				mxu[mxo] = m;
+				if (SCALE) mxu[mxo] = m;
 			}
 		} else
 			gl += wl * sl;
+		if (HESS) {  // num2_l = sum_i u_l,i (Qf Q bl)_i; tmp still holds Qf bl
+			scale_by_states<RT>(invf, S, tmp);  // diag(1 / pi) Qf b = Q b, in place (registers are short at 61 states)
+			d_as_b<RT, KT>(tmp, frag);
+			mfma_matvec<RT, KT>(imgQ, frag, tmp);
+			double s2 = 0.0;
+#pragma unroll
+			for (int t = 0; t < RT; t++) {
+				const f64x4 m = tmp[t] * (a[t] * br[t]);
+				s2 += (m[0] + m[1]) + (m[2] + m[3]);
+			}
+			const double num2 = lanes_sum16(s2);
+			if (ta.ok && lane < 16) nd[ndo + (size_t)3 * C * P] = num2;
+		}
 		// right child
 		if (QP && rtip) tip_matvec<RT, KT>(imgQR0, S, cr0, tipsets, tmp);
 		else {
@@ -735,20 +808,33 @@ __global__ __launch_bounds__(GenGeo<RT>::WAVES * 64, GenGeo<RT>::MIN_WAVES_PER_S
 			sr += (m[0] + m[1]) + (m[2] + m[3]);
 			if (SCALE) mxr = fmax(mxr, fmax(fmax(u[0], u[1]), fmax(u[2], u[3])));
 		}
-		if (SCALE) {
-			const double num = lanes_sum16(sr), m = lanes_max16(mxr);
+		if (ROWS) {
+			const double num = lanes_sum16(sr), m = SCALE ? lanes_max16(mxr) : 0.0;
 			if (ta.ok && lane < 16) {
 				nd[ndo + (size_t)C * P] = num;
-				mxu[mxo + (size_t)C * P] = m;
+				if (SCALE) mxu[mxo + (size_t)C * P] = m;
 			}
 		} else
 			gr += wl * sr;
+		if (HESS) {  // num2_r = sum_i u_r,i (Qf Q br)_i; tmp still holds Qf br
+			scale_by_states<RT>(invf, S, tmp);  // diag(1 / pi) Qf b = Q b, in place (registers are short at 61 states)
+			d_as_b<RT, KT>(tmp, frag);
+			mfma_matvec<RT, KT>(imgQ, frag, tmp);
+			double s2 = 0.0;
+#pragma unroll
+			for (int t = 0; t < RT; t++) {
+				const f64x4 m = tmp[t] * (a[t] * bl[t]);
+				s2 += (m[0] + m[1]) + (m[2] + m[3]);
+			}
+			const double num2 = lanes_sum16(s2);
+			if (ta.ok && lane < 16) nd[ndo + (size_t)4 * C * P] = num2;
+		}
 		if (FUSE) {
 			if (lch) cherry_gradient<RT, KT>(imgL, imgL0, imgL1, imgQ, uL, cl0, cl1, tipsets, wl, gl0, gl1, imgQL0, imgQL1);
 			if (rch) cherry_gradient<RT, KT>(imgR, imgR0, imgR1, imgQ, uR, cr0, cr1, tipsets, wl, gr0, gr1, imgQR0, imgQR1);
 		}
 	}
-	if (SCALE) return;  // k_scaled_gradient_gen finishes the gradient
+	if (ROWS) return;  // k_scaled_gradient_gen / k_hess_gen finish the branch terms
 	constexpr int NG = FUSE ? 6 : 2;
 	const double sums[6] = {wave_sum(gl), wave_sum(gr), FUSE ? wave_sum(gl0) : 0.0, FUSE ? wave_sum(gl1) : 0.0, FUSE ? wave_sum(gr0) : 0.0, FUSE ? wave_sum(gr1) : 0.0};
 	if (lane == 0) {

@@ -221,7 +221,7 @@ int launch_upper_levels(Shard *e, int p0 = 0, int pc = 0) {
 	const size_t lds = sizeof(double) * ((SCALE ? 6 * nw * WAVE : 0) + nw * nacc * WAVE + nw * nacc);
 	int rc;
 	if ((rc = check_reference_form(e, "k_upper4"))) return rc;
-	if ((rc = allow_big_lds(k_upper4<WAVES, SCALE, FOLD, COMPAT, PARAMS>, lds))) return rc;
+	if ((rc = allow_big_lds(k_upper4<WAVES, SCALE, FOLD, COMPAT, PARAMS, false>, lds))) return rc;
 	const int op_total = (int)e->upper_ops.size();
 	const double *dpm = PARAMS ? e->d_dpm + (size_t)p0 * e->N * e->C * 16 : nullptr;
 	const double *dptab = PARAMS ? e->d_dptab + (size_t)p0 * e->T * e->C * 64 : nullptr;
@@ -231,13 +231,106 @@ int launch_upper_levels(Shard *e, int p0 = 0, int pc = 0) {
 		if (cnt == 0) continue;
 		dim3 grid(e->nblk, cnt);
 		launched++;
-		hipLaunchKernelGGL((k_upper4<WAVES, SCALE, FOLD, COMPAT, PARAMS>), grid, block_dims(e), lds, e->stream, e->d_upper_ops + off, e->T, e->P, e->C,
+		hipLaunchKernelGGL((k_upper4<WAVES, SCALE, FOLD, COMPAT, PARAMS, false>), grid, block_dims(e), lds, e->stream, e->d_upper_ops + off, e->T, e->P, e->C,
 		                   e->d_tipmask, e->d_lower, e->d_upper, e->d_mats, e->d_tiptab, e->d_Q, e->d_freqs, e->d_props, e->d_weights, e->d_wl, e->d_gpart,
-		                   e->nblk, dpm, dptab, pc, e->N, ppart, off, op_total);
+		                   e->nblk, dpm, dptab, pc, e->N, ppart, off, op_total, (const double *)nullptr, (const int *)nullptr, (double *)nullptr);
 	}
 	HIP_TRY(hipGetLastError());
 	e->prof.upper_launches = launched;
 	return PHYAMD_OK;
+}
+
+// ---- every branch's first and second derivative (phyamd_branch_hessian_diagonal): the level pre-order pass, HESS form ----
+// LDS of one k_upper4<HESS> workgroup (C waves): the rescaled form's exchanges, the 2 NACC branch-term columns, 2 ceil(NACC / C)
+// accumulator columns and their lane sums
+void bisect_blocks(int lo, int hi, int levels, std::vector<int> &bounds);
+
+size_t hess_lds(const Shard *e) {
+	const size_t nw = (size_t)e->C, nacc = 2 * (size_t)((NACC + e->C - 1) / e->C);
+	return sizeof(double) * ((6 + 2 * NACC) * nw * WAVE + nw * nacc * WAVE + nw * nacc);
+}
+
+// Workgroups of the HESS pass: the canonical 64-pattern block range [0, ceil(P / 64)) is bisected like reduce_block_sums does, and
+// every segment is cut into workgroups of at most PPT_UPPER blocks from its own start.  A shard cut by the same bisection holds
+// whole segments with the same workgroups, so the slab entries, their segment sums and the pairwise additions on top are the
+// same whatever the shard count.  Device: d_hess_tab = [nwg][2] block ranges | [segments + 1] first workgroup of each segment;
+// d_hess = slab [nwg][2 N] | segment sums [8][2 N] | result [1 + 2 N] | tile total [1 + 2 N].
+int ensure_hess_storage(Shard *e) {
+	if (e->d_hess && e->hess_P == e->P && e->hess_levels == e->reduce_levels) return PHYAMD_OK;
+	const int nb = (e->P + WAVE - 1) / WAVE, segments = 1 << e->reduce_levels;
+	std::vector<int> bounds, wg, first;
+	bisect_blocks(0, nb, e->reduce_levels, bounds);
+	bounds.push_back(nb);
+	for (int o = 0; o < segments; o++) {
+		first.push_back((int)wg.size() / 2);
+		for (int b = bounds[o]; b < bounds[o + 1]; b += PPT_UPPER) {
+			wg.push_back(b);
+			wg.push_back(std::min(b + PPT_UPPER, bounds[o + 1]));
+		}
+	}
+	const int nwg = (int)wg.size() / 2;
+	first.push_back(nwg);
+	wg.insert(wg.end(), first.begin(), first.end());
+	dev_free(e, &e->d_hess_tab, e->hess_tab_alloc);
+	dev_free(e, &e->d_hess, e->hess_alloc);
+	e->hess_tab_alloc = e->hess_alloc = 0;
+	e->hess_P = -1;
+	int rc;
+	const size_t R = (size_t)2 * e->N, need = (size_t)nwg * R + 8 * R + 2 * (R + 1);
+	if ((rc = dev_alloc(e, &e->d_hess_tab, wg.size()))) return rc;
+	e->hess_tab_alloc = wg.size();
+	if ((rc = dev_alloc(e, &e->d_hess, need))) return rc;
+	e->hess_alloc = need;
+	HIP_TRY(hipMemcpyAsync(e->d_hess_tab, wg.data(), sizeof(int) * wg.size(), hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));  // (wg is a stack-lifetime buffer)
+	e->hess_nwg = nwg;
+	e->hess_P = e->P;
+	e->hess_levels = e->reduce_levels;
+	return PHYAMD_OK;
+}
+double *hess_result(const Shard *e) { return e->d_hess + (size_t)e->hess_nwg * 2 * e->N + (size_t)8 * 2 * e->N; }
+double *hess_total(const Shard *e) { return hess_result(e) + 1 + (size_t)2 * e->N; }
+
+// the HESS slab's segment sums, added pairwise (reduce_block_sums' order) -> out[1 ..], and lnL of the post-order pass -> out[0]
+int finish_hess_slab(Shard *e, double *out, int launched) {
+	const int R = 2 * e->N, segments = 1 << e->reduce_levels;
+	double *seg = e->d_hess + (size_t)e->hess_nwg * R;
+	hipLaunchKernelGGL(k_slab_segments, dim3((R + 31) / 32, 1, segments), dim3(256), 0, e->stream, e->d_hess, 1, R, (const int *)e->d_hess_tab + 2 * e->hess_nwg, seg);
+	hipLaunchKernelGGL(k_slab_finish, dim3((R + 255) / 256), dim3(256), 0, e->stream, seg, segments, 1, R, (const int *)nullptr, out + 1);
+	HIP_TRY(hipMemcpyAsync(out, e->d_result, sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+	HIP_TRY(hipGetLastError());
+	e->prof.upper_launches = launched;
+	return PHYAMD_OK;
+}
+
+// one HESS pre-order pass over the stored lowers (reference form) -> out[1 + 2 N] = [lnL | d1 | d2], sums over this engine's patterns
+template <int WAVES, bool SCALE>
+int launch_upper_hess(Shard *e, double *out) {
+	const int levels = (int)e->upper_level_off.size() - 1, R = 2 * e->N;
+	const size_t lds = hess_lds(e);
+	int rc;
+	if ((rc = check_reference_form(e, "k_upper4"))) return rc;
+	if ((rc = allow_big_lds(k_upper4<WAVES, SCALE, false, false, false, true>, lds))) return rc;
+	const int op_total = (int)e->upper_ops.size();
+	HIP_TRY(hipMemsetAsync(e->d_hess, 0, sizeof(double) * (size_t)e->hess_nwg * R, e->stream));  // (the root's entries stay zero)
+	int launched = 0;
+	for (int lv = 0; lv < levels; lv++) {
+		const int off = e->upper_level_off[lv], cnt = e->upper_level_off[lv + 1] - off;
+		if (cnt == 0 || e->hess_nwg == 0) continue;
+		launched++;
+		hipLaunchKernelGGL((k_upper4<WAVES, SCALE, false, false, false, true>), dim3(e->hess_nwg, cnt), dim3(WAVE, e->C, 1), lds, e->stream, e->d_upper_ops + off, e->T,
+		                   e->P, e->C, e->d_tipmask, e->d_lower, e->d_upper, e->d_mats, e->d_tiptab, e->d_Q, e->d_freqs, e->d_props, e->d_weights, e->d_wl,
+		                   (double *)nullptr, 0, (const double *)nullptr, (const double *)nullptr, 0, e->N, (double *)nullptr, off, op_total, e->d_rates,
+		                   (const int *)e->d_hess_tab, e->d_hess);
+	}
+	HIP_TRY(hipGetLastError());
+	return finish_hess_slab(e, out, launched);
+}
+
+int launch_hess4(Shard *e, double *out) {
+	const int waves = e->C;
+	if (e->scaling_on) return waves <= 4 ? launch_upper_hess<4, true>(e, out) : waves <= 8 ? launch_upper_hess<8, true>(e, out) : launch_upper_hess<16, true>(e, out);
+	return waves <= 4 ? launch_upper_hess<4, false>(e, out) : waves <= 8 ? launch_upper_hess<8, false>(e, out) : launch_upper_hess<16, false>(e, out);
 }
 
 int upload_qpi(Shard *e) {
@@ -629,11 +722,12 @@ int launch_upper_params_w(Shard *e, int flags) {
 // ---- S != 4: MFMA kernels -----------------------------------------------------------------------------------
 // scratch of the rescaled S != 4 path: per op of a level, 5 rows [C][P] (lower: 1 row of maxima; upper: 3 rows num_l,
 // num_r, den + 2 rows of maxima)
-int ensure_gen_scale_storage(Shard *e) {
+// rows: 5, or 7 for the HESS pre-order pass (num2_l, num2_r besides)
+int ensure_gen_scale_storage(Shard *e, int rows = 5) {
 	int widest = 1;
 	for (size_t i = 0; i + 1 < e->lower_level_off.size(); i++) widest = std::max(widest, e->lower_level_off[i + 1] - e->lower_level_off[i]);
 	for (size_t i = 0; i + 1 < e->upper_level_off.size(); i++) widest = std::max(widest, e->upper_level_off[i + 1] - e->upper_level_off[i]);
-	const size_t need = (size_t)widest * 5 * e->C * e->P;
+	const size_t need = (size_t)widest * rows * e->C * e->P;
 	if (e->d_gen_scratch && e->gen_scratch_alloc >= need) return PHYAMD_OK;
 	dev_free(e, &e->d_gen_scratch, e->gen_scratch_alloc);
 	e->gen_scratch_alloc = 0;
@@ -706,12 +800,12 @@ int launch_upper_gen_v(Shard *e, bool compat) {
 	const int levels = (int)e->upper_level_off.size() - 1;
 	const size_t lds = sizeof(double) * (GenFuse<RT>::UPPER_IMAGES * MatImage<RT, KT>::SIZE + 6 * GenGeo<RT>::WAVES);
 	int rc;
-	if ((rc = allow_big_lds(k_upper_gen<RT, KT, FOLD, SCALE>, lds))) return rc;
+	if ((rc = allow_big_lds(k_upper_gen<RT, KT, FOLD, SCALE, false>, lds))) return rc;
 	if (SCALE && (rc = ensure_gen_scale_storage(e))) return rc;
 	if (GenFuse<RT>::QP && (rc = ensure_tip_rate_products(e, FOLD))) return rc;
 	const int pblocks = (e->P + 255) / 256;
 	constexpr int WV = GenGeo<RT>::WAVES;
-	if (e->gen_slots[1 + FOLD][SCALE] == 0) e->gen_slots[1 + FOLD][SCALE] = resident_workgroups(e, k_upper_gen<RT, KT, FOLD, SCALE>, WV * 64, lds);
+	if (e->gen_slots[1 + FOLD][SCALE] == 0) e->gen_slots[1 + FOLD][SCALE] = resident_workgroups(e, k_upper_gen<RT, KT, FOLD, SCALE, false>, WV * 64, lds);
 	const int slots = e->gen_slots[1 + FOLD][SCALE];
 	double *nd = e->d_gen_scratch, *mxu = SCALE ? e->d_gen_scratch : nullptr;
 	// rows of the gradient slabs are e->nblk wide (the finest grid); a level writes the first grid.x entries of its rows and
@@ -723,9 +817,9 @@ int launch_upper_gen_v(Shard *e, bool compat) {
 		const int tiles = choose_gen_tiles(e->P, WV, (long)cnt * e->C, slots, gen_stage_cost(e->S));
 		dim3 grid((e->P + WV * 16 * tiles - 1) / (WV * 16 * tiles), cnt, e->C);
 		if (SCALE) mxu = e->d_gen_scratch + (size_t)cnt * 3 * e->C * e->P;
-		hipLaunchKernelGGL((k_upper_gen<RT, KT, FOLD, SCALE>), grid, dim3(WV * 64), lds, e->stream, e->d_upper_ops + off, e->T, e->P, e->Pp, e->C,
+		hipLaunchKernelGGL((k_upper_gen<RT, KT, FOLD, SCALE, false>), grid, dim3(WV * 64), lds, e->stream, e->d_upper_ops + off, e->T, e->P, e->Pp, e->C,
 		                   e->d_tipmask, e->d_tipsets, e->d_lower, e->d_upper, e->d_imgs, e->d_imgs + ((size_t)e->N * e->C + (FOLD ? 0 : 1)) * MatImage<RT, KT>::SIZE, e->d_freqs, e->d_wl,
-		                   e->d_gpart, e->nblk, nd, mxu, tiles, e->d_qp_imgs);
+		                   e->d_gpart, e->nblk, nd, mxu, tiles, e->d_qp_imgs, (const double *)nullptr);
 		if (SCALE) {
 			hipLaunchKernelGGL(k_scale_upper_gen, dim3(pblocks, cnt), dim3(256), 0, e->stream, e->d_upper_ops + off, e->P, e->Pp, e->S, e->C, e->d_upper, mxu);
 			const int ppb = 256;  // one pattern per thread and slab entry; pblocks <= e->nblk
@@ -740,6 +834,59 @@ int launch_upper_gen_v(Shard *e, bool compat) {
 	HIP_TRY(hipGetLastError());
 	e->prof.upper_launches = levels;
 	return PHYAMD_OK;
+}
+
+// The HESS pre-order pass, 20 / 60 / 61 states (unfused schedule: phyamd_eval.inc, run_hessian): k_upper_gen writes the five rows
+// of every op of a level, k_hess_gen mixes them into the Hessian slab.
+template <int RT, int KT, bool SCALE>
+int launch_upper_gen_hess(Shard *e, double *out) {
+	using Img = MatImage<RT, KT>;
+	const int levels = (int)e->upper_level_off.size() - 1, S = e->S;
+	for (int i = 0; i < S; i++)
+		if (!(e->freqs[i] > 0.0)) return fail(PHYAMD_EUNSUPPORTED, "the Hessian diagonal divides by the frequencies: state %d has frequency %g", i, e->freqs[i]);
+	const size_t lds = sizeof(double) * (GenFuse<RT>::UPPER_IMAGES * Img::SIZE + 6 * GenGeo<RT>::WAVES);
+	int rc;
+	if (e->fused) return fail(PHYAMD_EDEVICE, "k_upper_gen<HESS> runs on the unfused schedule");
+	if ((rc = allow_big_lds(k_upper_gen<RT, KT, false, SCALE, true>, lds))) return rc;
+	if ((rc = ensure_gen_scale_storage(e, 7))) return rc;
+	if (GenFuse<RT>::QP && (rc = ensure_tip_rate_products(e, false))) return rc;
+	if (!e->d_hess_invf && (rc = dev_alloc(e, &e->d_hess_invf, (size_t)S))) return rc;
+	std::vector<double> invf(S);
+	for (int i = 0; i < S; i++) invf[i] = 1.0 / e->freqs[i];
+	HIP_TRY(hipMemcpyAsync(e->d_hess_invf, invf.data(), sizeof(double) * S, hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));  // (invf is a stack-lifetime buffer)
+	const int pblocks = (e->P + 255) / 256;
+	constexpr int WV = GenGeo<RT>::WAVES;
+	if (e->gen_hess_slots[SCALE] == 0) e->gen_hess_slots[SCALE] = resident_workgroups(e, k_upper_gen<RT, KT, false, SCALE, true>, WV * 64, lds);
+	const int slots = e->gen_hess_slots[SCALE];
+	HIP_TRY(hipMemsetAsync(e->d_hess, 0, sizeof(double) * (size_t)e->hess_nwg * 2 * e->N, e->stream));  // (the root's entries stay zero)
+	double *nd = e->d_gen_scratch;
+	int launched = 0;
+	for (int lv = 0; lv < levels; lv++) {
+		const int off = e->upper_level_off[lv], cnt = e->upper_level_off[lv + 1] - off;
+		if (cnt == 0) continue;
+		launched++;
+		const int tiles = choose_gen_tiles(e->P, WV, (long)cnt * e->C, slots, gen_stage_cost(e->S));
+		dim3 grid((e->P + WV * 16 * tiles - 1) / (WV * 16 * tiles), cnt, e->C);
+		double *mxu = SCALE ? e->d_gen_scratch + (size_t)cnt * 5 * e->C * e->P : nullptr;
+		hipLaunchKernelGGL((k_upper_gen<RT, KT, false, SCALE, true>), grid, dim3(WV * 64), lds, e->stream, e->d_upper_ops + off, e->T, e->P, e->Pp, e->C,
+		                   e->d_tipmask, e->d_tipsets, e->d_lower, e->d_upper, e->d_imgs, e->d_imgs + ((size_t)e->N * e->C + 1) * Img::SIZE, e->d_freqs, e->d_wl,
+		                   (double *)nullptr, 0, nd, mxu, tiles, e->d_qp_imgs, (const double *)e->d_hess_invf);
+		if (SCALE)
+			hipLaunchKernelGGL(k_scale_upper_gen, dim3(pblocks, cnt), dim3(256), 0, e->stream, e->d_upper_ops + off, e->P, e->Pp, e->S, e->C, e->d_upper, mxu);
+		if (e->hess_nwg > 0)
+			hipLaunchKernelGGL(k_hess_gen, dim3(e->hess_nwg, cnt), dim3(256), 0, e->stream, e->d_upper_ops + off, e->P, e->C, e->N, (const double *)nd, e->d_weights,
+			                   e->d_props, e->d_rates, (const int *)e->d_hess_tab, e->d_hess);
+	}
+	HIP_TRY(hipGetLastError());
+	return finish_hess_slab(e, out, launched);
+}
+
+int launch_hess(Shard *e, double *out) {
+	if (!e->generic) return launch_hess4(e, out);
+	if (e->S == 20) return e->scaling_on ? launch_upper_gen_hess<2, 5, true>(e, out) : launch_upper_gen_hess<2, 5, false>(e, out);
+	if (e->S == 60) return e->scaling_on ? launch_upper_gen_hess<4, 15, true>(e, out) : launch_upper_gen_hess<4, 15, false>(e, out);
+	return e->scaling_on ? launch_upper_gen_hess<4, 16, true>(e, out) : launch_upper_gen_hess<4, 16, false>(e, out);
 }
 
 // the 20-state post-order tree walk (phyamd_genwalk.inc): one launch, workgroups draw (pattern group, category) units from a counter

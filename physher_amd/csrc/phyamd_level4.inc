@@ -148,6 +148,40 @@ struct GradPOnly {
 	__device__ __forceinline__ void addp_tip(const Ctx4 &x, int tip, const d4 &u) const { g.addp_tip(x, tip, u); }
 };
 
+// HESS: this category's two branch terms, left in the exchange for the categories' mixture (x[i * xsz]: f.(u o Q b),
+// x[(NACC + i) * xsz]: f.(u o Q Q b)); nothing is accumulated here
+struct GradH {
+	cptr Q;
+	d4 f;
+	double *x;
+	int xsz;
+	__device__ __forceinline__ void add(int i, const d4 &u, const d4 &b) const {
+		const d4 fu = mul4(f, u), qb = matvec4(opaque(Q), b);
+		x[i * xsz] = dot4(fu, qb);
+		x[(NACC + i) * xsz] = dot4(fu, matvec4(opaque(Q), qb));
+	}
+	__device__ __forceinline__ void addp_vec(const Ctx4 &, int, const d4 &, const d4 &) const {}
+	__device__ __forceinline__ void addp_tip(const Ctx4 &, int, const d4 &) const {}
+};
+
+// accumulator / branch term j of an op -> the node whose branch it belongs to (-1: the op has no such term)
+__device__ __forceinline__ int term_node(const NodeOp &op, int j) {
+	const int kl = op.kind_left, kr = op.kind_right;
+	switch (j) {
+		case 0: return op.left;
+		case 1: return op.right;
+		case 2: return kl >= CH_CHERRY ? op.lt0 : -1;
+		case 3: return kl >= CH_CHERRY ? op.lt1 : -1;
+		case 4: return kl == CH_CHERRY_TIP ? op.linner : -1;
+		case 5: return kl == CH_CHERRY_TIP ? op.lt2 : -1;
+		case 6: return kr >= CH_CHERRY ? op.rt0 : -1;
+		case 7: return kr >= CH_CHERRY ? op.rt1 : -1;
+		case 8: return kr == CH_CHERRY_TIP ? op.rinner : -1;
+		case 9: return kr == CH_CHERRY_TIP ? op.rt2 : -1;
+	}
+	return -1;
+}
+
 template <bool PARAMS, typename GradT>
 __device__ __forceinline__ void descend_fringe(const Ctx4 &x, const GradT &gr, int base, int kind, int node, int t0, int t1, int t2, int inner,
                                                const d4 &u) {
@@ -174,8 +208,16 @@ __device__ __forceinline__ void descend_fringe(const Ctx4 &x, const GradT &gr, i
 	}
 }
 
-template <int WAVES, bool SCALE, bool FOLD, bool COMPAT, bool PARAMS>
-__global__ __launch_bounds__(WAVES *WAVE, (WAVES == 4 && !PARAMS) ? UPPER_MIN_WAVES : 1) void k_upper4(const NodeOp *__restrict__ ops, int T, int P, int C,
+// HESS (phyamd_branch_hessian_diagonal): lnL's first and second derivative in every branch length.  G == 1; workgroup x takes the
+// 64-pattern blocks [hwg[2x], hwg[2x + 1]) (never across a segment of reduce_block_sums' bisection: sums do not depend on the shard
+// count).  Per pattern every category wave leaves its branch terms n1_jc = f.(u_j o Q b_j), n2_jc = f.(u_j o Q Q b_j) in LDS next to
+// w_c den_c, and after one more barrier wave c mixes the terms j = c (mod C) over the categories:
+//   A_j = sum_c w_c r_c n1_jc,  B_j = sum_c w_c r_c^2 n2_jc,  D = sum_c w_c den_c
+//   d1 += w_k A_j / D,  d2 += w_k (B_j / D - (A_j / D)^2)
+// D is the site likelihood in the op's units (rescaled or not), so the scale factors cancel in both ratios.
+// hpart: [workgroup][2 N] -- node n's d1 at n, its d2 at N + n.
+template <int WAVES, bool SCALE, bool FOLD, bool COMPAT, bool PARAMS, bool HESS>
+__global__ __launch_bounds__(WAVES *WAVE, (WAVES == 4 && !PARAMS && !HESS) ? UPPER_MIN_WAVES : 1) void k_upper4(const NodeOp *__restrict__ ops, int T, int P, int C,
                                                         const uint8_t *__restrict__ tipmask, const double *__restrict__ lower,
                                                         double *__restrict__ upper, const double *__restrict__ mats,
                                                         const double *__restrict__ tiptab, const double *__restrict__ Q,
@@ -183,14 +225,17 @@ __global__ __launch_bounds__(WAVES *WAVE, (WAVES == 4 && !PARAMS) ? UPPER_MIN_WA
                                                         const double *__restrict__ props, const double *__restrict__ weights,
                                                         const double *__restrict__ w_over_L, double *__restrict__ gpart, int nblk,
                                                         const double *__restrict__ dpm, const double *__restrict__ dptab, int np, int N,
-                                                        double *__restrict__ ppart, int op_base, int op_total) {
+                                                        double *__restrict__ ppart, int op_base, int op_total,
+                                                        const double *__restrict__ rates, const int *__restrict__ hwg, double *__restrict__ hpart) {
+	static_assert(!HESS || (!FOLD && !COMPAT && !PARAMS), "the Hessian variant is the plain reference arithmetic");
 	extern __shared__ double sh[];
 	// blockDim.x == 64: threadIdx.y/z are wave-uniform; readfirstlane tells the compiler so (SGPR addressing)
 	const int lane = threadIdx.x, c = __builtin_amdgcn_readfirstlane(threadIdx.y), g = __builtin_amdgcn_readfirstlane(threadIdx.z), G = blockDim.z;
 	const NodeOp op = ops[blockIdx.y];
 	const size_t plane = (size_t)P * 4;
 	const bool proot = op.upper_slot_parent < 0;
-	const int nacc = NACC + (PARAMS ? np : 0);  // accumulator columns per thread
+	const int hc = (NACC + C - 1) / C;  // HESS: branch terms per category wave
+	const int nacc = HESS ? 2 * hc : NACC + (PARAMS ? np : 0);  // accumulator columns per thread
 	const double *up = proot ? nullptr : upper + ((size_t)op.upper_slot_parent * C + c) * plane;
 	double *ul_dst = op.upper_slot_left < 0 ? nullptr : upper + ((size_t)op.upper_slot_left * C + c) * plane;
 	double *ur_dst = op.upper_slot_right < 0 ? nullptr : upper + ((size_t)op.upper_slot_right * C + c) * plane;
@@ -199,13 +244,14 @@ __global__ __launch_bounds__(WAVES *WAVE, (WAVES == 4 && !PARAMS) ? UPPER_MIN_WA
 	const int xsz = G * C * WAVE;
 	// gradient accumulators live in LDS (one column per thread), not in registers: the kernel is VGPR-limited
 	const int wv = g * C + c, nw = G * C;
-	double *red = sh + (SCALE ? 6 * xsz : 0);
+	double *red = sh + (HESS ? (6 + 2 * NACC) * xsz : SCALE ? 6 * xsz : 0);
 	Grad4 gr{as_const(Q), FOLD ? one : pi, 0.0, red + (size_t)wv * nacc * WAVE + lane, dpm, dptab, np, N, T, props[c]};
 	for (int i = 0; i < nacc; i++) gr.acc[i * WAVE] = 0.0;
 
 #pragma unroll 1
 	for (int q = 0; q < PPT_UPPER; q++) {
-		const int k0 = ((blockIdx.x * PPT_UPPER + q) * G + g) * WAVE + lane;
+		if (HESS && hwg[2 * blockIdx.x] + q >= hwg[2 * blockIdx.x + 1]) break;  // (the same for every wave of the workgroup)
+		const int k0 = HESS ? (hwg[2 * blockIdx.x] + q) * WAVE + lane : ((blockIdx.x * PPT_UPPER + q) * G + g) * WAVE + lane;
 		const bool valid = k0 < P;
 		const Ctx4 x{tipmask, mats, tiptab, P, C, c, valid ? k0 : P - 1, T};
 		const int k = x.k;
@@ -216,7 +262,7 @@ __global__ __launch_bounds__(WAVES *WAVE, (WAVES == 4 && !PARAMS) ? UPPER_MIN_WA
 		                     : child_message(x, op.kind_right, op.right, op.core_right, op.rt0, op.rt1, op.rt2, op.rinner, lower, plane);
 		const d4 a = proot ? (FOLD ? pi : one) : matvec4(x.M(op.parent), load4(up + (size_t)k * 4));
 		d4 ul = mul4(a, br), ur = mul4(a, bl);
-		if (!SCALE) {
+		if (!SCALE && !HESS) {
 			// unscaled: divide by the site likelihood formed at the root, like the reference (treelikelihood.c:2879);
 			// no cross-category exchange, no barrier, no division in this kernel
 			gr.wl = valid ? w_over_L[k] : 0.0;
@@ -237,8 +283,8 @@ __global__ __launch_bounds__(WAVES *WAVE, (WAVES == 4 && !PARAMS) ? UPPER_MIN_WA
 			// rescaled: L_k underflows by construction, so the mixture likelihood is re-formed
 			// in this branch's scaled units from all categories' den (exchange through LDS); the scale factors cancel in num / D
 			const double den = dot4(mul4(gr.f, a), mul4(bl, br));
-			const double numl = dot4(mul4(gr.f, ul), matvec4(opaque(gr.Q), bl));
-			const double numr = dot4(mul4(gr.f, ur), matvec4(opaque(gr.Q), br));
+			const double numl = HESS ? 0.0 : dot4(mul4(gr.f, ul), matvec4(opaque(gr.Q), bl));
+			const double numr = HESS ? 0.0 : dot4(mul4(gr.f, ur), matvec4(opaque(gr.Q), br));
 			double *xb = sh + (q & 1) * 3 * xsz;
 			const int xi = (g * C + c) * WAVE + lane;
 			xb[xi] = props[c] * den;
@@ -253,30 +299,52 @@ __global__ __launch_bounds__(WAVES *WAVE, (WAVES == 4 && !PARAMS) ? UPPER_MIN_WA
 			}
 			// num / L first: with COMPAT both can be denormal (a category that has underflowed) and 1 / den alone overflows
 			const double w = valid ? weights[k] : 0.0, d = COMPAT ? den : D;
-			gr.acc[0] += w * (numl / d);
-			gr.acc[WAVE] += w * (numr / d);
-			if (PARAMS) {  // mixture numerator over the mixture likelihood in this branch's units (treelikelihood.c:2545-2556)
-				gr.wl = w / D;
-				if (op.kind_left == CH_TIP) gr.addp_tip(x, op.left, ul);
-				else gr.addp_vec(x, op.left, ul, prel);
-				if (op.kind_right == CH_TIP) gr.addp_tip(x, op.right, ur);
-				else gr.addp_vec(x, op.right, ur, prer);
-			}
-			// Fringe children (fused schedules run rescaled too): a cherry or cherry + tip never reaches the rescaling threshold
-			// (products of two or three transition probabilities), so its likelihood is in this op's units and shares D
-			if (op.kind_left >= CH_CHERRY || op.kind_right >= CH_CHERRY) {
-				const GradS gs{gr.Q, gr.f, w, d, gr.acc};
-				if (op.kind_left >= CH_CHERRY) descend_fringe<false>(x, gs, 2, op.kind_left, op.left, op.lt0, op.lt1, op.lt2, op.linner, ul);
-				if (op.kind_right >= CH_CHERRY) descend_fringe<false>(x, gs, 6, op.kind_right, op.right, op.rt0, op.rt1, op.rt2, op.rinner, ur);
-				if (PARAMS) {
-					const GradPOnly gp{gr};  // gr.wl = w / D from above
-					if (op.kind_left >= CH_CHERRY) descend_fringe<true>(x, gp, 2, op.kind_left, op.left, op.lt0, op.lt1, op.lt2, op.linner, ul);
-					if (op.kind_right >= CH_CHERRY) descend_fringe<true>(x, gp, 6, op.kind_right, op.right, op.rt0, op.rt1, op.rt2, op.rinner, ur);
+			if (HESS) {
+				double *hx = sh + 6 * xsz;  // [2 NACC][waves][64] branch terms
+				const GradH gh{gr.Q, gr.f, hx + xi, xsz};
+				gh.add(0, ul, bl);
+				gh.add(1, ur, br);
+				if (op.kind_left >= CH_CHERRY) descend_fringe<false>(x, gh, 2, op.kind_left, op.left, op.lt0, op.lt1, op.lt2, op.linner, ul);
+				if (op.kind_right >= CH_CHERRY) descend_fringe<false>(x, gh, 6, op.kind_right, op.right, op.rt0, op.rt1, op.rt2, op.rinner, ur);
+				__syncthreads();
+				for (int j = c, m = 0; j < NACC; j += C, m++) {
+					if (term_node(op, j) < 0) continue;
+					double A = 0.0, B = 0.0;
+					for (int cc = 0; cc < C; cc++) {
+						const double wr = props[cc] * rates[cc];
+						A += wr * hx[j * xsz + (g * C + cc) * WAVE + lane];
+						B += wr * rates[cc] * hx[(NACC + j) * xsz + (g * C + cc) * WAVE + lane];
+					}
+					const double a1 = A / D;
+					gr.acc[m * WAVE] += w * a1;
+					gr.acc[(hc + m) * WAVE] += w * (B / D - a1 * a1);
+				}
+			} else {
+				gr.acc[0] += w * (numl / d);
+				gr.acc[WAVE] += w * (numr / d);
+				if (PARAMS) {  // mixture numerator over the mixture likelihood in this branch's units (treelikelihood.c:2545-2556)
+					gr.wl = w / D;
+					if (op.kind_left == CH_TIP) gr.addp_tip(x, op.left, ul);
+					else gr.addp_vec(x, op.left, ul, prel);
+					if (op.kind_right == CH_TIP) gr.addp_tip(x, op.right, ur);
+					else gr.addp_vec(x, op.right, ur, prer);
+				}
+				// Fringe children (fused schedules run rescaled too): a cherry or cherry + tip never reaches the rescaling threshold
+				// (products of two or three transition probabilities), so its likelihood is in this op's units and shares D
+				if (op.kind_left >= CH_CHERRY || op.kind_right >= CH_CHERRY) {
+					const GradS gs{gr.Q, gr.f, w, d, gr.acc};
+					if (op.kind_left >= CH_CHERRY) descend_fringe<false>(x, gs, 2, op.kind_left, op.left, op.lt0, op.lt1, op.lt2, op.linner, ul);
+					if (op.kind_right >= CH_CHERRY) descend_fringe<false>(x, gs, 6, op.kind_right, op.right, op.rt0, op.rt1, op.rt2, op.rinner, ur);
+					if (PARAMS) {
+						const GradPOnly gp{gr};  // gr.wl = w / D from above
+						if (op.kind_left >= CH_CHERRY) descend_fringe<true>(x, gp, 2, op.kind_left, op.left, op.lt0, op.lt1, op.lt2, op.linner, ul);
+						if (op.kind_right >= CH_CHERRY) descend_fringe<true>(x, gp, 6, op.kind_right, op.right, op.rt0, op.rt1, op.rt2, op.rinner, ur);
+					}
 				}
 			}
 			// uppers are rescaled like lowers (treelikelihood.c:1414, 1795-1796)
-			if (ml < SCALING_THRESHOLD) ul = d4{ul.x / ml, ul.y / ml, ul.z / ml, ul.w / ml};
-			if (mr < SCALING_THRESHOLD) ur = d4{ur.x / mr, ur.y / mr, ur.z / mr, ur.w / mr};
+			if (SCALE && ml < SCALING_THRESHOLD) ul = d4{ul.x / ml, ul.y / ml, ul.z / ml, ul.w / ml};
+			if (SCALE && mr < SCALING_THRESHOLD) ur = d4{ur.x / mr, ur.y / mr, ur.z / mr, ur.w / mr};
 		}
 		if (ul_dst && valid) store4(ul_dst + (size_t)k * 4, ul);
 		if (ur_dst && valid) store4(ur_dst + (size_t)k * 4, ur);
@@ -298,10 +366,20 @@ __global__ __launch_bounds__(WAVES *WAVE, (WAVES == 4 && !PARAMS) ? UPPER_MIN_WA
 	}
 	__syncthreads();
 	const double *tot = red + (size_t)nw * nacc * WAVE;
+	if (HESS) {  // G == 1: one slab entry per workgroup and node
+		const int j = c + lane * C;
+		const int node = lane < hc && j < NACC ? term_node(op, j) : -1;
+		if (node >= 0) {
+			hpart[(size_t)blockIdx.x * 2 * N + node] = tot[c * nacc + lane];
+			hpart[(size_t)blockIdx.x * 2 * N + N + node] = tot[c * nacc + hc + lane];
+		}
+		return;
+	}
 	if (g == 0 && lane < NACC) {
 		double s = tot[c * nacc + lane];
 		for (int gg = 1; gg < G; gg++) s += tot[(gg * C + c) * nacc + lane];
-		// accumulator -> gradient row (node id); -1 = unused for this op
+		// accumulator -> gradient row (node id); -1 = unused for this op (the same map as term_node, kept written out: calling it here
+		// changes the register allocation of the existing instantiations)
 		const int kl = op.kind_left, kr = op.kind_right;
 		int node = -1;
 		switch (lane) {

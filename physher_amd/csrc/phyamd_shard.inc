@@ -187,6 +187,13 @@ struct Shard {
 	double *d_pg_lower = nullptr;   // 20 / 60 / 61 states, parameter gradient: every stored node's partial itself (d_lower holds P p)
 	size_t pg_lower_alloc = 0;
 	int path_node = -1;              // node whose upper d_path_upper holds (-1: none); dropped whenever partials are recomputed
+	// phyamd_branch_hessian_diagonal (ensure_hess_storage): workgroup table and slab of the HESS pre-order pass
+	int *d_hess_tab = nullptr;
+	double *d_hess = nullptr;
+	size_t hess_tab_alloc = 0, hess_alloc = 0;
+	int hess_nwg = 0, hess_P = -1, hess_levels = -1;
+	double *d_hess_invf = nullptr;   // 20 / 60 / 61 states: 1 / pi [S]
+	int gen_hess_slots[2] = {0, 0};  // resident workgroups of k_upper_gen<HESS> [SCALE]
 	double *d_branch = nullptr;      // phyamd_branch_log_likelihood: [C][3][16] matrices | [3][blocks] partial sums | [3]
 	bool upper_fold = false;         // the stored uppers carry the root frequencies (last gradient call used FOLD)
 	double *d_rf_part = nullptr;     // [S][blocks] partial sums of k_root_frequency_term, then [S]

@@ -27,6 +27,7 @@ double tile_working_set(const Shard *e, double p, bool exact, const ScheduleCoun
 	if (exponents) doubles += 0.5 * ((double)(std::max(1, k.core_count) + std::max(1, k.upper_slots) + 1) * e->C * p + p);
 	if (e->S == 4) doubles += (double)e->C * p;  // the streamed post-order walk's per-category root terms (d_Lc)
 	doubles += (double)e->N * e->C * (p / (WAVE * std::max(1, 4 / e->C)) + 1.0);  // gradient slabs, one entry per wave group
+	if (e->S == 4) doubles += 2.0 * e->N * (p / (WAVE * PPT_UPPER) + 19.0) + 0.5 * p / 64.0;  // the Hessian diagonal's slab and its table
 	return 8.0 * doubles + per_pattern;
 }
 
@@ -141,6 +142,10 @@ void free_pattern_storage(Shard *e) {
 	dev_free(e, &e->d_Ec, (size_t)e->C * e->P);
 	dev_free(e, &e->d_Eroot, (size_t)e->P);
 	dev_free(e, &e->d_gpart, (size_t)e->N * e->C * e->gpart_row);
+	dev_free(e, &e->d_hess, e->hess_alloc);
+	dev_free(e, &e->d_hess_tab, e->hess_tab_alloc);
+	e->hess_alloc = e->hess_tab_alloc = 0;
+	e->hess_P = -1;
 	dev_free(e, &e->d_mstream, e->mstream_alloc);
 	e->mstream_alloc = 0;
 	e->d_gslab = nullptr;
@@ -258,7 +263,7 @@ void shard_destroy(Shard *e) {
 	for (void *p : {(void *)e->d_branch, (void *)e->d_path_steps, (void *)e->d_path_upper, (void *)e->d_path_tmp, (void *)e->d_path_lower, (void *)e->d_path_side, (void *)e->d_pg_lower, (void *)e->d_Bw, (void *)e->d_pbuf, (void *)e->d_Fw, (void *)e->d_gacc, (void *)e->d_gen_scratch, (void *)e->d_rf_part, (void *)e->d_B, (void *)e->d_dpm, (void *)e->d_dptab, (void *)e->d_ppart, (void *)e->d_imgs, (void *)e->d_qp_mats, (void *)e->d_qp_imgs, (void *)e->d_tipmask, (void *)e->d_tip_all, (void *)e->d_weights_all, (void *)e->d_plk_all, (void *)e->d_total, (void *)e->d_tipsets, (void *)e->d_pg_nodes, (void *)e->d_pg_core, (void *)e->d_pg_den, (void *)e->d_pg_Gw, (void *)e->d_pg_B, (void *)e->d_lower, (void *)e->d_upper, (void *)e->d_mats, (void *)e->d_dmats, (void *)e->d_model, (void *)e->d_Q, (void *)e->d_Lc, (void *)e->d_inv_part, (void *)e->d_tiptab,
 	                (void *)e->d_freqs, (void *)e->d_rates, (void *)e->d_props, (void *)e->d_lengths, (void *)e->d_weights, (void *)e->d_plk, (void *)e->d_wl,
 	                (void *)e->d_lscale, (void *)e->d_lnl_part, (void *)e->d_gpart, (void *)e->d_mstream, (void *)e->d_oct, (void *)e->d_stream_ops, (void *)e->d_stream_chunks, (void *)e->d_stream_row_entries, (void *)e->d_stream_site_tab, (void *)e->d_stream_qnode, (void *)e->d_lstream_ops, (void *)e->d_lstream_chunks, (void *)e->d_gen_walk_counter, (void *)e->d_oct_lo, (void *)e->d_stream_op_tips, (void *)e->d_stream_op_deep, (void *)e->d_stream_flag, (void *)e->d_optab, (void *)e->d_result, (void *)e->d_explicit, (void *)e->d_row_valid,
-	                (void *)e->d_lower_ops, (void *)e->d_upper_ops, (void *)e->d_walk_lower_ops, (void *)e->d_walk_upper_ops, (void *)e->d_walk_chunk_ops, (void *)e->d_walk_chunk_off, (void *)e->d_walk_lower_chunk_ops, (void *)e->d_walk_lower_chunk_off, (void *)e->d_inc_ops, (void *)e->d_Qpi})
+	                (void *)e->d_lower_ops, (void *)e->d_upper_ops, (void *)e->d_walk_lower_ops, (void *)e->d_walk_upper_ops, (void *)e->d_walk_chunk_ops, (void *)e->d_walk_chunk_off, (void *)e->d_walk_lower_chunk_ops, (void *)e->d_walk_lower_chunk_off, (void *)e->d_inc_ops, (void *)e->d_Qpi, (void *)e->d_hess, (void *)e->d_hess_tab, (void *)e->d_hess_invf})
 		if (p) (void)hipFree(p);
 	if (e->h_result) (void)hipHostFree(e->h_result);
 	if (e->h_lengths) (void)hipHostFree(e->h_lengths);
@@ -785,6 +790,41 @@ int shard_parameter_gradient_device(Shard *e, int flags, double *device_out) {
 	int rc;
 	if ((rc = eval_gradient(e, flags, true))) return rc;
 	HIP_TRY(hipMemcpyAsync(device_out, e->d_result, sizeof(double) * ((size_t)1 + e->N * e->C + e->np + e->S), hipMemcpyDeviceToDevice, e->stream));
+	return PHYAMD_OK;
+}
+
+// ---- every branch's first and second derivative at once (phyamd_branch_hessian_diagonal) ----
+// what the single-branch evaluation would return as d1, d2 for every node at its current length: the level pre-order pass in its
+// HESS form (k_upper4), which forms r_c Q P p and r_c^2 Q Q P p against the upper partial it builds anyway
+int hessian_ready(Shard *e, int flags) {
+	if (flags != 0) return fail(PHYAMD_EINVAL, "phyamd_branch_hessian_diagonal: flags %d (no flags are defined: pass 0)", flags);
+	if (!e->have_eigen) return fail(PHYAMD_EINVAL, "the Hessian diagonal needs the eigen system (phyamd_set_eigen)");
+	// The pass differentiates the matrices it multiplies with: Q P and Q Q P are the derivatives of P = exp(Q t r) only.  The
+	// single-branch call rebuilds P from the eigen system and ignores an explicit matrix, so here the two would disagree.
+	for (int n = 0; n < e->N; n++)
+		if (n != e->root && e->explicit_host[n])
+			return fail(PHYAMD_EUNSUPPORTED, "the Hessian diagonal differentiates exp(Q t r): node %d has explicit matrices", n);
+	// 4 states: one workgroup holds all categories' exchange (hess_lds: 124 KB at 8); more are refused
+	if (!e->generic && e->C > 8) return fail(PHYAMD_EUNSUPPORTED, "the Hessian diagonal takes at most 8 categories with 4 states (this engine has %d)", e->C);
+	return check_ready(e);
+}
+
+int shard_branch_hessian_diagonal_device(Shard *e, int flags, double *device_out) {
+	CHECK_ENGINE(e);
+	if (!device_out) return fail(PHYAMD_EINVAL, "null device_out");
+	int rc;
+	if ((rc = hessian_ready(e, flags)) || (rc = eval_hessian(e))) return rc;
+	HIP_TRY(hipMemcpyAsync(device_out, hess_result(e), sizeof(double) * ((size_t)1 + 2 * e->N), hipMemcpyDeviceToDevice, e->stream));
+	return PHYAMD_OK;
+}
+
+// out[1 + 2 N] = [lnL | d1 | d2] on the host
+int shard_branch_hessian_diagonal(Shard *e, int flags, double *out) {
+	CHECK_ENGINE(e);
+	int rc;
+	if ((rc = hessian_ready(e, flags)) || (rc = eval_hessian(e))) return rc;
+	HIP_TRY(hipMemcpyAsync(out, hess_result(e), sizeof(double) * ((size_t)1 + 2 * e->N), hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));
 	return PHYAMD_OK;
 }
 

@@ -191,6 +191,18 @@ class Engine:
         self._check(self._lib.phyamd_branch_log_likelihood(self._h, int(node), float(length), C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
+    def branch_hessian_diagonal(self, flags=0):
+        """(lnL, d1 [N], d2 [N]): every branch's d lnL/dt and d2 lnL/dt2 at its current length from one post-order and one
+        pre-order pass (row n = branch_log_likelihood(n, t_n)[1:]; root row 0)."""
+        v = C.c_double()
+        d1, d2 = np.empty(self.N), np.empty(self.N)
+        self._check(self._lib.phyamd_branch_hessian_diagonal(self._h, flags, C.byref(v), _ptr(d1), _ptr(d2)))
+        return v.value, d1, d2
+
+    def branch_hessian_diagonal_device(self, device_ptr, flags=0):
+        """[lnL | d1[N] | d2[N]] -> device_ptr on the engine's stream (sums over this engine's patterns)"""
+        self._check(self._lib.phyamd_branch_hessian_diagonal_device(self._h, flags, C.c_void_p(device_ptr)))
+
     def store(self):
         """Remember the current (evaluated) state: parameters, lnL and partials (MCMC store)."""
         self._check(self._lib.phyamd_store(self._h))
