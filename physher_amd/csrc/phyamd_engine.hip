@@ -1,6 +1,7 @@
 // phyamd_engine.hip -- MI355X (gfx950) tree-likelihood engine behind include/physher_amd.h.
 //
 // One translation unit, assembled from:
+//   phyamd_memory.inc       owning device arrays and the memory budget they are allocated through
 //   phyamd_device.inc / _level4 / _walk4 / _walk4s / _general / _genwalk / _patterns   device code (kernels)
 //   phyamd_shard.inc        state of one engine on one GPU (= one shard of the site patterns), the form of its stored lowers
 //   phyamd_schedule.inc     level and tree-walk schedules, device storage
@@ -110,6 +111,8 @@ struct NodeOp {
 	// (bit 3 is no longer set by the host; k_lower4_walk still tests it)
 	int32_t lds_park;
 };
+
+#include "phyamd_memory.inc"
 
 #include "phyamd_device.inc"
 #include "phyamd_level4.inc"

@@ -79,7 +79,7 @@ int run_lower(Shard *e, int need_host_check) {
 				if (dirty[e->lower_ops[i].parent]) e->inc_ops.push_back(e->lower_ops[i]);
 			e->inc_level_off.push_back((int)e->inc_ops.size());
 		}
-		if (!e->d_inc_ops && (rc = dev_alloc(e, &e->d_inc_ops, (size_t)e->N))) return rc;
+		if ((rc = e->d_inc_ops.ensure(e->N))) return rc;
 		HIP_TRY(hipMemcpyAsync(e->d_inc_ops, e->inc_ops.data(), e->inc_ops.size() * sizeof(NodeOp), hipMemcpyHostToDevice, e->stream));
 		HIP_TRY(hipStreamSynchronize(e->stream));  // inc_ops is reused by the next call
 		e->act_level_off = &e->inc_level_off;
@@ -130,23 +130,14 @@ int run_lower(Shard *e, int need_host_check) {
 int update_parameter_matrices(Shard *e) {
 	const int S = e->S, np = e->np;
 	int rc;
-	if ((size_t)np > e->np_alloc) {
-		dev_free(e, &e->d_B, e->np_alloc * S * S);
-		dev_free(e, &e->d_dpm, e->np_alloc * e->N * e->C * S * S);
-		dev_free(e, &e->d_dptab, e->np_alloc * e->T * e->C * 64);
-		e->np_alloc = 0;
-		if ((rc = dev_alloc(e, &e->d_B, (size_t)np * S * S)) || (rc = dev_alloc(e, &e->d_dpm, (size_t)np * e->N * e->C * S * S)) ||
-		    (rc = dev_alloc(e, &e->d_dptab, (size_t)np * e->T * e->C * 64)))
-			return rc;
-		e->np_alloc = np;
+	if ((size_t)np * S * S > e->d_B.size()) {  // (the three grow together: all are freed before any is allocated again)
+		e->d_B.release();
+		e->d_dpm.release();
+		e->d_dptab.release();
 	}
-	const size_t need = (size_t)np * e->upper_ops.size() * ((size_t)e->nblk + 1);
-	if (need > e->ppart_alloc) {
-		dev_free(e, &e->d_ppart, e->ppart_alloc);
-		e->ppart_alloc = 0;
-		if ((rc = dev_alloc(e, &e->d_ppart, need))) return rc;
-		e->ppart_alloc = need;
-	}
+	if ((rc = e->d_B.ensure((size_t)np * S * S)) || (rc = e->d_dpm.ensure((size_t)np * e->N * e->C * S * S)) || (rc = e->d_dptab.ensure((size_t)np * e->T * e->C * 64)) ||
+	    (rc = e->d_ppart.ensure((size_t)np * e->upper_ops.size() * ((size_t)e->nblk + 1))))
+		return rc;
 	if (e->params_dirty) {
 		const std::vector<double> B = eigen_basis_derivatives(e);
 		HIP_TRY(hipMemcpyAsync(e->d_B, B.data(), sizeof(double) * B.size(), hipMemcpyHostToDevice, e->stream));
@@ -167,18 +158,12 @@ int update_parameter_matrices(Shard *e) {
 int launch_parameters_gen(Shard *e, double *dst) {
 	const int S = e->S, S2 = S * S, np = e->np, B = e->N - 1;
 	int rc;
-	if (!e->d_pg_nodes) {
-		if ((rc = dev_alloc(e, &e->d_pg_nodes, (size_t)B)) || (rc = dev_alloc(e, &e->d_pg_core, (size_t)e->N)) ||
-		    (rc = dev_alloc(e, &e->d_pg_den, (size_t)B * e->P)) || (rc = dev_alloc(e, &e->d_pg_Gw, ((size_t)B * e->C + 1) * S2)))
-			return rc;
-	}
-	if ((size_t)np > e->pg_np_alloc) {
-		dev_free(e, &e->d_pg_B, e->pg_np_alloc * S2);
-		e->pg_np_alloc = 0;
-		if ((rc = dev_alloc(e, &e->d_pg_B, (size_t)np * S2))) return rc;
-		e->pg_np_alloc = np;
-		e->params_dirty = true;
-	}
+	if ((rc = e->d_pg_nodes.ensure(B)) || (rc = e->d_pg_core.ensure(e->N)) || (rc = e->d_pg_den.ensure((size_t)B * e->P)) ||
+	    (rc = e->d_pg_Gw.ensure(((size_t)B * e->C + 1) * S2)))
+		return rc;
+	bool grew;
+	if ((rc = e->d_pg_B.ensure((size_t)np * S2, &grew))) return rc;
+	if (grew) e->params_dirty = true;
 	{  // the schedule may have been rebuilt since the last call: the two index tables are N ints
 		std::vector<int> nodes;
 		for (int n = 0; n < e->N; n++)
@@ -194,13 +179,8 @@ int launch_parameters_gen(Shard *e, double *dst) {
 		e->params_dirty = false;
 	}
 	{  // the kernels below take every node's partial p_n itself; the post-order pass stores t_n = P_n p_n (k_lower_gen)
-		const size_t npd = node_partial_doubles(e), need = (size_t)e->lower_alloc_cores * npd;
-		if (e->pg_lower_alloc < need) {
-			dev_free(e, &e->d_pg_lower, e->pg_lower_alloc);
-			e->pg_lower_alloc = 0;
-			if ((rc = dev_alloc(e, &e->d_pg_lower, need))) return rc;
-			e->pg_lower_alloc = need;
-		}
+		const size_t npd = node_partial_doubles(e);
+		if ((rc = e->d_pg_lower.ensure(lower_slots(e) * npd))) return rc;
 		for (int n = e->T; n < e->N; n++)
 			if (e->core_index[n] >= 0 && (rc = true_lower_gen(e, n, e->d_pg_lower + (size_t)e->core_index[n] * npd, nullptr))) return rc;
 	}
@@ -221,7 +201,7 @@ int launch_parameters_gen(Shard *e, double *dst) {
 int launch_root_frequency_term(Shard *e, double *dst) {
 	int rc;
 	const int nb = (e->P + 255) / 256;
-	if (!e->d_rf_part && (rc = dev_alloc(e, &e->d_rf_part, ((size_t)nb + 1) * e->S))) return rc;
+	if ((rc = e->d_rf_part.ensure(((size_t)nb + 1) * e->S))) return rc;
 	const double *root = e->d_lower + (size_t)e->core_index[e->root] * node_partial_doubles(e);
 	const size_t cat_stride = e->generic ? (size_t)e->S * e->Pp : (size_t)e->P * e->S;
 	const size_t pat_stride = e->generic ? 1 : (size_t)e->S, state_stride = e->generic ? (size_t)e->Pp : 1;
@@ -237,7 +217,7 @@ int launch_root_frequency_term(Shard *e, double *dst) {
 int launch_root_invariant_term(Shard *e, double *dst) {
 	int rc;
 	const int nb = (e->P + 255) / 256;
-	if (!e->d_inv_part && (rc = dev_alloc(e, &e->d_inv_part, (size_t)nb + 1))) return rc;
+	if ((rc = e->d_inv_part.ensure((size_t)nb + 1))) return rc;
 	const double *root = e->d_lower + (size_t)e->core_index[e->root] * node_partial_doubles(e);
 	const size_t cat_stride = e->generic ? (size_t)e->S * e->Pp : (size_t)e->P * e->S;
 	const size_t pat_stride = e->generic ? 1 : (size_t)e->S, state_stride = e->generic ? (size_t)e->Pp : 1;

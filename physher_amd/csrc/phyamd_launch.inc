@@ -189,7 +189,7 @@ int launch_lower_w(Shard *e) {
 	if (lower_stream_applies(e)) {
 		int rc = ensure_mask_stream(e);
 		if (!rc) rc = ensure_optab(e);
-		if (!rc && !e->d_Lc) rc = dev_alloc(e, &e->d_Lc, (size_t)e->C * e->P);  // per-category root terms for k_root_finish64
+		if (!rc) rc = e->d_Lc.ensure((size_t)e->C * e->P);  // per-category root terms for k_root_finish64
 		if (rc == PHYAMD_ENOMEM && e->cfg.max_device_bytes > 0) e->lstream_on = false;  // the cap leaves no room for the words
 		else if (rc) return rc;
 		else if (!e->stream_unsupported) {
@@ -271,16 +271,12 @@ int ensure_hess_storage(Shard *e) {
 	const int nwg = (int)wg.size() / 2;
 	first.push_back(nwg);
 	wg.insert(wg.end(), first.begin(), first.end());
-	dev_free(e, &e->d_hess_tab, e->hess_tab_alloc);
-	dev_free(e, &e->d_hess, e->hess_alloc);
-	e->hess_tab_alloc = e->hess_alloc = 0;
+	e->d_hess_tab.release();
+	e->d_hess.release();
 	e->hess_P = -1;
 	int rc;
 	const size_t R = (size_t)2 * e->N, need = (size_t)nwg * R + 8 * R + 2 * (R + 1);
-	if ((rc = dev_alloc(e, &e->d_hess_tab, wg.size()))) return rc;
-	e->hess_tab_alloc = wg.size();
-	if ((rc = dev_alloc(e, &e->d_hess, need))) return rc;
-	e->hess_alloc = need;
+	if ((rc = e->d_hess_tab.ensure(wg.size())) || (rc = e->d_hess.ensure(need))) return rc;
 	HIP_TRY(hipMemcpyAsync(e->d_hess_tab, wg.data(), sizeof(int) * wg.size(), hipMemcpyHostToDevice, e->stream));
 	HIP_TRY(hipStreamSynchronize(e->stream));  // (wg is a stack-lifetime buffer)
 	e->hess_nwg = nwg;
@@ -336,7 +332,7 @@ int launch_hess4(Shard *e, double *out) {
 int upload_qpi(Shard *e) {
 	if (!e->qpi_dirty) return PHYAMD_OK;  // diag(pi) Q, 16 doubles
 	int rc;
-	if (!e->d_Qpi && (rc = dev_alloc(e, &e->d_Qpi, 16))) return rc;
+	if ((rc = e->d_Qpi.ensure(16))) return rc;
 	double qpi[16];
 	for (int i = 0; i < 4; i++)
 		for (int j = 0; j < 4; j++) qpi[i * 4 + j] = e->freqs[i] * e->Q_host[i * 4 + j];
@@ -348,15 +344,10 @@ int upload_qpi(Shard *e) {
 
 // mask words of the streamed walk: rebuilt when the tip data or the word layout (topology) changed
 int ensure_mask_stream(Shard *e) {
-	int rc;
-	const size_t mstride = (size_t)e->nblk_walk_upper * e->G * WAVE, need = (size_t)std::max(1, e->stream_words) * mstride;
-	if (need > e->mstream_alloc) {
-		dev_free(e, &e->d_mstream, e->mstream_alloc);
-		e->mstream_alloc = 0;
-		if ((rc = dev_alloc(e, &e->d_mstream, need))) return rc;
-		e->mstream_alloc = need;
-		e->mstream_epoch = 0;
-	}
+	const size_t mstride = (size_t)e->nblk_walk_upper * e->G * WAVE;
+	bool grew;
+	if (int rc = e->d_mstream.ensure((size_t)std::max(1, e->stream_words) * mstride, &grew)) return rc;
+	if (grew) e->mstream_epoch = 0;
 	if (e->mstream_epoch == e->tip_epoch && e->mstride == mstride && e->mstream_layout == e->stream_row_entries) return PHYAMD_OK;
 	e->mstride = mstride;
 	e->stream_unsupported = false;
@@ -379,14 +370,7 @@ int ensure_mask_stream(Shard *e) {
 
 // table blocks of the streamed walk: one per (pre-order op, category)
 int ensure_optab(Shard *e) {
-	const size_t tab_need = (size_t)std::max<size_t>(1, e->stream_ops.size()) * e->C * OPBLK_BYTES;
-	if (tab_need <= e->optab_alloc) return PHYAMD_OK;
-	dev_free(e, &e->d_optab, e->optab_alloc);
-	e->optab_alloc = 0;
-	int rc = dev_alloc(e, &e->d_optab, tab_need);
-	if (rc) return rc;
-	e->optab_alloc = tab_need;
-	return PHYAMD_OK;
+	return e->d_optab.ensure((size_t)std::max<size_t>(1, e->stream_ops.size()) * e->C * OPBLK_BYTES);
 }
 
 bool lower_stream_applies(const Shard *e) {
@@ -394,32 +378,20 @@ bool lower_stream_applies(const Shard *e) {
 	       !e->incremental_pass && !e->lstream_desc.empty();
 }
 
-// a device array of `count` ints that only grows (the exponents of the power-of-two rescaling)
-int ensure_ints(Shard *e, int **p, size_t *have, size_t count) {
-	if (*p && *have >= count) return PHYAMD_OK;
-	dev_free(e, p, *have);
-	*have = 0;
-	int rc = dev_alloc(e, p, count);
-	if (!rc) *have = count;
-	return rc;
-}
-
 // the exponents of the power-of-two rescaling (LowerForm::CarriedExp2), the pre-order walk's included: made before the post-order
 // pass that writes that form, so that a memory cap without room for them is met while the reference's form can still be written
 int ensure_exponent_storage(Shard *e) {
 	int rc;
-	if ((rc = ensure_ints(e, &e->d_lexp, &e->lexp_alloc, e->lower_alloc_cores * (size_t)e->C * e->P))) return rc;
-	if ((rc = ensure_ints(e, &e->d_uexp, &e->uexp_alloc, std::max(e->upper_alloc_slots, upper_slots_needed(e)) * e->C * e->P))) return rc;
-	if (!e->d_Ec && (rc = dev_alloc(e, &e->d_Ec, (size_t)e->C * e->P))) return rc;
-	if (!e->d_Eroot && (rc = dev_alloc(e, &e->d_Eroot, (size_t)e->P))) return rc;
+	if ((rc = e->d_lexp.ensure(lower_slots(e) * e->C * e->P)) || (rc = e->d_uexp.ensure(std::max(upper_slots_held(e), upper_slots_needed(e)) * e->C * e->P)) ||
+	    (rc = e->d_Ec.ensure((size_t)e->C * e->P)) || (rc = e->d_Eroot.ensure(e->P)))
+		return rc;
 	return PHYAMD_OK;
 }
 void free_exponent_storage(Shard *e) {
-	dev_free(e, &e->d_lexp, e->lexp_alloc);
-	dev_free(e, &e->d_uexp, e->uexp_alloc);
-	e->lexp_alloc = e->uexp_alloc = 0;
-	dev_free(e, &e->d_Ec, (size_t)e->C * e->P);
-	dev_free(e, &e->d_Eroot, (size_t)e->P);
+	e->d_lexp.release();
+	e->d_uexp.release();
+	e->d_Ec.release();
+	e->d_Eroot.release();
 }
 
 // the streamed post-order walk (k_lower4_stream): every cut subtree as workgroups of its own, then the top part with the root
@@ -431,7 +403,7 @@ int launch_lower_stream(Shard *e) {
 		if (e->stream_P != e->P || e->stream_mstride != e->mstride) return fail(PHYAMD_EDEVICE, "streamed walk: descriptors do not match the pattern storage");
 	}
 	hipLaunchKernelGGL(k_op_tables, dim3(nops, e->C), dim3(64), 0, e->stream, nops, e->C, (const int *)e->d_stream_op_tips, (const int *)e->d_stream_op_deep,
-	                   (const int *)e->d_stream_site_tab, e->d_mats, (const double *)nullptr, reinterpret_cast<double *>(e->d_optab));
+	                   (const int *)e->d_stream_site_tab, e->d_mats, (const double *)nullptr, reinterpret_cast<double *>(e->d_optab.get()));
 	// rescaled: powers of two per category (the plain workgroup shape), or the reference's maxima over categories -- workgroup = the
 	// category waves of one block + their exchange buffer
 	const LowerForm form = stream_lower_form(e);
@@ -452,7 +424,7 @@ int launch_lower_stream(Shard *e) {
 		hipLaunchKernelGGL(kernel, dim3(gx, phase ? 1 : subtrees), dim3(WAVE, waves), lds, e->stream, (const LowerDesc *)e->d_lstream_ops,
 		                   (const LowerChunk *)e->d_lstream_chunks, (const int *)e->d_walk_lower_chunk_off, phase ? std::max(0, subtrees) : 0, nops, e->P, e->C, nb,
 		                   (const uint32_t *)e->d_mstream, e->mstride, e->d_lower, (const double *)e->d_mats, (const char *)e->d_optab, (const double *)e->d_freqs,
-		                   (const double *)e->d_props, e->d_Lc, phase, exp2 ? reinterpret_cast<double *>(e->d_lexp) : scale ? e->d_lscale : (double *)nullptr, e->xcd_map,
+		                   (const double *)e->d_props, e->d_Lc, phase, exp2 ? reinterpret_cast<double *>(e->d_lexp.get()) : scale ? e->d_lscale : (double *)nullptr, e->xcd_map,
 		                   exp2 ? e->d_Ec : (int *)nullptr);
 	hipLaunchKernelGGL(k_root_finish64, dim3(nb), dim3(64), 0, e->stream, e->P, e->C, (const double *)e->d_Lc, (const double *)e->d_weights, e->d_plk, e->d_wl, e->d_lnl_part,
 	                   scale ? (const double *)(e->d_lscale + (size_t)e->core_index[e->root] * e->P) : (const double *)nullptr, exp2 ? (const int *)e->d_Ec : (const int *)nullptr,
@@ -478,23 +450,18 @@ int launch_upper_stream(Shard *e) {
 		if ((rc = upload_schedule(e))) return rc;
 		if (e->stream_P != e->P || e->stream_mstride != e->mstride) return fail(PHYAMD_EDEVICE, "streamed walk: descriptors do not match the pattern storage");
 	}
-	if ((size_t)8 * e->C * R > e->oct_alloc) {
-		dev_free(e, &e->d_oct, e->oct_alloc);
-		e->oct_alloc = 0;
-		if ((rc = dev_alloc(e, &e->d_oct, (size_t)8 * e->C * R))) return rc;
-		e->oct_alloc = (size_t)8 * e->C * R;
-	}
+	if ((rc = e->d_oct.ensure((size_t)8 * e->C * R))) return rc;
 	// plain: workgroup = four blocks of one category; rescaled as the reference does: the C <= 4 category waves of one block + their
 	// exchange buffers; rescaled by powers of two (the stored lowers are in that form): the plain shape + the parks' exponents
 	const StreamVariant v = stream_variant(e->lower_form, SCALE);  // (the stored lowers decide: they are what this walk reads)
 	if (v.scale < 0) return fail(PHYAMD_EDEVICE, "streamed walk: the stored lowers hold the %s form, which no %s post-order pass writes", form_name(e->lower_form), SCALE ? "rescaled" : "plain");
 	const bool exp2 = v.scale == 2, tf = v.tf;
-	if (exp2 && (rc = ensure_ints(e, &e->d_uexp, &e->uexp_alloc, std::max<size_t>(1, e->upper_alloc_slots) * e->C * e->P))) return rc;
+	if (exp2 && (rc = e->d_uexp.ensure(std::max<size_t>(1, upper_slots_held(e)) * e->C * e->P))) return rc;
 	const int waves = SCALE && !exp2 ? e->C : STREAM_WAVES;
 	const size_t lds = (size_t)STREAM_LDS_PER_WAVE * waves + (exp2 ? (size_t)waves * STREAM_PARK_SLOTS * WAVE * sizeof(int) : SCALE ? (size_t)4 * e->C * WAVE * sizeof(double) : 0);
 	const dim3 grid_x(SCALE && !exp2 ? (unsigned)nb : (unsigned)((nb + STREAM_WAVES - 1) / STREAM_WAVES) * e->C), block(WAVE, waves);
 	hipLaunchKernelGGL(k_op_tables, dim3(nops, e->C), dim3(64), 0, e->stream, nops, e->C, (const int *)e->d_stream_op_tips, (const int *)e->d_stream_op_deep,
-	                   (const int *)e->d_stream_site_tab, e->d_mats, FOLD ? e->d_Q : e->d_Qpi, reinterpret_cast<double *>(e->d_optab));
+	                   (const int *)e->d_stream_site_tab, e->d_mats, FOLD ? e->d_Q : e->d_Qpi, reinterpret_cast<double *>(e->d_optab.get()));
 	const int subtrees = (int)e->walk_chunk_off.size() - 2;
 	for (int phase = 0; phase < (subtrees > 0 ? 2 : 1); phase++) {
 		const bool amb = e->stream_ambiguous;
@@ -531,13 +498,7 @@ void bisect_blocks(int lo, int hi, int levels, std::vector<int> &bounds) {
 int reduce_block_sums(Shard *e, int which, const double *slab, int nb, int C, int R, const int *row_of, double *out) {
 	int rc;
 	const int segments = 1 << e->reduce_levels;
-	if (!e->d_oct_lo && (rc = dev_alloc(e, &e->d_oct_lo, (size_t)20))) return rc;
-	if ((size_t)8 * C * R > e->oct_alloc) {
-		dev_free(e, &e->d_oct, e->oct_alloc);
-		e->oct_alloc = 0;
-		if ((rc = dev_alloc(e, &e->d_oct, (size_t)8 * C * R))) return rc;
-		e->oct_alloc = (size_t)8 * C * R;
-	}
+	if ((rc = e->d_oct_lo.ensure(20)) || (rc = e->d_oct.ensure((size_t)8 * C * R))) return rc;
 	int *table = e->d_oct_lo + 10 * which;
 	if (e->seg_nb[which] != nb || e->seg_levels[which] != e->reduce_levels) {
 		std::vector<int> bounds;
@@ -633,15 +594,9 @@ int launch_upper_walk_params(Shard *e) {
 	int rc;
 	if ((rc = check_reference_form(e, "k_upper4_walk (parameters)"))) return rc;
 	if ((rc = upload_qpi(e))) return rc;
-	if ((size_t)np > e->np_alloc_B) {
-		dev_free(e, &e->d_Bw, e->np_alloc_B * 16);
-		e->np_alloc_B = 0;
-		if ((rc = dev_alloc(e, &e->d_Bw, (size_t)np * 16))) return rc;
-		e->np_alloc_B = np;
-	}
-	if (!e->d_pbuf && (rc = dev_alloc(e, &e->d_pbuf, 96))) return rc;
-	if (!e->d_Fw && (rc = dev_alloc(e, &e->d_Fw, (size_t)e->N * e->C * 20))) return rc;
-	if (!e->d_gacc && (rc = dev_alloc(e, &e->d_gacc, (size_t)16 * nb * e->C + 16))) return rc;
+	if ((rc = e->d_Bw.ensure((size_t)np * 16)) || (rc = e->d_pbuf.ensure(96)) || (rc = e->d_Fw.ensure((size_t)e->N * e->C * 20)) ||
+	    (rc = e->d_gacc.ensure((size_t)16 * nb * e->C + 16)))
+		return rc;
 	{
 		const double *evec = e->model.data() + S, *ivec = e->model.data() + S + S * S;
 		const std::vector<double> B = eigen_basis_derivatives(e);
@@ -727,14 +682,7 @@ int ensure_gen_scale_storage(Shard *e, int rows = 5) {
 	int widest = 1;
 	for (size_t i = 0; i + 1 < e->lower_level_off.size(); i++) widest = std::max(widest, e->lower_level_off[i + 1] - e->lower_level_off[i]);
 	for (size_t i = 0; i + 1 < e->upper_level_off.size(); i++) widest = std::max(widest, e->upper_level_off[i + 1] - e->upper_level_off[i]);
-	const size_t need = (size_t)widest * rows * e->C * e->P;
-	if (e->d_gen_scratch && e->gen_scratch_alloc >= need) return PHYAMD_OK;
-	dev_free(e, &e->d_gen_scratch, e->gen_scratch_alloc);
-	e->gen_scratch_alloc = 0;
-	int rc = dev_alloc(e, &e->d_gen_scratch, need);
-	if (rc) return rc;
-	e->gen_scratch_alloc = need;
-	return PHYAMD_OK;
+	return e->d_gen_scratch.ensure((size_t)widest * rows * e->C * e->P);
 }
 
 // 16-pattern tiles per wave for one level of `work` = ops x categories workgroup columns.  A workgroup costs one staging of its
@@ -850,7 +798,7 @@ int launch_upper_gen_hess(Shard *e, double *out) {
 	if ((rc = allow_big_lds(k_upper_gen<RT, KT, false, SCALE, true>, lds))) return rc;
 	if ((rc = ensure_gen_scale_storage(e, 7))) return rc;
 	if (GenFuse<RT>::QP && (rc = ensure_tip_rate_products(e, false))) return rc;
-	if (!e->d_hess_invf && (rc = dev_alloc(e, &e->d_hess_invf, (size_t)S))) return rc;
+	if ((rc = e->d_hess_invf.ensure(S))) return rc;
 	std::vector<double> invf(S);
 	for (int i = 0; i < S; i++) invf[i] = 1.0 / e->freqs[i];
 	HIP_TRY(hipMemcpyAsync(e->d_hess_invf, invf.data(), sizeof(double) * S, hipMemcpyHostToDevice, e->stream));
@@ -900,7 +848,7 @@ int launch_lower_gen_walk(Shard *e) {
 	if (e->gen_walk_slots[0] == 0) e->gen_walk_slots[0] = resident_workgroups(e, k_lower_gen_walk<RT, KT>, WV * 64, lds);
 	const int groups = (e->P + WV * 16 - 1) / (WV * 16), nops = (int)e->walk_lower_ops.size(), units = groups * e->C;
 	const int wgs = std::max(1, std::min(units, e->gen_walk_slots[0]));
-	if (!e->d_gen_walk_counter && (rc = dev_alloc(e, &e->d_gen_walk_counter, (size_t)1))) return rc;
+	if ((rc = e->d_gen_walk_counter.ensure(1))) return rc;
 	HIP_TRY(hipMemsetAsync(e->d_gen_walk_counter, 0, sizeof(int), e->stream));
 	hipLaunchKernelGGL((k_lower_gen_walk<RT, KT>), dim3(wgs), dim3(WV * 64), lds, e->stream, e->d_walk_lower_ops, nops, e->T, e->P, e->Pp, e->C, e->d_tipmask,
 	                   e->d_tipsets, e->d_lower, e->d_imgs, e->d_freqs, e->d_props, e->d_Lc, units, e->d_gen_walk_counter);

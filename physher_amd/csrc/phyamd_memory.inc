@@ -1,0 +1,81 @@
+// phyamd_memory.inc -- owning device arrays and the budget a shard allocates them through
+// (part of phyamd_engine.hip: one translation unit, internal linkage)
+
+class DeviceBuffer;
+
+// the device memory of one shard: the bytes its arrays hold and the cap on them (cfg.max_device_bytes; <= 0: none) -- or of a
+// group of its arrays, whose bytes also count in the shard's budget (`whole`)
+struct DeviceBudget {
+	explicit DeviceBudget(DeviceBudget *whole = nullptr) : whole(whole) {}
+	int64_t cap = 0;
+	int64_t bytes = 0;
+	DeviceBudget *const whole;
+	std::vector<DeviceBuffer *> arrays;  // the arrays bound to this budget
+	void release_all();
+};
+
+// device memory owned by one array, bound to a budget for its lifetime (none: a scoped temporary, not counted).  Allocating checks
+// the cap and adds the bytes; release() and the destructor free the array and take exactly those bytes off again.
+class DeviceBuffer {
+public:
+	explicit DeviceBuffer(DeviceBudget *budget) : budget_(budget) {
+		if (budget_) budget_->arrays.push_back(this);
+	}
+	DeviceBuffer(const DeviceBuffer &) = delete;
+	DeviceBuffer &operator=(const DeviceBuffer &) = delete;
+	~DeviceBuffer() {
+		release();
+		if (budget_) budget_->arrays.erase(std::find(budget_->arrays.begin(), budget_->arrays.end(), this));
+	}
+	size_t bytes() const { return bytes_; }
+	void release() {
+		if (!p_) return;
+		(void)hipFree(p_);
+		for (DeviceBudget *b = budget_; b; b = b->whole) b->bytes -= (int64_t)bytes_;
+		p_ = nullptr;
+		bytes_ = 0;
+	}
+	void swap(DeviceBuffer &o) {  // (two arrays of one budget)
+		std::swap(p_, o.p_);
+		std::swap(bytes_, o.bytes_);
+	}
+
+protected:
+	// at least `bytes`: kept if it holds as many, else freed and allocated anew (*grew: the old contents are gone)
+	int reserve(size_t bytes, bool *grew) {
+		if (grew) *grew = false;
+		if (p_ && bytes_ >= bytes) return PHYAMD_OK;
+		release();
+		for (DeviceBudget *b = budget_; b; b = b->whole)
+			if (b->cap > 0 && b->bytes + (int64_t)bytes > b->cap)
+				return fail(PHYAMD_ENOMEM, "max_device_bytes (%lld) would be exceeded: %lld bytes resident, %zu more requested", (long long)b->cap,
+				            (long long)b->bytes, bytes);
+		void *p = nullptr;
+		HIP_TRY(hipMalloc(&p, bytes));
+		p_ = p;
+		bytes_ = bytes;
+		for (DeviceBudget *b = budget_; b; b = b->whole) b->bytes += (int64_t)bytes;
+		if (grew) *grew = true;
+		return PHYAMD_OK;
+	}
+	void *p_ = nullptr;
+	size_t bytes_ = 0;
+
+private:
+	DeviceBudget *const budget_;
+};
+
+void DeviceBudget::release_all() {
+	for (DeviceBuffer *a : arrays) a->release();
+}
+
+template <typename T>
+class DeviceArray : public DeviceBuffer {
+public:
+	explicit DeviceArray(DeviceBudget *budget = nullptr) : DeviceBuffer(budget) {}
+	operator T *() const { return static_cast<T *>(p_); }
+	T *get() const { return static_cast<T *>(p_); }
+	size_t size() const { return bytes_ / sizeof(T); }
+	// at least `count` elements (0: one); see reserve
+	int ensure(size_t count, bool *grew = nullptr) { return reserve(std::max<size_t>(count, 1) * sizeof(T), grew); }
+};

@@ -127,15 +127,6 @@ __global__ __launch_bounds__(256) void k_pattern_emit(int T, size_t L, unsigned 
 	for (int t = blockIdx.y; t < T; t += gridDim.y) patterns[(size_t)t * n + k] = codes[(size_t)t * L + site];
 }
 
-struct DeviceBlock {  // hipFree on scope exit
-	void *p = nullptr;
-	~DeviceBlock() {
-		if (p) (void)hipFree(p);
-	}
-	template <typename Tp>
-	Tp *as() const { return static_cast<Tp *>(p); }
-};
-
 int compress_patterns_device(int device, int T, int64_t L64, const uint8_t *const *rows, const uint8_t *lut, int32_t *pattern_count, uint8_t *patterns,
                              double *weights) {
 	if (T < 1 || L64 < 1 || !rows || !pattern_count || !patterns || !weights) return fail(PHYAMD_EINVAL, "bad argument");
@@ -147,60 +138,56 @@ int compress_patterns_device(int device, int T, int64_t L64, const uint8_t *cons
 	if (device >= 0) HIP_TRY(hipSetDevice(device));
 	const size_t L = (size_t)L64;
 	hipStream_t st = nullptr;  // the null stream: this is a one-off, synchronous call
-	DeviceBlock codes, lutd, keys0, keys1, val0, val1, head, scan, gstart, gsite, ghash, rank, flag, tmp, outp, outw;
-	HIP_TRY(hipMalloc(&codes.p, (size_t)T * L));
-	HIP_TRY(hipMalloc(&keys0.p, 8 * L));
-	HIP_TRY(hipMalloc(&keys1.p, 8 * L));
-	HIP_TRY(hipMalloc(&val0.p, 4 * L));
-	HIP_TRY(hipMalloc(&val1.p, 4 * L));
-	HIP_TRY(hipMalloc(&head.p, 4 * L));
-	HIP_TRY(hipMalloc(&scan.p, 4 * L));
-	HIP_TRY(hipMalloc(&flag.p, sizeof(int)));
-	HIP_TRY(hipMemsetAsync(flag.p, 0, sizeof(int), st));
+	// scoped temporaries, not counted against any engine's memory
+	DeviceArray<uint8_t> codes, lutd, outp;
+	DeviceArray<unsigned long long> keys0, keys1;
+	DeviceArray<unsigned> val0, val1, head, scan, gstart, gsite, ghash, rank;
+	DeviceArray<int> flag;
+	DeviceArray<char> tmp;
+	DeviceArray<double> outw;
+	int rc;
+	if ((rc = codes.ensure((size_t)T * L)) || (rc = keys0.ensure(L)) || (rc = keys1.ensure(L)) || (rc = val0.ensure(L)) || (rc = val1.ensure(L)) ||
+	    (rc = head.ensure(L)) || (rc = scan.ensure(L)) || (rc = flag.ensure(1)))
+		return rc;
+	HIP_TRY(hipMemsetAsync(flag, 0, sizeof(int), st));
 	for (int t = 0; t < T; t++) {
 		if (!rows[t]) return fail(PHYAMD_EINVAL, "row %d is null", t);
-		HIP_TRY(hipMemcpyAsync(codes.as<uint8_t>() + (size_t)t * L, rows[t], L, hipMemcpyHostToDevice, st));
+		HIP_TRY(hipMemcpyAsync(codes + (size_t)t * L, rows[t], L, hipMemcpyHostToDevice, st));
 	}
 	if (lut) {
-		HIP_TRY(hipMalloc(&lutd.p, 256));
-		HIP_TRY(hipMemcpyAsync(lutd.p, lut, 256, hipMemcpyHostToDevice, st));
+		if ((rc = lutd.ensure(256))) return rc;
+		HIP_TRY(hipMemcpyAsync(lutd, lut, 256, hipMemcpyHostToDevice, st));
 	}
 	const unsigned lb = (unsigned)((L + 255) / 256);
-	hipLaunchKernelGGL(k_pattern_hash, dim3(lb), dim3(256), 0, st, T, L, codes.as<uint8_t>(), lutd.as<uint8_t>(), keys0.as<unsigned long long>(), val0.as<unsigned>());
+	hipLaunchKernelGGL(k_pattern_hash, dim3(lb), dim3(256), 0, st, T, L, codes, lutd, keys0, val0);
 	// one temporary block serves every sort / scan below (sizes queried for the largest problem)
 	size_t b1 = 0, b2 = 0, b3 = 0;
-	HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, b1, keys0.as<unsigned long long>(), keys1.as<unsigned long long>(), val0.as<unsigned>(), val1.as<unsigned>(),
-	                                           (int)L, 0, 64, st));
-	HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, b2, head.as<unsigned>(), scan.as<unsigned>(), (int)L, st));
-	HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, b3, val0.as<unsigned>(), val1.as<unsigned>(), val0.as<unsigned>(), val1.as<unsigned>(), (int)L, 0, 32, st));
+	HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, b1, keys0.get(), keys1.get(), val0.get(), val1.get(), (int)L, 0, 64, st));
+	HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, b2, head.get(), scan.get(), (int)L, st));
+	HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, b3, val0.get(), val1.get(), val0.get(), val1.get(), (int)L, 0, 32, st));
 	size_t tmp_bytes = std::max(b1, std::max(b2, b3));
-	HIP_TRY(hipMalloc(&tmp.p, tmp_bytes));
-	HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, keys0.as<unsigned long long>(), keys1.as<unsigned long long>(), val0.as<unsigned>(),
-	                                           val1.as<unsigned>(), (int)L, 0, 64, st));
-	const unsigned long long *skeys = keys1.as<unsigned long long>();
-	const unsigned *ssites = val1.as<unsigned>();
-	hipLaunchKernelGGL(k_pattern_heads, dim3(lb), dim3(256), 0, st, T, L, codes.as<uint8_t>(), skeys, ssites, head.as<unsigned>(), flag.as<int>());
+	if ((rc = tmp.ensure(tmp_bytes))) return rc;
+	HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, keys0.get(), keys1.get(), val0.get(), val1.get(), (int)L, 0, 64, st));
+	const unsigned long long *skeys = keys1;
+	const unsigned *ssites = val1;
+	hipLaunchKernelGGL(k_pattern_heads, dim3(lb), dim3(256), 0, st, T, L, codes, skeys, ssites, head, flag);
 	tmp_bytes = std::max(b1, std::max(b2, b3));
-	HIP_TRY(hipcub::DeviceScan::InclusiveSum(tmp.p, tmp_bytes, head.as<unsigned>(), scan.as<unsigned>(), (int)L, st));
+	HIP_TRY(hipcub::DeviceScan::InclusiveSum(tmp, tmp_bytes, head.get(), scan.get(), (int)L, st));
 	unsigned n = 0;
 	int collided = 0;
-	HIP_TRY(hipMemcpyAsync(&n, scan.as<unsigned>() + (L - 1), sizeof(unsigned), hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipMemcpyAsync(&collided, flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipMemcpyAsync(&n, scan + (L - 1), sizeof(unsigned), hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipMemcpyAsync(&collided, flag, sizeof(int), hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipStreamSynchronize(st));
 	if (collided) return fail(PHYAMD_EUNSUPPORTED, "two different columns share both hashes: compress this alignment on the host");
-	HIP_TRY(hipMalloc(&gstart.p, 4 * (size_t)n));
-	HIP_TRY(hipMalloc(&gsite.p, 4 * (size_t)n));
-	HIP_TRY(hipMalloc(&ghash.p, 4 * (size_t)n));
-	HIP_TRY(hipMalloc(&rank.p, 4 * (size_t)n));
+	if ((rc = gstart.ensure(n)) || (rc = gsite.ensure(n)) || (rc = ghash.ensure(n)) || (rc = rank.ensure(n))) return rc;
 	// group tables; val0 / keys0 are free again: val0 = group ids, then the working permutation
-	hipLaunchKernelGGL(k_pattern_groups, dim3(lb), dim3(256), 0, st, L, head.as<unsigned>(), scan.as<unsigned>(), skeys, ssites, gstart.as<unsigned>(),
-	                   gsite.as<unsigned>(), ghash.as<unsigned>(), val0.as<unsigned>());
+	hipLaunchKernelGGL(k_pattern_groups, dim3(lb), dim3(256), 0, st, L, head, scan, skeys, ssites, gstart, gsite, ghash, val0);
 	const unsigned nb = (n + 255) / 256;
 	// insertion rank = position among the groups ordered by first site (head/scan are free: reuse as sort buffers)
-	unsigned *site_sorted = head.as<unsigned>(), *order = scan.as<unsigned>();
+	unsigned *site_sorted = head, *order = scan;
 	tmp_bytes = std::max(b1, std::max(b2, b3));
-	HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, gsite.as<unsigned>(), site_sorted, val0.as<unsigned>(), order, (int)n, 0, 32, st));
-	hipLaunchKernelGGL(k_pattern_ranks, dim3(nb), dim3(256), 0, st, n, order, rank.as<unsigned>());
+	HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, gsite.get(), site_sorted, val0.get(), order, (int)n, 0, 32, st));
+	hipLaunchKernelGGL(k_pattern_ranks, dim3(nb), dim3(256), 0, st, n, order, rank);
 	PatternEpochs ep;
 	for (int j = 0; j < PATTERN_PRIME_COUNT; j++) {
 		ep.size[j] = PATTERN_PRIMES[j];
@@ -210,23 +197,21 @@ int compress_patterns_device(int device, int T, int64_t L64, const uint8_t *cons
 	ep.last = PATTERN_FIRST_PRIME;
 	while (n - 1 >= ep.limit[ep.last]) ep.last++;
 	// stable sorts, oldest table first; perm ping-pongs between val0 and val1, keys between keys0 and keys1
-	unsigned *perm = val0.as<unsigned>(), *perm_alt = val1.as<unsigned>();
-	unsigned long long *key = keys0.as<unsigned long long>(), *key_alt = keys1.as<unsigned long long>();
+	unsigned *perm = val0, *perm_alt = val1;
+	unsigned long long *key = keys0, *key_alt = keys1;
 	for (int level = PATTERN_FIRST_PRIME; level <= ep.last + 1; level++) {
 		const bool final_pass = level == ep.last + 1;
-		if (final_pass) hipLaunchKernelGGL(k_pattern_bucket, dim3(nb), dim3(256), 0, st, n, ep.size[ep.last], perm, ghash.as<unsigned>(), key);
-		else hipLaunchKernelGGL(k_pattern_component, dim3(nb), dim3(256), 0, st, n, level, ep, perm, rank.as<unsigned>(), ghash.as<unsigned>(), key);
+		if (final_pass) hipLaunchKernelGGL(k_pattern_bucket, dim3(nb), dim3(256), 0, st, n, ep.size[ep.last], perm, ghash, key);
+		else hipLaunchKernelGGL(k_pattern_component, dim3(nb), dim3(256), 0, st, n, level, ep, perm, rank, ghash, key);
 		tmp_bytes = std::max(b1, std::max(b2, b3));
-		HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, key, key_alt, perm, perm_alt, (int)n, 0, final_pass ? 32 : 33, st));
+		HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, key, key_alt, perm, perm_alt, (int)n, 0, final_pass ? 32 : 33, st));
 		std::swap(perm, perm_alt);
 	}
-	HIP_TRY(hipMalloc(&outp.p, (size_t)T * n));
-	HIP_TRY(hipMalloc(&outw.p, 8 * (size_t)n));
-	hipLaunchKernelGGL(k_pattern_emit, dim3(nb, (unsigned)std::min(T, 64)), dim3(256), 0, st, T, L, n, codes.as<uint8_t>(), perm, gstart.as<unsigned>(),
-	                   gsite.as<unsigned>(), outp.as<uint8_t>(), outw.as<double>());
+	if ((rc = outp.ensure((size_t)T * n)) || (rc = outw.ensure(n))) return rc;
+	hipLaunchKernelGGL(k_pattern_emit, dim3(nb, (unsigned)std::min(T, 64)), dim3(256), 0, st, T, L, n, codes, perm, gstart, gsite, outp, outw);
 	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpyAsync(patterns, outp.p, (size_t)T * n, hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipMemcpyAsync(weights, outw.p, 8 * (size_t)n, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipMemcpyAsync(patterns, outp, (size_t)T * n, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipMemcpyAsync(weights, outw, 8 * (size_t)n, hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipStreamSynchronize(st));
 	*pattern_count = (int32_t)n;
 	return PHYAMD_OK;

@@ -1,25 +1,5 @@
-// phyamd_schedule.inc -- device memory helpers, the level / tree-walk schedules and their storage
+// phyamd_schedule.inc -- the level / tree-walk schedules and their storage
 // (part of phyamd_engine.hip: one translation unit, internal linkage)
-
-template <typename Tp>
-int dev_alloc(Shard *e, Tp **p, size_t count) {
-	if (count == 0) count = 1;
-	if (e->cfg.max_device_bytes > 0 && e->device_bytes + (int64_t)(count * sizeof(Tp)) > e->cfg.max_device_bytes)
-		return fail(PHYAMD_ENOMEM, "max_device_bytes (%lld) would be exceeded: %lld bytes resident, %zu more requested", (long long)e->cfg.max_device_bytes,
-		            (long long)e->device_bytes, count * sizeof(Tp));
-	HIP_TRY(hipMalloc(reinterpret_cast<void **>(p), count * sizeof(Tp)));
-	e->device_bytes += (int64_t)(count * sizeof(Tp));
-	return PHYAMD_OK;
-}
-
-template <typename Tp>
-void dev_free(Shard *e, Tp **p, size_t count) {
-	if (*p) {
-		(void)hipFree(*p);
-		e->device_bytes -= (int64_t)((count ? count : 1) * sizeof(Tp));
-		*p = nullptr;
-	}
-}
 
 int bind_device(Shard *e) {
 	HIP_TRY(hipSetDevice(e->device));
@@ -27,6 +7,8 @@ int bind_device(Shard *e) {
 }
 
 size_t node_partial_doubles(const Shard *e) { return (size_t)e->C * e->S * (e->generic ? e->Pp : e->P); }
+size_t lower_slots(const Shard *e) { return e->d_lower.size() / node_partial_doubles(e); }  // node partials d_lower holds
+size_t upper_slots_held(const Shard *e) { return e->d_upper.size() / node_partial_doubles(e); }
 
 // Build the level schedule and the upper-slot assignment.
 // Chunked form of the pre-order walk (the launches with LDS park slots).  A workgroup's walk takes as long whatever shares its CU,
@@ -839,14 +821,10 @@ int build_schedule(Shard *e) {
 
 int ensure_lower_storage(Shard *e) {
 	const size_t need = (size_t)std::max(1, e->core_count) * (e->two_slots ? 2 : 1);
-	if (e->d_lower && e->lower_alloc_cores >= need) return PHYAMD_OK;
-	dev_free(e, &e->d_lower, e->lower_alloc_cores * node_partial_doubles(e));
-	dev_free(e, &e->d_lscale, e->lower_alloc_cores * (size_t)e->P);
-	e->lower_alloc_cores = 0;
-	int rc = dev_alloc(e, &e->d_lower, need * node_partial_doubles(e));
-	if (rc) return rc;
-	e->lower_alloc_cores = need;
-	return PHYAMD_OK;
+	if (lower_slots(e) >= need) return PHYAMD_OK;
+	e->d_lower.release();
+	e->d_lscale.release();  // (sized by d_lower: ensure_scaling_storage)
+	return e->d_lower.ensure(need * node_partial_doubles(e));
 }
 
 // after slots moved (store / restore): the ops carry slot indices
@@ -862,8 +840,7 @@ void refresh_op_cores(Shard *e) {
 int upload_schedule(Shard *e) {
 	// op tables are a few KB: allocated once at the maximum size (N - T ops each)
 	int rc;
-	if (!e->d_lower_ops && (rc = dev_alloc(e, &e->d_lower_ops, (size_t)e->N))) return rc;
-	if (!e->d_upper_ops && (rc = dev_alloc(e, &e->d_upper_ops, (size_t)e->N))) return rc;
+	if ((rc = e->d_lower_ops.ensure(e->N)) || (rc = e->d_upper_ops.ensure(e->N))) return rc;
 	HIP_TRY(hipMemcpyAsync(e->d_lower_ops, e->lower_ops.data(), e->lower_ops.size() * sizeof(NodeOp), hipMemcpyHostToDevice, e->stream));
 	HIP_TRY(hipMemcpyAsync(e->d_upper_ops, e->upper_ops.data(), e->upper_ops.size() * sizeof(NodeOp), hipMemcpyHostToDevice, e->stream));
 	static_assert(sizeof(DeepDesc) == 6 * sizeof(double), "DeepDesc is laid out in the tail of the tip-message table");
@@ -871,29 +848,24 @@ int upload_schedule(Shard *e) {
 		HIP_TRY(hipMemcpyAsync(e->d_tiptab + (size_t)e->T * e->C * 64, e->deep_host.data(), e->deep_host.size() * sizeof(DeepDesc), hipMemcpyHostToDevice,
 		                       e->stream));
 	if (e->walking || e->gen_walking) {
-		if (!e->d_walk_lower_ops && (rc = dev_alloc(e, &e->d_walk_lower_ops, (size_t)e->N))) return rc;
-		if (!e->d_walk_upper_ops && (rc = dev_alloc(e, &e->d_walk_upper_ops, (size_t)e->N))) return rc;
+		if ((rc = e->d_walk_lower_ops.ensure(e->N)) || (rc = e->d_walk_upper_ops.ensure(e->N))) return rc;
 		HIP_TRY(hipMemcpyAsync(e->d_walk_lower_ops, e->walk_lower_ops.data(), e->walk_lower_ops.size() * sizeof(NodeOp), hipMemcpyHostToDevice, e->stream));
 		HIP_TRY(hipMemcpyAsync(e->d_walk_upper_ops, e->walk_upper_ops.data(), e->walk_upper_ops.size() * sizeof(NodeOp), hipMemcpyHostToDevice, e->stream));
 	}
 	if (e->walking) {
-		if (!e->d_walk_chunk_ops && ((rc = dev_alloc(e, &e->d_walk_chunk_ops, (size_t)e->N)) || (rc = dev_alloc(e, &e->d_walk_chunk_off, (size_t)e->N + 2)))) return rc;
+		if ((rc = e->d_walk_chunk_ops.ensure(e->N)) || (rc = e->d_walk_chunk_off.ensure((size_t)e->N + 2))) return rc;
 		HIP_TRY(hipMemcpyAsync(e->d_walk_chunk_ops, e->walk_chunk_ops.data(), e->walk_chunk_ops.size() * sizeof(NodeOp), hipMemcpyHostToDevice, e->stream));
 		HIP_TRY(hipMemcpyAsync(e->d_walk_chunk_off, e->walk_chunk_off.data(), e->walk_chunk_off.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
-		if (!e->d_walk_lower_chunk_ops && ((rc = dev_alloc(e, &e->d_walk_lower_chunk_ops, (size_t)e->N)) || (rc = dev_alloc(e, &e->d_walk_lower_chunk_off, (size_t)e->N + 2))))
-			return rc;
+		if ((rc = e->d_walk_lower_chunk_ops.ensure(e->N)) || (rc = e->d_walk_lower_chunk_off.ensure((size_t)e->N + 2))) return rc;
 		HIP_TRY(hipMemcpyAsync(e->d_walk_lower_chunk_ops, e->walk_lower_chunk_ops.data(), e->walk_lower_chunk_ops.size() * sizeof(NodeOp), hipMemcpyHostToDevice, e->stream));
 		HIP_TRY(hipMemcpyAsync(e->d_walk_lower_chunk_off, e->walk_lower_chunk_off.data(), e->walk_lower_chunk_off.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
 		if (e->T >= (1 << 20)) e->stream_walk = false;  // (a packed mask-word entry keeps 20 bits of tip id: the table-gather walks beyond that)
 		if (e->stream_walk) {  // the streamed pre-order walk's tables follow the chunked list (core indices included: store / restore moves them)
 			build_stream_ops(e);
 			build_lower_stream_ops(e);
-			if (!e->d_stream_ops &&
-			    ((rc = dev_alloc(e, &e->d_stream_ops, (size_t)e->N)) || (rc = dev_alloc(e, &e->d_stream_chunks, (size_t)e->N + 2)) ||
-			     (rc = dev_alloc(e, &e->d_stream_row_entries, (size_t)e->N * 32)) || (rc = dev_alloc(e, &e->d_stream_site_tab, (size_t)e->N * 16)) ||
-			     (rc = dev_alloc(e, &e->d_stream_qnode, (size_t)e->N)) ||
-			     (rc = dev_alloc(e, &e->d_stream_op_tips, (size_t)e->N * 12)) || (rc = dev_alloc(e, &e->d_stream_flag, (size_t)1)) ||
-			     (rc = dev_alloc(e, &e->d_stream_op_deep, (size_t)e->N))))
+			if ((rc = e->d_stream_ops.ensure(e->N)) || (rc = e->d_stream_chunks.ensure((size_t)e->N + 2)) || (rc = e->d_stream_row_entries.ensure((size_t)e->N * 32)) ||
+			    (rc = e->d_stream_site_tab.ensure((size_t)e->N * 16)) || (rc = e->d_stream_qnode.ensure(e->N)) || (rc = e->d_stream_op_tips.ensure((size_t)e->N * 12)) ||
+			    (rc = e->d_stream_flag.ensure(1)) || (rc = e->d_stream_op_deep.ensure(e->N)))
 				return rc;
 			HIP_TRY(hipMemcpyAsync(e->d_stream_op_tips, e->stream_op_tips.data(), e->stream_op_tips.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
 			HIP_TRY(hipMemcpyAsync(e->d_stream_op_deep, e->stream_op_deep.data(), e->stream_op_deep.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
@@ -902,7 +874,7 @@ int upload_schedule(Shard *e) {
 			HIP_TRY(hipMemcpyAsync(e->d_stream_row_entries, e->stream_row_entries.data(), e->stream_row_entries.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
 			HIP_TRY(hipMemcpyAsync(e->d_stream_site_tab, e->stream_site_tab.data(), e->stream_site_tab.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
 			HIP_TRY(hipMemcpyAsync(e->d_stream_qnode, e->stream_qnode.data(), e->stream_qnode.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
-			if (!e->d_lstream_ops && ((rc = dev_alloc(e, &e->d_lstream_ops, (size_t)e->N)) || (rc = dev_alloc(e, &e->d_lstream_chunks, (size_t)e->N + 2)))) return rc;
+			if ((rc = e->d_lstream_ops.ensure(e->N)) || (rc = e->d_lstream_chunks.ensure((size_t)e->N + 2))) return rc;
 			HIP_TRY(hipMemcpyAsync(e->d_lstream_ops, e->lstream_desc.data(), e->lstream_desc.size() * sizeof(LowerDesc), hipMemcpyHostToDevice, e->stream));
 			HIP_TRY(hipMemcpyAsync(e->d_lstream_chunks, e->lstream_chunks.data(), e->lstream_chunks.size() * sizeof(LowerChunk), hipMemcpyHostToDevice, e->stream));
 		}
@@ -923,20 +895,10 @@ size_t upper_slots_needed(const Shard *e) {
 }
 
 int ensure_upper_storage(Shard *e) {
-	const size_t need = upper_slots_needed(e);
-	if (e->d_upper && e->upper_alloc_slots >= need) return PHYAMD_OK;
-	dev_free(e, &e->d_upper, e->upper_alloc_slots * node_partial_doubles(e));
-	e->upper_alloc_slots = 0;
-	int rc = dev_alloc(e, &e->d_upper, need * node_partial_doubles(e));
-	if (rc) return rc;
-	e->upper_alloc_slots = need;
-	return PHYAMD_OK;
+	return e->d_upper.ensure(upper_slots_needed(e) * node_partial_doubles(e));
 }
 
-int ensure_scaling_storage(Shard *e) {
-	if (e->d_lscale) return PHYAMD_OK;
-	return dev_alloc(e, &e->d_lscale, e->lower_alloc_cores * (size_t)e->P);
-}
+int ensure_scaling_storage(Shard *e) { return e->d_lscale.ensure(lower_slots(e) * e->P); }
 
 int check_ready(Shard *e) {
 	if (!e->have_topology) return fail(PHYAMD_EINVAL, "phyamd_set_topology has not been called");

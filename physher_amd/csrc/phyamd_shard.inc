@@ -10,6 +10,9 @@ struct ScheduleCounts { int core_count, upper_slots, widest; };
 
 struct Shard {
 	phyamd_config cfg{};
+	// device memory: every owning d_* array below is allocated through one of these budgets (phyamd_memory.inc)
+	DeviceBudget mem;             // all of it, capped by cfg.max_device_bytes (the profile's device_bytes)
+	DeviceBudget tile_mem{&mem};  // the arrays sized by the pattern tile, which a re-tile drops (free_pattern_storage)
 	int T = 0, N = 0, P = 0, S = 0, C = 0, root = -1;
 	int G = 1;  // pattern groups (waves along z) per workgroup
 	bool generic = false;  // S != 4: MFMA kernels, plane layout [C][S][Pp]
@@ -29,7 +32,7 @@ struct Shard {
 	std::vector<int> changed;         // nodes whose branch length changed since the last evaluation
 	std::vector<NodeOp> inc_ops;      // ops of the dirty core nodes, by level
 	std::vector<int> inc_level_off;
-	NodeOp *d_inc_ops = nullptr;
+	DeviceArray<NodeOp> d_inc_ops{&mem};
 	const std::vector<int> *act_level_off = nullptr;
 	NodeOp *act_lower_ops = nullptr;
 	bool level_upper_needed = false;  // a level-schedule pre-order pass (parameter gradients) has been requested
@@ -49,28 +52,28 @@ struct Shard {
 	int Ptot = 0, tiles = 1;
 	bool tiled_eval_done = false;
 	bool tiled_root_term = false;     // d_result holds the summed root frequency term of a tiled parameter gradient
-	uint8_t *d_tip_all = nullptr;      // [T][Ptot]
-	double *d_weights_all = nullptr, *d_plk_all = nullptr, *d_total = nullptr;
+	DeviceArray<uint8_t> d_tip_all{&tile_mem};  // [T][Ptot]
+	DeviceArray<double> d_weights_all{&tile_mem}, d_plk_all{&tile_mem}, d_total{&tile_mem};
 	unsigned long schedule_epoch = 0;  // bumped whenever slots are reassigned from scratch
 	bool two_slots = false;            // d_lower / d_lscale hold 2 * core_count slots
 	bool force_root = false;           // the root's outputs (lnL_k, w_k / L_k, lnL) belong to a discarded state
 	bool generic_fusion = true;  // 20 states: cherries fused into their parents' ops (PHYAMD_GEN_FUSION = 0: every node stored)
 	bool walk_enabled = true, walking = false;  // tree-walk kernels (4 states, unscaled, not keep_partials)
 	bool gen_walking = false;  // post-order walk for 20 states (phyamd_genwalk.inc)
-	int *d_gen_walk_counter = nullptr;  // work-unit counter of the walk
+	DeviceArray<int> d_gen_walk_counter{&mem};  // work-unit counter of the walk
 	int gen_walk_slots[1] = {0};  // resident workgroups of k_lower_gen_walk
 	std::vector<NodeOp> walk_lower_ops, walk_upper_ops;  // depth-first op orders
-	NodeOp *d_walk_lower_ops = nullptr, *d_walk_upper_ops = nullptr;
+	DeviceArray<NodeOp> d_walk_lower_ops{&mem}, d_walk_upper_ops{&mem};
 	int walk_upper_slots = 0;
 	std::vector<NodeOp> walk_chunk_ops;  // chunked form of walk_upper_ops (build_walk_chunks)
 	std::vector<int> walk_chunk_off;     // chunk offsets into walk_chunk_ops: [0] top part, then one per cut subtree
 	int walk_chunk_slots = 0;
 	std::vector<NodeOp> walk_lower_chunk_ops;  // chunked form of walk_lower_ops: cut subtrees, then the top part
 	std::vector<int> walk_lower_chunk_off;
-	NodeOp *d_walk_lower_chunk_ops = nullptr;
-	int *d_walk_lower_chunk_off = nullptr;
-	NodeOp *d_walk_chunk_ops = nullptr;
-	int *d_walk_chunk_off = nullptr;
+	DeviceArray<NodeOp> d_walk_lower_chunk_ops{&mem};
+	DeviceArray<int> d_walk_lower_chunk_off{&mem};
+	DeviceArray<NodeOp> d_walk_chunk_ops{&mem};
+	DeviceArray<int> d_walk_chunk_off{&mem};
 	// streamed pre-order walk (phyamd_walk4s.inc): flattened ops of the chunked list, mask words in walk order, walk-order slab
 	bool stream_walk = true;             // false (tiling ENOMEM, T >= 2^20): k_upper4_walk
 	int xcd_map = 1;                     // PHYAMD_XCD_MAP = 0: streamed walks with consecutive workgroup ids per block group (A/B; see xcd_position)
@@ -81,41 +84,40 @@ struct Shard {
 	std::vector<StreamChunk> stream_chunks;
 	std::vector<LowerDesc> lstream_desc;  // k_lower4_stream: one per op of walk_lower_chunk_ops
 	std::vector<LowerChunk> lstream_chunks;
-	LowerDesc *d_lstream_ops = nullptr;
-	LowerChunk *d_lstream_chunks = nullptr;
+	DeviceArray<LowerDesc> d_lstream_ops{&mem};
+	DeviceArray<LowerChunk> d_lstream_chunks{&mem};
 	bool lstream_on = true;              // false (tiling ENOMEM): k_lower4_walk
 	std::vector<int> stream_row_entries; // [rows][8] nibbles of the packed mask words (MaskPacker): the pre-order walk's rows, then the post-order walk's
 	std::vector<int> stream_site_tab;    // [ops][16] byte offset of each result lane's branch in a slab row (-1: none)
 	std::vector<int> stream_qnode;       // slab position -> node
 	std::vector<int> stream_op_tips;     // [ops][12] tip of every table slot (-1: unused)
 	std::vector<int> stream_op_deep;     // [ops] bit 0 / 1: the left / right child is a DEEP node (its table slots hold messages only)
-	int *d_stream_op_tips = nullptr, *d_stream_flag = nullptr, *d_stream_op_deep = nullptr;
-	char *d_optab = nullptr;             // [C][ops] table blocks of OPBLK_BYTES, rebuilt from the matrices every evaluation
+	DeviceArray<int> d_stream_op_tips{&mem}, d_stream_flag{&mem}, d_stream_op_deep{&mem};
+	DeviceArray<char> d_optab{&mem};     // [C][ops] table blocks of OPBLK_BYTES, rebuilt from the matrices every evaluation
 	bool stream_ambiguous = false;       // the tip data hold partial ambiguity codes: the AMBIG instantiation of the streamed walk
 	bool stream_unsupported = false;     // the tip data hold an empty state mask: k_upper4_walk's 16-row tables
 	int stream_words = 0, stream_R = 0;
-	StreamDesc *d_stream_ops = nullptr;
-	StreamChunk *d_stream_chunks = nullptr;
-	int *d_stream_row_entries = nullptr, *d_stream_site_tab = nullptr, *d_stream_qnode = nullptr, *d_oct_lo = nullptr;
-	size_t stream_words_alloc = 0;
-	uint32_t *d_mstream = nullptr;
-	size_t mstride = 0, mstream_alloc = 0;
+	DeviceArray<StreamDesc> d_stream_ops{&mem};
+	DeviceArray<StreamChunk> d_stream_chunks{&mem};
+	DeviceArray<int> d_stream_row_entries{&mem}, d_stream_site_tab{&mem}, d_stream_qnode{&mem}, d_oct_lo{&mem};
+	DeviceArray<uint32_t> d_mstream{&tile_mem};
+	size_t mstride = 0;
 	unsigned long tip_epoch = 1, mstream_epoch = 0;  // tip data / mask words as of which tip data
 	std::vector<int> mstream_layout;     // stream_row_entries the device stream was built for
-	double *d_gslab = nullptr, *d_oct = nullptr;  // d_gslab: the walk-order slab, in d_gpart's storage
-	size_t oct_alloc = 0, optab_alloc = 0;
+	double *d_gslab = nullptr;           // the walk-order slab, in d_gpart's storage
+	DeviceArray<double> d_oct{&mem};
 	bool slab_walk_order = false;        // the last pre-order pass wrote d_gslab (walk order), not d_gpart
 	// sums over pattern blocks (reduce_block_sums): bisection levels of this engine's block range (3 = eight segments; a shard that
 	// holds 1 / 2^k of a larger range cut by the same bisection runs with 3 - k), and what the segment table on the device is for
 	int reduce_levels = 3, seg_nb[2] = {-1, -1}, seg_levels[2] = {-1, -1};
 	bool lnl_per_block = false;          // d_lnl_part holds one entry per block of 64 patterns (the tree walk)
-	double *d_Lc = nullptr;  // [C][P] per-category site likelihoods at the root (generic)
-	double *d_imgs = nullptr;  // generic: MFMA fragment images of P(t) per (node, category), then of Q (k_matrix_images)
+	DeviceArray<double> d_Lc{&tile_mem};  // [C][P] per-category site likelihoods at the root
+	DeviceArray<double> d_imgs{&mem};  // generic: MFMA fragment images of P(t) per (node, category), then of Q (k_matrix_images)
 	bool qimg_dirty = true;
-	double *d_qp_mats = nullptr;  // generic: Qf P(t) per (tip, category), row-major, and its fragment images (k_tip_rate_products): the
-	double *d_qp_imgs = nullptr;  // branch term of a tip child is a column of that product, looked up instead of multiplied out
+	DeviceArray<double> d_qp_mats{&mem};  // generic: Qf P(t) per (tip, category), row-major, and its fragment images (k_tip_rate_products): the
+	DeviceArray<double> d_qp_imgs{&mem};  // branch term of a tip child is a column of that product, looked up instead of multiplied out
 	int qp_kind = -1;             // which Qf the images hold: 0 = Q (pi folded into the uppers), 1 = diag(pi) Q, -1 = none
-	double *d_inv_part = nullptr;  // partial sums of k_root_invariant_term
+	DeviceArray<double> d_inv_part{&tile_mem};  // partial sums of k_root_invariant_term
 	int device = 0;
 	hipStream_t stream = nullptr;
 	bool own_stream = false;
@@ -132,8 +134,7 @@ struct Shard {
 	LowerForm lower_form = LowerForm::Reference;
 	bool reference_form_only = false;
 	bool exp2_on = true, tform_on = true;  // PHYAMD_SCALE_EXP2 = 0 / PHYAMD_STREAM_TFORM = 0: the streamed walks never write CarriedExp2 / Carried
-	int *d_lexp = nullptr, *d_uexp = nullptr, *d_Ec = nullptr, *d_Eroot = nullptr;  // exponents: [stored][C][P], [upper slots][C][P], [C][P], [P]
-	size_t lexp_alloc = 0, uexp_alloc = 0;
+	DeviceArray<int> d_lexp{&tile_mem}, d_uexp{&tile_mem}, d_Ec{&tile_mem}, d_Eroot{&tile_mem};  // exponents: [stored][C][P], [upper slots][C][P], [C][P], [P]
 	bool keep_partials = false;
 	bool profiling = false;
 	bool upper_valid = false;
@@ -152,74 +153,64 @@ struct Shard {
 	std::vector<DeepDesc> deep_host;   // by node id (only DEEP nodes filled)
 	int deep_count = 0;
 	// (device copy: behind the tip-message table, see Ctx4::deep)
-	size_t lower_alloc_cores = 0;
 
 	// device memory
-	uint8_t *d_tipmask = nullptr;
+	DeviceArray<uint8_t> d_tipmask{&tile_mem};
 	// 20 / 60 / 61 states: tip code S + 1 + q = ambiguity set q, one bit per member state (tip partials that are neither
 	// one state nor all states: named sets of a general data type, states of a padded state space)
-	unsigned long long *d_tipsets = nullptr;
+	DeviceArray<unsigned long long> d_tipsets{&mem};
 	std::vector<unsigned long long> tipsets_host;
 	size_t tipsets_uploaded = 0;  // entries of tipsets_host the device table holds
-	double *d_lower = nullptr, *d_upper = nullptr, *d_mats = nullptr, *d_dmats = nullptr;
-	double *d_Q = nullptr;
-	double *d_Qpi = nullptr;          // diag(pi) Q: the tree-walk gradient contracts u with (pi o Q b) in one mat-vec (4 states)
+	DeviceArray<double> d_lower{&tile_mem}, d_upper{&tile_mem}, d_mats{&mem}, d_dmats{&mem};
+	DeviceArray<double> d_Q{&mem};
+	DeviceArray<double> d_Qpi{&mem};  // diag(pi) Q: the tree-walk gradient contracts u with (pi o Q b) in one mat-vec (4 states)
 	std::vector<double> Q_host;
 	bool qpi_dirty = true;
 	bool have_Q = false;
-	double *d_tiptab = nullptr;  // [T][C][16][4] tip messages (4-state)
+	DeviceArray<double> d_tiptab{&mem};  // [T][C][16][4] tip messages (4-state), then the DeepDesc table
 	// substitution-parameter gradient (G2)
 	int np = 0;                      // number of dQ/dtheta matrices set
 	std::vector<double> dQ_host;     // [np][S][S]
-	double *d_B = nullptr;           // [np][S][S]  U^-1 dQ U
-	double *d_dpm = nullptr;         // [np][N][C][S][S]
-	double *d_dptab = nullptr;       // [np][T][C][16][4]
-	double *d_ppart = nullptr;       // [np][upper ops][nblk] per-workgroup parameter sums, then [np][upper ops]
-	double *d_Bw = nullptr;          // tree-walk G2: [np][16] U^-1 dQ U
-	double *d_pbuf = nullptr;        // tree-walk G2: [UTpi 16 | Uinv 16 | utab 64]
-	double *d_Fw = nullptr;          // tree-walk G2: [N][C][20] w_c F_ab(t_n r_c), l_a e^{l_a t_n r_c}
-	double *d_gacc = nullptr;        // tree-walk G2: [16][slabs * C] per-wave eigen-basis sums, then [16] totals
+	DeviceArray<double> d_B{&mem};      // [np][S][S]  U^-1 dQ U
+	DeviceArray<double> d_dpm{&mem};    // [np][N][C][S][S]
+	DeviceArray<double> d_dptab{&mem};  // [np][T][C][16][4]
+	DeviceArray<double> d_ppart{&mem};  // [np][upper ops][nblk] per-workgroup parameter sums, then [np][upper ops]
+	DeviceArray<double> d_Bw{&mem};     // tree-walk G2: [np][16] U^-1 dQ U
+	DeviceArray<double> d_pbuf{&mem};   // tree-walk G2: [UTpi 16 | Uinv 16 | utab 64]
+	DeviceArray<double> d_Fw{&mem};     // tree-walk G2: [N][C][20] w_c F_ab(t_n r_c), l_a e^{l_a t_n r_c}
+	DeviceArray<double> d_gacc{&mem};   // tree-walk G2: [16][slabs * C] per-wave eigen-basis sums, then [16] totals
 	// phyamd_branch_log_likelihood without resident uppers: the one upper it needs is rebuilt by a root-to-node path walk
 	std::vector<int> node_kind;      // CH_* of every node in the current schedule
-	PathStep *d_path_steps = nullptr;
-	double *d_path_upper = nullptr, *d_path_tmp = nullptr, *d_path_lower = nullptr;  // one node partial each
-	double *d_path_side = nullptr;  // 20 / 60 / 61 states: two node partials beside true_lower_gen (fused cherries below the node)
-	double *d_pg_lower = nullptr;   // 20 / 60 / 61 states, parameter gradient: every stored node's partial itself (d_lower holds P p)
-	size_t pg_lower_alloc = 0;
+	DeviceArray<PathStep> d_path_steps{&mem};
+	DeviceArray<double> d_path_upper{&mem}, d_path_tmp{&mem}, d_path_lower{&mem};  // one node partial each
+	DeviceArray<double> d_path_side{&mem};  // 20 / 60 / 61 states: two node partials beside true_lower_gen (fused cherries below the node)
+	DeviceArray<double> d_pg_lower{&mem};   // 20 / 60 / 61 states, parameter gradient: every stored node's partial itself (d_lower holds P p)
 	int path_node = -1;              // node whose upper d_path_upper holds (-1: none); dropped whenever partials are recomputed
 	// phyamd_branch_hessian_diagonal (ensure_hess_storage): workgroup table and slab of the HESS pre-order pass
-	int *d_hess_tab = nullptr;
-	double *d_hess = nullptr;
-	size_t hess_tab_alloc = 0, hess_alloc = 0;
+	DeviceArray<int> d_hess_tab{&tile_mem};
+	DeviceArray<double> d_hess{&tile_mem};
 	int hess_nwg = 0, hess_P = -1, hess_levels = -1;
-	double *d_hess_invf = nullptr;   // 20 / 60 / 61 states: 1 / pi [S]
+	DeviceArray<double> d_hess_invf{&mem};  // 20 / 60 / 61 states: 1 / pi [S]
 	int gen_hess_slots[2] = {0, 0};  // resident workgroups of k_upper_gen<HESS> [SCALE]
-	double *d_branch = nullptr;      // phyamd_branch_log_likelihood: [C][3][16] matrices | [3][blocks] partial sums | [3]
+	DeviceArray<double> d_branch{&mem};  // phyamd_branch_log_likelihood: [C][3][16] matrices | [3][blocks] partial sums | [3]
 	bool upper_fold = false;         // the stored uppers carry the root frequencies (last gradient call used FOLD)
-	double *d_rf_part = nullptr;     // [S][blocks] partial sums of k_root_frequency_term, then [S]
-	double *d_gen_scratch = nullptr; // rescaled S != 4 path: per-level maxima / numerators / denominators
-	size_t gen_scratch_alloc = 0;
-	size_t np_alloc = 0, np_alloc_B = 0, ppart_alloc = 0;
+	DeviceArray<double> d_rf_part{&mem};      // [S][blocks] partial sums of k_root_frequency_term, then [S]
+	DeviceArray<double> d_gen_scratch{&mem};  // rescaled S != 4 path: per-level maxima / numerators / denominators
 	// 20 / 60 / 61 states (k_param_*_gen): branch nodes, node -> stored lower index, per-branch site likelihoods, G tables
-	int *d_pg_nodes = nullptr, *d_pg_core = nullptr;
-	double *d_pg_den = nullptr, *d_pg_Gw = nullptr, *d_pg_B = nullptr;
-	size_t pg_np_alloc = 0;
+	DeviceArray<int> d_pg_nodes{&mem}, d_pg_core{&mem};
+	DeviceArray<double> d_pg_den{&mem}, d_pg_Gw{&mem}, d_pg_B{&mem};
 	bool params_dirty = true;
-	double *d_model = nullptr, *d_freqs = nullptr, *d_rates = nullptr, *d_props = nullptr, *d_lengths = nullptr, *d_weights = nullptr;
-	double *d_wl = nullptr;  // [P] w_k / L_k from the root kernel (unscaled evaluations)
-	double *d_plk = nullptr, *d_lscale = nullptr, *d_lnl_part = nullptr, *d_gpart = nullptr, *d_result = nullptr;
-	uint8_t *d_explicit = nullptr, *d_row_valid = nullptr;
-	NodeOp *d_lower_ops = nullptr, *d_upper_ops = nullptr;
+	DeviceArray<double> d_model{&mem}, d_freqs{&mem}, d_rates{&mem}, d_props{&mem}, d_lengths{&mem}, d_result{&mem};
+	DeviceArray<double> d_weights{&tile_mem}, d_plk{&tile_mem}, d_lscale{&tile_mem}, d_lnl_part{&tile_mem}, d_gpart{&tile_mem};
+	DeviceArray<double> d_wl{&tile_mem};  // [P] w_k / L_k from the root kernel (unscaled evaluations)
+	DeviceArray<uint8_t> d_explicit{&mem}, d_row_valid{&mem};
+	DeviceArray<NodeOp> d_lower_ops{&mem}, d_upper_ops{&mem};
 	double *h_result = nullptr;  // pinned
 	double *h_lengths = nullptr;  // pinned staging of phyamd_set_branch_lengths
 	hipEvent_t ev_lengths = nullptr;
 	hipEvent_t ev_check = nullptr;  // the lazy rescaling switch of a gradient call: lnL of the post-order pass is on its way to h_result's last entry
 	bool check_pending = false;
 	int nblk = 0;
-	int64_t device_bytes = 0;
-	int64_t pattern_bytes = 0;  // the part of device_bytes whose size follows the tile size (allocate_pattern_storage)
-	size_t lnl_part_alloc = 0;
-	size_t upper_alloc_slots = 0;
 
 	hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
 	phyamd_profile prof{};

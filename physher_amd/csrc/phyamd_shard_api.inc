@@ -41,27 +41,26 @@ double tile_working_set(const Shard *e, double p, bool exact) {
 // and the pre-order walk's per-op scratch (d_oct: 8 C R doubles, R < N).  What is held already counts in device_bytes.
 double walk_reserve(const Shard *e) {
 	if (e->S != 4) return 0.0;
-	return std::max(0.0, (double)e->N * e->C * OPBLK_BYTES - (double)e->optab_alloc) + std::max(0.0, 8.0 * (8.0 * e->C * e->N - (double)e->oct_alloc));
+	return std::max(0.0, (double)e->N * e->C * OPBLK_BYTES - (double)e->d_optab.size()) + std::max(0.0, 8.0 * (8.0 * e->C * e->N - (double)e->d_oct.size()));
 }
 
 // tiles / patterns per tile for the cap (the caller's max_device_bytes, else most of what the device has free right now, so that
-// a problem larger than the card runs in tiles instead of failing in hipMalloc)
+// a problem larger than the card runs in tiles instead of failing to allocate)
 int choose_tiles(Shard *e, bool exact) {
 	double cap = (double)e->cfg.max_device_bytes;
 	const bool automatic = e->cfg.max_device_bytes <= 0;
-	// what this engine holds now in buffers sized by the tile (they are dropped and re-made if the tile size changes)
-	const double tile_sized = (double)e->pattern_bytes + 8.0 * ((double)(e->lower_alloc_cores + e->upper_alloc_slots) * (double)node_partial_doubles(e) +
-	                                                            (e->d_lscale ? (double)e->lower_alloc_cores * e->P : 0.0)) +
-	                          4.0 * ((double)(e->lexp_alloc + e->uexp_alloc) + (e->d_Ec ? (double)e->C * e->P : 0.0) + (e->d_Eroot ? (double)e->P : 0.0)) +
-	                          (e->S == 4 && e->d_Lc ? 8.0 * e->C * e->P : 0.0);
+	// what this engine holds now in buffers sized by the tile (they are dropped and re-made if the tile size changes), as ever without
+	// the Hessian slab and the mask words, and a one-category engine's d_inv_part (evaluations make them)
+	const double tile_sized = (double)(e->tile_mem.bytes - (int64_t)(e->d_hess.bytes() + e->d_hess_tab.bytes() + e->d_mstream.bytes() +
+	                                                                   (e->C < 2 ? e->d_inv_part.bytes() : 0)));
 	if (automatic) {
 		size_t free_bytes = 0, total_bytes = 0;
 		cap = hipMemGetInfo(&free_bytes, &total_bytes) == hipSuccess ? 0.92 * ((double)free_bytes + tile_sized) : 0.0;
 	} else
-		cap -= (double)e->device_bytes - tile_sized + 65536.0 + walk_reserve(e);  // resident whatever the tile size, and buffers made on demand
+		cap -= (double)e->mem.bytes - tile_sized + 65536.0 + walk_reserve(e);  // resident whatever the tile size, and buffers made on demand
 	if (!automatic && cap <= 0)
 		return fail(PHYAMD_ENOMEM, "max_device_bytes (%lld) does not even hold what is resident whatever the tile size (%lld bytes)",
-		            (long long)e->cfg.max_device_bytes, (long long)(e->device_bytes - (int64_t)tile_sized));
+		            (long long)e->cfg.max_device_bytes, (long long)(e->mem.bytes - (int64_t)tile_sized));
 	e->P = e->Ptot;
 	e->tiles = 1;
 	if (cap > 0 && tile_working_set(e, (double)e->Ptot, exact) > cap) {
@@ -83,7 +82,6 @@ int choose_tiles(Shard *e, bool exact) {
 // launch geometry and every allocation whose size follows the tile size e->P (the partial arrays themselves are sized by the
 // schedule: ensure_lower_storage / ensure_upper_storage)
 int allocate_pattern_storage(Shard *e) {
-	const int64_t before = e->device_bytes;
 	e->G = std::max(1, 4 / e->C);  // at least 4 waves per workgroup
 	e->nblk = (e->P + WAVE * e->G * PPT_UPPER - 1) / (WAVE * e->G * PPT_UPPER);        // pre-order kernel / gradient slabs
 	e->nblk_lower = (e->P + WAVE * e->G * PPT_LOWER - 1) / (WAVE * e->G * PPT_LOWER);  // post-order kernel / lnL slab
@@ -103,63 +101,30 @@ int allocate_pattern_storage(Shard *e) {
 		e->nblk_root = (e->P + 255) / 256;
 	}
 	int rc;
-	if ((rc = dev_alloc(e, &e->d_tipmask, (size_t)e->T * e->P + 8))) return rc;  // (+8: the matrix-core walk reads a lane's four mask bytes as one dword)
+	if ((rc = e->d_tipmask.ensure((size_t)e->T * e->P + 8))) return rc;  // (+8: the matrix-core walk reads a lane's four mask bytes as one dword)
 	if (e->tiles > 1) {
-		if ((rc = dev_alloc(e, &e->d_tip_all, (size_t)e->T * e->Ptot)) || (rc = dev_alloc(e, &e->d_weights_all, (size_t)e->Ptot)) ||
-		    (rc = dev_alloc(e, &e->d_plk_all, (size_t)e->Ptot)) || (rc = dev_alloc(e, &e->d_total, (size_t)1 + e->N * e->C + 2 * PHYAMD_MAX_PARAMETERS)))
+		if ((rc = e->d_tip_all.ensure((size_t)e->T * e->Ptot)) || (rc = e->d_weights_all.ensure(e->Ptot)) || (rc = e->d_plk_all.ensure(e->Ptot)) ||
+		    (rc = e->d_total.ensure((size_t)1 + e->N * e->C + 2 * PHYAMD_MAX_PARAMETERS)))
 			return rc;
 	}
-	if ((rc = dev_alloc(e, &e->d_weights, (size_t)e->P))) return rc;
-	if ((rc = dev_alloc(e, &e->d_plk, (size_t)e->P))) return rc;
-	if ((rc = dev_alloc(e, &e->d_wl, (size_t)e->P))) return rc;
-	e->lnl_part_alloc = (size_t)std::max(std::max(std::max(e->nblk, e->nblk_lower), (e->nblk_walk_upper + 2) * e->G), e->nblk_root);  // (walk: one entry per 64 patterns)
-	if ((rc = dev_alloc(e, &e->d_lnl_part, e->lnl_part_alloc))) return rc;
-	if (e->generic && (rc = dev_alloc(e, &e->d_Lc, (size_t)e->C * e->P))) return rc;
-	if (e->C >= 2 && (rc = dev_alloc(e, &e->d_inv_part, (size_t)(e->P + 255) / 256 + 1))) return rc;  // (the +I root term: held like the lnL slab)
+	if ((rc = e->d_weights.ensure(e->P)) || (rc = e->d_plk.ensure(e->P)) || (rc = e->d_wl.ensure(e->P))) return rc;
+	if ((rc = e->d_lnl_part.ensure(std::max(std::max(std::max(e->nblk, e->nblk_lower), (e->nblk_walk_upper + 2) * e->G), e->nblk_root))))  // (walk: one entry per 64 patterns)
+		return rc;
+	if (e->generic && (rc = e->d_Lc.ensure((size_t)e->C * e->P))) return rc;
+	if (e->C >= 2 && (rc = e->d_inv_part.ensure((size_t)(e->P + 255) / 256 + 1))) return rc;  // (the +I root term: held like the lnL slab)
 	e->gpart_row = (size_t)std::max(e->nblk, e->generic ? 0 : e->nblk_walk_upper * e->G);  // the tree-walk kernels write one entry per wave-group
-	if ((rc = dev_alloc(e, &e->d_gpart, (size_t)e->N * e->C * e->gpart_row))) return rc;
+	if ((rc = e->d_gpart.ensure((size_t)e->N * e->C * e->gpart_row))) return rc;
 	HIP_TRY(hipMemsetAsync(e->d_gpart, 0, sizeof(double) * (size_t)e->N * e->C * e->gpart_row, e->stream));
 	HIP_TRY(hipStreamSynchronize(e->stream));
-	e->pattern_bytes += e->device_bytes - before;
 	return PHYAMD_OK;
 }
 
 // before any tip data or weights have been loaded: drop everything sized by the tile (phyamd_set_topology re-tiles)
 void free_pattern_storage(Shard *e) {
-	const int64_t before = e->device_bytes;
-	const size_t npd = node_partial_doubles(e);
-	dev_free(e, &e->d_tipmask, (size_t)e->T * e->P + 8);
-	dev_free(e, &e->d_tip_all, (size_t)e->T * e->Ptot);
-	dev_free(e, &e->d_weights_all, (size_t)e->Ptot);
-	dev_free(e, &e->d_plk_all, (size_t)e->Ptot);
-	dev_free(e, &e->d_total, (size_t)1 + e->N * e->C + 2 * PHYAMD_MAX_PARAMETERS);
-	dev_free(e, &e->d_weights, (size_t)e->P);
-	dev_free(e, &e->d_plk, (size_t)e->P);
-	dev_free(e, &e->d_wl, (size_t)e->P);
-	dev_free(e, &e->d_lnl_part, e->lnl_part_alloc);
-	dev_free(e, &e->d_Lc, (size_t)e->C * e->P);
-	dev_free(e, &e->d_inv_part, (size_t)(e->P + 255) / 256 + 1);
-	dev_free(e, &e->d_Ec, (size_t)e->C * e->P);
-	dev_free(e, &e->d_Eroot, (size_t)e->P);
-	dev_free(e, &e->d_gpart, (size_t)e->N * e->C * e->gpart_row);
-	dev_free(e, &e->d_hess, e->hess_alloc);
-	dev_free(e, &e->d_hess_tab, e->hess_tab_alloc);
-	e->hess_alloc = e->hess_tab_alloc = 0;
-	e->hess_P = -1;
-	dev_free(e, &e->d_mstream, e->mstream_alloc);
-	e->mstream_alloc = 0;
+	e->tile_mem.release_all();
 	e->d_gslab = nullptr;
+	e->hess_P = -1;
 	e->mstream_epoch = 0;
-	e->pattern_bytes += e->device_bytes - before;
-	// partial arrays of the old tile size
-	dev_free(e, &e->d_lower, e->lower_alloc_cores * npd);
-	dev_free(e, &e->d_lscale, e->lower_alloc_cores * (size_t)e->P);
-	e->lower_alloc_cores = 0;
-	dev_free(e, &e->d_upper, e->upper_alloc_slots * npd);
-	e->upper_alloc_slots = 0;
-	dev_free(e, &e->d_lexp, e->lexp_alloc);
-	dev_free(e, &e->d_uexp, e->uexp_alloc);
-	e->lexp_alloc = e->uexp_alloc = 0;
 }
 
 void shard_destroy(Shard *e);
@@ -183,6 +148,7 @@ int shard_create(const phyamd_config *cfg, Shard **out) {
 	if (ndev == 0) return fail(PHYAMD_EDEVICE, "no HIP device visible");
 	Shard *e = new Shard();
 	e->cfg = *cfg;
+	e->mem.cap = cfg->max_device_bytes;
 	e->T = cfg->tip_count;
 	e->N = 2 * e->T - 1;
 	e->P = e->Ptot = cfg->pattern_count;
@@ -221,25 +187,19 @@ int shard_create(const phyamd_config *cfg, Shard **out) {
 	e->tip_set.assign(e->T, 0);
 	e->explicit_host.assign(e->N, 0);
 	const size_t msz = (size_t)e->N * e->C * e->S * e->S;
-	if (e->generic && (rc = dev_alloc(e, &e->d_tipsets, (size_t)256))) return bail(rc);
-	if (e->generic && (rc = dev_alloc(e, &e->d_imgs, ((size_t)e->N * e->C + 2) * gen_image_doubles(e)))) return bail(rc);
+	if (e->generic && ((rc = e->d_tipsets.ensure(256)) || (rc = e->d_imgs.ensure(((size_t)e->N * e->C + 2) * gen_image_doubles(e))))) return bail(rc);
 	if (e->S == 20 && GenFuse<2>::QP) {  // Qf P(t) per (tip, category) and its images (ensure_tip_rate_products): made here, so that the tile plan counts them
-		if ((rc = dev_alloc(e, &e->d_qp_mats, (size_t)e->T * e->C * e->S * e->S))) return bail(rc);
-		if ((rc = dev_alloc(e, &e->d_qp_imgs, (size_t)e->T * e->C * gen_image_doubles(e)))) return bail(rc);
+		if ((rc = e->d_qp_mats.ensure((size_t)e->T * e->C * e->S * e->S)) || (rc = e->d_qp_imgs.ensure((size_t)e->T * e->C * gen_image_doubles(e)))) return bail(rc);
 	}
 	// d_lower is sized by the schedule (stored "core" nodes only): ensure_lower_storage
-	if ((rc = dev_alloc(e, &e->d_mats, msz))) return bail(rc);
-	if ((rc = dev_alloc(e, &e->d_dmats, msz))) return bail(rc);
-	if ((rc = dev_alloc(e, &e->d_model, (size_t)e->S + 2 * e->S * e->S))) return bail(rc);
-	if ((rc = dev_alloc(e, &e->d_Q, (size_t)e->S * e->S))) return bail(rc);
-	if (!e->generic && (rc = dev_alloc(e, &e->d_tiptab, (size_t)e->T * e->C * 64 + (size_t)e->N * 6))) return bail(rc);
-	if ((rc = dev_alloc(e, &e->d_freqs, (size_t)e->S))) return bail(rc);
-	if ((rc = dev_alloc(e, &e->d_rates, (size_t)e->C))) return bail(rc);
-	if ((rc = dev_alloc(e, &e->d_props, (size_t)e->C))) return bail(rc);
-	if ((rc = dev_alloc(e, &e->d_lengths, (size_t)e->N))) return bail(rc);
-	if ((rc = dev_alloc(e, &e->d_result, (size_t)1 + e->N * e->C + 2 * PHYAMD_MAX_PARAMETERS))) return bail(rc);
-	if ((rc = dev_alloc(e, &e->d_explicit, (size_t)e->N))) return bail(rc);
-	if ((rc = dev_alloc(e, &e->d_row_valid, (size_t)e->N * e->C))) return bail(rc);
+	if ((rc = e->d_mats.ensure(msz)) || (rc = e->d_dmats.ensure(msz)) || (rc = e->d_model.ensure((size_t)e->S + 2 * e->S * e->S)) ||
+	    (rc = e->d_Q.ensure((size_t)e->S * e->S)))
+		return bail(rc);
+	if (!e->generic && (rc = e->d_tiptab.ensure((size_t)e->T * e->C * 64 + (size_t)e->N * 6))) return bail(rc);
+	if ((rc = e->d_freqs.ensure(e->S)) || (rc = e->d_rates.ensure(e->C)) || (rc = e->d_props.ensure(e->C)) || (rc = e->d_lengths.ensure(e->N)) ||
+	    (rc = e->d_result.ensure((size_t)1 + e->N * e->C + 2 * PHYAMD_MAX_PARAMETERS)) || (rc = e->d_explicit.ensure(e->N)) ||
+	    (rc = e->d_row_valid.ensure((size_t)e->N * e->C)))
+		return bail(rc);
 	{
 		hipError_t err = hipHostMalloc(reinterpret_cast<void **>(&e->h_result), sizeof(double) * ((size_t)2 + e->N * e->C + 2 * PHYAMD_MAX_PARAMETERS), hipHostMallocDefault);  // (+1: the lazy-switch copy)
 		if (err != hipSuccess) return bail(fail(PHYAMD_EDEVICE, "hipHostMalloc: %s", hipGetErrorString(err)));
@@ -256,21 +216,14 @@ int shard_create(const phyamd_config *cfg, Shard **out) {
 	return PHYAMD_OK;
 }
 
-void shard_destroy(Shard *e) {
+void shard_destroy(Shard *e) {  // (the device arrays free themselves)
 	if (!e) return;
 	(void)hipSetDevice(e->device);
 	if (e->stream) (void)hipStreamSynchronize(e->stream);
-	for (void *p : {(void *)e->d_branch, (void *)e->d_path_steps, (void *)e->d_path_upper, (void *)e->d_path_tmp, (void *)e->d_path_lower, (void *)e->d_path_side, (void *)e->d_pg_lower, (void *)e->d_Bw, (void *)e->d_pbuf, (void *)e->d_Fw, (void *)e->d_gacc, (void *)e->d_gen_scratch, (void *)e->d_rf_part, (void *)e->d_B, (void *)e->d_dpm, (void *)e->d_dptab, (void *)e->d_ppart, (void *)e->d_imgs, (void *)e->d_qp_mats, (void *)e->d_qp_imgs, (void *)e->d_tipmask, (void *)e->d_tip_all, (void *)e->d_weights_all, (void *)e->d_plk_all, (void *)e->d_total, (void *)e->d_tipsets, (void *)e->d_pg_nodes, (void *)e->d_pg_core, (void *)e->d_pg_den, (void *)e->d_pg_Gw, (void *)e->d_pg_B, (void *)e->d_lower, (void *)e->d_upper, (void *)e->d_mats, (void *)e->d_dmats, (void *)e->d_model, (void *)e->d_Q, (void *)e->d_Lc, (void *)e->d_inv_part, (void *)e->d_tiptab,
-	                (void *)e->d_freqs, (void *)e->d_rates, (void *)e->d_props, (void *)e->d_lengths, (void *)e->d_weights, (void *)e->d_plk, (void *)e->d_wl,
-	                (void *)e->d_lscale, (void *)e->d_lnl_part, (void *)e->d_gpart, (void *)e->d_mstream, (void *)e->d_oct, (void *)e->d_stream_ops, (void *)e->d_stream_chunks, (void *)e->d_stream_row_entries, (void *)e->d_stream_site_tab, (void *)e->d_stream_qnode, (void *)e->d_lstream_ops, (void *)e->d_lstream_chunks, (void *)e->d_gen_walk_counter, (void *)e->d_oct_lo, (void *)e->d_stream_op_tips, (void *)e->d_stream_op_deep, (void *)e->d_stream_flag, (void *)e->d_optab, (void *)e->d_result, (void *)e->d_explicit, (void *)e->d_row_valid,
-	                (void *)e->d_lower_ops, (void *)e->d_upper_ops, (void *)e->d_walk_lower_ops, (void *)e->d_walk_upper_ops, (void *)e->d_walk_chunk_ops, (void *)e->d_walk_chunk_off, (void *)e->d_walk_lower_chunk_ops, (void *)e->d_walk_lower_chunk_off, (void *)e->d_inc_ops, (void *)e->d_Qpi, (void *)e->d_hess, (void *)e->d_hess_tab, (void *)e->d_hess_invf})
-		if (p) (void)hipFree(p);
 	if (e->h_result) (void)hipHostFree(e->h_result);
 	if (e->h_lengths) (void)hipHostFree(e->h_lengths);
 	if (e->ev_lengths) (void)hipEventDestroy(e->ev_lengths);
 	if (e->ev_check) (void)hipEventDestroy(e->ev_check);
-	for (int *p : {e->d_lexp, e->d_uexp, e->d_Ec, e->d_Eroot})
-		if (p) (void)hipFree(p);
 	for (auto &ev : e->ev)
 		if (ev) (void)hipEventDestroy(ev);
 	if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);
@@ -497,29 +450,21 @@ int shard_store(Shard *e) {
 	if ((rc = run_lower(e, true))) return rc;  // the state that is stored is an evaluated one (a no-op when nothing is pending)
 	if (!e->two_slots) {  // first store: a second slot per stored node (allocate_storage(tlk, 1), treelikelihood.c:977-1003), contents kept
 		// the allocation never shrinks (keep_partials on and off again, a new topology with fewer stored nodes): only the
-		// core_count live slots move over
-		const size_t npd = node_partial_doubles(e), old_slots = e->lower_alloc_cores, want = (size_t)std::max(1, e->core_count) * 2;
-		const size_t live = std::min(old_slots, (size_t)std::max(1, e->core_count));
-		double *lower = nullptr, *lscale = nullptr;
-		hipError_t err = hipMalloc(reinterpret_cast<void **>(&lower), want * npd * sizeof(double));
-		if (err == hipSuccess) err = hipMemcpyAsync(lower, e->d_lower, live * npd * sizeof(double), hipMemcpyDeviceToDevice, e->stream);
-		if (err == hipSuccess && e->d_lscale) {
-			err = hipMalloc(reinterpret_cast<void **>(&lscale), want * e->P * sizeof(double));
-			if (err == hipSuccess) err = hipMemcpyAsync(lscale, e->d_lscale, live * e->P * sizeof(double), hipMemcpyDeviceToDevice, e->stream);
-		}
+		// core_count live slots move over.  Allocated next to the one-slot arrays, within the cap: if they do not fit, the engine
+		// keeps its one-slot state
+		const size_t npd = node_partial_doubles(e), want = (size_t)std::max(1, e->core_count) * 2;
+		const size_t live = std::min(lower_slots(e), (size_t)std::max(1, e->core_count));
+		DeviceArray<double> lower{&e->tile_mem}, lscale{&e->tile_mem};
+		if ((rc = lower.ensure(want * npd)) || (e->d_lscale && (rc = lscale.ensure(want * e->P)))) return rc;
+		hipError_t err = hipMemcpyAsync(lower, e->d_lower, live * npd * sizeof(double), hipMemcpyDeviceToDevice, e->stream);
+		if (err == hipSuccess && e->d_lscale) err = hipMemcpyAsync(lscale, e->d_lscale, live * e->P * sizeof(double), hipMemcpyDeviceToDevice, e->stream);
 		if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
 		if (err != hipSuccess) {
 			(void)hipStreamSynchronize(e->stream);
-			if (lower) (void)hipFree(lower);
-			if (lscale) (void)hipFree(lscale);
 			return fail(err == hipErrorOutOfMemory ? PHYAMD_ENOMEM : PHYAMD_EDEVICE, "phyamd_store: second slot per stored node: %s", hipGetErrorString(err));
 		}
-		e->device_bytes += (int64_t)(want * npd * sizeof(double)) + (lscale ? (int64_t)(want * e->P * sizeof(double)) : 0);
-		dev_free(e, &e->d_lower, old_slots * npd);
-		if (e->d_lscale) dev_free(e, &e->d_lscale, old_slots * (size_t)e->P);
-		e->d_lower = lower;
-		e->d_lscale = lscale;
-		e->lower_alloc_cores = want;
+		e->d_lower.swap(lower);
+		e->d_lscale.swap(lscale);  // (the one-slot arrays are freed on leaving this scope)
 		e->two_slots = true;
 	}
 	HIP_TRY(hipMemcpyAsync(e->h_result, e->d_result, sizeof(double), hipMemcpyDeviceToHost, e->stream));
@@ -883,10 +828,8 @@ static int cherry_partial_gen(Shard *e, int node, double *out) {
 static int rebuild_path_upper(Shard *e, int node) {
 	int rc;
 	const size_t npd = node_partial_doubles(e);
-	if (!e->d_path_upper && ((rc = dev_alloc(e, &e->d_path_upper, npd)) || (rc = dev_alloc(e, &e->d_path_lower, npd)) ||
-	                         (rc = dev_alloc(e, &e->d_path_steps, (size_t)e->N))))
-		return rc;
-	if (e->generic && !e->d_path_tmp && (rc = dev_alloc(e, &e->d_path_tmp, npd))) return rc;
+	if ((rc = e->d_path_upper.ensure(npd)) || (rc = e->d_path_lower.ensure(npd)) || (rc = e->d_path_steps.ensure(e->N))) return rc;
+	if (e->generic && (rc = e->d_path_tmp.ensure(npd))) return rc;
 	std::vector<int> path;  // node, parent, ..., root
 	for (int a = node; a >= 0; a = e->parent[a]) path.push_back(a);
 	const int m = (int)path.size() - 1;  // steps
@@ -966,15 +909,14 @@ int shard_branch_log_likelihood(Shard *e, int node, double length, double *lnl, 
 		low = node < e->T ? nullptr : (e->core_index[node] >= 0 ? e->d_lower + (size_t)e->core_index[node] * npd : e->d_path_lower);
 	}
 	if (e->generic && node >= e->T) {  // the branch's P(t) changes here: p_node itself, not the stored P p (k_lower_gen)
-		if (!e->d_path_lower && (rc = dev_alloc(e, &e->d_path_lower, npd))) return rc;
-		if (!e->d_path_side && (rc = dev_alloc(e, &e->d_path_side, 2 * npd))) return rc;
+		if ((rc = e->d_path_lower.ensure(npd)) || (rc = e->d_path_side.ensure(2 * npd))) return rc;
 		if ((rc = true_lower_gen(e, node, e->d_path_lower, e->d_path_side))) return rc;
 		low = e->d_path_lower;
 	}
 	const int C = e->C, S = e->S, S2 = S * S;
 	const int per_block = e->generic ? 256 : WAVE, nb = (e->P + per_block - 1) / per_block;
 	const size_t msz = (size_t)C * (e->generic ? 4 : 3) * S2, need = msz + (size_t)3 * nb + 3;
-	if (!e->d_branch && (rc = dev_alloc(e, &e->d_branch, need))) return rc;
+	if ((rc = e->d_branch.ensure(need))) return rc;
 	// P(t r_c), r_c Q P, r_c^2 Q Q P from the eigen system (host: S^3 per category)
 	const double *ev = e->model.data(), *U = ev + S, *Ui = U + S2;
 	std::vector<double> pm(msz), ex(S);
@@ -1091,21 +1033,17 @@ int shard_get_partials(Shard *e, int node, int upper, double *out) {
 		return fail(PHYAMD_EINVAL, "node %d is fused into its parent (cherry / cherry+tip) and not stored: shard_set_keep_partials(1) first", node);
 	const double *src = upper ? e->d_upper + (size_t)e->upper_slot[node] * np : e->d_lower + (size_t)e->core_index[node] * np;
 	if (e->generic) {  // planes [C][S][Pp] -> the reference's [C][P][S]
-		double *tmp = nullptr;
+		DeviceArray<double> tmp;  // (a temporary: not counted in device_bytes)
 		const size_t cnt = (size_t)e->C * e->P * e->S;
-		HIP_TRY(hipMalloc(reinterpret_cast<void **>(&tmp), (cnt + (upper ? 0 : 3 * np)) * sizeof(double)));
+		if ((rc = tmp.ensure(cnt + (upper ? 0 : 3 * np)))) return rc;
 		if (!upper) {  // a stored lower array is t = P p (k_lower_gen): the partial itself is formed from the node's children
-			if ((rc = true_lower_gen(e, node, tmp + cnt, tmp + cnt + np))) {
-				(void)hipFree(tmp);
-				return rc;
-			}
+			if ((rc = true_lower_gen(e, node, tmp + cnt, tmp + cnt + np))) return rc;
 			src = tmp + cnt;
 		}
 		hipLaunchKernelGGL(k_planes_to_reference, dim3((unsigned)std::min<size_t>((cnt + 255) / 256, 4096)), dim3(256), 0, e->stream, e->P, e->Pp, e->S,
 		                   e->C, src, tmp);
 		hipError_t err = hipMemcpyAsync(out, tmp, cnt * sizeof(double), hipMemcpyDeviceToHost, e->stream);
 		if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-		(void)hipFree(tmp);
 		if (err != hipSuccess) return fail(PHYAMD_EDEVICE, "get_partials: %s", hipGetErrorString(err));
 		return PHYAMD_OK;
 	}
@@ -1178,7 +1116,7 @@ int shard_get_profile(Shard *e, phyamd_profile *out) {
 	CHECK_ENGINE(e);
 	if (!out) return fail(PHYAMD_EINVAL, "null out");
 	finish_profile(e, e->prof_with_upper);  // waits for the last evaluation's events if they are still pending
-	e->prof.device_bytes = e->device_bytes;
+	e->prof.device_bytes = e->mem.bytes;
 	e->prof.tiles = e->tiles;
 	*out = e->prof;
 	return PHYAMD_OK;

@@ -1287,6 +1287,39 @@ def test_store_after_the_partial_storage_has_shrunk(S, T, P, C):
         assert np.abs(cg - ref["cat_grad"]).max() <= 1e-9 * max(1.0, np.abs(ref["cat_grad"]).max())
 
 
+def test_store_within_the_memory_cap():
+    """The second slot per stored node that the first phyamd_store allocates counts against max_device_bytes like every other
+    allocation.  Under a cap that runs the engine untiled but cannot hold those slots, store() is refused with PHYAMD_ENOMEM and
+    the engine keeps its one-slot state: the cap holds, and lnL and the gradient are the same to the bit."""
+    pb = random_problem(40, 2000, 4, seed=7800, gaps=0.02)
+
+    def evaluated(e):  # partials() settles the stored lowers in the reference's form, which store() would switch them to anyway
+        e.gradient()
+        e.partials(pb.root)
+        return e.gradient()
+
+    with engine_from_problem(pb, rescale=RESCALE_NEVER) as whole:
+        evaluated(whole)
+        one_slot = whole.profile()["device_bytes"]
+        whole.store()
+        two_slots = whole.profile()["device_bytes"]
+    assert two_slots > one_slot
+    for cap in np.linspace(two_slots - 1, one_slot, 8).astype(np.int64).tolist():
+        with engine_from_problem(pb, rescale=RESCALE_NEVER, max_device_bytes=cap) as e:
+            if e.profile()["tiles"] != 1:
+                continue  # (the tile plan asks for more than this cap)
+            lnl, cg = evaluated(e)
+            with pytest.raises(EngineError) as err:
+                e.store()
+            assert err.value.code == -3, err.value  # PHYAMD_ENOMEM
+            assert e.profile()["device_bytes"] <= cap
+            lnl_after, cg_after = e.gradient()
+            assert lnl_after == lnl and np.array_equal(cg_after, cg)
+            assert e.profile()["device_bytes"] <= cap
+            return
+    pytest.fail(f"no cap in [{one_slot}, {two_slots}) runs this problem untiled")
+
+
 def test_root_terms_agree_between_rescaled_and_unscaled_evaluations():
     """The +I root term and the frequency root term form L_k from the root partial itself, so they are the same numbers
     whether the evaluation was rescaled or not."""
