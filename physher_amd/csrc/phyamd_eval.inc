@@ -88,7 +88,8 @@ int run_lower(Shard *e, int need_host_check) {
 	}
 	for (int attempt = 0; attempt < 2; attempt++) {
 		e->lnl_per_block = false;
-		if ((rc = launch_lower(e))) return rc;
+		if (lower_kernel(e, false) == PassKernel::Stream && (rc = make_stream_buffers(e, true))) return rc;
+		if ((rc = launch_lower(e, lower_kernel(e, true)))) return rc;
 		if (e->lnl_per_block) {  // the tree walk: per-block sums, added in an order that depends on the pattern range alone
 			if ((rc = reduce_block_sums(e, 0, e->d_lnl_part, e->lnl_blocks, 1, 1, nullptr, e->d_result))) return rc;
 		} else
@@ -108,7 +109,7 @@ int run_lower(Shard *e, int need_host_check) {
 		HIP_TRY(hipStreamSynchronize(e->stream));
 		if (!std::isinf(e->h_result[0])) break;
 		e->scaling_on = true;
-		if ((rc = rebuild_schedule(e))) return rc;  // rescaling runs the level kernels (no tree walk), fringe fusion stays
+		if ((rc = rebuild_schedule(e))) return rc;  // the rescaled schedule (20 states: no walk lists), fringe fusion stays
 		if ((rc = ensure_scaling_storage(e))) return rc;
 		e->act_level_off = &e->lower_level_off;  // and recomputes every node
 		e->act_lower_ops = e->d_lower_ops;
@@ -280,27 +281,20 @@ int run_gradient(Shard *e, int flags, bool with_params = false) {
 	}
 	// (a tile's post-order pass decides the lazy switch itself: rescaling may have come on after the requirement above was settled)
 	if (e->scaling_on && (flags & PHYAMD_GRAD_COMPAT_SCALED) && (rc = require_reference_form(e))) return rc;
-	bool any_explicit = false;  // explicit matrices have no eigen system: the tree-walk's eigen-basis branch term does not cover them
-	for (uint8_t x : e->explicit_host) any_explicit |= x != 0;
-	const bool walk_params = with_params && !any_explicit && !e->generic && e->walking &&
-	                         !((flags & PHYAMD_GRAD_COMPAT_SCALED) && e->scaling_on);
-	if (with_params && !e->generic && !walk_params) e->level_upper_needed = true;
-	if ((rc = ensure_upper_storage(e))) return rc;
+	PassKernel k = upper_kernel(e, flags, with_params, false);
+	if ((rc = ensure_upper_storage(e, k))) return rc;
 	if (!e->have_Q) return fail(PHYAMD_EINVAL, "the gradient needs the rate matrix: phyamd_set_eigen or phyamd_set_rate_matrix");
+	if (k != PassKernel::Levels && (rc = upload_qpi(e))) return rc;  // (the walks' branch terms: diag(pi) Q)
+	if (k == PassKernel::Stream && (rc = make_stream_buffers(e, false))) return rc;
+	k = upper_kernel(e, flags, with_params, true);
+	const bool walk_params = with_params && k == PassKernel::Walk;
 	e->grad_blocks = e->nblk;
 	e->slab_walk_order = false;
 	// (the compat flag changes only the branch terms; parameter sums always use the mixture denominator: level kernels then)
-	if (walk_params) {
-		const int waves = e->C * e->G;
-		if (e->scaling_on)
-			rc = waves <= 4 ? launch_upper_walk_params<4, true>(e) : waves <= 8 ? launch_upper_walk_params<8, true>(e) : launch_upper_walk_params<16, true>(e);
-		else
-			rc = waves <= 4 ? launch_upper_walk_params<4, false>(e) : waves <= 8 ? launch_upper_walk_params<8, false>(e) : launch_upper_walk_params<16, false>(e);
-		if (rc) return rc;
-	} else if (with_params && !e->generic) {
-		if ((rc = update_parameter_matrices(e))) return rc;
-		if ((rc = launch_upper_params(e, flags))) return rc;
-	} else if ((rc = launch_upper(e, flags)))
+	if (with_params && !e->generic) {
+		if (k == PassKernel::Levels && (rc = update_parameter_matrices(e))) return rc;
+		if ((rc = launch_upper_params(e, flags, k))) return rc;
+	} else if ((rc = launch_upper(e, flags, k)))
 		return rc;
 	record(e, 3);
 	if (e->slab_walk_order) {
@@ -346,10 +340,7 @@ int run_hessian(Shard *e, double *out) {
 	}
 	if (!rc) rc = run_lower(e, 1);
 	if (!rc) rc = require_reference_form(e);
-	if (!rc) {
-		e->level_upper_needed = true;
-		if (!(rc = ensure_upper_storage(e)) && !(rc = ensure_hess_storage(e))) rc = launch_hess(e, out);
-	}
+	if (!rc && !(rc = ensure_upper_storage(e, PassKernel::Levels)) && !(rc = ensure_hess_storage(e))) rc = launch_hess(e, out);
 	if (unfuse) {
 		e->fusion_enabled = true;
 		const int rc2 = rebuild_schedule(e);

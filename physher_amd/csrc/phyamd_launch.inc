@@ -98,6 +98,15 @@ int ensure_tip_rate_products(Shard *e, bool fold) {
 
 dim3 block_dims(const Shard *e) { return dim3(WAVE, e->C, e->G); }
 
+// launch(W) with the wave bound W of a workgroup of `waves` waves as a template argument: 4, 8 or 16 (so that small groups are not
+// register-capped for 1024 threads)
+template <typename F>
+int by_waves(int waves, F launch) {
+	if (waves <= 4) return launch(std::integral_constant<int, 4>());
+	if (waves <= 8) return launch(std::integral_constant<int, 8>());
+	return launch(std::integral_constant<int, 16>());
+}
+
 // Workgroups the card runs at once for one kernel (occupancy x CUs), asked once per kernel instantiation and device.
 template <typename K>
 int resident_workgroups(Shard *e, K kernel, int threads, size_t lds) {
@@ -177,32 +186,9 @@ int launch_lower_walk(Shard *e) {
 	return PHYAMD_OK;
 }
 
-bool lower_stream_applies(const Shard *e);
-int ensure_mask_stream(Shard *e);
-int ensure_optab(Shard *e);
-int ensure_exponent_storage(Shard *e);
-void free_exponent_storage(Shard *e);
-int launch_lower_stream(Shard *e);
-
 template <int WAVES>
-int launch_lower_w(Shard *e) {
-	if (lower_stream_applies(e)) {
-		int rc = ensure_mask_stream(e);
-		if (!rc) rc = ensure_optab(e);
-		if (!rc) rc = e->d_Lc.ensure((size_t)e->C * e->P);  // per-category root terms for k_root_finish64
-		if (rc == PHYAMD_ENOMEM && e->cfg.max_device_bytes > 0) e->lstream_on = false;  // the cap leaves no room for the words
-		else if (rc) return rc;
-		else if (!e->stream_unsupported) {
-			if (stream_lower_form(e) == LowerForm::CarriedExp2 && (rc = ensure_exponent_storage(e))) {
-				if (rc != PHYAMD_ENOMEM || e->cfg.max_device_bytes <= 0) return rc;
-				prefer_reference_form(e);  // the cap leaves no room for the exponents: the reference's rescaling from here on
-				free_exponent_storage(e);
-			}
-			if (lower_stream_applies(e)) return launch_lower_stream(e);
-		}
-	}
-	e->lower_form = LowerForm::Reference;
-	if (e->walking && !e->incremental_pass) return e->scaling_on ? launch_lower_walk<WAVES, true>(e) : launch_lower_walk<WAVES, false>(e);
+int launch_lower_w(Shard *e, PassKernel k) {
+	if (k == PassKernel::Walk) return e->scaling_on ? launch_lower_walk<WAVES, true>(e) : launch_lower_walk<WAVES, false>(e);
 	return e->scaling_on ? launch_lower_levels<WAVES, true>(e) : launch_lower_levels<WAVES, false>(e);
 }
 
@@ -324,9 +310,10 @@ int launch_upper_hess(Shard *e, double *out) {
 }
 
 int launch_hess4(Shard *e, double *out) {
-	const int waves = e->C;
-	if (e->scaling_on) return waves <= 4 ? launch_upper_hess<4, true>(e, out) : waves <= 8 ? launch_upper_hess<8, true>(e, out) : launch_upper_hess<16, true>(e, out);
-	return waves <= 4 ? launch_upper_hess<4, false>(e, out) : waves <= 8 ? launch_upper_hess<8, false>(e, out) : launch_upper_hess<16, false>(e, out);
+	return by_waves(e->C, [&](auto w) {
+		constexpr int W = decltype(w)::value;
+		return e->scaling_on ? launch_upper_hess<W, true>(e, out) : launch_upper_hess<W, false>(e, out);
+	});
 }
 
 int upload_qpi(Shard *e) {
@@ -373,11 +360,6 @@ int ensure_optab(Shard *e) {
 	return e->d_optab.ensure((size_t)std::max<size_t>(1, e->stream_ops.size()) * e->C * OPBLK_BYTES);
 }
 
-bool lower_stream_applies(const Shard *e) {
-	return e->walking && e->stream_walk && e->lstream_on && (!e->scaling_on || stream_lower_form(e) == LowerForm::CarriedExp2 || e->C <= STREAM_WAVES) &&
-	       !e->incremental_pass && !e->lstream_desc.empty();
-}
-
 // the exponents of the power-of-two rescaling (LowerForm::CarriedExp2), the pre-order walk's included: made before the post-order
 // pass that writes that form, so that a memory cap without room for them is met while the reference's form can still be written
 int ensure_exponent_storage(Shard *e) {
@@ -392,6 +374,29 @@ void free_exponent_storage(Shard *e) {
 	e->d_uexp.release();
 	e->d_Ec.release();
 	e->d_Eroot.release();
+}
+
+// The buffers of a streamed walk that lower_kernel / upper_kernel chose (lower: the post-order walk), made before its pass: mask
+// words and table blocks, for the post-order walk also its per-category root terms and the exponents of CarriedExp2.  What only
+// this step finds out is recorded for the second question (made = true): a cap without room for the words, the tables or the root
+// terms (the table-gather walk from then on), a cap without room for the exponents (the reference's form from then on), tip data
+// with an empty state mask.
+int make_stream_buffers(Shard *e, bool lower) {
+	const bool capped = e->cfg.max_device_bytes > 0;
+	int rc = ensure_mask_stream(e);  // (pattern tiles: the mask words follow the tile's tip codes, rebuilt with every tile copy: ~0.1 ms per tile)
+	if (!rc) rc = ensure_optab(e);
+	if (!rc && lower) rc = e->d_Lc.ensure((size_t)e->C * e->P);  // per-category root terms for k_root_finish64
+	if (rc == PHYAMD_ENOMEM && capped) {
+		(lower ? e->lower_stream_capped : e->upper_stream_capped) = true;
+		return PHYAMD_OK;
+	}
+	if (rc || !lower || e->stream_unsupported || stream_lower_form(e) != LowerForm::CarriedExp2) return rc;
+	if ((rc = ensure_exponent_storage(e)) == PHYAMD_ENOMEM && capped) {
+		prefer_reference_form(e);
+		free_exponent_storage(e);
+		return PHYAMD_OK;
+	}
+	return rc;
 }
 
 // the streamed post-order walk (k_lower4_stream): every cut subtree as workgroups of its own, then the top part with the root
@@ -409,7 +414,6 @@ int launch_lower_stream(Shard *e) {
 	const LowerForm form = stream_lower_form(e);
 	const StreamVariant v = stream_variant(form, e->scaling_on);
 	const bool exp2 = v.scale == 2, scale = v.scale == 1, tf = v.tf;
-	if (exp2 && (rc = ensure_exponent_storage(e))) return rc;
 	e->lower_form = form;
 	const int waves = scale ? e->C : STREAM_WAVES;
 	const size_t lds = (size_t)LSTREAM_LDS_PER_WAVE * waves + (scale ? sizeof(double) * 2 * e->C * WAVE : 0);
@@ -444,7 +448,6 @@ int launch_upper_stream(Shard *e) {
 	// the walk-order slab [nb][C][R] lives in the [row][block] slab's storage (N * C * gpart_row doubles, gpart_row >= nb, R = N - 1)
 	if ((size_t)nb * e->C * R > (size_t)e->N * e->C * e->gpart_row) return fail(PHYAMD_EDEVICE, "gradient slab too small for the streamed walk");
 	e->d_gslab = e->d_gpart;
-	if ((rc = ensure_optab(e))) return rc;
 	// the descriptors carry byte offsets multiplied out for a pattern count and a mask-row stride: rebuilt if either has moved
 	if (e->stream_P != e->P || e->stream_mstride != e->mstride) {
 		if ((rc = upload_schedule(e))) return rc;
@@ -525,16 +528,6 @@ template <int WAVES, bool FOLD, bool SCALE, bool COMPAT>
 int launch_upper_walk_v(Shard *e) {
 	const int ops = (int)e->walk_upper_ops.size(), nb = e->nblk_walk_upper * e->G;
 	int rc;
-	if constexpr (!COMPAT) {
-		if (e->stream_walk && (!SCALE || e->lower_form == LowerForm::CarriedExp2 || e->C <= STREAM_WAVES)) {
-			// (pattern tiles: the mask words follow the tile's tip codes, rebuilt with every tile copy: ~0.1 ms per tile)
-			rc = ensure_mask_stream(e);
-			if (!rc) rc = ensure_optab(e);
-			if (rc == PHYAMD_ENOMEM && e->cfg.max_device_bytes > 0) e->stream_walk = false;  // the cap leaves no room for the words: the table-gather walk from here on
-			else if (rc) return rc;
-			else if (!e->stream_unsupported) return launch_upper_stream<FOLD, SCALE>(e);
-		}
-	}
 	if ((rc = check_reference_form(e, "k_upper4_walk"))) return rc;
 	// columns, the rescaling exchange, then the leaf parks' LDS slots (LPARK: 2 KB per wave)
 	const size_t lds = sizeof(double) * ((size_t)e->G * e->C * NACC * WCOL + (SCALE ? (size_t)4 * e->G * e->C * WAVE : 0) + (size_t)4 * e->G * e->C * WAVE);
@@ -554,8 +547,6 @@ int launch_upper_walk_v(Shard *e) {
 
 template <int WAVES>
 int launch_upper_walk(Shard *e, bool fold, bool compat) {
-	int rc;
-	if ((rc = upload_qpi(e))) return rc;
 	if (e->scaling_on) {
 		if (fold) return compat ? launch_upper_walk_v<WAVES, true, true, true>(e) : launch_upper_walk_v<WAVES, true, true, false>(e);
 		return compat ? launch_upper_walk_v<WAVES, false, true, true>(e) : launch_upper_walk_v<WAVES, false, true, false>(e);
@@ -593,7 +584,6 @@ int launch_upper_walk_params(Shard *e) {
 	const size_t lds = sizeof(double) * ((size_t)e->G * e->C * 16 * WCOL + (SCALE ? (size_t)4 * e->G * e->C * WAVE : 0));
 	int rc;
 	if ((rc = check_reference_form(e, "k_upper4_walk (parameters)"))) return rc;
-	if ((rc = upload_qpi(e))) return rc;
 	if ((rc = e->d_Bw.ensure((size_t)np * 16)) || (rc = e->d_pbuf.ensure(96)) || (rc = e->d_Fw.ensure((size_t)e->N * e->C * 20)) ||
 	    (rc = e->d_gacc.ensure((size_t)16 * nb * e->C + 16)))
 		return rc;
@@ -639,10 +629,10 @@ int launch_upper_walk_params(Shard *e) {
 }
 
 template <int WAVES>
-int launch_upper_w(Shard *e, int flags) {
+int launch_upper_w(Shard *e, int flags, PassKernel k) {
 	const bool fold = flags & PHYAMD_GRAD_FOLD_ROOT_FREQS, compat = (flags & PHYAMD_GRAD_COMPAT_SCALED) && e->scaling_on;
 	e->grad_blocks = e->nblk;
-	if (e->walking) return launch_upper_walk<WAVES>(e, fold, compat);
+	if (k == PassKernel::Walk) return launch_upper_walk<WAVES>(e, fold, compat);
 	if (e->scaling_on) {
 		if (fold) return compat ? launch_upper_levels<WAVES, true, true, true, false>(e) : launch_upper_levels<WAVES, true, true, false, false>(e);
 		return compat ? launch_upper_levels<WAVES, true, false, true, false>(e) : launch_upper_levels<WAVES, true, false, false, false>(e);
@@ -867,25 +857,33 @@ int launch_upper_gen(Shard *e, int flags) {
 
 template <int RT, int KT>
 int launch_lower_gen_s(Shard *e) {
-	if constexpr (RT == 2) {
-		if (e->gen_walking && !e->scaling_on && !e->incremental_pass) return launch_lower_gen_walk<RT, KT>(e);
-	}
 	return e->scaling_on ? launch_lower_gen<RT, KT, true>(e) : launch_lower_gen<RT, KT, false>(e);
 }
 
-// workgroups hold C*G waves; the bound is a template parameter so small groups are not register-capped for 1024 threads
-int launch_lower(Shard *e) {
-	if (e->generic) return e->S == 20 ? launch_lower_gen_s<2, 5>(e) : e->S == 60 ? launch_lower_gen_s<4, 15>(e) : launch_lower_gen_s<4, 16>(e);
-	const int waves = e->C * e->G;
-	return waves <= 4 ? launch_lower_w<4>(e) : waves <= 8 ? launch_lower_w<8>(e) : launch_lower_w<16>(e);
+// The post-order and pre-order passes of family k (lower_kernel, upper_kernel); the walks' workgroups hold C * G waves
+int launch_lower(Shard *e, PassKernel k) {
+	if (e->generic) {
+		if (k == PassKernel::Walk) return launch_lower_gen_walk<2, 5>(e);  // (20 states only)
+		return e->S == 20 ? launch_lower_gen_s<2, 5>(e) : e->S == 60 ? launch_lower_gen_s<4, 15>(e) : launch_lower_gen_s<4, 16>(e);
+	}
+	if (k == PassKernel::Stream) return launch_lower_stream(e);
+	e->lower_form = LowerForm::Reference;
+	return by_waves(e->C * e->G, [&](auto w) { return launch_lower_w<decltype(w)::value>(e, k); });
 }
-int launch_upper(Shard *e, int flags) {
+int launch_upper(Shard *e, int flags, PassKernel k) {
 	if (e->generic) return e->S == 20 ? launch_upper_gen<2, 5>(e, flags) : e->S == 60 ? launch_upper_gen<4, 15>(e, flags) : launch_upper_gen<4, 16>(e, flags);
-	const int waves = e->C * e->G;
-	return waves <= 4 ? launch_upper_w<4>(e, flags) : waves <= 8 ? launch_upper_w<8>(e, flags) : launch_upper_w<16>(e, flags);
+	if (k == PassKernel::Stream) {
+		const bool fold = flags & PHYAMD_GRAD_FOLD_ROOT_FREQS;
+		if (e->scaling_on) return fold ? launch_upper_stream<true, true>(e) : launch_upper_stream<false, true>(e);
+		return fold ? launch_upper_stream<true, false>(e) : launch_upper_stream<false, false>(e);
+	}
+	return by_waves(e->C * e->G, [&](auto w) { return launch_upper_w<decltype(w)::value>(e, flags, k); });
 }
-
-int launch_upper_params(Shard *e, int flags) {
-	const int waves = e->C * e->G;
-	return waves <= 4 ? launch_upper_params_w<4>(e, flags) : waves <= 8 ? launch_upper_params_w<8>(e, flags) : launch_upper_params_w<16>(e, flags);
+// 4 states, the substitution-parameter gradient (update_parameter_matrices first for the Levels family)
+int launch_upper_params(Shard *e, int flags, PassKernel k) {
+	return by_waves(e->C * e->G, [&](auto w) {
+		constexpr int W = decltype(w)::value;
+		if (k == PassKernel::Levels) return launch_upper_params_w<W>(e, flags);
+		return e->scaling_on ? launch_upper_walk_params<W, true>(e) : launch_upper_walk_params<W, false>(e);
+	});
 }

@@ -859,8 +859,7 @@ int upload_schedule(Shard *e) {
 		if ((rc = e->d_walk_lower_chunk_ops.ensure(e->N)) || (rc = e->d_walk_lower_chunk_off.ensure((size_t)e->N + 2))) return rc;
 		HIP_TRY(hipMemcpyAsync(e->d_walk_lower_chunk_ops, e->walk_lower_chunk_ops.data(), e->walk_lower_chunk_ops.size() * sizeof(NodeOp), hipMemcpyHostToDevice, e->stream));
 		HIP_TRY(hipMemcpyAsync(e->d_walk_lower_chunk_off, e->walk_lower_chunk_off.data(), e->walk_lower_chunk_off.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
-		if (e->T >= (1 << 20)) e->stream_walk = false;  // (a packed mask-word entry keeps 20 bits of tip id: the table-gather walks beyond that)
-		if (e->stream_walk) {  // the streamed pre-order walk's tables follow the chunked list (core indices included: store / restore moves them)
+		if (stream_possible(e)) {  // the streamed walks' tables follow the chunked lists (core indices included: store / restore moves them)
 			build_stream_ops(e);
 			build_lower_stream_ops(e);
 			if ((rc = e->d_stream_ops.ensure(e->N)) || (rc = e->d_stream_chunks.ensure((size_t)e->N + 2)) || (rc = e->d_stream_row_entries.ensure((size_t)e->N * 32)) ||
@@ -887,14 +886,16 @@ int upload_schedule(Shard *e) {
 	return PHYAMD_OK;
 }
 
-// the tree-walk schedule parks far fewer uppers than the level schedule keeps; parameter-gradient and inspection
-// calls still run the level kernels, so the larger of the two is held once either has been needed
+// the tree-walk schedule parks far fewer uppers than the level schedule keeps; parameter gradients and the Hessian can still run
+// the level kernels, so the larger of the two is held once a Levels pre-order pass has run
 size_t upper_slots_needed(const Shard *e) {
 	const bool level_path = !e->walking || e->level_upper_needed;  // (20-state walks: both, they alternate with level passes)
 	return (size_t)std::max(1, level_path ? std::max(e->upper_slots, e->walk_upper_slots) : e->walk_upper_slots);
 }
 
-int ensure_upper_storage(Shard *e) {
+// d_upper for a pre-order pass of family k (upper_kernel; the Hessian's: Levels)
+int ensure_upper_storage(Shard *e, PassKernel k) {
+	if (k == PassKernel::Levels) e->level_upper_needed = true;
 	return e->d_upper.ensure(upper_slots_needed(e) * node_partial_doubles(e));
 }
 

@@ -35,7 +35,7 @@ struct Shard {
 	DeviceArray<NodeOp> d_inc_ops{&mem};
 	const std::vector<int> *act_level_off = nullptr;
 	NodeOp *act_lower_ops = nullptr;
-	bool level_upper_needed = false;  // a level-schedule pre-order pass (parameter gradients) has been requested
+	bool level_upper_needed = false;  // a Levels pre-order pass has run: d_upper holds the level schedule's slots (ensure_upper_storage)
 	// MCMC store / restore (_singleTreeLikelihood_store, _treelikelihood_handle_restore: treelikelihood.c:116-161): after a
 	// store every stored node has two slots (slot = core index, + core_count for the second); an evaluation never writes the
 	// slot the stored state lives in, so restore is an index flip (plus re-integrating the root), not a recomputation
@@ -58,8 +58,10 @@ struct Shard {
 	bool two_slots = false;            // d_lower / d_lscale hold 2 * core_count slots
 	bool force_root = false;           // the root's outputs (lnL_k, w_k / L_k, lnL) belong to a discarded state
 	bool generic_fusion = true;  // 20 states: cherries fused into their parents' ops (PHYAMD_GEN_FUSION = 0: every node stored)
-	bool walk_enabled = true, walking = false;  // tree-walk kernels (4 states, unscaled, not keep_partials)
-	bool gen_walking = false;  // post-order walk for 20 states (phyamd_genwalk.inc)
+	bool walk_enabled = true;  // PHYAMD_WALK = 0: no walk lists, every pass runs the level kernels
+	// the schedule built walk lists (not keep_partials): 4 states / 20 states unscaled (phyamd_genwalk.inc); what runs on them is
+	// decided in "which kernel runs a pass"
+	bool walking = false, gen_walking = false;
 	DeviceArray<int> d_gen_walk_counter{&mem};  // work-unit counter of the walk
 	int gen_walk_slots[1] = {0};  // resident workgroups of k_lower_gen_walk
 	std::vector<NodeOp> walk_lower_ops, walk_upper_ops;  // depth-first op orders
@@ -75,8 +77,9 @@ struct Shard {
 	DeviceArray<NodeOp> d_walk_chunk_ops{&mem};
 	DeviceArray<int> d_walk_chunk_off{&mem};
 	// streamed pre-order walk (phyamd_walk4s.inc): flattened ops of the chunked list, mask words in walk order, walk-order slab
-	bool stream_walk = true;             // false (tiling ENOMEM, T >= 2^20): k_upper4_walk
-	int xcd_map = 1;                     // PHYAMD_XCD_MAP = 0: streamed walks with consecutive workgroup ids per block group (A/B; see xcd_position)
+	bool upper_stream_capped = false;    // the cap left no room for the pre-order walk's mask words / table blocks: neither walk streams
+	bool lower_stream_capped = false;    // ... for the post-order walk's (or its root terms): the post-order walk does not stream
+	int xcd_map = 1;                    // PHYAMD_XCD_MAP = 0: streamed walks with consecutive workgroup ids per block group (A/B; see xcd_position)
 	std::vector<StreamOp> stream_ops;    // one per op of walk_chunk_ops
 	std::vector<StreamDesc> stream_desc; // ... as the kernel reads them (byte offsets multiplied out for stream_P patterns, stream_mstride)
 	int stream_P = 0;
@@ -86,7 +89,6 @@ struct Shard {
 	std::vector<LowerChunk> lstream_chunks;
 	DeviceArray<LowerDesc> d_lstream_ops{&mem};
 	DeviceArray<LowerChunk> d_lstream_chunks{&mem};
-	bool lstream_on = true;              // false (tiling ENOMEM): k_lower4_walk
 	std::vector<int> stream_row_entries; // [rows][8] nibbles of the packed mask words (MaskPacker): the pre-order walk's rows, then the post-order walk's
 	std::vector<int> stream_site_tab;    // [ops][16] byte offset of each result lane's branch in a slab row (-1: none)
 	std::vector<int> stream_qnode;       // slab position -> node
@@ -95,7 +97,7 @@ struct Shard {
 	DeviceArray<int> d_stream_op_tips{&mem}, d_stream_flag{&mem}, d_stream_op_deep{&mem};
 	DeviceArray<char> d_optab{&mem};     // [C][ops] table blocks of OPBLK_BYTES, rebuilt from the matrices every evaluation
 	bool stream_ambiguous = false;       // the tip data hold partial ambiguity codes: the AMBIG instantiation of the streamed walk
-	bool stream_unsupported = false;     // the tip data hold an empty state mask: k_upper4_walk's 16-row tables
+	bool stream_unsupported = false;     // the tip data the mask words were built for hold an empty state mask: the table-gather walks
 	int stream_words = 0, stream_R = 0;
 	DeviceArray<StreamDesc> d_stream_ops{&mem};
 	DeviceArray<StreamChunk> d_stream_chunks{&mem};
@@ -256,4 +258,49 @@ int require_reference_form(Shard *e) {
 	e->all_dirty = true;
 	e->upper_valid = false;
 	return run_lower(e, 1);
+}
+
+// ---- which kernel runs a pass ----------------------------------------------------------------------------------------------
+// A 4-state pass runs one of three families, and lower_kernel / upper_kernel below are the whole rule: the launchers launch the
+// family they are given.
+//            post-order        pre-order
+//   Levels   k_lower4          k_upper4          one launch per tree level (phyamd_level4.inc)
+//   Walk     k_lower4_walk     k_upper4_walk     the table-gather tree walks (phyamd_walk4.inc)
+//   Stream   k_lower4_stream   k_upper4_stream   the streamed tree walks (phyamd_walk4s.inc)
+// 20 states: the post-order pass is k_lower_gen_walk (Walk) or k_lower_gen (Levels); the 20 / 60 / 61-state pre-order pass and
+// the branch Hessian's pass are always Levels.  A Stream answer holds once the walk's buffers are made (make_stream_buffers,
+// then the same question with made = true): a cap may leave no room for them, and whether the tip data hold an empty state mask
+// is known only once the mask words are built.
+enum class PassKernel { Levels, Walk, Stream };
+
+constexpr int STREAM_MAX_TIPS = 1 << 20;  // a packed mask-word entry keeps 20 bits of tip id
+
+// the streamed walks can run on this engine: 4-state walk lists, few enough tips, and no cap has taken the pre-order walk's buffers
+bool stream_possible(const Shard *e) { return e->walking && e->T < STREAM_MAX_TIPS && !e->upper_stream_capped; }
+
+// a streamed walk's workgroup holds the pass over stored lowers of form f: plain, rescaled by powers of two, or rescaled as the
+// reference does (the C category waves of one block exchange their maxima: at most STREAM_WAVES of them)
+bool stream_shape_fits(const Shard *e, LowerForm f) { return !e->scaling_on || f == LowerForm::CarriedExp2 || e->C <= STREAM_WAVES; }
+
+// the post-order pass; a streamed one writes stream_lower_form
+PassKernel lower_kernel(const Shard *e, bool made) {
+	if (e->generic) return e->gen_walking && !e->scaling_on && !e->incremental_pass ? PassKernel::Walk : PassKernel::Levels;
+	const bool walk = e->walking && !e->incremental_pass;
+	if (walk && stream_possible(e) && !e->lower_stream_capped && stream_shape_fits(e, stream_lower_form(e)) && !e->lstream_desc.empty() &&
+	    !(made && e->stream_unsupported))
+		return PassKernel::Stream;
+	return walk ? PassKernel::Walk : PassKernel::Levels;
+}
+
+// the pre-order pass of a gradient (with_params: of the substitution-parameter gradient, the walk in its PARAMS form); the walks
+// read the stored lowers in the form the post-order pass left
+PassKernel upper_kernel(const Shard *e, int flags, bool with_params, bool made) {
+	if (!e->walking) return PassKernel::Levels;
+	const bool compat = (flags & PHYAMD_GRAD_COMPAT_SCALED) && e->scaling_on;
+	if (with_params) {  // the walk's eigen-basis branch term: explicit matrices have no eigen system; the compat arithmetic is the level kernels'
+		const bool any_explicit = std::any_of(e->explicit_host.begin(), e->explicit_host.end(), [](uint8_t x) { return x != 0; });
+		return any_explicit || compat ? PassKernel::Levels : PassKernel::Walk;
+	}
+	if (!compat && stream_possible(e) && stream_shape_fits(e, e->lower_form) && !(made && e->stream_unsupported)) return PassKernel::Stream;
+	return PassKernel::Walk;
 }
