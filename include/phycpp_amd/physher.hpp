@@ -269,6 +269,17 @@ class TreeLikelihoodInterface : public CallableModelInterface {
 	// --- beyond the reference surface ---
 	// reproduce the reference's include_root_freqs = true / rescaled-gradient arithmetic bit for bit ("quirks")
 	void SetReferenceCompatibility(bool on) { referenceCompat_ = on; }
+	// lnL / lnL and the gradient for `count` parameter vectors of the tree model at once (one phyamd_gradient_batch call):
+	// treeParameters [count][n] is what the tree model's SetParameters takes -- branch lengths for unrooted trees, heights or
+	// ratios + root height for time trees (clock rates are folded in as for a single evaluation); logLikelihoods [count] is
+	// LogLikelihood() per item (may be null in GradientBatch); gradients [count][gradientLength_] is Gradient() per item: the
+	// TREE_HEIGHT block and, when requested, the BRANCH_MODEL block, in Gradient's order, with the ratio transform's Jacobian
+	// when the object includes it.  A request with SITE_MODEL or substitution-model flags throws.  The tree model holds its
+	// previous parameters afterwards.  With SetReferenceCompatibility(true) gradients are the reference's arithmetic, which the
+	// engine evaluates item by item (never batched); lnL is batched either way.
+	void LogLikelihoodBatch(size_t count, const double *treeParameters, double *logLikelihoods);
+	void GradientBatch(size_t count, const double *treeParameters, double *logLikelihoods, double *gradients);
+	size_t TreeParameterCount() const { return treeModel_->parameterCount_; }  // n of treeParameters [count][n]
 	size_t GetPatternCount() const;
 	const std::vector<double> &PatternWeights() const;
 	const std::vector<unsigned char> &PatternStates() const;  // [taxon][pattern], taxa in alignment order
@@ -276,6 +287,10 @@ class TreeLikelihoodInterface : public CallableModelInterface {
    private:
 	void Init(bool use_tip_states);
 	void Sync();
+	void FormBranchLengths(std::vector<double> &lengths);
+	void GradientEpilogue(double lnl, std::vector<double> &cat_grad, const std::vector<double> &branch_lengths, const std::vector<double> &subst_grad,
+	                      double *gradient);
+	void EvaluateBatch(size_t count, const double *treeParameters, double *logLikelihoods, double *gradients);
 	TreeModelInterface *treeModel_;
 	SubstitutionModelInterface *substitutionModel_;
 	SiteModelInterface *siteModel_;

@@ -232,6 +232,28 @@ int phyamd_branch_log_likelihood(phyamd_engine *e, int node, double length, doub
 int phyamd_branch_hessian_diagonal(phyamd_engine *e, int flags, double *lnl, double *d1, double *d2);
 /* device-resident form for sharding: [lnL | d1[2T-1] | d2[2T-1]], sums over this engine's patterns, no host sync */
 int phyamd_branch_hessian_diagonal_device(phyamd_engine *e, int flags, double *device_out);
+/* lnL and the per-category branch gradient for `count` branch-length vectors on the engine's tree, data and models.
+ * branch_lengths [count][2T-1] by node id (root entries ignored); lnl [count]; cat_gradient [count][2T-1][C], root rows 0,
+ * or NULL for lnL only (post-order work only).  Item b equals what phyamd_set_branch_lengths(item b) + phyamd_gradient(flags)
+ * returns.  The engine's own branch lengths are unchanged afterwards.  NaN/inf lnL of an item => that item's gradient all NaN.
+ * The call is defined as "evaluate the items one by one through the ordinary path, then put the engine's lengths back", so it
+ * works on every engine configuration; where the conditions below hold the items run together instead -- one launch walks every
+ * item's tree, a workgroup per (item, 64 patterns), with no floating-point atomics: an item's result does not depend on `count`,
+ * on its position in the batch or on how the batch was cut into chunks, bit for bit.  That fast path takes: 4 states, at most 8
+ * categories, an engine that is not rescaling (PHYAMD_RESCALE_NEVER: an underflowing item reports -inf / NaN in-band like a
+ * single evaluation; PHYAMD_RESCALE_AUTO: an item whose lnL is not finite is evaluated again one by one, which may switch the
+ * engine to rescaling as any evaluation does), untiled patterns and at most 8192 of them per shard (above that one evaluation
+ * fills the card and the loop is faster), no tip cell with an empty state mask, flags 0 or
+ * PHYAMD_GRAD_FOLD_ROOT_FREQS, and scratch for at least one item within the memory cap (a batch that does not fit as a whole
+ * runs in chunks of items).  After a batch whose items all took it, later evaluations return what they would have returned
+ * without the call.  Sharded handles run the batch on every shard's patterns and add the per-item results in shard order.
+ * PHYAMD_EINVAL: count < 1, null pointers; PHYAMD_EUNSUPPORTED: explicit node matrices (they cannot follow per-item lengths). */
+int phyamd_gradient_batch(phyamd_engine *e, int flags, int32_t count, const double *branch_lengths, double *lnl, double *cat_gradient);
+/* of the last batch call: items that ran together / one by one, chunks the fast path was cut into, bytes of batch scratch the
+ * engine holds (kept for the next call and counted in phyamd_profile.device_bytes, but released whenever an array of the engine
+ * itself needs the room: under max_device_bytes the engine behaves as one that never made the call), wall time of the call */
+typedef struct { int32_t items_fast, items_sequential, chunks; int64_t scratch_bytes; double ms; } phyamd_batch_profile;
+int phyamd_get_batch_profile(phyamd_engine *e, phyamd_batch_profile *out);   /* of the last batch call */
 int phyamd_synchronize(phyamd_engine *e);
 
 /* --- inspection (parity tests, debugging) --- */

@@ -35,6 +35,12 @@ class Profile(C.Structure):
     ]
 
 
+class BatchProfile(C.Structure):
+    _fields_ = [
+        ("items_fast", C.c_int32), ("items_sequential", C.c_int32), ("chunks", C.c_int32), ("scratch_bytes", C.c_int64), ("ms", C.c_double),
+    ]
+
+
 # every symbol include/physher_amd.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -70,6 +76,8 @@ SYMBOLS = [
     ("phyamd_branch_log_likelihood", C.c_int, [_P, C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("phyamd_branch_hessian_diagonal", C.c_int, [_P, C.c_int, C.POINTER(C.c_double), _P, _P]),
     ("phyamd_branch_hessian_diagonal_device", C.c_int, [_P, C.c_int, _P]),
+    ("phyamd_gradient_batch", C.c_int, [_P, C.c_int, C.c_int32, _P, _P, _P]),
+    ("phyamd_get_batch_profile", C.c_int, [_P, C.POINTER(BatchProfile)]),
     ("phyamd_synchronize", C.c_int, [_P]),
     ("phyamd_get_pattern_log_likelihoods", C.c_int, [_P, _P]),
     ("phyamd_get_partials", C.c_int, [_P, C.c_int, C.c_int, _P]),

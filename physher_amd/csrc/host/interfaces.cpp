@@ -1,5 +1,6 @@
 // interfaces.cpp -- the phycpp-compatible wrapper classes (include/phycpp_amd/physher.hpp) over the host model
 // code (phyamd_host.hpp) and the device engine's C ABI (include/physher_amd.h).
+#include <cstdint>
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -598,22 +599,28 @@ void TreeLikelihoodInterface::RequestGradient(std::vector<TreeLikelihoodGradient
 	if (branchModel_ == nullptr && (f & (int)TreeLikelihoodGradientFlags::TREE_HEIGHT)) gradientLength_ -= 2;
 }
 
+// the engine's branch lengths of the tree model's current parameters, clock rates included
+void TreeLikelihoodInterface::FormBranchLengths(std::vector<double> &lengths) {
+	const phyamd::Tree &t = *treeModel_->GetTree();
+	lengths.assign(t.node_count, 0.0);
+	for (int n = 0; n < t.node_count; n++) {
+		if (n == t.root) continue;
+		if (t.time_mode) {
+			const double rate = branchModel_ ? branchModel_->Rate((size_t)n) : 1.0;
+			const double bl = rate * (t.height[t.parent[n]] - t.height[n]);  // treelikelihood.c:1657
+			if (bl < 0) throw Error("negative branch length above node " + std::to_string(n));
+			lengths[n] = bl;
+		} else
+			lengths[n] = t.distance[n];
+	}
+}
+
 void TreeLikelihoodInterface::Sync() {
 	auto &I = *impl_;
 	phyamd::Tree &t = *treeModel_->GetTree();
 	const unsigned long cv = branchModel_ ? branchModel_->version_ : 0;
 	if (I.tree_v != treeModel_->version_ || I.clock_v != cv) {
-		I.branch_lengths.assign(t.node_count, 0.0);
-		for (int n = 0; n < t.node_count; n++) {
-			if (n == t.root) continue;
-			if (t.time_mode) {
-				const double rate = branchModel_ ? branchModel_->Rate((size_t)n) : 1.0;
-				const double bl = rate * (t.height[t.parent[n]] - t.height[n]);  // treelikelihood.c:1657
-				if (bl < 0) throw Error("negative branch length above node " + std::to_string(n));
-				I.branch_lengths[n] = bl;
-			} else
-				I.branch_lengths[n] = t.distance[n];
-		}
+		FormBranchLengths(I.branch_lengths);
 		// Parameters_set_values only fires listeners for values that changed (update_nodes[index], treelikelihood.c:73-92):
 		// a few changed branches are sent one by one and the engine recomputes only the paths above them
 		size_t diffs = 0;
@@ -712,8 +719,19 @@ void TreeLikelihoodInterface::Gradient(double *gradient) {
 		}
 	} else
 		phyamd::check(phyamd_gradient(I.engine, eflags, &lnl, I.cat_grad.data()));
+	GradientEpilogue(lnl, I.cat_grad, I.branch_lengths, subst_grad, gradient);
+}
+
+// from lnL and the per-category branch gradient of one evaluation (cat_grad [node][category], branch_lengths as sent to the engine,
+// the tree model holding that evaluation's parameters) to the requested blocks, in the reference's order
+void TreeLikelihoodInterface::GradientEpilogue(double lnl, std::vector<double> &cat_grad, const std::vector<double> &branch_lengths,
+                                               const std::vector<double> &subst_grad, double *gradient) {
+	auto &I = *impl_;
+	const phyamd::Tree &t = *treeModel_->GetTree();
+	phyamd::SiteModel &sm = *siteModel_->GetModel();
+	const int N = t.node_count, C = sm.cat_count;
 	if (!t.time_mode)  // treelikelihood.c:3249-3255: the right child of the root carries no branch of an unrooted tree
-		for (int c = 0; c < C; c++) I.cat_grad[(size_t)t.right[t.root] * C + c] = 0.0;
+		for (int c = 0; c < C; c++) cat_grad[(size_t)t.right[t.root] * C + c] = 0.0;
 	// site-model parameters: gradient_discrete_sitemodel (treelikelihood.c:3010-3052) on the per-category gradients
 	double site_grad[3];
 	size_t site_count = 0;
@@ -722,7 +740,7 @@ void TreeLikelihoodInterface::Gradient(double *gradient) {
 		const double mu = sm.has_mu ? sm.mu : 1.0;
 		for (int n = 0; n < N; n++) {
 			if (n == t.root || (!t.time_mode && n == t.right[t.root])) continue;
-			for (int c = sm.has_pinv ? 1 : 0; c < C; c++) ingrad[c] += I.cat_grad[(size_t)n * C + c] * I.branch_lengths[n] * mu;  // :3237-3242
+			for (int c = sm.has_pinv ? 1 : 0; c < C; c++) ingrad[c] += cat_grad[(size_t)n * C + c] * branch_lengths[n] * mu;  // :3237-3242
 		}
 		if (sm.dist != phyamd::RateDistribution::Constant) site_grad[site_count++] = sm.shape_gradient(ingrad.data());
 		if (sm.has_pinv) {
@@ -736,10 +754,10 @@ void TreeLikelihoodInterface::Gradient(double *gradient) {
 	std::vector<double> g(N, 0.0);
 	const double mu_factor = (sm.has_mu && !referenceCompat_) ? sm.mu : 1.0;
 	for (int n = 0; n < N; n++) {
-		if (C == 1) g[n] = I.cat_grad[n] * mu_factor;
+		if (C == 1) g[n] = cat_grad[n] * mu_factor;
 		else {
-			double s = I.cat_grad[(size_t)n * C] * sm.cat_props[0] * sm.cat_rates[0];
-			for (int c = 1; c < C; c++) s += I.cat_grad[(size_t)n * C + c] * sm.cat_props[c] * sm.cat_rates[c];
+			double s = cat_grad[(size_t)n * C] * sm.cat_props[0] * sm.cat_rates[0];
+			for (int c = 1; c < C; c++) s += cat_grad[(size_t)n * C + c] * sm.cat_props[c] * sm.cat_rates[c];
 			g[n] = s * mu_factor;
 		}
 	}
@@ -775,7 +793,7 @@ void TreeLikelihoodInterface::Gradient(double *gradient) {
 		if (sm.has_mu) {  // treelikelihood.c:3288-3302: sum over branches of d lnL / d(mu * length) times the length
 			double gm = 0.0;
 			for (int n = 0; n < N; n++)
-				if (n != t.root) gm += g[n] / mu_factor * I.branch_lengths[n];
+				if (n != t.root) gm += g[n] / mu_factor * branch_lengths[n];
 			gradient[j++] = gm;
 		}
 	}
@@ -789,4 +807,58 @@ void TreeLikelihoodInterface::Gradient(double *gradient) {
 	for (double v : subst_grad) gradient[j++] = v;  // [rates][frequencies], treelikelihood.c:3313-3357
 	if (std::isnan(lnl) || std::isinf(lnl))
 		for (size_t i = 0; i < j; i++) gradient[i] = NAN;  // treelikelihood.c:327-332
+}
+
+// lnL (LogLikelihoodBatch) or lnL and the gradient (GradientBatch) for `count` parameter vectors of the tree model: per item the
+// branch lengths as Sync() forms them, ONE phyamd_gradient_batch call, then Gradient's epilogue per item
+void TreeLikelihoodInterface::EvaluateBatch(size_t count, const double *treeParameters, double *logLikelihoods, double *gradients) {
+	if (count == 0) return;
+	if (!treeParameters) throw Error("null treeParameters");
+	if (count > (size_t)INT32_MAX) throw Error("a batch takes at most 2^31 - 1 items");
+	if (gradients && ((flags_ & (int)TreeLikelihoodGradientFlags::SITE_MODEL) || substRates_ || substFreqs_))
+		throw Error("GradientBatch takes TREE_HEIGHT and BRANCH_MODEL requests: site-model and substitution-model gradients need per-item root terms");
+	Sync();
+	auto &I = *impl_;
+	const phyamd::Tree &t = *treeModel_->GetTree();
+	const size_t n = treeModel_->parameterCount_, N = (size_t)t.node_count, C = (size_t)siteModel_->GetModel()->cat_count;
+	std::vector<double> previous(n), lengths(count * N), one;
+	treeModel_->GetParameters(previous.data());
+	struct PutBack {  // the tree model holds its previous parameters afterwards, whatever happens
+		TreeModelInterface *m;
+		const double *p;
+		~PutBack() { m->SetParameters(p); }
+	} put_back{treeModel_, previous.data()};
+	for (size_t b = 0; b < count; b++) {
+		treeModel_->SetParameters(treeParameters + b * n);
+		FormBranchLengths(one);
+		std::copy(one.begin(), one.end(), lengths.begin() + b * N);
+	}
+	// lnL does not depend on the gradient flags.  In compatibility mode the gradient asks for the reference's rescaled arithmetic
+	// (COMPAT_SCALED), which the engine's batched walk does not form: those items are evaluated one by one, never batched
+	const int eflags = gradients && referenceCompat_ ? (PHYAMD_GRAD_FOLD_ROOT_FREQS | PHYAMD_GRAD_COMPAT_SCALED) : 0;
+	std::vector<double> lnl(count), cat_grad(gradients ? count * N * C : 0), cg;
+	phyamd::check(phyamd_gradient_batch(I.engine, eflags, (int32_t)count, lengths.data(), lnl.data(), gradients ? cat_grad.data() : nullptr));
+	const std::vector<double> no_subst;
+	for (size_t b = 0; b < count; b++) {
+		if (!gradients && !(includeJacobian_ && t.reparameterized)) {
+			logLikelihoods[b] = lnl[b];
+			continue;
+		}
+		treeModel_->SetParameters(treeParameters + b * n);
+		if (logLikelihoods) logLikelihoods[b] = lnl[b] + (includeJacobian_ && t.reparameterized ? phyamd::ratio_transform_log_jacobian(t) : 0.0);
+		if (!gradients) continue;
+		cg.assign(cat_grad.begin() + b * N * C, cat_grad.begin() + (b + 1) * N * C);
+		one.assign(lengths.begin() + b * N, lengths.begin() + (b + 1) * N);
+		GradientEpilogue(lnl[b], cg, one, no_subst, gradients + b * gradientLength_);
+	}
+}
+
+void TreeLikelihoodInterface::LogLikelihoodBatch(size_t count, const double *treeParameters, double *logLikelihoods) {
+	if (!logLikelihoods) throw Error("null logLikelihoods");
+	EvaluateBatch(count, treeParameters, logLikelihoods, nullptr);
+}
+
+void TreeLikelihoodInterface::GradientBatch(size_t count, const double *treeParameters, double *logLikelihoods, double *gradients) {
+	if (!gradients) throw Error("null gradients");
+	EvaluateBatch(count, treeParameters, logLikelihoods, gradients);
 }

@@ -195,6 +195,19 @@ PYBIND11_MODULE(_phycpp_amd, m) {
 	         py::arg("include_jacobian") = false, py::keep_alive<1, 4>(), py::keep_alive<1, 5>(), py::keep_alive<1, 6>(), py::keep_alive<1, 7>())
 	    .def("request_gradient", &TreeLikelihoodInterface::RequestGradient, py::arg("flags") = std::vector<TreeLikelihoodGradientFlags>())
 	    .def("set_reference_compatibility", &TreeLikelihoodInterface::SetReferenceCompatibility)
+	    .def("log_likelihood_batch", [](TreeLikelihoodInterface &self, darray params) {
+		    if (params.ndim() != 2 || (size_t)params.shape(1) != self.TreeParameterCount()) throw phyamd::Error("tree parameters: [count][parameter_count]");
+		    std::vector<double> lnl((size_t)params.shape(0));
+		    self.LogLikelihoodBatch(lnl.size(), params.data(), lnl.data());
+		    return vec(lnl);
+	    })
+	    .def("gradient_batch", [](TreeLikelihoodInterface &self, darray params) {
+		    if (params.ndim() != 2 || (size_t)params.shape(1) != self.TreeParameterCount()) throw phyamd::Error("tree parameters: [count][parameter_count]");
+		    const size_t count = (size_t)params.shape(0);
+		    std::vector<double> lnl(count), g(count * self.gradientLength_);
+		    self.GradientBatch(count, params.data(), lnl.data(), g.data());
+		    return py::make_tuple(vec(lnl), darray({(py::ssize_t)count, (py::ssize_t)self.gradientLength_}, g.data()));
+	    })
 	    .def("get_pattern_count", &TreeLikelihoodInterface::GetPatternCount)
 	    .def("pattern_weights", [](TreeLikelihoodInterface &self) { return vec(self.PatternWeights()); })
 	    .def("pattern_states", [](TreeLikelihoodInterface &self) {

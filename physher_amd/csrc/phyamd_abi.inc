@@ -466,6 +466,44 @@ int phyamd_branch_hessian_diagonal(phyamd_engine *g, int flags, double *lnl, dou
 	return PHYAMD_OK;
 }
 
+// every shard runs the whole batch on its patterns; per-item results are added like phyamd_gradient's
+int phyamd_gradient_batch(phyamd_engine *g, int flags, int32_t count, const double *branch_lengths, double *lnl, double *cat_gradient) {
+	if (count < 1) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch: count must be >= 1 (got %d)", count);
+	if (!branch_lengths || !lnl) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch: null branch_lengths or lnl");
+	CHECK_GROUP(g);
+	if (group_size(g) == 1) return shard_gradient_batch(g->shards[0], flags, count, branch_lengths, lnl, cat_gradient);
+	const size_t ncat = (size_t)g->N * g->C, n = (size_t)count * (cat_gradient ? 1 + ncat : 1);
+	ensure_scratch(g, n);
+	int rc;
+	if ((rc = for_shards(g, [&](Shard *s, int i) {
+		     double *v = g->scratch[i].data();  // [lnl[count] | cat_gradient[count][N C]]
+		     return shard_gradient_batch(s, flags, count, branch_lengths, v, cat_gradient ? v + count : nullptr);
+	     })))
+		return rc;
+	std::vector<double> total(n);
+	sum_shards(g, n, total.data());
+	std::memcpy(lnl, total.data(), sizeof(double) * count);
+	if (cat_gradient) std::memcpy(cat_gradient, total.data() + count, sizeof(double) * count * ncat);
+	return PHYAMD_OK;
+}
+
+int phyamd_get_batch_profile(phyamd_engine *g, phyamd_batch_profile *out) {
+	CHECK_GROUP(g);
+	if (!out) return fail(PHYAMD_EINVAL, "null out");
+	int rc;
+	if ((rc = shard_get_batch_profile(g->shards[0], out))) return rc;
+	for (int i = 1; i < group_size(g); i++) {  // shards choose their paths themselves: the fewest fast items, the most of everything else
+		phyamd_batch_profile p;
+		if ((rc = shard_get_batch_profile(g->shards[i], &p))) return rc;
+		out->items_fast = std::min(out->items_fast, p.items_fast);
+		out->items_sequential = std::max(out->items_sequential, p.items_sequential);
+		out->chunks = std::max(out->chunks, p.chunks);
+		out->scratch_bytes += p.scratch_bytes;
+		out->ms = std::max(out->ms, p.ms);
+	}
+	return PHYAMD_OK;
+}
+
 // device-resident results (one process per GPU: the caller reduces them across processes with ONE RCCL all-reduce)
 int phyamd_log_likelihood_device(phyamd_engine *g, double *device_out) {
 	CHECK_GROUP(g);

@@ -1,0 +1,171 @@
+// phyamd_batch4.inc: 4-state kernels of phyamd_gradient_batch -- lnL and the branch gradient for many branch-length vectors on one
+// tree and one alignment in a single launch -- included by phyamd_engine.hip inside its anonymous namespace.
+//
+// The single-evaluation walks are built to fill the card with ONE evaluation.  A batch of B small ones (69 taxa x 238 patterns x 4
+// categories is 16 waves each) fills it along the item axis instead: workgroup (block, item) = the category waves of 64 patterns of
+// one item.  A wave walks the whole tree twice from two host-built op lists that every item shares (built once per topology,
+// build_batch_ops): post-order, storing every internal node's partial p_n in the item's scratch (one 32-byte access per lane);
+// after ONE meeting of the categories in LDS for the site likelihood, pre-order with the branch terms.  Matrices are wave-uniform
+// and come through scalar loads from the item's block; tip messages are P . mask from the 4-bit tip codes, the same bytes for
+// every item.  No floating-point atomics: a branch term is summed over the 64 lanes by wave_sum (fixed order), written to the
+// slab [item][block][C][node], and k_batch_finish adds the blocks in block order.  An item's arithmetic therefore depends on
+// nothing but its own lengths: not on the batch size, its position in the batch, or the chunk it ran in.
+
+// post-order: node = (P_left p_left) o (P_right p_right); carry 1 / 2: the left / right child's partial is the previous op's result
+// pre-order: the op of `node` forms its children's uppers.  src: where u_node is (BATCH_ROOT: node is the root; BATCH_CARRY: the
+// previous op handed it on in registers; >= 0: upper slot); dst_left / dst_right: where a child's upper goes (BATCH_NONE: a tip's
+// is not kept)
+struct BatchOp {
+	int32_t node, left, right;
+	int32_t carry;
+	int32_t src, dst_left, dst_right;
+	int32_t pad;
+};
+enum { BATCH_NONE = -1, BATCH_CARRY = -2, BATCH_ROOT = -3 };
+
+constexpr int BATCH_MAX_CATEGORIES = 8;  // one LDS row of site-likelihood terms per category; at most 8 category waves per workgroup
+
+// op i of a list, through the constant address space like the matrices: the lists are read-only kernel inputs at wave-uniform
+// addresses, so the eight words come by one s_load_dwordx8 instead of vector loads on the walk's dependent chain
+__device__ __forceinline__ BatchOp load_batch_op(const BatchOp *ops, int i) {
+	typedef const __attribute__((address_space(4))) int32_t *cint;
+	const cint o = (cint)reinterpret_cast<const int32_t *>(ops + i);
+	return BatchOp{o[0], o[1], o[2], o[3], o[4], o[5], o[6], 0};
+}
+
+struct BatchArgs {
+	const BatchOp *lower_ops, *upper_ops;  // T - 1 ops each
+	int T, N, P, C, nblk, upper_slots;
+	int grad;                              // 0: the post-order pass and lnL only
+	const uint8_t *tipmask;                // [T][P]
+	const double *freqs, *props, *weights, *Q;
+	const double *mats;                    // [item][N][C][16]
+	double *lower;                         // [item][T - 1][C][nblk * 64][4]
+	double *upper;                         // [item][upper_slots][C][nblk * 64][4]
+	double *lnl_part;                      // [item][nblk]
+	double *slab;                          // [item][nblk][C][N]
+};
+
+// P(t) of every (item, node, category) from the eigen system: k_transition_matrices' arithmetic, each item with its own lengths
+// ([items][N]; the root's entry is skipped, nothing reads its matrix)
+__global__ void k_batch_matrices(int C, int N, int items, const double *__restrict__ model, const double *__restrict__ rates,
+                                 const double *__restrict__ lengths, int root, double *__restrict__ mats) {
+	const size_t total = (size_t)items * N * C * 16;
+	const double *eval = model, *evec = model + 4, *ivec = model + 4 + 16;
+	for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+		const int j = idx & 3, i = (idx >> 2) & 3;
+		const int c = (idx >> 4) % C;
+		const size_t in = idx / ((size_t)16 * C);  // item * N + node
+		if ((int)(in % N) == root) continue;
+		const double t = lengths[in] * rates[c];
+		double p = 0.;
+		for (int k = 0; k < 4; k++) p += ivec[k * 4 + j] * evec[i * 4 + k] * exp(eval[k] * t);
+		mats[idx] = fabs(p);  // substmodel.c:552
+	}
+}
+
+// message of a child to its parent at (pattern lane, category c): P_child . mask for a tip, P_child . p_child for an internal node
+__device__ __forceinline__ d4 batch_message(const BatchArgs &a, cptr mats_c, const double *lower_c, size_t node_stride, int child, int k) {
+	const cptr M = opaque(mats_c + (size_t)child * a.C * 16);
+	if (child < a.T) return matvec4(M, mask4(a.tipmask[(size_t)child * a.P + k]));
+	return matvec4(M, load4(lower_c + (size_t)(child - a.T) * node_stride));
+}
+
+// grid (nblk, items), block (64, C): the C category waves of one (item, block).  a.grad: the pre-order
+// pass too (a launch argument, not an instantiation: the lnL-only form runs the very instructions of the gradient form's first
+// half, so both return the same lnL bits); FOLD: PHYAMD_GRAD_FOLD_ROOT_FREQS (k_upper4's arithmetic: the root's children start
+// from pi, the state sum drops it)
+template <bool FOLD>
+__global__ __launch_bounds__(BATCH_MAX_CATEGORIES *WAVE) void k_batch_walk4(const BatchArgs a) {
+	__shared__ double sh[BATCH_MAX_CATEGORIES * WAVE];
+	const int lane = threadIdx.x, c = __builtin_amdgcn_readfirstlane(threadIdx.y);  // this wave's category
+	const int blk = blockIdx.x, item = blockIdx.y;
+	const int k0 = blk * WAVE + lane;  // the scratch is padded to whole blocks: every lane owns its cells
+	const bool valid = k0 < a.P;
+	const int k = valid ? k0 : a.P - 1;
+	const int nops = a.T - 1;
+	const size_t plane = (size_t)a.nblk * WAVE * 4, node_stride = (size_t)a.C * plane;
+	const double *mats_i = a.mats + (size_t)item * a.N * a.C * 16;
+	double *lower_i = a.lower + (size_t)item * nops * node_stride + (size_t)k0 * 4;
+	const d4 pi = d4{a.freqs[0], a.freqs[1], a.freqs[2], a.freqs[3]};
+
+	{
+		const cptr mats_c = as_const(mats_i + (size_t)c * 16);
+		double *lower_c = lower_i + (size_t)c * plane;
+		d4 p = d4{0., 0., 0., 0.};
+#pragma unroll 1
+		for (int i = 0; i < nops; i++) {
+			const BatchOp op = load_batch_op(a.lower_ops, i);
+			const d4 l = op.carry == 1 ? matvec4(opaque(mats_c + (size_t)op.left * a.C * 16), p) : batch_message(a, mats_c, lower_c, node_stride, op.left, k);
+			const d4 r = op.carry == 2 ? matvec4(opaque(mats_c + (size_t)op.right * a.C * 16), p) : batch_message(a, mats_c, lower_c, node_stride, op.right, k);
+			p = mul4(l, r);
+			store4(lower_c + (size_t)(op.node - a.T) * node_stride, p);
+		}
+		// the last op is the root's: integrate_partials (treelikelihood.c:1473-1487), as k_lower4 forms it
+		sh[c * WAVE + lane] = a.props[c] * (pi.x * p.x + pi.y * p.y + pi.z * p.z + pi.w * p.w);
+	}
+	__syncthreads();  // the one meeting of the categories
+	double L = 0.0;
+	for (int cc = 0; cc < a.C; cc++) L += sh[cc * WAVE + lane];
+	const double w = valid ? a.weights[k] : 0.0;
+	if (c == 0) {
+		const double s = wave_sum(valid ? log(L) * w : 0.0);
+		if (lane == 0) a.lnl_part[(size_t)item * a.nblk + blk] = s;
+	}
+	if (!a.grad) return;
+
+	const double wl = valid ? w / L : 0.0;  // the gradient's w_k / L_k (treelikelihood.c:2879)
+	const d4 one = d4{1., 1., 1., 1.}, f = FOLD ? one : pi;
+	const cptr Q = as_const(a.Q);
+	double *upper_i = a.upper + (size_t)item * a.upper_slots * node_stride + (size_t)k0 * 4;
+	{
+		const cptr mats_c = as_const(mats_i + (size_t)c * 16);
+		const double *lower_c = lower_i + (size_t)c * plane;
+		double *upper_c = upper_i + (size_t)c * plane;
+		double *slab = a.slab + (((size_t)item * a.nblk + blk) * a.C + c) * a.N;
+		d4 carried = one;
+#pragma unroll 1
+		for (int i = 0; i < nops; i++) {
+			const BatchOp op = load_batch_op(a.upper_ops, i);
+			const d4 bl = batch_message(a, mats_c, lower_c, node_stride, op.left, k);
+			const d4 br = batch_message(a, mats_c, lower_c, node_stride, op.right, k);
+			d4 up = FOLD ? pi : one;
+			if (op.src != BATCH_ROOT) {
+				const d4 u = op.src == BATCH_CARRY ? carried : load4(upper_c + (size_t)op.src * node_stride);
+				up = matvec4(opaque(mats_c + (size_t)op.node * a.C * 16), u);
+			}
+			const d4 ul = mul4(up, br), ur = mul4(up, bl);  // treelikelihood.c:2142-2147
+			// g[child][c] = sum_k w_k / L_k sum_i f_i u_i (Q P p)_i   (treelikelihood.c:2846-2939)
+			const double gl = wave_sum(wl * dot4(mul4(f, ul), matvec4(opaque(Q), bl)));
+			const double gr = wave_sum(wl * dot4(mul4(f, ur), matvec4(opaque(Q), br)));
+			if (lane == 0) {
+				slab[op.left] = gl;
+				slab[op.right] = gr;
+			}
+			if (op.dst_left >= 0) store4(upper_c + (size_t)op.dst_left * node_stride, ul);
+			if (op.dst_right >= 0) store4(upper_c + (size_t)op.dst_right * node_stride, ur);
+			if (op.dst_left == BATCH_CARRY) carried = ul;
+			if (op.dst_right == BATCH_CARRY) carried = ur;
+		}
+	}
+}
+
+// out[item][0] = lnL, out[item][1 + node * C + c] = g[node][c] (the root's row 0): the blocks' entries added in block order.
+// rows = 1 (lnL only) or 1 + N C; thread r of an item reads the slab's entry r - 1 of every block ([C][N]: coalesced)
+__global__ __launch_bounds__(256) void k_batch_finish(int items, int N, int C, int nblk, int root, int rows, const double *__restrict__ lnl_part,
+                                                     const double *__restrict__ slab, double *__restrict__ out) {
+	const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+	if (idx >= (size_t)items * rows) return;
+	const size_t item = idx / rows;
+	const int r = (int)(idx % rows);
+	double s = 0.0;
+	if (r == 0) {
+		for (int b = 0; b < nblk; b++) s += lnl_part[item * nblk + b];
+		out[item * rows] = s;
+		return;
+	}
+	const int c = (r - 1) / N, node = (r - 1) % N;
+	if (node != root)
+		for (int b = 0; b < nblk; b++) s += slab[((item * nblk + b) * C + c) * N + node];
+	out[item * rows + 1 + (size_t)node * C + c] = s;
+}

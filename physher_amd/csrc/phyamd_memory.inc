@@ -11,6 +11,9 @@ struct DeviceBudget {
 	int64_t bytes = 0;
 	DeviceBudget *const whole;
 	std::vector<DeviceBuffer *> arrays;  // the arrays bound to this budget
+	// on a shard's whole budget: a group of its arrays that is only kept for reuse (the batch scratch).  It never stands in the way:
+	// an array outside the group that would not fit -- the cap, or the device itself -- has the group released first
+	DeviceBudget *spare = nullptr;
 	void release_all();
 };
 
@@ -46,12 +49,25 @@ protected:
 		if (grew) *grew = false;
 		if (p_ && bytes_ >= bytes) return PHYAMD_OK;
 		release();
+		DeviceBudget *spare = nullptr;  // the spare group, if this array is not of it and it holds anything
 		for (DeviceBudget *b = budget_; b; b = b->whole)
+			if (b->spare && b->spare != budget_ && b->spare->bytes > 0) spare = b->spare;
+		for (DeviceBudget *b = budget_; b; b = b->whole) {
+			if (b->cap > 0 && b->bytes + (int64_t)bytes > b->cap && spare) {
+				spare->release_all();
+				spare = nullptr;
+			}
 			if (b->cap > 0 && b->bytes + (int64_t)bytes > b->cap)
 				return fail(PHYAMD_ENOMEM, "max_device_bytes (%lld) would be exceeded: %lld bytes resident, %zu more requested", (long long)b->cap,
 				            (long long)b->bytes, bytes);
+		}
 		void *p = nullptr;
-		HIP_TRY(hipMalloc(&p, bytes));
+		if (spare && hipMalloc(&p, bytes) != hipSuccess) {  // (the device is full of spare arrays)
+			(void)hipGetLastError();
+			p = nullptr;
+			spare->release_all();
+		}
+		if (!p) HIP_TRY(hipMalloc(&p, bytes));
 		p_ = p;
 		bytes_ = bytes;
 		for (DeviceBudget *b = budget_; b; b = b->whole) b->bytes += (int64_t)bytes;

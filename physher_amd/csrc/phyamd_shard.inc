@@ -216,6 +216,23 @@ struct Shard {
 
 	hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
 	phyamd_profile prof{};
+
+	// phyamd_gradient_batch (phyamd_batch4.inc): op lists of the tree they were built for, and the scratch of batch_items items --
+	// per-item lengths, matrices and results; lowers, parked uppers and slabs
+	std::vector<uint8_t> tip_empty;      // tip -> some cell of its data has an empty state mask (0/1 tip partials that are all 0)
+	int batch_max_patterns = 0;          // the fast path's pattern bound (BATCH_MAX_PATTERNS; PHYAMD_BATCH_MAX_PATTERNS: the crossover sweep)
+	std::vector<int32_t> batch_left, batch_right;
+	int batch_root = -1, batch_upper_slots = 0;
+	std::vector<BatchOp> batch_ops;      // [post-order T - 1 | pre-order T - 1]
+	DeviceArray<BatchOp> d_batch_ops{&mem};
+	// the scratch is a spare group of the shard's budget (DeviceBudget::spare): counted in device_bytes while held, released
+	// whenever an array of the engine itself needs the room, with the pattern storage and on a new topology
+	DeviceBudget batch_mem{&mem};
+	DeviceArray<double> d_batch_len{&batch_mem}, d_batch_mats{&batch_mem}, d_batch_out{&batch_mem};
+	DeviceArray<double> d_batch_lower{&batch_mem}, d_batch_upper{&batch_mem}, d_batch_slab{&batch_mem}, d_batch_lnl{&batch_mem};
+	int batch_items = 0;                 // items the scratch holds
+	bool batch_grad = false;             // ... with the pre-order pass's part
+	phyamd_batch_profile batch_prof{};
 };
 
 // ---- what d_lower holds ----------------------------------------------------------------------------------------------------
@@ -303,4 +320,23 @@ PassKernel upper_kernel(const Shard *e, int flags, bool with_params, bool made) 
 	}
 	if (!compat && stream_possible(e) && stream_shape_fits(e, e->lower_form) && !(made && e->stream_unsupported)) return PassKernel::Stream;
 	return PassKernel::Walk;
+}
+
+// ---- which path a batch of branch-length vectors takes (phyamd_gradient_batch) ----------------------------------------------
+// The batched walk (k_batch_walk4) is an optimisation of "evaluate the items one by one": it runs exactly when every condition
+// below holds, and every other engine evaluates the items through the ordinary path.  fit: items whose scratch fits the budget.
+// Above BATCH_MAX_PATTERNS patterns the loop over the single-evaluation walks wins: one evaluation fills the card by itself there,
+// and those walks store half the partials (measured, profiles/batch_sweep.json, DESIGN.md "A batch of branch-length vectors": at
+// 8 192 patterns the batched call is 2.1-3.6x faster at 64 taxa and between 1.2x faster and 1.3x slower at 500; at 32 768 the loop
+// wins by up to 2.5x, but for a tie at 64 taxa x 32 items).
+// 8 192 is a compromise, not a clean crossover: the point moves with the tree size and the batch size (profiles/batch_sweep.json).
+constexpr int BATCH_MAX_PATTERNS = 8192;
+bool batch_fast_path(const Shard *e, int flags, size_t fit) {
+	if (e->generic || e->C > BATCH_MAX_CATEGORIES) return false;  // 4 states, one LDS row per category
+	if (e->scaling_on) return false;                               // the walk does not rescale (RESCALE_AUTO: a non-finite item is redone)
+	if (e->tiles > 1) return false;                                // the tip data of all patterns are resident
+	if (e->P > e->batch_max_patterns) return false;
+	if (std::any_of(e->tip_empty.begin(), e->tip_empty.end(), [](uint8_t x) { return x != 0; })) return false;
+	if (flags & ~PHYAMD_GRAD_FOLD_ROOT_FREQS) return false;
+	return fit >= 1;
 }

@@ -122,6 +122,7 @@ int allocate_pattern_storage(Shard *e) {
 // before any tip data or weights have been loaded: drop everything sized by the tile (phyamd_set_topology re-tiles)
 void free_pattern_storage(Shard *e) {
 	e->tile_mem.release_all();
+	e->batch_mem.release_all();
 	e->d_gslab = nullptr;
 	e->hess_P = -1;
 	e->mstream_epoch = 0;
@@ -185,6 +186,10 @@ int shard_create(const phyamd_config *cfg, Shard **out) {
 	if (const char *env = std::getenv("PHYAMD_STREAM_TFORM")) e->tform_on = std::atoi(env) != 0;
 	e->generic = e->S != 4;
 	e->tip_set.assign(e->T, 0);
+	e->tip_empty.assign(e->T, 0);
+	e->mem.spare = &e->batch_mem;
+	e->batch_max_patterns = BATCH_MAX_PATTERNS;
+	if (const char *env = std::getenv("PHYAMD_BATCH_MAX_PATTERNS")) e->batch_max_patterns = std::atoi(env);
 	e->explicit_host.assign(e->N, 0);
 	const size_t msz = (size_t)e->N * e->C * e->S * e->S;
 	if (e->generic && ((rc = e->d_tipsets.ensure(256)) || (rc = e->d_imgs.ensure(((size_t)e->N * e->C + 2) * gen_image_doubles(e))))) return bail(rc);
@@ -246,6 +251,7 @@ int shard_set_tip_states(Shard *e, int tip, const uint8_t *states) {
 	HIP_TRY(hipMemcpyAsync(tip_row(e, tip), mask.data(), e->Ptot, hipMemcpyHostToDevice, e->stream));
 	HIP_TRY(hipStreamSynchronize(e->stream));
 	e->tip_set[tip] = 1;
+	e->tip_empty[tip] = 0;
 	e->tip_epoch++;
 	e->all_dirty = true;
 	e->stored.valid = false;
@@ -304,6 +310,7 @@ int shard_set_tip_partials(Shard *e, int tip, const double *partials) {
 	HIP_TRY(hipMemcpyAsync(tip_row(e, tip), mask.data(), e->Ptot, hipMemcpyHostToDevice, e->stream));
 	HIP_TRY(hipStreamSynchronize(e->stream));
 	e->tip_set[tip] = 1;
+	e->tip_empty[tip] = std::find(mask.begin(), mask.end(), (uint8_t)0) != mask.end();
 	e->tip_epoch++;
 	e->all_dirty = true;
 	e->stored.valid = false;
@@ -328,6 +335,7 @@ int shard_set_topology(Shard *e, const int32_t *left, const int32_t *right, int 
 	if (!left || !right) return fail(PHYAMD_EINVAL, "null topology arrays");
 	int rc;
 	if ((rc = bind_device(e))) return rc;
+	e->batch_mem.release_all();  // (sized by the old tree; the tile plan below counts what the engine itself holds)
 	std::vector<int32_t> old_l = e->left, old_r = e->right;
 	const int old_root = e->root;
 	e->left.assign(left, left + e->N);
@@ -1119,5 +1127,265 @@ int shard_get_profile(Shard *e, phyamd_profile *out) {
 	e->prof.device_bytes = e->mem.bytes;
 	e->prof.tiles = e->tiles;
 	*out = e->prof;
+	return PHYAMD_OK;
+}
+
+// ---- a batch of branch-length vectors (phyamd_gradient_batch) ----------------------------------------------------------------
+
+// the two op lists of the batched walk for the engine's tree.  Post-order: depth first, the larger subtree first, so that the child
+// finished last hands its partial on in registers.  Pre-order: of two internal children the smaller subtree is entered first with
+// its upper in registers and the other's upper is parked in a slot that is free again once its op has read it: at most
+// log2(T) + 1 slots, whatever the shape (a caterpillar parks nothing).
+void build_batch_ops(Shard *e) {
+	const int T = e->T, N = e->N;
+	e->batch_left = e->left;
+	e->batch_right = e->right;
+	e->batch_root = e->root;
+	e->batch_ops.clear();
+	std::vector<int> size(N, 1), order;
+	{
+		std::vector<int> stack{e->root};
+		while (!stack.empty()) {
+			const int n = stack.back();
+			stack.pop_back();
+			order.push_back(n);
+			if (n >= T) {
+				stack.push_back(e->left[n]);
+				stack.push_back(e->right[n]);
+			}
+		}
+		for (size_t i = order.size(); i-- > 0;)
+			if (order[i] >= T) size[order[i]] += size[e->left[order[i]]] + size[e->right[order[i]]];
+	}
+	{  // post-order: (node, children done?) on an explicit stack
+		std::vector<std::pair<int, bool>> stack{{e->root, false}};
+		int last = -1;
+		while (!stack.empty()) {
+			const auto [n, done] = stack.back();
+			stack.pop_back();
+			const int l = e->left[n], r = e->right[n];
+			if (!done) {
+				stack.push_back({n, true});
+				const int first = size[l] >= size[r] ? l : r, second = first == l ? r : l;
+				if (second >= T) stack.push_back({second, false});
+				if (first >= T) stack.push_back({first, false});
+				continue;
+			}
+			BatchOp op{n, l, r, last == l && l >= T ? 1 : last == r && r >= T ? 2 : 0, BATCH_NONE, BATCH_NONE, BATCH_NONE, 0};
+			e->batch_ops.push_back(op);
+			last = n;
+		}
+	}
+	{  // pre-order
+		std::vector<std::pair<int, int>> stack{{e->root, BATCH_ROOT}};  // (node, where its upper is)
+		std::vector<int> free_slots;
+		int slots = 0;
+		while (!stack.empty()) {
+			const auto [n, src] = stack.back();
+			stack.pop_back();
+			const int l = e->left[n], r = e->right[n];
+			BatchOp op{n, l, r, 0, src, BATCH_NONE, BATCH_NONE, 0};
+			if (l >= T && r >= T) {
+				int slot;
+				if (free_slots.empty()) slot = slots++;
+				else {
+					slot = free_slots.back();
+					free_slots.pop_back();
+				}
+				const bool left_first = size[l] <= size[r];
+				op.dst_left = left_first ? BATCH_CARRY : slot;
+				op.dst_right = left_first ? slot : BATCH_CARRY;
+				stack.push_back({left_first ? r : l, slot});
+				stack.push_back({left_first ? l : r, BATCH_CARRY});
+			} else if (l >= T) {
+				op.dst_left = BATCH_CARRY;
+				stack.push_back({l, BATCH_CARRY});
+			} else if (r >= T) {
+				op.dst_right = BATCH_CARRY;
+				stack.push_back({r, BATCH_CARRY});
+			}
+			e->batch_ops.push_back(op);
+			if (src >= 0) free_slots.push_back(src);  // read by this op: later ops may park in it
+		}
+		e->batch_upper_slots = std::max(1, slots);
+	}
+}
+
+// bytes of batch scratch one item takes (grad: with the pre-order pass's uppers and slab)
+size_t batch_item_bytes(const Shard *e, bool grad) {
+	const size_t nblk = ((size_t)e->P + WAVE - 1) / WAVE, plane = nblk * WAVE * 4;
+	size_t doubles = (size_t)e->N + (size_t)e->N * e->C * 16 + 1 + (grad ? (size_t)e->N * e->C : 0) + (size_t)(e->T - 1) * e->C * plane + nblk;
+	if (grad) doubles += (size_t)e->batch_upper_slots * e->C * plane + nblk * e->C * e->N;
+	return sizeof(double) * doubles;
+}
+
+size_t batch_scratch_bytes(const Shard *e) { return (size_t)e->batch_mem.bytes; }
+
+void release_batch_scratch(Shard *e) {
+	e->batch_mem.release_all();
+	e->batch_items = 0;
+}
+
+// items the scratch holds now (none once the group has been released to make room)
+size_t batch_items_held(const Shard *e, bool grad) { return e->d_batch_lower.get() && (e->batch_grad || !grad) ? (size_t)e->batch_items : 0; }
+
+constexpr int BATCH_MAX_CHUNK = 65535;  // gridDim.y
+
+// items of a (count, grad) batch whose scratch fits beside the engine: within the cap less everything the engine holds or may
+// still allocate -- what is resident whatever the tile size, the tile's working set as choose_tiles reserves it, the walks'
+// on-demand buffers -- or, without a cap, within most of what the device has free right now.  What the scratch holds already is
+// kept unless more items would fit.
+size_t batch_items_that_fit(const Shard *e, size_t count, bool grad) {
+	const size_t want = std::min<size_t>(count, BATCH_MAX_CHUNK), have = batch_items_held(e, grad);
+	if (have >= want) return want;
+	const double held = (double)batch_scratch_bytes(e);
+	double room;
+	if (e->cfg.max_device_bytes > 0) {
+		const double tile_now = (double)e->tile_mem.bytes, resident = (double)e->mem.bytes - held - tile_now;
+		room = (double)e->cfg.max_device_bytes - (resident + 65536.0 + walk_reserve(e) + std::max(tile_now, tile_working_set(e, (double)e->P, true)));
+	} else {
+		size_t free_bytes = 0, total_bytes = 0;
+		room = hipMemGetInfo(&free_bytes, &total_bytes) == hipSuccess ? 0.8 * ((double)free_bytes + held) : 0.0;
+	}
+	const double fit = std::floor(room / (double)batch_item_bytes(e, grad));
+	if (fit <= (double)have) return have;
+	return (size_t)std::min((double)want, fit);
+}
+
+int ensure_batch_scratch(Shard *e, size_t items, bool grad) {
+	if (batch_items_held(e, grad) >= items) return PHYAMD_OK;
+	release_batch_scratch(e);  // (the arrays grow together: all are freed before any is allocated again)
+	const size_t nblk = ((size_t)e->P + WAVE - 1) / WAVE, plane = nblk * WAVE * 4, rows = grad ? (size_t)1 + e->N * e->C : 1;
+	int rc;
+	if ((rc = e->d_batch_len.ensure(items * e->N)) || (rc = e->d_batch_mats.ensure(items * e->N * e->C * 16)) || (rc = e->d_batch_out.ensure(items * rows)) ||
+	    (rc = e->d_batch_lower.ensure(items * (e->T - 1) * e->C * plane)) || (rc = e->d_batch_lnl.ensure(items * nblk)) ||
+	    (grad && ((rc = e->d_batch_upper.ensure(items * e->batch_upper_slots * e->C * plane)) || (rc = e->d_batch_slab.ensure(items * nblk * e->C * e->N))))) {
+		release_batch_scratch(e);
+		return rc;
+	}
+	e->batch_items = (int)items;
+	e->batch_grad = grad;
+	return PHYAMD_OK;
+}
+
+// one chunk of `items` items through the batched walk: lengths [items][N] (host) -> out [items][rows] (host), rows = 1 or 1 + N C
+int run_batch_chunk(Shard *e, int flags, int items, const double *lengths, bool grad, double *out) {
+	const int nblk = (e->P + WAVE - 1) / WAVE, rows = grad ? 1 + e->N * e->C : 1;
+	HIP_TRY(hipMemcpyAsync(e->d_batch_len, lengths, sizeof(double) * (size_t)items * e->N, hipMemcpyHostToDevice, e->stream));
+	const size_t total = (size_t)items * e->N * e->C * 16;
+	hipLaunchKernelGGL(k_batch_matrices, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, e->stream, e->C, e->N, items, e->d_model, e->d_rates,
+	                   e->d_batch_len, e->root, e->d_batch_mats);
+	const BatchArgs a{e->d_batch_ops, e->d_batch_ops + (e->T - 1), e->T, e->N, e->P, e->C, nblk, e->batch_upper_slots, grad ? 1 : 0, e->d_tipmask, e->d_freqs, e->d_props,
+	                  e->d_weights, e->d_Q, e->d_batch_mats, e->d_batch_lower, e->d_batch_upper, e->d_batch_lnl, e->d_batch_slab};
+	const dim3 grid(nblk, items), block(WAVE, e->C);
+	if (flags & PHYAMD_GRAD_FOLD_ROOT_FREQS) hipLaunchKernelGGL(k_batch_walk4<true>, grid, block, 0, e->stream, a);
+	else hipLaunchKernelGGL(k_batch_walk4<false>, grid, block, 0, e->stream, a);
+	hipLaunchKernelGGL(k_batch_finish, dim3((unsigned)(((size_t)items * rows + 255) / 256)), dim3(256), 0, e->stream, items, e->N, e->C, nblk, e->root, rows,
+	                   e->d_batch_lnl, e->d_batch_slab, e->d_batch_out);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(out, e->d_batch_out, sizeof(double) * (size_t)items * rows, hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	return PHYAMD_OK;
+}
+
+// the definition of the call: item by item through the ordinary path (the caller puts the engine's lengths back)
+int batch_item_sequential(Shard *e, int flags, const double *lengths, double *lnl, double *cat_gradient) {
+	int rc;
+	if ((rc = shard_set_branch_lengths(e, lengths))) return rc;
+	return cat_gradient ? shard_gradient(e, flags, lnl, cat_gradient) : shard_log_likelihood(e, lnl);
+}
+
+// the items of a batch, each through the batched walk or the ordinary path; prof: how many went which way
+int run_batch(Shard *e, int flags, int32_t count, const double *branch_lengths, double *lnl, double *cat_gradient, phyamd_batch_profile &prof) {
+	int rc;
+	{  // ready but for the lengths, which the call brings itself
+		const bool had = e->have_lengths;
+		e->have_lengths = true;
+		rc = check_ready(e);
+		e->have_lengths = had;
+		if (rc) return rc;
+	}
+	for (int n = 0; n < e->N; n++)
+		if (n != e->root && e->explicit_host[n])
+			return fail(PHYAMD_EUNSUPPORTED, "phyamd_gradient_batch: node %d has explicit matrices, which cannot follow per-item branch lengths", n);
+	if (cat_gradient && !e->have_Q) return fail(PHYAMD_EINVAL, "the gradient needs the rate matrix: phyamd_set_eigen or phyamd_set_rate_matrix");
+	const bool grad = cat_gradient != nullptr;
+	const size_t N = (size_t)e->N, ncat = N * e->C, rows = grad ? 1 + ncat : 1;
+	std::vector<uint8_t> redo(count, 1);  // items the sequential path (still) has to evaluate
+	if (e->batch_left != e->left || e->batch_right != e->right || e->batch_root != e->root || e->batch_ops.empty()) {
+		build_batch_ops(e);
+		release_batch_scratch(e);  // (sized by the tree's upper slots)
+		if ((rc = e->d_batch_ops.ensure(e->batch_ops.size()))) return rc;
+		HIP_TRY(hipMemcpyAsync(e->d_batch_ops, e->batch_ops.data(), sizeof(BatchOp) * e->batch_ops.size(), hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipStreamSynchronize(e->stream));
+	}
+	std::vector<double> lengths, out;
+	for (size_t first = 0; first < (size_t)count && batch_fast_path(e, flags, 1);) {
+		// (every chunk asks again: an item that went through the ordinary path may have taken the scratch's room)
+		const size_t chunk = batch_items_that_fit(e, (size_t)count - first, grad);
+		if (!batch_fast_path(e, flags, chunk)) break;
+		if ((rc = ensure_batch_scratch(e, chunk, grad))) return rc;
+		const size_t items = std::min(chunk, (size_t)count - first);
+		lengths.assign(branch_lengths + first * N, branch_lengths + (first + items) * N);
+		out.resize(items * rows);
+		for (size_t b = 0; b < items; b++) lengths[b * N + e->root] = 0.0;  // (ignored, as phyamd_set_branch_lengths does)
+		if ((rc = run_batch_chunk(e, flags, (int)items, lengths.data(), grad, out.data()))) return rc;
+		prof.chunks++;
+		for (size_t b = 0; b < items; b++) {
+			const double l = out[b * rows];
+			const bool bad = std::isnan(l) || std::isinf(l);
+			if (bad && e->cfg.rescale == PHYAMD_RESCALE_AUTO) {
+				// the lazy switch's case (treelikelihood.c:1496-1519): this item goes through the ordinary path right away, and
+				// if that turns rescaling on, so does the rest of the batch
+				if ((rc = batch_item_sequential(e, flags, branch_lengths + (first + b) * N, lnl + first + b, grad ? cat_gradient + (first + b) * ncat : nullptr))) return rc;
+				redo[first + b] = 0;
+				prof.items_sequential++;
+				continue;
+			}
+			lnl[first + b] = l;
+			for (size_t i = 0; grad && i < ncat; i++) cat_gradient[(first + b) * ncat + i] = bad ? NAN : out[b * rows + 1 + i];  // treelikelihood.c:327-332
+			redo[first + b] = 0;
+			prof.items_fast++;
+		}
+		first += items;
+	}
+	for (int b = 0; b < count; b++) {
+		if (!redo[b]) continue;
+		if ((rc = batch_item_sequential(e, flags, branch_lengths + (size_t)b * N, lnl + b, grad ? cat_gradient + (size_t)b * ncat : nullptr))) return rc;
+		prof.items_sequential++;
+	}
+	return PHYAMD_OK;
+}
+
+int shard_gradient_batch(Shard *e, int flags, int32_t count, const double *branch_lengths, double *lnl, double *cat_gradient) {
+	CHECK_ENGINE(e);
+	if (count < 1) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch: count must be >= 1 (got %d)", count);
+	if (!branch_lengths || !lnl) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch: null branch_lengths or lnl");
+	const auto t0 = std::chrono::steady_clock::now();
+	int rc;
+	if ((rc = bind_device(e))) return rc;
+	const std::vector<double> lengths = e->lengths;
+	const bool had_lengths = e->have_lengths;
+	phyamd_batch_profile prof{};
+	rc = run_batch(e, flags, count, branch_lengths, lnl, cat_gradient, prof);
+	if (prof.items_sequential > 0 || rc) {  // the ordinary path has set items' lengths: the engine's own go back
+		const std::string why = g_last_error;
+		if (had_lengths) {
+			const int rc2 = shard_set_branch_lengths(e, lengths.data());
+			if (!rc) rc = rc2;
+			else g_last_error = why;
+		} else
+			e->have_lengths = false;
+	}
+	prof.scratch_bytes = (int64_t)batch_scratch_bytes(e);
+	prof.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	e->batch_prof = prof;
+	return rc;
+}
+
+int shard_get_batch_profile(Shard *e, phyamd_batch_profile *out) {
+	CHECK_ENGINE(e);
+	if (!out) return fail(PHYAMD_EINVAL, "null out");
+	*out = e->batch_prof;
 	return PHYAMD_OK;
 }

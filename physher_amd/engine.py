@@ -203,6 +203,24 @@ class Engine:
         """[lnL | d1[N] | d2[N]] -> device_ptr on the engine's stream (sums over this engine's patterns)"""
         self._check(self._lib.phyamd_branch_hessian_diagonal_device(self._h, flags, C.c_void_p(device_ptr)))
 
+    def gradient_batch(self, branch_lengths, flags=0, want_gradient=True):
+        """lnL and the per-category branch gradient for B branch-length vectors [B, N] at once: (lnl [B], g [B, N, C] or None).
+        Item b is what set_branch_lengths(branch_lengths[b]) + gradient(flags) returns; the engine's own lengths stay."""
+        bl = _f64(branch_lengths)
+        if bl.ndim != 2 or bl.shape[1] != self.N or bl.shape[0] < 1:
+            raise ValueError(f"branch_lengths must be [B >= 1, {self.N}] (got {bl.shape})")
+        count = bl.shape[0]
+        lnl = np.empty(count)
+        g = np.empty((count, self.N, self.C)) if want_gradient else None
+        self._check(self._lib.phyamd_gradient_batch(self._h, flags, count, _ptr(bl), _ptr(lnl), None if g is None else _ptr(g)))
+        return lnl, g
+
+    def batch_profile(self):
+        """Of the last gradient_batch: items_fast / items_sequential, chunks, scratch_bytes, ms."""
+        p = _lib.BatchProfile()
+        self._check(self._lib.phyamd_get_batch_profile(self._h, C.byref(p)))
+        return {k: getattr(p, k) for k, _ in p._fields_}
+
     def store(self):
         """Remember the current (evaluated) state: parameters, lnL and partials (MCMC store)."""
         self._check(self._lib.phyamd_store(self._h))
