@@ -6,10 +6,7 @@ int rebuild_schedule(Shard *e) {
 	if ((rc = build_schedule(e))) return rc;
 	if ((rc = upload_schedule(e))) return rc;
 	if ((rc = ensure_lower_storage(e))) return rc;
-	e->schedule_epoch++;  // slots start over: a stored state no longer maps onto them
-	e->upper_valid = false;
-	e->all_dirty = true;
-	e->lower_valid = false;
+	input_changed(e, Input::ScheduleRebuilt);
 	return PHYAMD_OK;
 }
 
@@ -33,32 +30,32 @@ int run_lower(Shard *e, int need_host_check) {
 	e->act_level_off = &e->lower_level_off;
 	e->act_lower_ops = e->d_lower_ops;
 	e->incremental_pass = false;
-	bool incremental = e->lower_valid && !e->all_dirty;
-	if (incremental && e->lower_form != LowerForm::Reference && !(e->changed.empty() && !e->force_root)) {
+	bool incremental = !e->state.all_dirty;
+	if (incremental && e->lower_form != LowerForm::Reference && !lowers_current(e)) {
 		// an incremental update reads stored children in the reference's form: this pass recomputes every node in it
 		prefer_reference_form(e);
 		incremental = false;
 	}
-	if (incremental && e->changed.empty() && !e->force_root) {  // nothing changed: d_result[0] still holds lnL
+	if (lowers_current(e)) {  // nothing changed: d_result[0] still holds lnL
 		record(e, 2);
 		e->prof.lower_launches = 0;
 		e->prof_pending = e->profiling;
 		e->prof_with_upper = false;
 		return PHYAMD_OK;
 	}
-	e->path_node = -1;  // partials are about to change
+	uppers_dropped(e);  // partials are about to change
 	std::vector<uint8_t> dirty;
 	if (incremental) {
 		// only single branch lengths changed since the stored partials were computed: recompute the core nodes on the paths
 		// from those branches to the root, in level order (update_nodes[] semantics, treelikelihood.c:73-114, 1645-1734)
 		dirty.assign(e->N, 0);
 		// (20 / 60 / 61 states store t_n = P_n p_n: the branch's own node is recomputed too)
-		for (int n : e->changed)
+		for (int n : e->state.changed)
 			for (int a = e->generic && n >= e->T ? n : e->parent[n]; a >= 0 && !dirty[a]; a = e->parent[a])
 				if (e->core_index[a] >= 0) dirty[a] = 1;  // fused fringe nodes are recomputed inside their first stored ancestor
-		if (e->force_root) dirty[e->root] = 1;
+		if (e->state.force_root) dirty[e->root] = 1;
 	}
-	if (e->stored.valid && e->stored.epoch == e->schedule_epoch) {
+	if (e->state.stored_valid && e->stored.epoch == e->schedule_epoch) {
 		// nodes about to be written leave the slot the stored state lives in (current_partials_indexes flip, treelikelihood.c:1693-1700)
 		bool moved = false;
 		for (int n = e->T; n < e->N; n++)
@@ -116,14 +113,10 @@ int run_lower(Shard *e, int need_host_check) {
 		e->incremental_pass = false;
 	}
 	e->incremental_pass = false;
-	e->lower_valid = true;
-	e->all_dirty = false;
-	e->force_root = false;
-	e->changed.clear();
+	lowers_computed(e);
 	record(e, 2);
 	e->prof_pending = e->profiling;
 	e->prof_with_upper = false;
-	e->upper_valid = false;
 	return PHYAMD_OK;
 }
 
@@ -139,11 +132,11 @@ int update_parameter_matrices(Shard *e) {
 	if ((rc = e->d_B.ensure((size_t)np * S * S)) || (rc = e->d_dpm.ensure((size_t)np * e->N * e->C * S * S)) || (rc = e->d_dptab.ensure((size_t)np * e->T * e->C * 64)) ||
 	    (rc = e->d_ppart.ensure((size_t)np * e->upper_ops.size() * ((size_t)e->nblk + 1))))
 		return rc;
-	if (e->params_dirty) {
+	if (e->state.params_dirty) {
 		const std::vector<double> B = eigen_basis_derivatives(e);
 		HIP_TRY(hipMemcpyAsync(e->d_B, B.data(), sizeof(double) * B.size(), hipMemcpyHostToDevice, e->stream));
 		HIP_TRY(hipStreamSynchronize(e->stream));  // B is a stack-lifetime buffer
-		e->params_dirty = false;
+		parameter_basis_rebuilt(e);
 	}
 	const size_t total = (size_t)np * e->N * e->C * S * S;
 	hipLaunchKernelGGL(k_parameter_matrices, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, e->stream, S, e->C, e->N, np, e->d_model,
@@ -164,7 +157,6 @@ int launch_parameters_gen(Shard *e, double *dst) {
 		return rc;
 	bool grew;
 	if ((rc = e->d_pg_B.ensure((size_t)np * S2, &grew))) return rc;
-	if (grew) e->params_dirty = true;
 	{  // the schedule may have been rebuilt since the last call: the two index tables are N ints
 		std::vector<int> nodes;
 		for (int n = 0; n < e->N; n++)
@@ -173,11 +165,11 @@ int launch_parameters_gen(Shard *e, double *dst) {
 		HIP_TRY(hipMemcpyAsync(e->d_pg_core, e->core_index.data(), sizeof(int) * e->N, hipMemcpyHostToDevice, e->stream));
 		HIP_TRY(hipStreamSynchronize(e->stream));
 	}
-	if (e->params_dirty) {
+	if (grew || e->state.params_dirty) {
 		const std::vector<double> Bm = eigen_basis_derivatives(e);
 		HIP_TRY(hipMemcpyAsync(e->d_pg_B, Bm.data(), sizeof(double) * Bm.size(), hipMemcpyHostToDevice, e->stream));
 		HIP_TRY(hipStreamSynchronize(e->stream));
-		e->params_dirty = false;
+		parameter_basis_rebuilt(e);
 	}
 	{  // the kernels below take every node's partial p_n itself; the post-order pass stores t_n = P_n p_n (k_lower_gen)
 		const size_t npd = node_partial_doubles(e);
@@ -242,8 +234,6 @@ int finish_lazy_check(Shard *e, bool *again) {
 	e->scaling_on = true;
 	if ((rc = rebuild_schedule(e))) return rc;
 	if ((rc = ensure_scaling_storage(e))) return rc;
-	e->lower_valid = false;
-	e->all_dirty = true;
 	*again = true;
 	return PHYAMD_OK;
 }
@@ -316,7 +306,7 @@ int run_gradient(Shard *e, int flags, bool with_params = false) {
 	HIP_TRY(hipGetLastError());
 	record(e, 4);
 	e->prof_with_upper = true;
-	e->upper_valid = true;
+	uppers_computed(e);
 	bool again = false;
 	if ((rc = finish_lazy_check(e, &again))) return rc;
 	return again ? run_gradient(e, flags, with_params) : PHYAMD_OK;
@@ -346,13 +336,10 @@ int run_hessian(Shard *e, double *out) {
 		const int rc2 = rebuild_schedule(e);
 		if (!rc) rc = rc2;
 	}
-	e->upper_valid = false;  // (the level pass's uppers: not those a keep-partials gradient leaves)
+	uppers_dropped(e);  // (the level pass's uppers: not those a keep-partials gradient leaves)
 	if (!form_only) {
 		e->reference_form_only = false;
-		if (e->lower_form != stream_lower_form(e)) {
-			e->lower_valid = false;
-			e->all_dirty = true;
-		}
+		if (e->lower_form != stream_lower_form(e)) lowers_discarded(e);
 	}
 	return rc;
 }
@@ -388,13 +375,12 @@ int run_tiled(Shard *e, int mode, int flags) {
 		const size_t off = (size_t)t * e->P;
 		const size_t w = std::min<size_t>((size_t)e->P, (size_t)e->Ptot - off);
 		HIP_TRY(hipMemcpy2DAsync(e->d_tipmask, (size_t)e->P, e->d_tip_all + off, (size_t)e->Ptot, w, (size_t)e->T, hipMemcpyDeviceToDevice, e->stream));
-		e->tip_epoch++;
 		HIP_TRY(hipMemcpyAsync(e->d_weights, e->d_weights_all + off, sizeof(double) * w, hipMemcpyDeviceToDevice, e->stream));
 		if (w < (size_t)e->P) {  // ragged last tile: unknown tips of weight 0 (L = 1, log L = 0, no gradient)
 			HIP_TRY(hipMemset2DAsync(e->d_tipmask + w, (size_t)e->P, unknown, (size_t)e->P - w, (size_t)e->T, e->stream));
 			HIP_TRY(hipMemsetAsync(e->d_weights + w, 0, sizeof(double) * ((size_t)e->P - w), e->stream));
 		}
-		e->all_dirty = true;
+		tile_loaded(e);
 		if ((rc = mode == 0 ? run_lower(e, true) : mode == 3 ? run_hessian(e, result) : run_gradient(e, flags, mode == 2))) return rc;
 		hipLaunchKernelGGL(k_accumulate, dim3((n + 255) / 256), dim3(256), 0, e->stream, n, result, total);
 		if (e->C >= 2) {  // the +I site-model gradient needs this tile's root partial while it is resident (in the form it is in)
@@ -405,11 +391,7 @@ int run_tiled(Shard *e, int mode, int flags) {
 		HIP_TRY(hipMemcpyAsync(e->d_plk_all + off, e->d_plk, sizeof(double) * w, hipMemcpyDeviceToDevice, e->stream));
 	}
 	HIP_TRY(hipMemcpyAsync(result, total, sizeof(double) * n, hipMemcpyDeviceToDevice, e->stream));
-	e->tiled_root_term = mode == 2;
-	e->tiled_eval_done = true;
-	e->lower_valid = false;  // the resident partials are those of the last tile only
-	e->all_dirty = true;
-	e->upper_valid = false;
+	tiled_totals_computed(e, mode == 2);
 	return PHYAMD_OK;
 }
 

@@ -17,15 +17,13 @@ void build_matrix_images(Shard *e, int count, const double *src, double *dst, co
 }
 
 int update_matrices(Shard *e) {
-	if (e->generic && e->qimg_dirty && e->have_Q && e->have_freqs) {  // images of Q and of diag(pi) Q behind the per-(node, category) ones
+	if (e->generic && e->state.qimg_dirty && e->have_Q && e->have_freqs) {  // images of Q and of diag(pi) Q behind the per-(node, category) ones
 		build_matrix_images(e, 1, e->d_Q, e->d_imgs + (size_t)e->N * e->C * gen_image_doubles(e));
 		build_matrix_images(e, 1, e->d_Q, e->d_imgs + ((size_t)e->N * e->C + 1) * gen_image_doubles(e), e->d_freqs);
 		HIP_TRY(hipGetLastError());
-		e->qimg_dirty = false;
-		e->qp_kind = -1;
+		q_images_rebuilt(e);
 	}
-	if (!e->matrices_dirty) return PHYAMD_OK;
-	e->qp_kind = -1;
+	if (!e->state.matrices_dirty) return PHYAMD_OK;
 	if (e->have_eigen) {
 		const size_t total = (size_t)e->N * e->C * e->S * e->S;
 		const int blocks = (int)std::min<size_t>((total + 255) / 256, 4096);
@@ -41,7 +39,7 @@ int update_matrices(Shard *e) {
 		build_matrix_images(e, e->N * e->C, e->d_mats, e->d_imgs);
 		HIP_TRY(hipGetLastError());
 	}
-	e->matrices_dirty = false;
+	matrices_rebuilt(e);
 	return PHYAMD_OK;
 }
 
@@ -86,13 +84,13 @@ int true_lower_gen(Shard *e, int node, double *out, double *side) {
 // the branch term of a tip child, sum_i u_i (Qf P e_code)_i, from a column of that product instead of forming Qf . (P e_code)
 int ensure_tip_rate_products(Shard *e, bool fold) {
 	const int kind = fold ? 0 : 1;
-	if (e->qp_kind == kind) return PHYAMD_OK;
+	if (e->state.qp_kind == kind) return PHYAMD_OK;
 	const size_t count = (size_t)e->T * e->C;  // (d_qp_mats, d_qp_imgs: allocated with the engine, phyamd_create)
 	hipLaunchKernelGGL(k_tip_rate_products, dim3((unsigned)count), dim3(256), 0, e->stream, e->S, e->d_mats, e->d_Q, fold ? (const double *)nullptr : e->d_freqs,
 	                   e->d_qp_mats);
 	build_matrix_images(e, (int)count, e->d_qp_mats, e->d_qp_imgs);
 	HIP_TRY(hipGetLastError());
-	e->qp_kind = kind;
+	tip_rate_products_rebuilt(e, kind);
 	return PHYAMD_OK;
 }
 
@@ -317,7 +315,7 @@ int launch_hess4(Shard *e, double *out) {
 }
 
 int upload_qpi(Shard *e) {
-	if (!e->qpi_dirty) return PHYAMD_OK;  // diag(pi) Q, 16 doubles
+	if (!e->state.qpi_dirty) return PHYAMD_OK;  // diag(pi) Q, 16 doubles
 	int rc;
 	if ((rc = e->d_Qpi.ensure(16))) return rc;
 	double qpi[16];
@@ -325,7 +323,7 @@ int upload_qpi(Shard *e) {
 		for (int j = 0; j < 4; j++) qpi[i * 4 + j] = e->freqs[i] * e->Q_host[i * 4 + j];
 	HIP_TRY(hipMemcpyAsync(e->d_Qpi, qpi, sizeof(qpi), hipMemcpyHostToDevice, e->stream));
 	HIP_TRY(hipStreamSynchronize(e->stream));
-	e->qpi_dirty = false;
+	qpi_rebuilt(e);
 	return PHYAMD_OK;
 }
 
@@ -335,7 +333,7 @@ int ensure_mask_stream(Shard *e) {
 	bool grew;
 	if (int rc = e->d_mstream.ensure((size_t)std::max(1, e->stream_words) * mstride, &grew)) return rc;
 	if (grew) e->mstream_epoch = 0;
-	if (e->mstream_epoch == e->tip_epoch && e->mstride == mstride && e->mstream_layout == e->stream_row_entries) return PHYAMD_OK;
+	if (e->mstream_epoch == e->state.tip_epoch && e->mstride == mstride && e->mstream_layout == e->stream_row_entries) return PHYAMD_OK;
 	e->mstride = mstride;
 	e->stream_unsupported = false;
 	e->stream_ambiguous = false;
@@ -350,7 +348,7 @@ int ensure_mask_stream(Shard *e) {
 		e->stream_unsupported = (flag & 1) != 0;
 		e->stream_ambiguous = (flag & 2) != 0;
 	}
-	e->mstream_epoch = e->tip_epoch;
+	e->mstream_epoch = e->state.tip_epoch;
 	e->mstream_layout = e->stream_row_entries;
 	return PHYAMD_OK;
 }

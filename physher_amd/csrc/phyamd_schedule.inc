@@ -579,7 +579,6 @@ int build_schedule(Shard *e) {
 		}
 	}
 	e->node_kind = kind;
-	e->path_node = -1;
 	// stored lower arrays: core nodes in id order
 	e->core_index.assign(N, -1);
 	e->core_count = 0;

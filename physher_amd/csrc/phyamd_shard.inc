@@ -25,11 +25,25 @@ struct Shard {
 	int lnl_blocks = 0;    // entries of d_lnl_part the last post-order pass wrote
 	int grad_blocks = 0;   // entries per row of d_gpart the last pre-order pass wrote
 	size_t gpart_row = 0;  // allocated entries per row
-	// incremental (dirty-node) post-order updates: D1, treelikelihood.c:73-114, 1645-1734
-	bool lower_valid = false;         // stored lower partials are those of the current inputs except for `changed` branches
-	bool all_dirty = true;            // something other than single branch lengths changed: recompute every node
+	// which products of the inputs are current: written only by "what each input invalidates" below
+	struct State {
+		// stored lowers, with incremental (dirty-node) post-order updates: D1, treelikelihood.c:73-114, 1645-1734
+		bool all_dirty = true;         // they are not those of the current inputs: recompute every node
+		std::vector<int> changed;      // ... they are, except above these nodes, whose branch length changed since the last evaluation
+		bool force_root = false;       // ... except for the root's outputs (lnL_k, w_k / L_k, lnL), which belong to a discarded state
+		bool upper_valid = false;      // d_upper holds the uppers of a gradient at the current inputs (resident: of a keep-partials one)
+		int path_node = -1;            // node whose upper d_path_upper holds (-1: none)
+		bool matrices_dirty = true;    // P(t) with the tip tables / MFMA images
+		bool qimg_dirty = true;        // 20 / 60 / 61 states: the images of Q and diag(pi) Q
+		bool qpi_dirty = true;         // 4 states: diag(pi) Q
+		int qp_kind = -1;              // which Qf the images of Qf P(t) hold: 0 = Q (pi folded into the uppers), 1 = diag(pi) Q, -1 = none
+		bool params_dirty = true;      // U^-1 dQ U
+		bool stored_valid = false;     // the MCMC stored state below
+		bool tiled_eval_done = false;  // d_total holds the sums of a tiled evaluation at the current inputs
+		bool tiled_root_term = false;  // ... and d_result the summed root frequency term of a tiled parameter gradient
+		unsigned long tip_epoch = 1;   // the tip data in d_tipmask (the mask words: as of mstream_epoch)
+	} state;
 	bool incremental_pass = false;
-	std::vector<int> changed;         // nodes whose branch length changed since the last evaluation
 	std::vector<NodeOp> inc_ops;      // ops of the dirty core nodes, by level
 	std::vector<int> inc_level_off;
 	DeviceArray<NodeOp> d_inc_ops{&mem};
@@ -40,7 +54,6 @@ struct Shard {
 	// store every stored node has two slots (slot = core index, + core_count for the second); an evaluation never writes the
 	// slot the stored state lives in, so restore is an index flip (plus re-integrating the root), not a recomputation
 	struct Stored {
-		bool valid = false;
 		std::vector<double> lengths, model, freqs, rates, props;
 		std::vector<int32_t> core_index;  // node -> slot of the stored state
 		bool have_eigen = false, scaling_on = false;
@@ -50,13 +63,10 @@ struct Shard {
 	// pattern tiling (cfg.max_device_bytes): P = patterns per tile (what every kernel sees), Ptot = the caller's count;
 	// tip data, weights and per-pattern lnL of all tiles stay resident, the partial arrays are reused tile after tile
 	int Ptot = 0, tiles = 1;
-	bool tiled_eval_done = false;
-	bool tiled_root_term = false;     // d_result holds the summed root frequency term of a tiled parameter gradient
 	DeviceArray<uint8_t> d_tip_all{&tile_mem};  // [T][Ptot]
 	DeviceArray<double> d_weights_all{&tile_mem}, d_plk_all{&tile_mem}, d_total{&tile_mem};
 	unsigned long schedule_epoch = 0;  // bumped whenever slots are reassigned from scratch
 	bool two_slots = false;            // d_lower / d_lscale hold 2 * core_count slots
-	bool force_root = false;           // the root's outputs (lnL_k, w_k / L_k, lnL) belong to a discarded state
 	bool generic_fusion = true;  // 20 states: cherries fused into their parents' ops (PHYAMD_GEN_FUSION = 0: every node stored)
 	bool walk_enabled = true;  // PHYAMD_WALK = 0: no walk lists, every pass runs the level kernels
 	// the schedule built walk lists (not keep_partials): 4 states / 20 states unscaled (phyamd_genwalk.inc); what runs on them is
@@ -104,7 +114,7 @@ struct Shard {
 	DeviceArray<int> d_stream_row_entries{&mem}, d_stream_site_tab{&mem}, d_stream_qnode{&mem}, d_oct_lo{&mem};
 	DeviceArray<uint32_t> d_mstream{&tile_mem};
 	size_t mstride = 0;
-	unsigned long tip_epoch = 1, mstream_epoch = 0;  // tip data / mask words as of which tip data
+	unsigned long mstream_epoch = 0;     // state.tip_epoch of the tip data the mask words were built from
 	std::vector<int> mstream_layout;     // stream_row_entries the device stream was built for
 	double *d_gslab = nullptr;           // the walk-order slab, in d_gpart's storage
 	DeviceArray<double> d_oct{&mem};
@@ -115,10 +125,8 @@ struct Shard {
 	bool lnl_per_block = false;          // d_lnl_part holds one entry per block of 64 patterns (the tree walk)
 	DeviceArray<double> d_Lc{&tile_mem};  // [C][P] per-category site likelihoods at the root
 	DeviceArray<double> d_imgs{&mem};  // generic: MFMA fragment images of P(t) per (node, category), then of Q (k_matrix_images)
-	bool qimg_dirty = true;
 	DeviceArray<double> d_qp_mats{&mem};  // generic: Qf P(t) per (tip, category), row-major, and its fragment images (k_tip_rate_products): the
 	DeviceArray<double> d_qp_imgs{&mem};  // branch term of a tip child is a column of that product, looked up instead of multiplied out
-	int qp_kind = -1;             // which Qf the images hold: 0 = Q (pi folded into the uppers), 1 = diag(pi) Q, -1 = none
 	DeviceArray<double> d_inv_part{&tile_mem};  // partial sums of k_root_invariant_term
 	int device = 0;
 	hipStream_t stream = nullptr;
@@ -129,7 +137,6 @@ struct Shard {
 	std::vector<uint8_t> explicit_host;
 	bool have_topology = false, have_lengths = false, have_eigen = false, have_freqs = false, have_rates = false, have_weights = false;
 	std::vector<uint8_t> tip_set;
-	bool matrices_dirty = true;
 	bool scaling_on = false;
 	// the form of the stored 4-state lowers in the slots core_index points at now, and the policy that decides it (below,
 	// "what d_lower holds"): reference_form_only = some reader has needed the reference's form, every later post-order pass writes it
@@ -139,7 +146,6 @@ struct Shard {
 	DeviceArray<int> d_lexp{&tile_mem}, d_uexp{&tile_mem}, d_Ec{&tile_mem}, d_Eroot{&tile_mem};  // exponents: [stored][C][P], [upper slots][C][P], [C][P], [P]
 	bool keep_partials = false;
 	bool profiling = false;
-	bool upper_valid = false;
 	bool prof_pending = false, prof_with_upper = false;
 
 	// schedule
@@ -167,7 +173,6 @@ struct Shard {
 	DeviceArray<double> d_Q{&mem};
 	DeviceArray<double> d_Qpi{&mem};  // diag(pi) Q: the tree-walk gradient contracts u with (pi o Q b) in one mat-vec (4 states)
 	std::vector<double> Q_host;
-	bool qpi_dirty = true;
 	bool have_Q = false;
 	DeviceArray<double> d_tiptab{&mem};  // [T][C][16][4] tip messages (4-state), then the DeepDesc table
 	// substitution-parameter gradient (G2)
@@ -187,7 +192,6 @@ struct Shard {
 	DeviceArray<double> d_path_upper{&mem}, d_path_tmp{&mem}, d_path_lower{&mem};  // one node partial each
 	DeviceArray<double> d_path_side{&mem};  // 20 / 60 / 61 states: two node partials beside true_lower_gen (fused cherries below the node)
 	DeviceArray<double> d_pg_lower{&mem};   // 20 / 60 / 61 states, parameter gradient: every stored node's partial itself (d_lower holds P p)
-	int path_node = -1;              // node whose upper d_path_upper holds (-1: none); dropped whenever partials are recomputed
 	// phyamd_branch_hessian_diagonal (ensure_hess_storage): workgroup table and slab of the HESS pre-order pass
 	DeviceArray<int> d_hess_tab{&tile_mem};
 	DeviceArray<double> d_hess{&tile_mem};
@@ -201,7 +205,6 @@ struct Shard {
 	// 20 / 60 / 61 states (k_param_*_gen): branch nodes, node -> stored lower index, per-branch site likelihoods, G tables
 	DeviceArray<int> d_pg_nodes{&mem}, d_pg_core{&mem};
 	DeviceArray<double> d_pg_den{&mem}, d_pg_Gw{&mem}, d_pg_B{&mem};
-	bool params_dirty = true;
 	DeviceArray<double> d_model{&mem}, d_freqs{&mem}, d_rates{&mem}, d_props{&mem}, d_lengths{&mem}, d_result{&mem};
 	DeviceArray<double> d_weights{&tile_mem}, d_plk{&tile_mem}, d_lscale{&tile_mem}, d_lnl_part{&tile_mem}, d_gpart{&tile_mem};
 	DeviceArray<double> d_wl{&tile_mem};  // [P] w_k / L_k from the root kernel (unscaled evaluations)
@@ -234,6 +237,65 @@ struct Shard {
 	bool batch_grad = false;             // ... with the pre-order pass's part
 	phyamd_batch_profile batch_prof{};
 };
+
+// ---- what each input invalidates -------------------------------------------------------------------------------------------
+// The only place that writes Shard::state: a setter says which input changed (input_changed: the table), an evaluation what it has
+// computed or overwritten (the transitions), and readers ask one of the three predicates.
+enum class Input { TipData, PatternWeights, Topology, BranchLengths, BranchLength, Eigen, RateMatrix, Frequencies, CategoryRates, NodeMatrices,
+                   Matrices, RateMatrixDerivatives, UpdateAllNodes, ScheduleRebuilt };
+
+bool lowers_current(const Shard *e) { return !e->state.all_dirty && e->state.changed.empty() && !e->state.force_root; }
+bool uppers_resident(const Shard *e) { return e->keep_partials && e->state.upper_valid; }
+bool tiled_totals_current(const Shard *e, bool root_term = false) { return e->state.tiled_eval_done && (!root_term || e->state.tiled_root_term); }
+
+// d_upper and d_path_upper belong to other lowers or have been overwritten / the stored lowers are not those of the current
+// inputs, or not in the slots or the form their next reader needs: the next evaluation recomputes every node
+void uppers_dropped(Shard *e) { e->state.upper_valid = false, e->state.path_node = -1; }
+void lowers_discarded(Shard *e) { e->state.all_dirty = true, uppers_dropped(e); }
+
+// input -> the products it invalidates.  node: the branch of BranchLength / NodeMatrices (-1: the node has none)
+void input_changed(Shard *e, Input in, int node = -1) {
+	Shard::State &s = e->state;
+	s.tiled_eval_done = s.tiled_root_term = false;  // (every input: the totals are sums over what they were formed from)
+	bool tables = false, lowers = false;            // P(t) with the tip tables / MFMA images; all lowers, and the uppers with them
+	switch (in) {
+	case Input::TipData: lowers = true, s.stored_valid = false, s.tip_epoch++; break;
+	case Input::PatternWeights: lowers = true, s.stored_valid = false; break;
+	case Input::Topology: tables = lowers = true, s.stored_valid = false, e->schedule_epoch++; break;  // (not part of phyamd_store)
+	case Input::BranchLengths:  // the whole vector: every node is recomputed (SingleTreeLikelihood_update_all_nodes)
+	case Input::CategoryRates:
+	case Input::Matrices:
+	case Input::UpdateAllNodes: tables = lowers = true; break;
+	case Input::BranchLength:  // all P(t) are re-formed (microseconds); only the partials above `node` are recomputed
+	case Input::NodeMatrices:
+		tables = true, uppers_dropped(e);
+		if (node >= 0) s.changed.push_back(node);
+		break;
+	case Input::Eigen: tables = lowers = true, s.qimg_dirty = s.qpi_dirty = s.params_dirty = true; break;
+	case Input::RateMatrix: s.qimg_dirty = s.qpi_dirty = true; break;
+	case Input::Frequencies: lowers = true, s.qimg_dirty = s.qpi_dirty = true; break;  // (20 / 60 / 61 states: the image of diag(pi) Q)
+	case Input::RateMatrixDerivatives: s.params_dirty = true; break;
+	case Input::ScheduleRebuilt: lowers = true, e->schedule_epoch++; break;  // slots start over: a stored state no longer maps onto them
+	}
+	if (tables) s.matrices_dirty = true;
+	if (lowers) lowers_discarded(e);
+}
+
+// transitions: a tile's data are in place; the tails of run_lower, run_gradient and run_tiled (the resident partials are the last
+// tile's only); shard_store; rebuild_path_upper; shard_restore's index flip (the root's outputs are still the discarded state's)
+void tile_loaded(Shard *e) { e->state.tip_epoch++, lowers_discarded(e); }
+void lowers_computed(Shard *e) { e->state.all_dirty = e->state.force_root = false, e->state.changed.clear(); }
+void uppers_computed(Shard *e) { e->state.upper_valid = true; }
+void tiled_totals_computed(Shard *e, bool root_term) { e->state.tiled_eval_done = true, e->state.tiled_root_term = root_term, lowers_discarded(e); }
+void state_stored(Shard *e) { e->state.stored_valid = true; }
+void path_upper_rebuilt(Shard *e, int node) { e->state.path_node = node; }
+void lowers_restored(Shard *e) { lowers_computed(e), e->state.force_root = true; }
+// a consumer has rebuilt its product: update_matrices (two), upload_qpi, ensure_tip_rate_products, the two uploads of U^-1 dQ U
+void matrices_rebuilt(Shard *e) { e->state.matrices_dirty = false, e->state.qp_kind = -1; }
+void q_images_rebuilt(Shard *e) { e->state.qimg_dirty = false, e->state.qp_kind = -1; }
+void qpi_rebuilt(Shard *e) { e->state.qpi_dirty = false; }
+void tip_rate_products_rebuilt(Shard *e, int kind) { e->state.qp_kind = kind; }
+void parameter_basis_rebuilt(Shard *e) { e->state.params_dirty = false; }
 
 // ---- what d_lower holds ----------------------------------------------------------------------------------------------------
 // Every 4-state post-order pass records the form it wrote (launch_lower_w, launch_lower_stream).  A reader other than the two
@@ -271,9 +333,7 @@ void prefer_reference_form(Shard *e) { e->reference_form_only = true; }
 int require_reference_form(Shard *e) {
 	prefer_reference_form(e);
 	if (e->lower_form == LowerForm::Reference) return PHYAMD_OK;
-	e->lower_valid = false;
-	e->all_dirty = true;
-	e->upper_valid = false;
+	lowers_discarded(e);
 	return run_lower(e, 1);
 }
 

@@ -252,9 +252,7 @@ int shard_set_tip_states(Shard *e, int tip, const uint8_t *states) {
 	HIP_TRY(hipStreamSynchronize(e->stream));
 	e->tip_set[tip] = 1;
 	e->tip_empty[tip] = 0;
-	e->tip_epoch++;
-	e->all_dirty = true;
-	e->stored.valid = false;
+	input_changed(e, Input::TipData);
 	return PHYAMD_OK;
 }
 
@@ -289,31 +287,23 @@ int shard_set_tip_partials(Shard *e, int tip, const double *partials) {
 			HIP_TRY(hipMemcpyAsync(e->d_tipsets, e->tipsets_host.data(), e->tipsets_host.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, e->stream));
 			e->tipsets_uploaded = e->tipsets_host.size();
 		}
-		HIP_TRY(hipMemcpyAsync(tip_row(e, tip), mask.data(), e->Ptot, hipMemcpyHostToDevice, e->stream));
-		HIP_TRY(hipStreamSynchronize(e->stream));
-		e->tip_set[tip] = 1;
-		e->tip_epoch++;
-		e->all_dirty = true;
-		e->stored.valid = false;
-		return PHYAMD_OK;
-	}
-	for (int k = 0; k < e->Ptot; k++) {
-		unsigned m = 0;
-		for (int s = 0; s < 4; s++) {
-			const double v = partials[(size_t)k * 4 + s];
-			if (v == 1.0) m |= 1u << s;
-			else if (v != 0.0)
-				return fail(PHYAMD_EUNSUPPORTED, "tip %d pattern %d: tip partials other than 0/1 ambiguity masks are not built in this revision", tip, k);
+	} else {
+		for (int k = 0; k < e->Ptot; k++) {
+			unsigned m = 0;
+			for (int s = 0; s < 4; s++) {
+				const double v = partials[(size_t)k * 4 + s];
+				if (v == 1.0) m |= 1u << s;
+				else if (v != 0.0)
+					return fail(PHYAMD_EUNSUPPORTED, "tip %d pattern %d: tip partials other than 0/1 ambiguity masks are not built in this revision", tip, k);
+			}
+			mask[k] = (uint8_t)m;
 		}
-		mask[k] = (uint8_t)m;
+		e->tip_empty[tip] = std::find(mask.begin(), mask.end(), (uint8_t)0) != mask.end();
 	}
 	HIP_TRY(hipMemcpyAsync(tip_row(e, tip), mask.data(), e->Ptot, hipMemcpyHostToDevice, e->stream));
 	HIP_TRY(hipStreamSynchronize(e->stream));
 	e->tip_set[tip] = 1;
-	e->tip_empty[tip] = std::find(mask.begin(), mask.end(), (uint8_t)0) != mask.end();
-	e->tip_epoch++;
-	e->all_dirty = true;
-	e->stored.valid = false;
+	input_changed(e, Input::TipData);
 	return PHYAMD_OK;
 }
 
@@ -325,8 +315,7 @@ int shard_set_pattern_weights(Shard *e, const double *weights) {
 	HIP_TRY(hipMemcpyAsync(e->tiles > 1 ? e->d_weights_all : e->d_weights, weights, sizeof(double) * e->Ptot, hipMemcpyHostToDevice, e->stream));
 	HIP_TRY(hipStreamSynchronize(e->stream));
 	e->have_weights = true;
-	e->all_dirty = true;
-	e->stored.valid = false;
+	input_changed(e, Input::PatternWeights);
 	return PHYAMD_OK;
 }
 
@@ -336,6 +325,7 @@ int shard_set_topology(Shard *e, const int32_t *left, const int32_t *right, int 
 	int rc;
 	if ((rc = bind_device(e))) return rc;
 	e->batch_mem.release_all();  // (sized by the old tree; the tile plan below counts what the engine itself holds)
+	lowers_discarded(e);         // (whichever way this call ends: the schedule is built anew, every partial belongs to the old tree)
 	std::vector<int32_t> old_l = e->left, old_r = e->right;
 	const int old_root = e->root;
 	e->left.assign(left, left + e->N);
@@ -350,9 +340,6 @@ int shard_set_topology(Shard *e, const int32_t *left, const int32_t *right, int 
 		e->right = old_r;
 		e->root = old_root;
 		if (had_topology && (build_schedule(e) != PHYAMD_OK || upload_schedule(e) != PHYAMD_OK)) e->have_topology = false;
-		e->all_dirty = true;
-		e->lower_valid = false;
-		e->upper_valid = false;
 		g_last_error = why;
 		return code;
 	};
@@ -399,12 +386,7 @@ int shard_set_topology(Shard *e, const int32_t *left, const int32_t *right, int 
 	if ((rc = upload_schedule(e))) return roll_back(rc);
 	if ((rc = ensure_lower_storage(e))) return roll_back(rc);
 	e->have_topology = true;
-	e->matrices_dirty = true;
-	e->upper_valid = false;
-	e->all_dirty = true;  // every partial belongs to the old tree
-	e->lower_valid = false;
-	e->schedule_epoch++;
-	e->stored.valid = false;  // topology is not part of phyamd_store
+	input_changed(e, Input::Topology);
 	return PHYAMD_OK;
 }
 
@@ -426,8 +408,7 @@ int shard_set_branch_lengths(Shard *e, const double *lengths) {
 	HIP_TRY(hipMemcpyAsync(e->d_lengths, e->h_lengths, sizeof(double) * e->N, hipMemcpyHostToDevice, e->stream));
 	HIP_TRY(hipEventRecord(e->ev_lengths, e->stream));
 	e->have_lengths = true;
-	e->matrices_dirty = true;
-	e->all_dirty = true;  // the whole vector: every node is recomputed (SingleTreeLikelihood_update_all_nodes)
+	input_changed(e, Input::BranchLengths);
 	return PHYAMD_OK;
 }
 
@@ -441,9 +422,7 @@ int shard_set_branch_length(Shard *e, int node, double length) {
 	e->lengths[node] = length;
 	HIP_TRY(hipMemcpyAsync(e->d_lengths + node, &e->lengths[node], sizeof(double), hipMemcpyHostToDevice, e->stream));
 	HIP_TRY(hipStreamSynchronize(e->stream));
-	e->matrices_dirty = true;  // all P(t) are re-formed (microseconds); only the partials above `node` are recomputed
-	e->changed.push_back(node);
-	e->upper_valid = false;
+	input_changed(e, Input::BranchLength, node);
 	return PHYAMD_OK;
 }
 
@@ -488,13 +467,13 @@ int shard_store(Shard *e) {
 	st.scaling_on = e->scaling_on;
 	st.core_index = e->core_index;
 	st.epoch = e->schedule_epoch;
-	st.valid = true;
+	state_stored(e);
 	return PHYAMD_OK;
 }
 
 int shard_restore(Shard *e) {
 	CHECK_ENGINE(e);
-	if (!e->stored.valid) return fail(PHYAMD_EINVAL, "nothing is stored (phyamd_store has not been called, or tree / data changed since)");
+	if (!e->state.stored_valid) return fail(PHYAMD_EINVAL, "nothing is stored (phyamd_store has not been called, or tree / data changed since)");
 	int rc;
 	if ((rc = bind_device(e))) return rc;
 	const Shard::Stored st = e->stored;  // the setters below write the engine's own copies
@@ -503,8 +482,6 @@ int shard_restore(Shard *e) {
 	if ((rc = shard_set_frequencies(e, st.freqs.data()))) return rc;
 	if ((rc = shard_set_category_rates(e, st.rates.data(), st.props.data()))) return rc;
 	if ((rc = shard_set_branch_lengths(e, st.lengths.data()))) return rc;
-	e->changed.clear();
-	e->upper_valid = false;
 	if (st.epoch == e->schedule_epoch && st.scaling_on == e->scaling_on && e->two_slots) {
 		// the stored partials are still in their slots: point the nodes back at them (treelikelihood.c:116-124) and
 		// re-integrate the root, whose per-pattern outputs belong to the discarded state
@@ -518,17 +495,14 @@ int shard_restore(Shard *e) {
 			refresh_op_cores(e);
 			if ((rc = upload_schedule(e))) return rc;
 		}
-		e->all_dirty = false;
-		e->lower_valid = true;
-		e->force_root = true;
+		lowers_restored(e);
 	}  // else: slots were reassigned since (schedule rebuilt, rescaling switched on): the restored parameters are recomputed in full
 	return PHYAMD_OK;
 }
 
 int shard_update_all_nodes(Shard *e) {
 	CHECK_ENGINE(e);
-	e->all_dirty = true;
-	e->matrices_dirty = true;
+	input_changed(e, Input::UpdateAllNodes);
 	return PHYAMD_OK;
 }
 
@@ -553,16 +527,12 @@ int shard_set_eigen(Shard *e, const double *eval, const double *evec, const doub
 		}
 	HIP_TRY(hipMemcpyAsync(e->d_Q, Q.data(), sizeof(double) * Q.size(), hipMemcpyHostToDevice, e->stream));
 	e->Q_host = Q;
-	e->qpi_dirty = true;
 	e->have_Q = true;
-	e->qimg_dirty = true;
 	std::fill(e->explicit_host.begin(), e->explicit_host.end(), 0);
 	HIP_TRY(hipMemsetAsync(e->d_explicit, 0, e->N, e->stream));
 	HIP_TRY(hipStreamSynchronize(e->stream));
 	e->have_eigen = true;
-	e->matrices_dirty = true;
-	e->params_dirty = true;
-	e->all_dirty = true;
+	input_changed(e, Input::Eigen);
 	return PHYAMD_OK;
 }
 
@@ -575,9 +545,7 @@ int shard_set_frequencies(Shard *e, const double *freqs) {
 	HIP_TRY(hipMemcpyAsync(e->d_freqs, e->freqs.data(), sizeof(double) * e->S, hipMemcpyHostToDevice, e->stream));
 	HIP_TRY(hipStreamSynchronize(e->stream));
 	e->have_freqs = true;
-	e->all_dirty = true;
-	e->qpi_dirty = true;
-	e->qimg_dirty = true;  // 20 / 60 / 61 states: the image of diag(pi) Q
+	input_changed(e, Input::Frequencies);
 	return PHYAMD_OK;
 }
 
@@ -592,8 +560,7 @@ int shard_set_category_rates(Shard *e, const double *rates, const double *propor
 	HIP_TRY(hipMemcpyAsync(e->d_props, e->props.data(), sizeof(double) * e->C, hipMemcpyHostToDevice, e->stream));
 	HIP_TRY(hipStreamSynchronize(e->stream));
 	e->have_rates = true;
-	e->matrices_dirty = true;
-	e->all_dirty = true;
+	input_changed(e, Input::CategoryRates);
 	return PHYAMD_OK;
 }
 
@@ -607,9 +574,7 @@ int shard_set_node_matrices(Shard *e, int node, const double *matrices) {
 	e->explicit_host[node] = 1;
 	HIP_TRY(hipMemcpyAsync(e->d_explicit + node, &e->explicit_host[node], 1, hipMemcpyHostToDevice, e->stream));
 	HIP_TRY(hipStreamSynchronize(e->stream));
-	e->matrices_dirty = true;  // the tip tables are built from d_mats
-	if (e->have_topology && node != e->root) e->changed.push_back(node);  // like a branch-length change of this one node
-	e->upper_valid = false;
+	input_changed(e, Input::NodeMatrices, e->have_topology && node != e->root ? node : -1);  // like a branch-length change of this one node
 	return PHYAMD_OK;
 }
 
@@ -623,9 +588,7 @@ int shard_set_matrices(Shard *e, const double *matrices) {
 	std::fill(e->explicit_host.begin(), e->explicit_host.end(), 1);
 	HIP_TRY(hipMemsetAsync(e->d_explicit, 1, e->N, e->stream));
 	HIP_TRY(hipStreamSynchronize(e->stream));
-	e->matrices_dirty = true;  // the tip tables / MFMA images are built from d_mats
-	e->all_dirty = true;
-	e->upper_valid = false;
+	input_changed(e, Input::Matrices);
 	return PHYAMD_OK;
 }
 
@@ -637,9 +600,8 @@ int shard_set_rate_matrix(Shard *e, const double *Q) {
 	HIP_TRY(hipMemcpyAsync(e->d_Q, Q, sizeof(double) * e->S * e->S, hipMemcpyHostToDevice, e->stream));
 	HIP_TRY(hipStreamSynchronize(e->stream));
 	e->Q_host.assign(Q, Q + (size_t)e->S * e->S);
-	e->qpi_dirty = true;
 	e->have_Q = true;
-	e->qimg_dirty = true;
+	input_changed(e, Input::RateMatrix);
 	return PHYAMD_OK;
 }
 
@@ -716,7 +678,7 @@ int shard_set_rate_matrix_derivatives(Shard *e, int count, const double *dQ) {
 	if (count > 0 && !dQ) return fail(PHYAMD_EINVAL, "null dQ");
 	e->np = count;
 	e->dQ_host.assign(dQ, dQ + (size_t)count * e->S * e->S);
-	e->params_dirty = true;
+	input_changed(e, Input::RateMatrixDerivatives);
 	return PHYAMD_OK;
 }
 
@@ -787,16 +749,16 @@ int shard_root_frequency_term(Shard *e, double *out) {
 	int rc;
 	if ((rc = bind_device(e))) return rc;
 	if ((rc = check_ready(e))) return rc;
+	if (e->tiles == 1 && (!lowers_current(e) || e->core_index[e->root] < 0 || !e->d_lower)) return fail(PHYAMD_EINVAL, "no evaluation has been run yet");
 	// (the root's array is p_root in every storage convention: only a rescaled evaluation's factors have to be the reference's)
 	if (e->scaling_on && (rc = require_reference_form(e))) return rc;
 	if (e->tiles > 1) {  // the per-tile terms were summed by the last phyamd_parameter_gradient
-		if (!e->tiled_root_term) return fail(PHYAMD_EINVAL, "with tiled patterns the root frequency term comes with phyamd_parameter_gradient: call that first");
+		if (!tiled_totals_current(e, true)) return fail(PHYAMD_EINVAL, "with tiled patterns the root frequency term comes with phyamd_parameter_gradient: call that first");
 		HIP_TRY(hipMemcpyAsync(e->h_result, e->d_result + 1 + (size_t)e->N * e->C + e->np, sizeof(double) * e->S, hipMemcpyDeviceToHost, e->stream));
 		HIP_TRY(hipStreamSynchronize(e->stream));
 		std::memcpy(out, e->h_result, sizeof(double) * e->S);
 		return PHYAMD_OK;
 	}
-	if (e->core_index.empty() || e->core_index[e->root] < 0 || !e->d_lower) return fail(PHYAMD_EINVAL, "no evaluation has been run yet");
 	if ((rc = launch_root_frequency_term(e, nullptr))) return rc;
 	HIP_TRY(hipMemcpyAsync(e->h_result, e->d_rf_part + (size_t)((e->P + 255) / 256) * e->S, sizeof(double) * e->S, hipMemcpyDeviceToHost, e->stream));
 	HIP_TRY(hipStreamSynchronize(e->stream));
@@ -888,7 +850,7 @@ static int rebuild_path_upper(Shard *e, int node) {
 		}
 		HIP_TRY(hipGetLastError());  // (the node's own partial: true_lower_gen, shard_branch_log_likelihood)
 	}
-	e->path_node = node;
+	path_upper_rebuilt(e, node);
 	return PHYAMD_OK;
 }
 
@@ -903,16 +865,15 @@ int shard_branch_log_likelihood(Shard *e, int node, double length, double *lnl, 
 	const size_t npd = node_partial_doubles(e);
 	// the two partials that meet on the branch: resident after a keep-partials gradient, else the upper one is rebuilt by a
 	// walk down the path from the root (pending changes are evaluated first; the result is kept until partials change)
-	const bool resident = e->keep_partials && e->upper_valid;
 	const double *up, *low;
 	int fold = 0;
-	if (resident) {
+	if (uppers_resident(e)) {
 		up = e->d_upper + (size_t)e->upper_slot[node] * npd;
 		low = node < e->T ? nullptr : e->d_lower + (size_t)e->core_index[node] * npd;
 		fold = e->upper_fold ? 1 : 0;
 	} else {
 		if ((rc = run_lower(e, true))) return rc;
-		if (e->path_node != node && (rc = rebuild_path_upper(e, node))) return rc;
+		if (e->state.path_node != node && (rc = rebuild_path_upper(e, node))) return rc;
 		up = e->d_path_upper;
 		low = node < e->T ? nullptr : (e->core_index[node] >= 0 ? e->d_lower + (size_t)e->core_index[node] * npd : e->d_path_lower);
 	}
@@ -980,11 +941,11 @@ int shard_root_invariant_term(Shard *e, double *out) {
 	if ((rc = check_ready(e))) return rc;
 	const double *src;
 	if (e->tiles > 1) {  // summed over the tiles by the last evaluation (one entry behind everything else in the total), each tile in its own form
-		if (!e->tiled_eval_done) return fail(PHYAMD_EINVAL, "no evaluation has been run yet");
+		if (!tiled_totals_current(e)) return fail(PHYAMD_EINVAL, "no evaluation has been run yet");
 		src = e->d_total + (size_t)e->N * e->C + 2 * PHYAMD_MAX_PARAMETERS;
 	} else {
+		if (!lowers_current(e) || e->core_index[e->root] < 0 || !e->d_lower) return fail(PHYAMD_EINVAL, "no evaluation has been run yet");
 		if (e->scaling_on && (rc = require_reference_form(e))) return rc;  // (see shard_root_frequency_term)
-		if (!e->lower_valid || e->force_root || e->core_index.empty() || e->core_index[e->root] < 0 || !e->d_lower) return fail(PHYAMD_EINVAL, "no evaluation has been run yet");
 		if ((rc = launch_root_invariant_term(e, nullptr))) return rc;
 		src = e->d_inv_part + (e->P + 255) / 256;
 	}
@@ -1021,7 +982,7 @@ int shard_get_partials(Shard *e, int node, int upper, double *out) {
 	if ((rc = require_reference_form(e))) return rc;  // (stored partials: the partials themselves, in the reference's form)
 	const size_t np = node_partial_doubles(e);
 	if (upper) {
-		if (!e->keep_partials || !e->upper_valid) return fail(PHYAMD_EINVAL, "upper partials need shard_set_keep_partials(1) before phyamd_gradient");
+		if (!uppers_resident(e)) return fail(PHYAMD_EINVAL, "upper partials need shard_set_keep_partials(1) before phyamd_gradient");
 		if (node == e->root) return fail(PHYAMD_EINVAL, "the root has no upper partial");
 	}
 	if (!upper && node < e->T) {  // rebuild the replicated tip partial from its mask / code
@@ -1086,10 +1047,7 @@ int shard_set_rescaling(Shard *e, int policy) {
 	const bool want = policy == PHYAMD_RESCALE_ALWAYS ? true : policy == PHYAMD_RESCALE_NEVER ? false : e->scaling_on;
 	if (want == e->scaling_on) return PHYAMD_OK;
 	e->scaling_on = want;
-	e->upper_valid = false;
-	e->all_dirty = true;
-	e->lower_valid = false;
-	e->path_node = -1;
+	lowers_discarded(e);
 	if (e->have_topology) {
 		int rc;
 		if ((rc = bind_device(e))) return rc;
@@ -1105,7 +1063,7 @@ int shard_set_keep_partials(Shard *e, int on) {
 	if (want == e->keep_partials) return PHYAMD_OK;
 	if (want) prefer_reference_form(e);  // (resident partials are the reference's)
 	e->keep_partials = want;
-	e->upper_valid = false;
+	lowers_discarded(e);
 	if (e->have_topology) {
 		int rc;
 		if ((rc = bind_device(e))) return rc;
