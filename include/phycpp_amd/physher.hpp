@@ -12,6 +12,7 @@
 #pragma once
 
 #include <cstddef>
+#include <cstdint>
 #include <map>
 #include <memory>
 #include <optional>
@@ -279,6 +280,17 @@ class TreeLikelihoodInterface : public CallableModelInterface {
 	// engine evaluates item by item (never batched); lnL is batched either way.
 	void LogLikelihoodBatch(size_t count, const double *treeParameters, double *logLikelihoods);
 	void GradientBatch(size_t count, const double *treeParameters, double *logLikelihoods, double *gradients);
+	// lnL / lnL and the branch gradient of `count` TREES on this object's alignment and models at once (one
+	// phyamd_gradient_batch_trees call): left, right [count][2T-1] and roots [count] are plain node-id arrays, tips 0..T-1 in this
+	// object's taxon order (the tree model's tip ids), internal ids T..2T-2 in any order, -1 / -1 for tips; branchLengths
+	// [count][2T-1] by the item's node ids (root entry ignored); logLikelihoods [count] (may be null in GradientTrees);
+	// branchGradients [count][2T-1] is d lnL / d length by the item's node ids (the root's entry 0), formed from the per-category
+	// gradient as Gradient() does.  Only branch lengths are differentiated: a time-tree model (node heights) or a request with
+	// BRANCH_MODEL, SITE_MODEL or substitution-model flags throws.  The tree model and this object's own state are unchanged.
+	void LogLikelihoodTrees(size_t count, const int32_t *left, const int32_t *right, const int32_t *roots, const double *branchLengths, double *logLikelihoods);
+	void GradientTrees(size_t count, const int32_t *left, const int32_t *right, const int32_t *roots, const double *branchLengths, double *logLikelihoods,
+	                   double *branchGradients);
+	size_t NodeCount() const;  // 2T - 1
 	size_t TreeParameterCount() const { return treeModel_->parameterCount_; }  // n of treeParameters [count][n]
 	size_t GetPatternCount() const;
 	const std::vector<double> &PatternWeights() const;
@@ -291,6 +303,9 @@ class TreeLikelihoodInterface : public CallableModelInterface {
 	void GradientEpilogue(double lnl, std::vector<double> &cat_grad, const std::vector<double> &branch_lengths, const std::vector<double> &subst_grad,
 	                      double *gradient);
 	void EvaluateBatch(size_t count, const double *treeParameters, double *logLikelihoods, double *gradients);
+	void BranchGradientFromCat(const double *cat_grad, double *g);
+	void EvaluateTrees(size_t count, const int32_t *left, const int32_t *right, const int32_t *roots, const double *branchLengths, double *logLikelihoods,
+	                   double *branchGradients);
 	TreeModelInterface *treeModel_;
 	SubstitutionModelInterface *substitutionModel_;
 	SiteModelInterface *siteModel_;

@@ -249,7 +249,29 @@ int phyamd_branch_hessian_diagonal_device(phyamd_engine *e, int flags, double *d
  * without the call.  Sharded handles run the batch on every shard's patterns and add the per-item results in shard order.
  * PHYAMD_EINVAL: count < 1, null pointers; PHYAMD_EUNSUPPORTED: explicit node matrices (they cannot follow per-item lengths). */
 int phyamd_gradient_batch(phyamd_engine *e, int flags, int32_t count, const double *branch_lengths, double *lnl, double *cat_gradient);
-/* of the last batch call: items that ran together / one by one, chunks the fast path was cut into, bytes of batch scratch the
+/* lnL and the per-category branch gradient of `count` trees on the engine's tip data, weights and models.
+ * left, right [count][2T-1] and roots [count]: each item in phyamd_set_topology's convention (tips 0..T-1 are the engine's
+ * tips, internal ids T..2T-2 in any order, any internal node may be the root); branch_lengths [count][2T-1] by the ITEM's node
+ * ids (root entry ignored); lnl [count]; cat_gradient [count][2T-1][C] by the item's node ids, the item's root row 0, or NULL
+ * for lnL only.  Item b equals what a fresh engine with the same data and models returns from phyamd_set_topology(item b),
+ * phyamd_set_branch_lengths(item b) and phyamd_gradient(flags) / phyamd_log_likelihood.  The engine itself -- its topology,
+ * lengths, partials -- is unchanged: later evaluations return the bits they would have returned without the call.  An item's
+ * result does not depend on `count`, its position, the other items or the chunks the batch ran in, bit for bit; an item whose
+ * arrays equal the engine's own returns the bits of phyamd_gradient_batch for the same lengths (same op builder, same kernel).
+ * There is NO item-by-item fallback (a loop over phyamd_set_topology rebuilds the schedule and discards the partials per item):
+ * PHYAMD_EUNSUPPORTED, naming the condition, unless 4 states, at most 8 categories, an engine that is not rescaling now
+ * (PHYAMD_RESCALE_ALWAYS, or PHYAMD_RESCALE_AUTO after its switch, is refused), untiled patterns (any number), no tip cell with
+ * an empty state mask, no explicit node matrices, flags 0 or PHYAMD_GRAD_FOLD_ROOT_FREQS, and scratch for at least one item
+ * within the memory cap (a batch that does not fit as a whole runs in chunks of items).  An item whose lnL is not finite
+ * reports it in-band with an all-NaN gradient, under PHYAMD_RESCALE_NEVER and _AUTO alike: the engine is never switched to
+ * rescaling.  Every item is validated on the host before anything is launched (tips -1 / -1; two distinct children in range;
+ * one parent per node; a parentless internal root; all nodes reached): PHYAMD_EINVAL with the item's index in the message; also
+ * for count < 1 or a null pointer other than cat_gradient.  Needs data, models, weights and a topology of the engine's own.
+ * Sharded handles run the batch on every shard's patterns and add the per-item results in shard order. */
+int phyamd_gradient_batch_trees(phyamd_engine *e, int flags, int32_t count, const int32_t *left, const int32_t *right,
+                                const int32_t *roots, const double *branch_lengths, double *lnl, double *cat_gradient);
+/* of the last batch call of either kind (a batch of trees: items_fast = count, items_sequential = 0): items that ran together /
+ * one by one, chunks the fast path was cut into, bytes of batch scratch the
  * engine holds (kept for the next call and counted in phyamd_profile.device_bytes, but released whenever an array of the engine
  * itself needs the room: under max_device_bytes the engine behaves as one that never made the call), wall time of the call */
 typedef struct { int32_t items_fast, items_sequential, chunks; int64_t scratch_bytes; double ms; } phyamd_batch_profile;

@@ -77,6 +77,7 @@ SYMBOLS = [
     ("phyamd_branch_hessian_diagonal", C.c_int, [_P, C.c_int, C.POINTER(C.c_double), _P, _P]),
     ("phyamd_branch_hessian_diagonal_device", C.c_int, [_P, C.c_int, _P]),
     ("phyamd_gradient_batch", C.c_int, [_P, C.c_int, C.c_int32, _P, _P, _P]),
+    ("phyamd_gradient_batch_trees", C.c_int, [_P, C.c_int, C.c_int32, _P, _P, _P, _P, _P, _P]),
     ("phyamd_get_batch_profile", C.c_int, [_P, C.POINTER(BatchProfile)]),
     ("phyamd_synchronize", C.c_int, [_P]),
     ("phyamd_get_pattern_log_likelihoods", C.c_int, [_P, _P]),

@@ -561,6 +561,7 @@ void TreeLikelihoodInterface::Init(bool use_tip_states) {
 TreeLikelihoodInterface::~TreeLikelihoodInterface() = default;
 
 size_t TreeLikelihoodInterface::GetPatternCount() const { return (size_t)impl_->patterns.pattern_count; }
+size_t TreeLikelihoodInterface::NodeCount() const { return (size_t)treeModel_->GetTree()->node_count; }
 const std::vector<double> &TreeLikelihoodInterface::PatternWeights() const { return impl_->patterns.weights; }
 const std::vector<unsigned char> &TreeLikelihoodInterface::PatternStates() const { return impl_->patterns.states; }
 
@@ -722,6 +723,21 @@ void TreeLikelihoodInterface::Gradient(double *gradient) {
 	GradientEpilogue(lnl, I.cat_grad, I.branch_lengths, subst_grad, gradient);
 }
 
+// gradient_branch_length_from_cat_inplace (treelikelihood.c:3129-3143): g[node] = sum_c cat_grad[node][c] w_c r_c for every node id
+void TreeLikelihoodInterface::BranchGradientFromCat(const double *cat_grad, double *g) {
+	phyamd::SiteModel &sm = *siteModel_->GetModel();
+	const int N = treeModel_->GetTree()->node_count, C = sm.cat_count;
+	const double mu_factor = (sm.has_mu && !referenceCompat_) ? sm.mu : 1.0;
+	for (int n = 0; n < N; n++) {
+		if (C == 1) g[n] = cat_grad[n] * mu_factor;
+		else {
+			double s = cat_grad[(size_t)n * C] * sm.cat_props[0] * sm.cat_rates[0];
+			for (int c = 1; c < C; c++) s += cat_grad[(size_t)n * C + c] * sm.cat_props[c] * sm.cat_rates[c];
+			g[n] = s * mu_factor;
+		}
+	}
+}
+
 // from lnL and the per-category branch gradient of one evaluation (cat_grad [node][category], branch_lengths as sent to the engine,
 // the tree model holding that evaluation's parameters) to the requested blocks, in the reference's order
 void TreeLikelihoodInterface::GradientEpilogue(double lnl, std::vector<double> &cat_grad, const std::vector<double> &branch_lengths,
@@ -753,14 +769,7 @@ void TreeLikelihoodInterface::GradientEpilogue(double lnl, std::vector<double> &
 	// missing factor mu is applied and the result is d lnL / d length.
 	std::vector<double> g(N, 0.0);
 	const double mu_factor = (sm.has_mu && !referenceCompat_) ? sm.mu : 1.0;
-	for (int n = 0; n < N; n++) {
-		if (C == 1) g[n] = cat_grad[n] * mu_factor;
-		else {
-			double s = cat_grad[(size_t)n * C] * sm.cat_props[0] * sm.cat_rates[0];
-			for (int c = 1; c < C; c++) s += cat_grad[(size_t)n * C + c] * sm.cat_props[c] * sm.cat_rates[c];
-			g[n] = s * mu_factor;
-		}
-	}
+	BranchGradientFromCat(cat_grad.data(), g.data());
 	size_t j = 0;
 	if (flags_ & (int)TreeLikelihoodGradientFlags::TREE_HEIGHT) {
 		if (!t.time_mode) {
@@ -861,4 +870,40 @@ void TreeLikelihoodInterface::LogLikelihoodBatch(size_t count, const double *tre
 void TreeLikelihoodInterface::GradientBatch(size_t count, const double *treeParameters, double *logLikelihoods, double *gradients) {
 	if (!gradients) throw Error("null gradients");
 	EvaluateBatch(count, treeParameters, logLikelihoods, gradients);
+}
+
+// lnL (LogLikelihoodTrees) or lnL and the branch gradient (GradientTrees) of `count` trees: ONE phyamd_gradient_batch_trees call,
+// then the branch epilogue per item over the item's node ids
+void TreeLikelihoodInterface::EvaluateTrees(size_t count, const int32_t *left, const int32_t *right, const int32_t *roots, const double *branchLengths,
+                                            double *logLikelihoods, double *branchGradients) {
+	if (count == 0) return;
+	if (!left || !right || !roots || !branchLengths) throw Error("null left, right, roots or branchLengths");
+	if (count > (size_t)INT32_MAX) throw Error("a batch takes at most 2^31 - 1 items");
+	const phyamd::Tree &t = *treeModel_->GetTree();
+	if (branchGradients && (t.time_mode || (flags_ & ((int)TreeLikelihoodGradientFlags::SITE_MODEL | (int)TreeLikelihoodGradientFlags::BRANCH_MODEL)) || substRates_ || substFreqs_))
+		throw Error("GradientTrees takes branch-length requests (TREE_HEIGHT of an unrooted tree model): node heights, clock, site-model and substitution-model "
+		            "gradients belong to the tree model's own topology or need per-item root terms");
+	Sync();
+	auto &I = *impl_;
+	const size_t N = (size_t)t.node_count, C = (size_t)siteModel_->GetModel()->cat_count;
+	// (the reference's folded arithmetic; its rescaled form, COMPAT_SCALED, only differs on a rescaling engine, which the call refuses)
+	const int eflags = branchGradients && referenceCompat_ ? PHYAMD_GRAD_FOLD_ROOT_FREQS : 0;
+	std::vector<double> lnl(count), cat_grad(branchGradients ? count * N * C : 0);
+	phyamd::check(phyamd_gradient_batch_trees(I.engine, eflags, (int32_t)count, left, right, roots, branchLengths, lnl.data(), branchGradients ? cat_grad.data() : nullptr));
+	for (size_t b = 0; b < count; b++) {
+		if (logLikelihoods) logLikelihoods[b] = lnl[b];
+		if (branchGradients) BranchGradientFromCat(cat_grad.data() + b * N * C, branchGradients + b * N);
+	}
+}
+
+void TreeLikelihoodInterface::LogLikelihoodTrees(size_t count, const int32_t *left, const int32_t *right, const int32_t *roots, const double *branchLengths,
+                                                 double *logLikelihoods) {
+	if (!logLikelihoods) throw Error("null logLikelihoods");
+	EvaluateTrees(count, left, right, roots, branchLengths, logLikelihoods, nullptr);
+}
+
+void TreeLikelihoodInterface::GradientTrees(size_t count, const int32_t *left, const int32_t *right, const int32_t *roots, const double *branchLengths,
+                                            double *logLikelihoods, double *branchGradients) {
+	if (!branchGradients) throw Error("null branchGradients");
+	EvaluateTrees(count, left, right, roots, branchLengths, logLikelihoods, branchGradients);
 }

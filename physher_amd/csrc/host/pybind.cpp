@@ -11,6 +11,18 @@ namespace py = pybind11;
 using darray = py::array_t<double, py::array::c_style | py::array::forcecast>;
 
 static darray vec(const std::vector<double> &v) { return darray(v.size(), v.data()); }
+using iarray = py::array_t<int32_t, py::array::c_style | py::array::forcecast>;
+
+// shapes of a batch of trees: left, right, lengths [count][2T-1], roots [count]; returns count
+static size_t check_trees(const TreeLikelihoodInterface &tlk, const iarray &left, const iarray &right, const iarray &roots, const darray &lengths) {
+	const py::ssize_t N = (py::ssize_t)tlk.NodeCount();
+	if (left.ndim() != 2 || left.shape(1) != N) throw phyamd::Error("left: [count][node_count]");
+	const py::ssize_t count = left.shape(0);
+	if (right.ndim() != 2 || right.shape(0) != count || right.shape(1) != N) throw phyamd::Error("right: [count][node_count]");
+	if (roots.ndim() != 1 || roots.shape(0) != count) throw phyamd::Error("roots: [count]");
+	if (lengths.ndim() != 2 || lengths.shape(0) != count || lengths.shape(1) != N) throw phyamd::Error("branch lengths: [count][node_count]");
+	return (size_t)count;
+}
 
 PYBIND11_MODULE(_phycpp_amd, m) {
 	m.doc() = "phycpp-compatible host classes over the MI355X tree-likelihood engine";
@@ -207,6 +219,18 @@ PYBIND11_MODULE(_phycpp_amd, m) {
 		    std::vector<double> lnl(count), g(count * self.gradientLength_);
 		    self.GradientBatch(count, params.data(), lnl.data(), g.data());
 		    return py::make_tuple(vec(lnl), darray({(py::ssize_t)count, (py::ssize_t)self.gradientLength_}, g.data()));
+	    })
+	    .def("log_likelihood_trees", [](TreeLikelihoodInterface &self, iarray left, iarray right, iarray roots, darray lengths) {
+		    const size_t count = check_trees(self, left, right, roots, lengths);
+		    std::vector<double> lnl(count);
+		    self.LogLikelihoodTrees(count, left.data(), right.data(), roots.data(), lengths.data(), lnl.data());
+		    return vec(lnl);
+	    })
+	    .def("gradient_trees", [](TreeLikelihoodInterface &self, iarray left, iarray right, iarray roots, darray lengths) {
+		    const size_t count = check_trees(self, left, right, roots, lengths), N = self.NodeCount();
+		    std::vector<double> lnl(count), g(count * N);
+		    self.GradientTrees(count, left.data(), right.data(), roots.data(), lengths.data(), lnl.data(), g.data());
+		    return py::make_tuple(vec(lnl), darray({(py::ssize_t)count, (py::ssize_t)N}, g.data()));
 	    })
 	    .def("get_pattern_count", &TreeLikelihoodInterface::GetPatternCount)
 	    .def("pattern_weights", [](TreeLikelihoodInterface &self) { return vec(self.PatternWeights()); })

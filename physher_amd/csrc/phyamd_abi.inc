@@ -487,6 +487,28 @@ int phyamd_gradient_batch(phyamd_engine *g, int flags, int32_t count, const doub
 	return PHYAMD_OK;
 }
 
+// every shard runs the whole batch of trees on its patterns; per-item results are added like phyamd_gradient_batch's
+int phyamd_gradient_batch_trees(phyamd_engine *g, int flags, int32_t count, const int32_t *left, const int32_t *right, const int32_t *roots,
+                                const double *branch_lengths, double *lnl, double *cat_gradient) {
+	if (count < 1) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch_trees: count must be >= 1 (got %d)", count);
+	if (!left || !right || !roots || !branch_lengths || !lnl) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch_trees: null left, right, roots, branch_lengths or lnl");
+	CHECK_GROUP(g);
+	if (group_size(g) == 1) return shard_gradient_batch_trees(g->shards[0], flags, count, left, right, roots, branch_lengths, lnl, cat_gradient);
+	const size_t ncat = (size_t)g->N * g->C, n = (size_t)count * (cat_gradient ? 1 + ncat : 1);
+	ensure_scratch(g, n);
+	int rc;
+	if ((rc = for_shards(g, [&](Shard *s, int i) {
+		     double *v = g->scratch[i].data();  // [lnl[count] | cat_gradient[count][N C]]
+		     return shard_gradient_batch_trees(s, flags, count, left, right, roots, branch_lengths, v, cat_gradient ? v + count : nullptr);
+	     })))
+		return rc;
+	std::vector<double> total(n);
+	sum_shards(g, n, total.data());
+	std::memcpy(lnl, total.data(), sizeof(double) * count);
+	if (cat_gradient) std::memcpy(cat_gradient, total.data() + count, sizeof(double) * count * ncat);
+	return PHYAMD_OK;
+}
+
 int phyamd_get_batch_profile(phyamd_engine *g, phyamd_batch_profile *out) {
 	CHECK_GROUP(g);
 	if (!out) return fail(PHYAMD_EINVAL, "null out");

@@ -1,15 +1,17 @@
-// phyamd_batch4.inc: 4-state kernels of phyamd_gradient_batch -- lnL and the branch gradient for many branch-length vectors on one
-// tree and one alignment in a single launch -- included by phyamd_engine.hip inside its anonymous namespace.
+// phyamd_batch4.inc: 4-state kernels of phyamd_gradient_batch and phyamd_gradient_batch_trees -- lnL and the branch gradient for
+// many branch-length vectors on one tree, or for many trees, and one alignment in a single launch -- included by phyamd_engine.hip
+// inside its anonymous namespace.
 //
 // The single-evaluation walks are built to fill the card with ONE evaluation.  A batch of B small ones (69 taxa x 238 patterns x 4
 // categories is 16 waves each) fills it along the item axis instead: workgroup (block, item) = the category waves of 64 patterns of
-// one item.  A wave walks the whole tree twice from two host-built op lists that every item shares (built once per topology,
-// build_batch_ops): post-order, storing every internal node's partial p_n in the item's scratch (one 32-byte access per lane);
+// one item.  A wave walks the whole tree twice from two host-built op lists (build_batch_ops) -- shared by every item of a batch of
+// lengths (built once per topology), the item's own in a batch of trees (BatchArgs::item_stride) --: post-order, storing every
+// internal node's partial p_n in the item's scratch (one 32-byte access per lane);
 // after ONE meeting of the categories in LDS for the site likelihood, pre-order with the branch terms.  Matrices are wave-uniform
 // and come through scalar loads from the item's block; tip messages are P . mask from the 4-bit tip codes, the same bytes for
 // every item.  No floating-point atomics: a branch term is summed over the 64 lanes by wave_sum (fixed order), written to the
 // slab [item][block][C][node], and k_batch_finish adds the blocks in block order.  An item's arithmetic therefore depends on
-// nothing but its own lengths: not on the batch size, its position in the batch, or the chunk it ran in.
+// nothing but its own lengths and op lists: not on the batch size, its position in the batch, or the chunk it ran in.
 
 // post-order: node = (P_left p_left) o (P_right p_right); carry 1 / 2: the left / right child's partial is the previous op's result
 // pre-order: the op of `node` forms its children's uppers.  src: where u_node is (BATCH_ROOT: node is the root; BATCH_CARRY: the
@@ -34,7 +36,8 @@ __device__ __forceinline__ BatchOp load_batch_op(const BatchOp *ops, int i) {
 }
 
 struct BatchArgs {
-	const BatchOp *lower_ops, *upper_ops;  // T - 1 ops each
+	const BatchOp *lower_ops, *upper_ops;  // T - 1 ops each; item b's lists are at + b * item_stride
+	int item_stride;                       // in ops: 0 (every item walks the same lists) or 2 (T - 1) (a batch of trees)
 	int T, N, P, C, nblk, upper_slots;
 	int grad;                              // 0: the post-order pass and lnL only
 	const uint8_t *tipmask;                // [T][P]
@@ -47,16 +50,17 @@ struct BatchArgs {
 };
 
 // P(t) of every (item, node, category) from the eigen system: k_transition_matrices' arithmetic, each item with its own lengths
-// ([items][N]; the root's entry is skipped, nothing reads its matrix)
+// ([items][N]; the root's entry is skipped, nothing reads its matrix).  roots: [items], each item's own root (a batch of trees),
+// or null: `root` is every item's
 __global__ void k_batch_matrices(int C, int N, int items, const double *__restrict__ model, const double *__restrict__ rates,
-                                 const double *__restrict__ lengths, int root, double *__restrict__ mats) {
+                                 const double *__restrict__ lengths, int root, const int32_t *__restrict__ roots, double *__restrict__ mats) {
 	const size_t total = (size_t)items * N * C * 16;
 	const double *eval = model, *evec = model + 4, *ivec = model + 4 + 16;
 	for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
 		const int j = idx & 3, i = (idx >> 2) & 3;
 		const int c = (idx >> 4) % C;
 		const size_t in = idx / ((size_t)16 * C);  // item * N + node
-		if ((int)(in % N) == root) continue;
+		if ((int)(in % N) == (roots ? roots[in / N] : root)) continue;
 		const double t = lengths[in] * rates[c];
 		double p = 0.;
 		for (int k = 0; k < 4; k++) p += ivec[k * 4 + j] * evec[i * 4 + k] * exp(eval[k] * t);
@@ -80,6 +84,9 @@ __global__ __launch_bounds__(BATCH_MAX_CATEGORIES *WAVE) void k_batch_walk4(cons
 	__shared__ double sh[BATCH_MAX_CATEGORIES * WAVE];
 	const int lane = threadIdx.x, c = __builtin_amdgcn_readfirstlane(threadIdx.y);  // this wave's category
 	const int blk = blockIdx.x, item = blockIdx.y;
+	// the item's op lists: a wave-uniform offset (the workgroup id times a launch argument) on a kernel argument, so the lists stay
+	// at scalar addresses
+	const BatchOp *lower_ops = a.lower_ops + (size_t)item * a.item_stride, *upper_ops = a.upper_ops + (size_t)item * a.item_stride;
 	const int k0 = blk * WAVE + lane;  // the scratch is padded to whole blocks: every lane owns its cells
 	const bool valid = k0 < a.P;
 	const int k = valid ? k0 : a.P - 1;
@@ -95,7 +102,7 @@ __global__ __launch_bounds__(BATCH_MAX_CATEGORIES *WAVE) void k_batch_walk4(cons
 		d4 p = d4{0., 0., 0., 0.};
 #pragma unroll 1
 		for (int i = 0; i < nops; i++) {
-			const BatchOp op = load_batch_op(a.lower_ops, i);
+			const BatchOp op = load_batch_op(lower_ops, i);
 			const d4 l = op.carry == 1 ? matvec4(opaque(mats_c + (size_t)op.left * a.C * 16), p) : batch_message(a, mats_c, lower_c, node_stride, op.left, k);
 			const d4 r = op.carry == 2 ? matvec4(opaque(mats_c + (size_t)op.right * a.C * 16), p) : batch_message(a, mats_c, lower_c, node_stride, op.right, k);
 			p = mul4(l, r);
@@ -126,7 +133,7 @@ __global__ __launch_bounds__(BATCH_MAX_CATEGORIES *WAVE) void k_batch_walk4(cons
 		d4 carried = one;
 #pragma unroll 1
 		for (int i = 0; i < nops; i++) {
-			const BatchOp op = load_batch_op(a.upper_ops, i);
+			const BatchOp op = load_batch_op(upper_ops, i);
 			const d4 bl = batch_message(a, mats_c, lower_c, node_stride, op.left, k);
 			const d4 br = batch_message(a, mats_c, lower_c, node_stride, op.right, k);
 			d4 up = FOLD ? pi : one;
@@ -151,9 +158,10 @@ __global__ __launch_bounds__(BATCH_MAX_CATEGORIES *WAVE) void k_batch_walk4(cons
 }
 
 // out[item][0] = lnL, out[item][1 + node * C + c] = g[node][c] (the root's row 0): the blocks' entries added in block order.
-// rows = 1 (lnL only) or 1 + N C; thread r of an item reads the slab's entry r - 1 of every block ([C][N]: coalesced)
-__global__ __launch_bounds__(256) void k_batch_finish(int items, int N, int C, int nblk, int root, int rows, const double *__restrict__ lnl_part,
-                                                     const double *__restrict__ slab, double *__restrict__ out) {
+// rows = 1 (lnL only) or 1 + N C; thread r of an item reads the slab's entry r - 1 of every block ([C][N]: coalesced).  roots:
+// as k_batch_matrices'
+__global__ __launch_bounds__(256) void k_batch_finish(int items, int N, int C, int nblk, int root, const int32_t *__restrict__ roots, int rows,
+                                                     const double *__restrict__ lnl_part, const double *__restrict__ slab, double *__restrict__ out) {
 	const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
 	if (idx >= (size_t)items * rows) return;
 	const size_t item = idx / rows;
@@ -165,7 +173,7 @@ __global__ __launch_bounds__(256) void k_batch_finish(int items, int N, int C, i
 		return;
 	}
 	const int c = (r - 1) / N, node = (r - 1) % N;
-	if (node != root)
+	if (node != (roots ? roots[item] : root))
 		for (int b = 0; b < nblk; b++) s += slab[((item * nblk + b) * C + c) * N + node];
 	out[item * rows + 1 + (size_t)node * C + c] = s;
 }

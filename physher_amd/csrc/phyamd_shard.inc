@@ -220,21 +220,29 @@ struct Shard {
 	hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
 	phyamd_profile prof{};
 
-	// phyamd_gradient_batch (phyamd_batch4.inc): op lists of the tree they were built for, and the scratch of batch_items items --
-	// per-item lengths, matrices and results; lowers, parked uppers and slabs
+	// phyamd_gradient_batch, phyamd_gradient_batch_trees (phyamd_batch4.inc): op lists of the tree they were built for, and the
+	// scratch of batch_items items -- per-item lengths, matrices and results; lowers, parked uppers and slabs; for a batch of trees
+	// the items' own op lists and roots
 	std::vector<uint8_t> tip_empty;      // tip -> some cell of its data has an empty state mask (0/1 tip partials that are all 0)
 	int batch_max_patterns = 0;          // the fast path's pattern bound (BATCH_MAX_PATTERNS; PHYAMD_BATCH_MAX_PATTERNS: the crossover sweep)
+	bool batch_trace = false;            // PHYAMD_BATCH_TRACE: a batch of trees reports each chunk's host times on stderr (profiles/tree_batch_timing.py)
 	std::vector<int32_t> batch_left, batch_right;
 	int batch_root = -1, batch_upper_slots = 0;
-	std::vector<BatchOp> batch_ops;      // [post-order T - 1 | pre-order T - 1]
+	std::vector<BatchOp> batch_ops;      // [post-order T - 1 | pre-order T - 1] of the engine's tree
 	DeviceArray<BatchOp> d_batch_ops{&mem};
 	// the scratch is a spare group of the shard's budget (DeviceBudget::spare): counted in device_bytes while held, released
 	// whenever an array of the engine itself needs the room, with the pattern storage and on a new topology
 	DeviceBudget batch_mem{&mem};
 	DeviceArray<double> d_batch_len{&batch_mem}, d_batch_mats{&batch_mem}, d_batch_out{&batch_mem};
 	DeviceArray<double> d_batch_lower{&batch_mem}, d_batch_upper{&batch_mem}, d_batch_slab{&batch_mem}, d_batch_lnl{&batch_mem};
-	int batch_items = 0;                 // items the scratch holds
+	DeviceArray<BatchOp> d_batch_item_ops{&batch_mem};  // [item][post-order T - 1 | pre-order T - 1]
+	DeviceArray<int32_t> d_batch_roots{&batch_mem};     // [item]
+	// what the scratch holds: every batch call says what it needs (BatchShape) and gets at least that, so a call of one kind
+	// never runs in the scratch of the other with too few upper slots or without op lists
+	int batch_items = 0;                 // items
 	bool batch_grad = false;             // ... with the pre-order pass's part
+	int batch_slots = 0;                 // ... of so many upper slots each
+	bool batch_trees = false;            // ... with their own op lists and roots
 	phyamd_batch_profile batch_prof{};
 };
 
@@ -382,9 +390,24 @@ PassKernel upper_kernel(const Shard *e, int flags, bool with_params, bool made) 
 	return PassKernel::Walk;
 }
 
-// ---- which path a batch of branch-length vectors takes (phyamd_gradient_batch) ----------------------------------------------
-// The batched walk (k_batch_walk4) is an optimisation of "evaluate the items one by one": it runs exactly when every condition
-// below holds, and every other engine evaluates the items through the ordinary path.  fit: items whose scratch fits the budget.
+// ---- which path a batch takes (phyamd_gradient_batch, phyamd_gradient_batch_trees) -------------------------------------------
+// The batched walk (k_batch_walk4) runs exactly when no condition of batch_walk_refusal holds.  For a batch of branch-length
+// vectors it is an optimisation of "evaluate the items one by one": every other engine evaluates the items through the ordinary
+// path (batch_fast_path).  A batch of trees has no such path to fall back to -- a loop over phyamd_set_topology rebuilds the
+// schedule and discards the engine's partials per item -- and is refused with the condition's name (tree_batch_refusal).
+// fit: items whose scratch fits the budget.
+
+// the condition that keeps the batched walk off this engine, or null
+const char *batch_walk_refusal(const Shard *e, int flags) {
+	if (e->generic) return "the batched walk is built for 4 states";
+	if (e->C > BATCH_MAX_CATEGORIES) return "the batched walk takes at most 8 categories (one LDS row per category)";
+	if (e->scaling_on) return "the engine is rescaling and the batched walk does not rescale";
+	if (e->tiles > 1) return "the patterns are tiled and the batched walk needs the tip data of all patterns resident";
+	if (std::any_of(e->tip_empty.begin(), e->tip_empty.end(), [](uint8_t x) { return x != 0; })) return "a tip cell has an empty state mask";
+	if (flags & ~PHYAMD_GRAD_FOLD_ROOT_FREQS) return "the batched walk takes flags 0 or PHYAMD_GRAD_FOLD_ROOT_FREQS";
+	return nullptr;
+}
+
 // Above BATCH_MAX_PATTERNS patterns the loop over the single-evaluation walks wins: one evaluation fills the card by itself there,
 // and those walks store half the partials (measured, profiles/batch_sweep.json, DESIGN.md "A batch of branch-length vectors": at
 // 8 192 patterns the batched call is 2.1-3.6x faster at 64 taxa and between 1.2x faster and 1.3x slower at 500; at 32 768 the loop
@@ -392,11 +415,17 @@ PassKernel upper_kernel(const Shard *e, int flags, bool with_params, bool made) 
 // 8 192 is a compromise, not a clean crossover: the point moves with the tree size and the batch size (profiles/batch_sweep.json).
 constexpr int BATCH_MAX_PATTERNS = 8192;
 bool batch_fast_path(const Shard *e, int flags, size_t fit) {
-	if (e->generic || e->C > BATCH_MAX_CATEGORIES) return false;  // 4 states, one LDS row per category
-	if (e->scaling_on) return false;                               // the walk does not rescale (RESCALE_AUTO: a non-finite item is redone)
-	if (e->tiles > 1) return false;                                // the tip data of all patterns are resident
+	if (batch_walk_refusal(e, flags)) return false;  // (RESCALE_AUTO: a non-finite item is redone through the ordinary path)
 	if (e->P > e->batch_max_patterns) return false;
-	if (std::any_of(e->tip_empty.begin(), e->tip_empty.end(), [](uint8_t x) { return x != 0; })) return false;
-	if (flags & ~PHYAMD_GRAD_FOLD_ROOT_FREQS) return false;
 	return fit >= 1;
+}
+
+// a batch of trees: the walk's own conditions (no pattern bound: that one is a crossover against a loop that does not exist
+// here), no explicit node matrices -- they belong to node ids of the engine's tree and cannot follow per-item lengths -- and
+// scratch for at least one item.  RESCALE_AUTO: an item whose lnL is not finite is reported in-band; the engine is never switched
+const char *tree_batch_refusal(const Shard *e, int flags, size_t fit) {
+	if (const char *why = batch_walk_refusal(e, flags)) return why;
+	if (std::any_of(e->explicit_host.begin(), e->explicit_host.end(), [](uint8_t x) { return x != 0; })) return "a node has explicit matrices, which cannot follow per-item trees and lengths";
+	if (fit < 1) return "the scratch of one item does not fit the memory budget";
+	return nullptr;
 }

@@ -190,6 +190,7 @@ int shard_create(const phyamd_config *cfg, Shard **out) {
 	e->mem.spare = &e->batch_mem;
 	e->batch_max_patterns = BATCH_MAX_PATTERNS;
 	if (const char *env = std::getenv("PHYAMD_BATCH_MAX_PATTERNS")) e->batch_max_patterns = std::atoi(env);
+	if (const char *env = std::getenv("PHYAMD_BATCH_TRACE")) e->batch_trace = std::atoi(env) != 0;
 	e->explicit_host.assign(e->N, 0);
 	const size_t msz = (size_t)e->N * e->C * e->S * e->S;
 	if (e->generic && ((rc = e->d_tipsets.ensure(256)) || (rc = e->d_imgs.ensure(((size_t)e->N * e->C + 2) * gen_image_doubles(e))))) return bail(rc);
@@ -1090,38 +1091,37 @@ int shard_get_profile(Shard *e, phyamd_profile *out) {
 
 // ---- a batch of branch-length vectors (phyamd_gradient_batch) ----------------------------------------------------------------
 
-// the two op lists of the batched walk for the engine's tree.  Post-order: depth first, the larger subtree first, so that the child
-// finished last hands its partial on in registers.  Pre-order: of two internal children the smaller subtree is entered first with
-// its upper in registers and the other's upper is parked in a slot that is free again once its op has read it: at most
-// log2(T) + 1 slots, whatever the shape (a caterpillar parks nothing).
-void build_batch_ops(Shard *e) {
-	const int T = e->T, N = e->N;
-	e->batch_left = e->left;
-	e->batch_right = e->right;
-	e->batch_root = e->root;
-	e->batch_ops.clear();
+// the two op lists of the batched walk for a tree (T tips; left / right / root in phyamd_set_topology's convention, already
+// validated), appended to `ops` as [post-order T - 1 | pre-order T - 1]; returns the upper slots the pre-order list parks in.
+// ops == null: only counts the slots.  Post-order: depth first, the larger subtree first, so that the child finished last hands
+// its partial on in registers.  Pre-order: of two internal children the smaller subtree is entered first with its upper in
+// registers and the other's upper is parked in a slot that is free again once its op has read it: at most log2(T) + 1 slots,
+// whatever the shape (a caterpillar parks nothing).  Ties go by left / right, never by node id: the lists of one tree under two
+// labellings of its internal nodes differ in the ids only.
+int build_batch_ops(int T, const int32_t *left, const int32_t *right, int root, std::vector<BatchOp> *ops) {
+	const int N = 2 * T - 1;
 	std::vector<int> size(N, 1), order;
 	{
-		std::vector<int> stack{e->root};
+		std::vector<int> stack{root};
 		while (!stack.empty()) {
 			const int n = stack.back();
 			stack.pop_back();
 			order.push_back(n);
 			if (n >= T) {
-				stack.push_back(e->left[n]);
-				stack.push_back(e->right[n]);
+				stack.push_back(left[n]);
+				stack.push_back(right[n]);
 			}
 		}
 		for (size_t i = order.size(); i-- > 0;)
-			if (order[i] >= T) size[order[i]] += size[e->left[order[i]]] + size[e->right[order[i]]];
+			if (order[i] >= T) size[order[i]] += size[left[order[i]]] + size[right[order[i]]];
 	}
-	{  // post-order: (node, children done?) on an explicit stack
-		std::vector<std::pair<int, bool>> stack{{e->root, false}};
+	if (ops) {  // post-order: (node, children done?) on an explicit stack
+		std::vector<std::pair<int, bool>> stack{{root, false}};
 		int last = -1;
 		while (!stack.empty()) {
 			const auto [n, done] = stack.back();
 			stack.pop_back();
-			const int l = e->left[n], r = e->right[n];
+			const int l = left[n], r = right[n];
 			if (!done) {
 				stack.push_back({n, true});
 				const int first = size[l] >= size[r] ? l : r, second = first == l ? r : l;
@@ -1130,18 +1130,18 @@ void build_batch_ops(Shard *e) {
 				continue;
 			}
 			BatchOp op{n, l, r, last == l && l >= T ? 1 : last == r && r >= T ? 2 : 0, BATCH_NONE, BATCH_NONE, BATCH_NONE, 0};
-			e->batch_ops.push_back(op);
+			ops->push_back(op);
 			last = n;
 		}
 	}
+	int slots = 0;
 	{  // pre-order
-		std::vector<std::pair<int, int>> stack{{e->root, BATCH_ROOT}};  // (node, where its upper is)
+		std::vector<std::pair<int, int>> stack{{root, BATCH_ROOT}};  // (node, where its upper is)
 		std::vector<int> free_slots;
-		int slots = 0;
 		while (!stack.empty()) {
 			const auto [n, src] = stack.back();
 			stack.pop_back();
-			const int l = e->left[n], r = e->right[n];
+			const int l = left[n], r = right[n];
 			BatchOp op{n, l, r, 0, src, BATCH_NONE, BATCH_NONE, 0};
 			if (l >= T && r >= T) {
 				int slot;
@@ -1162,19 +1162,44 @@ void build_batch_ops(Shard *e) {
 				op.dst_right = BATCH_CARRY;
 				stack.push_back({r, BATCH_CARRY});
 			}
-			e->batch_ops.push_back(op);
+			if (ops) ops->push_back(op);
 			if (src >= 0) free_slots.push_back(src);  // read by this op: later ops may park in it
 		}
-		e->batch_upper_slots = std::max(1, slots);
 	}
+	return std::max(1, slots);
 }
 
-// bytes of batch scratch one item takes (grad: with the pre-order pass's uppers and slab)
-size_t batch_item_bytes(const Shard *e, bool grad) {
+// the engine's own lists (a batch of branch-length vectors), built once per topology
+int ensure_engine_batch_ops(Shard *e) {
+	if (e->batch_left == e->left && e->batch_right == e->right && e->batch_root == e->root && !e->batch_ops.empty() && e->d_batch_ops.get()) return PHYAMD_OK;
+	e->batch_left = e->left;
+	e->batch_right = e->right;
+	e->batch_root = e->root;
+	e->batch_ops.clear();
+	e->batch_upper_slots = build_batch_ops(e->T, e->left.data(), e->right.data(), e->root, &e->batch_ops);
+	int rc;
+	if ((rc = e->d_batch_ops.ensure(e->batch_ops.size()))) {
+		e->batch_ops.clear();
+		return rc;
+	}
+	HIP_TRY(hipMemcpyAsync(e->d_batch_ops, e->batch_ops.data(), sizeof(BatchOp) * e->batch_ops.size(), hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	return PHYAMD_OK;
+}
+
+// what a batch call needs of the scratch per item: the pre-order pass's part, so many upper slots, its own op lists and root
+struct BatchShape {
+	bool grad;
+	int slots;
+	bool trees;
+};
+
+// bytes of batch scratch one item takes
+size_t batch_item_bytes(const Shard *e, BatchShape w) {
 	const size_t nblk = ((size_t)e->P + WAVE - 1) / WAVE, plane = nblk * WAVE * 4;
-	size_t doubles = (size_t)e->N + (size_t)e->N * e->C * 16 + 1 + (grad ? (size_t)e->N * e->C : 0) + (size_t)(e->T - 1) * e->C * plane + nblk;
-	if (grad) doubles += (size_t)e->batch_upper_slots * e->C * plane + nblk * e->C * e->N;
-	return sizeof(double) * doubles;
+	size_t doubles = (size_t)e->N + (size_t)e->N * e->C * 16 + 1 + (w.grad ? (size_t)e->N * e->C : 0) + (size_t)(e->T - 1) * e->C * plane + nblk;
+	if (w.grad) doubles += (size_t)w.slots * e->C * plane + nblk * e->C * e->N;
+	return sizeof(double) * doubles + (w.trees ? sizeof(BatchOp) * 2 * (size_t)(e->T - 1) + sizeof(int32_t) : 0);
 }
 
 size_t batch_scratch_bytes(const Shard *e) { return (size_t)e->batch_mem.bytes; }
@@ -1184,17 +1209,20 @@ void release_batch_scratch(Shard *e) {
 	e->batch_items = 0;
 }
 
-// items the scratch holds now (none once the group has been released to make room)
-size_t batch_items_held(const Shard *e, bool grad) { return e->d_batch_lower.get() && (e->batch_grad || !grad) ? (size_t)e->batch_items : 0; }
+// items of shape w the scratch holds now (none once the group has been released to make room)
+size_t batch_items_held(const Shard *e, BatchShape w) {
+	const bool serves = e->d_batch_lower.get() && (e->batch_grad || !w.grad) && (!w.grad || e->batch_slots >= w.slots) && (e->batch_trees || !w.trees);
+	return serves ? (size_t)e->batch_items : 0;
+}
 
 constexpr int BATCH_MAX_CHUNK = 65535;  // gridDim.y
 
-// items of a (count, grad) batch whose scratch fits beside the engine: within the cap less everything the engine holds or may
-// still allocate -- what is resident whatever the tile size, the tile's working set as choose_tiles reserves it, the walks'
+// items of a batch (count items of shape w) whose scratch fits beside the engine: within the cap less everything the engine holds
+// or may still allocate -- what is resident whatever the tile size, the tile's working set as choose_tiles reserves it, the walks'
 // on-demand buffers -- or, without a cap, within most of what the device has free right now.  What the scratch holds already is
 // kept unless more items would fit.
-size_t batch_items_that_fit(const Shard *e, size_t count, bool grad) {
-	const size_t want = std::min<size_t>(count, BATCH_MAX_CHUNK), have = batch_items_held(e, grad);
+size_t batch_items_that_fit(const Shard *e, size_t count, BatchShape w) {
+	const size_t want = std::min<size_t>(count, BATCH_MAX_CHUNK), have = batch_items_held(e, w);
 	if (have >= want) return want;
 	const double held = (double)batch_scratch_bytes(e);
 	double room;
@@ -1205,40 +1233,57 @@ size_t batch_items_that_fit(const Shard *e, size_t count, bool grad) {
 		size_t free_bytes = 0, total_bytes = 0;
 		room = hipMemGetInfo(&free_bytes, &total_bytes) == hipSuccess ? 0.8 * ((double)free_bytes + held) : 0.0;
 	}
-	const double fit = std::floor(room / (double)batch_item_bytes(e, grad));
+	const double fit = std::floor(room / (double)batch_item_bytes(e, w));
 	if (fit <= (double)have) return have;
 	return (size_t)std::min((double)want, fit);
 }
 
-int ensure_batch_scratch(Shard *e, size_t items, bool grad) {
-	if (batch_items_held(e, grad) >= items) return PHYAMD_OK;
+int allocate_batch_scratch(Shard *e, size_t items, BatchShape w) {
 	release_batch_scratch(e);  // (the arrays grow together: all are freed before any is allocated again)
-	const size_t nblk = ((size_t)e->P + WAVE - 1) / WAVE, plane = nblk * WAVE * 4, rows = grad ? (size_t)1 + e->N * e->C : 1;
+	const size_t nblk = ((size_t)e->P + WAVE - 1) / WAVE, plane = nblk * WAVE * 4, rows = w.grad ? (size_t)1 + e->N * e->C : 1;
 	int rc;
 	if ((rc = e->d_batch_len.ensure(items * e->N)) || (rc = e->d_batch_mats.ensure(items * e->N * e->C * 16)) || (rc = e->d_batch_out.ensure(items * rows)) ||
 	    (rc = e->d_batch_lower.ensure(items * (e->T - 1) * e->C * plane)) || (rc = e->d_batch_lnl.ensure(items * nblk)) ||
-	    (grad && ((rc = e->d_batch_upper.ensure(items * e->batch_upper_slots * e->C * plane)) || (rc = e->d_batch_slab.ensure(items * nblk * e->C * e->N))))) {
+	    (w.grad && ((rc = e->d_batch_upper.ensure(items * w.slots * e->C * plane)) || (rc = e->d_batch_slab.ensure(items * nblk * e->C * e->N)))) ||
+	    (w.trees && ((rc = e->d_batch_item_ops.ensure(items * 2 * (e->T - 1))) || (rc = e->d_batch_roots.ensure(items))))) {
 		release_batch_scratch(e);
 		return rc;
 	}
 	e->batch_items = (int)items;
-	e->batch_grad = grad;
+	e->batch_grad = w.grad;
+	e->batch_slots = w.grad ? w.slots : 0;
+	e->batch_trees = w.trees;
 	return PHYAMD_OK;
 }
 
-// one chunk of `items` items through the batched walk: lengths [items][N] (host) -> out [items][rows] (host), rows = 1 or 1 + N C
-int run_batch_chunk(Shard *e, int flags, int items, const double *lengths, bool grad, double *out) {
-	const int nblk = (e->P + WAVE - 1) / WAVE, rows = grad ? 1 + e->N * e->C : 1;
+int ensure_batch_scratch(Shard *e, size_t items, BatchShape w) {
+	if (batch_items_held(e, w) >= items) return PHYAMD_OK;
+	if (e->cfg.max_device_bytes <= 0 && e->d_batch_lower.get()) {
+		// without a cap the scratch keeps what the previous call needed as well: calls of the two kinds, or of trees that park in
+		// fewer and in more slots, may alternate without an allocation each (under a cap every call gets exactly its own)
+		const BatchShape both{w.grad || e->batch_grad, std::max(w.slots, e->batch_slots), w.trees || e->batch_trees};
+		if (allocate_batch_scratch(e, items, both) == PHYAMD_OK) return PHYAMD_OK;
+	}
+	return allocate_batch_scratch(e, items, w);
+}
+
+// one chunk of `items` items through the batched walk: lengths [items][N] (host) -> out [items][rows] (host), rows = 1 or 1 + N C.
+// w.trees: the items walk their own op lists from their own roots, already in d_batch_item_ops and d_batch_roots; else the
+// engine's.  w.slots: the upper slots an item of this chunk has in d_batch_upper (at least what its list parks in)
+int run_batch_chunk(Shard *e, int flags, int items, const double *lengths, BatchShape w, double *out) {
+	const int nblk = (e->P + WAVE - 1) / WAVE, rows = w.grad ? 1 + e->N * e->C : 1, nops = e->T - 1;
+	const BatchOp *ops = w.trees ? e->d_batch_item_ops.get() : e->d_batch_ops.get();
+	const int32_t *roots = w.trees ? e->d_batch_roots.get() : nullptr;
 	HIP_TRY(hipMemcpyAsync(e->d_batch_len, lengths, sizeof(double) * (size_t)items * e->N, hipMemcpyHostToDevice, e->stream));
 	const size_t total = (size_t)items * e->N * e->C * 16;
 	hipLaunchKernelGGL(k_batch_matrices, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, e->stream, e->C, e->N, items, e->d_model, e->d_rates,
-	                   e->d_batch_len, e->root, e->d_batch_mats);
-	const BatchArgs a{e->d_batch_ops, e->d_batch_ops + (e->T - 1), e->T, e->N, e->P, e->C, nblk, e->batch_upper_slots, grad ? 1 : 0, e->d_tipmask, e->d_freqs, e->d_props,
+	                   e->d_batch_len, e->root, roots, e->d_batch_mats);
+	const BatchArgs a{ops, ops + nops, w.trees ? 2 * nops : 0, e->T, e->N, e->P, e->C, nblk, w.slots, w.grad ? 1 : 0, e->d_tipmask, e->d_freqs, e->d_props,
 	                  e->d_weights, e->d_Q, e->d_batch_mats, e->d_batch_lower, e->d_batch_upper, e->d_batch_lnl, e->d_batch_slab};
 	const dim3 grid(nblk, items), block(WAVE, e->C);
 	if (flags & PHYAMD_GRAD_FOLD_ROOT_FREQS) hipLaunchKernelGGL(k_batch_walk4<true>, grid, block, 0, e->stream, a);
 	else hipLaunchKernelGGL(k_batch_walk4<false>, grid, block, 0, e->stream, a);
-	hipLaunchKernelGGL(k_batch_finish, dim3((unsigned)(((size_t)items * rows + 255) / 256)), dim3(256), 0, e->stream, items, e->N, e->C, nblk, e->root, rows,
+	hipLaunchKernelGGL(k_batch_finish, dim3((unsigned)(((size_t)items * rows + 255) / 256)), dim3(256), 0, e->stream, items, e->N, e->C, nblk, e->root, roots, rows,
 	                   e->d_batch_lnl, e->d_batch_slab, e->d_batch_out);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpyAsync(out, e->d_batch_out, sizeof(double) * (size_t)items * rows, hipMemcpyDeviceToHost, e->stream));
@@ -1270,24 +1315,19 @@ int run_batch(Shard *e, int flags, int32_t count, const double *branch_lengths, 
 	const bool grad = cat_gradient != nullptr;
 	const size_t N = (size_t)e->N, ncat = N * e->C, rows = grad ? 1 + ncat : 1;
 	std::vector<uint8_t> redo(count, 1);  // items the sequential path (still) has to evaluate
-	if (e->batch_left != e->left || e->batch_right != e->right || e->batch_root != e->root || e->batch_ops.empty()) {
-		build_batch_ops(e);
-		release_batch_scratch(e);  // (sized by the tree's upper slots)
-		if ((rc = e->d_batch_ops.ensure(e->batch_ops.size()))) return rc;
-		HIP_TRY(hipMemcpyAsync(e->d_batch_ops, e->batch_ops.data(), sizeof(BatchOp) * e->batch_ops.size(), hipMemcpyHostToDevice, e->stream));
-		HIP_TRY(hipStreamSynchronize(e->stream));
-	}
+	if ((rc = ensure_engine_batch_ops(e))) return rc;
+	const BatchShape shape{grad, e->batch_upper_slots, false};
 	std::vector<double> lengths, out;
 	for (size_t first = 0; first < (size_t)count && batch_fast_path(e, flags, 1);) {
 		// (every chunk asks again: an item that went through the ordinary path may have taken the scratch's room)
-		const size_t chunk = batch_items_that_fit(e, (size_t)count - first, grad);
+		const size_t chunk = batch_items_that_fit(e, (size_t)count - first, shape);
 		if (!batch_fast_path(e, flags, chunk)) break;
-		if ((rc = ensure_batch_scratch(e, chunk, grad))) return rc;
+		if ((rc = ensure_batch_scratch(e, chunk, shape))) return rc;
 		const size_t items = std::min(chunk, (size_t)count - first);
 		lengths.assign(branch_lengths + first * N, branch_lengths + (first + items) * N);
 		out.resize(items * rows);
 		for (size_t b = 0; b < items; b++) lengths[b * N + e->root] = 0.0;  // (ignored, as phyamd_set_branch_lengths does)
-		if ((rc = run_batch_chunk(e, flags, (int)items, lengths.data(), grad, out.data()))) return rc;
+		if ((rc = run_batch_chunk(e, flags, (int)items, lengths.data(), shape, out.data()))) return rc;
 		prof.chunks++;
 		for (size_t b = 0; b < items; b++) {
 			const double l = out[b * rows];
@@ -1335,6 +1375,127 @@ int shard_gradient_batch(Shard *e, int flags, int32_t count, const double *branc
 		} else
 			e->have_lengths = false;
 	}
+	prof.scratch_bytes = (int64_t)batch_scratch_bytes(e);
+	prof.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	e->batch_prof = prof;
+	return rc;
+}
+
+// ---- a batch of trees (phyamd_gradient_batch_trees) ---------------------------------------------------------------------------
+
+// item `item` of a batch of trees is one binary tree over all 2T - 1 nodes in phyamd_set_topology's convention (build_schedule's
+// checks, on the item's arrays)
+int validate_batch_tree(int T, const int32_t *left, const int32_t *right, int root, int item, std::vector<int> &parents, std::vector<int> &stack) {
+	const int N = 2 * T - 1;
+	parents.assign(N, 0);
+	for (int n = 0; n < N; n++) {
+		const int l = left[n], r = right[n];
+		if (n < T) {
+			if (l != -1 || r != -1) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch_trees: item %d: node %d is a tip (id < tip_count) but has children", item, n);
+			continue;
+		}
+		if (l < 0 || r < 0 || l >= N || r >= N || l == r)
+			return fail(PHYAMD_EINVAL, "phyamd_gradient_batch_trees: item %d: internal node %d has invalid children (%d, %d)", item, n, l, r);
+		if (++parents[l] > 1 || ++parents[r] > 1) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch_trees: item %d: node %d or %d has two parents", item, l, r);
+	}
+	if (root < T || root >= N || parents[root] != 0) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch_trees: item %d: root %d is not a parentless internal node", item, root);
+	// (no node has two parents and the root has none: the walk from the root meets no node twice)
+	int reached = 0;
+	stack.assign(1, root);
+	while (!stack.empty()) {
+		const int n = stack.back();
+		stack.pop_back();
+		reached++;
+		if (n >= T) {
+			stack.push_back(left[n]);
+			stack.push_back(right[n]);
+		}
+	}
+	if (reached != N) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch_trees: item %d: the topology is not a single binary tree over all %d nodes", item, N);
+	return PHYAMD_OK;
+}
+
+// the items of a batch of trees through the batched walk, in chunks of what the scratch holds.  Per chunk: the items' op lists are
+// built and uploaded with their roots, the upper slots are those of the chunk's deepest-parking item, three launches
+int run_tree_batch(Shard *e, int flags, int32_t count, const int32_t *left, const int32_t *right, const int32_t *roots, const double *branch_lengths, double *lnl,
+                   double *cat_gradient, phyamd_batch_profile &prof) {
+	int rc;
+	{  // ready but for the lengths, which the call brings itself
+		const bool had = e->have_lengths;
+		e->have_lengths = true;
+		rc = check_ready(e);
+		e->have_lengths = had;
+		if (rc) return rc;
+	}
+	const bool grad = cat_gradient != nullptr;
+	if (const char *why = tree_batch_refusal(e, flags, 1)) return fail(PHYAMD_EUNSUPPORTED, "phyamd_gradient_batch_trees: %s", why);
+	if (grad && !e->have_Q) return fail(PHYAMD_EINVAL, "the gradient needs the rate matrix: phyamd_set_eigen or phyamd_set_rate_matrix");
+	const int T = e->T;
+	const size_t N = (size_t)e->N, ncat = N * e->C, rows = grad ? 1 + ncat : 1, nops = 2 * (size_t)(T - 1);
+	std::vector<int> slots(count);  // per item: the upper slots its pre-order list parks in
+	{
+		std::vector<int> parents, stack;
+		for (int32_t b = 0; b < count; b++) {  // every item, before anything is launched
+			const int32_t *l = left + (size_t)b * N, *r = right + (size_t)b * N;
+			if ((rc = validate_batch_tree(T, l, r, roots[b], b, parents, stack))) return rc;
+			slots[b] = grad ? build_batch_ops(T, l, r, roots[b], nullptr) : 1;
+		}
+	}
+	std::vector<double> lengths, out;
+	std::vector<BatchOp> ops;
+	for (size_t first = 0; first < (size_t)count;) {
+		// the chunk and its slot count settle each other: fewer items never need more slots
+		size_t items = std::min<size_t>((size_t)count - first, BATCH_MAX_CHUNK);
+		BatchShape shape{grad, 1, true};
+		for (;;) {
+			shape.slots = *std::max_element(slots.begin() + first, slots.begin() + first + items);
+			const size_t fit = batch_items_that_fit(e, items, shape);
+			if (const char *why = tree_batch_refusal(e, flags, fit)) return fail(PHYAMD_EUNSUPPORTED, "phyamd_gradient_batch_trees: %s", why);
+			if (fit >= items) break;
+			items = fit;
+		}
+		if ((rc = ensure_batch_scratch(e, items, shape))) return rc;
+		const auto t0 = std::chrono::steady_clock::now();
+		ops.clear();
+		for (size_t b = first; b < first + items; b++) build_batch_ops(T, left + b * N, right + b * N, roots[b], &ops);
+		const auto t1 = std::chrono::steady_clock::now();
+		HIP_TRY(hipMemcpyAsync(e->d_batch_item_ops, ops.data(), sizeof(BatchOp) * items * nops, hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_batch_roots, roots + first, sizeof(int32_t) * items, hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipStreamSynchronize(e->stream));  // (ops is reused by the next chunk)
+		const auto t2 = std::chrono::steady_clock::now();
+		lengths.assign(branch_lengths + first * N, branch_lengths + (first + items) * N);
+		out.resize(items * rows);
+		for (size_t b = 0; b < items; b++) lengths[b * N + roots[first + b]] = 0.0;  // (ignored, as phyamd_set_branch_lengths does)
+		if ((rc = run_batch_chunk(e, flags, (int)items, lengths.data(), shape, out.data()))) return rc;
+		if (e->batch_trace) {
+			const auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+			std::fprintf(stderr, "phyamd_gradient_batch_trees: chunk %d items %zu slots %d build_ms %.6f upload_ms %.6f\n", prof.chunks, items, shape.slots, ms(t0, t1),
+			             ms(t1, t2));
+		}
+		prof.chunks++;
+		for (size_t b = 0; b < items; b++) {
+			const double l = out[b * rows];
+			const bool bad = std::isnan(l) || std::isinf(l);  // in-band, whatever the rescaling mode: the engine is never switched
+			lnl[first + b] = l;
+			for (size_t i = 0; grad && i < ncat; i++) cat_gradient[(first + b) * ncat + i] = bad ? NAN : out[b * rows + 1 + i];  // treelikelihood.c:327-332
+			prof.items_fast++;
+		}
+		first += items;
+	}
+	return PHYAMD_OK;
+}
+
+// reads the engine's inputs and writes only the batch scratch: nothing in Shard::state changes
+int shard_gradient_batch_trees(Shard *e, int flags, int32_t count, const int32_t *left, const int32_t *right, const int32_t *roots, const double *branch_lengths,
+                               double *lnl, double *cat_gradient) {
+	CHECK_ENGINE(e);
+	if (count < 1) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch_trees: count must be >= 1 (got %d)", count);
+	if (!left || !right || !roots || !branch_lengths || !lnl) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch_trees: null left, right, roots, branch_lengths or lnl");
+	const auto t0 = std::chrono::steady_clock::now();
+	int rc;
+	if ((rc = bind_device(e))) return rc;
+	phyamd_batch_profile prof{};
+	rc = run_tree_batch(e, flags, count, left, right, roots, branch_lengths, lnl, cat_gradient, prof);
 	prof.scratch_bytes = (int64_t)batch_scratch_bytes(e);
 	prof.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 	e->batch_prof = prof;

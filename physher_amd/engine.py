@@ -215,8 +215,28 @@ class Engine:
         self._check(self._lib.phyamd_gradient_batch(self._h, flags, count, _ptr(bl), _ptr(lnl), None if g is None else _ptr(g)))
         return lnl, g
 
+    def gradient_batch_trees(self, left, right, roots, branch_lengths, flags=0, want_gradient=True):
+        """lnL and the per-category branch gradient of B trees on this engine's data and models at once: left, right [B, N] and
+        roots [B] in set_topology's convention per item, branch_lengths [B, N] by the item's node ids -> (lnl [B], g [B, N, C] by
+        the item's node ids, or None).  Item b is what a fresh engine returns from set_topology + set_branch_lengths +
+        gradient(flags); this engine's own tree, lengths and partials stay.  No item-by-item fallback: EngineError otherwise."""
+        l = np.ascontiguousarray(left, dtype=np.int32)
+        r = np.ascontiguousarray(right, dtype=np.int32)
+        ro = np.ascontiguousarray(roots, dtype=np.int32)
+        bl = _f64(branch_lengths)
+        if l.ndim != 2 or l.shape[1] != self.N or l.shape[0] < 1:
+            raise ValueError(f"left: [B >= 1, {self.N}], got {l.shape}")
+        count = l.shape[0]
+        if r.shape != l.shape or bl.shape != l.shape or ro.shape != (count,):
+            raise ValueError(f"right, branch_lengths: {l.shape} and roots: ({count},), got {r.shape}, {bl.shape}, {ro.shape}")
+        lnl = np.empty(count)
+        g = np.empty((count, self.N, self.C)) if want_gradient else None
+        self._check(self._lib.phyamd_gradient_batch_trees(self._h, flags, count, _ptr(l), _ptr(r), _ptr(ro), _ptr(bl), _ptr(lnl),
+                                                          None if g is None else _ptr(g)))
+        return lnl, g
+
     def batch_profile(self):
-        """Of the last gradient_batch: items_fast / items_sequential, chunks, scratch_bytes, ms."""
+        """Of the last gradient_batch / gradient_batch_trees: items_fast / items_sequential, chunks, scratch_bytes, ms."""
         p = _lib.BatchProfile()
         self._check(self._lib.phyamd_get_batch_profile(self._h, C.byref(p)))
         return {k: getattr(p, k) for k, _ in p._fields_}
