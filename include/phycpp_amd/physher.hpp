@@ -290,6 +290,13 @@ class TreeLikelihoodInterface : public CallableModelInterface {
 	void LogLikelihoodTrees(size_t count, const int32_t *left, const int32_t *right, const int32_t *roots, const double *branchLengths, double *logLikelihoods);
 	void GradientTrees(size_t count, const int32_t *left, const int32_t *right, const int32_t *roots, const double *branchLengths, double *logLikelihoods,
 	                   double *branchGradients);
+	// lnL and its first two derivatives in the central branch for every NNI neighbour of the tree model's tree at once (one
+	// phyamd_nni_log_likelihoods call; see include/physher_amd.h for the candidates and the three arrangements): logLikelihoods,
+	// d1, d2 [3][2T-1] by the tree's node ids, NaN at tips and the root; centralLengths [3][2T-1] trial lengths of the central
+	// branch, or null for the branch's own.  Lengths and derivatives are in the engine's branch lengths (what a single
+	// evaluation hands it: the tree model's lengths, with a clock rate or mu folded in).  d1 and d2 may be null.  The tree model
+	// and this object's own state are unchanged.
+	void NNILogLikelihoods(const double *centralLengths, double *logLikelihoods, double *d1, double *d2);
 	size_t NodeCount() const;  // 2T - 1
 	size_t TreeParameterCount() const { return treeModel_->parameterCount_; }  // n of treeParameters [count][n]
 	size_t GetPatternCount() const;

@@ -276,6 +276,38 @@ int phyamd_gradient_batch_trees(phyamd_engine *e, int flags, int32_t count, cons
  * itself needs the room: under max_device_bytes the engine behaves as one that never made the call), wall time of the call */
 typedef struct { int32_t items_fast, items_sequential, chunks; int64_t scratch_bytes; double ms; } phyamd_batch_profile;
 int phyamd_get_batch_profile(phyamd_engine *e, phyamd_batch_profile *out);   /* of the last batch call */
+/* lnL, and its first and second derivative in the central branch, of every NNI neighbour of the engine's tree: ONE post-order
+ * and ONE pre-order walk of the engine's tree, then every edge's three arrangements in one launch -- O(T) work for the whole
+ * neighbourhood, where phyamd_gradient_batch_trees walks each of the 2 (T - 2) neighbours from the tips.
+ * A CANDIDATE is every internal node v other than the root; u its parent, s its sibling, a = left[v], b = right[v].  Every
+ * subtree keeps its own branch length; the length of v is central_lengths[k][v], or the engine's t_v when central_lengths is
+ * NULL.  Row k of lnl, d1, d2 ([3][2T-1] each) at column v:
+ *   k = 0  the engine's tree
+ *   k = 1  a and s exchanged: v gets children (s, b), u gets a where s was
+ *   k = 2  b and s exchanged: v gets children (a, s), u gets b where s was
+ * lnl[k][v] is the rearranged tree's log-likelihood: the lnl of the phyamd_gradient_batch_trees item whose arrays are the engine's
+ * with the two child slots exchanged and branch_lengths[v] set to the trial length.  d1[k][v], d2[k][v] are its first and second
+ * derivative in the length of v, by phyamd_branch_hessian_diagonal's definitions (d1 = that item's sum_c g[v][c] w_c r_c).
+ * Columns of tips and of the root are NaN in all three outputs: no such rearrangement exists (two tips: everything is NaN).
+ * Entries of central_lengths at those columns are ignored.  d1 and d2 may be NULL (both NULL: their work is skipped; the lnl
+ * bits are the same).  When u is the root, k = 1 and k = 2 are, for a reversible model, the same unrooted topology with the
+ * lengths of a, b and s redistributed; they are computed like every other entry.  The unrooted NNI ACROSS the root edge (a child
+ * of one root child exchanged with a child of the other) is not among the candidates: a caller re-roots the tree to reach it.
+ * The engine -- its topology, lengths, partials -- is unchanged: later evaluations return the bits they would have returned
+ * without the call, two calls return identical bits, and the result does not depend on what the batch scratch held before.
+ * An entry whose lnL is not finite reports it in band with NaN d1 and d2, under PHYAMD_RESCALE_NEVER and _AUTO alike: the engine
+ * is never switched to rescaling.  There is no fallback path: PHYAMD_EUNSUPPORTED, naming the condition, under
+ * phyamd_gradient_batch_trees' conditions (not 4 states, more than 8 categories, an engine that is rescaling now, tiled patterns, a
+ * tip cell with an empty state mask, explicit node matrices, scratch -- every internal node's lower and upper partial, held in
+ * the batch scratch and released like it -- that does not fit the memory cap) and for flags other than 0.  PHYAMD_EINVAL: null
+ * engine or lnl, no eigen system, a negative or non-finite trial length of a candidate.  Sharded handles run on every shard's
+ * patterns and add the three arrays in shard order. */
+int phyamd_nni_log_likelihoods(phyamd_engine *e, int flags, const double *central_lengths /* [3][2T-1] or NULL */,
+                               double *lnl /* [3][2T-1] */, double *d1 /* [3][2T-1] or NULL */, double *d2 /* [3][2T-1] or NULL */);
+/* of the last phyamd_nni_log_likelihoods: candidate edges scored (T - 2), bytes of batch scratch the engine holds (see
+ * phyamd_batch_profile), wall time of the call */
+typedef struct { int32_t candidates; int64_t scratch_bytes; double ms; } phyamd_nni_profile;
+int phyamd_get_nni_profile(phyamd_engine *e, phyamd_nni_profile *out);
 int phyamd_synchronize(phyamd_engine *e);
 
 /* --- inspection (parity tests, debugging) --- */

@@ -907,3 +907,9 @@ void TreeLikelihoodInterface::GradientTrees(size_t count, const int32_t *left, c
 	if (!branchGradients) throw Error("null branchGradients");
 	EvaluateTrees(count, left, right, roots, branchLengths, logLikelihoods, branchGradients);
 }
+
+void TreeLikelihoodInterface::NNILogLikelihoods(const double *centralLengths, double *logLikelihoods, double *d1, double *d2) {
+	if (!logLikelihoods) throw Error("null logLikelihoods");
+	Sync();
+	phyamd::check(phyamd_nni_log_likelihoods(impl_->engine, 0, centralLengths, logLikelihoods, d1, d2));
+}

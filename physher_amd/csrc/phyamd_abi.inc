@@ -526,6 +526,42 @@ int phyamd_get_batch_profile(phyamd_engine *g, phyamd_batch_profile *out) {
 	return PHYAMD_OK;
 }
 
+// every shard scores the whole neighbourhood on its patterns; lnl, d1 and d2 are sums over patterns, added in shard order
+int phyamd_nni_log_likelihoods(phyamd_engine *g, int flags, const double *central_lengths, double *lnl, double *d1, double *d2) {
+	if (!lnl) return fail(PHYAMD_EINVAL, "phyamd_nni_log_likelihoods: null lnl");
+	CHECK_GROUP(g);
+	const size_t entries = (size_t)3 * g->N, n = 3 * entries;  // [lnl | d1 | d2], each [3][2T-1]
+	const bool deriv = d1 || d2;
+	std::vector<double> total(n);
+	int rc;
+	if (group_size(g) == 1) {
+		if ((rc = shard_nni_log_likelihoods(g->shards[0], flags, central_lengths, deriv, total.data()))) return rc;
+	} else {
+		ensure_scratch(g, n);
+		if ((rc = for_shards(g, [&](Shard *s, int i) { return shard_nni_log_likelihoods(s, flags, central_lengths, deriv, g->scratch[i].data()); }))) return rc;
+		sum_shards(g, n, total.data());
+		nni_mask_derivatives(entries, total.data());
+	}
+	std::memcpy(lnl, total.data(), sizeof(double) * entries);
+	if (d1) std::memcpy(d1, total.data() + entries, sizeof(double) * entries);
+	if (d2) std::memcpy(d2, total.data() + 2 * entries, sizeof(double) * entries);
+	return PHYAMD_OK;
+}
+
+int phyamd_get_nni_profile(phyamd_engine *g, phyamd_nni_profile *out) {
+	CHECK_GROUP(g);
+	if (!out) return fail(PHYAMD_EINVAL, "null out");
+	int rc;
+	if ((rc = shard_get_nni_profile(g->shards[0], out))) return rc;
+	for (int i = 1; i < group_size(g); i++) {  // the slowest shard is what the caller waits for; memory adds up
+		phyamd_nni_profile p;
+		if ((rc = shard_get_nni_profile(g->shards[i], &p))) return rc;
+		out->scratch_bytes += p.scratch_bytes;
+		out->ms = std::max(out->ms, p.ms);
+	}
+	return PHYAMD_OK;
+}
+
 // device-resident results (one process per GPU: the caller reduces them across processes with ONE RCCL all-reduce)
 int phyamd_log_likelihood_device(phyamd_engine *g, double *device_out) {
 	CHECK_GROUP(g);

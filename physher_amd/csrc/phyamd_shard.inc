@@ -243,7 +243,18 @@ struct Shard {
 	bool batch_grad = false;             // ... with the pre-order pass's part
 	int batch_slots = 0;                 // ... of so many upper slots each
 	bool batch_trees = false;            // ... with their own op lists and roots
+	bool batch_nni = false;              // ... with the arrays of phyamd_nni_log_likelihoods below
 	phyamd_batch_profile batch_prof{};
+	// phyamd_nni_log_likelihoods (phyamd_nni4.inc) walks ONE item of the scratch above with every upper parked (slots = T - 1) and
+	// adds to the group: the engine's tree's op lists in that form, the candidate edges and each node's candidate index, the trial
+	// lengths and matrices, the slab and the result
+	DeviceArray<BatchOp> d_nni_ops{&batch_mem};    // [post-order T - 1 | pre-order T - 1, every internal child's upper parked at child - T]
+	DeviceArray<NniCand> d_nni_cands{&batch_mem};  // [T - 2]
+	DeviceArray<int32_t> d_nni_cand_of{&batch_mem};  // [N]: node -> index in d_nni_cands, -1: a tip or the root
+	DeviceArray<double> d_nni_len{&batch_mem}, d_nni_mats{&batch_mem};  // [3][N], [3][N][C][16]
+	DeviceArray<double> d_nni_slab{&batch_mem}, d_nni_out{&batch_mem};  // [T - 2][blocks][9], [3 terms][3][N]
+	bool nni_lists_valid = false;        // d_nni_ops, d_nni_cands and d_nni_cand_of hold the engine's tree's (while they are allocated)
+	phyamd_nni_profile nni_prof{};
 };
 
 // ---- what each input invalidates -------------------------------------------------------------------------------------------

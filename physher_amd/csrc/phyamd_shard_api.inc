@@ -1098,7 +1098,9 @@ int shard_get_profile(Shard *e, phyamd_profile *out) {
 // registers and the other's upper is parked in a slot that is free again once its op has read it: at most log2(T) + 1 slots,
 // whatever the shape (a caterpillar parks nothing).  Ties go by left / right, never by node id: the lists of one tree under two
 // labellings of its internal nodes differ in the ids only.
-int build_batch_ops(int T, const int32_t *left, const int32_t *right, int root, std::vector<BatchOp> *ops) {
+// park_all (phyamd_nni_log_likelihoods): every internal child's upper is parked in a slot of its own, slot = node - T, and none
+// is handed on in registers: T - 1 slots, and after the walk every internal non-root node's upper is in the scratch.
+int build_batch_ops(int T, const int32_t *left, const int32_t *right, int root, std::vector<BatchOp> *ops, bool park_all = false) {
 	const int N = 2 * T - 1;
 	std::vector<int> size(N, 1), order;
 	{
@@ -1143,6 +1145,12 @@ int build_batch_ops(int T, const int32_t *left, const int32_t *right, int root, 
 			stack.pop_back();
 			const int l = left[n], r = right[n];
 			BatchOp op{n, l, r, 0, src, BATCH_NONE, BATCH_NONE, 0};
+			if (park_all) {
+				if (l >= T) op.dst_left = l - T, stack.push_back({l, l - T});
+				if (r >= T) op.dst_right = r - T, stack.push_back({r, r - T});
+				if (ops) ops->push_back(op);
+				continue;
+			}
 			if (l >= T && r >= T) {
 				int slot;
 				if (free_slots.empty()) slot = slots++;
@@ -1166,7 +1174,7 @@ int build_batch_ops(int T, const int32_t *left, const int32_t *right, int root, 
 			if (src >= 0) free_slots.push_back(src);  // read by this op: later ops may park in it
 		}
 	}
-	return std::max(1, slots);
+	return park_all ? std::max(1, T - 1) : std::max(1, slots);
 }
 
 // the engine's own lists (a batch of branch-length vectors), built once per topology
@@ -1187,19 +1195,29 @@ int ensure_engine_batch_ops(Shard *e) {
 	return PHYAMD_OK;
 }
 
-// what a batch call needs of the scratch per item: the pre-order pass's part, so many upper slots, its own op lists and root
+// what a batch call needs of the scratch per item: the pre-order pass's part, so many upper slots, its own op lists and root;
+// nni: the one item of phyamd_nni_log_likelihoods -- every upper parked (slots = T - 1) and that call's own arrays
 struct BatchShape {
 	bool grad;
 	int slots;
 	bool trees;
+	bool nni = false;
 };
+
+size_t nni_candidates(const Shard *e) { return (size_t)std::max(0, e->T - 2); }
 
 // bytes of batch scratch one item takes
 size_t batch_item_bytes(const Shard *e, BatchShape w) {
 	const size_t nblk = ((size_t)e->P + WAVE - 1) / WAVE, plane = nblk * WAVE * 4;
 	size_t doubles = (size_t)e->N + (size_t)e->N * e->C * 16 + 1 + (w.grad ? (size_t)e->N * e->C : 0) + (size_t)(e->T - 1) * e->C * plane + nblk;
 	if (w.grad) doubles += (size_t)w.slots * e->C * plane + nblk * e->C * e->N;
-	return sizeof(double) * doubles + (w.trees ? sizeof(BatchOp) * 2 * (size_t)(e->T - 1) + sizeof(int32_t) : 0);
+	size_t bytes = sizeof(double) * doubles + (w.trees ? sizeof(BatchOp) * 2 * (size_t)(e->T - 1) + sizeof(int32_t) : 0);
+	if (w.nni) {  // trial lengths and matrices, the slab, the result; the op lists, the candidates and their index by node
+		const size_t cands = std::max<size_t>(nni_candidates(e), 1);
+		bytes += sizeof(double) * ((size_t)3 * e->N + (size_t)3 * e->N * e->C * 16 + cands * nblk * 9 + (size_t)9 * e->N);
+		bytes += sizeof(BatchOp) * 2 * (size_t)(e->T - 1) + sizeof(NniCand) * cands + sizeof(int32_t) * e->N;
+	}
+	return bytes;
 }
 
 size_t batch_scratch_bytes(const Shard *e) { return (size_t)e->batch_mem.bytes; }
@@ -1211,7 +1229,8 @@ void release_batch_scratch(Shard *e) {
 
 // items of shape w the scratch holds now (none once the group has been released to make room)
 size_t batch_items_held(const Shard *e, BatchShape w) {
-	const bool serves = e->d_batch_lower.get() && (e->batch_grad || !w.grad) && (!w.grad || e->batch_slots >= w.slots) && (e->batch_trees || !w.trees);
+	const bool serves = e->d_batch_lower.get() && (e->batch_grad || !w.grad) && (!w.grad || e->batch_slots >= w.slots) && (e->batch_trees || !w.trees) &&
+	                    (e->batch_nni || !w.nni);
 	return serves ? (size_t)e->batch_items : 0;
 }
 
@@ -1245,10 +1264,15 @@ int allocate_batch_scratch(Shard *e, size_t items, BatchShape w) {
 	if ((rc = e->d_batch_len.ensure(items * e->N)) || (rc = e->d_batch_mats.ensure(items * e->N * e->C * 16)) || (rc = e->d_batch_out.ensure(items * rows)) ||
 	    (rc = e->d_batch_lower.ensure(items * (e->T - 1) * e->C * plane)) || (rc = e->d_batch_lnl.ensure(items * nblk)) ||
 	    (w.grad && ((rc = e->d_batch_upper.ensure(items * w.slots * e->C * plane)) || (rc = e->d_batch_slab.ensure(items * nblk * e->C * e->N)))) ||
-	    (w.trees && ((rc = e->d_batch_item_ops.ensure(items * 2 * (e->T - 1))) || (rc = e->d_batch_roots.ensure(items))))) {
+	    (w.trees && ((rc = e->d_batch_item_ops.ensure(items * 2 * (e->T - 1))) || (rc = e->d_batch_roots.ensure(items)))) ||
+	    (w.nni && ((rc = e->d_nni_ops.ensure((size_t)2 * (e->T - 1))) || (rc = e->d_nni_cands.ensure(nni_candidates(e))) || (rc = e->d_nni_cand_of.ensure(e->N)) ||
+	               (rc = e->d_nni_len.ensure((size_t)3 * e->N)) || (rc = e->d_nni_mats.ensure((size_t)3 * e->N * e->C * 16)) ||
+	               (rc = e->d_nni_slab.ensure(nni_candidates(e) * nblk * 9)) || (rc = e->d_nni_out.ensure((size_t)9 * e->N))))) {
 		release_batch_scratch(e);
 		return rc;
 	}
+	e->batch_nni = w.nni;
+	e->nni_lists_valid = false;  // (freed above with everything else)
 	e->batch_items = (int)items;
 	e->batch_grad = w.grad;
 	e->batch_slots = w.grad ? w.slots : 0;
@@ -1261,7 +1285,7 @@ int ensure_batch_scratch(Shard *e, size_t items, BatchShape w) {
 	if (e->cfg.max_device_bytes <= 0 && e->d_batch_lower.get()) {
 		// without a cap the scratch keeps what the previous call needed as well: calls of the two kinds, or of trees that park in
 		// fewer and in more slots, may alternate without an allocation each (under a cap every call gets exactly its own)
-		const BatchShape both{w.grad || e->batch_grad, std::max(w.slots, e->batch_slots), w.trees || e->batch_trees};
+		const BatchShape both{w.grad || e->batch_grad, std::max(w.slots, e->batch_slots), w.trees || e->batch_trees, w.nni || e->batch_nni};
 		if (allocate_batch_scratch(e, items, both) == PHYAMD_OK) return PHYAMD_OK;
 	}
 	return allocate_batch_scratch(e, items, w);
@@ -1506,5 +1530,116 @@ int shard_get_batch_profile(Shard *e, phyamd_batch_profile *out) {
 	CHECK_ENGINE(e);
 	if (!out) return fail(PHYAMD_EINVAL, "null out");
 	*out = e->batch_prof;
+	return PHYAMD_OK;
+}
+
+// ---- every NNI neighbour of the engine's tree (phyamd_nni_log_likelihoods) -----------------------------------------------------
+
+// the engine's tree's op lists with every upper parked, its candidate edges and their index by node, into the scratch
+int upload_nni_lists(Shard *e) {
+	if (e->nni_lists_valid && e->d_nni_ops.get()) return PHYAMD_OK;
+	const int T = e->T, N = e->N;
+	std::vector<BatchOp> ops;
+	build_batch_ops(T, e->left.data(), e->right.data(), e->root, &ops, true);
+	std::vector<NniCand> cands;
+	std::vector<int32_t> cand_of(N, -1);
+	for (int v = T; v < N; v++) {
+		if (v == e->root) continue;
+		const int u = e->parent[v];
+		cand_of[v] = (int32_t)cands.size();
+		cands.push_back(NniCand{v, u == e->root ? BATCH_ROOT : u, e->left[u] == v ? e->right[u] : e->left[u], e->left[v], e->right[v], {0, 0, 0}});
+	}
+	HIP_TRY(hipMemcpyAsync(e->d_nni_ops, ops.data(), sizeof(BatchOp) * ops.size(), hipMemcpyHostToDevice, e->stream));
+	if (!cands.empty()) HIP_TRY(hipMemcpyAsync(e->d_nni_cands, cands.data(), sizeof(NniCand) * cands.size(), hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipMemcpyAsync(e->d_nni_cand_of, cand_of.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));  // (stack-lifetime buffers)
+	e->nni_lists_valid = true;
+	return PHYAMD_OK;
+}
+
+// out [3 terms][3][N] (host): one walk of the engine's tree with every upper parked, the trial matrices, every edge's three
+// arrangements in one launch.  Reads the engine's inputs and writes only the batch scratch: nothing in Shard::state changes
+int run_nni(Shard *e, int flags, const double *central_lengths, bool deriv, double *out, phyamd_nni_profile &prof) {
+	int rc;
+	if ((rc = check_ready(e))) return rc;
+	if (flags != 0) return fail(PHYAMD_EUNSUPPORTED, "phyamd_nni_log_likelihoods: flags %d (no flags are defined: pass 0)", flags);
+	if (const char *why = tree_batch_refusal(e, 0, 1)) return fail(PHYAMD_EUNSUPPORTED, "phyamd_nni_log_likelihoods: %s", why);
+	if (!e->have_eigen || !e->have_Q)
+		return fail(PHYAMD_EINVAL, "phyamd_nni_log_likelihoods needs the eigen system (phyamd_set_eigen): the trial matrices, d1 and d2 are formed from it");
+	const int T = e->T, N = e->N, C = e->C;
+	// the trial lengths: a candidate's own three, every other entry the engine's (ignored: no arrangement reads that matrix)
+	std::vector<double> trial((size_t)3 * N);
+	for (int k = 0; k < 3; k++) std::copy(e->lengths.begin(), e->lengths.end(), trial.begin() + (size_t)k * N);
+	for (int v = T; v < N && central_lengths; v++) {
+		if (v == e->root) continue;
+		for (int k = 0; k < 3; k++) {
+			const double t = central_lengths[(size_t)k * N + v];
+			if (!std::isfinite(t) || t < 0.0)
+				return fail(PHYAMD_EINVAL, "phyamd_nni_log_likelihoods: central_lengths[%d][%d] = %g: a trial length is finite and not negative", k, v, t);
+			trial[(size_t)k * N + v] = t;
+		}
+	}
+	const size_t cands = nni_candidates(e);
+	prof.candidates = (int32_t)cands;
+	std::fill(out, out + (size_t)9 * N, NAN);
+	if (cands == 0) return PHYAMD_OK;  // two tips: no internal edge
+	const BatchShape shape{true, T - 1, false, true};
+	if (batch_items_that_fit(e, 1, shape) < 1)
+		return fail(PHYAMD_EUNSUPPORTED, "phyamd_nni_log_likelihoods: the scratch (%zu bytes: every internal node's lower and upper partial) does not fit the memory budget",
+		            batch_item_bytes(e, shape));
+	if ((rc = ensure_batch_scratch(e, 1, shape)) || (rc = upload_nni_lists(e))) return rc;
+	const int nblk = (e->P + WAVE - 1) / WAVE, nops = T - 1;
+	HIP_TRY(hipMemcpyAsync(e->d_nni_len, trial.data(), sizeof(double) * trial.size(), hipMemcpyHostToDevice, e->stream));
+	const auto matrices = [&](int items, const double *lengths, double *mats) {
+		const size_t total = (size_t)items * N * C * 16;
+		hipLaunchKernelGGL(k_batch_matrices, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, e->stream, C, N, items, e->d_model, e->d_rates, lengths,
+		                   e->root, (const int32_t *)nullptr, mats);
+	};
+	matrices(1, e->d_lengths, e->d_batch_mats);  // the walk's item: the engine's lengths
+	matrices(3, e->d_nni_len, e->d_nni_mats);
+	const BatchOp *ops = e->d_nni_ops.get();
+	const BatchArgs walk{ops, ops + nops, 0, T, N, e->P, C, nblk, T - 1, 1, e->d_tipmask, e->d_freqs, e->d_props, e->d_weights, e->d_Q, e->d_batch_mats, e->d_batch_lower,
+	                     e->d_batch_upper, e->d_batch_lnl, e->d_batch_slab};
+	hipLaunchKernelGGL(k_batch_walk4<false>, dim3(nblk, 1), dim3(WAVE, C), 0, e->stream, walk);
+	for (size_t first = 0; first < cands; first += BATCH_MAX_CHUNK) {  // (gridDim.y)
+		const size_t n = std::min<size_t>(cands - first, BATCH_MAX_CHUNK);
+		const NniArgs a{e->d_nni_cands.get() + first, T, N, e->P, C, nblk, deriv ? 1 : 0, e->d_tipmask, e->d_freqs, e->d_props, e->d_rates, e->d_weights, e->d_Q,
+		                e->d_batch_mats, e->d_nni_mats, e->d_batch_lower, e->d_batch_upper, e->d_nni_slab + first * nblk * 9};
+		hipLaunchKernelGGL(k_nni4, dim3(nblk, (unsigned)n), dim3(WAVE, C), 0, e->stream, a);
+	}
+	hipLaunchKernelGGL(k_nni_finish, dim3((unsigned)(((size_t)9 * N + 255) / 256)), dim3(256), 0, e->stream, N, nblk, e->d_nni_cand_of.get(), e->d_nni_slab.get(),
+	                   e->d_nni_out.get());
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(out, e->d_nni_out, sizeof(double) * (size_t)9 * N, hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));  // (also covers `trial`)
+	return PHYAMD_OK;
+}
+
+// an entry whose lnL is not finite reports it in band with NaN derivatives (treelikelihood.c:327-332, per entry); out: [lnl | d1 | d2]
+void nni_mask_derivatives(size_t entries, double *out) {
+	for (size_t i = 0; i < entries; i++)
+		if (std::isnan(out[i]) || std::isinf(out[i])) out[entries + i] = out[2 * entries + i] = NAN;
+}
+
+// out [3 terms][3][N] on the host; deriv: d1 and d2 as well (else those rows are NaN at tips and the root, 0 elsewhere)
+int shard_nni_log_likelihoods(Shard *e, int flags, const double *central_lengths, bool deriv, double *out) {
+	CHECK_ENGINE(e);
+	if (!out) return fail(PHYAMD_EINVAL, "phyamd_nni_log_likelihoods: null lnl");
+	const auto t0 = std::chrono::steady_clock::now();
+	int rc;
+	if ((rc = bind_device(e))) return rc;
+	phyamd_nni_profile prof{};
+	rc = run_nni(e, flags, central_lengths, deriv, out, prof);
+	if (!rc) nni_mask_derivatives((size_t)3 * e->N, out);
+	prof.scratch_bytes = (int64_t)batch_scratch_bytes(e);
+	prof.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	e->nni_prof = prof;
+	return rc;
+}
+
+int shard_get_nni_profile(Shard *e, phyamd_nni_profile *out) {
+	CHECK_ENGINE(e);
+	if (!out) return fail(PHYAMD_EINVAL, "null out");
+	*out = e->nni_prof;
 	return PHYAMD_OK;
 }

@@ -241,6 +241,31 @@ class Engine:
         self._check(self._lib.phyamd_get_batch_profile(self._h, C.byref(p)))
         return {k: getattr(p, k) for k, _ in p._fields_}
 
+    def nni_log_likelihoods(self, central_lengths=None, want_derivatives=True, flags=0):
+        """Every NNI neighbour of this engine's tree at once: (lnl, d1, d2), each [3, N] (d1, d2 None without want_derivatives).
+        Column v is an internal node other than the root, with parent u, sibling s and children a = left[v], b = right[v]; row 0 is
+        the engine's tree, row 1 has a and s exchanged, row 2 b and s.  central_lengths [3, N]: the trial length of branch v per row
+        (None: its own length; entries at tips and the root are ignored).  d1, d2: the derivatives of that lnL in the length of v,
+        as branch_hessian_diagonal defines them.  Tips' and the root's columns are NaN.  The engine's tree, lengths and partials
+        stay.  No fallback: EngineError where gradient_batch_trees refuses."""
+        cl = None
+        if central_lengths is not None:
+            cl = _f64(central_lengths)
+            if cl.shape != (3, self.N):
+                raise ValueError(f"central_lengths must be [3, {self.N}] (got {cl.shape})")
+        lnl = np.empty((3, self.N))
+        d1 = np.empty((3, self.N)) if want_derivatives else None
+        d2 = np.empty((3, self.N)) if want_derivatives else None
+        self._check(self._lib.phyamd_nni_log_likelihoods(self._h, flags, None if cl is None else _ptr(cl), _ptr(lnl),
+                                                         None if d1 is None else _ptr(d1), None if d2 is None else _ptr(d2)))
+        return lnl, d1, d2
+
+    def nni_profile(self):
+        """Of the last nni_log_likelihoods: candidates (edges scored), scratch_bytes, ms."""
+        p = _lib.NniProfile()
+        self._check(self._lib.phyamd_get_nni_profile(self._h, C.byref(p)))
+        return {k: getattr(p, k) for k, _ in p._fields_}
+
     def store(self):
         """Remember the current (evaluated) state: parameters, lnL and partials (MCMC store)."""
         self._check(self._lib.phyamd_store(self._h))
