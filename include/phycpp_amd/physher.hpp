@@ -297,6 +297,11 @@ class TreeLikelihoodInterface : public CallableModelInterface {
 	// evaluation hands it: the tree model's lengths, with a clock rate or mu folded in).  d1 and d2 may be null.  The tree model
 	// and this object's own state are unchanged.
 	void NNILogLikelihoods(const double *centralLengths, double *logLikelihoods, double *d1, double *d2);
+	// lnL of every SPR regraft of `count` prune nodes of the tree model's tree at once (one phyamd_spr_log_likelihoods call; see
+	// include/physher_amd.h for the move and the candidates): out [count][2T-1] by the tree's node ids, row i the prune node
+	// prune[i] (null: count = 2T-1 and row i is node i), column w the target edge; NaN where there is no candidate.  Lengths are
+	// the engine's branch lengths, as for NNILogLikelihoods.  The tree model and this object's own state are unchanged.
+	void SPRLogLikelihoods(const int *prune, int count, double *out);
 	size_t NodeCount() const;  // 2T - 1
 	size_t TreeParameterCount() const { return treeModel_->parameterCount_; }  // n of treeParameters [count][n]
 	size_t GetPatternCount() const;

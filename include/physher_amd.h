@@ -308,6 +308,39 @@ int phyamd_nni_log_likelihoods(phyamd_engine *e, int flags, const double *centra
  * phyamd_batch_profile), wall time of the call */
 typedef struct { int32_t candidates; int64_t scratch_bytes; double ms; } phyamd_nni_profile;
 int phyamd_get_nni_profile(phyamd_engine *e, phyamd_nni_profile *out);
+/* lnL of every SPR regraft of chosen subtrees of the engine's tree: per prune node ONE post-order and ONE pre-order walk of the
+ * tree without it, then every target edge in one launch -- O(T) work per prune node and O(T^2) for the whole neighbourhood, where
+ * phyamd_gradient_batch_trees walks each of the O(T^2) rearranged trees from the tips.
+ * Row i of lnl ([count][2T-1]) belongs to the prune node p = prune[i]; prune == NULL: count must be 2T-1 and row i is node i.
+ * Column w is the target edge, named by the node below it.  With u = parent(p), s = sibling(p), g = parent(u), x = parent(w),
+ * lnl[i][w] is the log-likelihood of the tree obtained from the engine's arrays by (node ids kept)
+ *   g's child slot that held u now holds s, with t'_s = t_s + t_u;
+ *   x's child slot that held w now holds u;
+ *   u keeps p in its slot and gets w in the slot s had, with t'_u = t'_w = 0.5 t_w;
+ * everything else -- the root, t_p -- unchanged: the graft edge is halved and the sibling's branch absorbs the parent's.  It is
+ * the lnl of the phyamd_gradient_batch_trees item with those arrays.  Column w is a CANDIDATE unless w is the root, u, s, p or a
+ * descendant of p; every other column is NaN.  A row is all NaN when p is the root or a child of the root (no error, so that
+ * prune == NULL works uniformly): a caller re-roots the tree to reach those moves, as for the NNI across the root edge above.
+ * Duplicates in prune are allowed.  There are no derivatives and no trial lengths in this call: a caller takes its best few
+ * candidates to phyamd_gradient_batch_trees.
+ * The remaining contract is phyamd_nni_log_likelihoods': the engine -- its topology, lengths, partials -- is unchanged and later
+ * evaluations return the bits they would have returned without the call; two calls return identical bits, and a row does not
+ * depend on what the batch scratch held before, on count, on its position in prune or on the chunks the rows ran in; a
+ * candidate whose lnL is not finite reports it in band, under PHYAMD_RESCALE_NEVER and _AUTO alike, and the engine is never
+ * switched to rescaling.  There is no fallback path: PHYAMD_EUNSUPPORTED, naming the condition, under
+ * phyamd_gradient_batch_trees' conditions (not 4 states, more than 8 categories, an engine that is rescaling now, tiled patterns,
+ * a tip cell with an empty state mask, explicit node matrices), for flags other than 0, and when the scratch of one row -- every
+ * internal node's lower and upper partial, held in the batch scratch and released like it -- does not fit the memory cap (rows
+ * that do not fit as a whole run in chunks of rows).  PHYAMD_EINVAL: null engine or lnl, count < 1, prune == NULL with another
+ * count than 2T-1, an id outside 0..2T-2 (with its index in the message), no eigen system (the half-length matrices come from
+ * it).  Sharded handles run on every shard's patterns and add the arrays in shard order. */
+int phyamd_spr_log_likelihoods(phyamd_engine *e, int flags, int32_t count, const int32_t *prune /* [count] or NULL */,
+                               double *lnl /* [count][2T-1] */);
+/* of the last phyamd_spr_log_likelihoods: rows asked for, chunks of rows they ran in, candidates scored, bytes of batch scratch
+ * the engine holds (see phyamd_batch_profile), wall time of the call.  Sharded handles: candidates and scratch_bytes are summed
+ * over the shards */
+typedef struct { int32_t prunes, chunks; int64_t candidates, scratch_bytes; double ms; } phyamd_spr_profile;
+int phyamd_get_spr_profile(phyamd_engine *e, phyamd_spr_profile *out);
 int phyamd_synchronize(phyamd_engine *e);
 
 /* --- inspection (parity tests, debugging) --- */

@@ -913,3 +913,9 @@ void TreeLikelihoodInterface::NNILogLikelihoods(const double *centralLengths, do
 	Sync();
 	phyamd::check(phyamd_nni_log_likelihoods(impl_->engine, 0, centralLengths, logLikelihoods, d1, d2));
 }
+
+void TreeLikelihoodInterface::SPRLogLikelihoods(const int *prune, int count, double *out) {
+	if (!out) throw Error("null out");
+	Sync();
+	phyamd::check(phyamd_spr_log_likelihoods(impl_->engine, 0, count, prune, out));
+}

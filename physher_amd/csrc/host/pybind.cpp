@@ -241,6 +241,14 @@ PYBIND11_MODULE(_phycpp_amd, m) {
 		    if (!want_derivatives) return py::make_tuple(darray(shape, lnl.data()), py::none(), py::none());
 		    return py::make_tuple(darray(shape, lnl.data()), darray(shape, d1.data()), darray(shape, d2.data()));
 	    }, py::arg("central_lengths") = py::none(), py::arg("want_derivatives") = true)
+	    .def("spr_log_likelihoods", [](TreeLikelihoodInterface &self, std::optional<iarray> prune) {
+		    const py::ssize_t N = (py::ssize_t)self.NodeCount();
+		    if (prune && prune->ndim() != 1) throw phyamd::Error("prune: [count]");
+		    const py::ssize_t count = prune ? prune->shape(0) : N;
+		    std::vector<double> lnl((size_t)count * N);
+		    self.SPRLogLikelihoods(prune ? prune->data() : nullptr, (int)count, lnl.data());
+		    return darray({count, N}, lnl.data());
+	    }, py::arg("prune") = py::none())
 	    .def("get_pattern_count", &TreeLikelihoodInterface::GetPatternCount)
 	    .def("pattern_weights", [](TreeLikelihoodInterface &self) { return vec(self.PatternWeights()); })
 	    .def("pattern_states", [](TreeLikelihoodInterface &self) {

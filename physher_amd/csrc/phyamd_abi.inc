@@ -85,6 +85,7 @@ struct phyamd_engine {
 	bool poisoned = false;                     // a replicated call failed on some shards only: their states differ, nothing can be summed
 	std::vector<std::vector<double>> scratch;  // per-shard host result vectors
 	std::vector<std::string> errors;
+	double spr_ms = 0.0;                       // wall time of the last phyamd_spr_log_likelihoods
 };
 
 namespace {
@@ -559,6 +560,40 @@ int phyamd_get_nni_profile(phyamd_engine *g, phyamd_nni_profile *out) {
 		out->scratch_bytes += p.scratch_bytes;
 		out->ms = std::max(out->ms, p.ms);
 	}
+	return PHYAMD_OK;
+}
+
+// every shard scores every row on its patterns; the rows are sums over patterns, added in shard order (NaN cells stay NaN)
+int phyamd_spr_log_likelihoods(phyamd_engine *g, int flags, int32_t count, const int32_t *prune, double *lnl) {
+	if (count < 1) return fail(PHYAMD_EINVAL, "phyamd_spr_log_likelihoods: count must be >= 1 (got %d)", count);
+	if (!lnl) return fail(PHYAMD_EINVAL, "phyamd_spr_log_likelihoods: null lnl");
+	CHECK_GROUP(g);
+	const auto t0 = std::chrono::steady_clock::now();
+	int rc;
+	if (group_size(g) == 1) rc = shard_spr_log_likelihoods(g->shards[0], flags, count, prune, lnl);
+	else {
+		const size_t n = (size_t)count * g->N;
+		ensure_scratch(g, n);
+		rc = for_shards(g, [&](Shard *s, int i) { return shard_spr_log_likelihoods(s, flags, count, prune, g->scratch[i].data()); });
+		if (!rc) sum_shards(g, n, lnl);
+	}
+	g->spr_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	return rc;
+}
+
+int phyamd_get_spr_profile(phyamd_engine *g, phyamd_spr_profile *out) {
+	CHECK_GROUP(g);
+	if (!out) return fail(PHYAMD_EINVAL, "null out");
+	int rc;
+	if ((rc = shard_get_spr_profile(g->shards[0], out))) return rc;
+	for (int i = 1; i < group_size(g); i++) {  // candidates and memory add up; the shards choose their chunks themselves: the most
+		phyamd_spr_profile p;
+		if ((rc = shard_get_spr_profile(g->shards[i], &p))) return rc;
+		out->chunks = std::max(out->chunks, p.chunks);
+		out->candidates += p.candidates;
+		out->scratch_bytes += p.scratch_bytes;
+	}
+	out->ms = g->spr_ms;
 	return PHYAMD_OK;
 }
 

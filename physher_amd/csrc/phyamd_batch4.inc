@@ -23,7 +23,7 @@ struct BatchOp {
 	int32_t src, dst_left, dst_right;
 	int32_t pad;
 };
-enum { BATCH_NONE = -1, BATCH_CARRY = -2, BATCH_ROOT = -3 };
+enum { BATCH_NONE = -1, BATCH_CARRY = -2, BATCH_ROOT = -3, BATCH_GHOST = -4 };  // BATCH_GHOST: a pruned child (phyamd_spr4.inc), whose message is all ones
 
 constexpr int BATCH_MAX_CATEGORIES = 8;  // one LDS row of site-likelihood terms per category; at most 8 category waves per workgroup
 

@@ -42,6 +42,7 @@ struct Shard {
 		bool tiled_eval_done = false;  // d_total holds the sums of a tiled evaluation at the current inputs
 		bool tiled_root_term = false;  // ... and d_result the summed root frequency term of a tiled parameter gradient
 		unsigned long tip_epoch = 1;   // the tip data in d_tipmask (the mask words: as of mstream_epoch)
+		bool spr_lists_dirty = true;   // spr_ops and spr_tin / spr_tout are not the current tree's
 	} state;
 	bool incremental_pass = false;
 	std::vector<NodeOp> inc_ops;      // ops of the dirty core nodes, by level
@@ -255,6 +256,19 @@ struct Shard {
 	DeviceArray<double> d_nni_slab{&batch_mem}, d_nni_out{&batch_mem};  // [T - 2][blocks][9], [3 terms][3][N]
 	bool nni_lists_valid = false;        // d_nni_ops, d_nni_cands and d_nni_cand_of hold the engine's tree's (while they are allocated)
 	phyamd_nni_profile nni_prof{};
+	// phyamd_spr_log_likelihoods (phyamd_spr4.inc) walks one item of the scratch above per prune node (a ROW), with its own op
+	// lists (d_batch_item_ops) and every upper parked (slots = T - 1), and adds to the group: per row the candidate edges, each
+	// cell's candidate index, the slab and the result; once the engine's lengths with their halves and the matrices of both.
+	// On the host: the engine's tree's park_all op lists, which every row's lists are a copy of but for the ghost, and each
+	// node's interval in a depth-first numbering (n is in p's subtree: spr_tin[p] <= spr_tin[n] < spr_tout[p])
+	std::vector<BatchOp> spr_ops;        // [post-order T - 1 | pre-order T - 1] (State::spr_lists_dirty)
+	std::vector<int32_t> spr_tin, spr_tout, spr_lower_at, spr_upper_at;  // [N]; the index of an internal node's op in either list
+	DeviceArray<SprCand> d_spr_cands{&batch_mem};    // [rows][at most N], the rows' candidates one after the other
+	DeviceArray<int32_t> d_spr_cand_of{&batch_mem};  // [rows][N]: cell -> index in d_spr_cands, -1: no candidate
+	DeviceArray<double> d_spr_slab{&batch_mem}, d_spr_out{&batch_mem};  // [candidate][blocks], [rows][N]
+	DeviceArray<double> d_spr_len{&batch_mem}, d_spr_mats{&batch_mem};  // [t | 0.5 t][N], [2][N][C][16]
+	bool batch_spr = false;              // the scratch holds these arrays for batch_items rows
+	phyamd_spr_profile spr_prof{};
 };
 
 // ---- what each input invalidates -------------------------------------------------------------------------------------------
@@ -280,7 +294,7 @@ void input_changed(Shard *e, Input in, int node = -1) {
 	switch (in) {
 	case Input::TipData: lowers = true, s.stored_valid = false, s.tip_epoch++; break;
 	case Input::PatternWeights: lowers = true, s.stored_valid = false; break;
-	case Input::Topology: tables = lowers = true, s.stored_valid = false, e->schedule_epoch++; break;  // (not part of phyamd_store)
+	case Input::Topology: tables = lowers = true, s.stored_valid = false, s.spr_lists_dirty = true, e->schedule_epoch++; break;  // (not part of phyamd_store)
 	case Input::BranchLengths:  // the whole vector: every node is recomputed (SingleTreeLikelihood_update_all_nodes)
 	case Input::CategoryRates:
 	case Input::Matrices:
@@ -315,6 +329,7 @@ void q_images_rebuilt(Shard *e) { e->state.qimg_dirty = false, e->state.qp_kind 
 void qpi_rebuilt(Shard *e) { e->state.qpi_dirty = false; }
 void tip_rate_products_rebuilt(Shard *e, int kind) { e->state.qp_kind = kind; }
 void parameter_basis_rebuilt(Shard *e) { e->state.params_dirty = false; }
+void spr_lists_rebuilt(Shard *e) { e->state.spr_lists_dirty = false; }
 
 // ---- what d_lower holds ----------------------------------------------------------------------------------------------------
 // Every 4-state post-order pass records the form it wrote (launch_lower_w, launch_lower_stream).  A reader other than the two

@@ -1196,12 +1196,14 @@ int ensure_engine_batch_ops(Shard *e) {
 }
 
 // what a batch call needs of the scratch per item: the pre-order pass's part, so many upper slots, its own op lists and root;
-// nni: the one item of phyamd_nni_log_likelihoods -- every upper parked (slots = T - 1) and that call's own arrays
+// nni: the one item of phyamd_nni_log_likelihoods -- every upper parked (slots = T - 1) and that call's own arrays; spr: the
+// items are rows of phyamd_spr_log_likelihoods -- every upper parked, their own op lists, and that call's arrays
 struct BatchShape {
 	bool grad;
 	int slots;
 	bool trees;
 	bool nni = false;
+	bool spr = false;
 };
 
 size_t nni_candidates(const Shard *e) { return (size_t)std::max(0, e->T - 2); }
@@ -1217,6 +1219,10 @@ size_t batch_item_bytes(const Shard *e, BatchShape w) {
 		bytes += sizeof(double) * ((size_t)3 * e->N + (size_t)3 * e->N * e->C * 16 + cands * nblk * 9 + (size_t)9 * e->N);
 		bytes += sizeof(BatchOp) * 2 * (size_t)(e->T - 1) + sizeof(NniCand) * cands + sizeof(int32_t) * e->N;
 	}
+	if (w.spr) {  // the row's candidates, their index by cell, the slab, the result; the two length vectors and their matrices (once: counted per row)
+		bytes += (sizeof(SprCand) + sizeof(int32_t) + sizeof(double) * (nblk + 1)) * (size_t)e->N;
+		bytes += sizeof(double) * ((size_t)2 * e->N + (size_t)2 * e->N * e->C * 16);
+	}
 	return bytes;
 }
 
@@ -1230,7 +1236,7 @@ void release_batch_scratch(Shard *e) {
 // items of shape w the scratch holds now (none once the group has been released to make room)
 size_t batch_items_held(const Shard *e, BatchShape w) {
 	const bool serves = e->d_batch_lower.get() && (e->batch_grad || !w.grad) && (!w.grad || e->batch_slots >= w.slots) && (e->batch_trees || !w.trees) &&
-	                    (e->batch_nni || !w.nni);
+	                    (e->batch_nni || !w.nni) && (e->batch_spr || !w.spr);
 	return serves ? (size_t)e->batch_items : 0;
 }
 
@@ -1267,12 +1273,15 @@ int allocate_batch_scratch(Shard *e, size_t items, BatchShape w) {
 	    (w.trees && ((rc = e->d_batch_item_ops.ensure(items * 2 * (e->T - 1))) || (rc = e->d_batch_roots.ensure(items)))) ||
 	    (w.nni && ((rc = e->d_nni_ops.ensure((size_t)2 * (e->T - 1))) || (rc = e->d_nni_cands.ensure(nni_candidates(e))) || (rc = e->d_nni_cand_of.ensure(e->N)) ||
 	               (rc = e->d_nni_len.ensure((size_t)3 * e->N)) || (rc = e->d_nni_mats.ensure((size_t)3 * e->N * e->C * 16)) ||
-	               (rc = e->d_nni_slab.ensure(nni_candidates(e) * nblk * 9)) || (rc = e->d_nni_out.ensure((size_t)9 * e->N))))) {
+	               (rc = e->d_nni_slab.ensure(nni_candidates(e) * nblk * 9)) || (rc = e->d_nni_out.ensure((size_t)9 * e->N)))) ||
+	    (w.spr && ((rc = e->d_spr_cands.ensure(items * e->N)) || (rc = e->d_spr_cand_of.ensure(items * e->N)) || (rc = e->d_spr_slab.ensure(items * e->N * nblk)) ||
+	               (rc = e->d_spr_out.ensure(items * e->N)) || (rc = e->d_spr_len.ensure((size_t)2 * e->N)) || (rc = e->d_spr_mats.ensure((size_t)2 * e->N * e->C * 16))))) {
 		release_batch_scratch(e);
 		return rc;
 	}
 	e->batch_nni = w.nni;
 	e->nni_lists_valid = false;  // (freed above with everything else)
+	e->batch_spr = w.spr;
 	e->batch_items = (int)items;
 	e->batch_grad = w.grad;
 	e->batch_slots = w.grad ? w.slots : 0;
@@ -1285,7 +1294,7 @@ int ensure_batch_scratch(Shard *e, size_t items, BatchShape w) {
 	if (e->cfg.max_device_bytes <= 0 && e->d_batch_lower.get()) {
 		// without a cap the scratch keeps what the previous call needed as well: calls of the two kinds, or of trees that park in
 		// fewer and in more slots, may alternate without an allocation each (under a cap every call gets exactly its own)
-		const BatchShape both{w.grad || e->batch_grad, std::max(w.slots, e->batch_slots), w.trees || e->batch_trees, w.nni || e->batch_nni};
+		const BatchShape both{w.grad || e->batch_grad, std::max(w.slots, e->batch_slots), w.trees || e->batch_trees, w.nni || e->batch_nni, w.spr || e->batch_spr};
 		if (allocate_batch_scratch(e, items, both) == PHYAMD_OK) return PHYAMD_OK;
 	}
 	return allocate_batch_scratch(e, items, w);
@@ -1641,5 +1650,153 @@ int shard_get_nni_profile(Shard *e, phyamd_nni_profile *out) {
 	CHECK_ENGINE(e);
 	if (!out) return fail(PHYAMD_EINVAL, "null out");
 	*out = e->nni_prof;
+	return PHYAMD_OK;
+}
+
+// ---- every SPR regraft of chosen subtrees (phyamd_spr_log_likelihoods) ---------------------------------------------------------
+
+// the engine's tree's park_all op lists, where each internal node's op is in them, and every node's depth-first interval
+void ensure_spr_lists(Shard *e) {
+	if (!e->state.spr_lists_dirty) return;
+	const int T = e->T, N = e->N, nops = T - 1;
+	e->spr_ops.clear();
+	build_batch_ops(T, e->left.data(), e->right.data(), e->root, &e->spr_ops, true);
+	e->spr_lower_at.assign(N, -1);
+	e->spr_upper_at.assign(N, -1);
+	for (int i = 0; i < nops; i++) e->spr_lower_at[e->spr_ops[i].node] = i, e->spr_upper_at[e->spr_ops[nops + i].node] = i;
+	e->spr_tin.assign(N, 0);
+	e->spr_tout.assign(N, 0);
+	int32_t clock = 0;
+	std::vector<std::pair<int, bool>> stack{{e->root, false}};
+	while (!stack.empty()) {
+		const auto [n, done] = stack.back();
+		stack.pop_back();
+		if (done) {
+			e->spr_tout[n] = clock;
+			continue;
+		}
+		e->spr_tin[n] = clock++;
+		stack.push_back({n, true});
+		if (n >= T) stack.push_back({e->right[n], false}), stack.push_back({e->left[n], false});
+	}
+	spr_lists_rebuilt(e);
+}
+
+// row p (not the root, not a child of it) into a chunk's lists: its op lists -- the engine's with p a ghost in its parent's two
+// ops, and nothing parked in p's subtree -- appended to `ops`, its candidates to `cands`, their indices into cand_of [N]
+void build_spr_row(const Shard *e, int row, int p, std::vector<BatchOp> *ops, std::vector<SprCand> *cands, int32_t *cand_of) {
+	const int T = e->T, N = e->N, nops = T - 1;
+	const int u = e->parent[p], s = e->left[u] == p ? e->right[u] : e->left[u];
+	const auto below_p = [&](int n) { return e->spr_tin[p] <= e->spr_tin[n] && e->spr_tin[n] < e->spr_tout[p]; };
+	const size_t first = ops->size();
+	ops->insert(ops->end(), e->spr_ops.begin(), e->spr_ops.end());
+	BatchOp &up = (*ops)[first + e->spr_lower_at[u]], &down = (*ops)[first + nops + e->spr_upper_at[u]];
+	if (up.left == p) up.left = BATCH_GHOST, up.carry = up.carry == 1 ? 0 : up.carry;
+	else up.right = BATCH_GHOST, up.carry = up.carry == 2 ? 0 : up.carry;
+	if (down.left == p) down.left = BATCH_GHOST, down.dst_left = BATCH_NONE;
+	else down.right = BATCH_GHOST, down.dst_right = BATCH_NONE;
+	for (int i = 0; i < nops; i++) {
+		BatchOp &op = (*ops)[first + nops + i];
+		if (below_p(op.node)) op.dst_left = op.dst_right = BATCH_NONE;
+	}
+	for (int w = 0; w < N; w++) {
+		cand_of[w] = -1;
+		if (w == e->root || w == u || w == s || below_p(w)) continue;
+		const int x = e->parent[w];
+		cand_of[w] = (int32_t)cands->size();
+		cands->push_back(SprCand{row, w, x == e->root ? BATCH_ROOT : x, e->left[x] == w ? e->right[x] : e->left[x], p, {0, 0, 0}});
+	}
+}
+
+// lnl [count][N] (host).  Reads the engine's inputs and writes only the batch scratch: nothing in Shard::state changes but the
+// record that the host lists are the tree's
+int run_spr(Shard *e, int flags, int32_t count, const int32_t *prune, double *lnl, phyamd_spr_profile &prof) {
+	int rc;
+	if ((rc = check_ready(e))) return rc;
+	if (flags != 0) return fail(PHYAMD_EUNSUPPORTED, "phyamd_spr_log_likelihoods: flags %d (no flags are defined: pass 0)", flags);
+	if (const char *why = tree_batch_refusal(e, 0, 1)) return fail(PHYAMD_EUNSUPPORTED, "phyamd_spr_log_likelihoods: %s", why);
+	if (!e->have_eigen) return fail(PHYAMD_EINVAL, "phyamd_spr_log_likelihoods needs the eigen system (phyamd_set_eigen): the half-length matrices are formed from it");
+	const int T = e->T, N = e->N, C = e->C, nops = T - 1;
+	if (!prune && count != N) return fail(PHYAMD_EINVAL, "phyamd_spr_log_likelihoods: prune is null, so count must be the node count %d (got %d)", N, count);
+	std::vector<int32_t> live;  // indices of the rows that have candidates: p is neither the root nor a child of it
+	for (int32_t i = 0; i < count; i++) {
+		const int p = prune ? prune[i] : i;
+		if (p < 0 || p >= N) return fail(PHYAMD_EINVAL, "phyamd_spr_log_likelihoods: prune[%d] = %d is not a node id (0..%d)", i, p, N - 1);
+		if (p != e->root && e->parent[p] != e->root) live.push_back(i);
+	}
+	std::fill(lnl, lnl + (size_t)count * N, NAN);
+	prof.prunes = count;
+	if (live.empty()) return PHYAMD_OK;
+	ensure_spr_lists(e);
+	const BatchShape shape{true, T - 1, true, false, true};
+	const int nblk = (e->P + WAVE - 1) / WAVE;
+	std::vector<double> lengths((size_t)2 * N), out;
+	for (int n = 0; n < N; n++) lengths[n] = e->lengths[n], lengths[N + n] = 0.5 * e->lengths[n];
+	std::vector<BatchOp> ops;
+	std::vector<SprCand> cands;
+	std::vector<int32_t> cand_of;
+	for (size_t first = 0; first < live.size();) {
+		const size_t rows = std::min(batch_items_that_fit(e, live.size() - first, shape), live.size() - first);
+		if (rows < 1)
+			return fail(PHYAMD_EUNSUPPORTED, "phyamd_spr_log_likelihoods: the scratch of one row (%zu bytes: every internal node's lower and upper partial) does not fit the memory budget",
+			            batch_item_bytes(e, shape));
+		if ((rc = ensure_batch_scratch(e, rows, shape))) return rc;
+		ops.clear();
+		cands.clear();
+		cand_of.resize(rows * N);
+		for (size_t r = 0; r < rows; r++) {
+			const int32_t i = live[first + r];
+			build_spr_row(e, (int)r, prune ? prune[i] : i, &ops, &cands, cand_of.data() + r * N);
+		}
+		HIP_TRY(hipMemcpyAsync(e->d_batch_item_ops, ops.data(), sizeof(BatchOp) * ops.size(), hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_spr_cands, cands.data(), sizeof(SprCand) * cands.size(), hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_spr_cand_of, cand_of.data(), sizeof(int32_t) * cand_of.size(), hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_spr_len, lengths.data(), sizeof(double) * lengths.size(), hipMemcpyHostToDevice, e->stream));
+		const size_t total = (size_t)2 * N * C * 16;  // the engine's lengths, then their halves
+		hipLaunchKernelGGL(k_batch_matrices, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, e->stream, C, N, 2, e->d_model, e->d_rates,
+		                   e->d_spr_len.get(), e->root, (const int32_t *)nullptr, e->d_spr_mats.get());
+		const double *mats = e->d_spr_mats.get(), *half = mats + (size_t)N * C * 16;
+		const SprWalkArgs walk{e->d_batch_item_ops.get(), T, N, e->P, C, nblk, e->d_tipmask, mats, e->d_batch_lower, e->d_batch_upper};
+		hipLaunchKernelGGL(k_spr_walk4, dim3(nblk, (unsigned)rows), dim3(WAVE, C), 0, e->stream, walk);
+		for (size_t c0 = 0; c0 < cands.size(); c0 += BATCH_MAX_CHUNK) {  // (gridDim.y)
+			const size_t n = std::min<size_t>(cands.size() - c0, BATCH_MAX_CHUNK);
+			const SprArgs a{e->d_spr_cands.get() + c0, T, N, e->P, C, nblk, e->d_tipmask, e->d_freqs, e->d_props, e->d_weights, mats, half, e->d_batch_lower, e->d_batch_upper,
+			                e->d_spr_slab.get() + c0 * nblk};
+			hipLaunchKernelGGL(k_spr4, dim3(nblk, (unsigned)n), dim3(WAVE, C), 0, e->stream, a);
+		}
+		const size_t cells = rows * N;
+		hipLaunchKernelGGL(k_spr_finish, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, e->stream, cells, nblk, e->d_spr_cand_of.get(), e->d_spr_slab.get(),
+		                   e->d_spr_out.get());
+		HIP_TRY(hipGetLastError());
+		out.resize(cells);
+		HIP_TRY(hipMemcpyAsync(out.data(), e->d_spr_out, sizeof(double) * cells, hipMemcpyDeviceToHost, e->stream));
+		HIP_TRY(hipStreamSynchronize(e->stream));  // (also covers the lists, which the next chunk builds anew)
+		for (size_t r = 0; r < rows; r++) std::copy(out.begin() + r * N, out.begin() + (r + 1) * N, lnl + (size_t)live[first + r] * N);
+		prof.chunks++;
+		prof.candidates += (int64_t)cands.size();
+		first += rows;
+	}
+	return PHYAMD_OK;
+}
+
+int shard_spr_log_likelihoods(Shard *e, int flags, int32_t count, const int32_t *prune, double *lnl) {
+	CHECK_ENGINE(e);
+	if (count < 1) return fail(PHYAMD_EINVAL, "phyamd_spr_log_likelihoods: count must be >= 1 (got %d)", count);
+	if (!lnl) return fail(PHYAMD_EINVAL, "phyamd_spr_log_likelihoods: null lnl");
+	const auto t0 = std::chrono::steady_clock::now();
+	int rc;
+	if ((rc = bind_device(e))) return rc;
+	phyamd_spr_profile prof{};
+	rc = run_spr(e, flags, count, prune, lnl, prof);
+	prof.scratch_bytes = (int64_t)batch_scratch_bytes(e);
+	prof.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	e->spr_prof = prof;
+	return rc;
+}
+
+int shard_get_spr_profile(Shard *e, phyamd_spr_profile *out) {
+	CHECK_ENGINE(e);
+	if (!out) return fail(PHYAMD_EINVAL, "null out");
+	*out = e->spr_prof;
 	return PHYAMD_OK;
 }

@@ -266,6 +266,29 @@ class Engine:
         self._check(self._lib.phyamd_get_nni_profile(self._h, C.byref(p)))
         return {k: getattr(p, k) for k, _ in p._fields_}
 
+    def spr_log_likelihoods(self, prune=None, flags=0):
+        """Every SPR regraft of the prune nodes' subtrees at once: lnl [count, N].  Row i prunes node prune[i] (None: every node, row
+        i is node i); column w regrafts it onto the edge above w: with u the prune node's parent and s its sibling, s takes u's
+        place under u's parent with length t_s + t_u, u takes w's place under w's parent and gets w where s was, and both halves
+        of the graft edge get 0.5 t_w.  NaN where w is the root, u, s, the prune node or one of its descendants, and in the whole
+        row of the root and of its children (re-root to reach those moves).  lnL only: the best few go to gradient_batch_trees.
+        The engine's tree, lengths and partials stay.  No fallback: EngineError where gradient_batch_trees refuses."""
+        pr = None
+        if prune is not None:
+            pr = np.ascontiguousarray(prune, dtype=np.int32)
+            if pr.ndim != 1:
+                raise ValueError(f"prune must be one-dimensional (got {pr.shape})")
+        count = self.N if pr is None else len(pr)
+        lnl = np.empty((count, self.N))
+        self._check(self._lib.phyamd_spr_log_likelihoods(self._h, flags, count, None if pr is None else _ptr(pr), _ptr(lnl)))
+        return lnl
+
+    def spr_profile(self):
+        """Of the last spr_log_likelihoods: prunes (rows), chunks, candidates, scratch_bytes, ms."""
+        p = _lib.SprProfile()
+        self._check(self._lib.phyamd_get_spr_profile(self._h, C.byref(p)))
+        return {k: getattr(p, k) for k, _ in p._fields_}
+
     def store(self):
         """Remember the current (evaluated) state: parameters, lnL and partials (MCMC store)."""
         self._check(self._lib.phyamd_store(self._h))
