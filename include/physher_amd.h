@@ -349,6 +349,14 @@ int phyamd_get_pattern_log_likelihoods(phyamd_engine *e, double *out /* [P] */);
  * [C][P][S]. Upper partials exist only after phyamd_gradient with keep_partials enabled. */
 int phyamd_get_partials(phyamd_engine *e, int node, int upper, double *out);
 int phyamd_get_node_matrices(phyamd_engine *e, int node, int derivative, double *out /* [C][S][S] */);
+/* The post-order walk of a tree as the streamed 4-state kernel runs it, from the host schedule alone (no device, no engine): the
+ * ops in launch order -- the cut subtrees' chunks, then the top part -- eight ints each: chunk | node | left | right | where the
+ * left child's partial comes from | the right child's (-1: not a stored child, 0: memory, 1: the op in front, 2: the wave's first
+ * park slot, 3: its second) | bit 0 / 1: the result is kept in the first / second slot | bit 0 / 1: the left / right child is the
+ * root of a cut subtree (written by another workgroup).  second_slot = 0: the schedule of PHYAMD_LOWER_PARK2=0.  Returns the
+ * number of ops (at most `capacity` of them are written) or a negative PHYAMD_E* code. */
+int phyamd_post_order_parks(int32_t tip_count, const int32_t *left /* [2T-1] */, const int32_t *right, int32_t root, int32_t second_slot,
+                            int32_t *out /* [capacity][8] */, int32_t capacity);
 int phyamd_is_rescaling(phyamd_engine *e);
 /* SingleTreeLikelihood_use_rescaling (treelikelihood.c:1410-1423) after construction: PHYAMD_RESCALE_ALWAYS / _NEVER switch
  * at once (the next evaluation recomputes every node), PHYAMD_RESCALE_AUTO keeps the current state and re-arms the lazy switch. */

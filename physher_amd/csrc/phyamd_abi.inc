@@ -653,6 +653,43 @@ int phyamd_get_node_matrices(phyamd_engine *g, int node, int derivative, double 
 	return shard_get_node_matrices(g->shards[0], node, derivative, out);
 }
 
+// the post-order walk's chunked op list of a tree as the streamed walk runs it: host code only (no device, no engine)
+int phyamd_post_order_parks(int32_t tip_count, const int32_t *left, const int32_t *right, int32_t root, int32_t second_slot, int32_t *out, int32_t capacity) {
+	if (tip_count < 2) return fail(PHYAMD_EINVAL, "tip_count must be >= 2 (got %d)", tip_count);
+	if (!left || !right) return fail(PHYAMD_EINVAL, "null left or right");
+	if (capacity < 0 || (capacity > 0 && !out)) return fail(PHYAMD_EINVAL, "null out with capacity %d", capacity);
+	std::unique_ptr<Shard> e(new Shard());
+	e->T = tip_count;
+	e->N = 2 * e->T - 1;
+	e->S = 4;
+	e->C = 1;
+	e->P = e->Ptot = 1;
+	e->root = root;
+	e->left.assign(left, left + e->N);
+	e->right.assign(right, right + e->N);
+	e->lower_park2_on = second_slot != 0;
+	int rc;
+	if ((rc = build_schedule(e.get()))) return rc;
+	const std::vector<NodeOp> &ops = e->walk_lower_chunk_ops;
+	const std::vector<int> &off = e->walk_lower_chunk_off;
+	std::vector<char> is_cut_root(e->N, 0);  // the roots of the cut subtrees: every chunk's last op but the top part's
+	for (size_t k = 1; k + 1 < off.size(); k++)
+		if (off[k] > off[k - 1]) is_cut_root[ops[off[k] - 1].parent] = 1;
+	int chunk = 0;
+	for (int i = 0; i < (int)ops.size() && i < capacity; i++) {
+		const NodeOp &o = ops[i];
+		while (i >= off[chunk + 1]) chunk++;
+		auto source = [&](int side) {
+			if ((side ? o.kind_right : o.kind_left) != CH_CORE) return -1;
+			return o.carry_in == side + 1 ? 1 : (o.lds_park & (1 << side)) ? 2 : (o.lds_park & (0x10 << side)) ? 3 : 0;
+		};
+		const int32_t rec[8] = {chunk, o.parent, o.left, o.right, source(0), source(1), ((o.lds_park & 4) ? 1 : 0) | ((o.lds_park & 0x40) ? 2 : 0),
+		                        (is_cut_root[o.left] ? 1 : 0) | (is_cut_root[o.right] ? 2 : 0)};
+		std::memcpy(out + (size_t)i * 8, rec, sizeof(rec));
+	}
+	return (int)ops.size();
+}
+
 int phyamd_is_rescaling(phyamd_engine *g) {
 	CHECK_GROUP(g);
 	int any = 0;  // shards switch on their own lnL (the lazy switch is per shard: the sum does not depend on who rescales)

@@ -44,6 +44,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -110,6 +111,8 @@ struct NodeOp {
 	// tree) can wait in the wave's LDS slot instead of HBM.  bit 0: the parent's upper is read from LDS; bit 1 / 2: the left /
 	// right child's upper is parked in LDS.  The HBM slot stays assigned (the rescaling and parameter variants use it).
 	// (bit 3 is no longer set by the host; k_lower4_walk still tests it)
+	// lower walk: bit 0 / 1: the left / right child comes from the wave's park slot, bit 2: the result is kept there; the streamed
+	// walk's second slot: bit 4 / 5 and bit 6 (build_schedule)
 	int32_t lds_park;
 };
 

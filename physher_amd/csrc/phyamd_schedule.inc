@@ -138,7 +138,10 @@ void build_walk_chunks(Shard *e) {
 
 // The same for the post-order walk: cut subtrees first (second index of the launch = subtree), then the top part, which reads a cut
 // subtree's root like any stored child.  Carries follow the op actually in front of an op in its chunk, and an op next to a cut
-// gives up the LDS copy of its other child.  walk_lower_chunk_ops: [subtree 1 | subtree 2 | ... | top], offsets in walk_lower_chunk_off.
+// gives up its parks (both slots) together with their writers' bits: a cut child was parked by another workgroup, and the other
+// child of such an op is either cut as well or the op in front of it in the top part, i.e. carried -- no park is lost that could
+// have been kept, and a park that survives has its writer and its reader in one chunk.
+// walk_lower_chunk_ops: [subtree 1 | subtree 2 | ... | top], offsets in walk_lower_chunk_off.
 void build_lower_walk_chunks(Shard *e) {
 	const std::vector<NodeOp> &src = e->walk_lower_ops;
 	const int n = (int)src.size(), N = e->N;
@@ -165,13 +168,14 @@ void build_lower_walk_chunks(Shard *e) {
 		}
 	}
 	std::vector<NodeOp> out;
-	std::vector<int> off{0}, cuts;
+	std::vector<int> off{0}, cuts, at(n, -1);  // at: op of the source list -> its place in `out`
 	for (int j = 0; j < n; j++)
 		if (cut[j]) cuts.push_back(j);
 	std::stable_sort(cuts.begin(), cuts.end(), [&](int a, int b) { return size[a] > size[b]; });  // longest first
 	for (int j : cuts) {
 		for (int i = j - size[j] + 1; i <= j; i++) {
 			in_cut[i] = 1;
+			at[i] = (int)out.size();
 			out.push_back(src[i]);
 		}
 		out[off.back()].carry_in = 0;  // (a subtree's first op has two unstored children anyway)
@@ -184,7 +188,15 @@ void build_lower_walk_chunks(Shard *e) {
 		const int jl = opi[op.left], jr = opi[op.right];
 		const bool next_to_cut = (jl >= 0 && cut[jl]) || (jr >= 0 && cut[jr]);
 		op.carry_in = prev >= 0 && prev == op.left ? 1 : prev >= 0 && prev == op.right ? 2 : 0;
-		if (next_to_cut) op.lds_park &= ~3;
+		if (next_to_cut) {
+			for (int side = 0; side < 2; side++) {
+				const int j = side ? jr : jl;
+				if (op.lds_park & (side ? 2 : 1)) out[at[j]].lds_park &= ~4;
+				if (op.lds_park & (side ? 0x20 : 0x10)) out[at[j]].lds_park &= ~0x40;
+			}
+			op.lds_park &= ~0x33;
+		}
+		at[i] = (int)out.size();
 		out.push_back(op);
 		prev = op.parent;
 	}
@@ -469,19 +481,21 @@ void build_lower_stream_ops(Shard *e) {
 			} else if (kinds[side] == CH_CHERRY_TIP)
 				m[4] = moff(a[3]);
 			if (kinds[side] != CH_CORE) continue;
-			// where a stored child comes from: the previous op's registers, the parked partial, or memory
+			// where a stored child comes from: the previous op's registers, one of the two parked partials, or memory
 			const int ch = side ? u.rnode : u.lnode;
 			const bool is_left = ch == o.left;  // of the post-order op (the pre-order op may have swapped its children)
 			int src = 0;
 			if (o.carry_in == (is_left ? 1 : 2)) src = 1;
 			else if (o.lds_park & (is_left ? 1 : 2)) src = 2;
-			else {
+			else if (o.lds_park & (is_left ? 0x10 : 0x20)) src = 3;
+			if (src == 0 || src == 3) {  // (3: for the instantiations that have one slot, lstream_park_slots; the others fetch nothing)
 				(side ? d.mem_r : d.mem_l) = (int64_t)e->core_index[ch] * array_bytes;
 				(side ? d.ls_r : d.ls_l) = (int64_t)e->core_index[ch] * e->P * 8;
 			}
 			fl |= src << (6 + 2 * side);
 		}
 		if (o.lds_park & 4) fl |= 1 << 10;
+		if (o.lds_park & 0x40) fl |= 1 << 26;
 		pieces[i] = (kinds[0] != CH_CORE ? 1 : 0) | (kinds[1] != CH_CORE ? 2 : 0);
 		d.flags = fl;
 	}
@@ -695,13 +709,18 @@ int build_schedule(Shard *e) {
 			int node, stage;
 		};
 		// two_core[n]: the subtree of n holds a node with two stored children, i.e. walking it re-reads a stored partial
+		// lparks[n]: the largest number of stored partials that wait at one time while the subtree of n is walked (the first-walked
+		// child of a node with two stored children waits while the second one's subtree is walked); two_core[n] = lparks[n] > 0
 		std::vector<uint8_t> two_core(N, 0);
+		std::vector<int> lparks(N, 0);
 		for (int i = N - 1; i >= 0; i--) {
 			const int n = order[i];
 			if (kind[n] != CH_CORE) continue;
 			const int l = e->left[n], r = e->right[n];
 			const bool lo = kind[l] == CH_CORE, ro = kind[r] == CH_CORE;
 			two_core[n] = (lo && ro) || (lo && two_core[l]) || (ro && two_core[r]);
+			if (lo && ro) lparks[n] = csize[l] >= csize[r] ? std::max(lparks[l], 1 + lparks[r]) : std::max(lparks[r], 1 + lparks[l]);
+			else lparks[n] = lo ? lparks[l] : ro ? lparks[r] : 0;
 		}
 		std::vector<int> lower_op_of(N, -1);
 		std::vector<Frame> st{{e->root, 0}};
@@ -726,10 +745,18 @@ int build_schedule(Shard *e) {
 				// Both children stored: the second one arrives in registers, the first was written a subtree ago.  If walking the
 				// second's subtree re-reads nothing itself, the first can also wait in the wave's LDS slot (it is still stored for
 				// the pre-order pass): bit 2 on the child's op = keep a copy in LDS, bit 0 / 1 here = left / right child from LDS.
+				// Second tier (the streamed walk only; the pre-order walk's in_lds2 rule): if every wait inside the second's subtree is
+				// of that kind, i.e. at most one of them is held at a time, the first waits in the wave's second slot: bit 0x40 on the
+				// child's op = keep a copy there, bit 0x10 / 0x20 here = left / right child from it.  No slot then ever holds two values.
 				op.lds_park = 0;
-				if (kind[first] == CH_CORE && kind[second] == CH_CORE && !two_core[second] && lower_op_of[first] >= 0) {
-					e->walk_lower_ops[lower_op_of[first]].lds_park |= 4;
-					op.lds_park |= first == l ? 1 : 2;
+				if (kind[first] == CH_CORE && kind[second] == CH_CORE && lower_op_of[first] >= 0) {
+					if (!two_core[second]) {
+						e->walk_lower_ops[lower_op_of[first]].lds_park |= 4;
+						op.lds_park |= first == l ? 1 : 2;
+					} else if (e->lower_park2_on && lparks[second] == 1) {
+						e->walk_lower_ops[lower_op_of[first]].lds_park |= 0x40;
+						op.lds_park |= first == l ? 0x10 : 0x20;
+					}
 				}
 				lower_op_of[n] = (int)e->walk_lower_ops.size();
 				e->walk_lower_ops.push_back(op);

@@ -672,7 +672,8 @@ __global__ __launch_bounds__(STREAM_WAVES *WAVE, (SCALE || AMBIG) ? STREAM_MIN_W
 // product), so the requests for op i + 1 leave at the TOP of op i and nothing in the common path is a load the compiler tracks
 // (one tracked load and its conservative s_waitcnt vmcnt(0) would land behind the requests and serialise every op):
 //   * table block and mask words: LDS-DMA into two-deep rings (the words as one dword per lane);
-//   * the wave's parked partial stays in registers (at most one is parked at a time);
+//   * the wave's parked partials stay in registers: two slots, the first for a wait that holds no other, the second for a wait
+//     that holds waits of the first kind only (build_schedule); a deeper nesting goes through memory;
 //   * an op's result is stored at the top of the next op, AFTER that op's requests: the wait at the top of an op then leaves
 //     the two store instructions in flight (vmcnt(2)) instead of waiting for the write to be acknowledged;
 //   * a stored child that is neither the previous op's result nor parked (next to a cut subtree: a handful per walk) is an ordinary
@@ -681,9 +682,10 @@ __global__ __launch_bounds__(STREAM_WAVES *WAVE, (SCALE || AMBIG) ? STREAM_MIN_W
 // cache and L2), no workgroup-level synchronisation; the root's sum over categories is k_root_finish64's.
 struct LowerDesc {
 	int32_t flags;     // kl 0-2 | kr 3-5 | where a stored left child comes from 6-7 (0: memory, 1: the previous op's result, 2: the parked
-	                   // partial) | same for the right child 8-9 | 10: park the result | 11: no store (no longer set) | 12-13: ring slot of
-	                   // the first mask row to request for the NEXT op | 14-15: how many rows to request for it (0..2: the rows it reads that
-	                   // no op before it has read) | half kinds 16-23 | 24 / 25: the next op's block needs its second / first piece
+	                   // partial, 3: the one in the second slot) | same for the right child 8-9 | 10: park the result | 11: no store (no
+	                   // longer set) | 12-13: ring slot of the first mask row to request for the NEXT op | 14-15: how many rows to request
+	                   // for it (0..2: the rows it reads that no op before it has read) | half kinds 16-23 | 24 / 25: the next op's block
+	                   // needs its second / first piece | 26: park the result in the second slot
 	int32_t nx_block;  // table block of the next op
 	int32_t lnode, rnode, lm[5], rm[5];  // matrices by byte offset, as in StreamDesc
 	int64_t nx_words;  // byte offset of the first mask row to request for the next op (the post-order walk's own stream)
@@ -701,6 +703,10 @@ struct LowerChunk {  // what the first op of a chunk wants requested before the 
 };
 
 constexpr int LSTREAM_MIN_WAVES = 5;  // (29 KB of LDS per workgroup allow five workgroups per CU: 96 registers)
+// Park slots of an instantiation: the second one is eight more registers, which the AMBIG instantiations do not have at five
+// workgroups per CU (they would spill); those read a second-slot child from memory like the one-slot schedule does -- the
+// descriptor keeps its offsets (build_lower_stream_ops).
+constexpr int lstream_park_slots(bool ambig) { return ambig ? 1 : 2; }
 constexpr int LSTREAM_LDS_PER_WAVE = 2 * OPBLK_BYTES + 5 * WAVE * 4 + WAVE * 32;  // two table blocks, a ring of four mask rows + a scratch row, the store staging area
 
 __device__ __forceinline__ void dma_dword(const char *gsrc, lds_cptr dst) {  // one dword per lane -> LDS base + 4 * lane
@@ -725,7 +731,7 @@ __global__ __launch_bounds__(STREAM_WAVES *WAVE, SCALE == 1 ? 4 : LSTREAM_MIN_WA
     const double *__restrict__ freqs, const double *__restrict__ props, double *__restrict__ Lc, int with_root, double *__restrict__ lscale, int xcd_map,
     int *__restrict__ Ec) {
 	extern __shared__ double sh[];
-	constexpr bool XCH = SCALE == 1, EXP2 = SCALE == 2;
+	constexpr bool XCH = SCALE == 1, EXP2 = SCALE == 2, PARK2 = lstream_park_slots(AMBIG) > 1;
 	const int lane = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(threadIdx.y);
 	const unsigned vx = XCH ? blockIdx.x : xcd_position(blockIdx.x, gridDim.x, xcd_map);
 	const int c = XCH ? wv : vx % C, blk = XCH ? (int)blockIdx.x : (int)(vx / C) * STREAM_WAVES + wv;
@@ -781,9 +787,9 @@ __global__ __launch_bounds__(STREAM_WAVES *WAVE, SCALE == 1 ? 4 : LSTREAM_MIN_WA
 		if (valid_lo) __builtin_nontemporal_store(lo, reinterpret_cast<dv2 *>(dst));
 		if (valid_hi) __builtin_nontemporal_store(hi, reinterpret_cast<dv2 *>(dst + 1024));
 	};
-	d4 carry = d4{1., 1., 1., 1.}, parked = carry;
-	double sfc = 0.0, sfp = 0.0;  // SCALE == 1: cumulative log factors of the carried / parked partial
-	int efc = 0, efp = 0;         // SCALE == 2: ... cumulative binary exponents
+	d4 carry = d4{1., 1., 1., 1.}, parked = carry, parked2 = carry;
+	double sfc = 0.0, sfp = 0.0, sfp2 = 0.0;  // SCALE == 1: cumulative log factors of the carried / parked partials
+	int efc = 0, efp = 0, efp2 = 0;           // SCALE == 2: ... cumulative binary exponents
 	double *const xbase = sh + (size_t)blockDim.y * (LSTREAM_LDS_PER_WAVE / 8);  // SCALE == 1: [2][C][64] maxima
 	char *const lscale_k = XCH ? reinterpret_cast<char *>(lscale) + (size_t)k * 8 : nullptr;
 	// SCALE == 2: this category's exponents; a descriptor's ls_* (byte offset of [stored][P] doubles) x C / 2 = that of [stored][C][P] ints
@@ -807,7 +813,8 @@ __global__ __launch_bounds__(STREAM_WAVES *WAVE, SCALE == 1 ? 4 : LSTREAM_MIN_WA
 		else if (EXP2 || (XCH && c == 0)) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");  // (+ the factor's store)
 		else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
 		const int fl = op.flags;
-		const int kl = fl & 7, kr = (fl >> 3) & 7, sl = (fl >> 6) & 3, sr = (fl >> 8) & 3, nxw = (fl >> 14) & 3;
+		const int kl = fl & 7, kr = (fl >> 3) & 7, nxw = (fl >> 14) & 3;
+		const int sl = !PARK2 && ((fl >> 6) & 3) == 3 ? 0 : (fl >> 6) & 3, sr = !PARK2 && ((fl >> 8) & 3) == 3 ? 0 : (fl >> 8) & 3;
 		x.tb = blocks + (i & 1) * OPBLK_BYTES;
 		// this op's mask groups, from the ring slots of their rows
 		const unsigned w0 = *(const __attribute__((address_space(3))) unsigned *)(wrows + ((op.wsh >> 10) & 3) * (WAVE * 4) + lane * 4) >> (op.wsh & 31);
@@ -828,28 +835,28 @@ __global__ __launch_bounds__(STREAM_WAVES *WAVE, SCALE == 1 ? 4 : LSTREAM_MIN_WA
 		double sf_in = 0.0;  // SCALE == 1: the stored children's cumulative factors
 		int ef_in = 0;       // SCALE == 2
 		if (kl == CH_CORE) {
-			d4 src = sl == 1 ? carry : parked;
+			d4 src = sl == 1 ? carry : sl == 3 ? parked2 : parked;
 			if (sl == 0) {  // from memory (next to a cut subtree): this op pays the round trip
 				src = load4(reinterpret_cast<const double *>(lower_c + op.mem_l + poff));
 				if (XCH) sf_in += *reinterpret_cast<const double *>(lscale_k + op.ls_l);
 				if (EXP2) ef_in += *exp_at(op.ls_l);
 				stored = false;
-			} else if (XCH) sf_in += sl == 1 ? sfc : sfp;
-			else if (EXP2) ef_in += sl == 1 ? efc : efp;
+			} else if (XCH) sf_in += sl == 1 ? sfc : sl == 3 ? sfp2 : sfp;
+			else if (EXP2) ef_in += sl == 1 ? efc : sl == 3 ? efp2 : efp;
 			bl = TF ? src : matvec4_opt<false>(x.M(op.lnode), src);
 		} else if (kl == CH_TIP) bl = x.site_tip<0, 0>(wL);
 		else if (kl == CH_DEEP)
 			bl = matvec4_opt<false>(x.M(op.lnode), mul4(s_half<0, 0>(x, (fl >> 16) & 3, op.lm[0], op.lm[1], wL), s_half<0, 3>(x, (fl >> 18) & 3, op.lm[2], op.lm[3], wL)));
 		else bl = s_fringe_message<0, false>(x, kl, op.lnode, op.lm[4], wL, bn);
 		if (kr == CH_CORE) {
-			d4 src = sr == 1 ? carry : parked;
+			d4 src = sr == 1 ? carry : sr == 3 ? parked2 : parked;
 			if (sr == 0) {
 				src = load4(reinterpret_cast<const double *>(lower_c + op.mem_r + poff));
 				if (XCH) sf_in += *reinterpret_cast<const double *>(lscale_k + op.ls_r);
 				if (EXP2) ef_in += *exp_at(op.ls_r);
 				stored = false;
-			} else if (XCH) sf_in += sr == 1 ? sfc : sfp;
-			else if (EXP2) ef_in += sr == 1 ? efc : efp;
+			} else if (XCH) sf_in += sr == 1 ? sfc : sr == 3 ? sfp2 : sfp;
+			else if (EXP2) ef_in += sr == 1 ? efc : sr == 3 ? efp2 : efp;
 			br = TF ? src : matvec4_opt<false>(x.M(op.rnode), src);
 		} else if (kr == CH_TIP) br = x.site_tip<1, 0>(wR);
 		else if (kr == CH_DEEP)
@@ -874,6 +881,11 @@ __global__ __launch_bounds__(STREAM_WAVES *WAVE, SCALE == 1 ? 4 : LSTREAM_MIN_WA
 			parked = carry;
 			sfp = sfc;
 			efp = efc;
+		}
+		if (PARK2 && (fl & (1 << 26))) {
+			parked2 = carry;
+			sfp2 = sfc;
+			efp2 = efc;
 		}
 		have_prev = !(fl & (1 << 11));  // (the host no longer sets bit 11)
 		prev_store = op.store;
