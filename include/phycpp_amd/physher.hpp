@@ -302,6 +302,17 @@ class TreeLikelihoodInterface : public CallableModelInterface {
 	// prune[i] (null: count = 2T-1 and row i is node i), column w the target edge; NaN where there is no candidate.  Lengths are
 	// the engine's branch lengths, as for NNILogLikelihoods.  The tree model and this object's own state are unchanged.
 	void SPRLogLikelihoods(const int *prune, int count, double *out);
+	// Beyond the reference surface: marginal ancestral reconstruction of `count` nodes of the tree model's tree at once (one
+	// phyamd_state_posteriors call; see include/physher_amd.h for the definition): posteriors [count][patterns][states] and states
+	// [count][patterns] by the tree's node ids, row i the node nodes[i] (null: count = 2T-1 and row i is node i; tips and the
+	// root included), patterns in this object's pattern order.  Either output may be null.  The engine behind this object keeps
+	// every partial resident from here on; the tree model is unchanged.
+	void StatePosteriors(const int *nodes, int count, double *posteriors, unsigned char *states);
+	// Beyond the reference surface: the posterior of each pattern's rate category, posteriors [patterns][categories], and its mean
+	// rate, meanRates [patterns] or null (one phyamd_site_rate_posteriors call).
+	void SiteRatePosteriors(double *posteriors, double *meanRates);
+	size_t StateCount() const;
+	size_t CategoryCount() const;
 	size_t NodeCount() const;  // 2T - 1
 	size_t TreeParameterCount() const { return treeModel_->parameterCount_; }  // n of treeParameters [count][n]
 	size_t GetPatternCount() const;

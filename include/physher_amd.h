@@ -341,6 +341,44 @@ int phyamd_spr_log_likelihoods(phyamd_engine *e, int flags, int32_t count, const
  * over the shards */
 typedef struct { int32_t prunes, chunks; int64_t candidates, scratch_bytes; double ms; } phyamd_spr_profile;
 int phyamd_get_spr_profile(phyamd_engine *e, phyamd_spr_profile *out);
+/* The marginal posterior of the state at a node, per site pattern, and its argmax -- the reconstructed ancestral sequence:
+ * asr_marginal / _marginal_reconstruction (asr.c:28-134) for `count` nodes at once, on the device, from the lower and the upper
+ * partial that meet on each node's branch (the pair phyamd_branch_log_likelihood reads).  With p_n the lower partial of node n (a
+ * tip: its 0/1 mask), u_n its upper partial in phyamd_get_partials' convention, P_{n,c} the matrices of its branch as the engine
+ * holds them (explicit node matrices included), pi the frequencies and w_c the proportions, per pattern k and state j
+ *   n != root:  J[n][k][j] = sum_c w_c p_n[c][k][j] sum_i pi_i u_n[c][k][i] P_{n,c}[i][j]
+ *   n == root:  J[n][k][j] = sum_c w_c pi_j p_root[c][k][j]
+ *   posteriors[n][k][j] = J[n][k][j] / sum_j' J[n][k][j'],   states[n][k] = the smallest j with the largest J (asr.c:73-86)
+ * -- the site likelihood with node n held in state j: sum_j J[n][k][j] = L_k at every node, so a per-pattern factor of a rescaled
+ * evaluation cancels in the quotient and the call serves every rescaling policy.  Every state count.
+ * nodes [count]: any ids in 0..2T-2, duplicates allowed; NULL: count must be 2T-1 and row i is node i.  Tips are rows like any
+ * other: one-hot where the tip is observed, the imputed state where it has a gap or an ambiguity code.  posteriors
+ * [count][P][S] and states [count][P]: either may be NULL (not both).  flags: 0 (others reserved, refused).
+ * The call evaluates whatever is pending and needs every partial resident: if phyamd_set_keep_partials is off it is turned on
+ * (as phyamd_parameter_gradient does for 20 / 60 / 61 states), and if no resident upper partials belong to the current inputs the
+ * flags-0 gradient runs.  Afterwards the engine is an engine with phyamd_set_keep_partials(1) that has run phyamd_gradient,
+ * and nothing else about it has changed: later evaluations return the bits such an engine returns.  Upper partials that a
+ * PHYAMD_GRAD_FOLD_ROOT_FREQS keep-partials gradient left resident are used as they are (pi is inside them).
+ * A NaN / inf lnL of the evaluation is reported in band: NaN posteriors, state 255.  A row depends on its node and the engine's
+ * inputs only -- not on count, its position, or the chunks the rows ran in (the staging of a chunk is sized to the memory cap, at
+ * least one row), bit for bit; two calls return identical bits.  Sharded handles: every shard fills its own pattern range, so a
+ * pattern's bits do not depend on the shard count.
+ * PHYAMD_EUNSUPPORTED: tiled patterns.  PHYAMD_EINVAL: null engine, flags other than 0,
+ * both outputs NULL, count < 1, nodes == NULL with another count than 2T-1, an id outside 0..2T-2 (with its index in the
+ * message); an engine that is not ready (data, models, weights, topology) reports what is missing. */
+int phyamd_state_posteriors(phyamd_engine *e, int flags, int32_t count, const int32_t *nodes /* [count] or NULL */,
+                            double *posteriors /* [count][P][S] or NULL */, uint8_t *states /* [count][P] or NULL */);
+/* The posterior of the rate category of each site pattern and its mean rate: SingleTreeLikelihood_posterior_sites
+ * (ppsites.c:17-43, 100),
+ *   posteriors[k][c] = w_c sum_i pi_i p_root[c][k][i] / sum_c' (the same),   mean_rates[k] = sum_c posteriors[k][c] r_c
+ * with r_c the engine's category rates.  The quotient is taken over the categories' own sum instead of exp(lnL_k): identical
+ * without rescaling, and the only one of the two defined with it.  Every state count and rescaling policy; an invariant class is
+ * a category like any other.  Whatever is pending is evaluated by a post-order pass; the call reads the root's stored partial, as
+ * phyamd_root_frequency_term does, and leaves the engine as that pass leaves it: later evaluations return the bits they would
+ * have returned without the call (a rescaling engine's stored partials are settled in the reference's form first, as by
+ * phyamd_root_frequency_term).  mean_rates may be NULL.  PHYAMD_EUNSUPPORTED: tiled patterns.  Sharded handles: every shard
+ * fills its own pattern range. */
+int phyamd_site_rate_posteriors(phyamd_engine *e, double *posteriors /* [P][C] */, double *mean_rates /* [P] or NULL */);
 int phyamd_synchronize(phyamd_engine *e);
 
 /* --- inspection (parity tests, debugging) --- */

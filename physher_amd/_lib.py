@@ -91,6 +91,8 @@ SYMBOLS = [
     ("phyamd_get_nni_profile", C.c_int, [_P, C.POINTER(NniProfile)]),
     ("phyamd_spr_log_likelihoods", C.c_int, [_P, C.c_int, C.c_int32, _P, _P]),
     ("phyamd_get_spr_profile", C.c_int, [_P, C.POINTER(SprProfile)]),
+    ("phyamd_state_posteriors", C.c_int, [_P, C.c_int, C.c_int32, _P, _P, _P]),
+    ("phyamd_site_rate_posteriors", C.c_int, [_P, _P, _P]),
     ("phyamd_synchronize", C.c_int, [_P]),
     ("phyamd_get_pattern_log_likelihoods", C.c_int, [_P, _P]),
     ("phyamd_get_partials", C.c_int, [_P, C.c_int, C.c_int, _P]),

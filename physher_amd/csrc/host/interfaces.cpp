@@ -919,3 +919,27 @@ void TreeLikelihoodInterface::SPRLogLikelihoods(const int *prune, int count, dou
 	Sync();
 	phyamd::check(phyamd_spr_log_likelihoods(impl_->engine, 0, count, prune, out));
 }
+
+size_t TreeLikelihoodInterface::StateCount() const { return (size_t)impl_->S; }
+size_t TreeLikelihoodInterface::CategoryCount() const { return (size_t)siteModel_->GetModel()->cat_count; }
+
+void TreeLikelihoodInterface::StatePosteriors(const int *nodes, int count, double *posteriors, unsigned char *states) {
+	if (!posteriors && !states) throw Error("null posteriors and states");
+	Sync();
+	auto &I = *impl_;
+	if (!posteriors || I.Sp == I.S) {
+		phyamd::check(phyamd_state_posteriors(I.engine, 0, count, nodes, posteriors, states));
+		return;
+	}
+	// a padded state space: the engine's rows are [Sp] wide, the padding states carry no probability
+	const size_t cells = (size_t)std::max(count, 0) * GetPatternCount();
+	std::vector<double> wide(cells * (size_t)I.Sp);
+	phyamd::check(phyamd_state_posteriors(I.engine, 0, count, nodes, wide.data(), states));
+	for (size_t i = 0; i < cells; i++) std::copy(wide.begin() + i * I.Sp, wide.begin() + i * I.Sp + I.S, posteriors + i * I.S);
+}
+
+void TreeLikelihoodInterface::SiteRatePosteriors(double *posteriors, double *meanRates) {
+	if (!posteriors) throw Error("null posteriors");
+	Sync();
+	phyamd::check(phyamd_site_rate_posteriors(impl_->engine, posteriors, meanRates));
+}

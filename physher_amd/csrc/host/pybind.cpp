@@ -249,6 +249,24 @@ PYBIND11_MODULE(_phycpp_amd, m) {
 		    self.SPRLogLikelihoods(prune ? prune->data() : nullptr, (int)count, lnl.data());
 		    return darray({count, N}, lnl.data());
 	    }, py::arg("prune") = py::none())
+	    .def("state_posteriors", [](TreeLikelihoodInterface &self, std::optional<iarray> nodes, bool want_posteriors, bool want_states) -> py::tuple {
+		    const py::ssize_t N = (py::ssize_t)self.NodeCount(), P = (py::ssize_t)self.GetPatternCount(), S = (py::ssize_t)self.StateCount();
+		    if (nodes && nodes->ndim() != 1) throw phyamd::Error("nodes: [count]");
+		    const py::ssize_t count = nodes ? nodes->shape(0) : N;
+		    std::vector<double> post(want_posteriors ? (size_t)(count * P * S) : 0);
+		    std::vector<unsigned char> states(want_states ? (size_t)(count * P) : 0);
+		    self.StatePosteriors(nodes ? nodes->data() : nullptr, (int)count, want_posteriors ? post.data() : nullptr, want_states ? states.data() : nullptr);
+		    py::object a = py::none(), b = py::none();
+		    if (want_posteriors) a = darray({count, P, S}, post.data());
+		    if (want_states) b = py::array_t<unsigned char>({count, P}, states.data());
+		    return py::make_tuple(a, b);
+	    }, py::arg("nodes") = py::none(), py::arg("want_posteriors") = true, py::arg("want_states") = true)
+	    .def("site_rate_posteriors", [](TreeLikelihoodInterface &self) {
+		    const py::ssize_t P = (py::ssize_t)self.GetPatternCount(), C = (py::ssize_t)self.CategoryCount();
+		    std::vector<double> R((size_t)(P * C)), mean((size_t)P);
+		    self.SiteRatePosteriors(R.data(), mean.data());
+		    return py::make_tuple(darray({P, C}, R.data()), vec(mean));
+	    })
 	    .def("get_pattern_count", &TreeLikelihoodInterface::GetPatternCount)
 	    .def("pattern_weights", [](TreeLikelihoodInterface &self) { return vec(self.PatternWeights()); })
 	    .def("pattern_states", [](TreeLikelihoodInterface &self) {

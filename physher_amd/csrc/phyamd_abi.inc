@@ -597,6 +597,31 @@ int phyamd_get_spr_profile(phyamd_engine *g, phyamd_spr_profile *out) {
 	return PHYAMD_OK;
 }
 
+// per-pattern results: every shard fills its own pattern range of the caller's arrays, so a pattern's bits do not depend on the
+// shard count.  The NaN rule goes by the handle's lnL (the shards' lnL added like phyamd_log_likelihood's)
+int phyamd_state_posteriors(phyamd_engine *g, int flags, int32_t count, const int32_t *nodes, double *posteriors, uint8_t *states) {
+	CHECK_GROUP(g);
+	ensure_scratch(g, 1);
+	int rc;
+	if ((rc = for_shards(g, [&](Shard *s, int i) {
+		     return shard_state_posteriors(s, flags, count, nodes, (size_t)g->P, posteriors ? posteriors + (size_t)g->offset[i] * g->S : nullptr,
+		                                   states ? states + g->offset[i] : nullptr, g->scratch[i].data());
+	     })))
+		return rc;
+	double lnl;
+	sum_shards(g, 1, &lnl);
+	post_mask_rows(lnl, (size_t)count * g->P, g->S, posteriors, states);
+	return PHYAMD_OK;
+}
+
+int phyamd_site_rate_posteriors(phyamd_engine *g, double *posteriors, double *mean_rates) {
+	CHECK_GROUP(g);
+	if (!posteriors) return fail(PHYAMD_EINVAL, "phyamd_site_rate_posteriors: null posteriors");
+	return for_shards(g, [&](Shard *s, int i) {
+		return shard_site_rate_posteriors(s, posteriors + (size_t)g->offset[i] * g->C, mean_rates ? mean_rates + g->offset[i] : nullptr);
+	});
+}
+
 // device-resident results (one process per GPU: the caller reduces them across processes with ONE RCCL all-reduce)
 int phyamd_log_likelihood_device(phyamd_engine *g, double *device_out) {
 	CHECK_GROUP(g);

@@ -270,6 +270,12 @@ struct Shard {
 	DeviceArray<double> d_spr_len{&batch_mem}, d_spr_mats{&batch_mem};  // [t | 0.5 t][N], [2][N][C][16]
 	bool batch_spr = false;              // the scratch holds these arrays for batch_items rows
 	phyamd_spr_profile spr_prof{};
+	// phyamd_state_posteriors / phyamd_site_rate_posteriors (phyamd_post.inc): the rows of a chunk, their staged results -- [rows][P][S]
+	// posteriors and [rows][P] states, or [P][C] + [P] site rates -- and, 20 / 60 / 61 states, each row's own partial p_n (true_lower_gen).
+	// On demand, like d_branch: the calls read what the keep-partials gradient left and have no entry in the record above
+	DeviceArray<PostRow> d_post_rows{&mem};
+	DeviceArray<double> d_post_out{&mem}, d_post_lower{&mem};
+	DeviceArray<uint8_t> d_post_states{&mem};
 };
 
 // ---- what each input invalidates -------------------------------------------------------------------------------------------

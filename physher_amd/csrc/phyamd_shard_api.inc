@@ -1801,3 +1801,163 @@ int shard_get_spr_profile(Shard *e, phyamd_spr_profile *out) {
 	*out = e->spr_prof;
 	return PHYAMD_OK;
 }
+
+// ---- per-pattern posteriors (phyamd_state_posteriors, phyamd_site_rate_posteriors) ---------------------------------------------
+
+// The staging arrays of the two calls, and rows of a chunk that fit beside the engine.  per_row[a]: bytes a row takes in array a
+// for this call, 0: the call does not use the array -- it is released first, so that what an earlier call left never takes this
+// call's room.  An array the call uses is kept where it is large enough (DeviceBuffer::reserve frees only an array it regrows),
+// so the arrays are counted at the larger of what they hold and what n rows need: n is the most rows that keep the engine's other
+// arrays (the batch scratch not counted: reserve() releases it when an array needs its room), these and a margin within the cap;
+// if arrays kept from a roomier time leave no such n, they are released and the rows sized for empty ones.  Without a cap: within
+// most of what the device has free right now.  At least one row: if even that does not fit, the allocation reports it
+constexpr int POST_ARRAYS = 4;
+size_t post_rows_that_fit(Shard *e, size_t count, const size_t (&per_row)[POST_ARRAYS]) {
+	DeviceBuffer *const arrays[POST_ARRAYS] = {&e->d_post_rows, &e->d_post_out, &e->d_post_lower, &e->d_post_states};
+	size_t row_bytes = 0;
+	for (int a = 0; a < POST_ARRAYS; a++) {
+		if (per_row[a] == 0) arrays[a]->release();
+		row_bytes += per_row[a];
+	}
+	const size_t most = std::min<size_t>(count, BATCH_MAX_CHUNK);
+	const auto held = [&] {
+		double h = 0.0;
+		for (DeviceBuffer *a : arrays) h += (double)a->bytes();
+		return h;
+	};
+	const auto rows_in = [&](double room) { return (size_t)std::min((double)most, std::max(std::floor(room / (double)row_bytes), 1.0)); };
+	if (e->cfg.max_device_bytes <= 0) {
+		size_t free_bytes = 0, total_bytes = 0;
+		return rows_in(hipMemGetInfo(&free_bytes, &total_bytes) == hipSuccess ? 0.8 * ((double)free_bytes + held()) : 0.0);
+	}
+	const double room = (double)e->cfg.max_device_bytes - ((double)e->mem.bytes - held() - (double)e->batch_mem.bytes) - 65536.0;
+	const size_t n = rows_in(room);
+	double after = 0.0;  // what the arrays hold once n rows are ensured
+	for (int a = 0; a < POST_ARRAYS; a++) after += (double)std::max(arrays[a]->bytes(), n * per_row[a]);
+	if (after > room)
+		for (DeviceBuffer *a : arrays) a->release();
+	return n;
+}
+
+// posteriors: row i at posteriors + (i * pattern_stride) * S, this shard's P patterns of it; states: row i at states + i *
+// pattern_stride (the group layer passes the handle's pattern count and pointers advanced to this shard's range).  lnl: the log
+// likelihood of the evaluation the partials belong to (this shard's patterns)
+int shard_state_posteriors(Shard *e, int flags, int32_t count, const int32_t *nodes, size_t pattern_stride, double *posteriors, uint8_t *states, double *lnl) {
+	CHECK_ENGINE(e);
+	NOT_TILED(e, "phyamd_state_posteriors (every partial resident)");
+	if (flags != 0) return fail(PHYAMD_EINVAL, "phyamd_state_posteriors: flags %d (no flags are defined: pass 0)", flags);
+	if (!posteriors && !states) return fail(PHYAMD_EINVAL, "phyamd_state_posteriors: posteriors and states are both null");
+	if (count < 1) return fail(PHYAMD_EINVAL, "phyamd_state_posteriors: count must be >= 1 (got %d)", count);
+	const int N = e->N, C = e->C, S = e->S, P = e->P;
+	if (!nodes && count != N) return fail(PHYAMD_EINVAL, "phyamd_state_posteriors: nodes is null, so count must be the node count %d (got %d)", N, count);
+	for (int32_t i = 0; nodes && i < count; i++)
+		if (nodes[i] < 0 || nodes[i] >= N) return fail(PHYAMD_EINVAL, "phyamd_state_posteriors: nodes[%d] = %d is not a node id (0..%d)", i, nodes[i], N - 1);
+	int rc;
+	if ((rc = bind_device(e)) || (rc = check_ready(e))) return rc;
+	// every partial resident: the engine becomes one with phyamd_set_keep_partials(1) that has run the flags-0 gradient
+	if (!e->keep_partials && (rc = shard_set_keep_partials(e, 1))) return rc;
+	if ((!uppers_resident(e) || !lowers_current(e)) && (rc = eval_gradient(e, 0))) return rc;
+	if ((rc = require_reference_form(e))) return rc;  // (stored partials: the partials themselves, in the reference's form)
+	if (!uppers_resident(e) || e->core_index[e->root] < 0) return fail(PHYAMD_EDEVICE, "phyamd_state_posteriors: the gradient left no resident partials");
+	const size_t npd = node_partial_doubles(e);
+	const size_t per_row[POST_ARRAYS] = {sizeof(PostRow), posteriors ? sizeof(double) * P * S : 0, e->generic ? sizeof(double) * npd : 0, states ? (size_t)P : 0};
+	const int fold = e->upper_fold ? 1 : 0;
+	std::vector<PostRow> rows;
+	std::vector<double> host_post;
+	std::vector<uint8_t> host_states;
+	const bool direct = pattern_stride == (size_t)P;  // one shard: a chunk's rows are contiguous in the caller's arrays
+	for (size_t first = 0; first < (size_t)count;) {
+		const size_t n = post_rows_that_fit(e, (size_t)count - first, per_row);
+		if ((rc = e->d_post_rows.ensure(n)) || (posteriors && (rc = e->d_post_out.ensure(n * P * S))) || (states && (rc = e->d_post_states.ensure(n * P))) ||
+		    (e->generic && (rc = e->d_post_lower.ensure(n * npd))))
+			return rc;
+		rows.resize(n);
+		for (size_t r = 0; r < n; r++) {
+			const int node = nodes ? nodes[first + r] : (int)(first + r);
+			PostRow &d = rows[r];
+			d.node = node;
+			d.mat = node == e->root ? -1 : node;
+			d.tip = node < e->T ? e->d_tipmask + (size_t)node * P : nullptr;
+			d.low = nullptr;
+			d.up = nullptr;
+			if (node != e->root) {
+				if (e->upper_slot[node] < 0) return fail(PHYAMD_EDEVICE, "phyamd_state_posteriors: node %d has no resident upper partial", node);
+				d.up = e->d_upper + (size_t)e->upper_slot[node] * npd;
+			}
+			if (node >= e->T) {
+				if (e->core_index[node] < 0) return fail(PHYAMD_EDEVICE, "phyamd_state_posteriors: node %d has no resident lower partial", node);
+				d.low = e->d_lower + (size_t)e->core_index[node] * npd;
+				if (e->generic && node != e->root) {  // a stored array is the message P p: the node's own partial, into this row's temporary
+					double *own = e->d_post_lower + r * npd;
+					if ((rc = true_lower_gen(e, node, own, nullptr))) return rc;
+					d.low = own;
+				}
+			}
+		}
+		HIP_TRY(hipMemcpyAsync(e->d_post_rows, rows.data(), sizeof(PostRow) * n, hipMemcpyHostToDevice, e->stream));
+		double *post = posteriors ? e->d_post_out.get() : nullptr;
+		uint8_t *st = states ? e->d_post_states.get() : nullptr;
+		if (e->generic)
+			hipLaunchKernelGGL(k_post_gen, dim3((P + 255) / 256, (unsigned)n), dim3(256), 0, e->stream, e->d_post_rows.get(), P, e->Pp, S, C, e->d_mats.get(), e->d_freqs.get(), fold,
+			                   e->d_props.get(), e->d_tipsets.get(), post, st);
+		else
+			hipLaunchKernelGGL(k_post4, dim3((P + WAVE - 1) / WAVE, (unsigned)n), dim3(WAVE, C), sizeof(double) * 4 * C * WAVE, e->stream, e->d_post_rows.get(), P, C,
+			                   e->d_mats.get(), e->d_freqs.get(), fold, e->d_props.get(), post, st);
+		HIP_TRY(hipGetLastError());
+		if (posteriors) {
+			double *dst = posteriors + first * pattern_stride * S;
+			if (!direct) host_post.resize(n * P * S), dst = host_post.data();
+			HIP_TRY(hipMemcpyAsync(dst, post, sizeof(double) * n * P * S, hipMemcpyDeviceToHost, e->stream));
+		}
+		if (states) {
+			uint8_t *dst = states + first * pattern_stride;
+			if (!direct) host_states.resize(n * P), dst = host_states.data();
+			HIP_TRY(hipMemcpyAsync(dst, st, n * P, hipMemcpyDeviceToHost, e->stream));
+		}
+		HIP_TRY(hipStreamSynchronize(e->stream));  // (also covers `rows`, which the next chunk builds anew)
+		for (size_t r = 0; !direct && r < n; r++) {
+			if (posteriors) std::memcpy(posteriors + (first + r) * pattern_stride * S, host_post.data() + r * P * S, sizeof(double) * P * S);
+			if (states) std::memcpy(states + (first + r) * pattern_stride, host_states.data() + r * P, (size_t)P);
+		}
+		first += n;
+	}
+	HIP_TRY(hipMemcpyAsync(e->h_result, e->d_result, sizeof(double), hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	*lnl = e->h_result[0];
+	return PHYAMD_OK;
+}
+
+// a NaN / inf lnL of the evaluation is reported in band (treelikelihood.c:327-332): NaN posteriors, state 255
+void post_mask_rows(double lnl, size_t cells, int S, double *posteriors, uint8_t *states) {
+	if (!std::isnan(lnl) && !std::isinf(lnl)) return;
+	if (posteriors) std::fill(posteriors, posteriors + cells * S, NAN);
+	if (states) std::fill(states, states + cells, (uint8_t)255);
+}
+
+// posteriors [P][C] and mean_rates [P] (or null) of this shard's patterns.  Reads the root's stored partial, like
+// phyamd_root_frequency_term: whatever is pending is evaluated by a post-order pass, and the engine is afterwards what that pass
+// leaves -- the root's array is p_root in every storage convention, only a rescaled evaluation's factors have to be the reference's
+int shard_site_rate_posteriors(Shard *e, double *posteriors, double *mean_rates) {
+	CHECK_ENGINE(e);
+	NOT_TILED(e, "phyamd_site_rate_posteriors (the root partial of every pattern resident)");
+	if (!posteriors) return fail(PHYAMD_EINVAL, "phyamd_site_rate_posteriors: null posteriors");
+	int rc;
+	if ((rc = bind_device(e)) || (rc = check_ready(e))) return rc;
+	if ((rc = run_lower(e, 1))) return rc;
+	if (e->scaling_on && (rc = require_reference_form(e))) return rc;  // (see shard_root_frequency_term: factors common to the categories)
+	if (e->core_index[e->root] < 0 || !e->d_lower) return fail(PHYAMD_EDEVICE, "phyamd_site_rate_posteriors: the root partial is not resident");
+	const int P = e->P, C = e->C;
+	e->d_post_rows.release(), e->d_post_lower.release(), e->d_post_states.release();  // (what a state call left is not this call's: its room is)
+	if ((rc = e->d_post_out.ensure((size_t)P * C + P))) return rc;
+	const double *root = e->d_lower + (size_t)e->core_index[e->root] * node_partial_doubles(e);
+	const size_t cat_stride = e->generic ? (size_t)e->S * e->Pp : (size_t)P * e->S;
+	const size_t pat_stride = e->generic ? 1 : (size_t)e->S, state_stride = e->generic ? (size_t)e->Pp : 1;
+	double *R = e->d_post_out.get(), *mean = R + (size_t)P * C;
+	hipLaunchKernelGGL(k_site_rate_post, dim3((P + 255) / 256), dim3(256), 0, e->stream, P, e->S, C, root, cat_stride, pat_stride, state_stride, e->d_freqs.get(),
+	                   e->d_props.get(), e->d_rates.get(), R, mean);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(posteriors, R, sizeof(double) * P * C, hipMemcpyDeviceToHost, e->stream));
+	if (mean_rates) HIP_TRY(hipMemcpyAsync(mean_rates, mean, sizeof(double) * P, hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	return PHYAMD_OK;
+}

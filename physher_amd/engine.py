@@ -289,6 +289,33 @@ class Engine:
         self._check(self._lib.phyamd_get_spr_profile(self._h, C.byref(p)))
         return {k: getattr(p, k) for k, _ in p._fields_}
 
+    def state_posteriors(self, nodes=None, want_posteriors=True, want_states=True):
+        """Marginal ancestral reconstruction on the device: (posteriors [count, P, S] float64, states [count, P] uint8), either None
+        when not wanted.  Row i is node nodes[i] (None: every node, row i is node i; tips and the root included, duplicates
+        allowed): the posterior of its state per pattern given all the data, and the most probable state (the smallest on a
+        tie).  An observed tip cell is one-hot; a gap cell holds the imputed state.  Evaluates whatever is pending; the engine
+        is afterwards one with set_keep_partials(True) that has run gradient().  NaN / 255 where lnL is not finite."""
+        if not (want_posteriors or want_states):
+            raise ValueError("want_posteriors and want_states are both False")
+        nd = None
+        if nodes is not None:
+            nd = np.ascontiguousarray(nodes, dtype=np.int32)
+            if nd.ndim != 1:
+                raise ValueError(f"nodes must be one-dimensional (got {nd.shape})")
+        count = self.N if nd is None else len(nd)
+        post = np.empty((count, self.P, self.S)) if want_posteriors else None
+        states = np.empty((count, self.P), dtype=np.uint8) if want_states else None
+        self._check(self._lib.phyamd_state_posteriors(self._h, 0, count, None if nd is None else _ptr(nd),
+                                                      None if post is None else _ptr(post), None if states is None else _ptr(states)))
+        return post, states
+
+    def site_rate_posteriors(self):
+        """(R [P, C], mean_rate [P]): the posterior of each pattern's rate category and its mean rate (sum_c R[k, c] r_c)."""
+        R = np.empty((self.P, self.C))
+        mean = np.empty(self.P)
+        self._check(self._lib.phyamd_site_rate_posteriors(self._h, _ptr(R), _ptr(mean)))
+        return R, mean
+
     def store(self):
         """Remember the current (evaluated) state: parameters, lnL and partials (MCMC store)."""
         self._check(self._lib.phyamd_store(self._h))
