@@ -311,6 +311,12 @@ class TreeLikelihoodInterface : public CallableModelInterface {
 	// Beyond the reference surface: the posterior of each pattern's rate category, posteriors [patterns][categories], and its mean
 	// rate, meanRates [patterns] or null (one phyamd_site_rate_posteriors call).
 	void SiteRatePosteriors(double *posteriors, double *meanRates);
+	// Beyond the reference surface: the full branch-length Hessian of lnL at the tree model's lengths (one phyamd_branch_hessian
+	// call; see include/physher_amd.h for the definition): hessian [2T-1][2T-1] and gradient [2T-1] (or null) by the tree's node
+	// ids, in the engine's branch lengths like NNILogLikelihoods; the root's row and column are 0, and the unrooted-tree epilogue
+	// (the row of the root's child whose length is not a parameter) is the caller's.  Returns lnL.  The engine behind this object
+	// keeps every partial resident from here on; the tree model is unchanged.
+	double BranchHessian(double *gradient, double *hessian);
 	size_t StateCount() const;
 	size_t CategoryCount() const;
 	size_t NodeCount() const;  // 2T - 1

@@ -379,6 +379,45 @@ int phyamd_state_posteriors(phyamd_engine *e, int flags, int32_t count, const in
  * phyamd_root_frequency_term).  mean_rates may be NULL.  PHYAMD_EUNSUPPORTED: tiled patterns.  Sharded handles: every shard
  * fills its own pattern range. */
 int phyamd_site_rate_posteriors(phyamd_engine *e, double *posteriors /* [P][C] */, double *mean_rates /* [P] or NULL */);
+/* The full branch-length Hessian of lnL, every pair of branches in one call: _singleTreeLikelihood_ddlogP
+ * (treelikelihood.c:532-690), which calculate_hessian (hessian.c:14-25) evaluates pair by pair with a pruning pass each.  Here it is
+ * formed from the lower and upper partials a keep-partials gradient leaves resident, with O(T^2) node operations.  With p_n the
+ * lower partial of node n (a tip: its 0/1 mask), u_n its upper partial in phyamd_get_partials' convention, P_{n,c} = exp(Q t_n r_c),
+ * pi the frequencies, w_c the proportions, r_c the category rates, w_k the pattern weights and L_k the site likelihood, for nodes
+ * a, b other than the root
+ *   gradient[a]   = sum_k w_k L_a,k / L_k                                (d lnL / d t_a: phyamd_branch_gradient's entry)
+ *   hessian[a][b] = sum_k w_k (L_ab,k / L_k - L_a,k L_b,k / L_k^2)        (d2 lnL / d t_a d t_b; symmetric, both triangles written)
+ * where L_a,k is the site likelihood with P_{a,c} replaced by r_c Q P_{a,c} and L_ab,k the one with both P_{a,c} and P_{b,c}
+ * replaced (a = b: the one replacement by r_c^2 Q Q P_{a,c}, so hessian[a][a] is phyamd_branch_hessian_diagonal's d2[a]).  The
+ * root's row and column are 0; for an unrooted tree the caller also zeroes the row and column of the root's child whose length
+ * is not a parameter, as for phyamd_gradient.  With msg(n) = P_n p_n, A_m = P_m^T (pi o u_m) (the root: pi),
+ * T_a^(par a) = r_c Q P_a p_a and T_a^(par m) = P_m (T_a^(m) o msg(other child of m)) the terms are
+ *   a below b:               L_ab,k = sum_c w_c r_c sum_i (pi o u_b)_i (Q P_b (T_a^(b) o msg(other child of b)))_i
+ *   a, b on two sides of m:  L_ab,k = sum_c w_c sum_i (A_m)_i (T_a^(m))_i (T_b^(m))_i
+ * hessian [2T-1][2T-1] row-major by node id; gradient [2T-1] or NULL; flags: 0 (others reserved, refused).
+ * The call evaluates whatever is pending and needs every partial resident, like phyamd_state_posteriors: if
+ * phyamd_set_keep_partials is off it is turned on, and if no resident upper partials belong to the current inputs the flags-0
+ * gradient runs.  Afterwards the engine is an engine with phyamd_set_keep_partials(1) that has run phyamd_gradient, and nothing
+ * else about it has changed.  Upper partials that a PHYAMD_GRAD_FOLD_ROOT_FREQS keep-partials gradient left resident are used as
+ * they are.  *lnl: the log likelihood of that evaluation; if it is NaN or +-inf, gradient and hessian are all NaN (in band:
+ * PHYAMD_RESCALE_NEVER on an underflowing tree reports -inf this way).
+ * Sums over patterns use no floating-point atomics: they are formed over blocks of 64 patterns and added in block order, so two
+ * calls return identical bits whatever the scratch held before.  The scratch (a tangent per (branch, ancestor): sum_a depth(a) C
+ * P 4 doubles, and a row of P doubles per branch) lives in the batch scratch and is counted and released like it; under
+ * max_device_bytes the patterns run in chunks of whole blocks whose sums are added in chunk order (PHYAMD_ENOMEM if not one
+ * block fits): the bits may depend on the cap and on nothing else.  Sharded handles: every shard runs its own patterns, and lnl,
+ * gradient and hessian are added over the shards like phyamd_gradient's sums.
+ * PHYAMD_EUNSUPPORTED, with the condition in the message: state counts other than 4, more than 8 categories, explicit node
+ * matrices (Q P is the derivative of exp(Q t r) only), tiled patterns, and an engine that is rescaling when the partials are read
+ * (PHYAMD_RESCALE_ALWAYS, or PHYAMD_RESCALE_AUTO after its switch, including a switch made by the evaluation this call
+ * triggered): the terms multiply partials of different nodes, and a rescaled evaluation's partials do not share units.
+ * PHYAMD_EINVAL, naming the function and the argument: null engine, lnl or hessian; flags other than 0; no eigen system; an
+ * engine that is not ready. */
+int phyamd_branch_hessian(phyamd_engine *e, int flags, double *lnl, double *gradient /* [2T-1] or NULL */, double *hessian /* [2T-1][2T-1] */);
+/* The last phyamd_branch_hessian: pairs = the unordered pairs a <= b scored, (2T-2)(2T-1)/2; chunks = the pattern chunks the call
+ * ran in (sharded: the most of any shard); scratch_bytes = the batch scratch held afterwards, summed over the shards */
+typedef struct { int32_t chunks; int64_t pairs, scratch_bytes; double ms; } phyamd_hessian_profile;
+int phyamd_get_hessian_profile(phyamd_engine *e, phyamd_hessian_profile *out);
 int phyamd_synchronize(phyamd_engine *e);
 
 /* --- inspection (parity tests, debugging) --- */

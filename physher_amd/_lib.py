@@ -43,6 +43,10 @@ class SprProfile(C.Structure):
     _fields_ = [("prunes", C.c_int32), ("chunks", C.c_int32), ("candidates", C.c_int64), ("scratch_bytes", C.c_int64), ("ms", C.c_double)]
 
 
+class HessianProfile(C.Structure):
+    _fields_ = [("chunks", C.c_int32), ("pairs", C.c_int64), ("scratch_bytes", C.c_int64), ("ms", C.c_double)]
+
+
 class BatchProfile(C.Structure):
     _fields_ = [
         ("items_fast", C.c_int32), ("items_sequential", C.c_int32), ("chunks", C.c_int32), ("scratch_bytes", C.c_int64), ("ms", C.c_double),
@@ -93,6 +97,8 @@ SYMBOLS = [
     ("phyamd_get_spr_profile", C.c_int, [_P, C.POINTER(SprProfile)]),
     ("phyamd_state_posteriors", C.c_int, [_P, C.c_int, C.c_int32, _P, _P, _P]),
     ("phyamd_site_rate_posteriors", C.c_int, [_P, _P, _P]),
+    ("phyamd_branch_hessian", C.c_int, [_P, C.c_int, _P, _P, _P]),
+    ("phyamd_get_hessian_profile", C.c_int, [_P, C.POINTER(HessianProfile)]),
     ("phyamd_synchronize", C.c_int, [_P]),
     ("phyamd_get_pattern_log_likelihoods", C.c_int, [_P, _P]),
     ("phyamd_get_partials", C.c_int, [_P, C.c_int, C.c_int, _P]),

@@ -943,3 +943,11 @@ void TreeLikelihoodInterface::SiteRatePosteriors(double *posteriors, double *mea
 	Sync();
 	phyamd::check(phyamd_site_rate_posteriors(impl_->engine, posteriors, meanRates));
 }
+
+double TreeLikelihoodInterface::BranchHessian(double *gradient, double *hessian) {
+	if (!hessian) throw Error("null hessian");
+	Sync();
+	double lnl = 0.0;
+	phyamd::check(phyamd_branch_hessian(impl_->engine, 0, &lnl, gradient, hessian));
+	return lnl;
+}

@@ -261,6 +261,14 @@ PYBIND11_MODULE(_phycpp_amd, m) {
 		    if (want_states) b = py::array_t<unsigned char>({count, P}, states.data());
 		    return py::make_tuple(a, b);
 	    }, py::arg("nodes") = py::none(), py::arg("want_posteriors") = true, py::arg("want_states") = true)
+	    .def("branch_hessian", [](TreeLikelihoodInterface &self, bool want_gradient) -> py::tuple {
+		    const py::ssize_t N = (py::ssize_t)self.NodeCount();
+		    std::vector<double> g(want_gradient ? (size_t)N : 0), H((size_t)(N * N));
+		    const double lnl = self.BranchHessian(want_gradient ? g.data() : nullptr, H.data());
+		    py::object gradient = py::none();
+		    if (want_gradient) gradient = vec(g);
+		    return py::make_tuple(lnl, gradient, darray({N, N}, H.data()));
+	    }, py::arg("want_gradient") = true)
 	    .def("site_rate_posteriors", [](TreeLikelihoodInterface &self) {
 		    const py::ssize_t P = (py::ssize_t)self.GetPatternCount(), C = (py::ssize_t)self.CategoryCount();
 		    std::vector<double> R((size_t)(P * C)), mean((size_t)P);

@@ -86,6 +86,7 @@ struct phyamd_engine {
 	std::vector<std::vector<double>> scratch;  // per-shard host result vectors
 	std::vector<std::string> errors;
 	double spr_ms = 0.0;                       // wall time of the last phyamd_spr_log_likelihoods
+	double bhess_ms = 0.0;                     // wall time of the last phyamd_branch_hessian
 };
 
 namespace {
@@ -620,6 +621,49 @@ int phyamd_site_rate_posteriors(phyamd_engine *g, double *posteriors, double *me
 	return for_shards(g, [&](Shard *s, int i) {
 		return shard_site_rate_posteriors(s, posteriors + (size_t)g->offset[i] * g->C, mean_rates ? mean_rates + g->offset[i] : nullptr);
 	});
+}
+
+// every shard forms lnl, the gradient and the matrix of its own patterns; they are added over the shards like phyamd_gradient's sums
+// (sum_shards: a fixed order of the shard indices).  The NaN rule goes by the handle's lnL
+int phyamd_branch_hessian(phyamd_engine *g, int flags, double *lnl, double *gradient, double *hessian) {
+	if (!lnl || !hessian) return fail(PHYAMD_EINVAL, "phyamd_branch_hessian: null %s", !lnl ? "lnl" : "hessian");
+	if (!g || g->shards.empty()) return fail(PHYAMD_EINVAL, "phyamd_branch_hessian: null engine");
+	const auto t0 = std::chrono::steady_clock::now();
+	int rc;
+	if (group_size(g) == 1) rc = shard_branch_hessian(g->shards[0], flags, lnl, gradient, hessian);
+	else {
+		const size_t N = (size_t)g->N, n = 1 + N + N * N;
+		ensure_scratch(g, n);
+		rc = for_shards(g, [&](Shard *s, int i) {
+			double *v = g->scratch[i].data();  // [lnl | gradient [N] | hessian [N][N]]
+			return shard_branch_hessian(s, flags, v, v + 1, v + 1 + N);
+		});
+		if (!rc) {
+			std::vector<double> total(n);
+			sum_shards(g, n, total.data());
+			*lnl = total[0];
+			if (gradient) std::memcpy(gradient, total.data() + 1, sizeof(double) * N);
+			std::memcpy(hessian, total.data() + 1 + N, sizeof(double) * N * N);
+			bhess_mask(*lnl, N, gradient, hessian);
+		}
+	}
+	g->bhess_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	return rc;
+}
+
+int phyamd_get_hessian_profile(phyamd_engine *g, phyamd_hessian_profile *out) {
+	CHECK_GROUP(g);
+	if (!out) return fail(PHYAMD_EINVAL, "null out");
+	int rc;
+	if ((rc = shard_get_hessian_profile(g->shards[0], out))) return rc;
+	for (int i = 1; i < group_size(g); i++) {  // memory adds up; the shards choose their chunks themselves: the most
+		phyamd_hessian_profile p;
+		if ((rc = shard_get_hessian_profile(g->shards[i], &p))) return rc;
+		out->chunks = std::max(out->chunks, p.chunks);
+		out->scratch_bytes += p.scratch_bytes;
+	}
+	out->ms = g->bhess_ms;
+	return PHYAMD_OK;
 }
 
 // device-resident results (one process per GPU: the caller reduces them across processes with ONE RCCL all-reduce)

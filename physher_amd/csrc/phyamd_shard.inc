@@ -276,6 +276,16 @@ struct Shard {
 	DeviceArray<PostRow> d_post_rows{&mem};
 	DeviceArray<double> d_post_out{&mem}, d_post_lower{&mem};
 	DeviceArray<uint8_t> d_post_states{&mem};
+	// phyamd_branch_hessian (phyamd_bhess.inc): scratch of one chunk of whole 64-pattern blocks, held in the batch scratch's group --
+	// counted in device_bytes while held, released with it (release_batch_scratch, a new topology, an array of the engine that needs
+	// the room) and never assumed to hold anything: every call writes what it reads.  tan: the tangents [steps][C][Pc][4]; rows: w / L
+	// and 1 / L [2][Pc], G [N][Pc], the walk's slab [steps + 2 N][blocks]; tiles: the cousin and the outer-product tiles
+	// [tiles][blocks][256]; sums: the chunk's and the running matrix and gradient, r Q P and r^2 Q Q P; lists: the walk's starts and
+	// steps, the tiles, each node's stored lower and upper.  Like the posteriors the call reads what the keep-partials gradient left
+	// and has no entry in the record below: it leaves valid exactly what phyamd_state_posteriors leaves valid
+	DeviceArray<double> d_bhess_tan{&batch_mem}, d_bhess_rows{&batch_mem}, d_bhess_tiles{&batch_mem}, d_bhess_sums{&batch_mem};
+	DeviceArray<char> d_bhess_lists{&batch_mem};
+	phyamd_hessian_profile bhess_prof{};
 };
 
 // ---- what each input invalidates -------------------------------------------------------------------------------------------

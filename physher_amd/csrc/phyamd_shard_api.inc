@@ -1961,3 +1961,211 @@ int shard_site_rate_posteriors(Shard *e, double *posteriors, double *mean_rates)
 	HIP_TRY(hipStreamSynchronize(e->stream));
 	return PHYAMD_OK;
 }
+
+// ---- the full branch-length Hessian (phyamd_branch_hessian) --------------------------------------------------------------------
+
+// the lists of the engine's tree: every node's walk to the root (one tangent slot per step), and the work lists of the two tile
+// kernels -- per internal node m the 16 x 16 tiles of (node below its left child) x (node below its right child), and the tiles
+// of the upper triangle of (branch) x (branch)
+struct BhessLists {
+	std::vector<BhessStart> starts;
+	std::vector<BhessStep> steps;
+	std::vector<BhessTile> cousins, outer;
+};
+
+void build_bhess_lists(const Shard *e, BhessLists &L) {
+	const int N = e->N, root = e->root;
+	std::vector<std::vector<std::pair<int32_t, int32_t>>> below((size_t)2 * N);  // [2 m + side]: (node, slot of its tangent at m)
+	std::vector<int32_t> branches;
+	for (int a = 0; a < N; a++) {
+		if (a == root) continue;
+		branches.push_back(a);
+		BhessStart s{a, (int32_t)L.steps.size(), 0, 0};
+		for (int cur = a, m = e->parent[a];; cur = m, m = e->parent[m]) {
+			const bool from_left = e->left[m] == cur;
+			below[(size_t)2 * m + (from_left ? 0 : 1)].push_back({a, (int32_t)L.steps.size()});
+			L.steps.push_back(BhessStep{m, from_left ? e->right[m] : e->left[m], a, 0});
+			s.count++;
+			if (m == root) break;
+		}
+		L.starts.push_back(s);
+	}
+	const auto fill = [](int32_t *rows, int32_t *nodes, const std::pair<int32_t, int32_t> *from, size_t n) {
+		for (size_t i = 0; i < 16; i++) rows[i] = from[i < n ? i : 0].second, nodes[i] = i < n ? from[i].first : -1;
+	};
+	for (int m = e->T; m < N; m++) {
+		const auto &l = below[(size_t)2 * m], &r = below[(size_t)2 * m + 1];
+		for (size_t i = 0; i < l.size(); i += 16)
+			for (size_t j = 0; j < r.size(); j += 16) {
+				BhessTile t{};
+				t.m = m;
+				fill(t.row_a, t.node_a, l.data() + i, std::min<size_t>(16, l.size() - i));
+				fill(t.row_b, t.node_b, r.data() + j, std::min<size_t>(16, r.size() - j));
+				L.cousins.push_back(t);
+			}
+	}
+	std::vector<std::pair<int32_t, int32_t>> rows;  // (node, its row of G)
+	for (int32_t a : branches) rows.push_back({a, a});
+	for (size_t i = 0; i < rows.size(); i += 16)
+		for (size_t j = i; j < rows.size(); j += 16) {
+			BhessTile t{};
+			t.m = -1;
+			fill(t.row_a, t.node_a, rows.data() + i, std::min<size_t>(16, rows.size() - i));
+			fill(t.row_b, t.node_b, rows.data() + j, std::min<size_t>(16, rows.size() - j));
+			L.outer.push_back(t);
+		}
+}
+
+// lnl, gradient [N] (or null) and hessian [N][N] of this shard's patterns (host)
+int run_branch_hessian(Shard *e, double *lnl, double *gradient, double *hessian, phyamd_hessian_profile &prof) {
+	static const char *const name = "phyamd_branch_hessian";
+	const int N = e->N, C = e->C, P = e->P;
+	int rc;
+	if (e->generic) return fail(PHYAMD_EUNSUPPORTED, "%s: %d states (the tangent walk and the pair tiles are built for 4)", name, e->S);
+	if (C > BHESS_MAX_CATEGORIES) return fail(PHYAMD_EUNSUPPORTED, "%s: %d categories (a workgroup holds the category waves of one block: at most %d)", name, C, BHESS_MAX_CATEGORIES);
+	NOT_TILED(e, "phyamd_branch_hessian (every partial resident)");
+	if ((rc = check_ready(e))) return rc;
+	if (std::any_of(e->explicit_host.begin(), e->explicit_host.end(), [](uint8_t x) { return x != 0; }))
+		return fail(PHYAMD_EUNSUPPORTED, "%s: a node has explicit matrices (Q P is the derivative of exp(Q t r) only)", name);
+	if (!e->have_eigen || !e->have_Q) return fail(PHYAMD_EINVAL, "%s needs the eigen system (phyamd_set_eigen): the derivatives of the matrices are formed from it", name);
+	static const char *const rescaling = "%s: the engine is rescaling (the terms multiply partials of different nodes, and a rescaled evaluation's partials do not share units)";
+	if (e->scaling_on) return fail(PHYAMD_EUNSUPPORTED, rescaling, name);
+	// every partial resident: the engine becomes one with phyamd_set_keep_partials(1) that has run the flags-0 gradient
+	if (!e->keep_partials && (rc = shard_set_keep_partials(e, 1))) return rc;
+	if ((!uppers_resident(e) || !lowers_current(e)) && (rc = eval_gradient(e, 0))) return rc;
+	if (e->scaling_on) return fail(PHYAMD_EUNSUPPORTED, rescaling, name);  // (PHYAMD_RESCALE_AUTO: that evaluation switched)
+	if ((rc = require_reference_form(e))) return rc;
+	if (!uppers_resident(e) || e->core_index[e->root] < 0) return fail(PHYAMD_EDEVICE, "%s: the gradient left no resident partials", name);
+
+	BhessLists L;
+	build_bhess_lists(e, L);
+	std::vector<int32_t> lower_of(N), upper_of(N);
+	for (int n = 0; n < N; n++) {
+		lower_of[n] = n < e->T ? -1 : e->core_index[n];
+		upper_of[n] = n == e->root ? 0 : e->upper_slot[n];
+		if ((n >= e->T && lower_of[n] < 0) || upper_of[n] < 0) return fail(PHYAMD_EDEVICE, "%s: node %d has no resident partial", name, n);
+	}
+	const size_t nsteps = L.steps.size(), ntc = L.cousins.size(), nto = L.outer.size(), nn = (size_t)N * N;
+	const size_t at_steps = sizeof(BhessStart) * L.starts.size(), at_cousins = at_steps + sizeof(BhessStep) * nsteps, at_outer = at_cousins + sizeof(BhessTile) * ntc,
+	             at_lower = at_outer + sizeof(BhessTile) * nto, at_upper = at_lower + sizeof(int32_t) * N, list_bytes = at_upper + sizeof(int32_t) * N;
+	// the chunk: whole blocks whose scratch fits beside the engine (batch_items_that_fit's room, the whole scratch group counted free)
+	const size_t nblk_all = ((size_t)P + WAVE - 1) / WAVE;
+	const double block_bytes = 8.0 * ((double)nsteps * C * WAVE * 4 + 2.0 * WAVE + (double)N * WAVE + (double)(nsteps + 2 * (size_t)N) + 256.0 * (double)(ntc + nto));
+	const size_t sums = 2 * nn + 2 * (size_t)N + 2 * (size_t)N * C * 16;
+	const double fixed_bytes = 8.0 * (double)sums + (double)list_bytes;
+	const double held = (double)batch_scratch_bytes(e);
+	double room;
+	if (e->cfg.max_device_bytes > 0) {
+		const double tile_now = (double)e->tile_mem.bytes, resident = (double)e->mem.bytes - held - tile_now;
+		room = (double)e->cfg.max_device_bytes - (resident + 65536.0 + walk_reserve(e) + std::max(tile_now, tile_working_set(e, (double)e->P, true)));
+	} else {
+		size_t free_bytes = 0, total_bytes = 0;
+		room = hipMemGetInfo(&free_bytes, &total_bytes) == hipSuccess ? 0.8 * ((double)free_bytes + held) : 0.0;
+	}
+	const double fit = std::floor((room - fixed_bytes) / block_bytes);
+	if (fit < 1.0)
+		return fail(PHYAMD_ENOMEM, "%s: the scratch of one block of 64 patterns (%.0f bytes, and %.0f for the matrix and the lists) does not fit the memory budget", name,
+		            block_bytes, fixed_bytes);
+	const size_t nblk = (size_t)std::min((double)nblk_all, fit), Pc = nblk * WAVE;
+	const size_t n_tan = nsteps * C * Pc * 4, n_rows = 2 * Pc + (size_t)N * Pc + (nsteps + 2 * (size_t)N) * nblk, n_tiles = (ntc + nto) * nblk * 256;
+	const bool serves = e->d_bhess_tan.size() >= n_tan && e->d_bhess_rows.size() >= n_rows && e->d_bhess_tiles.size() >= n_tiles && e->d_bhess_sums.size() >= sums &&
+	                    e->d_bhess_lists.size() >= list_bytes && e->d_bhess_tan.get();
+	if (!serves && e->cfg.max_device_bytes > 0) release_batch_scratch(e);  // (under a cap a call gets exactly its own scratch)
+	if ((rc = e->d_bhess_tan.ensure(n_tan)) || (rc = e->d_bhess_rows.ensure(n_rows)) || (rc = e->d_bhess_tiles.ensure(n_tiles)) || (rc = e->d_bhess_sums.ensure(sums)) ||
+	    (rc = e->d_bhess_lists.ensure(list_bytes)))
+		return rc;
+
+	std::vector<char> lists(list_bytes);
+	std::memcpy(lists.data(), L.starts.data(), at_steps);
+	std::memcpy(lists.data() + at_steps, L.steps.data(), sizeof(BhessStep) * nsteps);
+	if (ntc) std::memcpy(lists.data() + at_cousins, L.cousins.data(), sizeof(BhessTile) * ntc);
+	std::memcpy(lists.data() + at_outer, L.outer.data(), sizeof(BhessTile) * nto);
+	std::memcpy(lists.data() + at_lower, lower_of.data(), sizeof(int32_t) * N);
+	std::memcpy(lists.data() + at_upper, upper_of.data(), sizeof(int32_t) * N);
+	HIP_TRY(hipMemcpyAsync(e->d_bhess_lists, lists.data(), list_bytes, hipMemcpyHostToDevice, e->stream));
+	const char *dl = e->d_bhess_lists.get();
+	const BhessStart *d_starts = reinterpret_cast<const BhessStart *>(dl);
+	const BhessStep *d_steps = reinterpret_cast<const BhessStep *>(dl + at_steps);
+	const BhessTile *d_cousins = reinterpret_cast<const BhessTile *>(dl + at_cousins), *d_outer = reinterpret_cast<const BhessTile *>(dl + at_outer);
+	double *Hc = e->d_bhess_sums.get(), *H = Hc + nn, *gc = H + nn, *g = gc + N, *qp = g + N, *qqp = qp + (size_t)N * C * 16;
+	hipLaunchKernelGGL(k_bhess_matrices, dim3((unsigned)(((size_t)N * C * 16 + 255) / 256)), dim3(256), 0, e->stream, N * C, C, e->d_mats.get(), e->d_Q.get(), e->d_rates.get(), qp,
+	                   qqp);
+	BhessArgs a{};
+	a.steps = d_steps;
+	a.lower_of = reinterpret_cast<const int32_t *>(dl + at_lower), a.upper_of = reinterpret_cast<const int32_t *>(dl + at_upper);
+	a.T = e->T, a.N = N, a.P = P, a.C = C, a.root = e->root, a.fold = e->upper_fold ? 1 : 0;
+	a.nsteps = (int)nsteps;
+	a.tipmask = e->d_tipmask, a.lower = e->d_lower, a.upper = e->d_upper;
+	a.mats = e->d_mats, a.qp = qp, a.qqp = qqp;
+	a.freqs = e->d_freqs, a.props = e->d_props, a.weights = e->d_weights;
+	a.site = e->d_bhess_rows.get(), a.G = a.site + 2 * Pc, a.slab = a.G + (size_t)N * Pc;
+	a.tan = e->d_bhess_tan;
+	double *cousin_out = e->d_bhess_tiles.get(), *outer_out = cousin_out + ntc * nblk * 256;
+	for (size_t b0 = 0; b0 < nblk_all; b0 += nblk) {
+		const size_t nb = std::min(nblk, nblk_all - b0);  // (the last chunk may be shorter: it runs in the same arrays at its own width)
+		a.k0 = (int)(b0 * WAVE), a.nblk = (int)nb, a.Pc = (int)(nb * WAVE);
+		a.G = a.site + 2 * (size_t)a.Pc, a.slab = a.G + (size_t)N * a.Pc;
+		HIP_TRY(hipMemsetAsync(Hc, 0, sizeof(double) * nn, e->stream));
+		hipLaunchKernelGGL(k_bhess_site, dim3((unsigned)((a.Pc + 255) / 256)), dim3(256), 0, e->stream, a);
+		for (size_t y = 0; y < L.starts.size(); y += BATCH_MAX_CHUNK) {  // (gridDim.y)
+			a.starts = d_starts + y;
+			hipLaunchKernelGGL(k_bhess_walk, dim3((unsigned)nb, (unsigned)std::min<size_t>(L.starts.size() - y, BATCH_MAX_CHUNK)), dim3(WAVE, C), 0, e->stream, a);
+		}
+		for (size_t y = 0; y < ntc; y += BATCH_MAX_CHUNK)
+			hipLaunchKernelGGL(k_bhess_cousins, dim3((unsigned)nb, (unsigned)std::min<size_t>(ntc - y, BATCH_MAX_CHUNK)), dim3(256), 0, e->stream, a, d_cousins + y,
+			                   cousin_out + y * nb * 256);
+		for (size_t y = 0; y < nto; y += BATCH_MAX_CHUNK)
+			hipLaunchKernelGGL(k_bhess_outer, dim3((unsigned)nb, (unsigned)std::min<size_t>(nto - y, BATCH_MAX_CHUNK)), dim3(WAVE), 0, e->stream, a, d_outer + y,
+			                   outer_out + y * nb * 256);
+		BhessFinish f{0, N, (int)nb, e->root, (int)nsteps, b0 == 0 ? 1 : 0, nto * 256, d_outer, d_steps, outer_out, Hc, gc, H, g};
+		const auto finish = [&] { hipLaunchKernelGGL(k_bhess_finish, dim3((unsigned)((f.count + 255) / 256)), dim3(256), 0, e->stream, f); };
+		finish();
+		f.mode = 1, f.count = nsteps + N, f.slab = a.slab;
+		finish();
+		if (ntc) {
+			f.mode = 2, f.count = ntc * 256, f.tiles = d_cousins, f.slab = cousin_out;
+			finish();
+		}
+		f.mode = 3, f.count = nn;
+		finish();
+		HIP_TRY(hipGetLastError());
+		prof.chunks++;
+	}
+	HIP_TRY(hipMemcpyAsync(hessian, H, sizeof(double) * nn, hipMemcpyDeviceToHost, e->stream));
+	if (gradient) HIP_TRY(hipMemcpyAsync(gradient, g, sizeof(double) * N, hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipMemcpyAsync(e->h_result, e->d_result, sizeof(double), hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));  // (also covers `lists`)
+	*lnl = e->h_result[0];
+	return PHYAMD_OK;
+}
+
+// a NaN / inf lnL of the evaluation is reported in band (treelikelihood.c:327-332): every derivative NaN
+void bhess_mask(double lnl, size_t N, double *gradient, double *hessian) {
+	if (!std::isnan(lnl) && !std::isinf(lnl)) return;
+	if (gradient) std::fill(gradient, gradient + N, NAN);
+	std::fill(hessian, hessian + N * N, NAN);
+}
+
+int shard_branch_hessian(Shard *e, int flags, double *lnl, double *gradient, double *hessian) {
+	if (!e) return fail(PHYAMD_EINVAL, "phyamd_branch_hessian: null engine");
+	if (!lnl || !hessian) return fail(PHYAMD_EINVAL, "phyamd_branch_hessian: null %s", !lnl ? "lnl" : "hessian");
+	if (flags != 0) return fail(PHYAMD_EINVAL, "phyamd_branch_hessian: flags %d (no flags are defined: pass 0)", flags);
+	const auto t0 = std::chrono::steady_clock::now();
+	int rc;
+	if ((rc = bind_device(e))) return rc;
+	phyamd_hessian_profile prof{};
+	prof.pairs = (int64_t)(e->N - 1) * e->N / 2;
+	rc = run_branch_hessian(e, lnl, gradient, hessian, prof);
+	if (!rc) bhess_mask(*lnl, (size_t)e->N, gradient, hessian);
+	prof.scratch_bytes = (int64_t)batch_scratch_bytes(e);
+	prof.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	e->bhess_prof = prof;
+	return rc;
+}
+
+int shard_get_hessian_profile(Shard *e, phyamd_hessian_profile *out) {
+	CHECK_ENGINE(e);
+	if (!out) return fail(PHYAMD_EINVAL, "null out");
+	*out = e->bhess_prof;
+	return PHYAMD_OK;
+}

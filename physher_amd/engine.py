@@ -316,6 +316,23 @@ class Engine:
         self._check(self._lib.phyamd_site_rate_posteriors(self._h, _ptr(R), _ptr(mean)))
         return R, mean
 
+    def branch_hessian(self, flags=0, want_gradient=True):
+        """(lnL, g [N] or None, H [N, N]): the full branch-length Hessian of lnL, H[a, b] = d2 lnL / dt_a dt_b for every pair of
+        branches (symmetric; the root's row and column 0; diag(H) is branch_hessian_diagonal's d2), and g[a] = d lnL / dt_a.
+        4 states, at most 8 categories, an engine that is not rescaling.  Evaluates whatever is pending; the engine is afterwards
+        one with set_keep_partials(True) that has run gradient().  All NaN where lnL is not finite."""
+        v = C.c_double()
+        g = np.empty(self.N) if want_gradient else None
+        H = np.empty((self.N, self.N))
+        self._check(self._lib.phyamd_branch_hessian(self._h, flags, C.byref(v), None if g is None else _ptr(g), _ptr(H)))
+        return v.value, g, H
+
+    def hessian_profile(self):
+        """Of the last branch_hessian: chunks (of patterns), pairs (unordered, a <= b), scratch_bytes, ms."""
+        p = _lib.HessianProfile()
+        self._check(self._lib.phyamd_get_hessian_profile(self._h, C.byref(p)))
+        return {k: getattr(p, k) for k, _ in p._fields_}
+
     def store(self):
         """Remember the current (evaluated) state: parameters, lnL and partials (MCMC store)."""
         self._check(self._lib.phyamd_store(self._h))
