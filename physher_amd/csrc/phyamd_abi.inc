@@ -206,6 +206,41 @@ void ensure_scratch(phyamd_engine *g, size_t count) {
 		if (v.size() < count) v.resize(count);
 }
 
+// fn(shard, out) leaves a shard's `count` doubles in out: one shard writes `total` itself, several write their scratch vectors
+// at once and `total` is their sum (sum_shards).  What a shard masked in band the caller masks again by the summed lnL
+template <typename F>
+int sum_over_shards(phyamd_engine *g, size_t count, double *total, F fn) {
+	if (group_size(g) == 1) return fn(g->shards[0], total);
+	ensure_scratch(g, count);
+	int rc;
+	if ((rc = for_shards(g, [&](Shard *s, int i) { return fn(s, g->scratch[i].data()); }))) return rc;
+	sum_shards(g, count, total);
+	return PHYAMD_OK;
+}
+
+// a batch on several shards: fn(shard, lnl [count], cat_gradient [count][N C] or null) into the shard's scratch vector, laid out
+// [lnl | cat_gradient], and the sums unpacked into the caller's arrays
+template <typename F>
+int sum_batch_over_shards(phyamd_engine *g, int32_t count, double *lnl, double *cat_gradient, F fn) {
+	const size_t ncat = (size_t)g->N * g->C, n = (size_t)count * (cat_gradient ? 1 + ncat : 1);
+	std::vector<double> total(n);
+	int rc;
+	if ((rc = sum_over_shards(g, n, total.data(), [&](Shard *s, double *v) { return fn(s, v, cat_gradient ? v + count : nullptr); }))) return rc;
+	std::memcpy(lnl, total.data(), sizeof(double) * count);
+	if (cat_gradient) std::memcpy(cat_gradient, total.data() + count, sizeof(double) * count * ncat);
+	return PHYAMD_OK;
+}
+
+// the profile of a query call: the first shard's, the others' merged in by the call's own rule
+template <typename Prof, typename Merge>
+int merged_profile(phyamd_engine *g, Prof Shard::*slot, Prof *out, Merge merge) {
+	CHECK_GROUP(g);
+	if (!out) return fail(PHYAMD_EINVAL, "null out");
+	*out = g->shards[0]->*slot;
+	for (int i = 1; i < group_size(g); i++) merge(*out, g->shards[i]->*slot);
+	return PHYAMD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -390,15 +425,9 @@ int phyamd_parameter_gradient(phyamd_engine *g, int flags, double *lnl, double *
 	if (!parameter_gradient) return fail(PHYAMD_EINVAL, "null parameter_gradient");
 	if (group_size(g) == 1) return shard_parameter_gradient(g->shards[0], flags, lnl, cat_gradient, parameter_gradient);
 	const size_t ncat = (size_t)g->N * g->C, np = (size_t)g->shards[0]->np;
-	ensure_scratch(g, 1 + ncat + np);
-	int rc;
-	if ((rc = for_shards(g, [&](Shard *s, int i) {
-		     double *v = g->scratch[i].data();
-		     return shard_parameter_gradient(s, flags, v, v + 1, v + 1 + ncat);
-	     })))
-		return rc;
 	std::vector<double> total(1 + ncat + np);
-	sum_shards(g, total.size(), total.data());
+	int rc;
+	if ((rc = sum_over_shards(g, total.size(), total.data(), [&](Shard *s, double *v) { return shard_parameter_gradient(s, flags, v, v + 1, v + 1 + ncat); }))) return rc;
 	if (lnl) *lnl = total[0];
 	if (cat_gradient) std::memcpy(cat_gradient, total.data() + 1, sizeof(double) * ncat);
 	std::memcpy(parameter_gradient, total.data() + 1 + ncat, sizeof(double) * np);
@@ -408,38 +437,22 @@ int phyamd_parameter_gradient(phyamd_engine *g, int flags, double *lnl, double *
 int phyamd_root_invariant_term(phyamd_engine *g, double *out) {
 	CHECK_GROUP(g);
 	if (!out) return fail(PHYAMD_EINVAL, "null out");
-	if (group_size(g) == 1) return shard_root_invariant_term(g->shards[0], out);
-	ensure_scratch(g, 1);
-	int rc;
-	if ((rc = for_shards(g, [&](Shard *s, int i) { return shard_root_invariant_term(s, g->scratch[i].data()); }))) return rc;
-	sum_shards(g, 1, out);
-	return PHYAMD_OK;
+	return sum_over_shards(g, 1, out, [&](Shard *s, double *v) { return shard_root_invariant_term(s, v); });
 }
 
 int phyamd_root_frequency_term(phyamd_engine *g, double *out) {
 	CHECK_GROUP(g);
 	if (!out) return fail(PHYAMD_EINVAL, "null out");
-	if (group_size(g) == 1) return shard_root_frequency_term(g->shards[0], out);
-	ensure_scratch(g, (size_t)g->S);
-	int rc;
-	if ((rc = for_shards(g, [&](Shard *s, int i) { return shard_root_frequency_term(s, g->scratch[i].data()); }))) return rc;
-	sum_shards(g, (size_t)g->S, out);
-	return PHYAMD_OK;
+	return sum_over_shards(g, (size_t)g->S, out, [&](Shard *s, double *v) { return shard_root_frequency_term(s, v); });
 }
 
 int phyamd_branch_log_likelihood(phyamd_engine *g, int node, double length, double *lnl, double *d1, double *d2) {
 	CHECK_GROUP(g);
 	if (group_size(g) == 1) return shard_branch_log_likelihood(g->shards[0], node, length, lnl, d1, d2);
-	ensure_scratch(g, 3);
-	int rc;
 	// lnL(t), its first and second derivative are sums over patterns, shard by shard
-	if ((rc = for_shards(g, [&](Shard *s, int i) {
-		     double *v = g->scratch[i].data();
-		     return shard_branch_log_likelihood(s, node, length, v, v + 1, v + 2);
-	     })))
-		return rc;
 	double total[3];
-	sum_shards(g, 3, total);
+	int rc;
+	if ((rc = sum_over_shards(g, 3, total, [&](Shard *s, double *v) { return shard_branch_log_likelihood(s, node, length, v, v + 1, v + 2); }))) return rc;
 	if (lnl) *lnl = total[0];
 	if (d1) *d1 = total[1];
 	if (d2) *d2 = total[2];
@@ -450,18 +463,11 @@ int phyamd_branch_hessian_diagonal(phyamd_engine *g, int flags, double *lnl, dou
 	CHECK_GROUP(g);
 	if (!lnl || !d2) return fail(PHYAMD_EINVAL, "null lnl or d2");
 	const size_t n = (size_t)1 + 2 * g->N;
-	ensure_scratch(g, n);
 	std::vector<double> total(n);
 	int rc;
-	if (group_size(g) == 1) {
-		if ((rc = shard_branch_hessian_diagonal(g->shards[0], flags, total.data()))) return rc;
-	} else {
-		// per-shard sums added like the gradient's: 2 / 4 / 8 shards cut by the engine's bisection give the one-engine bits
-		if ((rc = for_shards(g, [&](Shard *s, int i) { return shard_branch_hessian_diagonal(s, flags, g->scratch[i].data()); }))) return rc;
-		sum_shards(g, n, total.data());
-		if (std::isnan(total[0]) || std::isinf(total[0]))
-			for (size_t i = 1; i < n; i++) total[i] = NAN;
-	}
+	// per-shard sums added like the gradient's: 2 / 4 / 8 shards cut by the engine's bisection give the one-engine bits
+	if ((rc = sum_over_shards(g, n, total.data(), [&](Shard *s, double *v) { return shard_branch_hessian_diagonal(s, flags, v); }))) return rc;
+	mask_if_not_finite(total[0], total.data() + 1, n - 1);
 	*lnl = total[0];
 	if (d1) std::memcpy(d1, total.data() + 1, sizeof(double) * g->N);
 	std::memcpy(d2, total.data() + 1 + g->N, sizeof(double) * g->N);
@@ -474,19 +480,7 @@ int phyamd_gradient_batch(phyamd_engine *g, int flags, int32_t count, const doub
 	if (!branch_lengths || !lnl) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch: null branch_lengths or lnl");
 	CHECK_GROUP(g);
 	if (group_size(g) == 1) return shard_gradient_batch(g->shards[0], flags, count, branch_lengths, lnl, cat_gradient);
-	const size_t ncat = (size_t)g->N * g->C, n = (size_t)count * (cat_gradient ? 1 + ncat : 1);
-	ensure_scratch(g, n);
-	int rc;
-	if ((rc = for_shards(g, [&](Shard *s, int i) {
-		     double *v = g->scratch[i].data();  // [lnl[count] | cat_gradient[count][N C]]
-		     return shard_gradient_batch(s, flags, count, branch_lengths, v, cat_gradient ? v + count : nullptr);
-	     })))
-		return rc;
-	std::vector<double> total(n);
-	sum_shards(g, n, total.data());
-	std::memcpy(lnl, total.data(), sizeof(double) * count);
-	if (cat_gradient) std::memcpy(cat_gradient, total.data() + count, sizeof(double) * count * ncat);
-	return PHYAMD_OK;
+	return sum_batch_over_shards(g, count, lnl, cat_gradient, [&](Shard *s, double *l, double *cg) { return shard_gradient_batch(s, flags, count, branch_lengths, l, cg); });
 }
 
 // every shard runs the whole batch of trees on its patterns; per-item results are added like phyamd_gradient_batch's
@@ -496,36 +490,18 @@ int phyamd_gradient_batch_trees(phyamd_engine *g, int flags, int32_t count, cons
 	if (!left || !right || !roots || !branch_lengths || !lnl) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch_trees: null left, right, roots, branch_lengths or lnl");
 	CHECK_GROUP(g);
 	if (group_size(g) == 1) return shard_gradient_batch_trees(g->shards[0], flags, count, left, right, roots, branch_lengths, lnl, cat_gradient);
-	const size_t ncat = (size_t)g->N * g->C, n = (size_t)count * (cat_gradient ? 1 + ncat : 1);
-	ensure_scratch(g, n);
-	int rc;
-	if ((rc = for_shards(g, [&](Shard *s, int i) {
-		     double *v = g->scratch[i].data();  // [lnl[count] | cat_gradient[count][N C]]
-		     return shard_gradient_batch_trees(s, flags, count, left, right, roots, branch_lengths, v, cat_gradient ? v + count : nullptr);
-	     })))
-		return rc;
-	std::vector<double> total(n);
-	sum_shards(g, n, total.data());
-	std::memcpy(lnl, total.data(), sizeof(double) * count);
-	if (cat_gradient) std::memcpy(cat_gradient, total.data() + count, sizeof(double) * count * ncat);
-	return PHYAMD_OK;
+	return sum_batch_over_shards(g, count, lnl, cat_gradient, [&](Shard *s, double *l, double *cg) { return shard_gradient_batch_trees(s, flags, count, left, right, roots, branch_lengths, l, cg); });
 }
 
 int phyamd_get_batch_profile(phyamd_engine *g, phyamd_batch_profile *out) {
-	CHECK_GROUP(g);
-	if (!out) return fail(PHYAMD_EINVAL, "null out");
-	int rc;
-	if ((rc = shard_get_batch_profile(g->shards[0], out))) return rc;
-	for (int i = 1; i < group_size(g); i++) {  // shards choose their paths themselves: the fewest fast items, the most of everything else
-		phyamd_batch_profile p;
-		if ((rc = shard_get_batch_profile(g->shards[i], &p))) return rc;
-		out->items_fast = std::min(out->items_fast, p.items_fast);
-		out->items_sequential = std::max(out->items_sequential, p.items_sequential);
-		out->chunks = std::max(out->chunks, p.chunks);
-		out->scratch_bytes += p.scratch_bytes;
-		out->ms = std::max(out->ms, p.ms);
-	}
-	return PHYAMD_OK;
+	// shards choose their paths themselves: the fewest fast items, the most of everything else
+	return merged_profile(g, &Shard::batch_prof, out, [](phyamd_batch_profile &o, const phyamd_batch_profile &p) {
+		o.items_fast = std::min(o.items_fast, p.items_fast);
+		o.items_sequential = std::max(o.items_sequential, p.items_sequential);
+		o.chunks = std::max(o.chunks, p.chunks);
+		o.scratch_bytes += p.scratch_bytes;
+		o.ms = std::max(o.ms, p.ms);
+	});
 }
 
 // every shard scores the whole neighbourhood on its patterns; lnl, d1 and d2 are sums over patterns, added in shard order
@@ -536,14 +512,8 @@ int phyamd_nni_log_likelihoods(phyamd_engine *g, int flags, const double *centra
 	const bool deriv = d1 || d2;
 	std::vector<double> total(n);
 	int rc;
-	if (group_size(g) == 1) {
-		if ((rc = shard_nni_log_likelihoods(g->shards[0], flags, central_lengths, deriv, total.data()))) return rc;
-	} else {
-		ensure_scratch(g, n);
-		if ((rc = for_shards(g, [&](Shard *s, int i) { return shard_nni_log_likelihoods(s, flags, central_lengths, deriv, g->scratch[i].data()); }))) return rc;
-		sum_shards(g, n, total.data());
-		nni_mask_derivatives(entries, total.data());
-	}
+	if ((rc = sum_over_shards(g, n, total.data(), [&](Shard *s, double *v) { return shard_nni_log_likelihoods(s, flags, central_lengths, deriv, v); }))) return rc;
+	nni_mask_derivatives(entries, total.data());
 	std::memcpy(lnl, total.data(), sizeof(double) * entries);
 	if (d1) std::memcpy(d1, total.data() + entries, sizeof(double) * entries);
 	if (d2) std::memcpy(d2, total.data() + 2 * entries, sizeof(double) * entries);
@@ -551,17 +521,11 @@ int phyamd_nni_log_likelihoods(phyamd_engine *g, int flags, const double *centra
 }
 
 int phyamd_get_nni_profile(phyamd_engine *g, phyamd_nni_profile *out) {
-	CHECK_GROUP(g);
-	if (!out) return fail(PHYAMD_EINVAL, "null out");
-	int rc;
-	if ((rc = shard_get_nni_profile(g->shards[0], out))) return rc;
-	for (int i = 1; i < group_size(g); i++) {  // the slowest shard is what the caller waits for; memory adds up
-		phyamd_nni_profile p;
-		if ((rc = shard_get_nni_profile(g->shards[i], &p))) return rc;
-		out->scratch_bytes += p.scratch_bytes;
-		out->ms = std::max(out->ms, p.ms);
-	}
-	return PHYAMD_OK;
+	// the slowest shard is what the caller waits for; memory adds up
+	return merged_profile(g, &Shard::nni_prof, out, [](phyamd_nni_profile &o, const phyamd_nni_profile &p) {
+		o.scratch_bytes += p.scratch_bytes;
+		o.ms = std::max(o.ms, p.ms);
+	});
 }
 
 // every shard scores every row on its patterns; the rows are sums over patterns, added in shard order (NaN cells stay NaN)
@@ -570,32 +534,20 @@ int phyamd_spr_log_likelihoods(phyamd_engine *g, int flags, int32_t count, const
 	if (!lnl) return fail(PHYAMD_EINVAL, "phyamd_spr_log_likelihoods: null lnl");
 	CHECK_GROUP(g);
 	const auto t0 = std::chrono::steady_clock::now();
-	int rc;
-	if (group_size(g) == 1) rc = shard_spr_log_likelihoods(g->shards[0], flags, count, prune, lnl);
-	else {
-		const size_t n = (size_t)count * g->N;
-		ensure_scratch(g, n);
-		rc = for_shards(g, [&](Shard *s, int i) { return shard_spr_log_likelihoods(s, flags, count, prune, g->scratch[i].data()); });
-		if (!rc) sum_shards(g, n, lnl);
-	}
+	const int rc = sum_over_shards(g, (size_t)count * g->N, lnl, [&](Shard *s, double *v) { return shard_spr_log_likelihoods(s, flags, count, prune, v); });
 	g->spr_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 	return rc;
 }
 
 int phyamd_get_spr_profile(phyamd_engine *g, phyamd_spr_profile *out) {
-	CHECK_GROUP(g);
-	if (!out) return fail(PHYAMD_EINVAL, "null out");
-	int rc;
-	if ((rc = shard_get_spr_profile(g->shards[0], out))) return rc;
-	for (int i = 1; i < group_size(g); i++) {  // candidates and memory add up; the shards choose their chunks themselves: the most
-		phyamd_spr_profile p;
-		if ((rc = shard_get_spr_profile(g->shards[i], &p))) return rc;
-		out->chunks = std::max(out->chunks, p.chunks);
-		out->candidates += p.candidates;
-		out->scratch_bytes += p.scratch_bytes;
-	}
-	out->ms = g->spr_ms;
-	return PHYAMD_OK;
+	// candidates and memory add up; the shards choose their chunks themselves: the most
+	const int rc = merged_profile(g, &Shard::spr_prof, out, [](phyamd_spr_profile &o, const phyamd_spr_profile &p) {
+		o.chunks = std::max(o.chunks, p.chunks);
+		o.candidates += p.candidates;
+		o.scratch_bytes += p.scratch_bytes;
+	});
+	if (!rc) out->ms = g->spr_ms;
+	return rc;
 }
 
 // per-pattern results: every shard fills its own pattern range of the caller's arrays, so a pattern's bits do not depend on the
@@ -611,7 +563,8 @@ int phyamd_state_posteriors(phyamd_engine *g, int flags, int32_t count, const in
 		return rc;
 	double lnl;
 	sum_shards(g, 1, &lnl);
-	post_mask_rows(lnl, (size_t)count * g->P, g->S, posteriors, states);
+	mask_if_not_finite(lnl, posteriors, (size_t)count * g->P * g->S);
+	mask_states_if_not_finite(lnl, states, (size_t)count * g->P);
 	return PHYAMD_OK;
 }
 
@@ -632,19 +585,14 @@ int phyamd_branch_hessian(phyamd_engine *g, int flags, double *lnl, double *grad
 	int rc;
 	if (group_size(g) == 1) rc = shard_branch_hessian(g->shards[0], flags, lnl, gradient, hessian);
 	else {
-		const size_t N = (size_t)g->N, n = 1 + N + N * N;
-		ensure_scratch(g, n);
-		rc = for_shards(g, [&](Shard *s, int i) {
-			double *v = g->scratch[i].data();  // [lnl | gradient [N] | hessian [N][N]]
-			return shard_branch_hessian(s, flags, v, v + 1, v + 1 + N);
-		});
+		const size_t N = (size_t)g->N;
+		std::vector<double> total(1 + N + N * N);  // [lnl | gradient [N] | hessian [N][N]]
+		rc = sum_over_shards(g, total.size(), total.data(), [&](Shard *s, double *v) { return shard_branch_hessian(s, flags, v, v + 1, v + 1 + N); });
 		if (!rc) {
-			std::vector<double> total(n);
-			sum_shards(g, n, total.data());
+			mask_if_not_finite(total[0], total.data() + 1, N + N * N);
 			*lnl = total[0];
 			if (gradient) std::memcpy(gradient, total.data() + 1, sizeof(double) * N);
 			std::memcpy(hessian, total.data() + 1 + N, sizeof(double) * N * N);
-			bhess_mask(*lnl, N, gradient, hessian);
 		}
 	}
 	g->bhess_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -652,18 +600,13 @@ int phyamd_branch_hessian(phyamd_engine *g, int flags, double *lnl, double *grad
 }
 
 int phyamd_get_hessian_profile(phyamd_engine *g, phyamd_hessian_profile *out) {
-	CHECK_GROUP(g);
-	if (!out) return fail(PHYAMD_EINVAL, "null out");
-	int rc;
-	if ((rc = shard_get_hessian_profile(g->shards[0], out))) return rc;
-	for (int i = 1; i < group_size(g); i++) {  // memory adds up; the shards choose their chunks themselves: the most
-		phyamd_hessian_profile p;
-		if ((rc = shard_get_hessian_profile(g->shards[i], &p))) return rc;
-		out->chunks = std::max(out->chunks, p.chunks);
-		out->scratch_bytes += p.scratch_bytes;
-	}
-	out->ms = g->bhess_ms;
-	return PHYAMD_OK;
+	// memory adds up; the shards choose their chunks themselves: the most
+	const int rc = merged_profile(g, &Shard::bhess_prof, out, [](phyamd_hessian_profile &o, const phyamd_hessian_profile &p) {
+		o.chunks = std::max(o.chunks, p.chunks);
+		o.scratch_bytes += p.scratch_bytes;
+	});
+	if (!rc) out->ms = g->bhess_ms;
+	return rc;
 }
 
 // device-resident results (one process per GPU: the caller reduces them across processes with ONE RCCL all-reduce)

@@ -7,7 +7,8 @@
 //   phyamd_schedule.inc     level and tree-walk schedules, device storage
 //   phyamd_launch.inc       kernel launches per pass
 //   phyamd_eval.inc         one evaluation (incremental updates, lazy rescaling, gradients, pattern tiling)
-//   phyamd_shard_api.inc    per-device half of the C ABI
+//   phyamd_shard_api.inc    per-device half of the C ABI: creation, setters, evaluations, single-branch calls, inspection
+//   phyamd_queries.inc      ... and its whole-tree query calls: batches, NNI and SPR scores, posteriors, the full branch Hessian
 //   phyamd_abi.inc          extern "C" entry points: a handle is a group of 1..n shards on 1..n GPUs
 //
 // Replaces the CPU hot path of physher's SingleTreeLikelihood (src/phyc/treelikelihood.c and the per-state-count kernel files)
@@ -137,6 +138,7 @@ struct NodeOp {
 #include "phyamd_launch.inc"
 #include "phyamd_eval.inc"
 #include "phyamd_shard_api.inc"
+#include "phyamd_queries.inc"
 
 }  // namespace
 

@@ -42,6 +42,8 @@ public:
 		std::swap(p_, o.p_);
 		std::swap(bytes_, o.bytes_);
 	}
+	// at least `bytes` (0: one), whatever the element type; see reserve
+	int ensure_bytes(size_t bytes) { return reserve(std::max<size_t>(bytes, 1), nullptr); }
 
 protected:
 	// at least `bytes`: kept if it holds as many, else freed and allocated anew (*grew: the old contents are gone)
@@ -94,4 +96,48 @@ public:
 	size_t size() const { return bytes_ / sizeof(T); }
 	// at least `count` elements (0: one); see reserve
 	int ensure(size_t count, bool *grew = nullptr) { return reserve(std::max<size_t>(count, 1) * sizeof(T), grew); }
+};
+
+// What a call needs of a group of scratch arrays to work on n items at once: array by array, so many bytes per item and so many
+// whatever n.  The one description of a call's scratch: the bytes a chunk is sized by, whether what is held serves n items, and
+// the allocation itself are all read off this list.
+struct ScratchPlan {
+	struct Entry {
+		DeviceBuffer *array;
+		size_t item_bytes, fixed_bytes;
+		bool once;  // item_bytes are counted for every item but allocated once (spr_plan)
+		size_t bytes(size_t n) const { return fixed_bytes + (once ? 1 : n) * item_bytes; }
+	};
+	std::vector<Entry> entries;
+	void add(DeviceBuffer &array, size_t item_bytes, size_t fixed_bytes = 0, bool once = false) { entries.push_back(Entry{&array, item_bytes, fixed_bytes, once}); }
+	size_t item_bytes() const {
+		size_t b = 0;
+		for (const Entry &x : entries) b += x.item_bytes;
+		return b;
+	}
+	size_t fixed_bytes() const {
+		size_t b = 0;
+		for (const Entry &x : entries) b += x.fixed_bytes;
+		return b;
+	}
+	// items that fit in `room` bytes (a double: compared before it is cut to a count; below 1: not even one)
+	double items_in(double room) const { return std::floor((room - (double)fixed_bytes()) / (double)item_bytes()); }
+	// the arrays hold n items already
+	bool held(size_t n) const {
+		return std::all_of(entries.begin(), entries.end(), [n](const Entry &x) { return x.array->bytes() >= x.bytes(n); });
+	}
+	// every array at least at its size for n items (an array that holds as much is kept: DeviceBuffer::reserve)
+	int allocate(size_t n) const {
+		for (const Entry &x : entries)
+			if (int rc = x.array->ensure_bytes(x.bytes(n))) return rc;
+		return PHYAMD_OK;
+	}
+	// also what `other` needs: its entries this plan lacks, and of an array both name the larger sizes
+	void merge(const ScratchPlan &other) {
+		for (const Entry &o : other.entries) {
+			const auto mine = std::find_if(entries.begin(), entries.end(), [&o](const Entry &x) { return x.array == o.array; });
+			if (mine == entries.end()) entries.push_back(o);
+			else mine->item_bytes = std::max(mine->item_bytes, o.item_bytes), mine->fixed_bytes = std::max(mine->fixed_bytes, o.fixed_bytes);
+		}
+	}
 };

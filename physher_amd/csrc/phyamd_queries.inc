@@ -1,0 +1,1028 @@
+// phyamd_queries.inc -- the whole-tree query calls on one shard: batches of branch-length vectors and of trees, NNI and SPR scores,
+// per-pattern posteriors and the full branch Hessian.  They read what the engine holds and write only their own scratch
+// (part of phyamd_engine.hip: one translation unit, internal linkage)
+
+// ---- what the calls share ------------------------------------------------------------------------------------------------------
+
+// the in-band rule for an evaluation whose lnL is NaN / inf (treelikelihood.c:327-332): everything derived from it is NaN, a
+// most probable state 255.  (Per entry, one lnL each: nni_mask_derivatives)
+bool not_finite(double lnl) { return std::isnan(lnl) || std::isinf(lnl); }
+void mask_if_not_finite(double lnl, double *values, size_t n) {
+	if (values && not_finite(lnl)) std::fill(values, values + n, NAN);
+}
+void mask_states_if_not_finite(double lnl, uint8_t *states, size_t n) {
+	if (states && not_finite(lnl)) std::fill(states, states + n, (uint8_t)255);
+}
+
+// ready but for the lengths, which the call brings itself
+int check_ready_but_lengths(Shard *e) {
+	const bool had = e->have_lengths;
+	e->have_lengths = true;
+	const int rc = check_ready(e);
+	e->have_lengths = had;
+	return rc;
+}
+
+// every partial resident: the engine becomes one with phyamd_set_keep_partials(1) that has run the flags-0 gradient
+int require_resident_partials(Shard *e, const char *call) {
+	int rc;
+	if (!e->keep_partials && (rc = shard_set_keep_partials(e, 1))) return rc;
+	if ((!uppers_resident(e) || !lowers_current(e)) && (rc = eval_gradient(e, 0))) return rc;
+	if ((rc = require_reference_form(e))) return rc;  // (stored partials: the partials themselves, in the reference's form)
+	if (!uppers_resident(e) || e->core_index[e->root] < 0) return fail(PHYAMD_EDEVICE, "%s: the gradient left no resident partials", call);
+	return PHYAMD_OK;
+}
+
+// transition matrices of `items` branch-length vectors [items][N] on the device -> mats [items][N][C][16]; roots: per item, or null:
+// the engine's
+void launch_batch_matrices(Shard *e, int items, const double *lengths, const int32_t *roots, double *mats) {
+	const size_t total = (size_t)items * e->N * e->C * 16;
+	hipLaunchKernelGGL(k_batch_matrices, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, e->stream, e->C, e->N, items, e->d_model, e->d_rates, lengths,
+	                   e->root, roots, mats);
+}
+
+size_t batch_scratch_bytes(const Shard *e) { return (size_t)e->batch_mem.bytes; }
+
+// the frame of a call that keeps a profile: the device bound, the body run on `prof` (what the entry point knows beforehand), and
+// the profile stored -- also of a call that failed -- with the scratch the call leaves and its wall time
+template <typename Prof, typename Body>
+int profiled_call(Shard *e, Prof Shard::*slot, Prof prof, Body body) {
+	const auto t0 = std::chrono::steady_clock::now();
+	int rc;
+	if ((rc = bind_device(e))) return rc;
+	rc = body(prof);
+	prof.scratch_bytes = (int64_t)batch_scratch_bytes(e);
+	prof.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	e->*slot = prof;
+	return rc;
+}
+
+// ---- a batch of branch-length vectors (phyamd_gradient_batch) ----------------------------------------------------------------
+
+// the two op lists of the batched walk for a tree (T tips; left / right / root in phyamd_set_topology's convention, already
+// validated), appended to `ops` as [post-order T - 1 | pre-order T - 1]; returns the upper slots the pre-order list parks in.
+// ops == null: only counts the slots.  Post-order: depth first, the larger subtree first, so that the child finished last hands
+// its partial on in registers.  Pre-order: of two internal children the smaller subtree is entered first with its upper in
+// registers and the other's upper is parked in a slot that is free again once its op has read it: at most log2(T) + 1 slots,
+// whatever the shape (a caterpillar parks nothing).  Ties go by left / right, never by node id: the lists of one tree under two
+// labellings of its internal nodes differ in the ids only.
+// park_all (phyamd_nni_log_likelihoods): every internal child's upper is parked in a slot of its own, slot = node - T, and none
+// is handed on in registers: T - 1 slots, and after the walk every internal non-root node's upper is in the scratch.
+int build_batch_ops(int T, const int32_t *left, const int32_t *right, int root, std::vector<BatchOp> *ops, bool park_all = false) {
+	const int N = 2 * T - 1;
+	std::vector<int> size(N, 1), order;
+	{
+		std::vector<int> stack{root};
+		while (!stack.empty()) {
+			const int n = stack.back();
+			stack.pop_back();
+			order.push_back(n);
+			if (n >= T) {
+				stack.push_back(left[n]);
+				stack.push_back(right[n]);
+			}
+		}
+		for (size_t i = order.size(); i-- > 0;)
+			if (order[i] >= T) size[order[i]] += size[left[order[i]]] + size[right[order[i]]];
+	}
+	if (ops) {  // post-order: (node, children done?) on an explicit stack
+		std::vector<std::pair<int, bool>> stack{{root, false}};
+		int last = -1;
+		while (!stack.empty()) {
+			const auto [n, done] = stack.back();
+			stack.pop_back();
+			const int l = left[n], r = right[n];
+			if (!done) {
+				stack.push_back({n, true});
+				const int first = size[l] >= size[r] ? l : r, second = first == l ? r : l;
+				if (second >= T) stack.push_back({second, false});
+				if (first >= T) stack.push_back({first, false});
+				continue;
+			}
+			BatchOp op{n, l, r, last == l && l >= T ? 1 : last == r && r >= T ? 2 : 0, BATCH_NONE, BATCH_NONE, BATCH_NONE, 0};
+			ops->push_back(op);
+			last = n;
+		}
+	}
+	int slots = 0;
+	{  // pre-order
+		std::vector<std::pair<int, int>> stack{{root, BATCH_ROOT}};  // (node, where its upper is)
+		std::vector<int> free_slots;
+		while (!stack.empty()) {
+			const auto [n, src] = stack.back();
+			stack.pop_back();
+			const int l = left[n], r = right[n];
+			BatchOp op{n, l, r, 0, src, BATCH_NONE, BATCH_NONE, 0};
+			if (park_all) {
+				if (l >= T) op.dst_left = l - T, stack.push_back({l, l - T});
+				if (r >= T) op.dst_right = r - T, stack.push_back({r, r - T});
+				if (ops) ops->push_back(op);
+				continue;
+			}
+			if (l >= T && r >= T) {
+				int slot;
+				if (free_slots.empty()) slot = slots++;
+				else {
+					slot = free_slots.back();
+					free_slots.pop_back();
+				}
+				const bool left_first = size[l] <= size[r];
+				op.dst_left = left_first ? BATCH_CARRY : slot;
+				op.dst_right = left_first ? slot : BATCH_CARRY;
+				stack.push_back({left_first ? r : l, slot});
+				stack.push_back({left_first ? l : r, BATCH_CARRY});
+			} else if (l >= T) {
+				op.dst_left = BATCH_CARRY;
+				stack.push_back({l, BATCH_CARRY});
+			} else if (r >= T) {
+				op.dst_right = BATCH_CARRY;
+				stack.push_back({r, BATCH_CARRY});
+			}
+			if (ops) ops->push_back(op);
+			if (src >= 0) free_slots.push_back(src);  // read by this op: later ops may park in it
+		}
+	}
+	return park_all ? std::max(1, T - 1) : std::max(1, slots);
+}
+
+// the engine's own lists (a batch of branch-length vectors), built once per topology
+int ensure_engine_batch_ops(Shard *e) {
+	if (e->batch_left == e->left && e->batch_right == e->right && e->batch_root == e->root && !e->batch_ops.empty() && e->d_batch_ops.get()) return PHYAMD_OK;
+	e->batch_left = e->left;
+	e->batch_right = e->right;
+	e->batch_root = e->root;
+	e->batch_ops.clear();
+	e->batch_upper_slots = build_batch_ops(e->T, e->left.data(), e->right.data(), e->root, &e->batch_ops);
+	int rc;
+	if ((rc = e->d_batch_ops.ensure(e->batch_ops.size()))) {
+		e->batch_ops.clear();
+		return rc;
+	}
+	HIP_TRY(hipMemcpyAsync(e->d_batch_ops, e->batch_ops.data(), sizeof(BatchOp) * e->batch_ops.size(), hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	return PHYAMD_OK;
+}
+
+size_t nni_candidates(const Shard *e) { return (size_t)std::max(0, e->T - 2); }
+
+// What a call needs of the batch scratch per item (ScratchPlan).  The batched walk's arrays are the common base: an item's lengths,
+// matrices and result rows, its stored lowers and per-block lnL, and with the pre-order pass (grad) so many parked uppers (slots)
+// and the gradient slab; trees: the items walk their own op lists from their own roots
+ScratchPlan batch_plan(Shard *e, bool grad, int slots, bool trees) {
+	const size_t D = sizeof(double), N = (size_t)e->N, C = (size_t)e->C, nblk = ((size_t)e->P + WAVE - 1) / WAVE, plane = nblk * WAVE * 4;
+	ScratchPlan p;
+	p.add(e->d_batch_len, D * N);
+	p.add(e->d_batch_mats, D * N * C * 16);
+	p.add(e->d_batch_out, D * (grad ? 1 + N * C : 1));
+	p.add(e->d_batch_lower, D * (size_t)(e->T - 1) * C * plane);
+	p.add(e->d_batch_lnl, D * nblk);
+	if (grad) {
+		p.add(e->d_batch_upper, D * (size_t)slots * C * plane);
+		p.add(e->d_batch_slab, D * nblk * C * N);
+	}
+	if (trees) {
+		p.add(e->d_batch_item_ops, sizeof(BatchOp) * 2 * (size_t)(e->T - 1));
+		p.add(e->d_batch_roots, sizeof(int32_t));
+	}
+	return p;
+}
+
+// phyamd_nni_log_likelihoods: ONE item with every upper parked (slots = T - 1), and whatever the item count the op lists, the
+// candidates and their index by node, the trial lengths and matrices, the slab and the result
+ScratchPlan nni_plan(Shard *e) {
+	const size_t D = sizeof(double), N = (size_t)e->N, C = (size_t)e->C, nblk = ((size_t)e->P + WAVE - 1) / WAVE, cands = std::max<size_t>(nni_candidates(e), 1);
+	ScratchPlan p = batch_plan(e, true, e->T - 1, false);
+	p.add(e->d_nni_ops, 0, sizeof(BatchOp) * 2 * (size_t)(e->T - 1));
+	p.add(e->d_nni_cands, 0, sizeof(NniCand) * cands);
+	p.add(e->d_nni_cand_of, 0, sizeof(int32_t) * N);
+	p.add(e->d_nni_len, 0, D * 3 * N);
+	p.add(e->d_nni_mats, 0, D * 3 * N * C * 16);
+	p.add(e->d_nni_slab, 0, D * cands * nblk * 9);
+	p.add(e->d_nni_out, 0, D * 9 * N);
+	return p;
+}
+
+// phyamd_spr_log_likelihoods: an item is a ROW -- every upper parked, its own op lists, its candidates, their index by cell, the
+// slab and the result.  The two length vectors and their matrices are allocated once but counted for every row when a chunk is
+// sized: an over-count of 16 N (1 + 16 C) bytes per row beyond the first, which the capped tests' chunk counts are pinned to
+ScratchPlan spr_plan(Shard *e) {
+	const size_t D = sizeof(double), N = (size_t)e->N, C = (size_t)e->C, nblk = ((size_t)e->P + WAVE - 1) / WAVE;
+	ScratchPlan p = batch_plan(e, true, e->T - 1, true);
+	p.add(e->d_spr_cands, sizeof(SprCand) * N);
+	p.add(e->d_spr_cand_of, sizeof(int32_t) * N);
+	p.add(e->d_spr_slab, D * N * nblk);
+	p.add(e->d_spr_out, D * N);
+	p.add(e->d_spr_len, D * 2 * N, 0, true);
+	p.add(e->d_spr_mats, D * 2 * N * C * 16, 0, true);
+	return p;
+}
+
+void release_batch_scratch(Shard *e) {
+	e->batch_mem.release_all();
+	e->batch_held = ScratchPlan{};
+	e->batch_items = 0;
+}
+
+// items of `plan` the scratch holds now (none once the group has been released to make room)
+size_t batch_items_held(const Shard *e, const ScratchPlan &plan) { return plan.held(e->batch_items) ? e->batch_items : 0; }
+
+constexpr int BATCH_MAX_CHUNK = 65535;  // gridDim.y
+
+// items of a batch (count items of `plan`) whose scratch fits beside the engine (scratch_room).  What the scratch holds already is
+// kept unless more items would fit.
+size_t batch_items_that_fit(const Shard *e, size_t count, const ScratchPlan &plan) {
+	const size_t want = std::min<size_t>(count, BATCH_MAX_CHUNK), have = batch_items_held(e, plan);
+	if (have >= want) return want;
+	const double fit = plan.items_in(scratch_room(e, (double)batch_scratch_bytes(e), EngineRoom::MayGrow));
+	if (fit <= (double)have) return have;
+	return (size_t)std::min((double)want, fit);
+}
+
+int allocate_batch_scratch(Shard *e, size_t items, const ScratchPlan &plan) {
+	release_batch_scratch(e);  // (the arrays grow together: all are freed before any is allocated again)
+	if (int rc = plan.allocate(items)) {
+		release_batch_scratch(e);
+		return rc;
+	}
+	e->batch_held = plan;
+	e->batch_items = items;
+	e->nni_lists_valid = false;  // (freed above with everything else)
+	return PHYAMD_OK;
+}
+
+int ensure_batch_scratch(Shard *e, size_t items, const ScratchPlan &plan) {
+	if (batch_items_held(e, plan) >= items) return PHYAMD_OK;
+	if (e->cfg.max_device_bytes <= 0 && e->batch_items > 0 && e->batch_held.held(e->batch_items)) {
+		// without a cap the scratch keeps what the previous call needed as well -- the held plan's entries that this one lacks, and
+		// of an array both name the larger size: calls of several kinds, or of trees that park in fewer and in more slots, may
+		// alternate without an allocation each (under a cap every call gets exactly its own)
+		ScratchPlan both = plan;
+		both.merge(e->batch_held);
+		if (allocate_batch_scratch(e, items, both) == PHYAMD_OK) return PHYAMD_OK;
+	}
+	return allocate_batch_scratch(e, items, plan);
+}
+
+// one chunk of `items` items through the batched walk: lengths [items][N] (host) -> out [items][rows] (host), rows = 1 or 1 + N C.
+// trees: the items walk their own op lists from their own roots, already in d_batch_item_ops and d_batch_roots; else the
+// engine's.  slots: the upper slots an item of this chunk has in d_batch_upper (at least what its list parks in)
+int run_batch_chunk(Shard *e, int flags, int items, const double *lengths, bool grad, int slots, bool trees, double *out) {
+	const int nblk = (e->P + WAVE - 1) / WAVE, rows = grad ? 1 + e->N * e->C : 1, nops = e->T - 1;
+	const BatchOp *ops = trees ? e->d_batch_item_ops.get() : e->d_batch_ops.get();
+	const int32_t *roots = trees ? e->d_batch_roots.get() : nullptr;
+	HIP_TRY(hipMemcpyAsync(e->d_batch_len, lengths, sizeof(double) * (size_t)items * e->N, hipMemcpyHostToDevice, e->stream));
+	launch_batch_matrices(e, items, e->d_batch_len, roots, e->d_batch_mats);
+	const BatchArgs a{ops, ops + nops, trees ? 2 * nops : 0, e->T, e->N, e->P, e->C, nblk, slots, grad ? 1 : 0, e->d_tipmask, e->d_freqs, e->d_props,
+	                  e->d_weights, e->d_Q, e->d_batch_mats, e->d_batch_lower, e->d_batch_upper, e->d_batch_lnl, e->d_batch_slab};
+	const dim3 grid(nblk, items), block(WAVE, e->C);
+	if (flags & PHYAMD_GRAD_FOLD_ROOT_FREQS) hipLaunchKernelGGL(k_batch_walk4<true>, grid, block, 0, e->stream, a);
+	else hipLaunchKernelGGL(k_batch_walk4<false>, grid, block, 0, e->stream, a);
+	hipLaunchKernelGGL(k_batch_finish, dim3((unsigned)(((size_t)items * rows + 255) / 256)), dim3(256), 0, e->stream, items, e->N, e->C, nblk, e->root, roots, rows,
+	                   e->d_batch_lnl, e->d_batch_slab, e->d_batch_out);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(out, e->d_batch_out, sizeof(double) * (size_t)items * rows, hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	return PHYAMD_OK;
+}
+
+// an item's row of the batched walk [lnl | gradient [N C]] into the caller's arrays, a lnL that is not finite in band
+void store_batch_item(const double *row, size_t ncat, double *lnl, double *cat_gradient) {
+	*lnl = row[0];
+	if (!cat_gradient) return;
+	std::copy(row + 1, row + 1 + ncat, cat_gradient);
+	mask_if_not_finite(row[0], cat_gradient, ncat);
+}
+
+// the definition of the call: item by item through the ordinary path (the caller puts the engine's lengths back)
+int batch_item_sequential(Shard *e, int flags, const double *lengths, double *lnl, double *cat_gradient) {
+	int rc;
+	if ((rc = shard_set_branch_lengths(e, lengths))) return rc;
+	return cat_gradient ? shard_gradient(e, flags, lnl, cat_gradient) : shard_log_likelihood(e, lnl);
+}
+
+// the items of a batch, each through the batched walk or the ordinary path; prof: how many went which way
+int run_batch(Shard *e, int flags, int32_t count, const double *branch_lengths, double *lnl, double *cat_gradient, phyamd_batch_profile &prof) {
+	int rc;
+	if ((rc = check_ready_but_lengths(e))) return rc;
+	for (int n = 0; n < e->N; n++)
+		if (n != e->root && e->explicit_host[n])
+			return fail(PHYAMD_EUNSUPPORTED, "phyamd_gradient_batch: node %d has explicit matrices, which cannot follow per-item branch lengths", n);
+	if (cat_gradient && !e->have_Q) return fail(PHYAMD_EINVAL, "the gradient needs the rate matrix: phyamd_set_eigen or phyamd_set_rate_matrix");
+	const bool grad = cat_gradient != nullptr;
+	const size_t N = (size_t)e->N, ncat = N * e->C, rows = grad ? 1 + ncat : 1;
+	std::vector<uint8_t> redo(count, 1);  // items the sequential path (still) has to evaluate
+	if ((rc = ensure_engine_batch_ops(e))) return rc;
+	const ScratchPlan plan = batch_plan(e, grad, e->batch_upper_slots, false);
+	std::vector<double> lengths, out;
+	for (size_t first = 0; first < (size_t)count && batch_fast_path(e, flags, 1);) {
+		// (every chunk asks again: an item that went through the ordinary path may have taken the scratch's room)
+		const size_t chunk = batch_items_that_fit(e, (size_t)count - first, plan);
+		if (!batch_fast_path(e, flags, chunk)) break;
+		if ((rc = ensure_batch_scratch(e, chunk, plan))) return rc;
+		const size_t items = std::min(chunk, (size_t)count - first);
+		lengths.assign(branch_lengths + first * N, branch_lengths + (first + items) * N);
+		out.resize(items * rows);
+		for (size_t b = 0; b < items; b++) lengths[b * N + e->root] = 0.0;  // (ignored, as phyamd_set_branch_lengths does)
+		if ((rc = run_batch_chunk(e, flags, (int)items, lengths.data(), grad, e->batch_upper_slots, false, out.data()))) return rc;
+		prof.chunks++;
+		for (size_t b = 0; b < items; b++) {
+			const double l = out[b * rows];
+			if (not_finite(l) && e->cfg.rescale == PHYAMD_RESCALE_AUTO) {
+				// the lazy switch's case (treelikelihood.c:1496-1519): this item goes through the ordinary path right away, and
+				// if that turns rescaling on, so does the rest of the batch
+				if ((rc = batch_item_sequential(e, flags, branch_lengths + (first + b) * N, lnl + first + b, grad ? cat_gradient + (first + b) * ncat : nullptr))) return rc;
+				redo[first + b] = 0;
+				prof.items_sequential++;
+				continue;
+			}
+			store_batch_item(&out[b * rows], ncat, lnl + first + b, grad ? cat_gradient + (first + b) * ncat : nullptr);
+			redo[first + b] = 0;
+			prof.items_fast++;
+		}
+		first += items;
+	}
+	for (int b = 0; b < count; b++) {
+		if (!redo[b]) continue;
+		if ((rc = batch_item_sequential(e, flags, branch_lengths + (size_t)b * N, lnl + b, grad ? cat_gradient + (size_t)b * ncat : nullptr))) return rc;
+		prof.items_sequential++;
+	}
+	return PHYAMD_OK;
+}
+
+int shard_gradient_batch(Shard *e, int flags, int32_t count, const double *branch_lengths, double *lnl, double *cat_gradient) {
+	CHECK_ENGINE(e);
+	if (count < 1) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch: count must be >= 1 (got %d)", count);
+	if (!branch_lengths || !lnl) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch: null branch_lengths or lnl");
+	return profiled_call(e, &Shard::batch_prof, phyamd_batch_profile{}, [&](phyamd_batch_profile &prof) {
+		const std::vector<double> lengths = e->lengths;
+		const bool had_lengths = e->have_lengths;
+		int rc = run_batch(e, flags, count, branch_lengths, lnl, cat_gradient, prof);
+		if (prof.items_sequential > 0 || rc) {  // the ordinary path has set items' lengths: the engine's own go back
+			const std::string why = g_last_error;
+			if (had_lengths) {
+				const int rc2 = shard_set_branch_lengths(e, lengths.data());
+				if (!rc) rc = rc2;
+				else g_last_error = why;
+			} else
+				e->have_lengths = false;
+		}
+		return rc;
+	});
+}
+
+// ---- a batch of trees (phyamd_gradient_batch_trees) ---------------------------------------------------------------------------
+
+// item `item` of a batch of trees is one binary tree over all 2T - 1 nodes in phyamd_set_topology's convention (build_schedule's
+// checks, on the item's arrays)
+int validate_batch_tree(int T, const int32_t *left, const int32_t *right, int root, int item, std::vector<int> &parents, std::vector<int> &stack) {
+	const int N = 2 * T - 1;
+	parents.assign(N, 0);
+	for (int n = 0; n < N; n++) {
+		const int l = left[n], r = right[n];
+		if (n < T) {
+			if (l != -1 || r != -1) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch_trees: item %d: node %d is a tip (id < tip_count) but has children", item, n);
+			continue;
+		}
+		if (l < 0 || r < 0 || l >= N || r >= N || l == r)
+			return fail(PHYAMD_EINVAL, "phyamd_gradient_batch_trees: item %d: internal node %d has invalid children (%d, %d)", item, n, l, r);
+		if (++parents[l] > 1 || ++parents[r] > 1) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch_trees: item %d: node %d or %d has two parents", item, l, r);
+	}
+	if (root < T || root >= N || parents[root] != 0) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch_trees: item %d: root %d is not a parentless internal node", item, root);
+	// (no node has two parents and the root has none: the walk from the root meets no node twice)
+	int reached = 0;
+	stack.assign(1, root);
+	while (!stack.empty()) {
+		const int n = stack.back();
+		stack.pop_back();
+		reached++;
+		if (n >= T) {
+			stack.push_back(left[n]);
+			stack.push_back(right[n]);
+		}
+	}
+	if (reached != N) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch_trees: item %d: the topology is not a single binary tree over all %d nodes", item, N);
+	return PHYAMD_OK;
+}
+
+// the items of a batch of trees through the batched walk, in chunks of what the scratch holds.  Per chunk: the items' op lists are
+// built and uploaded with their roots, the upper slots are those of the chunk's deepest-parking item, three launches
+int run_tree_batch(Shard *e, int flags, int32_t count, const int32_t *left, const int32_t *right, const int32_t *roots, const double *branch_lengths, double *lnl,
+                   double *cat_gradient, phyamd_batch_profile &prof) {
+	int rc;
+	if ((rc = check_ready_but_lengths(e))) return rc;
+	const bool grad = cat_gradient != nullptr;
+	if (const char *why = tree_batch_refusal(e, flags, 1)) return fail(PHYAMD_EUNSUPPORTED, "phyamd_gradient_batch_trees: %s", why);
+	if (grad && !e->have_Q) return fail(PHYAMD_EINVAL, "the gradient needs the rate matrix: phyamd_set_eigen or phyamd_set_rate_matrix");
+	const int T = e->T;
+	const size_t N = (size_t)e->N, ncat = N * e->C, rows = grad ? 1 + ncat : 1, nops = 2 * (size_t)(T - 1);
+	std::vector<int> slots(count);  // per item: the upper slots its pre-order list parks in
+	{
+		std::vector<int> parents, stack;
+		for (int32_t b = 0; b < count; b++) {  // every item, before anything is launched
+			const int32_t *l = left + (size_t)b * N, *r = right + (size_t)b * N;
+			if ((rc = validate_batch_tree(T, l, r, roots[b], b, parents, stack))) return rc;
+			slots[b] = grad ? build_batch_ops(T, l, r, roots[b], nullptr) : 1;
+		}
+	}
+	std::vector<double> lengths, out;
+	std::vector<BatchOp> ops;
+	for (size_t first = 0; first < (size_t)count;) {
+		// the chunk and its slot count settle each other: fewer items never need more slots
+		size_t items = std::min<size_t>((size_t)count - first, BATCH_MAX_CHUNK);
+		int chunk_slots = 1;
+		ScratchPlan plan;
+		for (;;) {
+			chunk_slots = *std::max_element(slots.begin() + first, slots.begin() + first + items);
+			plan = batch_plan(e, grad, chunk_slots, true);
+			const size_t fit = batch_items_that_fit(e, items, plan);
+			if (const char *why = tree_batch_refusal(e, flags, fit)) return fail(PHYAMD_EUNSUPPORTED, "phyamd_gradient_batch_trees: %s", why);
+			if (fit >= items) break;
+			items = fit;
+		}
+		if ((rc = ensure_batch_scratch(e, items, plan))) return rc;
+		const auto t0 = std::chrono::steady_clock::now();
+		ops.clear();
+		for (size_t b = first; b < first + items; b++) build_batch_ops(T, left + b * N, right + b * N, roots[b], &ops);
+		const auto t1 = std::chrono::steady_clock::now();
+		HIP_TRY(hipMemcpyAsync(e->d_batch_item_ops, ops.data(), sizeof(BatchOp) * items * nops, hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_batch_roots, roots + first, sizeof(int32_t) * items, hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipStreamSynchronize(e->stream));  // (ops is reused by the next chunk)
+		const auto t2 = std::chrono::steady_clock::now();
+		lengths.assign(branch_lengths + first * N, branch_lengths + (first + items) * N);
+		out.resize(items * rows);
+		for (size_t b = 0; b < items; b++) lengths[b * N + roots[first + b]] = 0.0;  // (ignored, as phyamd_set_branch_lengths does)
+		if ((rc = run_batch_chunk(e, flags, (int)items, lengths.data(), grad, chunk_slots, true, out.data()))) return rc;
+		if (e->batch_trace) {
+			const auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+			std::fprintf(stderr, "phyamd_gradient_batch_trees: chunk %d items %zu slots %d build_ms %.6f upload_ms %.6f\n", prof.chunks, items, chunk_slots, ms(t0, t1),
+			             ms(t1, t2));
+		}
+		prof.chunks++;
+		for (size_t b = 0; b < items; b++) {
+			// (a lnL that is not finite is in band whatever the rescaling mode: the engine is never switched)
+			store_batch_item(&out[b * rows], ncat, lnl + first + b, grad ? cat_gradient + (first + b) * ncat : nullptr);
+			prof.items_fast++;
+		}
+		first += items;
+	}
+	return PHYAMD_OK;
+}
+
+// reads the engine's inputs and writes only the batch scratch: nothing in Shard::state changes
+int shard_gradient_batch_trees(Shard *e, int flags, int32_t count, const int32_t *left, const int32_t *right, const int32_t *roots, const double *branch_lengths,
+                               double *lnl, double *cat_gradient) {
+	CHECK_ENGINE(e);
+	if (count < 1) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch_trees: count must be >= 1 (got %d)", count);
+	if (!left || !right || !roots || !branch_lengths || !lnl) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch_trees: null left, right, roots, branch_lengths or lnl");
+	return profiled_call(e, &Shard::batch_prof, phyamd_batch_profile{}, [&](phyamd_batch_profile &prof) {
+		return run_tree_batch(e, flags, count, left, right, roots, branch_lengths, lnl, cat_gradient, prof);
+	});
+}
+
+// ---- every NNI neighbour of the engine's tree (phyamd_nni_log_likelihoods) -----------------------------------------------------
+
+// the engine's tree's op lists with every upper parked, its candidate edges and their index by node, into the scratch
+int upload_nni_lists(Shard *e) {
+	if (e->nni_lists_valid && e->d_nni_ops.get()) return PHYAMD_OK;
+	const int T = e->T, N = e->N;
+	std::vector<BatchOp> ops;
+	build_batch_ops(T, e->left.data(), e->right.data(), e->root, &ops, true);
+	std::vector<NniCand> cands;
+	std::vector<int32_t> cand_of(N, -1);
+	for (int v = T; v < N; v++) {
+		if (v == e->root) continue;
+		const int u = e->parent[v];
+		cand_of[v] = (int32_t)cands.size();
+		cands.push_back(NniCand{v, u == e->root ? BATCH_ROOT : u, e->left[u] == v ? e->right[u] : e->left[u], e->left[v], e->right[v], {0, 0, 0}});
+	}
+	HIP_TRY(hipMemcpyAsync(e->d_nni_ops, ops.data(), sizeof(BatchOp) * ops.size(), hipMemcpyHostToDevice, e->stream));
+	if (!cands.empty()) HIP_TRY(hipMemcpyAsync(e->d_nni_cands, cands.data(), sizeof(NniCand) * cands.size(), hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipMemcpyAsync(e->d_nni_cand_of, cand_of.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));  // (stack-lifetime buffers)
+	e->nni_lists_valid = true;
+	return PHYAMD_OK;
+}
+
+// out [3 terms][3][N] (host): one walk of the engine's tree with every upper parked, the trial matrices, every edge's three
+// arrangements in one launch.  Reads the engine's inputs and writes only the batch scratch: nothing in Shard::state changes
+int run_nni(Shard *e, int flags, const double *central_lengths, bool deriv, double *out, phyamd_nni_profile &prof) {
+	int rc;
+	if ((rc = check_ready(e))) return rc;
+	if (flags != 0) return fail(PHYAMD_EUNSUPPORTED, "phyamd_nni_log_likelihoods: flags %d (no flags are defined: pass 0)", flags);
+	if (const char *why = tree_batch_refusal(e, 0, 1)) return fail(PHYAMD_EUNSUPPORTED, "phyamd_nni_log_likelihoods: %s", why);
+	if (!e->have_eigen || !e->have_Q)
+		return fail(PHYAMD_EINVAL, "phyamd_nni_log_likelihoods needs the eigen system (phyamd_set_eigen): the trial matrices, d1 and d2 are formed from it");
+	const int T = e->T, N = e->N, C = e->C;
+	// the trial lengths: a candidate's own three, every other entry the engine's (ignored: no arrangement reads that matrix)
+	std::vector<double> trial((size_t)3 * N);
+	for (int k = 0; k < 3; k++) std::copy(e->lengths.begin(), e->lengths.end(), trial.begin() + (size_t)k * N);
+	for (int v = T; v < N && central_lengths; v++) {
+		if (v == e->root) continue;
+		for (int k = 0; k < 3; k++) {
+			const double t = central_lengths[(size_t)k * N + v];
+			if (!std::isfinite(t) || t < 0.0)
+				return fail(PHYAMD_EINVAL, "phyamd_nni_log_likelihoods: central_lengths[%d][%d] = %g: a trial length is finite and not negative", k, v, t);
+			trial[(size_t)k * N + v] = t;
+		}
+	}
+	const size_t cands = nni_candidates(e);
+	prof.candidates = (int32_t)cands;
+	std::fill(out, out + (size_t)9 * N, NAN);
+	if (cands == 0) return PHYAMD_OK;  // two tips: no internal edge
+	const ScratchPlan plan = nni_plan(e);
+	if (batch_items_that_fit(e, 1, plan) < 1)
+		return fail(PHYAMD_EUNSUPPORTED, "phyamd_nni_log_likelihoods: the scratch (%zu bytes: every internal node's lower and upper partial) does not fit the memory budget",
+		            plan.item_bytes() + plan.fixed_bytes());
+	if ((rc = ensure_batch_scratch(e, 1, plan)) || (rc = upload_nni_lists(e))) return rc;
+	const int nblk = (e->P + WAVE - 1) / WAVE, nops = T - 1;
+	HIP_TRY(hipMemcpyAsync(e->d_nni_len, trial.data(), sizeof(double) * trial.size(), hipMemcpyHostToDevice, e->stream));
+	launch_batch_matrices(e, 1, e->d_lengths, nullptr, e->d_batch_mats);  // the walk's item: the engine's lengths
+	launch_batch_matrices(e, 3, e->d_nni_len, nullptr, e->d_nni_mats);
+	const BatchOp *ops = e->d_nni_ops.get();
+	const BatchArgs walk{ops, ops + nops, 0, T, N, e->P, C, nblk, T - 1, 1, e->d_tipmask, e->d_freqs, e->d_props, e->d_weights, e->d_Q, e->d_batch_mats, e->d_batch_lower,
+	                     e->d_batch_upper, e->d_batch_lnl, e->d_batch_slab};
+	hipLaunchKernelGGL(k_batch_walk4<false>, dim3(nblk, 1), dim3(WAVE, C), 0, e->stream, walk);
+	for (size_t first = 0; first < cands; first += BATCH_MAX_CHUNK) {  // (gridDim.y)
+		const size_t n = std::min<size_t>(cands - first, BATCH_MAX_CHUNK);
+		const NniArgs a{e->d_nni_cands.get() + first, T, N, e->P, C, nblk, deriv ? 1 : 0, e->d_tipmask, e->d_freqs, e->d_props, e->d_rates, e->d_weights, e->d_Q,
+		                e->d_batch_mats, e->d_nni_mats, e->d_batch_lower, e->d_batch_upper, e->d_nni_slab + first * nblk * 9};
+		hipLaunchKernelGGL(k_nni4, dim3(nblk, (unsigned)n), dim3(WAVE, C), 0, e->stream, a);
+	}
+	hipLaunchKernelGGL(k_nni_finish, dim3((unsigned)(((size_t)9 * N + 255) / 256)), dim3(256), 0, e->stream, N, nblk, e->d_nni_cand_of.get(), e->d_nni_slab.get(),
+	                   e->d_nni_out.get());
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(out, e->d_nni_out, sizeof(double) * (size_t)9 * N, hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));  // (also covers `trial`)
+	return PHYAMD_OK;
+}
+
+// mask_if_not_finite per entry: every entry has a lnL of its own; out: [lnl | d1 | d2]
+void nni_mask_derivatives(size_t entries, double *out) {
+	for (size_t i = 0; i < entries; i++)
+		if (not_finite(out[i])) out[entries + i] = out[2 * entries + i] = NAN;
+}
+
+// out [3 terms][3][N] on the host; deriv: d1 and d2 as well (else those rows are NaN at tips and the root, 0 elsewhere)
+int shard_nni_log_likelihoods(Shard *e, int flags, const double *central_lengths, bool deriv, double *out) {
+	CHECK_ENGINE(e);
+	if (!out) return fail(PHYAMD_EINVAL, "phyamd_nni_log_likelihoods: null lnl");
+	return profiled_call(e, &Shard::nni_prof, phyamd_nni_profile{}, [&](phyamd_nni_profile &prof) {
+		const int rc = run_nni(e, flags, central_lengths, deriv, out, prof);
+		if (!rc) nni_mask_derivatives((size_t)3 * e->N, out);
+		return rc;
+	});
+}
+
+// ---- every SPR regraft of chosen subtrees (phyamd_spr_log_likelihoods) ---------------------------------------------------------
+
+// the engine's tree's park_all op lists, where each internal node's op is in them, and every node's depth-first interval
+void ensure_spr_lists(Shard *e) {
+	if (!e->state.spr_lists_dirty) return;
+	const int T = e->T, N = e->N, nops = T - 1;
+	e->spr_ops.clear();
+	build_batch_ops(T, e->left.data(), e->right.data(), e->root, &e->spr_ops, true);
+	e->spr_lower_at.assign(N, -1);
+	e->spr_upper_at.assign(N, -1);
+	for (int i = 0; i < nops; i++) e->spr_lower_at[e->spr_ops[i].node] = i, e->spr_upper_at[e->spr_ops[nops + i].node] = i;
+	e->spr_tin.assign(N, 0);
+	e->spr_tout.assign(N, 0);
+	int32_t clock = 0;
+	std::vector<std::pair<int, bool>> stack{{e->root, false}};
+	while (!stack.empty()) {
+		const auto [n, done] = stack.back();
+		stack.pop_back();
+		if (done) {
+			e->spr_tout[n] = clock;
+			continue;
+		}
+		e->spr_tin[n] = clock++;
+		stack.push_back({n, true});
+		if (n >= T) stack.push_back({e->right[n], false}), stack.push_back({e->left[n], false});
+	}
+	spr_lists_rebuilt(e);
+}
+
+// row p (not the root, not a child of it) into a chunk's lists: its op lists -- the engine's with p a ghost in its parent's two
+// ops, and nothing parked in p's subtree -- appended to `ops`, its candidates to `cands`, their indices into cand_of [N]
+void build_spr_row(const Shard *e, int row, int p, std::vector<BatchOp> *ops, std::vector<SprCand> *cands, int32_t *cand_of) {
+	const int T = e->T, N = e->N, nops = T - 1;
+	const int u = e->parent[p], s = e->left[u] == p ? e->right[u] : e->left[u];
+	const auto below_p = [&](int n) { return e->spr_tin[p] <= e->spr_tin[n] && e->spr_tin[n] < e->spr_tout[p]; };
+	const size_t first = ops->size();
+	ops->insert(ops->end(), e->spr_ops.begin(), e->spr_ops.end());
+	BatchOp &up = (*ops)[first + e->spr_lower_at[u]], &down = (*ops)[first + nops + e->spr_upper_at[u]];
+	if (up.left == p) up.left = BATCH_GHOST, up.carry = up.carry == 1 ? 0 : up.carry;
+	else up.right = BATCH_GHOST, up.carry = up.carry == 2 ? 0 : up.carry;
+	if (down.left == p) down.left = BATCH_GHOST, down.dst_left = BATCH_NONE;
+	else down.right = BATCH_GHOST, down.dst_right = BATCH_NONE;
+	for (int i = 0; i < nops; i++) {
+		BatchOp &op = (*ops)[first + nops + i];
+		if (below_p(op.node)) op.dst_left = op.dst_right = BATCH_NONE;
+	}
+	for (int w = 0; w < N; w++) {
+		cand_of[w] = -1;
+		if (w == e->root || w == u || w == s || below_p(w)) continue;
+		const int x = e->parent[w];
+		cand_of[w] = (int32_t)cands->size();
+		cands->push_back(SprCand{row, w, x == e->root ? BATCH_ROOT : x, e->left[x] == w ? e->right[x] : e->left[x], p, {0, 0, 0}});
+	}
+}
+
+// lnl [count][N] (host).  Reads the engine's inputs and writes only the batch scratch: nothing in Shard::state changes but the
+// record that the host lists are the tree's
+int run_spr(Shard *e, int flags, int32_t count, const int32_t *prune, double *lnl, phyamd_spr_profile &prof) {
+	int rc;
+	if ((rc = check_ready(e))) return rc;
+	if (flags != 0) return fail(PHYAMD_EUNSUPPORTED, "phyamd_spr_log_likelihoods: flags %d (no flags are defined: pass 0)", flags);
+	if (const char *why = tree_batch_refusal(e, 0, 1)) return fail(PHYAMD_EUNSUPPORTED, "phyamd_spr_log_likelihoods: %s", why);
+	if (!e->have_eigen) return fail(PHYAMD_EINVAL, "phyamd_spr_log_likelihoods needs the eigen system (phyamd_set_eigen): the half-length matrices are formed from it");
+	const int T = e->T, N = e->N, C = e->C;
+	if (!prune && count != N) return fail(PHYAMD_EINVAL, "phyamd_spr_log_likelihoods: prune is null, so count must be the node count %d (got %d)", N, count);
+	std::vector<int32_t> live;  // indices of the rows that have candidates: p is neither the root nor a child of it
+	for (int32_t i = 0; i < count; i++) {
+		const int p = prune ? prune[i] : i;
+		if (p < 0 || p >= N) return fail(PHYAMD_EINVAL, "phyamd_spr_log_likelihoods: prune[%d] = %d is not a node id (0..%d)", i, p, N - 1);
+		if (p != e->root && e->parent[p] != e->root) live.push_back(i);
+	}
+	std::fill(lnl, lnl + (size_t)count * N, NAN);
+	prof.prunes = count;
+	if (live.empty()) return PHYAMD_OK;
+	ensure_spr_lists(e);
+	const ScratchPlan plan = spr_plan(e);
+	const int nblk = (e->P + WAVE - 1) / WAVE;
+	std::vector<double> lengths((size_t)2 * N), out;
+	for (int n = 0; n < N; n++) lengths[n] = e->lengths[n], lengths[N + n] = 0.5 * e->lengths[n];
+	std::vector<BatchOp> ops;
+	std::vector<SprCand> cands;
+	std::vector<int32_t> cand_of;
+	for (size_t first = 0; first < live.size();) {
+		const size_t rows = std::min(batch_items_that_fit(e, live.size() - first, plan), live.size() - first);
+		if (rows < 1)
+			return fail(PHYAMD_EUNSUPPORTED, "phyamd_spr_log_likelihoods: the scratch of one row (%zu bytes: every internal node's lower and upper partial) does not fit the memory budget",
+			            plan.item_bytes());
+		if ((rc = ensure_batch_scratch(e, rows, plan))) return rc;
+		ops.clear();
+		cands.clear();
+		cand_of.resize(rows * N);
+		for (size_t r = 0; r < rows; r++) {
+			const int32_t i = live[first + r];
+			build_spr_row(e, (int)r, prune ? prune[i] : i, &ops, &cands, cand_of.data() + r * N);
+		}
+		HIP_TRY(hipMemcpyAsync(e->d_batch_item_ops, ops.data(), sizeof(BatchOp) * ops.size(), hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_spr_cands, cands.data(), sizeof(SprCand) * cands.size(), hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_spr_cand_of, cand_of.data(), sizeof(int32_t) * cand_of.size(), hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_spr_len, lengths.data(), sizeof(double) * lengths.size(), hipMemcpyHostToDevice, e->stream));
+		launch_batch_matrices(e, 2, e->d_spr_len, nullptr, e->d_spr_mats);  // the engine's lengths, then their halves
+		const double *mats = e->d_spr_mats.get(), *half = mats + (size_t)N * C * 16;
+		const SprWalkArgs walk{e->d_batch_item_ops.get(), T, N, e->P, C, nblk, e->d_tipmask, mats, e->d_batch_lower, e->d_batch_upper};
+		hipLaunchKernelGGL(k_spr_walk4, dim3(nblk, (unsigned)rows), dim3(WAVE, C), 0, e->stream, walk);
+		for (size_t c0 = 0; c0 < cands.size(); c0 += BATCH_MAX_CHUNK) {  // (gridDim.y)
+			const size_t n = std::min<size_t>(cands.size() - c0, BATCH_MAX_CHUNK);
+			const SprArgs a{e->d_spr_cands.get() + c0, T, N, e->P, C, nblk, e->d_tipmask, e->d_freqs, e->d_props, e->d_weights, mats, half, e->d_batch_lower, e->d_batch_upper,
+			                e->d_spr_slab.get() + c0 * nblk};
+			hipLaunchKernelGGL(k_spr4, dim3(nblk, (unsigned)n), dim3(WAVE, C), 0, e->stream, a);
+		}
+		const size_t cells = rows * N;
+		hipLaunchKernelGGL(k_spr_finish, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, e->stream, cells, nblk, e->d_spr_cand_of.get(), e->d_spr_slab.get(),
+		                   e->d_spr_out.get());
+		HIP_TRY(hipGetLastError());
+		out.resize(cells);
+		HIP_TRY(hipMemcpyAsync(out.data(), e->d_spr_out, sizeof(double) * cells, hipMemcpyDeviceToHost, e->stream));
+		HIP_TRY(hipStreamSynchronize(e->stream));  // (also covers the lists, which the next chunk builds anew)
+		for (size_t r = 0; r < rows; r++) std::copy(out.begin() + r * N, out.begin() + (r + 1) * N, lnl + (size_t)live[first + r] * N);
+		prof.chunks++;
+		prof.candidates += (int64_t)cands.size();
+		first += rows;
+	}
+	return PHYAMD_OK;
+}
+
+int shard_spr_log_likelihoods(Shard *e, int flags, int32_t count, const int32_t *prune, double *lnl) {
+	CHECK_ENGINE(e);
+	if (count < 1) return fail(PHYAMD_EINVAL, "phyamd_spr_log_likelihoods: count must be >= 1 (got %d)", count);
+	if (!lnl) return fail(PHYAMD_EINVAL, "phyamd_spr_log_likelihoods: null lnl");
+	return profiled_call(e, &Shard::spr_prof, phyamd_spr_profile{}, [&](phyamd_spr_profile &prof) { return run_spr(e, flags, count, prune, lnl, prof); });
+}
+
+// ---- per-pattern posteriors (phyamd_state_posteriors, phyamd_site_rate_posteriors) ---------------------------------------------
+
+// The staging arrays of the two calls, and rows of a chunk that fit beside the engine.  per_row[a]: bytes a row takes in array a
+// for this call, 0: the call does not use the array -- it is released first, so that what an earlier call left never takes this
+// call's room.  An array the call uses is kept where it is large enough (DeviceBuffer::reserve frees only an array it regrows),
+// so the arrays are counted at the larger of what they hold and what n rows need: n is the most rows that fit the room beside a
+// fully resident engine (scratch_room); if arrays kept from a roomier time leave no such n under a cap, they are released and the
+// rows sized for empty ones.  At least one row: if even that does not fit, the allocation reports it
+constexpr int POST_ARRAYS = 4;
+size_t post_rows_that_fit(Shard *e, size_t count, const size_t (&per_row)[POST_ARRAYS]) {
+	DeviceBuffer *const arrays[POST_ARRAYS] = {&e->d_post_rows, &e->d_post_out, &e->d_post_lower, &e->d_post_states};
+	size_t row_bytes = 0;
+	double held = 0.0;
+	for (int a = 0; a < POST_ARRAYS; a++) {
+		if (per_row[a] == 0) arrays[a]->release();
+		row_bytes += per_row[a];
+		held += (double)arrays[a]->bytes();
+	}
+	const double room = scratch_room(e, held, EngineRoom::Resident);
+	const size_t n = (size_t)std::min((double)std::min<size_t>(count, BATCH_MAX_CHUNK), std::max(std::floor(room / (double)row_bytes), 1.0));
+	if (e->cfg.max_device_bytes <= 0) return n;
+	double after = 0.0;  // what the arrays hold once n rows are ensured
+	for (int a = 0; a < POST_ARRAYS; a++) after += (double)std::max(arrays[a]->bytes(), n * per_row[a]);
+	if (after > room)
+		for (DeviceBuffer *a : arrays) a->release();
+	return n;
+}
+
+// posteriors: row i at posteriors + (i * pattern_stride) * S, this shard's P patterns of it; states: row i at states + i *
+// pattern_stride (the group layer passes the handle's pattern count and pointers advanced to this shard's range).  lnl: the log
+// likelihood of the evaluation the partials belong to (this shard's patterns)
+int shard_state_posteriors(Shard *e, int flags, int32_t count, const int32_t *nodes, size_t pattern_stride, double *posteriors, uint8_t *states, double *lnl) {
+	CHECK_ENGINE(e);
+	NOT_TILED(e, "phyamd_state_posteriors (every partial resident)");
+	if (flags != 0) return fail(PHYAMD_EINVAL, "phyamd_state_posteriors: flags %d (no flags are defined: pass 0)", flags);
+	if (!posteriors && !states) return fail(PHYAMD_EINVAL, "phyamd_state_posteriors: posteriors and states are both null");
+	if (count < 1) return fail(PHYAMD_EINVAL, "phyamd_state_posteriors: count must be >= 1 (got %d)", count);
+	const int N = e->N, C = e->C, S = e->S, P = e->P;
+	if (!nodes && count != N) return fail(PHYAMD_EINVAL, "phyamd_state_posteriors: nodes is null, so count must be the node count %d (got %d)", N, count);
+	for (int32_t i = 0; nodes && i < count; i++)
+		if (nodes[i] < 0 || nodes[i] >= N) return fail(PHYAMD_EINVAL, "phyamd_state_posteriors: nodes[%d] = %d is not a node id (0..%d)", i, nodes[i], N - 1);
+	int rc;
+	if ((rc = bind_device(e)) || (rc = check_ready(e))) return rc;
+	if ((rc = require_resident_partials(e, "phyamd_state_posteriors"))) return rc;
+	const size_t npd = node_partial_doubles(e);
+	const size_t per_row[POST_ARRAYS] = {sizeof(PostRow), posteriors ? sizeof(double) * P * S : 0, e->generic ? sizeof(double) * npd : 0, states ? (size_t)P : 0};
+	const int fold = e->upper_fold ? 1 : 0;
+	std::vector<PostRow> rows;
+	std::vector<double> host_post;
+	std::vector<uint8_t> host_states;
+	const bool direct = pattern_stride == (size_t)P;  // one shard: a chunk's rows are contiguous in the caller's arrays
+	for (size_t first = 0; first < (size_t)count;) {
+		const size_t n = post_rows_that_fit(e, (size_t)count - first, per_row);
+		if ((rc = e->d_post_rows.ensure(n)) || (posteriors && (rc = e->d_post_out.ensure(n * P * S))) || (states && (rc = e->d_post_states.ensure(n * P))) ||
+		    (e->generic && (rc = e->d_post_lower.ensure(n * npd))))
+			return rc;
+		rows.resize(n);
+		for (size_t r = 0; r < n; r++) {
+			const int node = nodes ? nodes[first + r] : (int)(first + r);
+			PostRow &d = rows[r];
+			d.node = node;
+			d.mat = node == e->root ? -1 : node;
+			d.tip = node < e->T ? e->d_tipmask + (size_t)node * P : nullptr;
+			d.low = nullptr;
+			d.up = nullptr;
+			if (node != e->root) {
+				if (e->upper_slot[node] < 0) return fail(PHYAMD_EDEVICE, "phyamd_state_posteriors: node %d has no resident upper partial", node);
+				d.up = e->d_upper + (size_t)e->upper_slot[node] * npd;
+			}
+			if (node >= e->T) {
+				if (e->core_index[node] < 0) return fail(PHYAMD_EDEVICE, "phyamd_state_posteriors: node %d has no resident lower partial", node);
+				d.low = e->d_lower + (size_t)e->core_index[node] * npd;
+				if (e->generic && node != e->root) {  // a stored array is the message P p: the node's own partial, into this row's temporary
+					double *own = e->d_post_lower + r * npd;
+					if ((rc = true_lower_gen(e, node, own, nullptr))) return rc;
+					d.low = own;
+				}
+			}
+		}
+		HIP_TRY(hipMemcpyAsync(e->d_post_rows, rows.data(), sizeof(PostRow) * n, hipMemcpyHostToDevice, e->stream));
+		double *post = posteriors ? e->d_post_out.get() : nullptr;
+		uint8_t *st = states ? e->d_post_states.get() : nullptr;
+		if (e->generic)
+			hipLaunchKernelGGL(k_post_gen, dim3((P + 255) / 256, (unsigned)n), dim3(256), 0, e->stream, e->d_post_rows.get(), P, e->Pp, S, C, e->d_mats.get(), e->d_freqs.get(), fold,
+			                   e->d_props.get(), e->d_tipsets.get(), post, st);
+		else
+			hipLaunchKernelGGL(k_post4, dim3((P + WAVE - 1) / WAVE, (unsigned)n), dim3(WAVE, C), sizeof(double) * 4 * C * WAVE, e->stream, e->d_post_rows.get(), P, C,
+			                   e->d_mats.get(), e->d_freqs.get(), fold, e->d_props.get(), post, st);
+		HIP_TRY(hipGetLastError());
+		if (posteriors) {
+			double *dst = posteriors + first * pattern_stride * S;
+			if (!direct) host_post.resize(n * P * S), dst = host_post.data();
+			HIP_TRY(hipMemcpyAsync(dst, post, sizeof(double) * n * P * S, hipMemcpyDeviceToHost, e->stream));
+		}
+		if (states) {
+			uint8_t *dst = states + first * pattern_stride;
+			if (!direct) host_states.resize(n * P), dst = host_states.data();
+			HIP_TRY(hipMemcpyAsync(dst, st, n * P, hipMemcpyDeviceToHost, e->stream));
+		}
+		HIP_TRY(hipStreamSynchronize(e->stream));  // (also covers `rows`, which the next chunk builds anew)
+		for (size_t r = 0; !direct && r < n; r++) {
+			if (posteriors) std::memcpy(posteriors + (first + r) * pattern_stride * S, host_post.data() + r * P * S, sizeof(double) * P * S);
+			if (states) std::memcpy(states + (first + r) * pattern_stride, host_states.data() + r * P, (size_t)P);
+		}
+		first += n;
+	}
+	HIP_TRY(hipMemcpyAsync(e->h_result, e->d_result, sizeof(double), hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	*lnl = e->h_result[0];
+	return PHYAMD_OK;
+}
+
+// posteriors [P][C] and mean_rates [P] (or null) of this shard's patterns.  Reads the root's stored partial, like
+// phyamd_root_frequency_term: whatever is pending is evaluated by a post-order pass, and the engine is afterwards what that pass
+// leaves -- the root's array is p_root in every storage convention, only a rescaled evaluation's factors have to be the reference's
+int shard_site_rate_posteriors(Shard *e, double *posteriors, double *mean_rates) {
+	CHECK_ENGINE(e);
+	NOT_TILED(e, "phyamd_site_rate_posteriors (the root partial of every pattern resident)");
+	if (!posteriors) return fail(PHYAMD_EINVAL, "phyamd_site_rate_posteriors: null posteriors");
+	int rc;
+	if ((rc = bind_device(e)) || (rc = check_ready(e))) return rc;
+	if ((rc = run_lower(e, 1))) return rc;
+	if (e->scaling_on && (rc = require_reference_form(e))) return rc;  // (see shard_root_frequency_term: factors common to the categories)
+	if (e->core_index[e->root] < 0 || !e->d_lower) return fail(PHYAMD_EDEVICE, "phyamd_site_rate_posteriors: the root partial is not resident");
+	const int P = e->P, C = e->C;
+	e->d_post_rows.release(), e->d_post_lower.release(), e->d_post_states.release();  // (what a state call left is not this call's: its room is)
+	if ((rc = e->d_post_out.ensure((size_t)P * C + P))) return rc;
+	const double *root = e->d_lower + (size_t)e->core_index[e->root] * node_partial_doubles(e);
+	const size_t cat_stride = e->generic ? (size_t)e->S * e->Pp : (size_t)P * e->S;
+	const size_t pat_stride = e->generic ? 1 : (size_t)e->S, state_stride = e->generic ? (size_t)e->Pp : 1;
+	double *R = e->d_post_out.get(), *mean = R + (size_t)P * C;
+	hipLaunchKernelGGL(k_site_rate_post, dim3((P + 255) / 256), dim3(256), 0, e->stream, P, e->S, C, root, cat_stride, pat_stride, state_stride, e->d_freqs.get(),
+	                   e->d_props.get(), e->d_rates.get(), R, mean);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(posteriors, R, sizeof(double) * P * C, hipMemcpyDeviceToHost, e->stream));
+	if (mean_rates) HIP_TRY(hipMemcpyAsync(mean_rates, mean, sizeof(double) * P, hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	return PHYAMD_OK;
+}
+
+// ---- the full branch-length Hessian (phyamd_branch_hessian) --------------------------------------------------------------------
+
+// the lists of the engine's tree: every node's walk to the root (one tangent slot per step), and the work lists of the two tile
+// kernels -- per internal node m the 16 x 16 tiles of (node below its left child) x (node below its right child), and the tiles
+// of the upper triangle of (branch) x (branch)
+struct BhessLists {
+	std::vector<BhessStart> starts;
+	std::vector<BhessStep> steps;
+	std::vector<BhessTile> cousins, outer;
+};
+
+void build_bhess_lists(const Shard *e, BhessLists &L) {
+	const int N = e->N, root = e->root;
+	std::vector<std::vector<std::pair<int32_t, int32_t>>> below((size_t)2 * N);  // [2 m + side]: (node, slot of its tangent at m)
+	std::vector<int32_t> branches;
+	for (int a = 0; a < N; a++) {
+		if (a == root) continue;
+		branches.push_back(a);
+		BhessStart s{a, (int32_t)L.steps.size(), 0, 0};
+		for (int cur = a, m = e->parent[a];; cur = m, m = e->parent[m]) {
+			const bool from_left = e->left[m] == cur;
+			below[(size_t)2 * m + (from_left ? 0 : 1)].push_back({a, (int32_t)L.steps.size()});
+			L.steps.push_back(BhessStep{m, from_left ? e->right[m] : e->left[m], a, 0});
+			s.count++;
+			if (m == root) break;
+		}
+		L.starts.push_back(s);
+	}
+	const auto fill = [](int32_t *rows, int32_t *nodes, const std::pair<int32_t, int32_t> *from, size_t n) {
+		for (size_t i = 0; i < 16; i++) rows[i] = from[i < n ? i : 0].second, nodes[i] = i < n ? from[i].first : -1;
+	};
+	for (int m = e->T; m < N; m++) {
+		const auto &l = below[(size_t)2 * m], &r = below[(size_t)2 * m + 1];
+		for (size_t i = 0; i < l.size(); i += 16)
+			for (size_t j = 0; j < r.size(); j += 16) {
+				BhessTile t{};
+				t.m = m;
+				fill(t.row_a, t.node_a, l.data() + i, std::min<size_t>(16, l.size() - i));
+				fill(t.row_b, t.node_b, r.data() + j, std::min<size_t>(16, r.size() - j));
+				L.cousins.push_back(t);
+			}
+	}
+	std::vector<std::pair<int32_t, int32_t>> rows;  // (node, its row of G)
+	for (int32_t a : branches) rows.push_back({a, a});
+	for (size_t i = 0; i < rows.size(); i += 16)
+		for (size_t j = i; j < rows.size(); j += 16) {
+			BhessTile t{};
+			t.m = -1;
+			fill(t.row_a, t.node_a, rows.data() + i, std::min<size_t>(16, rows.size() - i));
+			fill(t.row_b, t.node_b, rows.data() + j, std::min<size_t>(16, rows.size() - j));
+			L.outer.push_back(t);
+		}
+}
+
+// the call's scratch (ScratchPlan): an item is one block of 64 patterns -- its tangents, its rows of w / L, 1 / L, G and the walk's
+// slab, its tiles; whatever the chunk, the sums (the chunk's and the running matrix and gradient, r Q P and r^2 Q Q P) and the lists
+ScratchPlan bhess_plan(Shard *e, size_t nsteps, size_t tiles, size_t list_bytes) {
+	const size_t D = sizeof(double), N = (size_t)e->N, C = (size_t)e->C;
+	ScratchPlan p;
+	p.add(e->d_bhess_tan, D * nsteps * C * WAVE * 4);
+	p.add(e->d_bhess_rows, D * (2 * WAVE + N * WAVE + nsteps + 2 * N));
+	p.add(e->d_bhess_tiles, D * 256 * tiles);
+	p.add(e->d_bhess_sums, 0, D * (2 * N * N + 2 * N + 2 * N * C * 16));
+	p.add(e->d_bhess_lists, 0, list_bytes);
+	return p;
+}
+
+// lnl, gradient [N] (or null) and hessian [N][N] of this shard's patterns (host)
+int run_branch_hessian(Shard *e, double *lnl, double *gradient, double *hessian, phyamd_hessian_profile &prof) {
+	static const char *const name = "phyamd_branch_hessian";
+	const int N = e->N, C = e->C, P = e->P;
+	int rc;
+	if (e->generic) return fail(PHYAMD_EUNSUPPORTED, "%s: %d states (the tangent walk and the pair tiles are built for 4)", name, e->S);
+	if (C > BHESS_MAX_CATEGORIES) return fail(PHYAMD_EUNSUPPORTED, "%s: %d categories (a workgroup holds the category waves of one block: at most %d)", name, C, BHESS_MAX_CATEGORIES);
+	NOT_TILED(e, "phyamd_branch_hessian (every partial resident)");
+	if ((rc = check_ready(e))) return rc;
+	if (std::any_of(e->explicit_host.begin(), e->explicit_host.end(), [](uint8_t x) { return x != 0; }))
+		return fail(PHYAMD_EUNSUPPORTED, "%s: a node has explicit matrices (Q P is the derivative of exp(Q t r) only)", name);
+	if (!e->have_eigen || !e->have_Q) return fail(PHYAMD_EINVAL, "%s needs the eigen system (phyamd_set_eigen): the derivatives of the matrices are formed from it", name);
+	static const char *const rescaling = "%s: the engine is rescaling (the terms multiply partials of different nodes, and a rescaled evaluation's partials do not share units)";
+	if (e->scaling_on) return fail(PHYAMD_EUNSUPPORTED, rescaling, name);
+	if ((rc = require_resident_partials(e, name))) return rc;
+	if (e->scaling_on) return fail(PHYAMD_EUNSUPPORTED, rescaling, name);  // (PHYAMD_RESCALE_AUTO: that evaluation switched)
+
+	BhessLists L;
+	build_bhess_lists(e, L);
+	std::vector<int32_t> lower_of(N), upper_of(N);
+	for (int n = 0; n < N; n++) {
+		lower_of[n] = n < e->T ? -1 : e->core_index[n];
+		upper_of[n] = n == e->root ? 0 : e->upper_slot[n];
+		if ((n >= e->T && lower_of[n] < 0) || upper_of[n] < 0) return fail(PHYAMD_EDEVICE, "%s: node %d has no resident partial", name, n);
+	}
+	const size_t nsteps = L.steps.size(), ntc = L.cousins.size(), nto = L.outer.size(), nn = (size_t)N * N;
+	const size_t at_steps = sizeof(BhessStart) * L.starts.size(), at_cousins = at_steps + sizeof(BhessStep) * nsteps, at_outer = at_cousins + sizeof(BhessTile) * ntc,
+	             at_lower = at_outer + sizeof(BhessTile) * nto, at_upper = at_lower + sizeof(int32_t) * N, list_bytes = at_upper + sizeof(int32_t) * N;
+	const size_t nblk_all = ((size_t)P + WAVE - 1) / WAVE;
+	const ScratchPlan plan = bhess_plan(e, nsteps, ntc + nto, list_bytes);
+	// the chunk: whole blocks whose scratch fits beside the engine, the whole scratch group counted free
+	const double fit = plan.items_in(scratch_room(e, (double)batch_scratch_bytes(e), EngineRoom::MayGrow));
+	if (fit < 1.0)
+		return fail(PHYAMD_ENOMEM, "%s: the scratch of one block of 64 patterns (%.0f bytes, and %.0f for the matrix and the lists) does not fit the memory budget", name,
+		            (double)plan.item_bytes(), (double)plan.fixed_bytes());
+	const size_t nblk = (size_t)std::min((double)nblk_all, fit), Pc = nblk * WAVE;
+	if (!plan.held(nblk) && e->cfg.max_device_bytes > 0) release_batch_scratch(e);  // (under a cap a call gets exactly its own scratch)
+	if ((rc = plan.allocate(nblk))) return rc;
+
+	std::vector<char> lists(list_bytes);
+	std::memcpy(lists.data(), L.starts.data(), at_steps);
+	std::memcpy(lists.data() + at_steps, L.steps.data(), sizeof(BhessStep) * nsteps);
+	if (ntc) std::memcpy(lists.data() + at_cousins, L.cousins.data(), sizeof(BhessTile) * ntc);
+	std::memcpy(lists.data() + at_outer, L.outer.data(), sizeof(BhessTile) * nto);
+	std::memcpy(lists.data() + at_lower, lower_of.data(), sizeof(int32_t) * N);
+	std::memcpy(lists.data() + at_upper, upper_of.data(), sizeof(int32_t) * N);
+	HIP_TRY(hipMemcpyAsync(e->d_bhess_lists, lists.data(), list_bytes, hipMemcpyHostToDevice, e->stream));
+	const char *dl = e->d_bhess_lists.get();
+	const BhessStart *d_starts = reinterpret_cast<const BhessStart *>(dl);
+	const BhessStep *d_steps = reinterpret_cast<const BhessStep *>(dl + at_steps);
+	const BhessTile *d_cousins = reinterpret_cast<const BhessTile *>(dl + at_cousins), *d_outer = reinterpret_cast<const BhessTile *>(dl + at_outer);
+	double *Hc = e->d_bhess_sums.get(), *H = Hc + nn, *gc = H + nn, *g = gc + N, *qp = g + N, *qqp = qp + (size_t)N * C * 16;
+	hipLaunchKernelGGL(k_bhess_matrices, dim3((unsigned)(((size_t)N * C * 16 + 255) / 256)), dim3(256), 0, e->stream, N * C, C, e->d_mats.get(), e->d_Q.get(), e->d_rates.get(), qp,
+	                   qqp);
+	BhessArgs a{};
+	a.steps = d_steps;
+	a.lower_of = reinterpret_cast<const int32_t *>(dl + at_lower), a.upper_of = reinterpret_cast<const int32_t *>(dl + at_upper);
+	a.T = e->T, a.N = N, a.P = P, a.C = C, a.root = e->root, a.fold = e->upper_fold ? 1 : 0;
+	a.nsteps = (int)nsteps;
+	a.tipmask = e->d_tipmask, a.lower = e->d_lower, a.upper = e->d_upper;
+	a.mats = e->d_mats, a.qp = qp, a.qqp = qqp;
+	a.freqs = e->d_freqs, a.props = e->d_props, a.weights = e->d_weights;
+	a.site = e->d_bhess_rows.get(), a.G = a.site + 2 * Pc, a.slab = a.G + (size_t)N * Pc;
+	a.tan = e->d_bhess_tan;
+	double *cousin_out = e->d_bhess_tiles.get(), *outer_out = cousin_out + ntc * nblk * 256;
+	for (size_t b0 = 0; b0 < nblk_all; b0 += nblk) {
+		const size_t nb = std::min(nblk, nblk_all - b0);  // (the last chunk may be shorter: it runs in the same arrays at its own width)
+		a.k0 = (int)(b0 * WAVE), a.nblk = (int)nb, a.Pc = (int)(nb * WAVE);
+		a.G = a.site + 2 * (size_t)a.Pc, a.slab = a.G + (size_t)N * a.Pc;
+		HIP_TRY(hipMemsetAsync(Hc, 0, sizeof(double) * nn, e->stream));
+		hipLaunchKernelGGL(k_bhess_site, dim3((unsigned)((a.Pc + 255) / 256)), dim3(256), 0, e->stream, a);
+		for (size_t y = 0; y < L.starts.size(); y += BATCH_MAX_CHUNK) {  // (gridDim.y)
+			a.starts = d_starts + y;
+			hipLaunchKernelGGL(k_bhess_walk, dim3((unsigned)nb, (unsigned)std::min<size_t>(L.starts.size() - y, BATCH_MAX_CHUNK)), dim3(WAVE, C), 0, e->stream, a);
+		}
+		for (size_t y = 0; y < ntc; y += BATCH_MAX_CHUNK)
+			hipLaunchKernelGGL(k_bhess_cousins, dim3((unsigned)nb, (unsigned)std::min<size_t>(ntc - y, BATCH_MAX_CHUNK)), dim3(256), 0, e->stream, a, d_cousins + y,
+			                   cousin_out + y * nb * 256);
+		for (size_t y = 0; y < nto; y += BATCH_MAX_CHUNK)
+			hipLaunchKernelGGL(k_bhess_outer, dim3((unsigned)nb, (unsigned)std::min<size_t>(nto - y, BATCH_MAX_CHUNK)), dim3(WAVE), 0, e->stream, a, d_outer + y,
+			                   outer_out + y * nb * 256);
+		BhessFinish f{0, N, (int)nb, e->root, (int)nsteps, b0 == 0 ? 1 : 0, nto * 256, d_outer, d_steps, outer_out, Hc, gc, H, g};
+		const auto finish = [&] { hipLaunchKernelGGL(k_bhess_finish, dim3((unsigned)((f.count + 255) / 256)), dim3(256), 0, e->stream, f); };
+		finish();
+		f.mode = 1, f.count = nsteps + N, f.slab = a.slab;
+		finish();
+		if (ntc) {
+			f.mode = 2, f.count = ntc * 256, f.tiles = d_cousins, f.slab = cousin_out;
+			finish();
+		}
+		f.mode = 3, f.count = nn;
+		finish();
+		HIP_TRY(hipGetLastError());
+		prof.chunks++;
+	}
+	HIP_TRY(hipMemcpyAsync(hessian, H, sizeof(double) * nn, hipMemcpyDeviceToHost, e->stream));
+	if (gradient) HIP_TRY(hipMemcpyAsync(gradient, g, sizeof(double) * N, hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipMemcpyAsync(e->h_result, e->d_result, sizeof(double), hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));  // (also covers `lists`)
+	*lnl = e->h_result[0];
+	return PHYAMD_OK;
+}
+
+int shard_branch_hessian(Shard *e, int flags, double *lnl, double *gradient, double *hessian) {
+	if (!e) return fail(PHYAMD_EINVAL, "phyamd_branch_hessian: null engine");
+	if (!lnl || !hessian) return fail(PHYAMD_EINVAL, "phyamd_branch_hessian: null %s", !lnl ? "lnl" : "hessian");
+	if (flags != 0) return fail(PHYAMD_EINVAL, "phyamd_branch_hessian: flags %d (no flags are defined: pass 0)", flags);
+	phyamd_hessian_profile known{};
+	known.pairs = (int64_t)(e->N - 1) * e->N / 2;
+	return profiled_call(e, &Shard::bhess_prof, known, [&](phyamd_hessian_profile &prof) {
+		const int rc = run_branch_hessian(e, lnl, gradient, hessian, prof);
+		if (!rc) mask_if_not_finite(*lnl, gradient, (size_t)e->N), mask_if_not_finite(*lnl, hessian, (size_t)e->N * e->N);
+		return rc;
+	});
+}

@@ -239,13 +239,12 @@ struct Shard {
 	DeviceArray<double> d_batch_lower{&batch_mem}, d_batch_upper{&batch_mem}, d_batch_slab{&batch_mem}, d_batch_lnl{&batch_mem};
 	DeviceArray<BatchOp> d_batch_item_ops{&batch_mem};  // [item][post-order T - 1 | pre-order T - 1]
 	DeviceArray<int32_t> d_batch_roots{&batch_mem};     // [item]
-	// what the scratch holds: every batch call says what it needs (BatchShape) and gets at least that, so a call of one kind
-	// never runs in the scratch of the other with too few upper slots or without op lists
-	int batch_items = 0;                 // items
-	bool batch_grad = false;             // ... with the pre-order pass's part
-	int batch_slots = 0;                 // ... of so many upper slots each
-	bool batch_trees = false;            // ... with their own op lists and roots
-	bool batch_nni = false;              // ... with the arrays of phyamd_nni_log_likelihoods below
+	// what the scratch holds: every call describes what it needs as a ScratchPlan (phyamd_queries.inc: batch_plan, nni_plan, spr_plan,
+	// bhess_plan) and gets at least that, so a call of one kind never runs in the scratch of another with too few upper slots or
+	// without its lists.  batch_held: the plan the arrays were last allocated by, for batch_items items (the Hessian's arrays, grown
+	// beside it, are judged by their sizes alone)
+	ScratchPlan batch_held;
+	size_t batch_items = 0;
 	phyamd_batch_profile batch_prof{};
 	// phyamd_nni_log_likelihoods (phyamd_nni4.inc) walks ONE item of the scratch above with every upper parked (slots = T - 1) and
 	// adds to the group: the engine's tree's op lists in that form, the candidate edges and each node's candidate index, the trial
@@ -268,7 +267,6 @@ struct Shard {
 	DeviceArray<int32_t> d_spr_cand_of{&batch_mem};  // [rows][N]: cell -> index in d_spr_cands, -1: no candidate
 	DeviceArray<double> d_spr_slab{&batch_mem}, d_spr_out{&batch_mem};  // [candidate][blocks], [rows][N]
 	DeviceArray<double> d_spr_len{&batch_mem}, d_spr_mats{&batch_mem};  // [t | 0.5 t][N], [2][N][C][16]
-	bool batch_spr = false;              // the scratch holds these arrays for batch_items rows
 	phyamd_spr_profile spr_prof{};
 	// phyamd_state_posteriors / phyamd_site_rate_posteriors (phyamd_post.inc): the rows of a chunk, their staged results -- [rows][P][S]
 	// posteriors and [rows][P] states, or [P][C] + [P] site rates -- and, 20 / 60 / 61 states, each row's own partial p_n (true_lower_gen).
