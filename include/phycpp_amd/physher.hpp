@@ -280,6 +280,13 @@ class TreeLikelihoodInterface : public CallableModelInterface {
 	// engine evaluates item by item (never batched); lnL is batched either way.
 	void LogLikelihoodBatch(size_t count, const double *treeParameters, double *logLikelihoods);
 	void GradientBatch(size_t count, const double *treeParameters, double *logLikelihoods, double *gradients);
+	// lnL and the gradient for `count` pattern-weight vectors at once (one phyamd_gradient_batch_weights call): bootstrap or
+	// jackknife replicates, RELL reweighting, site minibatches.  weights [count][patterns] in this object's pattern order
+	// (PatternWeights() is the alignment's own row), finite and >= 0; treeParameters [count][n] as in GradientBatch, or null:
+	// every item on the tree model's current parameters, which one walk of the tree then serves.  logLikelihoods (may be null)
+	// and gradients are GradientBatch's, item b being what Gradient() returns with weights[b] as the pattern weights; the same
+	// requests throw.  This object's own weights and the tree model's parameters are unchanged afterwards.
+	void GradientWeights(size_t count, const double *weights, const double *treeParameters, double *logLikelihoods, double *gradients);
 	// lnL / lnL and the branch gradient of `count` TREES on this object's alignment and models at once (one
 	// phyamd_gradient_batch_trees call): left, right [count][2T-1] and roots [count] are plain node-id arrays, tips 0..T-1 in this
 	// object's taxon order (the tree model's tip ids), internal ids T..2T-2 in any order, -1 / -1 for tips; branchLengths
@@ -331,7 +338,7 @@ class TreeLikelihoodInterface : public CallableModelInterface {
 	void FormBranchLengths(std::vector<double> &lengths);
 	void GradientEpilogue(double lnl, std::vector<double> &cat_grad, const std::vector<double> &branch_lengths, const std::vector<double> &subst_grad,
 	                      double *gradient);
-	void EvaluateBatch(size_t count, const double *treeParameters, double *logLikelihoods, double *gradients);
+	void EvaluateBatch(size_t count, const double *treeParameters, double *logLikelihoods, double *gradients, const double *weights);
 	void BranchGradientFromCat(const double *cat_grad, double *g);
 	void EvaluateTrees(size_t count, const int32_t *left, const int32_t *right, const int32_t *roots, const double *branchLengths, double *logLikelihoods,
 	                   double *branchGradients);

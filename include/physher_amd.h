@@ -418,6 +418,47 @@ int phyamd_branch_hessian(phyamd_engine *e, int flags, double *lnl, double *grad
  * ran in (sharded: the most of any shard); scratch_bytes = the batch scratch held afterwards, summed over the shards */
 typedef struct { int32_t chunks; int64_t pairs, scratch_bytes; double ms; } phyamd_hessian_profile;
 int phyamd_get_hessian_profile(phyamd_engine *e, phyamd_hessian_profile *out);
+/* lnL and the per-category branch gradient for `count` pattern-weight vectors on the engine's tree, data and models: the batch
+ * axis of resampling -- bootstrap and jackknife replicates of one alignment (phyresampling.c:105-260 builds a SitePattern and a
+ * likelihood object per replicate), RELL reweighting, site minibatches (a weight vector with zeros).  weights [count][P], any
+ * finite doubles >= 0 (a zero weight does what dropping the pattern does, its site likelihood being finite); branch_lengths [count][2T-1] by node id (root entries
+ * ignored), or NULL: every item on the engine's own lengths; lnl [count]; cat_gradient [count][2T-1][C], root rows 0, or NULL
+ * for lnL only.  Item b equals what phyamd_set_pattern_weights(weights[b]), phyamd_set_branch_lengths(branch_lengths[b]) if
+ * lengths are given, and phyamd_gradient(flags) / phyamd_log_likelihood return.  NaN/inf lnL of an item => that item's gradient
+ * all NaN.  Afterwards the engine's own weights and lengths are back and later evaluations return the bits they would have
+ * returned without the call.  Like phyamd_gradient_batch the call is defined as "evaluate the items one by one through the
+ * ordinary path, then put the engine's weights and lengths back" and so works on every engine configuration; under that call's
+ * conditions -- 4 states, at most 8 categories, an engine that is not rescaling, untiled patterns, no tip cell with an empty state
+ * mask, flags 0 or PHYAMD_GRAD_FOLD_ROOT_FREQS, scratch within the memory cap -- the items run together, with no floating-point
+ * atomics, on one of two paths:
+ *   with branch_lengths: phyamd_gradient_batch's walk with a weight row per item, under its bound of 8192 patterns per shard.  An
+ *     item's bits do not depend on `count`, its position or the chunks the batch ran in, and an item whose weights equal the
+ *     engine's own returns the bits of phyamd_gradient_batch for the same lengths.  PHYAMD_RESCALE_AUTO: an item whose lnL is
+ *     not finite is evaluated again through the ordinary path, which may switch the engine to rescaling; _NEVER: in band.
+ *   branch_lengths == NULL: partials and matrices do not depend on the weights, so ONE walk of the tree serves every item.  It
+ *     leaves the unweighted per-pattern terms (log L_k, and every (branch, category)'s gradient term over L_k) as rows, and item
+ *     b's results are the products of its weight row with them, formed on the matrix pipe over segments of 4096 patterns that
+ *     are added in segment order.  Any number of untiled patterns; explicit node matrices are used as the engine holds them.  An
+ *     item's bits do not depend on `count`, its position, the chunks of items or what the scratch held before; the lnL-only form
+ *     returns the same lnL bits.  If the rows do not fit the memory cap the patterns run in chunks of whole blocks of 64 whose
+ *     sums are added in chunk order (PHYAMD_ENOMEM if not one block fits): the bits may then depend on the cap.
+ *     PHYAMD_RESCALE_AUTO: if any pattern's log L_k is not finite the whole call goes item by item, which may switch the engine
+ *     to rescaling; _NEVER: in band.
+ * The scratch lives in the batch scratch and is counted and released like it.  Sharded handles: every shard takes its own
+ * pattern columns of `weights`, and the per-item results are added in shard order.
+ * PHYAMD_EINVAL, naming the function and the argument: null engine, weights or lnl; count < 1; a negative or non-finite weight
+ * (with the item's index in the message); an engine that is not ready (data, models, weights and a topology of its own, and
+ * lengths unless the call brings them).  PHYAMD_EUNSUPPORTED: explicit node matrices together with branch_lengths. */
+int phyamd_gradient_batch_weights(phyamd_engine *e, int flags, int32_t count, const double *weights /* [count][P] */,
+                                  const double *branch_lengths /* [count][2T-1] or NULL */, double *lnl /* [count] */,
+                                  double *cat_gradient /* [count][2T-1][C] or NULL */);
+/* of the last phyamd_gradient_batch_weights: items that ran together / one by one; chunks of items and of patterns the fast path
+ * was cut into; walks = tree walks of the fast path (with branch_lengths: the items walked; without: the pattern chunks, one
+ * walk each, whatever the item count); bytes of batch scratch the engine holds (see phyamd_batch_profile); wall time of the call.
+ * Sharded handles: the fewest items_fast, the most of the other counts, scratch_bytes summed over the shards */
+typedef struct { int32_t items_fast, items_sequential, item_chunks, pattern_chunks, walks;
+                 int64_t scratch_bytes; double ms; } phyamd_weight_batch_profile;
+int phyamd_get_weight_batch_profile(phyamd_engine *e, phyamd_weight_batch_profile *out);
 int phyamd_synchronize(phyamd_engine *e);
 
 /* --- inspection (parity tests, debugging) --- */

@@ -53,6 +53,13 @@ class BatchProfile(C.Structure):
     ]
 
 
+class WeightBatchProfile(C.Structure):
+    _fields_ = [
+        ("items_fast", C.c_int32), ("items_sequential", C.c_int32), ("item_chunks", C.c_int32), ("pattern_chunks", C.c_int32),
+        ("walks", C.c_int32), ("scratch_bytes", C.c_int64), ("ms", C.c_double),
+    ]
+
+
 # every symbol include/physher_amd.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -99,6 +106,8 @@ SYMBOLS = [
     ("phyamd_site_rate_posteriors", C.c_int, [_P, _P, _P]),
     ("phyamd_branch_hessian", C.c_int, [_P, C.c_int, _P, _P, _P]),
     ("phyamd_get_hessian_profile", C.c_int, [_P, C.POINTER(HessianProfile)]),
+    ("phyamd_gradient_batch_weights", C.c_int, [_P, C.c_int, C.c_int32, _P, _P, _P, _P]),
+    ("phyamd_get_weight_batch_profile", C.c_int, [_P, C.POINTER(WeightBatchProfile)]),
     ("phyamd_synchronize", C.c_int, [_P]),
     ("phyamd_get_pattern_log_likelihoods", C.c_int, [_P, _P]),
     ("phyamd_get_partials", C.c_int, [_P, C.c_int, C.c_int, _P]),

@@ -819,10 +819,12 @@ void TreeLikelihoodInterface::GradientEpilogue(double lnl, std::vector<double> &
 }
 
 // lnL (LogLikelihoodBatch) or lnL and the gradient (GradientBatch) for `count` parameter vectors of the tree model: per item the
-// branch lengths as Sync() forms them, ONE phyamd_gradient_batch call, then Gradient's epilogue per item
-void TreeLikelihoodInterface::EvaluateBatch(size_t count, const double *treeParameters, double *logLikelihoods, double *gradients) {
+// branch lengths as Sync() forms them, ONE phyamd_gradient_batch call, then Gradient's epilogue per item.  weights (GradientWeights):
+// a row of pattern weights per item, ONE phyamd_gradient_batch_weights call; treeParameters may then be null: every item on the
+// tree model's current parameters
+void TreeLikelihoodInterface::EvaluateBatch(size_t count, const double *treeParameters, double *logLikelihoods, double *gradients, const double *weights) {
 	if (count == 0) return;
-	if (!treeParameters) throw Error("null treeParameters");
+	if (!treeParameters && !weights) throw Error("null treeParameters");
 	if (count > (size_t)INT32_MAX) throw Error("a batch takes at most 2^31 - 1 items");
 	if (gradients && ((flags_ & (int)TreeLikelihoodGradientFlags::SITE_MODEL) || substRates_ || substFreqs_))
 		throw Error("GradientBatch takes TREE_HEIGHT and BRANCH_MODEL requests: site-model and substitution-model gradients need per-item root terms");
@@ -830,46 +832,58 @@ void TreeLikelihoodInterface::EvaluateBatch(size_t count, const double *treePara
 	auto &I = *impl_;
 	const phyamd::Tree &t = *treeModel_->GetTree();
 	const size_t n = treeModel_->parameterCount_, N = (size_t)t.node_count, C = (size_t)siteModel_->GetModel()->cat_count;
-	std::vector<double> previous(n), lengths(count * N), one;
+	std::vector<double> previous(n), lengths(treeParameters ? count * N : 0), one, current;
 	treeModel_->GetParameters(previous.data());
 	struct PutBack {  // the tree model holds its previous parameters afterwards, whatever happens
 		TreeModelInterface *m;
 		const double *p;
 		~PutBack() { m->SetParameters(p); }
 	} put_back{treeModel_, previous.data()};
-	for (size_t b = 0; b < count; b++) {
+	for (size_t b = 0; b < count && treeParameters; b++) {
 		treeModel_->SetParameters(treeParameters + b * n);
 		FormBranchLengths(one);
 		std::copy(one.begin(), one.end(), lengths.begin() + b * N);
 	}
+	if (!treeParameters) FormBranchLengths(current);
 	// lnL does not depend on the gradient flags.  In compatibility mode the gradient asks for the reference's rescaled arithmetic
 	// (COMPAT_SCALED), which the engine's batched walk does not form: those items are evaluated one by one, never batched
 	const int eflags = gradients && referenceCompat_ ? (PHYAMD_GRAD_FOLD_ROOT_FREQS | PHYAMD_GRAD_COMPAT_SCALED) : 0;
 	std::vector<double> lnl(count), cat_grad(gradients ? count * N * C : 0), cg;
-	phyamd::check(phyamd_gradient_batch(I.engine, eflags, (int32_t)count, lengths.data(), lnl.data(), gradients ? cat_grad.data() : nullptr));
+	if (weights)
+		phyamd::check(phyamd_gradient_batch_weights(I.engine, eflags, (int32_t)count, weights, treeParameters ? lengths.data() : nullptr, lnl.data(),
+		                                            gradients ? cat_grad.data() : nullptr));
+	else
+		phyamd::check(phyamd_gradient_batch(I.engine, eflags, (int32_t)count, lengths.data(), lnl.data(), gradients ? cat_grad.data() : nullptr));
 	const std::vector<double> no_subst;
 	for (size_t b = 0; b < count; b++) {
 		if (!gradients && !(includeJacobian_ && t.reparameterized)) {
 			logLikelihoods[b] = lnl[b];
 			continue;
 		}
-		treeModel_->SetParameters(treeParameters + b * n);
+		if (treeParameters) treeModel_->SetParameters(treeParameters + b * n);
 		if (logLikelihoods) logLikelihoods[b] = lnl[b] + (includeJacobian_ && t.reparameterized ? phyamd::ratio_transform_log_jacobian(t) : 0.0);
 		if (!gradients) continue;
 		cg.assign(cat_grad.begin() + b * N * C, cat_grad.begin() + (b + 1) * N * C);
-		one.assign(lengths.begin() + b * N, lengths.begin() + (b + 1) * N);
+		if (treeParameters) one.assign(lengths.begin() + b * N, lengths.begin() + (b + 1) * N);
+		else one = current;
 		GradientEpilogue(lnl[b], cg, one, no_subst, gradients + b * gradientLength_);
 	}
 }
 
 void TreeLikelihoodInterface::LogLikelihoodBatch(size_t count, const double *treeParameters, double *logLikelihoods) {
 	if (!logLikelihoods) throw Error("null logLikelihoods");
-	EvaluateBatch(count, treeParameters, logLikelihoods, nullptr);
+	EvaluateBatch(count, treeParameters, logLikelihoods, nullptr, nullptr);
 }
 
 void TreeLikelihoodInterface::GradientBatch(size_t count, const double *treeParameters, double *logLikelihoods, double *gradients) {
 	if (!gradients) throw Error("null gradients");
-	EvaluateBatch(count, treeParameters, logLikelihoods, gradients);
+	EvaluateBatch(count, treeParameters, logLikelihoods, gradients, nullptr);
+}
+
+void TreeLikelihoodInterface::GradientWeights(size_t count, const double *weights, const double *treeParameters, double *logLikelihoods, double *gradients) {
+	if (!weights) throw Error("null weights");
+	if (!gradients) throw Error("null gradients");
+	EvaluateBatch(count, treeParameters, logLikelihoods, gradients, weights);
 }
 
 // lnL (LogLikelihoodTrees) or lnL and the branch gradient (GradientTrees) of `count` trees: ONE phyamd_gradient_batch_trees call,

@@ -220,6 +220,15 @@ PYBIND11_MODULE(_phycpp_amd, m) {
 		    self.GradientBatch(count, params.data(), lnl.data(), g.data());
 		    return py::make_tuple(vec(lnl), darray({(py::ssize_t)count, (py::ssize_t)self.gradientLength_}, g.data()));
 	    })
+	    .def("gradient_weights", [](TreeLikelihoodInterface &self, darray weights, std::optional<darray> params) {
+		    if (weights.ndim() != 2 || (size_t)weights.shape(1) != self.GetPatternCount()) throw phyamd::Error("weights: [count][pattern_count]");
+		    const size_t count = (size_t)weights.shape(0);
+		    if (params && (params->ndim() != 2 || (size_t)params->shape(0) != count || (size_t)params->shape(1) != self.TreeParameterCount()))
+			    throw phyamd::Error("tree parameters: [count][parameter_count]");
+		    std::vector<double> lnl(count), g(count * self.gradientLength_);
+		    self.GradientWeights(count, weights.data(), params ? params->data() : nullptr, lnl.data(), g.data());
+		    return py::make_tuple(vec(lnl), darray({(py::ssize_t)count, (py::ssize_t)self.gradientLength_}, g.data()));
+	    }, py::arg("weights"), py::arg("tree_parameters") = py::none())
 	    .def("log_likelihood_trees", [](TreeLikelihoodInterface &self, iarray left, iarray right, iarray roots, darray lengths) {
 		    const size_t count = check_trees(self, left, right, roots, lengths);
 		    std::vector<double> lnl(count);

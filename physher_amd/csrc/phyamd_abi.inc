@@ -493,6 +493,38 @@ int phyamd_gradient_batch_trees(phyamd_engine *g, int flags, int32_t count, cons
 	return sum_batch_over_shards(g, count, lnl, cat_gradient, [&](Shard *s, double *l, double *cg) { return shard_gradient_batch_trees(s, flags, count, left, right, roots, branch_lengths, l, cg); });
 }
 
+// every shard runs the whole batch on its own pattern columns of `weights`; per-item results are added like phyamd_gradient_batch's
+int phyamd_gradient_batch_weights(phyamd_engine *g, int flags, int32_t count, const double *weights, const double *branch_lengths, double *lnl, double *cat_gradient) {
+	static const char *const name = "phyamd_gradient_batch_weights";
+	if (count < 1) return fail(PHYAMD_EINVAL, "%s: count must be >= 1 (got %d)", name, count);
+	if (!weights || !lnl) return fail(PHYAMD_EINVAL, "%s: null %s", name, !weights ? "weights" : "lnl");
+	if (!g || g->shards.empty()) return fail(PHYAMD_EINVAL, "%s: null engine", name);
+	const size_t P = (size_t)g->P;
+	for (size_t b = 0; b < (size_t)count; b++)
+		for (size_t k = 0; k < P; k++) {
+			const double w = weights[b * P + k];
+			if (!(w >= 0.0) || std::isinf(w)) return fail(PHYAMD_EINVAL, "%s: weights of item %zu: pattern %zu has weight %g (a weight is finite and >= 0)", name, b, k, w);
+		}
+	if (group_size(g) == 1) return shard_gradient_batch_weights(g->shards[0], flags, count, weights, P, branch_lengths, lnl, cat_gradient);
+	return sum_batch_over_shards(g, count, lnl, cat_gradient, [&](Shard *s, double *l, double *cg) {
+		const size_t i = (size_t)(std::find(g->shards.begin(), g->shards.end(), s) - g->shards.begin());
+		return shard_gradient_batch_weights(s, flags, count, weights + g->offset[i], P, branch_lengths, l, cg);
+	});
+}
+
+int phyamd_get_weight_batch_profile(phyamd_engine *g, phyamd_weight_batch_profile *out) {
+	// shards choose their paths and chunks themselves: the fewest fast items, the most of everything else; memory adds up
+	return merged_profile(g, &Shard::weight_prof, out, [](phyamd_weight_batch_profile &o, const phyamd_weight_batch_profile &p) {
+		o.items_fast = std::min(o.items_fast, p.items_fast);
+		o.items_sequential = std::max(o.items_sequential, p.items_sequential);
+		o.item_chunks = std::max(o.item_chunks, p.item_chunks);
+		o.pattern_chunks = std::max(o.pattern_chunks, p.pattern_chunks);
+		o.walks = std::max(o.walks, p.walks);
+		o.scratch_bytes += p.scratch_bytes;
+		o.ms = std::max(o.ms, p.ms);
+	});
+}
+
 int phyamd_get_batch_profile(phyamd_engine *g, phyamd_batch_profile *out) {
 	// shards choose their paths themselves: the fewest fast items, the most of everything else
 	return merged_profile(g, &Shard::batch_prof, out, [](phyamd_batch_profile &o, const phyamd_batch_profile &p) {

@@ -12,6 +12,8 @@
 // every item.  No floating-point atomics: a branch term is summed over the 64 lanes by wave_sum (fixed order), written to the
 // slab [item][block][C][node], and k_batch_finish adds the blocks in block order.  An item's arithmetic therefore depends on
 // nothing but its own lengths and op lists: not on the batch size, its position in the batch, or the chunk it ran in.
+// phyamd_gradient_batch_weights gives every item a weight row of its own (BatchArgs::weight_stride) and, where the items share the
+// engine's lengths, runs the walk once in its terms form (batch_walk4<FOLD, true>, phyamd_reweight.inc).
 
 // post-order: node = (P_left p_left) o (P_right p_right); carry 1 / 2: the left / right child's partial is the previous op's result
 // pre-order: the op of `node` forms its children's uppers.  src: where u_node is (BATCH_ROOT: node is the root; BATCH_CARRY: the
@@ -47,6 +49,13 @@ struct BatchArgs {
 	double *upper;                         // [item][upper_slots][C][nblk * 64][4]
 	double *lnl_part;                      // [item][nblk]
 	double *slab;                          // [item][nblk][C][N]
+	// a weight row per item (phyamd_gradient_batch_weights): item b reads weights + b * weight_stride; 0: every item the same row
+	size_t weight_stride;
+	// the terms form (k_reweight_terms4, phyamd_reweight.inc): ONE item over the blocks of a pattern chunk that starts at pattern
+	// k0, its unweighted per-pattern rows in R [1 + N C][Pc] (Pc = 64 nblk); not_finite: set to 1.0 by a pattern whose log L_k is
+	// not finite (null: nobody asks)
+	int k0, Pc;
+	double *R, *not_finite;
 };
 
 // P(t) of every (item, node, category) from the eigen system: k_transition_matrices' arithmetic, each item with its own lengths
@@ -75,21 +84,24 @@ __device__ __forceinline__ d4 batch_message(const BatchArgs &a, cptr mats_c, con
 	return matvec4(M, load4(lower_c + (size_t)(child - a.T) * node_stride));
 }
 
-// grid (nblk, items), block (64, C): the C category waves of one (item, block).  a.grad: the pre-order
-// pass too (a launch argument, not an instantiation: the lnL-only form runs the very instructions of the gradient form's first
-// half, so both return the same lnL bits); FOLD: PHYAMD_GRAD_FOLD_ROOT_FREQS (k_upper4's arithmetic: the root's children start
-// from pi, the state sum drops it)
-template <bool FOLD>
-__global__ __launch_bounds__(BATCH_MAX_CATEGORIES *WAVE) void k_batch_walk4(const BatchArgs a) {
-	__shared__ double sh[BATCH_MAX_CATEGORIES * WAVE];
+// The walk of one (item, block) by its C category waves: the body of k_batch_walk4 below and of k_reweight_terms4
+// (phyamd_reweight.inc).  a.grad: the pre-order pass too (a launch argument, not an instantiation: the lnL-only form runs the very
+// instructions of the gradient form's first half, so both return the same lnL bits); FOLD: PHYAMD_GRAD_FOLD_ROOT_FREQS (k_upper4's
+// arithmetic: the root's children start from pi, the state sum drops it).
+// TERMS: the same arithmetic for one item, but what k_batch_walk4 weights by w_k and sums over the lanes is stored per lane,
+// unweighted, as a row of a.R: row 0 = log L_k, row 1 + c N + node = f . u . (Q P p) / L_k, the root's rows and every row past the
+// last pattern 0
+template <bool FOLD, bool TERMS>
+__device__ __forceinline__ void batch_walk4(const BatchArgs &a, double *sh) {
 	const int lane = threadIdx.x, c = __builtin_amdgcn_readfirstlane(threadIdx.y);  // this wave's category
 	const int blk = blockIdx.x, item = blockIdx.y;
 	// the item's op lists: a wave-uniform offset (the workgroup id times a launch argument) on a kernel argument, so the lists stay
 	// at scalar addresses
 	const BatchOp *lower_ops = a.lower_ops + (size_t)item * a.item_stride, *upper_ops = a.upper_ops + (size_t)item * a.item_stride;
 	const int k0 = blk * WAVE + lane;  // the scratch is padded to whole blocks: every lane owns its cells
-	const bool valid = k0 < a.P;
-	const int k = valid ? k0 : a.P - 1;
+	const int kg = TERMS ? a.k0 + k0 : k0;
+	const bool valid = kg < a.P;
+	const int k = valid ? kg : a.P - 1;
 	const int nops = a.T - 1;
 	const size_t plane = (size_t)a.nblk * WAVE * 4, node_stride = (size_t)a.C * plane;
 	const double *mats_i = a.mats + (size_t)item * a.N * a.C * 16;
@@ -114,14 +126,23 @@ __global__ __launch_bounds__(BATCH_MAX_CATEGORIES *WAVE) void k_batch_walk4(cons
 	__syncthreads();  // the one meeting of the categories
 	double L = 0.0;
 	for (int cc = 0; cc < a.C; cc++) L += sh[cc * WAVE + lane];
-	const double w = valid ? a.weights[k] : 0.0;
-	if (c == 0) {
-		const double s = wave_sum(valid ? log(L) * w : 0.0);
-		if (lane == 0) a.lnl_part[(size_t)item * a.nblk + blk] = s;
+	double w = 1.0;
+	if constexpr (TERMS) {
+		if (c == 0) {
+			const double ll = log(L);
+			a.R[k0] = valid ? ll : 0.0;
+			if (valid && a.not_finite && !isfinite(ll)) *a.not_finite = 1.0;
+		}
+	} else {
+		w = valid ? a.weights[(size_t)item * a.weight_stride + k] : 0.0;
+		if (c == 0) {
+			const double s = wave_sum(valid ? log(L) * w : 0.0);
+			if (lane == 0) a.lnl_part[(size_t)item * a.nblk + blk] = s;
+		}
 	}
 	if (!a.grad) return;
 
-	const double wl = valid ? w / L : 0.0;  // the gradient's w_k / L_k (treelikelihood.c:2879)
+	const double wl = valid ? w / L : 0.0;  // the gradient's w_k / L_k (treelikelihood.c:2879); TERMS: 1 / L_k
 	const d4 one = d4{1., 1., 1., 1.}, f = FOLD ? one : pi;
 	const cptr Q = as_const(a.Q);
 	double *upper_i = a.upper + (size_t)item * a.upper_slots * node_stride + (size_t)k0 * 4;
@@ -129,7 +150,8 @@ __global__ __launch_bounds__(BATCH_MAX_CATEGORIES *WAVE) void k_batch_walk4(cons
 		const cptr mats_c = as_const(mats_i + (size_t)c * 16);
 		const double *lower_c = lower_i + (size_t)c * plane;
 		double *upper_c = upper_i + (size_t)c * plane;
-		double *slab = a.slab + (((size_t)item * a.nblk + blk) * a.C + c) * a.N;
+		double *slab = TERMS ? nullptr : a.slab + (((size_t)item * a.nblk + blk) * a.C + c) * a.N;
+		double *rows = TERMS ? a.R + ((size_t)1 + (size_t)c * a.N) * a.Pc + k0 : nullptr;  // this lane's cell of the category's rows
 		d4 carried = one;
 #pragma unroll 1
 		for (int i = 0; i < nops; i++) {
@@ -143,11 +165,18 @@ __global__ __launch_bounds__(BATCH_MAX_CATEGORIES *WAVE) void k_batch_walk4(cons
 			}
 			const d4 ul = mul4(up, br), ur = mul4(up, bl);  // treelikelihood.c:2142-2147
 			// g[child][c] = sum_k w_k / L_k sum_i f_i u_i (Q P p)_i   (treelikelihood.c:2846-2939)
-			const double gl = wave_sum(wl * dot4(mul4(f, ul), matvec4(opaque(Q), bl)));
-			const double gr = wave_sum(wl * dot4(mul4(f, ur), matvec4(opaque(Q), br)));
-			if (lane == 0) {
-				slab[op.left] = gl;
-				slab[op.right] = gr;
+			const double tl = wl * dot4(mul4(f, ul), matvec4(opaque(Q), bl));
+			const double tr = wl * dot4(mul4(f, ur), matvec4(opaque(Q), br));
+			if constexpr (TERMS) {  // one 512-byte row segment per wave each
+				rows[(size_t)op.left * a.Pc] = valid ? tl : 0.0;
+				rows[(size_t)op.right * a.Pc] = valid ? tr : 0.0;
+				if (op.src == BATCH_ROOT) rows[(size_t)op.node * a.Pc] = 0.0;
+			} else {
+				const double gl = wave_sum(tl), gr = wave_sum(tr);
+				if (lane == 0) {
+					slab[op.left] = gl;
+					slab[op.right] = gr;
+				}
 			}
 			if (op.dst_left >= 0) store4(upper_c + (size_t)op.dst_left * node_stride, ul);
 			if (op.dst_right >= 0) store4(upper_c + (size_t)op.dst_right * node_stride, ur);
@@ -155,6 +184,13 @@ __global__ __launch_bounds__(BATCH_MAX_CATEGORIES *WAVE) void k_batch_walk4(cons
 			if (op.dst_right == BATCH_CARRY) carried = ur;
 		}
 	}
+}
+
+// grid (nblk, items), block (64, C): the C category waves of one (item, block)
+template <bool FOLD>
+__global__ __launch_bounds__(BATCH_MAX_CATEGORIES *WAVE) void k_batch_walk4(const BatchArgs a) {
+	__shared__ double sh[BATCH_MAX_CATEGORIES * WAVE];
+	batch_walk4<FOLD, false>(a, sh);
 }
 
 // out[item][0] = lnL, out[item][1 + node * C + c] = g[node][c] (the root's row 0): the blocks' entries added in block order.

@@ -2,7 +2,7 @@
 //
 // One translation unit, assembled from:
 //   phyamd_memory.inc       owning device arrays and the memory budget they are allocated through
-//   phyamd_device.inc / _level4 / _walk4 / _walk4s / _general / _genwalk / _patterns / _batch4 / _nni4 / _spr4 / _post / _bhess   device code (kernels)
+//   phyamd_device.inc / _level4 / _walk4 / _walk4s / _general / _genwalk / _patterns / _batch4 / _nni4 / _spr4 / _post / _bhess / _reweight   device code (kernels)
 //   phyamd_shard.inc        state of one engine on one GPU (= one shard of the site patterns), the form of its stored lowers
 //   phyamd_schedule.inc     level and tree-walk schedules, device storage
 //   phyamd_launch.inc       kernel launches per pass
@@ -131,6 +131,7 @@ struct NodeOp {
 #include "phyamd_spr4.inc"
 #include "phyamd_post.inc"
 #include "phyamd_bhess.inc"
+#include "phyamd_reweight.inc"
 
 #include "phyamd_shard.inc"
 

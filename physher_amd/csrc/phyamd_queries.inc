@@ -1,4 +1,4 @@
-// phyamd_queries.inc -- the whole-tree query calls on one shard: batches of branch-length vectors and of trees, NNI and SPR scores,
+// phyamd_queries.inc -- the whole-tree query calls on one shard: batches of branch-length vectors, of pattern weights and of trees, NNI and SPR scores,
 // per-pattern posteriors and the full branch Hessian.  They read what the engine holds and write only their own scratch
 // (part of phyamd_engine.hip: one translation unit, internal linkage)
 
@@ -263,17 +263,29 @@ int ensure_batch_scratch(Shard *e, size_t items, const ScratchPlan &plan) {
 	return allocate_batch_scratch(e, items, plan);
 }
 
+// `rows` rows of `width` doubles, src_stride apart on the host, to rows dst_stride apart on the device
+int upload_rows(Shard *e, double *dst, size_t dst_stride, const double *src, size_t src_stride, size_t width, size_t rows) {
+	if (dst_stride == width && src_stride == width) HIP_TRY(hipMemcpyAsync(dst, src, sizeof(double) * width * rows, hipMemcpyHostToDevice, e->stream));
+	else HIP_TRY(hipMemcpy2DAsync(dst, sizeof(double) * dst_stride, src, sizeof(double) * src_stride, sizeof(double) * width, rows, hipMemcpyHostToDevice, e->stream));
+	return PHYAMD_OK;
+}
+
 // one chunk of `items` items through the batched walk: lengths [items][N] (host) -> out [items][rows] (host), rows = 1 or 1 + N C.
 // trees: the items walk their own op lists from their own roots, already in d_batch_item_ops and d_batch_roots; else the
-// engine's.  slots: the upper slots an item of this chunk has in d_batch_upper (at least what its list parks in)
-int run_batch_chunk(Shard *e, int flags, int items, const double *lengths, bool grad, int slots, bool trees, double *out) {
+// engine's.  slots: the upper slots an item of this chunk has in d_batch_upper (at least what its list parks in).  weights: a row
+// of pattern weights per item (host, rows weight_stride apart; phyamd_gradient_batch_weights), or null: the engine's for every item
+int run_batch_chunk(Shard *e, int flags, int items, const double *lengths, bool grad, int slots, bool trees, double *out, const double *weights = nullptr,
+                    size_t weight_stride = 0) {
 	const int nblk = (e->P + WAVE - 1) / WAVE, rows = grad ? 1 + e->N * e->C : 1, nops = e->T - 1;
 	const BatchOp *ops = trees ? e->d_batch_item_ops.get() : e->d_batch_ops.get();
 	const int32_t *roots = trees ? e->d_batch_roots.get() : nullptr;
 	HIP_TRY(hipMemcpyAsync(e->d_batch_len, lengths, sizeof(double) * (size_t)items * e->N, hipMemcpyHostToDevice, e->stream));
 	launch_batch_matrices(e, items, e->d_batch_len, roots, e->d_batch_mats);
-	const BatchArgs a{ops, ops + nops, trees ? 2 * nops : 0, e->T, e->N, e->P, e->C, nblk, slots, grad ? 1 : 0, e->d_tipmask, e->d_freqs, e->d_props,
-	                  e->d_weights, e->d_Q, e->d_batch_mats, e->d_batch_lower, e->d_batch_upper, e->d_batch_lnl, e->d_batch_slab};
+	int rc;
+	if (weights && (rc = upload_rows(e, e->d_reweight_w, (size_t)e->P, weights, weight_stride, (size_t)e->P, (size_t)items))) return rc;
+	BatchArgs a{ops, ops + nops, trees ? 2 * nops : 0, e->T, e->N, e->P, e->C, nblk, slots, grad ? 1 : 0, e->d_tipmask, e->d_freqs, e->d_props,
+	            e->d_weights, e->d_Q, e->d_batch_mats, e->d_batch_lower, e->d_batch_upper, e->d_batch_lnl, e->d_batch_slab};
+	if (weights) a.weights = e->d_reweight_w, a.weight_stride = (size_t)e->P;
 	const dim3 grid(nblk, items), block(WAVE, e->C);
 	if (flags & PHYAMD_GRAD_FOLD_ROOT_FREQS) hipLaunchKernelGGL(k_batch_walk4<true>, grid, block, 0, e->stream, a);
 	else hipLaunchKernelGGL(k_batch_walk4<false>, grid, block, 0, e->stream, a);
@@ -293,26 +305,33 @@ void store_batch_item(const double *row, size_t ncat, double *lnl, double *cat_g
 	mask_if_not_finite(row[0], cat_gradient, ncat);
 }
 
-// the definition of the call: item by item through the ordinary path (the caller puts the engine's lengths back)
-int batch_item_sequential(Shard *e, int flags, const double *lengths, double *lnl, double *cat_gradient) {
+// the definition of the call: item by item through the ordinary path (the caller puts the engine's lengths back, and its weights
+// where the item brings its own; either may be null: the engine's)
+int batch_item_sequential(Shard *e, int flags, const double *lengths, double *lnl, double *cat_gradient, const double *weights = nullptr) {
 	int rc;
-	if ((rc = shard_set_branch_lengths(e, lengths))) return rc;
+	if (weights && (rc = shard_set_pattern_weights(e, weights))) return rc;
+	if (lengths && (rc = shard_set_branch_lengths(e, lengths))) return rc;
 	return cat_gradient ? shard_gradient(e, flags, lnl, cat_gradient) : shard_log_likelihood(e, lnl);
 }
 
-// the items of a batch, each through the batched walk or the ordinary path; prof: how many went which way
-int run_batch(Shard *e, int flags, int32_t count, const double *branch_lengths, double *lnl, double *cat_gradient, phyamd_batch_profile &prof) {
+// the items of a batch, each through the batched walk or the ordinary path; prof: how many went which way.  weights: null, or a
+// row of pattern weights per item, weight_stride apart (phyamd_gradient_batch_weights with lengths: `name` and `walked`, the items
+// the batched walk was launched for)
+int run_batch(Shard *e, int flags, int32_t count, const double *branch_lengths, double *lnl, double *cat_gradient, phyamd_batch_profile &prof,
+              const char *name = "phyamd_gradient_batch", const double *weights = nullptr, size_t weight_stride = 0, int32_t *walked = nullptr) {
 	int rc;
 	if ((rc = check_ready_but_lengths(e))) return rc;
 	for (int n = 0; n < e->N; n++)
 		if (n != e->root && e->explicit_host[n])
-			return fail(PHYAMD_EUNSUPPORTED, "phyamd_gradient_batch: node %d has explicit matrices, which cannot follow per-item branch lengths", n);
+			return fail(PHYAMD_EUNSUPPORTED, "%s: node %d has explicit matrices, which cannot follow per-item branch lengths", name, n);
 	if (cat_gradient && !e->have_Q) return fail(PHYAMD_EINVAL, "the gradient needs the rate matrix: phyamd_set_eigen or phyamd_set_rate_matrix");
 	const bool grad = cat_gradient != nullptr;
 	const size_t N = (size_t)e->N, ncat = N * e->C, rows = grad ? 1 + ncat : 1;
 	std::vector<uint8_t> redo(count, 1);  // items the sequential path (still) has to evaluate
 	if ((rc = ensure_engine_batch_ops(e))) return rc;
-	const ScratchPlan plan = batch_plan(e, grad, e->batch_upper_slots, false);
+	ScratchPlan plan = batch_plan(e, grad, e->batch_upper_slots, false);
+	if (weights) plan.add(e->d_reweight_w, sizeof(double) * (size_t)e->P);
+	const auto row = [&](size_t b) { return weights ? weights + b * weight_stride : nullptr; };
 	std::vector<double> lengths, out;
 	for (size_t first = 0; first < (size_t)count && batch_fast_path(e, flags, 1);) {
 		// (every chunk asks again: an item that went through the ordinary path may have taken the scratch's room)
@@ -323,14 +342,16 @@ int run_batch(Shard *e, int flags, int32_t count, const double *branch_lengths, 
 		lengths.assign(branch_lengths + first * N, branch_lengths + (first + items) * N);
 		out.resize(items * rows);
 		for (size_t b = 0; b < items; b++) lengths[b * N + e->root] = 0.0;  // (ignored, as phyamd_set_branch_lengths does)
-		if ((rc = run_batch_chunk(e, flags, (int)items, lengths.data(), grad, e->batch_upper_slots, false, out.data()))) return rc;
+		if ((rc = run_batch_chunk(e, flags, (int)items, lengths.data(), grad, e->batch_upper_slots, false, out.data(), row(first), weight_stride))) return rc;
 		prof.chunks++;
+		if (walked) *walked += (int32_t)items;
 		for (size_t b = 0; b < items; b++) {
 			const double l = out[b * rows];
 			if (not_finite(l) && e->cfg.rescale == PHYAMD_RESCALE_AUTO) {
 				// the lazy switch's case (treelikelihood.c:1496-1519): this item goes through the ordinary path right away, and
 				// if that turns rescaling on, so does the rest of the batch
-				if ((rc = batch_item_sequential(e, flags, branch_lengths + (first + b) * N, lnl + first + b, grad ? cat_gradient + (first + b) * ncat : nullptr))) return rc;
+				if ((rc = batch_item_sequential(e, flags, branch_lengths + (first + b) * N, lnl + first + b, grad ? cat_gradient + (first + b) * ncat : nullptr, row(first + b))))
+					return rc;
 				redo[first + b] = 0;
 				prof.items_sequential++;
 				continue;
@@ -343,7 +364,7 @@ int run_batch(Shard *e, int flags, int32_t count, const double *branch_lengths, 
 	}
 	for (int b = 0; b < count; b++) {
 		if (!redo[b]) continue;
-		if ((rc = batch_item_sequential(e, flags, branch_lengths + (size_t)b * N, lnl + b, grad ? cat_gradient + (size_t)b * ncat : nullptr))) return rc;
+		if ((rc = batch_item_sequential(e, flags, branch_lengths + (size_t)b * N, lnl + b, grad ? cat_gradient + (size_t)b * ncat : nullptr, row((size_t)b)))) return rc;
 		prof.items_sequential++;
 	}
 	return PHYAMD_OK;
@@ -366,6 +387,154 @@ int shard_gradient_batch(Shard *e, int flags, int32_t count, const double *branc
 			} else
 				e->have_lengths = false;
 		}
+		return rc;
+	});
+}
+
+// ---- a batch of pattern-weight vectors (phyamd_gradient_batch_weights) ---------------------------------------------------------
+
+// The scratch of the shared-lengths path (phyamd_reweight.inc) for pattern chunks of nblk blocks.  An item is a REPLICATE: its
+// weight row over the chunk's patterns, its result row and its segment sums.  Whatever the replicate count: the walk's arrays of
+// ONE item (stored lowers, parked uppers), the rows R and the mark of a log L_k that is not finite.  The op lists and the matrices
+// are the engine's own and count with the engine
+ScratchPlan reweight_plan(Shard *e, bool grad, size_t nblk) {
+	const size_t D = sizeof(double), N = (size_t)e->N, C = (size_t)e->C, Pc = nblk * WAVE, rows = grad ? 1 + N * C : 1;
+	const size_t segments = (Pc + REWEIGHT_SEGMENT - 1) / REWEIGHT_SEGMENT;
+	ScratchPlan p;
+	p.add(e->d_batch_lower, 0, D * (size_t)(e->T - 1) * C * Pc * 4);
+	if (grad) p.add(e->d_batch_upper, 0, D * (size_t)e->batch_upper_slots * C * Pc * 4);
+	p.add(e->d_batch_lnl, 0, D);
+	p.add(e->d_reweight_R, 0, D * rows * Pc);
+	p.add(e->d_reweight_w, D * Pc);
+	p.add(e->d_batch_out, D * rows);
+	p.add(e->d_reweight_part, D * segments * rows);
+	return p;
+}
+
+constexpr size_t REWEIGHT_MAX_CHUNK = (size_t)1 << 20;  // replicates per chunk: gridDim.y of k_reweight_mfma is a sixteenth
+
+// every replicate on the engine's own lengths: ONE walk per pattern chunk leaves R, and the replicates are products with it.
+// *sequential: the engine does not take the batched walk, or (PHYAMD_RESCALE_AUTO) a pattern's log L_k is not finite: nothing has
+// been stored and the caller evaluates the replicates one by one
+int run_reweight(Shard *e, int flags, int32_t count, const double *weights, size_t weight_stride, double *lnl, double *cat_gradient,
+                 phyamd_weight_batch_profile &prof, bool *sequential) {
+	static const char *const name = "phyamd_gradient_batch_weights";
+	int rc;
+	*sequential = false;
+	if ((rc = check_ready(e))) return rc;
+	if (cat_gradient && !e->have_Q) return fail(PHYAMD_EINVAL, "the gradient needs the rate matrix: phyamd_set_eigen or phyamd_set_rate_matrix");
+	if (batch_walk_refusal(e, flags)) {
+		*sequential = true;
+		return PHYAMD_OK;
+	}
+	if ((rc = ensure_engine_batch_ops(e)) || (rc = update_matrices(e))) return rc;
+	const bool grad = cat_gradient != nullptr, lazy = e->cfg.rescale == PHYAMD_RESCALE_AUTO;
+	const int N = e->N, C = e->C, P = e->P, nops = e->T - 1;
+	const size_t ncat = (size_t)N * C, rows = grad ? 1 + ncat : 1, nblk_all = ((size_t)P + WAVE - 1) / WAVE;
+	// the pattern chunk: every block if one replicate fits beside it, else the most blocks that leave room for one
+	const double room = scratch_room(e, (double)batch_scratch_bytes(e), EngineRoom::MayGrow);
+	const auto fit = [&](size_t nb) { return reweight_plan(e, grad, nb).items_in(room); };
+	size_t nblk = nblk_all;
+	if (fit(nblk) < 1.0) {
+		if (fit(1) < 1.0) {
+			const ScratchPlan one = reweight_plan(e, grad, 1);
+			return fail(PHYAMD_ENOMEM, "%s: the scratch of one block of 64 patterns (%.0f bytes, and %.0f per replicate) does not fit the memory budget", name,
+			            (double)one.fixed_bytes(), (double)one.item_bytes());
+		}
+		size_t lo = 1, hi = nblk_all;  // fit(lo) >= 1 > fit(hi)
+		while (hi - lo > 1) {
+			const size_t mid = lo + (hi - lo) / 2;
+			(fit(mid) >= 1.0 ? lo : hi) = mid;
+		}
+		nblk = lo;
+	}
+	const ScratchPlan plan = reweight_plan(e, grad, nblk);
+	const size_t chunk = (size_t)std::min((double)std::min<size_t>((size_t)count, REWEIGHT_MAX_CHUNK), fit(nblk));
+	if (!plan.held(chunk) && e->cfg.max_device_bytes > 0) release_batch_scratch(e);  // (under a cap a call gets exactly its own scratch)
+	if ((rc = plan.allocate(chunk))) return rc;
+
+	const BatchOp *ops = e->d_batch_ops.get();
+	std::vector<double> total((size_t)count * rows), out;
+	double *const mark = lazy ? e->d_batch_lnl.get() : nullptr;
+	for (size_t b0 = 0; b0 < nblk_all; b0 += nblk) {
+		const size_t nb = std::min(nblk, nblk_all - b0), Pc = nb * WAVE, k0 = b0 * WAVE, width = std::min(Pc, (size_t)P - k0);
+		BatchArgs a{ops, ops + nops, 0, e->T, N, P, C, (int)nb, e->batch_upper_slots, grad ? 1 : 0, e->d_tipmask, e->d_freqs, e->d_props,
+		            e->d_weights, e->d_Q, e->d_mats, e->d_batch_lower, e->d_batch_upper, nullptr, nullptr};
+		a.k0 = (int)k0, a.Pc = (int)Pc, a.R = e->d_reweight_R, a.not_finite = mark;
+		if (mark) HIP_TRY(hipMemsetAsync(mark, 0, sizeof(double), e->stream));
+		const dim3 grid((unsigned)nb), block(WAVE, C);
+		if (flags & PHYAMD_GRAD_FOLD_ROOT_FREQS) hipLaunchKernelGGL(k_reweight_terms4<true>, grid, block, 0, e->stream, a);
+		else hipLaunchKernelGGL(k_reweight_terms4<false>, grid, block, 0, e->stream, a);
+		HIP_TRY(hipGetLastError());
+		prof.walks++;
+		prof.pattern_chunks++;
+		for (size_t first = 0; first < (size_t)count; first += chunk) {
+			const size_t items = std::min(chunk, (size_t)count - first);
+			if (width < Pc) HIP_TRY(hipMemsetAsync(e->d_reweight_w, 0, sizeof(double) * items * Pc, e->stream));  // (a garbage NaN times R's 0 is a NaN)
+			if ((rc = upload_rows(e, e->d_reweight_w, Pc, weights + first * weight_stride + k0, weight_stride, width, items))) return rc;
+			const ReweightArgs r{e->d_reweight_w, e->d_reweight_R, e->d_reweight_part, e->d_batch_out, (int)items, (int)rows, (int)Pc,
+			                     (int)((Pc + REWEIGHT_SEGMENT - 1) / REWEIGHT_SEGMENT), N, C};
+			hipLaunchKernelGGL(k_reweight_mfma, dim3((unsigned)((rows + 15) / 16), (unsigned)((items + 15) / 16), (unsigned)r.segments), dim3(WAVE), 0, e->stream, r);
+			hipLaunchKernelGGL(k_reweight_finish, dim3((unsigned)((items * rows + 255) / 256)), dim3(256), 0, e->stream, r);
+			HIP_TRY(hipGetLastError());
+			out.resize(items * rows);
+			double marked = 0.0;
+			HIP_TRY(hipMemcpyAsync(out.data(), e->d_batch_out, sizeof(double) * items * rows, hipMemcpyDeviceToHost, e->stream));
+			if (mark) HIP_TRY(hipMemcpyAsync(&marked, mark, sizeof(double), hipMemcpyDeviceToHost, e->stream));
+			HIP_TRY(hipStreamSynchronize(e->stream));
+			if (marked != 0.0) {  // the lazy switch's case: the ordinary path decides, replicate by replicate
+				*sequential = true;
+				return PHYAMD_OK;
+			}
+			if (b0 == 0) prof.item_chunks++;
+			double *const t = total.data() + first * rows;
+			for (size_t i = 0; i < items * rows; i++) t[i] = b0 == 0 ? out[i] : t[i] + out[i];  // (the pattern chunks in chunk order)
+		}
+	}
+	for (size_t b = 0; b < (size_t)count; b++) store_batch_item(&total[b * rows], ncat, lnl + b, grad ? cat_gradient + b * ncat : nullptr);
+	prof.items_fast = count;
+	return PHYAMD_OK;
+}
+
+// weights: row b at weights + b * weight_stride, this shard's P patterns of it (the group layer passes the handle's pattern count
+// and a pointer advanced to this shard's range)
+int shard_gradient_batch_weights(Shard *e, int flags, int32_t count, const double *weights, size_t weight_stride, const double *branch_lengths, double *lnl,
+                                 double *cat_gradient) {
+	static const char *const name = "phyamd_gradient_batch_weights";
+	if (!e) return fail(PHYAMD_EINVAL, "%s: null engine", name);
+	if (count < 1) return fail(PHYAMD_EINVAL, "%s: count must be >= 1 (got %d)", name, count);
+	if (!weights || !lnl) return fail(PHYAMD_EINVAL, "%s: null %s", name, !weights ? "weights" : "lnl");
+	return profiled_call(e, &Shard::weight_prof, phyamd_weight_batch_profile{}, [&](phyamd_weight_batch_profile &prof) {
+		const std::vector<double> lengths = e->lengths, own = e->weights_host;
+		const bool had_lengths = e->have_lengths, had_weights = e->have_weights;
+		const uint64_t epoch = e->weights_epoch;
+		const size_t ncat = (size_t)e->N * e->C;
+		int rc;
+		if (branch_lengths) {
+			phyamd_batch_profile walk{};
+			rc = run_batch(e, flags, count, branch_lengths, lnl, cat_gradient, walk, name, weights, weight_stride, &prof.walks);
+			prof.items_fast = walk.items_fast, prof.items_sequential = walk.items_sequential, prof.item_chunks = walk.chunks;
+		} else {
+			bool sequential = false;
+			rc = run_reweight(e, flags, count, weights, weight_stride, lnl, cat_gradient, prof, &sequential);
+			for (int b = 0; b < count && sequential && !rc; b++)
+				if (!(rc = batch_item_sequential(e, flags, nullptr, lnl + b, cat_gradient ? cat_gradient + (size_t)b * ncat : nullptr, weights + (size_t)b * weight_stride)))
+					prof.items_sequential++;
+		}
+		// the ordinary path has set items' weights and lengths: the engine's own go back, whichever way the call ends
+		const bool failed = rc != PHYAMD_OK;
+		const std::string why = g_last_error;
+		if (e->weights_epoch != epoch) {
+			const int rc2 = had_weights ? shard_set_pattern_weights(e, own.data()) : PHYAMD_OK;
+			if (!had_weights) e->have_weights = false;
+			if (!rc) rc = rc2;
+		}
+		if (branch_lengths && (prof.items_sequential > 0 || rc)) {
+			const int rc2 = had_lengths ? shard_set_branch_lengths(e, lengths.data()) : PHYAMD_OK;
+			if (!had_lengths) e->have_lengths = false;
+			if (!rc) rc = rc2;
+		}
+		if (failed) g_last_error = why;
 		return rc;
 	});
 }

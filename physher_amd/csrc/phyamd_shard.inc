@@ -284,6 +284,16 @@ struct Shard {
 	DeviceArray<double> d_bhess_tan{&batch_mem}, d_bhess_rows{&batch_mem}, d_bhess_tiles{&batch_mem}, d_bhess_sums{&batch_mem};
 	DeviceArray<char> d_bhess_lists{&batch_mem};
 	phyamd_hessian_profile bhess_prof{};
+	// phyamd_gradient_batch_weights (phyamd_reweight.inc), in the batch scratch's group like the Hessian's arrays: a weight row per
+	// item of a chunk ([items][P] beside the batched walk, [replicates][Pc] of a pattern chunk on the shared-lengths path), and on that
+	// path the walk's rows R [1 + N C][Pc] and the replicates' segment sums [segments][replicates][rows].  The walk itself runs in
+	// d_batch_lower / d_batch_upper and the results leave through d_batch_out
+	DeviceArray<double> d_reweight_w{&batch_mem}, d_reweight_R{&batch_mem}, d_reweight_part{&batch_mem};
+	// the engine's own weights on the host (shard_set_pattern_weights keeps them): a call that evaluates items with weights of
+	// their own through the ordinary path puts these back.  weights_epoch: counts the uploads
+	std::vector<double> weights_host;
+	uint64_t weights_epoch = 0;
+	phyamd_weight_batch_profile weight_prof{};
 };
 
 // ---- what each input invalidates -------------------------------------------------------------------------------------------

@@ -335,6 +335,8 @@ int shard_set_pattern_weights(Shard *e, const double *weights) {
 	if ((rc = bind_device(e))) return rc;
 	HIP_TRY(hipMemcpyAsync(e->tiles > 1 ? e->d_weights_all : e->d_weights, weights, sizeof(double) * e->Ptot, hipMemcpyHostToDevice, e->stream));
 	HIP_TRY(hipStreamSynchronize(e->stream));
+	if (weights != e->weights_host.data()) e->weights_host.assign(weights, weights + e->Ptot);
+	e->weights_epoch++;
 	e->have_weights = true;
 	input_changed(e, Input::PatternWeights);
 	return PHYAMD_OK;

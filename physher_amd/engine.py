@@ -333,6 +333,33 @@ class Engine:
         self._check(self._lib.phyamd_get_hessian_profile(self._h, C.byref(p)))
         return {k: getattr(p, k) for k, _ in p._fields_}
 
+    def gradient_batch_weights(self, weights, branch_lengths=None, flags=0, want_gradient=True):
+        """lnL and the per-category branch gradient for B pattern-weight vectors [B, P] at once -- bootstrap or jackknife replicates
+        (physher_amd.resampling), RELL reweighting, site minibatches: (lnl [B], g [B, N, C] or None).  Item b is what
+        set_pattern_weights(weights[b]), set_branch_lengths(branch_lengths[b]) if branch_lengths [B, N] is given, and
+        gradient(flags) return; the engine's own weights and lengths stay.  Weights are finite and >= 0; a zero drops the pattern.
+        Without branch_lengths one walk of the tree serves every item."""
+        w = _f64(weights)
+        if w.ndim != 2 or w.shape[1] != self.P or w.shape[0] < 1:
+            raise ValueError(f"weights must be [B >= 1, {self.P}] (got {w.shape})")
+        count = w.shape[0]
+        bl = None
+        if branch_lengths is not None:
+            bl = _f64(branch_lengths)
+            if bl.shape != (count, self.N):
+                raise ValueError(f"branch_lengths must be [{count}, {self.N}] (got {bl.shape})")
+        lnl = np.empty(count)
+        g = np.empty((count, self.N, self.C)) if want_gradient else None
+        self._check(self._lib.phyamd_gradient_batch_weights(self._h, flags, count, _ptr(w), None if bl is None else _ptr(bl), _ptr(lnl),
+                                                            None if g is None else _ptr(g)))
+        return lnl, g
+
+    def weight_batch_profile(self):
+        """Of the last gradient_batch_weights: items_fast / items_sequential, item_chunks, pattern_chunks, walks, scratch_bytes, ms."""
+        p = _lib.WeightBatchProfile()
+        self._check(self._lib.phyamd_get_weight_batch_profile(self._h, C.byref(p)))
+        return {k: getattr(p, k) for k, _ in p._fields_}
+
     def store(self):
         """Remember the current (evaluated) state: parameters, lnL and partials (MCMC store)."""
         self._check(self._lib.phyamd_store(self._h))
