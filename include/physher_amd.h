@@ -475,6 +475,26 @@ int phyamd_get_node_matrices(phyamd_engine *e, int node, int derivative, double 
  * number of ops (at most `capacity` of them are written) or a negative PHYAMD_E* code. */
 int phyamd_post_order_parks(int32_t tip_count, const int32_t *left /* [2T-1] */, const int32_t *right, int32_t root, int32_t second_slot,
                             int32_t *out /* [capacity][8] */, int32_t capacity);
+/* The pre-order walk of a tree as one of its 4-state kernels runs it, from the host schedule alone (no device, no engine): the ops
+ * in launch order -- the top part, then the cut subtrees' chunks -- PHYAMD_PRE_ORDER_COLUMNS ints each.
+ *   form 0: the chunked list as k_upper4_walk reads it (one LDS park slot per wave);
+ *   form 1: the same list after the streamed walk's rewrites, as k_upper4_stream reads its descriptors (two LDS slots, the op in
+ *           front's registers instead of a slot it would only just have stored, children swapped so that the carried one is left);
+ *   form 2: the one unchunked list, as k_upper4_walk's parameter form reads it (no LDS slot: every park has an HBM slot).
+ * Columns: 0 chunk | 1 node | 2 left | 3 right | 4, 5 kind of the left / right child (0 tip, 1 stored, 2 DEEP: two fringe or tip
+ * halves, an op of its own, 3 cherry, 4 cherry + tip) | 6, 7 kinds of a DEEP left child's halves, 8, 9 of a DEEP right child's
+ * (-1: the child is not DEEP) | 10 where the node's own upper comes from (0: nowhere, the root; 1: the registers of the op in
+ * front; 2 / 3: the wave's first / second LDS slot; 4: HBM) | 11 its HBM slot (-1: none) | 12 where the left child's upper goes
+ * (0: nowhere, a tip or fringe child; 1: to the next op in registers; 2 / 3: LDS slot; 4: HBM) | 13 the HBM slot it is stored to
+ * (-1: not stored) | 14, 15 the same for the right child | 16 form 1: the HBM slot prefetched for the next op (-1: none) |
+ * 17 bit 0 / 1: the left / right child is the root of a cut subtree (its op opens another chunk) | 18 the carried child (0: none,
+ * 1: left, 2: right; forms 0 and 2: as scheduled, even where a cut sent it through HBM) | 19 the number of branch terms the op
+ * produces | 20-29 their nodes, in the order of the op's result rows (-1: unused).
+ * *hbm_slots (may be NULL): the upper slots the list needs.  Returns the number of ops (at most `capacity` of them are written)
+ * or a negative PHYAMD_E* code. */
+#define PHYAMD_PRE_ORDER_COLUMNS 30
+int phyamd_pre_order_schedule(int32_t tip_count, const int32_t *left /* [2T-1] */, const int32_t *right, int32_t root, int32_t form,
+                              int32_t *out /* [capacity][PHYAMD_PRE_ORDER_COLUMNS] */, int32_t capacity, int32_t *hbm_slots);
 int phyamd_is_rescaling(phyamd_engine *e);
 /* SingleTreeLikelihood_use_rescaling (treelikelihood.c:1410-1423) after construction: PHYAMD_RESCALE_ALWAYS / _NEVER switch
  * at once (the next evaluation recomputes every node), PHYAMD_RESCALE_AUTO keeps the current state and re-arms the lazy switch. */
