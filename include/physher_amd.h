@@ -418,6 +418,19 @@ int phyamd_branch_hessian(phyamd_engine *e, int flags, double *lnl, double *grad
  * ran in (sharded: the most of any shard); scratch_bytes = the batch scratch held afterwards, summed over the shards */
 typedef struct { int32_t chunks; int64_t pairs, scratch_bytes; double ms; } phyamd_hessian_profile;
 int phyamd_get_hessian_profile(phyamd_engine *e, phyamd_hessian_profile *out);
+/* How the 20 / 60 / 61-state kernels of the last post-order pass and of the last pre-order pass were launched (read-only
+ * bookkeeping of the launchers; a pass that found its results current and launched nothing leaves the record as it was).
+ * lower_family: 0 = k_lower_gen, one launch per tree level; 1 = k_lower_gen_walk, one launch whose workgroups draw (pattern
+ * group, category) units from a counter; -1 = no post-order pass has run.  *_slots: the workgroups the card holds at one time for
+ * that pass's kernel, as the occupancy query answered (what the tile chooser and the walk's launch are sized by).  *_levels: tree
+ * levels launched (an incremental pass: only those with a node to recompute); *_tiles_min / _max: the fewest and the most
+ * 16-pattern tiles per wave over those levels (0: none launched; the walk has neither levels nor tiles: 0).  walk_units / walk_workgroups: the
+ * walk's work units and the workgroups launched for them (0 unless lower_family is 1).  The pre-order pass is the gradient's, the
+ * parameter gradient's or phyamd_branch_hessian_diagonal's (upper_hess = 1: k_upper_gen's HESS form); upper_levels = 0: none has
+ * run.  Sharded handles: the first shard's.  PHYAMD_EUNSUPPORTED on a 4-state engine, with the condition in the message. */
+typedef struct { int32_t lower_family, lower_slots, lower_levels, lower_tiles_min, lower_tiles_max, walk_units, walk_workgroups;
+                 int32_t upper_hess, upper_slots, upper_levels, upper_tiles_min, upper_tiles_max; } phyamd_general_profile;
+int phyamd_get_general_profile(phyamd_engine *e, phyamd_general_profile *out);
 /* lnL and the per-category branch gradient for `count` pattern-weight vectors on the engine's tree, data and models: the batch
  * axis of resampling -- bootstrap and jackknife replicates of one alignment (phyresampling.c:105-260 builds a SitePattern and a
  * likelihood object per replicate), RELL reweighting, site minibatches (a weight vector with zeros).  weights [count][P], any

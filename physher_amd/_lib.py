@@ -47,6 +47,11 @@ class HessianProfile(C.Structure):
     _fields_ = [("chunks", C.c_int32), ("pairs", C.c_int64), ("scratch_bytes", C.c_int64), ("ms", C.c_double)]
 
 
+class GeneralProfile(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("lower_family", "lower_slots", "lower_levels", "lower_tiles_min", "lower_tiles_max", "walk_units",
+                                         "walk_workgroups", "upper_hess", "upper_slots", "upper_levels", "upper_tiles_min", "upper_tiles_max")]
+
+
 class BatchProfile(C.Structure):
     _fields_ = [
         ("items_fast", C.c_int32), ("items_sequential", C.c_int32), ("chunks", C.c_int32), ("scratch_bytes", C.c_int64), ("ms", C.c_double),
@@ -106,6 +111,7 @@ SYMBOLS = [
     ("phyamd_site_rate_posteriors", C.c_int, [_P, _P, _P]),
     ("phyamd_branch_hessian", C.c_int, [_P, C.c_int, _P, _P, _P]),
     ("phyamd_get_hessian_profile", C.c_int, [_P, C.POINTER(HessianProfile)]),
+    ("phyamd_get_general_profile", C.c_int, [_P, C.POINTER(GeneralProfile)]),
     ("phyamd_gradient_batch_weights", C.c_int, [_P, C.c_int, C.c_int32, _P, _P, _P, _P]),
     ("phyamd_get_weight_batch_profile", C.c_int, [_P, C.POINTER(WeightBatchProfile)]),
     ("phyamd_synchronize", C.c_int, [_P]),

@@ -641,6 +641,15 @@ int phyamd_get_hessian_profile(phyamd_engine *g, phyamd_hessian_profile *out) {
 	return rc;
 }
 
+int phyamd_get_general_profile(phyamd_engine *g, phyamd_general_profile *out) {
+	if (!g || g->shards.empty()) return fail(PHYAMD_EINVAL, "phyamd_get_general_profile: null engine");
+	if (!out) return fail(PHYAMD_EINVAL, "phyamd_get_general_profile: null out");
+	const Shard *s = g->shards[0];  // (the shards choose their tiles themselves, from their own pattern counts: the first one's)
+	if (!s->generic) return fail(PHYAMD_EUNSUPPORTED, "phyamd_get_general_profile: %d states (the profile is of the 20 / 60 / 61-state kernels' launches)", s->S);
+	*out = s->gen_prof;
+	return PHYAMD_OK;
+}
+
 // device-resident results (one process per GPU: the caller reduces them across processes with ONE RCCL all-reduce)
 int phyamd_log_likelihood_device(phyamd_engine *g, double *device_out) {
 	CHECK_GROUP(g);

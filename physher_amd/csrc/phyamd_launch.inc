@@ -694,6 +694,25 @@ inline int choose_gen_tiles(int P, int waves, long work, int slots, double stage
 
 inline double gen_stage_cost(int S) { return S == 20 ? 2.0 : 0.6; }
 
+// the levels a pass launched and the fewest and the most tiles per wave among them (phyamd_get_general_profile)
+struct TileRange {
+	int levels = 0, lo = 0, hi = 0;
+	void add(int tiles) {
+		lo = levels ? std::min(lo, tiles) : tiles;
+		hi = levels ? std::max(hi, tiles) : tiles;
+		levels++;
+	}
+};
+void record_lower_levels(Shard *e, int slots, const TileRange &r) {
+	phyamd_general_profile &g = e->gen_prof;
+	g.lower_family = 0, g.lower_slots = slots, g.lower_levels = r.levels, g.lower_tiles_min = r.lo, g.lower_tiles_max = r.hi;
+	g.walk_units = g.walk_workgroups = 0;
+}
+void record_upper_levels(Shard *e, bool hess, int slots, const TileRange &r) {
+	phyamd_general_profile &g = e->gen_prof;
+	g.upper_hess = hess, g.upper_slots = slots, g.upper_levels = r.levels, g.upper_tiles_min = r.lo, g.upper_tiles_max = r.hi;
+}
+
 template <int RT, int KT, bool SCALE>
 int launch_lower_gen(Shard *e) {
 	const std::vector<int> &level_off = *e->act_level_off;
@@ -707,11 +726,13 @@ int launch_lower_gen(Shard *e) {
 	if (e->gen_slots[0][SCALE] == 0) e->gen_slots[0][SCALE] = resident_workgroups(e, k_lower_gen<RT, KT, false, SCALE>, WV * 64, lds);  // per engine: per device
 	const int slots = e->gen_slots[0][SCALE];
 	int launched = 0;
+	TileRange range;
 	for (int lv = 0; lv < levels; lv++) {
 		const int off = level_off[lv], cnt = level_off[lv + 1] - off;
 		if (cnt == 0) continue;
 		launched++;
 		const int tiles = choose_gen_tiles(e->P, WV, (long)cnt * e->C, slots, gen_stage_cost(e->S));
+		range.add(tiles);
 		dim3 grid((e->P + WV * 16 * tiles - 1) / (WV * 16 * tiles), cnt, e->C);
 		const bool is_root = lv == levels - 1;
 		if (is_root)
@@ -728,6 +749,7 @@ int launch_lower_gen(Shard *e) {
 	hipLaunchKernelGGL(k_root_finish, dim3(e->nblk_root), dim3(256), 0, e->stream, e->P, e->C, e->d_Lc, e->d_weights, lscale_root, e->d_plk, e->d_wl, e->d_lnl_part);
 	HIP_TRY(hipGetLastError());
 	e->prof.lower_launches = launched;
+	record_lower_levels(e, slots, range);
 	return PHYAMD_OK;
 }
 
@@ -747,10 +769,12 @@ int launch_upper_gen_v(Shard *e, bool compat) {
 	// rows of the gradient slabs are e->nblk wide (the finest grid); a level writes the first grid.x entries of its rows and
 	// the reduction adds the whole row in a fixed order: the rest must be zero
 	HIP_TRY(hipMemsetAsync(e->d_gpart, 0, sizeof(double) * (size_t)e->N * e->C * e->gpart_row, e->stream));
+	TileRange range;
 	for (int lv = 0; lv < levels; lv++) {
 		const int off = e->upper_level_off[lv], cnt = e->upper_level_off[lv + 1] - off;
 		if (cnt == 0) continue;
 		const int tiles = choose_gen_tiles(e->P, WV, (long)cnt * e->C, slots, gen_stage_cost(e->S));
+		range.add(tiles);
 		dim3 grid((e->P + WV * 16 * tiles - 1) / (WV * 16 * tiles), cnt, e->C);
 		if (SCALE) mxu = e->d_gen_scratch + (size_t)cnt * 3 * e->C * e->P;
 		hipLaunchKernelGGL((k_upper_gen<RT, KT, FOLD, SCALE, false>), grid, dim3(WV * 64), lds, e->stream, e->d_upper_ops + off, e->T, e->P, e->Pp, e->C,
@@ -769,6 +793,7 @@ int launch_upper_gen_v(Shard *e, bool compat) {
 	}
 	HIP_TRY(hipGetLastError());
 	e->prof.upper_launches = levels;
+	record_upper_levels(e, false, slots, range);
 	return PHYAMD_OK;
 }
 
@@ -798,11 +823,13 @@ int launch_upper_gen_hess(Shard *e, double *out) {
 	HIP_TRY(hipMemsetAsync(e->d_hess, 0, sizeof(double) * (size_t)e->hess_nwg * 2 * e->N, e->stream));  // (the root's entries stay zero)
 	double *nd = e->d_gen_scratch;
 	int launched = 0;
+	TileRange range;
 	for (int lv = 0; lv < levels; lv++) {
 		const int off = e->upper_level_off[lv], cnt = e->upper_level_off[lv + 1] - off;
 		if (cnt == 0) continue;
 		launched++;
 		const int tiles = choose_gen_tiles(e->P, WV, (long)cnt * e->C, slots, gen_stage_cost(e->S));
+		range.add(tiles);
 		dim3 grid((e->P + WV * 16 * tiles - 1) / (WV * 16 * tiles), cnt, e->C);
 		double *mxu = SCALE ? e->d_gen_scratch + (size_t)cnt * 5 * e->C * e->P : nullptr;
 		hipLaunchKernelGGL((k_upper_gen<RT, KT, false, SCALE, true>), grid, dim3(WV * 64), lds, e->stream, e->d_upper_ops + off, e->T, e->P, e->Pp, e->C,
@@ -815,6 +842,7 @@ int launch_upper_gen_hess(Shard *e, double *out) {
 			                   e->d_props, e->d_rates, (const int *)e->d_hess_tab, e->d_hess);
 	}
 	HIP_TRY(hipGetLastError());
+	record_upper_levels(e, true, slots, range);
 	return finish_hess_slab(e, out, launched);
 }
 
@@ -844,6 +872,9 @@ int launch_lower_gen_walk(Shard *e) {
 	                   e->d_lnl_part);
 	HIP_TRY(hipGetLastError());
 	e->prof.lower_launches = 1;
+	e->gen_prof.lower_family = 1, e->gen_prof.lower_slots = e->gen_walk_slots[0], e->gen_prof.lower_levels = 0;
+	e->gen_prof.lower_tiles_min = e->gen_prof.lower_tiles_max = 0;
+	e->gen_prof.walk_units = units, e->gen_prof.walk_workgroups = wgs;
 	return PHYAMD_OK;
 }
 template <int RT, int KT>

@@ -200,6 +200,8 @@ struct Shard {
 	int hess_nwg = 0, hess_P = -1, hess_levels = -1;
 	DeviceArray<double> d_hess_invf{&mem};  // 20 / 60 / 61 states: 1 / pi [S]
 	int gen_hess_slots[2] = {0, 0};  // resident workgroups of k_upper_gen<HESS> [SCALE]
+	// how the last 20 / 60 / 61-state post-order and pre-order passes were launched (phyamd_get_general_profile): written by their launchers
+	phyamd_general_profile gen_prof{-1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 	DeviceArray<double> d_branch{&mem};  // phyamd_branch_log_likelihood: [C][3][16] matrices | [3][blocks] partial sums | [3]
 	bool upper_fold = false;         // the stored uppers carry the root frequencies (last gradient call used FOLD)
 	DeviceArray<double> d_rf_part{&mem};      // [S][blocks] partial sums of k_root_frequency_term, then [S]

@@ -333,6 +333,15 @@ class Engine:
         self._check(self._lib.phyamd_get_hessian_profile(self._h, C.byref(p)))
         return {k: getattr(p, k) for k, _ in p._fields_}
 
+    def general_profile(self):
+        """How the 20 / 60 / 61-state kernels of the last post-order and the last pre-order pass were launched: lower_family (0: one
+        launch per level, 1: the walk, -1: none yet), lower_slots / upper_slots (resident workgroups the launches were sized by),
+        lower_levels / upper_levels, the fewest and the most tiles per wave over those levels (lower_tiles_min / _max, upper_tiles_min
+        / _max), walk_units and walk_workgroups, upper_hess (1: the pass of branch_hessian_diagonal).  EngineError at 4 states."""
+        p = _lib.GeneralProfile()
+        self._check(self._lib.phyamd_get_general_profile(self._h, C.byref(p)))
+        return {k: getattr(p, k) for k, _ in p._fields_}
+
     def gradient_batch_weights(self, weights, branch_lengths=None, flags=0, want_gradient=True):
         """lnL and the per-category branch gradient for B pattern-weight vectors [B, P] at once -- bootstrap or jackknife replicates
         (physher_amd.resampling), RELL reweighting, site minibatches: (lnl [B], g [B, N, C] or None).  Item b is what
