@@ -116,10 +116,16 @@ int phyamd_set_pattern_weights(phyamd_engine *e, const double *weights /* [P] */
 int phyamd_compress_patterns(int device /* -1: current */, int32_t taxon_count, int64_t site_count, const uint8_t *const *rows,
                              const uint8_t *symbol_codes /* [256] or NULL */, int32_t *pattern_count, uint8_t *patterns, double *weights);
 
-/* --- tree: Tree/Node ids, Node_left/right (tree.c:183-224) --- */
+/* --- tree: Tree/Node ids, Node_left/right (tree.c:183-224) ---
+ * Tips are 0..T-1, internal ids T..2T-2 in any order, any internal node may be the root.  May be called again on an engine that
+ * has evaluated: every partial is dropped, the schedule is rebuilt, a stored state (phyamd_store) is forgotten.  Branch lengths go
+ * by node id and stay: the engine keeps the vector of the last phyamd_set_branch_lengths / phyamd_set_branch_length as the caller
+ * sent it, the entry at the root's id included, so after a call that moves the root to another id the old root's id has the length
+ * that was sent for it (not 0), and the new root's entry is the one ignored.  Explicit node matrices stay with their ids too.
+ * A refused call (PHYAMD_EINVAL: not a binary tree over these ids) leaves the engine on the tree it had. */
 int phyamd_set_topology(phyamd_engine *e, const int32_t *left, const int32_t *right /* [2T-1], -1 for tips */, int root);
 /* branch length per node id, already multiplied by the clock rate for time trees
- * (treelikelihood.c:1652-1663); the root entry is ignored. */
+ * (treelikelihood.c:1652-1663); the root entry is ignored, and kept for a later change of root (phyamd_set_topology). */
 int phyamd_set_branch_lengths(phyamd_engine *e, const double *lengths /* [2T-1] */);
 
 /* One branch: Node_set_distance + update_nodes[node] = true (treelikelihood.c:73-92).  The next evaluation recomputes only
@@ -479,6 +485,10 @@ int phyamd_get_pattern_log_likelihoods(phyamd_engine *e, double *out /* [P] */);
 /* lower (upper=0) or upper (upper=1) partials of a node after the last evaluation, reference layout
  * [C][P][S]. Upper partials exist only after phyamd_gradient with keep_partials enabled. */
 int phyamd_get_partials(phyamd_engine *e, int node, int upper, double *out);
+/* P(t_n r_c) of a node, or with derivative = 1 its derivative in the argument t_n r_c (substmodel.c:695-723: WITHOUT the factor
+ * r_c), as the next evaluation uses them.  A node with explicit matrices (phyamd_set_node_matrices, phyamd_set_matrices): what
+ * was set, and Q P for the derivative -- the only one the engine defines for such a node (the branch term of its gradient), Q
+ * from phyamd_set_rate_matrix / phyamd_set_eigen; PHYAMD_EINVAL without a Q. */
 int phyamd_get_node_matrices(phyamd_engine *e, int node, int derivative, double *out /* [C][S][S] */);
 /* The post-order walk of a tree as the streamed 4-state kernel runs it, from the host schedule alone (no device, no engine): the
  * ops in launch order -- the cut subtrees' chunks, then the top part -- eight ints each: chunk | node | left | right | where the

@@ -375,7 +375,7 @@ int shard_gradient_batch(Shard *e, int flags, int32_t count, const double *branc
 	if (count < 1) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch: count must be >= 1 (got %d)", count);
 	if (!branch_lengths || !lnl) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch: null branch_lengths or lnl");
 	return profiled_call(e, &Shard::batch_prof, phyamd_batch_profile{}, [&](phyamd_batch_profile &prof) {
-		const std::vector<double> lengths = e->lengths;
+		const std::vector<double> lengths = e->lengths_sent;
 		const bool had_lengths = e->have_lengths;
 		int rc = run_batch(e, flags, count, branch_lengths, lnl, cat_gradient, prof);
 		if (prof.items_sequential > 0 || rc) {  // the ordinary path has set items' lengths: the engine's own go back
@@ -505,7 +505,7 @@ int shard_gradient_batch_weights(Shard *e, int flags, int32_t count, const doubl
 	if (count < 1) return fail(PHYAMD_EINVAL, "%s: count must be >= 1 (got %d)", name, count);
 	if (!weights || !lnl) return fail(PHYAMD_EINVAL, "%s: null %s", name, !weights ? "weights" : "lnl");
 	return profiled_call(e, &Shard::weight_prof, phyamd_weight_batch_profile{}, [&](phyamd_weight_batch_profile &prof) {
-		const std::vector<double> lengths = e->lengths, own = e->weights_host;
+		const std::vector<double> lengths = e->lengths_sent, own = e->weights_host;
 		const bool had_lengths = e->have_lengths, had_weights = e->have_weights;
 		const uint64_t epoch = e->weights_epoch;
 		const size_t ncat = (size_t)e->N * e->C;

@@ -135,6 +135,9 @@ struct Shard {
 
 	std::vector<int32_t> left, right, parent;
 	std::vector<double> lengths, model, freqs, rates, props;
+	// lengths: what the device holds (the root's entry 0).  lengths_sent: the caller's own values by node id, the entry at the
+	// root's id too: a new topology with another root takes the old root's branch from here (shard_set_topology)
+	std::vector<double> lengths_sent;
 	std::vector<uint8_t> explicit_host;
 	bool have_topology = false, have_lengths = false, have_eigen = false, have_freqs = false, have_rates = false, have_weights = false;
 	std::vector<uint8_t> tip_set;

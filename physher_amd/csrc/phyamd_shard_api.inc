@@ -342,6 +342,8 @@ int shard_set_pattern_weights(Shard *e, const double *weights) {
 	return PHYAMD_OK;
 }
 
+int upload_lengths(Shard *e);  // (below)
+
 int shard_set_topology(Shard *e, const int32_t *left, const int32_t *right, int root) {
 	CHECK_ENGINE(e);
 	if (!left || !right) return fail(PHYAMD_EINVAL, "null topology arrays");
@@ -409,6 +411,8 @@ int shard_set_topology(Shard *e, const int32_t *left, const int32_t *right, int 
 	if ((rc = upload_schedule(e))) return roll_back(rc);
 	if ((rc = ensure_lower_storage(e))) return roll_back(rc);
 	e->have_topology = true;
+	// lengths go by node id: the branch above the old root's id is the one the caller sent for that id, the new root's is ignored
+	if (e->have_lengths && (!had_topology || root != old_root) && (rc = upload_lengths(e))) return rc;
 	input_changed(e, Input::Topology);
 	return PHYAMD_OK;
 }
@@ -418,7 +422,16 @@ int shard_set_branch_lengths(Shard *e, const double *lengths) {
 	if (!lengths) return fail(PHYAMD_EINVAL, "null lengths");
 	int rc;
 	if ((rc = bind_device(e))) return rc;
-	e->lengths.assign(lengths, lengths + e->N);
+	e->lengths_sent.assign(lengths, lengths + e->N);
+	if ((rc = upload_lengths(e))) return rc;
+	e->have_lengths = true;
+	input_changed(e, Input::BranchLengths);
+	return PHYAMD_OK;
+}
+
+// the caller's lengths with the entry at the root's id zeroed (the kernels skip the root; the batch calls copy the vector) -> device
+int upload_lengths(Shard *e) {
+	e->lengths = e->lengths_sent;
 	if (e->have_topology) e->lengths[e->root] = 0.0;
 	// no stream synchronisation per call (one per evaluation in an optimiser's loop): the vector goes through a pinned staging
 	// buffer that is only waited for if the previous upload from it is still in flight
@@ -430,8 +443,6 @@ int shard_set_branch_lengths(Shard *e, const double *lengths) {
 	std::memcpy(e->h_lengths, e->lengths.data(), sizeof(double) * e->N);
 	HIP_TRY(hipMemcpyAsync(e->d_lengths, e->h_lengths, sizeof(double) * e->N, hipMemcpyHostToDevice, e->stream));
 	HIP_TRY(hipEventRecord(e->ev_lengths, e->stream));
-	e->have_lengths = true;
-	input_changed(e, Input::BranchLengths);
 	return PHYAMD_OK;
 }
 
@@ -442,7 +453,7 @@ int shard_set_branch_length(Shard *e, int node, double length) {
 	int rc;
 	if ((rc = bind_device(e))) return rc;
 	if (e->lengths[node] == length) return PHYAMD_OK;
-	e->lengths[node] = length;
+	e->lengths[node] = e->lengths_sent[node] = length;
 	HIP_TRY(hipMemcpyAsync(e->d_lengths + node, &e->lengths[node], sizeof(double), hipMemcpyHostToDevice, e->stream));
 	HIP_TRY(hipStreamSynchronize(e->stream));
 	input_changed(e, Input::BranchLength, node);
@@ -481,7 +492,7 @@ int shard_store(Shard *e) {
 	HIP_TRY(hipStreamSynchronize(e->stream));
 	auto &st = e->stored;
 	st.lnl = e->h_result[0];
-	st.lengths = e->lengths;
+	st.lengths = e->lengths_sent;
 	st.model = e->model;
 	st.freqs = e->freqs;
 	st.rates = e->rates;
@@ -1052,8 +1063,22 @@ int shard_get_node_matrices(Shard *e, int node, int derivative, double *out) {
 	if ((rc = check_ready(e))) return rc;
 	if ((rc = update_matrices(e))) return rc;
 	const size_t sz = (size_t)e->C * e->S * e->S;
-	HIP_TRY(hipMemcpyAsync(out, (derivative ? e->d_dmats : e->d_mats) + (size_t)node * sz, sizeof(double) * sz, hipMemcpyDeviceToHost, e->stream));
+	const bool from_Q = derivative && e->explicit_host[node];  // (k_transition_matrices skips the node: d_dmats holds nothing of it)
+	if (from_Q && !e->have_Q)
+		return fail(PHYAMD_EINVAL, "node %d has explicit matrices: their derivative is Q P, which needs phyamd_set_rate_matrix or phyamd_set_eigen", node);
+	HIP_TRY(hipMemcpyAsync(out, (derivative && !from_Q ? e->d_dmats : e->d_mats) + (size_t)node * sz, sizeof(double) * sz, hipMemcpyDeviceToHost, e->stream));
 	HIP_TRY(hipStreamSynchronize(e->stream));
+	if (from_Q) {  // the only derivative the engine defines for such a node: Q P per category, without r_c like the eigen nodes' rows
+		const int S = e->S;
+		std::vector<double> P(out, out + sz);
+		for (int c = 0; c < e->C; c++)
+			for (int i = 0; i < S; i++)
+				for (int j = 0; j < S; j++) {
+					double v = 0.0;
+					for (int k = 0; k < S; k++) v += e->Q_host[(size_t)i * S + k] * P[((size_t)c * S + k) * S + j];
+					out[((size_t)c * S + i) * S + j] = v;
+				}
+	}
 	return PHYAMD_OK;
 }
 

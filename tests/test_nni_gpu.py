@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from gpu_util import engine_from_problem, random_problem
+from invalidation_util import parents as _parents, rearranged as _rearranged  # (the NNI neighbours are built there)
 from oracle.phyoracle import branch_gradient_from_cat
 from physher_amd.engine import GRAD_FOLD_ROOT_FREQS, RESCALE_ALWAYS, RESCALE_AUTO, RESCALE_NEVER, EngineError
 from test_batch_gpu import _ambiguous_partials, _bits, _deep
@@ -22,27 +23,8 @@ pytestmark = pytest.mark.gpu
 EINVAL, EUNSUPPORTED = -1, -4
 
 
-def _parents(pb):
-    parent = -np.ones(pb.N, dtype=np.int64)
-    for n in range(pb.T, pb.N):
-        parent[pb.left[n]] = parent[pb.right[n]] = n
-    return parent
-
-
 def _candidates(pb):
     return [v for v in range(pb.T, pb.N) if v != pb.root]
-
-
-def _rearranged(pb, v, k, t):
-    """arrangement k of candidate v with the length of v set to t: (left, right, branch_lengths) of a whole tree"""
-    left, right, bl = pb.left.copy(), pb.right.copy(), pb.branch_lengths.copy()
-    bl[v] = t
-    if k > 0:
-        u = _parents(pb)[v]
-        of_u = left if left[u] != v else right  # the array that holds u's slot of the sibling
-        of_v = left if k == 1 else right       # k = 1: a = left[v] changes places with the sibling; k = 2: b = right[v]
-        of_u[u], of_v[v] = of_v[v], of_u[u]
-    return left, right, bl
 
 
 def _reference(pb, ref_engine, v, k, t):
