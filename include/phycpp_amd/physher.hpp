@@ -297,6 +297,13 @@ class TreeLikelihoodInterface : public CallableModelInterface {
 	void LogLikelihoodTrees(size_t count, const int32_t *left, const int32_t *right, const int32_t *roots, const double *branchLengths, double *logLikelihoods);
 	void GradientTrees(size_t count, const int32_t *left, const int32_t *right, const int32_t *roots, const double *branchLengths, double *logLikelihoods,
 	                   double *branchGradients);
+	// Beyond the reference surface: the per-pattern log-likelihoods of `count` TREES at once, and RELL replicates of them (one
+	// phyamd_pattern_log_likelihoods_trees call; see include/physher_amd.h): the arrays are LogLikelihoodTrees'; logLikelihoods
+	// [count]; patternLogLikelihoods [count][patterns] in this object's pattern order, or null; replicateWeights
+	// [replicateCount][patterns], finite and >= 0, with replicateLogLikelihoods [replicateCount][count], or 0 and both null.  The
+	// tree model and this object's own state are unchanged.
+	void PatternLogLikelihoodsTrees(size_t count, const int32_t *left, const int32_t *right, const int32_t *roots, const double *branchLengths, double *logLikelihoods,
+	                                double *patternLogLikelihoods, size_t replicateCount, const double *replicateWeights, double *replicateLogLikelihoods);
 	// lnL and its first two derivatives in the central branch for every NNI neighbour of the tree model's tree at once (one
 	// phyamd_nni_log_likelihoods call; see include/physher_amd.h for the candidates and the three arrangements): logLikelihoods,
 	// d1, d2 [3][2T-1] by the tree's node ids, NaN at tips and the root; centralLengths [3][2T-1] trial lengths of the central

@@ -478,6 +478,47 @@ int phyamd_gradient_batch_weights(phyamd_engine *e, int flags, int32_t count, co
 typedef struct { int32_t items_fast, items_sequential, item_chunks, pattern_chunks, walks;
                  int64_t scratch_bytes; double ms; } phyamd_weight_batch_profile;
 int phyamd_get_weight_batch_profile(phyamd_engine *e, phyamd_weight_batch_profile *out);
+/* The per-pattern log-likelihoods of `count` trees on the engine's tip data, weights and models, their weighted sums, and RELL
+ * replicates of them: what model comparison consumes -- the site log-likelihoods behind CPO, WAIC and PSIS-LOO (logmcmc.c logs
+ * them per sample, cpo.c:17-75 reads them back), and pattern_lnl [trees][P] times weights [replicates][P]^T behind RELL bootstrap
+ * support and the KH / SH / AU topology tests (phyresampling.c:105-260 builds a SitePattern and a likelihood object per replicate).
+ * left, right [count][2T-1] and roots [count]: each item in phyamd_set_topology's convention (tips 0..T-1 are the engine's tips,
+ * internal ids T..2T-2 in any order, any internal node may be the root), or all three NULL: every item is the engine's tree;
+ * branch_lengths [count][2T-1] by the ITEM's node ids (root entry ignored).
+ *   pattern_lnl[b][k] ([count][P], or NULL) = log L_k of item b: the quantity phyamd_get_pattern_log_likelihoods returns after
+ *     phyamd_set_topology(item b), phyamd_set_branch_lengths(item b) and phyamd_log_likelihood;
+ *   lnl[b] = sum_k w_k pattern_lnl[b][k] with the engine's weights, over blocks of 64 patterns added in block order;
+ *   replicate_lnl[r][b] ([replicate_count][count]) = sum_k replicate_weights[r][k] pattern_lnl[b][k], replicate_weights
+ *     [replicate_count][P] any finite doubles >= 0: formed on the matrix pipe over segments of 4096 patterns that are added in
+ *     segment order.  replicate_count 0 with both pointers NULL: no replicates.
+ * One post-order pass per item that stores only the partials a later op still reads -- at most floor(log2 T) - 1 per pattern and
+ * category, none for a caterpillar (phyamd_post_order_slots) -- so far more items fit a chunk than in phyamd_gradient_batch_trees'
+ * lnL-only form; the [count][P] matrix is never resident: each chunk of items is walked, read back and multiplied with every chunk
+ * of replicates before the next.  No floating-point atomics.  The engine itself -- its topology, lengths, weights, partials -- is
+ * unchanged: later evaluations return the bits they would have returned without the call.  An item's lnl, its pattern_lnl row and
+ * its replicate_lnl column depend on its own arrays, the engine's inputs and (the column) the replicate rows only: not on `count`,
+ * its position, the chunks of items or of replicates, what the scratch held, or which optional outputs were asked for, bit for
+ * bit; two calls return identical bits.
+ * There is NO item-by-item fallback: PHYAMD_EUNSUPPORTED, naming the condition, under phyamd_gradient_batch_trees' conditions (not
+ * 4 states, more than 8 categories, an engine that is rescaling now, tiled patterns, a tip cell with an empty state mask, explicit
+ * node matrices, scratch for one item that does not fit the memory cap) and for flags other than 0.  An item whose lnL is not
+ * finite reports it in band -- its row as computed, its replicate_lnl column all NaN -- under PHYAMD_RESCALE_NEVER and _AUTO
+ * alike: the engine is never switched to rescaling.  PHYAMD_EINVAL, naming the function and the argument: a null engine,
+ * branch_lengths or lnl; count < 1; only some of left / right / roots null; replicate_count < 0; replicates without replicate_lnl
+ * or the reverse; a negative or non-finite replicate weight (with the replicate's index); an invalid item (validated on the host
+ * before anything is launched, with the item's index); an engine that is not ready (data, models, weights and a topology of its
+ * own).  The scratch lives in the batch scratch and is counted and released like it.  Sharded handles: every shard fills its own
+ * pattern columns of pattern_lnl and takes its own columns of replicate_weights; lnl and replicate_lnl are added in shard order. */
+int phyamd_pattern_log_likelihoods_trees(phyamd_engine *e, int flags, int32_t count, const int32_t *left, const int32_t *right,
+                                         const int32_t *roots, const double *branch_lengths, double *lnl /* [count] */,
+                                         double *pattern_lnl /* [count][P] or NULL */, int32_t replicate_count,
+                                         const double *replicate_weights /* [replicate_count][P] or NULL */,
+                                         double *replicate_lnl /* [replicate_count][count] or NULL */);
+/* of the last phyamd_pattern_log_likelihoods_trees: its items; the chunks of items it ran in and the chunks of replicates each of
+ * them was multiplied with; the most partials any item parked per pattern and category; bytes of batch scratch the engine holds
+ * (see phyamd_batch_profile); wall time of the call.  Sharded handles: the most of each count, scratch_bytes summed */
+typedef struct { int32_t items, chunks, replicate_chunks, lower_slots; int64_t scratch_bytes; double ms; } phyamd_site_lnl_profile;
+int phyamd_get_site_lnl_profile(phyamd_engine *e, phyamd_site_lnl_profile *out);
 int phyamd_synchronize(phyamd_engine *e);
 
 /* --- inspection (parity tests, debugging) --- */
@@ -518,6 +559,14 @@ int phyamd_post_order_parks(int32_t tip_count, const int32_t *left /* [2T-1] */,
 #define PHYAMD_PRE_ORDER_COLUMNS 30
 int phyamd_pre_order_schedule(int32_t tip_count, const int32_t *left /* [2T-1] */, const int32_t *right, int32_t root, int32_t form,
                               int32_t *out /* [capacity][PHYAMD_PRE_ORDER_COLUMNS] */, int32_t capacity, int32_t *hbm_slots);
+/* The post-order pass of a tree as phyamd_pattern_log_likelihoods_trees runs it, from the host schedule alone (no device, no
+ * engine): the internal nodes' ops in order, the larger subtree first and ties by left / right, six ints each: node | left | right |
+ * where the left child's partial comes from | the right child's (-1: a tip, -2: the op in front's registers, >= 0: a slot, free
+ * again once read) | where the result goes (-2: handed on in registers, >= 0: a slot, -1: the root's).  *slots (may be NULL): the
+ * slots the list uses, at most max(0, floor(log2 T) - 1).  Returns the number of ops (at most `capacity` of them are written) or a
+ * negative PHYAMD_E* code. */
+int phyamd_post_order_slots(int32_t tip_count, const int32_t *left /* [2T-1] */, const int32_t *right, int32_t root,
+                            int32_t *out /* [capacity][6] */, int32_t capacity, int32_t *slots);
 int phyamd_is_rescaling(phyamd_engine *e);
 /* SingleTreeLikelihood_use_rescaling (treelikelihood.c:1410-1423) after construction: PHYAMD_RESCALE_ALWAYS / _NEVER switch
  * at once (the next evaluation recomputes every node), PHYAMD_RESCALE_AUTO keeps the current state and re-arms the lazy switch. */

@@ -65,6 +65,13 @@ class WeightBatchProfile(C.Structure):
     ]
 
 
+class SiteLnlProfile(C.Structure):
+    _fields_ = [
+        ("items", C.c_int32), ("chunks", C.c_int32), ("replicate_chunks", C.c_int32), ("lower_slots", C.c_int32),
+        ("scratch_bytes", C.c_int64), ("ms", C.c_double),
+    ]
+
+
 # every symbol include/physher_amd.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -114,11 +121,14 @@ SYMBOLS = [
     ("phyamd_get_general_profile", C.c_int, [_P, C.POINTER(GeneralProfile)]),
     ("phyamd_gradient_batch_weights", C.c_int, [_P, C.c_int, C.c_int32, _P, _P, _P, _P]),
     ("phyamd_get_weight_batch_profile", C.c_int, [_P, C.POINTER(WeightBatchProfile)]),
+    ("phyamd_pattern_log_likelihoods_trees", C.c_int, [_P, C.c_int, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int32, _P, _P]),
+    ("phyamd_get_site_lnl_profile", C.c_int, [_P, C.POINTER(SiteLnlProfile)]),
     ("phyamd_synchronize", C.c_int, [_P]),
     ("phyamd_get_pattern_log_likelihoods", C.c_int, [_P, _P]),
     ("phyamd_get_partials", C.c_int, [_P, C.c_int, C.c_int, _P]),
     ("phyamd_get_node_matrices", C.c_int, [_P, C.c_int, C.c_int, _P]),
     ("phyamd_post_order_parks", C.c_int, [C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32]),
+    ("phyamd_post_order_slots", C.c_int, [C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, _P]),
     ("phyamd_pre_order_schedule", C.c_int, [C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
     ("phyamd_is_rescaling", C.c_int, [_P]),
     ("phyamd_set_rescaling", C.c_int, [_P, C.c_int]),

@@ -922,6 +922,18 @@ void TreeLikelihoodInterface::GradientTrees(size_t count, const int32_t *left, c
 	EvaluateTrees(count, left, right, roots, branchLengths, logLikelihoods, branchGradients);
 }
 
+void TreeLikelihoodInterface::PatternLogLikelihoodsTrees(size_t count, const int32_t *left, const int32_t *right, const int32_t *roots, const double *branchLengths,
+                                                         double *logLikelihoods, double *patternLogLikelihoods, size_t replicateCount, const double *replicateWeights,
+                                                         double *replicateLogLikelihoods) {
+	if (count == 0) return;
+	if (!left || !right || !roots || !branchLengths) throw Error("null left, right, roots or branchLengths");
+	if (!logLikelihoods) throw Error("null logLikelihoods");
+	if (count > (size_t)INT32_MAX || replicateCount > (size_t)INT32_MAX) throw Error("a batch takes at most 2^31 - 1 items and as many replicates");
+	Sync();
+	phyamd::check(phyamd_pattern_log_likelihoods_trees(impl_->engine, 0, (int32_t)count, left, right, roots, branchLengths, logLikelihoods, patternLogLikelihoods,
+	                                                   (int32_t)replicateCount, replicateWeights, replicateLogLikelihoods));
+}
+
 void TreeLikelihoodInterface::NNILogLikelihoods(const double *centralLengths, double *logLikelihoods, double *d1, double *d2) {
 	if (!logLikelihoods) throw Error("null logLikelihoods");
 	Sync();

@@ -241,6 +241,20 @@ PYBIND11_MODULE(_phycpp_amd, m) {
 		    self.GradientTrees(count, left.data(), right.data(), roots.data(), lengths.data(), lnl.data(), g.data());
 		    return py::make_tuple(vec(lnl), darray({(py::ssize_t)count, (py::ssize_t)N}, g.data()));
 	    })
+	    .def("pattern_log_likelihoods_trees", [](TreeLikelihoodInterface &self, iarray left, iarray right, iarray roots, darray lengths, std::optional<darray> weights,
+	                                             bool want_patterns) -> py::tuple {
+		    const size_t count = check_trees(self, left, right, roots, lengths);
+		    const py::ssize_t P = (py::ssize_t)self.GetPatternCount();
+		    if (weights && (weights->ndim() != 2 || weights->shape(0) < 1 || weights->shape(1) != P)) throw phyamd::Error("replicate weights: [replicates >= 1][patterns]");
+		    const size_t R = weights ? (size_t)weights->shape(0) : 0;
+		    std::vector<double> lnl(count), rows(want_patterns ? count * (size_t)P : 0), rep(R * count);
+		    self.PatternLogLikelihoodsTrees(count, left.data(), right.data(), roots.data(), lengths.data(), lnl.data(), want_patterns ? rows.data() : nullptr, R,
+		                                    weights ? weights->data() : nullptr, R ? rep.data() : nullptr);
+		    py::object rows_out = py::none(), rep_out = py::none();
+		    if (want_patterns) rows_out = darray({(py::ssize_t)count, P}, rows.data());
+		    if (R) rep_out = darray({(py::ssize_t)R, (py::ssize_t)count}, rep.data());
+		    return py::make_tuple(vec(lnl), rows_out, rep_out);
+	    }, py::arg("left"), py::arg("right"), py::arg("roots"), py::arg("branch_lengths"), py::arg("replicate_weights") = py::none(), py::arg("want_patterns") = true)
 	    .def("nni_log_likelihoods", [](TreeLikelihoodInterface &self, std::optional<darray> central, bool want_derivatives) -> py::tuple {
 		    const py::ssize_t N = (py::ssize_t)self.NodeCount();
 		    if (central && (central->ndim() != 2 || central->shape(0) != 3 || central->shape(1) != N)) throw phyamd::Error("central lengths: [3][node_count]");

@@ -525,6 +525,61 @@ int phyamd_get_weight_batch_profile(phyamd_engine *g, phyamd_weight_batch_profil
 	});
 }
 
+// every shard walks every item on its own patterns: it fills its pattern columns of pattern_lnl and takes its columns of
+// replicate_weights; lnl and replicate_lnl are sums over patterns, added in shard order
+int phyamd_pattern_log_likelihoods_trees(phyamd_engine *g, int flags, int32_t count, const int32_t *left, const int32_t *right, const int32_t *roots,
+                                         const double *branch_lengths, double *lnl, double *pattern_lnl, int32_t replicate_count, const double *replicate_weights,
+                                         double *replicate_lnl) {
+	static const char *const name = "phyamd_pattern_log_likelihoods_trees";
+	if (count < 1) return fail(PHYAMD_EINVAL, "%s: count must be >= 1 (got %d)", name, count);
+	if (!branch_lengths || !lnl) return fail(PHYAMD_EINVAL, "%s: null %s", name, !branch_lengths ? "branch_lengths" : "lnl");
+	if ((!left || !right || !roots) && (left || right || roots))
+		return fail(PHYAMD_EINVAL, "%s: null %s (left, right and roots are given together, or all three are null: the engine's tree)", name,
+		            !left ? "left" : !right ? "right" : "roots");
+	if (replicate_count < 0) return fail(PHYAMD_EINVAL, "%s: replicate_count must be >= 0 (got %d)", name, replicate_count);
+	if (replicate_count > 0 && (!replicate_weights || !replicate_lnl))
+		return fail(PHYAMD_EINVAL, "%s: null %s with replicate_count %d", name, !replicate_weights ? "replicate_weights" : "replicate_lnl", replicate_count);
+	if (replicate_count == 0 && (replicate_weights || replicate_lnl))
+		return fail(PHYAMD_EINVAL, "%s: %s given with replicate_count 0", name, replicate_weights ? "replicate_weights" : "replicate_lnl");
+	if (!g || g->shards.empty()) return fail(PHYAMD_EINVAL, "%s: null engine", name);
+	const size_t P = (size_t)g->P, R = (size_t)replicate_count;
+	for (size_t r = 0; r < R; r++)
+		for (size_t k = 0; k < P; k++) {
+			const double w = replicate_weights[r * P + k];
+			if (!(w >= 0.0) || std::isinf(w))
+				return fail(PHYAMD_EINVAL, "%s: replicate_weights of replicate %zu: pattern %zu has weight %g (a weight is finite and >= 0)", name, r, k, w);
+		}
+	if (group_size(g) == 1)
+		return shard_pattern_log_likelihoods_trees(g->shards[0], flags, count, left, right, roots, branch_lengths, lnl, pattern_lnl, P, replicate_count, replicate_weights, P,
+		                                           replicate_lnl);
+	const size_t n = (size_t)count * (1 + R);  // [lnl | replicate_lnl [R][count]]
+	std::vector<double> total(n);
+	int rc;
+	if ((rc = sum_over_shards(g, n, total.data(), [&](Shard *s, double *v) {
+		     const size_t i = (size_t)(std::find(g->shards.begin(), g->shards.end(), s) - g->shards.begin());
+		     return shard_pattern_log_likelihoods_trees(s, flags, count, left, right, roots, branch_lengths, v, pattern_lnl ? pattern_lnl + g->offset[i] : nullptr, P,
+		                                                replicate_count, R ? replicate_weights + g->offset[i] : nullptr, P, R ? v + count : nullptr);
+	     })))
+		return rc;
+	std::memcpy(lnl, total.data(), sizeof(double) * count);
+	if (R) std::memcpy(replicate_lnl, total.data() + count, sizeof(double) * R * count);
+	for (size_t b = 0; b < (size_t)count && R; b++)  // (what a shard masked in band is masked again by the summed lnL)
+		if (not_finite(lnl[b]))
+			for (size_t r = 0; r < R; r++) replicate_lnl[r * (size_t)count + b] = NAN;
+	return PHYAMD_OK;
+}
+
+int phyamd_get_site_lnl_profile(phyamd_engine *g, phyamd_site_lnl_profile *out) {
+	// the shards choose their chunks themselves: the most of each count; memory adds up
+	return merged_profile(g, &Shard::site_prof, out, [](phyamd_site_lnl_profile &o, const phyamd_site_lnl_profile &p) {
+		o.chunks = std::max(o.chunks, p.chunks);
+		o.replicate_chunks = std::max(o.replicate_chunks, p.replicate_chunks);
+		o.lower_slots = std::max(o.lower_slots, p.lower_slots);
+		o.scratch_bytes += p.scratch_bytes;
+		o.ms = std::max(o.ms, p.ms);
+	});
+}
+
 int phyamd_get_batch_profile(phyamd_engine *g, phyamd_batch_profile *out) {
 	// shards choose their paths themselves: the fewest fast items, the most of everything else
 	return merged_profile(g, &Shard::batch_prof, out, [](phyamd_batch_profile &o, const phyamd_batch_profile &p) {
@@ -739,6 +794,26 @@ int phyamd_post_order_parks(int32_t tip_count, const int32_t *left, const int32_
 		const int32_t rec[8] = {chunk, o.parent, o.left, o.right, source(0), source(1), ((o.lds_park & 4) ? 1 : 0) | ((o.lds_park & 0x40) ? 2 : 0),
 		                        (is_cut_root[o.left] ? 1 : 0) | (is_cut_root[o.right] ? 2 : 0)};
 		std::memcpy(out + (size_t)i * 8, rec, sizeof(rec));
+	}
+	return (int)ops.size();
+}
+
+// the post-order pass of a tree as k_sitelnl_walk4 runs it: host code only (no device, no engine)
+int phyamd_post_order_slots(int32_t tip_count, const int32_t *left, const int32_t *right, int32_t root, int32_t *out, int32_t capacity, int32_t *slots) {
+	static const char *const name = "phyamd_post_order_slots";
+	if (tip_count < 2) return fail(PHYAMD_EINVAL, "%s: tip_count must be >= 2 (got %d)", name, tip_count);
+	if (!left || !right) return fail(PHYAMD_EINVAL, "%s: null left or right", name);
+	if (capacity < 0 || (capacity > 0 && !out)) return fail(PHYAMD_EINVAL, "%s: null out with capacity %d", name, capacity);
+	std::vector<int> parents, stack;
+	int rc;
+	if ((rc = validate_batch_tree(tip_count, left, right, root, 0, parents, stack, name))) return rc;
+	std::vector<BatchOp> work, ops;
+	const int used = site_lnl_ops(tip_count, left, right, root, work, &ops);
+	if (slots) *slots = used;
+	for (int i = 0; i < (int)ops.size() && i < capacity; i++) {
+		const BatchOp &o = ops[i];
+		const int32_t rec[6] = {o.node, o.left, o.right, o.src, o.dst_left, o.dst_right};
+		std::memcpy(out + (size_t)i * 6, rec, sizeof(rec));
 	}
 	return (int)ops.size();
 }

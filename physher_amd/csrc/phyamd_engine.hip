@@ -132,6 +132,7 @@ struct NodeOp {
 #include "phyamd_post.inc"
 #include "phyamd_bhess.inc"
 #include "phyamd_reweight.inc"
+#include "phyamd_sitelnl.inc"
 
 #include "phyamd_shard.inc"
 

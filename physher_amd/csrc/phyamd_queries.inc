@@ -1,5 +1,5 @@
 // phyamd_queries.inc -- the whole-tree query calls on one shard: batches of branch-length vectors, of pattern weights and of trees, NNI and SPR scores,
-// per-pattern posteriors and the full branch Hessian.  They read what the engine holds and write only their own scratch
+// per-pattern posteriors, the full branch Hessian, and the per-pattern lnL of a batch of trees with its RELL replicates.  They read what the engine holds and write only their own scratch
 // (part of phyamd_engine.hip: one translation unit, internal linkage)
 
 // ---- what the calls share ------------------------------------------------------------------------------------------------------
@@ -543,20 +543,21 @@ int shard_gradient_batch_weights(Shard *e, int flags, int32_t count, const doubl
 
 // item `item` of a batch of trees is one binary tree over all 2T - 1 nodes in phyamd_set_topology's convention (build_schedule's
 // checks, on the item's arrays)
-int validate_batch_tree(int T, const int32_t *left, const int32_t *right, int root, int item, std::vector<int> &parents, std::vector<int> &stack) {
+int validate_batch_tree(int T, const int32_t *left, const int32_t *right, int root, int item, std::vector<int> &parents, std::vector<int> &stack,
+                        const char *name = "phyamd_gradient_batch_trees") {
 	const int N = 2 * T - 1;
 	parents.assign(N, 0);
 	for (int n = 0; n < N; n++) {
 		const int l = left[n], r = right[n];
 		if (n < T) {
-			if (l != -1 || r != -1) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch_trees: item %d: node %d is a tip (id < tip_count) but has children", item, n);
+			if (l != -1 || r != -1) return fail(PHYAMD_EINVAL, "%s: item %d: node %d is a tip (id < tip_count) but has children", name, item, n);
 			continue;
 		}
 		if (l < 0 || r < 0 || l >= N || r >= N || l == r)
-			return fail(PHYAMD_EINVAL, "phyamd_gradient_batch_trees: item %d: internal node %d has invalid children (%d, %d)", item, n, l, r);
-		if (++parents[l] > 1 || ++parents[r] > 1) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch_trees: item %d: node %d or %d has two parents", item, l, r);
+			return fail(PHYAMD_EINVAL, "%s: item %d: internal node %d has invalid children (%d, %d)", name, item, n, l, r);
+		if (++parents[l] > 1 || ++parents[r] > 1) return fail(PHYAMD_EINVAL, "%s: item %d: node %d or %d has two parents", name, item, l, r);
 	}
-	if (root < T || root >= N || parents[root] != 0) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch_trees: item %d: root %d is not a parentless internal node", item, root);
+	if (root < T || root >= N || parents[root] != 0) return fail(PHYAMD_EINVAL, "%s: item %d: root %d is not a parentless internal node", name, item, root);
 	// (no node has two parents and the root has none: the walk from the root meets no node twice)
 	int reached = 0;
 	stack.assign(1, root);
@@ -569,7 +570,7 @@ int validate_batch_tree(int T, const int32_t *left, const int32_t *right, int ro
 			stack.push_back(right[n]);
 		}
 	}
-	if (reached != N) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch_trees: item %d: the topology is not a single binary tree over all %d nodes", item, N);
+	if (reached != N) return fail(PHYAMD_EINVAL, "%s: item %d: the topology is not a single binary tree over all %d nodes", name, item, N);
 	return PHYAMD_OK;
 }
 
@@ -1193,5 +1194,187 @@ int shard_branch_hessian(Shard *e, int flags, double *lnl, double *gradient, dou
 		const int rc = run_branch_hessian(e, lnl, gradient, hessian, prof);
 		if (!rc) mask_if_not_finite(*lnl, gradient, (size_t)e->N), mask_if_not_finite(*lnl, hessian, (size_t)e->N * e->N);
 		return rc;
+	});
+}
+
+// ---- per-pattern lnL of a batch of trees, and RELL replicates of them (phyamd_pattern_log_likelihoods_trees) --------------------
+
+// The post-order list of build_batch_ops for a tree (already validated) with the slot words k_sitelnl_walk4 reads
+// (phyamd_sitelnl.inc), appended to `ops` (null: only counted); returns the slots the list parks in.  A result whose parent is the
+// next op is handed on in registers; any other waits in a slot, which is free again once the parent has read it -- before the
+// parent's own result looks for one.  The list takes the larger subtree first, so the result that waits while a sibling subtree is
+// walked belongs to a subtree at least as large: at most floor(log2 T) - 1 wait at once, and a caterpillar parks none.
+// work: the builder's list, reused from call to call
+int site_lnl_ops(int T, const int32_t *left, const int32_t *right, int root, std::vector<BatchOp> &work, std::vector<BatchOp> *ops) {
+	work.clear();
+	build_batch_ops(T, left, right, root, &work);
+	const int nops = T - 1;
+	std::vector<int> slot_of(2 * T - 1, BATCH_NONE), free_slots;
+	int slots = 0;
+	for (int i = 0; i < nops; i++) {
+		BatchOp op = work[i];
+		const auto source = [&](int child, int side) {
+			if (child < T) return (int)BATCH_NONE;
+			if (op.carry == side) return (int)BATCH_CARRY;
+			const int s = slot_of[child];
+			free_slots.push_back(s);
+			return s;
+		};
+		op.src = source(op.left, 1);
+		op.dst_left = source(op.right, 2);
+		if (i + 1 == nops) op.dst_right = BATCH_NONE;  // the root's
+		else if (work[i + 1].carry != 0) op.dst_right = BATCH_CARRY;
+		else {
+			if (free_slots.empty()) slot_of[op.node] = slots++;
+			else {
+				slot_of[op.node] = free_slots.back();
+				free_slots.pop_back();
+			}
+			op.dst_right = slot_of[op.node];
+		}
+		if (ops) ops->push_back(op);
+	}
+	return slots;
+}
+
+constexpr size_t SITE_LNL_MAX_REPLICATES = (size_t)1 << 19;  // replicates per chunk: gridDim.y of k_reweight_mfma is a sixteenth
+
+// What the call needs of the batch scratch per item for replicate chunks of `reps` rows: an item's lengths, matrices, op list and
+// root, its `slots` parked partials (in d_batch_lower, where the batched walk keeps all T - 1), its row of log L_k (the product's R),
+// its per-block sums and its lnL; and with replicates the product's segment sums and results per (replicate, item).  Whatever the
+// item count: the replicate chunk's weight rows
+ScratchPlan sitelnl_plan(Shard *e, int slots, size_t reps) {
+	const size_t D = sizeof(double), N = (size_t)e->N, C = (size_t)e->C, nblk = ((size_t)e->P + WAVE - 1) / WAVE, Pc = nblk * WAVE;
+	const size_t segments = (Pc + REWEIGHT_SEGMENT - 1) / REWEIGHT_SEGMENT;
+	ScratchPlan p;
+	p.add(e->d_batch_len, D * N);
+	p.add(e->d_batch_mats, D * N * C * 16);
+	p.add(e->d_batch_out, D);
+	p.add(e->d_batch_lower, D * (size_t)slots * C * Pc * 4);
+	p.add(e->d_batch_lnl, D * nblk);
+	p.add(e->d_batch_item_ops, sizeof(BatchOp) * (size_t)(e->T - 1));
+	p.add(e->d_batch_roots, sizeof(int32_t));
+	p.add(e->d_reweight_R, D * Pc);
+	if (reps > 0) {
+		p.add(e->d_reweight_w, 0, D * reps * Pc);
+		p.add(e->d_reweight_part, D * segments * reps);
+		p.add(e->d_sitelnl_rell, D * reps);
+	}
+	return p;
+}
+
+// the items in chunks of what the scratch holds; per chunk: the op lists, roots and lengths go up, matrices, walk and finish are
+// launched, the rows come back if they are wanted, and every replicate chunk is multiplied with the rows while they are resident
+int run_site_lnl(Shard *e, int flags, int32_t count, const int32_t *left, const int32_t *right, const int32_t *roots, const double *branch_lengths, double *lnl,
+                 double *pattern_lnl, size_t pattern_stride, int32_t replicate_count, const double *replicate_weights, size_t weight_stride, double *replicate_lnl,
+                 phyamd_site_lnl_profile &prof) {
+	static const char *const name = "phyamd_pattern_log_likelihoods_trees";
+	int rc;
+	if ((rc = check_ready_but_lengths(e))) return fail(rc, "%s: the engine is not ready: %s", name, std::string(g_last_error).c_str());
+	if (flags != 0) return fail(PHYAMD_EUNSUPPORTED, "%s: flags %d (no flags are defined: pass 0)", name, flags);
+	if (const char *why = tree_batch_refusal(e, 0, 1)) return fail(PHYAMD_EUNSUPPORTED, "%s: %s", name, why);
+	const int T = e->T, P = e->P, C = e->C, nops = T - 1;
+	const size_t N = (size_t)e->N, nblk = ((size_t)P + WAVE - 1) / WAVE, Pc = nblk * WAVE, R = (size_t)replicate_count;
+	const int segments = (int)((Pc + REWEIGHT_SEGMENT - 1) / REWEIGHT_SEGMENT);
+	std::vector<int32_t> own_left, own_right, own_roots;
+	if (!left) {  // every item is the engine's tree
+		for (int32_t b = 0; b < count; b++) {
+			own_left.insert(own_left.end(), e->left.begin(), e->left.end());
+			own_right.insert(own_right.end(), e->right.begin(), e->right.end());
+		}
+		own_roots.assign(count, e->root);
+		left = own_left.data(), right = own_right.data(), roots = own_roots.data();
+	}
+	std::vector<BatchOp> work, ops;
+	std::vector<int> slots(count);  // per item: the slots its list parks in
+	{
+		std::vector<int> parents, stack;
+		for (int32_t b = 0; b < count; b++) {  // every item, before anything is launched
+			const int32_t *l = left + (size_t)b * N, *r = right + (size_t)b * N;
+			if ((rc = validate_batch_tree(T, l, r, roots[b], b, parents, stack, name))) return rc;
+			slots[b] = site_lnl_ops(T, l, r, roots[b], work, nullptr);
+			prof.lower_slots = std::max(prof.lower_slots, (int32_t)slots[b]);
+		}
+	}
+	// the replicate chunk: all of them if their weight rows take at most a quarter of the room, else as many as do (at least one)
+	size_t reps = 0;
+	if (R > 0) {
+		const double room = scratch_room(e, (double)batch_scratch_bytes(e), EngineRoom::MayGrow);
+		reps = (size_t)std::min((double)std::min(R, SITE_LNL_MAX_REPLICATES), std::max(1.0, std::floor(room / 4 / (double)(sizeof(double) * Pc))));
+	}
+	std::vector<double> lengths, out, rows, rell;
+	for (size_t first = 0; first < (size_t)count;) {
+		// the chunk and its slot count settle each other: fewer items never need more slots
+		size_t items = std::min<size_t>((size_t)count - first, BATCH_MAX_CHUNK);
+		int chunk_slots = 0;
+		ScratchPlan plan;
+		for (;;) {
+			chunk_slots = *std::max_element(slots.begin() + first, slots.begin() + first + items);
+			plan = sitelnl_plan(e, chunk_slots, reps);
+			const size_t fit = batch_items_that_fit(e, items, plan);
+			if (const char *why = tree_batch_refusal(e, 0, fit)) return fail(PHYAMD_EUNSUPPORTED, "%s: %s", name, why);
+			if (fit >= items) break;
+			items = fit;
+		}
+		if ((rc = ensure_batch_scratch(e, items, plan))) return rc;
+		ops.clear();
+		for (size_t b = first; b < first + items; b++) site_lnl_ops(T, left + b * N, right + b * N, roots[b], work, &ops);
+		lengths.assign(branch_lengths + first * N, branch_lengths + (first + items) * N);
+		for (size_t b = 0; b < items; b++) lengths[b * N + roots[first + b]] = 0.0;  // (ignored, as phyamd_set_branch_lengths does)
+		HIP_TRY(hipMemcpyAsync(e->d_batch_item_ops, ops.data(), sizeof(BatchOp) * items * nops, hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_batch_roots, roots + first, sizeof(int32_t) * items, hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_batch_len, lengths.data(), sizeof(double) * items * N, hipMemcpyHostToDevice, e->stream));
+		launch_batch_matrices(e, (int)items, e->d_batch_len, e->d_batch_roots, e->d_batch_mats);
+		const SiteLnlArgs a{e->d_batch_item_ops, T, e->N, P, C, (int)nblk, chunk_slots, e->d_tipmask, e->d_freqs, e->d_props, e->d_weights, e->d_batch_mats,
+		                    e->d_batch_lower, e->d_reweight_R, e->d_batch_lnl};
+		hipLaunchKernelGGL(k_sitelnl_walk4, dim3((unsigned)nblk, (unsigned)items), dim3(WAVE, C), 0, e->stream, a);
+		hipLaunchKernelGGL(k_batch_finish, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, e->stream, (int)items, e->N, C, (int)nblk, e->root, e->d_batch_roots.get(), 1,
+		                   e->d_batch_lnl.get(), (const double *)nullptr, e->d_batch_out.get());
+		HIP_TRY(hipGetLastError());
+		out.resize(items);
+		HIP_TRY(hipMemcpyAsync(out.data(), e->d_batch_out, sizeof(double) * items, hipMemcpyDeviceToHost, e->stream));
+		if (pattern_lnl) {
+			rows.resize(items * Pc);
+			HIP_TRY(hipMemcpyAsync(rows.data(), e->d_reweight_R, sizeof(double) * items * Pc, hipMemcpyDeviceToHost, e->stream));
+		}
+		HIP_TRY(hipStreamSynchronize(e->stream));  // (also covers ops and lengths, reused by the next chunk)
+		std::copy(out.begin(), out.end(), lnl + first);
+		for (size_t b = 0; b < items && pattern_lnl; b++) std::copy(rows.begin() + b * Pc, rows.begin() + b * Pc + P, pattern_lnl + (first + b) * pattern_stride);
+		prof.chunks++;
+		for (size_t r0 = 0; r0 < R; r0 += reps) {
+			const size_t nr = std::min(reps, R - r0);
+			if ((size_t)P < Pc) HIP_TRY(hipMemsetAsync(e->d_reweight_w, 0, sizeof(double) * nr * Pc, e->stream));  // (a garbage NaN times a row's 0 is a NaN)
+			if ((rc = upload_rows(e, e->d_reweight_w, Pc, replicate_weights + r0 * weight_stride, weight_stride, (size_t)P, nr))) return rc;
+			const ReweightArgs w{e->d_reweight_w, e->d_reweight_R, e->d_reweight_part, nullptr, (int)nr, (int)items, (int)Pc, segments, e->N, C};
+			hipLaunchKernelGGL(k_reweight_mfma, dim3((unsigned)((items + 15) / 16), (unsigned)((nr + 15) / 16), (unsigned)segments), dim3(WAVE), 0, e->stream, w);
+			hipLaunchKernelGGL(k_sitelnl_rell_finish, dim3((unsigned)((nr * items + 255) / 256)), dim3(256), 0, e->stream, (int)nr, (int)items, segments, e->d_reweight_part.get(),
+			                   e->d_sitelnl_rell.get());
+			HIP_TRY(hipGetLastError());
+			rell.resize(nr * items);
+			HIP_TRY(hipMemcpyAsync(rell.data(), e->d_sitelnl_rell, sizeof(double) * nr * items, hipMemcpyDeviceToHost, e->stream));
+			HIP_TRY(hipStreamSynchronize(e->stream));
+			for (size_t r = 0; r < nr; r++) std::copy(rell.begin() + r * items, rell.begin() + (r + 1) * items, replicate_lnl + (r0 + r) * (size_t)count + first);
+			if (first == 0) prof.replicate_chunks++;
+		}
+		first += items;
+	}
+	// a lnL that is not finite is in band whatever the rescaling mode (the engine is never switched): its replicates are all NaN
+	for (size_t b = 0; b < (size_t)count && R > 0; b++)
+		if (not_finite(lnl[b]))
+			for (size_t r = 0; r < R; r++) replicate_lnl[r * (size_t)count + b] = NAN;
+	return PHYAMD_OK;
+}
+
+// reads the engine's inputs and writes only the batch scratch: nothing in Shard::state changes.  pattern_lnl: rows pattern_stride
+// apart, replicate_weights: rows weight_stride apart, this shard's P patterns of either (the group layer passes the handle's
+// pattern count and pointers advanced to this shard's range)
+int shard_pattern_log_likelihoods_trees(Shard *e, int flags, int32_t count, const int32_t *left, const int32_t *right, const int32_t *roots, const double *branch_lengths,
+                                        double *lnl, double *pattern_lnl, size_t pattern_stride, int32_t replicate_count, const double *replicate_weights,
+                                        size_t weight_stride, double *replicate_lnl) {
+	phyamd_site_lnl_profile known{};
+	known.items = count;
+	return profiled_call(e, &Shard::site_prof, known, [&](phyamd_site_lnl_profile &prof) {
+		return run_site_lnl(e, flags, count, left, right, roots, branch_lengths, lnl, pattern_lnl, pattern_stride, replicate_count, replicate_weights, weight_stride,
+		                    replicate_lnl, prof);
 	});
 }

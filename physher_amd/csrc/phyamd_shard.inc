@@ -299,6 +299,12 @@ struct Shard {
 	std::vector<double> weights_host;
 	uint64_t weights_epoch = 0;
 	phyamd_weight_batch_profile weight_prof{};
+	// phyamd_pattern_log_likelihoods_trees (phyamd_sitelnl.inc) runs in the batch scratch's arrays: an item's lengths, matrices, op
+	// list, root, per-block sums and lnL where a batch of trees has them, its few parked partials in d_batch_lower, its row of log L_k
+	// in d_reweight_R, a replicate chunk's weight rows and segment sums in d_reweight_w and d_reweight_part; and adds the replicates'
+	// results [replicates][items] of a chunk
+	DeviceArray<double> d_sitelnl_rell{&batch_mem};
+	phyamd_site_lnl_profile site_prof{};
 };
 
 // ---- what each input invalidates -------------------------------------------------------------------------------------------

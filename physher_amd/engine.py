@@ -369,6 +369,48 @@ class Engine:
         self._check(self._lib.phyamd_get_weight_batch_profile(self._h, C.byref(p)))
         return {k: getattr(p, k) for k, _ in p._fields_}
 
+    def pattern_log_likelihoods_trees(self, left, right, roots, branch_lengths, replicate_weights=None, want_patterns=True, flags=0):
+        """The per-pattern log-likelihoods of B trees on this engine's data and models at once, and RELL replicates of them:
+        (lnl [B], pattern_lnl [B, P] or None, replicate_lnl [R, B] or None).  left, right [B, N], roots [B] and branch_lengths
+        [B, N] as gradient_batch_trees takes them; left = right = roots = None: every item is this engine's tree.  Row b is what
+        pattern_log_likelihoods() returns after set_topology + set_branch_lengths + log_likelihood on item b, lnl[b] its sum under
+        the engine's weights, replicate_lnl[r, b] its sum under replicate_weights[r] ([R, P], finite and >= 0:
+        physher_amd.resampling).  An item whose lnL is not finite has an all-NaN replicate column.  This engine's own tree, lengths,
+        weights and partials stay.  No item-by-item fallback: EngineError where gradient_batch_trees refuses."""
+        bl = _f64(branch_lengths)
+        if bl.ndim != 2 or bl.shape[1] != self.N or bl.shape[0] < 1:
+            raise ValueError(f"branch_lengths must be [B >= 1, {self.N}] (got {bl.shape})")
+        count = bl.shape[0]
+        given = [x is not None for x in (left, right, roots)]
+        l = r = ro = None
+        if all(given):
+            l = np.ascontiguousarray(left, dtype=np.int32)
+            r = np.ascontiguousarray(right, dtype=np.int32)
+            ro = np.ascontiguousarray(roots, dtype=np.int32)
+            if l.shape != bl.shape or r.shape != bl.shape or ro.shape != (count,):
+                raise ValueError(f"left, right: {bl.shape} and roots: ({count},), got {l.shape}, {r.shape}, {ro.shape}")
+        elif any(given):
+            raise ValueError("left, right and roots are given together, or all three are None (the engine's tree)")
+        w = None
+        if replicate_weights is not None:
+            w = _f64(replicate_weights)
+            if w.ndim != 2 or w.shape[1] != self.P or w.shape[0] < 1:
+                raise ValueError(f"replicate_weights must be [R >= 1, {self.P}] (got {w.shape})")
+        lnl = np.empty(count)
+        rows = np.empty((count, self.P)) if want_patterns else None
+        rep = np.empty((w.shape[0], count)) if w is not None else None
+        opt = lambda a: None if a is None else _ptr(a)
+        self._check(self._lib.phyamd_pattern_log_likelihoods_trees(self._h, flags, count, opt(l), opt(r), opt(ro), _ptr(bl), _ptr(lnl), opt(rows),
+                                                                   0 if w is None else w.shape[0], opt(w), opt(rep)))
+        return lnl, rows, rep
+
+    def site_lnl_profile(self):
+        """Of the last pattern_log_likelihoods_trees: items, chunks (of items), replicate_chunks (per chunk of items), lower_slots (the
+        most partials an item parked per pattern and category), scratch_bytes, ms."""
+        p = _lib.SiteLnlProfile()
+        self._check(self._lib.phyamd_get_site_lnl_profile(self._h, C.byref(p)))
+        return {k: getattr(p, k) for k, _ in p._fields_}
+
     def store(self):
         """Remember the current (evaluated) state: parameters, lnL and partials (MCMC store)."""
         self._check(self._lib.phyamd_store(self._h))
