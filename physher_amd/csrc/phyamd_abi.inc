@@ -766,21 +766,14 @@ int phyamd_post_order_parks(int32_t tip_count, const int32_t *left, const int32_
 	if (tip_count < 2) return fail(PHYAMD_EINVAL, "tip_count must be >= 2 (got %d)", tip_count);
 	if (!left || !right) return fail(PHYAMD_EINVAL, "null left or right");
 	if (capacity < 0 || (capacity > 0 && !out)) return fail(PHYAMD_EINVAL, "null out with capacity %d", capacity);
-	std::unique_ptr<Shard> e(new Shard());
-	e->T = tip_count;
-	e->N = 2 * e->T - 1;
-	e->S = 4;
-	e->C = 1;
-	e->P = e->Ptot = 1;
-	e->root = root;
-	e->left.assign(left, left + e->N);
-	e->right.assign(right, right + e->N);
-	e->lower_park2_on = second_slot != 0;
-	int rc;
-	if ((rc = build_schedule(e.get()))) return rc;
-	const std::vector<NodeOp> &ops = e->walk_lower_chunk_ops;
-	const std::vector<int> &off = e->walk_lower_chunk_off;
-	std::vector<char> is_cut_root(e->N, 0);  // the roots of the cut subtrees: every chunk's last op but the top part's
+	ScheduleOptions options;  // 4 states, an engine's defaults
+	options.lower_park2_on = second_slot != 0;
+	Schedule sched;
+	const std::string err = build_schedule(TreeRef{tip_count, left, right, root}, options, &sched);
+	if (!err.empty()) return fail(PHYAMD_EINVAL, "%s", err.c_str());
+	const std::vector<NodeOp> &ops = sched.walk_lower_chunk_ops;
+	const std::vector<int> &off = sched.walk_lower_chunk_off;
+	std::vector<char> is_cut_root(2 * tip_count - 1, 0);  // the roots of the cut subtrees: every chunk's last op but the top part's
 	for (size_t k = 1; k + 1 < off.size(); k++)
 		if (off[k] > off[k - 1]) is_cut_root[ops[off[k] - 1].parent] = 1;
 	int chunk = 0;
@@ -804,9 +797,9 @@ int phyamd_post_order_slots(int32_t tip_count, const int32_t *left, const int32_
 	if (tip_count < 2) return fail(PHYAMD_EINVAL, "%s: tip_count must be >= 2 (got %d)", name, tip_count);
 	if (!left || !right) return fail(PHYAMD_EINVAL, "%s: null left or right", name);
 	if (capacity < 0 || (capacity > 0 && !out)) return fail(PHYAMD_EINVAL, "%s: null out with capacity %d", name, capacity);
-	std::vector<int> parents, stack;
-	int rc;
-	if ((rc = validate_batch_tree(tip_count, left, right, root, 0, parents, stack, name))) return rc;
+	std::vector<int32_t> parents;
+	const std::string err = validate_tree(TreeRef{tip_count, left, right, root}, parents, name, 0);
+	if (!err.empty()) return fail(PHYAMD_EINVAL, "%s", err.c_str());
 	std::vector<BatchOp> work, ops;
 	const int used = site_lnl_ops(tip_count, left, right, root, work, &ops);
 	if (slots) *slots = used;
@@ -827,32 +820,24 @@ int phyamd_pre_order_schedule(int32_t tip_count, const int32_t *left, const int3
 	if (!left || !right) return fail(PHYAMD_EINVAL, "null left or right");
 	if (form < 0 || form > 2) return fail(PHYAMD_EINVAL, "form must be 0 (chunked list), 1 (streamed walk) or 2 (one list), got %d", form);
 	if (capacity < 0 || (capacity > 0 && !out)) return fail(PHYAMD_EINVAL, "null out with capacity %d", capacity);
-	std::unique_ptr<Shard> e(new Shard());
-	e->T = tip_count;
-	e->N = 2 * e->T - 1;
-	e->S = 4;
-	e->C = 1;
-	e->P = e->Ptot = 1;
-	e->G = 1;
-	e->nblk_walk_upper = 1;
-	e->root = root;
-	e->left.assign(left, left + e->N);
-	e->right.assign(right, right + e->N);
-	int rc;
-	if ((rc = build_schedule(e.get()))) return rc;
-	if (form == 1) build_stream_ops(e.get());
-	const std::vector<NodeOp> &ops = form == 2 ? e->walk_upper_ops : e->walk_chunk_ops;
+	const int N = 2 * tip_count - 1;
+	Schedule sched;  // 4 states, an engine's defaults; the streamed walk's tables for one pattern of one category
+	StreamTables stream_tab;
+	const std::string err = build_schedule(TreeRef{tip_count, left, right, root}, ScheduleOptions{}, &sched);
+	if (!err.empty()) return fail(PHYAMD_EINVAL, "%s", err.c_str());
+	if (form == 1) build_stream_tables(sched, StreamGeometry{1, 1, WAVE}, &stream_tab);
+	const std::vector<NodeOp> &ops = form == 2 ? sched.walk_upper_ops : sched.walk_chunk_ops;
 	const std::vector<int> one_chunk{0, (int)ops.size()};
-	const std::vector<int> &off = form == 2 ? one_chunk : e->walk_chunk_off;
+	const std::vector<int> &off = form == 2 ? one_chunk : sched.walk_chunk_off;
 	if (hbm_slots) {
-		*hbm_slots = e->walk_chunk_slots;
+		*hbm_slots = sched.walk_chunk_slots;
 		if (form == 2) {  // (walk_upper_slots has become the larger of the two lists' counts: the one list's own is its highest index + 1)
 			int most = -1;
 			for (const NodeOp &o : ops) most = std::max({most, o.upper_slot_parent, o.upper_slot_left, o.upper_slot_right});
 			*hbm_slots = most + 1;
 		}
 	}
-	std::vector<char> has_op(e->N, 0), is_cut_root(e->N, 0);  // the roots of the cut subtrees: every chunk's first op but the top part's
+	std::vector<char> has_op(N, 0), is_cut_root(N, 0);  // the roots of the cut subtrees: every chunk's first op but the top part's
 	for (const NodeOp &o : ops) has_op[o.parent] = 1;
 	for (size_t k = 1; k + 1 < off.size(); k++)
 		if (off[k + 1] > off[k]) is_cut_root[ops[off[k]].parent] = 1;
@@ -866,8 +851,8 @@ int phyamd_pre_order_schedule(int32_t tip_count, const int32_t *left, const int3
 		int32_t *q = rec + 20;
 		int nq = 0;
 		if (form == 1) {  // what k_upper4_stream reads: the descriptor's flags and slots
-			const StreamOp &s = e->stream_ops[i];
-			const int fl = e->stream_desc[i].flags, kl = fl & 7, kr = (fl >> 3) & 7, usrc = (fl >> 9) & 7, pk = (fl >> 12) & 3;
+			const StreamOp &s = stream_tab.ops[i];
+			const int fl = stream_tab.desc[i].flags, kl = fl & 7, kr = (fl >> 3) & 7, usrc = (fl >> 9) & 7, pk = (fl >> 12) & 3;
 			rec[1] = s.parent;
 			rec[2] = s.lnode;
 			rec[3] = s.rnode;
@@ -888,10 +873,10 @@ int phyamd_pre_order_schedule(int32_t tip_count, const int32_t *left, const int3
 				rec[13 + 2 * side] = stored ? slot : -1;
 			}
 			rec[16] = (fl & (1 << 28)) ? s.nx_u : -1;
-			rec[18] = rec[12] == S_CARRY ? 1 : 0;  // (after build_stream_ops' swap the carried child, if any, is the left one)
+			rec[18] = rec[12] == S_CARRY ? 1 : 0;  // (after stream_pre_order's swap the carried child, if any, is the left one)
 			for (int j = 0; j < 10; j++) {
-				const int at = e->stream_site_tab[(size_t)i * 16 + j];
-				if (at >= 0) q[nq++] = e->stream_qnode[at / 8];
+				const int at = stream_tab.site_tab[(size_t)i * 16 + j];
+				if (at >= 0) q[nq++] = stream_tab.qnode[at / 8];
 			}
 		} else {  // what k_upper4_walk reads: the NodeOp itself (form 2: its PARAMS form, which has no LDS slot)
 			const NodeOp &o = ops[i];
@@ -901,8 +886,8 @@ int phyamd_pre_order_schedule(int32_t tip_count, const int32_t *left, const int3
 			rec[3] = o.right;
 			rec[4] = o.kind_left;
 			rec[5] = o.kind_right;
-			if (o.kind_left == CH_DEEP) rec[6] = e->deep_host[o.left].kind_left, rec[7] = e->deep_host[o.left].kind_right;
-			if (o.kind_right == CH_DEEP) rec[8] = e->deep_host[o.right].kind_left, rec[9] = e->deep_host[o.right].kind_right;
+			if (o.kind_left == CH_DEEP) rec[6] = sched.deep_host[o.left].kind_left, rec[7] = sched.deep_host[o.left].kind_right;
+			if (o.kind_right == CH_DEEP) rec[8] = sched.deep_host[o.right].kind_left, rec[9] = sched.deep_host[o.right].kind_right;
 			const bool proot = o.upper_slot_parent < 0 && !o.carry_in && !(o.lds_park & 1);
 			rec[10] = proot ? S_ROOT : o.carry_in ? S_CARRY : (lpark && (o.lds_park & 1)) ? S_LDS0 : S_HBM;
 			rec[11] = rec[10] == S_HBM ? o.upper_slot_parent : -1;

@@ -15,18 +15,7 @@
 // phyamd_gradient_batch_weights gives every item a weight row of its own (BatchArgs::weight_stride) and, where the items share the
 // engine's lengths, runs the walk once in its terms form (batch_walk4<FOLD, true>, phyamd_reweight.inc).
 
-// post-order: node = (P_left p_left) o (P_right p_right); carry 1 / 2: the left / right child's partial is the previous op's result
-// pre-order: the op of `node` forms its children's uppers.  src: where u_node is (BATCH_ROOT: node is the root; BATCH_CARRY: the
-// previous op handed it on in registers; >= 0: upper slot); dst_left / dst_right: where a child's upper goes (BATCH_NONE: a tip's
-// is not kept)
-struct BatchOp {
-	int32_t node, left, right;
-	int32_t carry;
-	int32_t src, dst_left, dst_right;
-	int32_t pad;
-};
-enum { BATCH_NONE = -1, BATCH_CARRY = -2, BATCH_ROOT = -3, BATCH_GHOST = -4 };  // BATCH_GHOST: a pruned child (phyamd_spr4.inc), whose message is all ones
-
+// (BatchOp and BATCH_*: phyamd_types.h)
 constexpr int BATCH_MAX_CATEGORIES = 8;  // one LDS row of site-likelihood terms per category; at most 8 category waves per workgroup
 
 // op i of a list, through the constant address space like the matrices: the lists are read-only kernel inputs at wave-uniform

@@ -1,10 +1,12 @@
 // phyamd_engine.hip -- MI355X (gfx950) tree-likelihood engine behind include/physher_amd.h.
 //
 // One translation unit, assembled from:
+//   phyamd_types.h          plain data the host builds and the kernels read: op lists, descriptors, their enums and constants
+//   phyamd_tree_schedule.h  the tree check and every host-built list as a value built by a pure function (standard C++, no engine)
 //   phyamd_memory.inc       owning device arrays and the memory budget they are allocated through
 //   phyamd_device.inc / _level4 / _walk4 / _walk4s / _general / _genwalk / _patterns / _batch4 / _nni4 / _spr4 / _post / _bhess / _reweight   device code (kernels)
 //   phyamd_shard.inc        state of one engine on one GPU (= one shard of the site patterns), the form of its stored lowers
-//   phyamd_schedule.inc     level and tree-walk schedules, device storage
+//   phyamd_schedule.inc     the engine's schedule on the device: storage, upload, readiness
 //   phyamd_launch.inc       kernel launches per pass
 //   phyamd_eval.inc         one evaluation (incremental updates, lazy rescaling, gradients, pattern tiling)
 //   phyamd_shard_api.inc    per-device half of the C ABI: creation, setters, evaluations, single-branch calls, inspection
@@ -42,11 +44,14 @@
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
+#include <cstddef>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "physher_amd.h"
@@ -54,6 +59,11 @@
 #define PHYAMD_ABI_VERSION 5
 
 namespace {
+
+// (inside the namespace like the .inc files: the types keep internal linkage and every kernel its symbol; the standard headers the
+// two include are included above)
+#include "phyamd_types.h"
+#include "phyamd_tree_schedule.h"
 
 thread_local std::string g_last_error;
 
@@ -75,7 +85,6 @@ int fail(int code, const char *fmt, ...) {
 			            hipGetErrorString(err__), __FILE__, __LINE__);                                      \
 	} while (0)
 
-constexpr int WAVE = 64;             // lanes per wavefront (gfx950)
 // tuning constants (A/B measured on MI355X at 1000 taxa x 1e6 patterns): pattern groups swept
 // sequentially by one workgroup, and the occupancy the pre-order kernel is compiled for
 constexpr int PPT_LOWER = 2, PPT_UPPER = 8;
@@ -83,39 +92,6 @@ constexpr int UPPER_MIN_WAVES = 6;
 // patterns per thread of the tree-walk kernels are chosen per engine from the shard size (phyamd_create)
 constexpr int MAX_WAVES = 16;        // 1024 threads
 constexpr double SCALING_THRESHOLD = 1.0e-40;  // treelikelihood.c:1121
-
-// how a child's lower partial is obtained: read (CORE), or recomputed in registers from tips (CHERRY, CHERRY_TIP: "fringe",
-// which also has its inner branch gradients computed inside its parent's pre-order op) or from two fringe / tip children
-// (DEEP: no stored lower either, but a pre-order op of its own)
-enum { CH_TIP = 0, CH_CORE = 1, CH_DEEP = 2, CH_CHERRY = 3, CH_CHERRY_TIP = 4 };
-
-// children of a DEEP node, by node id: what child_message needs to rebuild its partial
-struct DeepDesc {
-	int32_t kind_left, left, lt0, lt1, lt2, linner;
-	int32_t kind_right, right, rt0, rt1, rt2, rinner;
-};
-
-struct NodeOp {
-	int32_t parent;  // lower pass: destination node; upper pass: the node whose children are produced
-	int32_t left, right;
-	int32_t upper_slot_parent;  // upper pass: slot of the parent's upper (-1: parent is the root)
-	int32_t upper_slot_left, upper_slot_right;  // slots to write (-1: nothing stored)
-	int32_t core_parent, core_left, core_right;  // index of the stored lower array (-1: tip or fused fringe node)
-	int32_t kind_left, kind_right;               // CH_*
-	int32_t lt0, lt1, lt2, linner;               // left fringe: cherry tips, outer tip, inner cherry node
-	int32_t rt0, rt1, rt2, rinner;               // right fringe
-	// tree-walk kernels only (ops in depth-first order, values handed from one op to the next in registers):
-	int32_t carry_in;   // lower walk: 1 / 2 = the left / right child's partial is the previous op's result;
-	                    // upper walk: 1 = the parent's upper is the previous op's carried child upper
-	int32_t carry_out;  // upper walk: 1 / 2 = the left / right child's upper goes to the next op in registers (not stored)
-	// upper walk, plain kernel: a parked upper whose waiting time holds no other park ("leaf park": two thirds of them in a random
-	// tree) can wait in the wave's LDS slot instead of HBM.  bit 0: the parent's upper is read from LDS; bit 1 / 2: the left /
-	// right child's upper is parked in LDS.  The HBM slot stays assigned (the rescaling and parameter variants use it).
-	// (bit 3 is no longer set by the host; k_lower4_walk still tests it)
-	// lower walk: bit 0 / 1: the left / right child comes from the wave's park slot, bit 2: the result is kept there; the streamed
-	// walk's second slot: bit 4 / 5 and bit 6 (build_schedule)
-	int32_t lds_park;
-};
 
 #include "phyamd_memory.inc"
 

@@ -1,9 +1,11 @@
 // phyamd_eval.inc -- one evaluation: lower pass with incremental updates and the lazy rescaling switch, gradient passes, pattern tiling
 // (part of phyamd_engine.hip: one translation unit, internal linkage)
 
+// the engine's tree under its current options (schedule_options): the callers that change a switch come through here
 int rebuild_schedule(Shard *e) {
 	int rc;
-	if ((rc = build_schedule(e))) return rc;
+	const std::string err = build_schedule(TreeRef{e->T, e->left.data(), e->right.data(), e->root}, schedule_options(e), &e->sched);
+	if (!err.empty()) return fail(PHYAMD_EINVAL, "%s", err.c_str());
 	if ((rc = upload_schedule(e))) return rc;
 	if ((rc = ensure_lower_storage(e))) return rc;
 	input_changed(e, Input::ScheduleRebuilt);
@@ -27,7 +29,7 @@ int run_lower(Shard *e, int need_host_check) {
 	if ((rc = update_matrices(e))) return rc;
 	record(e, 1);
 	if (e->scaling_on && (rc = ensure_scaling_storage(e))) return rc;
-	e->act_level_off = &e->lower_level_off;
+	e->act_level_off = &e->sched.lower_level_off;
 	e->act_lower_ops = e->d_lower_ops;
 	e->incremental_pass = false;
 	bool incremental = !e->state.all_dirty;
@@ -51,29 +53,29 @@ int run_lower(Shard *e, int need_host_check) {
 		dirty.assign(e->N, 0);
 		// (20 / 60 / 61 states store t_n = P_n p_n: the branch's own node is recomputed too)
 		for (int n : e->state.changed)
-			for (int a = e->generic && n >= e->T ? n : e->parent[n]; a >= 0 && !dirty[a]; a = e->parent[a])
-				if (e->core_index[a] >= 0) dirty[a] = 1;  // fused fringe nodes are recomputed inside their first stored ancestor
+			for (int a = e->generic && n >= e->T ? n : e->sched.parent[n]; a >= 0 && !dirty[a]; a = e->sched.parent[a])
+				if (e->sched.core_index[a] >= 0) dirty[a] = 1;  // fused fringe nodes are recomputed inside their first stored ancestor
 		if (e->state.force_root) dirty[e->root] = 1;
 	}
 	if (e->state.stored_valid && e->stored.epoch == e->schedule_epoch) {
 		// nodes about to be written leave the slot the stored state lives in (current_partials_indexes flip, treelikelihood.c:1693-1700)
 		bool moved = false;
 		for (int n = e->T; n < e->N; n++)
-			if (e->core_index[n] >= 0 && (!incremental || dirty[n]) && e->core_index[n] == e->stored.core_index[n]) {
-				e->core_index[n] += e->core_index[n] < e->core_count ? e->core_count : -e->core_count;
+			if (e->sched.core_index[n] >= 0 && (!incremental || dirty[n]) && e->sched.core_index[n] == e->stored.core_index[n]) {
+				e->sched.core_index[n] += e->sched.core_index[n] < e->sched.core_count ? e->sched.core_count : -e->sched.core_count;
 				moved = true;
 			}
 		if (moved) {
-			refresh_op_cores(e);
+			refresh_op_cores(e->sched);
 			if ((rc = upload_schedule(e))) return rc;
 		}
 	}
 	if (incremental) {
 		e->inc_ops.clear();
 		e->inc_level_off.assign(1, 0);
-		for (size_t lv = 0; lv + 1 < e->lower_level_off.size(); lv++) {
-			for (int i = e->lower_level_off[lv]; i < e->lower_level_off[lv + 1]; i++)
-				if (dirty[e->lower_ops[i].parent]) e->inc_ops.push_back(e->lower_ops[i]);
+		for (size_t lv = 0; lv + 1 < e->sched.lower_level_off.size(); lv++) {
+			for (int i = e->sched.lower_level_off[lv]; i < e->sched.lower_level_off[lv + 1]; i++)
+				if (dirty[e->sched.lower_ops[i].parent]) e->inc_ops.push_back(e->sched.lower_ops[i]);
 			e->inc_level_off.push_back((int)e->inc_ops.size());
 		}
 		if ((rc = e->d_inc_ops.ensure(e->N))) return rc;
@@ -108,7 +110,7 @@ int run_lower(Shard *e, int need_host_check) {
 		e->scaling_on = true;
 		if ((rc = rebuild_schedule(e))) return rc;  // the rescaled schedule (20 states: no walk lists), fringe fusion stays
 		if ((rc = ensure_scaling_storage(e))) return rc;
-		e->act_level_off = &e->lower_level_off;  // and recomputes every node
+		e->act_level_off = &e->sched.lower_level_off;  // and recomputes every node
 		e->act_lower_ops = e->d_lower_ops;
 		e->incremental_pass = false;
 	}
@@ -130,7 +132,7 @@ int update_parameter_matrices(Shard *e) {
 		e->d_dptab.release();
 	}
 	if ((rc = e->d_B.ensure((size_t)np * S * S)) || (rc = e->d_dpm.ensure((size_t)np * e->N * e->C * S * S)) || (rc = e->d_dptab.ensure((size_t)np * e->T * e->C * 64)) ||
-	    (rc = e->d_ppart.ensure((size_t)np * e->upper_ops.size() * ((size_t)e->nblk + 1))))
+	    (rc = e->d_ppart.ensure((size_t)np * e->sched.upper_ops.size() * ((size_t)e->nblk + 1))))
 		return rc;
 	if (e->state.params_dirty) {
 		const std::vector<double> B = eigen_basis_derivatives(e);
@@ -162,7 +164,7 @@ int launch_parameters_gen(Shard *e, double *dst) {
 		for (int n = 0; n < e->N; n++)
 			if (n != e->root) nodes.push_back(n);
 		HIP_TRY(hipMemcpyAsync(e->d_pg_nodes, nodes.data(), sizeof(int) * nodes.size(), hipMemcpyHostToDevice, e->stream));
-		HIP_TRY(hipMemcpyAsync(e->d_pg_core, e->core_index.data(), sizeof(int) * e->N, hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_pg_core, e->sched.core_index.data(), sizeof(int) * e->N, hipMemcpyHostToDevice, e->stream));
 		HIP_TRY(hipStreamSynchronize(e->stream));
 	}
 	if (grew || e->state.params_dirty) {
@@ -175,7 +177,7 @@ int launch_parameters_gen(Shard *e, double *dst) {
 		const size_t npd = node_partial_doubles(e);
 		if ((rc = e->d_pg_lower.ensure(lower_slots(e) * npd))) return rc;
 		for (int n = e->T; n < e->N; n++)
-			if (e->core_index[n] >= 0 && (rc = true_lower_gen(e, n, e->d_pg_lower + (size_t)e->core_index[n] * npd, nullptr))) return rc;
+			if (e->sched.core_index[n] >= 0 && (rc = true_lower_gen(e, n, e->d_pg_lower + (size_t)e->sched.core_index[n] * npd, nullptr))) return rc;
 	}
 	hipLaunchKernelGGL(k_param_den_gen, dim3((e->P + 255) / 256, B), dim3(256), 0, e->stream, e->d_pg_nodes, e->T, e->P, e->Pp, S, e->C, e->d_pg_core, e->d_tipmask,
 	                   e->d_tipsets, e->d_pg_lower, e->d_upper, e->d_mats, e->d_freqs, e->d_props, e->d_pg_den);
@@ -195,7 +197,7 @@ int launch_root_frequency_term(Shard *e, double *dst) {
 	int rc;
 	const int nb = (e->P + 255) / 256;
 	if ((rc = e->d_rf_part.ensure(((size_t)nb + 1) * e->S))) return rc;
-	const double *root = e->d_lower + (size_t)e->core_index[e->root] * node_partial_doubles(e);
+	const double *root = e->d_lower + (size_t)e->sched.core_index[e->root] * node_partial_doubles(e);
 	const size_t cat_stride = e->generic ? (size_t)e->S * e->Pp : (size_t)e->P * e->S;
 	const size_t pat_stride = e->generic ? 1 : (size_t)e->S, state_stride = e->generic ? (size_t)e->Pp : 1;
 	hipLaunchKernelGGL(k_root_frequency_term, dim3(nb), dim3(256), 0, e->stream, e->P, e->S, e->C, root, cat_stride, pat_stride, state_stride, e->d_freqs,
@@ -211,7 +213,7 @@ int launch_root_invariant_term(Shard *e, double *dst) {
 	int rc;
 	const int nb = (e->P + 255) / 256;
 	if ((rc = e->d_inv_part.ensure((size_t)nb + 1))) return rc;
-	const double *root = e->d_lower + (size_t)e->core_index[e->root] * node_partial_doubles(e);
+	const double *root = e->d_lower + (size_t)e->sched.core_index[e->root] * node_partial_doubles(e);
 	const size_t cat_stride = e->generic ? (size_t)e->S * e->Pp : (size_t)e->P * e->S;
 	const size_t pat_stride = e->generic ? 1 : (size_t)e->S, state_stride = e->generic ? (size_t)e->Pp : 1;
 	const int *Ec = e->lower_form == LowerForm::CarriedExp2 ? (const int *)e->d_Ec : nullptr;
@@ -261,7 +263,7 @@ int run_gradient(Shard *e, int flags, bool with_params = false) {
 		if ((rc = rebuild_schedule(e))) return rc;
 	}
 	if ((rc = run_lower(e, e->tiles == 1 ? 2 : 1))) return rc;
-	if ((flags & PHYAMD_GRAD_FOLD_ROOT_FREQS) && e->scaling_on && e->fused) {
+	if ((flags & PHYAMD_GRAD_FOLD_ROOT_FREQS) && e->scaling_on && e->sched.fused) {
 		// The reference's folded-frequency arithmetic is inexact for non-uniform pi (DESIGN.md, quirk 1): under rescaling every
 		// branch then has its own "site likelihood" as denominator, which the fused fringe does not form.  Reproducing it takes
 		// the unfused schedule (every internal node stored) from here on.
@@ -297,7 +299,7 @@ int run_gradient(Shard *e, int flags, bool with_params = false) {
 		if ((rc = launch_parameters_gen(e, e->d_result + 1 + (size_t)e->N * e->C))) return rc;
 		if ((rc = launch_root_frequency_term(e, e->d_result + 1 + (size_t)e->N * e->C + e->np))) return rc;
 	} else if (with_params) {  // [np][ops][nblk] -> [np][ops] -> [np], fixed order
-		const int ops = (int)e->upper_ops.size();
+		const int ops = (int)e->sched.upper_ops.size();
 		double *stage = e->d_ppart + (size_t)e->np * ops * e->nblk;
 		hipLaunchKernelGGL(k_reduce_rows, dim3(e->np * ops), dim3(64), 0, e->stream, e->d_ppart, e->nblk, (const uint8_t *)nullptr, stage);
 		hipLaunchKernelGGL(k_reduce_rows, dim3(e->np), dim3(64), 0, e->stream, stage, ops, (const uint8_t *)nullptr, e->d_result + 1 + (size_t)e->N * e->C);
@@ -323,7 +325,7 @@ int run_hessian(Shard *e, double *out) {
 	e->reference_form_only = true;
 	// 20 states fuse cherries into their parents' ops, which leaves their tip branches without rows: the unfused schedule for this
 	// call, the fused one again afterwards (rebuild_schedule: the next evaluation recomputes every node, as a new engine would)
-	const bool unfuse = e->generic && e->fused;
+	const bool unfuse = e->generic && e->sched.fused;
 	if (unfuse) {
 		e->fusion_enabled = false;
 		rc = rebuild_schedule(e);

@@ -47,8 +47,8 @@ int update_matrices(Shard *e) {
 // is its partial.  `side`: a second buffer of the same size for fused cherries below the node (formed on the way)
 int true_lower_gen(Shard *e, int node, double *out, double *side) {
 	const size_t npd = node_partial_doubles(e), msz = (size_t)e->C * e->S * e->S;
-	if (node == e->root && e->core_index[node] >= 0) {
-		HIP_TRY(hipMemcpyAsync(out, e->d_lower + (size_t)e->core_index[node] * npd, sizeof(double) * npd, hipMemcpyDeviceToDevice, e->stream));
+	if (node == e->root && e->sched.core_index[node] >= 0) {
+		HIP_TRY(hipMemcpyAsync(out, e->d_lower + (size_t)e->sched.core_index[node] * npd, sizeof(double) * npd, hipMemcpyDeviceToDevice, e->stream));
 		return PHYAMD_OK;
 	}
 	int mode[2];
@@ -60,9 +60,9 @@ int true_lower_gen(Shard *e, int node, double *out, double *side) {
 		if (n < e->T) {
 			mode[q] = 0;
 			src[q] = nullptr;
-		} else if (e->core_index[n] >= 0) {
+		} else if (e->sched.core_index[n] >= 0) {
 			mode[q] = 1;
-			src[q] = e->d_lower + (size_t)e->core_index[n] * npd;
+			src[q] = e->d_lower + (size_t)e->sched.core_index[n] * npd;
 		} else {  // a fused cherry: two tips
 			const int l = e->left[n], r = e->right[n];
 			if (l >= e->T || r >= e->T || !side) return fail(PHYAMD_EINVAL, "node %d is neither stored nor a fused cherry", n);
@@ -150,10 +150,10 @@ void launch_lower_walk_ppt(Shard *e, size_t lds) {
 	e->lnl_per_block = true;
 	lds += sizeof(double) * ((size_t)(e->G & 1) + (size_t)e->G * e->C * PPT * 4 * WAVE);  // + one park slot per wave and pattern group (LPARK)
 	// the chunked list: every cut subtree as workgroups of its own (blockIdx.y), then the top part with the root
-	const int subtrees = (int)e->walk_lower_chunk_off.size() - 2;
+	const int subtrees = (int)e->sched.walk_lower_chunk_off.size() - 2;
 	for (int phase = subtrees > 0 ? 0 : 1; phase < 2; phase++)
 		hipLaunchKernelGGL((k_lower4_walk<WAVES, PPT, SCALE>), dim3(nb, phase ? 1 : subtrees), block_dims(e), lds, e->stream, e->d_walk_lower_chunk_ops,
-		                   (int)e->walk_lower_chunk_ops.size(), e->T, e->P, e->C, e->d_tipmask, e->d_lower, e->d_mats, e->d_tiptab, e->d_lscale, e->d_freqs,
+		                   (int)e->sched.walk_lower_chunk_ops.size(), e->T, e->P, e->C, e->d_tipmask, e->d_lower, e->d_mats, e->d_tiptab, e->d_lscale, e->d_freqs,
 		                   e->d_props, e->d_weights, e->d_plk, e->d_wl, e->d_lnl_part, (const int *)e->d_walk_lower_chunk_off, phase ? std::max(0, subtrees) : 0,
 		                   phase);
 	e->prof.lower_launches = subtrees > 0 ? 2 : 1;
@@ -199,19 +199,19 @@ int allow_big_lds(K kernel, size_t bytes) {
 // one pre-order pass.  PARAMS: also accumulate the substitution-parameter sums of parameters [p0, p0 + pc)
 template <int WAVES, bool SCALE, bool FOLD, bool COMPAT, bool PARAMS>
 int launch_upper_levels(Shard *e, int p0 = 0, int pc = 0) {
-	const int levels = (int)e->upper_level_off.size() - 1;
+	const int levels = (int)e->sched.upper_level_off.size() - 1;
 	int launched = 0;
 	const size_t nw = (size_t)e->G * e->C, nacc = NACC + (PARAMS ? pc : 0);
 	const size_t lds = sizeof(double) * ((SCALE ? 6 * nw * WAVE : 0) + nw * nacc * WAVE + nw * nacc);
 	int rc;
 	if ((rc = check_reference_form(e, "k_upper4"))) return rc;
 	if ((rc = allow_big_lds(k_upper4<WAVES, SCALE, FOLD, COMPAT, PARAMS, false>, lds))) return rc;
-	const int op_total = (int)e->upper_ops.size();
+	const int op_total = (int)e->sched.upper_ops.size();
 	const double *dpm = PARAMS ? e->d_dpm + (size_t)p0 * e->N * e->C * 16 : nullptr;
 	const double *dptab = PARAMS ? e->d_dptab + (size_t)p0 * e->T * e->C * 64 : nullptr;
 	double *ppart = PARAMS ? e->d_ppart + (size_t)p0 * op_total * e->nblk : nullptr;
 	for (int lv = 0; lv < levels; lv++) {
-		const int off = e->upper_level_off[lv], cnt = e->upper_level_off[lv + 1] - off;
+		const int off = e->sched.upper_level_off[lv], cnt = e->sched.upper_level_off[lv + 1] - off;
 		if (cnt == 0) continue;
 		dim3 grid(e->nblk, cnt);
 		launched++;
@@ -286,16 +286,16 @@ int finish_hess_slab(Shard *e, double *out, int launched) {
 // one HESS pre-order pass over the stored lowers (reference form) -> out[1 + 2 N] = [lnL | d1 | d2], sums over this engine's patterns
 template <int WAVES, bool SCALE>
 int launch_upper_hess(Shard *e, double *out) {
-	const int levels = (int)e->upper_level_off.size() - 1, R = 2 * e->N;
+	const int levels = (int)e->sched.upper_level_off.size() - 1, R = 2 * e->N;
 	const size_t lds = hess_lds(e);
 	int rc;
 	if ((rc = check_reference_form(e, "k_upper4"))) return rc;
 	if ((rc = allow_big_lds(k_upper4<WAVES, SCALE, false, false, false, true>, lds))) return rc;
-	const int op_total = (int)e->upper_ops.size();
+	const int op_total = (int)e->sched.upper_ops.size();
 	HIP_TRY(hipMemsetAsync(e->d_hess, 0, sizeof(double) * (size_t)e->hess_nwg * R, e->stream));  // (the root's entries stay zero)
 	int launched = 0;
 	for (int lv = 0; lv < levels; lv++) {
-		const int off = e->upper_level_off[lv], cnt = e->upper_level_off[lv + 1] - off;
+		const int off = e->sched.upper_level_off[lv], cnt = e->sched.upper_level_off[lv + 1] - off;
 		if (cnt == 0 || e->hess_nwg == 0) continue;
 		launched++;
 		hipLaunchKernelGGL((k_upper4<WAVES, SCALE, false, false, false, true>), dim3(e->hess_nwg, cnt), dim3(WAVE, e->C, 1), lds, e->stream, e->d_upper_ops + off, e->T,
@@ -331,16 +331,16 @@ int upload_qpi(Shard *e) {
 int ensure_mask_stream(Shard *e) {
 	const size_t mstride = (size_t)e->nblk_walk_upper * e->G * WAVE;
 	bool grew;
-	if (int rc = e->d_mstream.ensure((size_t)std::max(1, e->stream_words) * mstride, &grew)) return rc;
+	if (int rc = e->d_mstream.ensure((size_t)std::max(1, e->stream_tab.words) * mstride, &grew)) return rc;
 	if (grew) e->mstream_epoch = 0;
-	if (e->mstream_epoch == e->state.tip_epoch && e->mstride == mstride && e->mstream_layout == e->stream_row_entries) return PHYAMD_OK;
+	if (e->mstream_epoch == e->state.tip_epoch && e->mstride == mstride && e->mstream_layout == e->stream_tab.row_entries) return PHYAMD_OK;
 	e->mstride = mstride;
 	e->stream_unsupported = false;
 	e->stream_ambiguous = false;
-	if (e->stream_words > 0) {
+	if (e->stream_tab.words > 0) {
 		int flag = 0;
 		HIP_TRY(hipMemsetAsync(e->d_stream_flag, 0, sizeof(int), e->stream));
-		hipLaunchKernelGGL(k_build_mask_stream, dim3((unsigned)((mstride + 255) / 256), std::min(e->stream_words, 32768)), dim3(256), 0, e->stream, e->stream_words, e->P, mstride,
+		hipLaunchKernelGGL(k_build_mask_stream, dim3((unsigned)((mstride + 255) / 256), std::min(e->stream_tab.words, 32768)), dim3(256), 0, e->stream, e->stream_tab.words, e->P, mstride,
 		                   (const int *)e->d_stream_row_entries, e->d_tipmask, e->d_mstream, e->d_stream_flag);
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipMemcpyAsync(&flag, e->d_stream_flag, sizeof(int), hipMemcpyDeviceToHost, e->stream));
@@ -349,13 +349,13 @@ int ensure_mask_stream(Shard *e) {
 		e->stream_ambiguous = (flag & 2) != 0;
 	}
 	e->mstream_epoch = e->state.tip_epoch;
-	e->mstream_layout = e->stream_row_entries;
+	e->mstream_layout = e->stream_tab.row_entries;
 	return PHYAMD_OK;
 }
 
 // table blocks of the streamed walk: one per (pre-order op, category)
 int ensure_optab(Shard *e) {
-	return e->d_optab.ensure((size_t)std::max<size_t>(1, e->stream_ops.size()) * e->C * OPBLK_BYTES);
+	return e->d_optab.ensure((size_t)std::max<size_t>(1, e->stream_tab.ops.size()) * e->C * OPBLK_BYTES);
 }
 
 // the exponents of the power-of-two rescaling (LowerForm::CarriedExp2), the pre-order walk's included: made before the post-order
@@ -400,10 +400,10 @@ int make_stream_buffers(Shard *e, bool lower) {
 // the streamed post-order walk (k_lower4_stream): every cut subtree as workgroups of its own, then the top part with the root
 int launch_lower_stream(Shard *e) {
 	int rc;
-	const int nb = (e->P + WAVE - 1) / WAVE, nops = (int)e->stream_ops.size();
-	if (e->stream_P != e->P || e->stream_mstride != e->mstride) {  // (the descriptors' byte offsets: see launch_upper_stream)
+	const int nb = (e->P + WAVE - 1) / WAVE, nops = (int)e->stream_tab.ops.size();
+	if (e->stream_tab.P != e->P || e->stream_tab.mstride != e->mstride) {  // (the descriptors' byte offsets: see launch_upper_stream)
 		if ((rc = upload_schedule(e))) return rc;
-		if (e->stream_P != e->P || e->stream_mstride != e->mstride) return fail(PHYAMD_EDEVICE, "streamed walk: descriptors do not match the pattern storage");
+		if (e->stream_tab.P != e->P || e->stream_tab.mstride != e->mstride) return fail(PHYAMD_EDEVICE, "streamed walk: descriptors do not match the pattern storage");
 	}
 	hipLaunchKernelGGL(k_op_tables, dim3(nops, e->C), dim3(64), 0, e->stream, nops, e->C, (const int *)e->d_stream_op_tips, (const int *)e->d_stream_op_deep,
 	                   (const int *)e->d_stream_site_tab, e->d_mats, (const double *)nullptr, reinterpret_cast<double *>(e->d_optab.get()));
@@ -416,7 +416,7 @@ int launch_lower_stream(Shard *e) {
 	const int waves = scale ? e->C : STREAM_WAVES;
 	const size_t lds = (size_t)LSTREAM_LDS_PER_WAVE * waves + (scale ? sizeof(double) * 2 * e->C * WAVE : 0);
 	const unsigned gx = scale ? (unsigned)nb : (unsigned)((nb + STREAM_WAVES - 1) / STREAM_WAVES) * e->C;
-	const int subtrees = (int)e->walk_lower_chunk_off.size() - 2;
+	const int subtrees = (int)e->sched.walk_lower_chunk_off.size() - 2;
 	const bool amb = e->stream_ambiguous;
 	auto *kernel = exp2 ? (amb ? k_lower4_stream<true, 2, true> : k_lower4_stream<false, 2, true>)
 	             : scale ? (amb ? k_lower4_stream<true, 1, false> : k_lower4_stream<false, 1, false>)
@@ -429,7 +429,7 @@ int launch_lower_stream(Shard *e) {
 		                   (const double *)e->d_props, e->d_Lc, phase, exp2 ? reinterpret_cast<double *>(e->d_lexp.get()) : scale ? e->d_lscale : (double *)nullptr, e->xcd_map,
 		                   exp2 ? e->d_Ec : (int *)nullptr);
 	hipLaunchKernelGGL(k_root_finish64, dim3(nb), dim3(64), 0, e->stream, e->P, e->C, (const double *)e->d_Lc, (const double *)e->d_weights, e->d_plk, e->d_wl, e->d_lnl_part,
-	                   scale ? (const double *)(e->d_lscale + (size_t)e->core_index[e->root] * e->P) : (const double *)nullptr, exp2 ? (const int *)e->d_Ec : (const int *)nullptr,
+	                   scale ? (const double *)(e->d_lscale + (size_t)e->sched.core_index[e->root] * e->P) : (const double *)nullptr, exp2 ? (const int *)e->d_Ec : (const int *)nullptr,
 	                   exp2 ? e->d_Eroot : (int *)nullptr);
 	HIP_TRY(hipGetLastError());
 	e->prof.lower_launches = subtrees > 0 ? 2 : 1;
@@ -442,14 +442,14 @@ int launch_lower_stream(Shard *e) {
 template <bool FOLD, bool SCALE>
 int launch_upper_stream(Shard *e) {
 	int rc;
-	const int nb = (e->P + WAVE - 1) / WAVE, R = e->stream_R, nops = (int)e->stream_ops.size();  // blocks of 64 patterns
+	const int nb = (e->P + WAVE - 1) / WAVE, R = e->stream_tab.R, nops = (int)e->stream_tab.ops.size();  // blocks of 64 patterns
 	// the walk-order slab [nb][C][R] lives in the [row][block] slab's storage (N * C * gpart_row doubles, gpart_row >= nb, R = N - 1)
 	if ((size_t)nb * e->C * R > (size_t)e->N * e->C * e->gpart_row) return fail(PHYAMD_EDEVICE, "gradient slab too small for the streamed walk");
 	e->d_gslab = e->d_gpart;
 	// the descriptors carry byte offsets multiplied out for a pattern count and a mask-row stride: rebuilt if either has moved
-	if (e->stream_P != e->P || e->stream_mstride != e->mstride) {
+	if (e->stream_tab.P != e->P || e->stream_tab.mstride != e->mstride) {
 		if ((rc = upload_schedule(e))) return rc;
-		if (e->stream_P != e->P || e->stream_mstride != e->mstride) return fail(PHYAMD_EDEVICE, "streamed walk: descriptors do not match the pattern storage");
+		if (e->stream_tab.P != e->P || e->stream_tab.mstride != e->mstride) return fail(PHYAMD_EDEVICE, "streamed walk: descriptors do not match the pattern storage");
 	}
 	if ((rc = e->d_oct.ensure((size_t)8 * e->C * R))) return rc;
 	// plain: workgroup = four blocks of one category; rescaled as the reference does: the C <= 4 category waves of one block + their
@@ -463,7 +463,7 @@ int launch_upper_stream(Shard *e) {
 	const dim3 grid_x(SCALE && !exp2 ? (unsigned)nb : (unsigned)((nb + STREAM_WAVES - 1) / STREAM_WAVES) * e->C), block(WAVE, waves);
 	hipLaunchKernelGGL(k_op_tables, dim3(nops, e->C), dim3(64), 0, e->stream, nops, e->C, (const int *)e->d_stream_op_tips, (const int *)e->d_stream_op_deep,
 	                   (const int *)e->d_stream_site_tab, e->d_mats, FOLD ? e->d_Q : e->d_Qpi, reinterpret_cast<double *>(e->d_optab.get()));
-	const int subtrees = (int)e->walk_chunk_off.size() - 2;
+	const int subtrees = (int)e->sched.walk_chunk_off.size() - 2;
 	for (int phase = 0; phase < (subtrees > 0 ? 2 : 1); phase++) {
 		const bool amb = e->stream_ambiguous;
 		auto *kernel = exp2 ? (amb ? k_upper4_stream<FOLD, 2, true, true> : k_upper4_stream<FOLD, 2, false, true>)
@@ -519,19 +519,19 @@ int reduce_block_sums(Shard *e, int which, const double *slab, int nb, int C, in
 // gradient rows from the walk-order slab
 int reduce_stream_slab(Shard *e, double *out) {
 	HIP_TRY(hipMemsetAsync(out, 0, sizeof(double) * (size_t)e->N * e->C, e->stream));  // the root's rows
-	return reduce_block_sums(e, 1, e->d_gslab, e->grad_blocks, e->C, e->stream_R, (const int *)e->d_stream_qnode, out);
+	return reduce_block_sums(e, 1, e->d_gslab, e->grad_blocks, e->C, e->stream_tab.R, (const int *)e->d_stream_qnode, out);
 }
 
 template <int WAVES, bool FOLD, bool SCALE, bool COMPAT>
 int launch_upper_walk_v(Shard *e) {
-	const int ops = (int)e->walk_upper_ops.size(), nb = e->nblk_walk_upper * e->G;
+	const int ops = (int)e->sched.walk_upper_ops.size(), nb = e->nblk_walk_upper * e->G;
 	int rc;
 	if ((rc = check_reference_form(e, "k_upper4_walk"))) return rc;
 	// columns, the rescaling exchange, then the leaf parks' LDS slots (LPARK: 2 KB per wave)
 	const size_t lds = sizeof(double) * ((size_t)e->G * e->C * NACC * WCOL + (SCALE ? (size_t)4 * e->G * e->C * WAVE : 0) + (size_t)4 * e->G * e->C * WAVE);
 	if ((rc = allow_big_lds(k_upper4_walk<WAVES, FOLD, false, SCALE, COMPAT>, lds))) return rc;
 	// the chunked list: the top part, then every cut subtree as workgroups of its own (blockIdx.y)
-	const int subtrees = (int)e->walk_chunk_off.size() - 2;
+	const int subtrees = (int)e->sched.walk_chunk_off.size() - 2;
 	for (int phase = 0; phase < (subtrees > 0 ? 2 : 1); phase++)
 		hipLaunchKernelGGL((k_upper4_walk<WAVES, FOLD, false, SCALE, COMPAT>), dim3(e->nblk_walk_upper, phase ? subtrees : 1), block_dims(e), lds, e->stream,
 		                   e->d_walk_chunk_ops, ops, e->T, e->P, e->C, e->d_tipmask, e->d_lower, e->d_upper, e->d_mats, e->d_tiptab, FOLD ? e->d_Q : e->d_Qpi,
@@ -578,7 +578,7 @@ std::vector<double> eigen_basis_derivatives(const Shard *e) {
 // G2 through the tree walk: B = U^-1 dQ U per parameter, the eigen-basis tables, one walk, then 16 sums and a contraction
 template <int WAVES, bool SCALE>
 int launch_upper_walk_params(Shard *e) {
-	const int ops = (int)e->walk_upper_ops.size(), nb = e->nblk_walk_upper * e->G, S = 4, np = e->np;
+	const int ops = (int)e->sched.walk_upper_ops.size(), nb = e->nblk_walk_upper * e->G, S = 4, np = e->np;
 	const size_t lds = sizeof(double) * ((size_t)e->G * e->C * 16 * WCOL + (SCALE ? (size_t)4 * e->G * e->C * WAVE : 0));
 	int rc;
 	if ((rc = check_reference_form(e, "k_upper4_walk (parameters)"))) return rc;
@@ -668,8 +668,8 @@ int launch_upper_params_w(Shard *e, int flags) {
 // rows: 5, or 7 for the HESS pre-order pass (num2_l, num2_r besides)
 int ensure_gen_scale_storage(Shard *e, int rows = 5) {
 	int widest = 1;
-	for (size_t i = 0; i + 1 < e->lower_level_off.size(); i++) widest = std::max(widest, e->lower_level_off[i + 1] - e->lower_level_off[i]);
-	for (size_t i = 0; i + 1 < e->upper_level_off.size(); i++) widest = std::max(widest, e->upper_level_off[i + 1] - e->upper_level_off[i]);
+	for (size_t i = 0; i + 1 < e->sched.lower_level_off.size(); i++) widest = std::max(widest, e->sched.lower_level_off[i + 1] - e->sched.lower_level_off[i]);
+	for (size_t i = 0; i + 1 < e->sched.upper_level_off.size(); i++) widest = std::max(widest, e->sched.upper_level_off[i + 1] - e->sched.upper_level_off[i]);
 	return e->d_gen_scratch.ensure((size_t)widest * rows * e->C * e->P);
 }
 
@@ -745,7 +745,7 @@ int launch_lower_gen(Shard *e) {
 			hipLaunchKernelGGL(k_scale_gen, dim3(pblocks, cnt), dim3(256), 0, e->stream, e->act_lower_ops + off, e->P, e->Pp, e->S, e->C, e->d_lower, e->d_gen_scratch,
 			                   e->d_lscale, is_root ? e->d_Lc : (double *)nullptr);
 	}
-	const double *lscale_root = SCALE ? e->d_lscale + (size_t)e->core_index[e->root] * e->P : nullptr;
+	const double *lscale_root = SCALE ? e->d_lscale + (size_t)e->sched.core_index[e->root] * e->P : nullptr;
 	hipLaunchKernelGGL(k_root_finish, dim3(e->nblk_root), dim3(256), 0, e->stream, e->P, e->C, e->d_Lc, e->d_weights, lscale_root, e->d_plk, e->d_wl, e->d_lnl_part);
 	HIP_TRY(hipGetLastError());
 	e->prof.lower_launches = launched;
@@ -755,7 +755,7 @@ int launch_lower_gen(Shard *e) {
 
 template <int RT, int KT, bool FOLD, bool SCALE>
 int launch_upper_gen_v(Shard *e, bool compat) {
-	const int levels = (int)e->upper_level_off.size() - 1;
+	const int levels = (int)e->sched.upper_level_off.size() - 1;
 	const size_t lds = sizeof(double) * (GenFuse<RT>::UPPER_IMAGES * MatImage<RT, KT>::SIZE + 6 * GenGeo<RT>::WAVES);
 	int rc;
 	if ((rc = allow_big_lds(k_upper_gen<RT, KT, FOLD, SCALE, false>, lds))) return rc;
@@ -771,7 +771,7 @@ int launch_upper_gen_v(Shard *e, bool compat) {
 	HIP_TRY(hipMemsetAsync(e->d_gpart, 0, sizeof(double) * (size_t)e->N * e->C * e->gpart_row, e->stream));
 	TileRange range;
 	for (int lv = 0; lv < levels; lv++) {
-		const int off = e->upper_level_off[lv], cnt = e->upper_level_off[lv + 1] - off;
+		const int off = e->sched.upper_level_off[lv], cnt = e->sched.upper_level_off[lv + 1] - off;
 		if (cnt == 0) continue;
 		const int tiles = choose_gen_tiles(e->P, WV, (long)cnt * e->C, slots, gen_stage_cost(e->S));
 		range.add(tiles);
@@ -802,12 +802,12 @@ int launch_upper_gen_v(Shard *e, bool compat) {
 template <int RT, int KT, bool SCALE>
 int launch_upper_gen_hess(Shard *e, double *out) {
 	using Img = MatImage<RT, KT>;
-	const int levels = (int)e->upper_level_off.size() - 1, S = e->S;
+	const int levels = (int)e->sched.upper_level_off.size() - 1, S = e->S;
 	for (int i = 0; i < S; i++)
 		if (!(e->freqs[i] > 0.0)) return fail(PHYAMD_EUNSUPPORTED, "the Hessian diagonal divides by the frequencies: state %d has frequency %g", i, e->freqs[i]);
 	const size_t lds = sizeof(double) * (GenFuse<RT>::UPPER_IMAGES * Img::SIZE + 6 * GenGeo<RT>::WAVES);
 	int rc;
-	if (e->fused) return fail(PHYAMD_EDEVICE, "k_upper_gen<HESS> runs on the unfused schedule");
+	if (e->sched.fused) return fail(PHYAMD_EDEVICE, "k_upper_gen<HESS> runs on the unfused schedule");
 	if ((rc = allow_big_lds(k_upper_gen<RT, KT, false, SCALE, true>, lds))) return rc;
 	if ((rc = ensure_gen_scale_storage(e, 7))) return rc;
 	if (GenFuse<RT>::QP && (rc = ensure_tip_rate_products(e, false))) return rc;
@@ -825,7 +825,7 @@ int launch_upper_gen_hess(Shard *e, double *out) {
 	int launched = 0;
 	TileRange range;
 	for (int lv = 0; lv < levels; lv++) {
-		const int off = e->upper_level_off[lv], cnt = e->upper_level_off[lv + 1] - off;
+		const int off = e->sched.upper_level_off[lv], cnt = e->sched.upper_level_off[lv + 1] - off;
 		if (cnt == 0) continue;
 		launched++;
 		const int tiles = choose_gen_tiles(e->P, WV, (long)cnt * e->C, slots, gen_stage_cost(e->S));
@@ -862,7 +862,7 @@ int launch_lower_gen_walk(Shard *e) {
 	int rc;
 	if ((rc = allow_big_lds(k_lower_gen_walk<RT, KT>, lds))) return rc;
 	if (e->gen_walk_slots[0] == 0) e->gen_walk_slots[0] = resident_workgroups(e, k_lower_gen_walk<RT, KT>, WV * 64, lds);
-	const int groups = (e->P + WV * 16 - 1) / (WV * 16), nops = (int)e->walk_lower_ops.size(), units = groups * e->C;
+	const int groups = (e->P + WV * 16 - 1) / (WV * 16), nops = (int)e->sched.walk_lower_ops.size(), units = groups * e->C;
 	const int wgs = std::max(1, std::min(units, e->gen_walk_slots[0]));
 	if ((rc = e->d_gen_walk_counter.ensure(1))) return rc;
 	HIP_TRY(hipMemsetAsync(e->d_gen_walk_counter, 0, sizeof(int), e->stream));

@@ -29,7 +29,7 @@ int require_resident_partials(Shard *e, const char *call) {
 	if (!e->keep_partials && (rc = shard_set_keep_partials(e, 1))) return rc;
 	if ((!uppers_resident(e) || !lowers_current(e)) && (rc = eval_gradient(e, 0))) return rc;
 	if ((rc = require_reference_form(e))) return rc;  // (stored partials: the partials themselves, in the reference's form)
-	if (!uppers_resident(e) || e->core_index[e->root] < 0) return fail(PHYAMD_EDEVICE, "%s: the gradient left no resident partials", call);
+	if (!uppers_resident(e) || e->sched.core_index[e->root] < 0) return fail(PHYAMD_EDEVICE, "%s: the gradient left no resident partials", call);
 	return PHYAMD_OK;
 }
 
@@ -59,91 +59,7 @@ int profiled_call(Shard *e, Prof Shard::*slot, Prof prof, Body body) {
 
 // ---- a batch of branch-length vectors (phyamd_gradient_batch) ----------------------------------------------------------------
 
-// the two op lists of the batched walk for a tree (T tips; left / right / root in phyamd_set_topology's convention, already
-// validated), appended to `ops` as [post-order T - 1 | pre-order T - 1]; returns the upper slots the pre-order list parks in.
-// ops == null: only counts the slots.  Post-order: depth first, the larger subtree first, so that the child finished last hands
-// its partial on in registers.  Pre-order: of two internal children the smaller subtree is entered first with its upper in
-// registers and the other's upper is parked in a slot that is free again once its op has read it: at most log2(T) + 1 slots,
-// whatever the shape (a caterpillar parks nothing).  Ties go by left / right, never by node id: the lists of one tree under two
-// labellings of its internal nodes differ in the ids only.
-// park_all (phyamd_nni_log_likelihoods): every internal child's upper is parked in a slot of its own, slot = node - T, and none
-// is handed on in registers: T - 1 slots, and after the walk every internal non-root node's upper is in the scratch.
-int build_batch_ops(int T, const int32_t *left, const int32_t *right, int root, std::vector<BatchOp> *ops, bool park_all = false) {
-	const int N = 2 * T - 1;
-	std::vector<int> size(N, 1), order;
-	{
-		std::vector<int> stack{root};
-		while (!stack.empty()) {
-			const int n = stack.back();
-			stack.pop_back();
-			order.push_back(n);
-			if (n >= T) {
-				stack.push_back(left[n]);
-				stack.push_back(right[n]);
-			}
-		}
-		for (size_t i = order.size(); i-- > 0;)
-			if (order[i] >= T) size[order[i]] += size[left[order[i]]] + size[right[order[i]]];
-	}
-	if (ops) {  // post-order: (node, children done?) on an explicit stack
-		std::vector<std::pair<int, bool>> stack{{root, false}};
-		int last = -1;
-		while (!stack.empty()) {
-			const auto [n, done] = stack.back();
-			stack.pop_back();
-			const int l = left[n], r = right[n];
-			if (!done) {
-				stack.push_back({n, true});
-				const int first = size[l] >= size[r] ? l : r, second = first == l ? r : l;
-				if (second >= T) stack.push_back({second, false});
-				if (first >= T) stack.push_back({first, false});
-				continue;
-			}
-			BatchOp op{n, l, r, last == l && l >= T ? 1 : last == r && r >= T ? 2 : 0, BATCH_NONE, BATCH_NONE, BATCH_NONE, 0};
-			ops->push_back(op);
-			last = n;
-		}
-	}
-	int slots = 0;
-	{  // pre-order
-		std::vector<std::pair<int, int>> stack{{root, BATCH_ROOT}};  // (node, where its upper is)
-		std::vector<int> free_slots;
-		while (!stack.empty()) {
-			const auto [n, src] = stack.back();
-			stack.pop_back();
-			const int l = left[n], r = right[n];
-			BatchOp op{n, l, r, 0, src, BATCH_NONE, BATCH_NONE, 0};
-			if (park_all) {
-				if (l >= T) op.dst_left = l - T, stack.push_back({l, l - T});
-				if (r >= T) op.dst_right = r - T, stack.push_back({r, r - T});
-				if (ops) ops->push_back(op);
-				continue;
-			}
-			if (l >= T && r >= T) {
-				int slot;
-				if (free_slots.empty()) slot = slots++;
-				else {
-					slot = free_slots.back();
-					free_slots.pop_back();
-				}
-				const bool left_first = size[l] <= size[r];
-				op.dst_left = left_first ? BATCH_CARRY : slot;
-				op.dst_right = left_first ? slot : BATCH_CARRY;
-				stack.push_back({left_first ? r : l, slot});
-				stack.push_back({left_first ? l : r, BATCH_CARRY});
-			} else if (l >= T) {
-				op.dst_left = BATCH_CARRY;
-				stack.push_back({l, BATCH_CARRY});
-			} else if (r >= T) {
-				op.dst_right = BATCH_CARRY;
-				stack.push_back({r, BATCH_CARRY});
-			}
-			if (ops) ops->push_back(op);
-			if (src >= 0) free_slots.push_back(src);  // read by this op: later ops may park in it
-		}
-	}
-	return park_all ? std::max(1, T - 1) : std::max(1, slots);
-}
+// (the op lists: build_batch_ops, phyamd_tree_schedule.h)
 
 // the engine's own lists (a batch of branch-length vectors), built once per topology
 int ensure_engine_batch_ops(Shard *e) {
@@ -541,39 +457,6 @@ int shard_gradient_batch_weights(Shard *e, int flags, int32_t count, const doubl
 
 // ---- a batch of trees (phyamd_gradient_batch_trees) ---------------------------------------------------------------------------
 
-// item `item` of a batch of trees is one binary tree over all 2T - 1 nodes in phyamd_set_topology's convention (build_schedule's
-// checks, on the item's arrays)
-int validate_batch_tree(int T, const int32_t *left, const int32_t *right, int root, int item, std::vector<int> &parents, std::vector<int> &stack,
-                        const char *name = "phyamd_gradient_batch_trees") {
-	const int N = 2 * T - 1;
-	parents.assign(N, 0);
-	for (int n = 0; n < N; n++) {
-		const int l = left[n], r = right[n];
-		if (n < T) {
-			if (l != -1 || r != -1) return fail(PHYAMD_EINVAL, "%s: item %d: node %d is a tip (id < tip_count) but has children", name, item, n);
-			continue;
-		}
-		if (l < 0 || r < 0 || l >= N || r >= N || l == r)
-			return fail(PHYAMD_EINVAL, "%s: item %d: internal node %d has invalid children (%d, %d)", name, item, n, l, r);
-		if (++parents[l] > 1 || ++parents[r] > 1) return fail(PHYAMD_EINVAL, "%s: item %d: node %d or %d has two parents", name, item, l, r);
-	}
-	if (root < T || root >= N || parents[root] != 0) return fail(PHYAMD_EINVAL, "%s: item %d: root %d is not a parentless internal node", name, item, root);
-	// (no node has two parents and the root has none: the walk from the root meets no node twice)
-	int reached = 0;
-	stack.assign(1, root);
-	while (!stack.empty()) {
-		const int n = stack.back();
-		stack.pop_back();
-		reached++;
-		if (n >= T) {
-			stack.push_back(left[n]);
-			stack.push_back(right[n]);
-		}
-	}
-	if (reached != N) return fail(PHYAMD_EINVAL, "%s: item %d: the topology is not a single binary tree over all %d nodes", name, item, N);
-	return PHYAMD_OK;
-}
-
 // the items of a batch of trees through the batched walk, in chunks of what the scratch holds.  Per chunk: the items' op lists are
 // built and uploaded with their roots, the upper slots are those of the chunk's deepest-parking item, three launches
 int run_tree_batch(Shard *e, int flags, int32_t count, const int32_t *left, const int32_t *right, const int32_t *roots, const double *branch_lengths, double *lnl,
@@ -587,10 +470,11 @@ int run_tree_batch(Shard *e, int flags, int32_t count, const int32_t *left, cons
 	const size_t N = (size_t)e->N, ncat = N * e->C, rows = grad ? 1 + ncat : 1, nops = 2 * (size_t)(T - 1);
 	std::vector<int> slots(count);  // per item: the upper slots its pre-order list parks in
 	{
-		std::vector<int> parents, stack;
+		std::vector<int32_t> parents;
 		for (int32_t b = 0; b < count; b++) {  // every item, before anything is launched
 			const int32_t *l = left + (size_t)b * N, *r = right + (size_t)b * N;
-			if ((rc = validate_batch_tree(T, l, r, roots[b], b, parents, stack))) return rc;
+			const std::string err = validate_tree(TreeRef{T, l, r, roots[b]}, parents, "phyamd_gradient_batch_trees", b);
+			if (!err.empty()) return fail(PHYAMD_EINVAL, "%s", err.c_str());
 			slots[b] = grad ? build_batch_ops(T, l, r, roots[b], nullptr) : 1;
 		}
 	}
@@ -661,7 +545,7 @@ int upload_nni_lists(Shard *e) {
 	std::vector<int32_t> cand_of(N, -1);
 	for (int v = T; v < N; v++) {
 		if (v == e->root) continue;
-		const int u = e->parent[v];
+		const int u = e->sched.parent[v];
 		cand_of[v] = (int32_t)cands.size();
 		cands.push_back(NniCand{v, u == e->root ? BATCH_ROOT : u, e->left[u] == v ? e->right[u] : e->left[u], e->left[v], e->right[v], {0, 0, 0}});
 	}
@@ -776,7 +660,7 @@ void ensure_spr_lists(Shard *e) {
 // ops, and nothing parked in p's subtree -- appended to `ops`, its candidates to `cands`, their indices into cand_of [N]
 void build_spr_row(const Shard *e, int row, int p, std::vector<BatchOp> *ops, std::vector<SprCand> *cands, int32_t *cand_of) {
 	const int T = e->T, N = e->N, nops = T - 1;
-	const int u = e->parent[p], s = e->left[u] == p ? e->right[u] : e->left[u];
+	const int u = e->sched.parent[p], s = e->left[u] == p ? e->right[u] : e->left[u];
 	const auto below_p = [&](int n) { return e->spr_tin[p] <= e->spr_tin[n] && e->spr_tin[n] < e->spr_tout[p]; };
 	const size_t first = ops->size();
 	ops->insert(ops->end(), e->spr_ops.begin(), e->spr_ops.end());
@@ -792,7 +676,7 @@ void build_spr_row(const Shard *e, int row, int p, std::vector<BatchOp> *ops, st
 	for (int w = 0; w < N; w++) {
 		cand_of[w] = -1;
 		if (w == e->root || w == u || w == s || below_p(w)) continue;
-		const int x = e->parent[w];
+		const int x = e->sched.parent[w];
 		cand_of[w] = (int32_t)cands->size();
 		cands->push_back(SprCand{row, w, x == e->root ? BATCH_ROOT : x, e->left[x] == w ? e->right[x] : e->left[x], p, {0, 0, 0}});
 	}
@@ -812,7 +696,7 @@ int run_spr(Shard *e, int flags, int32_t count, const int32_t *prune, double *ln
 	for (int32_t i = 0; i < count; i++) {
 		const int p = prune ? prune[i] : i;
 		if (p < 0 || p >= N) return fail(PHYAMD_EINVAL, "phyamd_spr_log_likelihoods: prune[%d] = %d is not a node id (0..%d)", i, p, N - 1);
-		if (p != e->root && e->parent[p] != e->root) live.push_back(i);
+		if (p != e->root && e->sched.parent[p] != e->root) live.push_back(i);
 	}
 	std::fill(lnl, lnl + (size_t)count * N, NAN);
 	prof.prunes = count;
@@ -940,12 +824,12 @@ int shard_state_posteriors(Shard *e, int flags, int32_t count, const int32_t *no
 			d.low = nullptr;
 			d.up = nullptr;
 			if (node != e->root) {
-				if (e->upper_slot[node] < 0) return fail(PHYAMD_EDEVICE, "phyamd_state_posteriors: node %d has no resident upper partial", node);
-				d.up = e->d_upper + (size_t)e->upper_slot[node] * npd;
+				if (e->sched.upper_slot[node] < 0) return fail(PHYAMD_EDEVICE, "phyamd_state_posteriors: node %d has no resident upper partial", node);
+				d.up = e->d_upper + (size_t)e->sched.upper_slot[node] * npd;
 			}
 			if (node >= e->T) {
-				if (e->core_index[node] < 0) return fail(PHYAMD_EDEVICE, "phyamd_state_posteriors: node %d has no resident lower partial", node);
-				d.low = e->d_lower + (size_t)e->core_index[node] * npd;
+				if (e->sched.core_index[node] < 0) return fail(PHYAMD_EDEVICE, "phyamd_state_posteriors: node %d has no resident lower partial", node);
+				d.low = e->d_lower + (size_t)e->sched.core_index[node] * npd;
 				if (e->generic && node != e->root) {  // a stored array is the message P p: the node's own partial, into this row's temporary
 					double *own = e->d_post_lower + r * npd;
 					if ((rc = true_lower_gen(e, node, own, nullptr))) return rc;
@@ -997,11 +881,11 @@ int shard_site_rate_posteriors(Shard *e, double *posteriors, double *mean_rates)
 	if ((rc = bind_device(e)) || (rc = check_ready(e))) return rc;
 	if ((rc = run_lower(e, 1))) return rc;
 	if (e->scaling_on && (rc = require_reference_form(e))) return rc;  // (see shard_root_frequency_term: factors common to the categories)
-	if (e->core_index[e->root] < 0 || !e->d_lower) return fail(PHYAMD_EDEVICE, "phyamd_site_rate_posteriors: the root partial is not resident");
+	if (e->sched.core_index[e->root] < 0 || !e->d_lower) return fail(PHYAMD_EDEVICE, "phyamd_site_rate_posteriors: the root partial is not resident");
 	const int P = e->P, C = e->C;
 	e->d_post_rows.release(), e->d_post_lower.release(), e->d_post_states.release();  // (what a state call left is not this call's: its room is)
 	if ((rc = e->d_post_out.ensure((size_t)P * C + P))) return rc;
-	const double *root = e->d_lower + (size_t)e->core_index[e->root] * node_partial_doubles(e);
+	const double *root = e->d_lower + (size_t)e->sched.core_index[e->root] * node_partial_doubles(e);
 	const size_t cat_stride = e->generic ? (size_t)e->S * e->Pp : (size_t)P * e->S;
 	const size_t pat_stride = e->generic ? 1 : (size_t)e->S, state_stride = e->generic ? (size_t)e->Pp : 1;
 	double *R = e->d_post_out.get(), *mean = R + (size_t)P * C;
@@ -1033,7 +917,7 @@ void build_bhess_lists(const Shard *e, BhessLists &L) {
 		if (a == root) continue;
 		branches.push_back(a);
 		BhessStart s{a, (int32_t)L.steps.size(), 0, 0};
-		for (int cur = a, m = e->parent[a];; cur = m, m = e->parent[m]) {
+		for (int cur = a, m = e->sched.parent[a];; cur = m, m = e->sched.parent[m]) {
 			const bool from_left = e->left[m] == cur;
 			below[(size_t)2 * m + (from_left ? 0 : 1)].push_back({a, (int32_t)L.steps.size()});
 			L.steps.push_back(BhessStep{m, from_left ? e->right[m] : e->left[m], a, 0});
@@ -1102,8 +986,8 @@ int run_branch_hessian(Shard *e, double *lnl, double *gradient, double *hessian,
 	build_bhess_lists(e, L);
 	std::vector<int32_t> lower_of(N), upper_of(N);
 	for (int n = 0; n < N; n++) {
-		lower_of[n] = n < e->T ? -1 : e->core_index[n];
-		upper_of[n] = n == e->root ? 0 : e->upper_slot[n];
+		lower_of[n] = n < e->T ? -1 : e->sched.core_index[n];
+		upper_of[n] = n == e->root ? 0 : e->sched.upper_slot[n];
 		if ((n >= e->T && lower_of[n] < 0) || upper_of[n] < 0) return fail(PHYAMD_EDEVICE, "%s: node %d has no resident partial", name, n);
 	}
 	const size_t nsteps = L.steps.size(), ntc = L.cousins.size(), nto = L.outer.size(), nn = (size_t)N * N;
@@ -1199,43 +1083,7 @@ int shard_branch_hessian(Shard *e, int flags, double *lnl, double *gradient, dou
 
 // ---- per-pattern lnL of a batch of trees, and RELL replicates of them (phyamd_pattern_log_likelihoods_trees) --------------------
 
-// The post-order list of build_batch_ops for a tree (already validated) with the slot words k_sitelnl_walk4 reads
-// (phyamd_sitelnl.inc), appended to `ops` (null: only counted); returns the slots the list parks in.  A result whose parent is the
-// next op is handed on in registers; any other waits in a slot, which is free again once the parent has read it -- before the
-// parent's own result looks for one.  The list takes the larger subtree first, so the result that waits while a sibling subtree is
-// walked belongs to a subtree at least as large: at most floor(log2 T) - 1 wait at once, and a caterpillar parks none.
-// work: the builder's list, reused from call to call
-int site_lnl_ops(int T, const int32_t *left, const int32_t *right, int root, std::vector<BatchOp> &work, std::vector<BatchOp> *ops) {
-	work.clear();
-	build_batch_ops(T, left, right, root, &work);
-	const int nops = T - 1;
-	std::vector<int> slot_of(2 * T - 1, BATCH_NONE), free_slots;
-	int slots = 0;
-	for (int i = 0; i < nops; i++) {
-		BatchOp op = work[i];
-		const auto source = [&](int child, int side) {
-			if (child < T) return (int)BATCH_NONE;
-			if (op.carry == side) return (int)BATCH_CARRY;
-			const int s = slot_of[child];
-			free_slots.push_back(s);
-			return s;
-		};
-		op.src = source(op.left, 1);
-		op.dst_left = source(op.right, 2);
-		if (i + 1 == nops) op.dst_right = BATCH_NONE;  // the root's
-		else if (work[i + 1].carry != 0) op.dst_right = BATCH_CARRY;
-		else {
-			if (free_slots.empty()) slot_of[op.node] = slots++;
-			else {
-				slot_of[op.node] = free_slots.back();
-				free_slots.pop_back();
-			}
-			op.dst_right = slot_of[op.node];
-		}
-		if (ops) ops->push_back(op);
-	}
-	return slots;
-}
+// (the post-order list with its slot words: site_lnl_ops, phyamd_tree_schedule.h)
 
 constexpr size_t SITE_LNL_MAX_REPLICATES = (size_t)1 << 19;  // replicates per chunk: gridDim.y of k_reweight_mfma is a sixteenth
 
@@ -1288,10 +1136,11 @@ int run_site_lnl(Shard *e, int flags, int32_t count, const int32_t *left, const 
 	std::vector<BatchOp> work, ops;
 	std::vector<int> slots(count);  // per item: the slots its list parks in
 	{
-		std::vector<int> parents, stack;
+		std::vector<int32_t> parents;
 		for (int32_t b = 0; b < count; b++) {  // every item, before anything is launched
 			const int32_t *l = left + (size_t)b * N, *r = right + (size_t)b * N;
-			if ((rc = validate_batch_tree(T, l, r, roots[b], b, parents, stack, name))) return rc;
+			const std::string err = validate_tree(TreeRef{T, l, r, roots[b]}, parents, name, b);
+			if (!err.empty()) return fail(PHYAMD_EINVAL, "%s", err.c_str());
 			slots[b] = site_lnl_ops(T, l, r, roots[b], work, nullptr);
 			prof.lower_slots = std::max(prof.lower_slots, (int32_t)slots[b]);
 		}

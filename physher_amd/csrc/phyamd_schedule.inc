@@ -1,4 +1,5 @@
-// phyamd_schedule.inc -- the level / tree-walk schedules and their storage
+// phyamd_schedule.inc -- the engine's side of its schedule (a Schedule and a StreamTables, built by phyamd_tree_schedule.h): device
+// storage, upload, readiness
 // (part of phyamd_engine.hip: one translation unit, internal linkage)
 
 int bind_device(Shard *e) {
@@ -10,843 +11,8 @@ size_t node_partial_doubles(const Shard *e) { return (size_t)e->C * e->S * (e->g
 size_t lower_slots(const Shard *e) { return e->d_lower.size() / node_partial_doubles(e); }  // node partials d_lower holds
 size_t upper_slots_held(const Shard *e) { return e->d_upper.size() / node_partial_doubles(e); }
 
-// Build the level schedule and the upper-slot assignment.
-// Chunked form of the pre-order walk (the launches with LDS park slots).  A workgroup's walk takes as long whatever shares its CU,
-// and the card holds 1280 of them: 15 625 workgroups (1e6 patterns) are 12.2 rounds, i.e. 13, and 1 563 (1e5 patterns) are two.
-// Cutting the op list into a top part and subtrees of at most 1 / WALK_CHUNKS of the ops that run as workgroups of their own
-// (second launch, blockIdx.y = subtree) makes the rounds short and many, so the unfilled last one costs a fraction of a walk.
-// A cut node's upper crosses from one workgroup to another through HBM; since the subtrees of one pattern block run at the same
-// time, no HBM slot is recycled here (every HBM park has its own), and LDS parks stay inside a chunk.
-// walk_chunk_ops: [top ops | subtree 1 | subtree 2 | ...], walk_chunk_off: offsets (chunks + 1 entries)
-constexpr int WALK_CHUNKS = 3;  // (3 measured best once a re-read beside a cut subtree cost the post-order pass its write rate)
-void build_walk_chunks(Shard *e) {
-	const std::vector<NodeOp> &src = e->walk_upper_ops;
-	const int n = (int)src.size(), N = e->N;
-	e->walk_chunk_ops = src;
-	e->walk_chunk_off.assign({0, n});
-	e->walk_chunk_slots = 0;
-	if (n == 0) return;
-	std::vector<int> opi(N, -1), size(n, 1);
-	for (int i = 0; i < n; i++) opi[src[i].parent] = i;
-	for (int i = n - 1; i >= 0; i--)
-		for (int ch : {src[i].left, src[i].right})
-			if (opi[ch] >= 0) size[i] += size[opi[ch]];
-	const int target = std::max(16, (n + WALK_CHUNKS - 1) / WALK_CHUNKS);
-	std::vector<char> top(n, 0), cut(n, 0);
-	if (n >= 32) {
-		std::vector<int> stack{0};
-		while (!stack.empty()) {
-			const int i = stack.back();
-			stack.pop_back();
-			top[i] = 1;
-			for (int ch : {src[i].left, src[i].right}) {
-				const int j = opi[ch];
-				if (j < 0) continue;
-				if (size[j] > target) stack.push_back(j);
-				else cut[j] = 1;
-			}
-		}
-	} else
-		std::fill(top.begin(), top.end(), 1);  // one chunk: the whole list (with the slot fields of this form)
-	// chunk of every op: 0 = the top part, m = the m-th cut subtree (in list order)
-	std::vector<int> chunk_of(n, 0);
-	int chunks = 1;
-	for (int j = 0; j < n; j++)
-		if (cut[j]) {
-			for (int i = j; i < j + size[j]; i++) chunk_of[i] = chunks;
-			chunks++;
-		}
-	// Where each child's upper goes: nowhere (carried inside a chunk), the LDS slot, an HBM slot private to the chunk (recycled
-	// inside it like the one-list walk does: a slot is free again once its reader has run), or an HBM slot that crosses chunks
-	// (unique).  Chunks of one pattern block run concurrently, so their private ranges are disjoint.
-	enum { NONE = 0, LDS = 1, INTERNAL = 2, CROSS = 3 };
-	std::vector<NodeOp> ops = src;
-	std::vector<int> kind(2 * n, NONE), local(2 * n, -1);          // [op * 2 + side]
-	std::vector<int> writer(n, -1);                                  // op j: index (op * 2 + side) of the entry that feeds it
-	std::vector<std::vector<int>> free_list(chunks);
-	std::vector<int> next_local(chunks, 0);
-	int cross = 0;
-	for (int i = 0; i < n; i++) {
-		const int k = chunk_of[i];
-		int freed = -1;
-		if (writer[i] >= 0 && kind[writer[i]] == INTERNAL) freed = local[writer[i]];
-		for (int side = 0; side < 2; side++) {
-			const int ch = side ? src[i].right : src[i].left, j = opi[ch];
-			if (j < 0) continue;
-			const int w = i * 2 + side;
-			writer[j] = w;
-			const bool carried = src[i].carry_out == side + 1;
-			const int lds_bit = side ? 4 : 2;
-			if (carried && !cut[j]) kind[w] = NONE;
-			else if (cut[j]) {  // a cut subtree (visited first or parked): its upper crosses to another workgroup through HBM
-				kind[w] = CROSS;
-				local[w] = cross++;
-			} else if (src[i].lds_park & lds_bit) kind[w] = LDS;
-			else {
-				kind[w] = INTERNAL;
-				std::vector<int> &fl = free_list[k];
-				if (!fl.empty()) {
-					local[w] = fl.back();
-					fl.pop_back();
-				} else
-					local[w] = next_local[k]++;
-			}
-		}
-		if (freed >= 0) free_list[k].push_back(freed);  // read by this op: reusable by the ops after it
-	}
-	std::vector<int> base(chunks + 1, 0);
-	for (int k = 0; k < chunks; k++) base[k + 1] = base[k] + next_local[k];
-	const int slots = base[chunks] + cross;
-	for (int i = 0; i < n; i++)
-		for (int side = 0; side < 2; side++) {
-			const int ch = side ? src[i].right : src[i].left, j = opi[ch];
-			if (j < 0) continue;
-			const int w = i * 2 + side, lds_bit = side ? 4 : 2;
-			int32_t &slot = side ? ops[i].upper_slot_right : ops[i].upper_slot_left;
-			if (kind[w] == NONE) slot = -1;
-			else if (kind[w] == LDS) {
-				slot = -1;
-				ops[j].upper_slot_parent = -1;  // (lds_park bit 0 of the reader is set in the source list)
-			} else {
-				slot = kind[w] == INTERNAL ? base[chunk_of[i]] + local[w] : base[chunks] + local[w];
-				ops[i].lds_park &= ~lds_bit;
-				if (kind[w] == CROSS) {  // (second LDS slot of the streamed walk: inside one workgroup only)
-					ops[i].lds_park &= ~(side ? 0x40 : 0x20);
-					ops[j].lds_park &= ~0x10;
-				}
-				ops[j].carry_in = 0;
-				ops[j].upper_slot_parent = slot;
-				ops[j].lds_park &= ~1;
-			}
-		}
-	e->walk_chunk_ops.clear();
-	e->walk_chunk_off.assign(1, 0);
-	for (int i = 0; i < n; i++)
-		if (top[i] && !cut[i]) e->walk_chunk_ops.push_back(ops[i]);
-	e->walk_chunk_off.push_back((int)e->walk_chunk_ops.size());
-	std::vector<int> cuts;
-	for (int j = 0; j < n; j++)
-		if (cut[j]) cuts.push_back(j);
-	std::stable_sort(cuts.begin(), cuts.end(), [&](int a, int b) { return size[a] > size[b]; });  // longest first: the launch's last workgroups are the short ones
-	for (int j : cuts) {
-		for (int i = j; i < j + size[j]; i++) e->walk_chunk_ops.push_back(ops[i]);
-		e->walk_chunk_off.push_back((int)e->walk_chunk_ops.size());
-	}
-	e->walk_chunk_slots = slots;
-	e->walk_upper_slots = std::max(e->walk_upper_slots, slots);
-}
-
-// The same for the post-order walk: cut subtrees first (second index of the launch = subtree), then the top part, which reads a cut
-// subtree's root like any stored child.  Carries follow the op actually in front of an op in its chunk, and an op next to a cut
-// gives up its parks (both slots) together with their writers' bits: a cut child was parked by another workgroup, and the other
-// child of such an op is either cut as well or the op in front of it in the top part, i.e. carried -- no park is lost that could
-// have been kept, and a park that survives has its writer and its reader in one chunk.
-// walk_lower_chunk_ops: [subtree 1 | subtree 2 | ... | top], offsets in walk_lower_chunk_off.
-void build_lower_walk_chunks(Shard *e) {
-	const std::vector<NodeOp> &src = e->walk_lower_ops;
-	const int n = (int)src.size(), N = e->N;
-	e->walk_lower_chunk_ops = src;
-	e->walk_lower_chunk_off.assign({0, n});
-	if (n == 0) return;
-	std::vector<int> opi(N, -1), size(n, 1);
-	for (int i = 0; i < n; i++) opi[src[i].parent] = i;
-	for (int i = 0; i < n; i++)  // post-order: children's ops come first
-		for (int ch : {src[i].left, src[i].right})
-			if (opi[ch] >= 0) size[i] += size[opi[ch]];
-	const int target = std::max(16, (n + WALK_CHUNKS - 1) / WALK_CHUNKS);
-	if (n < 32) return;
-	std::vector<char> cut(n, 0), in_cut(n, 0);
-	std::vector<int> stack{n - 1};  // the root's op is the last one
-	while (!stack.empty()) {
-		const int i = stack.back();
-		stack.pop_back();
-		for (int ch : {src[i].left, src[i].right}) {
-			const int j = opi[ch];
-			if (j < 0) continue;
-			if (size[j] > target) stack.push_back(j);
-			else cut[j] = 1;
-		}
-	}
-	std::vector<NodeOp> out;
-	std::vector<int> off{0}, cuts, at(n, -1);  // at: op of the source list -> its place in `out`
-	for (int j = 0; j < n; j++)
-		if (cut[j]) cuts.push_back(j);
-	std::stable_sort(cuts.begin(), cuts.end(), [&](int a, int b) { return size[a] > size[b]; });  // longest first
-	for (int j : cuts) {
-		for (int i = j - size[j] + 1; i <= j; i++) {
-			in_cut[i] = 1;
-			at[i] = (int)out.size();
-			out.push_back(src[i]);
-		}
-		out[off.back()].carry_in = 0;  // (a subtree's first op has two unstored children anyway)
-		off.push_back((int)out.size());
-	}
-	int prev = -1;  // node of the op in front, inside the top part
-	for (int i = 0; i < n; i++) {
-		if (in_cut[i]) continue;
-		NodeOp op = src[i];
-		const int jl = opi[op.left], jr = opi[op.right];
-		const bool next_to_cut = (jl >= 0 && cut[jl]) || (jr >= 0 && cut[jr]);
-		op.carry_in = prev >= 0 && prev == op.left ? 1 : prev >= 0 && prev == op.right ? 2 : 0;
-		if (next_to_cut) {
-			for (int side = 0; side < 2; side++) {
-				const int j = side ? jr : jl;
-				if (op.lds_park & (side ? 2 : 1)) out[at[j]].lds_park &= ~4;
-				if (op.lds_park & (side ? 0x20 : 0x10)) out[at[j]].lds_park &= ~0x40;
-			}
-			op.lds_park &= ~0x33;
-		}
-		at[i] = (int)out.size();
-		out.push_back(op);
-		prev = op.parent;
-	}
-	off.push_back((int)out.size());
-	e->walk_lower_chunk_ops = out;
-	e->walk_lower_chunk_off = off;
-}
-
-// Packed mask groups (phyamd_walk4s.inc, "Mask words"): the tips of one child of one op = one group = flag bit + one nibble per tip
-// slot (slots keep their positions: a DEEP child's halves sit at nibbles 0..2 and 3..5), appended to the current dword row while it
-// fits; a walk's groups are packed in its own op order.  rows: [row][8] entries for k_build_mask_stream.
-struct MaskPacker {
-	std::vector<int> &rows;
-	int row = -1, used = 32, entries = 8;
-	explicit MaskPacker(std::vector<int> &r) : rows(r), row((int)r.size() / 8 - 1) {}
-	void add(const int *tips, int &out_row, int &out_shift) {  // tips[6], -1 = unused slot
-		int span = 0, n = 0;
-		for (int j = 0; j < 6; j++)
-			if (tips[j] >= 0) {
-				span = j + 1;
-				n++;
-			}
-		const int bits = 1 + 4 * span;
-		if (used + bits > 32 || entries + n > 8) {
-			rows.insert(rows.end(), 8, -1);
-			row++;
-			used = 0;
-			entries = 0;
-		}
-		out_row = row;
-		out_shift = used;
-		for (int j = 0; j < 6; j++)
-			if (tips[j] >= 0) rows[(size_t)row * 8 + entries++] = tips[j] | (used + 1 + 4 * j) << 20 | used << 25;
-		used += bits;
-	}
-};
-
-// Flattened form of the chunked pre-order list for k_upper4_stream (phyamd_walk4s.inc): one 128-byte descriptor per op with its
-// DEEP children expanded, the mask groups (one per child that has tips: nibble j = the child's j-th tip, a DEEP child's halves at
-// nibbles 0..2 and 3..5; MaskPacker), what the NEXT op of the chunk wants prefetched, and each op's slab positions in walk order.
-// Every op's children are ordered so that the one whose upper the next op takes in registers is the LEFT one.
-void build_stream_ops(Shard *e) {
-	const int n = (int)e->walk_chunk_ops.size();
-	e->stream_ops.assign(n, StreamOp{});
-	e->stream_chunks.clear();
-	e->stream_row_entries.clear();
-	e->stream_site_tab.assign((size_t)n * 16, -1);
-	e->stream_op_tips.assign((size_t)n * 12, -1);
-	e->stream_op_deep.assign(n, 0);
-	e->stream_qnode.clear();
-	e->stream_words = 0;
-	if (n == 0) return;
-	std::vector<NodeOp> src = e->walk_chunk_ops;
-	std::vector<char> chunk_start(n + 1, 0);
-	for (int off : e->walk_chunk_off) chunk_start[off] = 1;
-	// In the chunked list the op in front may have produced this op's upper for an HBM slot (its carried child was cut away): a
-	// prefetch would read the slot before that op's store, and the value is in its registers anyway -- it is carried instead.
-	std::vector<char> from_prev(n, 0);
-	for (int i = 1; i < n; i++) {
-		const NodeOp &o = src[i];
-		NodeOp &pv = src[i - 1];
-		const bool proot = o.upper_slot_parent < 0 && !o.carry_in && !(o.lds_park & 1);
-		if (chunk_start[i] || proot || o.carry_in || (o.lds_park & 0x11) || o.upper_slot_parent < 0) continue;
-		if (pv.upper_slot_left == o.upper_slot_parent) {
-			pv.carry_out = 1;
-			pv.upper_slot_left = -1;
-			from_prev[i] = 1;
-		} else if (pv.upper_slot_right == o.upper_slot_parent) {
-			pv.carry_out = 2;
-			pv.upper_slot_right = -1;
-			from_prev[i] = 1;
-		}
-	}
-	for (NodeOp &o : src)
-		if (o.carry_out == 2) {  // the carried child becomes the left one
-			std::swap(o.left, o.right);
-			std::swap(o.core_left, o.core_right);
-			std::swap(o.kind_left, o.kind_right);
-			std::swap(o.lt0, o.rt0);
-			std::swap(o.lt1, o.rt1);
-			std::swap(o.lt2, o.rt2);
-			std::swap(o.linner, o.rinner);
-			std::swap(o.upper_slot_left, o.upper_slot_right);
-			o.lds_park = (o.lds_park & 0x11) | ((o.lds_park & 2) ? 4 : 0) | ((o.lds_park & 4) ? 2 : 0) | ((o.lds_park & 0x20) ? 0x40 : 0) | ((o.lds_park & 0x40) ? 0x20 : 0);
-			o.carry_out = 1;
-		}
-	auto half_kind = [](int k) { return k == CH_TIP ? HK_TIP : k == CH_CHERRY ? HK_CHERRY : HK_CHERRY_TIP; };
-	std::vector<int> first_word(n, -1), words(n, 0), same_row(n, 0), want_a(n, -1), want_b(n, -1), want_u(n, -1);
-	MaskPacker packer(e->stream_row_entries);
-	for (int i = 0; i < n; i++) {
-		const NodeOp &o = src[i];
-		StreamOp &s = e->stream_ops[i];
-		const bool proot = o.upper_slot_parent < 0 && !o.carry_in && !(o.lds_park & 1) && !from_prev[i];
-		int fl = (o.kind_left & 7) | (o.kind_right & 7) << 3;
-		fl |= ((o.lds_park & 2) ? 1 : (o.lds_park & 4) ? 2 : 0) << 12;
-		s.parent = o.parent;
-		s.slot_parent = o.upper_slot_parent;
-		s.slot_left = o.upper_slot_left;
-		s.slot_right = o.upper_slot_right;
-		const bool lds2_on = STREAM_PARK_SLOTS > 1;
-		if (lds2_on && (o.lds_park & 0x60)) {  // parked in the wave's second LDS slot instead of its HBM slot
-			fl |= ((o.lds_park & 0x20) ? 1 : 2) << 12 | 1 << 6;
-			((o.lds_park & 0x20) ? s.slot_left : s.slot_right) = -1;
-		}
-		s.lnode = o.left;
-		s.rnode = o.right;
-		for (int side = 0; side < 2; side++) {
-			const int kind = side ? o.kind_right : o.kind_left, node = side ? o.right : o.left;
-			int32_t *a = side ? s.ra : s.la;
-			for (int j = 0; j < 10; j++) a[j] = -1;
-			int tips[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
-			if (kind == CH_TIP) tips[0] = node;
-			else if (kind == CH_CHERRY || kind == CH_CHERRY_TIP) {
-				a[0] = side ? o.rt0 : o.lt0;
-				a[1] = side ? o.rt1 : o.lt1;
-				a[2] = side ? o.rt2 : o.lt2;
-				a[3] = side ? o.rinner : o.linner;
-				tips[0] = a[0];
-				tips[1] = a[1];
-				if (kind == CH_CHERRY_TIP) tips[2] = a[2];
-			} else if (kind == CH_DEEP) {
-				const DeepDesc &d = e->deep_host[node];
-				e->stream_op_deep[i] |= 1 << side;
-				for (int h = 0; h < 2; h++) {
-					const int hk = h ? d.kind_right : d.kind_left;
-					int32_t *q = a + 5 * h;
-					q[0] = h ? d.right : d.left;
-					q[1] = h ? d.rt0 : d.lt0;
-					q[2] = h ? d.rt1 : d.lt1;
-					q[3] = h ? d.rt2 : d.lt2;
-					q[4] = h ? d.rinner : d.linner;
-					fl |= half_kind(hk) << (16 + 4 * side + 2 * h);
-					if (hk == CH_TIP) tips[3 * h] = q[0];
-					else {
-						tips[3 * h] = q[1];
-						tips[3 * h + 1] = q[2];
-						if (hk == CH_CHERRY_TIP) tips[3 * h + 2] = q[3];
-					}
-				}
-			}
-			for (int j = 0; j < 6; j++) e->stream_op_tips[(size_t)i * 12 + 6 * side + j] = tips[j];
-			if (kind != CH_CORE) {
-				int row, shift;
-				packer.add(tips, row, shift);
-				if (words[i] == 0) first_word[i] = row;
-				else same_row[i] = row == first_word[i];
-				s.wsh |= shift << (5 * words[i]);
-				words[i]++;
-			}
-		}
-		// where the parent's upper comes from, and what the two register sets must hold when this op starts
-		int usrc;
-		if (o.kind_left == CH_CORE) want_a[i] = o.core_left;
-		if (o.kind_right == CH_CORE) want_b[i] = o.core_right;
-		if (proot) usrc = SU_ROOT;
-		else if (o.carry_in || from_prev[i]) usrc = SU_CARRY;
-		else if (o.lds_park & 1) usrc = SU_LDS;
-		else if (lds2_on && (o.lds_park & 0x10)) {
-			usrc = SU_LDS;
-			fl |= 1 << 7;
-		} else {
-			usrc = SU_U;
-			want_u[i] = o.upper_slot_parent;
-		}
-		fl |= usrc << 9;
-		s.flags = fl;
-		// slab positions, in the order the walk produces them; entry j belongs to result lane class j (k_upper4_stream: cid)
-		const int sites[10] = {o.left, o.kind_left >= CH_CHERRY ? o.lt0 : -1, o.kind_left >= CH_CHERRY ? o.lt1 : -1, o.kind_left == CH_CHERRY_TIP ? o.linner : -1,
-		                       o.right, o.kind_right >= CH_CHERRY ? o.rt0 : -1, o.kind_right >= CH_CHERRY ? o.rt1 : -1, o.kind_right == CH_CHERRY_TIP ? o.rinner : -1,
-		                       o.kind_left == CH_CHERRY_TIP ? o.lt2 : -1, o.kind_right == CH_CHERRY_TIP ? o.rt2 : -1};
-		for (int j = 0; j < 10; j++)
-			if (sites[j] >= 0) {
-				e->stream_site_tab[(size_t)i * 16 + j] = 8 * (int)e->stream_qnode.size();
-				e->stream_qnode.push_back(sites[j]);
-			}
-	}
-	e->stream_R = (int)e->stream_qnode.size();
-	e->stream_words = (int)e->stream_row_entries.size() / 8;  // (build_lower_stream_ops appends the post-order walk's rows)
-	const int chunks = (int)e->walk_chunk_off.size() - 1;
-	for (int k = 0; k < chunks; k++) {
-		const int b = e->walk_chunk_off[k], en = e->walk_chunk_off[k + 1];
-		StreamChunk ch{-1, 0, -1, -1, -1, 0, {0, 0}};
-		if (b < en) ch = StreamChunk{first_word[b], words[b], want_a[b], want_b[b], want_u[b], same_row[b], {0, 0}};
-		e->stream_chunks.push_back(ch);
-		for (int i = b; i < en; i++) {
-			StreamOp &s = e->stream_ops[i];
-			const bool last = i + 1 == en;
-			s.nx_mask_word = last ? -1 : first_word[i + 1];
-			s.flags |= (last ? 0 : words[i + 1]) << 14;
-			s.flags |= (!last && src[i + 1].kind_right != CH_CORE ? 1 : 0) << 24;  // the right child's tip slots are the block's second piece
-			s.flags |= (!last && same_row[i + 1] ? 1 : 0) << 25;
-			s.nx_a = last ? -1 : want_a[i + 1];
-			s.nx_b = last ? -1 : want_b[i + 1];
-			s.nx_u = last ? -1 : want_u[i + 1];
-		}
-	}
-	// the rows the kernel reads: matrices by byte offset (SX::M), every array the op touches by the byte offset of its plane of
-	// category 0 (the kernel adds c * plane once per wave), the next op's mask words by the byte offset of their first row
-	e->stream_P = e->P;
-	e->stream_mstride = (size_t)e->nblk_walk_upper * e->G * WAVE;
-	const int64_t plane_bytes = (int64_t)e->P * 4 * 8, array_bytes = plane_bytes * e->C, row_bytes = (int64_t)e->stream_mstride * 4;
-	e->stream_desc.assign(n, StreamDesc{});
-	for (int i = 0; i < n; i++) {
-		const StreamOp &s = e->stream_ops[i];
-		StreamDesc &d = e->stream_desc[i];
-		auto moff = [&](int32_t node) { return node >= 0 ? node * e->C * 128 : 0; };
-		const int kinds[2] = {s.flags & 7, (s.flags >> 3) & 7};
-		d.flags = s.flags;
-		d.parent = moff(s.parent);
-		d.lnode = moff(s.lnode);
-		d.rnode = moff(s.rnode);
-		for (int side = 0; side < 2; side++) {
-			const int32_t *a = side ? s.ra : s.la;
-			int32_t *m = side ? d.rm : d.lm;
-			for (int j = 0; j < 5; j++) m[j] = 0;
-			if (kinds[side] == CH_DEEP) {
-				m[0] = moff(a[0]);
-				m[1] = moff(a[4]);
-				m[2] = moff(a[5]);
-				m[3] = moff(a[9]);
-			} else if (kinds[side] == CH_CHERRY_TIP)
-				m[4] = moff(a[3]);
-		}
-		d.nx_words = s.nx_mask_word >= 0 ? (int64_t)s.nx_mask_word * row_bytes : 0;
-		d.nx_a = s.nx_a >= 0 ? (int64_t)s.nx_a * array_bytes : 0;
-		d.nx_b = s.nx_b >= 0 ? (int64_t)s.nx_b * array_bytes : 0;
-		d.nx_u = s.nx_u >= 0 ? (int64_t)s.nx_u * array_bytes : 0;
-		d.st_left = s.slot_left >= 0 ? (int64_t)s.slot_left * array_bytes : 0;
-		d.st_right = s.slot_right >= 0 ? (int64_t)s.slot_right * array_bytes : 0;
-		d.wsh = s.wsh;
-		d.flags |= (s.nx_a >= 0 ? 1 << 26 : 0) | (s.nx_b >= 0 ? 1 << 27 : 0) | (s.nx_u >= 0 ? 1 << 28 : 0) | (s.slot_left >= 0 ? 1 << 29 : 0) | (s.slot_right >= 0 ? 1 << 30 : 0);
-	}
-}
-
-// Descriptors of k_lower4_stream (phyamd_walk4s.inc): the chunked post-order list, every op taking its children (in the order
-// of the pre-order op of the same node: that is the order of its table block and of its mask groups' nibbles) and its table block
-// from the pre-order stream tables; its mask groups are packed again in post-order (rows appended to the pre-order walk's);
-// addresses multiplied out as in StreamDesc.  Call after build_stream_ops.
-void build_lower_stream_ops(Shard *e) {
-	const int n = (int)e->walk_lower_chunk_ops.size(), ns = (int)e->stream_ops.size();
-	e->lstream_desc.clear();
-	e->lstream_chunks.clear();
-	if (n == 0 || ns == 0) return;
-	std::vector<int> sop(e->N, -1);
-	for (int i = 0; i < ns; i++) sop[e->walk_chunk_ops[i].parent] = i;  // (stream_ops follow walk_chunk_ops one to one)
-	for (const NodeOp &o : e->walk_lower_chunk_ops)
-		if (sop[o.parent] < 0) return;  // every stored node has a pre-order op; without one the streamed post-order walk is not used
-	const int64_t plane_bytes = (int64_t)e->P * 4 * 8, array_bytes = plane_bytes * e->C, row_bytes = (int64_t)e->stream_mstride * 4;
-	auto moff = [&](int32_t node) { return node >= 0 ? node * e->C * 128 : 0; };
-	e->lstream_desc.assign(n, LowerDesc{});
-	std::vector<int> pieces(n, 0), first_word(n, 0), last_word(n, 0), words(n, 0);
-	MaskPacker packer(e->stream_row_entries);
-	for (int i = 0; i < n; i++) {
-		const NodeOp &o = e->walk_lower_chunk_ops[i];
-		const StreamOp &u = e->stream_ops[sop[o.parent]];
-		LowerDesc &d = e->lstream_desc[i];
-		const int kinds[2] = {u.flags & 7, (u.flags >> 3) & 7};
-		for (int side = 0; side < 2; side++)
-			if (kinds[side] != CH_CORE) {
-				int row, shift;
-				packer.add(&e->stream_op_tips[(size_t)sop[o.parent] * 12 + 6 * side], row, shift);
-				if (words[i] == 0) first_word[i] = row;
-				last_word[i] = row;
-				d.wsh |= shift << (5 * words[i]) | (row & 3) << (10 + 2 * words[i]);  // shift 0-4 / 5-9, ring slot 10-11 / 12-13
-				words[i]++;
-			}
-		int fl = (u.flags & 0x3F) | (u.flags & 0x00FF0000);  // kinds and half kinds
-		d.lnode = moff(u.lnode);
-		d.rnode = moff(u.rnode);
-		d.self = o.parent == e->root ? 0 : moff(o.parent);
-		d.store = (int64_t)o.core_parent * array_bytes;
-		d.ls_store = (int64_t)o.core_parent * e->P * 8;
-		for (int side = 0; side < 2; side++) {
-			const int32_t *a = side ? u.ra : u.la;
-			int32_t *m = side ? d.rm : d.lm;
-			for (int j = 0; j < 5; j++) m[j] = 0;
-			if (kinds[side] == CH_DEEP) {
-				m[0] = moff(a[0]);
-				m[1] = moff(a[4]);
-				m[2] = moff(a[5]);
-				m[3] = moff(a[9]);
-			} else if (kinds[side] == CH_CHERRY_TIP)
-				m[4] = moff(a[3]);
-			if (kinds[side] != CH_CORE) continue;
-			// where a stored child comes from: the previous op's registers, one of the two parked partials, or memory
-			const int ch = side ? u.rnode : u.lnode;
-			const bool is_left = ch == o.left;  // of the post-order op (the pre-order op may have swapped its children)
-			int src = 0;
-			if (o.carry_in == (is_left ? 1 : 2)) src = 1;
-			else if (o.lds_park & (is_left ? 1 : 2)) src = 2;
-			else if (o.lds_park & (is_left ? 0x10 : 0x20)) src = 3;
-			if (src == 0 || src == 3) {  // (3: for the instantiations that have one slot, lstream_park_slots; the others fetch nothing)
-				(side ? d.mem_r : d.mem_l) = (int64_t)e->core_index[ch] * array_bytes;
-				(side ? d.ls_r : d.ls_l) = (int64_t)e->core_index[ch] * e->P * 8;
-			}
-			fl |= src << (6 + 2 * side);
-		}
-		if (o.lds_park & 4) fl |= 1 << 10;
-		if (o.lds_park & 0x40) fl |= 1 << 26;
-		pieces[i] = (kinds[0] != CH_CORE ? 1 : 0) | (kinds[1] != CH_CORE ? 2 : 0);
-		d.flags = fl;
-	}
-	const int chunks = (int)e->walk_lower_chunk_off.size() - 1;
-	for (int k = 0; k < chunks; k++) {
-		const int b = e->walk_lower_chunk_off[k], en = e->walk_lower_chunk_off[k + 1];
-		// mask rows wait in a ring of four LDS slots (slot = row & 3) and are requested once: by the op in front of the first op that
-		// reads them (the rows of a chunk's groups are consecutive, an op reads at most two)
-		LowerChunk ch{0, 0, 0, 0, 0};
-		int have = -1;  // the highest row requested so far
-		auto fresh_rows = [&](int i, int &first) {  // rows op i reads that have not been requested yet
-			if (words[i] == 0) return 0;
-			first = have < 0 ? first_word[i] : std::max(first_word[i], have + 1);
-			const int count = last_word[i] - first + 1;
-			have = std::max(have, last_word[i]);
-			return std::max(0, count);
-		};
-		if (b < en) {
-			const int si = sop[e->walk_lower_chunk_ops[b].parent];
-			int first = 0;
-			const int count = fresh_rows(b, first);
-			ch = LowerChunk{si, pieces[b], count, first & 3, (int64_t)first * row_bytes};
-		}
-		e->lstream_chunks.push_back(ch);
-		for (int i = b; i < en; i++) {
-			LowerDesc &d = e->lstream_desc[i];
-			const bool last = i + 1 == en;
-			const int sn = last ? 0 : sop[e->walk_lower_chunk_ops[i + 1].parent];
-			d.nx_block = sn;
-			int first = 0;
-			const int count = last ? 0 : fresh_rows(i + 1, first);
-			d.nx_words = (int64_t)first * row_bytes;
-			d.flags |= count << 14;
-			d.flags |= (first & 3) << 12;
-			d.flags |= (last ? 0 : ((pieces[i + 1] & 2) ? 1 : 0)) << 24;
-			d.flags |= (last ? 0 : (pieces[i + 1] & 1)) << 25;
-		}
-	}
-	e->stream_words = (int)e->stream_row_entries.size() / 8;
-}
-
-int build_schedule(Shard *e) {
-	const int N = e->N, T = e->T;
-	e->parent.assign(N, -1);
-	std::vector<int> seen(N, 0);
-	for (int n = 0; n < N; n++) {
-		const int l = e->left[n], r = e->right[n];
-		if (n < T) {
-			if (l != -1 || r != -1) return fail(PHYAMD_EINVAL, "node %d is a tip (id < tip_count) but has children", n);
-			continue;
-		}
-		if (l < 0 || r < 0 || l >= N || r >= N || l == r) return fail(PHYAMD_EINVAL, "internal node %d has invalid children (%d, %d)", n, l, r);
-		if (++seen[l] > 1 || ++seen[r] > 1) return fail(PHYAMD_EINVAL, "node %d or %d has two parents", l, r);
-		e->parent[l] = n;
-		e->parent[r] = n;
-	}
-	if (e->root < T || e->root >= N || e->parent[e->root] != -1) return fail(PHYAMD_EINVAL, "root %d is not a parentless internal node", e->root);
-	// depth (root = 0) by a stack walk; also detects unreachable nodes / cycles
-	std::vector<int> depth(N, -1), order;
-	order.reserve(N);
-	std::vector<int> stack{e->root};
-	depth[e->root] = 0;
-	while (!stack.empty()) {
-		const int n = stack.back();
-		stack.pop_back();
-		order.push_back(n);
-		if (n >= T) {
-			for (int ch : {e->left[n], e->right[n]}) {
-				depth[ch] = depth[n] + 1;
-				stack.push_back(ch);
-			}
-		}
-	}
-	if ((int)order.size() != N) return fail(PHYAMD_EINVAL, "topology is not a single binary tree over all %d nodes", N);
-	// Fringe classification (4-state, not keep_partials): cherries (tip, tip) and cherry + tip nodes are fused
-	// into their parent's work and never stored.  Everything else that is internal is a "core" node with an array in HBM.
-	// (rescaled evaluations keep the fusion: fringe nodes never reach the rescaling threshold themselves)
-	// 20 states: cherries only, and only in plain evaluations -- the MFMA kernels rebuild a cherry's partial from two columns of
-	// LDS-resident matrix images (six images of 5 KB fit; 61-state images are 33 KB each) and push its upper down in registers;
-	// rescaled evaluations keep every node stored (their per-op scratch rows are indexed by the level's ops).
-	const bool fuse = e->fusion_enabled && !e->keep_partials && (!e->generic || (e->S == 20 && !e->scaling_on && e->generic_fusion));
-	e->fused = fuse;
-	std::vector<int> kind(N, CH_CORE);
-	for (int n = 0; n < T; n++) kind[n] = CH_TIP;
-	if (fuse) {
-		for (int i = N - 1; i >= 0; i--) {  // children before parents
-			const int n = order[i];
-			if (n < T || n == e->root) continue;
-			const int l = e->left[n], r = e->right[n];
-			if (l < T && r < T) kind[n] = CH_CHERRY;
-			else if (e->generic) continue;
-			else if ((l < T && kind[r] == CH_CHERRY) || (r < T && kind[l] == CH_CHERRY)) kind[n] = CH_CHERRY_TIP;
-			else if (kind[l] != CH_CORE && kind[l] != CH_DEEP && kind[r] != CH_CORE && kind[r] != CH_DEEP)
-				kind[n] = CH_DEEP;  // both children are tips or fringe: 4-6 tips below, rebuilt in registers wherever its partial is needed
-		}
-	}
-	e->node_kind = kind;
-	// stored lower arrays: core nodes in id order
-	e->core_index.assign(N, -1);
-	e->core_count = 0;
-	for (int n = T; n < N; n++)
-		if (kind[n] == CH_CORE) e->core_index[n] = e->core_count++;
-	auto describe = [&](int ch, int32_t &k, int32_t &core, int32_t &t0, int32_t &t1, int32_t &t2, int32_t &inner) {
-		k = kind[ch];
-		core = e->core_index[ch];
-		t0 = t1 = t2 = inner = -1;
-		if (k == CH_CHERRY) {
-			t0 = e->left[ch];
-			t1 = e->right[ch];
-		} else if (k == CH_CHERRY_TIP) {
-			const int l = e->left[ch], r = e->right[ch];
-			inner = l < T ? r : l;
-			t2 = l < T ? l : r;
-			t0 = e->left[inner];
-			t1 = e->right[inner];
-		}
-	};
-	e->deep_host.assign(N, DeepDesc{});
-	e->deep_count = 0;
-	for (int n = T; n < N; n++)
-		if (kind[n] == CH_DEEP) {
-			DeepDesc &d = e->deep_host[n];
-			int32_t core_unused;
-			d.left = e->left[n];
-			d.right = e->right[n];
-			describe(d.left, d.kind_left, core_unused, d.lt0, d.lt1, d.lt2, d.linner);
-			describe(d.right, d.kind_right, core_unused, d.rt0, d.rt1, d.rt2, d.rinner);
-			e->deep_count++;
-		}
-	auto make_op = [&](int n) {
-		NodeOp op{};
-		op.parent = n;
-		op.left = e->left[n];
-		op.right = e->right[n];
-		op.upper_slot_parent = op.upper_slot_left = op.upper_slot_right = -1;
-		op.core_parent = e->core_index[n];
-		describe(op.left, op.kind_left, op.core_left, op.lt0, op.lt1, op.lt2, op.linner);
-		describe(op.right, op.kind_right, op.core_right, op.rt0, op.rt1, op.rt2, op.rinner);
-		return op;
-	};
-	// height over the core tree (tips and fused nodes = 0), children before parents: reverse of the pre-order list
-	std::vector<int> height(N, 0);
-	int H = 0, Dmax = 0;
-	for (int i = N - 1; i >= 0; i--) {
-		const int n = order[i];
-		if (kind[n] == CH_CORE) height[n] = 1 + std::max(height[e->left[n]], height[e->right[n]]);
-		H = std::max(H, height[n]);
-		Dmax = std::max(Dmax, depth[n]);
-	}
-	// lower levels: core nodes by height 1..H (the root has the largest height and is alone on its level)
-	e->lower_ops.clear();
-	e->lower_level_off.assign(1, 0);
-	for (int h = 1; h <= H; h++) {
-		for (int n = T; n < N; n++)
-			if (kind[n] == CH_CORE && height[n] == h) e->lower_ops.push_back(make_op(n));
-		e->lower_level_off.push_back((int)e->lower_ops.size());
-	}
-	// upper levels: core parents by depth 0..Dmax-1.  Upper partials of depth-d nodes are only read while
-	// depth d+1 is produced, so slots are recycled two levels later (keep_partials: slot = own index).
-	e->upper_ops.clear();
-	e->upper_level_off.assign(1, 0);
-	e->upper_slot.assign(N, -1);
-	std::vector<int> free_slots;
-	int next_slot = 0;
-	std::vector<std::vector<int>> slots_of_depth(Dmax + 2);
-	for (int d = 0; d < Dmax; d++) {
-		if (!e->keep_partials && d >= 2) {  // uppers of depth d-1 were consumed while producing depth d
-			for (int s : slots_of_depth[d - 1]) free_slots.push_back(s);
-			slots_of_depth[d - 1].clear();
-		}
-		for (int n = T; n < N; n++) {
-			if (depth[n] != d || (kind[n] != CH_CORE && kind[n] != CH_DEEP)) continue;
-			NodeOp op = make_op(n);
-			op.upper_slot_parent = n == e->root ? -1 : e->upper_slot[n];
-			for (int side = 0; side < 2; side++) {
-				const int ch = side ? e->right[n] : e->left[n];
-				if (kind[ch] != CH_CORE && kind[ch] != CH_DEEP && !e->keep_partials) continue;  // uppers of tips and fringe nodes stay in registers
-				int s;
-				if (e->keep_partials) s = ch;
-				else if (!free_slots.empty()) {
-					s = free_slots.back();
-					free_slots.pop_back();
-				} else
-					s = next_slot++;
-				e->upper_slot[ch] = s;
-				slots_of_depth[d + 1].push_back(s);
-				(side ? op.upper_slot_right : op.upper_slot_left) = s;
-			}
-			e->upper_ops.push_back(op);
-		}
-		e->upper_level_off.push_back((int)e->upper_ops.size());
-	}
-	e->upper_slots = e->keep_partials ? N : next_slot;
-
-	// Depth-first op orders for the tree-walk kernels (see k_lower4_walk).  csize = core ops in the subtree.
-	e->walking = e->walk_enabled && !e->generic && !e->keep_partials;
-	// 20 states, plain evaluations: the post-order list drives k_lower_gen_walk (phyamd_genwalk.inc)
-	e->gen_walking = e->walk_enabled && e->generic && e->S == 20 && !e->keep_partials && !e->scaling_on;
-	e->walk_lower_ops.clear();
-	e->walk_upper_ops.clear();
-	e->walk_upper_slots = 0;
-	if (e->walking || e->gen_walking) {
-		std::vector<int> csize(N, 0), usize(N, 0);  // stored nodes / pre-order ops (stored + DEEP) in the subtree
-		for (int i = N - 1; i >= 0; i--) {
-			const int n = order[i];
-			if (kind[n] == CH_CORE) csize[n] = 1 + csize[e->left[n]] + csize[e->right[n]];
-			if (kind[n] == CH_CORE || kind[n] == CH_DEEP) usize[n] = 1 + usize[e->left[n]] + usize[e->right[n]];
-		}
-		// post-order, larger core subtree first: the op before a node is its second (smaller) core child, or its only one
-		struct Frame {
-			int node, stage;
-		};
-		// two_core[n]: the subtree of n holds a node with two stored children, i.e. walking it re-reads a stored partial
-		// lparks[n]: the largest number of stored partials that wait at one time while the subtree of n is walked (the first-walked
-		// child of a node with two stored children waits while the second one's subtree is walked); two_core[n] = lparks[n] > 0
-		std::vector<uint8_t> two_core(N, 0);
-		std::vector<int> lparks(N, 0);
-		for (int i = N - 1; i >= 0; i--) {
-			const int n = order[i];
-			if (kind[n] != CH_CORE) continue;
-			const int l = e->left[n], r = e->right[n];
-			const bool lo = kind[l] == CH_CORE, ro = kind[r] == CH_CORE;
-			two_core[n] = (lo && ro) || (lo && two_core[l]) || (ro && two_core[r]);
-			if (lo && ro) lparks[n] = csize[l] >= csize[r] ? std::max(lparks[l], 1 + lparks[r]) : std::max(lparks[r], 1 + lparks[l]);
-			else lparks[n] = lo ? lparks[l] : ro ? lparks[r] : 0;
-		}
-		std::vector<int> lower_op_of(N, -1);
-		std::vector<Frame> st{{e->root, 0}};
-		while (!st.empty()) {
-			Frame &f = st.back();
-			const int n = f.node, l = e->left[n], r = e->right[n];
-			const int first = csize[l] >= csize[r] ? l : r, second = first == l ? r : l;
-			if (f.stage == 0) {
-				f.stage = 1;
-				if (kind[first] == CH_CORE) st.push_back({first, 0});
-			} else if (f.stage == 1) {
-				f.stage = 2;
-				if (kind[second] == CH_CORE) st.push_back({second, 0});
-			} else {
-				NodeOp op = make_op(n);
-				op.carry_in = 0;
-				if (!e->walk_lower_ops.empty()) {
-					const int prev = e->walk_lower_ops.back().parent;
-					if (prev == l) op.carry_in = 1;
-					else if (prev == r) op.carry_in = 2;
-				}
-				// Both children stored: the second one arrives in registers, the first was written a subtree ago.  If walking the
-				// second's subtree re-reads nothing itself, the first can also wait in the wave's LDS slot (it is still stored for
-				// the pre-order pass): bit 2 on the child's op = keep a copy in LDS, bit 0 / 1 here = left / right child from LDS.
-				// Second tier (the streamed walk only; the pre-order walk's in_lds2 rule): if every wait inside the second's subtree is
-				// of that kind, i.e. at most one of them is held at a time, the first waits in the wave's second slot: bit 0x40 on the
-				// child's op = keep a copy there, bit 0x10 / 0x20 here = left / right child from it.  No slot then ever holds two values.
-				op.lds_park = 0;
-				if (kind[first] == CH_CORE && kind[second] == CH_CORE && lower_op_of[first] >= 0) {
-					if (!two_core[second]) {
-						e->walk_lower_ops[lower_op_of[first]].lds_park |= 4;
-						op.lds_park |= first == l ? 1 : 2;
-					} else if (e->lower_park2_on && lparks[second] == 1) {
-						e->walk_lower_ops[lower_op_of[first]].lds_park |= 0x40;
-						op.lds_park |= first == l ? 0x10 : 0x20;
-					}
-				}
-				lower_op_of[n] = (int)e->walk_lower_ops.size();
-				e->walk_lower_ops.push_back(op);
-				st.pop_back();
-			}
-		}
-		// pre-order, SMALLER core subtree first: the first-visited core child takes its upper in registers (never stored);
-		// the other child's upper waits in a slot while the small subtree is walked (nesting depth <= log2 of the core count)
-		// parks[n]: the subtree of n holds an op with two op-children, i.e. walking it parks an upper
-		// height[n]: the largest number of uppers parked at one time while the subtree of n is walked
-		std::vector<uint8_t> parks(N, 0), in_lds(N, 0), in_lds2(N, 0);
-		std::vector<int> height(N, 0);
-		for (int i = N - 1; i >= 0; i--) {
-			const int n = order[i];
-			if (kind[n] != CH_CORE && kind[n] != CH_DEEP) continue;
-			const int l = e->left[n], r = e->right[n];
-			const bool lo = kind[l] == CH_CORE || kind[l] == CH_DEEP, ro = kind[r] == CH_CORE || kind[r] == CH_DEEP;
-			parks[n] = (lo && ro) || (lo && parks[l]) || (ro && parks[r]);
-			if (lo && ro) {
-				const int first = usize[l] <= usize[r] ? l : r, second = first == l ? r : l;
-				height[n] = std::max(1 + height[first], height[second]);
-			} else
-				height[n] = lo ? height[l] : ro ? height[r] : 0;
-		}
-		std::vector<int> free_w;
-		int next_w = 0;
-		std::vector<int> slot_of(N, -1);
-		std::vector<int> stack2{e->root};
-		int carried_node = -1;  // node whose upper the previous op carried out
-		while (!stack2.empty()) {
-			const int n = stack2.back();
-			stack2.pop_back();
-			NodeOp op = make_op(n);
-			op.carry_in = (n != e->root && carried_node == n) ? 1 : 0;
-			op.upper_slot_parent = -1;
-			op.lds_park = 0;
-			if (n != e->root && !op.carry_in) {
-				op.upper_slot_parent = slot_of[n];
-				free_w.push_back(slot_of[n]);  // read by this op; reusable by ops after it
-				if (in_lds[n]) op.lds_park |= 1;
-				if (in_lds2[n]) op.lds_park |= 0x10;
-			}
-			const int l = e->left[n], r = e->right[n];
-			const bool lc = kind[l] == CH_CORE || kind[l] == CH_DEEP, rc2 = kind[r] == CH_CORE || kind[r] == CH_DEEP;  // children with ops of their own
-			int first = -1, second = -1;
-			if (lc && rc2) {
-				first = usize[l] <= usize[r] ? l : r;
-				second = first == l ? r : l;
-			} else if (lc || rc2)
-				first = lc ? l : r;
-			op.carry_out = first < 0 ? 0 : (first == l ? 1 : 2);
-			carried_node = first;
-			if (second >= 0) {
-				int sl;
-				// a slot freed by THIS op (its own parent upper) must not be reused for its output: lanes of other waves may
-				// still be reading it -- not an issue within a thread, but keep it simple and safe: take another one
-				if (free_w.size() > 1 || (free_w.size() == 1 && free_w.back() != op.upper_slot_parent)) {
-					size_t pick = free_w.size() - 1;
-					if (free_w[pick] == op.upper_slot_parent) pick--;
-					sl = free_w[pick];
-					free_w.erase(free_w.begin() + pick);
-				} else
-					sl = next_w++;
-				slot_of[second] = sl;
-				(second == l ? op.upper_slot_left : op.upper_slot_right) = sl;
-				if (!parks[first]) {  // nothing else is parked while `second` waits: one LDS slot per wave is enough
-					in_lds[second] = 1;
-					op.lds_park |= second == l ? 2 : 4;
-				} else if (height[first] == 1) {
-					// one park at a time inside the wait (leaf parks, all of them in LDS slot 0): the streamed walk keeps this one in
-					// a second LDS slot (bits 0x20 / 0x40 store, 0x10 read); the other kernels park it in the HBM slot assigned above
-					in_lds2[second] = 1;
-					op.lds_park |= second == l ? 0x20 : 0x40;
-				}
-				stack2.push_back(second);
-			}
-			if (first >= 0) stack2.push_back(first);  // visited next
-			e->walk_upper_ops.push_back(op);
-		}
-		e->walk_upper_slots = next_w;
-		if (e->walking) {
-			build_walk_chunks(e);
-			build_lower_walk_chunks(e);
-		}
-	}
-	return PHYAMD_OK;
-}
-
 int ensure_lower_storage(Shard *e) {
-	const size_t need = (size_t)std::max(1, e->core_count) * (e->two_slots ? 2 : 1);
+	const size_t need = (size_t)std::max(1, e->sched.core_count) * (e->two_slots ? 2 : 1);
 	if (lower_slots(e) >= need) return PHYAMD_OK;
 	e->d_lower.release();
 	e->d_lscale.release();  // (sized by d_lower: ensure_scaling_storage)
@@ -854,12 +20,12 @@ int ensure_lower_storage(Shard *e) {
 }
 
 // after slots moved (store / restore): the ops carry slot indices
-void refresh_op_cores(Shard *e) {
-	for (std::vector<NodeOp> *ops : {&e->lower_ops, &e->upper_ops, &e->walk_lower_ops, &e->walk_upper_ops, &e->walk_chunk_ops, &e->walk_lower_chunk_ops})
+void refresh_op_cores(Schedule &s) {
+	for (std::vector<NodeOp> *ops : {&s.lower_ops, &s.upper_ops, &s.walk_lower_ops, &s.walk_upper_ops, &s.walk_chunk_ops, &s.walk_lower_chunk_ops})
 		for (NodeOp &op : *ops) {
-			op.core_parent = e->core_index[op.parent];
-			op.core_left = e->core_index[op.left];
-			op.core_right = e->core_index[op.right];
+			op.core_parent = s.core_index[op.parent];
+			op.core_left = s.core_index[op.left];
+			op.core_right = s.core_index[op.right];
 		}
 }
 
@@ -867,41 +33,40 @@ int upload_schedule(Shard *e) {
 	// op tables are a few KB: allocated once at the maximum size (N - T ops each)
 	int rc;
 	if ((rc = e->d_lower_ops.ensure(e->N)) || (rc = e->d_upper_ops.ensure(e->N))) return rc;
-	HIP_TRY(hipMemcpyAsync(e->d_lower_ops, e->lower_ops.data(), e->lower_ops.size() * sizeof(NodeOp), hipMemcpyHostToDevice, e->stream));
-	HIP_TRY(hipMemcpyAsync(e->d_upper_ops, e->upper_ops.data(), e->upper_ops.size() * sizeof(NodeOp), hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipMemcpyAsync(e->d_lower_ops, e->sched.lower_ops.data(), e->sched.lower_ops.size() * sizeof(NodeOp), hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipMemcpyAsync(e->d_upper_ops, e->sched.upper_ops.data(), e->sched.upper_ops.size() * sizeof(NodeOp), hipMemcpyHostToDevice, e->stream));
 	static_assert(sizeof(DeepDesc) == 6 * sizeof(double), "DeepDesc is laid out in the tail of the tip-message table");
 	if (!e->generic)
-		HIP_TRY(hipMemcpyAsync(e->d_tiptab + (size_t)e->T * e->C * 64, e->deep_host.data(), e->deep_host.size() * sizeof(DeepDesc), hipMemcpyHostToDevice,
+		HIP_TRY(hipMemcpyAsync(e->d_tiptab + (size_t)e->T * e->C * 64, e->sched.deep_host.data(), e->sched.deep_host.size() * sizeof(DeepDesc), hipMemcpyHostToDevice,
 		                       e->stream));
-	if (e->walking || e->gen_walking) {
+	if (e->sched.walking || e->sched.gen_walking) {
 		if ((rc = e->d_walk_lower_ops.ensure(e->N)) || (rc = e->d_walk_upper_ops.ensure(e->N))) return rc;
-		HIP_TRY(hipMemcpyAsync(e->d_walk_lower_ops, e->walk_lower_ops.data(), e->walk_lower_ops.size() * sizeof(NodeOp), hipMemcpyHostToDevice, e->stream));
-		HIP_TRY(hipMemcpyAsync(e->d_walk_upper_ops, e->walk_upper_ops.data(), e->walk_upper_ops.size() * sizeof(NodeOp), hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_walk_lower_ops, e->sched.walk_lower_ops.data(), e->sched.walk_lower_ops.size() * sizeof(NodeOp), hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_walk_upper_ops, e->sched.walk_upper_ops.data(), e->sched.walk_upper_ops.size() * sizeof(NodeOp), hipMemcpyHostToDevice, e->stream));
 	}
-	if (e->walking) {
+	if (e->sched.walking) {
 		if ((rc = e->d_walk_chunk_ops.ensure(e->N)) || (rc = e->d_walk_chunk_off.ensure((size_t)e->N + 2))) return rc;
-		HIP_TRY(hipMemcpyAsync(e->d_walk_chunk_ops, e->walk_chunk_ops.data(), e->walk_chunk_ops.size() * sizeof(NodeOp), hipMemcpyHostToDevice, e->stream));
-		HIP_TRY(hipMemcpyAsync(e->d_walk_chunk_off, e->walk_chunk_off.data(), e->walk_chunk_off.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_walk_chunk_ops, e->sched.walk_chunk_ops.data(), e->sched.walk_chunk_ops.size() * sizeof(NodeOp), hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_walk_chunk_off, e->sched.walk_chunk_off.data(), e->sched.walk_chunk_off.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
 		if ((rc = e->d_walk_lower_chunk_ops.ensure(e->N)) || (rc = e->d_walk_lower_chunk_off.ensure((size_t)e->N + 2))) return rc;
-		HIP_TRY(hipMemcpyAsync(e->d_walk_lower_chunk_ops, e->walk_lower_chunk_ops.data(), e->walk_lower_chunk_ops.size() * sizeof(NodeOp), hipMemcpyHostToDevice, e->stream));
-		HIP_TRY(hipMemcpyAsync(e->d_walk_lower_chunk_off, e->walk_lower_chunk_off.data(), e->walk_lower_chunk_off.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_walk_lower_chunk_ops, e->sched.walk_lower_chunk_ops.data(), e->sched.walk_lower_chunk_ops.size() * sizeof(NodeOp), hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_walk_lower_chunk_off, e->sched.walk_lower_chunk_off.data(), e->sched.walk_lower_chunk_off.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
 		if (stream_possible(e)) {  // the streamed walks' tables follow the chunked lists (core indices included: store / restore moves them)
-			build_stream_ops(e);
-			build_lower_stream_ops(e);
+			build_stream_tables(e->sched, StreamGeometry{e->P, e->C, (size_t)e->nblk_walk_upper * e->G * WAVE}, &e->stream_tab);
 			if ((rc = e->d_stream_ops.ensure(e->N)) || (rc = e->d_stream_chunks.ensure((size_t)e->N + 2)) || (rc = e->d_stream_row_entries.ensure((size_t)e->N * 32)) ||
 			    (rc = e->d_stream_site_tab.ensure((size_t)e->N * 16)) || (rc = e->d_stream_qnode.ensure(e->N)) || (rc = e->d_stream_op_tips.ensure((size_t)e->N * 12)) ||
 			    (rc = e->d_stream_flag.ensure(1)) || (rc = e->d_stream_op_deep.ensure(e->N)))
 				return rc;
-			HIP_TRY(hipMemcpyAsync(e->d_stream_op_tips, e->stream_op_tips.data(), e->stream_op_tips.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
-			HIP_TRY(hipMemcpyAsync(e->d_stream_op_deep, e->stream_op_deep.data(), e->stream_op_deep.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
-			HIP_TRY(hipMemcpyAsync(e->d_stream_ops, e->stream_desc.data(), e->stream_desc.size() * sizeof(StreamDesc), hipMemcpyHostToDevice, e->stream));
-			HIP_TRY(hipMemcpyAsync(e->d_stream_chunks, e->stream_chunks.data(), e->stream_chunks.size() * sizeof(StreamChunk), hipMemcpyHostToDevice, e->stream));
-			HIP_TRY(hipMemcpyAsync(e->d_stream_row_entries, e->stream_row_entries.data(), e->stream_row_entries.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
-			HIP_TRY(hipMemcpyAsync(e->d_stream_site_tab, e->stream_site_tab.data(), e->stream_site_tab.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
-			HIP_TRY(hipMemcpyAsync(e->d_stream_qnode, e->stream_qnode.data(), e->stream_qnode.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
+			HIP_TRY(hipMemcpyAsync(e->d_stream_op_tips, e->stream_tab.op_tips.data(), e->stream_tab.op_tips.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
+			HIP_TRY(hipMemcpyAsync(e->d_stream_op_deep, e->stream_tab.op_deep.data(), e->stream_tab.op_deep.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
+			HIP_TRY(hipMemcpyAsync(e->d_stream_ops, e->stream_tab.desc.data(), e->stream_tab.desc.size() * sizeof(StreamDesc), hipMemcpyHostToDevice, e->stream));
+			HIP_TRY(hipMemcpyAsync(e->d_stream_chunks, e->stream_tab.chunks.data(), e->stream_tab.chunks.size() * sizeof(StreamChunk), hipMemcpyHostToDevice, e->stream));
+			HIP_TRY(hipMemcpyAsync(e->d_stream_row_entries, e->stream_tab.row_entries.data(), e->stream_tab.row_entries.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
+			HIP_TRY(hipMemcpyAsync(e->d_stream_site_tab, e->stream_tab.site_tab.data(), e->stream_tab.site_tab.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
+			HIP_TRY(hipMemcpyAsync(e->d_stream_qnode, e->stream_tab.qnode.data(), e->stream_tab.qnode.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
 			if ((rc = e->d_lstream_ops.ensure(e->N)) || (rc = e->d_lstream_chunks.ensure((size_t)e->N + 2))) return rc;
-			HIP_TRY(hipMemcpyAsync(e->d_lstream_ops, e->lstream_desc.data(), e->lstream_desc.size() * sizeof(LowerDesc), hipMemcpyHostToDevice, e->stream));
-			HIP_TRY(hipMemcpyAsync(e->d_lstream_chunks, e->lstream_chunks.data(), e->lstream_chunks.size() * sizeof(LowerChunk), hipMemcpyHostToDevice, e->stream));
+			HIP_TRY(hipMemcpyAsync(e->d_lstream_ops, e->stream_tab.lower_desc.data(), e->stream_tab.lower_desc.size() * sizeof(LowerDesc), hipMemcpyHostToDevice, e->stream));
+			HIP_TRY(hipMemcpyAsync(e->d_lstream_chunks, e->stream_tab.lower_chunks.data(), e->stream_tab.lower_chunks.size() * sizeof(LowerChunk), hipMemcpyHostToDevice, e->stream));
 		}
 	}
 	// rows of the gradient slab that are produced by the upper pass (every non-root node)
@@ -915,8 +80,8 @@ int upload_schedule(Shard *e) {
 // the tree-walk schedule parks far fewer uppers than the level schedule keeps; parameter gradients and the Hessian can still run
 // the level kernels, so the larger of the two is held once a Levels pre-order pass has run
 size_t upper_slots_needed(const Shard *e) {
-	const bool level_path = !e->walking || e->level_upper_needed;  // (20-state walks: both, they alternate with level passes)
-	return (size_t)std::max(1, level_path ? std::max(e->upper_slots, e->walk_upper_slots) : e->walk_upper_slots);
+	const bool level_path = !e->sched.walking || e->level_upper_needed;  // (20-state walks: both, they alternate with level passes)
+	return (size_t)std::max(1, level_path ? std::max(e->sched.upper_slots, e->sched.walk_upper_slots) : e->sched.walk_upper_slots);
 }
 
 // d_upper for a pre-order pass of family k (upper_kernel; the Hessian's: Levels)

@@ -70,19 +70,9 @@ struct Shard {
 	bool two_slots = false;            // d_lower / d_lscale hold 2 * core_count slots
 	bool generic_fusion = true;  // 20 states: cherries fused into their parents' ops (PHYAMD_GEN_FUSION = 0: every node stored)
 	bool walk_enabled = true;  // PHYAMD_WALK = 0: no walk lists, every pass runs the level kernels
-	// the schedule built walk lists (not keep_partials): 4 states / 20 states unscaled (phyamd_genwalk.inc); what runs on them is
-	// decided in "which kernel runs a pass"
-	bool walking = false, gen_walking = false;
 	DeviceArray<int> d_gen_walk_counter{&mem};  // work-unit counter of the walk
 	int gen_walk_slots[1] = {0};  // resident workgroups of k_lower_gen_walk
-	std::vector<NodeOp> walk_lower_ops, walk_upper_ops;  // depth-first op orders
 	DeviceArray<NodeOp> d_walk_lower_ops{&mem}, d_walk_upper_ops{&mem};
-	int walk_upper_slots = 0;
-	std::vector<NodeOp> walk_chunk_ops;  // chunked form of walk_upper_ops (build_walk_chunks)
-	std::vector<int> walk_chunk_off;     // chunk offsets into walk_chunk_ops: [0] top part, then one per cut subtree
-	int walk_chunk_slots = 0;
-	std::vector<NodeOp> walk_lower_chunk_ops;  // chunked form of walk_lower_ops: cut subtrees, then the top part
-	std::vector<int> walk_lower_chunk_off;
 	DeviceArray<NodeOp> d_walk_lower_chunk_ops{&mem};
 	DeviceArray<int> d_walk_lower_chunk_off{&mem};
 	DeviceArray<NodeOp> d_walk_chunk_ops{&mem};
@@ -91,32 +81,19 @@ struct Shard {
 	bool upper_stream_capped = false;    // the cap left no room for the pre-order walk's mask words / table blocks: neither walk streams
 	bool lower_stream_capped = false;    // ... for the post-order walk's (or its root terms): the post-order walk does not stream
 	int xcd_map = 1;                    // PHYAMD_XCD_MAP = 0: streamed walks with consecutive workgroup ids per block group (A/B; see xcd_position)
-	std::vector<StreamOp> stream_ops;    // one per op of walk_chunk_ops
-	std::vector<StreamDesc> stream_desc; // ... as the kernel reads them (byte offsets multiplied out for stream_P patterns, stream_mstride)
-	int stream_P = 0;
-	size_t stream_mstride = 0;
-	std::vector<StreamChunk> stream_chunks;
-	std::vector<LowerDesc> lstream_desc;  // k_lower4_stream: one per op of walk_lower_chunk_ops
-	std::vector<LowerChunk> lstream_chunks;
 	DeviceArray<LowerDesc> d_lstream_ops{&mem};
 	DeviceArray<LowerChunk> d_lstream_chunks{&mem};
-	std::vector<int> stream_row_entries; // [rows][8] nibbles of the packed mask words (MaskPacker): the pre-order walk's rows, then the post-order walk's
-	std::vector<int> stream_site_tab;    // [ops][16] byte offset of each result lane's branch in a slab row (-1: none)
-	std::vector<int> stream_qnode;       // slab position -> node
-	std::vector<int> stream_op_tips;     // [ops][12] tip of every table slot (-1: unused)
-	std::vector<int> stream_op_deep;     // [ops] bit 0 / 1: the left / right child is a DEEP node (its table slots hold messages only)
 	DeviceArray<int> d_stream_op_tips{&mem}, d_stream_flag{&mem}, d_stream_op_deep{&mem};
 	DeviceArray<char> d_optab{&mem};     // [C][ops] table blocks of OPBLK_BYTES, rebuilt from the matrices every evaluation
 	bool stream_ambiguous = false;       // the tip data hold partial ambiguity codes: the AMBIG instantiation of the streamed walk
 	bool stream_unsupported = false;     // the tip data the mask words were built for hold an empty state mask: the table-gather walks
-	int stream_words = 0, stream_R = 0;
 	DeviceArray<StreamDesc> d_stream_ops{&mem};
 	DeviceArray<StreamChunk> d_stream_chunks{&mem};
 	DeviceArray<int> d_stream_row_entries{&mem}, d_stream_site_tab{&mem}, d_stream_qnode{&mem}, d_oct_lo{&mem};
 	DeviceArray<uint32_t> d_mstream{&tile_mem};
 	size_t mstride = 0;
 	unsigned long mstream_epoch = 0;     // state.tip_epoch of the tip data the mask words were built from
-	std::vector<int> mstream_layout;     // stream_row_entries the device stream was built for
+	std::vector<int> mstream_layout;     // stream_tab.row_entries the device stream was built for
 	double *d_gslab = nullptr;           // the walk-order slab, in d_gpart's storage
 	DeviceArray<double> d_oct{&mem};
 	bool slab_walk_order = false;        // the last pre-order pass wrote d_gslab (walk order), not d_gpart
@@ -133,7 +110,7 @@ struct Shard {
 	hipStream_t stream = nullptr;
 	bool own_stream = false;
 
-	std::vector<int32_t> left, right, parent;
+	std::vector<int32_t> left, right;
 	std::vector<double> lengths, model, freqs, rates, props;
 	// lengths: what the device holds (the root's entry 0).  lengths_sent: the caller's own values by node id, the entry at the
 	// root's id too: a new topology with another root takes the old root's branch from here (shard_set_topology)
@@ -147,25 +124,21 @@ struct Shard {
 	LowerForm lower_form = LowerForm::Reference;
 	bool reference_form_only = false;
 	bool exp2_on = true, tform_on = true;  // PHYAMD_SCALE_EXP2 = 0 / PHYAMD_STREAM_TFORM = 0: the streamed walks never write CarriedExp2 / Carried
-	bool lower_park2_on = true;            // PHYAMD_LOWER_PARK2 = 0: the post-order schedule parks in one slot only (build_schedule)
+	bool lower_park2_on = true;            // PHYAMD_LOWER_PARK2 = 0: the post-order schedule parks in one slot only (ScheduleOptions)
 	DeviceArray<int> d_lexp{&tile_mem}, d_uexp{&tile_mem}, d_Ec{&tile_mem}, d_Eroot{&tile_mem};  // exponents: [stored][C][P], [upper slots][C][P], [C][P], [P]
 	bool keep_partials = false;
 	bool profiling = false;
 	bool prof_pending = false, prof_with_upper = false;
 
-	// schedule
-	std::vector<NodeOp> lower_ops, upper_ops;
-	std::vector<int> lower_level_off, upper_level_off;  // offsets into the op arrays, one past the last at the end
-	std::vector<int32_t> upper_slot;                    // node -> slot of its upper partial in the last schedule (-1 none)
-	int upper_slots = 0;
-	std::vector<int32_t> core_index;  // node -> index of its stored lower array (-1: tip or fused)
-	int core_count = 0;
+	// the current tree's schedule under schedule_options (below), and the streamed walks' tables upload_schedule builds from it for
+	// the current tile size; what runs on the walk lists is decided in "which kernel runs a pass"
+	Schedule sched;
+	Schedule sched_spare;  // the schedule the last phyamd_set_topology replaced: only its storage is used, by the next one
+	StreamTables stream_tab;
 	ScheduleCounts scaled_counts{0, 0, 1};  // those of the schedule a lazy rescaling switch would build (have_scaled_counts)
 	bool have_scaled_counts = false;
-	bool fusion_enabled = true, fused = false;
-	std::vector<DeepDesc> deep_host;   // by node id (only DEEP nodes filled)
-	int deep_count = 0;
-	// (device copy: behind the tip-message table, see Ctx4::deep)
+	bool fusion_enabled = true;
+	// (device copy of sched.deep_host: behind the tip-message table, see Ctx4::deep)
 
 	// device memory
 	DeviceArray<uint8_t> d_tipmask{&tile_mem};
@@ -192,7 +165,6 @@ struct Shard {
 	DeviceArray<double> d_Fw{&mem};     // tree-walk G2: [N][C][20] w_c F_ab(t_n r_c), l_a e^{l_a t_n r_c}
 	DeviceArray<double> d_gacc{&mem};   // tree-walk G2: [16][slabs * C] per-wave eigen-basis sums, then [16] totals
 	// phyamd_branch_log_likelihood without resident uppers: the one upper it needs is rebuilt by a root-to-node path walk
-	std::vector<int> node_kind;      // CH_* of every node in the current schedule
 	DeviceArray<PathStep> d_path_steps{&mem};
 	DeviceArray<double> d_path_upper{&mem}, d_path_tmp{&mem}, d_path_lower{&mem};  // one node partial each
 	DeviceArray<double> d_path_side{&mem};  // 20 / 60 / 61 states: two node partials beside true_lower_gen (fused cherries below the node)
@@ -306,6 +278,20 @@ struct Shard {
 	DeviceArray<double> d_sitelnl_rell{&batch_mem};
 	phyamd_site_lnl_profile site_prof{};
 };
+
+// what the engine's schedule depends on besides its tree: the only place that derives it from an engine.  A caller that changes one
+// of these switches rebuilds the schedule (rebuild_schedule, phyamd_eval.inc)
+ScheduleOptions schedule_options(const Shard *e) {
+	ScheduleOptions o;
+	o.S = e->S;
+	o.keep_partials = e->keep_partials;
+	o.scaling_on = e->scaling_on;
+	o.fusion_enabled = e->fusion_enabled;
+	o.generic_fusion = e->generic_fusion;
+	o.walk_enabled = e->walk_enabled;
+	o.lower_park2_on = e->lower_park2_on;
+	return o;
+}
 
 // ---- what each input invalidates -------------------------------------------------------------------------------------------
 // The only place that writes Shard::state: a setter says which input changed (input_changed: the table), an evaluation what it has
@@ -423,7 +409,7 @@ enum class PassKernel { Levels, Walk, Stream };
 constexpr int STREAM_MAX_TIPS = 1 << 20;  // a packed mask-word entry keeps 20 bits of tip id
 
 // the streamed walks can run on this engine: 4-state walk lists, few enough tips, and no cap has taken the pre-order walk's buffers
-bool stream_possible(const Shard *e) { return e->walking && e->T < STREAM_MAX_TIPS && !e->upper_stream_capped; }
+bool stream_possible(const Shard *e) { return e->sched.walking && e->T < STREAM_MAX_TIPS && !e->upper_stream_capped; }
 
 // a streamed walk's workgroup holds the pass over stored lowers of form f: plain, rescaled by powers of two, or rescaled as the
 // reference does (the C category waves of one block exchange their maxima: at most STREAM_WAVES of them)
@@ -431,9 +417,9 @@ bool stream_shape_fits(const Shard *e, LowerForm f) { return !e->scaling_on || f
 
 // the post-order pass; a streamed one writes stream_lower_form
 PassKernel lower_kernel(const Shard *e, bool made) {
-	if (e->generic) return e->gen_walking && !e->scaling_on && !e->incremental_pass ? PassKernel::Walk : PassKernel::Levels;
-	const bool walk = e->walking && !e->incremental_pass;
-	if (walk && stream_possible(e) && !e->lower_stream_capped && stream_shape_fits(e, stream_lower_form(e)) && !e->lstream_desc.empty() &&
+	if (e->generic) return e->sched.gen_walking && !e->scaling_on && !e->incremental_pass ? PassKernel::Walk : PassKernel::Levels;
+	const bool walk = e->sched.walking && !e->incremental_pass;
+	if (walk && stream_possible(e) && !e->lower_stream_capped && stream_shape_fits(e, stream_lower_form(e)) && !e->stream_tab.lower_desc.empty() &&
 	    !(made && e->stream_unsupported))
 		return PassKernel::Stream;
 	return walk ? PassKernel::Walk : PassKernel::Levels;
@@ -442,7 +428,7 @@ PassKernel lower_kernel(const Shard *e, bool made) {
 // the pre-order pass of a gradient (with_params: of the substitution-parameter gradient, the walk in its PARAMS form); the walks
 // read the stored lowers in the form the post-order pass left
 PassKernel upper_kernel(const Shard *e, int flags, bool with_params, bool made) {
-	if (!e->walking) return PassKernel::Levels;
+	if (!e->sched.walking) return PassKernel::Levels;
 	const bool compat = (flags & PHYAMD_GRAD_COMPAT_SCALED) && e->scaling_on;
 	if (with_params) {  // the walk's eigen-basis branch term: explicit matrices have no eigen system; the compat arithmetic is the level kernels'
 		const bool any_explicit = std::any_of(e->explicit_host.begin(), e->explicit_host.end(), [](uint8_t x) { return x != 0; });

@@ -10,10 +10,10 @@
 // streamed walks' power-of-two exponents: one int per (stored lower or upper slot, category, pattern), plus the root's per
 // category and per pattern (d_lexp, d_uexp, d_Ec, d_Eroot; ensure_exponent_storage).
 // the counts of the schedule the tiles must hold (ScheduleCounts: the current one's, or those of the schedule a lazy switch builds)
-ScheduleCounts schedule_counts(const Shard *e) {
-	ScheduleCounts c{e->core_count, std::max(e->upper_slots, e->walk_upper_slots), 1};
-	for (size_t i = 0; i + 1 < e->lower_level_off.size(); i++) c.widest = std::max(c.widest, e->lower_level_off[i + 1] - e->lower_level_off[i]);
-	for (size_t i = 0; i + 1 < e->upper_level_off.size(); i++) c.widest = std::max(c.widest, e->upper_level_off[i + 1] - e->upper_level_off[i]);
+ScheduleCounts schedule_counts(const Schedule &s) {
+	ScheduleCounts c{s.core_count, std::max(s.upper_slots, s.walk_upper_slots), 1};
+	for (size_t i = 0; i + 1 < s.lower_level_off.size(); i++) c.widest = std::max(c.widest, s.lower_level_off[i + 1] - s.lower_level_off[i]);
+	for (size_t i = 0; i + 1 < s.upper_level_off.size(); i++) c.widest = std::max(c.widest, s.upper_level_off[i + 1] - s.upper_level_off[i]);
 	return c;
 }
 
@@ -33,7 +33,7 @@ double tile_working_set(const Shard *e, double p, bool exact, const ScheduleCoun
 
 // the larger of the working sets of the current schedule and, if a lazy switch may still replace it, of the rescaled one
 double tile_working_set(const Shard *e, double p, bool exact) {
-	const double now = tile_working_set(e, p, exact, schedule_counts(e));
+	const double now = tile_working_set(e, p, exact, schedule_counts(e->sched));
 	return e->have_scaled_counts ? std::max(now, tile_working_set(e, p, exact, e->scaled_counts)) : now;
 }
 
@@ -350,36 +350,49 @@ int shard_set_topology(Shard *e, const int32_t *left, const int32_t *right, int 
 	int rc;
 	if ((rc = bind_device(e))) return rc;
 	e->batch_mem.release_all();  // (sized by the old tree; the tile plan below counts what the engine itself holds)
-	lowers_discarded(e);         // (whichever way this call ends: the schedule is built anew, every partial belongs to the old tree)
-	std::vector<int32_t> old_l = e->left, old_r = e->right;
+	lowers_discarded(e);         // (whichever way this call ends: every partial belongs to the old tree or to a schedule put back)
+	// the new tree's schedule from the caller's arrays: a refused tree changes nothing.  The lazy switch rebuilds the 20 / 60 /
+	// 61-state schedule without fringe fusion or tree walk (more stored nodes and upper slots): the tiles are sized for that
+	// schedule too, so that the switch never needs more than the cap
+	const TreeRef tree{e->T, left, right, root};
+	ScheduleOptions options = schedule_options(e);
+	Schedule other = std::move(e->sched_spare);  // (built into the lists the last call replaced: a topology change per MCMC move allocates nothing)
+	const std::string err = build_schedule(tree, options, &other);
+	if (!err.empty()) return fail(PHYAMD_EINVAL, "%s", err.c_str());
+	e->have_scaled_counts = e->generic && e->cfg.rescale == PHYAMD_RESCALE_AUTO && !e->scaling_on;
+	if (e->have_scaled_counts) {
+		Schedule rescaled;
+		options.scaling_on = true;
+		build_schedule(tree, options, &rescaled);  // (the tree has passed the check)
+		e->scaled_counts = schedule_counts(rescaled);
+	}
+	// tree and schedule are installed together; the old ones wait in other_* for a failure further down, which leaves the engine on
+	// the tree it had (host lists, device op tables) -- or, if that cannot be re-established, without a topology, so that the next
+	// evaluation is refused instead of walking half-updated tables
+	std::vector<int32_t> other_l(left, left + e->N), other_r(right, right + e->N);
+	int other_root = root;
 	const int old_root = e->root;
-	e->left.assign(left, left + e->N);
-	e->right.assign(right, right + e->N);
-	e->root = root;
-	// every failure from here on leaves the engine on the tree it had (host lists, device op tables) -- or, if that cannot be
-	// re-established, without a topology, so that the next evaluation is refused instead of walking half-updated tables
+	auto exchange = [&] {
+		e->left.swap(other_l);
+		e->right.swap(other_r);
+		std::swap(e->root, other_root);
+		std::swap(e->sched, other);
+	};
+	exchange();
 	const bool had_topology = e->have_topology;
 	auto roll_back = [&](int code) {
 		const std::string why = g_last_error;
-		e->left = old_l;
-		e->right = old_r;
-		e->root = old_root;
-		if (had_topology && (build_schedule(e) != PHYAMD_OK || upload_schedule(e) != PHYAMD_OK)) e->have_topology = false;
+		exchange();
+		if (had_topology) {  // the old schedule as a build leaves it: stored nodes in id order (a store may have moved them)
+			int next = 0;
+			for (int32_t &slot : e->sched.core_index)
+				if (slot >= 0) slot = next++;
+			refresh_op_cores(e->sched);
+			if (upload_schedule(e) != PHYAMD_OK) e->have_topology = false;
+		}
 		g_last_error = why;
 		return code;
 	};
-	if ((rc = build_schedule(e))) return roll_back(rc);
-	e->have_scaled_counts = false;
-	if (e->generic && e->cfg.rescale == PHYAMD_RESCALE_AUTO && !e->scaling_on) {
-		// the lazy switch rebuilds the 20 / 60 / 61-state schedule without fringe fusion or tree walk (more stored nodes and upper
-		// slots): the tiles are sized for that schedule too, so that the switch never needs more than the cap
-		e->scaling_on = true;
-		rc = build_schedule(e);
-		if (!rc) e->scaled_counts = schedule_counts(e);
-		e->scaling_on = false;
-		if (rc || (rc = build_schedule(e))) return roll_back(rc);
-		e->have_scaled_counts = true;
-	}
 	{
 		// now that the tree is known the tile size follows its real storage needs (a ladder-like tree stores twice what the
 		// estimate of phyamd_create assumed): possible as long as no tip data or weights sit in buffers of the old tile size
@@ -411,6 +424,7 @@ int shard_set_topology(Shard *e, const int32_t *left, const int32_t *right, int 
 	if ((rc = upload_schedule(e))) return roll_back(rc);
 	if ((rc = ensure_lower_storage(e))) return roll_back(rc);
 	e->have_topology = true;
+	e->sched_spare = std::move(other);
 	// lengths go by node id: the branch above the old root's id is the one the caller sent for that id, the new root's is ignored
 	if (e->have_lengths && (!had_topology || root != old_root) && (rc = upload_lengths(e))) return rc;
 	input_changed(e, Input::Topology);
@@ -473,8 +487,8 @@ int shard_store(Shard *e) {
 		// the allocation never shrinks (keep_partials on and off again, a new topology with fewer stored nodes): only the
 		// core_count live slots move over.  Allocated next to the one-slot arrays, within the cap: if they do not fit, the engine
 		// keeps its one-slot state
-		const size_t npd = node_partial_doubles(e), want = (size_t)std::max(1, e->core_count) * 2;
-		const size_t live = std::min(lower_slots(e), (size_t)std::max(1, e->core_count));
+		const size_t npd = node_partial_doubles(e), want = (size_t)std::max(1, e->sched.core_count) * 2;
+		const size_t live = std::min(lower_slots(e), (size_t)std::max(1, e->sched.core_count));
 		DeviceArray<double> lower{&e->tile_mem}, lscale{&e->tile_mem};
 		if ((rc = lower.ensure(want * npd)) || (e->d_lscale && (rc = lscale.ensure(want * e->P)))) return rc;
 		hipError_t err = hipMemcpyAsync(lower, e->d_lower, live * npd * sizeof(double), hipMemcpyDeviceToDevice, e->stream);
@@ -499,7 +513,7 @@ int shard_store(Shard *e) {
 	st.props = e->props;
 	st.have_eigen = e->have_eigen;
 	st.scaling_on = e->scaling_on;
-	st.core_index = e->core_index;
+	st.core_index = e->sched.core_index;
 	st.epoch = e->schedule_epoch;
 	state_stored(e);
 	return PHYAMD_OK;
@@ -521,12 +535,12 @@ int shard_restore(Shard *e) {
 		// re-integrate the root, whose per-pattern outputs belong to the discarded state
 		bool moved = false;
 		for (int n = e->T; n < e->N; n++)
-			if (e->core_index[n] != st.core_index[n]) {
-				e->core_index[n] = st.core_index[n];
+			if (e->sched.core_index[n] != st.core_index[n]) {
+				e->sched.core_index[n] = st.core_index[n];
 				moved = true;
 			}
 		if (moved) {
-			refresh_op_cores(e);
+			refresh_op_cores(e->sched);
 			if ((rc = upload_schedule(e))) return rc;
 		}
 		lowers_restored(e);
@@ -783,7 +797,7 @@ int shard_root_frequency_term(Shard *e, double *out) {
 	int rc;
 	if ((rc = bind_device(e))) return rc;
 	if ((rc = check_ready(e))) return rc;
-	if (e->tiles == 1 && (!lowers_current(e) || e->core_index[e->root] < 0 || !e->d_lower)) return fail(PHYAMD_EINVAL, "no evaluation has been run yet");
+	if (e->tiles == 1 && (!lowers_current(e) || e->sched.core_index[e->root] < 0 || !e->d_lower)) return fail(PHYAMD_EINVAL, "no evaluation has been run yet");
 	// (the root's array is p_root in every storage convention: only a rescaled evaluation's factors have to be the reference's)
 	if (e->scaling_on && (rc = require_reference_form(e))) return rc;
 	if (e->tiles > 1) {  // the per-tile terms were summed by the last phyamd_parameter_gradient
@@ -802,9 +816,9 @@ int shard_root_frequency_term(Shard *e, double *out) {
 
 // the sibling subtree `s` as child_message / PathStep take it
 static void describe_subtree(const Shard *e, int s, PathStep &st) {
-	st.kind = e->node_kind[s];
+	st.kind = e->sched.node_kind[s];
 	st.node = s;
-	st.core = e->core_index[s];
+	st.core = e->sched.core_index[s];
 	st.t0 = st.t1 = st.t2 = st.inner = -1;
 	if (st.kind == CH_CHERRY) {
 		st.t0 = e->left[s];
@@ -835,7 +849,7 @@ static int rebuild_path_upper(Shard *e, int node) {
 	if ((rc = e->d_path_upper.ensure(npd)) || (rc = e->d_path_lower.ensure(npd)) || (rc = e->d_path_steps.ensure(e->N))) return rc;
 	if (e->generic && (rc = e->d_path_tmp.ensure(npd))) return rc;
 	std::vector<int> path;  // node, parent, ..., root
-	for (int a = node; a >= 0; a = e->parent[a]) path.push_back(a);
+	for (int a = node; a >= 0; a = e->sched.parent[a]) path.push_back(a);
 	const int m = (int)path.size() - 1;  // steps
 	if (!e->generic) {
 		std::vector<PathStep> steps(m);
@@ -852,7 +866,7 @@ static int rebuild_path_upper(Shard *e, int node) {
 		else
 			hipLaunchKernelGGL(k_path_upper4<false>, grid, block, 0, e->stream, e->d_path_steps, m, e->T, e->P, e->C, e->d_tipmask, e->d_lower, e->d_mats,
 			                   e->d_tiptab, e->d_path_upper);
-		if (node >= e->T && e->core_index[node] < 0) {  // fringe / DEEP node: its own partial is not stored either
+		if (node >= e->T && e->sched.core_index[node] < 0) {  // fringe / DEEP node: its own partial is not stored either
 			PathStep self;
 			describe_subtree(e, node, self);
 			hipLaunchKernelGGL(k_unstored_partial4, grid, block, 0, e->stream, self.kind, node, self.t0, self.t1, self.t2, self.inner, e->T, e->P, e->C, e->d_tipmask,
@@ -869,9 +883,9 @@ static int rebuild_path_upper(Shard *e, int node) {
 			const int par = path[m - j], child = path[m - j - 1];
 			const int sib = e->left[par] == child ? e->right[par] : e->left[par];
 			double *dst = ((m - 1 - j) & 1) ? e->d_path_tmp : e->d_path_upper;
-			const double *sp = sib < e->T ? nullptr : e->d_lower + (size_t)e->core_index[sib] * npd;  // a stored node: t = P p (k_lower_gen)
+			const double *sp = sib < e->T ? nullptr : e->d_lower + (size_t)e->sched.core_index[sib] * npd;  // a stored node: t = P p (k_lower_gen)
 			int carried = 1;
-			if (sib >= e->T && e->core_index[sib] < 0) {  // a fused cherry: its partial is formed on the side (d_path_lower is free until the end)
+			if (sib >= e->T && e->sched.core_index[sib] < 0) {  // a fused cherry: its partial is formed on the side (d_path_lower is free until the end)
 				if ((rc = cherry_partial_gen(e, sib, e->d_path_lower))) return rc;
 				sp = e->d_path_lower;
 				carried = 0;
@@ -902,14 +916,14 @@ int shard_branch_log_likelihood(Shard *e, int node, double length, double *lnl, 
 	const double *up, *low;
 	int fold = 0;
 	if (uppers_resident(e)) {
-		up = e->d_upper + (size_t)e->upper_slot[node] * npd;
-		low = node < e->T ? nullptr : e->d_lower + (size_t)e->core_index[node] * npd;
+		up = e->d_upper + (size_t)e->sched.upper_slot[node] * npd;
+		low = node < e->T ? nullptr : e->d_lower + (size_t)e->sched.core_index[node] * npd;
 		fold = e->upper_fold ? 1 : 0;
 	} else {
 		if ((rc = run_lower(e, true))) return rc;
 		if (e->state.path_node != node && (rc = rebuild_path_upper(e, node))) return rc;
 		up = e->d_path_upper;
-		low = node < e->T ? nullptr : (e->core_index[node] >= 0 ? e->d_lower + (size_t)e->core_index[node] * npd : e->d_path_lower);
+		low = node < e->T ? nullptr : (e->sched.core_index[node] >= 0 ? e->d_lower + (size_t)e->sched.core_index[node] * npd : e->d_path_lower);
 	}
 	if (e->generic && node >= e->T) {  // the branch's P(t) changes here: p_node itself, not the stored P p (k_lower_gen)
 		if ((rc = e->d_path_lower.ensure(npd)) || (rc = e->d_path_side.ensure(2 * npd))) return rc;
@@ -978,7 +992,7 @@ int shard_root_invariant_term(Shard *e, double *out) {
 		if (!tiled_totals_current(e)) return fail(PHYAMD_EINVAL, "no evaluation has been run yet");
 		src = e->d_total + (size_t)e->N * e->C + 2 * PHYAMD_MAX_PARAMETERS;
 	} else {
-		if (!lowers_current(e) || e->core_index[e->root] < 0 || !e->d_lower) return fail(PHYAMD_EINVAL, "no evaluation has been run yet");
+		if (!lowers_current(e) || e->sched.core_index[e->root] < 0 || !e->d_lower) return fail(PHYAMD_EINVAL, "no evaluation has been run yet");
 		if (e->scaling_on && (rc = require_reference_form(e))) return rc;  // (see shard_root_frequency_term)
 		if ((rc = launch_root_invariant_term(e, nullptr))) return rc;
 		src = e->d_inv_part + (e->P + 255) / 256;
@@ -1032,9 +1046,9 @@ int shard_get_partials(Shard *e, int node, int upper, double *out) {
 					                                      : (mask[k] == S || mask[k] == s) ? 1.0 : 0.0;
 		return PHYAMD_OK;
 	}
-	if (!upper && e->core_index[node] < 0)
+	if (!upper && e->sched.core_index[node] < 0)
 		return fail(PHYAMD_EINVAL, "node %d is fused into its parent (cherry / cherry+tip) and not stored: shard_set_keep_partials(1) first", node);
-	const double *src = upper ? e->d_upper + (size_t)e->upper_slot[node] * np : e->d_lower + (size_t)e->core_index[node] * np;
+	const double *src = upper ? e->d_upper + (size_t)e->sched.upper_slot[node] * np : e->d_lower + (size_t)e->sched.core_index[node] * np;
 	if (e->generic) {  // planes [C][S][Pp] -> the reference's [C][P][S]
 		DeviceArray<double> tmp;  // (a temporary: not counted in device_bytes)
 		const size_t cnt = (size_t)e->C * e->P * e->S;

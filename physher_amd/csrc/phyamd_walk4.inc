@@ -1,5 +1,5 @@
 // phyamd_walk4.inc: depth-first tree-walk 4-state kernels (k_lower4_walk, k_upper4_walk): two launches per pass (cut subtrees and the
-// top of the tree: build_walk_chunks / build_lower_walk_chunks) -- included by phyamd_engine.hip inside its anonymous namespace.
+// top of the tree: chunk_pre_order / chunk_post_order) -- included by phyamd_engine.hip inside its anonymous namespace.
 
 // ------------------------------------------------------------------------------------------------
 // Tree-walk form of the post-order pass (unscaled evaluations).  Patterns are independent, so instead of one launch
@@ -91,7 +91,7 @@ __global__ __launch_bounds__(WAVES *WAVE, (WAVES == 4 && PPT_WALK == 1 && !SCALE
 	int flip = 0;
 	// LPARK: park slots behind the root exchange (xsz + G doubles) and the SCALE exchange: [wave][q][2 halves][64 lanes] of 16 bytes
 	dv2 *park = reinterpret_cast<dv2 *>(sh + xsz + G + (G & 1) + (SCALE ? 2 * xsz : 0)) + (size_t)(g * C + c) * PPT_WALK * 2 * WAVE + lane;
-	// chunked launches (build_lower_walk_chunks): ops [op_begin, op_end) of the list, chunk blockIdx.y of the launch
+	// chunked launches (chunk_post_order): ops [op_begin, op_end) of the list, chunk blockIdx.y of the launch
 	const int op_begin = chunk_off ? chunk_off[chunk_base + blockIdx.y] : 0, op_end = chunk_off ? chunk_off[chunk_base + blockIdx.y + 1] : nops;
 #pragma unroll 1
 	for (int i = op_begin; i < op_end; i++) {
@@ -373,7 +373,7 @@ __global__ __launch_bounds__(WAVES *WAVE, WAVES == 4 ? (PARAMS ? 3 : (SCALE ? WA
 	d4 carry = one;
 	double Gab[16] = {0., 0., 0., 0., 0., 0., 0., 0., 0., 0., 0., 0., 0., 0., 0., 0.};
 	const ParamCtx pc{as_const(pbuf), as_const(pbuf + 16), pbuf + 32, Fw};
-	// chunked launches (build_walk_chunks): this workgroup walks ops [op_begin, op_end) of the list, chunk blockIdx.y of the launch
+	// chunked launches (chunk_pre_order): this workgroup walks ops [op_begin, op_end) of the list, chunk blockIdx.y of the launch
 	const int op_begin = chunk_off ? chunk_off[chunk_base + blockIdx.y] : 0, op_end = chunk_off ? chunk_off[chunk_base + blockIdx.y + 1] : nops;
 #pragma unroll 1
 	for (int i = op_begin; i < op_end; i++) {

@@ -28,52 +28,7 @@
 // Four waves per SIMD (<= 128 registers): the prefetch needs registers, and with its operands already there a wave is rarely
 // parked on memory, so the fifth wave buys less than the registers do.
 
-enum { HK_TIP = 0, HK_CHERRY = 1, HK_CHERRY_TIP = 2 };
-enum { SU_CARRY = 0, SU_LDS = 1, SU_U = 2, SU_ROOT = 3 };
-
-// side: node, then a[10]: CH_CHERRY / CH_CHERRY_TIP: {t0, t1, t2, inner}; CH_DEEP: two halves {node, t0, t1, t2, inner}
-struct StreamOp {
-	int32_t flags;        // kl 0-2 | kr 3-5 | 6: LDS slot of the park | 7: LDS slot the parent's upper is read from | upper source 9-11 |
-	                      // park 12-13 (1: left child's upper -> LDS, 2: right) | mask groups of the
-	                      // NEXT op 14-15 | half kinds: left h0 16-17, h1 18-19, right h0 20-21, h1 22-23 | 24: the next op's block is two pieces |
-	                      // 25: the next op's second group sits in its first group's row
-	int32_t parent;       // node whose matrix multiplies the incoming upper (this and every other matrix: byte offset node * C * 128, see SX::M)
-	int32_t slot_parent, slot_left, slot_right;  // HBM upper slots (-1: none)
-	int32_t nx_mask_word;  // row of the next op's first mask group (-1: none)
-	int32_t nx_a, nx_b;   // stored lower arrays the next op wants in register sets A (its left child) / B (right): -1 nothing
-	int32_t lnode, la[10];
-	int32_t rnode, ra[10];
-	int32_t nx_u;         // HBM upper slot the next op wants in register set U (its parent's upper): -1 nothing
-	int32_t wsh;          // this op's mask groups: shift of the first 0-4 | of the second 5-9 (inside their rows)
-};
-static_assert(sizeof(StreamOp) == 128, "one StreamOp = 32 dwords");
-
-// What the kernel reads (build_stream_ops converts the StreamOp rows, which keep node ids for the host's bookkeeping): every
-// address an op needs is a byte offset the host has multiplied out -- both walks are bound by instruction issue, and 64-bit
-// scalar multiplies for (array index x plane size) were a third of the scalar instructions of an op.
-struct StreamDesc {
-	int32_t flags;               // StreamOp::flags | 26 / 27 / 28: the next op wants register set A / B / U | 29 / 30: the left / right child's upper is stored
-	int32_t parent, lnode, rnode;  // matrices (SX::M): byte offset node * C * 128
-	int32_t lm[5], rm[5];        // matrices inside a child: DEEP halves {node, inner} x 2, then a fringe child's inner cherry
-	int64_t nx_words;            // byte offset of the row of the next op's first mask group
-	int64_t nx_a, nx_b, nx_u;    // byte offsets of the planes the next op wants (category 0; a wave adds its category's)
-	int64_t st_left, st_right;   // ... of the upper slots this op stores
-	int32_t wsh;                 // StreamOp::wsh
-	int32_t pad[5];
-};
-static_assert(sizeof(StreamDesc) == 128 && offsetof(StreamDesc, nx_words) == 56, "one StreamDesc = 32 dwords");
-
-struct StreamChunk {  // what the first op of a chunk wants fetched before the loop (same_row: its second group sits in the first one's row)
-	int32_t mask_word, mask_words, a, b, u, same_row, pad[2];
-};
-
-// Per-(op, category) table block, 2048 bytes:
-//   [0, 64)       16 ints: byte offset in a slab row of the branch each result lane stores (-1: none), see k_upper4_stream
-//   [64, 1024)    the left child's tips, [1024, 1984) the right child's:
-//                 a DEEP child: six slots of 160 bytes = 5 rows x 4 doubles, P_tip . e_s for s = 0..3, then P_tip . 1;
-//                 any other child (its tips' branch terms are formed in this op): three slots of 320 bytes = those 5 rows, then the
-//                 5 rows of Qs P_tip . e_s / Qs P_tip . 1, Qs = the matrix of the branch terms (diag(pi) Q, or Q under FOLD)
-constexpr int OPBLK_BYTES = 2048, OPBLK_LEFT = 64, OPBLK_RIGHT = 1024, OPTIP_BYTES = 160;
+// (StreamOp, StreamDesc, StreamChunk, HK_* / SU_* and the table block's layout OPBLK_*: phyamd_types.h)
 
 // Mask words (packed): one dword row per pattern, mstream[row * mstride + k] (mstride = patterns rounded up to whole waves; the tail
 // holds gaps).  A GROUP = the tips of one child of one op: bit 0 = "a nibble of this group holds a partial ambiguity code", then
@@ -368,7 +323,7 @@ __device__ __forceinline__ unsigned prefetch1(const char *base, unsigned lane_of
 // Slot 0 holds leaf parks (nothing else is parked while they wait), slot 1 parks whose wait holds leaf parks only -- an upper parked
 // in HBM is written and read back (7.4 GB per evaluation at the headline shape with one slot), and without those stores the pass is
 // 1.4 ms shorter (a timing-only ablation, since retired).  8 KB per wave: four workgroups per CU use 128 KB of the 160.
-constexpr int STREAM_PARK_SLOTS = 2, STREAM_PARK_BYTES = 2 * WAVE * 16;
+constexpr int STREAM_PARK_BYTES = 2 * WAVE * 16;  // (STREAM_PARK_SLOTS: phyamd_types.h)
 constexpr int STREAM_LDS_PER_WAVE = STREAM_PARK_SLOTS * STREAM_PARK_BYTES + 2 * OPBLK_BYTES;
 
 // Workgroup = STREAM_WAVES waves = that many consecutive blocks of 64 patterns of ONE category (blockIdx.x = block group * C + category):
@@ -680,32 +635,12 @@ __global__ __launch_bounds__(STREAM_WAVES *WAVE, (SCALE || AMBIG) ? STREAM_MIN_W
 //     load where it is used; that op pays the round trip.
 // Workgroup = four consecutive 64-pattern blocks of ONE category (shared descriptors, matrices and table blocks in the scalar
 // cache and L2), no workgroup-level synchronisation; the root's sum over categories is k_root_finish64's.
-struct LowerDesc {
-	int32_t flags;     // kl 0-2 | kr 3-5 | where a stored left child comes from 6-7 (0: memory, 1: the previous op's result, 2: the parked
-	                   // partial, 3: the one in the second slot) | same for the right child 8-9 | 10: park the result | 11: no store (no
-	                   // longer set) | 12-13: ring slot of the first mask row to request for the NEXT op | 14-15: how many rows to request
-	                   // for it (0..2: the rows it reads that no op before it has read) | half kinds 16-23 | 24 / 25: the next op's block
-	                   // needs its second / first piece | 26: park the result in the second slot
-	int32_t nx_block;  // table block of the next op
-	int32_t lnode, rnode, lm[5], rm[5];  // matrices by byte offset, as in StreamDesc
-	int64_t nx_words;  // byte offset of the first mask row to request for the next op (the post-order walk's own stream)
-	int64_t store;     // ... of the plane (category 0) that receives the result
-	int64_t mem_l, mem_r;  // ... of a child that comes from memory
-	int32_t wsh;       // this op's mask groups: shift of the first 0-4 | of the second 5-9 | ring slots of their rows 10-11 | 12-13
-	int32_t self;      // TF: the node's own matrices by byte offset (0: the root, which has no branch)
-	int64_t ls_store, ls_l, ls_r;  // rescaled evaluations: the same three as byte offsets into the cumulative log scale factors [stored][P]
-	int32_t pad[2];
-};
-static_assert(sizeof(LowerDesc) == 128 && offsetof(LowerDesc, nx_words) == 56, "one LowerDesc = 32 dwords");
-struct LowerChunk {  // what the first op of a chunk wants requested before the loop: table block, mask rows (count, ring slot and byte offset of the first)
-	int32_t block, pieces, mask_rows, slot;
-	int64_t words;
-};
+// (LowerDesc, LowerChunk: phyamd_types.h)
 
 constexpr int LSTREAM_MIN_WAVES = 5;  // (29 KB of LDS per workgroup allow five workgroups per CU: 96 registers)
 // Park slots of an instantiation: the second one is eight more registers, which the AMBIG instantiations do not have at five
 // workgroups per CU (they would spill); those read a second-slot child from memory like the one-slot schedule does -- the
-// descriptor keeps its offsets (build_lower_stream_ops).
+// descriptor keeps its offsets (stream_post_order).
 constexpr int lstream_park_slots(bool ambig) { return ambig ? 1 : 2; }
 constexpr int LSTREAM_LDS_PER_WAVE = 2 * OPBLK_BYTES + 5 * WAVE * 4 + WAVE * 32;  // two table blocks, a ring of four mask rows + a scratch row, the store staging area
 

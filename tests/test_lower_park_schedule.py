@@ -1,5 +1,5 @@
 """CPU-only: the post-order walk's park slots in the host schedule (phyamd_post_order_parks: build_schedule and
-build_lower_walk_chunks, no device).  A stored child waits in one of a wave's two register slots while its sibling's subtree is
+chunk_post_order, no device).  A stored child waits in one of a wave's two register slots while its sibling's subtree is
 walked; the kernel neither checks that a slot is free when it writes it nor that it holds the right node when it reads it, so the
 schedule has to: no slot holds two values at once, every slot read finds the value its own chunk wrote, every carried child is
 the result of the op in front, and nothing is left parked at a chunk's end."""

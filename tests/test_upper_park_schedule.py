@@ -1,5 +1,5 @@
 """CPU-only: the contract of the 4-state pre-order walk's host schedule (phyamd_pre_order_schedule: build_schedule,
-build_walk_chunks and build_stream_ops, no device).  An op's own upper arrives in the registers of the op in front, from one of a
+chunk_pre_order and stream_pre_order, no device).  An op's own upper arrives in the registers of the op in front, from one of a
 wave's two LDS park slots, from an HBM slot recycled inside a chunk or from one that crosses from the top part to a cut subtree;
 k_upper4_walk and k_upper4_stream check none of it, so the schedule has to (upper_park_util.check_contract):
   * coverage: one op per CORE / DEEP node, the root's the only one without a source, every non-root branch term once;
@@ -11,7 +11,7 @@ k_upper4_walk and k_upper4_stream check none of it, so the schedule has to (uppe
     part, read by the first op of one other chunk and never recycled;
   * prefetch (streamed form): op i requests exactly the slot op i + 1 reads, which an op before i wrote; a chunk's last op none;
   * chunks: under 32 ops one chunk, else the top part and contiguous subtrees of at most `target` ops, longest first;
-  * the streamed form against the chunked list: the same ops, differing only by build_stream_ops' documented rewrites.
+  * the streamed form against the chunked list: the same ops, differing only by stream_pre_order's documented rewrites.
 Form 2 (the unchunked list) is what k_upper4_walk's parameter form reads: one chunk, no LDS slot, the free_w slots."""
 import time
 

@@ -28,7 +28,7 @@ TIP, CORE, DEEP, CHERRY, CHERRY_TIP = range(5)
 KIND_NAMES = ("TIP", "CORE", "DEEP", "CHERRY", "CHERRY_TIP")
 ROOT, CARRY, LDS0, LDS1, HBM = range(5)  # sources; destinations use the same codes with 0 = NONE
 NONE = 0
-CHUNK_MIN_OPS, CHUNK_MIN_TARGET, WALK_CHUNKS = 32, 16, 3  # build_walk_chunks
+CHUNK_MIN_OPS, CHUNK_MIN_TARGET, WALK_CHUNKS = 32, 16, 3  # chunk_pre_order
 
 
 def chunk_target(n):
@@ -400,7 +400,7 @@ def _parent(tree, node):
 
 
 def check_forms_agree(zero, one):
-    """form 1 is form 0 op by op but for what build_stream_ops documents: children swapped where the carried child was the right
+    """form 1 is form 0 op by op but for what stream_pre_order documents: children swapped where the carried child was the right
     one, the registers of the op in front instead of an HBM slot that op stored, and slot-1 parks instead of HBM parks"""
     assert len(zero) == len(one)
     assert (zero[:, CHUNK] == one[:, CHUNK]).all() and (zero[:, NODE] == one[:, NODE]).all(), "not the same ops in the same order"
@@ -443,7 +443,7 @@ def check_forms_agree(zero, one):
 
 @functools.lru_cache(maxsize=None)
 def named_stats(name):
-    """(statistics of form 0, of form 1, what build_stream_ops moved) of a named tree, contract checked"""
+    """(statistics of form 0, of form 1, what stream_pre_order moved) of a named tree, contract checked"""
     tree = make_tree(name)
     st = [check_contract(tree, *named_schedule(name, form), form) for form in (0, 1)]
     return st[0], st[1], check_forms_agree(named_schedule(name, 0)[0], named_schedule(name, 1)[0])
