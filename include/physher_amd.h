@@ -567,6 +567,15 @@ int phyamd_pre_order_schedule(int32_t tip_count, const int32_t *left /* [2T-1] *
  * negative PHYAMD_E* code. */
 int phyamd_post_order_slots(int32_t tip_count, const int32_t *left /* [2T-1] */, const int32_t *right, int32_t root,
                             int32_t *out /* [capacity][6] */, int32_t capacity, int32_t *slots);
+/* The stored nodes that the streamed 4-state walks of a tree do not store (PHYAMD_STREAM_ELIDE, on by default), from the host
+ * schedule alone (no device, no engine): a stored node with one stored child and one child that is a tip or a cherry, which the
+ * post-order walk hands to its parent in registers and the pre-order walk forms again from the stored child.  Children before
+ * parents, eight ints each: node | its parent | its stored child | its other child | that child's kind (0 tip, 3 cherry) | how
+ * the post-order walk hands the node to its parent (1: the op in front, 2: the wave's first park slot) | the side the node has in
+ * its parent's streamed pre-order op (0 left, 1 right) | the post-order chunk of the node's and its parent's ops.  Returns the
+ * number of such nodes (at most `capacity` of them are written) or a negative PHYAMD_E* code. */
+int phyamd_stream_elisions(int32_t tip_count, const int32_t *left /* [2T-1] */, const int32_t *right, int32_t root,
+                           int32_t *out /* [capacity][8] */, int32_t capacity);
 int phyamd_is_rescaling(phyamd_engine *e);
 /* SingleTreeLikelihood_use_rescaling (treelikelihood.c:1410-1423) after construction: PHYAMD_RESCALE_ALWAYS / _NEVER switch
  * at once (the next evaluation recomputes every node), PHYAMD_RESCALE_AUTO keeps the current state and re-arms the lazy switch. */

@@ -915,6 +915,24 @@ int phyamd_pre_order_schedule(int32_t tip_count, const int32_t *left, const int3
 	return (int)ops.size();
 }
 
+// the stored nodes the streamed walks of a tree do without (stream_elide): host code only (no device, no engine)
+int phyamd_stream_elisions(int32_t tip_count, const int32_t *left, const int32_t *right, int32_t root, int32_t *out, int32_t capacity) {
+	if (tip_count < 2) return fail(PHYAMD_EINVAL, "tip_count must be >= 2 (got %d)", tip_count);
+	if (!left || !right) return fail(PHYAMD_EINVAL, "null left or right");
+	if (capacity < 0 || (capacity > 0 && !out)) return fail(PHYAMD_EINVAL, "null out with capacity %d", capacity);
+	Schedule sched;  // 4 states, an engine's defaults; the streamed walks' tables for one pattern of one category, as an engine builds them
+	StreamTables stream_tab;
+	const std::string err = build_schedule(TreeRef{tip_count, left, right, root}, ScheduleOptions{}, &sched);
+	if (!err.empty()) return fail(PHYAMD_EINVAL, "%s", err.c_str());
+	build_stream_tables(sched, StreamGeometry{1, 1, WAVE, true}, &stream_tab);
+	const std::vector<StreamElision> &el = stream_tab.elisions;
+	for (int i = 0; i < (int)el.size() && i < capacity; i++) {
+		const int32_t rec[8] = {el[i].node, el[i].parent, el[i].stored, el[i].sibling, el[i].sibling_kind, el[i].source, el[i].side, el[i].chunk};
+		std::memcpy(out + (size_t)i * 8, rec, sizeof(rec));
+	}
+	return (int)el.size();
+}
+
 int phyamd_is_rescaling(phyamd_engine *g) {
 	CHECK_GROUP(g);
 	int any = 0;  // shards switch on their own lnL (the lazy switch is per shard: the sum does not depend on who rescales)

@@ -470,7 +470,10 @@ int launch_upper_stream(Shard *e) {
 		             : SCALE ? (amb ? k_upper4_stream<FOLD, 1, true, false> : k_upper4_stream<FOLD, 1, false, false>)
 		             : tf    ? (amb ? k_upper4_stream<FOLD, 0, true, true> : k_upper4_stream<FOLD, 0, false, true>)
 		                     : (amb ? k_upper4_stream<FOLD, 0, true, false> : k_upper4_stream<FOLD, 0, false, false>);
-		hipLaunchKernelGGL(kernel, dim3(grid_x.x, phase ? subtrees : 1), block, lds, e->stream, (const StreamDesc *)e->d_stream_ops, (const StreamChunk *)e->d_stream_chunks,
+		// (descriptors that name unstored children belong to the TF forms; any other pass reads the plain ones behind them: upload_schedule)
+		const bool plain = !tf && !e->stream_tab.plain_desc.empty();
+		hipLaunchKernelGGL(kernel, dim3(grid_x.x, phase ? subtrees : 1), block, lds, e->stream,
+		                   (const StreamDesc *)e->d_stream_ops + (plain ? e->stream_tab.desc.size() : 0), (const StreamChunk *)e->d_stream_chunks + (plain ? e->stream_tab.chunks.size() : 0),
 		                   (const int *)e->d_walk_chunk_off, phase, nops, e->P, e->C, nb, (const uint32_t *)e->d_mstream, e->mstride, (const double *)e->d_lower, e->d_upper,
 		                   (const double *)e->d_mats, (const char *)e->d_optab, (const double *)(FOLD ? e->d_Q : e->d_Qpi), (const double *)e->d_freqs, (const double *)e->d_wl,
 		                   e->d_gslab, R, (const double *)e->d_props, (const double *)e->d_weights, e->xcd_map, (const int *)e->d_lexp, e->d_uexp, (const int *)e->d_Eroot);

@@ -125,6 +125,7 @@ struct Shard {
 	bool reference_form_only = false;
 	bool exp2_on = true, tform_on = true;  // PHYAMD_SCALE_EXP2 = 0 / PHYAMD_STREAM_TFORM = 0: the streamed walks never write CarriedExp2 / Carried
 	bool lower_park2_on = true;            // PHYAMD_LOWER_PARK2 = 0: the post-order schedule parks in one slot only (ScheduleOptions)
+	bool stream_elide_on = true;           // PHYAMD_STREAM_ELIDE = 0: the streamed walks store every stored node (stream_elide, phyamd_tree_schedule.h)
 	DeviceArray<int> d_lexp{&tile_mem}, d_uexp{&tile_mem}, d_Ec{&tile_mem}, d_Eroot{&tile_mem};  // exponents: [stored][C][P], [upper slots][C][P], [C][P], [P]
 	bool keep_partials = false;
 	bool profiling = false;

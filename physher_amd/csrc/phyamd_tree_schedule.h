@@ -633,6 +633,15 @@ inline std::string build_schedule(const TreeRef &tree, const ScheduleOptions &op
 struct StreamGeometry {
 	int P, C;
 	size_t mstride;
+	bool elide = false;  // stream_elide: the post-order walk stops storing the nodes the pre-order walk can form beside a tip or a cherry
+};
+
+// a stored node the streamed walks no longer store (stream_elide)
+struct StreamElision {
+	int32_t node, parent, stored, sibling, sibling_kind;  // its parent, its stored child, its other child (CH_TIP / CH_CHERRY)
+	int32_t source;                                       // how the post-order walk hands it to its parent: 1 the op in front, 2 park slot 0
+	int32_t side;                                         // the side it has in its parent's pre-order op (0 left, 1 right)
+	int32_t chunk;                                        // the post-order chunk of both ops
 };
 
 // the streamed 4-state walks' host tables (phyamd_walk4s.inc), built from the chunked lists of a Schedule for one geometry
@@ -649,6 +658,11 @@ struct StreamTables {
 	std::vector<int> qnode;         // slab position -> node
 	std::vector<int> op_tips;       // [ops][12] tip of every table slot (-1: unused)
 	std::vector<int> op_deep;       // [ops] bit 0 / 1: the left / right child is a DEEP node (its table slots hold messages only)
+	// stream_elide (StreamGeometry::elide; otherwise empty): the pre-order walk's descriptors and chunks as they were before it, for a
+	// pass over stored lowers in the reference's form, and the nodes it took out
+	std::vector<StreamDesc> plain_desc;
+	std::vector<StreamChunk> plain_chunks;
+	std::vector<StreamElision> elisions;
 	int words = 0, R = 0;           // mask rows of both walks; slab positions
 };
 
@@ -984,10 +998,121 @@ inline void stream_post_order(const Schedule &sc, const StreamGeometry &g, Strea
 	t.words = (int)t.row_entries.size() / 8;
 }
 
-// both walks' tables (the post-order walk's mask rows follow the pre-order walk's)
+// Stored nodes the two streamed walks can do without (the TF forms only, LowerForm::Carried / CarriedExp2): a stored node n with one
+// stored child s and one child f that is a tip or a cherry.  Its parent's pre-order op needs t_n = P_n (m_f o t_s): m_f is a table
+// row (a tip) or one mat-vec over two (a cherry), and t_s is stored anyway -- the op reads s's plane where it read n's, forms t_n in
+// a few dozen instructions, and the post-order walk, which is bound by its writes, keeps n in registers only.
+// E is chosen bottom-up over the chunked post-order list.  n is in E if
+//   * n is stored and not the root, s is stored and not in E (t_s must be in memory), f is CH_TIP or CH_CHERRY;
+//   * the post-order walk hands n to its parent in registers, inside one chunk: as the op in front's result (source 1) or from
+//     park slot 0 (source 2) -- not from memory, and not from the second slot, which the AMBIG instantiations read from memory.
+// A rewrite of the flattened tables only (Schedule, the walk lists, core_index and the storage stay as they are):
+//   * LowerDesc of n: bit 11, "no store" (honoured by the TF instantiations);
+//   * StreamDesc of the parent's op: the child's kind becomes SK_CORE_TIP / SK_CORE_CHERRY, lnode / rnode stay n, f's matrices go
+//     to lm[0] / rm[0], f's tips to table slots 0 and 1 of the side (message rows), and the op's mask groups -- the child now has
+//     one -- are packed again into rows behind the post-order walk's; the op in front (or the chunk's prologue) requests those
+//     rows, both pieces of the block where the right child has tips now, and s's plane instead of n's.  n's own op reads s as before.
+// The descriptors and chunks as they were are kept (plain_desc, plain_chunks) for a pass that reads the reference's form; the
+// StreamOp rows (node ids, the host's bookkeeping) and the post-order walk's own kinds and mask groups stay plain as well.
+// After stream_pre_order and stream_post_order.
+inline void stream_elide(const Schedule &sc, const StreamGeometry &g, StreamTables &t) {
+	t.plain_desc = t.desc;
+	t.plain_chunks = t.chunks;
+	t.elisions.clear();
+	const int n = (int)t.lower_desc.size(), ns = (int)t.ops.size(), N = (int)sc.parent.size();
+	if (n == 0 || ns == 0) return;
+	const std::vector<NodeOp> &lops = sc.walk_lower_chunk_ops;
+	std::vector<int> sop(N, -1), lop(N, -1), lchunk(n, 0);
+	for (int i = 0; i < ns; i++) sop[sc.walk_chunk_ops[i].parent] = i;
+	for (int i = 0; i < n; i++) lop[lops[i].parent] = i;
+	for (int k = 0; k + 1 < (int)sc.walk_lower_chunk_off.size(); k++)
+		for (int i = sc.walk_lower_chunk_off[k]; i < sc.walk_lower_chunk_off[k + 1]; i++) lchunk[i] = k;
+	std::vector<char> in_e(N, 0);
+	std::vector<int> elided_at((size_t)ns * 2, -1);  // [pre-order op][side] -> index into t.elisions
+	for (int i = 0; i < n; i++) {  // children before parents: the cut subtrees' chunks, then the top part, each in post-order
+		const NodeOp &o = lops[i];
+		const int nd = o.parent, p = sc.parent[nd];
+		if (p < 0 || lop[p] < 0 || sop[p] < 0) continue;
+		const int kl = sc.node_kind[o.left], kr = sc.node_kind[o.right];
+		int s, f;
+		if (kl == CH_CORE && (kr == CH_TIP || kr == CH_CHERRY)) s = o.left, f = o.right;
+		else if (kr == CH_CORE && (kl == CH_TIP || kl == CH_CHERRY)) s = o.right, f = o.left;
+		else continue;
+		if (in_e[s] || lchunk[lop[p]] != lchunk[i]) continue;
+		const StreamOp &pu = t.ops[sop[p]];
+		const int side = pu.lnode == nd ? 0 : 1;
+		if ((side ? pu.rnode : pu.lnode) != nd || ((pu.flags >> (3 * side)) & 7) != CH_CORE) continue;
+		const int source = (t.lower_desc[lop[p]].flags >> (6 + 2 * side)) & 3;
+		if (source != 1 && source != 2) continue;
+		in_e[nd] = 1;
+		elided_at[(size_t)sop[p] * 2 + side] = (int)t.elisions.size();
+		t.elisions.push_back(StreamElision{nd, p, s, f, sc.node_kind[f], source, side, lchunk[i]});
+		t.lower_desc[i].flags |= 1 << 11;
+	}
+	if (t.elisions.empty()) return;
+	const int64_t plane_bytes = (int64_t)g.P * 4 * 8, array_bytes = plane_bytes * g.C, row_bytes = (int64_t)t.mstride * 4;
+	std::vector<int> chunk_of_start(ns, -1);
+	for (int k = 0; k + 1 < (int)sc.walk_chunk_off.size(); k++)
+		if (sc.walk_chunk_off[k] < sc.walk_chunk_off[k + 1]) chunk_of_start[sc.walk_chunk_off[k]] = k;
+	MaskPacker packer(t.row_entries);
+	for (int i = 0; i < ns; i++) {
+		if (elided_at[(size_t)i * 2] < 0 && elided_at[(size_t)i * 2 + 1] < 0) continue;
+		StreamDesc &d = t.desc[i];
+		int want[2] = {-1, -1};
+		for (int side = 0; side < 2; side++) {
+			if (elided_at[(size_t)i * 2 + side] < 0) continue;
+			const StreamElision &el = t.elisions[elided_at[(size_t)i * 2 + side]];
+			const NodeOp &o = lops[lop[el.node]];
+			const bool f_left = o.left == el.sibling;
+			int *tips = &t.op_tips[(size_t)i * 12 + 6 * side];
+			if (el.sibling_kind == CH_TIP) tips[0] = el.sibling;
+			else {
+				tips[0] = f_left ? o.lt0 : o.rt0;
+				tips[1] = f_left ? o.lt1 : o.rt1;
+			}
+			d.flags = (d.flags & ~(7 << (3 * side))) | (el.sibling_kind == CH_TIP ? SK_CORE_TIP : SK_CORE_CHERRY) << (3 * side);
+			(side ? d.rm : d.lm)[0] = el.sibling * g.C * 128;
+			want[side] = sc.core_index[el.stored];
+		}
+		// the op's mask groups again, the new ones among them: the left child's first, the second in the first one's row or the next
+		int words = 0, first_word = -1, same_row = 0, wsh = 0;
+		for (int side = 0; side < 2; side++)
+			if (((d.flags >> (3 * side)) & 7) != CH_CORE) {
+				int row, shift;
+				packer.add(&t.op_tips[(size_t)i * 12 + 6 * side], row, shift);
+				if (words == 0) first_word = row;
+				else same_row = row == first_word;
+				wsh |= shift << (5 * words);
+				words++;
+			}
+		d.wsh = wsh;
+		const int two_pieces = ((d.flags >> 3) & 7) != CH_CORE;
+		if (chunk_of_start[i] >= 0) {
+			StreamChunk &ch = t.chunks[chunk_of_start[i]];
+			ch.mask_word = first_word;
+			ch.mask_words = words;
+			ch.same_row = same_row;
+			if (want[0] >= 0) ch.a = want[0];
+			if (want[1] >= 0) ch.b = want[1];
+		} else {
+			StreamDesc &pv = t.desc[i - 1];
+			pv.flags = (pv.flags & ~(3 << 14 | 1 << 24 | 1 << 25)) | words << 14 | two_pieces << 24 | same_row << 25;
+			pv.nx_words = (int64_t)first_word * row_bytes;
+			if (want[0] >= 0) pv.nx_a = (int64_t)want[0] * array_bytes;
+			if (want[1] >= 0) pv.nx_b = (int64_t)want[1] * array_bytes;
+		}
+	}
+	t.words = (int)t.row_entries.size() / 8;
+}
+
+// both walks' tables (the post-order walk's mask rows follow the pre-order walk's; g.elide: stream_elide's rewrite of both)
 inline void build_stream_tables(const Schedule &sc, const StreamGeometry &g, StreamTables *out) {
 	stream_pre_order(sc, g, *out);
 	stream_post_order(sc, g, *out);
+	out->plain_desc.clear();
+	out->plain_chunks.clear();
+	out->elisions.clear();
+	if (g.elide) stream_elide(sc, g, *out);
 }
 
 // ---- the batched walks' op lists ----------------------------------------------------------------------------------------------

@@ -61,6 +61,9 @@ enum { BATCH_NONE = -1, BATCH_CARRY = -2, BATCH_ROOT = -3, BATCH_GHOST = -4 };  
 // ---- the streamed 4-state walks (phyamd_walk4s.inc) ----------------------------------------------------------------------------
 enum { HK_TIP = 0, HK_CHERRY = 1, HK_CHERRY_TIP = 2 };
 enum { SU_CARRY = 0, SU_LDS = 1, SU_U = 2, SU_ROOT = 3 };
+// kinds of a child that only the streamed pre-order walk's descriptors know (stream_elide, phyamd_tree_schedule.h): a stored node
+// that the post-order walk did not store, formed from its stored child (whose plane the op is handed) and its tip / cherry child
+enum { SK_CORE_TIP = 5, SK_CORE_CHERRY = 6 };
 
 // side: node, then a[10]: CH_CHERRY / CH_CHERRY_TIP: {t0, t1, t2, inner}; CH_DEEP: two halves {node, t0, t1, t2, inner}
 struct StreamOp {
@@ -112,8 +115,8 @@ constexpr int STREAM_PARK_SLOTS = 2;
 // one op of the streamed post-order walk (k_lower4_stream; the plumbing: phyamd_walk4s.inc, "the post-order walk on the same plumbing")
 struct LowerDesc {
 	int32_t flags;     // kl 0-2 | kr 3-5 | where a stored left child comes from 6-7 (0: memory, 1: the previous op's result, 2: the parked
-	                   // partial, 3: the one in the second slot) | same for the right child 8-9 | 10: park the result | 11: no store (no
-	                   // longer set) | 12-13: ring slot of the first mask row to request for the NEXT op | 14-15: how many rows to request
+	                   // partial, 3: the one in the second slot) | same for the right child 8-9 | 10: park the result | 11: no store
+	                   // (stream_elide; the TF instantiations) | 12-13: ring slot of the first mask row to request for the NEXT op | 14-15: how many rows to request
 	                   // for it (0..2: the rows it reads that no op before it has read) | half kinds 16-23 | 24 / 25: the next op's block
 	                   // needs its second / first piece | 26: park the result in the second slot
 	int32_t nx_block;  // table block of the next op

@@ -210,6 +210,16 @@ __device__ __forceinline__ d4 s_fringe_message(const SX &x, int kind, int node, 
 	return matvec4_opt<false>(x.M(node), p);
 }
 
+// message of a child the post-order walk did not store (SK_CORE_TIP / SK_CORE_CHERRY, stream_elide): t_n = P_n (m_f o t_s), t_s = the
+// stored child's array, which the op was handed in place of the node's own, m_f = the tip / cherry child's message from table slots
+// 0 and 1 of the side (fm: the cherry's matrices)
+template <int SIDE>
+__device__ __forceinline__ d4 s_elided_message(const SX &x, int kind, int node, int fm, unsigned w, const d4 &ts) {
+	d4 unused;
+	const d4 mf = kind == SK_CORE_TIP ? x.site_tip<SIDE, 0>(w) : s_fringe_message<SIDE, false>(x, CH_CHERRY, fm, 0, w, unused);
+	return matvec4_opt<false>(x.M(node), mul4(mf, ts));
+}
+
 // fringe child (cherry, cherry + tip) of an op: its upper u goes down in registers; SIDE = accumulator of this side (0 left, 1 right),
 // rows 1, 2 = the cherry's tips, row 3 = the inner cherry node, accumulator 2 row SIDE = the outer tip.
 // FIRST2: this descent makes the first entry of accumulator 2.
@@ -369,7 +379,9 @@ __device__ __forceinline__ d4 own_registers(const d4 &v) {
 	return r;
 }
 // TF: the stored children arrive as t = P p (the streamed post-order walk's TF variant stored them so: k_lower4_stream) -- a CORE
-// child's message is the stored array itself, sixteen multiply-adds and a matrix fewer per such child.
+// child's message is the stored array itself, sixteen multiply-adds and a matrix fewer per such child.  Its descriptors may name
+// children that walk did not store (SK_CORE_TIP / SK_CORE_CHERRY, s_elided_message); a child of such a kind counts as one with
+// tips (a mask group of its own, the second piece of the table block) and is a stored child in everything after its message.
 template <bool FOLD, int SCALE, bool AMBIG = false, bool TF = false>
 __global__ __launch_bounds__(STREAM_WAVES *WAVE, (SCALE || AMBIG) ? STREAM_MIN_WAVES_SCALE : STREAM_MIN_WAVES) void k_upper4_stream(
     const StreamDesc *__restrict__ ops, const StreamChunk *__restrict__ chunks, const int *__restrict__ chunk_off, int chunk_base, int nops, int P, int C, int nb,
@@ -523,13 +535,16 @@ __global__ __launch_bounds__(STREAM_WAVES *WAVE, (SCALE || AMBIG) ? STREAM_MIN_W
 		else if (kl == CH_TIP) bl = x.site_tip<0, 0>(wL);
 		else if (kl == CH_DEEP)
 			bl = matvec4_opt<false>(x.M(op.lnode), mul4(s_half<0, 0>(x, (fl >> 16) & 3, op.lm[0], op.lm[1], wL), s_half<0, 3>(x, (fl >> 18) & 3, op.lm[2], op.lm[3], wL)));
+		else if (TF && kl >= SK_CORE_TIP) bl = s_elided_message<0>(x, kl, op.lnode, op.lm[0], wL, A);  // (A = its stored child's array)
 		else bl = s_fringe_message<0, KEEP_BN>(x, kl, op.lnode, op.lm[4], wL, bnl);
 		if (kr == CH_CORE) br = TF ? own_registers(B) : matvec4_opt<false>(x.M(op.rnode), B);
 		else if (kr == CH_TIP) br = x.site_tip<1, 0>(wR);
 		else if (kr == CH_DEEP)
 			br = matvec4_opt<false>(x.M(op.rnode), mul4(s_half<1, 0>(x, (fl >> 20) & 3, op.rm[0], op.rm[1], wR), s_half<1, 3>(x, (fl >> 22) & 3, op.rm[2], op.rm[3], wR)));
+		else if (TF && kr >= SK_CORE_TIP) br = s_elided_message<1>(x, kr, op.rnode, op.rm[0], wR, B);
 		else br = s_fringe_message<1, KEEP_BN>(x, kr, op.rnode, op.rm[4], wR, bnr);
-		const int e_bl = EXP2 && kl == CH_CORE ? eA : 0, e_br = EXP2 && kr == CH_CORE ? eB : 0;  // (messages rebuilt from tips: no exponent)
+		// (messages rebuilt from tips: no exponent; a child formed from its stored child's array: that array's)
+		const int e_bl = EXP2 && (kl == CH_CORE || kl >= SK_CORE_TIP) ? eA : 0, e_br = EXP2 && (kr == CH_CORE || kr >= SK_CORE_TIP) ? eB : 0;
 		// the next op's table block, words and stored operands (A, B and U have been consumed; requesting them before the messages of
 		// DEEP and fringe children -- a third of an op's arithmetic earlier -- was measured: the longer lives of A / B / U spill)
 		__builtin_amdgcn_s_setprio(3);
@@ -601,7 +616,7 @@ __global__ __launch_bounds__(STREAM_WAVES *WAVE, (SCALE || AMBIG) ? STREAM_MIN_W
 		else ss.template add<1, 0, true>(ur_terms, br);
 		if (kl == CH_CHERRY_TIP) {
 			s_descend<0, true, KEEP_BN>(x, ss, CH_CHERRY_TIP, op.lnode, op.lm[4], ul_terms, wL, bnl);
-			if (kr >= CH_CHERRY) s_descend<1, false, KEEP_BN>(x, ss, kr, op.rnode, op.rm[4], ur_terms, wR, bnr);
+			if (kr == CH_CHERRY || kr == CH_CHERRY_TIP) s_descend<1, false, KEEP_BN>(x, ss, kr, op.rnode, op.rm[4], ur_terms, wR, bnr);
 			prev_tot = fold_sites<true>(ss.acc0, ss.acc1, ss.acc2);
 		} else if (kr == CH_CHERRY_TIP) {
 			if (kl == CH_CHERRY) s_descend<0, false, KEEP_BN>(x, ss, CH_CHERRY, op.lnode, op.lm[4], ul_terms, wL, bnl);
@@ -822,7 +837,10 @@ __global__ __launch_bounds__(STREAM_WAVES *WAVE, SCALE == 1 ? 4 : LSTREAM_MIN_WA
 			sfp2 = sfc;
 			efp2 = efc;
 		}
-		have_prev = !(fl & (1 << 11));  // (the host no longer sets bit 11)
+		// (bit 11, stream_elide: the pre-order walk forms this node from its stored child; only the forms that walk reads -- any other
+		// reader's pass, the rerun of require_reference_form, stores every node from the same descriptors.  The op that follows
+		// an unstored one issues no stores, so the op after it waits for everything: `stored` above)
+		have_prev = !(TF && (fl & (1 << 11)));
 		prev_store = op.store;
 		prev_ls = op.ls_store;
 	}
