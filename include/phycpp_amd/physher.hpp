@@ -311,6 +311,15 @@ class TreeLikelihoodInterface : public CallableModelInterface {
 	// evaluation hands it: the tree model's lengths, with a clock rate or mu folded in).  d1 and d2 may be null.  The tree model
 	// and this object's own state are unchanged.
 	void NNILogLikelihoods(const double *centralLengths, double *logLikelihoods, double *d1, double *d2);
+	// The central branch of every NNI neighbour of the tree model's tree optimised at once (one phyamd_nni_optimize call; see
+	// include/physher_amd.h for the rule): lengths, logLikelihoods, d1, d2 and iterations [3][2T-1] by the tree's node ids, in
+	// NNILogLikelihoods' rows and columns (NaN, iterations 0, at tips and the root); startLengths [3][2T-1], or null for the
+	// branch's own length; the optimum is sought in [lower, upper] until a step is no longer than tolerance, in at most
+	// maxIterations steps (an entry that runs out of them, or whose lnL is not finite, has a negative count).  Lengths and
+	// derivatives are in the engine's branch lengths, as for NNILogLikelihoods.  d1, d2 and iterations may be null.  The tree
+	// model and this object's own state are unchanged.
+	void NNIOptimize(const double *startLengths, double lower, double upper, double tolerance, int maxIterations, double *lengths, double *logLikelihoods, double *d1,
+	                 double *d2, int32_t *iterations);
 	// lnL of every SPR regraft of `count` prune nodes of the tree model's tree at once (one phyamd_spr_log_likelihoods call; see
 	// include/physher_amd.h for the move and the candidates): out [count][2T-1] by the tree's node ids, row i the prune node
 	// prune[i] (null: count = 2T-1 and row i is node i), column w the target edge; NaN where there is no candidate.  Lengths are

@@ -314,6 +314,37 @@ int phyamd_nni_log_likelihoods(phyamd_engine *e, int flags, const double *centra
  * phyamd_batch_profile), wall time of the call */
 typedef struct { int32_t candidates; int64_t scratch_bytes; double ms; } phyamd_nni_profile;
 int phyamd_get_nni_profile(phyamd_engine *e, phyamd_nni_profile *out);
+/* The central branch of every NNI neighbour optimised in one call: for every entry (k, v) of phyamd_nni_log_likelihoods -- the same
+ * candidates v, the same arrangements k = 0, 1, 2, NaN in the columns of tips and of the root (iterations: 0) -- the length of v in
+ * [lower, upper] that maximises the entry's lnL, found on the device by ONE walk of the engine's tree and then, per entry, an
+ * iteration that repeats no walk, no matrix launch and no host round trip (the four messages that meet on the edge do not depend
+ * on the length).  THE RULE, per entry: t = clamp(start, lower, upper), a = lower, b = upper, where start is start_lengths[k][v] or,
+ * with start_lengths NULL, the engine's t_v.  Each iteration evaluates d1(t) and d2(t); if d1 > 0 then a = t, else b = t; it
+ * proposes t' = t - d1 / d2 when d2 < 0 and a < t' < b, otherwise t' = (a + b) / 2; it stops when |t' - t| <= tolerance, and t* = t'.
+ * iterations[k][v] is the number of proposals made.  After max_iterations proposals without that the entry stops all the same:
+ * t* is the last proposal and the count is stored negated.  lengths[k][v] = t*; lnl, d1 and d2 are evaluated at t* and are, by
+ * definition, what phyamd_nni_log_likelihoods returns for the entry at central_lengths[k][v] = t* (here they are formed from the
+ * eigen system without the reference's fabs on P(t): a rounding difference).  A lnL that is not finite at an iterate ends the entry
+ * in band: lengths holds that iterate, lnl the value that is not finite, d1 and d2 NaN and iterations a negative count; the engine
+ * is never switched to rescaling.  d1, d2 and iterations may be NULL.
+ * The engine -- its topology, lengths, partials -- is unchanged and later evaluations return the bits they would have returned
+ * without the call; two calls return identical bits, and an entry's bits do not depend on the other candidates, on the chunks
+ * the entries ran in or on which optional outputs are asked for.  The scratch is the batch scratch's: the walk's item of
+ * phyamd_nni_log_likelihoods and per entry C x 4 doubles per pattern; candidates that do not fit the memory cap together run in
+ * chunks.  There is no fallback path: PHYAMD_EUNSUPPORTED, naming the condition, under phyamd_gradient_batch_trees' conditions (not
+ * 4 states, more than 8 categories, an engine that is rescaling now, tiled patterns, a tip cell with an empty state mask, explicit
+ * node matrices), when the scratch of the walk and one candidate does not fit the memory cap, for flags other than 0, and on a
+ * handle sharded over several devices (every iteration would need a sum across the shards).  PHYAMD_EINVAL: null engine, lengths
+ * or lnl, no eigen system, bounds that are not 0 <= lower < upper < inf, a tolerance that is not finite and positive,
+ * max_iterations outside 1..1000, a negative or non-finite start length of a candidate. */
+int phyamd_nni_optimize(phyamd_engine *e, int flags, const double *start_lengths /* [3][2T-1] or NULL: the engine's t_v */,
+                        double lower, double upper, double tolerance, int32_t max_iterations,
+                        double *lengths /* [3][2T-1] */, double *lnl /* [3][2T-1] */, double *d1 /* [3][2T-1] or NULL */,
+                        double *d2 /* [3][2T-1] or NULL */, int32_t *iterations /* [3][2T-1] or NULL */);
+/* of the last phyamd_nni_optimize: candidate edges, chunks of candidates they ran in, bytes of batch scratch the engine holds (see
+ * phyamd_batch_profile), proposals made over all entries, wall time of the call */
+typedef struct { int32_t candidates, chunks; int64_t scratch_bytes, iterations; double ms; } phyamd_nni_optimize_profile;
+int phyamd_get_nni_optimize_profile(phyamd_engine *e, phyamd_nni_optimize_profile *out);
 /* lnL of every SPR regraft of chosen subtrees of the engine's tree: per prune node ONE post-order and ONE pre-order walk of the
  * tree without it, then every target edge in one launch -- O(T) work per prune node and O(T^2) for the whole neighbourhood, where
  * phyamd_gradient_batch_trees walks each of the O(T^2) rearranged trees from the tips.

@@ -940,6 +940,13 @@ void TreeLikelihoodInterface::NNILogLikelihoods(const double *centralLengths, do
 	phyamd::check(phyamd_nni_log_likelihoods(impl_->engine, 0, centralLengths, logLikelihoods, d1, d2));
 }
 
+void TreeLikelihoodInterface::NNIOptimize(const double *startLengths, double lower, double upper, double tolerance, int maxIterations, double *lengths,
+                                          double *logLikelihoods, double *d1, double *d2, int32_t *iterations) {
+	if (!lengths || !logLikelihoods) throw Error("null lengths or logLikelihoods");
+	Sync();
+	phyamd::check(phyamd_nni_optimize(impl_->engine, 0, startLengths, lower, upper, tolerance, maxIterations, lengths, logLikelihoods, d1, d2, iterations));
+}
+
 void TreeLikelihoodInterface::SPRLogLikelihoods(const int *prune, int count, double *out) {
 	if (!out) throw Error("null out");
 	Sync();

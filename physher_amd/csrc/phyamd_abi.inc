@@ -615,6 +615,24 @@ int phyamd_get_nni_profile(phyamd_engine *g, phyamd_nni_profile *out) {
 	});
 }
 
+// one device only: every iteration of an entry would need its sums across the shards
+int phyamd_nni_optimize(phyamd_engine *g, int flags, const double *start_lengths, double lower, double upper, double tolerance, int32_t max_iterations, double *lengths,
+                        double *lnl, double *d1, double *d2, int32_t *iterations) {
+	static const char *const name = "phyamd_nni_optimize";
+	if (!lengths || !lnl) return fail(PHYAMD_EINVAL, "%s: null %s", name, !lengths ? "lengths" : "lnl");
+	CHECK_GROUP(g);
+	if (!(lower >= 0.0 && lower < upper && std::isfinite(upper))) return fail(PHYAMD_EINVAL, "%s: bounds [%g, %g]: they must be 0 <= lower < upper < inf", name, lower, upper);
+	if (!(tolerance > 0.0 && std::isfinite(tolerance))) return fail(PHYAMD_EINVAL, "%s: tolerance %g: it must be finite and positive", name, tolerance);
+	if (max_iterations < 1 || max_iterations > 1000) return fail(PHYAMD_EINVAL, "%s: max_iterations %d is outside 1..1000", name, max_iterations);
+	if (group_size(g) > 1)
+		return fail(PHYAMD_EUNSUPPORTED, "%s: a handle sharded over several devices is out of scope: every iteration of an entry would need a sum across the shards", name);
+	return shard_nni_optimize(g->shards[0], flags, NniOptimizeArgs{start_lengths, lower, upper, tolerance, max_iterations, lengths, lnl, d1, d2, iterations});
+}
+
+int phyamd_get_nni_optimize_profile(phyamd_engine *g, phyamd_nni_optimize_profile *out) {
+	return merged_profile(g, &Shard::cbopt_prof, out, [](phyamd_nni_optimize_profile &, const phyamd_nni_optimize_profile &) {});  // (never sharded)
+}
+
 // every shard scores every row on its patterns; the rows are sums over patterns, added in shard order (NaN cells stay NaN)
 int phyamd_spr_log_likelihoods(phyamd_engine *g, int flags, int32_t count, const int32_t *prune, double *lnl) {
 	if (count < 1) return fail(PHYAMD_EINVAL, "phyamd_spr_log_likelihoods: count must be >= 1 (got %d)", count);

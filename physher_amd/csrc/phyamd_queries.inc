@@ -627,6 +627,126 @@ int shard_nni_log_likelihoods(Shard *e, int flags, const double *central_lengths
 	});
 }
 
+// ---- the optimised central branch of every NNI neighbour (phyamd_nni_optimize) ------------------------------------------------
+
+// ONE item, as nni_plan's: the walk with every upper parked, its lists, the start lengths -- and for the `chunk` candidates that
+// run at once the coefficients and the results of their three entries (sizes: d_cbopt_K, d_cbopt_out, d_cbopt_iter)
+ScratchPlan cbopt_plan(Shard *e, size_t chunk) {
+	const size_t D = sizeof(double), N = (size_t)e->N, C = (size_t)e->C, nblk = ((size_t)e->P + WAVE - 1) / WAVE, cands = std::max<size_t>(nni_candidates(e), 1);
+	ScratchPlan p = batch_plan(e, true, e->T - 1, false);
+	p.add(e->d_nni_ops, 0, sizeof(BatchOp) * 2 * (size_t)(e->T - 1));
+	p.add(e->d_nni_cands, 0, sizeof(NniCand) * cands);
+	p.add(e->d_nni_cand_of, 0, sizeof(int32_t) * N);
+	p.add(e->d_nni_len, 0, D * 3 * N);
+	p.add(e->d_cbopt_K, 0, chunk * D * 3 * C * 4 * nblk * WAVE);
+	p.add(e->d_cbopt_out, 0, chunk * D * 3 * 4);
+	p.add(e->d_cbopt_iter, 0, chunk * sizeof(int32_t) * 3);
+	return p;
+}
+
+// the candidates of a chunk: all of them (at most gridDim.y's) if the scratch holds as much or has room for it, else what fits
+// beside the walk (0: not even one)
+size_t cbopt_chunk(Shard *e, size_t cands) {
+	const size_t want = std::min<size_t>(cands, BATCH_MAX_CHUNK);
+	if (batch_items_held(e, cbopt_plan(e, want)) >= 1) return want;
+	const ScratchPlan none = cbopt_plan(e, 0), one = cbopt_plan(e, 1);
+	const double walk = (double)(none.fixed_bytes() + none.item_bytes()), per = (double)(one.fixed_bytes() - none.fixed_bytes());
+	const double fit = std::floor((scratch_room(e, (double)batch_scratch_bytes(e), EngineRoom::MayGrow) - walk) / per);
+	return fit < 1.0 ? 0 : (size_t)std::min((double)want, fit);
+}
+
+struct NniOptimizeArgs {
+	const double *start;
+	double lower, upper, tolerance;
+	int32_t max_iterations;
+	double *lengths, *lnl, *d1, *d2;
+	int32_t *iterations;
+};
+
+// one walk of the engine's tree with every upper parked, then chunk by chunk the candidates' coefficients and their iterations.
+// Reads the engine's inputs and writes only the batch scratch: nothing in Shard::state changes
+int run_nni_optimize(Shard *e, int flags, const NniOptimizeArgs &o, phyamd_nni_optimize_profile &prof) {
+	static const char *const name = "phyamd_nni_optimize";
+	int rc;
+	if ((rc = check_ready(e))) return rc;
+	if (flags != 0) return fail(PHYAMD_EUNSUPPORTED, "%s: flags %d (no flags are defined: pass 0)", name, flags);
+	if (const char *why = tree_batch_refusal(e, 0, 1)) return fail(PHYAMD_EUNSUPPORTED, "%s: %s", name, why);
+	if (!e->have_eigen || !e->have_Q) return fail(PHYAMD_EINVAL, "%s needs the eigen system (phyamd_set_eigen): the likelihood in the central length is formed from it", name);
+	const int T = e->T, N = e->N, C = e->C;
+	std::vector<double> start((size_t)3 * N);
+	for (int k = 0; k < 3; k++) std::copy(e->lengths.begin(), e->lengths.end(), start.begin() + (size_t)k * N);
+	for (int v = T; v < N && o.start; v++) {
+		if (v == e->root) continue;
+		for (int k = 0; k < 3; k++) {
+			const double t = o.start[(size_t)k * N + v];
+			if (!std::isfinite(t) || t < 0.0) return fail(PHYAMD_EINVAL, "%s: start_lengths[%d][%d] = %g: a start length is finite and not negative", name, k, v, t);
+			start[(size_t)k * N + v] = t;
+		}
+	}
+	const size_t cands = nni_candidates(e), entries = (size_t)3 * N;
+	prof.candidates = (int32_t)cands;
+	std::fill(o.lengths, o.lengths + entries, NAN);
+	std::fill(o.lnl, o.lnl + entries, NAN);
+	if (o.d1) std::fill(o.d1, o.d1 + entries, NAN);
+	if (o.d2) std::fill(o.d2, o.d2 + entries, NAN);
+	if (o.iterations) std::fill(o.iterations, o.iterations + entries, 0);
+	if (cands == 0) return PHYAMD_OK;  // two tips: no internal edge
+	const size_t chunk = cbopt_chunk(e, cands);
+	if (chunk < 1) {
+		const ScratchPlan one = cbopt_plan(e, 1);
+		return fail(PHYAMD_EUNSUPPORTED, "%s: the scratch of one candidate (%zu bytes: every internal node's lower and upper partial, and its entries' coefficients) does not fit the memory budget",
+		            name, one.fixed_bytes() + one.item_bytes());
+	}
+	if ((rc = ensure_batch_scratch(e, 1, cbopt_plan(e, chunk))) || (rc = upload_nni_lists(e))) return rc;
+	const int nblk = (e->P + WAVE - 1) / WAVE, nops = T - 1;
+	HIP_TRY(hipMemcpyAsync(e->d_nni_len, start.data(), sizeof(double) * start.size(), hipMemcpyHostToDevice, e->stream));
+	launch_batch_matrices(e, 1, e->d_lengths, nullptr, e->d_batch_mats);  // the walk's item: the engine's lengths
+	const BatchOp *ops = e->d_nni_ops.get();
+	const BatchArgs walk{ops, ops + nops, 0, T, N, e->P, C, nblk, T - 1, 1, e->d_tipmask, e->d_freqs, e->d_props, e->d_weights, e->d_Q, e->d_batch_mats, e->d_batch_lower,
+	                     e->d_batch_upper, e->d_batch_lnl, e->d_batch_slab};
+	hipLaunchKernelGGL(k_batch_walk4<false>, dim3(nblk, 1), dim3(WAVE, C), 0, e->stream, walk);
+	HIP_TRY(hipGetLastError());
+	// (the candidates' nodes in d_nni_cands' order: upload_nni_lists')
+	std::vector<int> node;
+	for (int v = T; v < N; v++)
+		if (v != e->root) node.push_back(v);
+	std::vector<double> out;
+	std::vector<int32_t> iter;
+	for (size_t first = 0; first < cands; first += chunk) {
+		const size_t n = std::min(chunk, cands - first);
+		const CboptCoeffArgs ca{e->d_nni_cands.get() + first, T, N, e->P, C, nblk, e->d_tipmask, e->d_freqs, e->d_props, e->d_model, e->d_batch_mats, e->d_batch_lower,
+		                        e->d_batch_upper, e->d_cbopt_K};
+		hipLaunchKernelGGL(k_cbopt_coeff4, dim3(nblk, (unsigned)n), dim3(WAVE, C), 0, e->stream, ca);
+		const CboptSolveArgs sa{e->d_nni_cands.get() + first, N, e->P, C, nblk * WAVE, o.max_iterations, o.lower, o.upper, o.tolerance, e->d_model, e->d_rates, e->d_weights,
+		                        e->d_nni_len, e->d_cbopt_K, e->d_cbopt_out, e->d_cbopt_iter};
+		hipLaunchKernelGGL(k_cbopt_solve4, dim3((unsigned)(3 * n)), dim3(CBOPT_THREADS), 0, e->stream, sa);
+		HIP_TRY(hipGetLastError());
+		out.resize(n * 12);
+		iter.resize(n * 3);
+		HIP_TRY(hipMemcpyAsync(out.data(), e->d_cbopt_out, sizeof(double) * out.size(), hipMemcpyDeviceToHost, e->stream));
+		HIP_TRY(hipMemcpyAsync(iter.data(), e->d_cbopt_iter, sizeof(int32_t) * iter.size(), hipMemcpyDeviceToHost, e->stream));
+		HIP_TRY(hipStreamSynchronize(e->stream));  // (also covers `start`)
+		prof.chunks++;
+		for (size_t i = 0; i < n; i++)
+			for (int k = 0; k < 3; k++) {
+				const double *r = &out[(i * 3 + k) * 4];
+				const size_t at = (size_t)k * N + node[first + i];
+				o.lengths[at] = r[0];
+				o.lnl[at] = r[1];
+				if (o.d1) o.d1[at] = r[2];
+				if (o.d2) o.d2[at] = r[3];
+				if (o.iterations) o.iterations[at] = iter[i * 3 + k];
+				prof.iterations += std::abs(iter[i * 3 + k]);
+			}
+	}
+	return PHYAMD_OK;
+}
+
+int shard_nni_optimize(Shard *e, int flags, const NniOptimizeArgs &o) {
+	CHECK_ENGINE(e);
+	return profiled_call(e, &Shard::cbopt_prof, phyamd_nni_optimize_profile{}, [&](phyamd_nni_optimize_profile &prof) { return run_nni_optimize(e, flags, o, prof); });
+}
+
 // ---- every SPR regraft of chosen subtrees (phyamd_spr_log_likelihoods) ---------------------------------------------------------
 
 // the engine's tree's park_all op lists, where each internal node's op is in them, and every node's depth-first interval

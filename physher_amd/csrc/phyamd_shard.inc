@@ -234,6 +234,12 @@ struct Shard {
 	DeviceArray<double> d_nni_slab{&batch_mem}, d_nni_out{&batch_mem};  // [T - 2][blocks][9], [3 terms][3][N]
 	bool nni_lists_valid = false;        // d_nni_ops, d_nni_cands and d_nni_cand_of hold the engine's tree's (while they are allocated)
 	phyamd_nni_profile nni_prof{};
+	// phyamd_nni_optimize (phyamd_nniopt4.inc) runs the same walk with the same lists (the start lengths go through d_nni_len) and
+	// adds to the group, per candidate of a chunk: the coefficients of its three entries and their results
+	DeviceArray<double> d_cbopt_K{&batch_mem};       // [candidate][3][C][4][blocks * 64]
+	DeviceArray<double> d_cbopt_out{&batch_mem};     // [candidate][3][t*, lnL, d1, d2]
+	DeviceArray<int32_t> d_cbopt_iter{&batch_mem};   // [candidate][3]
+	phyamd_nni_optimize_profile cbopt_prof{};
 	// phyamd_spr_log_likelihoods (phyamd_spr4.inc) walks one item of the scratch above per prune node (a ROW), with its own op
 	// lists (d_batch_item_ops) and every upper parked (slots = T - 1), and adds to the group: per row the candidate edges, each
 	// cell's candidate index, the slab and the result; once the engine's lengths with their halves and the matrices of both.

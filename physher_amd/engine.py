@@ -266,6 +266,36 @@ class Engine:
         self._check(self._lib.phyamd_get_nni_profile(self._h, C.byref(p)))
         return {k: getattr(p, k) for k, _ in p._fields_}
 
+    def nni_optimize(self, start_lengths=None, lower=1e-8, upper=10.0, tolerance=1e-8, max_iterations=100, want_derivatives=True,
+                     want_iterations=True, flags=0):
+        """The central branch of every NNI neighbour optimised on the device: (lengths, lnl, d1, d2, iterations), each [3, N] in
+        nni_log_likelihoods' rows and columns (NaN, iterations 0, at tips and the root; d1, d2 / iterations None when not wanted).
+        Per entry the length of v in [lower, upper] that maximises its lnL, by a safeguarded Newton iteration from start_lengths
+        [3, N] (None: the branch's own length): d1 > 0 moves the bracket's low end to t, else its high end; the Newton step is
+        taken when d2 < 0 and it stays inside the bracket, else the bracket is halved; the entry stops on a step <= tolerance.
+        iterations: the steps proposed, negated where max_iterations ran out or lnL was not finite.  lnl, d1, d2 are those of
+        nni_log_likelihoods at the returned lengths.  The engine's tree, lengths and partials stay.  No fallback: EngineError
+        where nni_log_likelihoods refuses, and on a sharded engine."""
+        sl = None
+        if start_lengths is not None:
+            sl = _f64(start_lengths)
+            if sl.shape != (3, self.N):
+                raise ValueError(f"start_lengths must be [3, {self.N}] (got {sl.shape})")
+        lengths, lnl = np.empty((3, self.N)), np.empty((3, self.N))
+        d1 = np.empty((3, self.N)) if want_derivatives else None
+        d2 = np.empty((3, self.N)) if want_derivatives else None
+        it = np.empty((3, self.N), dtype=np.int32) if want_iterations else None
+        self._check(self._lib.phyamd_nni_optimize(self._h, flags, None if sl is None else _ptr(sl), lower, upper, tolerance, max_iterations,
+                                                  _ptr(lengths), _ptr(lnl), None if d1 is None else _ptr(d1), None if d2 is None else _ptr(d2),
+                                                  None if it is None else _ptr(it)))
+        return lengths, lnl, d1, d2, it
+
+    def nni_optimize_profile(self):
+        """Of the last nni_optimize: candidates, chunks (of candidates), scratch_bytes, iterations (over all entries), ms."""
+        p = _lib.NniOptimizeProfile()
+        self._check(self._lib.phyamd_get_nni_optimize_profile(self._h, C.byref(p)))
+        return {k: getattr(p, k) for k, _ in p._fields_}
+
     def spr_log_likelihoods(self, prune=None, flags=0):
         """Every SPR regraft of the prune nodes' subtrees at once: lnl [count, N].  Row i prunes node prune[i] (None: every node, row
         i is node i); column w regrafts it onto the edge above w: with u the prune node's parent and s its sibling, s takes u's
