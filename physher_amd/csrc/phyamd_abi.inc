@@ -206,30 +206,44 @@ void ensure_scratch(phyamd_engine *g, size_t count) {
 		if (v.size() < count) v.resize(count);
 }
 
-// fn(shard, out) leaves a shard's `count` doubles in out: one shard writes `total` itself, several write their scratch vectors
-// at once and `total` is their sum (sum_shards).  What a shard masked in band the caller masks again by the summed lnL
+// fn(shard, index, out) leaves a shard's `count` doubles in out: one shard writes `total` itself, several write their scratch
+// vectors at once and `total` is their sum (sum_shards).  What a shard masked in band the caller masks again by the summed lnL
 template <typename F>
 int sum_over_shards(phyamd_engine *g, size_t count, double *total, F fn) {
-	if (group_size(g) == 1) return fn(g->shards[0], total);
+	if (group_size(g) == 1) return fn(g->shards[0], 0, total);
 	ensure_scratch(g, count);
 	int rc;
-	if ((rc = for_shards(g, [&](Shard *s, int i) { return fn(s, g->scratch[i].data()); }))) return rc;
+	if ((rc = for_shards(g, [&](Shard *s, int i) { return fn(s, i, g->scratch[i].data()); }))) return rc;
 	sum_shards(g, count, total);
 	return PHYAMD_OK;
 }
 
-// a batch on several shards: fn(shard, lnl [count], cat_gradient [count][N C] or null) into the shard's scratch vector, laid out
-// [lnl | cat_gradient], and the sums unpacked into the caller's arrays
+// a packed vector [part | part | ...] into the caller's arrays, part by part (array, doubles); a null array's part is skipped
+void unpack(const double *packed, std::initializer_list<std::pair<double *, size_t>> parts) {
+	for (const auto &[to, count] : parts) {
+		if (to) std::memcpy(to, packed, sizeof(double) * count);
+		packed += count;
+	}
+}
+
+// a batch on several shards: fn(shard, index, lnl [count], cat_gradient [count][N C] or null) into the shard's scratch vector,
+// laid out [lnl | cat_gradient], and the sums unpacked into the caller's arrays
 template <typename F>
 int sum_batch_over_shards(phyamd_engine *g, int32_t count, double *lnl, double *cat_gradient, F fn) {
 	const size_t ncat = (size_t)g->N * g->C, n = (size_t)count * (cat_gradient ? 1 + ncat : 1);
 	std::vector<double> total(n);
 	int rc;
-	if ((rc = sum_over_shards(g, n, total.data(), [&](Shard *s, double *v) { return fn(s, v, cat_gradient ? v + count : nullptr); }))) return rc;
-	std::memcpy(lnl, total.data(), sizeof(double) * count);
-	if (cat_gradient) std::memcpy(cat_gradient, total.data() + count, sizeof(double) * count * ncat);
+	if ((rc = sum_over_shards(g, n, total.data(), [&](Shard *s, int i, double *v) { return fn(s, i, v, cat_gradient ? v + count : nullptr); }))) return rc;
+	unpack(total.data(), {{lnl, (size_t)count}, {cat_gradient, (size_t)count * ncat}});
 	return PHYAMD_OK;
 }
+
+// the wall time of a group-level call, into *ms when the call returns
+struct WallTime {
+	double *ms;
+	std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+	~WallTime() { *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
 
 // the profile of a query call: the first shard's, the others' merged in by the call's own rule
 template <typename Prof, typename Merge>
@@ -375,12 +389,7 @@ int phyamd_synchronize(phyamd_engine *g) {
 int phyamd_log_likelihood(phyamd_engine *g, double *lnl) {
 	CHECK_GROUP(g);
 	if (!lnl) return fail(PHYAMD_EINVAL, "null lnl");
-	if (group_size(g) == 1) return shard_log_likelihood(g->shards[0], lnl);
-	ensure_scratch(g, 1);
-	int rc;
-	if ((rc = for_shards(g, [&](Shard *s, int i) { return shard_log_likelihood(s, g->scratch[i].data()); }))) return rc;
-	sum_shards(g, 1, lnl);
-	return PHYAMD_OK;
+	return sum_over_shards(g, 1, lnl, [&](Shard *s, int, double *v) { return shard_log_likelihood(s, v); });
 }
 
 int phyamd_gradient(phyamd_engine *g, int flags, double *lnl, double *cat_gradient) {
@@ -388,15 +397,11 @@ int phyamd_gradient(phyamd_engine *g, int flags, double *lnl, double *cat_gradie
 	if (!cat_gradient) return fail(PHYAMD_EINVAL, "null cat_gradient");
 	if (group_size(g) == 1) return shard_gradient(g->shards[0], flags, lnl, cat_gradient);
 	const size_t n = (size_t)g->N * g->C;
-	ensure_scratch(g, 1 + n);
+	std::vector<double> total(1 + n);
 	int rc;
 	// a shard whose own lnL is NaN / inf hands back an all-NaN gradient (treelikelihood.c:327-332): the sums inherit it
-	if ((rc = for_shards(g, [&](Shard *s, int i) { return shard_gradient(s, flags, g->scratch[i].data(), g->scratch[i].data() + 1); }))) return rc;
-	double total;
-	sum_shards(g, 1, &total);
-	if (lnl) *lnl = total;
-	for (int s = 0; s < group_size(g); s++) std::memmove(g->scratch[s].data(), g->scratch[s].data() + 1, sizeof(double) * n);
-	sum_shards(g, n, cat_gradient);
+	if ((rc = sum_over_shards(g, total.size(), total.data(), [&](Shard *s, int, double *v) { return shard_gradient(s, flags, v, v + 1); }))) return rc;
+	unpack(total.data(), {{lnl, 1}, {cat_gradient, n}});
 	return PHYAMD_OK;
 }
 
@@ -427,23 +432,21 @@ int phyamd_parameter_gradient(phyamd_engine *g, int flags, double *lnl, double *
 	const size_t ncat = (size_t)g->N * g->C, np = (size_t)g->shards[0]->np;
 	std::vector<double> total(1 + ncat + np);
 	int rc;
-	if ((rc = sum_over_shards(g, total.size(), total.data(), [&](Shard *s, double *v) { return shard_parameter_gradient(s, flags, v, v + 1, v + 1 + ncat); }))) return rc;
-	if (lnl) *lnl = total[0];
-	if (cat_gradient) std::memcpy(cat_gradient, total.data() + 1, sizeof(double) * ncat);
-	std::memcpy(parameter_gradient, total.data() + 1 + ncat, sizeof(double) * np);
+	if ((rc = sum_over_shards(g, total.size(), total.data(), [&](Shard *s, int, double *v) { return shard_parameter_gradient(s, flags, v, v + 1, v + 1 + ncat); }))) return rc;
+	unpack(total.data(), {{lnl, 1}, {cat_gradient, ncat}, {parameter_gradient, np}});
 	return PHYAMD_OK;
 }
 
 int phyamd_root_invariant_term(phyamd_engine *g, double *out) {
 	CHECK_GROUP(g);
 	if (!out) return fail(PHYAMD_EINVAL, "null out");
-	return sum_over_shards(g, 1, out, [&](Shard *s, double *v) { return shard_root_invariant_term(s, v); });
+	return sum_over_shards(g, 1, out, [&](Shard *s, int, double *v) { return shard_root_invariant_term(s, v); });
 }
 
 int phyamd_root_frequency_term(phyamd_engine *g, double *out) {
 	CHECK_GROUP(g);
 	if (!out) return fail(PHYAMD_EINVAL, "null out");
-	return sum_over_shards(g, (size_t)g->S, out, [&](Shard *s, double *v) { return shard_root_frequency_term(s, v); });
+	return sum_over_shards(g, (size_t)g->S, out, [&](Shard *s, int, double *v) { return shard_root_frequency_term(s, v); });
 }
 
 int phyamd_branch_log_likelihood(phyamd_engine *g, int node, double length, double *lnl, double *d1, double *d2) {
@@ -452,10 +455,8 @@ int phyamd_branch_log_likelihood(phyamd_engine *g, int node, double length, doub
 	// lnL(t), its first and second derivative are sums over patterns, shard by shard
 	double total[3];
 	int rc;
-	if ((rc = sum_over_shards(g, 3, total, [&](Shard *s, double *v) { return shard_branch_log_likelihood(s, node, length, v, v + 1, v + 2); }))) return rc;
-	if (lnl) *lnl = total[0];
-	if (d1) *d1 = total[1];
-	if (d2) *d2 = total[2];
+	if ((rc = sum_over_shards(g, 3, total, [&](Shard *s, int, double *v) { return shard_branch_log_likelihood(s, node, length, v, v + 1, v + 2); }))) return rc;
+	unpack(total, {{lnl, 1}, {d1, 1}, {d2, 1}});
 	return PHYAMD_OK;
 }
 
@@ -466,11 +467,9 @@ int phyamd_branch_hessian_diagonal(phyamd_engine *g, int flags, double *lnl, dou
 	std::vector<double> total(n);
 	int rc;
 	// per-shard sums added like the gradient's: 2 / 4 / 8 shards cut by the engine's bisection give the one-engine bits
-	if ((rc = sum_over_shards(g, n, total.data(), [&](Shard *s, double *v) { return shard_branch_hessian_diagonal(s, flags, v); }))) return rc;
+	if ((rc = sum_over_shards(g, n, total.data(), [&](Shard *s, int, double *v) { return shard_branch_hessian_diagonal(s, flags, v); }))) return rc;
 	mask_if_not_finite(total[0], total.data() + 1, n - 1);
-	*lnl = total[0];
-	if (d1) std::memcpy(d1, total.data() + 1, sizeof(double) * g->N);
-	std::memcpy(d2, total.data() + 1 + g->N, sizeof(double) * g->N);
+	unpack(total.data(), {{lnl, 1}, {d1, (size_t)g->N}, {d2, (size_t)g->N}});
 	return PHYAMD_OK;
 }
 
@@ -480,7 +479,7 @@ int phyamd_gradient_batch(phyamd_engine *g, int flags, int32_t count, const doub
 	if (!branch_lengths || !lnl) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch: null branch_lengths or lnl");
 	CHECK_GROUP(g);
 	if (group_size(g) == 1) return shard_gradient_batch(g->shards[0], flags, count, branch_lengths, lnl, cat_gradient);
-	return sum_batch_over_shards(g, count, lnl, cat_gradient, [&](Shard *s, double *l, double *cg) { return shard_gradient_batch(s, flags, count, branch_lengths, l, cg); });
+	return sum_batch_over_shards(g, count, lnl, cat_gradient, [&](Shard *s, int, double *l, double *cg) { return shard_gradient_batch(s, flags, count, branch_lengths, l, cg); });
 }
 
 // every shard runs the whole batch of trees on its patterns; per-item results are added like phyamd_gradient_batch's
@@ -490,7 +489,7 @@ int phyamd_gradient_batch_trees(phyamd_engine *g, int flags, int32_t count, cons
 	if (!left || !right || !roots || !branch_lengths || !lnl) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch_trees: null left, right, roots, branch_lengths or lnl");
 	CHECK_GROUP(g);
 	if (group_size(g) == 1) return shard_gradient_batch_trees(g->shards[0], flags, count, left, right, roots, branch_lengths, lnl, cat_gradient);
-	return sum_batch_over_shards(g, count, lnl, cat_gradient, [&](Shard *s, double *l, double *cg) { return shard_gradient_batch_trees(s, flags, count, left, right, roots, branch_lengths, l, cg); });
+	return sum_batch_over_shards(g, count, lnl, cat_gradient, [&](Shard *s, int, double *l, double *cg) { return shard_gradient_batch_trees(s, flags, count, left, right, roots, branch_lengths, l, cg); });
 }
 
 // every shard runs the whole batch on its own pattern columns of `weights`; per-item results are added like phyamd_gradient_batch's
@@ -506,8 +505,7 @@ int phyamd_gradient_batch_weights(phyamd_engine *g, int flags, int32_t count, co
 			if (!(w >= 0.0) || std::isinf(w)) return fail(PHYAMD_EINVAL, "%s: weights of item %zu: pattern %zu has weight %g (a weight is finite and >= 0)", name, b, k, w);
 		}
 	if (group_size(g) == 1) return shard_gradient_batch_weights(g->shards[0], flags, count, weights, P, branch_lengths, lnl, cat_gradient);
-	return sum_batch_over_shards(g, count, lnl, cat_gradient, [&](Shard *s, double *l, double *cg) {
-		const size_t i = (size_t)(std::find(g->shards.begin(), g->shards.end(), s) - g->shards.begin());
+	return sum_batch_over_shards(g, count, lnl, cat_gradient, [&](Shard *s, int i, double *l, double *cg) {
 		return shard_gradient_batch_weights(s, flags, count, weights + g->offset[i], P, branch_lengths, l, cg);
 	});
 }
@@ -555,14 +553,12 @@ int phyamd_pattern_log_likelihoods_trees(phyamd_engine *g, int flags, int32_t co
 	const size_t n = (size_t)count * (1 + R);  // [lnl | replicate_lnl [R][count]]
 	std::vector<double> total(n);
 	int rc;
-	if ((rc = sum_over_shards(g, n, total.data(), [&](Shard *s, double *v) {
-		     const size_t i = (size_t)(std::find(g->shards.begin(), g->shards.end(), s) - g->shards.begin());
+	if ((rc = sum_over_shards(g, n, total.data(), [&](Shard *s, int i, double *v) {
 		     return shard_pattern_log_likelihoods_trees(s, flags, count, left, right, roots, branch_lengths, v, pattern_lnl ? pattern_lnl + g->offset[i] : nullptr, P,
 		                                                replicate_count, R ? replicate_weights + g->offset[i] : nullptr, P, R ? v + count : nullptr);
 	     })))
 		return rc;
-	std::memcpy(lnl, total.data(), sizeof(double) * count);
-	if (R) std::memcpy(replicate_lnl, total.data() + count, sizeof(double) * R * count);
+	unpack(total.data(), {{lnl, (size_t)count}, {replicate_lnl, R * count}});
 	for (size_t b = 0; b < (size_t)count && R; b++)  // (what a shard masked in band is masked again by the summed lnL)
 		if (not_finite(lnl[b]))
 			for (size_t r = 0; r < R; r++) replicate_lnl[r * (size_t)count + b] = NAN;
@@ -599,11 +595,9 @@ int phyamd_nni_log_likelihoods(phyamd_engine *g, int flags, const double *centra
 	const bool deriv = d1 || d2;
 	std::vector<double> total(n);
 	int rc;
-	if ((rc = sum_over_shards(g, n, total.data(), [&](Shard *s, double *v) { return shard_nni_log_likelihoods(s, flags, central_lengths, deriv, v); }))) return rc;
+	if ((rc = sum_over_shards(g, n, total.data(), [&](Shard *s, int, double *v) { return shard_nni_log_likelihoods(s, flags, central_lengths, deriv, v); }))) return rc;
 	nni_mask_derivatives(entries, total.data());
-	std::memcpy(lnl, total.data(), sizeof(double) * entries);
-	if (d1) std::memcpy(d1, total.data() + entries, sizeof(double) * entries);
-	if (d2) std::memcpy(d2, total.data() + 2 * entries, sizeof(double) * entries);
+	unpack(total.data(), {{lnl, entries}, {d1, entries}, {d2, entries}});
 	return PHYAMD_OK;
 }
 
@@ -638,10 +632,8 @@ int phyamd_spr_log_likelihoods(phyamd_engine *g, int flags, int32_t count, const
 	if (count < 1) return fail(PHYAMD_EINVAL, "phyamd_spr_log_likelihoods: count must be >= 1 (got %d)", count);
 	if (!lnl) return fail(PHYAMD_EINVAL, "phyamd_spr_log_likelihoods: null lnl");
 	CHECK_GROUP(g);
-	const auto t0 = std::chrono::steady_clock::now();
-	const int rc = sum_over_shards(g, (size_t)count * g->N, lnl, [&](Shard *s, double *v) { return shard_spr_log_likelihoods(s, flags, count, prune, v); });
-	g->spr_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-	return rc;
+	const WallTime timed{&g->spr_ms};
+	return sum_over_shards(g, (size_t)count * g->N, lnl, [&](Shard *s, int, double *v) { return shard_spr_log_likelihoods(s, flags, count, prune, v); });
 }
 
 int phyamd_get_spr_profile(phyamd_engine *g, phyamd_spr_profile *out) {
@@ -686,22 +678,15 @@ int phyamd_site_rate_posteriors(phyamd_engine *g, double *posteriors, double *me
 int phyamd_branch_hessian(phyamd_engine *g, int flags, double *lnl, double *gradient, double *hessian) {
 	if (!lnl || !hessian) return fail(PHYAMD_EINVAL, "phyamd_branch_hessian: null %s", !lnl ? "lnl" : "hessian");
 	if (!g || g->shards.empty()) return fail(PHYAMD_EINVAL, "phyamd_branch_hessian: null engine");
-	const auto t0 = std::chrono::steady_clock::now();
+	const WallTime timed{&g->bhess_ms};
+	if (group_size(g) == 1) return shard_branch_hessian(g->shards[0], flags, lnl, gradient, hessian);
+	const size_t N = (size_t)g->N;
+	std::vector<double> total(1 + N + N * N);  // [lnl | gradient [N] | hessian [N][N]]
 	int rc;
-	if (group_size(g) == 1) rc = shard_branch_hessian(g->shards[0], flags, lnl, gradient, hessian);
-	else {
-		const size_t N = (size_t)g->N;
-		std::vector<double> total(1 + N + N * N);  // [lnl | gradient [N] | hessian [N][N]]
-		rc = sum_over_shards(g, total.size(), total.data(), [&](Shard *s, double *v) { return shard_branch_hessian(s, flags, v, v + 1, v + 1 + N); });
-		if (!rc) {
-			mask_if_not_finite(total[0], total.data() + 1, N + N * N);
-			*lnl = total[0];
-			if (gradient) std::memcpy(gradient, total.data() + 1, sizeof(double) * N);
-			std::memcpy(hessian, total.data() + 1 + N, sizeof(double) * N * N);
-		}
-	}
-	g->bhess_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-	return rc;
+	if ((rc = sum_over_shards(g, total.size(), total.data(), [&](Shard *s, int, double *v) { return shard_branch_hessian(s, flags, v, v + 1, v + 1 + N); }))) return rc;
+	mask_if_not_finite(total[0], total.data() + 1, N + N * N);
+	unpack(total.data(), {{lnl, 1}, {gradient, N}, {hessian, N * N}});
+	return PHYAMD_OK;
 }
 
 int phyamd_get_hessian_profile(phyamd_engine *g, phyamd_hessian_profile *out) {
@@ -779,177 +764,7 @@ int phyamd_get_node_matrices(phyamd_engine *g, int node, int derivative, double 
 	return shard_get_node_matrices(g->shards[0], node, derivative, out);
 }
 
-// the post-order walk's chunked op list of a tree as the streamed walk runs it: host code only (no device, no engine)
-int phyamd_post_order_parks(int32_t tip_count, const int32_t *left, const int32_t *right, int32_t root, int32_t second_slot, int32_t *out, int32_t capacity) {
-	if (tip_count < 2) return fail(PHYAMD_EINVAL, "tip_count must be >= 2 (got %d)", tip_count);
-	if (!left || !right) return fail(PHYAMD_EINVAL, "null left or right");
-	if (capacity < 0 || (capacity > 0 && !out)) return fail(PHYAMD_EINVAL, "null out with capacity %d", capacity);
-	ScheduleOptions options;  // 4 states, an engine's defaults
-	options.lower_park2_on = second_slot != 0;
-	Schedule sched;
-	const std::string err = build_schedule(TreeRef{tip_count, left, right, root}, options, &sched);
-	if (!err.empty()) return fail(PHYAMD_EINVAL, "%s", err.c_str());
-	const std::vector<NodeOp> &ops = sched.walk_lower_chunk_ops;
-	const std::vector<int> &off = sched.walk_lower_chunk_off;
-	std::vector<char> is_cut_root(2 * tip_count - 1, 0);  // the roots of the cut subtrees: every chunk's last op but the top part's
-	for (size_t k = 1; k + 1 < off.size(); k++)
-		if (off[k] > off[k - 1]) is_cut_root[ops[off[k] - 1].parent] = 1;
-	int chunk = 0;
-	for (int i = 0; i < (int)ops.size() && i < capacity; i++) {
-		const NodeOp &o = ops[i];
-		while (i >= off[chunk + 1]) chunk++;
-		auto source = [&](int side) {
-			if ((side ? o.kind_right : o.kind_left) != CH_CORE) return -1;
-			return o.carry_in == side + 1 ? 1 : (o.lds_park & (1 << side)) ? 2 : (o.lds_park & (0x10 << side)) ? 3 : 0;
-		};
-		const int32_t rec[8] = {chunk, o.parent, o.left, o.right, source(0), source(1), ((o.lds_park & 4) ? 1 : 0) | ((o.lds_park & 0x40) ? 2 : 0),
-		                        (is_cut_root[o.left] ? 1 : 0) | (is_cut_root[o.right] ? 2 : 0)};
-		std::memcpy(out + (size_t)i * 8, rec, sizeof(rec));
-	}
-	return (int)ops.size();
-}
-
-// the post-order pass of a tree as k_sitelnl_walk4 runs it: host code only (no device, no engine)
-int phyamd_post_order_slots(int32_t tip_count, const int32_t *left, const int32_t *right, int32_t root, int32_t *out, int32_t capacity, int32_t *slots) {
-	static const char *const name = "phyamd_post_order_slots";
-	if (tip_count < 2) return fail(PHYAMD_EINVAL, "%s: tip_count must be >= 2 (got %d)", name, tip_count);
-	if (!left || !right) return fail(PHYAMD_EINVAL, "%s: null left or right", name);
-	if (capacity < 0 || (capacity > 0 && !out)) return fail(PHYAMD_EINVAL, "%s: null out with capacity %d", name, capacity);
-	std::vector<int32_t> parents;
-	const std::string err = validate_tree(TreeRef{tip_count, left, right, root}, parents, name, 0);
-	if (!err.empty()) return fail(PHYAMD_EINVAL, "%s", err.c_str());
-	std::vector<BatchOp> work, ops;
-	const int used = site_lnl_ops(tip_count, left, right, root, work, &ops);
-	if (slots) *slots = used;
-	for (int i = 0; i < (int)ops.size() && i < capacity; i++) {
-		const BatchOp &o = ops[i];
-		const int32_t rec[6] = {o.node, o.left, o.right, o.src, o.dst_left, o.dst_right};
-		std::memcpy(out + (size_t)i * 6, rec, sizeof(rec));
-	}
-	return (int)ops.size();
-}
-
-// the pre-order walk's op list of a tree as one of its readers runs it: host code only (no device, no engine)
-int phyamd_pre_order_schedule(int32_t tip_count, const int32_t *left, const int32_t *right, int32_t root, int32_t form, int32_t *out, int32_t capacity,
-                              int32_t *hbm_slots) {
-	constexpr int W = PHYAMD_PRE_ORDER_COLUMNS;
-	enum { S_ROOT = 0, S_CARRY = 1, S_LDS0 = 2, S_LDS1 = 3, S_HBM = 4, D_NONE = 0 };  // (destinations: the same codes, 0 = none)
-	if (tip_count < 2) return fail(PHYAMD_EINVAL, "tip_count must be >= 2 (got %d)", tip_count);
-	if (!left || !right) return fail(PHYAMD_EINVAL, "null left or right");
-	if (form < 0 || form > 2) return fail(PHYAMD_EINVAL, "form must be 0 (chunked list), 1 (streamed walk) or 2 (one list), got %d", form);
-	if (capacity < 0 || (capacity > 0 && !out)) return fail(PHYAMD_EINVAL, "null out with capacity %d", capacity);
-	const int N = 2 * tip_count - 1;
-	Schedule sched;  // 4 states, an engine's defaults; the streamed walk's tables for one pattern of one category
-	StreamTables stream_tab;
-	const std::string err = build_schedule(TreeRef{tip_count, left, right, root}, ScheduleOptions{}, &sched);
-	if (!err.empty()) return fail(PHYAMD_EINVAL, "%s", err.c_str());
-	if (form == 1) build_stream_tables(sched, StreamGeometry{1, 1, WAVE}, &stream_tab);
-	const std::vector<NodeOp> &ops = form == 2 ? sched.walk_upper_ops : sched.walk_chunk_ops;
-	const std::vector<int> one_chunk{0, (int)ops.size()};
-	const std::vector<int> &off = form == 2 ? one_chunk : sched.walk_chunk_off;
-	if (hbm_slots) {
-		*hbm_slots = sched.walk_chunk_slots;
-		if (form == 2) {  // (walk_upper_slots has become the larger of the two lists' counts: the one list's own is its highest index + 1)
-			int most = -1;
-			for (const NodeOp &o : ops) most = std::max({most, o.upper_slot_parent, o.upper_slot_left, o.upper_slot_right});
-			*hbm_slots = most + 1;
-		}
-	}
-	std::vector<char> has_op(N, 0), is_cut_root(N, 0);  // the roots of the cut subtrees: every chunk's first op but the top part's
-	for (const NodeOp &o : ops) has_op[o.parent] = 1;
-	for (size_t k = 1; k + 1 < off.size(); k++)
-		if (off[k + 1] > off[k]) is_cut_root[ops[off[k]].parent] = 1;
-	auto half_ch = [](int hk) { return hk == HK_TIP ? (int)CH_TIP : hk == HK_CHERRY ? (int)CH_CHERRY : (int)CH_CHERRY_TIP; };
-	int chunk = 0;
-	for (int i = 0; i < (int)ops.size() && i < capacity; i++) {
-		while (i >= off[chunk + 1]) chunk++;
-		int32_t rec[W];
-		for (int j = 0; j < W; j++) rec[j] = -1;
-		rec[0] = chunk;
-		int32_t *q = rec + 20;
-		int nq = 0;
-		if (form == 1) {  // what k_upper4_stream reads: the descriptor's flags and slots
-			const StreamOp &s = stream_tab.ops[i];
-			const int fl = stream_tab.desc[i].flags, kl = fl & 7, kr = (fl >> 3) & 7, usrc = (fl >> 9) & 7, pk = (fl >> 12) & 3;
-			rec[1] = s.parent;
-			rec[2] = s.lnode;
-			rec[3] = s.rnode;
-			rec[4] = kl;
-			rec[5] = kr;
-			if (kl == CH_DEEP) rec[6] = half_ch((fl >> 16) & 3), rec[7] = half_ch((fl >> 18) & 3);
-			if (kr == CH_DEEP) rec[8] = half_ch((fl >> 20) & 3), rec[9] = half_ch((fl >> 22) & 3);
-			rec[10] = usrc == SU_ROOT ? S_ROOT : usrc == SU_CARRY ? S_CARRY : usrc == SU_LDS ? (((fl >> 7) & 1) ? S_LDS1 : S_LDS0) : S_HBM;
-			rec[11] = usrc == SU_U ? s.slot_parent : -1;
-			for (int side = 0; side < 2; side++) {
-				const bool stored = fl & (1 << (29 + side));
-				const int slot = side ? s.slot_right : s.slot_left;
-				int d = D_NONE;
-				if (pk == side + 1) d = ((fl >> 6) & 1) ? S_LDS1 : S_LDS0;
-				else if (stored) d = S_HBM;
-				else if (side == 0 && has_op[s.lnode]) d = S_CARRY;  // (the kernel hands `ul` on, always: neither parked nor stored = carried)
-				rec[12 + 2 * side] = d;
-				rec[13 + 2 * side] = stored ? slot : -1;
-			}
-			rec[16] = (fl & (1 << 28)) ? s.nx_u : -1;
-			rec[18] = rec[12] == S_CARRY ? 1 : 0;  // (after stream_pre_order's swap the carried child, if any, is the left one)
-			for (int j = 0; j < 10; j++) {
-				const int at = stream_tab.site_tab[(size_t)i * 16 + j];
-				if (at >= 0) q[nq++] = stream_tab.qnode[at / 8];
-			}
-		} else {  // what k_upper4_walk reads: the NodeOp itself (form 2: its PARAMS form, which has no LDS slot)
-			const NodeOp &o = ops[i];
-			const bool lpark = form == 0;
-			rec[1] = o.parent;
-			rec[2] = o.left;
-			rec[3] = o.right;
-			rec[4] = o.kind_left;
-			rec[5] = o.kind_right;
-			if (o.kind_left == CH_DEEP) rec[6] = sched.deep_host[o.left].kind_left, rec[7] = sched.deep_host[o.left].kind_right;
-			if (o.kind_right == CH_DEEP) rec[8] = sched.deep_host[o.right].kind_left, rec[9] = sched.deep_host[o.right].kind_right;
-			const bool proot = o.upper_slot_parent < 0 && !o.carry_in && !(o.lds_park & 1);
-			rec[10] = proot ? S_ROOT : o.carry_in ? S_CARRY : (lpark && (o.lds_park & 1)) ? S_LDS0 : S_HBM;
-			rec[11] = rec[10] == S_HBM ? o.upper_slot_parent : -1;
-			for (int side = 0; side < 2; side++) {
-				const int slot = side ? o.upper_slot_right : o.upper_slot_left, ch = side ? o.right : o.left;
-				int d = D_NONE;
-				if (lpark && (o.lds_park & 6) && ((o.lds_park & 2) ? 0 : 1) == side) d = S_LDS0;
-				else if (slot >= 0) d = S_HBM;
-				else if (o.carry_out == side + 1 && has_op[ch]) d = S_CARRY;
-				rec[12 + 2 * side] = d;
-				rec[13 + 2 * side] = slot;
-			}
-			rec[18] = o.carry_out;
-			const int kl = o.kind_left, kr = o.kind_right;  // the rows the kernel's accumulators are stored to, in its order
-			const int rows[10] = {o.left, o.right, kl >= CH_CHERRY ? o.lt0 : -1, kl >= CH_CHERRY ? o.lt1 : -1, kl == CH_CHERRY_TIP ? o.linner : -1,
-			                      kl == CH_CHERRY_TIP ? o.lt2 : -1, kr >= CH_CHERRY ? o.rt0 : -1, kr >= CH_CHERRY ? o.rt1 : -1,
-			                      kr == CH_CHERRY_TIP ? o.rinner : -1, kr == CH_CHERRY_TIP ? o.rt2 : -1};
-			for (int j = 0; j < 10; j++)
-				if (rows[j] >= 0) q[nq++] = rows[j];
-		}
-		rec[17] = (is_cut_root[rec[2]] ? 1 : 0) | (is_cut_root[rec[3]] ? 2 : 0);
-		rec[19] = nq;
-		std::memcpy(out + (size_t)i * W, rec, sizeof(rec));
-	}
-	return (int)ops.size();
-}
-
-// the stored nodes the streamed walks of a tree do without (stream_elide): host code only (no device, no engine)
-int phyamd_stream_elisions(int32_t tip_count, const int32_t *left, const int32_t *right, int32_t root, int32_t *out, int32_t capacity) {
-	if (tip_count < 2) return fail(PHYAMD_EINVAL, "tip_count must be >= 2 (got %d)", tip_count);
-	if (!left || !right) return fail(PHYAMD_EINVAL, "null left or right");
-	if (capacity < 0 || (capacity > 0 && !out)) return fail(PHYAMD_EINVAL, "null out with capacity %d", capacity);
-	Schedule sched;  // 4 states, an engine's defaults; the streamed walks' tables for one pattern of one category, as an engine builds them
-	StreamTables stream_tab;
-	const std::string err = build_schedule(TreeRef{tip_count, left, right, root}, ScheduleOptions{}, &sched);
-	if (!err.empty()) return fail(PHYAMD_EINVAL, "%s", err.c_str());
-	build_stream_tables(sched, StreamGeometry{1, 1, WAVE, true}, &stream_tab);
-	const std::vector<StreamElision> &el = stream_tab.elisions;
-	for (int i = 0; i < (int)el.size() && i < capacity; i++) {
-		const int32_t rec[8] = {el[i].node, el[i].parent, el[i].stored, el[i].sibling, el[i].sibling_kind, el[i].source, el[i].side, el[i].chunk};
-		std::memcpy(out + (size_t)i * 8, rec, sizeof(rec));
-	}
-	return (int)el.size();
-}
+#include "phyamd_schedule_export.inc"
 
 int phyamd_is_rescaling(phyamd_engine *g) {
 	CHECK_GROUP(g);

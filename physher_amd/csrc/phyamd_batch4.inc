@@ -18,13 +18,22 @@
 // (BatchOp and BATCH_*: phyamd_types.h)
 constexpr int BATCH_MAX_CATEGORIES = 8;  // one LDS row of site-likelihood terms per category; at most 8 category waves per workgroup
 
-// op i of a list, through the constant address space like the matrices: the lists are read-only kernel inputs at wave-uniform
-// addresses, so the eight words come by one s_load_dwordx8 instead of vector loads on the walk's dependent chain
-__device__ __forceinline__ BatchOp load_batch_op(const BatchOp *ops, int i) {
+// record i of a list of eight-dword records, its first WORDS words (the others 0), through the constant address space like the
+// matrices: the lists are read-only kernel inputs at wave-uniform addresses, so the words come by one s_load_dwordx8 instead of
+// vector loads on the walk's dependent chain
+template <int WORDS, typename Rec>
+__device__ __forceinline__ Rec load_const_record(const Rec *list, int i) {
+	static_assert(sizeof(Rec) == 32 && WORDS <= 8, "a record is eight dwords");
 	typedef const __attribute__((address_space(4))) int32_t *cint;
-	const cint o = (cint)reinterpret_cast<const int32_t *>(ops + i);
-	return BatchOp{o[0], o[1], o[2], o[3], o[4], o[5], o[6], 0};
+	const cint o = (cint)reinterpret_cast<const int32_t *>(list + i);
+	int32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+	for (int j = 0; j < WORDS; j++) w[j] = o[j];
+	Rec r;
+	__builtin_memcpy(&r, w, sizeof r);
+	return r;
 }
+__device__ __forceinline__ BatchOp load_batch_op(const BatchOp *ops, int i) { return load_const_record<7>(ops, i); }
 
 struct BatchArgs {
 	const BatchOp *lower_ops, *upper_ops;  // T - 1 ops each; item b's lists are at + b * item_stride
@@ -66,11 +75,17 @@ __global__ void k_batch_matrices(int C, int N, int items, const double *__restri
 	}
 }
 
+// message of a node through the matrix M at this lane's pattern: M . mask for a tip (node < T; tip_k: the lane's pattern in the
+// tips' code rows, P apart), M . p_node for an internal node (lower_c: the lane's cell of internal node T's stored partial, the
+// nodes' node_stride apart).  The product is formed inside either branch (k_spr4)
+__device__ __forceinline__ d4 child_message4(cptr M, const uint8_t *tip_k, int P, const double *lower_c, size_t node_stride, int T, int node) {
+	if (node < T) return matvec4(opaque(M), mask4(tip_k[(size_t)node * P]));
+	return matvec4(opaque(M), load4(lower_c + (size_t)(node - T) * node_stride));
+}
+
 // message of a child to its parent at (pattern lane, category c): P_child . mask for a tip, P_child . p_child for an internal node
 __device__ __forceinline__ d4 batch_message(const BatchArgs &a, cptr mats_c, const double *lower_c, size_t node_stride, int child, int k) {
-	const cptr M = opaque(mats_c + (size_t)child * a.C * 16);
-	if (child < a.T) return matvec4(M, mask4(a.tipmask[(size_t)child * a.P + k]));
-	return matvec4(M, load4(lower_c + (size_t)(child - a.T) * node_stride));
+	return child_message4(mats_c + (size_t)child * a.C * 16, a.tipmask + k, a.P, lower_c, node_stride, a.T, child);
 }
 
 // The walk of one (item, block) by its C category waves: the body of k_batch_walk4 below and of k_reweight_terms4

@@ -12,6 +12,7 @@
 //   phyamd_shard_api.inc    per-device half of the C ABI: creation, setters, evaluations, single-branch calls, inspection
 //   phyamd_queries.inc      ... and its whole-tree query calls: batches, NNI and SPR scores, posteriors, the full branch Hessian
 //   phyamd_abi.inc          extern "C" entry points: a handle is a group of 1..n shards on 1..n GPUs
+//   phyamd_schedule_export.inc  ... and the host-only ones that export a tree's schedules (included by phyamd_abi.inc)
 //
 // Replaces the CPU hot path of physher's SingleTreeLikelihood (src/phyc/treelikelihood.c and the per-state-count kernel files)
 // with hand-written HIP kernels.  The shipped design:

@@ -23,11 +23,7 @@ struct NniCand {
 	int32_t pad[3];
 };
 
-__device__ __forceinline__ NniCand load_nni_cand(const NniCand *cands, int i) {  // (as load_batch_op: one s_load_dwordx8)
-	typedef const __attribute__((address_space(4))) int32_t *cint;
-	const cint o = (cint)reinterpret_cast<const int32_t *>(cands + i);
-	return NniCand{o[0], o[1], o[2], o[3], o[4], {0, 0, 0}};
-}
+__device__ __forceinline__ NniCand load_nni_cand(const NniCand *cands, int i) { return load_const_record<5>(cands, i); }
 
 struct NniArgs {
 	const NniCand *cands;    // [gridDim.y]

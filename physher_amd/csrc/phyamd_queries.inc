@@ -103,15 +103,22 @@ ScratchPlan batch_plan(Shard *e, bool grad, int slots, bool trees) {
 	return p;
 }
 
-// phyamd_nni_log_likelihoods: ONE item with every upper parked (slots = T - 1), and whatever the item count the op lists, the
-// candidates and their index by node, the trial lengths and matrices, the slab and the result
-ScratchPlan nni_plan(Shard *e) {
-	const size_t D = sizeof(double), N = (size_t)e->N, C = (size_t)e->C, nblk = ((size_t)e->P + WAVE - 1) / WAVE, cands = std::max<size_t>(nni_candidates(e), 1);
+// what phyamd_nni_log_likelihoods and phyamd_nni_optimize share (launch_nni_walk): ONE item with every upper parked (slots = T - 1),
+// and whatever the item count the op lists, the candidates and their index by node, and the caller's [3][N] lengths
+ScratchPlan nni_base_plan(Shard *e) {
+	const size_t N = (size_t)e->N, cands = std::max<size_t>(nni_candidates(e), 1);
 	ScratchPlan p = batch_plan(e, true, e->T - 1, false);
 	p.add(e->d_nni_ops, 0, sizeof(BatchOp) * 2 * (size_t)(e->T - 1));
 	p.add(e->d_nni_cands, 0, sizeof(NniCand) * cands);
 	p.add(e->d_nni_cand_of, 0, sizeof(int32_t) * N);
-	p.add(e->d_nni_len, 0, D * 3 * N);
+	p.add(e->d_nni_len, 0, sizeof(double) * 3 * N);
+	return p;
+}
+
+// phyamd_nni_log_likelihoods: the walk's, and the trial matrices, the slab and the result
+ScratchPlan nni_plan(Shard *e) {
+	const size_t D = sizeof(double), N = (size_t)e->N, C = (size_t)e->C, nblk = ((size_t)e->P + WAVE - 1) / WAVE, cands = std::max<size_t>(nni_candidates(e), 1);
+	ScratchPlan p = nni_base_plan(e);
 	p.add(e->d_nni_mats, 0, D * 3 * N * C * 16);
 	p.add(e->d_nni_slab, 0, D * cands * nblk * 9);
 	p.add(e->d_nni_out, 0, D * 9 * N);
@@ -186,6 +193,17 @@ int upload_rows(Shard *e, double *dst, size_t dst_stride, const double *src, siz
 	return PHYAMD_OK;
 }
 
+// the batched walk's arguments on the engine's inputs and the batch scratch: every block of the patterns, the engine's weight row for
+// every item.  ops: post-order then pre-order list (item_stride: BatchArgs'); slots: an item's upper slots; mats: [item][N][C][16]
+BatchArgs batch_args(Shard *e, const BatchOp *ops, int item_stride, int slots, bool grad, const double *mats) {
+	BatchArgs a{};
+	a.lower_ops = ops, a.upper_ops = ops + (e->T - 1), a.item_stride = item_stride;
+	a.T = e->T, a.N = e->N, a.P = e->P, a.C = e->C, a.nblk = (e->P + WAVE - 1) / WAVE, a.upper_slots = slots, a.grad = grad ? 1 : 0;
+	a.tipmask = e->d_tipmask, a.freqs = e->d_freqs, a.props = e->d_props, a.weights = e->d_weights, a.Q = e->d_Q, a.mats = mats;
+	a.lower = e->d_batch_lower, a.upper = e->d_batch_upper, a.lnl_part = e->d_batch_lnl, a.slab = e->d_batch_slab;
+	return a;
+}
+
 // one chunk of `items` items through the batched walk: lengths [items][N] (host) -> out [items][rows] (host), rows = 1 or 1 + N C.
 // trees: the items walk their own op lists from their own roots, already in d_batch_item_ops and d_batch_roots; else the
 // engine's.  slots: the upper slots an item of this chunk has in d_batch_upper (at least what its list parks in).  weights: a row
@@ -199,8 +217,7 @@ int run_batch_chunk(Shard *e, int flags, int items, const double *lengths, bool 
 	launch_batch_matrices(e, items, e->d_batch_len, roots, e->d_batch_mats);
 	int rc;
 	if (weights && (rc = upload_rows(e, e->d_reweight_w, (size_t)e->P, weights, weight_stride, (size_t)e->P, (size_t)items))) return rc;
-	BatchArgs a{ops, ops + nops, trees ? 2 * nops : 0, e->T, e->N, e->P, e->C, nblk, slots, grad ? 1 : 0, e->d_tipmask, e->d_freqs, e->d_props,
-	            e->d_weights, e->d_Q, e->d_batch_mats, e->d_batch_lower, e->d_batch_upper, e->d_batch_lnl, e->d_batch_slab};
+	BatchArgs a = batch_args(e, ops, trees ? 2 * nops : 0, slots, grad, e->d_batch_mats);
 	if (weights) a.weights = e->d_reweight_w, a.weight_stride = (size_t)e->P;
 	const dim3 grid(nblk, items), block(WAVE, e->C);
 	if (flags & PHYAMD_GRAD_FOLD_ROOT_FREQS) hipLaunchKernelGGL(k_batch_walk4<true>, grid, block, 0, e->stream, a);
@@ -288,8 +305,6 @@ int run_batch(Shard *e, int flags, int32_t count, const double *branch_lengths, 
 
 int shard_gradient_batch(Shard *e, int flags, int32_t count, const double *branch_lengths, double *lnl, double *cat_gradient) {
 	CHECK_ENGINE(e);
-	if (count < 1) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch: count must be >= 1 (got %d)", count);
-	if (!branch_lengths || !lnl) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch: null branch_lengths or lnl");
 	return profiled_call(e, &Shard::batch_prof, phyamd_batch_profile{}, [&](phyamd_batch_profile &prof) {
 		const std::vector<double> lengths = e->lengths_sent;
 		const bool had_lengths = e->have_lengths;
@@ -329,6 +344,17 @@ ScratchPlan reweight_plan(Shard *e, bool grad, size_t nblk) {
 
 constexpr size_t REWEIGHT_MAX_CHUNK = (size_t)1 << 20;  // replicates per chunk: gridDim.y of k_reweight_mfma is a sixteenth
 
+// the product W R^T of `reps` weight rows (host, weight_stride apart, `width` patterns wide) with the `rows` rows of d_reweight_R
+// (Pc wide): the weights go up into rows padded to Pc and k_reweight_mfma leaves the segment sums in d_reweight_part.  *r: the
+// product's arguments for the caller's finish kernel (out: where k_reweight_finish puts the results, or null)
+int launch_reweight_product(Shard *e, const double *weights, size_t weight_stride, size_t width, size_t reps, size_t rows, size_t Pc, double *out, ReweightArgs *r) {
+	if (width < Pc) HIP_TRY(hipMemsetAsync(e->d_reweight_w, 0, sizeof(double) * reps * Pc, e->stream));  // (a garbage NaN times R's 0 is a NaN)
+	if (int rc = upload_rows(e, e->d_reweight_w, Pc, weights, weight_stride, width, reps)) return rc;
+	*r = ReweightArgs{e->d_reweight_w, e->d_reweight_R, e->d_reweight_part, out, (int)reps, (int)rows, (int)Pc, (int)((Pc + REWEIGHT_SEGMENT - 1) / REWEIGHT_SEGMENT), e->N, e->C};
+	hipLaunchKernelGGL(k_reweight_mfma, dim3((unsigned)((rows + 15) / 16), (unsigned)((reps + 15) / 16), (unsigned)r->segments), dim3(WAVE), 0, e->stream, *r);
+	return PHYAMD_OK;
+}
+
 // every replicate on the engine's own lengths: ONE walk per pattern chunk leaves R, and the replicates are products with it.
 // *sequential: the engine does not take the batched walk, or (PHYAMD_RESCALE_AUTO) a pattern's log L_k is not finite: nothing has
 // been stored and the caller evaluates the replicates one by one
@@ -345,7 +371,7 @@ int run_reweight(Shard *e, int flags, int32_t count, const double *weights, size
 	}
 	if ((rc = ensure_engine_batch_ops(e)) || (rc = update_matrices(e))) return rc;
 	const bool grad = cat_gradient != nullptr, lazy = e->cfg.rescale == PHYAMD_RESCALE_AUTO;
-	const int N = e->N, C = e->C, P = e->P, nops = e->T - 1;
+	const int N = e->N, C = e->C, P = e->P;
 	const size_t ncat = (size_t)N * C, rows = grad ? 1 + ncat : 1, nblk_all = ((size_t)P + WAVE - 1) / WAVE;
 	// the pattern chunk: every block if one replicate fits beside it, else the most blocks that leave room for one
 	const double room = scratch_room(e, (double)batch_scratch_bytes(e), EngineRoom::MayGrow);
@@ -374,8 +400,8 @@ int run_reweight(Shard *e, int flags, int32_t count, const double *weights, size
 	double *const mark = lazy ? e->d_batch_lnl.get() : nullptr;
 	for (size_t b0 = 0; b0 < nblk_all; b0 += nblk) {
 		const size_t nb = std::min(nblk, nblk_all - b0), Pc = nb * WAVE, k0 = b0 * WAVE, width = std::min(Pc, (size_t)P - k0);
-		BatchArgs a{ops, ops + nops, 0, e->T, N, P, C, (int)nb, e->batch_upper_slots, grad ? 1 : 0, e->d_tipmask, e->d_freqs, e->d_props,
-		            e->d_weights, e->d_Q, e->d_mats, e->d_batch_lower, e->d_batch_upper, nullptr, nullptr};
+		BatchArgs a = batch_args(e, ops, 0, e->batch_upper_slots, grad, e->d_mats);
+		a.nblk = (int)nb, a.lnl_part = a.slab = nullptr;  // the terms form: the chunk's blocks, rows of R instead of sums
 		a.k0 = (int)k0, a.Pc = (int)Pc, a.R = e->d_reweight_R, a.not_finite = mark;
 		if (mark) HIP_TRY(hipMemsetAsync(mark, 0, sizeof(double), e->stream));
 		const dim3 grid((unsigned)nb), block(WAVE, C);
@@ -386,11 +412,8 @@ int run_reweight(Shard *e, int flags, int32_t count, const double *weights, size
 		prof.pattern_chunks++;
 		for (size_t first = 0; first < (size_t)count; first += chunk) {
 			const size_t items = std::min(chunk, (size_t)count - first);
-			if (width < Pc) HIP_TRY(hipMemsetAsync(e->d_reweight_w, 0, sizeof(double) * items * Pc, e->stream));  // (a garbage NaN times R's 0 is a NaN)
-			if ((rc = upload_rows(e, e->d_reweight_w, Pc, weights + first * weight_stride + k0, weight_stride, width, items))) return rc;
-			const ReweightArgs r{e->d_reweight_w, e->d_reweight_R, e->d_reweight_part, e->d_batch_out, (int)items, (int)rows, (int)Pc,
-			                     (int)((Pc + REWEIGHT_SEGMENT - 1) / REWEIGHT_SEGMENT), N, C};
-			hipLaunchKernelGGL(k_reweight_mfma, dim3((unsigned)((rows + 15) / 16), (unsigned)((items + 15) / 16), (unsigned)r.segments), dim3(WAVE), 0, e->stream, r);
+			ReweightArgs r;
+			if ((rc = launch_reweight_product(e, weights + first * weight_stride + k0, weight_stride, width, items, rows, Pc, e->d_batch_out, &r))) return rc;
 			hipLaunchKernelGGL(k_reweight_finish, dim3((unsigned)((items * rows + 255) / 256)), dim3(256), 0, e->stream, r);
 			HIP_TRY(hipGetLastError());
 			out.resize(items * rows);
@@ -418,8 +441,6 @@ int shard_gradient_batch_weights(Shard *e, int flags, int32_t count, const doubl
                                  double *cat_gradient) {
 	static const char *const name = "phyamd_gradient_batch_weights";
 	if (!e) return fail(PHYAMD_EINVAL, "%s: null engine", name);
-	if (count < 1) return fail(PHYAMD_EINVAL, "%s: count must be >= 1 (got %d)", name, count);
-	if (!weights || !lnl) return fail(PHYAMD_EINVAL, "%s: null %s", name, !weights ? "weights" : "lnl");
 	return profiled_call(e, &Shard::weight_prof, phyamd_weight_batch_profile{}, [&](phyamd_weight_batch_profile &prof) {
 		const std::vector<double> lengths = e->lengths_sent, own = e->weights_host;
 		const bool had_lengths = e->have_lengths, had_weights = e->have_weights;
@@ -457,58 +478,78 @@ int shard_gradient_batch_weights(Shard *e, int flags, int32_t count, const doubl
 
 // ---- a batch of trees (phyamd_gradient_batch_trees) ---------------------------------------------------------------------------
 
-// the items of a batch of trees through the batched walk, in chunks of what the scratch holds.  Per chunk: the items' op lists are
-// built and uploaded with their roots, the upper slots are those of the chunk's deepest-parking item, three launches
-int run_tree_batch(Shard *e, int flags, int32_t count, const int32_t *left, const int32_t *right, const int32_t *roots, const double *branch_lengths, double *lnl,
-                   double *cat_gradient, phyamd_batch_profile &prof) {
-	int rc;
-	if ((rc = check_ready_but_lengths(e))) return rc;
-	const bool grad = cat_gradient != nullptr;
-	if (const char *why = tree_batch_refusal(e, flags, 1)) return fail(PHYAMD_EUNSUPPORTED, "phyamd_gradient_batch_trees: %s", why);
-	if (grad && !e->have_Q) return fail(PHYAMD_EINVAL, "the gradient needs the rate matrix: phyamd_set_eigen or phyamd_set_rate_matrix");
-	const int T = e->T;
-	const size_t N = (size_t)e->N, ncat = N * e->C, rows = grad ? 1 + ncat : 1, nops = 2 * (size_t)(T - 1);
-	std::vector<int> slots(count);  // per item: the upper slots its pre-order list parks in
+// The items of a batch of trees in chunks of what the scratch holds.  item_ops(left, right, root, ops): an item's op list appended
+// to ops (null: nothing is built), the slots it parks in; plan_of(slots): the scratch of a chunk whose items park in that many.
+// Every item's tree is validated before anything is launched.  Per chunk the scratch is ensured, the items' op lists and roots go
+// up (d_batch_item_ops, d_batch_roots; not waited for) and body runs on items [first, first + items), the slots of the deepest-
+// parking one, their lengths [items][N] with the roots' entries zeroed (host), and the times before and after the lists were built
+template <typename ItemOps, typename PlanOf, typename Body>
+int for_tree_chunks(Shard *e, const char *name, int flags, int32_t count, const int32_t *left, const int32_t *right, const int32_t *roots, const double *branch_lengths,
+                    ItemOps item_ops, PlanOf plan_of, Body body) {
+	const size_t N = (size_t)e->N;
+	std::vector<int> slots(count);  // per item: the slots its list parks in
 	{
 		std::vector<int32_t> parents;
 		for (int32_t b = 0; b < count; b++) {  // every item, before anything is launched
 			const int32_t *l = left + (size_t)b * N, *r = right + (size_t)b * N;
-			const std::string err = validate_tree(TreeRef{T, l, r, roots[b]}, parents, "phyamd_gradient_batch_trees", b);
+			const std::string err = validate_tree(TreeRef{e->T, l, r, roots[b]}, parents, name, b);
 			if (!err.empty()) return fail(PHYAMD_EINVAL, "%s", err.c_str());
-			slots[b] = grad ? build_batch_ops(T, l, r, roots[b], nullptr) : 1;
+			slots[b] = item_ops(l, r, roots[b], nullptr);
 		}
 	}
-	std::vector<double> lengths, out;
+	std::vector<double> lengths;
 	std::vector<BatchOp> ops;
+	int rc;
 	for (size_t first = 0; first < (size_t)count;) {
 		// the chunk and its slot count settle each other: fewer items never need more slots
 		size_t items = std::min<size_t>((size_t)count - first, BATCH_MAX_CHUNK);
-		int chunk_slots = 1;
+		int chunk_slots = 0;
 		ScratchPlan plan;
 		for (;;) {
 			chunk_slots = *std::max_element(slots.begin() + first, slots.begin() + first + items);
-			plan = batch_plan(e, grad, chunk_slots, true);
+			plan = plan_of(chunk_slots);
 			const size_t fit = batch_items_that_fit(e, items, plan);
-			if (const char *why = tree_batch_refusal(e, flags, fit)) return fail(PHYAMD_EUNSUPPORTED, "phyamd_gradient_batch_trees: %s", why);
+			if (const char *why = tree_batch_refusal(e, flags, fit)) return fail(PHYAMD_EUNSUPPORTED, "%s: %s", name, why);
 			if (fit >= items) break;
 			items = fit;
 		}
 		if ((rc = ensure_batch_scratch(e, items, plan))) return rc;
+		lengths.assign(branch_lengths + first * N, branch_lengths + (first + items) * N);
+		for (size_t b = 0; b < items; b++) lengths[b * N + roots[first + b]] = 0.0;  // (ignored, as phyamd_set_branch_lengths does)
 		const auto t0 = std::chrono::steady_clock::now();
 		ops.clear();
-		for (size_t b = first; b < first + items; b++) build_batch_ops(T, left + b * N, right + b * N, roots[b], &ops);
+		for (size_t b = first; b < first + items; b++) item_ops(left + b * N, right + b * N, roots[b], &ops);
 		const auto t1 = std::chrono::steady_clock::now();
-		HIP_TRY(hipMemcpyAsync(e->d_batch_item_ops, ops.data(), sizeof(BatchOp) * items * nops, hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_batch_item_ops, ops.data(), sizeof(BatchOp) * ops.size(), hipMemcpyHostToDevice, e->stream));
 		HIP_TRY(hipMemcpyAsync(e->d_batch_roots, roots + first, sizeof(int32_t) * items, hipMemcpyHostToDevice, e->stream));
-		HIP_TRY(hipStreamSynchronize(e->stream));  // (ops is reused by the next chunk)
+		if ((rc = body(first, items, chunk_slots, lengths.data(), t0, t1))) return rc;  // (ends with the stream waited for: ops and lengths are reused)
+		first += items;
+	}
+	return PHYAMD_OK;
+}
+
+// the items of a batch of trees through the batched walk: per chunk the upper slots of its deepest-parking item, three launches
+int run_tree_batch(Shard *e, int flags, int32_t count, const int32_t *left, const int32_t *right, const int32_t *roots, const double *branch_lengths, double *lnl,
+                   double *cat_gradient, phyamd_batch_profile &prof) {
+	static const char *const name = "phyamd_gradient_batch_trees";
+	int rc;
+	if ((rc = check_ready_but_lengths(e))) return rc;
+	const bool grad = cat_gradient != nullptr;
+	if (const char *why = tree_batch_refusal(e, flags, 1)) return fail(PHYAMD_EUNSUPPORTED, "%s: %s", name, why);
+	if (grad && !e->have_Q) return fail(PHYAMD_EINVAL, "the gradient needs the rate matrix: phyamd_set_eigen or phyamd_set_rate_matrix");
+	const size_t ncat = (size_t)e->N * e->C, rows = grad ? 1 + ncat : 1;
+	std::vector<double> out;
+	// (an item's upper slots are its pre-order list's: without the gradient nothing is parked)
+	const auto item_ops = [&](const int32_t *l, const int32_t *r, int32_t root, std::vector<BatchOp> *ops) { return ops || grad ? build_batch_ops(e->T, l, r, root, ops) : 1; };
+	const auto plan_of = [&](int slots) { return batch_plan(e, grad, slots, true); };
+	const auto chunk = [&](size_t first, size_t items, int slots, const double *lengths, auto t0, auto t1) -> int {
+		HIP_TRY(hipStreamSynchronize(e->stream));  // (the lists' upload, timed on its own)
 		const auto t2 = std::chrono::steady_clock::now();
-		lengths.assign(branch_lengths + first * N, branch_lengths + (first + items) * N);
 		out.resize(items * rows);
-		for (size_t b = 0; b < items; b++) lengths[b * N + roots[first + b]] = 0.0;  // (ignored, as phyamd_set_branch_lengths does)
-		if ((rc = run_batch_chunk(e, flags, (int)items, lengths.data(), grad, chunk_slots, true, out.data()))) return rc;
+		if (int rc = run_batch_chunk(e, flags, (int)items, lengths, grad, slots, true, out.data())) return rc;
 		if (e->batch_trace) {
 			const auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-			std::fprintf(stderr, "phyamd_gradient_batch_trees: chunk %d items %zu slots %d build_ms %.6f upload_ms %.6f\n", prof.chunks, items, chunk_slots, ms(t0, t1),
+			std::fprintf(stderr, "phyamd_gradient_batch_trees: chunk %d items %zu slots %d build_ms %.6f upload_ms %.6f\n", prof.chunks, items, slots, ms(t0, t1),
 			             ms(t1, t2));
 		}
 		prof.chunks++;
@@ -517,20 +558,16 @@ int run_tree_batch(Shard *e, int flags, int32_t count, const int32_t *left, cons
 			store_batch_item(&out[b * rows], ncat, lnl + first + b, grad ? cat_gradient + (first + b) * ncat : nullptr);
 			prof.items_fast++;
 		}
-		first += items;
-	}
-	return PHYAMD_OK;
+		return PHYAMD_OK;
+	};
+	return for_tree_chunks(e, name, flags, count, left, right, roots, branch_lengths, item_ops, plan_of, chunk);
 }
 
 // reads the engine's inputs and writes only the batch scratch: nothing in Shard::state changes
 int shard_gradient_batch_trees(Shard *e, int flags, int32_t count, const int32_t *left, const int32_t *right, const int32_t *roots, const double *branch_lengths,
                                double *lnl, double *cat_gradient) {
 	CHECK_ENGINE(e);
-	if (count < 1) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch_trees: count must be >= 1 (got %d)", count);
-	if (!left || !right || !roots || !branch_lengths || !lnl) return fail(PHYAMD_EINVAL, "phyamd_gradient_batch_trees: null left, right, roots, branch_lengths or lnl");
-	return profiled_call(e, &Shard::batch_prof, phyamd_batch_profile{}, [&](phyamd_batch_profile &prof) {
-		return run_tree_batch(e, flags, count, left, right, roots, branch_lengths, lnl, cat_gradient, prof);
-	});
+	return profiled_call(e, &Shard::batch_prof, phyamd_batch_profile{}, [&](phyamd_batch_profile &prof) { return run_tree_batch(e, flags, count, left, right, roots, branch_lengths, lnl, cat_gradient, prof); });
 }
 
 // ---- every NNI neighbour of the engine's tree (phyamd_nni_log_likelihoods) -----------------------------------------------------
@@ -557,28 +594,55 @@ int upload_nni_lists(Shard *e) {
 	return PHYAMD_OK;
 }
 
+// a call on the NNI candidates of the walked tree: its name, its [3][N] lengths' argument, what one is called, what the eigen system forms
+struct NniWalkCall {
+	const char *name, *argument, *noun, *formed;
+};
+
+// the call's checks, and its lengths [3][N]: a candidate's own three where the caller gives them (own, or null), every other entry
+// the engine's (ignored: no arrangement reads that matrix)
+int check_nni_walk(Shard *e, const NniWalkCall &call, int flags, const double *own, std::vector<double> &lengths) {
+	int rc;
+	if ((rc = check_ready(e))) return rc;
+	if (flags != 0) return fail(PHYAMD_EUNSUPPORTED, "%s: flags %d (no flags are defined: pass 0)", call.name, flags);
+	if (const char *why = tree_batch_refusal(e, 0, 1)) return fail(PHYAMD_EUNSUPPORTED, "%s: %s", call.name, why);
+	if (!e->have_eigen || !e->have_Q) return fail(PHYAMD_EINVAL, "%s needs the eigen system (phyamd_set_eigen): %s formed from it", call.name, call.formed);
+	const int T = e->T, N = e->N;
+	lengths.resize((size_t)3 * N);
+	for (int k = 0; k < 3; k++) std::copy(e->lengths.begin(), e->lengths.end(), lengths.begin() + (size_t)k * N);
+	for (int v = T; v < N && own; v++) {
+		if (v == e->root) continue;
+		for (int k = 0; k < 3; k++) {
+			const double t = own[(size_t)k * N + v];
+			if (!std::isfinite(t) || t < 0.0) return fail(PHYAMD_EINVAL, "%s: %s[%d][%d] = %g: a %s is finite and not negative", call.name, call.argument, k, v, t, call.noun);
+			lengths[(size_t)k * N + v] = t;
+		}
+	}
+	return PHYAMD_OK;
+}
+
+// the scratch of `plan` (nni_base_plan's and the caller's own), the lists, the lengths [3][N] (host) into d_nni_len, the matrices
+// of the engine's lengths -- and with `trial` those of the three length vectors, into d_nni_mats -- and ONE item through
+// the batched walk with every upper parked.  The caller waits for the stream before `lengths` goes
+int launch_nni_walk(Shard *e, const ScratchPlan &plan, const std::vector<double> &lengths, bool trial) {
+	int rc;
+	if ((rc = ensure_batch_scratch(e, 1, plan)) || (rc = upload_nni_lists(e))) return rc;
+	HIP_TRY(hipMemcpyAsync(e->d_nni_len, lengths.data(), sizeof(double) * lengths.size(), hipMemcpyHostToDevice, e->stream));
+	launch_batch_matrices(e, 1, e->d_lengths, nullptr, e->d_batch_mats);  // the walk's item: the engine's lengths
+	if (trial) launch_batch_matrices(e, 3, e->d_nni_len, nullptr, e->d_nni_mats);
+	const BatchArgs walk = batch_args(e, e->d_nni_ops.get(), 0, e->T - 1, true, e->d_batch_mats);
+	hipLaunchKernelGGL(k_batch_walk4<false>, dim3(walk.nblk, 1), dim3(WAVE, e->C), 0, e->stream, walk);
+	return PHYAMD_OK;
+}
+
 // out [3 terms][3][N] (host): one walk of the engine's tree with every upper parked, the trial matrices, every edge's three
 // arrangements in one launch.  Reads the engine's inputs and writes only the batch scratch: nothing in Shard::state changes
 int run_nni(Shard *e, int flags, const double *central_lengths, bool deriv, double *out, phyamd_nni_profile &prof) {
+	static const NniWalkCall call{"phyamd_nni_log_likelihoods", "central_lengths", "trial length", "the trial matrices, d1 and d2 are"};
 	int rc;
-	if ((rc = check_ready(e))) return rc;
-	if (flags != 0) return fail(PHYAMD_EUNSUPPORTED, "phyamd_nni_log_likelihoods: flags %d (no flags are defined: pass 0)", flags);
-	if (const char *why = tree_batch_refusal(e, 0, 1)) return fail(PHYAMD_EUNSUPPORTED, "phyamd_nni_log_likelihoods: %s", why);
-	if (!e->have_eigen || !e->have_Q)
-		return fail(PHYAMD_EINVAL, "phyamd_nni_log_likelihoods needs the eigen system (phyamd_set_eigen): the trial matrices, d1 and d2 are formed from it");
+	std::vector<double> trial;
+	if ((rc = check_nni_walk(e, call, flags, central_lengths, trial))) return rc;
 	const int T = e->T, N = e->N, C = e->C;
-	// the trial lengths: a candidate's own three, every other entry the engine's (ignored: no arrangement reads that matrix)
-	std::vector<double> trial((size_t)3 * N);
-	for (int k = 0; k < 3; k++) std::copy(e->lengths.begin(), e->lengths.end(), trial.begin() + (size_t)k * N);
-	for (int v = T; v < N && central_lengths; v++) {
-		if (v == e->root) continue;
-		for (int k = 0; k < 3; k++) {
-			const double t = central_lengths[(size_t)k * N + v];
-			if (!std::isfinite(t) || t < 0.0)
-				return fail(PHYAMD_EINVAL, "phyamd_nni_log_likelihoods: central_lengths[%d][%d] = %g: a trial length is finite and not negative", k, v, t);
-			trial[(size_t)k * N + v] = t;
-		}
-	}
 	const size_t cands = nni_candidates(e);
 	prof.candidates = (int32_t)cands;
 	std::fill(out, out + (size_t)9 * N, NAN);
@@ -587,15 +651,8 @@ int run_nni(Shard *e, int flags, const double *central_lengths, bool deriv, doub
 	if (batch_items_that_fit(e, 1, plan) < 1)
 		return fail(PHYAMD_EUNSUPPORTED, "phyamd_nni_log_likelihoods: the scratch (%zu bytes: every internal node's lower and upper partial) does not fit the memory budget",
 		            plan.item_bytes() + plan.fixed_bytes());
-	if ((rc = ensure_batch_scratch(e, 1, plan)) || (rc = upload_nni_lists(e))) return rc;
-	const int nblk = (e->P + WAVE - 1) / WAVE, nops = T - 1;
-	HIP_TRY(hipMemcpyAsync(e->d_nni_len, trial.data(), sizeof(double) * trial.size(), hipMemcpyHostToDevice, e->stream));
-	launch_batch_matrices(e, 1, e->d_lengths, nullptr, e->d_batch_mats);  // the walk's item: the engine's lengths
-	launch_batch_matrices(e, 3, e->d_nni_len, nullptr, e->d_nni_mats);
-	const BatchOp *ops = e->d_nni_ops.get();
-	const BatchArgs walk{ops, ops + nops, 0, T, N, e->P, C, nblk, T - 1, 1, e->d_tipmask, e->d_freqs, e->d_props, e->d_weights, e->d_Q, e->d_batch_mats, e->d_batch_lower,
-	                     e->d_batch_upper, e->d_batch_lnl, e->d_batch_slab};
-	hipLaunchKernelGGL(k_batch_walk4<false>, dim3(nblk, 1), dim3(WAVE, C), 0, e->stream, walk);
+	if ((rc = launch_nni_walk(e, plan, trial, true))) return rc;
+	const int nblk = (e->P + WAVE - 1) / WAVE;
 	for (size_t first = 0; first < cands; first += BATCH_MAX_CHUNK) {  // (gridDim.y)
 		const size_t n = std::min<size_t>(cands - first, BATCH_MAX_CHUNK);
 		const NniArgs a{e->d_nni_cands.get() + first, T, N, e->P, C, nblk, deriv ? 1 : 0, e->d_tipmask, e->d_freqs, e->d_props, e->d_rates, e->d_weights, e->d_Q,
@@ -619,7 +676,6 @@ void nni_mask_derivatives(size_t entries, double *out) {
 // out [3 terms][3][N] on the host; deriv: d1 and d2 as well (else those rows are NaN at tips and the root, 0 elsewhere)
 int shard_nni_log_likelihoods(Shard *e, int flags, const double *central_lengths, bool deriv, double *out) {
 	CHECK_ENGINE(e);
-	if (!out) return fail(PHYAMD_EINVAL, "phyamd_nni_log_likelihoods: null lnl");
 	return profiled_call(e, &Shard::nni_prof, phyamd_nni_profile{}, [&](phyamd_nni_profile &prof) {
 		const int rc = run_nni(e, flags, central_lengths, deriv, out, prof);
 		if (!rc) nni_mask_derivatives((size_t)3 * e->N, out);
@@ -629,15 +685,11 @@ int shard_nni_log_likelihoods(Shard *e, int flags, const double *central_lengths
 
 // ---- the optimised central branch of every NNI neighbour (phyamd_nni_optimize) ------------------------------------------------
 
-// ONE item, as nni_plan's: the walk with every upper parked, its lists, the start lengths -- and for the `chunk` candidates that
-// run at once the coefficients and the results of their three entries (sizes: d_cbopt_K, d_cbopt_out, d_cbopt_iter)
+// the walk's (nni_base_plan: its [3][N] lengths are the start lengths), and for the `chunk` candidates that run at once the
+// coefficients and the results of their three entries (sizes: d_cbopt_K, d_cbopt_out, d_cbopt_iter)
 ScratchPlan cbopt_plan(Shard *e, size_t chunk) {
-	const size_t D = sizeof(double), N = (size_t)e->N, C = (size_t)e->C, nblk = ((size_t)e->P + WAVE - 1) / WAVE, cands = std::max<size_t>(nni_candidates(e), 1);
-	ScratchPlan p = batch_plan(e, true, e->T - 1, false);
-	p.add(e->d_nni_ops, 0, sizeof(BatchOp) * 2 * (size_t)(e->T - 1));
-	p.add(e->d_nni_cands, 0, sizeof(NniCand) * cands);
-	p.add(e->d_nni_cand_of, 0, sizeof(int32_t) * N);
-	p.add(e->d_nni_len, 0, D * 3 * N);
+	const size_t D = sizeof(double), C = (size_t)e->C, nblk = ((size_t)e->P + WAVE - 1) / WAVE;
+	ScratchPlan p = nni_base_plan(e);
 	p.add(e->d_cbopt_K, 0, chunk * D * 3 * C * 4 * nblk * WAVE);
 	p.add(e->d_cbopt_out, 0, chunk * D * 3 * 4);
 	p.add(e->d_cbopt_iter, 0, chunk * sizeof(int32_t) * 3);
@@ -666,23 +718,11 @@ struct NniOptimizeArgs {
 // one walk of the engine's tree with every upper parked, then chunk by chunk the candidates' coefficients and their iterations.
 // Reads the engine's inputs and writes only the batch scratch: nothing in Shard::state changes
 int run_nni_optimize(Shard *e, int flags, const NniOptimizeArgs &o, phyamd_nni_optimize_profile &prof) {
-	static const char *const name = "phyamd_nni_optimize";
+	static const NniWalkCall call{"phyamd_nni_optimize", "start_lengths", "start length", "the likelihood in the central length is"};
 	int rc;
-	if ((rc = check_ready(e))) return rc;
-	if (flags != 0) return fail(PHYAMD_EUNSUPPORTED, "%s: flags %d (no flags are defined: pass 0)", name, flags);
-	if (const char *why = tree_batch_refusal(e, 0, 1)) return fail(PHYAMD_EUNSUPPORTED, "%s: %s", name, why);
-	if (!e->have_eigen || !e->have_Q) return fail(PHYAMD_EINVAL, "%s needs the eigen system (phyamd_set_eigen): the likelihood in the central length is formed from it", name);
+	std::vector<double> start;
+	if ((rc = check_nni_walk(e, call, flags, o.start, start))) return rc;
 	const int T = e->T, N = e->N, C = e->C;
-	std::vector<double> start((size_t)3 * N);
-	for (int k = 0; k < 3; k++) std::copy(e->lengths.begin(), e->lengths.end(), start.begin() + (size_t)k * N);
-	for (int v = T; v < N && o.start; v++) {
-		if (v == e->root) continue;
-		for (int k = 0; k < 3; k++) {
-			const double t = o.start[(size_t)k * N + v];
-			if (!std::isfinite(t) || t < 0.0) return fail(PHYAMD_EINVAL, "%s: start_lengths[%d][%d] = %g: a start length is finite and not negative", name, k, v, t);
-			start[(size_t)k * N + v] = t;
-		}
-	}
 	const size_t cands = nni_candidates(e), entries = (size_t)3 * N;
 	prof.candidates = (int32_t)cands;
 	std::fill(o.lengths, o.lengths + entries, NAN);
@@ -695,16 +735,10 @@ int run_nni_optimize(Shard *e, int flags, const NniOptimizeArgs &o, phyamd_nni_o
 	if (chunk < 1) {
 		const ScratchPlan one = cbopt_plan(e, 1);
 		return fail(PHYAMD_EUNSUPPORTED, "%s: the scratch of one candidate (%zu bytes: every internal node's lower and upper partial, and its entries' coefficients) does not fit the memory budget",
-		            name, one.fixed_bytes() + one.item_bytes());
+		            call.name, one.fixed_bytes() + one.item_bytes());
 	}
-	if ((rc = ensure_batch_scratch(e, 1, cbopt_plan(e, chunk))) || (rc = upload_nni_lists(e))) return rc;
-	const int nblk = (e->P + WAVE - 1) / WAVE, nops = T - 1;
-	HIP_TRY(hipMemcpyAsync(e->d_nni_len, start.data(), sizeof(double) * start.size(), hipMemcpyHostToDevice, e->stream));
-	launch_batch_matrices(e, 1, e->d_lengths, nullptr, e->d_batch_mats);  // the walk's item: the engine's lengths
-	const BatchOp *ops = e->d_nni_ops.get();
-	const BatchArgs walk{ops, ops + nops, 0, T, N, e->P, C, nblk, T - 1, 1, e->d_tipmask, e->d_freqs, e->d_props, e->d_weights, e->d_Q, e->d_batch_mats, e->d_batch_lower,
-	                     e->d_batch_upper, e->d_batch_lnl, e->d_batch_slab};
-	hipLaunchKernelGGL(k_batch_walk4<false>, dim3(nblk, 1), dim3(WAVE, C), 0, e->stream, walk);
+	if ((rc = launch_nni_walk(e, cbopt_plan(e, chunk), start, false))) return rc;
+	const int nblk = (e->P + WAVE - 1) / WAVE;
 	HIP_TRY(hipGetLastError());
 	// (the candidates' nodes in d_nni_cands' order: upload_nni_lists')
 	std::vector<int> node;
@@ -873,8 +907,6 @@ int run_spr(Shard *e, int flags, int32_t count, const int32_t *prune, double *ln
 
 int shard_spr_log_likelihoods(Shard *e, int flags, int32_t count, const int32_t *prune, double *lnl) {
 	CHECK_ENGINE(e);
-	if (count < 1) return fail(PHYAMD_EINVAL, "phyamd_spr_log_likelihoods: count must be >= 1 (got %d)", count);
-	if (!lnl) return fail(PHYAMD_EINVAL, "phyamd_spr_log_likelihoods: null lnl");
 	return profiled_call(e, &Shard::spr_prof, phyamd_spr_profile{}, [&](phyamd_spr_profile &prof) { return run_spr(e, flags, count, prune, lnl, prof); });
 }
 
@@ -996,7 +1028,6 @@ int shard_state_posteriors(Shard *e, int flags, int32_t count, const int32_t *no
 int shard_site_rate_posteriors(Shard *e, double *posteriors, double *mean_rates) {
 	CHECK_ENGINE(e);
 	NOT_TILED(e, "phyamd_site_rate_posteriors (the root partial of every pattern resident)");
-	if (!posteriors) return fail(PHYAMD_EINVAL, "phyamd_site_rate_posteriors: null posteriors");
 	int rc;
 	if ((rc = bind_device(e)) || (rc = check_ready(e))) return rc;
 	if ((rc = run_lower(e, 1))) return rc;
@@ -1190,7 +1221,6 @@ int run_branch_hessian(Shard *e, double *lnl, double *gradient, double *hessian,
 
 int shard_branch_hessian(Shard *e, int flags, double *lnl, double *gradient, double *hessian) {
 	if (!e) return fail(PHYAMD_EINVAL, "phyamd_branch_hessian: null engine");
-	if (!lnl || !hessian) return fail(PHYAMD_EINVAL, "phyamd_branch_hessian: null %s", !lnl ? "lnl" : "hessian");
 	if (flags != 0) return fail(PHYAMD_EINVAL, "phyamd_branch_hessian: flags %d (no flags are defined: pass 0)", flags);
 	phyamd_hessian_profile known{};
 	known.pairs = (int64_t)(e->N - 1) * e->N / 2;
@@ -1231,7 +1261,7 @@ ScratchPlan sitelnl_plan(Shard *e, int slots, size_t reps) {
 	return p;
 }
 
-// the items in chunks of what the scratch holds; per chunk: the op lists, roots and lengths go up, matrices, walk and finish are
+// the items in chunks of what the scratch holds (for_tree_chunks); per chunk: the lengths go up, matrices, walk and finish are
 // launched, the rows come back if they are wanted, and every replicate chunk is multiplied with the rows while they are resident
 int run_site_lnl(Shard *e, int flags, int32_t count, const int32_t *left, const int32_t *right, const int32_t *roots, const double *branch_lengths, double *lnl,
                  double *pattern_lnl, size_t pattern_stride, int32_t replicate_count, const double *replicate_weights, size_t weight_stride, double *replicate_lnl,
@@ -1241,9 +1271,8 @@ int run_site_lnl(Shard *e, int flags, int32_t count, const int32_t *left, const 
 	if ((rc = check_ready_but_lengths(e))) return fail(rc, "%s: the engine is not ready: %s", name, std::string(g_last_error).c_str());
 	if (flags != 0) return fail(PHYAMD_EUNSUPPORTED, "%s: flags %d (no flags are defined: pass 0)", name, flags);
 	if (const char *why = tree_batch_refusal(e, 0, 1)) return fail(PHYAMD_EUNSUPPORTED, "%s: %s", name, why);
-	const int T = e->T, P = e->P, C = e->C, nops = T - 1;
+	const int T = e->T, P = e->P, C = e->C;
 	const size_t N = (size_t)e->N, nblk = ((size_t)P + WAVE - 1) / WAVE, Pc = nblk * WAVE, R = (size_t)replicate_count;
-	const int segments = (int)((Pc + REWEIGHT_SEGMENT - 1) / REWEIGHT_SEGMENT);
 	std::vector<int32_t> own_left, own_right, own_roots;
 	if (!left) {  // every item is the engine's tree
 		for (int32_t b = 0; b < count; b++) {
@@ -1253,48 +1282,24 @@ int run_site_lnl(Shard *e, int flags, int32_t count, const int32_t *left, const 
 		own_roots.assign(count, e->root);
 		left = own_left.data(), right = own_right.data(), roots = own_roots.data();
 	}
-	std::vector<BatchOp> work, ops;
-	std::vector<int> slots(count);  // per item: the slots its list parks in
-	{
-		std::vector<int32_t> parents;
-		for (int32_t b = 0; b < count; b++) {  // every item, before anything is launched
-			const int32_t *l = left + (size_t)b * N, *r = right + (size_t)b * N;
-			const std::string err = validate_tree(TreeRef{T, l, r, roots[b]}, parents, name, b);
-			if (!err.empty()) return fail(PHYAMD_EINVAL, "%s", err.c_str());
-			slots[b] = site_lnl_ops(T, l, r, roots[b], work, nullptr);
-			prof.lower_slots = std::max(prof.lower_slots, (int32_t)slots[b]);
-		}
-	}
 	// the replicate chunk: all of them if their weight rows take at most a quarter of the room, else as many as do (at least one)
 	size_t reps = 0;
 	if (R > 0) {
 		const double room = scratch_room(e, (double)batch_scratch_bytes(e), EngineRoom::MayGrow);
 		reps = (size_t)std::min((double)std::min(R, SITE_LNL_MAX_REPLICATES), std::max(1.0, std::floor(room / 4 / (double)(sizeof(double) * Pc))));
 	}
-	std::vector<double> lengths, out, rows, rell;
-	for (size_t first = 0; first < (size_t)count;) {
-		// the chunk and its slot count settle each other: fewer items never need more slots
-		size_t items = std::min<size_t>((size_t)count - first, BATCH_MAX_CHUNK);
-		int chunk_slots = 0;
-		ScratchPlan plan;
-		for (;;) {
-			chunk_slots = *std::max_element(slots.begin() + first, slots.begin() + first + items);
-			plan = sitelnl_plan(e, chunk_slots, reps);
-			const size_t fit = batch_items_that_fit(e, items, plan);
-			if (const char *why = tree_batch_refusal(e, 0, fit)) return fail(PHYAMD_EUNSUPPORTED, "%s: %s", name, why);
-			if (fit >= items) break;
-			items = fit;
-		}
-		if ((rc = ensure_batch_scratch(e, items, plan))) return rc;
-		ops.clear();
-		for (size_t b = first; b < first + items; b++) site_lnl_ops(T, left + b * N, right + b * N, roots[b], work, &ops);
-		lengths.assign(branch_lengths + first * N, branch_lengths + (first + items) * N);
-		for (size_t b = 0; b < items; b++) lengths[b * N + roots[first + b]] = 0.0;  // (ignored, as phyamd_set_branch_lengths does)
-		HIP_TRY(hipMemcpyAsync(e->d_batch_item_ops, ops.data(), sizeof(BatchOp) * items * nops, hipMemcpyHostToDevice, e->stream));
-		HIP_TRY(hipMemcpyAsync(e->d_batch_roots, roots + first, sizeof(int32_t) * items, hipMemcpyHostToDevice, e->stream));
-		HIP_TRY(hipMemcpyAsync(e->d_batch_len, lengths.data(), sizeof(double) * items * N, hipMemcpyHostToDevice, e->stream));
+	std::vector<BatchOp> work;
+	std::vector<double> out, rows, rell;
+	const auto item_ops = [&](const int32_t *l, const int32_t *r, int32_t root, std::vector<BatchOp> *ops) {
+		const int parks = site_lnl_ops(T, l, r, root, work, ops);
+		prof.lower_slots = std::max(prof.lower_slots, (int32_t)parks);
+		return parks;
+	};
+	const auto plan_of = [&](int slots) { return sitelnl_plan(e, slots, reps); };
+	const auto chunk = [&](size_t first, size_t items, int slots, const double *lengths, auto, auto) -> int {
+		HIP_TRY(hipMemcpyAsync(e->d_batch_len, lengths, sizeof(double) * items * N, hipMemcpyHostToDevice, e->stream));
 		launch_batch_matrices(e, (int)items, e->d_batch_len, e->d_batch_roots, e->d_batch_mats);
-		const SiteLnlArgs a{e->d_batch_item_ops, T, e->N, P, C, (int)nblk, chunk_slots, e->d_tipmask, e->d_freqs, e->d_props, e->d_weights, e->d_batch_mats,
+		const SiteLnlArgs a{e->d_batch_item_ops, T, e->N, P, C, (int)nblk, slots, e->d_tipmask, e->d_freqs, e->d_props, e->d_weights, e->d_batch_mats,
 		                    e->d_batch_lower, e->d_reweight_R, e->d_batch_lnl};
 		hipLaunchKernelGGL(k_sitelnl_walk4, dim3((unsigned)nblk, (unsigned)items), dim3(WAVE, C), 0, e->stream, a);
 		hipLaunchKernelGGL(k_batch_finish, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, e->stream, (int)items, e->N, C, (int)nblk, e->root, e->d_batch_roots.get(), 1,
@@ -1306,17 +1311,15 @@ int run_site_lnl(Shard *e, int flags, int32_t count, const int32_t *left, const 
 			rows.resize(items * Pc);
 			HIP_TRY(hipMemcpyAsync(rows.data(), e->d_reweight_R, sizeof(double) * items * Pc, hipMemcpyDeviceToHost, e->stream));
 		}
-		HIP_TRY(hipStreamSynchronize(e->stream));  // (also covers ops and lengths, reused by the next chunk)
+		HIP_TRY(hipStreamSynchronize(e->stream));  // (also covers the chunk's lists and lengths, reused by the next chunk)
 		std::copy(out.begin(), out.end(), lnl + first);
 		for (size_t b = 0; b < items && pattern_lnl; b++) std::copy(rows.begin() + b * Pc, rows.begin() + b * Pc + P, pattern_lnl + (first + b) * pattern_stride);
 		prof.chunks++;
-		for (size_t r0 = 0; r0 < R; r0 += reps) {
+		for (size_t r0 = 0; r0 < R; r0 += reps) {  // every replicate chunk is multiplied with the rows while they are resident
 			const size_t nr = std::min(reps, R - r0);
-			if ((size_t)P < Pc) HIP_TRY(hipMemsetAsync(e->d_reweight_w, 0, sizeof(double) * nr * Pc, e->stream));  // (a garbage NaN times a row's 0 is a NaN)
-			if ((rc = upload_rows(e, e->d_reweight_w, Pc, replicate_weights + r0 * weight_stride, weight_stride, (size_t)P, nr))) return rc;
-			const ReweightArgs w{e->d_reweight_w, e->d_reweight_R, e->d_reweight_part, nullptr, (int)nr, (int)items, (int)Pc, segments, e->N, C};
-			hipLaunchKernelGGL(k_reweight_mfma, dim3((unsigned)((items + 15) / 16), (unsigned)((nr + 15) / 16), (unsigned)segments), dim3(WAVE), 0, e->stream, w);
-			hipLaunchKernelGGL(k_sitelnl_rell_finish, dim3((unsigned)((nr * items + 255) / 256)), dim3(256), 0, e->stream, (int)nr, (int)items, segments, e->d_reweight_part.get(),
+			ReweightArgs w;
+			if (int rc = launch_reweight_product(e, replicate_weights + r0 * weight_stride, weight_stride, (size_t)P, nr, items, Pc, nullptr, &w)) return rc;
+			hipLaunchKernelGGL(k_sitelnl_rell_finish, dim3((unsigned)((nr * items + 255) / 256)), dim3(256), 0, e->stream, (int)nr, (int)items, w.segments, e->d_reweight_part.get(),
 			                   e->d_sitelnl_rell.get());
 			HIP_TRY(hipGetLastError());
 			rell.resize(nr * items);
@@ -1325,8 +1328,9 @@ int run_site_lnl(Shard *e, int flags, int32_t count, const int32_t *left, const 
 			for (size_t r = 0; r < nr; r++) std::copy(rell.begin() + r * items, rell.begin() + (r + 1) * items, replicate_lnl + (r0 + r) * (size_t)count + first);
 			if (first == 0) prof.replicate_chunks++;
 		}
-		first += items;
-	}
+		return PHYAMD_OK;
+	};
+	if ((rc = for_tree_chunks(e, name, 0, count, left, right, roots, branch_lengths, item_ops, plan_of, chunk))) return rc;
 	// a lnL that is not finite is in band whatever the rescaling mode (the engine is never switched): its replicates are all NaN
 	for (size_t b = 0; b < (size_t)count && R > 0; b++)
 		if (not_finite(lnl[b]))

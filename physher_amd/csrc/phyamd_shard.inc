@@ -217,10 +217,10 @@ struct Shard {
 	DeviceArray<double> d_batch_lower{&batch_mem}, d_batch_upper{&batch_mem}, d_batch_slab{&batch_mem}, d_batch_lnl{&batch_mem};
 	DeviceArray<BatchOp> d_batch_item_ops{&batch_mem};  // [item][post-order T - 1 | pre-order T - 1]
 	DeviceArray<int32_t> d_batch_roots{&batch_mem};     // [item]
-	// what the scratch holds: every call describes what it needs as a ScratchPlan (phyamd_queries.inc: batch_plan, nni_plan, spr_plan,
-	// bhess_plan) and gets at least that, so a call of one kind never runs in the scratch of another with too few upper slots or
-	// without its lists.  batch_held: the plan the arrays were last allocated by, for batch_items items (the Hessian's arrays, grown
-	// beside it, are judged by their sizes alone)
+	// what the scratch holds: every call describes what it needs as a ScratchPlan (phyamd_queries.inc: batch_plan, reweight_plan,
+	// nni_base_plan with nni_plan and cbopt_plan, spr_plan, bhess_plan, sitelnl_plan) and gets at least that, so a call of one kind
+	// never runs in the scratch of another with too few upper slots or without its lists.  batch_held: the plan the arrays were last
+	// allocated by, for batch_items items (the Hessian's arrays, grown beside it, are judged by their sizes alone)
 	ScratchPlan batch_held;
 	size_t batch_items = 0;
 	phyamd_batch_profile batch_prof{};

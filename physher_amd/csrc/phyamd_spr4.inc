@@ -72,11 +72,7 @@ struct SprCand {
 	int32_t pad[3];
 };
 
-__device__ __forceinline__ SprCand load_spr_cand(const SprCand *cands, int i) {  // (as load_batch_op: one s_load_dwordx8)
-	typedef const __attribute__((address_space(4))) int32_t *cint;
-	const cint o = (cint)reinterpret_cast<const int32_t *>(cands + i);
-	return SprCand{o[0], o[1], o[2], o[3], o[4], {0, 0, 0}};
-}
+__device__ __forceinline__ SprCand load_spr_cand(const SprCand *cands, int i) { return load_const_record<5>(cands, i); }
 
 struct SprArgs {
 	const SprCand *cands;    // [gridDim.y], row-major: neighbouring workgroups share p's lower and the row's scratch in L2
@@ -103,12 +99,9 @@ __global__ __launch_bounds__(BATCH_MAX_CATEGORIES *WAVE) void k_spr4(const SprAr
 	const size_t cell = ((size_t)cd.row * (a.T - 1) * a.C + c) * plane + (size_t)k0 * 4;
 	const cptr mats_c = as_const(a.mats + (size_t)c * 16), half_c = as_const(a.half + (size_t)c * 16);
 	const double *lower_c = a.lower + cell, *upper_c = a.upper + cell;
-	// M . mask for a tip, M . p_node (the pruned tree's) for an internal node.  The product is formed inside either branch: after
-	// them, the scalar loads of three matrices meet in one block and overflow the SGPRs
-	const auto message = [&](cptr M, int node) {
-		if (node < a.T) return matvec4(opaque(M), mask4(a.tipmask[(size_t)node * a.P + k]));
-		return matvec4(opaque(M), load4(lower_c + (size_t)(node - a.T) * node_stride));
-	};
+	// M . mask for a tip, M . p_node (the pruned tree's) for an internal node.  The product is formed inside either branch
+	// (child_message4 does): after them, the scalar loads of three matrices meet in one block and overflow the SGPRs
+	const auto message = [&](cptr M, int node) { return child_message4(M, a.tipmask + k, a.P, lower_c, node_stride, a.T, node); };
 	const cptr Hw = half_c + (size_t)cd.w * a.C * 16;
 	const d4 lo = message(Hw, cd.w), mp = message(mats_c + (size_t)cd.p * a.C * 16, cd.p);
 	d4 U = message(mats_c + (size_t)cd.y * a.C * 16, cd.y);
