@@ -166,15 +166,16 @@ def branch_gradient_from_cat(cat_grad, cat_rates, cat_props, zero_node=None):
 
 
 def parameter_matrix(eval_, evec, ivec, dQ, t):
-    """dP/dtheta at time t from dQ/dtheta: dPdp_with_dQdp (substmodel.c:469-489)."""
+    """dP/dtheta at time t from dQ/dtheta: U (B o F) U^-1 with B = U^-1 dQ U, the structure of dPdp_with_dQdp (substmodel.c:469-489).
+    F_ab = (e^{l_a t} - e^{l_b t}) / (l_a - l_b) is formed as e^{hi t} (1 - e^{-(hi - lo) t}) / (hi - lo) with expm1, and is t e^{l_a t}
+    where the two are equal.  The reference's quotient of two differences (:478) is rounding noise where an eigen solver has split a
+    repeated eigenvalue by an ulp (K80, F81, GTR near them): a quirk this yardstick does not restate (DESIGN.md "Reference quirks")."""
     lam = np.asarray(eval_, dtype=np.float64)
-    e = np.exp(lam * t)
     B = np.asarray(ivec) @ np.asarray(dQ) @ np.asarray(evec)
-    S = len(lam)
-    F = np.empty((S, S))
-    for i in range(S):
-        for j in range(S):
-            F[i, j] = (e[i] - e[j]) / (lam[i] - lam[j]) if lam[i] != lam[j] else t * e[i]
+    hi = np.maximum(lam[:, None], lam[None, :])
+    d = hi - np.minimum(lam[:, None], lam[None, :])
+    safe = np.where(d != 0.0, d, 1.0)
+    F = np.exp(hi * t) * np.where(d != 0.0, -np.expm1(-safe * t) / safe, t)
     return np.asarray(evec) @ (B * F) @ np.asarray(ivec)
 
 

@@ -147,9 +147,19 @@ __global__ void k_tip_tables(int T, int C, const double *__restrict__ mats, doub
 	tiptab[idx] = s;
 }
 
+// F_ab(t) = (e^{l_a t} - e^{l_b t}) / (l_a - l_b), the divided difference of exp(l t) that dP/dtheta weighs U^-1 dQ U with, and its
+// limit t e^{l_a t} where l_a == l_b.  Formed as e^{hi t} (1 - e^{-(hi - lo) t}) / (hi - lo) with expm1: an eigen solver returns a
+// repeated eigenvalue (K80, F81, any GTR near them) split by an ulp or so, where the quotient of the two differences is rounding
+// noise -- the reference's form (dPdp_with_dQdp, substmodel.c:478) and its l_a == l_b test do not survive that.  With the larger
+// eigenvalue in front nothing overflows on a saturated branch: e^{hi t} <= 1 and the bracket lies in [0, 1].
+__device__ __forceinline__ double exp_divided_difference(double la, double lb, double t) {
+	const double hi = fmax(la, lb), d = hi - fmin(la, lb), eh = exp(hi * t);
+	return d != 0.0 ? eh * (-expm1(-d * t) / d) : t * eh;
+}
+
 // G2: dP/dtheta for every (parameter, node, category) from B_theta = U^-1 (dQ/dtheta) U:
-//   dP = U ( B o F(t) ) U^-1,  F_ab = (e^{l_a t} - e^{l_b t}) / (l_a - l_b)  or  t e^{l_a t} when l_a == l_b
-// (dPdp_with_dQdp, substmodel.c:469-489).  dpm: [NP][N][C][S][S]; root and explicit-matrix nodes get zeros.
+//   dP = U ( B o F(t) ) U^-1,  F_ab = exp_divided_difference(l_a, l_b, t)
+// (the structure of dPdp_with_dQdp, substmodel.c:469-489).  dpm: [NP][N][C][S][S]; root and explicit-matrix nodes get zeros.
 __global__ void k_parameter_matrices(int S, int C, int node_count, int np, const double *__restrict__ model, const double *__restrict__ B,
                                      const double *__restrict__ rates, const double *__restrict__ lengths,
                                      const uint8_t *__restrict__ is_explicit, int root, double *__restrict__ dpm) {
@@ -166,12 +176,8 @@ __global__ void k_parameter_matrices(int S, int C, int node_count, int np, const
 			const double t = lengths[n] * rates[c];
 			const double *Bt = B + (size_t)th * S * S;
 			for (int a = 0; a < S; a++) {
-				const double ea = exp(eval[a] * t);
 				double row = 0.0;
-				for (int b = 0; b < S; b++) {
-					const double f = eval[a] != eval[b] ? (ea - exp(eval[b] * t)) / (eval[a] - eval[b]) : t * ea;
-					row += Bt[a * S + b] * f * ivec[b * S + j];
-				}
+				for (int b = 0; b < S; b++) row += Bt[a * S + b] * exp_divided_difference(eval[a], eval[b], t) * ivec[b * S + j];
 				v += evec[i * S + a] * row;
 			}
 		}

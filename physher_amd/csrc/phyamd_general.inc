@@ -870,7 +870,7 @@ __global__ void k_planes_to_reference(int P, int Pp, int S, int C, const double 
 //   den[n][k]   = sum_c w_c sum_i f_i u_n,i (P_n p_n)_i         the site likelihood in the units of branch n (any rescaling
 //                                                                factors of u and p cancel against the numerator below)
 //   W^{nc}_ij   = sum_k (w_k / den[n][k]) f_i u_i p_j            outer products over the patterns
-//   G^{nc}      = w_c F(t_n r_c) o (U^T W U^-T),  F_ab = (e^{l_a t} - e^{l_b t}) / (l_a - l_b) or t e^{l_a t}
+//   G^{nc}      = w_c F(t_n r_c) o (U^T W U^-T),  F_ab = exp_divided_difference(l_a, l_b, t) (phyamd_device.inc)
 //   d lnL / d theta = sum_ab (U^-1 dQ_theta U)_ab sum_{n,c} G^{nc}_ab      (dPdp_with_dQdp_general, gensubst.c:284-308)
 
 // p_j of a tip from its code (state, S = unknown, S + 1 + q = ambiguity set q)
@@ -977,9 +977,7 @@ __global__ __launch_bounds__(256) void k_param_outer_gen(const int *__restrict__
 		const int a = ab / S, b = ab % S;
 		double s = 0.0;
 		for (int j = 0; j < S; j++) s += B[a * S + j] * Ui[b * S + j];
-		const double la = ev[a], lb = ev[b];
-		const double F = la != lb ? exp(lb * t) * expm1((la - lb) * t) / (la - lb) : t * exp(la * t);
-		out[ab] = w * F * s;
+		out[ab] = w * exp_divided_difference(ev[a], ev[b], t) * s;
 	}
 }
 

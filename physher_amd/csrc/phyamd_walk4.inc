@@ -515,8 +515,8 @@ __global__ __launch_bounds__(WAVES *WAVE, WAVES == 4 ? (PARAMS ? 3 : (SCALE ? WA
 	}
 }
 
-// G2 tables of the tree-walk kernel: Fw[n][c][20] = 16 entries w_c F_ab(t_n r_c) + 4 entries l_a e^{l_a t_n r_c}; F_ab = (e^{l_a t} - e^{l_b t}) / (l_a - l_b) or
-// t e^{l_a t} (dPdp_with_dQdp, substmodel.c:469-489); root and explicit-matrix nodes get zeros.  4 states.
+// G2 tables of the tree-walk kernel: Fw[n][c][20] = 16 entries w_c F_ab(t_n r_c) + 4 entries l_a e^{l_a t_n r_c}; F_ab = exp_divided_difference(l_a, l_b, t)
+// (phyamd_device.inc: stable at repeated and nearly repeated eigenvalues); root and explicit-matrix nodes get zeros.  4 states.
 __global__ void k_eigen_weights(int C, int node_count, const double *__restrict__ model, const double *__restrict__ rates,
                                 const double *__restrict__ props, const double *__restrict__ lengths, const uint8_t *__restrict__ is_explicit, int root,
                                 double *__restrict__ Fw) {
@@ -527,8 +527,7 @@ __global__ void k_eigen_weights(int C, int node_count, const double *__restrict_
 	if (n != root && !is_explicit[n]) {
 		const double t = lengths[n] * rates[c];
 		if (e < 16) {
-			const double la = model[e >> 2], lb = model[e & 3], ea = exp(la * t);
-			v = props[c] * (la != lb ? (ea - exp(lb * t)) / (la - lb) : t * ea);
+			v = props[c] * exp_divided_difference(model[e >> 2], model[e & 3], t);
 		} else {  // l_a e^{l_a t}: (Q P)'s eigenvalues; the category weight is applied by the caller's epilogue, not here
 			const double la = model[e - 16];
 			v = la * exp(la * t);
