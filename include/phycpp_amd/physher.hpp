@@ -320,6 +320,17 @@ class TreeLikelihoodInterface : public CallableModelInterface {
 	// model and this object's own state are unchanged.
 	void NNIOptimize(const double *startLengths, double lower, double upper, double tolerance, int maxIterations, double *lengths, double *logLikelihoods, double *d1,
 	                 double *d2, int32_t *iterations);
+	// Every branch length of `count` TREES optimised on the device, one branch at a time, pass after pass (one
+	// phyamd_optimize_branch_lengths call; see include/physher_amd.h for the rule): left, right, roots and branchLengths are
+	// LogLikelihoodTrees' arrays, branchLengths the start; optimise [count][2T-1] marks the nodes whose branches are visited, or null:
+	// every node but the root.  A visit seeks its branch's optimum in [lower, upper] until a step is no longer than tolerance, in at
+	// most maxIterations steps; an item stops when a pass gains no more than lnlTolerance, or after maxPasses passes.  lengths
+	// [count][2T-1] by the item's node ids, logLikelihoods [count]; initialLogLikelihoods [count] and passes [count] (negative: the
+	// passes ran out, or lnL was not finite) may be null.  Lengths are the engine's branch lengths, as for NNILogLikelihoods.  The
+	// tree model and this object's own state are unchanged.
+	void OptimizeBranchLengths(size_t count, const int32_t *left, const int32_t *right, const int32_t *roots, const double *branchLengths, const uint8_t *optimise,
+	                           double lower, double upper, double tolerance, int maxIterations, double lnlTolerance, int maxPasses, double *lengths,
+	                           double *logLikelihoods, double *initialLogLikelihoods, int32_t *passes);
 	// lnL of every SPR regraft of `count` prune nodes of the tree model's tree at once (one phyamd_spr_log_likelihoods call; see
 	// include/physher_amd.h for the move and the candidates): out [count][2T-1] by the tree's node ids, row i the prune node
 	// prune[i] (null: count = 2T-1 and row i is node i), column w the target edge; NaN where there is no candidate.  Lengths are

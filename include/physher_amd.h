@@ -631,6 +631,71 @@ int phyamd_set_reduction_levels(phyamd_engine *e, int levels);
 int phyamd_set_profiling(phyamd_engine *e, int on);
 int phyamd_get_profile(phyamd_engine *e, phyamd_profile *out);
 
+/* --- all branch lengths of a batch of trees --- */
+/* Every branch length of `count` trees optimised on the device, one branch at a time, pass after pass: the sweep a hill-climb runs
+ * between topology rounds, for many trees at once.  left, right [count][2T-1] and roots [count] are the items, each in
+ * phyamd_gradient_batch_trees' convention, or all three NULL: every item is the engine's tree.  branch_lengths [count][2T-1], by the
+ * ITEM's node ids, is the start.  optimise [count][2T-1] marks the nodes whose branches are visited (non-zero), or NULL: every node
+ * but the root; the root's own entry is ignored.
+ * THE RULE.  The state of an item is its lengths t, a copy of the start.  Entries of the root and of nodes that are not visited
+ * are never changed and come back in `lengths` bit for bit.
+ *   A pass visits the nodes n with n != root and optimise[n] != 0 in the post-order of the item's tree: the left subtree, the right
+ * subtree, then the node.
+ *   A visit of n: f(t) = (lnL, d1, d2) of the item's tree with t_n = t and every other length as it stands now, d1 and d2 by
+ * phyamd_branch_hessian_diagonal's definitions.  t0 = clamp(t_n, lower, upper).  t' comes from phyamd_nni_optimize's rule started at
+ * t0: t = t0, a = lower, b = upper; each iteration evaluates d1(t) and d2(t); if d1 > 0 then a = t, else b = t; it proposes
+ * t' = t - d1 / d2 when d2 < 0 and a < t' < b, otherwise t' = (a + b) / 2; it stops when |t' - t| <= tolerance or after
+ * max_iterations proposals.  The visit accepts t_n = t' when lnL(t') is finite and lnL(t') >= lnL(t0); otherwise t_n = t0.  So lnL
+ * never falls from visit to visit.
+ *   A lnL that is not finite at an iterate (one of the t whose d1 and d2 the iteration evaluates, t0 among them) ends the item in
+ * band: lengths is the state before that visit, lnl the value that is not finite, passes the negated index of the pass (from 1).
+ * The engine is never switched to rescaling, under PHYAMD_RESCALE_NEVER and _AUTO alike.
+ *   After pass p: lnl_p is lnL at the current lengths (lnl_0 that of the start, which initial_lnl reports).  The item stops when
+ * lnl_p - lnl_(p-1) <= lnl_tolerance, with passes = p; after max_passes passes without that, with passes = -max_passes.  With
+ * nothing to visit passes = 0 and lnl = initial_lnl.
+ *   The root's two children are not special: for a reversible model only their sum matters, and a caller who wants the
+ * reference's convention sends one of them with optimise = 0.
+ * lnl and the derivatives of a visit are formed from the eigen system like phyamd_nni_optimize's (without the reference's fabs on
+ * P(t): a rounding difference); initial_lnl is phyamd_gradient_batch_trees' lnl of the start.  initial_lnl and passes may be NULL.
+ * The engine -- its topology, lengths, partials -- is unchanged and later evaluations return the bits they would have returned
+ * without the call; two calls return identical bits; an item's bits do not depend on `count`, its position, the other items, the
+ * chunks the items ran in, the optional outputs or what the batch scratch held.  The scratch is the batch scratch's: per item the
+ * lnL-only walk's of phyamd_gradient_batch_trees and a partial per node; items that do not fit the memory cap together run in chunks.
+ * Every item is validated on the host before anything is launched, with its index in the message.  There is no fallback path:
+ * PHYAMD_EUNSUPPORTED, naming the condition, under phyamd_gradient_batch_trees' conditions (not 4 states, more than 8 categories, an
+ * engine that is rescaling now, tiled patterns, a tip cell with an empty state mask, explicit node matrices, scratch of one item
+ * that does not fit the memory cap), for flags other than 0, and on a handle sharded over several devices (every iteration would
+ * need a sum across the shards).  PHYAMD_EINVAL: null engine, branch_lengths, lengths or lnl; only some of left / right / roots
+ * null; count < 1; no eigen system; bounds that are not 0 <= lower < upper < inf; a tolerance that is not finite and positive;
+ * max_iterations outside 1..1000; an lnl_tolerance that is negative or not finite; max_passes outside 1..1000; an invalid tree; a
+ * negative or non-finite start length of a visited node. */
+int phyamd_optimize_branch_lengths(phyamd_engine *e, int flags, int32_t count,
+                                   const int32_t *left, const int32_t *right, const int32_t *roots, /* [count][2T-1], [count]; or all NULL */
+                                   const double *branch_lengths /* [count][2T-1] */, const uint8_t *optimise /* [count][2T-1] or NULL */,
+                                   double lower, double upper, double tolerance, int32_t max_iterations,
+                                   double lnl_tolerance, int32_t max_passes,
+                                   double *lengths /* [count][2T-1] */, double *lnl /* [count] */,
+                                   double *initial_lnl /* [count] or NULL */, int32_t *passes /* [count] or NULL */);
+/* of the last phyamd_optimize_branch_lengths: items, chunks of items they ran in, the most passes a chunk ran, visits made and
+ * proposals made over all items, bytes of batch scratch the engine holds (see phyamd_batch_profile), wall time of the call */
+typedef struct { int32_t items, chunks, passes; int64_t visits, iterations, scratch_bytes; double ms; } phyamd_branch_optimize_profile;
+int phyamd_get_branch_optimize_profile(phyamd_engine *e, phyamd_branch_optimize_profile *out);
+/* One pass of phyamd_optimize_branch_lengths over a tree as the device runs it, from the host schedule alone (no device, no
+ * engine): a depth-first tour that, on entering an internal node, forms what meets each child's branch from above (O), and on
+ * leaving it forms the node's lower partial (p) again and visits it.  The ops in launch order, six ints each:
+ *   0 the index of the visit the op belongs to (an op that is no visit runs in front of that visit) |
+ *   1 kind: 0 forms O of a node, 1 forms p of an internal node, 2 is the visit of a node |
+ *   2 the node |
+ *   3, 4 operands -- kind 0: the node's parent, whose O and matrix are read (-3: the parent is the root, which has no O), and its
+ *        sibling, whose message is read; kind 1: the node's left and right child, whose messages are read; kind 2: the plane of
+ *        the node's O and of its p (-1: a tip, whose p is its data) |
+ *   5 the plane written: node for O of a node, 2T-1 + (node - T) for p of an internal node, -1 for a visit.
+ * A message of a node reads its matrix and, for an internal node, its p.  Every node but the root is visited once, in post-order
+ * (left subtree, right subtree, node); a visit changes the node's length, that is its matrix.  Returns the number of ops,
+ * 5 T - 6 (at most `capacity` of them are written), or a negative PHYAMD_E* code. */
+int phyamd_branch_sweep_schedule(int32_t tip_count, const int32_t *left /* [2T-1] */, const int32_t *right, int32_t root,
+                                 int32_t *out /* [capacity][6] */, int32_t capacity);
+
 #ifdef __cplusplus
 }
 #endif

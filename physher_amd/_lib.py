@@ -43,6 +43,11 @@ class NniOptimizeProfile(C.Structure):
     _fields_ = [("candidates", C.c_int32), ("chunks", C.c_int32), ("scratch_bytes", C.c_int64), ("iterations", C.c_int64), ("ms", C.c_double)]
 
 
+class BranchOptimizeProfile(C.Structure):
+    _fields_ = [("items", C.c_int32), ("chunks", C.c_int32), ("passes", C.c_int32), ("visits", C.c_int64), ("iterations", C.c_int64),
+                ("scratch_bytes", C.c_int64), ("ms", C.c_double)]
+
+
 class SprProfile(C.Structure):
     _fields_ = [("prunes", C.c_int32), ("chunks", C.c_int32), ("candidates", C.c_int64), ("scratch_bytes", C.c_int64), ("ms", C.c_double)]
 
@@ -118,6 +123,10 @@ SYMBOLS = [
     ("phyamd_get_nni_profile", C.c_int, [_P, C.POINTER(NniProfile)]),
     ("phyamd_nni_optimize", C.c_int, [_P, C.c_int, _P, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P, _P, _P, _P]),
     ("phyamd_get_nni_optimize_profile", C.c_int, [_P, C.POINTER(NniOptimizeProfile)]),
+    ("phyamd_optimize_branch_lengths", C.c_int, [_P, C.c_int, C.c_int32, _P, _P, _P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_double,
+                                                 C.c_int32, _P, _P, _P, _P]),
+    ("phyamd_get_branch_optimize_profile", C.c_int, [_P, C.POINTER(BranchOptimizeProfile)]),
+    ("phyamd_branch_sweep_schedule", C.c_int, [C.c_int32, _P, _P, C.c_int32, _P, C.c_int32]),
     ("phyamd_spr_log_likelihoods", C.c_int, [_P, C.c_int, C.c_int32, _P, _P]),
     ("phyamd_get_spr_profile", C.c_int, [_P, C.POINTER(SprProfile)]),
     ("phyamd_state_posteriors", C.c_int, [_P, C.c_int, C.c_int32, _P, _P, _P]),

@@ -947,6 +947,18 @@ void TreeLikelihoodInterface::NNIOptimize(const double *startLengths, double low
 	phyamd::check(phyamd_nni_optimize(impl_->engine, 0, startLengths, lower, upper, tolerance, maxIterations, lengths, logLikelihoods, d1, d2, iterations));
 }
 
+void TreeLikelihoodInterface::OptimizeBranchLengths(size_t count, const int32_t *left, const int32_t *right, const int32_t *roots, const double *branchLengths,
+                                                    const uint8_t *optimise, double lower, double upper, double tolerance, int maxIterations, double lnlTolerance,
+                                                    int maxPasses, double *lengths, double *logLikelihoods, double *initialLogLikelihoods, int32_t *passes) {
+	if (count == 0) return;
+	if (!left || !right || !roots || !branchLengths) throw Error("null left, right, roots or branchLengths");
+	if (!lengths || !logLikelihoods) throw Error("null lengths or logLikelihoods");
+	if (count > (size_t)INT32_MAX) throw Error("a batch takes at most 2^31 - 1 items");
+	Sync();
+	phyamd::check(phyamd_optimize_branch_lengths(impl_->engine, 0, (int32_t)count, left, right, roots, branchLengths, optimise, lower, upper, tolerance, maxIterations,
+	                                             lnlTolerance, maxPasses, lengths, logLikelihoods, initialLogLikelihoods, passes));
+}
+
 void TreeLikelihoodInterface::SPRLogLikelihoods(const int *prune, int count, double *out) {
 	if (!out) throw Error("null out");
 	Sync();

@@ -273,6 +273,18 @@ PYBIND11_MODULE(_phycpp_amd, m) {
 		    const std::vector<py::ssize_t> shape{3, N};
 		    return py::make_tuple(darray(shape, len.data()), darray(shape, lnl.data()), darray(shape, d1.data()), darray(shape, d2.data()), iarray(shape, it.data()));
 	    }, py::arg("start_lengths") = py::none(), py::arg("lower") = 1e-8, py::arg("upper") = 10.0, py::arg("tolerance") = 1e-8, py::arg("max_iterations") = 100)
+	    .def("optimize_branch_lengths", [](TreeLikelihoodInterface &self, iarray left, iarray right, iarray roots, darray lengths, std::optional<py::array_t<uint8_t, py::array::c_style | py::array::forcecast>> optimise,
+	                                       double lower, double upper, double tolerance, int max_iterations, double lnl_tolerance, int max_passes) -> py::tuple {
+		    const size_t count = check_trees(self, left, right, roots, lengths);
+		    const py::ssize_t N = (py::ssize_t)self.NodeCount();
+		    if (optimise && (optimise->ndim() != 2 || (size_t)optimise->shape(0) != count || optimise->shape(1) != N)) throw phyamd::Error("optimise: [count][node_count]");
+		    std::vector<double> len(count * (size_t)N), lnl(count), lnl0(count);
+		    std::vector<int32_t> passes(count);
+		    self.OptimizeBranchLengths(count, left.data(), right.data(), roots.data(), lengths.data(), optimise ? optimise->data() : nullptr, lower, upper, tolerance,
+		                               max_iterations, lnl_tolerance, max_passes, len.data(), lnl.data(), lnl0.data(), passes.data());
+		    return py::make_tuple(darray({(py::ssize_t)count, N}, len.data()), vec(lnl), vec(lnl0), iarray(std::vector<py::ssize_t>{(py::ssize_t)count}, passes.data()));
+	    }, py::arg("left"), py::arg("right"), py::arg("roots"), py::arg("branch_lengths"), py::arg("optimise") = py::none(), py::arg("lower") = 1e-8, py::arg("upper") = 10.0,
+	       py::arg("tolerance") = 1e-8, py::arg("max_iterations") = 100, py::arg("lnl_tolerance") = 1e-6, py::arg("max_passes") = 50)
 	    .def("spr_log_likelihoods", [](TreeLikelihoodInterface &self, std::optional<iarray> prune) {
 		    const py::ssize_t N = (py::ssize_t)self.NodeCount();
 		    if (prune && prune->ndim() != 1) throw phyamd::Error("prune: [count]");

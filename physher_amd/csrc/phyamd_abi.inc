@@ -627,6 +627,32 @@ int phyamd_get_nni_optimize_profile(phyamd_engine *g, phyamd_nni_optimize_profil
 	return merged_profile(g, &Shard::cbopt_prof, out, [](phyamd_nni_optimize_profile &, const phyamd_nni_optimize_profile &) {});  // (never sharded)
 }
 
+// one device only: every iteration of a visit would need its sums across the shards
+int phyamd_optimize_branch_lengths(phyamd_engine *g, int flags, int32_t count, const int32_t *left, const int32_t *right, const int32_t *roots, const double *branch_lengths,
+                                   const uint8_t *optimise, double lower, double upper, double tolerance, int32_t max_iterations, double lnl_tolerance, int32_t max_passes,
+                                   double *lengths, double *lnl, double *initial_lnl, int32_t *passes) {
+	static const char *const name = "phyamd_optimize_branch_lengths";
+	if (!branch_lengths || !lengths || !lnl) return fail(PHYAMD_EINVAL, "%s: null %s", name, !branch_lengths ? "branch_lengths" : !lengths ? "lengths" : "lnl");
+	if ((!left || !right || !roots) && (left || right || roots))
+		return fail(PHYAMD_EINVAL, "%s: null %s (left, right and roots are given together, or all three are null: the engine's tree)", name,
+		            !left ? "left" : !right ? "right" : "roots");
+	if (count < 1) return fail(PHYAMD_EINVAL, "%s: count must be >= 1 (got %d)", name, count);
+	if (!g || g->shards.empty()) return fail(PHYAMD_EINVAL, "%s: null engine", name);
+	if (!(lower >= 0.0 && lower < upper && std::isfinite(upper))) return fail(PHYAMD_EINVAL, "%s: bounds [%g, %g]: they must be 0 <= lower < upper < inf", name, lower, upper);
+	if (!(tolerance > 0.0 && std::isfinite(tolerance))) return fail(PHYAMD_EINVAL, "%s: tolerance %g: it must be finite and positive", name, tolerance);
+	if (max_iterations < 1 || max_iterations > 1000) return fail(PHYAMD_EINVAL, "%s: max_iterations %d is outside 1..1000", name, max_iterations);
+	if (!(lnl_tolerance >= 0.0 && std::isfinite(lnl_tolerance))) return fail(PHYAMD_EINVAL, "%s: lnl_tolerance %g: it must be finite and not negative", name, lnl_tolerance);
+	if (max_passes < 1 || max_passes > 1000) return fail(PHYAMD_EINVAL, "%s: max_passes %d is outside 1..1000", name, max_passes);
+	if (group_size(g) > 1)
+		return fail(PHYAMD_EUNSUPPORTED, "%s: a handle sharded over several devices is out of scope: every iteration of a visit would need a sum across the shards", name);
+	return shard_branch_optimize(g->shards[0], flags, BranchOptimizeArgs{count, left, right, roots, branch_lengths, optimise, lower, upper, tolerance, max_iterations, lnl_tolerance,
+	                                                                      max_passes, lengths, lnl, initial_lnl, passes});
+}
+
+int phyamd_get_branch_optimize_profile(phyamd_engine *g, phyamd_branch_optimize_profile *out) {
+	return merged_profile(g, &Shard::blopt_prof, out, [](phyamd_branch_optimize_profile &, const phyamd_branch_optimize_profile &) {});  // (never sharded)
+}
+
 // every shard scores every row on its patterns; the rows are sums over patterns, added in shard order (NaN cells stay NaN)
 int phyamd_spr_log_likelihoods(phyamd_engine *g, int flags, int32_t count, const int32_t *prune, double *lnl) {
 	if (count < 1) return fail(PHYAMD_EINVAL, "phyamd_spr_log_likelihoods: count must be >= 1 (got %d)", count);

@@ -781,6 +781,170 @@ int shard_nni_optimize(Shard *e, int flags, const NniOptimizeArgs &o) {
 	return profiled_call(e, &Shard::cbopt_prof, phyamd_nni_optimize_profile{}, [&](phyamd_nni_optimize_profile &prof) { return run_nni_optimize(e, flags, o, prof); });
 }
 
+// ---- all branch lengths of a batch of trees (phyamd_optimize_branch_lengths) -----------------------------------------------------
+
+// per item: the lnL-only walk's of a batch of trees (batch_plan: lengths, matrices, lnL, every internal lower, op lists, root), a
+// plane O_n per node, the visited branch's coefficients, the tour's ops and visit slots, the mask, lnL before and now, the status
+ScratchPlan blopt_plan(Shard *e) {
+	const size_t D = sizeof(double), N = (size_t)e->N, C = (size_t)e->C, nblk = ((size_t)e->P + WAVE - 1) / WAVE, plane = nblk * WAVE * 4;
+	ScratchPlan p = batch_plan(e, false, 1, true);
+	p.add(e->d_blopt_O, D * N * C * plane);
+	p.add(e->d_blopt_K, D * C * plane);
+	p.add(e->d_blopt_ops, sizeof(BloptOp) * 3 * (size_t)(e->T - 1));
+	p.add(e->d_blopt_visits, sizeof(BloptVisit) * 2 * (size_t)(e->T - 1));
+	p.add(e->d_blopt_mask, N);
+	p.add(e->d_blopt_lnl, D * 2);
+	p.add(e->d_blopt_status, sizeof(int32_t) * BLOPT_STATUS);
+	return p;
+}
+
+struct BranchOptimizeArgs {
+	int32_t count;
+	const int32_t *left, *right, *roots;
+	const double *start;
+	const uint8_t *optimise;
+	double lower, upper, tolerance;
+	int32_t max_iterations;
+	double lnl_tolerance;
+	int32_t max_passes;
+	double *lengths, *lnl, *initial_lnl;
+	int32_t *passes;
+};
+
+// the items in chunks of what the scratch holds (for_tree_chunks); per chunk the lnL-only walk of the tree batch, then pass after
+// pass every visit slot's two launches, enqueued without a wait; the status words come back once per pass.  Reads the engine's
+// inputs and writes only the batch scratch: nothing in Shard::state changes
+int run_branch_optimize(Shard *e, int flags, const BranchOptimizeArgs &o, phyamd_branch_optimize_profile &prof) {
+	static const char *const name = "phyamd_optimize_branch_lengths";
+	int rc;
+	if ((rc = check_ready_but_lengths(e))) return fail(rc, "%s: the engine is not ready: %s", name, std::string(g_last_error).c_str());
+	if (flags != 0) return fail(PHYAMD_EUNSUPPORTED, "%s: flags %d (no flags are defined: pass 0)", name, flags);
+	if (const char *why = tree_batch_refusal(e, 0, 1)) return fail(PHYAMD_EUNSUPPORTED, "%s: %s", name, why);
+	if (!e->have_eigen) return fail(PHYAMD_EINVAL, "%s needs the eigen system (phyamd_set_eigen): the likelihood in a branch length is formed from it", name);
+	const int T = e->T, C = e->C, nblk = (e->P + WAVE - 1) / WAVE, nvisits = 2 * (T - 1), nops = 3 * (T - 1);
+	const size_t N = (size_t)e->N, count = (size_t)o.count;
+	const int32_t *left = o.left, *right = o.right, *roots = o.roots;
+	std::vector<int32_t> own_left, own_right, own_roots;
+	if (!left) {  // every item is the engine's tree
+		for (size_t b = 0; b < count; b++) {
+			own_left.insert(own_left.end(), e->left.begin(), e->left.end());
+			own_right.insert(own_right.end(), e->right.begin(), e->right.end());
+		}
+		own_roots.assign(count, e->root);
+		left = own_left.data(), right = own_right.data(), roots = own_roots.data();
+	}
+	// every item before anything is launched: its tree, then the start lengths of the nodes it visits
+	std::vector<uint8_t> mask(count * N, 1);
+	{
+		std::vector<int32_t> parents;
+		for (size_t b = 0; b < count; b++) {
+			const std::string err = validate_tree(TreeRef{T, left + b * N, right + b * N, roots[b]}, parents, name, (int)b);
+			if (!err.empty()) return fail(PHYAMD_EINVAL, "%s", err.c_str());
+			for (size_t n = 0; n < N; n++) {
+				uint8_t &m = mask[b * N + n];
+				m = (int32_t)n != roots[b] && (!o.optimise || o.optimise[b * N + n]) ? 1 : 0;
+				const double t = o.start[b * N + n];
+				if (m && (!std::isfinite(t) || t < 0.0))
+					return fail(PHYAMD_EINVAL, "%s: item %zu: branch_lengths[%zu] = %g: the start length of a visited node is finite and not negative", name, b, n, t);
+			}
+		}
+	}
+	std::copy(o.start, o.start + count * N, o.lengths);
+	std::vector<SweepOp> sweep;
+	std::vector<BloptOp> ops;
+	std::vector<BloptVisit> visits;
+	std::vector<double> out, lnl2, len;
+	std::vector<int32_t> status;
+	const auto item_ops = [&](const int32_t *l, const int32_t *r, int32_t root, std::vector<BatchOp> *list) { return list ? build_batch_ops(T, l, r, root, list) : 1; };
+	const auto plan_of = [&](int) { return blopt_plan(e); };
+	const auto chunk = [&](size_t first, size_t items, int, const double *lengths, auto, auto) -> int {
+		// the tours, and which items have anything to visit
+		ops.assign(items * nops, BloptOp{});
+		visits.assign(items * nvisits, BloptVisit{});
+		status.assign(items * BLOPT_STATUS, 0);
+		for (size_t b = 0; b < items; b++) {
+			sweep.clear();
+			build_branch_sweep(T, left + (first + b) * N, right + (first + b) * N, roots[first + b], &sweep);
+			BloptOp *io = &ops[b * nops];
+			BloptVisit *iv = &visits[b * nvisits];
+			int32_t at = 0;
+			for (const SweepOp &s : sweep) {
+				if (s.kind != SWEEP_VISIT) {
+					io[at++] = BloptOp{s.kind, s.node, s.a, s.b, {0, 0, 0, 0}};
+					continue;
+				}
+				iv[s.visit] = BloptVisit{s.node, s.visit ? iv[s.visit - 1].end : 0, at, s.visit + 1 == nvisits ? 1 : 0, {0, 0, 0, 0}};
+			}
+			const uint8_t *m = &mask[(first + b) * N];
+			if (!std::any_of(m, m + N, [](uint8_t x) { return x != 0; })) status[b * BLOPT_STATUS + BLOPT_DONE] = 1;  // (passes: 0)
+		}
+		HIP_TRY(hipMemcpyAsync(e->d_blopt_ops, ops.data(), sizeof(BloptOp) * ops.size(), hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_blopt_visits, visits.data(), sizeof(BloptVisit) * visits.size(), hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_blopt_mask, &mask[first * N], items * N, hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_blopt_status, status.data(), sizeof(int32_t) * status.size(), hipMemcpyHostToDevice, e->stream));
+		// the start state: the tree batch's lnL-only walk leaves the items' lengths, matrices and every internal lower resident
+		out.resize(items);
+		if (int rc = run_batch_chunk(e, 0, (int)items, lengths, false, 1, true, out.data())) return rc;
+		lnl2.resize(items * 2);
+		for (size_t b = 0; b < items; b++) lnl2[2 * b] = lnl2[2 * b + 1] = out[b];
+		HIP_TRY(hipMemcpyAsync(e->d_blopt_lnl, lnl2.data(), sizeof(double) * lnl2.size(), hipMemcpyHostToDevice, e->stream));
+		BloptStepArgs sa{};
+		sa.ops = e->d_blopt_ops, sa.visits = e->d_blopt_visits, sa.ops_stride = nops, sa.visits_stride = nvisits;
+		sa.T = T, sa.N = e->N, sa.P = e->P, sa.C = C, sa.nblk = nblk;
+		sa.tipmask = e->d_tipmask, sa.freqs = e->d_freqs, sa.props = e->d_props, sa.model = e->d_model, sa.optimise = e->d_blopt_mask, sa.status = e->d_blopt_status;
+		sa.mats = e->d_batch_mats, sa.lower = e->d_batch_lower, sa.O = e->d_blopt_O, sa.K = e->d_blopt_K;
+		BloptSolveArgs so{};
+		so.visits = e->d_blopt_visits, so.visits_stride = nvisits, so.max_passes = o.max_passes;
+		so.N = e->N, so.P = e->P, so.C = C, so.Pp = nblk * WAVE, so.max_iterations = o.max_iterations;
+		so.lower = o.lower, so.upper = o.upper, so.tolerance = o.tolerance, so.lnl_tolerance = o.lnl_tolerance;
+		so.model = e->d_model, so.rates = e->d_rates, so.weights = e->d_weights, so.optimise = e->d_blopt_mask, so.K = e->d_blopt_K;
+		so.lengths = e->d_batch_len, so.mats = e->d_batch_mats, so.lnl = e->d_blopt_lnl, so.status = e->d_blopt_status;
+		const auto all_done = [&] {
+			for (size_t b = 0; b < items; b++)
+				if (!status[b * BLOPT_STATUS + BLOPT_DONE]) return false;
+			return true;
+		};
+		int32_t pass = 0;
+		while (!all_done()) {  // (ends after max_passes: the last pass's stop test ends every item)
+			if (++pass > o.max_passes) return fail(PHYAMD_EDEVICE, "%s: an item of chunk %d is not done after %d passes", name, prof.chunks, o.max_passes);
+			for (int i = 0; i < nvisits; i++) {
+				sa.step = so.step = i;
+				so.pass = pass;
+				hipLaunchKernelGGL(k_blopt_step4, dim3((unsigned)nblk, (unsigned)items), dim3(WAVE, C), 0, e->stream, sa);
+				hipLaunchKernelGGL(k_blopt_solve4, dim3((unsigned)items), dim3(CBOPT_THREADS), 0, e->stream, so);
+			}
+			HIP_TRY(hipGetLastError());
+			HIP_TRY(hipMemcpyAsync(status.data(), e->d_blopt_status, sizeof(int32_t) * status.size(), hipMemcpyDeviceToHost, e->stream));
+			HIP_TRY(hipStreamSynchronize(e->stream));
+		}
+		prof.passes = std::max(prof.passes, pass);
+		len.resize(items * N);
+		HIP_TRY(hipMemcpyAsync(len.data(), e->d_batch_len, sizeof(double) * len.size(), hipMemcpyDeviceToHost, e->stream));
+		HIP_TRY(hipMemcpyAsync(lnl2.data(), e->d_blopt_lnl, sizeof(double) * lnl2.size(), hipMemcpyDeviceToHost, e->stream));
+		HIP_TRY(hipStreamSynchronize(e->stream));
+		prof.chunks++;
+		for (size_t b = 0; b < items; b++) {
+			const size_t at = first + b;
+			for (size_t n = 0; n < N; n++)  // (the root's entry and those of nodes that are not visited stay the caller's)
+				if (mask[at * N + n]) o.lengths[at * N + n] = len[b * N + n];
+			o.lnl[at] = lnl2[2 * b + 1];
+			if (o.initial_lnl) o.initial_lnl[at] = out[b];
+			if (o.passes) o.passes[at] = status[b * BLOPT_STATUS + BLOPT_PASSES];
+			prof.visits += status[b * BLOPT_STATUS + BLOPT_VISITS];
+			prof.iterations += status[b * BLOPT_STATUS + BLOPT_ITERATIONS];
+		}
+		return PHYAMD_OK;
+	};
+	return for_tree_chunks(e, name, 0, o.count, left, right, roots, o.start, item_ops, plan_of, chunk);
+}
+
+int shard_branch_optimize(Shard *e, int flags, const BranchOptimizeArgs &o) {
+	CHECK_ENGINE(e);
+	phyamd_branch_optimize_profile known{};
+	known.items = o.count;
+	return profiled_call(e, &Shard::blopt_prof, known, [&](phyamd_branch_optimize_profile &prof) { return run_branch_optimize(e, flags, o, prof); });
+}
+
 // ---- every SPR regraft of chosen subtrees (phyamd_spr_log_likelihoods) ---------------------------------------------------------
 
 // the engine's tree's park_all op lists, where each internal node's op is in them, and every node's depth-first interval

@@ -51,6 +51,27 @@ int phyamd_post_order_slots(int32_t tip_count, const int32_t *left, const int32_
 	return (int)ops.size();
 }
 
+// one pass of phyamd_optimize_branch_lengths over a tree as k_blopt_step4 and k_blopt_solve4 run it: host code only (no device, no engine)
+int phyamd_branch_sweep_schedule(int32_t tip_count, const int32_t *left, const int32_t *right, int32_t root, int32_t *out, int32_t capacity) {
+	static const char *const name = "phyamd_branch_sweep_schedule";
+	if (tip_count < 2) return fail(PHYAMD_EINVAL, "%s: tip_count must be >= 2 (got %d)", name, tip_count);
+	if (!left || !right) return fail(PHYAMD_EINVAL, "%s: null left or right", name);
+	if (capacity < 0 || (capacity > 0 && !out)) return fail(PHYAMD_EINVAL, "%s: null out with capacity %d", name, capacity);
+	std::vector<int32_t> parents;
+	const std::string err = validate_tree(TreeRef{tip_count, left, right, root}, parents, name, 0);
+	if (!err.empty()) return fail(PHYAMD_EINVAL, "%s", err.c_str());
+	std::vector<SweepOp> ops;
+	build_branch_sweep(tip_count, left, right, root, &ops);
+	const int T = tip_count, N = 2 * T - 1;
+	for (int i = 0; i < (int)ops.size() && i < capacity; i++) {
+		const SweepOp &o = ops[i];
+		const int32_t lower_plane = o.node >= T ? N + (o.node - T) : -1;
+		const int32_t rec[6] = {o.visit, o.kind, o.node, o.a, o.kind == SWEEP_VISIT ? lower_plane : o.b, o.kind == SWEEP_UPPER ? o.node : o.kind == SWEEP_LOWER ? lower_plane : -1};
+		std::memcpy(out + (size_t)i * 6, rec, sizeof(rec));
+	}
+	return (int)ops.size();
+}
+
 // the pre-order walk's op list of a tree as one of its readers runs it: host code only (no device, no engine)
 int phyamd_pre_order_schedule(int32_t tip_count, const int32_t *left, const int32_t *right, int32_t root, int32_t form, int32_t *out, int32_t capacity,
                               int32_t *hbm_slots) {

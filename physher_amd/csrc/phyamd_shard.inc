@@ -218,7 +218,7 @@ struct Shard {
 	DeviceArray<BatchOp> d_batch_item_ops{&batch_mem};  // [item][post-order T - 1 | pre-order T - 1]
 	DeviceArray<int32_t> d_batch_roots{&batch_mem};     // [item]
 	// what the scratch holds: every call describes what it needs as a ScratchPlan (phyamd_queries.inc: batch_plan, reweight_plan,
-	// nni_base_plan with nni_plan and cbopt_plan, spr_plan, bhess_plan, sitelnl_plan) and gets at least that, so a call of one kind
+	// nni_base_plan with nni_plan and cbopt_plan, blopt_plan, spr_plan, bhess_plan, sitelnl_plan) and gets at least that, so a call of one kind
 	// never runs in the scratch of another with too few upper slots or without its lists.  batch_held: the plan the arrays were last
 	// allocated by, for batch_items items (the Hessian's arrays, grown beside it, are judged by their sizes alone)
 	ScratchPlan batch_held;
@@ -240,6 +240,17 @@ struct Shard {
 	DeviceArray<double> d_cbopt_out{&batch_mem};     // [candidate][3][t*, lnL, d1, d2]
 	DeviceArray<int32_t> d_cbopt_iter{&batch_mem};   // [candidate][3]
 	phyamd_nni_optimize_profile cbopt_prof{};
+	// phyamd_optimize_branch_lengths (phyamd_blopt4.inc) starts from the lnL-only walk of a batch of trees in the scratch above (the
+	// items' lengths, matrices and lowers are its state) and adds to the group, per item: a plane O_n per node, the coefficients of
+	// the branch being visited, the tour's ops and visit slots, the mask of visited nodes, lnL before and now, and the status words
+	DeviceArray<double> d_blopt_O{&batch_mem};           // [item][N][C][blocks * 64][4]
+	DeviceArray<double> d_blopt_K{&batch_mem};           // [item][C][4][blocks * 64]
+	DeviceArray<BloptOp> d_blopt_ops{&batch_mem};        // [item][3 (T - 1)]
+	DeviceArray<BloptVisit> d_blopt_visits{&batch_mem};  // [item][2 (T - 1)]
+	DeviceArray<uint8_t> d_blopt_mask{&batch_mem};       // [item][N]
+	DeviceArray<double> d_blopt_lnl{&batch_mem};         // [item][previous pass | now]
+	DeviceArray<int32_t> d_blopt_status{&batch_mem};     // [item][BLOPT_STATUS]
+	phyamd_branch_optimize_profile blopt_prof{};
 	// phyamd_spr_log_likelihoods (phyamd_spr4.inc) walks one item of the scratch above per prune node (a ROW), with its own op
 	// lists (d_batch_item_ops) and every upper parked (slots = T - 1), and adds to the group: per row the candidate edges, each
 	// cell's candidate index, the slab and the result; once the engine's lengths with their halves and the matrices of both.

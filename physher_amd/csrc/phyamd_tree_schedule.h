@@ -1241,4 +1241,41 @@ inline int site_lnl_ops(int T, const int32_t *left, const int32_t *right, int ro
 	return slots;
 }
 
+// ---- the branch-length sweep (phyamd_optimize_branch_lengths, phyamd_blopt4.inc) -------------------------------------------------
+
+// One pass over a tree (already validated) as a depth-first tour, appended to `ops` in launch order.  O_n is what meets the
+// branch of a non-root node n from above -- A_m o msg(sibling), A_m = P_m O_m of the parent m, ones when m is the root -- and has
+// a plane of its own per node; p_n is internal node n's lower partial, in the plane the batched walk stores it in.
+//   SWEEP_UPPER: O_node from the parent a (BATCH_ROOT: the root) and the sibling b;
+//   SWEEP_LOWER: p_node from its children a and b;
+//   SWEEP_VISIT: the branch of `node` is optimised from O_node and p_node.
+// The tour enters an internal node n, forms O_left, tours the left subtree, forms O_right from the left child's new message, tours
+// the right subtree, forms p_n and visits n: the visits are the post-order (left subtree, right subtree, node) of the nodes other
+// than the root, and nothing outside a subtree changes while the tour is inside it, so O_n is still current when n is visited.
+// visit: the index of the visit the op belongs to -- the next one in the tour (a visit's own).  The root's p is never formed:
+// nothing reads it.  2 (T - 1) uppers, T - 2 lowers and 2 (T - 1) visits
+enum { SWEEP_UPPER = 0, SWEEP_LOWER = 1, SWEEP_VISIT = 2 };
+struct SweepOp {
+	int32_t visit, kind, node, a, b;
+};
+inline void build_branch_sweep(int T, const int32_t *left, const int32_t *right, int root, std::vector<SweepOp> *ops) {
+	std::vector<std::pair<int, int>> stack{{root, 0}};  // (node, children toured)
+	int32_t visit = 0;
+	while (!stack.empty()) {
+		const int n = stack.back().first, stage = stack.back().second;
+		if (n >= T && stage < 2) {
+			const int child = stage == 0 ? left[n] : right[n], sibling = stage == 0 ? right[n] : left[n];
+			ops->push_back(SweepOp{visit, SWEEP_UPPER, child, n == root ? (int32_t)BATCH_ROOT : n, sibling});
+			stack.back().second = stage + 1;
+			stack.push_back({child, 0});
+			continue;
+		}
+		stack.pop_back();
+		if (n == root) continue;
+		if (n >= T) ops->push_back(SweepOp{visit, SWEEP_LOWER, n, left[n], right[n]});
+		ops->push_back(SweepOp{visit, SWEEP_VISIT, n, n, n >= T ? n : (int32_t)BATCH_NONE});
+		visit++;
+	}
+}
+
 #endif

@@ -28,6 +28,7 @@ class Engine:
         self._lib = _lib.load()
         self.T, self.P, self.S, self.C = int(tip_count), int(pattern_count), int(state_count), int(category_count)
         self.N = 2 * self.T - 1
+        self._lengths = self._stored_lengths = None  # what set_branch_lengths / set_branch_length last sent, and store()'s copy
         cfg = _lib.Config(self.T, self.P, self.S, self.C, device, rescale, max_device_bytes, stream)
         h = C.c_void_p()
         self._h = None
@@ -89,10 +90,13 @@ class Engine:
         a = _f64(bl)
         assert a.shape == (self.N,)
         self._check(self._lib.phyamd_set_branch_lengths(self._h, _ptr(a)))
+        self._lengths = a.copy()  # (optimize_branch_lengths' default start)
 
     def set_branch_length(self, node, length):
         """One branch; the next evaluation only recomputes the path from `node` to the root."""
         self._check(self._lib.phyamd_set_branch_length(self._h, int(node), float(length)))
+        if self._lengths is not None:
+            self._lengths[int(node)] = float(length)
 
     def update_all_nodes(self):
         self._check(self._lib.phyamd_update_all_nodes(self._h))
@@ -296,6 +300,50 @@ class Engine:
         self._check(self._lib.phyamd_get_nni_optimize_profile(self._h, C.byref(p)))
         return {k: getattr(p, k) for k, _ in p._fields_}
 
+    def optimize_branch_lengths(self, trees=None, lengths=None, optimise=None, lower=1e-8, upper=10.0, tolerance=1e-8, max_iterations=100,
+                                lnl_tolerance=1e-6, max_passes=50, want_initial=True, want_passes=True, flags=0):
+        """Every branch length of B trees optimised on the device, one branch at a time, pass after pass: (lengths [B, N], lnl [B],
+        initial_lnl [B], passes [B]; the last two None when not wanted).  trees: (left [B, N], right [B, N], roots [B]) as
+        gradient_batch_trees takes them, or None: every item is this engine's tree.  lengths [B, N] by the item's node ids is the
+        start; None with trees None: one item on the lengths last given to set_branch_lengths.  optimise [B, N]: non-zero where
+        the node's branch is visited (None: every node but the root).  A pass visits the nodes in post-order; a visit moves its
+        branch by nni_optimize's safeguarded Newton rule in [lower, upper] and keeps the move when lnL did not fall.  An item stops
+        when a pass gains no more than lnl_tolerance (passes > 0) or after max_passes (passes = -max_passes); a lnL that is not
+        finite ends it in band with passes negative.  The engine's tree, lengths and partials stay.  No fallback: EngineError where
+        gradient_batch_trees refuses, and on a sharded engine."""
+        if lengths is None:
+            if trees is not None or self._lengths is None:
+                raise ValueError("lengths=None needs trees=None and an engine whose set_branch_lengths has been called")
+            lengths = self._lengths[None, :]
+        bl = _f64(lengths)
+        if bl.ndim != 2 or bl.shape[1] != self.N or bl.shape[0] < 1:
+            raise ValueError(f"lengths must be [B >= 1, {self.N}] (got {bl.shape})")
+        count = bl.shape[0]
+        l = r = ro = None
+        if trees is not None:
+            l, r, ro = (np.ascontiguousarray(x, dtype=np.int32) for x in trees)
+            if l.shape != bl.shape or r.shape != bl.shape or ro.shape != (count,):
+                raise ValueError(f"trees: left, right {bl.shape} and roots ({count},), got {l.shape}, {r.shape}, {ro.shape}")
+        m = None
+        if optimise is not None:
+            m = np.ascontiguousarray(np.asarray(optimise) != 0, dtype=np.uint8)
+            if m.shape != bl.shape:
+                raise ValueError(f"optimise must be {bl.shape} (got {m.shape})")
+        out, lnl = np.empty((count, self.N)), np.empty(count)
+        lnl0 = np.empty(count) if want_initial else None
+        passes = np.empty(count, dtype=np.int32) if want_passes else None
+        opt = lambda a: None if a is None else _ptr(a)
+        self._check(self._lib.phyamd_optimize_branch_lengths(self._h, flags, count, opt(l), opt(r), opt(ro), _ptr(bl), opt(m), lower, upper, tolerance,
+                                                             max_iterations, lnl_tolerance, max_passes, _ptr(out), _ptr(lnl), opt(lnl0), opt(passes)))
+        return out, lnl, lnl0, passes
+
+    def branch_optimize_profile(self):
+        """Of the last optimize_branch_lengths: items, chunks (of items), passes (the most a chunk ran), visits and iterations
+        (over all items), scratch_bytes, ms."""
+        p = _lib.BranchOptimizeProfile()
+        self._check(self._lib.phyamd_get_branch_optimize_profile(self._h, C.byref(p)))
+        return {k: getattr(p, k) for k, _ in p._fields_}
+
     def spr_log_likelihoods(self, prune=None, flags=0):
         """Every SPR regraft of the prune nodes' subtrees at once: lnl [count, N].  Row i prunes node prune[i] (None: every node, row
         i is node i); column w regrafts it onto the edge above w: with u the prune node's parent and s its sibling, s takes u's
@@ -444,10 +492,12 @@ class Engine:
     def store(self):
         """Remember the current (evaluated) state: parameters, lnL and partials (MCMC store)."""
         self._check(self._lib.phyamd_store(self._h))
+        self._stored_lengths = None if self._lengths is None else self._lengths.copy()
 
     def restore(self):
         """Back to the stored state without recomputing the tree (MCMC reject)."""
         self._check(self._lib.phyamd_restore(self._h))
+        self._lengths = None if self._stored_lengths is None else self._stored_lengths.copy()
 
     def synchronize(self):
         self._check(self._lib.phyamd_synchronize(self._h))
