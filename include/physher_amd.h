@@ -607,6 +607,24 @@ int phyamd_post_order_slots(int32_t tip_count, const int32_t *left /* [2T-1] */,
  * number of such nodes (at most `capacity` of them are written) or a negative PHYAMD_E* code. */
 int phyamd_stream_elisions(int32_t tip_count, const int32_t *left /* [2T-1] */, const int32_t *right, int32_t root,
                            int32_t *out /* [capacity][8] */, int32_t capacity);
+/* The pair ops of the streamed pre-order walk of a tree (PHYAMD_STREAM_PAIRS, on by default), from the host schedule alone (no
+ * device, no engine): the plain pass runs the op of a DEEP child inside its parent's op where that child is walked first, the op's
+ * other child is stored or a tip, and the parent's table block has room for the child's tips.  One record of
+ * PHYAMD_STREAM_PAIR_COLUMNS ints per op of the streamed list (phyamd_pre_order_schedule, form 1, with PHYAMD_STREAM_ELIDE's kinds):
+ * 0 chunk | 1 node | 2 what the rule decided (0: fused with its DEEP child's op; 1: no DEEP child; 2: no DEEP child whose op is the
+ * next of the chunk and takes its upper in registers; 3: the other child is neither stored nor a tip; 4: a tip beside a DEEP child
+ * of five or six tips; 5: the op runs inside the pair in front; -1: pairs = 0) | 3 the DEEP child looked at | 4 the other child |
+ * 5 its kind in the descriptor (0 tip, 1 stored, 2 DEEP, 3 cherry, 4 cherry + tip, 5 / 6 stored and formed beside a tip / cherry) |
+ * 6 the DEEP child's tips | 7 fused: 1 = the op behind the pair is the other child's and takes its upper in registers | 8 where the
+ * op's own upper comes from in the pair set (0 root, 1 registers, 2 / 3 LDS slot, 4 HBM) | 9 where its right child's upper goes
+ * (0 nowhere or registers, 2 / 3 LDS slot, 4 HBM) | 10 the HBM slot it requests for the next op (-1: none) | 11 the op that runs
+ * next (-1: the chunk ends) | 12 whether it requests both pieces of that op's table block | 13 a digest of the op's rows in the
+ * tables every other pass reads (the same with pairs = 0 and 1) | 14 a digest of its descriptor in the pair set | 16-31 fused: the
+ * node of each of the sixteen result lanes' branch terms (-1: none) | 32-47 and its slab position.  Returns the number of ops (at
+ * most `capacity` of them are written) or a negative PHYAMD_E* code. */
+#define PHYAMD_STREAM_PAIR_COLUMNS 48
+int phyamd_stream_pairs(int32_t tip_count, const int32_t *left /* [2T-1] */, const int32_t *right, int32_t root, int32_t pairs,
+                        int32_t *out /* [capacity][PHYAMD_STREAM_PAIR_COLUMNS] */, int32_t capacity);
 int phyamd_is_rescaling(phyamd_engine *e);
 /* SingleTreeLikelihood_use_rescaling (treelikelihood.c:1410-1423) after construction: PHYAMD_RESCALE_ALWAYS / _NEVER switch
  * at once (the next evaluation recomputes every node), PHYAMD_RESCALE_AUTO keeps the current state and re-arms the lazy switch. */

@@ -406,7 +406,7 @@ int launch_lower_stream(Shard *e) {
 		if (e->stream_tab.P != e->P || e->stream_tab.mstride != e->mstride) return fail(PHYAMD_EDEVICE, "streamed walk: descriptors do not match the pattern storage");
 	}
 	hipLaunchKernelGGL(k_op_tables, dim3(nops, e->C), dim3(64), 0, e->stream, nops, e->C, (const int *)e->d_stream_op_tips, (const int *)e->d_stream_op_deep,
-	                   (const int *)e->d_stream_site_tab, e->d_mats, (const double *)nullptr, reinterpret_cast<double *>(e->d_optab.get()));
+	                   (const int *)e->d_stream_site_tab, (const int *)e->d_stream_pair_tab, e->d_mats, (const double *)nullptr, reinterpret_cast<double *>(e->d_optab.get()));
 	// rescaled: powers of two per category (the plain workgroup shape), or the reference's maxima over categories -- workgroup = the
 	// category waves of one block + their exchange buffer
 	const LowerForm form = stream_lower_form(e);
@@ -462,7 +462,7 @@ int launch_upper_stream(Shard *e) {
 	const size_t lds = (size_t)STREAM_LDS_PER_WAVE * waves + (exp2 ? (size_t)waves * STREAM_PARK_SLOTS * WAVE * sizeof(int) : SCALE ? (size_t)4 * e->C * WAVE * sizeof(double) : 0);
 	const dim3 grid_x(SCALE && !exp2 ? (unsigned)nb : (unsigned)((nb + STREAM_WAVES - 1) / STREAM_WAVES) * e->C), block(WAVE, waves);
 	hipLaunchKernelGGL(k_op_tables, dim3(nops, e->C), dim3(64), 0, e->stream, nops, e->C, (const int *)e->d_stream_op_tips, (const int *)e->d_stream_op_deep,
-	                   (const int *)e->d_stream_site_tab, e->d_mats, FOLD ? e->d_Q : e->d_Qpi, reinterpret_cast<double *>(e->d_optab.get()));
+	                   (const int *)e->d_stream_site_tab, (const int *)e->d_stream_pair_tab, e->d_mats, FOLD ? e->d_Q : e->d_Qpi, reinterpret_cast<double *>(e->d_optab.get()));
 	const int subtrees = (int)e->sched.walk_chunk_off.size() - 2;
 	for (int phase = 0; phase < (subtrees > 0 ? 2 : 1); phase++) {
 		const bool amb = e->stream_ambiguous;
@@ -471,9 +471,11 @@ int launch_upper_stream(Shard *e) {
 		             : tf    ? (amb ? k_upper4_stream<FOLD, 0, true, true> : k_upper4_stream<FOLD, 0, false, true>)
 		                     : (amb ? k_upper4_stream<FOLD, 0, true, false> : k_upper4_stream<FOLD, 0, false, false>);
 		// (descriptors that name unstored children belong to the TF forms; any other pass reads the plain ones behind them: upload_schedule)
+		// (... and the one instantiation that knows pair ops, the plain TF one, reads the set that has them: stream_pairs)
 		const bool plain = !tf && !e->stream_tab.plain_desc.empty();
+		const bool pairs = tf && !exp2 && !SCALE && !amb && !e->stream_tab.pair_desc.empty();
 		hipLaunchKernelGGL(kernel, dim3(grid_x.x, phase ? subtrees : 1), block, lds, e->stream,
-		                   (const StreamDesc *)e->d_stream_ops + (plain ? e->stream_tab.desc.size() : 0), (const StreamChunk *)e->d_stream_chunks + (plain ? e->stream_tab.chunks.size() : 0),
+		                   (const StreamDesc *)e->d_stream_ops + (plain ? e->stream_tab.desc.size() : pairs ? 2 * e->stream_tab.desc.size() : 0), (const StreamChunk *)e->d_stream_chunks + (plain ? e->stream_tab.chunks.size() : 0),
 		                   (const int *)e->d_walk_chunk_off, phase, nops, e->P, e->C, nb, (const uint32_t *)e->d_mstream, e->mstride, (const double *)e->d_lower, e->d_upper,
 		                   (const double *)e->d_mats, (const char *)e->d_optab, (const double *)(FOLD ? e->d_Q : e->d_Qpi), (const double *)e->d_freqs, (const double *)e->d_wl,
 		                   e->d_gslab, R, (const double *)e->d_props, (const double *)e->d_weights, e->xcd_map, (const int *)e->d_lexp, e->d_uexp, (const int *)e->d_Eroot);

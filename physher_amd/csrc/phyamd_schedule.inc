@@ -52,9 +52,10 @@ int upload_schedule(Shard *e) {
 		HIP_TRY(hipMemcpyAsync(e->d_walk_lower_chunk_ops, e->sched.walk_lower_chunk_ops.data(), e->sched.walk_lower_chunk_ops.size() * sizeof(NodeOp), hipMemcpyHostToDevice, e->stream));
 		HIP_TRY(hipMemcpyAsync(e->d_walk_lower_chunk_off, e->sched.walk_lower_chunk_off.data(), e->sched.walk_lower_chunk_off.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
 		if (stream_possible(e)) {  // the streamed walks' tables follow the chunked lists (core indices included: store / restore moves them)
-			build_stream_tables(e->sched, StreamGeometry{e->P, e->C, (size_t)e->nblk_walk_upper * e->G * WAVE, e->stream_elide_on}, &e->stream_tab);
-			// (descriptors and chunks twice: those of the TF forms, then the plain ones behind them -- stream_elide, stream_plain_ops)
-			if ((rc = e->d_stream_ops.ensure((size_t)2 * e->N)) || (rc = e->d_stream_chunks.ensure((size_t)2 * e->N + 4)) ||
+			build_stream_tables(e->sched, StreamGeometry{e->P, e->C, (size_t)e->nblk_walk_upper * e->G * WAVE, e->stream_elide_on, e->stream_pairs_on}, &e->stream_tab);
+			// (descriptors and chunks twice: those of the TF forms, then the plain ones behind them -- stream_elide, stream_plain_ops;
+			// the descriptors a third time, with the pair ops, at 2 x their count -- stream_pairs)
+			if ((rc = e->d_stream_ops.ensure((size_t)3 * e->N)) || (rc = e->d_stream_pair_tab.ensure((size_t)e->N * 16)) || (rc = e->d_stream_chunks.ensure((size_t)2 * e->N + 4)) ||
 			    (rc = e->d_stream_row_entries.ensure(std::max((size_t)e->N * 32, e->stream_tab.row_entries.size()))) ||
 			    (rc = e->d_stream_site_tab.ensure((size_t)e->N * 16)) || (rc = e->d_stream_qnode.ensure(e->N)) || (rc = e->d_stream_op_tips.ensure((size_t)e->N * 12)) ||
 			    (rc = e->d_stream_flag.ensure(1)) || (rc = e->d_stream_op_deep.ensure(e->N)))
@@ -68,6 +69,11 @@ int upload_schedule(Shard *e) {
 				                       hipMemcpyHostToDevice, e->stream));
 				HIP_TRY(hipMemcpyAsync(e->d_stream_chunks + e->stream_tab.chunks.size(), e->stream_tab.plain_chunks.data(),
 				                       e->stream_tab.plain_chunks.size() * sizeof(StreamChunk), hipMemcpyHostToDevice, e->stream));
+			}
+			if (!e->stream_tab.pair_desc.empty()) {
+				HIP_TRY(hipMemcpyAsync(e->d_stream_ops + 2 * e->stream_tab.desc.size(), e->stream_tab.pair_desc.data(), e->stream_tab.pair_desc.size() * sizeof(StreamDesc),
+				                       hipMemcpyHostToDevice, e->stream));
+				HIP_TRY(hipMemcpyAsync(e->d_stream_pair_tab, e->stream_tab.pair_tab.data(), e->stream_tab.pair_tab.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
 			}
 			HIP_TRY(hipMemcpyAsync(e->d_stream_row_entries, e->stream_tab.row_entries.data(), e->stream_tab.row_entries.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
 			HIP_TRY(hipMemcpyAsync(e->d_stream_site_tab, e->stream_tab.site_tab.data(), e->stream_tab.site_tab.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));

@@ -193,3 +193,61 @@ int phyamd_stream_elisions(int32_t tip_count, const int32_t *left, const int32_t
 	}
 	return (int)el.size();
 }
+
+// what stream_pairs makes of the streamed pre-order walk of a tree: host code only (no device, no engine)
+int phyamd_stream_pairs(int32_t tip_count, const int32_t *left, const int32_t *right, int32_t root, int32_t pairs, int32_t *out, int32_t capacity) {
+	constexpr int W = PHYAMD_STREAM_PAIR_COLUMNS;
+	if (tip_count < 2) return fail(PHYAMD_EINVAL, "tip_count must be >= 2 (got %d)", tip_count);
+	if (!left || !right) return fail(PHYAMD_EINVAL, "null left or right");
+	if (capacity < 0 || (capacity > 0 && !out)) return fail(PHYAMD_EINVAL, "null out with capacity %d", capacity);
+	Schedule sched;  // 4 states, an engine's defaults; the streamed walks' tables for one pattern of one category, as an engine builds them
+	StreamTables tab;
+	const std::string err = build_schedule(TreeRef{tip_count, left, right, root}, ScheduleOptions{}, &sched);
+	if (!err.empty()) return fail(PHYAMD_EINVAL, "%s", err.c_str());
+	build_stream_tables(sched, StreamGeometry{1, 1, WAVE, true, pairs != 0}, &tab);
+	const int ns = (int)tab.ops.size();
+	auto digest = [](uint32_t h, const void *data, size_t bytes) {  // FNV-1a
+		const unsigned char *b = static_cast<const unsigned char *>(data);
+		for (size_t j = 0; j < bytes; j++) h = (h ^ b[j]) * 16777619u;
+		return h;
+	};
+	int chunk = 0;
+	for (int i = 0; i < ns && i < capacity; i++) {
+		while (i >= sched.walk_chunk_off[chunk + 1]) chunk++;
+		int32_t rec[W];
+		for (int j = 0; j < W; j++) rec[j] = -1;
+		rec[0] = chunk;
+		rec[1] = tab.ops[i].parent;
+		uint32_t h = 2166136261u;
+		h = digest(h, &tab.ops[i], sizeof(StreamOp));
+		h = digest(h, &tab.desc[i], sizeof(StreamDesc));
+		if (!tab.plain_desc.empty()) h = digest(h, &tab.plain_desc[i], sizeof(StreamDesc));
+		h = digest(h, &tab.site_tab[(size_t)i * 16], 16 * sizeof(int));
+		h = digest(h, &tab.op_tips[(size_t)i * 12], 12 * sizeof(int));
+		rec[13] = (int32_t)(h & 0x7FFFFFFFu);
+		if (!tab.pairs.empty()) {
+			const StreamPair &pr = tab.pairs[i];
+			const StreamDesc &d = tab.pair_desc[i];
+			const int fl = d.flags, usrc = (fl >> 9) & 7, pk = (fl >> 12) & 3;
+			rec[2] = pr.reason;
+			rec[3] = pr.child;
+			rec[4] = pr.sibling;
+			rec[5] = pr.sibling_kind;
+			rec[6] = pr.child_tips;
+			rec[7] = pr.carry;
+			rec[8] = usrc == SU_ROOT ? 0 : usrc == SU_CARRY ? 1 : usrc == SU_LDS ? (((fl >> 7) & 1) ? 3 : 2) : 4;
+			rec[9] = pk == 2 ? (((fl >> 6) & 1) ? 3 : 2) : (fl & (1 << 30)) ? 4 : 0;
+			rec[10] = (fl & (1 << 28)) ? (int32_t)(d.nx_u / ((int64_t)4 * 8)) : -1;  // (one pattern, one category: an array is 32 bytes)
+			const int next = i + 1 + (pr.reason == PAIR_FUSED ? 1 : 0);
+			rec[11] = next < sched.walk_chunk_off[chunk + 1] ? next : -1;
+			rec[12] = (fl >> 24) & 1;
+			rec[14] = (int32_t)(digest(2166136261u, &d, sizeof(StreamDesc)) & 0x7FFFFFFFu);
+			for (int j = 0; j < 16; j++) {
+				const int at = tab.pair_tab[(size_t)i * 16 + j];
+				if (at >= 0) rec[16 + j] = tab.qnode[at / 8], rec[32 + j] = at / 8;
+			}
+		}
+		std::memcpy(out + (size_t)i * W, rec, sizeof(rec));
+	}
+	return ns;
+}

@@ -83,7 +83,7 @@ struct Shard {
 	int xcd_map = 1;                    // PHYAMD_XCD_MAP = 0: streamed walks with consecutive workgroup ids per block group (A/B; see xcd_position)
 	DeviceArray<LowerDesc> d_lstream_ops{&mem};
 	DeviceArray<LowerChunk> d_lstream_chunks{&mem};
-	DeviceArray<int> d_stream_op_tips{&mem}, d_stream_flag{&mem}, d_stream_op_deep{&mem};
+	DeviceArray<int> d_stream_op_tips{&mem}, d_stream_flag{&mem}, d_stream_op_deep{&mem}, d_stream_pair_tab{&mem};
 	DeviceArray<char> d_optab{&mem};     // [C][ops] table blocks of OPBLK_BYTES, rebuilt from the matrices every evaluation
 	bool stream_ambiguous = false;       // the tip data hold partial ambiguity codes: the AMBIG instantiation of the streamed walk
 	bool stream_unsupported = false;     // the tip data the mask words were built for hold an empty state mask: the table-gather walks
@@ -125,6 +125,7 @@ struct Shard {
 	bool reference_form_only = false;
 	bool exp2_on = true, tform_on = true;  // PHYAMD_SCALE_EXP2 = 0 / PHYAMD_STREAM_TFORM = 0: the streamed walks never write CarriedExp2 / Carried
 	bool lower_park2_on = true;            // PHYAMD_LOWER_PARK2 = 0: the post-order schedule parks in one slot only (ScheduleOptions)
+	bool stream_pairs_on = true;           // PHYAMD_STREAM_PAIRS = 0: the plain pre-order pass runs every DEEP child's op on its own (stream_pairs, phyamd_tree_schedule.h)
 	bool stream_elide_on = true;           // PHYAMD_STREAM_ELIDE = 0: the streamed walks store every stored node (stream_elide, phyamd_tree_schedule.h)
 	DeviceArray<int> d_lexp{&tile_mem}, d_uexp{&tile_mem}, d_Ec{&tile_mem}, d_Eroot{&tile_mem};  // exponents: [stored][C][P], [upper slots][C][P], [C][P], [P]
 	bool keep_partials = false;

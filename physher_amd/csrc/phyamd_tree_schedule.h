@@ -634,6 +634,7 @@ struct StreamGeometry {
 	int P, C;
 	size_t mstride;
 	bool elide = false;  // stream_elide: the post-order walk stops storing the nodes the pre-order walk can form beside a tip or a cherry
+	bool pairs = false;  // stream_pairs: a third descriptor set in which a DEEP child's pre-order op runs inside its parent's
 };
 
 // a stored node the streamed walks no longer store (stream_elide)
@@ -642,6 +643,18 @@ struct StreamElision {
 	int32_t source;                                       // how the post-order walk hands it to its parent: 1 the op in front, 2 park slot 0
 	int32_t side;                                         // the side it has in its parent's pre-order op (0 left, 1 right)
 	int32_t chunk;                                        // the post-order chunk of both ops
+};
+
+// what stream_pairs decided for one pre-order op
+enum { PAIR_FUSED = 0, PAIR_NO_DEEP = 1, PAIR_NOT_NEXT = 2, PAIR_SIBLING = 3, PAIR_BLOCK = 4, PAIR_ABSORBED = 5 };
+struct StreamPair {
+	int32_t node;          // the op's node
+	int32_t reason;        // PAIR_FUSED, or why not: no DEEP child; no DEEP child's op directly behind in the chunk; the other child
+	                       // neither stored nor a tip; a tip beside a DEEP child of five or six tips; the op runs inside the pair in front
+	int32_t child;         // the DEEP child the rule looked at (-1: none)
+	int32_t sibling, sibling_kind;  // the other child and its kind in the descriptor (CH_*, SK_*)
+	int32_t child_tips;    // tips of `child`
+	int32_t carry;         // fused: 1 = the op behind the pair is the sibling's and takes its upper in registers
 };
 
 // the streamed 4-state walks' host tables (phyamd_walk4s.inc), built from the chunked lists of a Schedule for one geometry
@@ -663,6 +676,11 @@ struct StreamTables {
 	std::vector<StreamDesc> plain_desc;
 	std::vector<StreamChunk> plain_chunks;
 	std::vector<StreamElision> elisions;
+	// stream_pairs (StreamGeometry::pairs; otherwise empty): a copy of `desc` with the pair ops, for the plain TF pass; the pair
+	// blocks' position tables [ops][16] (OPBLK_PAIR_SITES); the decision per op
+	std::vector<StreamDesc> pair_desc;
+	std::vector<int> pair_tab;
+	std::vector<StreamPair> pairs;
 	int words = 0, R = 0;           // mask rows of both walks; slab positions
 };
 
@@ -1105,6 +1123,111 @@ inline void stream_elide(const Schedule &sc, const StreamGeometry &g, StreamTabl
 	t.words = (int)t.row_entries.size() / 8;
 }
 
+// Pair ops: a third set of pre-order descriptors, read by the plain TF pass alone (k_upper4_stream<.., 0, false, true>).  A DEEP
+// node d has no stored partial: its parent's op n rebuilds its message from its two half messages, and d's own op, when it is the
+// next one, forms the same two halves again as its children's messages and pays an op's fixed cost.  In this set n runs d's op
+// inside its own (descriptor bit 8) and the walk steps over d's descriptor, which stays where it is, unread.  n and d are fused when
+//   * d is n's LEFT child (the one walked first: its upper arrives in registers) and d's op is the next of the same chunk;
+//   * n's other child s is CH_CORE or CH_TIP in the descriptor -- not a fringe child, a second DEEP child or an elided kind;
+//   * s is stored, or d has four tips: the block's other side holds s's tip rows (320 bytes) and the Qs P rows of d's tips (160 each).
+// n's descriptor already names d's matrices, half kinds and mask group.  What changes:
+//   * n requests what the op behind d wants (d's request fields), and the op in front of n both pieces of n's block;
+//   * the block of n gains the Qs P rows and a position table of the pair's twelve terms (pair_tab; op_deep bit 2; phyamd_types.h),
+//     in places no other reader of the block looks at -- the table blocks are shared with the other descriptor sets;
+//   * s stored and its op directly behind d's: that op takes s's upper as the carry (it IS the left child's upper of the op in
+//     front, as the kernel keeps it), and n neither parks nor stores it.
+// `desc`, `ops`, the chunks, the site table and the slab positions stay as they are.  After stream_elide.
+inline void stream_pairs(const Schedule &sc, const StreamGeometry &g, StreamTables &t) {
+	const int ns = (int)t.ops.size();
+	t.pair_desc = t.desc;
+	t.pair_tab.assign((size_t)ns * 16, -1);
+	t.pairs.assign(ns, StreamPair{-1, PAIR_NO_DEEP, -1, -1, -1, 0, 0});
+	if (ns == 0) return;
+	std::vector<int> chunk_of(ns, 0);
+	for (int k = 0; k + 1 < (int)sc.walk_chunk_off.size(); k++)
+		for (int i = sc.walk_chunk_off[k]; i < sc.walk_chunk_off[k + 1]; i++) chunk_of[i] = k;
+	auto tips_of = [&](int i, int side) {
+		int n = 0;
+		for (int j = 0; j < 6; j++) n += t.op_tips[(size_t)i * 12 + 6 * side + j] >= 0;
+		return n;
+	};
+	for (int i = 0; i < ns; i++) {
+		StreamPair &pr = t.pairs[i];
+		const StreamOp &s = t.ops[i];
+		const int fl = t.desc[i].flags, kl = fl & 7, kr = (fl >> 3) & 7;
+		pr.node = s.parent;
+		if (i > 0 && t.pairs[i - 1].reason == PAIR_FUSED) {
+			pr.reason = PAIR_ABSORBED;
+			continue;
+		}
+		if (kl != CH_DEEP && kr != CH_DEEP) continue;
+		const bool next_here = i + 1 < ns && chunk_of[i + 1] == chunk_of[i];
+		const int side = kl == CH_DEEP && (kr != CH_DEEP || !next_here || t.ops[i + 1].parent != s.rnode) ? 0 : 1;
+		pr.child = side ? s.rnode : s.lnode;
+		pr.sibling = side ? s.lnode : s.rnode;
+		pr.sibling_kind = side ? kl : kr;
+		pr.child_tips = tips_of(i, side);
+		if (side != 0 || !next_here || t.ops[i + 1].parent != pr.child || ((t.desc[i + 1].flags >> 9) & 7) != SU_CARRY) pr.reason = PAIR_NOT_NEXT;
+		else if (pr.sibling_kind != CH_CORE && pr.sibling_kind != CH_TIP) pr.reason = PAIR_SIBLING;
+		else if (pr.sibling_kind == CH_TIP && pr.child_tips > 4) pr.reason = PAIR_BLOCK;
+		else pr.reason = PAIR_FUSED;
+	}
+	const int next_mask = 3 << 14 | 1 << 24 | 1 << 25 | 1 << 26 | 1 << 27 | 1 << 28;
+	for (int i = 0; i < ns; i++) {
+		if (t.pairs[i].reason != PAIR_FUSED) continue;
+		StreamPair &pr = t.pairs[i];
+		StreamDesc &pd = t.pair_desc[i];
+		const StreamDesc &dd = t.desc[i + 1];
+		const StreamOp &s = t.ops[i];
+		pd.flags = (pd.flags & ~next_mask) | (dd.flags & next_mask) | 1 << 8;
+		pd.nx_words = dd.nx_words;
+		pd.nx_a = dd.nx_a;
+		pd.nx_b = dd.nx_b;
+		pd.nx_u = dd.nx_u;
+		t.op_deep[i] |= 4;
+		// the twelve terms by result lane: this op's two where they were, d's by the places of its own op's rows
+		std::vector<int> pos_of((size_t)sc.parent.size(), -1);
+		for (int j = 0; j < 10; j++) {
+			const int at = t.site_tab[(size_t)(i + 1) * 16 + j];
+			if (at >= 0) pos_of[t.qnode[at / 8]] = at;
+		}
+		int *tab = &t.pair_tab[(size_t)i * 16];
+		tab[0] = t.site_tab[(size_t)i * 16];
+		tab[4] = t.site_tab[(size_t)i * 16 + 4];
+		for (int h = 0; h < 2; h++) {
+			const int32_t *q = s.la + 5 * h;  // {node, t0, t1, t2, inner}
+			const int hk = (pd.flags >> (16 + 2 * h)) & 3;
+			tab[10 + h] = pos_of[q[0]];
+			if (hk == HK_TIP) continue;
+			tab[4 * h + 1] = pos_of[q[1]];
+			tab[4 * h + 2] = pos_of[q[2]];
+			if (hk == HK_CHERRY_TIP) {
+				tab[4 * h + 3] = pos_of[q[4]];
+				tab[8 + h] = pos_of[q[3]];
+			}
+		}
+		// s's upper in registers to s's own op
+		const int j = i + 2;
+		if (pr.sibling_kind == CH_CORE && j < ns && chunk_of[j] == chunk_of[i] && t.ops[j].parent == pr.sibling) {
+			StreamDesc &sd = t.pair_desc[j];
+			const int usrc = (sd.flags >> 9) & 7;
+			if (usrc == SU_LDS || usrc == SU_U) {
+				pr.carry = 1;
+				sd.flags = (sd.flags & ~(7 << 9 | 1 << 7)) | SU_CARRY << 9;
+				pd.flags &= ~(3 << 12 | 1 << 6 | 1 << 28 | 1 << 30);
+				pd.nx_u = 0;
+				pd.st_right = 0;
+			}
+		}
+	}
+	// the op in front of a pair requests both pieces of its block (a chunk's first block is requested whole)
+	for (int i = 0, front = -1; i < ns; i++) {
+		if (t.pairs[i].reason == PAIR_ABSORBED) continue;
+		if (t.pairs[i].reason == PAIR_FUSED && front >= 0 && chunk_of[front] == chunk_of[i]) t.pair_desc[front].flags |= 1 << 24;
+		front = i;
+	}
+}
+
 // both walks' tables (the post-order walk's mask rows follow the pre-order walk's; g.elide: stream_elide's rewrite of both)
 inline void build_stream_tables(const Schedule &sc, const StreamGeometry &g, StreamTables *out) {
 	stream_pre_order(sc, g, *out);
@@ -1112,7 +1235,11 @@ inline void build_stream_tables(const Schedule &sc, const StreamGeometry &g, Str
 	out->plain_desc.clear();
 	out->plain_chunks.clear();
 	out->elisions.clear();
+	out->pair_desc.clear();
+	out->pair_tab.clear();
+	out->pairs.clear();
 	if (g.elide) stream_elide(sc, g, *out);
+	if (g.pairs) stream_pairs(sc, g, *out);
 }
 
 // ---- the batched walks' op lists ----------------------------------------------------------------------------------------------

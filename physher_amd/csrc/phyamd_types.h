@@ -71,6 +71,7 @@ struct StreamOp {
 	                      // park 12-13 (1: left child's upper -> LDS, 2: right) | mask groups of the
 	                      // NEXT op 14-15 | half kinds: left h0 16-17, h1 18-19, right h0 20-21, h1 22-23 | 24: the next op's block is two pieces |
 	                      // 25: the next op's second group sits in its first group's row
+	                      // 8 (descriptors only, stream_pairs): a pair op -- the left child is DEEP and its own op, the next in the list, runs inside this one
 	int32_t parent;       // node whose matrix multiplies the incoming upper (this and every other matrix: byte offset node * C * 128, see SX::M)
 	int32_t slot_parent, slot_left, slot_right;  // HBM upper slots (-1: none)
 	int32_t nx_mask_word;  // row of the next op's first mask group (-1: none)
@@ -107,7 +108,13 @@ struct StreamChunk {  // what the first op of a chunk wants fetched before the l
 //                 a DEEP child: six slots of 160 bytes = 5 rows x 4 doubles, P_tip . e_s for s = 0..3, then P_tip . 1;
 //                 any other child (its tips' branch terms are formed in this op): three slots of 320 bytes = those 5 rows, then the
 //                 5 rows of Qs P_tip . e_s / Qs P_tip . 1, Qs = the matrix of the branch terms (diag(pi) Q, or Q under FOLD)
-constexpr int OPBLK_BYTES = 2048, OPBLK_LEFT = 64, OPBLK_RIGHT = 1024, OPTIP_BYTES = 160;
+// A pair op's block (stream_pairs, phyamd_tree_schedule.h: the DEEP left child's own op runs inside its parent's) is the block above
+// with more in it, so that every kernel that does not know pairs reads it as before:
+//   [1024, 1984)  the sibling stored: six slots of 160 bytes, the rows Qs P_tip . e_s / Qs P_tip . 1 of the DEEP child's tip slots;
+//                 the sibling a tip: its 320 bytes as above, then those rows of the DEEP child's four tips, packed in slot order
+//   [1984, 2048)  16 ints: the slab positions of the pair's twelve terms by result lane (the parent's two at 0 and 4, the child's
+//                 descents at 1-3, 5-7, 8, 9 as in its own op, the child's two children at 10 and 11)
+constexpr int OPBLK_BYTES = 2048, OPBLK_LEFT = 64, OPBLK_RIGHT = 1024, OPTIP_BYTES = 160, OPBLK_PAIR_SITES = 1984;
 
 // LDS park slots per wave of the streamed pre-order walk (their use and their cost: phyamd_walk4s.inc, "dynamic LDS per wave")
 constexpr int STREAM_PARK_SLOTS = 2;

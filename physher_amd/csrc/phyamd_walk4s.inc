@@ -70,21 +70,37 @@ __global__ __launch_bounds__(256) void k_build_mask_stream(int rows, int P, size
 }
 
 // the table blocks of one evaluation: grid (ops, C), 64 threads; op_tips: [ops][12] (left child's tips 0..5, right 6..11),
-// op_deep: bit 0 / 1 = the left / right child is a DEEP node, site_tab: [ops][16], Qs: 4 x 4 row-major
+// op_deep: bit 0 / 1 = the left / right child is a DEEP node, bit 2 = a pair op's block (OPBLK_PAIR_SITES, phyamd_types.h; pair_tab:
+// [ops][16], its position table), site_tab: [ops][16], Qs: 4 x 4 row-major
 __global__ __launch_bounds__(64) void k_op_tables(int nops, int C, const int *__restrict__ op_tips, const int *__restrict__ op_deep, const int *__restrict__ site_tab,
-                                                  const double *__restrict__ mats, const double *__restrict__ Qs, double *__restrict__ optab) {
+                                                  const int *__restrict__ pair_tab, const double *__restrict__ mats, const double *__restrict__ Qs, double *__restrict__ optab) {
 	const int op = blockIdx.x, c = blockIdx.y, t = threadIdx.x;
 	double *blk = optab + ((size_t)c * nops + op) * (OPBLK_BYTES / 8);
 	if (t < 16) reinterpret_cast<int *>(blk)[t] = site_tab[op * 16 + t];
 	const int deep = op_deep[op];
+	const bool pair = (deep >> 2) & 1;
+	if (t >= 16 && t < 32) reinterpret_cast<int *>(blk)[OPBLK_PAIR_SITES / 4 + t - 16] = pair ? pair_tab[op * 16 + t - 16] : -1;
+	const bool sib_tip = pair && op_tips[op * 12 + 6] >= 0;
 	for (int e = t; e < 2 * 120; e += 64) {  // 2 sides x 120 doubles
 		const int side = e / 120, f = e % 120;
 		const bool dp = (deep >> side) & 1;
 		// DEEP: slot = f / 20, rows of P; otherwise slot = f / 40, first 20 doubles rows of P, next 20 rows of Qs P
-		const int slot = dp ? f / 20 : f / 40, g = dp ? f % 20 : f % 40;
-		const bool qrow = !dp && g >= 20;
+		int slot = dp ? f / 20 : f / 40, g = dp ? f % 20 : f % 40;
+		bool qrow = !dp && g >= 20;
+		int tip = op_tips[op * 12 + side * 6 + slot];
+		if (pair && side == 1 && !(sib_tip && f < 40)) {  // rows of Qs P of the left child's tips
+			const int q = (sib_tip ? f - 40 : f) / 20;
+			g = f % 20;
+			qrow = true;
+			tip = -1;
+			if (!sib_tip) tip = op_tips[op * 12 + q];
+			else
+				for (int j = 0, seen = 0; j < 6; j++) {  // the q-th tip slot in use
+					const int tj = op_tips[op * 12 + j];
+					if (tj >= 0 && seen++ == q) tip = tj;
+				}
+		}
 		const int row = (g % 20) / 4, i = g % 4;
-		const int tip = op_tips[op * 12 + side * 6 + slot];
 		double v = 0.0;
 		if (tip >= 0) {
 			const double *M = mats + ((size_t)tip * C + c) * 16;
@@ -156,6 +172,12 @@ struct SX {
 	template <int SIDE, int SLOT>
 	__device__ __forceinline__ d4 site_tip_q(unsigned w) const {
 		return tip_rows<SLOT>((SIDE ? OPBLK_RIGHT : OPBLK_LEFT) + SLOT * 2 * OPTIP_BYTES + OPTIP_BYTES, w);
+	}
+	// pair op (stream_pairs): Qs P e_s of the DEEP left child's tip in slot SLOT (0..5), from the block's other side.  qb = the LDS
+	// address of that half's rows (wave-uniform, not 256-aligned: the row is added, not OR-ed -- v_bfe, v_lshl_add)
+	template <int SLOT>
+	static __device__ __forceinline__ d4 pair_tip_q(unsigned qb, unsigned w) {
+		return lds_read4((lds_cptr)(uintptr_t)(qb + (((w >> (4 * SLOT + 1)) & 7u) << 5)) + SLOT * OPTIP_BYTES);
 	}
 };
 
@@ -235,6 +257,24 @@ __device__ __forceinline__ void s_descend(const SX &x, SS &ss, int kind, int nod
 	}
 	ss.template add_tip<SIDE, 1>(mul4(a2, x.site_tip<SIDE, 1>(w)), x.site_tip_q<SIDE, 0>(w));
 	ss.template add_tip<SIDE, 2>(mul4(a2, x.site_tip<SIDE, 0>(w)), x.site_tip_q<SIDE, 1>(w));
+}
+
+// pair op (stream_pairs): the descent into half H (a cherry or a cherry + tip in slots 3 H ..) of the DEEP child whose own op runs
+// inside its parent's.  s_descend with the child's tips where the parent's block has them: message rows in the left side's DEEP
+// slots, Qs P rows behind `qb` on the other side; the inner cherry's message is formed again (the same instructions on the same
+// rows as in s_half).  Accumulator H rows 1..3 and accumulator 2 row H, as in the child's own op.
+template <int H, typename SS>
+__device__ __forceinline__ void s_descend_pair(const SX &x, SS &ss, int hk, int node, int inner, const d4 &u, unsigned w, unsigned qb) {
+	d4 a2 = matvec4_opt<false>(x.M(node), u);
+	if (hk == HK_CHERRY_TIP) {
+		const d4 bn = matvec4_opt<false>(x.M(inner), mul4(x.deep_tip<0, 3 * H>(w), x.deep_tip<0, 3 * H + 1>(w)));
+		const d4 un = mul4(a2, x.deep_tip<0, 3 * H + 2>(w));
+		ss.template add<H, 3>(un, bn);
+		ss.template add_tip<2, H, false>(mul4(a2, bn), SX::pair_tip_q<3 * H + 2>(qb, w));
+		a2 = matvec4_opt<false>(x.M(inner), un);
+	}
+	ss.template add_tip<H, 1>(mul4(a2, x.deep_tip<0, 3 * H + 1>(w)), SX::pair_tip_q<3 * H>(qb, w));
+	ss.template add_tip<H, 2>(mul4(a2, x.deep_tip<0, 3 * H>(w)), SX::pair_tip_q<3 * H + 1>(qb, w));
 }
 
 __device__ __forceinline__ double dpp_f64(double old, double src, const int ctrl, const int bank) {
@@ -391,6 +431,7 @@ __global__ __launch_bounds__(STREAM_WAVES *WAVE, (SCALE || AMBIG) ? STREAM_MIN_W
     int *__restrict__ uexp, const int *__restrict__ Eroot) {
 	extern __shared__ double sh[];
 	constexpr bool KEEP_BN = !SCALE && !AMBIG;  // (s_fringe_message)
+	constexpr bool PAIRS = TF && !SCALE && !AMBIG;  // the one instantiation that reads descriptors with pair ops (stream_pairs)
 	constexpr bool XCH = SCALE == 1, EXP2 = SCALE == 2;
 	const int lane = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(threadIdx.y);
 	const unsigned vx = XCH ? blockIdx.x : xcd_position(blockIdx.x, gridDim.x, xcd_map);
@@ -405,7 +446,6 @@ __global__ __launch_bounds__(STREAM_WAVES *WAVE, (SCALE || AMBIG) ? STREAM_MIN_W
 	const lds_cptr wave_lds = (lds_cptr)sh + (size_t)wv * STREAM_LDS_PER_WAVE;
 	const lds_cptr blocks = wave_lds + STREAM_PARK_SLOTS * STREAM_PARK_BYTES;
 	SX x{reinterpret_cast<const char *>(mats + (size_t)c * 16), blocks};
-	const double wl = SCALE ? 1.0 : (valid ? w_over_L[k] : 0.0);  // w_k / L_k: folded into the root's message, so every upper below carries it
 	const double wk = XCH ? (valid ? weights[k] : 0.0) : EXP2 ? (valid ? w_over_L[k] : 0.0) : 0.0;  // (SCALE == 2: w_k / L_k in units of 2^Eroot[k])
 	const double pc = XCH ? props[c] : 0.0;
 	const int eroot = EXP2 ? Eroot[k] : 0;
@@ -429,6 +469,9 @@ __global__ __launch_bounds__(STREAM_WAVES *WAVE, (SCALE || AMBIG) ? STREAM_MIN_W
 	const unsigned cid4 = (unsigned)(n16 == 0 ? r4 : n16 == 8 ? 4 + r4 : n16 == 4 ? 8 + r4 : 15) * 4u;
 	char *const slab = reinterpret_cast<char *>(gslab + ((size_t)blk * C + c) * R);
 	__attribute__((address_space(3))) dv2 *park = (__attribute__((address_space(3))) dv2 *)wave_lds + lane;
+	// w_k / L_k is folded into the root's message, so every upper below carries it.  One use per walk, by its first op: it waits in
+	// the wave's first park slot, which nothing is parked in before that op, instead of two registers held through the whole walk
+	if (!SCALE) park[0].x = valid ? w_over_L[k] : 0.0;
 	const int chunk = chunk_base + blockIdx.y;
 	const int op_begin = chunk_off[chunk], op_end = chunk_off[chunk + 1];
 	const char *const optab_c = optab + (size_t)c * nops * OPBLK_BYTES + lane * 16;  // this category's blocks, this lane's 16 bytes of a piece
@@ -443,15 +486,21 @@ __global__ __launch_bounds__(STREAM_WAVES *WAVE, (SCALE || AMBIG) ? STREAM_MIN_W
 		return ASM_PREFETCH ? prefetch4(lower_c + off, poff, true) : load4_stream(reinterpret_cast<const double *>(lower_c + off + poff));
 	};
 	auto upper_at = [&](int64_t off) -> d4 { return ASM_PREFETCH ? prefetch4(upper_c + off, poff, false) : load4(reinterpret_cast<const double *>(upper_c + off + poff)); };
-	auto store_upper_at = [&](int64_t off, const d4 &v) { store4(reinterpret_cast<double *>(upper_c + off + poff), v); };
+	// (the lane offset is hidden from the compiler here: it would otherwise add it to upper_c once per walk and hold the 64-bit
+	// address in two registers for the few ops that store; as "uniform base + 32-bit lane offset" the store needs neither)
+	auto store_upper_at = [&](int64_t off, const d4 &v) {
+		unsigned po = poff;
+		asm volatile("" : "+v"(po));
+		store4(reinterpret_cast<double *>(upper_c + off + po), v);
+	};
 	auto word_at = [&](int64_t off) -> unsigned { return ASM_PREFETCH ? prefetch1(mstream_b + off, moff) : *reinterpret_cast<const unsigned *>(mstream_b + off + moff); };
 	// (the prologue takes indices: once per chunk)
 	auto fetch_lower = [&](int core) -> d4 { return load4_stream(reinterpret_cast<const double *>(reinterpret_cast<const char *>(lower + ((size_t)core * C + c) * plane) + poff)); };
 	auto fetch_upper = [&](int slot) -> d4 { return load4(reinterpret_cast<const double *>(reinterpret_cast<const char *>(upper + ((size_t)slot * C + c) * plane) + poff)); };
 	auto fetch_word = [&](int w) -> unsigned { return *reinterpret_cast<const unsigned *>(reinterpret_cast<const char *>(mstream + (size_t)w * mstride) + moff); };
-	auto fetch_block = [&](int op_index, bool two) {  // table block of an op -> the LDS buffer of its parity
+	auto fetch_block = [&](int op_index, int buffer, bool two) {  // table block of an op -> one of the two LDS buffers
 		const char *src = optab_c + (size_t)op_index * OPBLK_BYTES;
-		const lds_cptr dst = blocks + (op_index & 1) * OPBLK_BYTES;
+		const lds_cptr dst = blocks + buffer * OPBLK_BYTES;
 		dma_piece(src, dst);
 		if (two) dma_piece(src + 1024, dst + 1024);
 	};
@@ -462,7 +511,7 @@ __global__ __launch_bounds__(STREAM_WAVES *WAVE, (SCALE || AMBIG) ? STREAM_MIN_W
 	int eA = 0, eB = 0, eU = 0;  // SCALE == 2: the exponents that come with A / B / U
 	if (op_begin < op_end) {
 		const StreamChunk ch = chunks[chunk];
-		fetch_block(op_begin, true);
+		fetch_block(op_begin, 0, true);
 		if (ch.mask_words > 0) w0 = fetch_word(ch.mask_word);
 		if (ch.mask_words > 1) w1 = fetch_word(ch.mask_word + (ch.same_row ? 0 : 1));
 		if (ch.a != -1) A = fetch_lower(ch.a);
@@ -478,8 +527,9 @@ __global__ __launch_bounds__(STREAM_WAVES *WAVE, (SCALE || AMBIG) ? STREAM_MIN_W
 	int e_ul = 0;  // SCALE == 2: ... and its exponent
 	double prev_tot = 0.0;
 	int prev_off = -1;
+	int buf = 0;  // the LDS buffer that holds this op's table block (they alternate; op indices do not: a pair op steps over its child's)
 #pragma unroll 1
-	for (int i = op_begin; i < op_end; i++) {
+	for (int i = op_begin; i < op_end; i++, buf ^= 1) {
 		StreamDesc op;  // wave-uniform: scalar loads through the constant address space
 		{
 			typedef const __attribute__((address_space(4))) int32_t *ciptr;
@@ -496,8 +546,11 @@ __global__ __launch_bounds__(STREAM_WAVES *WAVE, (SCALE || AMBIG) ? STREAM_MIN_W
 		const int fl = op.flags;
 		const int kl = fl & 7, kr = (fl >> 3) & 7;
 		const int usrc = (fl >> 9) & 7, pk = (fl >> 12) & 3, nxw = (fl >> 14) & 3;
-		x.tb = blocks + (i & 1) * OPBLK_BYTES;
-		const int soff = *(const __attribute__((address_space(3))) int *)(x.tb + cid4);  // this lane's slab position (-1: none)
+		x.tb = blocks + buf * OPBLK_BYTES;
+		// pair op (stream_pairs, phyamd_tree_schedule.h): the DEEP left child's own op runs inside this one, and the next op is the one
+		// behind the child's; its twelve slab positions have a table of their own at the block's end
+		const bool pair = PAIRS && (fl & (1 << 8));
+		const int soff = *(const __attribute__((address_space(3))) int *)(x.tb + (pair ? OPBLK_PAIR_SITES : 0) + cid4);  // this lane's slab position (-1: none)
 		// a child with tips has a mask group of its own, the left one's first (w0 / w1 hold the groups' rows: the same row twice when they share it)
 		const unsigned g0 = w0 >> (op.wsh & 31), g1 = w1 >> ((op.wsh >> 5) & 31);
 		const unsigned wL = g0, wR = (kl != CH_CORE) ? g1 : g0;
@@ -520,7 +573,10 @@ __global__ __launch_bounds__(STREAM_WAVES *WAVE, (SCALE || AMBIG) ? STREAM_MIN_W
 			a = matvec4_opt<false>(x.M(op.parent), U);
 			if (!SCALE && !valid) a = d4{0., 0., 0., 0.};
 		}
-		else a = FOLD ? d4{wl * freqs[0], wl * freqs[1], wl * freqs[2], wl * freqs[3]} : d4{wl, wl, wl, wl};  // the root
+		else {  // the root
+			const double wl = SCALE ? 1.0 : (double)park[0].x;
+			a = FOLD ? d4{wl * freqs[0], wl * freqs[1], wl * freqs[2], wl * freqs[3]} : d4{wl, wl, wl, wl};
+		}
 		// the children's messages
 		d4 bl, br, bnl, bnr;  // bn*: the inner cherry's message of a cherry + tip child
 		// (written and read on the cherry + tip paths only.  Left uninitialised -- or made variables of the whole walk -- the compiler
@@ -531,7 +587,13 @@ __global__ __launch_bounds__(STREAM_WAVES *WAVE, (SCALE || AMBIG) ? STREAM_MIN_W
 			any_value(bnl);
 			any_value(bnr);
 		}
-		if (kl == CH_CORE) bl = TF ? own_registers(A) : matvec4_opt<false>(x.M(op.lnode), A);
+		if (PAIRS && pair) {
+			// the left child d is DEEP and its own op, the next of the walk, runs inside this one: its two half messages stay live
+			// (in the registers a cherry + tip child's inner message has in other ops); the other child s is stored or a tip
+			bnl = s_half<0, 0>(x, (fl >> 16) & 3, op.lm[0], op.lm[1], wL);
+			bnr = s_half<0, 3>(x, (fl >> 18) & 3, op.lm[2], op.lm[3], wL);
+			bl = matvec4_opt<false>(x.M(op.lnode), mul4(bnl, bnr));
+		} else if (kl == CH_CORE) bl = TF ? own_registers(A) : matvec4_opt<false>(x.M(op.lnode), A);
 		else if (kl == CH_TIP) bl = x.site_tip<0, 0>(wL);
 		else if (kl == CH_DEEP)
 			bl = matvec4_opt<false>(x.M(op.lnode), mul4(s_half<0, 0>(x, (fl >> 16) & 3, op.lm[0], op.lm[1], wL), s_half<0, 3>(x, (fl >> 18) & 3, op.lm[2], op.lm[3], wL)));
@@ -547,9 +609,10 @@ __global__ __launch_bounds__(STREAM_WAVES *WAVE, (SCALE || AMBIG) ? STREAM_MIN_W
 		const int e_bl = EXP2 && (kl == CH_CORE || kl >= SK_CORE_TIP) ? eA : 0, e_br = EXP2 && (kr == CH_CORE || kr >= SK_CORE_TIP) ? eB : 0;
 		// the next op's table block, words and stored operands (A, B and U have been consumed; requesting them before the messages of
 		// DEEP and fringe children -- a third of an op's arithmetic earlier -- was measured: the longer lives of A / B / U spill)
-		__builtin_amdgcn_s_setprio(3);
 		unsigned nw0 = 0, nw1 = 0;
-		if (i + 1 < op_end) fetch_block(i + 1, (fl >> 24) & 1);
+		const int nxt = i + 1 + (pair ? 1 : 0);
+		__builtin_amdgcn_s_setprio(3);
+		if (nxt < op_end) fetch_block(nxt, buf ^ 1, (fl >> 24) & 1);
 		if (nxw > 0) nw0 = word_at(op.nx_words);
 		if (nxw > 1) nw1 = word_at(op.nx_words + ((fl >> 25) & 1 ? (int64_t)0 : (int64_t)mrow));  // (the same row again: the dword just requested, an L1 hit)
 		if (fl & (1 << 26)) A = lower_at(op.nx_a);
@@ -614,7 +677,26 @@ __global__ __launch_bounds__(STREAM_WAVES *WAVE, (SCALE || AMBIG) ? STREAM_MIN_W
 		else ss.template add<0, 0, true>(ul_terms, bl);
 		if (kr == CH_TIP) ss.template add_tip<1, 0, true>(ur_terms, x.site_tip_q<1, 0>(wR));
 		else ss.template add<1, 0, true>(ur_terms, br);
-		if (kl == CH_CHERRY_TIP) {
+		if (PAIRS && pair) {
+			// d's op on the live halves: a = P_d u_d, its children's messages are the halves.  Every term keeps an accumulator row of
+			// its own (this op's two: rows 0 of accumulators 0 and 1, above; d's two: rows 2 and 3 of accumulator 2; d's descents:
+			// the rows of its own op).  Its tips' Qs P rows sit on this block's other side, behind s's own rows when s is a tip (d
+			// then has four tips: its second half's rows follow its first half's).
+			const int hk0 = (fl >> 16) & 3, hk1 = (fl >> 18) & 3;
+			const d4 ad = matvec4_opt<false>(x.M(op.lnode), ul);
+			const d4 uhl = mul4(ad, bnr), uhr = mul4(ad, bnl);
+			const unsigned q0 = (unsigned)(uintptr_t)x.tb + OPBLK_RIGHT + (kr == CH_TIP ? 2 * OPTIP_BYTES : 0);
+			const unsigned q1 = (unsigned)(uintptr_t)x.tb + OPBLK_RIGHT + (kr == CH_TIP ? hk0 * OPTIP_BYTES : 0);
+			if (hk0 == HK_TIP) ss.template add_tip<2, 2, true>(uhl, SX::pair_tip_q<0>(q0, wL));
+			else ss.template add<2, 2, true>(uhl, bnl);
+			if (hk1 == HK_TIP) ss.template add_tip<2, 3>(uhr, SX::pair_tip_q<3>(q1, wL));
+			else ss.template add<2, 3>(uhr, bnr);
+			if (hk0 != HK_TIP) s_descend_pair<0>(x, ss, hk0, op.lm[0], op.lm[1], uhl, wL, q0);
+			if (hk1 != HK_TIP) s_descend_pair<1>(x, ss, hk1, op.lm[2], op.lm[3], uhr, wL, q1);
+			prev_tot = fold_sites<true>(ss.acc0, ss.acc1, ss.acc2);
+			ul = ur;  // s's upper: the carry of the op behind d's when that is s's own
+			i++;
+		} else if (kl == CH_CHERRY_TIP) {
 			s_descend<0, true, KEEP_BN>(x, ss, CH_CHERRY_TIP, op.lnode, op.lm[4], ul_terms, wL, bnl);
 			if (kr == CH_CHERRY || kr == CH_CHERRY_TIP) s_descend<1, false, KEEP_BN>(x, ss, kr, op.rnode, op.rm[4], ur_terms, wR, bnr);
 			prev_tot = fold_sites<true>(ss.acc0, ss.acc1, ss.acc2);
