@@ -336,6 +336,15 @@ class TreeLikelihoodInterface : public CallableModelInterface {
 	// prune[i] (null: count = 2T-1 and row i is node i), column w the target edge; NaN where there is no candidate.  Lengths are
 	// the engine's branch lengths, as for NNILogLikelihoods.  The tree model and this object's own state are unchanged.
 	void SPRLogLikelihoods(const int *prune, int count, double *out);
+	// The three branches that meet at the graft point of every SPR regraft optimised at once (one phyamd_spr_optimize call; see
+	// include/physher_amd.h for the rule): SPRLogLikelihoods' rows, columns and candidates; lengths [count][2T-1][3] holds the lengths
+	// of the prune node, of the target node and of the prune node's parent, logLikelihoods [count][2T-1]; initialLogLikelihoods
+	// [count][2T-1] and passes [count][2T-1] (negative: the passes ran out, or lnL was not finite) may be null; NaN and 0 where there is
+	// no candidate.  A visit seeks its branch's optimum in [lower, upper] until a step is no longer than tolerance, in at most
+	// maxIterations steps; an entry stops when a pass gains no more than lnlTolerance, or after maxPasses passes.  Lengths are the
+	// engine's branch lengths, as for NNILogLikelihoods.  The tree model and this object's own state are unchanged.
+	void SPROptimize(const int *prune, int count, double lower, double upper, double tolerance, int maxIterations, double lnlTolerance, int maxPasses, double *lengths,
+	                 double *logLikelihoods, double *initialLogLikelihoods, int32_t *passes);
 	// Beyond the reference surface: marginal ancestral reconstruction of `count` nodes of the tree model's tree at once (one
 	// phyamd_state_posteriors call; see include/physher_amd.h for the definition): posteriors [count][patterns][states] and states
 	// [count][patterns] by the tree's node ids, row i the node nodes[i] (null: count = 2T-1 and row i is node i; tips and the

@@ -358,8 +358,8 @@ int phyamd_get_nni_optimize_profile(phyamd_engine *e, phyamd_nni_optimize_profil
  * the lnl of the phyamd_gradient_batch_trees item with those arrays.  Column w is a CANDIDATE unless w is the root, u, s, p or a
  * descendant of p; every other column is NaN.  A row is all NaN when p is the root or a child of the root (no error, so that
  * prune == NULL works uniformly): a caller re-roots the tree to reach those moves, as for the NNI across the root edge above.
- * Duplicates in prune are allowed.  There are no derivatives and no trial lengths in this call: a caller takes its best few
- * candidates to phyamd_gradient_batch_trees.
+ * Duplicates in prune are allowed.  There are no derivatives and no trial lengths in this call: the lengths are a fixed, arbitrary
+ * assignment.  phyamd_spr_optimize (at the end of this header) optimises the three branches at the graft point of every candidate.
  * The remaining contract is phyamd_nni_log_likelihoods': the engine -- its topology, lengths, partials -- is unchanged and later
  * evaluations return the bits they would have returned without the call; two calls return identical bits, and a row does not
  * depend on what the batch scratch held before, on count, on its position in prune or on the chunks the rows ran in; a
@@ -713,6 +713,56 @@ int phyamd_get_branch_optimize_profile(phyamd_engine *e, phyamd_branch_optimize_
  * 5 T - 6 (at most `capacity` of them are written), or a negative PHYAMD_E* code. */
 int phyamd_branch_sweep_schedule(int32_t tip_count, const int32_t *left /* [2T-1] */, const int32_t *right, int32_t root,
                                  int32_t *out /* [capacity][6] */, int32_t capacity);
+
+/* --- the three graft branches of every SPR regraft --- */
+/* The three branches that meet at the graft point of every SPR regraft optimised in one call: what a likelihood SPR search
+ * compares (the reference's optimize_tripod after every SPR_move, spropt.c:1538-1623).  Rows, columns and the move are
+ * phyamd_spr_log_likelihoods': row i is the prune node p = prune[i] (prune == NULL: count must be 2T-1 and row i is node i), column
+ * w the target edge, u = parent(p) the new central node, and the candidates and their rearranged trees are the same.  Per cell
+ * lengths holds (t_p, t_w, t_u), lnl the log-likelihood there, initial_lnl that of the start and passes the pass count; every
+ * cell that is no candidate is NaN in lengths, lnl and initial_lnl and 0 in passes, and a row whose p is the root or a child of the
+ * root is all NaN.  initial_lnl and passes may be NULL.
+ * THE RULE.  Entry (p, w) is, by definition, what phyamd_optimize_branch_lengths returns for ONE item whose tree is the rearranged
+ * tree of the entry, whose branch_lengths are that tree's -- t'_s = t_s + t_u, t'_u = t'_w = 0.5 t_w, everything else the
+ * engine's -- and whose optimise marks p, w and u only.  Spelled out: the state is (t_p, t_w, t_u), at the start
+ * (t_p, 0.5 t_w, 0.5 t_w) of the engine's lengths.
+ *   A pass visits u's left child, u's right child, then u; in the rearranged tree p keeps its slot and w has the slot s had.
+ *   A visit of branch z: f(t) = (lnL, d1, d2) of the rearranged tree with t_z = t and the other two lengths as they stand now, d1 and
+ * d2 by phyamd_branch_hessian_diagonal's definitions.  t0 = clamp(t_z, lower, upper).  t' comes from phyamd_nni_optimize's rule
+ * started at t0: t = t0, a = lower, b = upper; each iteration evaluates d1(t) and d2(t); if d1 > 0 then a = t, else b = t; it
+ * proposes t' = t - d1 / d2 when d2 < 0 and a < t' < b, otherwise t' = (a + b) / 2; it stops when |t' - t| <= tolerance or after
+ * max_iterations proposals.  The visit accepts t_z = t' when lnL(t') is finite and lnL(t') >= lnL(t0); otherwise t_z = t0.  So lnL
+ * never falls from visit to visit.
+ *   lnl_0 is lnL at the start, which initial_lnl reports: phyamd_spr_log_likelihoods' entry up to rounding.  After pass k, lnl_k is
+ * lnL at the current lengths.  The entry stops after pass k when lnl_k - lnl_(k-1) <= lnl_tolerance, with passes = k; after
+ * max_passes passes without that, with passes = -max_passes.
+ *   A lnL that is not finite at an iterate (one of the t whose d1 and d2 the iteration evaluates, t0 among them) ends the entry in
+ * band: lengths is the state before that visit, lnl the value that is not finite, passes the negated index of the pass (from 1).
+ * The engine is never switched to rescaling, under PHYAMD_RESCALE_NEVER and _AUTO alike.
+ * lnL and the derivatives are formed from the eigen system like phyamd_nni_optimize's (without the reference's fabs on P(t): a
+ * rounding difference; a category of rate zero behaves as it does there).  Everything happens on the device after the SPR call's
+ * one walk per row: the three messages that meet at u -- p's lower, w's lower and w's upper in the pruned tree -- depend on none of
+ * the three lengths, so an entry's whole iteration runs in one workgroup without a further walk, matrix launch or host round trip.
+ * The engine -- its topology, lengths, partials -- is unchanged and later evaluations return the bits they would have returned
+ * without the call; two calls return identical bits; an entry's bits do not depend on count, the row's position in prune, the other
+ * rows or candidates, the chunks the rows ran in, the optional outputs or what the batch scratch held.  The scratch is the batch
+ * scratch's: per row phyamd_spr_log_likelihoods' and per candidate 2 x C x 4 doubles per pattern; rows that do not fit the memory
+ * cap together run in chunks of rows.  There is no fallback path: PHYAMD_EUNSUPPORTED, naming the condition, under
+ * phyamd_gradient_batch_trees' conditions (not 4 states, more than 8 categories, an engine that is rescaling now, tiled patterns, a
+ * tip cell with an empty state mask, explicit node matrices), for flags other than 0, on a handle sharded over several devices
+ * (every iteration would need a sum across the shards), and when the scratch of one row does not fit the memory cap.
+ * PHYAMD_EINVAL: null engine, lengths or lnl; count < 1; prune == NULL with another count than 2T-1; an id outside 0..2T-2 (with its
+ * index in the message); no eigen system; bounds that are not 0 <= lower < upper < inf; a tolerance that is not finite and
+ * positive; max_iterations outside 1..1000; an lnl_tolerance that is negative or not finite; max_passes outside 1..1000. */
+int phyamd_spr_optimize(phyamd_engine *e, int flags, int32_t count, const int32_t *prune /* [count] or NULL */,
+                        double lower, double upper, double tolerance, int32_t max_iterations,
+                        double lnl_tolerance, int32_t max_passes,
+                        double *lengths /* [count][2T-1][3]: t_p, t_w, t_u */, double *lnl /* [count][2T-1] */,
+                        double *initial_lnl /* [count][2T-1] or NULL */, int32_t *passes /* [count][2T-1] or NULL */);
+/* of the last phyamd_spr_optimize: rows asked for, chunks of rows they ran in, candidates optimised, visits made and proposals made
+ * over all of them, bytes of batch scratch the engine holds (see phyamd_batch_profile), wall time of the call */
+typedef struct { int32_t prunes, chunks; int64_t candidates, visits, iterations, scratch_bytes; double ms; } phyamd_spr_optimize_profile;
+int phyamd_get_spr_optimize_profile(phyamd_engine *e, phyamd_spr_optimize_profile *out);
 
 #ifdef __cplusplus
 }

@@ -52,6 +52,11 @@ class SprProfile(C.Structure):
     _fields_ = [("prunes", C.c_int32), ("chunks", C.c_int32), ("candidates", C.c_int64), ("scratch_bytes", C.c_int64), ("ms", C.c_double)]
 
 
+class SprOptimizeProfile(C.Structure):
+    _fields_ = [("prunes", C.c_int32), ("chunks", C.c_int32), ("candidates", C.c_int64), ("visits", C.c_int64), ("iterations", C.c_int64),
+                ("scratch_bytes", C.c_int64), ("ms", C.c_double)]
+
+
 class HessianProfile(C.Structure):
     _fields_ = [("chunks", C.c_int32), ("pairs", C.c_int64), ("scratch_bytes", C.c_int64), ("ms", C.c_double)]
 
@@ -129,6 +134,8 @@ SYMBOLS = [
     ("phyamd_branch_sweep_schedule", C.c_int, [C.c_int32, _P, _P, C.c_int32, _P, C.c_int32]),
     ("phyamd_spr_log_likelihoods", C.c_int, [_P, C.c_int, C.c_int32, _P, _P]),
     ("phyamd_get_spr_profile", C.c_int, [_P, C.POINTER(SprProfile)]),
+    ("phyamd_spr_optimize", C.c_int, [_P, C.c_int, C.c_int32, _P, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32, _P, _P, _P, _P]),
+    ("phyamd_get_spr_optimize_profile", C.c_int, [_P, C.POINTER(SprOptimizeProfile)]),
     ("phyamd_state_posteriors", C.c_int, [_P, C.c_int, C.c_int32, _P, _P, _P]),
     ("phyamd_site_rate_posteriors", C.c_int, [_P, _P, _P]),
     ("phyamd_branch_hessian", C.c_int, [_P, C.c_int, _P, _P, _P]),

@@ -965,6 +965,14 @@ void TreeLikelihoodInterface::SPRLogLikelihoods(const int *prune, int count, dou
 	phyamd::check(phyamd_spr_log_likelihoods(impl_->engine, 0, count, prune, out));
 }
 
+void TreeLikelihoodInterface::SPROptimize(const int *prune, int count, double lower, double upper, double tolerance, int maxIterations, double lnlTolerance, int maxPasses,
+                                          double *lengths, double *logLikelihoods, double *initialLogLikelihoods, int32_t *passes) {
+	if (!lengths || !logLikelihoods) throw Error("null lengths or logLikelihoods");
+	Sync();
+	phyamd::check(phyamd_spr_optimize(impl_->engine, 0, count, prune, lower, upper, tolerance, maxIterations, lnlTolerance, maxPasses, lengths, logLikelihoods,
+	                                  initialLogLikelihoods, passes));
+}
+
 size_t TreeLikelihoodInterface::StateCount() const { return (size_t)impl_->S; }
 size_t TreeLikelihoodInterface::CategoryCount() const { return (size_t)siteModel_->GetModel()->cat_count; }
 

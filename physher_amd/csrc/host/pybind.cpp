@@ -293,6 +293,19 @@ PYBIND11_MODULE(_phycpp_amd, m) {
 		    self.SPRLogLikelihoods(prune ? prune->data() : nullptr, (int)count, lnl.data());
 		    return darray({count, N}, lnl.data());
 	    }, py::arg("prune") = py::none())
+	    .def("spr_optimize", [](TreeLikelihoodInterface &self, std::optional<iarray> prune, double lower, double upper, double tolerance, int max_iterations,
+	                            double lnl_tolerance, int max_passes) -> py::tuple {
+		    const py::ssize_t N = (py::ssize_t)self.NodeCount();
+		    if (prune && prune->ndim() != 1) throw phyamd::Error("prune: [count]");
+		    const py::ssize_t count = prune ? prune->shape(0) : N;
+		    std::vector<double> len((size_t)count * N * 3), lnl((size_t)count * N), lnl0(lnl.size());
+		    std::vector<int32_t> passes(lnl.size());
+		    self.SPROptimize(prune ? prune->data() : nullptr, (int)count, lower, upper, tolerance, max_iterations, lnl_tolerance, max_passes, len.data(), lnl.data(),
+		                     lnl0.data(), passes.data());
+		    const std::vector<py::ssize_t> shape{count, N};
+		    return py::make_tuple(darray({count, N, (py::ssize_t)3}, len.data()), darray(shape, lnl.data()), darray(shape, lnl0.data()), iarray(shape, passes.data()));
+	    }, py::arg("prune") = py::none(), py::arg("lower") = 1e-8, py::arg("upper") = 10.0, py::arg("tolerance") = 1e-8, py::arg("max_iterations") = 100,
+	       py::arg("lnl_tolerance") = 1e-6, py::arg("max_passes") = 50)
 	    .def("state_posteriors", [](TreeLikelihoodInterface &self, std::optional<iarray> nodes, bool want_posteriors, bool want_states) -> py::tuple {
 		    const py::ssize_t N = (py::ssize_t)self.NodeCount(), P = (py::ssize_t)self.GetPatternCount(), S = (py::ssize_t)self.StateCount();
 		    if (nodes && nodes->ndim() != 1) throw phyamd::Error("nodes: [count]");

@@ -996,42 +996,45 @@ void build_spr_row(const Shard *e, int row, int p, std::vector<BatchOp> *ops, st
 		if (w == e->root || w == u || w == s || below_p(w)) continue;
 		const int x = e->sched.parent[w];
 		cand_of[w] = (int32_t)cands->size();
-		cands->push_back(SprCand{row, w, x == e->root ? BATCH_ROOT : x, e->left[x] == w ? e->right[x] : e->left[x], p, {0, 0, 0}});
+		cands->push_back(SprCand{row, w, x == e->root ? BATCH_ROOT : x, e->left[x] == w ? e->right[x] : e->left[x], p, e->left[u] == p ? 1 : 0, {0, 0}});
 	}
 }
 
-// lnl [count][N] (host).  Reads the engine's inputs and writes only the batch scratch: nothing in Shard::state changes but the
-// record that the host lists are the tree's
-int run_spr(Shard *e, int flags, int32_t count, const int32_t *prune, double *lnl, phyamd_spr_profile &prof) {
+// what phyamd_spr_log_likelihoods and phyamd_spr_optimize (`name`) check alike; live: the indices of the rows that have candidates
+// -- p is neither the root nor a child of it
+int check_spr_call(Shard *e, const char *name, const char *eigen_use, int flags, int32_t count, const int32_t *prune, std::vector<int32_t> &live) {
 	int rc;
 	if ((rc = check_ready(e))) return rc;
-	if (flags != 0) return fail(PHYAMD_EUNSUPPORTED, "phyamd_spr_log_likelihoods: flags %d (no flags are defined: pass 0)", flags);
-	if (const char *why = tree_batch_refusal(e, 0, 1)) return fail(PHYAMD_EUNSUPPORTED, "phyamd_spr_log_likelihoods: %s", why);
-	if (!e->have_eigen) return fail(PHYAMD_EINVAL, "phyamd_spr_log_likelihoods needs the eigen system (phyamd_set_eigen): the half-length matrices are formed from it");
-	const int T = e->T, N = e->N, C = e->C;
-	if (!prune && count != N) return fail(PHYAMD_EINVAL, "phyamd_spr_log_likelihoods: prune is null, so count must be the node count %d (got %d)", N, count);
-	std::vector<int32_t> live;  // indices of the rows that have candidates: p is neither the root nor a child of it
+	if (flags != 0) return fail(PHYAMD_EUNSUPPORTED, "%s: flags %d (no flags are defined: pass 0)", name, flags);
+	if (const char *why = tree_batch_refusal(e, 0, 1)) return fail(PHYAMD_EUNSUPPORTED, "%s: %s", name, why);
+	if (!e->have_eigen) return fail(PHYAMD_EINVAL, "%s needs the eigen system (phyamd_set_eigen): %s", name, eigen_use);
+	const int N = e->N;
+	if (!prune && count != N) return fail(PHYAMD_EINVAL, "%s: prune is null, so count must be the node count %d (got %d)", name, N, count);
 	for (int32_t i = 0; i < count; i++) {
 		const int p = prune ? prune[i] : i;
-		if (p < 0 || p >= N) return fail(PHYAMD_EINVAL, "phyamd_spr_log_likelihoods: prune[%d] = %d is not a node id (0..%d)", i, p, N - 1);
+		if (p < 0 || p >= N) return fail(PHYAMD_EINVAL, "%s: prune[%d] = %d is not a node id (0..%d)", name, i, p, N - 1);
 		if (p != e->root && e->sched.parent[p] != e->root) live.push_back(i);
 	}
-	std::fill(lnl, lnl + (size_t)count * N, NAN);
-	prof.prunes = count;
-	if (live.empty()) return PHYAMD_OK;
+	return PHYAMD_OK;
+}
+
+// the live rows in chunks of what the scratch holds of `plan`; per chunk the rows' lists built and sent, the matrices of the
+// engine's lengths (and, halves: of half of them behind) and k_spr_walk4, then body(first, rows, cands, mats) -- which ends with
+// the stream synchronised, since the next chunk builds the lists anew.  row_holds: what a row's scratch is, for the refusal
+template <typename Body>
+int for_spr_row_chunks(Shard *e, const char *name, const char *row_holds, const ScratchPlan &plan, const std::vector<int32_t> &live, const int32_t *prune, bool halves,
+                       Body body) {
+	const int T = e->T, N = e->N, C = e->C, nblk = (e->P + WAVE - 1) / WAVE;
+	int rc;
 	ensure_spr_lists(e);
-	const ScratchPlan plan = spr_plan(e);
-	const int nblk = (e->P + WAVE - 1) / WAVE;
-	std::vector<double> lengths((size_t)2 * N), out;
+	std::vector<double> lengths((size_t)2 * N);
 	for (int n = 0; n < N; n++) lengths[n] = e->lengths[n], lengths[N + n] = 0.5 * e->lengths[n];
 	std::vector<BatchOp> ops;
 	std::vector<SprCand> cands;
 	std::vector<int32_t> cand_of;
 	for (size_t first = 0; first < live.size();) {
 		const size_t rows = std::min(batch_items_that_fit(e, live.size() - first, plan), live.size() - first);
-		if (rows < 1)
-			return fail(PHYAMD_EUNSUPPORTED, "phyamd_spr_log_likelihoods: the scratch of one row (%zu bytes: every internal node's lower and upper partial) does not fit the memory budget",
-			            plan.item_bytes());
+		if (rows < 1) return fail(PHYAMD_EUNSUPPORTED, "%s: the scratch of one row (%zu bytes: %s) does not fit the memory budget", name, plan.item_bytes(), row_holds);
 		if ((rc = ensure_batch_scratch(e, rows, plan))) return rc;
 		ops.clear();
 		cands.clear();
@@ -1044,10 +1047,31 @@ int run_spr(Shard *e, int flags, int32_t count, const int32_t *prune, double *ln
 		HIP_TRY(hipMemcpyAsync(e->d_spr_cands, cands.data(), sizeof(SprCand) * cands.size(), hipMemcpyHostToDevice, e->stream));
 		HIP_TRY(hipMemcpyAsync(e->d_spr_cand_of, cand_of.data(), sizeof(int32_t) * cand_of.size(), hipMemcpyHostToDevice, e->stream));
 		HIP_TRY(hipMemcpyAsync(e->d_spr_len, lengths.data(), sizeof(double) * lengths.size(), hipMemcpyHostToDevice, e->stream));
-		launch_batch_matrices(e, 2, e->d_spr_len, nullptr, e->d_spr_mats);  // the engine's lengths, then their halves
-		const double *mats = e->d_spr_mats.get(), *half = mats + (size_t)N * C * 16;
+		launch_batch_matrices(e, halves ? 2 : 1, e->d_spr_len, nullptr, e->d_spr_mats);  // the engine's lengths, then their halves
+		const double *mats = e->d_spr_mats.get();
 		const SprWalkArgs walk{e->d_batch_item_ops.get(), T, N, e->P, C, nblk, e->d_tipmask, mats, e->d_batch_lower, e->d_batch_upper};
 		hipLaunchKernelGGL(k_spr_walk4, dim3(nblk, (unsigned)rows), dim3(WAVE, C), 0, e->stream, walk);
+		if ((rc = body(first, rows, cands, mats))) return rc;
+		first += rows;
+	}
+	return PHYAMD_OK;
+}
+
+// lnl [count][N] (host).  Reads the engine's inputs and writes only the batch scratch: nothing in Shard::state changes but the
+// record that the host lists are the tree's
+int run_spr(Shard *e, int flags, int32_t count, const int32_t *prune, double *lnl, phyamd_spr_profile &prof) {
+	static const char *const name = "phyamd_spr_log_likelihoods";
+	int rc;
+	std::vector<int32_t> live;
+	if ((rc = check_spr_call(e, name, "the half-length matrices are formed from it", flags, count, prune, live))) return rc;
+	const int T = e->T, N = e->N, C = e->C, nblk = (e->P + WAVE - 1) / WAVE;
+	std::fill(lnl, lnl + (size_t)count * N, NAN);
+	prof.prunes = count;
+	if (live.empty()) return PHYAMD_OK;
+	std::vector<double> out;
+	return for_spr_row_chunks(e, name, "every internal node's lower and upper partial", spr_plan(e), live, prune, true,
+	                          [&](size_t first, size_t rows, const std::vector<SprCand> &cands, const double *mats) -> int {
+		const double *half = mats + (size_t)N * C * 16;
 		for (size_t c0 = 0; c0 < cands.size(); c0 += BATCH_MAX_CHUNK) {  // (gridDim.y)
 			const size_t n = std::min<size_t>(cands.size() - c0, BATCH_MAX_CHUNK);
 			const SprArgs a{e->d_spr_cands.get() + c0, T, N, e->P, C, nblk, e->d_tipmask, e->d_freqs, e->d_props, e->d_weights, mats, half, e->d_batch_lower, e->d_batch_upper,
@@ -1064,14 +1088,105 @@ int run_spr(Shard *e, int flags, int32_t count, const int32_t *prune, double *ln
 		for (size_t r = 0; r < rows; r++) std::copy(out.begin() + r * N, out.begin() + (r + 1) * N, lnl + (size_t)live[first + r] * N);
 		prof.chunks++;
 		prof.candidates += (int64_t)cands.size();
-		first += rows;
-	}
-	return PHYAMD_OK;
+		return PHYAMD_OK;
+	});
 }
 
 int shard_spr_log_likelihoods(Shard *e, int flags, int32_t count, const int32_t *prune, double *lnl) {
 	CHECK_ENGINE(e);
 	return profiled_call(e, &Shard::spr_prof, phyamd_spr_profile{}, [&](phyamd_spr_profile &prof) { return run_spr(e, flags, count, prune, lnl, prof); });
+}
+
+// ---- the three graft branches of every SPR regraft, optimised (phyamd_spr_optimize) ----------------------------------------------
+
+// the SPR row's, and per row for its (at most N) candidates: pi o U, the visited branch's coefficients, the results and status
+// words, and the cells they are scattered into
+ScratchPlan tripod_plan(Shard *e) {
+	const size_t D = sizeof(double), N = (size_t)e->N, C = (size_t)e->C, nblk = ((size_t)e->P + WAVE - 1) / WAVE, plane = nblk * WAVE * 4;
+	ScratchPlan p = spr_plan(e);
+	p.add(e->d_tripod_fU, D * N * C * plane);
+	p.add(e->d_tripod_K, D * N * C * plane);
+	p.add(e->d_tripod_res, D * N * 5);
+	p.add(e->d_tripod_status, sizeof(int32_t) * N * TRIPOD_STATUS);
+	p.add(e->d_tripod_out, D * N * 5);
+	p.add(e->d_tripod_counts, sizeof(int32_t) * N * 3);
+	return p;
+}
+
+struct SprOptimizeArgs {
+	int32_t count;
+	const int32_t *prune;
+	double lower, upper, tolerance;
+	int32_t max_iterations;
+	double lnl_tolerance;
+	int32_t max_passes;
+	double *lengths, *lnl, *initial_lnl;
+	int32_t *passes;
+};
+
+// lengths [count][N][3], lnl, initial_lnl, passes [count][N] (host): the SPR call's rows and walk, then per chunk of rows pi o U of
+// every candidate and one workgroup per candidate that runs its whole rule.  Reads the engine's inputs and writes only the batch
+// scratch: nothing in Shard::state changes but the record that the host lists are the tree's
+int run_spr_optimize(Shard *e, int flags, const SprOptimizeArgs &o, phyamd_spr_optimize_profile &prof) {
+	static const char *const name = "phyamd_spr_optimize";
+	int rc;
+	std::vector<int32_t> live;
+	if ((rc = check_ready(e))) return fail(rc, "%s: the engine is not ready: %s", name, std::string(g_last_error).c_str());
+	if ((rc = check_spr_call(e, name, "the likelihood in a branch length is formed from it", flags, o.count, o.prune, live))) return rc;
+	const int T = e->T, N = e->N, C = e->C, nblk = (e->P + WAVE - 1) / WAVE;
+	const size_t all = (size_t)o.count * N;
+	std::fill(o.lengths, o.lengths + all * 3, NAN);
+	std::fill(o.lnl, o.lnl + all, NAN);
+	if (o.initial_lnl) std::fill(o.initial_lnl, o.initial_lnl + all, NAN);
+	if (o.passes) std::fill(o.passes, o.passes + all, 0);
+	prof.prunes = o.count;
+	if (live.empty()) return PHYAMD_OK;
+	std::vector<double> out;
+	std::vector<int32_t> counts;
+	return for_spr_row_chunks(e, name, "every internal node's lower and upper partial, and two planes per candidate", tripod_plan(e), live, o.prune, false,
+	                          [&](size_t first, size_t rows, const std::vector<SprCand> &cands, const double *mats) -> int {
+		const size_t plane = (size_t)nblk * WAVE * 4;
+		for (size_t c0 = 0; c0 < cands.size(); c0 += BATCH_MAX_CHUNK) {  // (gridDim.y)
+			const size_t n = std::min<size_t>(cands.size() - c0, BATCH_MAX_CHUNK);
+			const TripodUpperArgs a{e->d_spr_cands.get() + c0, T, N, e->P, C, nblk, e->d_tipmask, e->d_freqs, mats, e->d_batch_lower, e->d_batch_upper,
+			                        e->d_tripod_fU.get() + c0 * C * plane};
+			hipLaunchKernelGGL(k_tripod_upper4, dim3(nblk, (unsigned)n), dim3(WAVE, C), 0, e->stream, a);
+		}
+		TripodSolveArgs s{};
+		s.cands = e->d_spr_cands, s.T = T, s.P = e->P, s.C = C, s.nblk = nblk, s.max_iterations = o.max_iterations, s.max_passes = o.max_passes;
+		s.lower = o.lower, s.upper = o.upper, s.tolerance = o.tolerance, s.lnl_tolerance = o.lnl_tolerance;
+		s.tipmask = e->d_tipmask, s.props = e->d_props, s.model = e->d_model, s.rates = e->d_rates, s.weights = e->d_weights;
+		s.lengths = e->d_spr_len, s.row_lower = e->d_batch_lower, s.fU = e->d_tripod_fU, s.K = e->d_tripod_K, s.out = e->d_tripod_res, s.status = e->d_tripod_status;
+		if (!cands.empty()) hipLaunchKernelGGL(k_tripod_solve4, dim3((unsigned)cands.size()), dim3(CBOPT_THREADS), 0, e->stream, s);
+		const size_t cells = rows * N;
+		hipLaunchKernelGGL(k_tripod_finish, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, e->stream, cells, e->d_spr_cand_of.get(), e->d_tripod_res.get(),
+		                   e->d_tripod_status.get(), e->d_tripod_out.get(), e->d_tripod_counts.get());
+		HIP_TRY(hipGetLastError());
+		out.resize(cells * 5);
+		counts.resize(cells * 3);
+		HIP_TRY(hipMemcpyAsync(out.data(), e->d_tripod_out, sizeof(double) * out.size(), hipMemcpyDeviceToHost, e->stream));
+		HIP_TRY(hipMemcpyAsync(counts.data(), e->d_tripod_counts, sizeof(int32_t) * counts.size(), hipMemcpyDeviceToHost, e->stream));
+		HIP_TRY(hipStreamSynchronize(e->stream));  // (also covers the lists, which the next chunk builds anew)
+		for (size_t r = 0; r < rows; r++)
+			for (size_t w = 0; w < (size_t)N; w++) {
+				const size_t from = r * N + w, to = (size_t)live[first + r] * N + w;
+				const double *v = &out[from * 5];
+				std::copy(v, v + 3, o.lengths + to * 3);
+				o.lnl[to] = v[3];
+				if (o.initial_lnl) o.initial_lnl[to] = v[4];
+				if (o.passes) o.passes[to] = counts[from * 3];
+				prof.visits += counts[from * 3 + 1];
+				prof.iterations += counts[from * 3 + 2];
+			}
+		prof.chunks++;
+		prof.candidates += (int64_t)cands.size();
+		return PHYAMD_OK;
+	});
+}
+
+int shard_spr_optimize(Shard *e, int flags, const SprOptimizeArgs &o) {
+	CHECK_ENGINE(e);
+	return profiled_call(e, &Shard::tripod_prof, phyamd_spr_optimize_profile{}, [&](phyamd_spr_optimize_profile &prof) { return run_spr_optimize(e, flags, o, prof); });
 }
 
 // ---- per-pattern posteriors (phyamd_state_posteriors, phyamd_site_rate_posteriors) ---------------------------------------------

@@ -219,7 +219,7 @@ struct Shard {
 	DeviceArray<BatchOp> d_batch_item_ops{&batch_mem};  // [item][post-order T - 1 | pre-order T - 1]
 	DeviceArray<int32_t> d_batch_roots{&batch_mem};     // [item]
 	// what the scratch holds: every call describes what it needs as a ScratchPlan (phyamd_queries.inc: batch_plan, reweight_plan,
-	// nni_base_plan with nni_plan and cbopt_plan, blopt_plan, spr_plan, bhess_plan, sitelnl_plan) and gets at least that, so a call of one kind
+	// nni_base_plan with nni_plan and cbopt_plan, blopt_plan, spr_plan with tripod_plan, bhess_plan, sitelnl_plan) and gets at least that, so a call of one kind
 	// never runs in the scratch of another with too few upper slots or without its lists.  batch_held: the plan the arrays were last
 	// allocated by, for batch_items items (the Hessian's arrays, grown beside it, are judged by their sizes alone)
 	ScratchPlan batch_held;
@@ -264,6 +264,16 @@ struct Shard {
 	DeviceArray<double> d_spr_slab{&batch_mem}, d_spr_out{&batch_mem};  // [candidate][blocks], [rows][N]
 	DeviceArray<double> d_spr_len{&batch_mem}, d_spr_mats{&batch_mem};  // [t | 0.5 t][N], [2][N][C][16]
 	phyamd_spr_profile spr_prof{};
+	// phyamd_spr_optimize (phyamd_tripod4.inc) runs the same walk of the same rows with the same lists and adds to the group, per
+	// candidate of a row: pi o U, the coefficients of the branch being visited, the result and the status words; per cell the
+	// scattered results and counts
+	DeviceArray<double> d_tripod_fU{&batch_mem};        // [candidate][C][blocks * 64][4]
+	DeviceArray<double> d_tripod_K{&batch_mem};         // [candidate][C][4][blocks * 64]
+	DeviceArray<double> d_tripod_res{&batch_mem};       // [candidate][t_p, t_w, t_u, lnl, initial_lnl]
+	DeviceArray<int32_t> d_tripod_status{&batch_mem};   // [candidate][TRIPOD_STATUS]
+	DeviceArray<double> d_tripod_out{&batch_mem};       // [rows][N][5]
+	DeviceArray<int32_t> d_tripod_counts{&batch_mem};   // [rows][N][passes, visits, iterations]
+	phyamd_spr_optimize_profile tripod_prof{};
 	// phyamd_state_posteriors / phyamd_site_rate_posteriors (phyamd_post.inc): the rows of a chunk, their staged results -- [rows][P][S]
 	// posteriors and [rows][P] states, or [P][C] + [P] site rates -- and, 20 / 60 / 61 states, each row's own partial p_n (true_lower_gen).
 	// On demand, like d_branch: the calls read what the keep-partials gradient left and have no entry in the record above

@@ -66,10 +66,11 @@ __global__ __launch_bounds__(BATCH_MAX_CATEGORIES *WAVE) void k_spr_walk4(const 
 	}
 }
 
-// a regraft: row (prune node p) onto the edge above w; x: w's parent (BATCH_ROOT: the root, whose upper is ones), y: w's sibling
+// a regraft: row (prune node p) onto the edge above w; x: w's parent (BATCH_ROOT: the root, whose upper is ones), y: w's sibling;
+// p_left: p is its parent's left child (phyamd_tripod4.inc: the order of a pass)
 struct SprCand {
-	int32_t row, w, x, y, p;
-	int32_t pad[3];
+	int32_t row, w, x, y, p, p_left;
+	int32_t pad[2];
 };
 
 __device__ __forceinline__ SprCand load_spr_cand(const SprCand *cands, int i) { return load_const_record<5>(cands, i); }

@@ -349,7 +349,8 @@ class Engine:
         i is node i); column w regrafts it onto the edge above w: with u the prune node's parent and s its sibling, s takes u's
         place under u's parent with length t_s + t_u, u takes w's place under w's parent and gets w where s was, and both halves
         of the graft edge get 0.5 t_w.  NaN where w is the root, u, s, the prune node or one of its descendants, and in the whole
-        row of the root and of its children (re-root to reach those moves).  lnL only: the best few go to gradient_batch_trees.
+        row of the root and of its children (re-root to reach those moves).  lnL only, at that fixed assignment: spr_optimize
+        optimises the three branches at the graft point of every candidate.
         The engine's tree, lengths and partials stay.  No fallback: EngineError where gradient_batch_trees refuses."""
         pr = None
         if prune is not None:
@@ -365,6 +366,38 @@ class Engine:
         """Of the last spr_log_likelihoods: prunes (rows), chunks, candidates, scratch_bytes, ms."""
         p = _lib.SprProfile()
         self._check(self._lib.phyamd_get_spr_profile(self._h, C.byref(p)))
+        return {k: getattr(p, k) for k, _ in p._fields_}
+
+    def spr_optimize(self, prune=None, lower=1e-8, upper=10.0, tolerance=1e-8, max_iterations=100, lnl_tolerance=1e-6, max_passes=50,
+                     want_initial_lnl=True, want_passes=True, flags=0):
+        """The three branches that meet at the graft point of every SPR regraft optimised on the device: (lengths [count, N, 3],
+        lnl [count, N], initial_lnl [count, N], passes [count, N]; the last two None when not wanted), in spr_log_likelihoods' rows,
+        columns and rearranged trees.  lengths holds (t_p, t_w, t_u) of the prune node, the target node and the prune node's
+        parent, from the start (t_p, 0.5 t_w, 0.5 t_w).  An entry is what optimize_branch_lengths returns for its rearranged tree
+        with only those three nodes marked: a pass visits the parent's left child, its right child, then the parent; a visit moves
+        its branch by nni_optimize's safeguarded Newton rule in [lower, upper] and keeps the move when lnL did not fall; the entry
+        stops when a pass gains no more than lnl_tolerance (passes > 0) or after max_passes (passes = -max_passes); a lnL that is
+        not finite ends it in band with passes negative.  NaN (passes 0) wherever spr_log_likelihoods has NaN.  The engine's tree,
+        lengths and partials stay.  No fallback: EngineError where spr_log_likelihoods refuses, and on a sharded engine."""
+        pr = None
+        if prune is not None:
+            pr = np.ascontiguousarray(prune, dtype=np.int32)
+            if pr.ndim != 1:
+                raise ValueError(f"prune must be one-dimensional (got {pr.shape})")
+        count = self.N if pr is None else len(pr)
+        lengths, lnl = np.empty((count, self.N, 3)), np.empty((count, self.N))
+        lnl0 = np.empty((count, self.N)) if want_initial_lnl else None
+        passes = np.empty((count, self.N), dtype=np.int32) if want_passes else None
+        opt = lambda a: None if a is None else _ptr(a)
+        self._check(self._lib.phyamd_spr_optimize(self._h, flags, count, opt(pr), lower, upper, tolerance, max_iterations, lnl_tolerance, max_passes,
+                                                  _ptr(lengths), _ptr(lnl), opt(lnl0), opt(passes)))
+        return lengths, lnl, lnl0, passes
+
+    def spr_optimize_profile(self):
+        """Of the last spr_optimize: prunes (rows), chunks (of rows), candidates, visits and iterations (over all candidates),
+        scratch_bytes, ms."""
+        p = _lib.SprOptimizeProfile()
+        self._check(self._lib.phyamd_get_spr_optimize_profile(self._h, C.byref(p)))
         return {k: getattr(p, k) for k, _ in p._fields_}
 
     def state_posteriors(self, nodes=None, want_posteriors=True, want_states=True):
