@@ -345,6 +345,14 @@ class TreeLikelihoodInterface : public CallableModelInterface {
 	// engine's branch lengths, as for NNILogLikelihoods.  The tree model and this object's own state are unchanged.
 	void SPROptimize(const int *prune, int count, double lower, double upper, double tolerance, int maxIterations, double lnlTolerance, int maxPasses, double *lengths,
 	                 double *logLikelihoods, double *initialLogLikelihoods, int32_t *passes);
+	// Beyond the reference surface: the maximum-likelihood distance of `count` pairs of taxa under this object's own models, before
+	// any tree is scored (one phyamd_pairwise_distances call; see include/physher_amd.h for the definition and the rule): pairs
+	// [count][2] holds two tip ids of the tree model each (null: count = T(T-1)/2, all i < j row-major); start [count] may be null
+	// (0.1).  distances [count]; logLikelihoods, d1, d2 and iterations [count] may be null; counts [count][16][16], if not null,
+	// receives the weighted tables of state-mask pairs.  With distances null and counts given the call only counts.  The tree
+	// model and this object's own state are unchanged.
+	void PairwiseDistances(const int *pairs, int count, const double *start, double lower, double upper, double tolerance, int maxIterations, double *distances,
+	                       double *logLikelihoods, double *d1, double *d2, int32_t *iterations, double *counts);
 	// Beyond the reference surface: marginal ancestral reconstruction of `count` nodes of the tree model's tree at once (one
 	// phyamd_state_posteriors call; see include/physher_amd.h for the definition): posteriors [count][patterns][states] and states
 	// [count][patterns] by the tree's node ids, row i the node nodes[i] (null: count = 2T-1 and row i is node i; tips and the

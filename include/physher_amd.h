@@ -764,6 +764,47 @@ int phyamd_spr_optimize(phyamd_engine *e, int flags, int32_t count, const int32_
 typedef struct { int32_t prunes, chunks; int64_t candidates, visits, iterations, scratch_bytes; double ms; } phyamd_spr_optimize_profile;
 int phyamd_get_spr_optimize_profile(phyamd_engine *e, phyamd_spr_optimize_profile *out);
 
+/* --- the maximum-likelihood distance of pairs of taxa --- */
+/* The ML distance of `count` pairs of taxa under the engine's own model (eigen system, frequencies, category rates and proportions,
+ * ambiguity masks), before any topology exists: what a distance method (NJ, UPGMA) builds a starting tree from, where the
+ * reference's closed forms (distancematrix.c: uncorrected, JC69, K2P) ignore the model.  pairs [count][2] holds (i, j), i != j, both
+ * in 0..T-1; pairs == NULL: count must be T(T-1)/2 and the entries are (0,1), (0,2), ..., (T-2,T-1).  i is the side that carries
+ * pi; nothing assumes reversibility.
+ * For a pair and a length t, pattern k has L_k(t) = sum_c w_c sum_a (V^T (pi o m_i))_a (V^-1 m_j)_a exp(lambda_a r_c t) with m_i, m_j
+ * the two 0/1 state masks: the two-tip tree of phyamd_log_likelihood with one branch of length t.  L_k depends on k only through
+ * the pair of masks, so with the weighted table N[mi][mj] = sum_k w_k [mask_i[k] = mi][mask_j[k] = mj] (16 x 16, masks as 4-bit
+ * numbers, bit s = state s), S_n[a](t) = sum_c w_c (lambda_a r_c)^n exp(lambda_a r_c t) and G[mi][mj][a] = (V^T (pi o mi))_a (V^-1 mj)_a:
+ *   F_n[mi][mj] = sum_a G[mi][mj][a] S_n[a],  lnL = sum N log F_0,  d1 = sum N F_1 / F_0,  d2 = sum N (F_2 / F_0 - (F_1 / F_0)^2),
+ * the sums over the bins with N > 0.  f(t) = (lnL, d1, d2).
+ * THE RULE, per pair, is phyamd_nni_optimize's (see there) on this f: start is start[p] or, with start NULL, 0.1.  distances[p] = t*;
+ * lnl, d1 and d2 are evaluated at t*; iterations has phyamd_nni_optimize's sign convention; a lnL that is not finite at an iterate
+ * ends the pair in band exactly as there.  Identical rows end at lower and saturated pairs at upper: results, not errors.  lnl, d1,
+ * d2 and iterations may be NULL.  counts [count][16][16], if given, receives the tables N (counts[p][mi][mj]): the sufficient
+ * statistic of every count-based distance as well (physher_amd/distances.py: p-distance, JC69, K2P).  With distances == NULL and
+ * counts given the call ONLY COUNTS: it needs no eigen system, frequencies or rates, and ignores start, the bounds, the tolerance and
+ * max_iterations.
+ * The call needs tip data for every tip and the pattern weights, and for distances the eigen system, the frequencies and the
+ * category rates and proportions.  It needs no topology and no branch lengths and reads no partials: it works before
+ * phyamd_set_topology, on an engine that is rescaling, and with any number of categories.  The tables are formed on the matrix pipe
+ * over segments of 4096 patterns added in order, a pair's whole iteration runs in one workgroup, and nothing is added with atomics:
+ * the engine is unchanged and later evaluations return the bits they would have returned without the call; two calls return identical
+ * bits; a pair's bits do not depend on the other pairs, on its position in the list, on the chunks the pairs ran in or on which
+ * optional outputs are asked for.  The scratch is the batch scratch's, per pair 2 KB per segment and 2 KB; pairs that do not fit the
+ * memory cap together run in chunks.  PHYAMD_EUNSUPPORTED, naming the condition: not 4 states, tiled patterns, a tip cell with an
+ * empty state mask, a handle sharded over several devices (the tables would add up across the shards: not built), flags other than
+ * 0, scratch of one pair that does not fit the memory cap.  PHYAMD_EINVAL: null engine; neither distances nor counts; lnl, d1, d2 or
+ * iterations without distances; count < 1, or another count than T(T-1)/2 with pairs NULL; an index outside 0..T-1 or i == j; a tip
+ * without data; no pattern weights; for distances a missing eigen system, frequencies or rates, and phyamd_nni_optimize's conditions
+ * on the bounds, the tolerance, max_iterations and the start values. */
+int phyamd_pairwise_distances(phyamd_engine *e, int flags, int32_t count, const int32_t *pairs /* [count][2] or NULL: all i<j, row-major */,
+                              const double *start /* [count] or NULL: 0.1 */, double lower, double upper, double tolerance, int32_t max_iterations,
+                              double *distances /* [count] or NULL */, double *lnl /* [count] or NULL */, double *d1, double *d2 /* or NULL */,
+                              int32_t *iterations /* or NULL */, double *counts /* [count][16][16] or NULL */);
+/* of the last phyamd_pairwise_distances: pairs asked for, chunks of pairs they ran in, segments of the pattern axis, bytes of batch
+ * scratch the engine holds (see phyamd_batch_profile), proposals made over all pairs, wall time of the call */
+typedef struct { int32_t pairs, chunks, segments; int64_t scratch_bytes, iterations; double ms; } phyamd_distance_profile;
+int phyamd_get_distance_profile(phyamd_engine *e, phyamd_distance_profile *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -57,6 +57,11 @@ class SprOptimizeProfile(C.Structure):
                 ("scratch_bytes", C.c_int64), ("ms", C.c_double)]
 
 
+class DistanceProfile(C.Structure):
+    _fields_ = [("pairs", C.c_int32), ("chunks", C.c_int32), ("segments", C.c_int32), ("scratch_bytes", C.c_int64), ("iterations", C.c_int64),
+                ("ms", C.c_double)]
+
+
 class HessianProfile(C.Structure):
     _fields_ = [("chunks", C.c_int32), ("pairs", C.c_int64), ("scratch_bytes", C.c_int64), ("ms", C.c_double)]
 
@@ -136,6 +141,8 @@ SYMBOLS = [
     ("phyamd_get_spr_profile", C.c_int, [_P, C.POINTER(SprProfile)]),
     ("phyamd_spr_optimize", C.c_int, [_P, C.c_int, C.c_int32, _P, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32, _P, _P, _P, _P]),
     ("phyamd_get_spr_optimize_profile", C.c_int, [_P, C.POINTER(SprOptimizeProfile)]),
+    ("phyamd_pairwise_distances", C.c_int, [_P, C.c_int, C.c_int32, _P, _P, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    ("phyamd_get_distance_profile", C.c_int, [_P, C.POINTER(DistanceProfile)]),
     ("phyamd_state_posteriors", C.c_int, [_P, C.c_int, C.c_int32, _P, _P, _P]),
     ("phyamd_site_rate_posteriors", C.c_int, [_P, _P, _P]),
     ("phyamd_branch_hessian", C.c_int, [_P, C.c_int, _P, _P, _P]),

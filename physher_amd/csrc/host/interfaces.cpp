@@ -973,6 +973,14 @@ void TreeLikelihoodInterface::SPROptimize(const int *prune, int count, double lo
 	                                  initialLogLikelihoods, passes));
 }
 
+void TreeLikelihoodInterface::PairwiseDistances(const int *pairs, int count, const double *start, double lower, double upper, double tolerance, int maxIterations,
+                                                double *distances, double *logLikelihoods, double *d1, double *d2, int32_t *iterations, double *counts) {
+	if (!distances && !counts) throw Error("null distances and counts");
+	Sync();
+	phyamd::check(phyamd_pairwise_distances(impl_->engine, 0, count, pairs, start, lower, upper, tolerance, maxIterations, distances, logLikelihoods, d1, d2, iterations,
+	                                        counts));
+}
+
 size_t TreeLikelihoodInterface::StateCount() const { return (size_t)impl_->S; }
 size_t TreeLikelihoodInterface::CategoryCount() const { return (size_t)siteModel_->GetModel()->cat_count; }
 

@@ -695,6 +695,39 @@ int phyamd_get_spr_optimize_profile(phyamd_engine *g, phyamd_spr_optimize_profil
 	return merged_profile(g, &Shard::tripod_prof, out, [](phyamd_spr_optimize_profile &, const phyamd_spr_optimize_profile &) {});  // (never sharded)
 }
 
+// one device only: a pair's table would be the sum of the shards' tables
+int phyamd_pairwise_distances(phyamd_engine *g, int flags, int32_t count, const int32_t *pairs, const double *start, double lower, double upper, double tolerance,
+                              int32_t max_iterations, double *distances, double *lnl, double *d1, double *d2, int32_t *iterations, double *counts) {
+	static const char *const name = "phyamd_pairwise_distances";
+	if (!distances && !counts) return fail(PHYAMD_EINVAL, "%s: null distances and null counts: one of them is the result", name);
+	if (!distances && (lnl || d1 || d2 || iterations))
+		return fail(PHYAMD_EINVAL, "%s: %s without distances (null distances: the call only counts)", name, lnl ? "lnl" : d1 ? "d1" : d2 ? "d2" : "iterations");
+	if (!g || g->shards.empty()) return fail(PHYAMD_EINVAL, "%s: null engine", name);
+	if (count < 1) return fail(PHYAMD_EINVAL, "%s: count must be >= 1 (got %d)", name, count);
+	if (distances) {
+		if (!(lower >= 0.0 && lower < upper && std::isfinite(upper))) return fail(PHYAMD_EINVAL, "%s: bounds [%g, %g]: they must be 0 <= lower < upper < inf", name, lower, upper);
+		if (!(tolerance > 0.0 && std::isfinite(tolerance))) return fail(PHYAMD_EINVAL, "%s: tolerance %g: it must be finite and positive", name, tolerance);
+		if (max_iterations < 1 || max_iterations > 1000) return fail(PHYAMD_EINVAL, "%s: max_iterations %d is outside 1..1000", name, max_iterations);
+		for (int32_t p = 0; p < count && start; p++)
+			if (!std::isfinite(start[p]) || start[p] < 0.0) return fail(PHYAMD_EINVAL, "%s: start[%d] = %g: a start length is finite and not negative", name, p, start[p]);
+	}
+	const int64_t T = g->T;
+	if (!pairs && (int64_t)count != T * (T - 1) / 2)
+		return fail(PHYAMD_EINVAL, "%s: count %d with null pairs: all pairs of %d taxa are %lld", name, count, g->T, (long long)(T * (T - 1) / 2));
+	for (int32_t p = 0; p < count && pairs; p++) {
+		const int32_t i = pairs[2 * p], j = pairs[2 * p + 1];
+		if (i < 0 || i >= g->T || j < 0 || j >= g->T) return fail(PHYAMD_EINVAL, "%s: pairs[%d] = (%d, %d): a taxon index is outside 0..%d", name, p, i, j, g->T - 1);
+		if (i == j) return fail(PHYAMD_EINVAL, "%s: pairs[%d] = (%d, %d): a pair is two different taxa", name, p, i, j);
+	}
+	if (group_size(g) > 1)
+		return fail(PHYAMD_EUNSUPPORTED, "%s: a handle sharded over several devices is out of scope: a pair's table would be the sum of the shards' tables", name);
+	return shard_pairwise_distances(g->shards[0], flags, PairDistanceArgs{count, pairs, start, lower, upper, tolerance, max_iterations, distances, lnl, d1, d2, iterations, counts});
+}
+
+int phyamd_get_distance_profile(phyamd_engine *g, phyamd_distance_profile *out) {
+	return merged_profile(g, &Shard::dist_prof, out, [](phyamd_distance_profile &, const phyamd_distance_profile &) {});  // (never sharded)
+}
+
 // per-pattern results: every shard fills its own pattern range of the caller's arrays, so a pattern's bits do not depend on the
 // shard count.  The NaN rule goes by the handle's lnL (the shards' lnL added like phyamd_log_likelihood's)
 int phyamd_state_posteriors(phyamd_engine *g, int flags, int32_t count, const int32_t *nodes, double *posteriors, uint8_t *states) {

@@ -1189,6 +1189,127 @@ int shard_spr_optimize(Shard *e, int flags, const SprOptimizeArgs &o) {
 	return profiled_call(e, &Shard::tripod_prof, phyamd_spr_optimize_profile{}, [&](phyamd_spr_optimize_profile &prof) { return run_spr_optimize(e, flags, o, prof); });
 }
 
+// ---- the ML distance of pairs of taxa (phyamd_pairwise_distances) ---------------------------------------------------------------
+
+// an item is a PAIR: its two taxa and its group record, its table's segment sums and the table, its start and its results.  Nothing
+// whatever the pair count: the call walks no tree and reads the engine's tip data, weights and model where they are
+ScratchPlan pairdist_plan(Shard *e, size_t segments) {
+	const size_t D = sizeof(double);
+	ScratchPlan p;
+	p.add(e->d_pairdist_pairs, sizeof(int32_t) * 2);
+	p.add(e->d_pairdist_groups, sizeof(int32_t) * 2);
+	p.add(e->d_pairdist_part, D * segments * 256);
+	p.add(e->d_pairdist_counts, D * 256);
+	p.add(e->d_pairdist_start, D);
+	p.add(e->d_pairdist_out, D * 4);
+	p.add(e->d_pairdist_iter, sizeof(int32_t));
+	return p;
+}
+
+constexpr size_t PAIRDIST_MAX_CHUNK = (size_t)1 << 20;  // pairs per chunk: gridDim.x of k_pairdist_solve4, 2 GB of tables
+
+struct PairDistanceArgs {
+	int32_t count;
+	const int32_t *pairs;  // [count][2], validated (phyamd_pairwise_distances); null: all i < j, row-major
+	const double *start;
+	double lower, upper, tolerance;
+	int32_t max_iterations;
+	double *distances, *lnl, *d1, *d2;
+	int32_t *iterations;
+	double *counts;
+};
+
+// chunk by chunk the pairs' tables on the matrix pipe and, with `distances`, each pair's whole iteration in one workgroup.  Reads
+// the engine's tip data, weights and model and writes only the batch scratch: nothing in Shard::state changes
+int run_pairwise_distances(Shard *e, int flags, const PairDistanceArgs &o, phyamd_distance_profile &prof) {
+	static const char *const name = "phyamd_pairwise_distances";
+	const bool solve = o.distances != nullptr;
+	if (e->S != 4) return fail(PHYAMD_EUNSUPPORTED, "%s: the mask-pair tables are built for 4 states (the engine has %d)", name, e->S);
+	if (e->tiles > 1) return fail(PHYAMD_EUNSUPPORTED, "%s: the patterns are tiled and the call needs the tip data of all patterns resident", name);
+	if (flags != 0) return fail(PHYAMD_EUNSUPPORTED, "%s: flags %d (no flags are defined: pass 0)", name, flags);
+	for (int t = 0; t < e->T; t++)
+		if (!e->tip_set[t]) return fail(PHYAMD_EINVAL, "%s: tip %d has no data (phyamd_set_tip_states / phyamd_set_tip_partials)", name, t);
+	if (std::any_of(e->tip_empty.begin(), e->tip_empty.end(), [](uint8_t x) { return x != 0; })) return fail(PHYAMD_EUNSUPPORTED, "%s: a tip cell has an empty state mask", name);
+	if (!e->have_weights) return fail(PHYAMD_EINVAL, "%s: phyamd_set_pattern_weights has not been called", name);
+	if (solve && !e->have_eigen) return fail(PHYAMD_EINVAL, "%s needs the eigen system (phyamd_set_eigen): the likelihood in the distance is formed from it", name);
+	if (solve && !e->have_freqs) return fail(PHYAMD_EINVAL, "%s: phyamd_set_frequencies has not been called", name);
+	if (solve && !e->have_rates) return fail(PHYAMD_EINVAL, "%s: phyamd_set_category_rates has not been called", name);
+	const int T = e->T, P = e->P;
+	const size_t count = (size_t)o.count, segments = ((size_t)P + REWEIGHT_SEGMENT - 1) / REWEIGHT_SEGMENT;
+	if (segments > 65535) return fail(PHYAMD_EUNSUPPORTED, "%s: %zu segments of %d patterns (at most 65535: gridDim.y)", name, segments, REWEIGHT_SEGMENT);
+	prof.pairs = o.count;
+	prof.segments = (int32_t)segments;
+	std::vector<int32_t> all;
+	const int32_t *pairs = o.pairs;
+	if (!pairs) {
+		all.reserve(count * 2);
+		for (int i = 0; i < T; i++)
+			for (int j = i + 1; j < T; j++) all.push_back(i), all.push_back(j);
+		pairs = all.data();
+	}
+	const ScratchPlan plan = pairdist_plan(e, segments);
+	const size_t want = std::min(count, PAIRDIST_MAX_CHUNK);
+	size_t chunk = want;
+	if (!plan.held(want)) {
+		const double fit = plan.items_in(scratch_room(e, (double)batch_scratch_bytes(e), EngineRoom::MayGrow));
+		if (fit < 1.0)
+			return fail(PHYAMD_EUNSUPPORTED, "%s: the scratch of one pair (%zu bytes: its table's %zu segment sums, the table and its results) does not fit the memory budget", name,
+			            plan.item_bytes(), segments);
+		chunk = (size_t)std::min((double)want, fit);
+		if (!plan.held(chunk))
+			if (int rc = allocate_batch_scratch(e, chunk, plan)) return rc;
+	}
+	std::vector<int32_t> groups, iter;
+	std::vector<double> start, out;
+	for (size_t first = 0; first < count; first += chunk) {
+		const size_t n = std::min(chunk, count - first);
+		const int32_t *pc = pairs + 2 * first;
+		groups.clear();  // runs of pairs that share their first taxon, at most PAIRDIST_PARTNERS long
+		for (size_t i = 0; i < n;) {
+			size_t len = 1;
+			while (len < (size_t)PAIRDIST_PARTNERS && i + len < n && pc[2 * (i + len)] == pc[2 * i]) len++;
+			groups.push_back((int32_t)i), groups.push_back((int32_t)len);
+			i += len;
+		}
+		HIP_TRY(hipMemcpyAsync(e->d_pairdist_pairs, pc, sizeof(int32_t) * 2 * n, hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_pairdist_groups, groups.data(), sizeof(int32_t) * groups.size(), hipMemcpyHostToDevice, e->stream));
+		const PairCountArgs ca{e->d_pairdist_pairs, e->d_pairdist_groups, e->d_tipmask, e->d_weights, e->d_pairdist_part, e->d_pairdist_counts, P, (int)n, (int)segments};
+		hipLaunchKernelGGL(k_pairdist_counts4, dim3((unsigned)(groups.size() / 2), (unsigned)segments), dim3(WAVE), 0, e->stream, ca);
+		hipLaunchKernelGGL(k_pairdist_finish, dim3((unsigned)n), dim3(256), 0, e->stream, ca);
+		if (solve) {
+			start.assign(n, 0.1);
+			if (o.start) std::copy(o.start + first, o.start + first + n, start.begin());
+			HIP_TRY(hipMemcpyAsync(e->d_pairdist_start, start.data(), sizeof(double) * n, hipMemcpyHostToDevice, e->stream));
+			const PairSolveArgs sa{e->d_pairdist_counts, e->d_pairdist_start, e->C, o.max_iterations, o.lower, o.upper, o.tolerance, e->d_model, e->d_freqs, e->d_rates, e->d_props,
+			                       e->d_pairdist_out, e->d_pairdist_iter};
+			hipLaunchKernelGGL(k_pairdist_solve4, dim3((unsigned)n), dim3(PAIRDIST_THREADS), 0, e->stream, sa);
+			out.resize(n * 4);
+			iter.resize(n);
+			HIP_TRY(hipMemcpyAsync(out.data(), e->d_pairdist_out, sizeof(double) * out.size(), hipMemcpyDeviceToHost, e->stream));
+			HIP_TRY(hipMemcpyAsync(iter.data(), e->d_pairdist_iter, sizeof(int32_t) * n, hipMemcpyDeviceToHost, e->stream));
+		}
+		HIP_TRY(hipGetLastError());
+		if (o.counts) HIP_TRY(hipMemcpyAsync(o.counts + first * 256, e->d_pairdist_counts, sizeof(double) * n * 256, hipMemcpyDeviceToHost, e->stream));
+		HIP_TRY(hipStreamSynchronize(e->stream));  // (also covers the chunk's lists and starts)
+		prof.chunks++;
+		for (size_t i = 0; i < n && solve; i++) {
+			const double *r = &out[i * 4];
+			o.distances[first + i] = r[0];
+			if (o.lnl) o.lnl[first + i] = r[1];
+			if (o.d1) o.d1[first + i] = r[2];
+			if (o.d2) o.d2[first + i] = r[3];
+			if (o.iterations) o.iterations[first + i] = iter[i];
+			prof.iterations += std::abs(iter[i]);
+		}
+	}
+	return PHYAMD_OK;
+}
+
+int shard_pairwise_distances(Shard *e, int flags, const PairDistanceArgs &o) {
+	CHECK_ENGINE(e);
+	return profiled_call(e, &Shard::dist_prof, phyamd_distance_profile{}, [&](phyamd_distance_profile &prof) { return run_pairwise_distances(e, flags, o, prof); });
+}
+
 // ---- per-pattern posteriors (phyamd_state_posteriors, phyamd_site_rate_posteriors) ---------------------------------------------
 
 // The staging arrays of the two calls, and rows of a chunk that fit beside the engine.  per_row[a]: bytes a row takes in array a

@@ -219,7 +219,7 @@ struct Shard {
 	DeviceArray<BatchOp> d_batch_item_ops{&batch_mem};  // [item][post-order T - 1 | pre-order T - 1]
 	DeviceArray<int32_t> d_batch_roots{&batch_mem};     // [item]
 	// what the scratch holds: every call describes what it needs as a ScratchPlan (phyamd_queries.inc: batch_plan, reweight_plan,
-	// nni_base_plan with nni_plan and cbopt_plan, blopt_plan, spr_plan with tripod_plan, bhess_plan, sitelnl_plan) and gets at least that, so a call of one kind
+	// nni_base_plan with nni_plan and cbopt_plan, blopt_plan, spr_plan with tripod_plan, pairdist_plan, bhess_plan, sitelnl_plan) and gets at least that, so a call of one kind
 	// never runs in the scratch of another with too few upper slots or without its lists.  batch_held: the plan the arrays were last
 	// allocated by, for batch_items items (the Hessian's arrays, grown beside it, are judged by their sizes alone)
 	ScratchPlan batch_held;
@@ -274,6 +274,15 @@ struct Shard {
 	DeviceArray<double> d_tripod_out{&batch_mem};       // [rows][N][5]
 	DeviceArray<int32_t> d_tripod_counts{&batch_mem};   // [rows][N][passes, visits, iterations]
 	phyamd_spr_optimize_profile tripod_prof{};
+	// phyamd_pairwise_distances (phyamd_pairdist4.inc) walks no tree: per pair of a chunk its two taxa, the record of the run of pairs
+	// it shares its first taxon with, the segment sums of its 16 x 16 mask-pair table and the table, its start and its results
+	DeviceArray<int32_t> d_pairdist_pairs{&batch_mem}, d_pairdist_groups{&batch_mem};  // [pair][i, j], [group][first pair, pairs]
+	DeviceArray<double> d_pairdist_part{&batch_mem};     // [segments][pair][256]
+	DeviceArray<double> d_pairdist_counts{&batch_mem};   // [pair][16 mi + mj]
+	DeviceArray<double> d_pairdist_start{&batch_mem};    // [pair]
+	DeviceArray<double> d_pairdist_out{&batch_mem};      // [pair][t*, lnL, d1, d2]
+	DeviceArray<int32_t> d_pairdist_iter{&batch_mem};    // [pair]
+	phyamd_distance_profile dist_prof{};
 	// phyamd_state_posteriors / phyamd_site_rate_posteriors (phyamd_post.inc): the rows of a chunk, their staged results -- [rows][P][S]
 	// posteriors and [rows][P] states, or [P][C] + [P] site rates -- and, 20 / 60 / 61 states, each row's own partial p_n (true_lower_gen).
 	// On demand, like d_branch: the calls read what the keep-partials gradient left and have no entry in the record above

@@ -400,6 +400,49 @@ class Engine:
         self._check(self._lib.phyamd_get_spr_optimize_profile(self._h, C.byref(p)))
         return {k: getattr(p, k) for k, _ in p._fields_}
 
+    def pairwise_distances(self, pairs=None, start=None, lower=1e-8, upper=10.0, tolerance=1e-8, max_iterations=100, want_derivatives=True,
+                           want_iterations=True, want_counts=False, counts_only=False, flags=0):
+        """The maximum-likelihood distance of pairs of taxa under the engine's own model, on the device, before any topology exists:
+        (distances [count], lnl [count], d1 [count], d2 [count], iterations [count] int32, counts [count, 16, 16]); what is not
+        wanted is None.  pairs [count, 2] holds (i, j), i the side that carries pi (None: all i < j, row-major: distances.square
+        makes the matrix).  Per pair the length in [lower, upper] that maximises the two-tip likelihood, by nni_optimize's
+        safeguarded Newton rule from start[p] (None: 0.1); lnl, d1 and d2 there; iterations negative where max_iterations ran out
+        or lnL was not finite.  Identical rows end at lower, saturated pairs at upper.  counts[p, mi, mj] is the summed weight of
+        the patterns where taxon i has state mask mi and taxon j mask mj (bit s = state s): the sufficient statistic of the ML
+        distance and of physher_amd.distances' p-distance, JC69 and K2P.  counts_only: only the tables -- no model needed, the
+        bounds ignored.  Needs tip data and weights (and for distances the eigen system, frequencies and rates), no topology and
+        no lengths; works on a rescaling engine and with any number of categories.  The engine is unchanged.  EngineError on
+        engines that are not 4-state, tiled or sharded, and where a tip cell has an empty mask."""
+        pr = None
+        if pairs is not None:
+            pr = np.ascontiguousarray(pairs, dtype=np.int32)
+            if pr.ndim != 2 or pr.shape[1] != 2:
+                raise ValueError(f"pairs must be [count, 2] (got {pr.shape})")
+        count = self.T * (self.T - 1) // 2 if pr is None else len(pr)
+        st = None
+        if start is not None:
+            st = np.ascontiguousarray(start, dtype=np.float64)
+            if st.shape != (count,):
+                raise ValueError(f"start must be [{count}] (got {st.shape})")
+        solve = not counts_only
+        dist = np.empty(count) if solve else None
+        lnl = np.empty(count) if solve else None
+        d1 = np.empty(count) if solve and want_derivatives else None
+        d2 = np.empty(count) if solve and want_derivatives else None
+        it = np.empty(count, dtype=np.int32) if solve and want_iterations else None
+        counts = np.empty((count, 16, 16)) if want_counts or counts_only else None
+        opt = lambda a: None if a is None else _ptr(a)
+        self._check(self._lib.phyamd_pairwise_distances(self._h, flags, count, opt(pr), opt(st), lower, upper, tolerance, max_iterations, opt(dist), opt(lnl),
+                                                        opt(d1), opt(d2), opt(it), opt(counts)))
+        return dist, lnl, d1, d2, it, counts
+
+    def distance_profile(self):
+        """Of the last pairwise_distances: pairs, chunks (of pairs), segments (of the pattern axis), scratch_bytes, iterations (over
+        all pairs), ms."""
+        p = _lib.DistanceProfile()
+        self._check(self._lib.phyamd_get_distance_profile(self._h, C.byref(p)))
+        return {k: getattr(p, k) for k, _ in p._fields_}
+
     def state_posteriors(self, nodes=None, want_posteriors=True, want_states=True):
         """Marginal ancestral reconstruction on the device: (posteriors [count, P, S] float64, states [count, P] uint8), either None
         when not wanted.  Row i is node nodes[i] (None: every node, row i is node i; tips and the root included, duplicates
