@@ -468,6 +468,25 @@ int phyamd_get_hessian_profile(phyamd_engine *e, phyamd_hessian_profile *out);
 typedef struct { int32_t lower_family, lower_slots, lower_levels, lower_tiles_min, lower_tiles_max, walk_units, walk_workgroups;
                  int32_t upper_hess, upper_slots, upper_levels, upper_tiles_min, upper_tiles_max; } phyamd_general_profile;
 int phyamd_get_general_profile(phyamd_engine *e, phyamd_general_profile *out);
+/* Which 4-state kernel the last post-order pass and the last pre-order pass of an evaluation launched (read-only bookkeeping of
+ * the launchers, written where the instantiation is picked; a pass that found its results current and launched nothing leaves
+ * the record as it was, and so does the pass of phyamd_branch_hessian_diagonal).  Every field is -1 before the first pass of
+ * its kind.  *_family: 0 = the level kernels (k_lower4 / k_upper4, one launch per tree level), 1 = the table-gather tree walks
+ * (k_lower4_walk / k_upper4_walk), 2 = the streamed tree walks (k_lower4_stream / k_upper4_stream).  lower_form: what the pass
+ * left in the stored lowers, 0 = the reference's p_n, 1 = t_n = P_n p_n, 2 = t_n rescaled by powers of two per category.
+ * *_scale: 0 = no rescaling, 1 = the reference's, 2 = powers of two.  *_ambiguous: the streamed walks' form for tip data with
+ * partial ambiguity codes.  lower_incremental: the pass recomputed only the nodes above changed branches.  *_waves: the wave
+ * bound the kernel was compiled for, 4 / 8 / 16 (the streamed walks: 4, the most waves their workgroup holds).  lower_ppt: patterns per
+ * thread of k_lower4_walk, 1 or 2 (0: another kernel).  upper_tf: the pass read stored lowers of form 1 or 2.  upper_fold /
+ * upper_compat: PHYAMD_GRAD_FOLD_ROOT_FREQS / the PHYAMD_GRAD_COMPAT_SCALED arithmetic.  upper_params: the pass also formed the
+ * substitution-parameter sums; upper_catblk: ... in k_upper4_walk's form of four pattern groups of one category per workgroup.
+ * upper_pair_ops: the pair ops (phyamd_stream_pairs) of the descriptor set the streamed walk read, 0 where it read a set
+ * without them.  Sharded handles: the first shard's; pattern tiles: the last tile's.  PHYAMD_EUNSUPPORTED on a 20 / 60 /
+ * 61-state engine, with the condition in the message. */
+typedef struct { int32_t lower_family, lower_form, lower_scale, lower_ambiguous, lower_incremental, lower_waves, lower_ppt;
+                 int32_t upper_family, upper_scale, upper_ambiguous, upper_waves, upper_tf, upper_fold, upper_compat, upper_params, upper_catblk,
+                         upper_pair_ops; } phyamd_pass_profile;
+int phyamd_get_pass_profile(phyamd_engine *e, phyamd_pass_profile *out);
 /* lnL and the per-category branch gradient for `count` pattern-weight vectors on the engine's tree, data and models: the batch
  * axis of resampling -- bootstrap and jackknife replicates of one alignment (phyresampling.c:105-260 builds a SitePattern and a
  * likelihood object per replicate), RELL reweighting, site minibatches (a weight vector with zeros).  weights [count][P], any

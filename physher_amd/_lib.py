@@ -71,6 +71,12 @@ class GeneralProfile(C.Structure):
                                          "walk_workgroups", "upper_hess", "upper_slots", "upper_levels", "upper_tiles_min", "upper_tiles_max")]
 
 
+class PassProfile(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("lower_family", "lower_form", "lower_scale", "lower_ambiguous", "lower_incremental", "lower_waves", "lower_ppt",
+                                         "upper_family", "upper_scale", "upper_ambiguous", "upper_waves", "upper_tf", "upper_fold", "upper_compat",
+                                         "upper_params", "upper_catblk", "upper_pair_ops")]
+
+
 class BatchProfile(C.Structure):
     _fields_ = [
         ("items_fast", C.c_int32), ("items_sequential", C.c_int32), ("chunks", C.c_int32), ("scratch_bytes", C.c_int64), ("ms", C.c_double),
@@ -148,6 +154,7 @@ SYMBOLS = [
     ("phyamd_branch_hessian", C.c_int, [_P, C.c_int, _P, _P, _P]),
     ("phyamd_get_hessian_profile", C.c_int, [_P, C.POINTER(HessianProfile)]),
     ("phyamd_get_general_profile", C.c_int, [_P, C.POINTER(GeneralProfile)]),
+    ("phyamd_get_pass_profile", C.c_int, [_P, C.POINTER(PassProfile)]),
     ("phyamd_gradient_batch_weights", C.c_int, [_P, C.c_int, C.c_int32, _P, _P, _P, _P]),
     ("phyamd_get_weight_batch_profile", C.c_int, [_P, C.POINTER(WeightBatchProfile)]),
     ("phyamd_pattern_log_likelihoods_trees", C.c_int, [_P, C.c_int, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int32, _P, _P]),

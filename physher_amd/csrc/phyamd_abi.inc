@@ -789,6 +789,15 @@ int phyamd_get_general_profile(phyamd_engine *g, phyamd_general_profile *out) {
 	return PHYAMD_OK;
 }
 
+int phyamd_get_pass_profile(phyamd_engine *g, phyamd_pass_profile *out) {
+	if (!g || g->shards.empty()) return fail(PHYAMD_EINVAL, "phyamd_get_pass_profile: null engine");
+	if (!out) return fail(PHYAMD_EINVAL, "phyamd_get_pass_profile: null out");
+	const Shard *s = g->shards[0];  // (the shards run the same rule on their own pattern counts and tip data: the first one's)
+	if (s->generic) return fail(PHYAMD_EUNSUPPORTED, "phyamd_get_pass_profile: %d states (the profile is of the 4-state kernels' launches)", s->S);
+	*out = s->pass_prof;
+	return PHYAMD_OK;
+}
+
 // device-resident results (one process per GPU: the caller reduces them across processes with ONE RCCL all-reduce)
 int phyamd_log_likelihood_device(phyamd_engine *g, double *device_out) {
 	CHECK_GROUP(g);

@@ -115,6 +115,19 @@ int resident_workgroups(Shard *e, K kernel, int threads, size_t lds) {
 }
 
 
+// which instantiation a 4-state pass launched (phyamd_get_pass_profile): the launchers call these where they have picked it
+void record_lower_pass(Shard *e, PassKernel family, int scale, bool ambiguous, bool incremental, int waves, int ppt) {
+	phyamd_pass_profile &p = e->pass_prof;
+	p.lower_family = (int)family, p.lower_form = (int)e->lower_form, p.lower_scale = scale, p.lower_ambiguous = ambiguous;
+	p.lower_incremental = incremental, p.lower_waves = waves, p.lower_ppt = ppt;
+}
+struct UpperPass { int scale = 0; bool ambiguous = false; int waves = 0; bool tf = false, fold = false, compat = false, params = false, catblk = false; int pair_ops = 0; };
+void record_upper_pass(Shard *e, PassKernel family, const UpperPass &u) {
+	phyamd_pass_profile &p = e->pass_prof;
+	p.upper_family = (int)family, p.upper_scale = u.scale, p.upper_ambiguous = u.ambiguous, p.upper_waves = u.waves, p.upper_tf = u.tf;
+	p.upper_fold = u.fold, p.upper_compat = u.compat, p.upper_params = u.params, p.upper_catblk = u.catblk, p.upper_pair_ops = u.pair_ops;
+}
+
 template <int WAVES, bool SCALE>
 int launch_lower_levels(Shard *e) {
 	const std::vector<int> &level_off = *e->act_level_off;  // all core nodes, or only the dirty ones (incremental update)
@@ -140,6 +153,7 @@ int launch_lower_levels(Shard *e) {
 	e->prof.lower_launches = launched;
 	e->lnl_blocks = e->nblk_lower;
 	e->lnl_per_block = false;
+	record_lower_pass(e, PassKernel::Levels, SCALE, false, e->act_level_off == &e->inc_level_off, WAVES, 0);
 	return PHYAMD_OK;
 }
 
@@ -157,6 +171,7 @@ void launch_lower_walk_ppt(Shard *e, size_t lds) {
 		                   e->d_props, e->d_weights, e->d_plk, e->d_wl, e->d_lnl_part, (const int *)e->d_walk_lower_chunk_off, phase ? std::max(0, subtrees) : 0,
 		                   phase);
 	e->prof.lower_launches = subtrees > 0 ? 2 : 1;
+	record_lower_pass(e, PassKernel::Walk, SCALE, false, false, WAVES, PPT);
 }
 
 template <int WAVES, bool SCALE>
@@ -221,6 +236,9 @@ int launch_upper_levels(Shard *e, int p0 = 0, int pc = 0) {
 	}
 	HIP_TRY(hipGetLastError());
 	e->prof.upper_launches = launched;
+	UpperPass u;
+	u.scale = SCALE, u.waves = WAVES, u.fold = FOLD, u.compat = COMPAT, u.params = PARAMS;
+	record_upper_pass(e, PassKernel::Levels, u);
 	return PHYAMD_OK;
 }
 
@@ -435,6 +453,7 @@ int launch_lower_stream(Shard *e) {
 	e->prof.lower_launches = subtrees > 0 ? 2 : 1;
 	e->lnl_blocks = nb;
 	e->lnl_per_block = true;
+	record_lower_pass(e, PassKernel::Stream, v.scale, amb, false, STREAM_WAVES, 0);
 	return PHYAMD_OK;
 }
 
@@ -464,6 +483,7 @@ int launch_upper_stream(Shard *e) {
 	hipLaunchKernelGGL(k_op_tables, dim3(nops, e->C), dim3(64), 0, e->stream, nops, e->C, (const int *)e->d_stream_op_tips, (const int *)e->d_stream_op_deep,
 	                   (const int *)e->d_stream_site_tab, (const int *)e->d_stream_pair_tab, e->d_mats, FOLD ? e->d_Q : e->d_Qpi, reinterpret_cast<double *>(e->d_optab.get()));
 	const int subtrees = (int)e->sched.walk_chunk_off.size() - 2;
+	UpperPass rec;
 	for (int phase = 0; phase < (subtrees > 0 ? 2 : 1); phase++) {
 		const bool amb = e->stream_ambiguous;
 		auto *kernel = exp2 ? (amb ? k_upper4_stream<FOLD, 2, true, true> : k_upper4_stream<FOLD, 2, false, true>)
@@ -474,6 +494,8 @@ int launch_upper_stream(Shard *e) {
 		// (... and the one instantiation that knows pair ops, the plain TF one, reads the set that has them: stream_pairs)
 		const bool plain = !tf && !e->stream_tab.plain_desc.empty();
 		const bool pairs = tf && !exp2 && !SCALE && !amb && !e->stream_tab.pair_desc.empty();
+		rec.scale = v.scale, rec.ambiguous = amb, rec.waves = STREAM_WAVES, rec.tf = tf, rec.fold = FOLD;
+		rec.pair_ops = pairs;  // (counted below, once)
 		hipLaunchKernelGGL(kernel, dim3(grid_x.x, phase ? subtrees : 1), block, lds, e->stream,
 		                   (const StreamDesc *)e->d_stream_ops + (plain ? e->stream_tab.desc.size() : pairs ? 2 * e->stream_tab.desc.size() : 0), (const StreamChunk *)e->d_stream_chunks + (plain ? e->stream_tab.chunks.size() : 0),
 		                   (const int *)e->d_walk_chunk_off, phase, nops, e->P, e->C, nb, (const uint32_t *)e->d_mstream, e->mstride, (const double *)e->d_lower, e->d_upper,
@@ -484,6 +506,8 @@ int launch_upper_stream(Shard *e) {
 	e->prof.upper_launches = subtrees > 0 ? 2 : 1;
 	e->grad_blocks = nb;
 	e->slab_walk_order = true;
+	if (rec.pair_ops) rec.pair_ops = (int)std::count_if(e->stream_tab.pairs.begin(), e->stream_tab.pairs.end(), [](const StreamPair &p) { return p.reason == PAIR_FUSED; });
+	record_upper_pass(e, PassKernel::Stream, rec);
 	return PHYAMD_OK;
 }
 
@@ -545,6 +569,9 @@ int launch_upper_walk_v(Shard *e) {
 	HIP_TRY(hipGetLastError());
 	e->prof.upper_launches = subtrees > 0 ? 2 : 1;
 	e->grad_blocks = nb;
+	UpperPass u;
+	u.scale = SCALE, u.waves = WAVES, u.fold = FOLD, u.compat = COMPAT;
+	record_upper_pass(e, PassKernel::Walk, u);
 	return PHYAMD_OK;
 }
 
@@ -628,6 +655,9 @@ int launch_upper_walk_params(Shard *e) {
 	HIP_TRY(hipGetLastError());
 	e->prof.upper_launches = 1;
 	e->grad_blocks = nb;
+	UpperPass u;
+	u.scale = SCALE, u.waves = WAVES, u.params = true, u.catblk = !SCALE && WAVES == 4;
+	record_upper_pass(e, PassKernel::Walk, u);
 	return PHYAMD_OK;
 }
 

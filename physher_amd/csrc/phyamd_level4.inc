@@ -34,7 +34,9 @@ __global__ __launch_bounds__(WAVES *WAVE) void k_lower4(const NodeOp *__restrict
 			__syncthreads();
 			double m = 0.0;
 			for (int cc = 0; cc < C; cc++) m = fmax(m, xb[(g * C + cc) * WAVE + lane]);
-			if (m < SCALING_THRESHOLD) {
+			// (m == 0: a tip cell below has an empty state mask.  The reference divides by it -- 0 / 0, and NaN for the pattern and for
+			// lnL; the partials stay 0 here and the root gives the pattern log 0 = -inf, as the unscaled evaluation does)
+			if (m < SCALING_THRESHOLD && m > 0.0) {
 				out = d4{out.x / m, out.y / m, out.z / m, out.w / m};
 				sf = log(m);
 			}

@@ -179,6 +179,9 @@ struct Shard {
 	int gen_hess_slots[2] = {0, 0};  // resident workgroups of k_upper_gen<HESS> [SCALE]
 	// how the last 20 / 60 / 61-state post-order and pre-order passes were launched (phyamd_get_general_profile): written by their launchers
 	phyamd_general_profile gen_prof{-1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+	// which 4-state kernel the last post-order and pre-order passes launched (phyamd_get_pass_profile): written by their launchers
+	// where they pick the instantiation (record_lower_pass, record_upper_pass), never by lower_kernel / upper_kernel
+	phyamd_pass_profile pass_prof{-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
 	DeviceArray<double> d_branch{&mem};  // phyamd_branch_log_likelihood: [C][3][16] matrices | [3][blocks] partial sums | [3]
 	bool upper_fold = false;         // the stored uppers carry the root frequencies (last gradient call used FOLD)
 	DeviceArray<double> d_rf_part{&mem};      // [S][blocks] partial sums of k_root_frequency_term, then [S]

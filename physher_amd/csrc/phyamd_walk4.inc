@@ -132,7 +132,7 @@ __global__ __launch_bounds__(WAVES *WAVE, (WAVES == 4 && PPT_WALK == 1 && !SCALE
 				lds_barrier();
 				double m = 0.0, sf = 0.0;
 				for (int cc = 0; cc < C; cc++) m = fmax(m, xb[(g * C + cc) * WAVE + lane]);
-				if (m < SCALING_THRESHOLD) {
+				if (m < SCALING_THRESHOLD && m > 0.0) {  // (m == 0, an empty state mask below: see k_lower4)
 					out = d4{out.x / m, out.y / m, out.z / m, out.w / m};
 					sf = log(m);
 				}

@@ -496,6 +496,16 @@ class Engine:
         self._check(self._lib.phyamd_get_general_profile(self._h, C.byref(p)))
         return {k: getattr(p, k) for k, _ in p._fields_}
 
+    def pass_profile(self):
+        """Which 4-state kernel the last post-order and the last pre-order pass launched, every field -1 before the first pass of
+        its kind: lower_family / upper_family (0: the level kernels, 1: the table-gather walks, 2: the streamed walks), lower_form
+        (0: Reference, 1: Carried, 2: CarriedExp2), lower_scale / upper_scale (0: none, 1: the reference's, 2: powers of two),
+        lower_ambiguous / upper_ambiguous, lower_incremental, lower_waves / upper_waves, lower_ppt, upper_tf, upper_fold,
+        upper_compat, upper_params, upper_catblk, upper_pair_ops.  EngineError at 20 / 60 / 61 states."""
+        p = _lib.PassProfile()
+        self._check(self._lib.phyamd_get_pass_profile(self._h, C.byref(p)))
+        return {k: getattr(p, k) for k, _ in p._fields_}
+
     def gradient_batch_weights(self, weights, branch_lengths=None, flags=0, want_gradient=True):
         """lnL and the per-category branch gradient for B pattern-weight vectors [B, P] at once -- bootstrap or jackknife replicates
         (physher_amd.resampling), RELL reweighting, site minibatches: (lnl [B], g [B, N, C] or None).  Item b is what

@@ -342,9 +342,11 @@ def test_fusion_switch_and_memory():
 @pytest.mark.parametrize("T,P,C,shape", [(300, 2500, 4, "random"), (120, 777, 1, "caterpillar"), (64, 1000, 2, "balanced"), (50, 300, 3, "random"),
                                          (40, 500, 8, "random"), (33, 129, 16, "random"), (3, 70, 4, "random"), (2, 5, 4, "random")])
 def test_tree_walk_kernels_match_level_kernels(T, P, C, shape):
-    """The depth-first tree-walk kernels (default for unscaled 4-state evaluations: one launch per pass, child/parent
-    partials handed on in registers / LDS) against the level-batched kernels (PHYAMD_WALK=0) and the oracle; fused and
-    unfused fringe; the walk parks far fewer upper partials."""
+    """The streamed depth-first tree walks (k_lower4_stream / k_upper4_stream, the default for 4-state evaluations: one launch per
+    pass, child/parent partials handed on in registers / LDS) against the level-batched kernels (PHYAMD_WALK=0) and the oracle;
+    fused and unfused fringe; the walk parks far fewer upper partials.  phyamd_get_pass_profile says which family ran.  The
+    table-gather walks (k_lower4_walk / k_upper4_walk), the default before the streamed ones, are fallbacks now and are not
+    reached here: tests/test_pass_kernels_gpu.py reaches them."""
     import os
     pb = random_problem(T, P, C, seed=900 + T + C, shape=shape, gaps=0.03)
     ref = pb.gradient()
@@ -358,6 +360,8 @@ def test_tree_walk_kernels_match_level_kernels(T, P, C, shape):
                 lnl2, cg2 = e.gradient()
                 assert lnl == lnl2 and np.array_equal(cg, cg2)  # fixed-order reductions in both forms
                 assert abs(lnl - lnl0) <= 1e-13 * abs(lnl)
+                ran = e.pass_profile()
+                assert (ran["lower_family"], ran["upper_family"]) == ((2, 2) if walk else (0, 0)), (walk, fuse, ran)  # Stream / Levels
                 e.set_profiling(True)
                 res[(walk, fuse)] = (lnl, cg, e.pattern_log_likelihoods(), e.profile()["device_bytes"])
         finally:
