@@ -353,6 +353,16 @@ class TreeLikelihoodInterface : public CallableModelInterface {
 	// model and this object's own state are unchanged.
 	void PairwiseDistances(const int *pairs, int count, const double *start, double lower, double upper, double tolerance, int maxIterations, double *distances,
 	                       double *logLikelihoods, double *d1, double *d2, int32_t *iterations, double *counts);
+	// Beyond the reference surface: lnL of `queries` sequences that are not among the tree model's taxa, each placed on every edge
+	// of its tree (one phyamd_placement_log_likelihoods call; see include/physher_amd.h for the definition): masks
+	// [queries][patterns] holds a 4-bit state mask 1..15 per query and pattern over THIS OBJECT'S OWN PATTERNS (GetPatternCount(); the
+	// reference and the queries are compressed jointly, or not at all), pendant [lengths] the pendant lengths, split the part of
+	// an edge's length that stays below the new node.  logLikelihoods [lengths][queries][2T-1] by the tree's node ids, NaN in the
+	// root's column; bestNodes and bestLogLikelihoods [lengths][queries]: the smallest node id with the largest lnL, and that lnL.
+	// logLikelihoods or bestNodes may be null, bestLogLikelihoods only needs bestNodes.  Lengths are the engine's branch lengths,
+	// as for NNILogLikelihoods.  The tree model and this object's own state are unchanged.
+	void PlacementLogLikelihoods(const uint8_t *masks, int queries, const double *pendant, int lengths, double split, double *logLikelihoods, int32_t *bestNodes,
+	                             double *bestLogLikelihoods);
 	// Beyond the reference surface: marginal ancestral reconstruction of `count` nodes of the tree model's tree at once (one
 	// phyamd_state_posteriors call; see include/physher_amd.h for the definition): posteriors [count][patterns][states] and states
 	// [count][patterns] by the tree's node ids, row i the node nodes[i] (null: count = 2T-1 and row i is node i; tips and the

@@ -824,6 +824,47 @@ int phyamd_pairwise_distances(phyamd_engine *e, int flags, int32_t count, const 
 typedef struct { int32_t pairs, chunks, segments; int64_t scratch_bytes, iterations; double ms; } phyamd_distance_profile;
 int phyamd_get_distance_profile(phyamd_engine *e, phyamd_distance_profile *out);
 
+/* --- query sequences placed on every edge of the engine's tree --- */
+/* lnL of `queries` sequences that are NOT among the engine's taxa, each placed on every edge of the engine's tree, in one call:
+ * phylogenetic placement (EPA / pplacer style: reads scored on a fixed reference tree) and stepwise addition (a tree grown one taxon
+ * at a time).
+ * THE DEFINITION.  An edge is a non-root node n of the engine's tree, meaning the branch above it with length t_n.  Placing query x
+ * on n with the split sigma in [0, 1] and the pendant length l > 0 is the tree with T + 1 tips in which a new internal node z takes
+ * n's place under n's parent; z has the children n and x; n's branch becomes sigma t_n, z's branch (1 - sigma) t_n and x's branch l;
+ * every other length, the models and the pattern weights are the engine's.  lnl[i][q][n] is the log-likelihood of that tree
+ * (phyamd_log_likelihood's) under pendant[i].  Both children of the root are edges by this same definition; the root's column holds
+ * NaN.  sigma = 0.5 and l = t_x is the reference's SPR_move of x onto n (phyamd_spr_log_likelihoods on the tree that holds x).
+ * masks [queries][P] holds per query and pattern a 4-bit state mask 1..15 (bit s = state s; 15: a gap; phyamd_set_tip_states' tip
+ * encoding).  THE MASKS REFER TO THE ENGINE'S OWN PATTERNS: the caller compresses the reference alignment and the queries jointly
+ * (a column of the joint alignment is a pattern, and the engine's weights count the joint columns), or not at all.
+ * best_node [lengths][queries], if given, receives per (length, query) the smallest node id with the largest lnL (a later edge
+ * replaces an earlier one only when its lnL is strictly larger; the root is never chosen) and best_lnl, if given, that lnL.  They
+ * are formed on the device: with lnl == NULL only 2 lengths queries numbers come back instead of [lengths][queries][2T-1].
+ * The tree side is independent of the query: one walk of the engine's tree (phyamd_nni_log_likelihoods') leaves what every edge
+ * contributes, and a query enters a pattern only through its mask, so per (pendant length, edge, pattern) the 16 possible weighted
+ * log site likelihoods are tabulated once and a (query, edge) score is a gather-and-add over the patterns: no walk, matrix, exp or log
+ * per query.  The patterns are added in order inside fixed segments of 4096 and the segments in order; nothing is added with
+ * atomics: the engine's tree, lengths and partials are unchanged and later evaluations return the bits they would have returned
+ * without the call; two calls return identical bits; a (length, query, edge) result does not depend on the other queries, on their
+ * order, or on the chunks of edges and queries the call ran in under the memory cap.  An lnL that underflows is -inf in band (the
+ * call does not rescale).
+ * PHYAMD_EINVAL: null lnl and best_node; best_lnl without best_node; null masks or pendant; queries < 1 or lengths < 1; a split
+ * outside [0, 1] or not finite; a pendant length that is not finite or not > 0; null engine; a mask byte of 0 or above 15 (the query
+ * and the pattern are named); no eigen system; an engine that is not ready to evaluate.  PHYAMD_EUNSUPPORTED, naming the
+ * condition: a handle sharded over several devices, flags other than 0, not 4 states, more than 8 categories, an engine that is
+ * rescaling, tiled patterns, a tip cell with an empty state mask, explicit node matrices, scratch of one query on one edge that
+ * does not fit the memory cap.  The argument checks come before the handle's state is looked at. */
+int phyamd_placement_log_likelihoods(phyamd_engine *e, int flags, int32_t queries,
+                                     const uint8_t *masks /* [queries][P]: 4-bit state masks 1..15 over the engine's patterns */, int32_t lengths,
+                                     const double *pendant /* [lengths] */, double split,
+                                     double *lnl /* [lengths][queries][2T-1] or NULL; NaN in the root's column */,
+                                     int32_t *best_node /* [lengths][queries] or NULL */, double *best_lnl /* [lengths][queries] or NULL */);
+/* of the last phyamd_placement_log_likelihoods: queries and pendant lengths asked for, edges of the tree (2T-2), chunks of edges the
+ * tables were built in, chunks of queries scored against each, bytes of batch scratch the engine holds (see phyamd_batch_profile),
+ * wall time of the call */
+typedef struct { int32_t queries, lengths, edges, edge_chunks, query_chunks; int64_t scratch_bytes; double ms; } phyamd_placement_profile;
+int phyamd_get_placement_profile(phyamd_engine *e, phyamd_placement_profile *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,6 +62,11 @@ class DistanceProfile(C.Structure):
                 ("ms", C.c_double)]
 
 
+class PlacementProfile(C.Structure):
+    _fields_ = [("queries", C.c_int32), ("lengths", C.c_int32), ("edges", C.c_int32), ("edge_chunks", C.c_int32), ("query_chunks", C.c_int32),
+                ("scratch_bytes", C.c_int64), ("ms", C.c_double)]
+
+
 class HessianProfile(C.Structure):
     _fields_ = [("chunks", C.c_int32), ("pairs", C.c_int64), ("scratch_bytes", C.c_int64), ("ms", C.c_double)]
 
@@ -149,6 +154,8 @@ SYMBOLS = [
     ("phyamd_get_spr_optimize_profile", C.c_int, [_P, C.POINTER(SprOptimizeProfile)]),
     ("phyamd_pairwise_distances", C.c_int, [_P, C.c_int, C.c_int32, _P, _P, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P, _P, _P, _P, _P]),
     ("phyamd_get_distance_profile", C.c_int, [_P, C.POINTER(DistanceProfile)]),
+    ("phyamd_placement_log_likelihoods", C.c_int, [_P, C.c_int, C.c_int32, _P, C.c_int32, _P, C.c_double, _P, _P, _P]),
+    ("phyamd_get_placement_profile", C.c_int, [_P, C.POINTER(PlacementProfile)]),
     ("phyamd_state_posteriors", C.c_int, [_P, C.c_int, C.c_int32, _P, _P, _P]),
     ("phyamd_site_rate_posteriors", C.c_int, [_P, _P, _P]),
     ("phyamd_branch_hessian", C.c_int, [_P, C.c_int, _P, _P, _P]),

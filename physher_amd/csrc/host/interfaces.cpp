@@ -981,6 +981,13 @@ void TreeLikelihoodInterface::PairwiseDistances(const int *pairs, int count, con
 	                                        counts));
 }
 
+void TreeLikelihoodInterface::PlacementLogLikelihoods(const uint8_t *masks, int queries, const double *pendant, int lengths, double split, double *logLikelihoods,
+                                                      int32_t *bestNodes, double *bestLogLikelihoods) {
+	if (!logLikelihoods && !bestNodes) throw Error("null logLikelihoods and bestNodes");
+	Sync();
+	phyamd::check(phyamd_placement_log_likelihoods(impl_->engine, 0, queries, masks, lengths, pendant, split, logLikelihoods, bestNodes, bestLogLikelihoods));
+}
+
 size_t TreeLikelihoodInterface::StateCount() const { return (size_t)impl_->S; }
 size_t TreeLikelihoodInterface::CategoryCount() const { return (size_t)siteModel_->GetModel()->cat_count; }
 

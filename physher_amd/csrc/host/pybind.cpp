@@ -324,6 +324,21 @@ PYBIND11_MODULE(_phycpp_amd, m) {
 		                          table.empty() ? py::object(py::none()) : py::object(darray({count, (py::ssize_t)16, (py::ssize_t)16}, table.data())));
 	    }, py::arg("pairs") = py::none(), py::arg("start") = py::none(), py::arg("lower") = 1e-8, py::arg("upper") = 10.0, py::arg("tolerance") = 1e-8,
 	       py::arg("max_iterations") = 100, py::arg("want_counts") = false, py::arg("counts_only") = false)
+	    .def("placement_log_likelihoods", [](TreeLikelihoodInterface &self, py::array_t<uint8_t, py::array::c_style | py::array::forcecast> masks, darray pendant, double split,
+	                                         bool want_lnl, bool want_best) -> py::tuple {
+		    const py::ssize_t N = (py::ssize_t)self.NodeCount();
+		    if (masks.ndim() != 2 || (size_t)masks.shape(1) != self.GetPatternCount()) throw phyamd::Error("masks: [queries][pattern_count]");
+		    if (pendant.ndim() != 1) throw phyamd::Error("pendant: [lengths]");
+		    const py::ssize_t Q = masks.shape(0), L = pendant.shape(0);
+		    std::vector<double> lnl(want_lnl ? (size_t)L * Q * N : 0), best(want_best ? (size_t)L * Q : 0);
+		    std::vector<int32_t> node(best.size());
+		    self.PlacementLogLikelihoods(masks.data(), (int)Q, pendant.data(), (int)L, split, want_lnl ? lnl.data() : nullptr, want_best ? node.data() : nullptr,
+		                                 want_best ? best.data() : nullptr);
+		    const std::vector<py::ssize_t> shape{L, Q};
+		    return py::make_tuple(want_lnl ? py::object(darray({L, Q, N}, lnl.data())) : py::object(py::none()),
+		                          want_best ? py::object(iarray(shape, node.data())) : py::object(py::none()),
+		                          want_best ? py::object(darray(shape, best.data())) : py::object(py::none()));
+	    }, py::arg("masks"), py::arg("pendant"), py::arg("split") = 0.5, py::arg("want_lnl") = true, py::arg("want_best") = true)
 	    .def("state_posteriors", [](TreeLikelihoodInterface &self, std::optional<iarray> nodes, bool want_posteriors, bool want_states) -> py::tuple {
 		    const py::ssize_t N = (py::ssize_t)self.NodeCount(), P = (py::ssize_t)self.GetPatternCount(), S = (py::ssize_t)self.StateCount();
 		    if (nodes && nodes->ndim() != 1) throw phyamd::Error("nodes: [count]");

@@ -728,6 +728,38 @@ int phyamd_get_distance_profile(phyamd_engine *g, phyamd_distance_profile *out) 
 	return merged_profile(g, &Shard::dist_prof, out, [](phyamd_distance_profile &, const phyamd_distance_profile &) {});  // (never sharded)
 }
 
+// one device only: a query's lnL on an edge would be the sum of the shards', and its best edge follows from the sums
+int phyamd_placement_log_likelihoods(phyamd_engine *g, int flags, int32_t queries, const uint8_t *masks, int32_t lengths, const double *pendant, double split, double *lnl,
+                                     int32_t *best_node, double *best_lnl) {
+	static const char *const name = "phyamd_placement_log_likelihoods";
+	if (!lnl && !best_node) return fail(PHYAMD_EINVAL, "%s: null lnl and null best_node: one of them is the result", name);
+	if (best_lnl && !best_node) return fail(PHYAMD_EINVAL, "%s: best_lnl without best_node", name);
+	if (!masks || !pendant) return fail(PHYAMD_EINVAL, "%s: null %s", name, !masks ? "masks" : "pendant");
+	if (queries < 1) return fail(PHYAMD_EINVAL, "%s: queries must be >= 1 (got %d)", name, queries);
+	if (lengths < 1) return fail(PHYAMD_EINVAL, "%s: lengths must be >= 1 (got %d)", name, lengths);
+	if (!(split >= 0.0 && split <= 1.0)) return fail(PHYAMD_EINVAL, "%s: split %g: it must be in [0, 1]", name, split);
+	for (int32_t l = 0; l < lengths; l++)
+		if (!std::isfinite(pendant[l]) || !(pendant[l] > 0.0)) return fail(PHYAMD_EINVAL, "%s: pendant[%d] = %g: a pendant length is finite and positive", name, l, pendant[l]);
+	if (!g || g->shards.empty()) return fail(PHYAMD_EINVAL, "%s: null engine", name);
+	const size_t P = (size_t)g->P;
+	for (int32_t q = 0; q < queries; q++) {
+		const uint8_t *row = masks + (size_t)q * P;
+		unsigned bad = 0;
+		for (size_t k = 0; k < P; k++) bad |= (unsigned)(uint8_t)(row[k] - 1) > 14u;
+		if (!bad) continue;
+		for (size_t k = 0; k < P; k++)
+			if (row[k] < 1 || row[k] > 15)
+				return fail(PHYAMD_EINVAL, "%s: masks[%d][%zu] = %d (query %d, pattern %zu): a state mask is 1..15 (bit s: state s; 15: a gap)", name, q, k, (int)row[k], q, k);
+	}
+	if (group_size(g) > 1)
+		return fail(PHYAMD_EUNSUPPORTED, "%s: a handle sharded over several devices is out of scope: a query's best edge would need its sums across the shards", name);
+	return shard_placement(g->shards[0], flags, PlacementArgs{queries, masks, lengths, pendant, split, lnl, best_node, best_lnl});
+}
+
+int phyamd_get_placement_profile(phyamd_engine *g, phyamd_placement_profile *out) {
+	return merged_profile(g, &Shard::place_prof, out, [](phyamd_placement_profile &, const phyamd_placement_profile &) {});  // (never sharded)
+}
+
 // per-pattern results: every shard fills its own pattern range of the caller's arrays, so a pattern's bits do not depend on the
 // shard count.  The NaN rule goes by the handle's lnL (the shards' lnL added like phyamd_log_likelihood's)
 int phyamd_state_posteriors(phyamd_engine *g, int flags, int32_t count, const int32_t *nodes, double *posteriors, uint8_t *states) {

@@ -1,4 +1,4 @@
-// phyamd_queries.inc -- the whole-tree query calls on one shard: batches of branch-length vectors, of pattern weights and of trees, NNI and SPR scores,
+// phyamd_queries.inc -- the whole-tree query calls on one shard: batches of branch-length vectors, of pattern weights and of trees, NNI and SPR scores, pairwise distances, query placements,
 // per-pattern posteriors, the full branch Hessian, and the per-pattern lnL of a batch of trees with its RELL replicates.  They read what the engine holds and write only their own scratch
 // (part of phyamd_engine.hip: one translation unit, internal linkage)
 
@@ -1308,6 +1308,172 @@ int run_pairwise_distances(Shard *e, int flags, const PairDistanceArgs &o, phyam
 int shard_pairwise_distances(Shard *e, int flags, const PairDistanceArgs &o) {
 	CHECK_ENGINE(e);
 	return profiled_call(e, &Shard::dist_prof, phyamd_distance_profile{}, [&](phyamd_distance_profile &prof) { return run_pairwise_distances(e, flags, o, prof); });
+}
+
+// ---- query sequences on every edge of the engine's tree (phyamd_placement_log_likelihoods) --------------------------------------
+
+struct PlacementArgs {
+	int32_t queries;
+	const uint8_t *masks;  // [queries][P], validated (phyamd_placement_log_likelihoods)
+	int32_t lengths;
+	const double *pendant;
+	double split;
+	double *lnl;
+	int32_t *best_node;
+	double *best_lnl;
+};
+
+// the NNI walk's (nni_base_plan, with d_nni_mats for the split matrices), and whatever the item count: the pendant lengths and
+// their matrices, the edges, every query's best edge so far, and for a chunk of `cols` node columns and `queries` queries the
+// table, the caller's mask rows and their packed form, the slab and the result
+ScratchPlan place_plan(Shard *e, size_t L, size_t all_queries, size_t cols, size_t queries, size_t segments, bool want_lnl) {
+	const size_t D = sizeof(double), N = (size_t)e->N, C = (size_t)e->C, Ppad = ((size_t)e->P + WAVE - 1) / WAVE * WAVE;
+	ScratchPlan p = nni_base_plan(e);
+	p.add(e->d_nni_mats, 0, D * 3 * N * C * 16);
+	p.add(e->d_place_pend_len, 0, D * L);
+	p.add(e->d_place_pend, 0, D * L * C * 16);
+	p.add(e->d_place_edges, 0, sizeof(PlaceEdge) * N);
+	p.add(e->d_place_best_lnl, 0, D * L * all_queries);
+	p.add(e->d_place_best_node, 0, sizeof(int32_t) * L * all_queries);
+	p.add(e->d_place_table, 0, D * L * cols * Ppad * 16);
+	p.add(e->d_place_raw, 0, queries * (size_t)e->P);
+	p.add(e->d_place_packed, 0, queries * Ppad);
+	p.add(e->d_place_slab, 0, D * segments * L * cols * queries);
+	p.add(e->d_place_out, 0, want_lnl ? D * L * cols * queries : 0);
+	return p;
+}
+
+constexpr size_t PLACE_MAX_CHUNK_QUERIES = (size_t)1 << 20;
+constexpr size_t PLACE_MIN_CHUNK_QUERIES = WAVE;  // queries are cut no further than a wave of lanes while edges can still be cut
+// the largest x in lo..hi with ok(x), ok being true up to some x and false beyond; lo - 1: none
+template <typename Ok>
+size_t largest_that(size_t lo, size_t hi, Ok ok) {
+	if (!ok(lo)) return lo - 1;
+	while (lo < hi) {
+		const size_t mid = lo + (hi - lo + 1) / 2;
+		if (ok(mid)) lo = mid;
+		else hi = mid - 1;
+	}
+	return lo;
+}
+
+// one walk of the engine's tree with every upper parked, then chunk by chunk of node columns the tables, and chunk by chunk of
+// queries the gather.  Reads the engine's inputs and writes only the batch scratch: nothing in Shard::state changes
+int run_placement(Shard *e, int flags, const PlacementArgs &o, phyamd_placement_profile &prof) {
+	static const NniWalkCall call{"phyamd_placement_log_likelihoods", "", "", "the split and pendant matrices are"};
+	int rc;
+	std::vector<double> lengths;
+	if ((rc = check_nni_walk(e, call, flags, nullptr, lengths))) return rc;
+	const int T = e->T, N = e->N, C = e->C, P = e->P, root = e->root;
+	const size_t Q = (size_t)o.queries, L = (size_t)o.lengths;
+	const int nblk = (P + WAVE - 1) / WAVE, Ppad = nblk * WAVE;
+	const size_t segments = ((size_t)Ppad + REWEIGHT_SEGMENT - 1) / REWEIGHT_SEGMENT;
+	if (segments * L > 65535)
+		return fail(PHYAMD_EUNSUPPORTED, "%s: %zu segments of %d patterns x %zu pendant lengths (their product is at most 65535: gridDim.z)", call.name, segments, REWEIGHT_SEGMENT, L);
+	prof.edges = N - 1;
+	for (int n = 0; n < N; n++) {  // d_nni_len [3][N]: sigma t_n | (1 - sigma) t_n | t_n
+		lengths[n] = o.split * e->lengths[n];
+		lengths[(size_t)N + n] = (1.0 - o.split) * e->lengths[n];
+	}
+	std::vector<PlaceEdge> edges;  // the non-root nodes in node order: node n is edge n, or n - 1 above the root
+	for (int n = 0; n < N; n++) {
+		if (n == root) continue;
+		const int u = e->sched.parent[n];
+		edges.push_back(PlaceEdge{n, u == root ? BATCH_ROOT : u, e->left[u] == n ? e->right[u] : e->left[u], {0, 0, 0, 0, 0}});
+	}
+	// the chunks: all node columns and all queries if they fit; else fewer queries, down to a wave of them; else fewer columns;
+	// else, with one column, fewer queries still
+	const bool want_lnl = o.lnl != nullptr;
+	const double room = scratch_room(e, (double)batch_scratch_bytes(e), EngineRoom::MayGrow);
+	const auto fits = [&](size_t cols, size_t queries) {
+		const ScratchPlan p = place_plan(e, L, Q, cols, queries, segments, want_lnl);
+		return p.held(1) || (double)(p.fixed_bytes() + p.item_bytes()) <= room;
+	};
+	const size_t max_cols = std::min<size_t>((size_t)N, BATCH_MAX_CHUNK), max_queries = std::min(Q, PLACE_MAX_CHUNK_QUERIES);
+	const size_t min_queries = std::min(max_queries, PLACE_MIN_CHUNK_QUERIES);
+	size_t cols = max_cols, chunk = max_queries;
+	if (!fits(cols, chunk)) {
+		chunk = largest_that(min_queries, max_queries, [&](size_t x) { return fits(max_cols, x); });
+		if (chunk >= min_queries) chunk = chunk / min_queries * min_queries;
+		else {
+			chunk = min_queries;
+			cols = largest_that(1, max_cols, [&](size_t x) { return fits(x, min_queries); });
+			if (cols < 1) {
+				cols = 1;
+				chunk = largest_that(1, min_queries, [&](size_t x) { return fits(1, x); });
+				if (chunk < 1) {
+					const ScratchPlan one = place_plan(e, L, Q, 1, 1, segments, want_lnl);
+					return fail(PHYAMD_EUNSUPPORTED, "%s: the scratch of one query on one edge (%zu bytes: every internal node's lower and upper partial, and the edge's table) does not fit the memory budget",
+					            call.name, one.fixed_bytes() + one.item_bytes());
+				}
+			}
+		}
+	}
+	const ScratchPlan plan = place_plan(e, L, Q, cols, chunk, segments, want_lnl);
+	if (T > 2) {
+		if ((rc = launch_nni_walk(e, plan, lengths, true))) return rc;
+	} else {  // two tips: both edges hang off the root, no partial is read and nothing is walked
+		if ((rc = ensure_batch_scratch(e, 1, plan))) return rc;
+		HIP_TRY(hipMemcpyAsync(e->d_nni_len, lengths.data(), sizeof(double) * lengths.size(), hipMemcpyHostToDevice, e->stream));
+		launch_batch_matrices(e, 1, e->d_lengths, nullptr, e->d_batch_mats);
+		launch_batch_matrices(e, 3, e->d_nni_len, nullptr, e->d_nni_mats);
+	}
+	HIP_TRY(hipMemcpyAsync(e->d_place_pend_len, o.pendant, sizeof(double) * L, hipMemcpyHostToDevice, e->stream));
+	hipLaunchKernelGGL(k_batch_matrices, dim3((unsigned)((L * C * 16 + 255) / 256)), dim3(256), 0, e->stream, C, (int)L, 1, e->d_model, e->d_rates, e->d_place_pend_len.get(), -1,
+	                   (const int32_t *)nullptr, e->d_place_pend.get());
+	HIP_TRY(hipMemcpyAsync(e->d_place_edges, edges.data(), sizeof(PlaceEdge) * edges.size(), hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipGetLastError());
+	const bool want_best = o.best_node != nullptr;
+	for (size_t first_node = 0; first_node < (size_t)N; first_node += cols) {
+		const size_t ncols = std::min(cols, (size_t)N - first_node);
+		const bool holds_root = (size_t)root >= first_node && (size_t)root < first_node + ncols;
+		const size_t first_edge = first_node <= (size_t)root ? first_node : first_node - 1, E = ncols - (holds_root ? 1 : 0);
+		if (E > 0) {
+			const PlaceTableArgs ta{e->d_place_edges.get() + first_edge, T, N, P, C, nblk, (int)L, e->d_tipmask, e->d_freqs, e->d_props, e->d_weights, e->d_batch_mats, e->d_nni_mats,
+			                        e->d_place_pend, e->d_batch_lower, e->d_batch_upper, e->d_place_table};
+			hipLaunchKernelGGL(k_place_table4, dim3(nblk, (unsigned)E), dim3(WAVE, C), 0, e->stream, ta);
+		}
+		prof.query_chunks = 0;
+		for (size_t first = 0; first < Q; first += chunk) {
+			const size_t n = std::min(chunk, Q - first);
+			if (E > 0) {
+				HIP_TRY(hipMemcpyAsync(e->d_place_raw, o.masks + first * (size_t)P, n * (size_t)P, hipMemcpyHostToDevice, e->stream));
+				const int groups = Ppad / 8;
+				hipLaunchKernelGGL(k_place_masks, dim3((unsigned)(((size_t)groups * n + 255) / 256)), dim3(256), 0, e->stream, (int)n, P, groups, e->d_place_raw.get(),
+				                   e->d_place_packed.get());
+				const unsigned lanes = (unsigned)std::min<size_t>((n + WAVE - 1) / WAVE * WAVE, PLACE_MAX_QUERIES);
+				const PlaceScoreArgs sa{e->d_place_table, e->d_place_packed, e->d_place_slab, (int)E, (int)n, Ppad, (int)segments, (int)L};
+				hipLaunchKernelGGL(k_place_score4, dim3((unsigned)((n + lanes - 1) / lanes), (unsigned)((E + PLACE_EDGES - 1) / PLACE_EDGES), (unsigned)(segments * L)), dim3(lanes), 0,
+				                   e->stream, sa);
+			}
+			const PlaceFinishArgs fa{e->d_place_slab, want_lnl ? e->d_place_out.get() : nullptr, want_best ? e->d_place_best_lnl.get() : nullptr, e->d_place_best_node,
+			                         (int)E, (int)n, (int)segments, (int)L, (int)ncols, (int)first_node, (int)first_edge, root, (int)first, (int)Q, first_node > 0 ? 1 : 0};
+			hipLaunchKernelGGL(k_place_finish, dim3((unsigned)((L * n + 255) / 256)), dim3(256), 0, e->stream, fa);
+			HIP_TRY(hipGetLastError());
+			for (size_t l = 0; l < L && want_lnl; l++) {  // out [L][n][ncols] into lnl [L][Q][N] at (l, first, first_node)
+				double *dst = o.lnl + (l * Q + first) * N + first_node;
+				const double *src = e->d_place_out.get() + l * n * ncols;
+				if (ncols == (size_t)N) HIP_TRY(hipMemcpyAsync(dst, src, sizeof(double) * n * N, hipMemcpyDeviceToHost, e->stream));
+				else HIP_TRY(hipMemcpy2DAsync(dst, sizeof(double) * N, src, sizeof(double) * ncols, sizeof(double) * ncols, n, hipMemcpyDeviceToHost, e->stream));
+			}
+			HIP_TRY(hipStreamSynchronize(e->stream));  // (the next chunk writes the same arrays; also covers `lengths` and `edges`)
+			prof.query_chunks++;
+		}
+		prof.edge_chunks++;
+	}
+	if (want_best) {
+		HIP_TRY(hipMemcpyAsync(o.best_node, e->d_place_best_node, sizeof(int32_t) * L * Q, hipMemcpyDeviceToHost, e->stream));
+		if (o.best_lnl) HIP_TRY(hipMemcpyAsync(o.best_lnl, e->d_place_best_lnl, sizeof(double) * L * Q, hipMemcpyDeviceToHost, e->stream));
+		HIP_TRY(hipStreamSynchronize(e->stream));
+	}
+	return PHYAMD_OK;
+}
+
+int shard_placement(Shard *e, int flags, const PlacementArgs &o) {
+	CHECK_ENGINE(e);
+	phyamd_placement_profile start{};
+	start.queries = o.queries, start.lengths = o.lengths;
+	return profiled_call(e, &Shard::place_prof, start, [&](phyamd_placement_profile &prof) { return run_placement(e, flags, o, prof); });
 }
 
 // ---- per-pattern posteriors (phyamd_state_posteriors, phyamd_site_rate_posteriors) ---------------------------------------------

@@ -222,7 +222,7 @@ struct Shard {
 	DeviceArray<BatchOp> d_batch_item_ops{&batch_mem};  // [item][post-order T - 1 | pre-order T - 1]
 	DeviceArray<int32_t> d_batch_roots{&batch_mem};     // [item]
 	// what the scratch holds: every call describes what it needs as a ScratchPlan (phyamd_queries.inc: batch_plan, reweight_plan,
-	// nni_base_plan with nni_plan and cbopt_plan, blopt_plan, spr_plan with tripod_plan, pairdist_plan, bhess_plan, sitelnl_plan) and gets at least that, so a call of one kind
+	// nni_base_plan with nni_plan and cbopt_plan, blopt_plan, spr_plan with tripod_plan, pairdist_plan, place_plan, bhess_plan, sitelnl_plan) and gets at least that, so a call of one kind
 	// never runs in the scratch of another with too few upper slots or without its lists.  batch_held: the plan the arrays were last
 	// allocated by, for batch_items items (the Hessian's arrays, grown beside it, are judged by their sizes alone)
 	ScratchPlan batch_held;
@@ -286,6 +286,20 @@ struct Shard {
 	DeviceArray<double> d_pairdist_out{&batch_mem};      // [pair][t*, lnL, d1, d2]
 	DeviceArray<int32_t> d_pairdist_iter{&batch_mem};    // [pair]
 	phyamd_distance_profile dist_prof{};
+	// phyamd_placement_log_likelihoods (phyamd_place4.inc) runs the NNI call's walk (the split lengths go through d_nni_len, their
+	// matrices through d_nni_mats) and adds to the group: the pendant lengths and their matrices, the edges, every query's best edge
+	// so far, and per chunk of node columns and of queries the table, the caller's mask rows and their packed form, the slab and
+	// the result
+	DeviceArray<double> d_place_pend_len{&batch_mem}, d_place_pend{&batch_mem};  // [L], [L][C][16]
+	DeviceArray<PlaceEdge> d_place_edges{&batch_mem};              // [N - 1]: the non-root nodes in node order
+	DeviceArray<double> d_place_best_lnl{&batch_mem};              // [L][queries]
+	DeviceArray<int32_t> d_place_best_node{&batch_mem};            // [L][queries]
+	DeviceArray<double> d_place_table{&batch_mem};                 // [L][edges of the chunk][blocks * 64][16]
+	DeviceArray<uint8_t> d_place_raw{&batch_mem};                  // [queries of the chunk][P]
+	DeviceArray<unsigned long long> d_place_packed{&batch_mem};    // [blocks * 8][queries of the chunk]: eight patterns' masks per word
+	DeviceArray<double> d_place_slab{&batch_mem};                  // [segments][L][edges of the chunk][queries of the chunk]
+	DeviceArray<double> d_place_out{&batch_mem};                   // [L][queries of the chunk][node columns of the chunk]
+	phyamd_placement_profile place_prof{};
 	// phyamd_state_posteriors / phyamd_site_rate_posteriors (phyamd_post.inc): the rows of a chunk, their staged results -- [rows][P][S]
 	// posteriors and [rows][P] states, or [P][C] + [P] site rates -- and, 20 / 60 / 61 states, each row's own partial p_n (true_lower_gen).
 	// On demand, like d_branch: the calls read what the keep-partials gradient left and have no entry in the record above

@@ -443,6 +443,38 @@ class Engine:
         self._check(self._lib.phyamd_get_distance_profile(self._h, C.byref(p)))
         return {k: getattr(p, k) for k, _ in p._fields_}
 
+    def placement_log_likelihoods(self, masks, pendant, split=0.5, want_lnl=True, want_best=True, flags=0):
+        """Query sequences that are not among the engine's taxa, each placed on every edge of the engine's tree, on the device:
+        (lnl [lengths, queries, N], best_node [lengths, queries] int32, best_lnl [lengths, queries]); what is not wanted is None.
+        masks [queries, P] uint8 holds a 4-bit state mask 1..15 per query and pattern (bit s = state s, 15 a gap:
+        physher_amd.placement.masks_from_states) OVER THE ENGINE'S OWN PATTERNS -- compress the reference and the queries jointly,
+        or not at all.  pendant [lengths] > 0.  Column n places the query on the branch above node n: a new node takes n's place
+        under n's parent, with the children n (branch split * t_n) and the query (branch pendant[i]), on a branch of
+        (1 - split) * t_n; NaN in the root's column.  best_node is the smallest node id with the largest lnL, formed on the device:
+        with want_lnl=False only the best edges come back.  lnL only, at those lengths; -inf in band where it underflows.
+        The engine's tree, lengths and partials stay.  No fallback: EngineError where nni_log_likelihoods refuses, and on a sharded
+        handle."""
+        m = np.ascontiguousarray(masks, dtype=np.uint8)
+        if m.ndim != 2 or m.shape[1] != self.P:
+            raise ValueError(f"masks must be [queries, {self.P}] (got {m.shape})")
+        pd = np.ascontiguousarray(np.atleast_1d(pendant), dtype=np.float64)
+        if pd.ndim != 1:
+            raise ValueError(f"pendant must be one-dimensional (got {pd.shape})")
+        Q, L = m.shape[0], len(pd)
+        lnl = np.empty((L, Q, self.N)) if want_lnl else None
+        node = np.empty((L, Q), dtype=np.int32) if want_best else None
+        best = np.empty((L, Q)) if want_best else None
+        opt = lambda a: None if a is None else _ptr(a)
+        self._check(self._lib.phyamd_placement_log_likelihoods(self._h, flags, Q, _ptr(m), L, _ptr(pd), split, opt(lnl), opt(node), opt(best)))
+        return lnl, node, best
+
+    def placement_profile(self):
+        """Of the last placement_log_likelihoods: queries, lengths, edges, edge_chunks, query_chunks (per edge chunk), scratch_bytes,
+        ms."""
+        p = _lib.PlacementProfile()
+        self._check(self._lib.phyamd_get_placement_profile(self._h, C.byref(p)))
+        return {k: getattr(p, k) for k, _ in p._fields_}
+
     def state_posteriors(self, nodes=None, want_posteriors=True, want_states=True):
         """Marginal ancestral reconstruction on the device: (posteriors [count, P, S] float64, states [count, P] uint8), either None
         when not wanted.  Row i is node nodes[i] (None: every node, row i is node i; tips and the root included, duplicates
