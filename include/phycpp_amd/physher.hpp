@@ -363,6 +363,16 @@ class TreeLikelihoodInterface : public CallableModelInterface {
 	// as for NNILogLikelihoods.  The tree model and this object's own state are unchanged.
 	void PlacementLogLikelihoods(const uint8_t *masks, int queries, const double *pendant, int lengths, double split, double *logLikelihoods, int32_t *bestNodes,
 	                             double *bestLogLikelihoods);
+	// The three branches around chosen placements optimised at once (one phyamd_placement_optimize call; see include/physher_amd.h
+	// for the rule): masks and queries as for PlacementLogLikelihoods; candidates [count][2] holds (query, node) pairs by the tree's
+	// node ids; pendantStart [count] may be null (0.1); split as there; branches marks what is optimised (bit 0: the node's branch
+	// below the new node, bit 1: the query's, bit 2: the new node's; 7: all three).  lengths [count][3] holds those three in that
+	// order, logLikelihoods [count]; initialLogLikelihoods [count] and passes [count] (negative: the passes ran out, or lnL was not
+	// finite) may be null.  The bounds, tolerances and counts are SPROptimize's.  Lengths are the engine's branch lengths, as for
+	// NNILogLikelihoods.  The tree model and this object's own state are unchanged.
+	void PlacementOptimize(const uint8_t *masks, int queries, const int32_t *candidates, int count, const double *pendantStart, double split, int branches, double lower,
+	                       double upper, double tolerance, int maxIterations, double lnlTolerance, int maxPasses, double *lengths, double *logLikelihoods,
+	                       double *initialLogLikelihoods, int32_t *passes);
 	// Beyond the reference surface: marginal ancestral reconstruction of `count` nodes of the tree model's tree at once (one
 	// phyamd_state_posteriors call; see include/physher_amd.h for the definition): posteriors [count][patterns][states] and states
 	// [count][patterns] by the tree's node ids, row i the node nodes[i] (null: count = 2T-1 and row i is node i; tips and the

@@ -865,6 +865,57 @@ int phyamd_placement_log_likelihoods(phyamd_engine *e, int flags, int32_t querie
 typedef struct { int32_t queries, lengths, edges, edge_chunks, query_chunks; int64_t scratch_bytes; double ms; } phyamd_placement_profile;
 int phyamd_get_placement_profile(phyamd_engine *e, phyamd_placement_profile *out);
 
+/* --- the three branches around chosen placements --- */
+/* The three branches that meet at the insertion point of `count` chosen placements optimised in one call: what a placement tool
+ * (EPA-ng's branch triplet, pplacer, RAxML-EPA) or a stepwise addition runs on the few best edges per query after
+ * phyamd_placement_log_likelihoods has scored all of them, and where its likelihood weight ratios and pendant lengths come from.
+ * queries and masks are phyamd_placement_log_likelihoods'.  Candidate i is the query q = candidates[i][0] on the edge
+ * n = candidates[i][1], a non-root node.  Per candidate lengths holds (distal t_n, pendant t_x, proximal t_z), lnl the
+ * log-likelihood there, initial_lnl that of the start and passes the pass count.  initial_lnl and passes may be NULL.  Duplicates
+ * among the candidates are allowed.
+ * THE RULE.  The tree of candidate i is the placed tree of phyamd_placement_log_likelihoods' definition: T + 1 tips, a new node z in
+ * n's place with the left child n and the right child x (the query).  The start is t_n = split t_n (distal),
+ * t_x = pendant_start[i] (pendant; pendant_start NULL: 0.1) and t_z = (1 - split) t_n (proximal), t_n on the right sides the engine's.
+ * Entry i is, by definition, what phyamd_optimize_branch_lengths returns for ONE item with that tree and those start lengths whose
+ * optimise marks the nodes chosen by `branches`: bit 0 n (distal), bit 1 x (pendant), bit 2 z (proximal).  A pass visits the marked
+ * ones in the order n, x, z (z's left child, its right child, z).  The visit, its safeguarded Newton iteration and its acceptance,
+ * the stop test after a pass (passes = k, or -max_passes), the end in band at an lnL that is not finite (lengths the state before
+ * that visit, lnl the value, passes the negated pass index) and how lnL and the derivatives are formed are phyamd_spr_optimize's
+ * (see there), with (t_n, t_x, t_z) for its (t_w, t_p, t_u).  A branch that is not marked is never clamped or changed and comes back
+ * as its start value, bit for bit.  initial_lnl is lnL at the start: phyamd_placement_log_likelihoods' entry at that pendant length
+ * and split, up to rounding.  branches = 7 is the EPA-ng / optimize_tripod form; branches = 2 optimises the pendant length alone.
+ * Everything happens on the device after phyamd_placement_log_likelihoods' one walk of the engine's tree: the three messages that
+ * meet at z -- the query's mask vector, n's lower partial and what n's edge sees from above -- depend on none of the three lengths
+ * and only the first on the query, so the third is formed once per distinct edge, and a candidate's whole iteration runs in one
+ * workgroup without a further walk, matrix launch or host round trip.  The engine -- its topology, lengths, partials -- is unchanged
+ * and later evaluations return the bits they would have returned without the call; two calls return identical bits; a candidate's
+ * bits do not depend on count, its position, the other candidates or queries, the chunks the candidates ran in, the optional
+ * outputs or what the batch scratch held.  Nothing is added with atomics.  The engine is never switched to rescaling.  The scratch
+ * is the batch scratch's: phyamd_nni_log_likelihoods' walk, per candidate C x 4 doubles per padded pattern and per distinct edge of
+ * a chunk as much again; candidates that do not fit the memory cap together run in chunks.  There is no fallback path:
+ * PHYAMD_EUNSUPPORTED, naming the condition, under phyamd_placement_log_likelihoods' conditions (not 4 states, more than 8
+ * categories, an engine that is rescaling, tiled patterns, a tip cell with an empty state mask, explicit node matrices, a handle
+ * sharded over several devices, flags other than 0) and when the scratch of one candidate does not fit the memory cap.
+ * PHYAMD_EINVAL, naming the function and the argument: null masks, candidates, lengths or lnl; queries < 1 or count < 1; a
+ * candidate's query outside 0..queries-1 (with its index); branches outside 1..7; a split outside [0, 1]; a start that is not finite
+ * and > 0; phyamd_spr_optimize's conditions on the bounds, tolerances and counts; null engine; a candidate's node outside 0..2T-2
+ * or equal to the root (with its index); a mask byte of 0 or above 15 (the query and the pattern are named); no eigen system.  The
+ * argument checks come before the handle is looked at. */
+int phyamd_placement_optimize(phyamd_engine *e, int flags, int32_t queries,
+                              const uint8_t *masks /* [queries][P], 1..15, as phyamd_placement_log_likelihoods */,
+                              int32_t count, const int32_t *candidates /* [count][2]: (query, node) */,
+                              const double *pendant_start /* [count] or NULL: 0.1 */, double split,
+                              int32_t branches /* bit 0: distal (n's), bit 1: pendant (the query's), bit 2: proximal (z's); 1..7 */,
+                              double lower, double upper, double tolerance, int32_t max_iterations,
+                              double lnl_tolerance, int32_t max_passes,
+                              double *lengths /* [count][3]: distal, pendant, proximal */, double *lnl /* [count] */,
+                              double *initial_lnl /* [count] or NULL */, int32_t *passes /* [count] or NULL */);
+/* of the last phyamd_placement_optimize: candidates asked for, distinct edges among them, chunks of candidates they ran in, visits
+ * made and proposals made over all of them, bytes of batch scratch the engine holds (see phyamd_batch_profile), wall time of the
+ * call */
+typedef struct { int32_t candidates, edges, chunks; int64_t visits, iterations, scratch_bytes; double ms; } phyamd_placement_optimize_profile;
+int phyamd_get_placement_optimize_profile(phyamd_engine *e, phyamd_placement_optimize_profile *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,6 +67,11 @@ class PlacementProfile(C.Structure):
                 ("scratch_bytes", C.c_int64), ("ms", C.c_double)]
 
 
+class PlacementOptimizeProfile(C.Structure):
+    _fields_ = [("candidates", C.c_int32), ("edges", C.c_int32), ("chunks", C.c_int32), ("visits", C.c_int64), ("iterations", C.c_int64),
+                ("scratch_bytes", C.c_int64), ("ms", C.c_double)]
+
+
 class HessianProfile(C.Structure):
     _fields_ = [("chunks", C.c_int32), ("pairs", C.c_int64), ("scratch_bytes", C.c_int64), ("ms", C.c_double)]
 
@@ -156,6 +161,9 @@ SYMBOLS = [
     ("phyamd_get_distance_profile", C.c_int, [_P, C.POINTER(DistanceProfile)]),
     ("phyamd_placement_log_likelihoods", C.c_int, [_P, C.c_int, C.c_int32, _P, C.c_int32, _P, C.c_double, _P, _P, _P]),
     ("phyamd_get_placement_profile", C.c_int, [_P, C.POINTER(PlacementProfile)]),
+    ("phyamd_placement_optimize", C.c_int, [_P, C.c_int, C.c_int32, _P, C.c_int32, _P, _P, C.c_double, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32,
+                                            C.c_double, C.c_int32, _P, _P, _P, _P]),
+    ("phyamd_get_placement_optimize_profile", C.c_int, [_P, C.POINTER(PlacementOptimizeProfile)]),
     ("phyamd_state_posteriors", C.c_int, [_P, C.c_int, C.c_int32, _P, _P, _P]),
     ("phyamd_site_rate_posteriors", C.c_int, [_P, _P, _P]),
     ("phyamd_branch_hessian", C.c_int, [_P, C.c_int, _P, _P, _P]),

@@ -988,6 +988,15 @@ void TreeLikelihoodInterface::PlacementLogLikelihoods(const uint8_t *masks, int 
 	phyamd::check(phyamd_placement_log_likelihoods(impl_->engine, 0, queries, masks, lengths, pendant, split, logLikelihoods, bestNodes, bestLogLikelihoods));
 }
 
+void TreeLikelihoodInterface::PlacementOptimize(const uint8_t *masks, int queries, const int32_t *candidates, int count, const double *pendantStart, double split, int branches,
+                                                double lower, double upper, double tolerance, int maxIterations, double lnlTolerance, int maxPasses, double *lengths,
+                                                double *logLikelihoods, double *initialLogLikelihoods, int32_t *passes) {
+	if (!lengths || !logLikelihoods) throw Error("null lengths or logLikelihoods");
+	Sync();
+	phyamd::check(phyamd_placement_optimize(impl_->engine, 0, queries, masks, count, candidates, pendantStart, split, branches, lower, upper, tolerance, maxIterations,
+	                                        lnlTolerance, maxPasses, lengths, logLikelihoods, initialLogLikelihoods, passes));
+}
+
 size_t TreeLikelihoodInterface::StateCount() const { return (size_t)impl_->S; }
 size_t TreeLikelihoodInterface::CategoryCount() const { return (size_t)siteModel_->GetModel()->cat_count; }
 

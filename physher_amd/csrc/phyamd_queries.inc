@@ -1476,6 +1476,154 @@ int shard_placement(Shard *e, int flags, const PlacementArgs &o) {
 	return profiled_call(e, &Shard::place_prof, start, [&](phyamd_placement_profile &prof) { return run_placement(e, flags, o, prof); });
 }
 
+// ---- the three branches around chosen placements, optimised (phyamd_placement_optimize) ------------------------------------------
+
+struct PlacementOptimizeArgs {
+	int32_t queries;
+	const uint8_t *masks;       // [queries][P], validated (phyamd_placement_optimize)
+	int32_t count;
+	const int32_t *candidates;  // [count][2]: (query, node), the queries validated
+	const double *pendant_start;
+	double split;
+	int32_t branches;
+	double lower, upper, tolerance;
+	int32_t max_iterations;
+	double lnl_tolerance;
+	int32_t max_passes;
+	double *lengths, *lnl, *initial_lnl;
+	int32_t *passes;
+};
+
+// the NNI walk's (nni_base_plan), and for the `chunk` candidates that run at once -- whatever their edges and queries: as many of
+// each as there can be -- the distinct edges and pi o U of each, the distinct queries' mask rows, the candidates, their starts,
+// coefficients, results and status words
+ScratchPlan qopt_plan(Shard *e, size_t chunk) {
+	const size_t D = sizeof(double), C = (size_t)e->C, plane = ((size_t)e->P + WAVE - 1) / WAVE * WAVE * 4;
+	const size_t edges = std::min(chunk, (size_t)e->N - 1);
+	ScratchPlan p = nni_base_plan(e);
+	p.add(e->d_qopt_edges, 0, sizeof(PlaceEdge) * edges);
+	p.add(e->d_qopt_fU, 0, D * edges * C * plane);
+	p.add(e->d_qopt_masks, 0, chunk * (size_t)e->P);
+	p.add(e->d_qopt_cands, 0, sizeof(QoptCand) * chunk);
+	p.add(e->d_qopt_start, 0, D * chunk * 3);
+	p.add(e->d_qopt_K, 0, D * chunk * C * plane);
+	p.add(e->d_qopt_res, 0, D * chunk * 5);
+	p.add(e->d_qopt_status, 0, sizeof(int32_t) * chunk * QOPT_STATUS);
+	return p;
+}
+
+// one walk of the engine's tree with every upper parked, then chunk by chunk of the candidates sorted by edge: pi o U of the chunk's
+// edges and one workgroup per candidate that runs its whole rule.  Reads the engine's inputs and writes only the batch scratch:
+// nothing in Shard::state changes
+int run_placement_optimize(Shard *e, int flags, const PlacementOptimizeArgs &o, phyamd_placement_optimize_profile &prof) {
+	static const NniWalkCall call{"phyamd_placement_optimize", "", "", "the likelihood in a branch length is"};
+	int rc;
+	std::vector<double> lengths;
+	if ((rc = check_ready(e))) return fail(rc, "%s: the engine is not ready: %s", call.name, std::string(g_last_error).c_str());
+	if ((rc = check_nni_walk(e, call, flags, nullptr, lengths))) return rc;
+	const int T = e->T, N = e->N, C = e->C, P = e->P, root = e->root;
+	const size_t count = (size_t)o.count;
+	for (size_t i = 0; i < count; i++)
+		if (o.candidates[2 * i + 1] == root)
+			return fail(PHYAMD_EINVAL, "%s: candidates[%zu] = (%d, %d): the root (node %d) has no branch to place a query on", call.name, i, o.candidates[2 * i], root, root);
+	const int nblk = (P + WAVE - 1) / WAVE;
+	// the candidates by edge, then query, then position: a chunk's candidates of one edge read the same pi o U
+	std::vector<int32_t> order(count);
+	for (size_t i = 0; i < count; i++) order[i] = (int32_t)i;
+	std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
+		const int32_t *ca = o.candidates + 2 * (size_t)a, *cb = o.candidates + 2 * (size_t)b;
+		return ca[1] != cb[1] ? ca[1] < cb[1] : ca[0] != cb[0] ? ca[0] < cb[0] : a < b;
+	});
+	prof.edges = 1;
+	for (size_t i = 1; i < count; i++) prof.edges += o.candidates[2 * (size_t)order[i] + 1] != o.candidates[2 * (size_t)order[i - 1] + 1];
+	// the chunk: all candidates (at most gridDim.x's) if the scratch holds as much or has room for it, else what fits beside the walk
+	const size_t want = std::min<size_t>(count, BATCH_MAX_CHUNK);
+	size_t chunk = want;
+	if (batch_items_held(e, qopt_plan(e, want)) < 1) {
+		const double room = scratch_room(e, (double)batch_scratch_bytes(e), EngineRoom::MayGrow);
+		chunk = largest_that(1, want, [&](size_t x) {
+			const ScratchPlan p = qopt_plan(e, x);
+			return (double)(p.fixed_bytes() + p.item_bytes()) <= room;
+		});
+		if (chunk < 1) {
+			const ScratchPlan one = qopt_plan(e, 1);
+			return fail(PHYAMD_EUNSUPPORTED, "%s: the scratch of one candidate (%zu bytes: every internal node's lower and upper partial, and two planes) does not fit the memory budget",
+			            call.name, one.fixed_bytes() + one.item_bytes());
+		}
+	}
+	const ScratchPlan plan = qopt_plan(e, chunk);
+	if (T > 2) {
+		if ((rc = launch_nni_walk(e, plan, lengths, false))) return rc;
+	} else {  // two tips: both edges hang off the root, no partial is read and nothing is walked
+		if ((rc = ensure_batch_scratch(e, 1, plan))) return rc;
+		launch_batch_matrices(e, 1, e->d_lengths, nullptr, e->d_batch_mats);
+	}
+	HIP_TRY(hipGetLastError());
+	std::vector<PlaceEdge> edges;
+	std::vector<QoptCand> cands;
+	std::vector<double> start, out;
+	std::vector<uint8_t> rows;
+	std::vector<int32_t> row_of((size_t)o.queries), status;
+	for (size_t first = 0; first < count; first += chunk) {
+		const size_t n = std::min(chunk, count - first);
+		edges.clear(), cands.clear(), start.clear(), rows.clear();
+		std::fill(row_of.begin(), row_of.end(), -1);
+		for (size_t i = 0; i < n; i++) {
+			const size_t at = (size_t)order[first + i];
+			const int q = o.candidates[2 * at], node = o.candidates[2 * at + 1];
+			if (edges.empty() || edges.back().n != node) {
+				const int u = e->sched.parent[node];
+				edges.push_back(PlaceEdge{node, u == root ? BATCH_ROOT : u, e->left[u] == node ? e->right[u] : e->left[u], {0, 0, 0, 0, 0}});
+			}
+			if (row_of[q] < 0) {
+				row_of[q] = (int32_t)(rows.size() / (size_t)P);
+				rows.insert(rows.end(), o.masks + (size_t)q * P, o.masks + (size_t)(q + 1) * P);
+			}
+			cands.push_back(QoptCand{node, (int32_t)edges.size() - 1, row_of[q], {0, 0, 0, 0, 0}});
+			start.push_back(o.split * e->lengths[node]);
+			start.push_back(o.pendant_start ? o.pendant_start[at] : 0.1);
+			start.push_back((1.0 - o.split) * e->lengths[node]);
+		}
+		HIP_TRY(hipMemcpyAsync(e->d_qopt_edges, edges.data(), sizeof(PlaceEdge) * edges.size(), hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_qopt_masks, rows.data(), rows.size(), hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_qopt_cands, cands.data(), sizeof(QoptCand) * n, hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_qopt_start, start.data(), sizeof(double) * start.size(), hipMemcpyHostToDevice, e->stream));
+		const QoptUpperArgs ua{e->d_qopt_edges, T, N, P, C, nblk, e->d_tipmask, e->d_freqs, e->d_batch_mats, e->d_batch_lower, e->d_batch_upper, e->d_qopt_fU};
+		hipLaunchKernelGGL(k_qopt_upper4, dim3(nblk, (unsigned)edges.size()), dim3(WAVE, C), 0, e->stream, ua);
+		QoptSolveArgs s{};
+		s.cands = e->d_qopt_cands, s.T = T, s.P = P, s.C = C, s.nblk = nblk, s.branches = o.branches, s.max_iterations = o.max_iterations, s.max_passes = o.max_passes;
+		s.lower = o.lower, s.upper = o.upper, s.tolerance = o.tolerance, s.lnl_tolerance = o.lnl_tolerance;
+		s.tipmask = e->d_tipmask, s.masks = e->d_qopt_masks, s.props = e->d_props, s.model = e->d_model, s.rates = e->d_rates, s.weights = e->d_weights;
+		s.start = e->d_qopt_start, s.lower_all = e->d_batch_lower, s.fU = e->d_qopt_fU, s.K = e->d_qopt_K, s.out = e->d_qopt_res, s.status = e->d_qopt_status;
+		hipLaunchKernelGGL(k_qopt_solve4, dim3((unsigned)n), dim3(CBOPT_THREADS), 0, e->stream, s);
+		HIP_TRY(hipGetLastError());
+		out.resize(n * 5);
+		status.resize(n * QOPT_STATUS);
+		HIP_TRY(hipMemcpyAsync(out.data(), e->d_qopt_res, sizeof(double) * out.size(), hipMemcpyDeviceToHost, e->stream));
+		HIP_TRY(hipMemcpyAsync(status.data(), e->d_qopt_status, sizeof(int32_t) * status.size(), hipMemcpyDeviceToHost, e->stream));
+		HIP_TRY(hipStreamSynchronize(e->stream));  // (the next chunk writes the same arrays; also covers `lengths` and the lists)
+		for (size_t i = 0; i < n; i++) {
+			const size_t to = (size_t)order[first + i];
+			const double *v = &out[i * 5];
+			std::copy(v, v + 3, o.lengths + to * 3);
+			o.lnl[to] = v[3];
+			if (o.initial_lnl) o.initial_lnl[to] = v[4];
+			if (o.passes) o.passes[to] = status[i * QOPT_STATUS + QOPT_PASSES];
+			prof.visits += status[i * QOPT_STATUS + QOPT_VISITS];
+			prof.iterations += status[i * QOPT_STATUS + QOPT_ITERATIONS];
+		}
+		prof.chunks++;
+	}
+	return PHYAMD_OK;
+}
+
+int shard_placement_optimize(Shard *e, int flags, const PlacementOptimizeArgs &o) {
+	CHECK_ENGINE(e);
+	phyamd_placement_optimize_profile start{};
+	start.candidates = o.count;
+	return profiled_call(e, &Shard::qopt_prof, start, [&](phyamd_placement_optimize_profile &prof) { return run_placement_optimize(e, flags, o, prof); });
+}
+
 // ---- per-pattern posteriors (phyamd_state_posteriors, phyamd_site_rate_posteriors) ---------------------------------------------
 
 // The staging arrays of the two calls, and rows of a chunk that fit beside the engine.  per_row[a]: bytes a row takes in array a

@@ -222,7 +222,7 @@ struct Shard {
 	DeviceArray<BatchOp> d_batch_item_ops{&batch_mem};  // [item][post-order T - 1 | pre-order T - 1]
 	DeviceArray<int32_t> d_batch_roots{&batch_mem};     // [item]
 	// what the scratch holds: every call describes what it needs as a ScratchPlan (phyamd_queries.inc: batch_plan, reweight_plan,
-	// nni_base_plan with nni_plan and cbopt_plan, blopt_plan, spr_plan with tripod_plan, pairdist_plan, place_plan, bhess_plan, sitelnl_plan) and gets at least that, so a call of one kind
+	// nni_base_plan with nni_plan and cbopt_plan, blopt_plan, spr_plan with tripod_plan, pairdist_plan, place_plan, qopt_plan, bhess_plan, sitelnl_plan) and gets at least that, so a call of one kind
 	// never runs in the scratch of another with too few upper slots or without its lists.  batch_held: the plan the arrays were last
 	// allocated by, for batch_items items (the Hessian's arrays, grown beside it, are judged by their sizes alone)
 	ScratchPlan batch_held;
@@ -300,6 +300,18 @@ struct Shard {
 	DeviceArray<double> d_place_slab{&batch_mem};                  // [segments][L][edges of the chunk][queries of the chunk]
 	DeviceArray<double> d_place_out{&batch_mem};                   // [L][queries of the chunk][node columns of the chunk]
 	phyamd_placement_profile place_prof{};
+	// phyamd_placement_optimize (phyamd_qopt4.inc) runs the same walk and adds to the group, per chunk of candidates sorted by edge:
+	// the chunk's distinct edges and pi o U of each, its distinct queries' mask rows, the candidates and their starts, the
+	// coefficients of the branch being visited, the results and the status words
+	DeviceArray<PlaceEdge> d_qopt_edges{&batch_mem};    // [edges of the chunk]
+	DeviceArray<double> d_qopt_fU{&batch_mem};          // [edges of the chunk][C][blocks * 64][4]
+	DeviceArray<uint8_t> d_qopt_masks{&batch_mem};      // [queries of the chunk][P]
+	DeviceArray<QoptCand> d_qopt_cands{&batch_mem};     // [candidate]
+	DeviceArray<double> d_qopt_start{&batch_mem};       // [candidate][t_n, t_x, t_z]
+	DeviceArray<double> d_qopt_K{&batch_mem};           // [candidate][C][4][blocks * 64]
+	DeviceArray<double> d_qopt_res{&batch_mem};         // [candidate][t_n, t_x, t_z, lnl, initial_lnl]
+	DeviceArray<int32_t> d_qopt_status{&batch_mem};     // [candidate][QOPT_STATUS]
+	phyamd_placement_optimize_profile qopt_prof{};
 	// phyamd_state_posteriors / phyamd_site_rate_posteriors (phyamd_post.inc): the rows of a chunk, their staged results -- [rows][P][S]
 	// posteriors and [rows][P] states, or [P][C] + [P] site rates -- and, 20 / 60 / 61 states, each row's own partial p_n (true_lower_gen).
 	// On demand, like d_branch: the calls read what the keep-partials gradient left and have no entry in the record above

@@ -475,6 +475,45 @@ class Engine:
         self._check(self._lib.phyamd_get_placement_profile(self._h, C.byref(p)))
         return {k: getattr(p, k) for k, _ in p._fields_}
 
+    def placement_optimize(self, masks, candidates, pendant_start=None, split=0.5, branches=7, lower=1e-8, upper=10.0, tolerance=1e-8, max_iterations=100,
+                           lnl_tolerance=1e-6, max_passes=50, want_initial_lnl=True, want_passes=True, flags=0):
+        """The three branches around chosen placements optimised on the device: (lengths [count, 3], lnl [count], initial_lnl
+        [count], passes [count] int32; the last two None when not wanted).  masks [queries, P] as placement_log_likelihoods takes
+        them; candidates [count, 2] int32 holds (query, node) pairs (physher_amd.placement.top_candidates picks each query's best
+        edges from a placement_log_likelihoods result; duplicates allowed).  lengths holds (distal, pendant, proximal): the branch
+        of node n below the insertion point, the query's and the new node's, from the start (split * t_n, pendant_start[i] or 0.1,
+        (1 - split) * t_n).  An entry is what optimize_branch_lengths returns for the placed tree with the branches of `branches`
+        marked (bit 0 distal, bit 1 pendant, bit 2 proximal; 7: all three, 2: the pendant length alone): a pass visits them in
+        that order by spr_optimize's rule and stop test; a branch that is not marked comes back as its start.  A lnL that is not
+        finite ends an entry in band with passes negative.  The engine's tree, lengths and partials stay.  No fallback:
+        EngineError where placement_log_likelihoods refuses."""
+        m = np.ascontiguousarray(masks, dtype=np.uint8)
+        if m.ndim != 2 or m.shape[1] != self.P:
+            raise ValueError(f"masks must be [queries, {self.P}] (got {m.shape})")
+        cd = np.ascontiguousarray(candidates, dtype=np.int32)
+        if cd.ndim != 2 or cd.shape[1] != 2:
+            raise ValueError(f"candidates must be [count, 2] (got {cd.shape})")
+        count = len(cd)
+        st = None
+        if pendant_start is not None:
+            st = np.ascontiguousarray(pendant_start, dtype=np.float64)
+            if st.shape != (count,):
+                raise ValueError(f"pendant_start must be [{count}] (got {st.shape})")
+        lengths, lnl = np.empty((count, 3)), np.empty(count)
+        lnl0 = np.empty(count) if want_initial_lnl else None
+        passes = np.empty(count, dtype=np.int32) if want_passes else None
+        opt = lambda a: None if a is None else _ptr(a)
+        self._check(self._lib.phyamd_placement_optimize(self._h, flags, m.shape[0], _ptr(m), count, _ptr(cd), opt(st), split, branches, lower, upper, tolerance,
+                                                        max_iterations, lnl_tolerance, max_passes, _ptr(lengths), _ptr(lnl), opt(lnl0), opt(passes)))
+        return lengths, lnl, lnl0, passes
+
+    def placement_optimize_profile(self):
+        """Of the last placement_optimize: candidates, edges (distinct among them), chunks (of candidates), visits and iterations
+        (over all candidates), scratch_bytes, ms."""
+        p = _lib.PlacementOptimizeProfile()
+        self._check(self._lib.phyamd_get_placement_optimize_profile(self._h, C.byref(p)))
+        return {k: getattr(p, k) for k, _ in p._fields_}
+
     def state_posteriors(self, nodes=None, want_posteriors=True, want_states=True):
         """Marginal ancestral reconstruction on the device: (posteriors [count, P, S] float64, states [count, P] uint8), either None
         when not wanted.  Row i is node nodes[i] (None: every node, row i is node i; tips and the root included, duplicates

@@ -1,4 +1,5 @@
-"""NumPy helpers around Engine.placement_log_likelihoods: the masks it takes and what a placement tool makes of its result.
+"""NumPy helpers around Engine.placement_log_likelihoods and Engine.placement_optimize: the masks they take, the candidates the
+second takes from the first's scores, and what a placement tool makes of either result.
 
 A query's masks are 4-bit numbers over the engine's own patterns, bit s = state s (nucleotides in the order A, C, G, T), 15 a gap.
 lnl [..., N] holds a query's log-likelihood on the branch above every node, NaN in the root's column."""
@@ -17,10 +18,45 @@ def masks_from_states(states, state_count=4):
     return np.where(single, np.left_shift(1, np.where(single, states, 0)), 15).astype(np.uint8)
 
 
-def likelihood_weight_ratios(lnl):
+def top_candidates(lnl_or_best, k):
+    """One pendant length's scores [Q, N] (Engine.placement_log_likelihoods' lnl[i]) -> the candidates [count, 2] int32 of
+    Engine.placement_optimize: per query its k best edges as (query, node) rows, query after query, the best edge first.  Ties go
+    to the smaller node id; a column of NaN (the root's) is never chosen and neither is a NaN entry; a query with fewer than k
+    usable edges gets as many as it has.  A one-dimensional argument is best_node [Q] of one length: every query's one edge."""
+    a = np.asarray(lnl_or_best)
+    if a.ndim == 1:
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"a one-dimensional argument is best_node: integers (got {a.dtype})")
+        return np.stack([np.arange(len(a)), a], axis=1).astype(np.int32)
+    if a.ndim != 2:
+        raise ValueError(f"scores are [queries, nodes] (got {a.shape})")
+    if k < 1:
+        raise ValueError(f"k must be >= 1 (got {k})")
+    score = np.where(np.isnan(a), -np.inf, a.astype(np.float64))
+    order = np.argsort(-score, axis=1, kind="stable")[:, :k]  # (stable: among equal scores the smaller node id comes first)
+    usable = ~np.isnan(np.take_along_axis(a, order, axis=1))
+    query = np.broadcast_to(np.arange(a.shape[0])[:, None], order.shape)
+    return np.stack([query[usable], order[usable]], axis=1).astype(np.int32)
+
+
+def likelihood_weight_ratios(lnl, queries=None):
     """The likelihood weight ratio of every edge (EPA / pplacer's LWR): exp(lnl) normalised over the edges of each query, a softmax
     over the last axis.  NaN entries (the root's column) and -inf entries (underflow) get 0; a row without any finite entry is all
-    0.  Stable: the row's largest lnL is taken off before exp."""
+    0.  Stable: the row's largest lnL is taken off before exp.
+    queries: lnl [count] is laid out sparsely, as Engine.placement_optimize returns it -- queries [count] holds each entry's query
+    (candidates[:, 0]), in any order -- and the result [count] is normalised over the entries of each query."""
+    if queries is not None:
+        lnl, queries = np.asarray(lnl, dtype=np.float64), np.asarray(queries)
+        if lnl.ndim != 1 or queries.shape != lnl.shape:
+            raise ValueError(f"sparse scores and their queries are both [count] (got {lnl.shape} and {queries.shape})")
+        ids, row = np.unique(queries, return_inverse=True)
+        column = np.zeros(len(lnl), dtype=np.int64)
+        for r in range(len(ids)):
+            at = np.nonzero(row == r)[0]
+            column[at] = np.arange(len(at))
+        dense = np.full((len(ids), int(column.max()) + 1 if len(lnl) else 0), np.nan)
+        dense[row, column] = lnl
+        return likelihood_weight_ratios(dense)[row, column]
     lnl = np.asarray(lnl, dtype=np.float64)
     usable = np.isfinite(lnl)
     if np.any(lnl[~usable] == np.inf):
