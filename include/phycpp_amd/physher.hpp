@@ -353,6 +353,12 @@ class TreeLikelihoodInterface : public CallableModelInterface {
 	// model and this object's own state are unchanged.
 	void PairwiseDistances(const int *pairs, int count, const double *start, double lower, double upper, double tolerance, int maxIterations, double *distances,
 	                       double *logLikelihoods, double *d1, double *d2, int32_t *iterations, double *counts);
+	// The same for a data type of 20 states (one phyamd_pairwise_distances_general call; see include/physher_amd.h for the classes):
+	// counts [count][32][32], if not null, receives the weighted tables of tip-class pairs, and classMembers [32], if not null, one
+	// bit per member state of each class -- the classes of ambiguity sets are numbered by the engine, so classMembers is what
+	// gives counts its meaning.
+	void PairwiseDistancesGeneral(const int *pairs, int count, const double *start, double lower, double upper, double tolerance, int maxIterations, double *distances,
+	                              double *logLikelihoods, double *d1, double *d2, int32_t *iterations, double *counts, uint64_t *classMembers);
 	// Beyond the reference surface: lnL of `queries` sequences that are not among the tree model's taxa, each placed on every edge
 	// of its tree (one phyamd_placement_log_likelihoods call; see include/physher_amd.h for the definition): masks
 	// [queries][patterns] holds a 4-bit state mask 1..15 per query and pattern over THIS OBJECT'S OWN PATTERNS (GetPatternCount(); the

@@ -823,6 +823,32 @@ int phyamd_pairwise_distances(phyamd_engine *e, int flags, int32_t count, const 
  * scratch the engine holds (see phyamd_batch_profile), proposals made over all pairs, wall time of the call */
 typedef struct { int32_t pairs, chunks, segments; int64_t scratch_bytes, iterations; double ms; } phyamd_distance_profile;
 int phyamd_get_distance_profile(phyamd_engine *e, phyamd_distance_profile *out);
+/* phyamd_pairwise_distances for an engine of 20 states (proteins under WAG / LG + Gamma: the classical use of ML distances, where the
+ * reference has Kimura's -log(1 - p - 0.2 p^2) alone): the same pairs, the same likelihood, THE SAME RULE word for word (start 0.1,
+ * the sign convention of iterations, a lnL that is not finite ends the pair in band, identical rows end at lower and saturated pairs
+ * at upper as results) and the same outputs, with the tables over tip CLASSES instead of masks.  A tip cell's class is the code the
+ * engine stores for it: 0..19 the state; 20 unknown (all states: a state code >= 20, or partials that are all 1); 21 + q the
+ * engine's ambiguity set q, the sets numbered in the order in which phyamd_set_tip_partials first met them on this engine.  With m_c
+ * the 0/1 vector of class c, L_k(t) = sum_c w_c sum_a (V^T (pi o m_ci))_a (V^-1 m_cj)_a exp(lambda_a r_c t),
+ * N[ci][cj] = sum_k w_k [class_i[k] = ci][class_j[k] = cj] (32 x 32), S_n[a] as above for a < 20, G[ci][cj][a] = (V^T (pi o m_ci))_a
+ * (V^-1 m_cj)_a, and F_n, lnL, d1 and d2 as above over the bins with N > 0; the bins of class 20 are computed like every other bin.
+ * counts [count][32][32], if given, receives the tables (counts[p][ci][cj]).  class_members [32], if given, receives one bit per
+ * member state of each class: 1 << c for a state, 2^20 - 1 for class 20, the set's members for 21 + q, 0 for a class no set stands
+ * for.  The numbering of the sets is the engine's own, so class_members is what gives counts its meaning (physher_amd/distances.py:
+ * state_counts_general, p_distance_general, kimura_protein).  With distances == NULL and counts given the call only counts, as above.
+ * What the call needs and what it leaves alone are phyamd_pairwise_distances': no topology, no lengths, no partials; a rescaling
+ * engine and any number of categories; segments of 4096 patterns added in order, no atomics, the engine unchanged, identical bits
+ * from two calls, a pair's bits independent of the other pairs, its position, the grouping of pairs into waves, the chunks and the
+ * optional outputs.  The scratch is the batch scratch's, per pair 8 KB per segment and 8 KB.  PHYAMD_EUNSUPPORTED, naming the
+ * condition: a state count other than 20 (4: use phyamd_pairwise_distances; 60 / 61: 64 x 64 tables are not built), more than 11
+ * ambiguity sets recorded on the engine (a class is below 32), a recorded set with no member (tip partials that are all 0), tiled
+ * patterns, a handle sharded over several devices, flags other than 0, scratch of one pair that does not fit the memory cap.
+ * PHYAMD_EINVAL: as for phyamd_pairwise_distances.  phyamd_get_distance_profile reports the last distance call of either kind. */
+int phyamd_pairwise_distances_general(phyamd_engine *e, int flags, int32_t count, const int32_t *pairs /* [count][2] or NULL: all i<j, row-major */,
+                                      const double *start /* [count] or NULL: 0.1 */, double lower, double upper, double tolerance, int32_t max_iterations,
+                                      double *distances /* [count] or NULL */, double *lnl, double *d1, double *d2 /* [count] or NULL */,
+                                      int32_t *iterations /* or NULL */, double *counts /* [count][32][32] or NULL */,
+                                      uint64_t *class_members /* [32] or NULL */);
 
 /* --- query sequences placed on every edge of the engine's tree --- */
 /* lnL of `queries` sequences that are NOT among the engine's taxa, each placed on every edge of the engine's tree, in one call:

@@ -981,6 +981,15 @@ void TreeLikelihoodInterface::PairwiseDistances(const int *pairs, int count, con
 	                                        counts));
 }
 
+void TreeLikelihoodInterface::PairwiseDistancesGeneral(const int *pairs, int count, const double *start, double lower, double upper, double tolerance, int maxIterations,
+                                                       double *distances, double *logLikelihoods, double *d1, double *d2, int32_t *iterations, double *counts,
+                                                       uint64_t *classMembers) {
+	if (!distances && !counts) throw Error("null distances and counts");
+	Sync();
+	phyamd::check(phyamd_pairwise_distances_general(impl_->engine, 0, count, pairs, start, lower, upper, tolerance, maxIterations, distances, logLikelihoods, d1, d2,
+	                                                iterations, counts, classMembers));
+}
+
 void TreeLikelihoodInterface::PlacementLogLikelihoods(const uint8_t *masks, int queries, const double *pendant, int lengths, double split, double *logLikelihoods,
                                                       int32_t *bestNodes, double *bestLogLikelihoods) {
 	if (!logLikelihoods && !bestNodes) throw Error("null logLikelihoods and bestNodes");

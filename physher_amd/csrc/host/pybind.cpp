@@ -324,6 +324,26 @@ PYBIND11_MODULE(_phycpp_amd, m) {
 		                          table.empty() ? py::object(py::none()) : py::object(darray({count, (py::ssize_t)16, (py::ssize_t)16}, table.data())));
 	    }, py::arg("pairs") = py::none(), py::arg("start") = py::none(), py::arg("lower") = 1e-8, py::arg("upper") = 10.0, py::arg("tolerance") = 1e-8,
 	       py::arg("max_iterations") = 100, py::arg("want_counts") = false, py::arg("counts_only") = false)
+	    .def("pairwise_distances_general", [](TreeLikelihoodInterface &self, std::optional<iarray> pairs, std::optional<darray> start, double lower, double upper,
+	                                          double tolerance, int max_iterations, bool want_counts, bool counts_only, bool want_class_members) -> py::tuple {
+		    const py::ssize_t T = ((py::ssize_t)self.NodeCount() + 1) / 2;
+		    if (pairs && (pairs->ndim() != 2 || pairs->shape(1) != 2)) throw phyamd::Error("pairs: [count][2]");
+		    const py::ssize_t count = pairs ? pairs->shape(0) : T * (T - 1) / 2;
+		    if (start && (start->ndim() != 1 || start->shape(0) != count)) throw phyamd::Error("start: [count]");
+		    const size_t n = counts_only ? 0 : (size_t)count;
+		    std::vector<double> dist(n), lnl(n), d1(n), d2(n), table(want_counts || counts_only ? (size_t)count * 1024 : 0);
+		    std::vector<int32_t> it(n);
+		    std::vector<uint64_t> members(want_class_members ? 32 : 0);
+		    self.PairwiseDistancesGeneral(pairs ? pairs->data() : nullptr, (int)count, start ? start->data() : nullptr, lower, upper, tolerance, max_iterations,
+		                                  n ? dist.data() : nullptr, n ? lnl.data() : nullptr, n ? d1.data() : nullptr, n ? d2.data() : nullptr, n ? it.data() : nullptr,
+		                                  table.empty() ? nullptr : table.data(), members.empty() ? nullptr : members.data());
+		    const std::vector<py::ssize_t> shape{count};
+		    const auto vec = [&](const std::vector<double> &v) -> py::object { return n ? py::object(darray(shape, v.data())) : py::object(py::none()); };
+		    return py::make_tuple(vec(dist), vec(lnl), vec(d1), vec(d2), n ? py::object(iarray(shape, it.data())) : py::object(py::none()),
+		                          table.empty() ? py::object(py::none()) : py::object(darray({count, (py::ssize_t)32, (py::ssize_t)32}, table.data())),
+		                          members.empty() ? py::object(py::none()) : py::object(py::array_t<uint64_t>({(py::ssize_t)32}, members.data())));
+	    }, py::arg("pairs") = py::none(), py::arg("start") = py::none(), py::arg("lower") = 1e-8, py::arg("upper") = 10.0, py::arg("tolerance") = 1e-8,
+	       py::arg("max_iterations") = 100, py::arg("want_counts") = false, py::arg("counts_only") = false, py::arg("want_class_members") = false)
 	    .def("placement_log_likelihoods", [](TreeLikelihoodInterface &self, py::array_t<uint8_t, py::array::c_style | py::array::forcecast> masks, darray pendant, double split,
 	                                         bool want_lnl, bool want_best) -> py::tuple {
 		    const py::ssize_t N = (py::ssize_t)self.NodeCount();

@@ -695,10 +695,10 @@ int phyamd_get_spr_optimize_profile(phyamd_engine *g, phyamd_spr_optimize_profil
 	return merged_profile(g, &Shard::tripod_prof, out, [](phyamd_spr_optimize_profile &, const phyamd_spr_optimize_profile &) {});  // (never sharded)
 }
 
-// one device only: a pair's table would be the sum of the shards' tables
-int phyamd_pairwise_distances(phyamd_engine *g, int flags, int32_t count, const int32_t *pairs, const double *start, double lower, double upper, double tolerance,
-                              int32_t max_iterations, double *distances, double *lnl, double *d1, double *d2, int32_t *iterations, double *counts) {
-	static const char *const name = "phyamd_pairwise_distances";
+// the argument checks of the two distance calls, up to the handle's shards
+static int check_pair_distance_arguments(const char *name, phyamd_engine *g, int32_t count, const int32_t *pairs, const double *start, double lower, double upper,
+                                         double tolerance, int32_t max_iterations, const double *distances, const double *lnl, const double *d1, const double *d2,
+                                         const int32_t *iterations, const double *counts) {
 	if (!distances && !counts) return fail(PHYAMD_EINVAL, "%s: null distances and null counts: one of them is the result", name);
 	if (!distances && (lnl || d1 || d2 || iterations))
 		return fail(PHYAMD_EINVAL, "%s: %s without distances (null distances: the call only counts)", name, lnl ? "lnl" : d1 ? "d1" : d2 ? "d2" : "iterations");
@@ -721,7 +721,25 @@ int phyamd_pairwise_distances(phyamd_engine *g, int flags, int32_t count, const 
 	}
 	if (group_size(g) > 1)
 		return fail(PHYAMD_EUNSUPPORTED, "%s: a handle sharded over several devices is out of scope: a pair's table would be the sum of the shards' tables", name);
-	return shard_pairwise_distances(g->shards[0], flags, PairDistanceArgs{count, pairs, start, lower, upper, tolerance, max_iterations, distances, lnl, d1, d2, iterations, counts});
+	return PHYAMD_OK;
+}
+
+// one device only: a pair's table would be the sum of the shards' tables
+int phyamd_pairwise_distances(phyamd_engine *g, int flags, int32_t count, const int32_t *pairs, const double *start, double lower, double upper, double tolerance,
+                              int32_t max_iterations, double *distances, double *lnl, double *d1, double *d2, int32_t *iterations, double *counts) {
+	if (int rc = check_pair_distance_arguments("phyamd_pairwise_distances", g, count, pairs, start, lower, upper, tolerance, max_iterations, distances, lnl, d1, d2, iterations, counts))
+		return rc;
+	return shard_pairwise_distances(g->shards[0], flags, PairDistanceArgs{count, pairs, start, lower, upper, tolerance, max_iterations, distances, lnl, d1, d2, iterations, counts, nullptr});
+}
+
+int phyamd_pairwise_distances_general(phyamd_engine *g, int flags, int32_t count, const int32_t *pairs, const double *start, double lower, double upper, double tolerance,
+                                      int32_t max_iterations, double *distances, double *lnl, double *d1, double *d2, int32_t *iterations, double *counts,
+                                      uint64_t *class_members) {
+	if (int rc = check_pair_distance_arguments("phyamd_pairwise_distances_general", g, count, pairs, start, lower, upper, tolerance, max_iterations, distances, lnl, d1, d2,
+	                                           iterations, counts))
+		return rc;
+	return shard_pairwise_distances_general(g->shards[0], flags,
+	                                        PairDistanceArgs{count, pairs, start, lower, upper, tolerance, max_iterations, distances, lnl, d1, d2, iterations, counts, class_members});
 }
 
 int phyamd_get_distance_profile(phyamd_engine *g, phyamd_distance_profile *out) {

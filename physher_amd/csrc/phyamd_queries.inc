@@ -1191,15 +1191,16 @@ int shard_spr_optimize(Shard *e, int flags, const SprOptimizeArgs &o) {
 
 // ---- the ML distance of pairs of taxa (phyamd_pairwise_distances) ---------------------------------------------------------------
 
-// an item is a PAIR: its two taxa and its group record, its table's segment sums and the table, its start and its results.  Nothing
-// whatever the pair count: the call walks no tree and reads the engine's tip data, weights and model where they are
-ScratchPlan pairdist_plan(Shard *e, size_t segments) {
+// an item is a PAIR: its two taxa and its group record, its table's segment sums and the table (`bins` doubles each: 256 mask pairs at
+// 4 states, 1024 class pairs at 20), its start and its results.  Nothing whatever the pair count: the call walks no tree and reads
+// the engine's tip data, weights and model where they are
+ScratchPlan pairdist_plan(Shard *e, size_t segments, size_t bins = 256) {
 	const size_t D = sizeof(double);
 	ScratchPlan p;
 	p.add(e->d_pairdist_pairs, sizeof(int32_t) * 2);
 	p.add(e->d_pairdist_groups, sizeof(int32_t) * 2);
-	p.add(e->d_pairdist_part, D * segments * 256);
-	p.add(e->d_pairdist_counts, D * 256);
+	p.add(e->d_pairdist_part, D * segments * bins);
+	p.add(e->d_pairdist_counts, D * bins);
 	p.add(e->d_pairdist_start, D);
 	p.add(e->d_pairdist_out, D * 4);
 	p.add(e->d_pairdist_iter, sizeof(int32_t));
@@ -1207,6 +1208,7 @@ ScratchPlan pairdist_plan(Shard *e, size_t segments) {
 }
 
 constexpr size_t PAIRDIST_MAX_CHUNK = (size_t)1 << 20;  // pairs per chunk: gridDim.x of k_pairdist_solve4, 2 GB of tables
+constexpr size_t PAIRDIST_GEN_MAX_CHUNK = (size_t)1 << 18;  // the same 2 GB of the larger tables (k_pairdist_finish runs four blocks per pair)
 
 struct PairDistanceArgs {
 	int32_t count;
@@ -1217,14 +1219,17 @@ struct PairDistanceArgs {
 	double *distances, *lnl, *d1, *d2;
 	int32_t *iterations;
 	double *counts;
+	uint64_t *class_members;  // phyamd_pairwise_distances_general only
 };
 
-// chunk by chunk the pairs' tables on the matrix pipe and, with `distances`, each pair's whole iteration in one workgroup.  Reads
-// the engine's tip data, weights and model and writes only the batch scratch: nothing in Shard::state changes
-int run_pairwise_distances(Shard *e, int flags, const PairDistanceArgs &o, phyamd_distance_profile &prof) {
-	static const char *const name = "phyamd_pairwise_distances";
-	const bool solve = o.distances != nullptr;
-	if (e->S != 4) return fail(PHYAMD_EUNSUPPORTED, "%s: the mask-pair tables are built for 4 states (the engine has %d)", name, e->S);
+// what the two distance calls differ in, beside their kernels: the table's bins, the partners of a wave of the counting kernel and
+// the pairs of a chunk
+struct PairDistanceKind {
+	size_t bins, partners, max_chunk;
+};
+
+// the checks the two distance calls share, after the state count's
+int check_pairwise_distances(Shard *e, const char *name, int flags, bool solve) {
 	if (e->tiles > 1) return fail(PHYAMD_EUNSUPPORTED, "%s: the patterns are tiled and the call needs the tip data of all patterns resident", name);
 	if (flags != 0) return fail(PHYAMD_EUNSUPPORTED, "%s: flags %d (no flags are defined: pass 0)", name, flags);
 	for (int t = 0; t < e->T; t++)
@@ -1234,8 +1239,18 @@ int run_pairwise_distances(Shard *e, int flags, const PairDistanceArgs &o, phyam
 	if (solve && !e->have_eigen) return fail(PHYAMD_EINVAL, "%s needs the eigen system (phyamd_set_eigen): the likelihood in the distance is formed from it", name);
 	if (solve && !e->have_freqs) return fail(PHYAMD_EINVAL, "%s: phyamd_set_frequencies has not been called", name);
 	if (solve && !e->have_rates) return fail(PHYAMD_EINVAL, "%s: phyamd_set_category_rates has not been called", name);
+	return PHYAMD_OK;
+}
+
+// chunk by chunk the pairs' tables on the matrix pipe and, with `distances`, each pair's whole iteration in one workgroup.  Reads
+// the engine's tip data, weights and model and writes only the batch scratch: nothing in Shard::state changes.  launch_count(args,
+// grid) and launch_solve(args, pairs) launch the call's counting kernel and its iterations
+template <class LaunchCount, class LaunchSolve>
+int run_pairdist_chunks(Shard *e, const char *name, const PairDistanceArgs &o, phyamd_distance_profile &prof, const PairDistanceKind &kind, const LaunchCount &launch_count,
+                        const LaunchSolve &launch_solve) {
+	const bool solve = o.distances != nullptr;
 	const int T = e->T, P = e->P;
-	const size_t count = (size_t)o.count, segments = ((size_t)P + REWEIGHT_SEGMENT - 1) / REWEIGHT_SEGMENT;
+	const size_t count = (size_t)o.count, segments = ((size_t)P + REWEIGHT_SEGMENT - 1) / REWEIGHT_SEGMENT, bins = kind.bins;
 	if (segments > 65535) return fail(PHYAMD_EUNSUPPORTED, "%s: %zu segments of %d patterns (at most 65535: gridDim.y)", name, segments, REWEIGHT_SEGMENT);
 	prof.pairs = o.count;
 	prof.segments = (int32_t)segments;
@@ -1247,8 +1262,8 @@ int run_pairwise_distances(Shard *e, int flags, const PairDistanceArgs &o, phyam
 			for (int j = i + 1; j < T; j++) all.push_back(i), all.push_back(j);
 		pairs = all.data();
 	}
-	const ScratchPlan plan = pairdist_plan(e, segments);
-	const size_t want = std::min(count, PAIRDIST_MAX_CHUNK);
+	const ScratchPlan plan = pairdist_plan(e, segments, bins);
+	const size_t want = std::min(count, kind.max_chunk);
 	size_t chunk = want;
 	if (!plan.held(want)) {
 		const double fit = plan.items_in(scratch_room(e, (double)batch_scratch_bytes(e), EngineRoom::MayGrow));
@@ -1264,32 +1279,34 @@ int run_pairwise_distances(Shard *e, int flags, const PairDistanceArgs &o, phyam
 	for (size_t first = 0; first < count; first += chunk) {
 		const size_t n = std::min(chunk, count - first);
 		const int32_t *pc = pairs + 2 * first;
-		groups.clear();  // runs of pairs that share their first taxon, at most PAIRDIST_PARTNERS long
+		groups.clear();  // runs of pairs that share their first taxon, at most kind.partners long
 		for (size_t i = 0; i < n;) {
 			size_t len = 1;
-			while (len < (size_t)PAIRDIST_PARTNERS && i + len < n && pc[2 * (i + len)] == pc[2 * i]) len++;
+			while (len < kind.partners && i + len < n && pc[2 * (i + len)] == pc[2 * i]) len++;
 			groups.push_back((int32_t)i), groups.push_back((int32_t)len);
 			i += len;
 		}
 		HIP_TRY(hipMemcpyAsync(e->d_pairdist_pairs, pc, sizeof(int32_t) * 2 * n, hipMemcpyHostToDevice, e->stream));
 		HIP_TRY(hipMemcpyAsync(e->d_pairdist_groups, groups.data(), sizeof(int32_t) * groups.size(), hipMemcpyHostToDevice, e->stream));
 		const PairCountArgs ca{e->d_pairdist_pairs, e->d_pairdist_groups, e->d_tipmask, e->d_weights, e->d_pairdist_part, e->d_pairdist_counts, P, (int)n, (int)segments};
-		hipLaunchKernelGGL(k_pairdist_counts4, dim3((unsigned)(groups.size() / 2), (unsigned)segments), dim3(WAVE), 0, e->stream, ca);
-		hipLaunchKernelGGL(k_pairdist_finish, dim3((unsigned)n), dim3(256), 0, e->stream, ca);
+		launch_count(ca, dim3((unsigned)(groups.size() / 2), (unsigned)segments));
+		PairCountArgs fa = ca;  // k_pairdist_finish adds records of 256 bins: a table of `bins` is bins / 256 of them
+		fa.npairs = (int)(n * (bins / 256));
+		hipLaunchKernelGGL(k_pairdist_finish, dim3((unsigned)fa.npairs), dim3(256), 0, e->stream, fa);
 		if (solve) {
 			start.assign(n, 0.1);
 			if (o.start) std::copy(o.start + first, o.start + first + n, start.begin());
 			HIP_TRY(hipMemcpyAsync(e->d_pairdist_start, start.data(), sizeof(double) * n, hipMemcpyHostToDevice, e->stream));
 			const PairSolveArgs sa{e->d_pairdist_counts, e->d_pairdist_start, e->C, o.max_iterations, o.lower, o.upper, o.tolerance, e->d_model, e->d_freqs, e->d_rates, e->d_props,
 			                       e->d_pairdist_out, e->d_pairdist_iter};
-			hipLaunchKernelGGL(k_pairdist_solve4, dim3((unsigned)n), dim3(PAIRDIST_THREADS), 0, e->stream, sa);
+			launch_solve(sa, (unsigned)n);
 			out.resize(n * 4);
 			iter.resize(n);
 			HIP_TRY(hipMemcpyAsync(out.data(), e->d_pairdist_out, sizeof(double) * out.size(), hipMemcpyDeviceToHost, e->stream));
 			HIP_TRY(hipMemcpyAsync(iter.data(), e->d_pairdist_iter, sizeof(int32_t) * n, hipMemcpyDeviceToHost, e->stream));
 		}
 		HIP_TRY(hipGetLastError());
-		if (o.counts) HIP_TRY(hipMemcpyAsync(o.counts + first * 256, e->d_pairdist_counts, sizeof(double) * n * 256, hipMemcpyDeviceToHost, e->stream));
+		if (o.counts) HIP_TRY(hipMemcpyAsync(o.counts + first * bins, e->d_pairdist_counts, sizeof(double) * n * bins, hipMemcpyDeviceToHost, e->stream));
 		HIP_TRY(hipStreamSynchronize(e->stream));  // (also covers the chunk's lists and starts)
 		prof.chunks++;
 		for (size_t i = 0; i < n && solve; i++) {
@@ -1305,9 +1322,52 @@ int run_pairwise_distances(Shard *e, int flags, const PairDistanceArgs &o, phyam
 	return PHYAMD_OK;
 }
 
+int run_pairwise_distances(Shard *e, int flags, const PairDistanceArgs &o, phyamd_distance_profile &prof) {
+	static const char *const name = "phyamd_pairwise_distances";
+	if (e->S != 4) return fail(PHYAMD_EUNSUPPORTED, "%s: the mask-pair tables are built for 4 states (the engine has %d)", name, e->S);
+	if (int rc = check_pairwise_distances(e, name, flags, o.distances != nullptr)) return rc;
+	return run_pairdist_chunks(
+	    e, name, o, prof, PairDistanceKind{256, (size_t)PAIRDIST_PARTNERS, PAIRDIST_MAX_CHUNK},
+	    [e](const PairCountArgs &ca, dim3 grid) { hipLaunchKernelGGL(k_pairdist_counts4, grid, dim3(WAVE), 0, e->stream, ca); },
+	    [e](const PairSolveArgs &sa, unsigned n) { hipLaunchKernelGGL(k_pairdist_solve4, dim3(n), dim3(PAIRDIST_THREADS), 0, e->stream, sa); });
+}
+
+// the 20-state call: the classes are the codes of d_tipmask (phyamd_pairdist_gen.inc), so the sets the engine has recorded must leave
+// every code below 32; class_members is the host's copy of what the kernel builds its class tables from
+int run_pairwise_distances_general(Shard *e, int flags, const PairDistanceArgs &o, phyamd_distance_profile &prof) {
+	static const char *const name = "phyamd_pairwise_distances_general";
+	if (e->S == 4) return fail(PHYAMD_EUNSUPPORTED, "%s: the class-pair tables are built for 20 states (the engine has 4: use phyamd_pairwise_distances)", name);
+	if (e->S != PAIRDIST_GEN_STATES)
+		return fail(PHYAMD_EUNSUPPORTED, "%s: the class-pair tables are built for 20 states (the engine has %d: 64 x 64 tables are not built)", name, e->S);
+	constexpr size_t max_sets = PAIRDIST_GEN_CLASSES - PAIRDIST_GEN_STATES - 1;
+	const size_t sets = e->tipsets_host.size();
+	if (sets > max_sets)
+		return fail(PHYAMD_EUNSUPPORTED, "%s: the engine has recorded %zu ambiguity sets (at most %zu: a tip cell's class must be below %d)", name, sets, max_sets, PAIRDIST_GEN_CLASSES);
+	for (size_t q = 0; q < sets; q++)
+		if (e->tipsets_host[q] == 0) return fail(PHYAMD_EUNSUPPORTED, "%s: ambiguity set %zu has no member (a tip cell's partials are all 0)", name, q);
+	if (int rc = check_pairwise_distances(e, name, flags, o.distances != nullptr)) return rc;
+	const int rc = run_pairdist_chunks(
+	    e, name, o, prof, PairDistanceKind{(size_t)PAIRDIST_GEN_BINS, (size_t)PAIRDIST_GEN_PARTNERS, PAIRDIST_GEN_MAX_CHUNK},
+	    [e](const PairCountArgs &ca, dim3 grid) { hipLaunchKernelGGL(k_classpair_counts, grid, dim3(WAVE), 0, e->stream, ca); },
+	    [e, sets](const PairSolveArgs &sa, unsigned n) {
+		    const PairSolveGenArgs ga{sa, e->d_tipsets, (int)sets};
+		    hipLaunchKernelGGL(k_classpair_solve, dim3(n), dim3(PAIRDIST_THREADS), 0, e->stream, ga);
+	    });
+	if (rc) return rc;
+	if (o.class_members)
+		for (size_t c = 0; c < (size_t)PAIRDIST_GEN_CLASSES; c++)
+			o.class_members[c] = c < 20 ? (uint64_t)1 << c : c == 20 ? ((uint64_t)1 << 20) - 1 : c - 21 < sets ? (uint64_t)e->tipsets_host[c - 21] : 0;
+	return PHYAMD_OK;
+}
+
 int shard_pairwise_distances(Shard *e, int flags, const PairDistanceArgs &o) {
 	CHECK_ENGINE(e);
 	return profiled_call(e, &Shard::dist_prof, phyamd_distance_profile{}, [&](phyamd_distance_profile &prof) { return run_pairwise_distances(e, flags, o, prof); });
+}
+
+int shard_pairwise_distances_general(Shard *e, int flags, const PairDistanceArgs &o) {
+	CHECK_ENGINE(e);
+	return profiled_call(e, &Shard::dist_prof, phyamd_distance_profile{}, [&](phyamd_distance_profile &prof) { return run_pairwise_distances_general(e, flags, o, prof); });
 }
 
 // ---- query sequences on every edge of the engine's tree (phyamd_placement_log_likelihoods) --------------------------------------

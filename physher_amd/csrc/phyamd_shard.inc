@@ -278,10 +278,11 @@ struct Shard {
 	DeviceArray<int32_t> d_tripod_counts{&batch_mem};   // [rows][N][passes, visits, iterations]
 	phyamd_spr_optimize_profile tripod_prof{};
 	// phyamd_pairwise_distances (phyamd_pairdist4.inc) walks no tree: per pair of a chunk its two taxa, the record of the run of pairs
-	// it shares its first taxon with, the segment sums of its 16 x 16 mask-pair table and the table, its start and its results
+	// it shares its first taxon with, the segment sums of its 16 x 16 mask-pair table and the table, its start and its results.
+	// phyamd_pairwise_distances_general (phyamd_pairdist_gen.inc) uses the same arrays with 32 x 32 class-pair tables: 1024 bins
 	DeviceArray<int32_t> d_pairdist_pairs{&batch_mem}, d_pairdist_groups{&batch_mem};  // [pair][i, j], [group][first pair, pairs]
-	DeviceArray<double> d_pairdist_part{&batch_mem};     // [segments][pair][256]
-	DeviceArray<double> d_pairdist_counts{&batch_mem};   // [pair][16 mi + mj]
+	DeviceArray<double> d_pairdist_part{&batch_mem};     // [segments][pair][256] ([1024])
+	DeviceArray<double> d_pairdist_counts{&batch_mem};   // [pair][16 mi + mj] ([32 ci + cj])
 	DeviceArray<double> d_pairdist_start{&batch_mem};    // [pair]
 	DeviceArray<double> d_pairdist_out{&batch_mem};      // [pair][t*, lnL, d1, d2]
 	DeviceArray<int32_t> d_pairdist_iter{&batch_mem};    // [pair]

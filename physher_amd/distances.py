@@ -68,3 +68,40 @@ def k2p(counts):
     with np.errstate(divide="ignore", invalid="ignore"):
         P, Q = ts / n, tv / n
         return -0.5 * np.log(1.0 - 2.0 * P - Q) - 0.25 * np.log(1.0 - 2.0 * Q)
+
+
+# --- the 32 x 32 class tables of Engine.pairwise_distances_general (20 states) ---
+# counts[..., ci, cj] is the summed weight of the patterns where the pair's first taxon has class ci and its second class cj: classes
+# 0..19 are the states, 20 is unknown and 21 + q an ambiguity set whose number is the engine's own (class_members says what it
+# holds).  The count-based distances look at single states only -- the reference's `n1 < state_count && n2 < state_count` -- so
+# they need the leading 20 x 20 block and no class_members.
+def state_counts_general(counts):
+    """[..., 20, 20]: the cells where both classes are a single state, by state"""
+    counts = np.asarray(counts, dtype=np.float64)
+    if counts.shape[-2:] != (32, 32):
+        raise ValueError(f"counts must be [..., 32, 32] (got {counts.shape})")
+    return counts[..., :20, :20]
+
+
+def _differences_general(counts):
+    n20 = state_counts_general(counts)
+    n = n20.sum(axis=(-2, -1))
+    same = np.trace(n20, axis1=-2, axis2=-1)
+    return n - same, n
+
+
+def p_distance_general(counts):
+    """p_distance over the class tables: d / n of the cells where both classes are states; 1000.0 where nothing was compared."""
+    d, n = _differences_general(counts)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(n == 0, 1000.0, d / n)
+
+
+def kimura_protein(counts):
+    """Kimura's protein distance -log(1 - p - 0.2 p^2) of _distance_aa_kimura_patterns, p = d / n over the cells where both codes
+    are states.  As in the reference: NaN where nothing was compared (0 / 0) or the logarithm's argument is negative, inf where it is
+    0."""
+    d, n = _differences_general(counts)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        p = d / n
+        return -np.log(1.0 - p - 0.2 * p * p)

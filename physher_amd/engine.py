@@ -413,6 +413,12 @@ class Engine:
         bounds ignored.  Needs tip data and weights (and for distances the eigen system, frequencies and rates), no topology and
         no lengths; works on a rescaling engine and with any number of categories.  The engine is unchanged.  EngineError on
         engines that are not 4-state, tiled or sharded, and where a tip cell has an empty mask."""
+        return self._pair_distances(self._lib.phyamd_pairwise_distances, 16, pairs, start, lower, upper, tolerance, max_iterations, want_derivatives, want_iterations,
+                                    want_counts, counts_only, flags)
+
+    def _pair_distances(self, call, classes, pairs, start, lower, upper, tolerance, max_iterations, want_derivatives, want_iterations, want_counts, counts_only, flags,
+                        *more):
+        """the arrays of the two distance calls: counts is [count, classes, classes]; more: the pointers behind counts"""
         pr = None
         if pairs is not None:
             pr = np.ascontiguousarray(pairs, dtype=np.int32)
@@ -430,15 +436,30 @@ class Engine:
         d1 = np.empty(count) if solve and want_derivatives else None
         d2 = np.empty(count) if solve and want_derivatives else None
         it = np.empty(count, dtype=np.int32) if solve and want_iterations else None
-        counts = np.empty((count, 16, 16)) if want_counts or counts_only else None
+        counts = np.empty((count, classes, classes)) if want_counts or counts_only else None
         opt = lambda a: None if a is None else _ptr(a)
-        self._check(self._lib.phyamd_pairwise_distances(self._h, flags, count, opt(pr), opt(st), lower, upper, tolerance, max_iterations, opt(dist), opt(lnl),
-                                                        opt(d1), opt(d2), opt(it), opt(counts)))
+        self._check(call(self._h, flags, count, opt(pr), opt(st), lower, upper, tolerance, max_iterations, opt(dist), opt(lnl), opt(d1), opt(d2), opt(it), opt(counts),
+                         *more))
         return dist, lnl, d1, d2, it, counts
 
+    def pairwise_distances_general(self, pairs=None, start=None, lower=1e-8, upper=10.0, tolerance=1e-8, max_iterations=100, want_derivatives=True,
+                                   want_iterations=True, want_counts=False, counts_only=False, want_class_members=False, flags=0):
+        """pairwise_distances for an engine of 20 states (proteins): (distances, lnl, d1, d2, iterations, counts [count, 32, 32],
+        class_members [32] uint64); what is not wanted is None.  The same pairs, rule, start, bounds and outputs, with the tables
+        over tip classes: counts[p, ci, cj] is the summed weight of the patterns where taxon i has class ci and taxon j class cj.
+        A class is a state (0..19), unknown (20) or one of the engine's ambiguity sets (21 + q, numbered in the order in which
+        set_tip_partials first met them): class_members[c] has bit s set where state s is a member of class c and is 0 for a
+        class no set stands for, so it is what gives counts its meaning (physher_amd.distances: state_counts_general,
+        p_distance_general, kimura_protein).  EngineError on engines that are not 20-state, tiled or sharded, and with more than
+        11 recorded sets or a set without a member."""
+        members = np.zeros(32, dtype=np.uint64) if want_class_members else None
+        out = self._pair_distances(self._lib.phyamd_pairwise_distances_general, 32, pairs, start, lower, upper, tolerance, max_iterations, want_derivatives,
+                                   want_iterations, want_counts, counts_only, flags, None if members is None else _ptr(members))
+        return out + (members,)
+
     def distance_profile(self):
-        """Of the last pairwise_distances: pairs, chunks (of pairs), segments (of the pattern axis), scratch_bytes, iterations (over
-        all pairs), ms."""
+        """Of the last pairwise_distances or pairwise_distances_general: pairs, chunks (of pairs), segments (of the pattern axis),
+        scratch_bytes, iterations (over all pairs), ms."""
         p = _lib.DistanceProfile()
         self._check(self._lib.phyamd_get_distance_profile(self._h, C.byref(p)))
         return {k: getattr(p, k) for k, _ in p._fields_}
