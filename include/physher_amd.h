@@ -644,6 +644,20 @@ int phyamd_stream_elisions(int32_t tip_count, const int32_t *left /* [2T-1] */, 
 #define PHYAMD_STREAM_PAIR_COLUMNS 48
 int phyamd_stream_pairs(int32_t tip_count, const int32_t *left /* [2T-1] */, const int32_t *right, int32_t root, int32_t pairs,
                         int32_t *out /* [capacity][PHYAMD_STREAM_PAIR_COLUMNS] */, int32_t capacity);
+/* The elided nodes (phyamd_stream_elisions) whose own op of the streamed pre-order walk takes its stored child's plane from its
+ * parent's op in registers instead of requesting it again (PHYAMD_STREAM_KEEP, on by default), from the host schedule alone (no
+ * device, no engine).  The parent's op is handed that plane to form the elided node's message; where the node's op is the very
+ * next op of the chunk and the stored child sits there on the side the node had in its parent's op, the parent's op requests
+ * nothing for that side.  One record of PHYAMD_STREAM_KEEP_COLUMNS ints per elided node, in phyamd_stream_elisions' order:
+ * 0 node | 1 its parent | 2 the side it has in its parent's op (0 left, 1 right) | 3 what the rule decided (0: kept; 1: the node's
+ * op is not the next op of its parent's chunk -- its upper is parked or the other child is walked first; 2: its stored child sits
+ * on the other side there; 3: its op opens a chunk, whose prologue fetches its operands; 4: keep = 0) | 4 whether the parent's op
+ * requests a plane for that side in the descriptor set of the rescaled and ambiguity-code passes (1) or not (0) | 5 the same in
+ * the plain pass's set (phyamd_stream_pairs).  Returns the number of elided nodes (at most `capacity` of them are written) or a
+ * negative PHYAMD_E* code. */
+#define PHYAMD_STREAM_KEEP_COLUMNS 6
+int phyamd_stream_keeps(int32_t tip_count, const int32_t *left /* [2T-1] */, const int32_t *right, int32_t root, int32_t keep,
+                        int32_t *out /* [capacity][PHYAMD_STREAM_KEEP_COLUMNS] */, int32_t capacity);
 int phyamd_is_rescaling(phyamd_engine *e);
 /* SingleTreeLikelihood_use_rescaling (treelikelihood.c:1410-1423) after construction: PHYAMD_RESCALE_ALWAYS / _NEVER switch
  * at once (the next evaluation recomputes every node), PHYAMD_RESCALE_AUTO keeps the current state and re-arms the lazy switch. */

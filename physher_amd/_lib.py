@@ -184,6 +184,7 @@ SYMBOLS = [
     ("phyamd_pre_order_schedule", C.c_int, [C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
     ("phyamd_stream_elisions", C.c_int, [C.c_int32, _P, _P, C.c_int32, _P, C.c_int32]),
     ("phyamd_stream_pairs", C.c_int, [C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32]),
+    ("phyamd_stream_keeps", C.c_int, [C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32]),
     ("phyamd_is_rescaling", C.c_int, [_P]),
     ("phyamd_set_rescaling", C.c_int, [_P, C.c_int]),
     ("phyamd_set_keep_partials", C.c_int, [_P, C.c_int]),

@@ -52,7 +52,8 @@ int upload_schedule(Shard *e) {
 		HIP_TRY(hipMemcpyAsync(e->d_walk_lower_chunk_ops, e->sched.walk_lower_chunk_ops.data(), e->sched.walk_lower_chunk_ops.size() * sizeof(NodeOp), hipMemcpyHostToDevice, e->stream));
 		HIP_TRY(hipMemcpyAsync(e->d_walk_lower_chunk_off, e->sched.walk_lower_chunk_off.data(), e->sched.walk_lower_chunk_off.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
 		if (stream_possible(e)) {  // the streamed walks' tables follow the chunked lists (core indices included: store / restore moves them)
-			build_stream_tables(e->sched, StreamGeometry{e->P, e->C, (size_t)e->nblk_walk_upper * e->G * WAVE, e->stream_elide_on, e->stream_pairs_on}, &e->stream_tab);
+			build_stream_tables(e->sched, StreamGeometry{e->P, e->C, (size_t)e->nblk_walk_upper * e->G * WAVE, e->stream_elide_on, e->stream_pairs_on, e->stream_keep_on},
+			                    &e->stream_tab);
 			// (descriptors and chunks twice: those of the TF forms, then the plain ones behind them -- stream_elide, stream_plain_ops;
 			// the descriptors a third time, with the pair ops, at 2 x their count -- stream_pairs)
 			if ((rc = e->d_stream_ops.ensure((size_t)3 * e->N)) || (rc = e->d_stream_pair_tab.ensure((size_t)e->N * 16)) || (rc = e->d_stream_chunks.ensure((size_t)2 * e->N + 4)) ||

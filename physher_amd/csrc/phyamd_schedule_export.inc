@@ -194,6 +194,33 @@ int phyamd_stream_elisions(int32_t tip_count, const int32_t *left, const int32_t
 	return (int)el.size();
 }
 
+// the elided nodes whose op takes its stored child's plane from its parent's op in registers (stream_keep): host code only (no
+// device, no engine)
+int phyamd_stream_keeps(int32_t tip_count, const int32_t *left, const int32_t *right, int32_t root, int32_t keep, int32_t *out, int32_t capacity) {
+	if (tip_count < 2) return fail(PHYAMD_EINVAL, "tip_count must be >= 2 (got %d)", tip_count);
+	if (!left || !right) return fail(PHYAMD_EINVAL, "null left or right");
+	if (capacity < 0 || (capacity > 0 && !out)) return fail(PHYAMD_EINVAL, "null out with capacity %d", capacity);
+	Schedule sched;  // 4 states, an engine's defaults; the streamed walks' tables for one pattern of one category, as an engine builds them
+	StreamTables tab;
+	const std::string err = build_schedule(TreeRef{tip_count, left, right, root}, ScheduleOptions{}, &sched);
+	if (!err.empty()) return fail(PHYAMD_EINVAL, "%s", err.c_str());
+	build_stream_tables(sched, StreamGeometry{1, 1, WAVE, true, true, keep != 0}, &tab);
+	const std::vector<StreamKeep> &kp = tab.keeps;
+	for (int i = 0; i < (int)kp.size() && i < capacity; i++) {
+		// what the two descriptor sets that know elided kinds say of the request, so that a test can hold the rewrite itself
+		const int at = [&] {
+			for (int j = 0; j < (int)tab.ops.size(); j++)
+				if (tab.ops[j].parent == kp[i].parent) return j;
+			return -1;
+		}();
+		const int bit = 1 << (26 + kp[i].side);
+		const int32_t rec[PHYAMD_STREAM_KEEP_COLUMNS] = {kp[i].node, kp[i].parent, kp[i].side, kp[i].reason, at >= 0 && (tab.desc[at].flags & bit) ? 1 : 0,
+		                                                 at >= 0 && (tab.pair_desc[at].flags & bit) ? 1 : 0};
+		std::memcpy(out + (size_t)i * PHYAMD_STREAM_KEEP_COLUMNS, rec, sizeof(rec));
+	}
+	return (int)kp.size();
+}
+
 // what stream_pairs makes of the streamed pre-order walk of a tree: host code only (no device, no engine)
 int phyamd_stream_pairs(int32_t tip_count, const int32_t *left, const int32_t *right, int32_t root, int32_t pairs, int32_t *out, int32_t capacity) {
 	constexpr int W = PHYAMD_STREAM_PAIR_COLUMNS;

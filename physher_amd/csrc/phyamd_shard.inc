@@ -127,6 +127,7 @@ struct Shard {
 	bool lower_park2_on = true;            // PHYAMD_LOWER_PARK2 = 0: the post-order schedule parks in one slot only (ScheduleOptions)
 	bool stream_pairs_on = true;           // PHYAMD_STREAM_PAIRS = 0: the plain pre-order pass runs every DEEP child's op on its own (stream_pairs, phyamd_tree_schedule.h)
 	bool stream_elide_on = true;           // PHYAMD_STREAM_ELIDE = 0: the streamed walks store every stored node (stream_elide, phyamd_tree_schedule.h)
+	bool stream_keep_on = true;            // PHYAMD_STREAM_KEEP = 0: an elided node's op always requests its stored child's plane again (stream_keep, phyamd_tree_schedule.h)
 	DeviceArray<int> d_lexp{&tile_mem}, d_uexp{&tile_mem}, d_Ec{&tile_mem}, d_Eroot{&tile_mem};  // exponents: [stored][C][P], [upper slots][C][P], [C][P], [P]
 	bool keep_partials = false;
 	bool profiling = false;

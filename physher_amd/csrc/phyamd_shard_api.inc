@@ -206,6 +206,7 @@ int shard_create(const phyamd_config *cfg, Shard **out) {
 	if (const char *env = std::getenv("PHYAMD_LOWER_PARK2")) e->lower_park2_on = std::atoi(env) != 0;
 	if (const char *env = std::getenv("PHYAMD_STREAM_ELIDE")) e->stream_elide_on = std::atoi(env) != 0;
 	if (const char *env = std::getenv("PHYAMD_STREAM_PAIRS")) e->stream_pairs_on = std::atoi(env) != 0;
+	if (const char *env = std::getenv("PHYAMD_STREAM_KEEP")) e->stream_keep_on = std::atoi(env) != 0;
 	e->generic = e->S != 4;
 	e->tip_set.assign(e->T, 0);
 	e->tip_empty.assign(e->T, 0);

@@ -635,6 +635,7 @@ struct StreamGeometry {
 	size_t mstride;
 	bool elide = false;  // stream_elide: the post-order walk stops storing the nodes the pre-order walk can form beside a tip or a cherry
 	bool pairs = false;  // stream_pairs: a third descriptor set in which a DEEP child's pre-order op runs inside its parent's
+	bool keep = false;   // stream_keep: an elided child's op, where it runs next, takes its stored child's plane from its parent's op in registers
 };
 
 // a stored node the streamed walks no longer store (stream_elide)
@@ -643,6 +644,15 @@ struct StreamElision {
 	int32_t source;                                       // how the post-order walk hands it to its parent: 1 the op in front, 2 park slot 0
 	int32_t side;                                         // the side it has in its parent's pre-order op (0 left, 1 right)
 	int32_t chunk;                                        // the post-order chunk of both ops
+};
+
+// what stream_keep decided for one elided node
+enum { KEEP_KEPT = 0, KEEP_NOT_NEXT = 1, KEEP_OTHER_SIDE = 2, KEEP_OPENER = 3, KEEP_OFF = 4 };
+struct StreamKeep {
+	int32_t node, parent, side;  // the elided node, its parent, the side it has in its parent's pre-order op (StreamElision)
+	int32_t reason;              // KEEP_KEPT, or why its own op requests its stored child's plane again: the op is not the next of its
+	                             // parent's chunk (its upper is parked, or the other child is walked first); the stored child sits on
+	                             // the other side there; the op opens a chunk (the prologue fetches its operands); the switch is off
 };
 
 // what stream_pairs decided for one pre-order op
@@ -676,6 +686,8 @@ struct StreamTables {
 	std::vector<StreamDesc> plain_desc;
 	std::vector<StreamChunk> plain_chunks;
 	std::vector<StreamElision> elisions;
+	// stream_keep (with the elisions; otherwise empty): one decision per elided node, in their order
+	std::vector<StreamKeep> keeps;
 	// stream_pairs (StreamGeometry::pairs; otherwise empty): a copy of `desc` with the pair ops, for the plain TF pass; the pair
 	// blocks' position tables [ops][16] (OPBLK_PAIR_SITES); the decision per op
 	std::vector<StreamDesc> pair_desc;
@@ -1123,6 +1135,44 @@ inline void stream_elide(const Schedule &sc, const StreamGeometry &g, StreamTabl
 	t.words = (int)t.row_entries.size() / 8;
 }
 
+// An elided node's stored child is read twice, one op apart: the parent's op is handed s's plane in register set A (B) and forms
+// t_n = P_n (m_f o t_s) from it, and n's own op reads the same plane as its stored child.  Where n's op is the very next op the
+// loop runs, and s sits there on the side n had in its parent's op, the wave still holds t_s in that register set when the
+// parent's op issues its requests: the kernel keeps A / B across the loop edge when descriptor bit 26 / 27 is clear (under
+// SCALE == 2 the exponent eA / eB with it, guarded by the same bits), nothing but the prefetch writes them between the elided
+// child's message and the loop edge, and n's op copies the kept value as it copies a fetched one (own_registers).  So the
+// parent's op does not request the plane: the bit is cleared, nx_a / nx_b is unused.  Everything else keeps its requests: an
+// elided node whose op is not the next one (its upper is parked, or the other child is walked first), one whose op opens a chunk
+// (the prologue fetches its operands), one whose stored child changes sides, and the plain descriptors.  A pair op never has an
+// elided child and an elided node never a DEEP one, so stream_pairs, which copies `desc` afterwards, neither moves nor absorbs
+// an op this rule looks at.  A rewrite of `desc` only; one StreamKeep per elided node.  After stream_elide.
+inline void stream_keep(const Schedule &sc, const StreamGeometry &g, StreamTables &t) {
+	t.keeps.clear();
+	const int ns = (int)t.ops.size();
+	std::vector<int> sop((size_t)sc.parent.size(), -1), chunk_of(ns, 0);
+	std::vector<char> opens(ns, 0);
+	for (int i = 0; i < ns; i++) sop[t.ops[i].parent] = i;
+	for (int k = 0; k + 1 < (int)sc.walk_chunk_off.size(); k++)
+		for (int i = sc.walk_chunk_off[k]; i < sc.walk_chunk_off[k + 1]; i++) {
+			chunk_of[i] = k;
+			opens[i] = i == sc.walk_chunk_off[k];
+		}
+	for (const StreamElision &el : t.elisions) {
+		StreamKeep kp{el.node, el.parent, el.side, KEEP_KEPT};
+		const int i = sop[el.parent], j = sop[el.node];
+		if (!g.keep) kp.reason = KEEP_OFF;
+		else if (j >= 0 && opens[j]) kp.reason = KEEP_OPENER;
+		else if (i < 0 || j != i + 1 || chunk_of[j] != chunk_of[i]) kp.reason = KEEP_NOT_NEXT;
+		else if ((el.side ? t.ops[j].rnode : t.ops[j].lnode) != el.stored || ((t.desc[j].flags >> (3 * el.side)) & 7) != CH_CORE) kp.reason = KEEP_OTHER_SIDE;
+		else {
+			StreamDesc &d = t.desc[i];
+			d.flags &= ~(1 << (26 + el.side));
+			(el.side ? d.nx_b : d.nx_a) = 0;
+		}
+		t.keeps.push_back(kp);
+	}
+}
+
 // Pair ops: a third set of pre-order descriptors, read by the plain TF pass alone (k_upper4_stream<.., 0, false, true>).  A DEEP
 // node d has no stored partial: its parent's op n rebuilds its message from its two half messages, and d's own op, when it is the
 // next one, forms the same two halves again as its children's messages and pays an op's fixed cost.  In this set n runs d's op
@@ -1235,10 +1285,12 @@ inline void build_stream_tables(const Schedule &sc, const StreamGeometry &g, Str
 	out->plain_desc.clear();
 	out->plain_chunks.clear();
 	out->elisions.clear();
+	out->keeps.clear();
 	out->pair_desc.clear();
 	out->pair_tab.clear();
 	out->pairs.clear();
 	if (g.elide) stream_elide(sc, g, *out);
+	if (g.elide) stream_keep(sc, g, *out);
 	if (g.pairs) stream_pairs(sc, g, *out);
 }
 
