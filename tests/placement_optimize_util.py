@@ -22,7 +22,9 @@ PENDANT = 0.1  # the start pendant length of every candidate
 
 # (T, shape, P, C, Q, split, ambiguity codes in the tips, candidates that appear twice): no internal edge (T = 2), one (T = 3), a
 # root child that is a tip (caterpillar); less than a block of patterns, exactly one, one and a bit, two with a ragged end; 1, 2, 4
-# and 8 category waves
+# and 8 category waves; and past k_qopt_solve4's 256 threads (CBOPT_THREADS), where a thread builds the coefficients of a second
+# and a third pattern: 257 patterns (a second trip with one live thread), 300 over tip-partial masks (a ragged second trip), 600
+# (three trips, the last ragged)
 CASES = {
     "t2_p5_c1": (2, "random", 5, 1, 3, 0.5, False, 0),
     "t3_p64_c4": (3, "random", 64, 4, 5, 0.25, False, 0),
@@ -31,6 +33,9 @@ CASES = {
     "t9_p65_c2": (9, "random", 65, 2, 4, 0.7, False, 0),
     "t5_p70_c2_ambiguous": (5, "random", 70, 2, 3, 0.4, True, 0),
     "t4_p66_c1_twice": (4, "random", 66, 1, 2, 0.5, False, 5),
+    "t6_p257_c8": (6, "random", 257, 8, 2, 0.3, False, 0),
+    "t5_p300_c2_ambiguous": (5, "random", 300, 2, 3, 0.4, True, 0),
+    "t4_p600_c4": (4, "random", 600, 4, 3, 0.5, False, 0),
 }
 TABLED = ["t2_p5_c1", "t3_p64_c4", "t9_p130_c8", "t9_caterpillar_p70_c4", "t9_p65_c2"]
 SEEDS = {}  # case -> the seed of its problem, where the default (7 T + P + C) leaves fewer than nine entries in ten qualified

@@ -2,8 +2,8 @@
 edge and a gather-and-add per (query, edge) -- entry by entry against the CPU oracle's tree with T + 1 tips built from the
 definition (tests/placement_util.py), which knows nothing of the shortcut.  The tolerance is the suite's for single evaluations
 (tests/test_spr_gpu.py, tests/test_nni_gpu.py): 1e-10 relative on lnL.  Then the best edge, the cross-check with
-phyamd_spr_log_likelihoods, bits across calls, query orders, batch sizes and chunks, the engine afterwards, underflow, and every
-refusal."""
+phyamd_spr_log_likelihoods, bits across calls, query orders, batch sizes and chunks, the engine afterwards, underflow, the same
+past the first segment of patterns and the first block of queries, and every refusal."""
 import ctypes
 import functools
 
@@ -12,6 +12,7 @@ import pytest
 
 import placement_util as u
 from gpu_util import engine_from_problem, random_problem
+from periodic_util import periodic_pair
 from physher_amd.engine import RESCALE_ALWAYS, RESCALE_AUTO, RESCALE_NEVER, Engine, EngineError
 from test_batch_gpu import _ambiguous_partials, _bits, _deep
 
@@ -206,6 +207,131 @@ def test_underflow_is_reported_in_band(rescale):
     with engine_from_problem(pb, rescale=rescale) as e:
         lnl, node, best = e.placement_log_likelihoods(masks, [0.1, 0.5])
         assert not e.rescaling  # never a switch to rescaling
+    assert np.all(np.isnan(lnl[:, :, pb.root])) and np.all(np.isneginf(np.delete(lnl, pb.root, axis=2)))
+    assert np.all(np.isneginf(best)) and np.all(node == (1 if pb.root == 0 else 0))
+
+
+# ---- past the first segment of patterns and the first block of queries ------------------------------------------------------------
+#
+# k_place_score4 adds a fixed segment of 4096 patterns (REWEIGHT_SEGMENT) per workgroup and takes at most 1024 queries
+# (PLACE_MAX_QUERIES) as lanes; k_place_finish adds a column's segments and takes 256 (length, query) threads per block.  4096 + 70
+# patterns are two segments, the second ragged (66 blocks of 64, the last ragged); 1100 queries are two blocks of lanes, the second
+# with 76 live ones; 2 x 1100 (length, query) threads are nine blocks of the finish.  The scratch is padded to whole blocks, so a
+# wrong offset reads valid memory and returns a plausible lnL: only a reference shows it.
+
+P_SEGMENTS = 4096 + 70
+Q_BLOCKS, Q_DISTINCT = 1100, 24
+SEGMENT_PENDANT, SEGMENT_SPLIT = (0.05, 0.4), 0.3
+
+
+@functools.lru_cache(maxsize=None)
+def _segment_case(ambig):
+    """(problem, tip mode, the 24 distinct query rows, row [1100]: which of them query q is, the oracle's [2][24][N]): the oracle
+    runs the distinct rows only; the 1100 queries are the 24 tiled and then shuffled"""
+    T, C = 5, 2
+    pb = random_problem(T, P_SEGMENTS, C, seed=7 * T + P_SEGMENTS + C, gaps=0.08)
+    if ambig:
+        _ambiguous_partials(pb, 3)
+    distinct = u.random_masks(np.random.default_rng(P_SEGMENTS + Q_BLOCKS), Q_DISTINCT, P_SEGMENTS, gaps=0.1, ambiguous=0.15)
+    distinct[1] = 15  # an all-gap query
+    row = np.random.default_rng(17).permutation(np.arange(Q_BLOCKS) % Q_DISTINCT)
+    ref = u.oracle_all(pb, distinct, SEGMENT_PENDANT, SEGMENT_SPLIT)
+    for a in (distinct, row, ref):
+        a.setflags(write=False)
+    return pb, ("partials" if ambig else "states"), distinct, row, ref
+
+
+def _reached_two_segments_and_two_query_blocks(e, masks):
+    """FAILS where the case no longer crosses the boundaries it is there for.  The call's profile does not report its segments; a
+    counts-only pairwise_distances call on the same engine does, and both are computed from the same constant, REWEIGHT_SEGMENT
+    (phyamd_reweight.inc): a later change of the constant shows here and not as a test that quietly covers less"""
+    assert len(masks) > 1024, f"{len(masks)} queries are one block of k_place_score4's lanes (PLACE_MAX_QUERIES = 1024)"
+    e.pairwise_distances([[0, 1]], counts_only=True)
+    segments = e.distance_profile()["segments"]
+    assert segments >= 2, f"{e.P} patterns are {segments} segment(s) of REWEIGHT_SEGMENT patterns: the pattern count of this case is too small"
+
+
+def _same_outputs(got, want):
+    return all(np.array_equal(_bits(a) if a.dtype == np.float64 else a, _bits(b) if b.dtype == np.float64 else b) for a, b in zip(got, want))
+
+
+@pytest.mark.parametrize("ambig", [True, False], ids=["ambiguous", "states"])
+def test_two_segments_and_two_query_blocks_match_the_oracle(ambig):
+    pb, tip_mode, distinct, row, ref = _segment_case(ambig)
+    masks = distinct[row]
+    assert masks.shape == (Q_BLOCKS, P_SEGMENTS) and len(SEGMENT_PENDANT) * Q_BLOCKS > 8 * 256  # nine blocks of k_place_finish
+    assert np.array_equal(np.bincount(row, minlength=Q_DISTINCT) > 0, np.ones(Q_DISTINCT, dtype=bool))
+    with engine_from_problem(pb, rescale=RESCALE_AUTO, tip_mode=tip_mode) as e:
+        lnl, node, best = e.placement_log_likelihoods(masks, SEGMENT_PENDANT, split=SEGMENT_SPLIT)
+        prof = e.placement_profile()
+        assert not e.rescaling
+        _reached_two_segments_and_two_query_blocks(e, masks)
+    assert prof["queries"] == Q_BLOCKS and prof["lengths"] == 2 and prof["edges"] == pb.N - 1, prof
+    assert prof["edge_chunks"] == 1 and prof["query_chunks"] == 1, prof
+    assert lnl.shape == (2, Q_BLOCKS, pb.N)
+    assert np.all(np.isnan(lnl[:, :, pb.root])) and np.all(np.isfinite(np.delete(lnl, pb.root, axis=2)))
+    want = ref[:, row]
+    err = np.abs(lnl - want) / np.abs(want)
+    worst = np.nanmax(err)
+    print(f"{'ambiguous' if ambig else 'states'}: {np.isfinite(want).sum()} entries, worst relative lnL error {worst:.3e} ({worst / 1e-10:.2e} of the tolerance)")
+    assert worst <= 1e-10, np.unravel_index(np.nanargmax(err), err.shape)
+    for r in range(Q_DISTINCT):  # copies of one row, wherever they stand: the same bits
+        at = np.nonzero(row == r)[0]
+        assert len(at) >= 2
+        assert np.all(_bits(np.delete(lnl[:, at], pb.root, axis=2)) == _bits(np.delete(lnl[:, at[:1]], pb.root, axis=2))), r
+        assert np.all(node[:, at] == node[:, at[:1]]) and np.all(_bits(best[:, at]) == _bits(best[:, at[:1]])), r
+    _check_best(lnl, node, best, pb.root)
+    base = pb.log_likelihood()["lnl"]  # the all-gap row scores the base tree's own lnL on every edge
+    assert np.nanmax(np.abs(lnl[:, row == 1] - base)) <= 1e-10 * abs(base)
+
+
+def test_two_segments_and_two_query_blocks_under_a_memory_cap():
+    """the largest cap of the ladder that cuts the edges into at least two chunks and the 1100 queries into at least two, so that a
+    chunk's slab holds two segments and the best edge so far is resumed across edge chunks at every query chunk's offset: the same
+    bits as the uncapped call, with and without the lnL rows"""
+    pb, tip_mode, distinct, row, _ = _segment_case(True)
+    masks = distinct[row]
+    with engine_from_problem(pb, rescale=RESCALE_NEVER, tip_mode=tip_mode) as e:
+        e.gradient()
+        held = e.profile()["device_bytes"]  # (what the engine holds besides the batch scratch)
+        want = e.placement_log_likelihoods(masks, SEGMENT_PENDANT, split=SEGMENT_SPLIT)
+        prof = e.placement_profile()
+        scratch = prof["scratch_bytes"]
+        assert prof["edge_chunks"] == 1 and prof["query_chunks"] == 1 and scratch > 0
+        _reached_two_segments_and_two_query_blocks(e, masks)
+    found = None
+    for extra in (0.7, 0.6, 0.5, 0.4, 0.3, 0.2, 0.1):  # (test_under_a_memory_cap's ladder)
+        cap = int(held + extra * scratch)
+        with engine_from_problem(pb, rescale=RESCALE_NEVER, tip_mode=tip_mode, max_device_bytes=cap) as e:
+            e.gradient()  # (the engine's own buffers are made first: the room is what is left beside them)
+            assert e.profile()["tiles"] == 1
+            try:
+                got = e.placement_log_likelihoods(masks, SEGMENT_PENDANT, split=SEGMENT_SPLIT)
+            except EngineError as err:
+                assert err.code == EUNSUPPORTED and "scratch" in str(err), err
+                continue
+            prof = e.placement_profile()
+            print(f"cap = held + {extra} x scratch = {cap}: {prof['edge_chunks']} edge chunks x {prof['query_chunks']} query chunks")
+            assert e.profile()["device_bytes"] <= cap
+            assert _same_outputs(got, want)
+            best_only = e.placement_log_likelihoods(masks, SEGMENT_PENDANT, split=SEGMENT_SPLIT, want_lnl=False)
+            assert best_only[0] is None and _same_outputs(best_only[1:], want[1:])
+            if prof["edge_chunks"] >= 2 and prof["query_chunks"] >= 2:
+                found = prof
+                break
+    assert found is not None, "no cap cut both the edges and the queries"
+
+
+@pytest.mark.parametrize("rescale", [RESCALE_NEVER, RESCALE_AUTO])
+def test_underflow_is_reported_in_band_across_two_segments(rescale):
+    """test_underflow_is_reported_in_band's 100 columns repeated over 4096 + 70 patterns: every segment sum is -inf"""
+    pb = periodic_pair(_deep(800, 100, 4, seed=5), P_SEGMENTS, seed=5)[0]
+    masks = u.random_masks(np.random.default_rng(1), 3, pb.P)
+    with engine_from_problem(pb, rescale=rescale) as e:
+        lnl, node, best = e.placement_log_likelihoods(masks, [0.1, 0.5])
+        assert not e.rescaling  # never a switch to rescaling
+        e.pairwise_distances([[0, 1]], counts_only=True)
+        assert e.distance_profile()["segments"] >= 2  # (the same REWEIGHT_SEGMENT: see _reached_two_segments_and_two_query_blocks)
     assert np.all(np.isnan(lnl[:, :, pb.root])) and np.all(np.isneginf(np.delete(lnl, pb.root, axis=2)))
     assert np.all(np.isneginf(best)) and np.all(node == (1 if pb.root == 0 else 0))
 

@@ -209,6 +209,23 @@ def test_bits_do_not_depend_on_the_call_the_order_or_the_batch():
         assert not e.rescaling
 
 
+def test_bits_do_not_depend_on_the_order_or_the_batch_past_256_patterns():
+    """600 patterns, three trips of a thread through qopt_coefficients: shuffled candidates, and every candidate as its own call"""
+    name = "t4_p600_c4"
+    pb, tip_mode, masks, split, cands = t.case(name)
+    assert pb.P > 2 * 256
+    first = _solved(name)[0]
+    with engine_from_problem(pb, rescale=RESCALE_AUTO, tip_mode=tip_mode) as e:
+        assert _same(first, e.placement_optimize(masks, cands, split=split))  # another engine, a scratch that held nothing
+        perm = np.random.default_rng(9).permutation(len(cands))
+        assert _same([x[perm] for x in first], e.placement_optimize(masks, cands[perm], split=split))
+        for i in range(len(cands)):  # every candidate as its own call, with its query alone
+            q, n = cands[i]
+            one = e.placement_optimize(masks[q:q + 1], [[0, n]], split=split)
+            assert _same([x[[i]] for x in first], one), i
+        assert not e.rescaling
+
+
 def test_under_a_memory_cap():
     """a cap that cuts the 64 candidates into at least three chunks: the same bits; one that leaves no room for a candidate: refused"""
     name = "t9_p130_c8"

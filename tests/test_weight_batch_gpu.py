@@ -28,11 +28,15 @@ def _oracle(pb, weights, lengths=None, fold=False):
 
 
 def _check_against_oracle(pb, W, lnl, g, bl=None, fold=False):
+    shares = [0.0, 0.0]  # the worst share of each tolerance that an item used
     for b in range(len(W)):
         ref = _oracle(pb, W[b], None if bl is None else bl[b], fold)
         print(f"item {b}: lnL {lnl[b]!r} oracle {ref['lnl']!r}  max|dg| {np.abs(g[b] - ref['cat_grad']).max():.3e}")
+        shares[0] = max(shares[0], abs(lnl[b] - ref["lnl"]) / (1e-10 * abs(ref["lnl"])))
+        shares[1] = max(shares[1], np.abs(g[b] - ref["cat_grad"]).max() / (1e-9 * max(1.0, np.abs(ref["cat_grad"]).max())))
         assert abs(lnl[b] - ref["lnl"]) <= 1e-10 * abs(ref["lnl"]), (b, lnl[b], ref["lnl"])
         assert np.abs(g[b] - ref["cat_grad"]).max() <= 1e-9 * max(1.0, np.abs(ref["cat_grad"]).max()), b
+    print(f"{len(W)} items: worst share of the lnL tolerance {shares[0]:.2e}, of the gradient tolerance {shares[1]:.2e}")
 
 
 def _replicates(pb, B, seed, kind="bootstrap", keep_first=False):
@@ -48,7 +52,9 @@ def _replicates(pb, B, seed, kind="bootstrap", keep_first=False):
     return np.ascontiguousarray(W)
 
 
-# (shape, T, P, C, B, fold, pinv, gaps, ambiguity codes, weights)
+# (shape, T, P, C, B, fold, pinv, gaps, ambiguity codes, weights).  The last two: 4096 + 70 patterns are two segments of
+# k_reweight_mfma's K axis (REWEIGHT_SEGMENT = 4096), the second ragged, so k_reweight_finish adds two terms; 8 taxa and 2 categories
+# are 1 + 15 x 2 = 31 rows, two row tiles of 16 with the second ragged, and 17 or 33 replicates two or three replicate tiles
 SHARED = [
     ("random", 2, 1, 1, 1, False, None, 0.0, False, "bootstrap"),
     ("caterpillar", 3, 63, 2, 3, True, None, 0.0, False, "bootstrap"),
@@ -56,7 +62,17 @@ SHARED = [
     ("random", 37, 700, 4, 33, False, 0.25, 0.0, False, "fractional"),
     ("caterpillar", 200, 65, 8, 16, False, None, 0.0, False, "bootstrap"),
     ("random", 37, 238, 4, 3, False, None, 0.05, True, "bootstrap"),
+    ("random", 8, 4096 + 70, 2, 17, False, None, 0.03, False, "bootstrap"),
+    ("random", 8, 4096 + 70, 2, 33, True, None, 0.03, False, "fractional"),
 ]
+
+
+def _segments(e):
+    """segments of REWEIGHT_SEGMENT patterns of the engine's pattern axis.  The call's own profile does not report them; a
+    counts-only pairwise_distances call does, from the same constant (phyamd_reweight.inc), so a change of the constant shows in the
+    tests that rely on it"""
+    e.pairwise_distances([[0, 1]], counts_only=True)
+    return e.distance_profile()["segments"]
 
 
 @pytest.mark.parametrize("shape,T,P,C,B,fold,pinv,gaps,ambig,kind", SHARED)
@@ -74,6 +90,7 @@ def test_shared_lengths_match_oracle_replicate_by_replicate(shape, T, P, C, B, f
         assert prof["walks"] == 1 and prof["pattern_chunks"] == 1, prof
         assert not e.rescaling
         assert np.all(g[:, pb.root, :] == 0.0)
+        assert P <= 4096 or _segments(e) >= 2  # the rows past 4096 patterns are there for the second segment: fail, not pass, without it
         e.log_likelihood()
         plk = e.pattern_log_likelihoods()
     for b in range(B):  # lnl is the weighted sum of the pattern log-likelihoods of ONE evaluation
@@ -175,6 +192,45 @@ def test_pattern_chunks_under_a_cap():
         assert e.profile()["device_bytes"] <= cap
     assert np.abs(lc - lnl).max() <= 1e-10 * np.abs(lnl).max()
     assert np.abs(gc - g).max() <= 1e-9 * max(1.0, np.abs(g).max())
+    _check_against_oracle(pb, W, lc, gc)
+
+
+def test_a_pattern_chunk_wider_than_a_segment_under_a_cap():
+    """shared lengths, 3 x 4096 + 70 patterns: the largest cap of the ladder that cuts the patterns into at least two chunks of
+    more than 4096 patterns on average.  Chunks are equal but for the last, so the first spans at least two segments, with its own
+    k0 and Pc and (but by chance) a boundary that is no multiple of a segment.  The oracle at the suite's tolerances, and the
+    uncapped call to 1e-12 relative (the bits may depend on the cap: the chunks are added in chunk order)"""
+    P = 3 * 4096 + 70
+    pb = random_problem(8, P, 2, seed=7 * 8 + P + 2, gaps=0.03)
+    W = _replicates(pb, 17, seed=17)
+    with engine_from_problem(pb, rescale=RESCALE_NEVER) as e:
+        e.gradient()
+        held = e.profile()["device_bytes"]
+        lnl, g = e.gradient_batch_weights(W)
+        prof = e.weight_batch_profile()
+        assert prof["pattern_chunks"] == 1 and prof["items_fast"] == 17, prof
+        scratch = prof["scratch_bytes"]
+        assert _segments(e) >= 4
+    found = None
+    for extra in (0.9, 0.8, 0.7, 0.6, 0.5, 0.4, 0.3):
+        cap = int(held + extra * scratch)
+        with engine_from_problem(pb, rescale=RESCALE_NEVER, max_device_bytes=cap) as e:
+            e.gradient()
+            assert e.profile()["tiles"] == 1
+            lc, gc = e.gradient_batch_weights(W)
+            prof = e.weight_batch_profile()
+            print(f"cap = held + {extra} x scratch = {cap}: {prof}")
+            assert e.profile()["device_bytes"] <= cap
+            if prof["pattern_chunks"] >= 2:
+                found = prof
+                break
+    assert found is not None, "no cap cut the patterns"
+    assert P / found["pattern_chunks"] > 4096, found  # (else the ladder needs a rung between this cap and the one before)
+    assert found["walks"] == found["pattern_chunks"] and found["items_fast"] == 17 and found["items_sequential"] == 0, found
+    print(f"against the uncapped call: lnL {np.abs(lc - lnl).max() / np.abs(lnl).max():.3e} relative, "
+          f"gradient {np.abs(gc - g).max() / max(1.0, np.abs(g).max()):.3e}")
+    assert np.abs(lc - lnl).max() <= 1e-12 * np.abs(lnl).max()
+    assert np.abs(gc - g).max() <= 1e-12 * max(1.0, np.abs(g).max())
     _check_against_oracle(pb, W, lc, gc)
 
 
