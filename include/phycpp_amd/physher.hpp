@@ -369,6 +369,12 @@ class TreeLikelihoodInterface : public CallableModelInterface {
 	// as for NNILogLikelihoods.  The tree model and this object's own state are unchanged.
 	void PlacementLogLikelihoods(const uint8_t *masks, int queries, const double *pendant, int lengths, double split, double *logLikelihoods, int32_t *bestNodes,
 	                             double *bestLogLikelihoods);
+	// The same for a data type of 20 states (one phyamd_placement_log_likelihoods_general call; see include/physher_amd.h for the
+	// classes): codes [queries][patterns] holds a class code per query and pattern -- 0..19 a state, 20 unknown, 21 + q the set
+	// sets[q] of this call (bit s = state s is a member; setCount <= 11, sets may be null with setCount 0).  The outputs are
+	// PlacementLogLikelihoods'.  The engine behind this object keeps every partial resident from here on; the tree model is unchanged.
+	void PlacementLogLikelihoodsGeneral(const uint8_t *codes, int queries, const uint64_t *sets, int setCount, const double *pendant, int lengths, double split,
+	                                    double *logLikelihoods, int32_t *bestNodes, double *bestLogLikelihoods);
 	// The three branches around chosen placements optimised at once (one phyamd_placement_optimize call; see include/physher_amd.h
 	// for the rule): masks and queries as for PlacementLogLikelihoods; candidates [count][2] holds (query, node) pairs by the tree's
 	// node ids; pendantStart [count] may be null (0.1); split as there; branches marks what is optimised (bit 0: the node's branch

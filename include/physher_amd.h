@@ -956,6 +956,38 @@ int phyamd_placement_optimize(phyamd_engine *e, int flags, int32_t queries,
 typedef struct { int32_t candidates, edges, chunks; int64_t visits, iterations, scratch_bytes; double ms; } phyamd_placement_optimize_profile;
 int phyamd_get_placement_optimize_profile(phyamd_engine *e, phyamd_placement_optimize_profile *out);
 
+/* --- query sequences placed on every edge, 20 states --- */
+/* phyamd_placement_log_likelihoods for an engine of 20 states (proteins): its definition word for word -- the edge n, the new node z
+ * in n's place with the children n (branch sigma t_n) and the query (branch pendant[i]), z's branch (1 - sigma) t_n, NaN in the
+ * root's column, best_node the smallest node id with the largest lnL -- with another vector for the query.  A cell of codes
+ * [queries][P] is a CLASS code: 0..19 a state, 20 unknown (all states), 21 + q the CALLER's set sets[q] (bit s = state s is a
+ * member; set_count <= 11, so every code is below 32).  The sets are the call's own and not the numbering phyamd_set_tip_partials
+ * records for the engine's tips: a query is not an engine tip.  THE CODES REFER TO THE ENGINE'S OWN PATTERNS, as in the 4-state call.
+ * The tree side is read from resident partials: THE ENGINE IS AFTERWARDS ONE WITH phyamd_set_keep_partials(1) THAT HAS RUN THE
+ * FLAGS-0 GRADIENT (as after phyamd_state_posteriors); its topology, lengths and models are unchanged, a call on an engine already
+ * in that state changes nothing, and later evaluations return the bits they would have returned.  Per edge the upper partial (the
+ * message at the top of n's branch) and the node's own partial meet the split matrices, and a query enters a pattern only through
+ * its class, so per (pendant length, edge, pattern) the 32 possible weighted log site likelihoods are tabulated once -- three
+ * 20-wide products per (edge, category, 16 patterns) on the fp64 matrix cores, the categories added in category order -- and a
+ * (query, edge) score is a gather-and-add over the patterns: in order inside fixed segments of 4096, the segments in order, no
+ * atomics.  Two calls return identical bits; a (length, query, edge) result does not depend on the other queries, on their order,
+ * on whether lnl is asked for, or on the chunks of edges and queries the call ran in under the memory cap.  An lnL that underflows
+ * is -inf in band and reaches only the queries whose cells select the underflowed entries (the call does not rescale).
+ * PHYAMD_EINVAL, naming the function and the argument: phyamd_placement_log_likelihoods' argument conditions (codes for masks);
+ * set_count outside 0..11; null sets with set_count > 0; a set word of 0 or with bits at or above 2^20; a code above 20 + set_count
+ * (the query and the pattern are named); no eigen system; an engine that is not ready to evaluate.  PHYAMD_EUNSUPPORTED, naming
+ * the condition: a state count other than 20 (4: use phyamd_placement_log_likelihoods; 60 / 61: not built), more than 8 categories,
+ * an engine that is rescaling -- also when PHYAMD_RESCALE_AUTO switched it on during the call's own evaluation --, tiled patterns,
+ * explicit node matrices, a handle sharded over several devices, flags other than 0, scratch of one query on one edge that does
+ * not fit the memory cap.  The argument checks come before the handle's state is looked at.  phyamd_get_placement_profile reports
+ * the last placement call of either kind. */
+int phyamd_placement_log_likelihoods_general(phyamd_engine *e, int flags, int32_t queries,
+                                             const uint8_t *codes /* [queries][P]: class codes over the engine's patterns */,
+                                             int32_t set_count, const uint64_t *sets /* [set_count] member words, or NULL with set_count 0 */,
+                                             int32_t lengths, const double *pendant /* [lengths] */, double split,
+                                             double *lnl /* [lengths][queries][2T-1] or NULL; NaN in the root's column */,
+                                             int32_t *best_node /* [lengths][queries] or NULL */, double *best_lnl /* [lengths][queries] or NULL */);
+
 #ifdef __cplusplus
 }
 #endif

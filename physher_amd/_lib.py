@@ -161,6 +161,7 @@ SYMBOLS = [
     ("phyamd_pairwise_distances_general", C.c_int, [_P, C.c_int, C.c_int32, _P, _P, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     ("phyamd_get_distance_profile", C.c_int, [_P, C.POINTER(DistanceProfile)]),
     ("phyamd_placement_log_likelihoods", C.c_int, [_P, C.c_int, C.c_int32, _P, C.c_int32, _P, C.c_double, _P, _P, _P]),
+    ("phyamd_placement_log_likelihoods_general", C.c_int, [_P, C.c_int, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, C.c_double, _P, _P, _P]),
     ("phyamd_get_placement_profile", C.c_int, [_P, C.POINTER(PlacementProfile)]),
     ("phyamd_placement_optimize", C.c_int, [_P, C.c_int, C.c_int32, _P, C.c_int32, _P, _P, C.c_double, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32,
                                             C.c_double, C.c_int32, _P, _P, _P, _P]),

@@ -997,6 +997,14 @@ void TreeLikelihoodInterface::PlacementLogLikelihoods(const uint8_t *masks, int 
 	phyamd::check(phyamd_placement_log_likelihoods(impl_->engine, 0, queries, masks, lengths, pendant, split, logLikelihoods, bestNodes, bestLogLikelihoods));
 }
 
+void TreeLikelihoodInterface::PlacementLogLikelihoodsGeneral(const uint8_t *codes, int queries, const uint64_t *sets, int setCount, const double *pendant, int lengths,
+                                                             double split, double *logLikelihoods, int32_t *bestNodes, double *bestLogLikelihoods) {
+	if (!logLikelihoods && !bestNodes) throw Error("null logLikelihoods and bestNodes");
+	Sync();
+	phyamd::check(phyamd_placement_log_likelihoods_general(impl_->engine, 0, queries, codes, setCount, sets, lengths, pendant, split, logLikelihoods, bestNodes,
+	                                                       bestLogLikelihoods));
+}
+
 void TreeLikelihoodInterface::PlacementOptimize(const uint8_t *masks, int queries, const int32_t *candidates, int count, const double *pendantStart, double split, int branches,
                                                 double lower, double upper, double tolerance, int maxIterations, double lnlTolerance, int maxPasses, double *lengths,
                                                 double *logLikelihoods, double *initialLogLikelihoods, int32_t *passes) {

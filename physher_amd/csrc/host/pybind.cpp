@@ -359,6 +359,23 @@ PYBIND11_MODULE(_phycpp_amd, m) {
 		                          want_best ? py::object(iarray(shape, node.data())) : py::object(py::none()),
 		                          want_best ? py::object(darray(shape, best.data())) : py::object(py::none()));
 	    }, py::arg("masks"), py::arg("pendant"), py::arg("split") = 0.5, py::arg("want_lnl") = true, py::arg("want_best") = true)
+	    .def("placement_log_likelihoods_general", [](TreeLikelihoodInterface &self, py::array_t<uint8_t, py::array::c_style | py::array::forcecast> codes, darray pendant,
+	                                                 double split, py::array_t<uint64_t, py::array::c_style | py::array::forcecast> sets, bool want_lnl,
+	                                                 bool want_best) -> py::tuple {
+		    const py::ssize_t N = (py::ssize_t)self.NodeCount();
+		    if (codes.ndim() != 2 || (size_t)codes.shape(1) != self.GetPatternCount()) throw phyamd::Error("codes: [queries][pattern_count]");
+		    if (pendant.ndim() != 1) throw phyamd::Error("pendant: [lengths]");
+		    if (sets.ndim() != 1) throw phyamd::Error("sets: [set_count]");
+		    const py::ssize_t Q = codes.shape(0), L = pendant.shape(0), nsets = sets.shape(0);
+		    std::vector<double> lnl(want_lnl ? (size_t)L * Q * N : 0), best(want_best ? (size_t)L * Q : 0);
+		    std::vector<int32_t> node(best.size());
+		    self.PlacementLogLikelihoodsGeneral(codes.data(), (int)Q, nsets ? sets.data() : nullptr, (int)nsets, pendant.data(), (int)L, split, want_lnl ? lnl.data() : nullptr,
+		                                        want_best ? node.data() : nullptr, want_best ? best.data() : nullptr);
+		    const std::vector<py::ssize_t> shape{L, Q};
+		    return py::make_tuple(want_lnl ? py::object(darray({L, Q, N}, lnl.data())) : py::object(py::none()),
+		                          want_best ? py::object(iarray(shape, node.data())) : py::object(py::none()),
+		                          want_best ? py::object(darray(shape, best.data())) : py::object(py::none()));
+	    }, py::arg("codes"), py::arg("pendant"), py::arg("split") = 0.5, py::arg("sets") = py::array_t<uint64_t>(0), py::arg("want_lnl") = true, py::arg("want_best") = true)
 	    .def("placement_optimize", [](TreeLikelihoodInterface &self, py::array_t<uint8_t, py::array::c_style | py::array::forcecast> masks, iarray candidates,
 	                                  std::optional<darray> pendant_start, double split, int branches, double lower, double upper, double tolerance, int max_iterations,
 	                                  double lnl_tolerance, int max_passes) -> py::tuple {

@@ -774,6 +774,41 @@ int phyamd_placement_log_likelihoods(phyamd_engine *g, int flags, int32_t querie
 	return shard_placement(g->shards[0], flags, PlacementArgs{queries, masks, lengths, pendant, split, lnl, best_node, best_lnl});
 }
 
+// the same for 20 states: a query cell is a class code over the call's own sets
+int phyamd_placement_log_likelihoods_general(phyamd_engine *g, int flags, int32_t queries, const uint8_t *codes, int32_t set_count, const uint64_t *sets, int32_t lengths,
+                                             const double *pendant, double split, double *lnl, int32_t *best_node, double *best_lnl) {
+	static const char *const name = "phyamd_placement_log_likelihoods_general";
+	if (!lnl && !best_node) return fail(PHYAMD_EINVAL, "%s: null lnl and null best_node: one of them is the result", name);
+	if (best_lnl && !best_node) return fail(PHYAMD_EINVAL, "%s: best_lnl without best_node", name);
+	if (!codes || !pendant) return fail(PHYAMD_EINVAL, "%s: null %s", name, !codes ? "codes" : "pendant");
+	if (queries < 1) return fail(PHYAMD_EINVAL, "%s: queries must be >= 1 (got %d)", name, queries);
+	if (lengths < 1) return fail(PHYAMD_EINVAL, "%s: lengths must be >= 1 (got %d)", name, lengths);
+	if (!(split >= 0.0 && split <= 1.0)) return fail(PHYAMD_EINVAL, "%s: split %g: it must be in [0, 1]", name, split);
+	for (int32_t l = 0; l < lengths; l++)
+		if (!std::isfinite(pendant[l]) || !(pendant[l] > 0.0)) return fail(PHYAMD_EINVAL, "%s: pendant[%d] = %g: a pendant length is finite and positive", name, l, pendant[l]);
+	if (set_count < 0 || set_count > PLACE_GEN_MAX_SETS) return fail(PHYAMD_EINVAL, "%s: set_count %d is outside 0..%d (a class code is below %d)", name, set_count, PLACE_GEN_MAX_SETS, PLACE_GEN_CLASSES);
+	if (set_count > 0 && !sets) return fail(PHYAMD_EINVAL, "%s: null sets with set_count %d", name, set_count);
+	for (int32_t q = 0; q < set_count; q++)
+		if (sets[q] == 0 || sets[q] >> PLACE_GEN_STATES)
+			return fail(PHYAMD_EINVAL, "%s: sets[%d] = 0x%llx: a set has a member and no bit at or above 2^%d (bit s: state s)", name, q, (unsigned long long)sets[q], PLACE_GEN_STATES);
+	if (!g || g->shards.empty()) return fail(PHYAMD_EINVAL, "%s: null engine", name);
+	const size_t P = (size_t)g->P;
+	const unsigned top = (unsigned)(PLACE_GEN_STATES + set_count);
+	for (int32_t q = 0; q < queries; q++) {
+		const uint8_t *row = codes + (size_t)q * P;
+		unsigned bad = 0;
+		for (size_t k = 0; k < P; k++) bad |= row[k] > top;
+		if (!bad) continue;
+		for (size_t k = 0; k < P; k++)
+			if (row[k] > top)
+				return fail(PHYAMD_EINVAL, "%s: codes[%d][%zu] = %d (query %d, pattern %zu): a class code is 0..%u (a state, 20: unknown, 21 + q: sets[q] of the call's %d sets)", name, q, k,
+				            (int)row[k], q, k, top, set_count);
+	}
+	if (group_size(g) > 1)
+		return fail(PHYAMD_EUNSUPPORTED, "%s: a handle sharded over several devices is out of scope: a query's best edge would need its sums across the shards", name);
+	return shard_placement_general(g->shards[0], flags, PlacementGeneralArgs{PlacementArgs{queries, codes, lengths, pendant, split, lnl, best_node, best_lnl}, set_count, sets});
+}
+
 int phyamd_get_placement_profile(phyamd_engine *g, phyamd_placement_profile *out) {
 	return merged_profile(g, &Shard::place_prof, out, [](phyamd_placement_profile &, const phyamd_placement_profile &) {});  // (never sharded)
 }

@@ -301,7 +301,19 @@ struct Shard {
 	DeviceArray<unsigned long long> d_place_packed{&batch_mem};    // [blocks * 8][queries of the chunk]: eight patterns' masks per word
 	DeviceArray<double> d_place_slab{&batch_mem};                  // [segments][L][edges of the chunk][queries of the chunk]
 	DeviceArray<double> d_place_out{&batch_mem};                   // [L][queries of the chunk][node columns of the chunk]
-	phyamd_placement_profile place_prof{};
+	phyamd_placement_profile place_prof{};  // the last placement call of either kind
+	// phyamd_placement_log_likelihoods_general (phyamd_place_gen.inc) reads the engine's resident partials and shares the 4-state
+	// call's best edges, table, code rows, slab and result; it adds the lengths sigma t | (1 - sigma) t | pendant, their matrices
+	// (and the derivatives the matrix kernel writes beside them), the images, the call's sets, and per node column of a chunk the
+	// edge and its node's own partial
+	DeviceArray<double> d_placeg_len{&batch_mem};                  // [2 N + L]
+	DeviceArray<uint8_t> d_placeg_zero{&batch_mem};                // [2 N + L] zeros: no length has an explicit matrix
+	DeviceArray<double> d_placeg_mats{&batch_mem}, d_placeg_dmats{&batch_mem};  // [2 N + L][C][400]
+	DeviceArray<double> d_placeg_imgs{&batch_mem};                 // P_lo [N][C][image] | P_hi^T [N][C][image] | classes [L][C][640]
+	DeviceArray<unsigned long long> d_placeg_sets{&batch_mem};     // [11]
+	DeviceArray<PlaceGenEdge> d_placeg_edges{&batch_mem};          // [edges of the chunk]
+	DeviceArray<double> d_placeg_own{&batch_mem};                  // [node columns of the chunk][C][20][Pp]
+	DeviceArray<PlaceGenOwn> d_placeg_owns{&batch_mem};            // [internal nodes of the chunk]: what k_classplace_own forms each from
 	// phyamd_placement_optimize (phyamd_qopt4.inc) runs the same walk and adds to the group, per chunk of candidates sorted by edge:
 	// the chunk's distinct edges and pi o U of each, its distinct queries' mask rows, the candidates and their starts, the
 	// coefficients of the branch being visited, the results and the status words

@@ -489,8 +489,35 @@ class Engine:
         self._check(self._lib.phyamd_placement_log_likelihoods(self._h, flags, Q, _ptr(m), L, _ptr(pd), split, opt(lnl), opt(node), opt(best)))
         return lnl, node, best
 
+    def placement_log_likelihoods_general(self, codes, pendant, split=0.5, sets=(), want_lnl=True, want_best=True, flags=0):
+        """placement_log_likelihoods for an engine of 20 states (proteins): the same definition, columns and outputs -- (lnl
+        [lengths, queries, N], best_node [lengths, queries] int32, best_lnl [lengths, queries]); what is not wanted is None.
+        codes [queries, P] uint8 holds a class code per query and pattern OVER THE ENGINE'S OWN PATTERNS: 0..19 a state, 20
+        unknown, 21 + q the set sets[q] of THIS call (an integer with bit s set where state s is a member; at most 11 sets;
+        physher_amd.placement.codes_from_protein makes both).  The engine is afterwards one with set_keep_partials(True) that has
+        run the flags-0 gradient; its tree, lengths and models stay.  -inf in band where a lnL underflows.  No fallback: EngineError
+        on engines that are not 20-state, have more than 8 categories, are rescaling, tiled or sharded, or hold explicit node
+        matrices."""
+        m = np.ascontiguousarray(codes, dtype=np.uint8)
+        if m.ndim != 2 or m.shape[1] != self.P:
+            raise ValueError(f"codes must be [queries, {self.P}] (got {m.shape})")
+        pd = np.ascontiguousarray(np.atleast_1d(pendant), dtype=np.float64)
+        if pd.ndim != 1:
+            raise ValueError(f"pendant must be one-dimensional (got {pd.shape})")
+        st = np.ascontiguousarray(sets, dtype=np.uint64)
+        if st.ndim != 1:
+            raise ValueError(f"sets must be one-dimensional (got {st.shape})")
+        Q, L = m.shape[0], len(pd)
+        lnl = np.empty((L, Q, self.N)) if want_lnl else None
+        node = np.empty((L, Q), dtype=np.int32) if want_best else None
+        best = np.empty((L, Q)) if want_best else None
+        opt = lambda a: None if a is None else _ptr(a)
+        self._check(self._lib.phyamd_placement_log_likelihoods_general(self._h, flags, Q, _ptr(m), len(st), _ptr(st) if len(st) else None, L, _ptr(pd), split, opt(lnl),
+                                                                       opt(node), opt(best)))
+        return lnl, node, best
+
     def placement_profile(self):
-        """Of the last placement_log_likelihoods: queries, lengths, edges, edge_chunks, query_chunks (per edge chunk), scratch_bytes,
+        """Of the last placement_log_likelihoods or placement_log_likelihoods_general: queries, lengths, edges, edge_chunks, query_chunks (per edge chunk), scratch_bytes,
         ms."""
         p = _lib.PlacementProfile()
         self._check(self._lib.phyamd_get_placement_profile(self._h, C.byref(p)))

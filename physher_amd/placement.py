@@ -1,5 +1,5 @@
-"""NumPy helpers around Engine.placement_log_likelihoods and Engine.placement_optimize: the masks they take, the candidates the
-second takes from the first's scores, and what a placement tool makes of either result.
+"""NumPy helpers around Engine.placement_log_likelihoods, Engine.placement_log_likelihoods_general and Engine.placement_optimize: the
+masks and class codes they take, the candidates the last takes from the first's scores, and what a placement tool makes of a result.
 
 A query's masks are 4-bit numbers over the engine's own patterns, bit s = state s (nucleotides in the order A, C, G, T), 15 a gap.
 lnl [..., N] holds a query's log-likelihood on the branch above every node, NaN in the root's column."""
@@ -16,6 +16,30 @@ def masks_from_states(states, state_count=4):
         raise ValueError(f"state codes are integers (got {states.dtype})")
     single = (states >= 0) & (states < 4)
     return np.where(single, np.left_shift(1, np.where(single, states, 0)), 15).astype(np.uint8)
+
+
+AMINO_ACIDS = "ACDEFGHIKLMNPQRSTVWY"  # the engine's state order (physher_amd.synth.AA)
+PROTEIN_SETS = (("B", "DN"), ("Z", "EQ"), ("J", "IL"))  # the three standard ambiguity letters and their members
+
+
+def codes_from_protein(sequences, alphabet=AMINO_ACIDS):
+    """Protein sequences (strings of one length, or an array of single letters [queries, P]) -> (codes [queries, P] uint8, sets
+    [3] uint64) as Engine.placement_log_likelihoods_general takes them: a letter of `alphabet` is its state 0..19; B, Z and J are
+    the sets 21, 22 and 23 (D or N, E or Q, I or L; bit s of sets[q] = state s is a member); X, '-', '?' and every other symbol
+    are unknown (20).  Lower case is read as upper case.  The columns are the caller's: they have to be the engine's patterns."""
+    if len(alphabet) != 20 or len(set(alphabet.upper())) != 20 or set(alphabet.upper()) & {"B", "Z", "J"}:
+        raise ValueError("the alphabet is 20 different letters, none of them B, Z or J")
+    table = np.full(256, 20, dtype=np.uint8)
+    for s, ch in enumerate(alphabet.upper()):
+        table[ord(ch)] = table[ord(ch.lower())] = s
+    sets = np.zeros(len(PROTEIN_SETS), dtype=np.uint64)
+    for q, (letter, members) in enumerate(PROTEIN_SETS):
+        table[ord(letter)] = table[ord(letter.lower())] = 21 + q
+        sets[q] = sum(1 << alphabet.upper().index(m) for m in members)
+    rows = [np.frombuffer(s.encode("latin-1"), dtype=np.uint8) if isinstance(s, str) else np.frombuffer("".join(s).encode("latin-1"), dtype=np.uint8) for s in sequences]
+    if not rows or any(len(r) != len(rows[0]) for r in rows):
+        raise ValueError("the sequences are one or more rows of one length")
+    return table[np.stack(rows)], sets
 
 
 def top_candidates(lnl_or_best, k):
