@@ -385,6 +385,12 @@ class TreeLikelihoodInterface : public CallableModelInterface {
 	void PlacementOptimize(const uint8_t *masks, int queries, const int32_t *candidates, int count, const double *pendantStart, double split, int branches, double lower,
 	                       double upper, double tolerance, int maxIterations, double lnlTolerance, int maxPasses, double *lengths, double *logLikelihoods,
 	                       double *initialLogLikelihoods, int32_t *passes);
+	// The same for a data type of 20 states (one phyamd_placement_optimize_general call; see include/physher_amd.h for the rule in
+	// full): codes, sets and setCount as for PlacementLogLikelihoodsGeneral, everything else as for PlacementOptimize.  The engine
+	// behind this object keeps every partial resident from here on; the tree model is unchanged.
+	void PlacementOptimizeGeneral(const uint8_t *codes, int queries, const uint64_t *sets, int setCount, const int32_t *candidates, int count, const double *pendantStart,
+	                              double split, int branches, double lower, double upper, double tolerance, int maxIterations, double lnlTolerance, int maxPasses,
+	                              double *lengths, double *logLikelihoods, double *initialLogLikelihoods, int32_t *passes);
 	// Beyond the reference surface: marginal ancestral reconstruction of `count` nodes of the tree model's tree at once (one
 	// phyamd_state_posteriors call; see include/physher_amd.h for the definition): posteriors [count][patterns][states] and states
 	// [count][patterns] by the tree's node ids, row i the node nodes[i] (null: count = 2T-1 and row i is node i; tips and the

@@ -950,7 +950,7 @@ int phyamd_placement_optimize(phyamd_engine *e, int flags, int32_t queries,
                               double lnl_tolerance, int32_t max_passes,
                               double *lengths /* [count][3]: distal, pendant, proximal */, double *lnl /* [count] */,
                               double *initial_lnl /* [count] or NULL */, int32_t *passes /* [count] or NULL */);
-/* of the last phyamd_placement_optimize: candidates asked for, distinct edges among them, chunks of candidates they ran in, visits
+/* of the last phyamd_placement_optimize or phyamd_placement_optimize_general: candidates asked for, distinct edges among them, chunks of candidates they ran in, visits
  * made and proposals made over all of them, bytes of batch scratch the engine holds (see phyamd_batch_profile), wall time of the
  * call */
 typedef struct { int32_t candidates, edges, chunks; int64_t visits, iterations, scratch_bytes; double ms; } phyamd_placement_optimize_profile;
@@ -987,6 +987,70 @@ int phyamd_placement_log_likelihoods_general(phyamd_engine *e, int flags, int32_
                                              int32_t lengths, const double *pendant /* [lengths] */, double split,
                                              double *lnl /* [lengths][queries][2T-1] or NULL; NaN in the root's column */,
                                              int32_t *best_node /* [lengths][queries] or NULL */, double *best_lnl /* [lengths][queries] or NULL */);
+
+/* --- the three branches around chosen placements, 20 states --- */
+/* phyamd_placement_optimize for an engine of 20 states (proteins): the second half of the pair that
+ * phyamd_placement_log_likelihoods_general opens -- the distal, pendant and proximal branch of `count` chosen (query, edge)
+ * placements optimised in one call.  queries, codes, set_count and sets are phyamd_placement_log_likelihoods_general's: a cell of
+ * codes [queries][P] is a CLASS code over the engine's own patterns, 0..19 a state, 20 unknown (all states), 21 + q the CALLER's set
+ * sets[q] (bit s = state s is a member; set_count <= 11).  Candidate i is the query q = candidates[i][0] on the edge
+ * n = candidates[i][1], a non-root node.  Per candidate lengths holds (distal t_n, pendant t_x, proximal t_z), lnl the
+ * log-likelihood there, initial_lnl that of the start and passes the pass count.  initial_lnl and passes may be NULL.  Duplicates
+ * among the candidates are allowed.
+ * THE RULE, in full (it is phyamd_placement_optimize's, word for word; that call defines it through
+ * phyamd_optimize_branch_lengths, which does not exist for 20 states).  The tree of candidate i is the placed tree: T + 1 tips, a
+ * new node z in n's place with the left child n and the right child x (the query), everything else the engine's.  The model is the
+ * engine's eigen system, P(t r_c) = |V e^(lambda t r_c) V^-1| elementwise, and the query's vector at a pattern is the 0/1 member
+ * vector of its class code.  The start is t_n = split t_n (distal), t_x = pendant_start[i] (pendant; pendant_start NULL: 0.1) and
+ * t_z = (1 - split) t_n (proximal), t_n on the right sides the engine's.  initial_lnl is lnL of the placed tree at the start, the
+ * lengths as they are given (not clamped): phyamd_placement_log_likelihoods_general's entry at that pendant length and split, up
+ * to rounding.  `branches` marks the branches that are optimised: bit 0 n (distal), bit 1 x (pendant), bit 2 z (proximal).  A PASS
+ * visits the marked ones in the order n, x, z (z's left child, its right child, z).  A VISIT of a branch holds the other two
+ * lengths where they stand, clamps the branch's length to t_0 in [lower, upper] and runs phyamd_nni_optimize's safeguarded Newton
+ * iteration on lnL(t) of the placed tree: with the bracket [lo, hi] = [lower, upper] and t = t_0, evaluate lnL, d1 = dlnL/dt and
+ * d2 = d2lnL/dt2 at t; lo = t if d1 > 0, else hi = t; the proposal is t - d1 / d2 if d2 < 0 and it lies strictly inside
+ * (lo, hi), else the midpoint (lo + hi) / 2; the iteration ends when the proposal moves by no more than `tolerance` or after
+ * max_iterations proposals, and the last proposal is the visit's candidate length t_1.  The visit keeps t_1 if lnL(t_1) is
+ * finite and not below lnL(t_0), else it leaves t_0 (the clamped length).  After a pass the STOP TEST: if lnL after the pass
+ * minus lnL after the previous pass (the first pass: initial_lnl) is <= lnl_tolerance, the entry ends with passes = k, the
+ * number of passes made; else after max_passes passes it ends with passes = -max_passes.  lnl is lnL at the lengths returned.
+ * An lnL that is NOT FINITE at an iterate of a visit (some pattern's site likelihood is not in (0, inf): underflow, the call
+ * does not rescale) ends the entry IN BAND: lengths are the state before that visit, lnl is the value that is not finite (-inf or
+ * NaN) and passes is the negated index of the pass, counted from 1.  A branch that is not marked is never clamped or changed and
+ * comes back as its start value, bit for bit.
+ * The tree side is read from resident partials, exactly as in phyamd_placement_log_likelihoods_general: THE ENGINE IS AFTERWARDS ONE
+ * WITH phyamd_set_keep_partials(1) THAT HAS RUN THE FLAGS-0 GRADIENT; its topology, lengths and models are unchanged, and later
+ * evaluations return the bits they would have returned.  The three messages that meet at z -- the query's class vector, n's own
+ * partial and pi times the upper partial at the top of n's branch -- depend on none of the three lengths, so a candidate's whole
+ * rule runs in one workgroup without a walk, a matrix launch or a host round trip per visit: per visit the coefficients
+ * K[c][e] of lnL's exponential sum sum_c sum_e K[c][e] exp(lambda_e r_c t) are formed per pattern with three 20-wide products on
+ * the fp64 matrix cores (the query enters through tables over its 32 classes) and every iterate is a fixed-order sum over them.
+ * Two calls return identical bits; a candidate's bits depend on the engine's inputs, its query's codes, the sets, its edge and its
+ * start, and not on count, its position, the other candidates or queries, the chunks the candidates ran in, the optional outputs
+ * or what the batch scratch held.  Nothing is added with atomics.  The engine is never switched to rescaling by the solve.  The
+ * scratch is the batch scratch's: per candidate C x 20 doubles per padded pattern and per distinct internal edge of a chunk as
+ * much again; candidates that do not fit the memory cap together run in chunks.
+ * PHYAMD_EINVAL, naming the function and the argument: null codes, candidates, lengths or lnl; queries < 1 or count < 1; a
+ * candidate's query outside 0..queries-1 (with its index); branches outside 1..7; a split outside [0, 1]; a start that is not finite
+ * and > 0; bounds that are not 0 <= lower < upper < inf; a tolerance that is not finite and > 0; max_iterations or max_passes
+ * outside 1..1000; an lnl_tolerance that is not finite and >= 0; set_count outside 0..11; null sets with set_count > 0; a set word
+ * of 0 or with bits at or above 2^20; null engine; a candidate's node outside 0..2T-2 or equal to the root (with its index); a
+ * code above 20 + set_count (the query and the pattern are named); no eigen system; an engine that is not ready to evaluate.  The
+ * argument checks come before the handle's state is looked at.  There is no fallback path: PHYAMD_EUNSUPPORTED, naming the
+ * condition: a state count other than 20 (4: use phyamd_placement_optimize; 60 / 61: not built), more than 8 categories, an engine
+ * that is rescaling -- also when PHYAMD_RESCALE_AUTO switched it on during the call's own evaluation --, tiled patterns, explicit
+ * node matrices, a handle sharded over several devices, flags other than 0, scratch of one candidate that does not fit the memory
+ * cap.  phyamd_get_placement_optimize_profile reports the last call of either kind. */
+int phyamd_placement_optimize_general(phyamd_engine *e, int flags, int32_t queries,
+                                      const uint8_t *codes /* [queries][P] class codes, as phyamd_placement_log_likelihoods_general */,
+                                      int32_t set_count, const uint64_t *sets /* [set_count] member words, or NULL with set_count 0 */,
+                                      int32_t count, const int32_t *candidates /* [count][2]: (query, node) */,
+                                      const double *pendant_start /* [count] or NULL: 0.1 */, double split,
+                                      int32_t branches /* bit 0: distal (n's), bit 1: pendant (the query's), bit 2: proximal (z's); 1..7 */,
+                                      double lower, double upper, double tolerance, int32_t max_iterations,
+                                      double lnl_tolerance, int32_t max_passes,
+                                      double *lengths /* [count][3]: distal, pendant, proximal */, double *lnl /* [count] */,
+                                      double *initial_lnl /* [count] or NULL */, int32_t *passes /* [count] or NULL */);
 
 #ifdef __cplusplus
 }

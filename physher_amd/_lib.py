@@ -165,6 +165,8 @@ SYMBOLS = [
     ("phyamd_get_placement_profile", C.c_int, [_P, C.POINTER(PlacementProfile)]),
     ("phyamd_placement_optimize", C.c_int, [_P, C.c_int, C.c_int32, _P, C.c_int32, _P, _P, C.c_double, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32,
                                             C.c_double, C.c_int32, _P, _P, _P, _P]),
+    ("phyamd_placement_optimize_general", C.c_int, [_P, C.c_int, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, C.c_double, C.c_int32, C.c_double, C.c_double, C.c_double,
+                                                    C.c_int32, C.c_double, C.c_int32, _P, _P, _P, _P]),
     ("phyamd_get_placement_optimize_profile", C.c_int, [_P, C.POINTER(PlacementOptimizeProfile)]),
     ("phyamd_state_posteriors", C.c_int, [_P, C.c_int, C.c_int32, _P, _P, _P]),
     ("phyamd_site_rate_posteriors", C.c_int, [_P, _P, _P]),

@@ -1014,6 +1014,16 @@ void TreeLikelihoodInterface::PlacementOptimize(const uint8_t *masks, int querie
 	                                        lnlTolerance, maxPasses, lengths, logLikelihoods, initialLogLikelihoods, passes));
 }
 
+void TreeLikelihoodInterface::PlacementOptimizeGeneral(const uint8_t *codes, int queries, const uint64_t *sets, int setCount, const int32_t *candidates, int count,
+                                                       const double *pendantStart, double split, int branches, double lower, double upper, double tolerance,
+                                                       int maxIterations, double lnlTolerance, int maxPasses, double *lengths, double *logLikelihoods,
+                                                       double *initialLogLikelihoods, int32_t *passes) {
+	if (!lengths || !logLikelihoods) throw Error("null lengths or logLikelihoods");
+	Sync();
+	phyamd::check(phyamd_placement_optimize_general(impl_->engine, 0, queries, codes, setCount, sets, count, candidates, pendantStart, split, branches, lower, upper, tolerance,
+	                                                maxIterations, lnlTolerance, maxPasses, lengths, logLikelihoods, initialLogLikelihoods, passes));
+}
+
 size_t TreeLikelihoodInterface::StateCount() const { return (size_t)impl_->S; }
 size_t TreeLikelihoodInterface::CategoryCount() const { return (size_t)siteModel_->GetModel()->cat_count; }
 

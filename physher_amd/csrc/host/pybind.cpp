@@ -391,6 +391,25 @@ PYBIND11_MODULE(_phycpp_amd, m) {
 		    return py::make_tuple(darray({count, (py::ssize_t)3}, len.data()), darray(shape, lnl.data()), darray(shape, lnl0.data()), iarray(shape, passes.data()));
 	    }, py::arg("masks"), py::arg("candidates"), py::arg("pendant_start") = py::none(), py::arg("split") = 0.5, py::arg("branches") = 7, py::arg("lower") = 1e-8,
 	       py::arg("upper") = 10.0, py::arg("tolerance") = 1e-8, py::arg("max_iterations") = 100, py::arg("lnl_tolerance") = 1e-6, py::arg("max_passes") = 50)
+	    .def("placement_optimize_general", [](TreeLikelihoodInterface &self, py::array_t<uint8_t, py::array::c_style | py::array::forcecast> codes, iarray candidates,
+	                                          py::array_t<uint64_t, py::array::c_style | py::array::forcecast> sets, std::optional<darray> pendant_start, double split,
+	                                          int branches, double lower, double upper, double tolerance, int max_iterations, double lnl_tolerance,
+	                                          int max_passes) -> py::tuple {
+		    if (codes.ndim() != 2 || (size_t)codes.shape(1) != self.GetPatternCount()) throw phyamd::Error("codes: [queries][pattern_count]");
+		    if (candidates.ndim() != 2 || candidates.shape(1) != 2) throw phyamd::Error("candidates: [count][2]");
+		    if (sets.ndim() != 1) throw phyamd::Error("sets: [set_count]");
+		    const py::ssize_t Q = codes.shape(0), count = candidates.shape(0), nsets = sets.shape(0);
+		    if (pendant_start && (pendant_start->ndim() != 1 || pendant_start->shape(0) != count)) throw phyamd::Error("pendant_start: [count]");
+		    std::vector<double> len((size_t)count * 3), lnl((size_t)count), lnl0(lnl.size());
+		    std::vector<int32_t> passes(lnl.size());
+		    self.PlacementOptimizeGeneral(codes.data(), (int)Q, nsets ? sets.data() : nullptr, (int)nsets, candidates.data(), (int)count,
+		                                  pendant_start ? pendant_start->data() : nullptr, split, branches, lower, upper, tolerance, max_iterations, lnl_tolerance, max_passes,
+		                                  len.data(), lnl.data(), lnl0.data(), passes.data());
+		    const std::vector<py::ssize_t> shape{count};
+		    return py::make_tuple(darray({count, (py::ssize_t)3}, len.data()), darray(shape, lnl.data()), darray(shape, lnl0.data()), iarray(shape, passes.data()));
+	    }, py::arg("codes"), py::arg("candidates"), py::arg("sets") = py::array_t<uint64_t>(0), py::arg("pendant_start") = py::none(), py::arg("split") = 0.5,
+	       py::arg("branches") = 7, py::arg("lower") = 1e-8, py::arg("upper") = 10.0, py::arg("tolerance") = 1e-8, py::arg("max_iterations") = 100,
+	       py::arg("lnl_tolerance") = 1e-6, py::arg("max_passes") = 50)
 	    .def("state_posteriors", [](TreeLikelihoodInterface &self, std::optional<iarray> nodes, bool want_posteriors, bool want_states) -> py::tuple {
 		    const py::ssize_t N = (py::ssize_t)self.NodeCount(), P = (py::ssize_t)self.GetPatternCount(), S = (py::ssize_t)self.StateCount();
 		    if (nodes && nodes->ndim() != 1) throw phyamd::Error("nodes: [count]");

@@ -855,6 +855,57 @@ int phyamd_placement_optimize(phyamd_engine *g, int flags, int32_t queries, cons
 	                                                      max_passes, lengths, lnl, initial_lnl, passes});
 }
 
+// the same for 20 states: phyamd_placement_optimize's argument checks, then the codes and sets checks of
+// phyamd_placement_log_likelihoods_general
+int phyamd_placement_optimize_general(phyamd_engine *g, int flags, int32_t queries, const uint8_t *codes, int32_t set_count, const uint64_t *sets, int32_t count,
+                                      const int32_t *candidates, const double *pendant_start, double split, int32_t branches, double lower, double upper, double tolerance,
+                                      int32_t max_iterations, double lnl_tolerance, int32_t max_passes, double *lengths, double *lnl, double *initial_lnl, int32_t *passes) {
+	static const char *const name = "phyamd_placement_optimize_general";
+	if (!codes || !candidates || !lengths || !lnl) return fail(PHYAMD_EINVAL, "%s: null %s", name, !codes ? "codes" : !candidates ? "candidates" : !lengths ? "lengths" : "lnl");
+	if (queries < 1) return fail(PHYAMD_EINVAL, "%s: queries must be >= 1 (got %d)", name, queries);
+	if (count < 1) return fail(PHYAMD_EINVAL, "%s: count must be >= 1 (got %d)", name, count);
+	for (int32_t i = 0; i < count; i++)
+		if (candidates[2 * (size_t)i] < 0 || candidates[2 * (size_t)i] >= queries)
+			return fail(PHYAMD_EINVAL, "%s: candidates[%d] = (%d, %d): the query is outside 0..%d", name, i, candidates[2 * (size_t)i], candidates[2 * (size_t)i + 1], queries - 1);
+	if (branches < 1 || branches > 7) return fail(PHYAMD_EINVAL, "%s: branches %d is outside 1..7 (bit 0: distal, bit 1: pendant, bit 2: proximal)", name, branches);
+	if (!(split >= 0.0 && split <= 1.0)) return fail(PHYAMD_EINVAL, "%s: split %g: it must be in [0, 1]", name, split);
+	for (int32_t i = 0; i < count && pendant_start; i++)
+		if (!std::isfinite(pendant_start[i]) || !(pendant_start[i] > 0.0))
+			return fail(PHYAMD_EINVAL, "%s: pendant_start[%d] = %g: a pendant length is finite and positive", name, i, pendant_start[i]);
+	if (!(lower >= 0.0 && lower < upper && std::isfinite(upper))) return fail(PHYAMD_EINVAL, "%s: bounds [%g, %g]: they must be 0 <= lower < upper < inf", name, lower, upper);
+	if (!(tolerance > 0.0 && std::isfinite(tolerance))) return fail(PHYAMD_EINVAL, "%s: tolerance %g: it must be finite and positive", name, tolerance);
+	if (max_iterations < 1 || max_iterations > 1000) return fail(PHYAMD_EINVAL, "%s: max_iterations %d is outside 1..1000", name, max_iterations);
+	if (!(lnl_tolerance >= 0.0 && std::isfinite(lnl_tolerance))) return fail(PHYAMD_EINVAL, "%s: lnl_tolerance %g: it must be finite and not negative", name, lnl_tolerance);
+	if (max_passes < 1 || max_passes > 1000) return fail(PHYAMD_EINVAL, "%s: max_passes %d is outside 1..1000", name, max_passes);
+	if (set_count < 0 || set_count > PLACE_GEN_MAX_SETS) return fail(PHYAMD_EINVAL, "%s: set_count %d is outside 0..%d (a class code is below %d)", name, set_count, PLACE_GEN_MAX_SETS, PLACE_GEN_CLASSES);
+	if (set_count > 0 && !sets) return fail(PHYAMD_EINVAL, "%s: null sets with set_count %d", name, set_count);
+	for (int32_t q = 0; q < set_count; q++)
+		if (sets[q] == 0 || sets[q] >> PLACE_GEN_STATES)
+			return fail(PHYAMD_EINVAL, "%s: sets[%d] = 0x%llx: a set has a member and no bit at or above 2^%d (bit s: state s)", name, q, (unsigned long long)sets[q], PLACE_GEN_STATES);
+	if (!g || g->shards.empty()) return fail(PHYAMD_EINVAL, "%s: null engine", name);
+	for (int32_t i = 0; i < count; i++)
+		if (candidates[2 * (size_t)i + 1] < 0 || candidates[2 * (size_t)i + 1] >= g->N)
+			return fail(PHYAMD_EINVAL, "%s: candidates[%d] = (%d, %d): the node is outside 0..%d", name, i, candidates[2 * (size_t)i], candidates[2 * (size_t)i + 1], g->N - 1);
+	const size_t P = (size_t)g->P;
+	const unsigned top = (unsigned)(PLACE_GEN_STATES + set_count);
+	for (int32_t q = 0; q < queries; q++) {
+		const uint8_t *row = codes + (size_t)q * P;
+		unsigned bad = 0;
+		for (size_t k = 0; k < P; k++) bad |= row[k] > top;
+		if (!bad) continue;
+		for (size_t k = 0; k < P; k++)
+			if (row[k] > top)
+				return fail(PHYAMD_EINVAL, "%s: codes[%d][%zu] = %d (query %d, pattern %zu): a class code is 0..%u (a state, 20: unknown, 21 + q: sets[q] of the call's %d sets)", name, q, k,
+				            (int)row[k], q, k, top, set_count);
+	}
+	if (group_size(g) > 1)
+		return fail(PHYAMD_EUNSUPPORTED, "%s: a handle sharded over several devices is out of scope: every iteration of a visit would need a sum across the shards", name);
+	return shard_placement_optimize_general(g->shards[0], flags,
+	                                        PlacementOptimizeGeneralArgs{PlacementOptimizeArgs{queries, codes, count, candidates, pendant_start, split, branches, lower, upper, tolerance,
+	                                                                                           max_iterations, lnl_tolerance, max_passes, lengths, lnl, initial_lnl, passes},
+	                                                                     set_count, sets});
+}
+
 int phyamd_get_placement_optimize_profile(phyamd_engine *g, phyamd_placement_optimize_profile *out) {
 	return merged_profile(g, &Shard::qopt_prof, out, [](phyamd_placement_optimize_profile &, const phyamd_placement_optimize_profile &) {});  // (never sharded)
 }

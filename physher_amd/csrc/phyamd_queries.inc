@@ -1881,6 +1881,177 @@ int shard_placement_optimize(Shard *e, int flags, const PlacementOptimizeArgs &o
 	return profiled_call(e, &Shard::qopt_prof, start, [&](phyamd_placement_optimize_profile &prof) { return run_placement_optimize(e, flags, o, prof); });
 }
 
+// ---- the same for 20 states (phyamd_placement_optimize_general) -------------------------------------------------------------------
+
+struct PlacementOptimizeGeneralArgs {
+	PlacementOptimizeArgs p;  // masks: the class codes [queries][P], validated (phyamd_placement_optimize_general)
+	int32_t set_count;
+	const uint64_t *sets;     // [set_count], validated
+};
+
+// for the `chunk` candidates that run at once -- whatever their edges and queries: as many of each as there can be -- the call's
+// sets, the own partials of the distinct internal edges and what k_classplace_own forms each from, the distinct queries' code rows,
+// the candidates, their starts, coefficients, results and status words
+ScratchPlan qopt_gen_plan(Shard *e, size_t chunk) {
+	const size_t D = sizeof(double), npd = node_partial_doubles(e);
+	const size_t owns = std::min(chunk, (size_t)std::max(0, e->T - 2));
+	ScratchPlan p;
+	p.add(e->d_placeg_sets, 0, sizeof(unsigned long long) * PLACE_GEN_MAX_SETS);
+	p.add(e->d_placeg_own, 0, D * owns * npd);
+	p.add(e->d_placeg_owns, 0, sizeof(PlaceGenOwn) * owns);
+	p.add(e->d_qopt_masks, 0, chunk * (size_t)e->P);
+	p.add(e->d_qoptg_cands, 0, sizeof(ClassOptCand) * chunk);
+	p.add(e->d_qopt_start, 0, D * chunk * 3);
+	p.add(e->d_qopt_K, 0, D * chunk * npd);
+	p.add(e->d_qopt_res, 0, D * chunk * 5);
+	p.add(e->d_qopt_status, 0, sizeof(int32_t) * chunk * QOPT_STATUS);
+	return p;
+}
+
+// the engine's resident partials (require_resident_partials: the engine is afterwards a keep-partials engine that has run the
+// flags-0 gradient), then chunk by chunk of the candidates sorted by edge: the own partials of the chunk's distinct internal edges
+// and one workgroup per candidate that runs its whole rule.  Writes only the batch scratch beyond that evaluation
+int run_placement_optimize_general(Shard *e, int flags, const PlacementOptimizeGeneralArgs &g, phyamd_placement_optimize_profile &prof) {
+	static const char *const name = "phyamd_placement_optimize_general";
+	const PlacementOptimizeArgs &o = g.p;
+	if (e->S == 4) return fail(PHYAMD_EUNSUPPORTED, "%s: the class tables are built for 20 states (the engine has 4: use phyamd_placement_optimize)", name);
+	if (e->S != PLACE_GEN_STATES) return fail(PHYAMD_EUNSUPPORTED, "%s: the class tables are built for 20 states (the engine has %d: tables of 64 classes are not built)", name, e->S);
+	if (e->C > BATCH_MAX_CATEGORIES) return fail(PHYAMD_EUNSUPPORTED, "%s: %d rate categories (at most %d categories)", name, e->C, BATCH_MAX_CATEGORIES);
+	if (flags != 0) return fail(PHYAMD_EUNSUPPORTED, "%s: flags %d (no flags are defined: pass 0)", name, flags);
+	if (e->tiles > 1) return fail(PHYAMD_EUNSUPPORTED, "%s: the patterns are tiled and the call needs every partial of all patterns resident", name);
+	if (std::any_of(e->explicit_host.begin(), e->explicit_host.end(), [](uint8_t x) { return x != 0; }))
+		return fail(PHYAMD_EUNSUPPORTED, "%s: a node has explicit matrices, which cannot be split at sigma", name);
+	if (!e->have_eigen) return fail(PHYAMD_EINVAL, "%s needs the eigen system (phyamd_set_eigen): the likelihood in a branch length is formed from it", name);
+	int rc;
+	if ((rc = check_ready(e))) return rc;
+	const int T = e->T, C = e->C, P = e->P, root = e->root;
+	const size_t count = (size_t)o.count;
+	for (size_t i = 0; i < count; i++)
+		if (o.candidates[2 * i + 1] == root)
+			return fail(PHYAMD_EINVAL, "%s: candidates[%zu] = (%d, %d): the root (node %d) has no branch to place a query on", name, i, o.candidates[2 * i], root, root);
+	static const char *const rescaling = "%s: the engine is rescaling%s and the solve does not rescale (underflow is otherwise -inf in band)";
+	if (e->scaling_on) return fail(PHYAMD_EUNSUPPORTED, rescaling, name, "");
+	if ((rc = require_resident_partials(e, name))) return rc;
+	if (e->scaling_on) return fail(PHYAMD_EUNSUPPORTED, rescaling, name, " (PHYAMD_RESCALE_AUTO switched it on during the call's own evaluation)");
+	if (e->tiles > 1) return fail(PHYAMD_EUNSUPPORTED, "%s: the patterns are tiled and the call needs every partial of all patterns resident", name);
+	const size_t npd = node_partial_doubles(e), msz = (size_t)C * PLACE_GEN_MATRIX;
+	// the candidates by edge, then query, then position: a chunk's candidates of one edge read the same own partial
+	std::vector<int32_t> order(count);
+	for (size_t i = 0; i < count; i++) order[i] = (int32_t)i;
+	std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
+		const int32_t *ca = o.candidates + 2 * (size_t)a, *cb = o.candidates + 2 * (size_t)b;
+		return ca[1] != cb[1] ? ca[1] < cb[1] : ca[0] != cb[0] ? ca[0] < cb[0] : a < b;
+	});
+	prof.edges = 1;
+	for (size_t i = 1; i < count; i++) prof.edges += o.candidates[2 * (size_t)order[i] + 1] != o.candidates[2 * (size_t)order[i - 1] + 1];
+	for (size_t i = 0; i < count; i++) {
+		const int n = o.candidates[2 * i + 1];
+		if (e->sched.upper_slot[n] < 0 || !e->d_upper) return fail(PHYAMD_EDEVICE, "%s: node %d has no resident upper partial", name, n);
+	}
+	// the chunk: all candidates (at most gridDim.x's) if the scratch holds as much or has room for it, else what fits
+	const size_t want = std::min<size_t>(count, BATCH_MAX_CHUNK);
+	size_t chunk = want;
+	if (!qopt_gen_plan(e, want).held(1)) {
+		const double room = scratch_room(e, (double)batch_scratch_bytes(e), EngineRoom::MayGrow);
+		chunk = largest_that(1, want, [&](size_t x) {
+			const ScratchPlan p = qopt_gen_plan(e, x);
+			return (double)(p.fixed_bytes() + p.item_bytes()) <= room;
+		});
+		if (chunk < 1) {
+			const ScratchPlan one = qopt_gen_plan(e, 1);
+			return fail(PHYAMD_EUNSUPPORTED, "%s: the scratch of one candidate (%zu bytes: its node's own partial and its coefficients, a node's partial each) does not fit the memory budget",
+			            name, one.fixed_bytes() + one.item_bytes());
+		}
+	}
+	const ScratchPlan plan = qopt_gen_plan(e, chunk);
+	if ((rc = ensure_batch_scratch(e, 1, plan))) return rc;
+	unsigned long long sets[PLACE_GEN_MAX_SETS] = {};
+	for (int q = 0; q < g.set_count; q++) sets[q] = g.sets[q];
+	HIP_TRY(hipMemcpyAsync(e->d_placeg_sets, sets, sizeof sets, hipMemcpyHostToDevice, e->stream));
+	std::vector<PlaceGenOwn> owns;
+	std::vector<ClassOptCand> cands;
+	std::vector<double> start, out;
+	std::vector<uint8_t> rows;
+	std::vector<int32_t> row_of((size_t)o.queries), status;
+	for (size_t first = 0; first < count; first += chunk) {
+		const size_t n = std::min(chunk, count - first);
+		owns.clear(), cands.clear(), start.clear(), rows.clear();
+		std::fill(row_of.begin(), row_of.end(), -1);
+		int last_node = -1;
+		const double *own_of_last = nullptr;
+		for (size_t i = 0; i < n; i++) {
+			const size_t at = (size_t)order[first + i];
+			const int q = o.candidates[2 * at], node = o.candidates[2 * at + 1];
+			if (node != last_node) {
+				last_node = node, own_of_last = nullptr;
+				if (node >= T) {  // a stored array is the message P_n p_n: the node's own partial, into this edge's temporary
+					PlaceGenOwn own{};
+					own.out = e->d_placeg_own.get() + owns.size() * npd;
+					const int ch[2] = {e->left[node], e->right[node]};
+					for (int side = 0; side < 2; side++) {
+						const int v = ch[side];
+						if (v >= T && e->sched.core_index[v] < 0) return fail(PHYAMD_EDEVICE, "%s: node %d has no resident lower partial", name, v);
+						(side ? own.mat_r : own.mat_l) = e->d_mats + (size_t)v * msz;
+						(side ? own.src_r : own.src_l) = v < T ? nullptr : e->d_lower + (size_t)e->sched.core_index[v] * npd;
+						(side ? own.row_r : own.row_l) = v < T ? e->d_tipmask + (size_t)v * P : nullptr;
+					}
+					owns.push_back(own);
+					own_of_last = own.out;
+				}
+			}
+			if (row_of[q] < 0) {
+				row_of[q] = (int32_t)(rows.size() / (size_t)P);
+				rows.insert(rows.end(), o.masks + (size_t)q * P, o.masks + (size_t)(q + 1) * P);
+			}
+			cands.push_back(ClassOptCand{e->d_upper + (size_t)e->sched.upper_slot[node] * npd, own_of_last, node, row_of[q]});
+			start.push_back(o.split * e->lengths[node]);
+			start.push_back(o.pendant_start ? o.pendant_start[at] : 0.1);
+			start.push_back((1.0 - o.split) * e->lengths[node]);
+		}
+		if (!owns.empty()) {
+			HIP_TRY(hipMemcpyAsync(e->d_placeg_owns, owns.data(), sizeof(PlaceGenOwn) * owns.size(), hipMemcpyHostToDevice, e->stream));
+			hipLaunchKernelGGL(k_classplace_own, dim3((unsigned)((P + 255) / 256), (unsigned)owns.size(), (unsigned)C), dim3(256), 0, e->stream, e->d_placeg_owns.get(), P, e->Pp,
+			                   e->d_tipsets.get());
+		}
+		HIP_TRY(hipMemcpyAsync(e->d_qopt_masks, rows.data(), rows.size(), hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_qoptg_cands, cands.data(), sizeof(ClassOptCand) * n, hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_qopt_start, start.data(), sizeof(double) * start.size(), hipMemcpyHostToDevice, e->stream));
+		ClassOptArgs s{};
+		s.cands = e->d_qoptg_cands, s.P = P, s.Pp = e->Pp, s.C = C, s.fold = e->upper_fold ? 1 : 0, s.set_count = g.set_count;
+		s.branches = o.branches, s.max_iterations = o.max_iterations, s.max_passes = o.max_passes;
+		s.lower = o.lower, s.upper = o.upper, s.tolerance = o.tolerance, s.lnl_tolerance = o.lnl_tolerance;
+		s.tipcode = e->d_tipmask, s.tipsets = e->d_tipsets, s.sets = e->d_placeg_sets, s.codes = e->d_qopt_masks;
+		s.freqs = e->d_freqs, s.props = e->d_props, s.model = e->d_model, s.rates = e->d_rates, s.weights = e->d_weights;
+		s.start = e->d_qopt_start, s.K = e->d_qopt_K, s.out = e->d_qopt_res, s.status = e->d_qopt_status;
+		hipLaunchKernelGGL(k_classopt_solve, dim3((unsigned)n), dim3(CLASSOPT_THREADS), 0, e->stream, s);
+		HIP_TRY(hipGetLastError());
+		out.resize(n * 5);
+		status.resize(n * QOPT_STATUS);
+		HIP_TRY(hipMemcpyAsync(out.data(), e->d_qopt_res, sizeof(double) * out.size(), hipMemcpyDeviceToHost, e->stream));
+		HIP_TRY(hipMemcpyAsync(status.data(), e->d_qopt_status, sizeof(int32_t) * status.size(), hipMemcpyDeviceToHost, e->stream));
+		HIP_TRY(hipStreamSynchronize(e->stream));  // (the next chunk writes the same arrays; also covers `sets` and the lists)
+		for (size_t i = 0; i < n; i++) {
+			const size_t to = (size_t)order[first + i];
+			const double *v = &out[i * 5];
+			std::copy(v, v + 3, o.lengths + to * 3);
+			o.lnl[to] = v[3];
+			if (o.initial_lnl) o.initial_lnl[to] = v[4];
+			if (o.passes) o.passes[to] = status[i * QOPT_STATUS + QOPT_PASSES];
+			prof.visits += status[i * QOPT_STATUS + QOPT_VISITS];
+			prof.iterations += status[i * QOPT_STATUS + QOPT_ITERATIONS];
+		}
+		prof.chunks++;
+	}
+	return PHYAMD_OK;
+}
+
+int shard_placement_optimize_general(Shard *e, int flags, const PlacementOptimizeGeneralArgs &g) {
+	CHECK_ENGINE(e);
+	phyamd_placement_optimize_profile start{};
+	start.candidates = g.p.count;
+	return profiled_call(e, &Shard::qopt_prof, start, [&](phyamd_placement_optimize_profile &prof) { return run_placement_optimize_general(e, flags, g, prof); });
+}
+
 // ---- per-pattern posteriors (phyamd_state_posteriors, phyamd_site_rate_posteriors) ---------------------------------------------
 
 // The staging arrays of the two calls, and rows of a chunk that fit beside the engine.  per_row[a]: bytes a row takes in array a

@@ -325,7 +325,11 @@ struct Shard {
 	DeviceArray<double> d_qopt_K{&batch_mem};           // [candidate][C][4][blocks * 64]
 	DeviceArray<double> d_qopt_res{&batch_mem};         // [candidate][t_n, t_x, t_z, lnl, initial_lnl]
 	DeviceArray<int32_t> d_qopt_status{&batch_mem};     // [candidate][QOPT_STATUS]
-	phyamd_placement_optimize_profile qopt_prof{};
+	phyamd_placement_optimize_profile qopt_prof{};  // the last placement-optimise call of either kind
+	// phyamd_placement_optimize_general (phyamd_qopt_gen.inc) walks nothing: it reads the resident partials like
+	// phyamd_placement_log_likelihoods_general and shares its sets and own partials (here: per distinct internal edge of a chunk) and
+	// the 4-state call's code rows, starts, coefficients [candidate][C][20][Pp], results and status words; it adds its candidates
+	DeviceArray<ClassOptCand> d_qoptg_cands{&batch_mem};  // [candidate]
 	// phyamd_state_posteriors / phyamd_site_rate_posteriors (phyamd_post.inc): the rows of a chunk, their staged results -- [rows][P][S]
 	// posteriors and [rows][P] states, or [P][C] + [P] site rates -- and, 20 / 60 / 61 states, each row's own partial p_n (true_lower_gen).
 	// On demand, like d_branch: the calls read what the keep-partials gradient left and have no entry in the record above

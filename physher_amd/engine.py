@@ -555,8 +555,42 @@ class Engine:
                                                         max_iterations, lnl_tolerance, max_passes, _ptr(lengths), _ptr(lnl), opt(lnl0), opt(passes)))
         return lengths, lnl, lnl0, passes
 
+    def placement_optimize_general(self, codes, candidates, sets=None, pendant_start=None, split=0.5, branches=7, lower=1e-8, upper=10.0, tolerance=1e-8,
+                                   max_iterations=100, lnl_tolerance=1e-6, max_passes=50, want_initial_lnl=True, want_passes=True, flags=0):
+        """placement_optimize for an engine of 20 states (proteins): the same rule, arguments and outputs -- (lengths [count, 3],
+        lnl [count], initial_lnl [count], passes [count] int32; the last two None when not wanted) -- with class codes for the
+        queries.  codes [queries, P] uint8 and sets are placement_log_likelihoods_general's: 0..19 a state, 20 unknown, 21 + q the
+        set sets[q] of THIS call (at most 11).  candidates [count, 2] int32 holds (query, node) pairs
+        (physher_amd.placement.top_candidates picks them from a placement_log_likelihoods_general result;
+        physher_amd.placement.likelihood_weight_ratios(lnl, queries) takes the sparse result).  The engine is afterwards one with
+        set_keep_partials(True) that has run the flags-0 gradient; its tree, lengths and models stay.  A lnL that is not finite ends
+        an entry in band with passes negative.  No fallback: EngineError where placement_log_likelihoods_general refuses."""
+        m = np.ascontiguousarray(codes, dtype=np.uint8)
+        if m.ndim != 2 or m.shape[1] != self.P:
+            raise ValueError(f"codes must be [queries, {self.P}] (got {m.shape})")
+        cd = np.ascontiguousarray(candidates, dtype=np.int32)
+        if cd.ndim != 2 or cd.shape[1] != 2:
+            raise ValueError(f"candidates must be [count, 2] (got {cd.shape})")
+        sw = np.ascontiguousarray(() if sets is None else sets, dtype=np.uint64)
+        if sw.ndim != 1:
+            raise ValueError(f"sets must be one-dimensional (got {sw.shape})")
+        count = len(cd)
+        st = None
+        if pendant_start is not None:
+            st = np.ascontiguousarray(pendant_start, dtype=np.float64)
+            if st.shape != (count,):
+                raise ValueError(f"pendant_start must be [{count}] (got {st.shape})")
+        lengths, lnl = np.empty((count, 3)), np.empty(count)
+        lnl0 = np.empty(count) if want_initial_lnl else None
+        passes = np.empty(count, dtype=np.int32) if want_passes else None
+        opt = lambda a: None if a is None else _ptr(a)
+        self._check(self._lib.phyamd_placement_optimize_general(self._h, flags, m.shape[0], _ptr(m), len(sw), _ptr(sw) if len(sw) else None, count, _ptr(cd), opt(st), split,
+                                                                branches, lower, upper, tolerance, max_iterations, lnl_tolerance, max_passes, _ptr(lengths), _ptr(lnl),
+                                                                opt(lnl0), opt(passes)))
+        return lengths, lnl, lnl0, passes
+
     def placement_optimize_profile(self):
-        """Of the last placement_optimize: candidates, edges (distinct among them), chunks (of candidates), visits and iterations
+        """Of the last placement_optimize or placement_optimize_general: candidates, edges (distinct among them), chunks (of candidates), visits and iterations
         (over all candidates), scratch_bytes, ms."""
         p = _lib.PlacementOptimizeProfile()
         self._check(self._lib.phyamd_get_placement_optimize_profile(self._h, C.byref(p)))

@@ -1,5 +1,6 @@
-"""NumPy helpers around Engine.placement_log_likelihoods, Engine.placement_log_likelihoods_general and Engine.placement_optimize: the
-masks and class codes they take, the candidates the last takes from the first's scores, and what a placement tool makes of a result.
+"""NumPy helpers around Engine.placement_log_likelihoods, Engine.placement_log_likelihoods_general, Engine.placement_optimize and
+Engine.placement_optimize_general: the masks and class codes they take, the candidates the optimising calls take from the scoring
+calls' results, and what a placement tool makes of a result.
 
 A query's masks are 4-bit numbers over the engine's own patterns, bit s = state s (nucleotides in the order A, C, G, T), 15 a gap.
 lnl [..., N] holds a query's log-likelihood on the branch above every node, NaN in the root's column."""
@@ -43,8 +44,9 @@ def codes_from_protein(sequences, alphabet=AMINO_ACIDS):
 
 
 def top_candidates(lnl_or_best, k):
-    """One pendant length's scores [Q, N] (Engine.placement_log_likelihoods' lnl[i]) -> the candidates [count, 2] int32 of
-    Engine.placement_optimize: per query its k best edges as (query, node) rows, query after query, the best edge first.  Ties go
+    """One pendant length's scores [Q, N] (lnl[i] of Engine.placement_log_likelihoods or, for 20 states,
+    Engine.placement_log_likelihoods_general) -> the candidates [count, 2] int32 of Engine.placement_optimize and
+    Engine.placement_optimize_general: per query its k best edges as (query, node) rows, query after query, the best edge first.  Ties go
     to the smaller node id; a column of NaN (the root's) is never chosen and neither is a NaN entry; a query with fewer than k
     usable edges gets as many as it has.  A one-dimensional argument is best_node [Q] of one length: every query's one edge."""
     a = np.asarray(lnl_or_best)
@@ -67,7 +69,8 @@ def likelihood_weight_ratios(lnl, queries=None):
     """The likelihood weight ratio of every edge (EPA / pplacer's LWR): exp(lnl) normalised over the edges of each query, a softmax
     over the last axis.  NaN entries (the root's column) and -inf entries (underflow) get 0; a row without any finite entry is all
     0.  Stable: the row's largest lnL is taken off before exp.
-    queries: lnl [count] is laid out sparsely, as Engine.placement_optimize returns it -- queries [count] holds each entry's query
+    queries: lnl [count] is laid out sparsely, as Engine.placement_optimize and Engine.placement_optimize_general return it --
+    queries [count] holds each entry's query
     (candidates[:, 0]), in any order -- and the result [count] is normalised over the entries of each query."""
     if queries is not None:
         lnl, queries = np.asarray(lnl, dtype=np.float64), np.asarray(queries)
