@@ -746,19 +746,55 @@ int phyamd_get_distance_profile(phyamd_engine *g, phyamd_distance_profile *out) 
 	return merged_profile(g, &Shard::dist_prof, out, [](phyamd_distance_profile &, const phyamd_distance_profile &) {});  // (never sharded)
 }
 
-// one device only: a query's lnL on an edge would be the sum of the shards', and its best edge follows from the sums
-int phyamd_placement_log_likelihoods(phyamd_engine *g, int flags, int32_t queries, const uint8_t *masks, int32_t lengths, const double *pendant, double split, double *lnl,
-                                     int32_t *best_node, double *best_lnl) {
-	static const char *const name = "phyamd_placement_log_likelihoods";
+// the argument checks of the four placement calls, each written once: an entry point runs them in its own order, the engine's own
+// check among them (callers see the first check that fails)
+
+// rows_word: "masks" or "codes", what the caller's rows are called
+static int check_placement_score_arguments(const char *name, const char *rows_word, const uint8_t *rows, int32_t queries, int32_t lengths, const double *pendant, double split,
+                                    const double *lnl, const int32_t *best_node, const double *best_lnl) {
 	if (!lnl && !best_node) return fail(PHYAMD_EINVAL, "%s: null lnl and null best_node: one of them is the result", name);
 	if (best_lnl && !best_node) return fail(PHYAMD_EINVAL, "%s: best_lnl without best_node", name);
-	if (!masks || !pendant) return fail(PHYAMD_EINVAL, "%s: null %s", name, !masks ? "masks" : "pendant");
+	if (!rows || !pendant) return fail(PHYAMD_EINVAL, "%s: null %s", name, !rows ? rows_word : "pendant");
 	if (queries < 1) return fail(PHYAMD_EINVAL, "%s: queries must be >= 1 (got %d)", name, queries);
 	if (lengths < 1) return fail(PHYAMD_EINVAL, "%s: lengths must be >= 1 (got %d)", name, lengths);
 	if (!(split >= 0.0 && split <= 1.0)) return fail(PHYAMD_EINVAL, "%s: split %g: it must be in [0, 1]", name, split);
 	for (int32_t l = 0; l < lengths; l++)
 		if (!std::isfinite(pendant[l]) || !(pendant[l] > 0.0)) return fail(PHYAMD_EINVAL, "%s: pendant[%d] = %g: a pendant length is finite and positive", name, l, pendant[l]);
-	if (!g || g->shards.empty()) return fail(PHYAMD_EINVAL, "%s: null engine", name);
+	return PHYAMD_OK;
+}
+
+static int check_placement_optimize_arguments(const char *name, const char *rows_word, const PlacementOptimizeArgs &o) {
+	const int32_t *candidates = o.candidates;
+	if (!o.masks || !candidates || !o.lengths || !o.lnl)
+		return fail(PHYAMD_EINVAL, "%s: null %s", name, !o.masks ? rows_word : !candidates ? "candidates" : !o.lengths ? "lengths" : "lnl");
+	if (o.queries < 1) return fail(PHYAMD_EINVAL, "%s: queries must be >= 1 (got %d)", name, o.queries);
+	if (o.count < 1) return fail(PHYAMD_EINVAL, "%s: count must be >= 1 (got %d)", name, o.count);
+	for (int32_t i = 0; i < o.count; i++)
+		if (candidates[2 * (size_t)i] < 0 || candidates[2 * (size_t)i] >= o.queries)
+			return fail(PHYAMD_EINVAL, "%s: candidates[%d] = (%d, %d): the query is outside 0..%d", name, i, candidates[2 * (size_t)i], candidates[2 * (size_t)i + 1], o.queries - 1);
+	if (o.branches < 1 || o.branches > 7) return fail(PHYAMD_EINVAL, "%s: branches %d is outside 1..7 (bit 0: distal, bit 1: pendant, bit 2: proximal)", name, o.branches);
+	if (!(o.split >= 0.0 && o.split <= 1.0)) return fail(PHYAMD_EINVAL, "%s: split %g: it must be in [0, 1]", name, o.split);
+	for (int32_t i = 0; i < o.count && o.pendant_start; i++)
+		if (!std::isfinite(o.pendant_start[i]) || !(o.pendant_start[i] > 0.0))
+			return fail(PHYAMD_EINVAL, "%s: pendant_start[%d] = %g: a pendant length is finite and positive", name, i, o.pendant_start[i]);
+	if (!(o.lower >= 0.0 && o.lower < o.upper && std::isfinite(o.upper))) return fail(PHYAMD_EINVAL, "%s: bounds [%g, %g]: they must be 0 <= lower < upper < inf", name, o.lower, o.upper);
+	if (!(o.tolerance > 0.0 && std::isfinite(o.tolerance))) return fail(PHYAMD_EINVAL, "%s: tolerance %g: it must be finite and positive", name, o.tolerance);
+	if (o.max_iterations < 1 || o.max_iterations > 1000) return fail(PHYAMD_EINVAL, "%s: max_iterations %d is outside 1..1000", name, o.max_iterations);
+	if (!(o.lnl_tolerance >= 0.0 && std::isfinite(o.lnl_tolerance))) return fail(PHYAMD_EINVAL, "%s: lnl_tolerance %g: it must be finite and not negative", name, o.lnl_tolerance);
+	if (o.max_passes < 1 || o.max_passes > 1000) return fail(PHYAMD_EINVAL, "%s: max_passes %d is outside 1..1000", name, o.max_passes);
+	return PHYAMD_OK;
+}
+
+// the candidates' nodes, which the engine bounds
+static int check_candidate_nodes(const char *name, const phyamd_engine *g, const PlacementOptimizeArgs &o) {
+	for (int32_t i = 0; i < o.count; i++)
+		if (o.candidates[2 * (size_t)i + 1] < 0 || o.candidates[2 * (size_t)i + 1] >= g->N)
+			return fail(PHYAMD_EINVAL, "%s: candidates[%d] = (%d, %d): the node is outside 0..%d", name, i, o.candidates[2 * (size_t)i], o.candidates[2 * (size_t)i + 1], g->N - 1);
+	return PHYAMD_OK;
+}
+
+// every cell of the queries' rows [queries][P] a state mask (a row is scanned without a branch, and again for the message)
+static int check_mask_rows(const char *name, const phyamd_engine *g, int32_t queries, const uint8_t *masks) {
 	const size_t P = (size_t)g->P;
 	for (int32_t q = 0; q < queries; q++) {
 		const uint8_t *row = masks + (size_t)q * P;
@@ -769,29 +805,21 @@ int phyamd_placement_log_likelihoods(phyamd_engine *g, int flags, int32_t querie
 			if (row[k] < 1 || row[k] > 15)
 				return fail(PHYAMD_EINVAL, "%s: masks[%d][%zu] = %d (query %d, pattern %zu): a state mask is 1..15 (bit s: state s; 15: a gap)", name, q, k, (int)row[k], q, k);
 	}
-	if (group_size(g) > 1)
-		return fail(PHYAMD_EUNSUPPORTED, "%s: a handle sharded over several devices is out of scope: a query's best edge would need its sums across the shards", name);
-	return shard_placement(g->shards[0], flags, PlacementArgs{queries, masks, lengths, pendant, split, lnl, best_node, best_lnl});
+	return PHYAMD_OK;
 }
 
-// the same for 20 states: a query cell is a class code over the call's own sets
-int phyamd_placement_log_likelihoods_general(phyamd_engine *g, int flags, int32_t queries, const uint8_t *codes, int32_t set_count, const uint64_t *sets, int32_t lengths,
-                                             const double *pendant, double split, double *lnl, int32_t *best_node, double *best_lnl) {
-	static const char *const name = "phyamd_placement_log_likelihoods_general";
-	if (!lnl && !best_node) return fail(PHYAMD_EINVAL, "%s: null lnl and null best_node: one of them is the result", name);
-	if (best_lnl && !best_node) return fail(PHYAMD_EINVAL, "%s: best_lnl without best_node", name);
-	if (!codes || !pendant) return fail(PHYAMD_EINVAL, "%s: null %s", name, !codes ? "codes" : "pendant");
-	if (queries < 1) return fail(PHYAMD_EINVAL, "%s: queries must be >= 1 (got %d)", name, queries);
-	if (lengths < 1) return fail(PHYAMD_EINVAL, "%s: lengths must be >= 1 (got %d)", name, lengths);
-	if (!(split >= 0.0 && split <= 1.0)) return fail(PHYAMD_EINVAL, "%s: split %g: it must be in [0, 1]", name, split);
-	for (int32_t l = 0; l < lengths; l++)
-		if (!std::isfinite(pendant[l]) || !(pendant[l] > 0.0)) return fail(PHYAMD_EINVAL, "%s: pendant[%d] = %g: a pendant length is finite and positive", name, l, pendant[l]);
+// the call's sets, which need no engine ...
+static int check_sets(const char *name, int32_t set_count, const uint64_t *sets) {
 	if (set_count < 0 || set_count > PLACE_GEN_MAX_SETS) return fail(PHYAMD_EINVAL, "%s: set_count %d is outside 0..%d (a class code is below %d)", name, set_count, PLACE_GEN_MAX_SETS, PLACE_GEN_CLASSES);
 	if (set_count > 0 && !sets) return fail(PHYAMD_EINVAL, "%s: null sets with set_count %d", name, set_count);
 	for (int32_t q = 0; q < set_count; q++)
 		if (sets[q] == 0 || sets[q] >> PLACE_GEN_STATES)
 			return fail(PHYAMD_EINVAL, "%s: sets[%d] = 0x%llx: a set has a member and no bit at or above 2^%d (bit s: state s)", name, q, (unsigned long long)sets[q], PLACE_GEN_STATES);
-	if (!g || g->shards.empty()) return fail(PHYAMD_EINVAL, "%s: null engine", name);
+	return PHYAMD_OK;
+}
+
+// ... and every cell of the queries' rows [queries][P] a class code over them, which needs its P
+static int check_code_rows(const char *name, const phyamd_engine *g, int32_t set_count, int32_t queries, const uint8_t *codes) {
 	const size_t P = (size_t)g->P;
 	const unsigned top = (unsigned)(PLACE_GEN_STATES + set_count);
 	for (int32_t q = 0; q < queries; q++) {
@@ -804,8 +832,32 @@ int phyamd_placement_log_likelihoods_general(phyamd_engine *g, int flags, int32_
 				return fail(PHYAMD_EINVAL, "%s: codes[%d][%zu] = %d (query %d, pattern %zu): a class code is 0..%u (a state, 20: unknown, 21 + q: sets[q] of the call's %d sets)", name, q, k,
 				            (int)row[k], q, k, top, set_count);
 	}
-	if (group_size(g) > 1)
-		return fail(PHYAMD_EUNSUPPORTED, "%s: a handle sharded over several devices is out of scope: a query's best edge would need its sums across the shards", name);
+	return PHYAMD_OK;
+}
+
+static const char *const PLACE_SCORE_ONE_DEVICE = "%s: a handle sharded over several devices is out of scope: a query's best edge would need its sums across the shards";
+static const char *const PLACE_OPTIMIZE_ONE_DEVICE = "%s: a handle sharded over several devices is out of scope: every iteration of a visit would need a sum across the shards";
+
+// one device only: a query's lnL on an edge would be the sum of the shards', and its best edge follows from the sums
+int phyamd_placement_log_likelihoods(phyamd_engine *g, int flags, int32_t queries, const uint8_t *masks, int32_t lengths, const double *pendant, double split, double *lnl,
+                                     int32_t *best_node, double *best_lnl) {
+	static const char *const name = "phyamd_placement_log_likelihoods";
+	if (int rc = check_placement_score_arguments(name, "masks", masks, queries, lengths, pendant, split, lnl, best_node, best_lnl)) return rc;
+	if (!g || g->shards.empty()) return fail(PHYAMD_EINVAL, "%s: null engine", name);
+	if (int rc = check_mask_rows(name, g, queries, masks)) return rc;
+	if (group_size(g) > 1) return fail(PHYAMD_EUNSUPPORTED, PLACE_SCORE_ONE_DEVICE, name);
+	return shard_placement(g->shards[0], flags, PlacementArgs{queries, masks, lengths, pendant, split, lnl, best_node, best_lnl});
+}
+
+// the same for 20 states: a query cell is a class code over the call's own sets
+int phyamd_placement_log_likelihoods_general(phyamd_engine *g, int flags, int32_t queries, const uint8_t *codes, int32_t set_count, const uint64_t *sets, int32_t lengths,
+                                             const double *pendant, double split, double *lnl, int32_t *best_node, double *best_lnl) {
+	static const char *const name = "phyamd_placement_log_likelihoods_general";
+	if (int rc = check_placement_score_arguments(name, "codes", codes, queries, lengths, pendant, split, lnl, best_node, best_lnl)) return rc;
+	if (int rc = check_sets(name, set_count, sets)) return rc;
+	if (!g || g->shards.empty()) return fail(PHYAMD_EINVAL, "%s: null engine", name);
+	if (int rc = check_code_rows(name, g, set_count, queries, codes)) return rc;
+	if (group_size(g) > 1) return fail(PHYAMD_EUNSUPPORTED, PLACE_SCORE_ONE_DEVICE, name);
 	return shard_placement_general(g->shards[0], flags, PlacementGeneralArgs{PlacementArgs{queries, codes, lengths, pendant, split, lnl, best_node, best_lnl}, set_count, sets});
 }
 
@@ -818,92 +870,30 @@ int phyamd_placement_optimize(phyamd_engine *g, int flags, int32_t queries, cons
                               double split, int32_t branches, double lower, double upper, double tolerance, int32_t max_iterations, double lnl_tolerance, int32_t max_passes,
                               double *lengths, double *lnl, double *initial_lnl, int32_t *passes) {
 	static const char *const name = "phyamd_placement_optimize";
-	if (!masks || !candidates || !lengths || !lnl) return fail(PHYAMD_EINVAL, "%s: null %s", name, !masks ? "masks" : !candidates ? "candidates" : !lengths ? "lengths" : "lnl");
-	if (queries < 1) return fail(PHYAMD_EINVAL, "%s: queries must be >= 1 (got %d)", name, queries);
-	if (count < 1) return fail(PHYAMD_EINVAL, "%s: count must be >= 1 (got %d)", name, count);
-	for (int32_t i = 0; i < count; i++)
-		if (candidates[2 * (size_t)i] < 0 || candidates[2 * (size_t)i] >= queries)
-			return fail(PHYAMD_EINVAL, "%s: candidates[%d] = (%d, %d): the query is outside 0..%d", name, i, candidates[2 * (size_t)i], candidates[2 * (size_t)i + 1], queries - 1);
-	if (branches < 1 || branches > 7) return fail(PHYAMD_EINVAL, "%s: branches %d is outside 1..7 (bit 0: distal, bit 1: pendant, bit 2: proximal)", name, branches);
-	if (!(split >= 0.0 && split <= 1.0)) return fail(PHYAMD_EINVAL, "%s: split %g: it must be in [0, 1]", name, split);
-	for (int32_t i = 0; i < count && pendant_start; i++)
-		if (!std::isfinite(pendant_start[i]) || !(pendant_start[i] > 0.0))
-			return fail(PHYAMD_EINVAL, "%s: pendant_start[%d] = %g: a pendant length is finite and positive", name, i, pendant_start[i]);
-	if (!(lower >= 0.0 && lower < upper && std::isfinite(upper))) return fail(PHYAMD_EINVAL, "%s: bounds [%g, %g]: they must be 0 <= lower < upper < inf", name, lower, upper);
-	if (!(tolerance > 0.0 && std::isfinite(tolerance))) return fail(PHYAMD_EINVAL, "%s: tolerance %g: it must be finite and positive", name, tolerance);
-	if (max_iterations < 1 || max_iterations > 1000) return fail(PHYAMD_EINVAL, "%s: max_iterations %d is outside 1..1000", name, max_iterations);
-	if (!(lnl_tolerance >= 0.0 && std::isfinite(lnl_tolerance))) return fail(PHYAMD_EINVAL, "%s: lnl_tolerance %g: it must be finite and not negative", name, lnl_tolerance);
-	if (max_passes < 1 || max_passes > 1000) return fail(PHYAMD_EINVAL, "%s: max_passes %d is outside 1..1000", name, max_passes);
+	const PlacementOptimizeArgs o{queries, masks, count, candidates, pendant_start, split, branches, lower, upper, tolerance, max_iterations, lnl_tolerance, max_passes, lengths, lnl,
+	                              initial_lnl, passes};
+	if (int rc = check_placement_optimize_arguments(name, "masks", o)) return rc;
 	if (!g || g->shards.empty()) return fail(PHYAMD_EINVAL, "%s: null engine", name);
-	for (int32_t i = 0; i < count; i++)
-		if (candidates[2 * (size_t)i + 1] < 0 || candidates[2 * (size_t)i + 1] >= g->N)
-			return fail(PHYAMD_EINVAL, "%s: candidates[%d] = (%d, %d): the node is outside 0..%d", name, i, candidates[2 * (size_t)i], candidates[2 * (size_t)i + 1], g->N - 1);
-	const size_t P = (size_t)g->P;
-	for (int32_t q = 0; q < queries; q++) {
-		const uint8_t *row = masks + (size_t)q * P;
-		unsigned bad = 0;
-		for (size_t k = 0; k < P; k++) bad |= (unsigned)(uint8_t)(row[k] - 1) > 14u;
-		if (!bad) continue;
-		for (size_t k = 0; k < P; k++)
-			if (row[k] < 1 || row[k] > 15)
-				return fail(PHYAMD_EINVAL, "%s: masks[%d][%zu] = %d (query %d, pattern %zu): a state mask is 1..15 (bit s: state s; 15: a gap)", name, q, k, (int)row[k], q, k);
-	}
-	if (group_size(g) > 1)
-		return fail(PHYAMD_EUNSUPPORTED, "%s: a handle sharded over several devices is out of scope: every iteration of a visit would need a sum across the shards", name);
-	return shard_placement_optimize(g->shards[0], flags,
-	                                PlacementOptimizeArgs{queries, masks, count, candidates, pendant_start, split, branches, lower, upper, tolerance, max_iterations, lnl_tolerance,
-	                                                      max_passes, lengths, lnl, initial_lnl, passes});
+	if (int rc = check_candidate_nodes(name, g, o)) return rc;
+	if (int rc = check_mask_rows(name, g, queries, masks)) return rc;
+	if (group_size(g) > 1) return fail(PHYAMD_EUNSUPPORTED, PLACE_OPTIMIZE_ONE_DEVICE, name);
+	return shard_placement_optimize(g->shards[0], flags, o);
 }
 
-// the same for 20 states: phyamd_placement_optimize's argument checks, then the codes and sets checks of
-// phyamd_placement_log_likelihoods_general
+// the same for 20 states
 int phyamd_placement_optimize_general(phyamd_engine *g, int flags, int32_t queries, const uint8_t *codes, int32_t set_count, const uint64_t *sets, int32_t count,
                                       const int32_t *candidates, const double *pendant_start, double split, int32_t branches, double lower, double upper, double tolerance,
                                       int32_t max_iterations, double lnl_tolerance, int32_t max_passes, double *lengths, double *lnl, double *initial_lnl, int32_t *passes) {
 	static const char *const name = "phyamd_placement_optimize_general";
-	if (!codes || !candidates || !lengths || !lnl) return fail(PHYAMD_EINVAL, "%s: null %s", name, !codes ? "codes" : !candidates ? "candidates" : !lengths ? "lengths" : "lnl");
-	if (queries < 1) return fail(PHYAMD_EINVAL, "%s: queries must be >= 1 (got %d)", name, queries);
-	if (count < 1) return fail(PHYAMD_EINVAL, "%s: count must be >= 1 (got %d)", name, count);
-	for (int32_t i = 0; i < count; i++)
-		if (candidates[2 * (size_t)i] < 0 || candidates[2 * (size_t)i] >= queries)
-			return fail(PHYAMD_EINVAL, "%s: candidates[%d] = (%d, %d): the query is outside 0..%d", name, i, candidates[2 * (size_t)i], candidates[2 * (size_t)i + 1], queries - 1);
-	if (branches < 1 || branches > 7) return fail(PHYAMD_EINVAL, "%s: branches %d is outside 1..7 (bit 0: distal, bit 1: pendant, bit 2: proximal)", name, branches);
-	if (!(split >= 0.0 && split <= 1.0)) return fail(PHYAMD_EINVAL, "%s: split %g: it must be in [0, 1]", name, split);
-	for (int32_t i = 0; i < count && pendant_start; i++)
-		if (!std::isfinite(pendant_start[i]) || !(pendant_start[i] > 0.0))
-			return fail(PHYAMD_EINVAL, "%s: pendant_start[%d] = %g: a pendant length is finite and positive", name, i, pendant_start[i]);
-	if (!(lower >= 0.0 && lower < upper && std::isfinite(upper))) return fail(PHYAMD_EINVAL, "%s: bounds [%g, %g]: they must be 0 <= lower < upper < inf", name, lower, upper);
-	if (!(tolerance > 0.0 && std::isfinite(tolerance))) return fail(PHYAMD_EINVAL, "%s: tolerance %g: it must be finite and positive", name, tolerance);
-	if (max_iterations < 1 || max_iterations > 1000) return fail(PHYAMD_EINVAL, "%s: max_iterations %d is outside 1..1000", name, max_iterations);
-	if (!(lnl_tolerance >= 0.0 && std::isfinite(lnl_tolerance))) return fail(PHYAMD_EINVAL, "%s: lnl_tolerance %g: it must be finite and not negative", name, lnl_tolerance);
-	if (max_passes < 1 || max_passes > 1000) return fail(PHYAMD_EINVAL, "%s: max_passes %d is outside 1..1000", name, max_passes);
-	if (set_count < 0 || set_count > PLACE_GEN_MAX_SETS) return fail(PHYAMD_EINVAL, "%s: set_count %d is outside 0..%d (a class code is below %d)", name, set_count, PLACE_GEN_MAX_SETS, PLACE_GEN_CLASSES);
-	if (set_count > 0 && !sets) return fail(PHYAMD_EINVAL, "%s: null sets with set_count %d", name, set_count);
-	for (int32_t q = 0; q < set_count; q++)
-		if (sets[q] == 0 || sets[q] >> PLACE_GEN_STATES)
-			return fail(PHYAMD_EINVAL, "%s: sets[%d] = 0x%llx: a set has a member and no bit at or above 2^%d (bit s: state s)", name, q, (unsigned long long)sets[q], PLACE_GEN_STATES);
+	const PlacementOptimizeArgs o{queries, codes, count, candidates, pendant_start, split, branches, lower, upper, tolerance, max_iterations, lnl_tolerance, max_passes, lengths, lnl,
+	                              initial_lnl, passes};
+	if (int rc = check_placement_optimize_arguments(name, "codes", o)) return rc;
+	if (int rc = check_sets(name, set_count, sets)) return rc;
 	if (!g || g->shards.empty()) return fail(PHYAMD_EINVAL, "%s: null engine", name);
-	for (int32_t i = 0; i < count; i++)
-		if (candidates[2 * (size_t)i + 1] < 0 || candidates[2 * (size_t)i + 1] >= g->N)
-			return fail(PHYAMD_EINVAL, "%s: candidates[%d] = (%d, %d): the node is outside 0..%d", name, i, candidates[2 * (size_t)i], candidates[2 * (size_t)i + 1], g->N - 1);
-	const size_t P = (size_t)g->P;
-	const unsigned top = (unsigned)(PLACE_GEN_STATES + set_count);
-	for (int32_t q = 0; q < queries; q++) {
-		const uint8_t *row = codes + (size_t)q * P;
-		unsigned bad = 0;
-		for (size_t k = 0; k < P; k++) bad |= row[k] > top;
-		if (!bad) continue;
-		for (size_t k = 0; k < P; k++)
-			if (row[k] > top)
-				return fail(PHYAMD_EINVAL, "%s: codes[%d][%zu] = %d (query %d, pattern %zu): a class code is 0..%u (a state, 20: unknown, 21 + q: sets[q] of the call's %d sets)", name, q, k,
-				            (int)row[k], q, k, top, set_count);
-	}
-	if (group_size(g) > 1)
-		return fail(PHYAMD_EUNSUPPORTED, "%s: a handle sharded over several devices is out of scope: every iteration of a visit would need a sum across the shards", name);
-	return shard_placement_optimize_general(g->shards[0], flags,
-	                                        PlacementOptimizeGeneralArgs{PlacementOptimizeArgs{queries, codes, count, candidates, pendant_start, split, branches, lower, upper, tolerance,
-	                                                                                           max_iterations, lnl_tolerance, max_passes, lengths, lnl, initial_lnl, passes},
-	                                                                     set_count, sets});
+	if (int rc = check_candidate_nodes(name, g, o)) return rc;
+	if (int rc = check_code_rows(name, g, set_count, queries, codes)) return rc;
+	if (group_size(g) > 1) return fail(PHYAMD_EUNSUPPORTED, PLACE_OPTIMIZE_ONE_DEVICE, name);
+	return shard_placement_optimize_general(g->shards[0], flags, PlacementOptimizeGeneralArgs{o, set_count, sets});
 }
 
 int phyamd_get_placement_optimize_profile(phyamd_engine *g, phyamd_placement_optimize_profile *out) {

@@ -129,10 +129,7 @@ __global__ __launch_bounds__(CBOPT_THREADS) void k_blopt_solve4(const BloptSolve
 		if (n == 0) lnl0 = lnl;
 		n++;
 		if (bad || !visited) break;  // lnL is not finite at this iterate: it ends the item
-		if (d1 > 0.0) lo = t;
-		else hi = t;
-		double next = t - d1 / d2;
-		if (!(d2 < 0.0 && lo < next && next < hi)) next = 0.5 * (lo + hi);
+		const double next = newton_propose(t, d1, d2, lo, hi);
 		const bool converged = fabs(next - t) <= a.tolerance;
 		t = next;
 		if (converged) break;

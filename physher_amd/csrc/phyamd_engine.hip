@@ -4,13 +4,14 @@
 //   phyamd_types.h          plain data the host builds and the kernels read: op lists, descriptors, their enums and constants
 //   phyamd_tree_schedule.h  the tree check and every host-built list as a value built by a pure function (standard C++, no engine)
 //   phyamd_memory.inc       owning device arrays and the memory budget they are allocated through
-//   phyamd_device.inc / _level4 / _walk4 / _walk4s / _general / _genwalk / _patterns / _batch4 / _nni4 / _nniopt4 / _blopt4 / _spr4 / _tripod4 / _post / _bhess / _reweight / _pairdist4 / _pairdist_gen / _place4 / _place_gen / _qopt4  device code (kernels)
+//   phyamd_device.inc / _level4 / _walk4 / _walk4s / _general / _genwalk / _patterns / _batch4 / _nni4 / _nniopt4 / _blopt4 / _spr4 / _tripod4 / _post / _bhess / _reweight / _pairdist4 / _pairdist_gen / _place4 / _place_gen / _qopt4 / _qopt_gen  device code (kernels; _rule: the branch-length rule they share)
 //   phyamd_shard.inc        state of one engine on one GPU (= one shard of the site patterns), the form of its stored lowers
 //   phyamd_schedule.inc     the engine's schedule on the device: storage, upload, readiness
 //   phyamd_launch.inc       kernel launches per pass
 //   phyamd_eval.inc         one evaluation (incremental updates, lazy rescaling, gradients, pattern tiling)
 //   phyamd_shard_api.inc    per-device half of the C ABI: creation, setters, evaluations, single-branch calls, inspection
 //   phyamd_queries.inc      ... and its whole-tree query calls: batches, NNI and SPR scores, posteriors, the full branch Hessian
+//   phyamd_place_calls.inc  ... and the placement calls, 4 and 20 states over one frame
 //   phyamd_abi.inc          extern "C" entry points: a handle is a group of 1..n shards on 1..n GPUs
 //   phyamd_schedule_export.inc  ... and the host-only ones that export a tree's schedules (included by phyamd_abi.inc)
 //
@@ -105,6 +106,7 @@ constexpr double SCALING_THRESHOLD = 1.0e-40;  // treelikelihood.c:1121
 #include "phyamd_patterns.inc"
 #include "phyamd_batch4.inc"
 #include "phyamd_nni4.inc"
+#include "phyamd_rule.inc"
 #include "phyamd_nniopt4.inc"
 #include "phyamd_blopt4.inc"
 #include "phyamd_spr4.inc"
@@ -127,6 +129,7 @@ constexpr double SCALING_THRESHOLD = 1.0e-40;  // treelikelihood.c:1121
 #include "phyamd_eval.inc"
 #include "phyamd_shard_api.inc"
 #include "phyamd_queries.inc"
+#include "phyamd_place_calls.inc"
 
 }  // namespace
 

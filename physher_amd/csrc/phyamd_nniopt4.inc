@@ -125,30 +125,6 @@ __global__ __launch_bounds__(CBOPT_THREADS) void k_cbopt_solve4(const CboptSolve
 	const int entry = blockIdx.x, arr = entry % 3;
 	const NniCand cd = load_nni_cand(a.cands, entry / 3);
 	const double *K = a.K + (size_t)entry * a.C * 4 * a.Pp;
-	double t = fmin(fmax(a.start[(size_t)arr * a.N + cd.v], a.lower), a.upper), lo = a.lower, hi = a.upper;
-	double lnl, d1, d2;
-	bool bad;
-	int n = 0, converged = 0;
-	while (n < a.max_iterations) {
-		cbopt_evaluate(a, K, t, false, sh_e, sh_w, &lnl, &d1, &d2, &bad);
-		n++;
-		if (bad) break;  // lnL is not finite at this iterate: it is the entry's report
-		if (d1 > 0.0) lo = t;
-		else hi = t;
-		double next = t - d1 / d2;
-		if (!(d2 < 0.0 && lo < next && next < hi)) next = 0.5 * (lo + hi);
-		converged = fabs(next - t) <= a.tolerance;
-		t = next;
-		if (converged) break;
-	}
-	cbopt_evaluate(a, K, t, true, sh_e, sh_w, &lnl, &d1, &d2, &bad);
-	if (threadIdx.x == 0) {
-		const bool finite = !(isnan(lnl) || isinf(lnl));
-		double *out = a.out + (size_t)entry * 4;
-		out[0] = t;
-		out[1] = lnl;
-		out[2] = finite ? d1 : NAN;
-		out[3] = finite ? d2 : NAN;
-		a.iterations[entry] = converged && finite ? n : -n;
-	}
+	solve_one_length([&](double t, bool final, double *lnl, double *d1, double *d2, bool *bad) { cbopt_evaluate(a, K, t, final, sh_e, sh_w, lnl, d1, d2, bad); },
+	                 a.start[(size_t)arr * a.N + cd.v], a.lower, a.upper, a.tolerance, a.max_iterations, a.out + (size_t)entry * 4, a.iterations + entry);
 }

@@ -164,30 +164,7 @@ __global__ __launch_bounds__(PAIRDIST_THREADS) void k_classpair_solve(const Pair
 #pragma unroll
 	for (int r = 0; r < PAIRDIST_GEN_OWN; r++) N[r] = a.counts[(size_t)pair * PAIRDIST_GEN_BINS + threadIdx.x + PAIRDIST_THREADS * r];
 	__syncthreads();
-	double t = fmin(fmax(a.start[pair], a.lower), a.upper), lo = a.lower, hi = a.upper;
-	double lnl, d1, d2;
-	bool bad;
-	int n = 0, converged = 0;
-	while (n < a.max_iterations) {
-		pairdist_evaluate_gen(a, N, sh_g, sh_q, t, false, sh_S, sh_w, &lnl, &d1, &d2, &bad);
-		n++;
-		if (bad) break;  // lnL is not finite at this iterate: it is the pair's report
-		if (d1 > 0.0) lo = t;
-		else hi = t;
-		double next = t - d1 / d2;
-		if (!(d2 < 0.0 && lo < next && next < hi)) next = 0.5 * (lo + hi);
-		converged = fabs(next - t) <= a.tolerance;
-		t = next;
-		if (converged) break;
-	}
-	pairdist_evaluate_gen(a, N, sh_g, sh_q, t, true, sh_S, sh_w, &lnl, &d1, &d2, &bad);
-	if (threadIdx.x == 0) {
-		const bool finite = !(isnan(lnl) || isinf(lnl));
-		double *out = a.out + (size_t)pair * 4;
-		out[0] = t;
-		out[1] = lnl;
-		out[2] = finite ? d1 : NAN;
-		out[3] = finite ? d2 : NAN;
-		a.iterations[pair] = converged && finite ? n : -n;
-	}
+	solve_one_length(
+	    [&](double t, bool final, double *lnl, double *d1, double *d2, bool *bad) { pairdist_evaluate_gen(a, N, sh_g, sh_q, t, final, sh_S, sh_w, lnl, d1, d2, bad); },
+	    a.start[pair], a.lower, a.upper, a.tolerance, a.max_iterations, a.out + (size_t)pair * 4, a.iterations + pair);
 }

@@ -16,8 +16,8 @@
 // not multiplied out per pattern: a visit of z or n tabulates P(b r_c) A for the 16 masks in LDS ([C][16] 4-vectors, summed in
 // state order like the mat-vec they replace), V^-1 A is tabulated once per candidate, and a pattern looks its vector up.
 // k_qopt_upper4 writes pi o U once per distinct EDGE of a chunk -- every candidate of the edge reads the same plane -- and
-// k_qopt_solve4 runs a candidate's whole rule (include/physher_amd.h) in one workgroup: per visit two 4x4 matrices per category in
-// LDS, K formed per pattern by the thread that reads it back, then the safeguarded Newton iteration on cbopt_evaluate's
+// k_qopt_solve4 runs a candidate's whole rule (include/physher_amd.h; its one body: three_branch_rule, phyamd_rule.inc) in one
+// workgroup: per visit two 4x4 matrices per category in LDS, K formed per pattern by the thread that reads it back, then the safeguarded Newton iteration on cbopt_evaluate's
 // fixed-order sums, so every thread holds the same bits and takes the same accept, bisect and stop decisions.  No walk, no matrix
 // launch and no host round trip per visit; no floating-point atomics.  A candidate's arithmetic depends on the engine's inputs,
 // its query's masks, its edge and its start alone: not on the chunk, the order of the candidates or what else the chunk holds.
@@ -55,7 +55,7 @@ struct QoptCand {
 };
 
 enum { QOPT_N = 0, QOPT_X = 1, QOPT_Z = 2 };  // the three branches, in `lengths`' order, the visit order and `branches`' bits
-enum { QOPT_PASSES = 0, QOPT_VISITS = 1, QOPT_ITERATIONS = 2, QOPT_STATUS = 4 };  // a candidate's status words
+enum { QOPT_PASSES = RULE_PASSES, QOPT_VISITS = RULE_VISITS, QOPT_ITERATIONS = RULE_ITERATIONS, QOPT_STATUS = RULE_STATUS };  // a candidate's status words
 
 struct QoptSolveArgs {
 	const QoptCand *cands;   // [gridDim.x]
@@ -144,8 +144,8 @@ __device__ __forceinline__ void qopt_coefficients(const QoptSolveArgs &a, const 
 	// again only after the barriers of the evaluations in between)
 }
 
-// grid (candidates of the chunk), block 256: one candidate's whole rule, every thread with the same bits.  One loop over the start
-// (slot -1: lnl_0 in the length of z, as it is given) and the visits of the marked branches, one over a visit's evaluations
+// grid (candidates of the chunk), block 256: one candidate's whole rule (three_branch_rule, phyamd_rule.inc: a slot is its branch,
+// the start is lnl_0 in the length of z as it is given), every thread with the same bits
 __global__ __launch_bounds__(CBOPT_THREADS) void k_qopt_solve4(const QoptSolveArgs a) {
 	__shared__ double sh_e[3 * 4 * BATCH_MAX_CATEGORIES], sh_w[3 * CBOPT_WAVES], sh_m[2 * 16 * BATCH_MAX_CATEGORIES], sh_x[2 * 4 * BATCH_MAX_CATEGORIES], sh_v[32];
 	__shared__ double sh_t[16 * 4 * BATCH_MAX_CATEGORIES], sh_q[16 * 4];
@@ -171,67 +171,9 @@ __global__ __launch_bounds__(CBOPT_THREADS) void k_qopt_solve4(const QoptSolveAr
 	cells.K = tripod_in_vgprs(a.K + cand * node_stride + tid);
 	double *const out = tripod_in_vgprs(a.out + cand * 5);
 	int32_t *const status = tripod_in_vgprs(a.status + cand * QOPT_STATUS);
-	double tn = a.start[cand * 3], tx = a.start[cand * 3 + 1], tz = a.start[cand * 3 + 2];
-	const int first = a.branches & 1 ? QOPT_N : a.branches & 2 ? QOPT_X : QOPT_Z;
-	double initial = 0.0, previous = 0.0, result = 0.0;
-	int passes = 0, visits = 0, iterations = 0;
-	int pass = 1, slot = -1;
-#pragma unroll 1
-	while (passes == 0) {
-		const int z = slot < 0 ? QOPT_Z : slot;  // z's left child n, its right child x, z
-		qopt_coefficients(a, cells, z, tn, tx, tz, sh_m, sh_x, sh_t, sh_q, sh_v);
-		const double tv = z == QOPT_N ? tn : z == QOPT_X ? tx : tz;
-		const double t0 = slot < 0 ? tv : fmin(fmax(tv, a.lower), a.upper);
-		double t = t0, lo = a.lower, hi = a.upper, lnl = 0.0, lnl0 = 0.0, d1, d2;
-		int n = 0;
-		bool last = slot < 0, bad = false, wrong;  // last: the evaluation that ends the visit (the start has no other)
-#pragma unroll 1
-		for (;;) {
-			cbopt_evaluate(ev, K, t, n == 0 || last, sh_e, sh_w, &lnl, &d1, &d2, &wrong);
-			if (last) break;
-			if (n == 0) lnl0 = lnl;
-			n++;
-			if (wrong) {  // lnL is not finite at this iterate: it ends the candidate, with the value there
-				bad = true;
-				if (n == 1) break;
-				last = true;
-				continue;
-			}
-			if (d1 > 0.0) lo = t;
-			else hi = t;
-			double next = t - d1 / d2;
-			if (!(d2 < 0.0 && lo < next && next < hi)) next = 0.5 * (lo + hi);
-			last = fabs(next - t) <= a.tolerance || n == a.max_iterations;
-			t = next;
-		}
-		if (slot < 0) {
-			initial = previous = result = lnl;
-			slot = first;
-			continue;
-		}
-		iterations += n;
-		if (bad) {
-			result = isnan(lnl) || isinf(lnl) ? lnl : NAN;
-			passes = -pass;
-			break;
-		}
-		const bool accept = !wrong && !(isnan(lnl) || isinf(lnl)) && lnl >= lnl0;
-		const double tnew = accept ? t : t0;
-		result = accept ? lnl : lnl0;  // lnL at the length the visit leaves
-		if (z == QOPT_N) tn = tnew;
-		else if (z == QOPT_X) tx = tnew;
-		else tz = tnew;
-		visits++;
-		do slot++;
-		while (slot < 3 && !(a.branches >> slot & 1));
-		if (slot < 3) continue;
-		if (result - previous <= a.lnl_tolerance) passes = pass;  // the stop test
-		else if (pass == a.max_passes) passes = -a.max_passes;
-		previous = result;
-		slot = first, pass++;
-	}
-	if (threadIdx.x == 0) {
-		out[0] = tn, out[1] = tx, out[2] = tz, out[3] = result, out[4] = initial;
-		status[QOPT_PASSES] = passes, status[QOPT_VISITS] = visits, status[QOPT_ITERATIONS] = iterations;
-	}
+	three_branch_rule<false>(
+	    [&](int z, double tn, double tx, double tz) { qopt_coefficients(a, cells, z, tn, tx, tz, sh_m, sh_x, sh_t, sh_q, sh_v); },
+	    [&](double t, bool final, double *lnl, double *d1, double *d2, bool *bad) { cbopt_evaluate(ev, K, t, final, sh_e, sh_w, lnl, d1, d2, bad); },
+	    [](int slot) { return slot; },  // z's left child n, its right child x, z
+	    a.branches, a.start[cand * 3], a.start[cand * 3 + 1], a.start[cand * 3 + 2], a.lower, a.upper, a.tolerance, a.max_iterations, a.lnl_tolerance, a.max_passes, out, status);
 }

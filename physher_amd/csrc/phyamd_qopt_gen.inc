@@ -1,7 +1,8 @@
 // phyamd_qopt_gen.inc: 20-state kernel of phyamd_placement_optimize_general -- for chosen (query, edge) placements the three branch
 // lengths that meet at the insertion point, optimised one at a time, pass after pass -- included by phyamd_engine.hip inside its
 // anonymous namespace, behind phyamd_place_gen.inc (whose resident partials, own-partial kernel and class codes it shares) and
-// phyamd_qopt4.inc (whose rule, visit loop and K formulas these are, with 20-vectors in place of 4-vectors).
+// phyamd_qopt4.inc (whose K formulas these are, with 20-vectors in place of 4-vectors).  The rule and its visit loop are
+// phyamd_rule.inc's three_branch_rule.
 //
 // Three messages meet at the new node z and none depends on the three lengths a = t_n (distal), b = t_x (pendant), cz = t_z
 // (proximal): A, the 0/1 member vector of the query's class code; B = p_n, the node's own partial (a tip: its code over the ENGINE's
@@ -240,9 +241,8 @@ __device__ __forceinline__ void classopt_evaluate(const ClassOptArgs &a, const d
 	__syncthreads();  // sh.e and sh.w are free for the next evaluation
 }
 
-// grid (candidates of the chunk), block 256: one candidate's whole rule, every thread with the same bits.  k_qopt_solve4's loops:
-// one over the start (slot -1: lnl_0 in the length of z, as it is given) and the visits of the marked branches, one over a visit's
-// evaluations.  Compiled for two waves per SIMD: left alone the compiler takes 277 registers (255 + 22 accumulation), one workgroup per
+// grid (candidates of the chunk), block 256: one candidate's whole rule (three_branch_rule, phyamd_rule.inc: a slot is its branch),
+// every thread with the same bits.  Compiled for two waves per SIMD: left alone the compiler takes 277 registers (255 + 22 accumulation), one workgroup per
 // CU; bounded it takes 165, nothing spills, and three workgroups share a CU and its 160 KB of LDS
 __global__ __launch_bounds__(CLASSOPT_THREADS, 2) void k_classopt_solve(const ClassOptArgs a) {
 	constexpr int S = PLACE_GEN_STATES;
@@ -258,69 +258,10 @@ __global__ __launch_bounds__(CLASSOPT_THREADS, 2) void k_classopt_solve(const Cl
 	const size_t cand = blockIdx.x;
 	const ClassOptCand cd = a.cands[cand];
 	double *const Kcand = a.K + cand * (size_t)a.C * S * a.Pp;
-	double tn = a.start[cand * 3], tx = a.start[cand * 3 + 1], tz = a.start[cand * 3 + 2];
-	const int first = a.branches & 1 ? QOPT_N : a.branches & 2 ? QOPT_X : QOPT_Z;
-	double initial = 0.0, previous = 0.0, result = 0.0;
-	int passes = 0, visits = 0, iterations = 0;
-	int pass = 1, slot = -1;
-#pragma unroll 1
-	while (passes == 0) {
-		const int z = slot < 0 ? QOPT_Z : slot;  // z's left child n, its right child x, z
-		classopt_coefficients(a, cd, Kcand, z, tn, tx, tz, sh);
-		const double tv = z == QOPT_N ? tn : z == QOPT_X ? tx : tz;
-		const double t0 = slot < 0 ? tv : fmin(fmax(tv, a.lower), a.upper);
-		double t = t0, lo = a.lower, hi = a.upper, lnl = 0.0, lnl0 = 0.0, d1, d2;
-		int n = 0;
-		bool last = slot < 0, bad = false, wrong;  // last: the evaluation that ends the visit (the start has no other)
-#pragma unroll 1
-		for (;;) {
-			classopt_evaluate(a, Kcand, t, n == 0 || last, sh, &lnl, &d1, &d2, &wrong);
-			if (last) break;
-			if (n == 0) lnl0 = lnl;
-			n++;
-			if (wrong) {  // lnL is not finite at this iterate: it ends the candidate, with the value there
-				bad = true;
-				if (n == 1) break;
-				last = true;
-				continue;
-			}
-			if (d1 > 0.0) lo = t;
-			else hi = t;
-			double next = t - d1 / d2;
-			if (!(d2 < 0.0 && lo < next && next < hi)) next = 0.5 * (lo + hi);
-			last = fabs(next - t) <= a.tolerance || n == a.max_iterations;
-			t = next;
-		}
-		if (slot < 0) {
-			initial = previous = result = lnl;
-			slot = first;
-			continue;
-		}
-		iterations += n;
-		if (bad) {
-			result = isnan(lnl) || isinf(lnl) ? lnl : NAN;
-			passes = -pass;
-			break;
-		}
-		const bool accept = !wrong && !(isnan(lnl) || isinf(lnl)) && lnl >= lnl0;
-		const double tnew = accept ? t : t0;
-		result = accept ? lnl : lnl0;  // lnL at the length the visit leaves
-		if (z == QOPT_N) tn = tnew;
-		else if (z == QOPT_X) tx = tnew;
-		else tz = tnew;
-		visits++;
-		do slot++;
-		while (slot < 3 && !(a.branches >> slot & 1));
-		if (slot < 3) continue;
-		if (result - previous <= a.lnl_tolerance) passes = pass;  // the stop test
-		else if (pass == a.max_passes) passes = -a.max_passes;
-		previous = result;
-		slot = first, pass++;
-	}
-	if (tid == 0) {
-		double *out = a.out + cand * 5;
-		int32_t *status = a.status + cand * QOPT_STATUS;
-		out[0] = tn, out[1] = tx, out[2] = tz, out[3] = result, out[4] = initial;
-		status[QOPT_PASSES] = passes, status[QOPT_VISITS] = visits, status[QOPT_ITERATIONS] = iterations;
-	}
+	three_branch_rule<false>(
+	    [&](int z, double tn, double tx, double tz) { classopt_coefficients(a, cd, Kcand, z, tn, tx, tz, sh); },
+	    [&](double t, bool final, double *lnl, double *d1, double *d2, bool *bad) { classopt_evaluate(a, Kcand, t, final, sh, lnl, d1, d2, bad); },
+	    [](int slot) { return slot; },  // z's left child n, its right child x, z
+	    a.branches, a.start[cand * 3], a.start[cand * 3 + 1], a.start[cand * 3 + 2], a.lower, a.upper, a.tolerance, a.max_iterations, a.lnl_tolerance, a.max_passes,
+	    a.out + cand * 5, a.status + cand * QOPT_STATUS);
 }

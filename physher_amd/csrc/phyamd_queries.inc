@@ -1,4 +1,4 @@
-// phyamd_queries.inc -- the whole-tree query calls on one shard: batches of branch-length vectors, of pattern weights and of trees, NNI and SPR scores, pairwise distances, query placements,
+// phyamd_queries.inc -- the whole-tree query calls on one shard: batches of branch-length vectors, of pattern weights and of trees, NNI and SPR scores, pairwise distances,
 // per-pattern posteriors, the full branch Hessian, and the per-pattern lnL of a batch of trees with its RELL replicates.  They read what the engine holds and write only their own scratch
 // (part of phyamd_engine.hip: one translation unit, internal linkage)
 
@@ -1368,688 +1368,6 @@ int shard_pairwise_distances(Shard *e, int flags, const PairDistanceArgs &o) {
 int shard_pairwise_distances_general(Shard *e, int flags, const PairDistanceArgs &o) {
 	CHECK_ENGINE(e);
 	return profiled_call(e, &Shard::dist_prof, phyamd_distance_profile{}, [&](phyamd_distance_profile &prof) { return run_pairwise_distances_general(e, flags, o, prof); });
-}
-
-// ---- query sequences on every edge of the engine's tree (phyamd_placement_log_likelihoods) --------------------------------------
-
-struct PlacementArgs {
-	int32_t queries;
-	const uint8_t *masks;  // [queries][P], validated (phyamd_placement_log_likelihoods)
-	int32_t lengths;
-	const double *pendant;
-	double split;
-	double *lnl;
-	int32_t *best_node;
-	double *best_lnl;
-};
-
-// the NNI walk's (nni_base_plan, with d_nni_mats for the split matrices), and whatever the item count: the pendant lengths and
-// their matrices, the edges, every query's best edge so far, and for a chunk of `cols` node columns and `queries` queries the
-// table, the caller's mask rows and their packed form, the slab and the result
-ScratchPlan place_plan(Shard *e, size_t L, size_t all_queries, size_t cols, size_t queries, size_t segments, bool want_lnl) {
-	const size_t D = sizeof(double), N = (size_t)e->N, C = (size_t)e->C, Ppad = ((size_t)e->P + WAVE - 1) / WAVE * WAVE;
-	ScratchPlan p = nni_base_plan(e);
-	p.add(e->d_nni_mats, 0, D * 3 * N * C * 16);
-	p.add(e->d_place_pend_len, 0, D * L);
-	p.add(e->d_place_pend, 0, D * L * C * 16);
-	p.add(e->d_place_edges, 0, sizeof(PlaceEdge) * N);
-	p.add(e->d_place_best_lnl, 0, D * L * all_queries);
-	p.add(e->d_place_best_node, 0, sizeof(int32_t) * L * all_queries);
-	p.add(e->d_place_table, 0, D * L * cols * Ppad * 16);
-	p.add(e->d_place_raw, 0, queries * (size_t)e->P);
-	p.add(e->d_place_packed, 0, queries * Ppad);
-	p.add(e->d_place_slab, 0, D * segments * L * cols * queries);
-	p.add(e->d_place_out, 0, want_lnl ? D * L * cols * queries : 0);
-	return p;
-}
-
-constexpr size_t PLACE_MAX_CHUNK_QUERIES = (size_t)1 << 20;
-constexpr size_t PLACE_MIN_CHUNK_QUERIES = WAVE;  // queries are cut no further than a wave of lanes while edges can still be cut
-// the largest x in lo..hi with ok(x), ok being true up to some x and false beyond; lo - 1: none
-template <typename Ok>
-size_t largest_that(size_t lo, size_t hi, Ok ok) {
-	if (!ok(lo)) return lo - 1;
-	while (lo < hi) {
-		const size_t mid = lo + (hi - lo + 1) / 2;
-		if (ok(mid)) lo = mid;
-		else hi = mid - 1;
-	}
-	return lo;
-}
-
-// the chunks of the two placement calls, fits(cols, queries) saying whether such a chunk's scratch fits: all N node columns and all Q
-// queries if they fit; else fewer queries, down to a wave of them; else fewer columns; else, with one column, fewer queries still.
-// false: not even one query on one column
-template <typename Fits>
-bool place_chunks(size_t N, size_t Q, Fits fits, size_t *cols_out, size_t *chunk_out) {
-	const size_t max_cols = std::min<size_t>(N, BATCH_MAX_CHUNK), max_queries = std::min(Q, PLACE_MAX_CHUNK_QUERIES);
-	const size_t min_queries = std::min(max_queries, PLACE_MIN_CHUNK_QUERIES);
-	size_t cols = max_cols, chunk = max_queries;
-	if (!fits(cols, chunk)) {
-		chunk = largest_that(min_queries, max_queries, [&](size_t x) { return fits(max_cols, x); });
-		if (chunk >= min_queries) chunk = chunk / min_queries * min_queries;
-		else {
-			chunk = min_queries;
-			cols = largest_that(1, max_cols, [&](size_t x) { return fits(x, min_queries); });
-			if (cols < 1) {
-				cols = 1;
-				chunk = largest_that(1, min_queries, [&](size_t x) { return fits(1, x); });
-				if (chunk < 1) return false;
-			}
-		}
-	}
-	*cols_out = cols, *chunk_out = chunk;
-	return true;
-}
-
-// one walk of the engine's tree with every upper parked, then chunk by chunk of node columns the tables, and chunk by chunk of
-// queries the gather.  Reads the engine's inputs and writes only the batch scratch: nothing in Shard::state changes
-int run_placement(Shard *e, int flags, const PlacementArgs &o, phyamd_placement_profile &prof) {
-	static const NniWalkCall call{"phyamd_placement_log_likelihoods", "", "", "the split and pendant matrices are"};
-	int rc;
-	std::vector<double> lengths;
-	if ((rc = check_nni_walk(e, call, flags, nullptr, lengths))) return rc;
-	const int T = e->T, N = e->N, C = e->C, P = e->P, root = e->root;
-	const size_t Q = (size_t)o.queries, L = (size_t)o.lengths;
-	const int nblk = (P + WAVE - 1) / WAVE, Ppad = nblk * WAVE;
-	const size_t segments = ((size_t)Ppad + REWEIGHT_SEGMENT - 1) / REWEIGHT_SEGMENT;
-	if (segments * L > 65535)
-		return fail(PHYAMD_EUNSUPPORTED, "%s: %zu segments of %d patterns x %zu pendant lengths (their product is at most 65535: gridDim.z)", call.name, segments, REWEIGHT_SEGMENT, L);
-	prof.edges = N - 1;
-	for (int n = 0; n < N; n++) {  // d_nni_len [3][N]: sigma t_n | (1 - sigma) t_n | t_n
-		lengths[n] = o.split * e->lengths[n];
-		lengths[(size_t)N + n] = (1.0 - o.split) * e->lengths[n];
-	}
-	std::vector<PlaceEdge> edges;  // the non-root nodes in node order: node n is edge n, or n - 1 above the root
-	for (int n = 0; n < N; n++) {
-		if (n == root) continue;
-		const int u = e->sched.parent[n];
-		edges.push_back(PlaceEdge{n, u == root ? BATCH_ROOT : u, e->left[u] == n ? e->right[u] : e->left[u], {0, 0, 0, 0, 0}});
-	}
-	const bool want_lnl = o.lnl != nullptr;
-	const double room = scratch_room(e, (double)batch_scratch_bytes(e), EngineRoom::MayGrow);
-	const auto fits = [&](size_t cols, size_t queries) {
-		const ScratchPlan p = place_plan(e, L, Q, cols, queries, segments, want_lnl);
-		return p.held(1) || (double)(p.fixed_bytes() + p.item_bytes()) <= room;
-	};
-	size_t cols, chunk;
-	if (!place_chunks((size_t)N, Q, fits, &cols, &chunk)) {
-		const ScratchPlan one = place_plan(e, L, Q, 1, 1, segments, want_lnl);
-		return fail(PHYAMD_EUNSUPPORTED, "%s: the scratch of one query on one edge (%zu bytes: every internal node's lower and upper partial, and the edge's table) does not fit the memory budget",
-		            call.name, one.fixed_bytes() + one.item_bytes());
-	}
-	const ScratchPlan plan = place_plan(e, L, Q, cols, chunk, segments, want_lnl);
-	if (T > 2) {
-		if ((rc = launch_nni_walk(e, plan, lengths, true))) return rc;
-	} else {  // two tips: both edges hang off the root, no partial is read and nothing is walked
-		if ((rc = ensure_batch_scratch(e, 1, plan))) return rc;
-		HIP_TRY(hipMemcpyAsync(e->d_nni_len, lengths.data(), sizeof(double) * lengths.size(), hipMemcpyHostToDevice, e->stream));
-		launch_batch_matrices(e, 1, e->d_lengths, nullptr, e->d_batch_mats);
-		launch_batch_matrices(e, 3, e->d_nni_len, nullptr, e->d_nni_mats);
-	}
-	HIP_TRY(hipMemcpyAsync(e->d_place_pend_len, o.pendant, sizeof(double) * L, hipMemcpyHostToDevice, e->stream));
-	hipLaunchKernelGGL(k_batch_matrices, dim3((unsigned)((L * C * 16 + 255) / 256)), dim3(256), 0, e->stream, C, (int)L, 1, e->d_model, e->d_rates, e->d_place_pend_len.get(), -1,
-	                   (const int32_t *)nullptr, e->d_place_pend.get());
-	HIP_TRY(hipMemcpyAsync(e->d_place_edges, edges.data(), sizeof(PlaceEdge) * edges.size(), hipMemcpyHostToDevice, e->stream));
-	HIP_TRY(hipGetLastError());
-	const bool want_best = o.best_node != nullptr;
-	for (size_t first_node = 0; first_node < (size_t)N; first_node += cols) {
-		const size_t ncols = std::min(cols, (size_t)N - first_node);
-		const bool holds_root = (size_t)root >= first_node && (size_t)root < first_node + ncols;
-		const size_t first_edge = first_node <= (size_t)root ? first_node : first_node - 1, E = ncols - (holds_root ? 1 : 0);
-		if (E > 0) {
-			const PlaceTableArgs ta{e->d_place_edges.get() + first_edge, T, N, P, C, nblk, (int)L, e->d_tipmask, e->d_freqs, e->d_props, e->d_weights, e->d_batch_mats, e->d_nni_mats,
-			                        e->d_place_pend, e->d_batch_lower, e->d_batch_upper, e->d_place_table};
-			hipLaunchKernelGGL(k_place_table4, dim3(nblk, (unsigned)E), dim3(WAVE, C), 0, e->stream, ta);
-		}
-		prof.query_chunks = 0;
-		for (size_t first = 0; first < Q; first += chunk) {
-			const size_t n = std::min(chunk, Q - first);
-			if (E > 0) {
-				HIP_TRY(hipMemcpyAsync(e->d_place_raw, o.masks + first * (size_t)P, n * (size_t)P, hipMemcpyHostToDevice, e->stream));
-				const int groups = Ppad / 8;
-				hipLaunchKernelGGL(k_place_masks, dim3((unsigned)(((size_t)groups * n + 255) / 256)), dim3(256), 0, e->stream, (int)n, P, groups, e->d_place_raw.get(),
-				                   e->d_place_packed.get());
-				const unsigned lanes = (unsigned)std::min<size_t>((n + WAVE - 1) / WAVE * WAVE, PLACE_MAX_QUERIES);
-				const PlaceScoreArgs sa{e->d_place_table, e->d_place_packed, e->d_place_slab, (int)E, (int)n, Ppad, (int)segments, (int)L};
-				hipLaunchKernelGGL(k_place_score4, dim3((unsigned)((n + lanes - 1) / lanes), (unsigned)((E + PLACE_EDGES - 1) / PLACE_EDGES), (unsigned)(segments * L)), dim3(lanes), 0,
-				                   e->stream, sa);
-			}
-			const PlaceFinishArgs fa{e->d_place_slab, want_lnl ? e->d_place_out.get() : nullptr, want_best ? e->d_place_best_lnl.get() : nullptr, e->d_place_best_node,
-			                         (int)E, (int)n, (int)segments, (int)L, (int)ncols, (int)first_node, (int)first_edge, root, (int)first, (int)Q, first_node > 0 ? 1 : 0};
-			hipLaunchKernelGGL(k_place_finish, dim3((unsigned)((L * n + 255) / 256)), dim3(256), 0, e->stream, fa);
-			HIP_TRY(hipGetLastError());
-			for (size_t l = 0; l < L && want_lnl; l++) {  // out [L][n][ncols] into lnl [L][Q][N] at (l, first, first_node)
-				double *dst = o.lnl + (l * Q + first) * N + first_node;
-				const double *src = e->d_place_out.get() + l * n * ncols;
-				if (ncols == (size_t)N) HIP_TRY(hipMemcpyAsync(dst, src, sizeof(double) * n * N, hipMemcpyDeviceToHost, e->stream));
-				else HIP_TRY(hipMemcpy2DAsync(dst, sizeof(double) * N, src, sizeof(double) * ncols, sizeof(double) * ncols, n, hipMemcpyDeviceToHost, e->stream));
-			}
-			HIP_TRY(hipStreamSynchronize(e->stream));  // (the next chunk writes the same arrays; also covers `lengths` and `edges`)
-			prof.query_chunks++;
-		}
-		prof.edge_chunks++;
-	}
-	if (want_best) {
-		HIP_TRY(hipMemcpyAsync(o.best_node, e->d_place_best_node, sizeof(int32_t) * L * Q, hipMemcpyDeviceToHost, e->stream));
-		if (o.best_lnl) HIP_TRY(hipMemcpyAsync(o.best_lnl, e->d_place_best_lnl, sizeof(double) * L * Q, hipMemcpyDeviceToHost, e->stream));
-		HIP_TRY(hipStreamSynchronize(e->stream));
-	}
-	return PHYAMD_OK;
-}
-
-int shard_placement(Shard *e, int flags, const PlacementArgs &o) {
-	CHECK_ENGINE(e);
-	phyamd_placement_profile start{};
-	start.queries = o.queries, start.lengths = o.lengths;
-	return profiled_call(e, &Shard::place_prof, start, [&](phyamd_placement_profile &prof) { return run_placement(e, flags, o, prof); });
-}
-
-// ---- the same for 20 states (phyamd_placement_log_likelihoods_general) ------------------------------------------------------------
-
-struct PlacementGeneralArgs {
-	PlacementArgs p;       // masks: the class codes [queries][P], validated (phyamd_placement_log_likelihoods_general)
-	int32_t set_count;
-	const uint64_t *sets;  // [set_count], validated
-};
-
-constexpr size_t PLACE_GEN_MATRIX = (size_t)PLACE_GEN_STATES * PLACE_GEN_STATES;
-
-// whatever the item count: the lengths, their matrices and images, the call's sets and every query's best edge so far; for a chunk
-// of `cols` node columns and `queries` queries: the edges, their nodes' own partials, the table, the caller's code rows and their
-// packed form, the slab and the result
-ScratchPlan place_gen_plan(Shard *e, size_t L, size_t all_queries, size_t cols, size_t queries, size_t segments, size_t Ppad, bool want_lnl) {
-	const size_t D = sizeof(double), N = (size_t)e->N, C = (size_t)e->C, M = 2 * N + L, image = MatImage<2, 5>::SIZE;
-	ScratchPlan p;
-	p.add(e->d_placeg_len, 0, D * M);
-	p.add(e->d_placeg_zero, 0, M);
-	p.add(e->d_placeg_mats, 0, D * M * C * PLACE_GEN_MATRIX);
-	p.add(e->d_placeg_dmats, 0, D * M * C * PLACE_GEN_MATRIX);
-	p.add(e->d_placeg_imgs, 0, D * (2 * N * C * image + L * C * PLACE_GEN_CLASS_IMAGE));
-	p.add(e->d_placeg_sets, 0, sizeof(unsigned long long) * PLACE_GEN_MAX_SETS);
-	p.add(e->d_place_best_lnl, 0, D * L * all_queries);
-	p.add(e->d_place_best_node, 0, sizeof(int32_t) * L * all_queries);
-	p.add(e->d_placeg_edges, 0, sizeof(PlaceGenEdge) * cols);
-	p.add(e->d_placeg_own, 0, D * cols * node_partial_doubles(e));
-	p.add(e->d_placeg_owns, 0, sizeof(PlaceGenOwn) * cols);
-	p.add(e->d_place_table, 0, D * L * cols * Ppad * PLACE_GEN_CLASSES);
-	p.add(e->d_place_raw, 0, queries * (size_t)e->P);
-	p.add(e->d_place_packed, 0, queries * Ppad);
-	p.add(e->d_place_slab, 0, D * segments * L * cols * queries);
-	p.add(e->d_place_out, 0, want_lnl ? D * L * cols * queries : 0);
-	return p;
-}
-
-// the engine's resident partials (require_resident_partials: the engine is afterwards a keep-partials engine that has run the
-// flags-0 gradient), then chunk by chunk of node columns the tables, and chunk by chunk of queries the gather (run_placement's
-// chunks).  Writes only the batch scratch beyond that evaluation
-int run_placement_general(Shard *e, int flags, const PlacementGeneralArgs &g, phyamd_placement_profile &prof) {
-	static const char *const name = "phyamd_placement_log_likelihoods_general";
-	const PlacementArgs &o = g.p;
-	if (e->S == 4) return fail(PHYAMD_EUNSUPPORTED, "%s: the class tables are built for 20 states (the engine has 4: use phyamd_placement_log_likelihoods)", name);
-	if (e->S != PLACE_GEN_STATES) return fail(PHYAMD_EUNSUPPORTED, "%s: the class tables are built for 20 states (the engine has %d: tables of 64 classes are not built)", name, e->S);
-	if (e->C > BATCH_MAX_CATEGORIES) return fail(PHYAMD_EUNSUPPORTED, "%s: %d rate categories (at most %d categories)", name, e->C, BATCH_MAX_CATEGORIES);
-	if (flags != 0) return fail(PHYAMD_EUNSUPPORTED, "%s: flags %d (no flags are defined: pass 0)", name, flags);
-	if (e->tiles > 1) return fail(PHYAMD_EUNSUPPORTED, "%s: the patterns are tiled and the call needs every partial of all patterns resident", name);
-	if (std::any_of(e->explicit_host.begin(), e->explicit_host.end(), [](uint8_t x) { return x != 0; }))
-		return fail(PHYAMD_EUNSUPPORTED, "%s: a node has explicit matrices, which cannot be split at sigma", name);
-	if (!e->have_eigen) return fail(PHYAMD_EINVAL, "%s needs the eigen system (phyamd_set_eigen): the split and pendant matrices are formed from it", name);
-	int rc;
-	if ((rc = check_ready(e))) return rc;
-	static const char *const rescaling = "%s: the engine is rescaling%s and the tables do not rescale (underflow is otherwise -inf in band)";
-	if (e->scaling_on) return fail(PHYAMD_EUNSUPPORTED, rescaling, name, "");
-	if ((rc = require_resident_partials(e, name))) return rc;
-	if (e->scaling_on) return fail(PHYAMD_EUNSUPPORTED, rescaling, name, " (PHYAMD_RESCALE_AUTO switched it on during the call's own evaluation)");
-	if (e->tiles > 1) return fail(PHYAMD_EUNSUPPORTED, "%s: the patterns are tiled and the call needs every partial of all patterns resident", name);
-	const int T = e->T, N = e->N, C = e->C, P = e->P, root = e->root;
-	const size_t Q = (size_t)o.queries, L = (size_t)o.lengths;
-	const int Ppad = (P + PLACE_GEN_BLOCK - 1) / PLACE_GEN_BLOCK * PLACE_GEN_BLOCK;
-	const size_t segments = ((size_t)Ppad + REWEIGHT_SEGMENT - 1) / REWEIGHT_SEGMENT, groups_l = (L + PLACE_GEN_LENGTHS - 1) / PLACE_GEN_LENGTHS;
-	if (segments * L > 65535)
-		return fail(PHYAMD_EUNSUPPORTED, "%s: %zu segments of %d patterns x %zu pendant lengths (their product is at most 65535: gridDim.z)", name, segments, REWEIGHT_SEGMENT, L);
-	prof.edges = N - 1;
-	const size_t npd = node_partial_doubles(e);
-	for (int n = 0; n < N; n++)
-		if (n != root && (e->sched.upper_slot[n] < 0 || !e->d_upper)) return fail(PHYAMD_EDEVICE, "%s: node %d has no resident upper partial", name, n);
-	const bool want_lnl = o.lnl != nullptr;
-	const double room = scratch_room(e, (double)batch_scratch_bytes(e), EngineRoom::MayGrow);
-	const auto fits = [&](size_t cols, size_t queries) {
-		const ScratchPlan p = place_gen_plan(e, L, Q, cols, queries, segments, (size_t)Ppad, want_lnl);
-		return p.held(1) || (double)(p.fixed_bytes() + p.item_bytes()) <= room;
-	};
-	size_t cols, chunk;
-	if (!place_chunks((size_t)N, Q, fits, &cols, &chunk)) {
-		const ScratchPlan one = place_gen_plan(e, L, Q, 1, 1, segments, (size_t)Ppad, want_lnl);
-		return fail(PHYAMD_EUNSUPPORTED, "%s: the scratch of one query on one edge (%zu bytes: the split and pendant matrices and their images, the node's own partial and the edge's table) does not fit the memory budget",
-		            name, one.fixed_bytes() + one.item_bytes());
-	}
-	const ScratchPlan plan = place_gen_plan(e, L, Q, cols, chunk, segments, (size_t)Ppad, want_lnl);
-	if ((rc = ensure_batch_scratch(e, 1, plan))) return rc;
-	// the lengths sigma t_n | (1 - sigma) t_n | pendant, their matrices through the engine's own matrix kernel, and the images
-	const size_t M = 2 * (size_t)N + L, image = MatImage<2, 5>::SIZE;
-	std::vector<double> lengths(M);
-	for (int n = 0; n < N; n++) {
-		lengths[n] = o.split * e->lengths[n];
-		lengths[(size_t)N + n] = (1.0 - o.split) * e->lengths[n];
-	}
-	std::copy(o.pendant, o.pendant + L, lengths.begin() + 2 * (size_t)N);
-	unsigned long long sets[PLACE_GEN_MAX_SETS] = {};
-	for (int q = 0; q < g.set_count; q++) sets[q] = g.sets[q];
-	HIP_TRY(hipMemcpyAsync(e->d_placeg_len, lengths.data(), sizeof(double) * M, hipMemcpyHostToDevice, e->stream));
-	HIP_TRY(hipMemcpyAsync(e->d_placeg_sets, sets, sizeof sets, hipMemcpyHostToDevice, e->stream));
-	HIP_TRY(hipMemsetAsync(e->d_placeg_zero, 0, M, e->stream));
-	{
-		const size_t total = M * C * PLACE_GEN_MATRIX;
-		hipLaunchKernelGGL(k_transition_matrices, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, e->stream, PLACE_GEN_STATES, C, (int)M, e->d_model.get(),
-		                   e->d_rates.get(), e->d_placeg_len.get(), e->d_placeg_zero.get(), -1, e->d_placeg_mats.get(), e->d_placeg_dmats.get());
-	}
-	double *img_lo = e->d_placeg_imgs.get(), *img_hi = img_lo + (size_t)N * C * image, *img_cls = img_hi + (size_t)N * C * image;
-	const double *mats_hi = e->d_placeg_mats.get() + (size_t)N * C * PLACE_GEN_MATRIX, *mats_pend = mats_hi + (size_t)N * C * PLACE_GEN_MATRIX;
-	build_matrix_images(e, N * C, e->d_placeg_mats, img_lo);
-	hipLaunchKernelGGL(k_classplace_transposed_images, dim3((unsigned)(N * C)), dim3(256), 0, e->stream, mats_hi, img_hi);
-	hipLaunchKernelGGL(k_classplace_images, dim3((unsigned)(L * C)), dim3(256), 0, e->stream, C, mats_pend, e->d_props.get(), e->d_placeg_sets.get(), (int)g.set_count, img_cls);
-	HIP_TRY(hipGetLastError());
-	const bool want_best = o.best_node != nullptr;
-	std::vector<PlaceGenEdge> edges;
-	std::vector<PlaceGenOwn> owns;
-	const size_t msz = (size_t)C * PLACE_GEN_MATRIX;
-	for (size_t first_node = 0; first_node < (size_t)N; first_node += cols) {
-		const size_t ncols = std::min(cols, (size_t)N - first_node);
-		const bool holds_root = (size_t)root >= first_node && (size_t)root < first_node + ncols;
-		const size_t first_edge = first_node <= (size_t)root ? first_node : first_node - 1, E = ncols - (holds_root ? 1 : 0);
-		edges.clear();
-		owns.clear();
-		for (size_t col = 0; col < ncols; col++) {  // the chunk's non-root nodes in node order
-			const int n = (int)(first_node + col);
-			if (n == root) continue;
-			PlaceGenEdge ed{e->d_upper + (size_t)e->sched.upper_slot[n] * npd, nullptr, n, {0, 0, 0}};
-			if (n >= T) {  // a stored array is the message P_n p_n: the node's own partial, into this column's temporary
-				PlaceGenOwn own{};
-				own.out = e->d_placeg_own.get() + col * npd;
-				const int ch[2] = {e->left[n], e->right[n]};
-				for (int side = 0; side < 2; side++) {
-					const int v = ch[side];
-					if (v >= T && e->sched.core_index[v] < 0) return fail(PHYAMD_EDEVICE, "%s: node %d has no resident lower partial", name, v);
-					(side ? own.mat_r : own.mat_l) = e->d_mats + (size_t)v * msz;
-					(side ? own.src_r : own.src_l) = v < T ? nullptr : e->d_lower + (size_t)e->sched.core_index[v] * npd;
-					(side ? own.row_r : own.row_l) = v < T ? e->d_tipmask + (size_t)v * P : nullptr;
-				}
-				owns.push_back(own);
-				ed.own = own.out;
-			}
-			edges.push_back(ed);
-		}
-		if (!owns.empty()) {
-			HIP_TRY(hipMemcpyAsync(e->d_placeg_owns, owns.data(), sizeof(PlaceGenOwn) * owns.size(), hipMemcpyHostToDevice, e->stream));
-			hipLaunchKernelGGL(k_classplace_own, dim3((unsigned)((P + 255) / 256), (unsigned)owns.size(), (unsigned)C), dim3(256), 0, e->stream, e->d_placeg_owns.get(), P, e->Pp,
-			                   e->d_tipsets.get());
-		}
-		if (E > 0) {
-			HIP_TRY(hipMemcpyAsync(e->d_placeg_edges, edges.data(), sizeof(PlaceGenEdge) * E, hipMemcpyHostToDevice, e->stream));
-			const PlaceTableGenArgs ta{e->d_placeg_edges, P, e->Pp, Ppad, C, (int)L, e->upper_fold ? 1 : 0, PLACE_GEN_STATES + 1 + g.set_count, e->d_tipmask, e->d_tipsets,
-			                           e->d_freqs, e->d_weights, img_lo, img_hi, img_cls, e->d_place_table};
-			hipLaunchKernelGGL(k_classplace_table, dim3((unsigned)(Ppad / PLACE_GEN_BLOCK), (unsigned)E, (unsigned)groups_l), dim3(GenGeo<2>::WAVES * 64), 0, e->stream, ta);
-		}
-		prof.query_chunks = 0;
-		for (size_t first = 0; first < Q; first += chunk) {
-			const size_t n = std::min(chunk, Q - first);
-			if (E > 0) {
-				HIP_TRY(hipMemcpyAsync(e->d_place_raw, o.masks + first * (size_t)P, n * (size_t)P, hipMemcpyHostToDevice, e->stream));
-				const int groups = Ppad / 8;
-				hipLaunchKernelGGL(k_classplace_codes, dim3((unsigned)(((size_t)groups * n + 255) / 256)), dim3(256), 0, e->stream, (int)n, P, groups, e->d_place_raw.get(),
-				                   e->d_place_packed.get());
-				const unsigned lanes = (unsigned)std::min<size_t>((n + WAVE - 1) / WAVE * WAVE, PLACE_MAX_QUERIES);
-				const PlaceScoreArgs sa{e->d_place_table, e->d_place_packed, e->d_place_slab, (int)E, (int)n, Ppad, (int)segments, (int)L};
-				hipLaunchKernelGGL(k_classplace_score, dim3((unsigned)((n + lanes - 1) / lanes), (unsigned)((E + PLACE_EDGES - 1) / PLACE_EDGES), (unsigned)(segments * L)), dim3(lanes), 0,
-				                   e->stream, sa);
-			}
-			const PlaceFinishArgs fa{e->d_place_slab, want_lnl ? e->d_place_out.get() : nullptr, want_best ? e->d_place_best_lnl.get() : nullptr, e->d_place_best_node,
-			                         (int)E, (int)n, (int)segments, (int)L, (int)ncols, (int)first_node, (int)first_edge, root, (int)first, (int)Q, first_node > 0 ? 1 : 0};
-			hipLaunchKernelGGL(k_place_finish, dim3((unsigned)((L * n + 255) / 256)), dim3(256), 0, e->stream, fa);
-			HIP_TRY(hipGetLastError());
-			for (size_t l = 0; l < L && want_lnl; l++) {  // out [L][n][ncols] into lnl [L][Q][N] at (l, first, first_node)
-				double *dst = o.lnl + (l * Q + first) * N + first_node;
-				const double *src = e->d_place_out.get() + l * n * ncols;
-				if (ncols == (size_t)N) HIP_TRY(hipMemcpyAsync(dst, src, sizeof(double) * n * N, hipMemcpyDeviceToHost, e->stream));
-				else HIP_TRY(hipMemcpy2DAsync(dst, sizeof(double) * N, src, sizeof(double) * ncols, sizeof(double) * ncols, n, hipMemcpyDeviceToHost, e->stream));
-			}
-			HIP_TRY(hipStreamSynchronize(e->stream));  // (the next chunk writes the same arrays; also covers `lengths`, `sets`, `edges` and `owns`)
-			prof.query_chunks++;
-		}
-		prof.edge_chunks++;
-	}
-	if (want_best) {
-		HIP_TRY(hipMemcpyAsync(o.best_node, e->d_place_best_node, sizeof(int32_t) * L * Q, hipMemcpyDeviceToHost, e->stream));
-		if (o.best_lnl) HIP_TRY(hipMemcpyAsync(o.best_lnl, e->d_place_best_lnl, sizeof(double) * L * Q, hipMemcpyDeviceToHost, e->stream));
-		HIP_TRY(hipStreamSynchronize(e->stream));
-	}
-	return PHYAMD_OK;
-}
-
-int shard_placement_general(Shard *e, int flags, const PlacementGeneralArgs &g) {
-	CHECK_ENGINE(e);
-	phyamd_placement_profile start{};
-	start.queries = g.p.queries, start.lengths = g.p.lengths;
-	return profiled_call(e, &Shard::place_prof, start, [&](phyamd_placement_profile &prof) { return run_placement_general(e, flags, g, prof); });
-}
-
-// ---- the three branches around chosen placements, optimised (phyamd_placement_optimize) ------------------------------------------
-
-struct PlacementOptimizeArgs {
-	int32_t queries;
-	const uint8_t *masks;       // [queries][P], validated (phyamd_placement_optimize)
-	int32_t count;
-	const int32_t *candidates;  // [count][2]: (query, node), the queries validated
-	const double *pendant_start;
-	double split;
-	int32_t branches;
-	double lower, upper, tolerance;
-	int32_t max_iterations;
-	double lnl_tolerance;
-	int32_t max_passes;
-	double *lengths, *lnl, *initial_lnl;
-	int32_t *passes;
-};
-
-// the NNI walk's (nni_base_plan), and for the `chunk` candidates that run at once -- whatever their edges and queries: as many of
-// each as there can be -- the distinct edges and pi o U of each, the distinct queries' mask rows, the candidates, their starts,
-// coefficients, results and status words
-ScratchPlan qopt_plan(Shard *e, size_t chunk) {
-	const size_t D = sizeof(double), C = (size_t)e->C, plane = ((size_t)e->P + WAVE - 1) / WAVE * WAVE * 4;
-	const size_t edges = std::min(chunk, (size_t)e->N - 1);
-	ScratchPlan p = nni_base_plan(e);
-	p.add(e->d_qopt_edges, 0, sizeof(PlaceEdge) * edges);
-	p.add(e->d_qopt_fU, 0, D * edges * C * plane);
-	p.add(e->d_qopt_masks, 0, chunk * (size_t)e->P);
-	p.add(e->d_qopt_cands, 0, sizeof(QoptCand) * chunk);
-	p.add(e->d_qopt_start, 0, D * chunk * 3);
-	p.add(e->d_qopt_K, 0, D * chunk * C * plane);
-	p.add(e->d_qopt_res, 0, D * chunk * 5);
-	p.add(e->d_qopt_status, 0, sizeof(int32_t) * chunk * QOPT_STATUS);
-	return p;
-}
-
-// one walk of the engine's tree with every upper parked, then chunk by chunk of the candidates sorted by edge: pi o U of the chunk's
-// edges and one workgroup per candidate that runs its whole rule.  Reads the engine's inputs and writes only the batch scratch:
-// nothing in Shard::state changes
-int run_placement_optimize(Shard *e, int flags, const PlacementOptimizeArgs &o, phyamd_placement_optimize_profile &prof) {
-	static const NniWalkCall call{"phyamd_placement_optimize", "", "", "the likelihood in a branch length is"};
-	int rc;
-	std::vector<double> lengths;
-	if ((rc = check_ready(e))) return fail(rc, "%s: the engine is not ready: %s", call.name, std::string(g_last_error).c_str());
-	if ((rc = check_nni_walk(e, call, flags, nullptr, lengths))) return rc;
-	const int T = e->T, N = e->N, C = e->C, P = e->P, root = e->root;
-	const size_t count = (size_t)o.count;
-	for (size_t i = 0; i < count; i++)
-		if (o.candidates[2 * i + 1] == root)
-			return fail(PHYAMD_EINVAL, "%s: candidates[%zu] = (%d, %d): the root (node %d) has no branch to place a query on", call.name, i, o.candidates[2 * i], root, root);
-	const int nblk = (P + WAVE - 1) / WAVE;
-	// the candidates by edge, then query, then position: a chunk's candidates of one edge read the same pi o U
-	std::vector<int32_t> order(count);
-	for (size_t i = 0; i < count; i++) order[i] = (int32_t)i;
-	std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
-		const int32_t *ca = o.candidates + 2 * (size_t)a, *cb = o.candidates + 2 * (size_t)b;
-		return ca[1] != cb[1] ? ca[1] < cb[1] : ca[0] != cb[0] ? ca[0] < cb[0] : a < b;
-	});
-	prof.edges = 1;
-	for (size_t i = 1; i < count; i++) prof.edges += o.candidates[2 * (size_t)order[i] + 1] != o.candidates[2 * (size_t)order[i - 1] + 1];
-	// the chunk: all candidates (at most gridDim.x's) if the scratch holds as much or has room for it, else what fits beside the walk
-	const size_t want = std::min<size_t>(count, BATCH_MAX_CHUNK);
-	size_t chunk = want;
-	if (batch_items_held(e, qopt_plan(e, want)) < 1) {
-		const double room = scratch_room(e, (double)batch_scratch_bytes(e), EngineRoom::MayGrow);
-		chunk = largest_that(1, want, [&](size_t x) {
-			const ScratchPlan p = qopt_plan(e, x);
-			return (double)(p.fixed_bytes() + p.item_bytes()) <= room;
-		});
-		if (chunk < 1) {
-			const ScratchPlan one = qopt_plan(e, 1);
-			return fail(PHYAMD_EUNSUPPORTED, "%s: the scratch of one candidate (%zu bytes: every internal node's lower and upper partial, and two planes) does not fit the memory budget",
-			            call.name, one.fixed_bytes() + one.item_bytes());
-		}
-	}
-	const ScratchPlan plan = qopt_plan(e, chunk);
-	if (T > 2) {
-		if ((rc = launch_nni_walk(e, plan, lengths, false))) return rc;
-	} else {  // two tips: both edges hang off the root, no partial is read and nothing is walked
-		if ((rc = ensure_batch_scratch(e, 1, plan))) return rc;
-		launch_batch_matrices(e, 1, e->d_lengths, nullptr, e->d_batch_mats);
-	}
-	HIP_TRY(hipGetLastError());
-	std::vector<PlaceEdge> edges;
-	std::vector<QoptCand> cands;
-	std::vector<double> start, out;
-	std::vector<uint8_t> rows;
-	std::vector<int32_t> row_of((size_t)o.queries), status;
-	for (size_t first = 0; first < count; first += chunk) {
-		const size_t n = std::min(chunk, count - first);
-		edges.clear(), cands.clear(), start.clear(), rows.clear();
-		std::fill(row_of.begin(), row_of.end(), -1);
-		for (size_t i = 0; i < n; i++) {
-			const size_t at = (size_t)order[first + i];
-			const int q = o.candidates[2 * at], node = o.candidates[2 * at + 1];
-			if (edges.empty() || edges.back().n != node) {
-				const int u = e->sched.parent[node];
-				edges.push_back(PlaceEdge{node, u == root ? BATCH_ROOT : u, e->left[u] == node ? e->right[u] : e->left[u], {0, 0, 0, 0, 0}});
-			}
-			if (row_of[q] < 0) {
-				row_of[q] = (int32_t)(rows.size() / (size_t)P);
-				rows.insert(rows.end(), o.masks + (size_t)q * P, o.masks + (size_t)(q + 1) * P);
-			}
-			cands.push_back(QoptCand{node, (int32_t)edges.size() - 1, row_of[q], {0, 0, 0, 0, 0}});
-			start.push_back(o.split * e->lengths[node]);
-			start.push_back(o.pendant_start ? o.pendant_start[at] : 0.1);
-			start.push_back((1.0 - o.split) * e->lengths[node]);
-		}
-		HIP_TRY(hipMemcpyAsync(e->d_qopt_edges, edges.data(), sizeof(PlaceEdge) * edges.size(), hipMemcpyHostToDevice, e->stream));
-		HIP_TRY(hipMemcpyAsync(e->d_qopt_masks, rows.data(), rows.size(), hipMemcpyHostToDevice, e->stream));
-		HIP_TRY(hipMemcpyAsync(e->d_qopt_cands, cands.data(), sizeof(QoptCand) * n, hipMemcpyHostToDevice, e->stream));
-		HIP_TRY(hipMemcpyAsync(e->d_qopt_start, start.data(), sizeof(double) * start.size(), hipMemcpyHostToDevice, e->stream));
-		const QoptUpperArgs ua{e->d_qopt_edges, T, N, P, C, nblk, e->d_tipmask, e->d_freqs, e->d_batch_mats, e->d_batch_lower, e->d_batch_upper, e->d_qopt_fU};
-		hipLaunchKernelGGL(k_qopt_upper4, dim3(nblk, (unsigned)edges.size()), dim3(WAVE, C), 0, e->stream, ua);
-		QoptSolveArgs s{};
-		s.cands = e->d_qopt_cands, s.T = T, s.P = P, s.C = C, s.nblk = nblk, s.branches = o.branches, s.max_iterations = o.max_iterations, s.max_passes = o.max_passes;
-		s.lower = o.lower, s.upper = o.upper, s.tolerance = o.tolerance, s.lnl_tolerance = o.lnl_tolerance;
-		s.tipmask = e->d_tipmask, s.masks = e->d_qopt_masks, s.props = e->d_props, s.model = e->d_model, s.rates = e->d_rates, s.weights = e->d_weights;
-		s.start = e->d_qopt_start, s.lower_all = e->d_batch_lower, s.fU = e->d_qopt_fU, s.K = e->d_qopt_K, s.out = e->d_qopt_res, s.status = e->d_qopt_status;
-		hipLaunchKernelGGL(k_qopt_solve4, dim3((unsigned)n), dim3(CBOPT_THREADS), 0, e->stream, s);
-		HIP_TRY(hipGetLastError());
-		out.resize(n * 5);
-		status.resize(n * QOPT_STATUS);
-		HIP_TRY(hipMemcpyAsync(out.data(), e->d_qopt_res, sizeof(double) * out.size(), hipMemcpyDeviceToHost, e->stream));
-		HIP_TRY(hipMemcpyAsync(status.data(), e->d_qopt_status, sizeof(int32_t) * status.size(), hipMemcpyDeviceToHost, e->stream));
-		HIP_TRY(hipStreamSynchronize(e->stream));  // (the next chunk writes the same arrays; also covers `lengths` and the lists)
-		for (size_t i = 0; i < n; i++) {
-			const size_t to = (size_t)order[first + i];
-			const double *v = &out[i * 5];
-			std::copy(v, v + 3, o.lengths + to * 3);
-			o.lnl[to] = v[3];
-			if (o.initial_lnl) o.initial_lnl[to] = v[4];
-			if (o.passes) o.passes[to] = status[i * QOPT_STATUS + QOPT_PASSES];
-			prof.visits += status[i * QOPT_STATUS + QOPT_VISITS];
-			prof.iterations += status[i * QOPT_STATUS + QOPT_ITERATIONS];
-		}
-		prof.chunks++;
-	}
-	return PHYAMD_OK;
-}
-
-int shard_placement_optimize(Shard *e, int flags, const PlacementOptimizeArgs &o) {
-	CHECK_ENGINE(e);
-	phyamd_placement_optimize_profile start{};
-	start.candidates = o.count;
-	return profiled_call(e, &Shard::qopt_prof, start, [&](phyamd_placement_optimize_profile &prof) { return run_placement_optimize(e, flags, o, prof); });
-}
-
-// ---- the same for 20 states (phyamd_placement_optimize_general) -------------------------------------------------------------------
-
-struct PlacementOptimizeGeneralArgs {
-	PlacementOptimizeArgs p;  // masks: the class codes [queries][P], validated (phyamd_placement_optimize_general)
-	int32_t set_count;
-	const uint64_t *sets;     // [set_count], validated
-};
-
-// for the `chunk` candidates that run at once -- whatever their edges and queries: as many of each as there can be -- the call's
-// sets, the own partials of the distinct internal edges and what k_classplace_own forms each from, the distinct queries' code rows,
-// the candidates, their starts, coefficients, results and status words
-ScratchPlan qopt_gen_plan(Shard *e, size_t chunk) {
-	const size_t D = sizeof(double), npd = node_partial_doubles(e);
-	const size_t owns = std::min(chunk, (size_t)std::max(0, e->T - 2));
-	ScratchPlan p;
-	p.add(e->d_placeg_sets, 0, sizeof(unsigned long long) * PLACE_GEN_MAX_SETS);
-	p.add(e->d_placeg_own, 0, D * owns * npd);
-	p.add(e->d_placeg_owns, 0, sizeof(PlaceGenOwn) * owns);
-	p.add(e->d_qopt_masks, 0, chunk * (size_t)e->P);
-	p.add(e->d_qoptg_cands, 0, sizeof(ClassOptCand) * chunk);
-	p.add(e->d_qopt_start, 0, D * chunk * 3);
-	p.add(e->d_qopt_K, 0, D * chunk * npd);
-	p.add(e->d_qopt_res, 0, D * chunk * 5);
-	p.add(e->d_qopt_status, 0, sizeof(int32_t) * chunk * QOPT_STATUS);
-	return p;
-}
-
-// the engine's resident partials (require_resident_partials: the engine is afterwards a keep-partials engine that has run the
-// flags-0 gradient), then chunk by chunk of the candidates sorted by edge: the own partials of the chunk's distinct internal edges
-// and one workgroup per candidate that runs its whole rule.  Writes only the batch scratch beyond that evaluation
-int run_placement_optimize_general(Shard *e, int flags, const PlacementOptimizeGeneralArgs &g, phyamd_placement_optimize_profile &prof) {
-	static const char *const name = "phyamd_placement_optimize_general";
-	const PlacementOptimizeArgs &o = g.p;
-	if (e->S == 4) return fail(PHYAMD_EUNSUPPORTED, "%s: the class tables are built for 20 states (the engine has 4: use phyamd_placement_optimize)", name);
-	if (e->S != PLACE_GEN_STATES) return fail(PHYAMD_EUNSUPPORTED, "%s: the class tables are built for 20 states (the engine has %d: tables of 64 classes are not built)", name, e->S);
-	if (e->C > BATCH_MAX_CATEGORIES) return fail(PHYAMD_EUNSUPPORTED, "%s: %d rate categories (at most %d categories)", name, e->C, BATCH_MAX_CATEGORIES);
-	if (flags != 0) return fail(PHYAMD_EUNSUPPORTED, "%s: flags %d (no flags are defined: pass 0)", name, flags);
-	if (e->tiles > 1) return fail(PHYAMD_EUNSUPPORTED, "%s: the patterns are tiled and the call needs every partial of all patterns resident", name);
-	if (std::any_of(e->explicit_host.begin(), e->explicit_host.end(), [](uint8_t x) { return x != 0; }))
-		return fail(PHYAMD_EUNSUPPORTED, "%s: a node has explicit matrices, which cannot be split at sigma", name);
-	if (!e->have_eigen) return fail(PHYAMD_EINVAL, "%s needs the eigen system (phyamd_set_eigen): the likelihood in a branch length is formed from it", name);
-	int rc;
-	if ((rc = check_ready(e))) return rc;
-	const int T = e->T, C = e->C, P = e->P, root = e->root;
-	const size_t count = (size_t)o.count;
-	for (size_t i = 0; i < count; i++)
-		if (o.candidates[2 * i + 1] == root)
-			return fail(PHYAMD_EINVAL, "%s: candidates[%zu] = (%d, %d): the root (node %d) has no branch to place a query on", name, i, o.candidates[2 * i], root, root);
-	static const char *const rescaling = "%s: the engine is rescaling%s and the solve does not rescale (underflow is otherwise -inf in band)";
-	if (e->scaling_on) return fail(PHYAMD_EUNSUPPORTED, rescaling, name, "");
-	if ((rc = require_resident_partials(e, name))) return rc;
-	if (e->scaling_on) return fail(PHYAMD_EUNSUPPORTED, rescaling, name, " (PHYAMD_RESCALE_AUTO switched it on during the call's own evaluation)");
-	if (e->tiles > 1) return fail(PHYAMD_EUNSUPPORTED, "%s: the patterns are tiled and the call needs every partial of all patterns resident", name);
-	const size_t npd = node_partial_doubles(e), msz = (size_t)C * PLACE_GEN_MATRIX;
-	// the candidates by edge, then query, then position: a chunk's candidates of one edge read the same own partial
-	std::vector<int32_t> order(count);
-	for (size_t i = 0; i < count; i++) order[i] = (int32_t)i;
-	std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
-		const int32_t *ca = o.candidates + 2 * (size_t)a, *cb = o.candidates + 2 * (size_t)b;
-		return ca[1] != cb[1] ? ca[1] < cb[1] : ca[0] != cb[0] ? ca[0] < cb[0] : a < b;
-	});
-	prof.edges = 1;
-	for (size_t i = 1; i < count; i++) prof.edges += o.candidates[2 * (size_t)order[i] + 1] != o.candidates[2 * (size_t)order[i - 1] + 1];
-	for (size_t i = 0; i < count; i++) {
-		const int n = o.candidates[2 * i + 1];
-		if (e->sched.upper_slot[n] < 0 || !e->d_upper) return fail(PHYAMD_EDEVICE, "%s: node %d has no resident upper partial", name, n);
-	}
-	// the chunk: all candidates (at most gridDim.x's) if the scratch holds as much or has room for it, else what fits
-	const size_t want = std::min<size_t>(count, BATCH_MAX_CHUNK);
-	size_t chunk = want;
-	if (!qopt_gen_plan(e, want).held(1)) {
-		const double room = scratch_room(e, (double)batch_scratch_bytes(e), EngineRoom::MayGrow);
-		chunk = largest_that(1, want, [&](size_t x) {
-			const ScratchPlan p = qopt_gen_plan(e, x);
-			return (double)(p.fixed_bytes() + p.item_bytes()) <= room;
-		});
-		if (chunk < 1) {
-			const ScratchPlan one = qopt_gen_plan(e, 1);
-			return fail(PHYAMD_EUNSUPPORTED, "%s: the scratch of one candidate (%zu bytes: its node's own partial and its coefficients, a node's partial each) does not fit the memory budget",
-			            name, one.fixed_bytes() + one.item_bytes());
-		}
-	}
-	const ScratchPlan plan = qopt_gen_plan(e, chunk);
-	if ((rc = ensure_batch_scratch(e, 1, plan))) return rc;
-	unsigned long long sets[PLACE_GEN_MAX_SETS] = {};
-	for (int q = 0; q < g.set_count; q++) sets[q] = g.sets[q];
-	HIP_TRY(hipMemcpyAsync(e->d_placeg_sets, sets, sizeof sets, hipMemcpyHostToDevice, e->stream));
-	std::vector<PlaceGenOwn> owns;
-	std::vector<ClassOptCand> cands;
-	std::vector<double> start, out;
-	std::vector<uint8_t> rows;
-	std::vector<int32_t> row_of((size_t)o.queries), status;
-	for (size_t first = 0; first < count; first += chunk) {
-		const size_t n = std::min(chunk, count - first);
-		owns.clear(), cands.clear(), start.clear(), rows.clear();
-		std::fill(row_of.begin(), row_of.end(), -1);
-		int last_node = -1;
-		const double *own_of_last = nullptr;
-		for (size_t i = 0; i < n; i++) {
-			const size_t at = (size_t)order[first + i];
-			const int q = o.candidates[2 * at], node = o.candidates[2 * at + 1];
-			if (node != last_node) {
-				last_node = node, own_of_last = nullptr;
-				if (node >= T) {  // a stored array is the message P_n p_n: the node's own partial, into this edge's temporary
-					PlaceGenOwn own{};
-					own.out = e->d_placeg_own.get() + owns.size() * npd;
-					const int ch[2] = {e->left[node], e->right[node]};
-					for (int side = 0; side < 2; side++) {
-						const int v = ch[side];
-						if (v >= T && e->sched.core_index[v] < 0) return fail(PHYAMD_EDEVICE, "%s: node %d has no resident lower partial", name, v);
-						(side ? own.mat_r : own.mat_l) = e->d_mats + (size_t)v * msz;
-						(side ? own.src_r : own.src_l) = v < T ? nullptr : e->d_lower + (size_t)e->sched.core_index[v] * npd;
-						(side ? own.row_r : own.row_l) = v < T ? e->d_tipmask + (size_t)v * P : nullptr;
-					}
-					owns.push_back(own);
-					own_of_last = own.out;
-				}
-			}
-			if (row_of[q] < 0) {
-				row_of[q] = (int32_t)(rows.size() / (size_t)P);
-				rows.insert(rows.end(), o.masks + (size_t)q * P, o.masks + (size_t)(q + 1) * P);
-			}
-			cands.push_back(ClassOptCand{e->d_upper + (size_t)e->sched.upper_slot[node] * npd, own_of_last, node, row_of[q]});
-			start.push_back(o.split * e->lengths[node]);
-			start.push_back(o.pendant_start ? o.pendant_start[at] : 0.1);
-			start.push_back((1.0 - o.split) * e->lengths[node]);
-		}
-		if (!owns.empty()) {
-			HIP_TRY(hipMemcpyAsync(e->d_placeg_owns, owns.data(), sizeof(PlaceGenOwn) * owns.size(), hipMemcpyHostToDevice, e->stream));
-			hipLaunchKernelGGL(k_classplace_own, dim3((unsigned)((P + 255) / 256), (unsigned)owns.size(), (unsigned)C), dim3(256), 0, e->stream, e->d_placeg_owns.get(), P, e->Pp,
-			                   e->d_tipsets.get());
-		}
-		HIP_TRY(hipMemcpyAsync(e->d_qopt_masks, rows.data(), rows.size(), hipMemcpyHostToDevice, e->stream));
-		HIP_TRY(hipMemcpyAsync(e->d_qoptg_cands, cands.data(), sizeof(ClassOptCand) * n, hipMemcpyHostToDevice, e->stream));
-		HIP_TRY(hipMemcpyAsync(e->d_qopt_start, start.data(), sizeof(double) * start.size(), hipMemcpyHostToDevice, e->stream));
-		ClassOptArgs s{};
-		s.cands = e->d_qoptg_cands, s.P = P, s.Pp = e->Pp, s.C = C, s.fold = e->upper_fold ? 1 : 0, s.set_count = g.set_count;
-		s.branches = o.branches, s.max_iterations = o.max_iterations, s.max_passes = o.max_passes;
-		s.lower = o.lower, s.upper = o.upper, s.tolerance = o.tolerance, s.lnl_tolerance = o.lnl_tolerance;
-		s.tipcode = e->d_tipmask, s.tipsets = e->d_tipsets, s.sets = e->d_placeg_sets, s.codes = e->d_qopt_masks;
-		s.freqs = e->d_freqs, s.props = e->d_props, s.model = e->d_model, s.rates = e->d_rates, s.weights = e->d_weights;
-		s.start = e->d_qopt_start, s.K = e->d_qopt_K, s.out = e->d_qopt_res, s.status = e->d_qopt_status;
-		hipLaunchKernelGGL(k_classopt_solve, dim3((unsigned)n), dim3(CLASSOPT_THREADS), 0, e->stream, s);
-		HIP_TRY(hipGetLastError());
-		out.resize(n * 5);
-		status.resize(n * QOPT_STATUS);
-		HIP_TRY(hipMemcpyAsync(out.data(), e->d_qopt_res, sizeof(double) * out.size(), hipMemcpyDeviceToHost, e->stream));
-		HIP_TRY(hipMemcpyAsync(status.data(), e->d_qopt_status, sizeof(int32_t) * status.size(), hipMemcpyDeviceToHost, e->stream));
-		HIP_TRY(hipStreamSynchronize(e->stream));  // (the next chunk writes the same arrays; also covers `sets` and the lists)
-		for (size_t i = 0; i < n; i++) {
-			const size_t to = (size_t)order[first + i];
-			const double *v = &out[i * 5];
-			std::copy(v, v + 3, o.lengths + to * 3);
-			o.lnl[to] = v[3];
-			if (o.initial_lnl) o.initial_lnl[to] = v[4];
-			if (o.passes) o.passes[to] = status[i * QOPT_STATUS + QOPT_PASSES];
-			prof.visits += status[i * QOPT_STATUS + QOPT_VISITS];
-			prof.iterations += status[i * QOPT_STATUS + QOPT_ITERATIONS];
-		}
-		prof.chunks++;
-	}
-	return PHYAMD_OK;
-}
-
-int shard_placement_optimize_general(Shard *e, int flags, const PlacementOptimizeGeneralArgs &g) {
-	CHECK_ENGINE(e);
-	phyamd_placement_optimize_profile start{};
-	start.candidates = g.p.count;
-	return profiled_call(e, &Shard::qopt_prof, start, [&](phyamd_placement_optimize_profile &prof) { return run_placement_optimize_general(e, flags, g, prof); });
 }
 
 // ---- per-pattern posteriors (phyamd_state_posteriors, phyamd_site_rate_posteriors) ---------------------------------------------

@@ -223,7 +223,8 @@ struct Shard {
 	DeviceArray<BatchOp> d_batch_item_ops{&batch_mem};  // [item][post-order T - 1 | pre-order T - 1]
 	DeviceArray<int32_t> d_batch_roots{&batch_mem};     // [item]
 	// what the scratch holds: every call describes what it needs as a ScratchPlan (phyamd_queries.inc: batch_plan, reweight_plan,
-	// nni_base_plan with nni_plan and cbopt_plan, blopt_plan, spr_plan with tripod_plan, pairdist_plan, place_plan, qopt_plan, bhess_plan, sitelnl_plan) and gets at least that, so a call of one kind
+	// nni_base_plan with nni_plan and cbopt_plan, blopt_plan, spr_plan with tripod_plan, pairdist_plan, bhess_plan, sitelnl_plan; phyamd_place_calls.inc: place_plan,
+	// place_gen_plan, qopt_plan, qopt_gen_plan) and gets at least that, so a call of one kind
 	// never runs in the scratch of another with too few upper slots or without its lists.  batch_held: the plan the arrays were last
 	// allocated by, for batch_items items (the Hessian's arrays, grown beside it, are judged by their sizes alone)
 	ScratchPlan batch_held;

@@ -12,7 +12,7 @@
 //   w:  K = w_c (V^T [(P(cu)^T (pi o U)) o (P(a) A)])_e (V^-1 B)_e
 //   p:  the same with A and B (a and b) exchanged
 // (no reversibility is used).  k_tripod_upper4 writes pi o U once per candidate; k_tripod_solve4 runs a candidate's whole rule
-// (include/physher_amd.h) in one workgroup: per visit two 4x4 matrices per category in LDS, K formed per pattern by the thread that
+// (include/physher_amd.h; its one body: three_branch_rule, phyamd_rule.inc) in one workgroup: per visit two 4x4 matrices per category in LDS, K formed per pattern by the thread that
 // reads it back, then the safeguarded Newton iteration on cbopt_evaluate's fixed-order sums, so every thread holds the same bits and
 // takes the same accept, bisect and stop decisions.  No walk, no matrix launch and no host round trip per visit; no floating-point
 // atomics.  A candidate's arithmetic depends on the engine's inputs, p and w alone.
@@ -54,7 +54,7 @@ __device__ __forceinline__ d4 tripod_matvec_t(const double *M, const d4 &v) {
 }
 
 enum { TRIPOD_P = 0, TRIPOD_W = 1, TRIPOD_U = 2 };                                     // the three branches, in `lengths`' order
-enum { TRIPOD_PASSES = 0, TRIPOD_VISITS = 1, TRIPOD_ITERATIONS = 2, TRIPOD_STATUS = 4 };  // a candidate's status words
+enum { TRIPOD_PASSES = RULE_PASSES, TRIPOD_VISITS = RULE_VISITS, TRIPOD_ITERATIONS = RULE_ITERATIONS, TRIPOD_STATUS = RULE_STATUS };  // a candidate's status words
 
 struct TripodSolveArgs {
 	const SprCand *cands;    // [gridDim.x]
@@ -134,9 +134,9 @@ __device__ __forceinline__ void tripod_coefficients(const TripodSolveArgs &a, co
 	// only after the barriers of the evaluations in between)
 }
 
-// grid (candidates of the chunk), block 256: one candidate's whole rule, every thread with the same bits.  One loop over the start
-// (slot -1: lnl_0 in the length of u, as it is given) and the visits, one over a visit's evaluations: tripod_coefficients and
-// cbopt_evaluate are expanded once each
+// grid (candidates of the chunk), block 256: one candidate's whole rule (three_branch_rule, phyamd_rule.inc: every slot is visited,
+// the start is lnl_0 in the length of u as it is given; tripod_coefficients and cbopt_evaluate are expanded once each), every thread
+// with the same bits
 __global__ __launch_bounds__(CBOPT_THREADS) void k_tripod_solve4(const TripodSolveArgs a) {
 	__shared__ double sh_e[3 * 4 * BATCH_MAX_CATEGORIES], sh_w[3 * CBOPT_WAVES], sh_m[2 * 16 * BATCH_MAX_CATEGORIES], sh_x[2 * 4 * BATCH_MAX_CATEGORIES], sh_v[32];
 	if (threadIdx.x < 32) sh_v[threadIdx.x] = a.model[4 + threadIdx.x];  // (the first barrier is tripod_coefficients')
@@ -157,67 +157,14 @@ __global__ __launch_bounds__(CBOPT_THREADS) void k_tripod_solve4(const TripodSol
 	cells.K = tripod_in_vgprs(a.K + cand * node_stride + tid);
 	double *const out = tripod_in_vgprs(a.out + cand * 5);
 	int32_t *const status = tripod_in_vgprs(a.status + cand * TRIPOD_STATUS);
-	double ta = a.lengths[cd.p], tb = 0.5 * a.lengths[cd.w], tu = tb;
-	double initial = 0.0, previous = 0.0, result = 0.0;
-	int passes = 0, visits = 0, iterations = 0;
-	int pass = 1, slot = -1;
-#pragma unroll 1
-	while (passes == 0) {
-		// u's left child, its right child, u: p keeps its slot, w has the one s had
-		const int z = slot < 0 || slot == 2 ? TRIPOD_U : (slot == 0) == (cd.p_left != 0) ? TRIPOD_P : TRIPOD_W;
-		tripod_coefficients(a, cells, z, ta, tb, tu, sh_m, sh_x, sh_v);
-		const double tz = z == TRIPOD_P ? ta : z == TRIPOD_W ? tb : tu;
-		const double t0 = slot < 0 ? tz : fmin(fmax(tz, a.lower), a.upper);
-		double t = t0, lo = a.lower, hi = a.upper, lnl = 0.0, lnl0 = 0.0, d1, d2;
-		int n = 0;
-		bool last = slot < 0, bad = false, wrong;  // last: the evaluation that ends the visit (the start has no other)
-#pragma unroll 1
-		for (;;) {
-			cbopt_evaluate(ev, K, t, n == 0 || last, sh_e, sh_w, &lnl, &d1, &d2, &wrong);
-			if (last) break;
-			if (n == 0) lnl0 = lnl;
-			n++;
-			if (wrong) {  // lnL is not finite at this iterate: it ends the candidate, with the value there
-				bad = true;
-				if (n == 1) break;
-				last = true;
-				continue;
-			}
-			if (d1 > 0.0) lo = t;
-			else hi = t;
-			double next = t - d1 / d2;
-			if (!(d2 < 0.0 && lo < next && next < hi)) next = 0.5 * (lo + hi);
-			last = fabs(next - t) <= a.tolerance || n == a.max_iterations;
-			t = next;
-		}
-		if (slot < 0) {
-			initial = previous = result = lnl;
-			slot = 0;
-			continue;
-		}
-		iterations += n;
-		if (bad) {
-			result = isnan(lnl) || isinf(lnl) ? lnl : NAN;
-			passes = -pass;
-			break;
-		}
-		const bool accept = !wrong && !(isnan(lnl) || isinf(lnl)) && lnl >= lnl0;
-		const double tn = accept ? t : t0;
-		result = accept ? lnl : lnl0;  // lnL at the length the visit leaves
-		if (z == TRIPOD_P) ta = tn;
-		else if (z == TRIPOD_W) tb = tn;
-		else tu = tn;
-		visits++;
-		if (++slot < 3) continue;
-		if (result - previous <= a.lnl_tolerance) passes = pass;  // the stop test
-		else if (pass == a.max_passes) passes = -a.max_passes;
-		previous = result;
-		slot = 0, pass++;
-	}
-	if (threadIdx.x == 0) {
-		out[0] = ta, out[1] = tb, out[2] = tu, out[3] = result, out[4] = initial;
-		status[TRIPOD_PASSES] = passes, status[TRIPOD_VISITS] = visits, status[TRIPOD_ITERATIONS] = iterations;
-	}
+	const double tw = 0.5 * a.lengths[cd.w];
+	const bool p_first = cd.p_left != 0;
+	three_branch_rule<true>(
+	    [&](int z, double ta, double tb, double tu) { tripod_coefficients(a, cells, z, ta, tb, tu, sh_m, sh_x, sh_v); },
+	    [&](double t, bool final, double *lnl, double *d1, double *d2, bool *bad) { cbopt_evaluate(ev, K, t, final, sh_e, sh_w, lnl, d1, d2, bad); },
+	    // u's left child, its right child, u: p keeps its slot, w has the one s had
+	    [p_first](int slot) { return slot == 2 ? TRIPOD_U : (slot == 0) == p_first ? TRIPOD_P : TRIPOD_W; }, 7, a.lengths[cd.p], tw, tw, a.lower, a.upper, a.tolerance,
+	    a.max_iterations, a.lnl_tolerance, a.max_passes, out, status);
 }
 
 // results [rows][N][5] and counts [rows][N][3] (passes, visits, iterations): a candidate's in its cell, NaN and 0 in every other
