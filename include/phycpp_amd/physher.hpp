@@ -311,6 +311,10 @@ class TreeLikelihoodInterface : public CallableModelInterface {
 	// evaluation hands it: the tree model's lengths, with a clock rate or mu folded in).  d1 and d2 may be null.  The tree model
 	// and this object's own state are unchanged.
 	void NNILogLikelihoods(const double *centralLengths, double *logLikelihoods, double *d1, double *d2);
+	// The same for a model of 20 states (one phyamd_nni_log_likelihoods_general call; see include/physher_amd.h): the arrays are
+	// NNILogLikelihoods'.  The call reads the engine's resident partials, which it makes resident if they are not; the tree model
+	// and this object's own state are unchanged.
+	void NNILogLikelihoodsGeneral(const double *centralLengths, double *logLikelihoods, double *d1, double *d2);
 	// The central branch of every NNI neighbour of the tree model's tree optimised at once (one phyamd_nni_optimize call; see
 	// include/physher_amd.h for the rule): lengths, logLikelihoods, d1, d2 and iterations [3][2T-1] by the tree's node ids, in
 	// NNILogLikelihoods' rows and columns (NaN, iterations 0, at tips and the root); startLengths [3][2T-1], or null for the

@@ -1052,6 +1052,48 @@ int phyamd_placement_optimize_general(phyamd_engine *e, int flags, int32_t queri
                                       double *lengths /* [count][3]: distal, pendant, proximal */, double *lnl /* [count] */,
                                       double *initial_lnl /* [count] or NULL */, int32_t *passes /* [count] or NULL */);
 
+/* --- every NNI neighbour of the engine's tree, 20 states --- */
+/* phyamd_nni_log_likelihoods for an engine of 20 states (proteins): lnL, and its first and second derivative in the central
+ * branch, of every NNI neighbour of the engine's tree in one call -- O(T) work for the whole neighbourhood, where the loop it
+ * replaces (phyamd_set_topology + phyamd_set_branch_length + phyamd_branch_hessian_diagonal on a second engine) walks the tree
+ * twice from the tips per entry.
+ * THE DEFINITION, in full (it is phyamd_nni_log_likelihoods', word for word).  A CANDIDATE is every internal node v other than the
+ * root; u its parent, s its sibling, a = left[v], b = right[v].  Every subtree keeps its own branch length; the length of v is
+ * central_lengths[k][v], or the engine's t_v when central_lengths is NULL.  Row k of lnl, d1, d2 ([3][2T-1] each) at column v:
+ *   k = 0  the engine's tree
+ *   k = 1  a and s exchanged: v gets children (s, b), u gets a where s was
+ *   k = 2  b and s exchanged: v gets children (a, s), u gets b where s was
+ * Entry (k, v) is what the engine itself returns for the rearranged tree with t_v set to the trial length: lnl[k][v] is
+ * phyamd_log_likelihood, d1[k][v] and d2[k][v] are rows v of phyamd_branch_hessian_diagonal's first and second derivative.  (The
+ * central branch's transition matrix enters as V e^(lambda t r_c) V^-1 without the reference's elementwise |.|: a rounding
+ * difference, as in phyamd_nni_optimize.)  A trial length of 0 is legal.  Columns of tips and of the root are NaN in all three
+ * outputs (two tips: everything is NaN); entries of central_lengths at those columns are ignored.  d1 and d2 may be NULL (both NULL:
+ * their sums are skipped; the lnl bits are the same).  When u is the root, k = 1 and k = 2 are, for a reversible model, the same
+ * unrooted topology with the lengths of a, b and s redistributed; they are computed like every other entry.  An entry whose lnL
+ * is not finite (some pattern's site likelihood is not in (0, inf): underflow, the call does not rescale) reports it in band with
+ * NaN d1 and d2.
+ * The tree side is read from resident partials, exactly as in phyamd_placement_log_likelihoods_general: THE ENGINE IS AFTERWARDS ONE
+ * WITH phyamd_set_keep_partials(1) THAT HAS RUN THE FLAGS-0 GRADIENT; its topology, lengths and models are unchanged, and later
+ * evaluations return the bits such an engine returns without the call.  Upper partials that a PHYAMD_GRAD_FOLD_ROOT_FREQS
+ * keep-partials gradient left resident are used as they are (pi is inside them).  The three arrangements round an edge differ in
+ * four messages only, and all four are resident: a stored lower partial is the message P_x p_x itself (a tip: a column, the row sums
+ * or a set's columns of its branch matrix), and the parent's is P_u times the upper partial at the top of u's branch (ones at the
+ * root).  With F = pi o A_u o m_o and p = m_x o m_y for (o; x, y) = (s; a, b), (a; s, b), (b; a, s) the site likelihood in the central
+ * length t is sum_c sum_e K[c][e] exp(lambda_e r_c t), K[c][e] = w_c (V^T F)_e (V^-1 p)_e, so nothing is walked, no trial matrix is
+ * formed and the derivatives cost no further product: seven 20-wide products on the fp64 matrix cores per (candidate, category,
+ * 16 patterns).  Two calls return identical bits; an entry's bits depend on the engine's inputs and on its own trial length alone
+ * -- not on the other entries' lengths, the optional outputs or what the batch scratch held.  Nothing is added with atomics: sums
+ * over patterns are formed over blocks of 128 patterns and added in block order.  The engine is never switched to rescaling by the
+ * call's own kernels.  The scratch is the batch scratch's: 64 bytes and nine doubles per block per candidate.
+ * PHYAMD_EINVAL: null engine or lnl (checked before the handle's state is looked at), no eigen system, a negative or non-finite
+ * trial length of a candidate (named), an engine that is not ready to evaluate.  There is no fallback path: PHYAMD_EUNSUPPORTED,
+ * naming the function and the condition: a state count other than 20 (4: use phyamd_nni_log_likelihoods; 60 / 61: not built),
+ * more than 8 categories, flags other than 0, tiled patterns, explicit node matrices, an engine that is rescaling -- also when
+ * PHYAMD_RESCALE_AUTO switched it on during the call's own evaluation --, a handle sharded over several devices, scratch that does
+ * not fit the memory cap.  phyamd_get_nni_profile reports the last call of either kind. */
+int phyamd_nni_log_likelihoods_general(phyamd_engine *e, int flags, const double *central_lengths /* [3][2T-1] or NULL */,
+                                       double *lnl /* [3][2T-1] */, double *d1 /* [3][2T-1] or NULL */, double *d2 /* [3][2T-1] or NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -146,6 +146,7 @@ SYMBOLS = [
     ("phyamd_gradient_batch_trees", C.c_int, [_P, C.c_int, C.c_int32, _P, _P, _P, _P, _P, _P]),
     ("phyamd_get_batch_profile", C.c_int, [_P, C.POINTER(BatchProfile)]),
     ("phyamd_nni_log_likelihoods", C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
+    ("phyamd_nni_log_likelihoods_general", C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
     ("phyamd_get_nni_profile", C.c_int, [_P, C.POINTER(NniProfile)]),
     ("phyamd_nni_optimize", C.c_int, [_P, C.c_int, _P, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P, _P, _P, _P]),
     ("phyamd_get_nni_optimize_profile", C.c_int, [_P, C.POINTER(NniOptimizeProfile)]),

@@ -940,6 +940,12 @@ void TreeLikelihoodInterface::NNILogLikelihoods(const double *centralLengths, do
 	phyamd::check(phyamd_nni_log_likelihoods(impl_->engine, 0, centralLengths, logLikelihoods, d1, d2));
 }
 
+void TreeLikelihoodInterface::NNILogLikelihoodsGeneral(const double *centralLengths, double *logLikelihoods, double *d1, double *d2) {
+	if (!logLikelihoods) throw Error("null logLikelihoods");
+	Sync();
+	phyamd::check(phyamd_nni_log_likelihoods_general(impl_->engine, 0, centralLengths, logLikelihoods, d1, d2));
+}
+
 void TreeLikelihoodInterface::NNIOptimize(const double *startLengths, double lower, double upper, double tolerance, int maxIterations, double *lengths,
                                           double *logLikelihoods, double *d1, double *d2, int32_t *iterations) {
 	if (!lengths || !logLikelihoods) throw Error("null lengths or logLikelihoods");

@@ -264,6 +264,15 @@ PYBIND11_MODULE(_phycpp_amd, m) {
 		    if (!want_derivatives) return py::make_tuple(darray(shape, lnl.data()), py::none(), py::none());
 		    return py::make_tuple(darray(shape, lnl.data()), darray(shape, d1.data()), darray(shape, d2.data()));
 	    }, py::arg("central_lengths") = py::none(), py::arg("want_derivatives") = true)
+	    .def("nni_log_likelihoods_general", [](TreeLikelihoodInterface &self, std::optional<darray> central, bool want_derivatives) -> py::tuple {
+		    const py::ssize_t N = (py::ssize_t)self.NodeCount();
+		    if (central && (central->ndim() != 2 || central->shape(0) != 3 || central->shape(1) != N)) throw phyamd::Error("central lengths: [3][node_count]");
+		    std::vector<double> lnl((size_t)3 * N), d1(want_derivatives ? lnl.size() : 0), d2(d1.size());
+		    self.NNILogLikelihoodsGeneral(central ? central->data() : nullptr, lnl.data(), want_derivatives ? d1.data() : nullptr, want_derivatives ? d2.data() : nullptr);
+		    const std::vector<py::ssize_t> shape{3, N};
+		    if (!want_derivatives) return py::make_tuple(darray(shape, lnl.data()), py::none(), py::none());
+		    return py::make_tuple(darray(shape, lnl.data()), darray(shape, d1.data()), darray(shape, d2.data()));
+	    }, py::arg("central_lengths") = py::none(), py::arg("want_derivatives") = true)
 	    .def("nni_optimize", [](TreeLikelihoodInterface &self, std::optional<darray> start, double lower, double upper, double tolerance, int max_iterations) -> py::tuple {
 		    const py::ssize_t N = (py::ssize_t)self.NodeCount();
 		    if (start && (start->ndim() != 2 || start->shape(0) != 3 || start->shape(1) != N)) throw phyamd::Error("start lengths: [3][node_count]");

@@ -601,6 +601,20 @@ int phyamd_nni_log_likelihoods(phyamd_engine *g, int flags, const double *centra
 	return PHYAMD_OK;
 }
 
+// the same for 20 states, from the resident partials; one device only, like the other 20-state query calls
+int phyamd_nni_log_likelihoods_general(phyamd_engine *g, int flags, const double *central_lengths, double *lnl, double *d1, double *d2) {
+	static const char *const name = "phyamd_nni_log_likelihoods_general";
+	if (!lnl) return fail(PHYAMD_EINVAL, "%s: null lnl", name);
+	if (!g || g->shards.empty()) return fail(PHYAMD_EINVAL, "%s: null engine", name);
+	if (group_size(g) > 1)
+		return fail(PHYAMD_EUNSUPPORTED, "%s: a handle sharded over several devices is out of scope: the call reads one engine's resident partials (use one device)", name);
+	const size_t entries = (size_t)3 * g->N;  // [lnl | d1 | d2], each [3][2T-1]
+	std::vector<double> out(3 * entries);
+	if (int rc = shard_nni_general(g->shards[0], flags, central_lengths, d1 || d2, out.data())) return rc;
+	unpack(out.data(), {{lnl, entries}, {d1, entries}, {d2, entries}});
+	return PHYAMD_OK;
+}
+
 int phyamd_get_nni_profile(phyamd_engine *g, phyamd_nni_profile *out) {
 	// the slowest shard is what the caller waits for; memory adds up
 	return merged_profile(g, &Shard::nni_prof, out, [](phyamd_nni_profile &o, const phyamd_nni_profile &p) {

@@ -119,6 +119,7 @@ constexpr double SCALING_THRESHOLD = 1.0e-40;  // treelikelihood.c:1121
 #include "phyamd_pairdist_gen.inc"
 #include "phyamd_place4.inc"
 #include "phyamd_place_gen.inc"
+#include "phyamd_nni_gen.inc"
 #include "phyamd_qopt4.inc"
 #include "phyamd_qopt_gen.inc"
 

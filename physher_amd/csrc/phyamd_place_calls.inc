@@ -1,8 +1,8 @@
 // phyamd_place_calls.inc -- the placement calls on one shard: query sequences scored on every edge of the engine's tree and the three
 // branches around chosen placements optimised, for 4 and for 20 states.  What a 4-state call and its 20-state twin share is written
 // once -- the chunk sizes and the loop over node columns x query chunks (place_chunk_sizes, run_place_chunks), the sorted
-// candidates, their chunks and the scatter of their results (sort_candidates, qopt_chunk_size, run_qopt_chunks), the preconditions
-// and the own-partial records of the 20-state calls (check_general_placement, place_own_of) -- and a call keeps what is its own:
+// candidates, their chunks and the scatter of their results (sort_candidates, qopt_chunk_size, run_qopt_chunks), the wording of the
+// preconditions and the own-partial records of the 20-state calls (general_placement_call, place_own_of) -- and a call keeps what is its own:
 // its scratch plan, what it prepares once, its tables or records and its kernels.  They read what the engine holds and write only
 // the batch scratch (part of phyamd_engine.hip: one translation unit, internal linkage; behind phyamd_queries.inc, whose scratch
 // plans, NNI walk and profiled_call these use)
@@ -62,32 +62,10 @@ size_t largest_that(size_t lo, size_t hi, Ok ok) {
 	return lo;
 }
 
-// The preconditions of the two 20-state calls, in two halves (phyamd_placement_optimize_general checks its candidates in between).
-// The first reads the engine's inputs; the second makes every partial resident (require_resident_partials: the engine is afterwards
-// a keep-partials engine that has run the flags-0 gradient).  use_4_state_call: the call an engine of 4 states is sent to;
-// eigen_use: what "is formed from" the eigen system; what_does_not_rescale: "tables do" or "solve does"
-int check_general_placement_inputs(Shard *e, const char *name, int flags, const char *use_4_state_call, const char *eigen_use) {
-	if (e->S == 4) return fail(PHYAMD_EUNSUPPORTED, "%s: the class tables are built for 20 states (the engine has 4: use %s)", name, use_4_state_call);
-	if (e->S != PLACE_GEN_STATES) return fail(PHYAMD_EUNSUPPORTED, "%s: the class tables are built for 20 states (the engine has %d: tables of 64 classes are not built)", name, e->S);
-	if (e->C > BATCH_MAX_CATEGORIES) return fail(PHYAMD_EUNSUPPORTED, "%s: %d rate categories (at most %d categories)", name, e->C, BATCH_MAX_CATEGORIES);
-	if (flags != 0) return fail(PHYAMD_EUNSUPPORTED, "%s: flags %d (no flags are defined: pass 0)", name, flags);
-	if (e->tiles > 1) return fail(PHYAMD_EUNSUPPORTED, "%s: the patterns are tiled and the call needs every partial of all patterns resident", name);
-	if (std::any_of(e->explicit_host.begin(), e->explicit_host.end(), [](uint8_t x) { return x != 0; }))
-		return fail(PHYAMD_EUNSUPPORTED, "%s: a node has explicit matrices, which cannot be split at sigma", name);
-	if (!e->have_eigen) return fail(PHYAMD_EINVAL, "%s needs the eigen system (phyamd_set_eigen): %s formed from it", name, eigen_use);
-	return check_ready(e);
-}
-int check_general_placement_resident(Shard *e, const char *name, const char *what_does_not_rescale) {
-	static const char *const rescaling = "%s: the engine is rescaling%s and the %s not rescale (underflow is otherwise -inf in band)";
-	if (e->scaling_on) return fail(PHYAMD_EUNSUPPORTED, rescaling, name, "", what_does_not_rescale);
-	if (int rc = require_resident_partials(e, name)) return rc;
-	if (e->scaling_on) return fail(PHYAMD_EUNSUPPORTED, rescaling, name, " (PHYAMD_RESCALE_AUTO switched it on during the call's own evaluation)", what_does_not_rescale);
-	if (e->tiles > 1) return fail(PHYAMD_EUNSUPPORTED, "%s: the patterns are tiled and the call needs every partial of all patterns resident", name);
-	return PHYAMD_OK;
-}
-int check_general_placement(Shard *e, const char *name, int flags, const char *use_4_state_call, const char *eigen_use, const char *what_does_not_rescale) {
-	if (int rc = check_general_placement_inputs(e, name, flags, use_4_state_call, eigen_use)) return rc;
-	return check_general_placement_resident(e, name, what_does_not_rescale);
+// (the preconditions of the two 20-state calls: check_general_query_inputs / _resident, phyamd_queries.inc, which
+// phyamd_placement_optimize_general runs in two halves with its candidates checked in between)
+GeneralQueryCall general_placement_call(const char *name, const char *use_4_state_call, const char *eigen_use, const char *what_does_not_rescale) {
+	return GeneralQueryCall{name, "the class tables are", use_4_state_call, "tables of 64 classes are", "which cannot be split at sigma", eigen_use, what_does_not_rescale};
 }
 
 // What k_classplace_own forms internal node `node`'s own partial from, into `out`: a stored array is the message P_n p_n, so the
@@ -333,7 +311,8 @@ int run_placement_general(Shard *e, int flags, const PlacementGeneralArgs &g, ph
 	static const char *const name = "phyamd_placement_log_likelihoods_general";
 	const PlacementArgs &o = g.p;
 	int rc;
-	if ((rc = check_general_placement(e, name, flags, "phyamd_placement_log_likelihoods", "the split and pendant matrices are", "tables do"))) return rc;
+	const GeneralQueryCall call = general_placement_call(name, "phyamd_placement_log_likelihoods", "the split and pendant matrices are", "tables do");
+	if ((rc = check_general_query_inputs(e, call, flags)) || (rc = check_general_query_resident(e, call))) return rc;
 	const int T = e->T, N = e->N, C = e->C, P = e->P, root = e->root;
 	const size_t Q = (size_t)o.queries, L = (size_t)o.lengths, groups_l = (L + PLACE_GEN_LENGTHS - 1) / PLACE_GEN_LENGTHS;
 	const PlaceKind kind{(P + PLACE_GEN_BLOCK - 1) / PLACE_GEN_BLOCK * PLACE_GEN_BLOCK, k_classplace_codes, k_classplace_score,
@@ -605,9 +584,10 @@ int run_placement_optimize_general(Shard *e, int flags, const PlacementOptimizeG
 	static const char *const name = "phyamd_placement_optimize_general";
 	const PlacementOptimizeArgs &o = g.p;
 	int rc;
-	if ((rc = check_general_placement_inputs(e, name, flags, "phyamd_placement_optimize", "the likelihood in a branch length is"))) return rc;
+	const GeneralQueryCall call = general_placement_call(name, "phyamd_placement_optimize", "the likelihood in a branch length is", "solve does");
+	if ((rc = check_general_query_inputs(e, call, flags))) return rc;
 	if ((rc = check_candidates_off_root(name, o, e->root))) return rc;
-	if ((rc = check_general_placement_resident(e, name, "solve does"))) return rc;
+	if ((rc = check_general_query_resident(e, call))) return rc;
 	const int T = e->T, C = e->C, P = e->P;
 	const size_t npd = node_partial_doubles(e);
 	const std::vector<int32_t> order = sort_candidates(o, prof);

@@ -33,6 +33,41 @@ int require_resident_partials(Shard *e, const char *call) {
 	return PHYAMD_OK;
 }
 
+// The preconditions of the 20-state calls that read the resident partials (the two placement calls, phyamd_place_calls.inc, and
+// phyamd_nni_log_likelihoods_general), in two halves: a call may check its own arguments against the engine in between.  The first
+// reads the engine's inputs; the second makes every partial resident (require_resident_partials: the engine is afterwards a
+// keep-partials engine that has run the flags-0 gradient).  A call words what is its own
+struct GeneralQueryCall {
+	const char *name;
+	const char *built;                  // what "is / are" built for 20 states only
+	const char *use_4_state_call;       // the call an engine of 4 states is sent to
+	const char *not_built;              // what 60 / 61 states would need and "is / are" not built
+	const char *explicit_why;           // why explicit node matrices are refused: "which ..."
+	const char *eigen_use;              // what "is / are" formed from the eigen system
+	const char *what_does_not_rescale;  // "tables do", "solve does"
+};
+int check_general_query_inputs(Shard *e, const GeneralQueryCall &call, int flags) {
+	const char *name = call.name;
+	if (e->S == 4) return fail(PHYAMD_EUNSUPPORTED, "%s: %s built for 20 states (the engine has 4: use %s)", name, call.built, call.use_4_state_call);
+	if (e->S != PLACE_GEN_STATES) return fail(PHYAMD_EUNSUPPORTED, "%s: %s built for 20 states (the engine has %d: %s not built)", name, call.built, e->S, call.not_built);
+	if (e->C > BATCH_MAX_CATEGORIES) return fail(PHYAMD_EUNSUPPORTED, "%s: %d rate categories (at most %d categories)", name, e->C, BATCH_MAX_CATEGORIES);
+	if (flags != 0) return fail(PHYAMD_EUNSUPPORTED, "%s: flags %d (no flags are defined: pass 0)", name, flags);
+	if (e->tiles > 1) return fail(PHYAMD_EUNSUPPORTED, "%s: the patterns are tiled and the call needs every partial of all patterns resident", name);
+	if (std::any_of(e->explicit_host.begin(), e->explicit_host.end(), [](uint8_t x) { return x != 0; }))
+		return fail(PHYAMD_EUNSUPPORTED, "%s: a node has explicit matrices, %s", name, call.explicit_why);
+	if (!e->have_eigen) return fail(PHYAMD_EINVAL, "%s needs the eigen system (phyamd_set_eigen): %s formed from it", name, call.eigen_use);
+	return check_ready(e);
+}
+int check_general_query_resident(Shard *e, const GeneralQueryCall &call) {
+	static const char *const rescaling = "%s: the engine is rescaling%s and the %s not rescale (underflow is otherwise -inf in band)";
+	if (e->scaling_on) return fail(PHYAMD_EUNSUPPORTED, rescaling, call.name, "", call.what_does_not_rescale);
+	if (int rc = require_resident_partials(e, call.name)) return rc;
+	if (e->scaling_on)
+		return fail(PHYAMD_EUNSUPPORTED, rescaling, call.name, " (PHYAMD_RESCALE_AUTO switched it on during the call's own evaluation)", call.what_does_not_rescale);
+	if (e->tiles > 1) return fail(PHYAMD_EUNSUPPORTED, "%s: the patterns are tiled and the call needs every partial of all patterns resident", call.name);
+	return PHYAMD_OK;
+}
+
 // transition matrices of `items` branch-length vectors [items][N] on the device -> mats [items][N][C][16]; roots: per item, or null:
 // the engine's
 void launch_batch_matrices(Shard *e, int items, const double *lengths, const int32_t *roots, double *mats) {
@@ -678,6 +713,94 @@ int shard_nni_log_likelihoods(Shard *e, int flags, const double *central_lengths
 	CHECK_ENGINE(e);
 	return profiled_call(e, &Shard::nni_prof, phyamd_nni_profile{}, [&](phyamd_nni_profile &prof) {
 		const int rc = run_nni(e, flags, central_lengths, deriv, out, prof);
+		if (!rc) nni_mask_derivatives((size_t)3 * e->N, out);
+		return rc;
+	});
+}
+
+// ---- every NNI neighbour of a 20-state engine's tree (phyamd_nni_log_likelihoods_general) ---------------------------------------
+
+// nothing is walked and nothing scales with an item count: the candidates and their index by node, the caller's [3][N] lengths, the
+// images of V^T and V^-1, the slab (blocks of CLASSNNI_BLOCK patterns) and the result
+ScratchPlan nni_gen_plan(Shard *e, size_t nblk) {
+	const size_t D = sizeof(double), N = (size_t)e->N, cands = std::max<size_t>(nni_candidates(e), 1);
+	ScratchPlan p;
+	p.add(e->d_nnig_cands, 0, sizeof(ClassNniCand) * cands);
+	p.add(e->d_nnig_eig, 0, D * 2 * MatImage<2, 5>::SIZE);
+	p.add(e->d_nni_cand_of, 0, sizeof(int32_t) * N);
+	p.add(e->d_nni_len, 0, D * 3 * N);
+	p.add(e->d_nni_slab, 0, D * cands * nblk * 9);
+	p.add(e->d_nni_out, 0, D * 9 * N);
+	return p;
+}
+
+// out [3 terms][3][N] (host): the four messages round every candidate edge read from the resident partials, every edge's three
+// arrangements in one launch.  Writes only the batch scratch beyond the evaluation that made the partials resident
+int run_nni_general(Shard *e, int flags, const double *central_lengths, bool deriv, double *out, phyamd_nni_profile &prof) {
+	static const GeneralQueryCall call{"phyamd_nni_log_likelihoods_general", "the kernel is", "phyamd_nni_log_likelihoods", "64-wide products are",
+	                                   "which have no exponential sum in the central length", "the likelihood in the central length is", "coefficients do"};
+	int rc;
+	if ((rc = check_general_query_inputs(e, call, flags))) return rc;
+	const int T = e->T, N = e->N, C = e->C, P = e->P, root = e->root;
+	std::vector<double> trial((size_t)3 * N);  // a candidate's own three where the caller gives them, every other entry the engine's (not read)
+	for (int k = 0; k < 3; k++) std::copy(e->lengths.begin(), e->lengths.end(), trial.begin() + (size_t)k * N);
+	for (int v = T; v < N && central_lengths; v++) {
+		if (v == root) continue;
+		for (int k = 0; k < 3; k++) {
+			const double t = central_lengths[(size_t)k * N + v];
+			if (!std::isfinite(t) || t < 0.0) return fail(PHYAMD_EINVAL, "%s: central_lengths[%d][%d] = %g: a trial length is finite and not negative", call.name, k, v, t);
+			trial[(size_t)k * N + v] = t;
+		}
+	}
+	if ((rc = check_general_query_resident(e, call))) return rc;
+	const size_t cands = nni_candidates(e), npd = node_partial_doubles(e), image = MatImage<2, 5>::SIZE;
+	prof.candidates = (int32_t)cands;
+	std::fill(out, out + (size_t)9 * N, NAN);
+	if (cands == 0) return PHYAMD_OK;  // two tips: no internal edge
+	const int nblk = (P + CLASSNNI_BLOCK - 1) / CLASSNNI_BLOCK;
+	const ScratchPlan plan = nni_gen_plan(e, (size_t)nblk);
+	if (batch_items_that_fit(e, 1, plan) < 1)
+		return fail(PHYAMD_EUNSUPPORTED, "%s: the scratch (%zu bytes: the candidates, the slab and the result) does not fit the memory budget", call.name,
+		            plan.item_bytes() + plan.fixed_bytes());
+	if ((rc = ensure_batch_scratch(e, 1, plan))) return rc;
+	const auto lower_of = [&](int n) { return n < T ? (const double *)nullptr : e->d_lower + (size_t)e->sched.core_index[n] * npd; };
+	std::vector<ClassNniCand> records;
+	std::vector<int32_t> cand_of(N, -1);
+	for (int v = T; v < N; v++) {
+		if (v == root) continue;
+		const int u = e->sched.parent[v], s = e->left[u] == v ? e->right[u] : e->left[u], a = e->left[v], b = e->right[v];
+		for (const int n : {a, b, s})
+			if (n >= T && e->sched.core_index[n] < 0) return fail(PHYAMD_EDEVICE, "%s: node %d has no resident lower partial", call.name, n);
+		if (u != root && (e->sched.upper_slot[u] < 0 || !e->d_upper)) return fail(PHYAMD_EDEVICE, "%s: node %d has no resident upper partial", call.name, u);
+		cand_of[v] = (int32_t)records.size();
+		records.push_back(ClassNniCand{u == root ? nullptr : e->d_upper + (size_t)e->sched.upper_slot[u] * npd, lower_of(a), lower_of(b), lower_of(s), v, u, a, b, s, {0, 0, 0}});
+	}
+	e->nni_lists_valid = false;  // (d_nni_cand_of holds this call's index, which is the 4-state lists' too, but their ops and candidates are not here)
+	HIP_TRY(hipMemcpyAsync(e->d_nnig_cands, records.data(), sizeof(ClassNniCand) * records.size(), hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipMemcpyAsync(e->d_nni_cand_of, cand_of.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipMemcpyAsync(e->d_nni_len, trial.data(), sizeof(double) * trial.size(), hipMemcpyHostToDevice, e->stream));
+	const double *evec = e->d_model.get() + PLACE_GEN_STATES, *ivec = evec + PLACE_GEN_STATES * PLACE_GEN_STATES;  // d_model: eval [20] | evec [20][20] | ivec [20][20]
+	hipLaunchKernelGGL(k_classplace_transposed_images, dim3(1), dim3(256), 0, e->stream, evec, e->d_nnig_eig.get());
+	build_matrix_images(e, 1, ivec, e->d_nnig_eig.get() + image);
+	for (size_t first = 0; first < cands; first += BATCH_MAX_CHUNK) {  // (gridDim.y)
+		const size_t n = std::min<size_t>(cands - first, BATCH_MAX_CHUNK);
+		const ClassNniArgs a{e->d_nnig_cands.get() + first, N, P, e->Pp, C, e->upper_fold ? 1 : 0, deriv ? 1 : 0, e->d_tipmask, e->d_tipsets, e->d_freqs, e->d_props, e->d_rates,
+		                     e->d_weights, e->d_model, e->d_imgs, e->d_nnig_eig, e->d_nni_len, e->d_nni_slab + first * nblk * 9};
+		hipLaunchKernelGGL(k_classnni, dim3((unsigned)nblk, (unsigned)n), dim3(GenGeo<2>::WAVES * 64), 0, e->stream, a);
+	}
+	hipLaunchKernelGGL(k_nni_finish, dim3((unsigned)(((size_t)9 * N + 255) / 256)), dim3(256), 0, e->stream, N, nblk, e->d_nni_cand_of.get(), e->d_nni_slab.get(),
+	                   e->d_nni_out.get());
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(out, e->d_nni_out, sizeof(double) * (size_t)9 * N, hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));  // (also covers the records, the index and `trial`)
+	return PHYAMD_OK;
+}
+
+// out [3 terms][3][N] on the host; deriv: d1 and d2 as well (else those rows are NaN at tips and the root, 0 elsewhere)
+int shard_nni_general(Shard *e, int flags, const double *central_lengths, bool deriv, double *out) {
+	CHECK_ENGINE(e);
+	return profiled_call(e, &Shard::nni_prof, phyamd_nni_profile{}, [&](phyamd_nni_profile &prof) {
+		const int rc = run_nni_general(e, flags, central_lengths, deriv, out, prof);
 		if (!rc) nni_mask_derivatives((size_t)3 * e->N, out);
 		return rc;
 	});

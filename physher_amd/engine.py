@@ -264,8 +264,27 @@ class Engine:
                                                          None if d1 is None else _ptr(d1), None if d2 is None else _ptr(d2)))
         return lnl, d1, d2
 
+    def nni_log_likelihoods_general(self, central_lengths=None, want_derivatives=True, flags=0):
+        """nni_log_likelihoods for an engine of 20 states: (lnl, d1, d2), each [3, N], in that method's rows and columns and by its
+        definition -- entry (k, v) is this engine's own log_likelihood and rows v of branch_hessian_diagonal on the rearranged tree
+        with the length of v set to central_lengths[k, v] (None: its own).  The four messages round every edge are read from the
+        resident partials: afterwards the engine is one with set_keep_partials(True) that has run gradient(); its tree, lengths and
+        models stay.  An entry whose lnL is not finite has NaN d1 and d2.  No fallback: EngineError for a state count other than 20,
+        more than 8 categories, flags, tiled patterns, explicit matrices, a rescaling or a sharded engine."""
+        cl = None
+        if central_lengths is not None:
+            cl = _f64(central_lengths)
+            if cl.shape != (3, self.N):
+                raise ValueError(f"central_lengths must be [3, {self.N}] (got {cl.shape})")
+        lnl = np.empty((3, self.N))
+        d1 = np.empty((3, self.N)) if want_derivatives else None
+        d2 = np.empty((3, self.N)) if want_derivatives else None
+        self._check(self._lib.phyamd_nni_log_likelihoods_general(self._h, flags, None if cl is None else _ptr(cl), _ptr(lnl),
+                                                                 None if d1 is None else _ptr(d1), None if d2 is None else _ptr(d2)))
+        return lnl, d1, d2
+
     def nni_profile(self):
-        """Of the last nni_log_likelihoods: candidates (edges scored), scratch_bytes, ms."""
+        """Of the last nni_log_likelihoods or nni_log_likelihoods_general: candidates (edges scored), scratch_bytes, ms."""
         p = _lib.NniProfile()
         self._check(self._lib.phyamd_get_nni_profile(self._h, C.byref(p)))
         return {k: getattr(p, k) for k, _ in p._fields_}
