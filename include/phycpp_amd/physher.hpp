@@ -324,6 +324,11 @@ class TreeLikelihoodInterface : public CallableModelInterface {
 	// model and this object's own state are unchanged.
 	void NNIOptimize(const double *startLengths, double lower, double upper, double tolerance, int maxIterations, double *lengths, double *logLikelihoods, double *d1,
 	                 double *d2, int32_t *iterations);
+	// The same for a model of 20 states (one phyamd_nni_optimize_general call; see include/physher_amd.h): the arguments and arrays
+	// are NNIOptimize's.  The call reads the engine's resident partials, which it makes resident if they are not; the tree model
+	// and this object's own state are unchanged.
+	void NNIOptimizeGeneral(const double *startLengths, double lower, double upper, double tolerance, int maxIterations, double *lengths, double *logLikelihoods,
+	                        double *d1, double *d2, int32_t *iterations);
 	// Every branch length of `count` TREES optimised on the device, one branch at a time, pass after pass (one
 	// phyamd_optimize_branch_lengths call; see include/physher_amd.h for the rule): left, right, roots and branchLengths are
 	// LogLikelihoodTrees' arrays, branchLengths the start; optimise [count][2T-1] marks the nodes whose branches are visited, or null:

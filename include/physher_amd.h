@@ -1093,6 +1093,55 @@ int phyamd_placement_optimize_general(phyamd_engine *e, int flags, int32_t queri
  * not fit the memory cap.  phyamd_get_nni_profile reports the last call of either kind. */
 int phyamd_nni_log_likelihoods_general(phyamd_engine *e, int flags, const double *central_lengths /* [3][2T-1] or NULL */,
                                        double *lnl /* [3][2T-1] */, double *d1 /* [3][2T-1] or NULL */, double *d2 /* [3][2T-1] or NULL */);
+/* phyamd_nni_optimize for an engine of 20 states (proteins): the central branch of every NNI neighbour of the engine's tree
+ * optimised in one call.  A tree search judges an NNI move at its best central length, not at the old one; the routes this replaces
+ * are one phyamd_nni_log_likelihoods_general call per Newton round with the rule on the host, or a second engine looped over all
+ * 3 (T - 2) entries.
+ * THE DEFINITION, in full (it is phyamd_nni_optimize's, word for word).  A CANDIDATE is every internal node v other than the root; u
+ * its parent, s its sibling, a = left[v], b = right[v].  Every subtree keeps its own branch length.  Row k of every output
+ * ([3][2T-1] each) at column v:
+ *   k = 0  the engine's tree
+ *   k = 1  a and s exchanged: v gets children (s, b), u gets a where s was
+ *   k = 2  b and s exchanged: v gets children (a, s), u gets b where s was
+ * and entry (k, v) is the length of v in [lower, upper] that maximises the lnL of that tree, found by THE RULE: t = clamp(start,
+ * lower, upper), a = lower, b = upper, where start is start_lengths[k][v] or, with start_lengths NULL, the engine's t_v.  Each
+ * iteration evaluates d1(t) and d2(t), the first and second derivative of the entry's lnL in the length of v
+ * (phyamd_branch_hessian_diagonal's definitions, row v); if d1 > 0 then a = t, else b = t; it proposes t' = t - d1 / d2 when d2 < 0
+ * and a < t' < b, otherwise t' = (a + b) / 2; it stops when |t' - t| <= tolerance, and t* = t'.  iterations[k][v] is the number of
+ * proposals made.  After max_iterations proposals without that the entry stops all the same: t* is the last proposal and the count
+ * is stored negated.  lengths[k][v] = t*; lnl, d1 and d2 are evaluated at t* and are what phyamd_nni_log_likelihoods_general
+ * returns for the entry at central_lengths[k][v] = t*, up to the order of the sum over patterns.  (The central branch's transition
+ * matrix enters as V e^(lambda t r_c) V^-1 without the reference's elementwise |.|: a rounding difference.)  A lnL that is not
+ * finite at an iterate (some pattern's site likelihood is not in (0, inf): underflow, the call does not rescale) ends the entry in
+ * band: lengths holds that iterate, lnl the value that is not finite, d1 and d2 NaN and iterations a negative count.  Columns of
+ * tips and of the root hold NaN in the double outputs and 0 in iterations (two tips: everywhere); entries of start_lengths at those
+ * columns are not read.  d1, d2 and iterations may be NULL.  When u is the root, k = 1 and k = 2 are, for a reversible model, the
+ * same unrooted topology with the lengths of a, b and s redistributed; they are computed like every other entry.
+ * The tree side is read from resident partials, exactly as in phyamd_nni_log_likelihoods_general: THE ENGINE IS AFTERWARDS ONE WITH
+ * phyamd_set_keep_partials(1) THAT HAS RUN THE FLAGS-0 GRADIENT; its topology, lengths and models are unchanged, and later
+ * evaluations return the bits such an engine returns without the call.  Upper partials that a PHYAMD_GRAD_FOLD_ROOT_FREQS
+ * keep-partials gradient left resident are used as they are (pi is inside them).  The four messages that meet on a candidate edge
+ * do not depend on the central length, so an entry's site likelihood is sum_c sum_e K[c][e] exp(lambda_e r_c t) with
+ * K[c][e] = w_c (V^T F)_e (V^-1 p)_e (F and p: see phyamd_nni_log_likelihoods_general).  K is formed once per entry -- seven
+ * 20-wide products on the fp64 matrix cores per (candidate, category, 16 patterns) -- and kept in the batch scratch; then one
+ * workgroup runs the entry's whole rule, and an iteration costs C x 20 exponentials and a pass over K: nothing is walked, no trial
+ * matrix is formed, and no iteration costs a walk, a launch or a host round trip.  Two calls return identical bits; an entry's
+ * bits depend on the engine's inputs and on its own start alone -- not on the other entries, the chunks the candidates ran in, the
+ * optional outputs or what the batch scratch held.  Nothing is added with atomics: sums over patterns are formed in a fixed order
+ * inside the entry's workgroup.  The engine is never switched to rescaling by the call's own kernels.  The scratch is the batch
+ * scratch's: per candidate 3 x C x 20 doubles per (padded) pattern and its three entries' results; candidates that do not fit the
+ * memory cap together run in chunks.
+ * PHYAMD_EINVAL: null engine, lengths or lnl (checked before the handle's state is looked at), no eigen system, bounds that are not
+ * 0 <= lower < upper < inf, a tolerance that is not finite and positive, max_iterations outside 1..1000, a negative or non-finite
+ * start length of a candidate (named), an engine that is not ready to evaluate.  There is no fallback path: PHYAMD_EUNSUPPORTED,
+ * naming the function and the condition: a state count other than 20 (4: use phyamd_nni_optimize; 60 / 61: not built), more than 8
+ * categories, flags other than 0, tiled patterns, explicit node matrices, an engine that is rescaling -- also when
+ * PHYAMD_RESCALE_AUTO switched it on during the call's own evaluation --, a handle sharded over several devices, scratch of one
+ * candidate that does not fit the memory cap.  phyamd_get_nni_optimize_profile reports the last call of either kind. */
+int phyamd_nni_optimize_general(phyamd_engine *e, int flags, const double *start_lengths /* [3][2T-1] or NULL: the engine's t_v */,
+                                double lower, double upper, double tolerance, int32_t max_iterations,
+                                double *lengths /* [3][2T-1] */, double *lnl /* [3][2T-1] */, double *d1 /* [3][2T-1] or NULL */,
+                                double *d2 /* [3][2T-1] or NULL */, int32_t *iterations /* [3][2T-1] or NULL */);
 
 #ifdef __cplusplus
 }

@@ -149,6 +149,7 @@ SYMBOLS = [
     ("phyamd_nni_log_likelihoods_general", C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
     ("phyamd_get_nni_profile", C.c_int, [_P, C.POINTER(NniProfile)]),
     ("phyamd_nni_optimize", C.c_int, [_P, C.c_int, _P, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P, _P, _P, _P]),
+    ("phyamd_nni_optimize_general", C.c_int, [_P, C.c_int, _P, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P, _P, _P, _P]),
     ("phyamd_get_nni_optimize_profile", C.c_int, [_P, C.POINTER(NniOptimizeProfile)]),
     ("phyamd_optimize_branch_lengths", C.c_int, [_P, C.c_int, C.c_int32, _P, _P, _P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_double,
                                                  C.c_int32, _P, _P, _P, _P]),

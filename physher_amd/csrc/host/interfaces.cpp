@@ -953,6 +953,13 @@ void TreeLikelihoodInterface::NNIOptimize(const double *startLengths, double low
 	phyamd::check(phyamd_nni_optimize(impl_->engine, 0, startLengths, lower, upper, tolerance, maxIterations, lengths, logLikelihoods, d1, d2, iterations));
 }
 
+void TreeLikelihoodInterface::NNIOptimizeGeneral(const double *startLengths, double lower, double upper, double tolerance, int maxIterations, double *lengths,
+                                                 double *logLikelihoods, double *d1, double *d2, int32_t *iterations) {
+	if (!lengths || !logLikelihoods) throw Error("null lengths or logLikelihoods");
+	Sync();
+	phyamd::check(phyamd_nni_optimize_general(impl_->engine, 0, startLengths, lower, upper, tolerance, maxIterations, lengths, logLikelihoods, d1, d2, iterations));
+}
+
 void TreeLikelihoodInterface::OptimizeBranchLengths(size_t count, const int32_t *left, const int32_t *right, const int32_t *roots, const double *branchLengths,
                                                     const uint8_t *optimise, double lower, double upper, double tolerance, int maxIterations, double lnlTolerance,
                                                     int maxPasses, double *lengths, double *logLikelihoods, double *initialLogLikelihoods, int32_t *passes) {

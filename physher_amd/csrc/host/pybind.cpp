@@ -282,6 +282,15 @@ PYBIND11_MODULE(_phycpp_amd, m) {
 		    const std::vector<py::ssize_t> shape{3, N};
 		    return py::make_tuple(darray(shape, len.data()), darray(shape, lnl.data()), darray(shape, d1.data()), darray(shape, d2.data()), iarray(shape, it.data()));
 	    }, py::arg("start_lengths") = py::none(), py::arg("lower") = 1e-8, py::arg("upper") = 10.0, py::arg("tolerance") = 1e-8, py::arg("max_iterations") = 100)
+	    .def("nni_optimize_general", [](TreeLikelihoodInterface &self, std::optional<darray> start, double lower, double upper, double tolerance, int max_iterations) -> py::tuple {
+		    const py::ssize_t N = (py::ssize_t)self.NodeCount();
+		    if (start && (start->ndim() != 2 || start->shape(0) != 3 || start->shape(1) != N)) throw phyamd::Error("start lengths: [3][node_count]");
+		    std::vector<double> len((size_t)3 * N), lnl(len.size()), d1(len.size()), d2(len.size());
+		    std::vector<int32_t> it(len.size());
+		    self.NNIOptimizeGeneral(start ? start->data() : nullptr, lower, upper, tolerance, max_iterations, len.data(), lnl.data(), d1.data(), d2.data(), it.data());
+		    const std::vector<py::ssize_t> shape{3, N};
+		    return py::make_tuple(darray(shape, len.data()), darray(shape, lnl.data()), darray(shape, d1.data()), darray(shape, d2.data()), iarray(shape, it.data()));
+	    }, py::arg("start_lengths") = py::none(), py::arg("lower") = 1e-8, py::arg("upper") = 10.0, py::arg("tolerance") = 1e-8, py::arg("max_iterations") = 100)
 	    .def("optimize_branch_lengths", [](TreeLikelihoodInterface &self, iarray left, iarray right, iarray roots, darray lengths, std::optional<py::array_t<uint8_t, py::array::c_style | py::array::forcecast>> optimise,
 	                                       double lower, double upper, double tolerance, int max_iterations, double lnl_tolerance, int max_passes) -> py::tuple {
 		    const size_t count = check_trees(self, left, right, roots, lengths);

@@ -637,6 +637,20 @@ int phyamd_nni_optimize(phyamd_engine *g, int flags, const double *start_lengths
 	return shard_nni_optimize(g->shards[0], flags, NniOptimizeArgs{start_lengths, lower, upper, tolerance, max_iterations, lengths, lnl, d1, d2, iterations});
 }
 
+// the same for 20 states, from the resident partials; one device only, like the other 20-state query calls
+int phyamd_nni_optimize_general(phyamd_engine *g, int flags, const double *start_lengths, double lower, double upper, double tolerance, int32_t max_iterations, double *lengths,
+                                double *lnl, double *d1, double *d2, int32_t *iterations) {
+	static const char *const name = "phyamd_nni_optimize_general";
+	if (!lengths || !lnl) return fail(PHYAMD_EINVAL, "%s: null %s", name, !lengths ? "lengths" : "lnl");
+	if (!g || g->shards.empty()) return fail(PHYAMD_EINVAL, "%s: null engine", name);
+	if (!(lower >= 0.0 && lower < upper && std::isfinite(upper))) return fail(PHYAMD_EINVAL, "%s: bounds [%g, %g]: they must be 0 <= lower < upper < inf", name, lower, upper);
+	if (!(tolerance > 0.0 && std::isfinite(tolerance))) return fail(PHYAMD_EINVAL, "%s: tolerance %g: it must be finite and positive", name, tolerance);
+	if (max_iterations < 1 || max_iterations > 1000) return fail(PHYAMD_EINVAL, "%s: max_iterations %d is outside 1..1000", name, max_iterations);
+	if (group_size(g) > 1)
+		return fail(PHYAMD_EUNSUPPORTED, "%s: a handle sharded over several devices is out of scope: the call reads one engine's resident partials (use one device)", name);
+	return shard_nni_optimize_general(g->shards[0], flags, NniOptimizeArgs{start_lengths, lower, upper, tolerance, max_iterations, lengths, lnl, d1, d2, iterations});
+}
+
 int phyamd_get_nni_optimize_profile(phyamd_engine *g, phyamd_nni_optimize_profile *out) {
 	return merged_profile(g, &Shard::cbopt_prof, out, [](phyamd_nni_optimize_profile &, const phyamd_nni_optimize_profile &) {});  // (never sharded)
 }

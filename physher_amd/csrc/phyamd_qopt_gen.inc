@@ -190,9 +190,10 @@ __device__ __forceinline__ void classopt_coefficients(const ClassOptArgs &a, con
 }
 
 // the sums of w log L (final only), w L'/L and w (L''/L - (L'/L)^2) over the patterns at length t, the same bits in every thread;
-// *bad: some pattern's L is not in (0, inf), so lnL at t is not finite.  cbopt_evaluate over 20 eigen terms
-__device__ __forceinline__ void classopt_evaluate(const ClassOptArgs &a, const double *Kcand, double t, bool final, ClassOptShared &sh, double *lnl, double *d1, double *d2,
-                                                  bool *bad) {
+// *bad: some pattern's L is not in (0, inf), so lnL at t is not finite.  cbopt_evaluate over 20 eigen terms.  Args: P, Pp, C, model
+// (its eigenvalues), rates, weights; Shared: e [3 C 20] and w [3 waves] (k_classopt_solve, and k_classcb_solve of phyamd_nniopt_gen.inc)
+template <class Args, class Shared>
+__device__ __forceinline__ void classopt_evaluate(const Args &a, const double *Kcand, double t, bool final, Shared &sh, double *lnl, double *d1, double *d2, bool *bad) {
 	constexpr int S = PLACE_GEN_STATES, KT = 5;
 	const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), rq = lane >> 4, CS = a.C * S;
 	const size_t Pp = (size_t)a.Pp;

@@ -734,6 +734,37 @@ ScratchPlan nni_gen_plan(Shard *e, size_t nblk) {
 	return p;
 }
 
+// the candidate edges of the engine's tree with the resident partials of their four messages, in node order, and their index by
+// node, into d_nnig_cands and d_nni_cand_of (the caller waits for the stream before the two vectors go).  What the two 20-state NNI
+// calls share
+int upload_classnni_records(Shard *e, const char *name, std::vector<ClassNniCand> &records, std::vector<int32_t> &cand_of) {
+	const int T = e->T, N = e->N, root = e->root;
+	const size_t npd = node_partial_doubles(e);
+	const auto lower_of = [&](int n) { return n < T ? (const double *)nullptr : e->d_lower + (size_t)e->sched.core_index[n] * npd; };
+	records.clear();
+	cand_of.assign(N, -1);
+	for (int v = T; v < N; v++) {
+		if (v == root) continue;
+		const int u = e->sched.parent[v], s = e->left[u] == v ? e->right[u] : e->left[u], a = e->left[v], b = e->right[v];
+		for (const int n : {a, b, s})
+			if (n >= T && e->sched.core_index[n] < 0) return fail(PHYAMD_EDEVICE, "%s: node %d has no resident lower partial", name, n);
+		if (u != root && (e->sched.upper_slot[u] < 0 || !e->d_upper)) return fail(PHYAMD_EDEVICE, "%s: node %d has no resident upper partial", name, u);
+		cand_of[v] = (int32_t)records.size();
+		records.push_back(ClassNniCand{u == root ? nullptr : e->d_upper + (size_t)e->sched.upper_slot[u] * npd, lower_of(a), lower_of(b), lower_of(s), v, u, a, b, s, {0, 0, 0}});
+	}
+	e->nni_lists_valid = false;  // (d_nni_cand_of holds this call's index, which is the 4-state lists' too, but their ops and candidates are not here)
+	HIP_TRY(hipMemcpyAsync(e->d_nnig_cands, records.data(), sizeof(ClassNniCand) * records.size(), hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipMemcpyAsync(e->d_nni_cand_of, cand_of.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, e->stream));
+	return PHYAMD_OK;
+}
+
+// the images of V^T and V^-1 into d_nnig_eig
+void launch_classnni_eigen_images(Shard *e) {
+	const double *evec = e->d_model.get() + PLACE_GEN_STATES, *ivec = evec + PLACE_GEN_STATES * PLACE_GEN_STATES;  // d_model: eval [20] | evec [20][20] | ivec [20][20]
+	hipLaunchKernelGGL(k_classplace_transposed_images, dim3(1), dim3(256), 0, e->stream, evec, e->d_nnig_eig.get());
+	build_matrix_images(e, 1, ivec, e->d_nnig_eig.get() + MatImage<2, 5>::SIZE);
+}
+
 // out [3 terms][3][N] (host): the four messages round every candidate edge read from the resident partials, every edge's three
 // arrangements in one launch.  Writes only the batch scratch beyond the evaluation that made the partials resident
 int run_nni_general(Shard *e, int flags, const double *central_lengths, bool deriv, double *out, phyamd_nni_profile &prof) {
@@ -753,7 +784,7 @@ int run_nni_general(Shard *e, int flags, const double *central_lengths, bool der
 		}
 	}
 	if ((rc = check_general_query_resident(e, call))) return rc;
-	const size_t cands = nni_candidates(e), npd = node_partial_doubles(e), image = MatImage<2, 5>::SIZE;
+	const size_t cands = nni_candidates(e);
 	prof.candidates = (int32_t)cands;
 	std::fill(out, out + (size_t)9 * N, NAN);
 	if (cands == 0) return PHYAMD_OK;  // two tips: no internal edge
@@ -763,25 +794,11 @@ int run_nni_general(Shard *e, int flags, const double *central_lengths, bool der
 		return fail(PHYAMD_EUNSUPPORTED, "%s: the scratch (%zu bytes: the candidates, the slab and the result) does not fit the memory budget", call.name,
 		            plan.item_bytes() + plan.fixed_bytes());
 	if ((rc = ensure_batch_scratch(e, 1, plan))) return rc;
-	const auto lower_of = [&](int n) { return n < T ? (const double *)nullptr : e->d_lower + (size_t)e->sched.core_index[n] * npd; };
 	std::vector<ClassNniCand> records;
-	std::vector<int32_t> cand_of(N, -1);
-	for (int v = T; v < N; v++) {
-		if (v == root) continue;
-		const int u = e->sched.parent[v], s = e->left[u] == v ? e->right[u] : e->left[u], a = e->left[v], b = e->right[v];
-		for (const int n : {a, b, s})
-			if (n >= T && e->sched.core_index[n] < 0) return fail(PHYAMD_EDEVICE, "%s: node %d has no resident lower partial", call.name, n);
-		if (u != root && (e->sched.upper_slot[u] < 0 || !e->d_upper)) return fail(PHYAMD_EDEVICE, "%s: node %d has no resident upper partial", call.name, u);
-		cand_of[v] = (int32_t)records.size();
-		records.push_back(ClassNniCand{u == root ? nullptr : e->d_upper + (size_t)e->sched.upper_slot[u] * npd, lower_of(a), lower_of(b), lower_of(s), v, u, a, b, s, {0, 0, 0}});
-	}
-	e->nni_lists_valid = false;  // (d_nni_cand_of holds this call's index, which is the 4-state lists' too, but their ops and candidates are not here)
-	HIP_TRY(hipMemcpyAsync(e->d_nnig_cands, records.data(), sizeof(ClassNniCand) * records.size(), hipMemcpyHostToDevice, e->stream));
-	HIP_TRY(hipMemcpyAsync(e->d_nni_cand_of, cand_of.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, e->stream));
+	std::vector<int32_t> cand_of;
+	if ((rc = upload_classnni_records(e, call.name, records, cand_of))) return rc;
 	HIP_TRY(hipMemcpyAsync(e->d_nni_len, trial.data(), sizeof(double) * trial.size(), hipMemcpyHostToDevice, e->stream));
-	const double *evec = e->d_model.get() + PLACE_GEN_STATES, *ivec = evec + PLACE_GEN_STATES * PLACE_GEN_STATES;  // d_model: eval [20] | evec [20][20] | ivec [20][20]
-	hipLaunchKernelGGL(k_classplace_transposed_images, dim3(1), dim3(256), 0, e->stream, evec, e->d_nnig_eig.get());
-	build_matrix_images(e, 1, ivec, e->d_nnig_eig.get() + image);
+	launch_classnni_eigen_images(e);
 	for (size_t first = 0; first < cands; first += BATCH_MAX_CHUNK) {  // (gridDim.y)
 		const size_t n = std::min<size_t>(cands - first, BATCH_MAX_CHUNK);
 		const ClassNniArgs a{e->d_nnig_cands.get() + first, N, P, e->Pp, C, e->upper_fold ? 1 : 0, deriv ? 1 : 0, e->d_tipmask, e->d_tipsets, e->d_freqs, e->d_props, e->d_rates,
@@ -819,15 +836,19 @@ ScratchPlan cbopt_plan(Shard *e, size_t chunk) {
 	return p;
 }
 
-// the candidates of a chunk: all of them (at most gridDim.y's) if the scratch holds as much or has room for it, else what fits
-// beside the walk (0: not even one)
-size_t cbopt_chunk(Shard *e, size_t cands) {
+// the candidates of a chunk under plan_of(chunk), whose fixed bytes grow with the chunk: all of them (at most gridDim.y's) if the
+// scratch holds as much or has room for it, else what fits beside the part that does not grow (0: not even one)
+template <typename PlanOf>
+size_t candidates_that_fit(Shard *e, size_t cands, PlanOf plan_of) {
 	const size_t want = std::min<size_t>(cands, BATCH_MAX_CHUNK);
-	if (batch_items_held(e, cbopt_plan(e, want)) >= 1) return want;
-	const ScratchPlan none = cbopt_plan(e, 0), one = cbopt_plan(e, 1);
+	if (batch_items_held(e, plan_of(want)) >= 1) return want;
+	const ScratchPlan none = plan_of(0), one = plan_of(1);
 	const double walk = (double)(none.fixed_bytes() + none.item_bytes()), per = (double)(one.fixed_bytes() - none.fixed_bytes());
 	const double fit = std::floor((scratch_room(e, (double)batch_scratch_bytes(e), EngineRoom::MayGrow) - walk) / per);
 	return fit < 1.0 ? 0 : (size_t)std::min((double)want, fit);
+}
+size_t cbopt_chunk(Shard *e, size_t cands) {
+	return candidates_that_fit(e, cands, [e](size_t chunk) { return cbopt_plan(e, chunk); });
 }
 
 struct NniOptimizeArgs {
@@ -902,6 +923,100 @@ int run_nni_optimize(Shard *e, int flags, const NniOptimizeArgs &o, phyamd_nni_o
 int shard_nni_optimize(Shard *e, int flags, const NniOptimizeArgs &o) {
 	CHECK_ENGINE(e);
 	return profiled_call(e, &Shard::cbopt_prof, phyamd_nni_optimize_profile{}, [&](phyamd_nni_optimize_profile &prof) { return run_nni_optimize(e, flags, o, prof); });
+}
+
+// ---- the optimised central branch of every NNI neighbour of a 20-state engine's tree (phyamd_nni_optimize_general) ---------------
+
+// nothing is walked: the candidates, their index by node, the images of V^T and V^-1 and the caller's [3][N] start lengths, and for
+// the `chunk` candidates that run at once the coefficients and the results of their three entries
+ScratchPlan classcb_plan(Shard *e, size_t chunk) {
+	const size_t D = sizeof(double), N = (size_t)e->N, C = (size_t)e->C, cands = std::max<size_t>(nni_candidates(e), 1);
+	ScratchPlan p;
+	p.add(e->d_nnig_cands, 0, sizeof(ClassNniCand) * cands);
+	p.add(e->d_nnig_eig, 0, D * 2 * MatImage<2, 5>::SIZE);
+	p.add(e->d_nni_cand_of, 0, sizeof(int32_t) * N);
+	p.add(e->d_nni_len, 0, D * 3 * N);
+	p.add(e->d_classcb_K, 0, chunk * D * 3 * C * PLACE_GEN_STATES * (size_t)e->Pp);
+	p.add(e->d_classcb_out, 0, chunk * D * 3 * 4);
+	p.add(e->d_classcb_iter, 0, chunk * sizeof(int32_t) * 3);
+	return p;
+}
+
+// the four messages round every candidate edge read from the resident partials, then chunk by chunk the candidates' coefficients
+// and their iterations.  Writes only the batch scratch beyond the evaluation that made the partials resident
+int run_nni_optimize_general(Shard *e, int flags, const NniOptimizeArgs &o, phyamd_nni_optimize_profile &prof) {
+	static const GeneralQueryCall call{"phyamd_nni_optimize_general", "the kernels are", "phyamd_nni_optimize", "64-wide products are",
+	                                   "which have no exponential sum in the central length", "the likelihood in the central length is", "coefficients do"};
+	int rc;
+	if ((rc = check_general_query_inputs(e, call, flags))) return rc;
+	const int T = e->T, N = e->N, C = e->C, P = e->P, root = e->root;
+	std::vector<double> start((size_t)3 * N);  // a candidate's own three where the caller gives them, every other entry the engine's (not read)
+	for (int k = 0; k < 3; k++) std::copy(e->lengths.begin(), e->lengths.end(), start.begin() + (size_t)k * N);
+	for (int v = T; v < N && o.start; v++) {
+		if (v == root) continue;
+		for (int k = 0; k < 3; k++) {
+			const double t = o.start[(size_t)k * N + v];
+			if (!std::isfinite(t) || t < 0.0) return fail(PHYAMD_EINVAL, "%s: start_lengths[%d][%d] = %g: a start length is finite and not negative", call.name, k, v, t);
+			start[(size_t)k * N + v] = t;
+		}
+	}
+	if ((rc = check_general_query_resident(e, call))) return rc;
+	const size_t cands = nni_candidates(e), entries = (size_t)3 * N;
+	prof.candidates = (int32_t)cands;
+	std::fill(o.lengths, o.lengths + entries, NAN);
+	std::fill(o.lnl, o.lnl + entries, NAN);
+	if (o.d1) std::fill(o.d1, o.d1 + entries, NAN);
+	if (o.d2) std::fill(o.d2, o.d2 + entries, NAN);
+	if (o.iterations) std::fill(o.iterations, o.iterations + entries, 0);
+	if (cands == 0) return PHYAMD_OK;  // two tips: no internal edge
+	const size_t chunk = candidates_that_fit(e, cands, [e](size_t n) { return classcb_plan(e, n); });
+	if (chunk < 1) {
+		const ScratchPlan one = classcb_plan(e, 1);
+		return fail(PHYAMD_EUNSUPPORTED, "%s: the scratch of one candidate (%zu bytes: the candidates, and its entries' coefficients) does not fit the memory budget", call.name,
+		            one.fixed_bytes() + one.item_bytes());
+	}
+	if ((rc = ensure_batch_scratch(e, 1, classcb_plan(e, chunk)))) return rc;
+	std::vector<ClassNniCand> records;
+	std::vector<int32_t> cand_of;
+	if ((rc = upload_classnni_records(e, call.name, records, cand_of))) return rc;
+	HIP_TRY(hipMemcpyAsync(e->d_nni_len, start.data(), sizeof(double) * start.size(), hipMemcpyHostToDevice, e->stream));
+	launch_classnni_eigen_images(e);
+	const int nblk = (P + CLASSNNI_BLOCK - 1) / CLASSNNI_BLOCK;
+	std::vector<double> out;
+	std::vector<int32_t> iter;
+	for (size_t first = 0; first < cands; first += chunk) {
+		const size_t n = std::min(chunk, cands - first);
+		const ClassCbCoeffArgs ca{e->d_nnig_cands.get() + first, P, e->Pp, C, e->upper_fold ? 1 : 0, e->d_tipmask, e->d_tipsets, e->d_freqs, e->d_props, e->d_imgs, e->d_nnig_eig,
+		                          e->d_classcb_K};
+		hipLaunchKernelGGL(k_classcb_coeff, dim3((unsigned)nblk, (unsigned)n), dim3(GenGeo<2>::WAVES * 64), 0, e->stream, ca);
+		const ClassCbSolveArgs sa{e->d_nnig_cands.get() + first, N, P, e->Pp, C, o.max_iterations, o.lower, o.upper, o.tolerance, e->d_model, e->d_rates, e->d_weights,
+		                          e->d_nni_len, e->d_classcb_K, e->d_classcb_out, e->d_classcb_iter};
+		hipLaunchKernelGGL(k_classcb_solve, dim3((unsigned)(3 * n)), dim3(CLASSOPT_THREADS), 0, e->stream, sa);
+		HIP_TRY(hipGetLastError());
+		out.resize(n * 12);
+		iter.resize(n * 3);
+		HIP_TRY(hipMemcpyAsync(out.data(), e->d_classcb_out, sizeof(double) * out.size(), hipMemcpyDeviceToHost, e->stream));
+		HIP_TRY(hipMemcpyAsync(iter.data(), e->d_classcb_iter, sizeof(int32_t) * iter.size(), hipMemcpyDeviceToHost, e->stream));
+		HIP_TRY(hipStreamSynchronize(e->stream));  // (also covers the records, the index and `start`)
+		prof.chunks++;
+		for (size_t i = 0; i < n; i++)
+			for (int k = 0; k < 3; k++) {
+				const double *r = &out[(i * 3 + k) * 4];
+				const size_t at = (size_t)k * N + records[first + i].v;
+				o.lengths[at] = r[0];
+				o.lnl[at] = r[1];
+				if (o.d1) o.d1[at] = r[2];
+				if (o.d2) o.d2[at] = r[3];
+				if (o.iterations) o.iterations[at] = iter[i * 3 + k];
+				prof.iterations += std::abs(iter[i * 3 + k]);
+			}
+	}
+	return PHYAMD_OK;
+}
+
+int shard_nni_optimize_general(Shard *e, int flags, const NniOptimizeArgs &o) {
+	CHECK_ENGINE(e);
+	return profiled_call(e, &Shard::cbopt_prof, phyamd_nni_optimize_profile{}, [&](phyamd_nni_optimize_profile &prof) { return run_nni_optimize_general(e, flags, o, prof); });
 }
 
 // ---- all branch lengths of a batch of trees (phyamd_optimize_branch_lengths) -----------------------------------------------------

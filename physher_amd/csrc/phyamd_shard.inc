@@ -223,7 +223,7 @@ struct Shard {
 	DeviceArray<BatchOp> d_batch_item_ops{&batch_mem};  // [item][post-order T - 1 | pre-order T - 1]
 	DeviceArray<int32_t> d_batch_roots{&batch_mem};     // [item]
 	// what the scratch holds: every call describes what it needs as a ScratchPlan (phyamd_queries.inc: batch_plan, reweight_plan,
-	// nni_base_plan with nni_plan and cbopt_plan, nni_gen_plan, blopt_plan, spr_plan with tripod_plan, pairdist_plan, bhess_plan, sitelnl_plan; phyamd_place_calls.inc: place_plan,
+	// nni_base_plan with nni_plan and cbopt_plan, nni_gen_plan, classcb_plan, blopt_plan, spr_plan with tripod_plan, pairdist_plan, bhess_plan, sitelnl_plan; phyamd_place_calls.inc: place_plan,
 	// place_gen_plan, qopt_plan, qopt_gen_plan) and gets at least that, so a call of one kind
 	// never runs in the scratch of another with too few upper slots or without its lists.  batch_held: the plan the arrays were last
 	// allocated by, for batch_items items (the Hessian's arrays, grown beside it, are judged by their sizes alone)
@@ -336,6 +336,12 @@ struct Shard {
 	// d_nni_slab with blocks of 128 patterns, d_nni_out); it adds its candidates and the images of V^T and V^-1
 	DeviceArray<ClassNniCand> d_nnig_cands{&batch_mem};   // [T - 2]
 	DeviceArray<double> d_nnig_eig{&batch_mem};           // [V^T | V^-1][image]
+	// phyamd_nni_optimize_general (phyamd_nniopt_gen.inc) reads the same partials through the same candidates, index and eigen images
+	// (the start lengths go through d_nni_len) and adds, per candidate of a chunk: the coefficients of its three entries and their
+	// results.  cbopt_prof keeps the last optimise call of either kind
+	DeviceArray<double> d_classcb_K{&batch_mem};          // [candidate][3][C][20][Pp]
+	DeviceArray<double> d_classcb_out{&batch_mem};        // [candidate][3][t*, lnL, d1, d2]
+	DeviceArray<int32_t> d_classcb_iter{&batch_mem};      // [candidate][3]
 	// phyamd_state_posteriors / phyamd_site_rate_posteriors (phyamd_post.inc): the rows of a chunk, their staged results -- [rows][P][S]
 	// posteriors and [rows][P] states, or [P][C] + [P] site rates -- and, 20 / 60 / 61 states, each row's own partial p_n (true_lower_gen).
 	// On demand, like d_branch: the calls read what the keep-partials gradient left and have no entry in the record above

@@ -299,6 +299,20 @@ class Engine:
         iterations: the steps proposed, negated where max_iterations ran out or lnL was not finite.  lnl, d1, d2 are those of
         nni_log_likelihoods at the returned lengths.  The engine's tree, lengths and partials stay.  No fallback: EngineError
         where nni_log_likelihoods refuses, and on a sharded engine."""
+        return self._nni_optimize(self._lib.phyamd_nni_optimize, start_lengths, lower, upper, tolerance, max_iterations, want_derivatives, want_iterations, flags)
+
+    def nni_optimize_general(self, start_lengths=None, lower=1e-8, upper=10.0, tolerance=1e-8, max_iterations=100, want_derivatives=True,
+                             want_iterations=True, flags=0):
+        """nni_optimize for an engine of 20 states: (lengths, lnl, d1, d2, iterations), each [3, N], in that method's rows and
+        columns, by its rule and with its sign convention for iterations.  lnl, d1, d2 are those of nni_log_likelihoods_general at
+        the returned lengths.  The four messages round every edge are read from the resident partials: afterwards the engine is
+        one with set_keep_partials(True) that has run gradient(); its tree, lengths and models stay.  An entry whose lnL is not
+        finite at an iterate ends there with NaN d1 and d2 and a negative count.  No fallback: EngineError for a state count other
+        than 20, more than 8 categories, flags, tiled patterns, explicit matrices, a rescaling or a sharded engine."""
+        return self._nni_optimize(self._lib.phyamd_nni_optimize_general, start_lengths, lower, upper, tolerance, max_iterations, want_derivatives, want_iterations,
+                                  flags)
+
+    def _nni_optimize(self, call, start_lengths, lower, upper, tolerance, max_iterations, want_derivatives, want_iterations, flags):
         sl = None
         if start_lengths is not None:
             sl = _f64(start_lengths)
@@ -308,13 +322,12 @@ class Engine:
         d1 = np.empty((3, self.N)) if want_derivatives else None
         d2 = np.empty((3, self.N)) if want_derivatives else None
         it = np.empty((3, self.N), dtype=np.int32) if want_iterations else None
-        self._check(self._lib.phyamd_nni_optimize(self._h, flags, None if sl is None else _ptr(sl), lower, upper, tolerance, max_iterations,
-                                                  _ptr(lengths), _ptr(lnl), None if d1 is None else _ptr(d1), None if d2 is None else _ptr(d2),
-                                                  None if it is None else _ptr(it)))
+        self._check(call(self._h, flags, None if sl is None else _ptr(sl), lower, upper, tolerance, max_iterations, _ptr(lengths), _ptr(lnl),
+                         None if d1 is None else _ptr(d1), None if d2 is None else _ptr(d2), None if it is None else _ptr(it)))
         return lengths, lnl, d1, d2, it
 
     def nni_optimize_profile(self):
-        """Of the last nni_optimize: candidates, chunks (of candidates), scratch_bytes, iterations (over all entries), ms."""
+        """Of the last nni_optimize or nni_optimize_general: candidates, chunks (of candidates), scratch_bytes, iterations (over all entries), ms."""
         p = _lib.NniOptimizeProfile()
         self._check(self._lib.phyamd_get_nni_optimize_profile(self._h, C.byref(p)))
         return {k: getattr(p, k) for k, _ in p._fields_}
