@@ -345,6 +345,10 @@ class TreeLikelihoodInterface : public CallableModelInterface {
 	// prune[i] (null: count = 2T-1 and row i is node i), column w the target edge; NaN where there is no candidate.  Lengths are
 	// the engine's branch lengths, as for NNILogLikelihoods.  The tree model and this object's own state are unchanged.
 	void SPRLogLikelihoods(const int *prune, int count, double *out);
+	// The same for a model of 20 states (one phyamd_spr_log_likelihoods_general call; see include/physher_amd.h): the arguments and
+	// the array are SPRLogLikelihoods'.  The call reads the engine's resident partials, which it makes resident if they are not;
+	// the tree model and this object's own state are unchanged.
+	void SPRLogLikelihoodsGeneral(const int *prune, int count, double *out);
 	// The three branches that meet at the graft point of every SPR regraft optimised at once (one phyamd_spr_optimize call; see
 	// include/physher_amd.h for the rule): SPRLogLikelihoods' rows, columns and candidates; lengths [count][2T-1][3] holds the lengths
 	// of the prune node, of the target node and of the prune node's parent, logLikelihoods [count][2T-1]; initialLogLikelihoods

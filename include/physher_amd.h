@@ -373,7 +373,7 @@ int phyamd_get_nni_optimize_profile(phyamd_engine *e, phyamd_nni_optimize_profil
  * it).  Sharded handles run on every shard's patterns and add the arrays in shard order. */
 int phyamd_spr_log_likelihoods(phyamd_engine *e, int flags, int32_t count, const int32_t *prune /* [count] or NULL */,
                                double *lnl /* [count][2T-1] */);
-/* of the last phyamd_spr_log_likelihoods: rows asked for, chunks of rows they ran in, candidates scored, bytes of batch scratch
+/* of the last phyamd_spr_log_likelihoods or phyamd_spr_log_likelihoods_general: rows asked for, chunks of rows they ran in, candidates scored, bytes of batch scratch
  * the engine holds (see phyamd_batch_profile), wall time of the call.  Sharded handles: candidates and scratch_bytes are summed
  * over the shards */
 typedef struct { int32_t prunes, chunks; int64_t candidates, scratch_bytes; double ms; } phyamd_spr_profile;
@@ -1142,6 +1142,45 @@ int phyamd_nni_optimize_general(phyamd_engine *e, int flags, const double *start
                                 double lower, double upper, double tolerance, int32_t max_iterations,
                                 double *lengths /* [3][2T-1] */, double *lnl /* [3][2T-1] */, double *d1 /* [3][2T-1] or NULL */,
                                 double *d2 /* [3][2T-1] or NULL */, int32_t *iterations /* [3][2T-1] or NULL */);
+/* phyamd_spr_log_likelihoods for an engine of 20 states (proteins): lnL of every SPR regraft of chosen subtrees of the engine's tree
+ * in one call.  The route this replaces is a second engine looped over the O(T^2) rearranged trees, each walked from the tips.
+ * THE DEFINITION, in full (it is phyamd_spr_log_likelihoods', word for word).  Row i of lnl ([count][2T-1]) belongs to the prune node
+ * p = prune[i]; prune == NULL: count must be 2T-1 and row i is node i.  Column w is the target edge, named by the node below it.
+ * With u = parent(p), s = sibling(p), g = parent(u), x = parent(w), lnl[i][w] is the log-likelihood of the tree obtained from the
+ * engine's arrays by (node ids kept)
+ *   g's child slot that held u now holds s, with t'_s = t_s + t_u;
+ *   x's child slot that held w now holds u;
+ *   u keeps p in its slot and gets w in the slot s had, with t'_u = t'_w = 0.5 t_w;
+ * everything else -- the root, t_p -- unchanged.  Entry (i, w) is what the engine itself returns from phyamd_log_likelihood for that
+ * tree (the sibling's branch enters as P(t_u r_c) P(t_s r_c), not as the matrix of the summed length: a rounding difference).
+ * Column w is a CANDIDATE unless w is the root, u, s, p or a descendant of p; every other column is NaN.  A row is all NaN when p is
+ * the root or a child of the root (no error, so that prune == NULL works uniformly).  Duplicates in prune are allowed.  A candidate
+ * whose lnL is not finite (some pattern's site likelihood is not in (0, inf): underflow, the call does not rescale) reports it in
+ * band.
+ * The tree side is read from resident partials, exactly as in phyamd_nni_log_likelihoods_general: THE ENGINE IS AFTERWARDS ONE WITH
+ * phyamd_set_keep_partials(1) THAT HAS RUN THE FLAGS-0 GRADIENT; its topology, lengths and models are unchanged, and later
+ * evaluations return the bits such an engine returns without the call.  Only LOWER partials are read -- a stored lower is the
+ * message P_n p_n itself -- so the result is the likelihood's whether or not a PHYAMD_GRAD_FOLD_ROOT_FREQS gradient left pi inside
+ * the resident uppers.  Per row, the messages on the path from u to the root are formed anew (the first is P_u m_s: no merged matrix),
+ * then the pruned tree's upper of every internal node outside p's subtree, parent before child; per candidate, category and 16
+ * patterns three 20-wide products on the fp64 matrix cores give sum_i pi_i U_i (H_w ((H_w p'_w) o m_p))_i with H_w = P(0.5 t_w r_c).
+ * Two calls return identical bits; a row's bits depend on the engine's inputs and on p alone -- not on count, the row's position
+ * in prune, the chunk it ran in or what the batch scratch held.  Nothing is added with atomics: sums over patterns are formed over
+ * blocks of 128 patterns and added in block order.  The engine is never switched to rescaling by the call's own kernels.  The
+ * scratch is the batch scratch's, counted and released like it: per row (T - 1 + D) x C x 20 x Pp x 8 bytes of partials -- the
+ * upper of every internal node and D path messages, D the depth of the deepest internal node, Pp the patterns rounded up to 16 --,
+ * 64 (T - 1 + D) + 4 bytes of ops, and per node 64 bytes of candidate, 4 of index, 8 of result and 8 per block of 128 patterns;
+ * beside the rows, half the engine's lengths with their matrices and images.  Rows that do not fit the memory cap together run in
+ * chunks of rows.
+ * PHYAMD_EINVAL: null engine or lnl (checked before the handle's state is looked at), count < 1, prune == NULL with another count
+ * than 2T-1, an id outside 0..2T-2 (with its index in the message), no eigen system, an engine that is not ready to evaluate.
+ * There is no fallback path: PHYAMD_EUNSUPPORTED, naming the function and the condition: a state count other than 20 (4: use
+ * phyamd_spr_log_likelihoods; 60 / 61: not built), more than 8 categories, flags other than 0, tiled patterns, explicit node
+ * matrices, an engine that is rescaling -- also when PHYAMD_RESCALE_AUTO switched it on during the call's own evaluation --, a
+ * handle sharded over several devices, scratch of one row that does not fit the memory cap.  phyamd_get_spr_profile reports the
+ * last call of either kind. */
+int phyamd_spr_log_likelihoods_general(phyamd_engine *e, int flags, int32_t count, const int32_t *prune /* [count] or NULL */,
+                                       double *lnl /* [count][2T-1] */);
 
 #ifdef __cplusplus
 }

@@ -978,6 +978,12 @@ void TreeLikelihoodInterface::SPRLogLikelihoods(const int *prune, int count, dou
 	phyamd::check(phyamd_spr_log_likelihoods(impl_->engine, 0, count, prune, out));
 }
 
+void TreeLikelihoodInterface::SPRLogLikelihoodsGeneral(const int *prune, int count, double *out) {
+	if (!out) throw Error("null out");
+	Sync();
+	phyamd::check(phyamd_spr_log_likelihoods_general(impl_->engine, 0, count, prune, out));
+}
+
 void TreeLikelihoodInterface::SPROptimize(const int *prune, int count, double lower, double upper, double tolerance, int maxIterations, double lnlTolerance, int maxPasses,
                                           double *lengths, double *logLikelihoods, double *initialLogLikelihoods, int32_t *passes) {
 	if (!lengths || !logLikelihoods) throw Error("null lengths or logLikelihoods");

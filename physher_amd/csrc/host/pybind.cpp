@@ -311,6 +311,14 @@ PYBIND11_MODULE(_phycpp_amd, m) {
 		    self.SPRLogLikelihoods(prune ? prune->data() : nullptr, (int)count, lnl.data());
 		    return darray({count, N}, lnl.data());
 	    }, py::arg("prune") = py::none())
+	    .def("spr_log_likelihoods_general", [](TreeLikelihoodInterface &self, std::optional<iarray> prune) {
+		    const py::ssize_t N = (py::ssize_t)self.NodeCount();
+		    if (prune && prune->ndim() != 1) throw phyamd::Error("prune: [count]");
+		    const py::ssize_t count = prune ? prune->shape(0) : N;
+		    std::vector<double> lnl((size_t)count * N);
+		    self.SPRLogLikelihoodsGeneral(prune ? prune->data() : nullptr, (int)count, lnl.data());
+		    return darray({count, N}, lnl.data());
+	    }, py::arg("prune") = py::none())
 	    .def("spr_optimize", [](TreeLikelihoodInterface &self, std::optional<iarray> prune, double lower, double upper, double tolerance, int max_iterations,
 	                            double lnl_tolerance, int max_passes) -> py::tuple {
 		    const py::ssize_t N = (py::ssize_t)self.NodeCount();

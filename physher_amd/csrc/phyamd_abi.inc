@@ -690,6 +690,18 @@ int phyamd_spr_log_likelihoods(phyamd_engine *g, int flags, int32_t count, const
 	return sum_over_shards(g, (size_t)count * g->N, lnl, [&](Shard *s, int, double *v) { return shard_spr_log_likelihoods(s, flags, count, prune, v); });
 }
 
+// the same for 20 states, from the resident lowers; one device only, like the other 20-state query calls
+int phyamd_spr_log_likelihoods_general(phyamd_engine *g, int flags, int32_t count, const int32_t *prune, double *lnl) {
+	static const char *const name = "phyamd_spr_log_likelihoods_general";
+	if (!lnl) return fail(PHYAMD_EINVAL, "%s: null lnl", name);
+	if (!g || g->shards.empty()) return fail(PHYAMD_EINVAL, "%s: null engine", name);
+	if (count < 1) return fail(PHYAMD_EINVAL, "%s: count must be >= 1 (got %d)", name, count);
+	if (group_size(g) > 1)
+		return fail(PHYAMD_EUNSUPPORTED, "%s: a handle sharded over several devices is out of scope: the call reads one engine's resident partials (use one device)", name);
+	const WallTime timed{&g->spr_ms};
+	return shard_spr_general(g->shards[0], flags, count, prune, lnl);
+}
+
 int phyamd_get_spr_profile(phyamd_engine *g, phyamd_spr_profile *out) {
 	// candidates and memory add up; the shards choose their chunks themselves: the most
 	const int rc = merged_profile(g, &Shard::spr_prof, out, [](phyamd_spr_profile &o, const phyamd_spr_profile &p) {

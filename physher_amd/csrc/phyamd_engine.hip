@@ -4,7 +4,7 @@
 //   phyamd_types.h          plain data the host builds and the kernels read: op lists, descriptors, their enums and constants
 //   phyamd_tree_schedule.h  the tree check and every host-built list as a value built by a pure function (standard C++, no engine)
 //   phyamd_memory.inc       owning device arrays and the memory budget they are allocated through
-//   phyamd_device.inc / _level4 / _walk4 / _walk4s / _general / _genwalk / _patterns / _batch4 / _nni4 / _nniopt4 / _blopt4 / _spr4 / _tripod4 / _post / _bhess / _reweight / _pairdist4 / _pairdist_gen / _place4 / _place_gen / _qopt4 / _qopt_gen  device code (kernels; _rule: the branch-length rule they share)
+//   phyamd_device.inc / _level4 / _walk4 / _walk4s / _general / _genwalk / _patterns / _batch4 / _nni4 / _nniopt4 / _blopt4 / _spr4 / _tripod4 / _post / _bhess / _reweight / _pairdist4 / _pairdist_gen / _place4 / _place_gen / _nni_gen / _spr_gen / _qopt4 / _qopt_gen / _nniopt_gen  device code (kernels; _rule: the branch-length rule they share)
 //   phyamd_shard.inc        state of one engine on one GPU (= one shard of the site patterns), the form of its stored lowers
 //   phyamd_schedule.inc     the engine's schedule on the device: storage, upload, readiness
 //   phyamd_launch.inc       kernel launches per pass
@@ -120,6 +120,7 @@ constexpr double SCALING_THRESHOLD = 1.0e-40;  // treelikelihood.c:1121
 #include "phyamd_place4.inc"
 #include "phyamd_place_gen.inc"
 #include "phyamd_nni_gen.inc"
+#include "phyamd_spr_gen.inc"
 #include "phyamd_qopt4.inc"
 #include "phyamd_qopt_gen.inc"
 #include "phyamd_nniopt_gen.inc"

@@ -1238,14 +1238,9 @@ void build_spr_row(const Shard *e, int row, int p, std::vector<BatchOp> *ops, st
 	}
 }
 
-// what phyamd_spr_log_likelihoods and phyamd_spr_optimize (`name`) check alike; live: the indices of the rows that have candidates
-// -- p is neither the root nor a child of it
-int check_spr_call(Shard *e, const char *name, const char *eigen_use, int flags, int32_t count, const int32_t *prune, std::vector<int32_t> &live) {
-	int rc;
-	if ((rc = check_ready(e))) return rc;
-	if (flags != 0) return fail(PHYAMD_EUNSUPPORTED, "%s: flags %d (no flags are defined: pass 0)", name, flags);
-	if (const char *why = tree_batch_refusal(e, 0, 1)) return fail(PHYAMD_EUNSUPPORTED, "%s: %s", name, why);
-	if (!e->have_eigen) return fail(PHYAMD_EINVAL, "%s needs the eigen system (phyamd_set_eigen): %s", name, eigen_use);
+// the prune list of an SPR call (`name`), 4 or 20 states: null with the node count, or ids; live: the indices of the rows that have
+// candidates -- p is neither the root nor a child of it
+int check_prune_list(const Shard *e, const char *name, int32_t count, const int32_t *prune, std::vector<int32_t> &live) {
 	const int N = e->N;
 	if (!prune && count != N) return fail(PHYAMD_EINVAL, "%s: prune is null, so count must be the node count %d (got %d)", name, N, count);
 	for (int32_t i = 0; i < count; i++) {
@@ -1254,6 +1249,16 @@ int check_spr_call(Shard *e, const char *name, const char *eigen_use, int flags,
 		if (p != e->root && e->sched.parent[p] != e->root) live.push_back(i);
 	}
 	return PHYAMD_OK;
+}
+
+// what phyamd_spr_log_likelihoods and phyamd_spr_optimize (`name`) check alike
+int check_spr_call(Shard *e, const char *name, const char *eigen_use, int flags, int32_t count, const int32_t *prune, std::vector<int32_t> &live) {
+	int rc;
+	if ((rc = check_ready(e))) return rc;
+	if (flags != 0) return fail(PHYAMD_EUNSUPPORTED, "%s: flags %d (no flags are defined: pass 0)", name, flags);
+	if (const char *why = tree_batch_refusal(e, 0, 1)) return fail(PHYAMD_EUNSUPPORTED, "%s: %s", name, why);
+	if (!e->have_eigen) return fail(PHYAMD_EINVAL, "%s needs the eigen system (phyamd_set_eigen): %s", name, eigen_use);
+	return check_prune_list(e, name, count, prune, live);
 }
 
 // the live rows in chunks of what the scratch holds of `plan`; per chunk the rows' lists built and sent, the matrices of the
@@ -1333,6 +1338,167 @@ int run_spr(Shard *e, int flags, int32_t count, const int32_t *prune, double *ln
 int shard_spr_log_likelihoods(Shard *e, int flags, int32_t count, const int32_t *prune, double *lnl) {
 	CHECK_ENGINE(e);
 	return profiled_call(e, &Shard::spr_prof, phyamd_spr_profile{}, [&](phyamd_spr_profile &prof) { return run_spr(e, flags, count, prune, lnl, prof); });
+}
+
+// ---- every SPR regraft of chosen subtrees of a 20-state engine's tree (phyamd_spr_log_likelihoods_general) -----------------------
+
+// an item is a ROW: its planes [C][20][Pp] -- the pruned tree's upper of every internal node by node, then `slots` path messages --,
+// its ops and their count, its candidates, their index by cell, the slab (blocks of CLASSSPR_BLOCK patterns) and the result; whatever
+// the row count: half the engine's lengths, their matrices and images
+ScratchPlan spr_gen_plan(Shard *e, size_t slots, size_t nblk) {
+	const size_t D = sizeof(double), N = (size_t)e->N, C = (size_t)e->C, ops = (size_t)(e->T - 1) + slots, matrix = (size_t)PLACE_GEN_STATES * PLACE_GEN_STATES;
+	ScratchPlan p;
+	p.add(e->d_sprg_work, D * ops * node_partial_doubles(e));
+	p.add(e->d_sprg_ops, sizeof(ClassSprOp) * ops);
+	p.add(e->d_sprg_nops, sizeof(int32_t));
+	p.add(e->d_sprg_cands, sizeof(ClassSprCand) * N);
+	p.add(e->d_spr_cand_of, sizeof(int32_t) * N);
+	p.add(e->d_spr_slab, D * N * nblk);
+	p.add(e->d_spr_out, D * N);
+	p.add(e->d_placeg_len, 0, D * N);
+	p.add(e->d_placeg_zero, 0, N);
+	p.add(e->d_placeg_mats, 0, D * N * C * matrix);
+	p.add(e->d_placeg_dmats, 0, D * N * C * matrix);
+	p.add(e->d_placeg_imgs, 0, D * N * C * MatImage<2, 5>::SIZE);
+	return p;
+}
+
+// row p (not the root, not a child of it) into a chunk's lists: its path ops and pre-order ops into ops[0..], their count returned;
+// its candidates appended to `cands`, their indices into cand_of [N].  work: the row's planes; path: [N] nulls, and nulls again afterwards
+int build_spr_gen_row(const Shard *e, int p, double *work, std::vector<const double *> &path, ClassSprOp *ops, std::vector<ClassSprCand> *cands, int32_t *cand_of) {
+	const int T = e->T, N = e->N, nops = T - 1, root = e->root;
+	const size_t npd = node_partial_doubles(e);
+	const int u = e->sched.parent[p], s = e->left[u] == p ? e->right[u] : e->left[u];
+	const auto below_p = [&](int n) { return e->spr_tin[p] <= e->spr_tin[n] && e->spr_tin[n] < e->spr_tout[p]; };
+	const auto upper_of = [&](int n) { return work + (size_t)(n - T) * npd; };
+	const auto message = [&](int n) {  // the pruned tree's message of n: a path message, the resident lower, or null for a tip
+		return path[n] ? path[n] : n < T ? (const double *)nullptr : e->d_lower + (size_t)e->sched.core_index[n] * npd;
+	};
+	int count = 0, slot = 0;
+	std::vector<int> on_path;
+	const auto path_op = [&](int node, const double *ma, int a, const double *mb, int b) {
+		double *dst = work + (size_t)(nops + slot++) * npd;
+		ops[count++] = ClassSprOp{nullptr, ma, mb, dst, nullptr, node, a, b, 1, {0, 0}};
+		path[node] = dst;
+		on_path.push_back(node);
+	};
+	path_op(u, message(s), s, nullptr, -1);  // m'(slot of u) = P_u m_s
+	for (int child = u, n = e->sched.parent[u]; n != root; child = n, n = e->sched.parent[n]) {
+		const int sib = e->left[n] == child ? e->right[n] : e->left[n];
+		path_op(n, path[child], child, message(sib), sib);
+	}
+	for (int i = 0; i < nops; i++) {
+		const int x = e->spr_ops[nops + i].node;
+		if (x == p || below_p(x)) continue;
+		const int l = e->left[x], r = e->right[x];
+		double *dl = l >= T && l != p ? upper_of(l) : nullptr, *dr = r >= T && r != p ? upper_of(r) : nullptr;
+		if (!dl && !dr) continue;
+		ops[count++] = ClassSprOp{x == root ? nullptr : upper_of(x), l == p ? nullptr : message(l), r == p ? nullptr : message(r), dl, dr, x, l == p ? -1 : l, r == p ? -1 : r, 0, {0, 0}};
+	}
+	const double *mp = p < T ? nullptr : e->d_lower + (size_t)e->sched.core_index[p] * npd;
+	for (int w = 0; w < N; w++) {
+		cand_of[w] = -1;
+		if (w == root || w == u || w == s || below_p(w)) continue;
+		const int x = e->sched.parent[w], y = e->left[x] == w ? e->right[x] : e->left[x];
+		const int l = w < T ? -1 : e->left[w], r = w < T ? -1 : e->right[w];
+		cand_of[w] = (int32_t)cands->size();
+		cands->push_back(ClassSprCand{x == root ? nullptr : upper_of(x), message(y), w < T ? nullptr : message(l), w < T ? nullptr : message(r), mp, w, x, y, l, r, p});
+	}
+	for (const int n : on_path) path[n] = nullptr;
+	return count;
+}
+
+// lnl [count][N] (host): every row walked from the resident lowers into its own planes, every candidate of the chunk in one launch.
+// Writes only the batch scratch beyond the evaluation that made the partials resident
+int run_spr_general(Shard *e, int flags, int32_t count, const int32_t *prune, double *lnl, phyamd_spr_profile &prof) {
+	static const GeneralQueryCall call{"phyamd_spr_log_likelihoods_general", "the kernels are", "phyamd_spr_log_likelihoods", "64-wide products are",
+	                                   "which have no half-length counterpart", "the half-length matrices are", "kernels do"};
+	int rc;
+	if ((rc = check_general_query_inputs(e, call, flags))) {
+		if (g_last_error.find(call.name) != std::string::npos) return rc;
+		const std::string why = g_last_error;  // (an engine that is not ready: check_ready's words, which name no call)
+		return fail(rc, "%s: %s", call.name, why.c_str());
+	}
+	std::vector<int32_t> live;
+	if ((rc = check_prune_list(e, call.name, count, prune, live))) return rc;
+	if ((rc = check_general_query_resident(e, call))) return rc;
+	const int T = e->T, N = e->N, C = e->C, P = e->P, nops = T - 1;
+	std::fill(lnl, lnl + (size_t)count * N, NAN);
+	prof.prunes = count;
+	if (live.empty()) return PHYAMD_OK;
+	for (int n = T; n < N; n++)
+		if (n != e->root && e->sched.core_index[n] < 0) return fail(PHYAMD_EDEVICE, "%s: node %d has no resident lower partial", call.name, n);
+	ensure_spr_lists(e);
+	std::vector<int32_t> depth(N, 0);
+	size_t slots = 1;  // the depth of the deepest internal node: a row whose u lies at depth d forms d path messages
+	for (int i = 0; i < nops; i++) {
+		const int x = e->spr_ops[nops + i].node;
+		depth[e->left[x]] = depth[e->right[x]] = depth[x] + 1;
+		slots = std::max(slots, (size_t)depth[x]);
+	}
+	const int nblk = (P + CLASSSPR_BLOCK - 1) / CLASSSPR_BLOCK;
+	const size_t npd = node_partial_doubles(e), stride = (size_t)nops + slots;
+	const ScratchPlan plan = spr_gen_plan(e, slots, (size_t)nblk);
+	std::vector<double> half(N);
+	for (int n = 0; n < N; n++) half[n] = 0.5 * e->lengths[n];
+	std::vector<ClassSprOp> ops;
+	std::vector<int32_t> op_counts, cand_of;
+	std::vector<ClassSprCand> cands;
+	std::vector<const double *> path(N, nullptr);
+	std::vector<double> out;
+	for (size_t first = 0; first < live.size();) {
+		const size_t rows = std::min(batch_items_that_fit(e, live.size() - first, plan), live.size() - first);
+		if (rows < 1)
+			return fail(PHYAMD_EUNSUPPORTED, "%s: the scratch of one row (%zu bytes: the pruned tree's upper of every internal node and the path messages) does not fit the memory budget",
+			            call.name, plan.item_bytes());
+		if ((rc = ensure_batch_scratch(e, rows, plan))) return rc;
+		ops.assign(rows * stride, ClassSprOp{});
+		op_counts.resize(rows);
+		cands.clear();
+		cand_of.resize(rows * N);
+		for (size_t r = 0; r < rows; r++) {
+			const int32_t i = live[first + r];
+			op_counts[r] = build_spr_gen_row(e, prune ? prune[i] : i, e->d_sprg_work.get() + r * stride * npd, path, ops.data() + r * stride, &cands, cand_of.data() + r * N);
+		}
+		HIP_TRY(hipMemcpyAsync(e->d_sprg_ops, ops.data(), sizeof(ClassSprOp) * ops.size(), hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_sprg_nops, op_counts.data(), sizeof(int32_t) * rows, hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_sprg_cands, cands.data(), sizeof(ClassSprCand) * cands.size(), hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_spr_cand_of, cand_of.data(), sizeof(int32_t) * cand_of.size(), hipMemcpyHostToDevice, e->stream));
+		// half the engine's lengths: their matrices through the engine's own matrix kernel, and the images
+		HIP_TRY(hipMemcpyAsync(e->d_placeg_len, half.data(), sizeof(double) * N, hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemsetAsync(e->d_placeg_zero, 0, N, e->stream));
+		{
+			const size_t total = (size_t)N * C * PLACE_GEN_STATES * PLACE_GEN_STATES;
+			hipLaunchKernelGGL(k_transition_matrices, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, e->stream, PLACE_GEN_STATES, C, N, e->d_model.get(),
+			                   e->d_rates.get(), e->d_placeg_len.get(), e->d_placeg_zero.get(), -1, e->d_placeg_mats.get(), e->d_placeg_dmats.get());
+		}
+		build_matrix_images(e, N * C, e->d_placeg_mats, e->d_placeg_imgs);
+		const ClassSprWalkArgs walk{e->d_sprg_ops.get(), e->d_sprg_nops.get(), (int)stride, P, e->Pp, C, e->d_tipmask, e->d_tipsets, e->d_imgs};
+		hipLaunchKernelGGL(k_classspr_walk, dim3((unsigned)nblk, (unsigned)rows), dim3(GenGeo<2>::WAVES * 64), 0, e->stream, walk);
+		for (size_t c0 = 0; c0 < cands.size(); c0 += BATCH_MAX_CHUNK) {  // (gridDim.y)
+			const size_t n = std::min<size_t>(cands.size() - c0, BATCH_MAX_CHUNK);
+			const ClassSprArgs a{e->d_sprg_cands.get() + c0, P, e->Pp, C, e->d_tipmask, e->d_tipsets, e->d_freqs, e->d_props, e->d_weights, e->d_imgs, e->d_placeg_imgs,
+			                     e->d_spr_slab.get() + c0 * nblk};
+			hipLaunchKernelGGL(k_classspr, dim3((unsigned)nblk, (unsigned)n), dim3(GenGeo<2>::WAVES * 64), 0, e->stream, a);
+		}
+		const size_t cells = rows * N;
+		hipLaunchKernelGGL(k_spr_finish, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, e->stream, cells, nblk, e->d_spr_cand_of.get(), e->d_spr_slab.get(),
+		                   e->d_spr_out.get());
+		HIP_TRY(hipGetLastError());
+		out.resize(cells);
+		HIP_TRY(hipMemcpyAsync(out.data(), e->d_spr_out, sizeof(double) * cells, hipMemcpyDeviceToHost, e->stream));
+		HIP_TRY(hipStreamSynchronize(e->stream));  // (also covers the lists, which the next chunk builds anew)
+		for (size_t r = 0; r < rows; r++) std::copy(out.begin() + r * N, out.begin() + (r + 1) * N, lnl + (size_t)live[first + r] * N);
+		prof.chunks++;
+		prof.candidates += (int64_t)cands.size();
+		first += rows;
+	}
+	return PHYAMD_OK;
+}
+
+int shard_spr_general(Shard *e, int flags, int32_t count, const int32_t *prune, double *lnl) {
+	CHECK_ENGINE(e);
+	return profiled_call(e, &Shard::spr_prof, phyamd_spr_profile{}, [&](phyamd_spr_profile &prof) { return run_spr_general(e, flags, count, prune, lnl, prof); });
 }
 
 // ---- the three graft branches of every SPR regraft, optimised (phyamd_spr_optimize) ----------------------------------------------

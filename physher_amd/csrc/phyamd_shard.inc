@@ -223,7 +223,7 @@ struct Shard {
 	DeviceArray<BatchOp> d_batch_item_ops{&batch_mem};  // [item][post-order T - 1 | pre-order T - 1]
 	DeviceArray<int32_t> d_batch_roots{&batch_mem};     // [item]
 	// what the scratch holds: every call describes what it needs as a ScratchPlan (phyamd_queries.inc: batch_plan, reweight_plan,
-	// nni_base_plan with nni_plan and cbopt_plan, nni_gen_plan, classcb_plan, blopt_plan, spr_plan with tripod_plan, pairdist_plan, bhess_plan, sitelnl_plan; phyamd_place_calls.inc: place_plan,
+	// nni_base_plan with nni_plan and cbopt_plan, nni_gen_plan, classcb_plan, blopt_plan, spr_plan with tripod_plan, spr_gen_plan, pairdist_plan, bhess_plan, sitelnl_plan; phyamd_place_calls.inc: place_plan,
 	// place_gen_plan, qopt_plan, qopt_gen_plan) and gets at least that, so a call of one kind
 	// never runs in the scratch of another with too few upper slots or without its lists.  batch_held: the plan the arrays were last
 	// allocated by, for batch_items items (the Hessian's arrays, grown beside it, are judged by their sizes alone)
@@ -342,6 +342,15 @@ struct Shard {
 	DeviceArray<double> d_classcb_K{&batch_mem};          // [candidate][3][C][20][Pp]
 	DeviceArray<double> d_classcb_out{&batch_mem};        // [candidate][3][t*, lnL, d1, d2]
 	DeviceArray<int32_t> d_classcb_iter{&batch_mem};      // [candidate][3]
+	// phyamd_spr_log_likelihoods_general (phyamd_spr_gen.inc) reads the resident lowers and walks, per prune node of a chunk (a ROW),
+	// the messages and uppers that pruning changes into the row's own planes.  It shares the 4-state SPR call's candidate index, slab
+	// (blocks of 128 patterns) and result (d_spr_cand_of, d_spr_slab, d_spr_out) and host lists (spr_ops' pre-order, spr_tin, spr_tout),
+	// and the placement call's lengths, matrices and images for the half lengths (d_placeg_len, _zero, _mats, _dmats, _imgs); it
+	// adds the rows' ops, their counts, candidates and planes.  spr_prof keeps the last SPR scoring call of either kind
+	DeviceArray<ClassSprOp> d_sprg_ops{&batch_mem};       // [row][T - 1 + path slots]
+	DeviceArray<int32_t> d_sprg_nops{&batch_mem};         // [row]
+	DeviceArray<ClassSprCand> d_sprg_cands{&batch_mem};   // [row][at most N], the rows' candidates one after the other
+	DeviceArray<double> d_sprg_work{&batch_mem};          // [row][T - 1 uppers by internal node | path slots][C][20][Pp]
 	// phyamd_state_posteriors / phyamd_site_rate_posteriors (phyamd_post.inc): the rows of a chunk, their staged results -- [rows][P][S]
 	// posteriors and [rows][P] states, or [P][C] + [P] site rates -- and, 20 / 60 / 61 states, each row's own partial p_n (true_lower_gen).
 	// On demand, like d_branch: the calls read what the keep-partials gradient left and have no entry in the record above

@@ -384,6 +384,18 @@ class Engine:
         row of the root and of its children (re-root to reach those moves).  lnL only, at that fixed assignment: spr_optimize
         optimises the three branches at the graft point of every candidate.
         The engine's tree, lengths and partials stay.  No fallback: EngineError where gradient_batch_trees refuses."""
+        return self._spr_log_likelihoods(self._lib.phyamd_spr_log_likelihoods, prune, flags)
+
+    def spr_log_likelihoods_general(self, prune=None, flags=0):
+        """spr_log_likelihoods for an engine of 20 states: lnl [count, N] in that method's rows and columns, by its move and its
+        candidate rule; an entry is the engine's own log_likelihood() of the rearranged tree.  The messages and uppers that
+        pruning changes are walked per row from the resident lower partials: afterwards the engine is one with
+        set_keep_partials(True) that has run gradient(); its tree, lengths and models stay.  A candidate whose lnL is not finite
+        reports it in band.  No fallback: EngineError for a state count other than 20, more than 8 categories, flags, tiled
+        patterns, explicit matrices, a rescaling or a sharded engine, and a row whose scratch does not fit the memory cap."""
+        return self._spr_log_likelihoods(self._lib.phyamd_spr_log_likelihoods_general, prune, flags)
+
+    def _spr_log_likelihoods(self, call, prune, flags):
         pr = None
         if prune is not None:
             pr = np.ascontiguousarray(prune, dtype=np.int32)
@@ -391,11 +403,11 @@ class Engine:
                 raise ValueError(f"prune must be one-dimensional (got {pr.shape})")
         count = self.N if pr is None else len(pr)
         lnl = np.empty((count, self.N))
-        self._check(self._lib.phyamd_spr_log_likelihoods(self._h, flags, count, None if pr is None else _ptr(pr), _ptr(lnl)))
+        self._check(call(self._h, flags, count, None if pr is None else _ptr(pr), _ptr(lnl)))
         return lnl
 
     def spr_profile(self):
-        """Of the last spr_log_likelihoods: prunes (rows), chunks, candidates, scratch_bytes, ms."""
+        """Of the last spr_log_likelihoods or spr_log_likelihoods_general: prunes (rows), chunks, candidates, scratch_bytes, ms."""
         p = _lib.SprProfile()
         self._check(self._lib.phyamd_get_spr_profile(self._h, C.byref(p)))
         return {k: getattr(p, k) for k, _ in p._fields_}
