@@ -358,6 +358,11 @@ class TreeLikelihoodInterface : public CallableModelInterface {
 	// engine's branch lengths, as for NNILogLikelihoods.  The tree model and this object's own state are unchanged.
 	void SPROptimize(const int *prune, int count, double lower, double upper, double tolerance, int maxIterations, double lnlTolerance, int maxPasses, double *lengths,
 	                 double *logLikelihoods, double *initialLogLikelihoods, int32_t *passes);
+	// The same for a model of 20 states (one phyamd_spr_optimize_general call; see include/physher_amd.h): the arguments and arrays are
+	// SPROptimize's, the rows, columns and candidates SPRLogLikelihoodsGeneral's.  The call reads the engine's resident partials, which
+	// it makes resident if they are not; the tree model and this object's own state are unchanged.
+	void SPROptimizeGeneral(const int *prune, int count, double lower, double upper, double tolerance, int maxIterations, double lnlTolerance, int maxPasses,
+	                        double *lengths, double *logLikelihoods, double *initialLogLikelihoods, int32_t *passes);
 	// Beyond the reference surface: the maximum-likelihood distance of `count` pairs of taxa under this object's own models, before
 	// any tree is scored (one phyamd_pairwise_distances call; see include/physher_amd.h for the definition and the rule): pairs
 	// [count][2] holds two tip ids of the tree model each (null: count = T(T-1)/2, all i < j row-major); start [count] may be null

@@ -792,7 +792,7 @@ int phyamd_spr_optimize(phyamd_engine *e, int flags, int32_t count, const int32_
                         double lnl_tolerance, int32_t max_passes,
                         double *lengths /* [count][2T-1][3]: t_p, t_w, t_u */, double *lnl /* [count][2T-1] */,
                         double *initial_lnl /* [count][2T-1] or NULL */, int32_t *passes /* [count][2T-1] or NULL */);
-/* of the last phyamd_spr_optimize: rows asked for, chunks of rows they ran in, candidates optimised, visits made and proposals made
+/* of the last phyamd_spr_optimize or phyamd_spr_optimize_general: rows asked for, chunks of rows they ran in, candidates optimised, visits made and proposals made
  * over all of them, bytes of batch scratch the engine holds (see phyamd_batch_profile), wall time of the call */
 typedef struct { int32_t prunes, chunks; int64_t candidates, visits, iterations, scratch_bytes; double ms; } phyamd_spr_optimize_profile;
 int phyamd_get_spr_optimize_profile(phyamd_engine *e, phyamd_spr_optimize_profile *out);
@@ -1181,6 +1181,71 @@ int phyamd_nni_optimize_general(phyamd_engine *e, int flags, const double *start
  * last call of either kind. */
 int phyamd_spr_log_likelihoods_general(phyamd_engine *e, int flags, int32_t count, const int32_t *prune /* [count] or NULL */,
                                        double *lnl /* [count][2T-1] */);
+/* phyamd_spr_optimize for an engine of 20 states (proteins): the three branches that meet at the graft point of every SPR regraft
+ * of chosen subtrees optimised in one call -- what a likelihood SPR search compares after it has scored the regrafts.  The route this
+ * replaces is a second engine looped over the O(T^2) rearranged trees with the rule on the host through
+ * phyamd_branch_log_likelihood: one walk and one host round trip per iterate.
+ * THE DEFINITION, in full.  Rows, columns, candidates and the rearranged tree are phyamd_spr_log_likelihoods_general's: row i belongs
+ * to the prune node p = prune[i] (prune == NULL: count must be 2T-1 and row i is node i), column w is the target edge, named by the
+ * node below it; with u = parent(p), s = sibling(p), g = parent(u), x = parent(w) the rearranged tree is (node ids kept)
+ *   g's child slot that held u now holds s, with t'_s = t_s + t_u;
+ *   x's child slot that held w now holds u;
+ *   u keeps p in its slot and gets w in the slot s had;
+ * everything else unchanged.  Column w is a CANDIDATE unless w is the root, u, s, p or a descendant of p.  Per cell lengths holds
+ * (t_p, t_w, t_u), lnl the log-likelihood there, initial_lnl that of the start and passes the pass count; a cell that is no candidate
+ * is NaN in lengths, lnl and initial_lnl and 0 in passes, and a row whose p is the root or a child of the root is all NaN.
+ * Duplicates in prune are allowed.  initial_lnl and passes may be NULL.
+ * THE RULE.  The state is (t_p, t_w, t_u), at the start (t_p, 0.5 t_w, 0.5 t_w) of the engine's lengths.  lnl_0 is lnL of the
+ * rearranged tree at the start with the lengths as they are given (not clamped), which initial_lnl reports: up to rounding
+ * phyamd_spr_log_likelihoods_general's entry.
+ *   A pass visits u's left child, u's right child, then u; in the rearranged tree p keeps its slot and w has the slot s had.  All
+ * three branches are always visited.
+ *   A visit of branch z: f(t) = (lnL, d1, d2) of the rearranged tree with t_z = t and the other two lengths as they stand now, d1 and
+ * d2 the first and second derivative of lnL in t_z.  t0 = clamp(t_z, lower, upper).  t' comes from phyamd_nni_optimize's rule started
+ * at t0: t = t0, a = lower, b = upper; each iteration evaluates d1(t) and d2(t); if d1 > 0 then a = t, else b = t; it proposes
+ * t' = t - d1 / d2 when d2 < 0 and a < t' < b, otherwise t' = (a + b) / 2; it stops when |t' - t| <= tolerance or after
+ * max_iterations proposals.  The visit accepts t_z = t' when lnL(t') is finite and lnL(t') >= lnL(t0); otherwise t_z = t0.  So lnL
+ * never falls from visit to visit.
+ *   After pass k, lnl_k is lnL at the current lengths.  The entry stops after pass k when lnl_k - lnl_(k-1) <= lnl_tolerance, with
+ * passes = k; after max_passes passes without that, with passes = -max_passes.
+ *   A lnL that is not finite at an iterate (one of the t whose d1 and d2 the iteration evaluates, t0 among them; some pattern's site
+ * likelihood is not in (0, inf): underflow, the call does not rescale) ends the entry in band: lengths is the state before that
+ * visit, lnl the value that is not finite, passes the negated index of the pass (from 1).
+ * THE MODEL.  The two branches a visit holds enter as P(t r_c) = |V e^(lambda t r_c) V^-1| elementwise, the engine's own matrix
+ * arithmetic; the visited branch enters through the eigen sum sum_c sum_e K[c][e] exp(lambda_e r_c t) without the |.| (a rounding
+ * difference); the sibling's merged branch enters as P(t_u r_c) P(t_s r_c), not as the matrix of the summed length (a rounding
+ * difference, as in phyamd_spr_log_likelihoods_general).
+ * The tree side is read from resident partials, exactly as in phyamd_spr_log_likelihoods_general: THE ENGINE IS AFTERWARDS ONE WITH
+ * phyamd_set_keep_partials(1) THAT HAS RUN THE FLAGS-0 GRADIENT; its topology, lengths and models are unchanged, and later
+ * evaluations return the bits such an engine returns without the call.  Only LOWER partials are read, so a
+ * PHYAMD_GRAD_FOLD_ROOT_FREQS gradient changes nothing.  After the scoring call's walk per row, three vectors meet at u and none
+ * depends on the three lengths: A, p's own partial; B, w's own partial in the pruned tree; F = pi o U, U the scoring call's
+ * (x is the root ? 1 : P_x u'_x) o m'_y.  With K = w_c (V^T F)_e (V^-1 [(P(t_w) B) o (P(t_p) A)])_e for u,
+ * w_c (V^T [(P(t_u)^T F) o (P(t_p) A)])_e (V^-1 B)_e for w and the same with A and B exchanged for p, one workgroup runs an entry's
+ * whole rule: a visit forms K with four 20-wide products on the fp64 matrix cores per (category, 16 patterns), an iterate costs
+ * C x 20 exponentials and a pass over K, and nothing is walked, launched or sent to the host per visit.  Two calls return identical
+ * bits; an entry's bits depend on the engine's inputs and on (p, w) alone -- not on count, the row's position in prune, the other
+ * rows, the chunks the rows ran in, the optional outputs or what the batch scratch held.  Nothing is added with atomics.  The engine
+ * is never switched to rescaling by the call's own kernels.
+ * The scratch is the batch scratch's, counted and released like it.  With npd = C x 20 x Pp doubles (Pp the patterns rounded up to
+ * 16), D the depth of the deepest internal node and N = 2T-1: per row 8 npd (T - 1 + 2 D + 2 N) bytes -- the scoring call's T - 1
+ * uppers and D path messages, D own partials of path nodes, and pi o U and K of at most N candidates -- and 64 (T - 1 + D) + 4 bytes of
+ * ops, 56 D of own-partial records, and per node 64 + 32 bytes of candidate records, 4 of index, 24 of start and 40 + 16 + 40 + 12 of
+ * results; beside the rows 8 npd (T - 1) bytes, every internal node's own partial, and 56 (T - 1) of records.  Rows that do not fit
+ * the memory cap together run in chunks of rows, with the same bits.
+ * PHYAMD_EINVAL (the arguments are checked before the handle's state is looked at): null engine, lengths or lnl; count < 1; prune ==
+ * NULL with another count than 2T-1; an id outside 0..2T-2 (with its index in the message); no eigen system; bounds that are not
+ * 0 <= lower < upper < inf; a tolerance that is not finite and positive; max_iterations outside 1..1000; an lnl_tolerance that is
+ * negative or not finite; max_passes outside 1..1000; an engine that is not ready to evaluate.  There is no fallback path:
+ * PHYAMD_EUNSUPPORTED, naming the function and the condition: a state count other than 20 (4: use phyamd_spr_optimize; 60 / 61: not
+ * built), more than 8 categories, flags other than 0, tiled patterns, explicit node matrices, an engine that is rescaling -- also
+ * when PHYAMD_RESCALE_AUTO switched it on during the call's own evaluation --, a handle sharded over several devices, scratch of one
+ * row that does not fit the memory cap.  phyamd_get_spr_optimize_profile reports the last call of either kind. */
+int phyamd_spr_optimize_general(phyamd_engine *e, int flags, int32_t count, const int32_t *prune /* [count] or NULL */,
+                                double lower, double upper, double tolerance, int32_t max_iterations,
+                                double lnl_tolerance, int32_t max_passes,
+                                double *lengths /* [count][2T-1][3]: t_p, t_w, t_u */, double *lnl /* [count][2T-1] */,
+                                double *initial_lnl /* [count][2T-1] or NULL */, int32_t *passes /* [count][2T-1] or NULL */);
 
 #ifdef __cplusplus
 }

@@ -159,6 +159,7 @@ SYMBOLS = [
     ("phyamd_spr_log_likelihoods_general", C.c_int, [_P, C.c_int, C.c_int32, _P, _P]),
     ("phyamd_get_spr_profile", C.c_int, [_P, C.POINTER(SprProfile)]),
     ("phyamd_spr_optimize", C.c_int, [_P, C.c_int, C.c_int32, _P, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32, _P, _P, _P, _P]),
+    ("phyamd_spr_optimize_general", C.c_int, [_P, C.c_int, C.c_int32, _P, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32, _P, _P, _P, _P]),
     ("phyamd_get_spr_optimize_profile", C.c_int, [_P, C.POINTER(SprOptimizeProfile)]),
     ("phyamd_pairwise_distances", C.c_int, [_P, C.c_int, C.c_int32, _P, _P, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P, _P, _P, _P, _P]),
     ("phyamd_pairwise_distances_general", C.c_int, [_P, C.c_int, C.c_int32, _P, _P, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),

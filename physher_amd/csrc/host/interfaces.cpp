@@ -992,6 +992,14 @@ void TreeLikelihoodInterface::SPROptimize(const int *prune, int count, double lo
 	                                  initialLogLikelihoods, passes));
 }
 
+void TreeLikelihoodInterface::SPROptimizeGeneral(const int *prune, int count, double lower, double upper, double tolerance, int maxIterations, double lnlTolerance,
+                                                 int maxPasses, double *lengths, double *logLikelihoods, double *initialLogLikelihoods, int32_t *passes) {
+	if (!lengths || !logLikelihoods) throw Error("null lengths or logLikelihoods");
+	Sync();
+	phyamd::check(phyamd_spr_optimize_general(impl_->engine, 0, count, prune, lower, upper, tolerance, maxIterations, lnlTolerance, maxPasses, lengths, logLikelihoods,
+	                                          initialLogLikelihoods, passes));
+}
+
 void TreeLikelihoodInterface::PairwiseDistances(const int *pairs, int count, const double *start, double lower, double upper, double tolerance, int maxIterations,
                                                 double *distances, double *logLikelihoods, double *d1, double *d2, int32_t *iterations, double *counts) {
 	if (!distances && !counts) throw Error("null distances and counts");

@@ -332,6 +332,19 @@ PYBIND11_MODULE(_phycpp_amd, m) {
 		    return py::make_tuple(darray({count, N, (py::ssize_t)3}, len.data()), darray(shape, lnl.data()), darray(shape, lnl0.data()), iarray(shape, passes.data()));
 	    }, py::arg("prune") = py::none(), py::arg("lower") = 1e-8, py::arg("upper") = 10.0, py::arg("tolerance") = 1e-8, py::arg("max_iterations") = 100,
 	       py::arg("lnl_tolerance") = 1e-6, py::arg("max_passes") = 50)
+	    .def("spr_optimize_general", [](TreeLikelihoodInterface &self, std::optional<iarray> prune, double lower, double upper, double tolerance, int max_iterations,
+	                                    double lnl_tolerance, int max_passes) -> py::tuple {
+		    const py::ssize_t N = (py::ssize_t)self.NodeCount();
+		    if (prune && prune->ndim() != 1) throw phyamd::Error("prune: [count]");
+		    const py::ssize_t count = prune ? prune->shape(0) : N;
+		    std::vector<double> len((size_t)count * N * 3), lnl((size_t)count * N), lnl0(lnl.size());
+		    std::vector<int32_t> passes(lnl.size());
+		    self.SPROptimizeGeneral(prune ? prune->data() : nullptr, (int)count, lower, upper, tolerance, max_iterations, lnl_tolerance, max_passes, len.data(), lnl.data(),
+		                            lnl0.data(), passes.data());
+		    const std::vector<py::ssize_t> shape{count, N};
+		    return py::make_tuple(darray({count, N, (py::ssize_t)3}, len.data()), darray(shape, lnl.data()), darray(shape, lnl0.data()), iarray(shape, passes.data()));
+	    }, py::arg("prune") = py::none(), py::arg("lower") = 1e-8, py::arg("upper") = 10.0, py::arg("tolerance") = 1e-8, py::arg("max_iterations") = 100,
+	       py::arg("lnl_tolerance") = 1e-6, py::arg("max_passes") = 50)
 	    .def("pairwise_distances", [](TreeLikelihoodInterface &self, std::optional<iarray> pairs, std::optional<darray> start, double lower, double upper, double tolerance,
 	                                  int max_iterations, bool want_counts, bool counts_only) -> py::tuple {
 		    const py::ssize_t T = ((py::ssize_t)self.NodeCount() + 1) / 2;

@@ -731,6 +731,24 @@ int phyamd_spr_optimize(phyamd_engine *g, int flags, int32_t count, const int32_
 	                          SprOptimizeArgs{count, prune, lower, upper, tolerance, max_iterations, lnl_tolerance, max_passes, lengths, lnl, initial_lnl, passes});
 }
 
+// one device only: the call reads one engine's resident partials
+int phyamd_spr_optimize_general(phyamd_engine *g, int flags, int32_t count, const int32_t *prune, double lower, double upper, double tolerance, int32_t max_iterations,
+                                double lnl_tolerance, int32_t max_passes, double *lengths, double *lnl, double *initial_lnl, int32_t *passes) {
+	static const char *const name = "phyamd_spr_optimize_general";
+	if (count < 1) return fail(PHYAMD_EINVAL, "%s: count must be >= 1 (got %d)", name, count);
+	if (!lengths || !lnl) return fail(PHYAMD_EINVAL, "%s: null %s", name, !lengths ? "lengths" : "lnl");
+	if (!g || g->shards.empty()) return fail(PHYAMD_EINVAL, "%s: null engine", name);
+	if (!(lower >= 0.0 && lower < upper && std::isfinite(upper))) return fail(PHYAMD_EINVAL, "%s: bounds [%g, %g]: they must be 0 <= lower < upper < inf", name, lower, upper);
+	if (!(tolerance > 0.0 && std::isfinite(tolerance))) return fail(PHYAMD_EINVAL, "%s: tolerance %g: it must be finite and positive", name, tolerance);
+	if (max_iterations < 1 || max_iterations > 1000) return fail(PHYAMD_EINVAL, "%s: max_iterations %d is outside 1..1000", name, max_iterations);
+	if (!(lnl_tolerance >= 0.0 && std::isfinite(lnl_tolerance))) return fail(PHYAMD_EINVAL, "%s: lnl_tolerance %g: it must be finite and not negative", name, lnl_tolerance);
+	if (max_passes < 1 || max_passes > 1000) return fail(PHYAMD_EINVAL, "%s: max_passes %d is outside 1..1000", name, max_passes);
+	if (group_size(g) > 1)
+		return fail(PHYAMD_EUNSUPPORTED, "%s: a handle sharded over several devices is out of scope: the call reads one engine's resident partials (use one device)", name);
+	return shard_spr_optimize_general(g->shards[0], flags,
+	                                  SprOptimizeArgs{count, prune, lower, upper, tolerance, max_iterations, lnl_tolerance, max_passes, lengths, lnl, initial_lnl, passes});
+}
+
 int phyamd_get_spr_optimize_profile(phyamd_engine *g, phyamd_spr_optimize_profile *out) {
 	return merged_profile(g, &Shard::tripod_prof, out, [](phyamd_spr_optimize_profile &, const phyamd_spr_optimize_profile &) {});  // (never sharded)
 }

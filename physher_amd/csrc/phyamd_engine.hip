@@ -124,6 +124,7 @@ constexpr double SCALING_THRESHOLD = 1.0e-40;  // treelikelihood.c:1121
 #include "phyamd_qopt4.inc"
 #include "phyamd_qopt_gen.inc"
 #include "phyamd_nniopt_gen.inc"
+#include "phyamd_graft_gen.inc"
 
 #include "phyamd_shard.inc"
 

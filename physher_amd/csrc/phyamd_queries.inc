@@ -217,6 +217,7 @@ int ensure_batch_scratch(Shard *e, size_t items, const ScratchPlan &plan) {
 		ScratchPlan both = plan;
 		both.merge(e->batch_held);
 		if (allocate_batch_scratch(e, items, both) == PHYAMD_OK) return PHYAMD_OK;
+		(void)hipGetLastError();  // (the attempt's out-of-memory is not the call's: a later hipGetLastError() of the call would report it)
 	}
 	return allocate_batch_scratch(e, items, plan);
 }
@@ -1408,26 +1409,37 @@ int build_spr_gen_row(const Shard *e, int p, double *work, std::vector<const dou
 	return count;
 }
 
-// lnl [count][N] (host): every row walked from the resident lowers into its own planes, every candidate of the chunk in one launch.
-// Writes only the batch scratch beyond the evaluation that made the partials resident
-int run_spr_general(Shard *e, int flags, int32_t count, const int32_t *prune, double *lnl, phyamd_spr_profile &prof) {
-	static const GeneralQueryCall call{"phyamd_spr_log_likelihoods_general", "the kernels are", "phyamd_spr_log_likelihoods", "64-wide products are",
-	                                   "which have no half-length counterpart", "the half-length matrices are", "kernels do"};
+// the preconditions of the two 20-state SPR calls up to the prune list, and every partial resident
+int check_spr_general_call(Shard *e, const GeneralQueryCall &call, int flags, int32_t count, const int32_t *prune, std::vector<int32_t> &live) {
 	int rc;
 	if ((rc = check_general_query_inputs(e, call, flags))) {
 		if (g_last_error.find(call.name) != std::string::npos) return rc;
 		const std::string why = g_last_error;  // (an engine that is not ready: check_ready's words, which name no call)
 		return fail(rc, "%s: %s", call.name, why.c_str());
 	}
-	std::vector<int32_t> live;
 	if ((rc = check_prune_list(e, call.name, count, prune, live))) return rc;
-	if ((rc = check_general_query_resident(e, call))) return rc;
+	return check_general_query_resident(e, call);
+}
+
+// a chunk of rows of the two 20-state SPR calls, walked: the rows live[first .. first + rows), a row's planes `stride` apart in
+// d_sprg_work (T - 1 uppers, then `slots` path messages), the rows' candidates one after the other and their index by cell
+struct SprGenChunk {
+	size_t first, rows, slots, stride;
+	int nblk;
+	const std::vector<ClassSprCand> *cands;
+	const std::vector<int32_t> *cand_of;  // [rows][N]
+};
+
+// the live rows in chunks of what the scratch holds of plan_of(slots, nblk); per chunk the rows' lists built (build_spr_gen_row) and
+// sent, halves: the matrices and images of half the engine's lengths, and k_classspr_walk, then body(chunk) -- which ends with the
+// stream synchronised, since the next chunk builds the lists anew.  row_holds: what a row's scratch is, for the refusal
+template <typename PlanOf, typename Body>
+int for_spr_gen_row_chunks(Shard *e, const char *name, const char *row_holds, const std::vector<int32_t> &live, const int32_t *prune, bool halves, const PlanOf &plan_of,
+                           const Body &body) {
 	const int T = e->T, N = e->N, C = e->C, P = e->P, nops = T - 1;
-	std::fill(lnl, lnl + (size_t)count * N, NAN);
-	prof.prunes = count;
-	if (live.empty()) return PHYAMD_OK;
+	int rc;
 	for (int n = T; n < N; n++)
-		if (n != e->root && e->sched.core_index[n] < 0) return fail(PHYAMD_EDEVICE, "%s: node %d has no resident lower partial", call.name, n);
+		if (n != e->root && e->sched.core_index[n] < 0) return fail(PHYAMD_EDEVICE, "%s: node %d has no resident lower partial", name, n);
 	ensure_spr_lists(e);
 	std::vector<int32_t> depth(N, 0);
 	size_t slots = 1;  // the depth of the deepest internal node: a row whose u lies at depth d forms d path messages
@@ -1438,19 +1450,16 @@ int run_spr_general(Shard *e, int flags, int32_t count, const int32_t *prune, do
 	}
 	const int nblk = (P + CLASSSPR_BLOCK - 1) / CLASSSPR_BLOCK;
 	const size_t npd = node_partial_doubles(e), stride = (size_t)nops + slots;
-	const ScratchPlan plan = spr_gen_plan(e, slots, (size_t)nblk);
+	const ScratchPlan plan = plan_of(slots, (size_t)nblk);
 	std::vector<double> half(N);
 	for (int n = 0; n < N; n++) half[n] = 0.5 * e->lengths[n];
 	std::vector<ClassSprOp> ops;
 	std::vector<int32_t> op_counts, cand_of;
 	std::vector<ClassSprCand> cands;
 	std::vector<const double *> path(N, nullptr);
-	std::vector<double> out;
 	for (size_t first = 0; first < live.size();) {
 		const size_t rows = std::min(batch_items_that_fit(e, live.size() - first, plan), live.size() - first);
-		if (rows < 1)
-			return fail(PHYAMD_EUNSUPPORTED, "%s: the scratch of one row (%zu bytes: the pruned tree's upper of every internal node and the path messages) does not fit the memory budget",
-			            call.name, plan.item_bytes());
+		if (rows < 1) return fail(PHYAMD_EUNSUPPORTED, "%s: the scratch of one row (%zu bytes: %s) does not fit the memory budget", name, plan.item_bytes(), row_holds);
 		if ((rc = ensure_batch_scratch(e, rows, plan))) return rc;
 		ops.assign(rows * stride, ClassSprOp{});
 		op_counts.resize(rows);
@@ -1464,36 +1473,59 @@ int run_spr_general(Shard *e, int flags, int32_t count, const int32_t *prune, do
 		HIP_TRY(hipMemcpyAsync(e->d_sprg_nops, op_counts.data(), sizeof(int32_t) * rows, hipMemcpyHostToDevice, e->stream));
 		HIP_TRY(hipMemcpyAsync(e->d_sprg_cands, cands.data(), sizeof(ClassSprCand) * cands.size(), hipMemcpyHostToDevice, e->stream));
 		HIP_TRY(hipMemcpyAsync(e->d_spr_cand_of, cand_of.data(), sizeof(int32_t) * cand_of.size(), hipMemcpyHostToDevice, e->stream));
-		// half the engine's lengths: their matrices through the engine's own matrix kernel, and the images
-		HIP_TRY(hipMemcpyAsync(e->d_placeg_len, half.data(), sizeof(double) * N, hipMemcpyHostToDevice, e->stream));
-		HIP_TRY(hipMemsetAsync(e->d_placeg_zero, 0, N, e->stream));
-		{
+		if (halves) {  // half the engine's lengths: their matrices through the engine's own matrix kernel, and the images
+			HIP_TRY(hipMemcpyAsync(e->d_placeg_len, half.data(), sizeof(double) * N, hipMemcpyHostToDevice, e->stream));
+			HIP_TRY(hipMemsetAsync(e->d_placeg_zero, 0, N, e->stream));
 			const size_t total = (size_t)N * C * PLACE_GEN_STATES * PLACE_GEN_STATES;
 			hipLaunchKernelGGL(k_transition_matrices, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, e->stream, PLACE_GEN_STATES, C, N, e->d_model.get(),
 			                   e->d_rates.get(), e->d_placeg_len.get(), e->d_placeg_zero.get(), -1, e->d_placeg_mats.get(), e->d_placeg_dmats.get());
+			build_matrix_images(e, N * C, e->d_placeg_mats, e->d_placeg_imgs);
 		}
-		build_matrix_images(e, N * C, e->d_placeg_mats, e->d_placeg_imgs);
 		const ClassSprWalkArgs walk{e->d_sprg_ops.get(), e->d_sprg_nops.get(), (int)stride, P, e->Pp, C, e->d_tipmask, e->d_tipsets, e->d_imgs};
 		hipLaunchKernelGGL(k_classspr_walk, dim3((unsigned)nblk, (unsigned)rows), dim3(GenGeo<2>::WAVES * 64), 0, e->stream, walk);
-		for (size_t c0 = 0; c0 < cands.size(); c0 += BATCH_MAX_CHUNK) {  // (gridDim.y)
-			const size_t n = std::min<size_t>(cands.size() - c0, BATCH_MAX_CHUNK);
-			const ClassSprArgs a{e->d_sprg_cands.get() + c0, P, e->Pp, C, e->d_tipmask, e->d_tipsets, e->d_freqs, e->d_props, e->d_weights, e->d_imgs, e->d_placeg_imgs,
-			                     e->d_spr_slab.get() + c0 * nblk};
-			hipLaunchKernelGGL(k_classspr, dim3((unsigned)nblk, (unsigned)n), dim3(GenGeo<2>::WAVES * 64), 0, e->stream, a);
-		}
-		const size_t cells = rows * N;
-		hipLaunchKernelGGL(k_spr_finish, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, e->stream, cells, nblk, e->d_spr_cand_of.get(), e->d_spr_slab.get(),
-		                   e->d_spr_out.get());
-		HIP_TRY(hipGetLastError());
-		out.resize(cells);
-		HIP_TRY(hipMemcpyAsync(out.data(), e->d_spr_out, sizeof(double) * cells, hipMemcpyDeviceToHost, e->stream));
-		HIP_TRY(hipStreamSynchronize(e->stream));  // (also covers the lists, which the next chunk builds anew)
-		for (size_t r = 0; r < rows; r++) std::copy(out.begin() + r * N, out.begin() + (r + 1) * N, lnl + (size_t)live[first + r] * N);
-		prof.chunks++;
-		prof.candidates += (int64_t)cands.size();
+		if ((rc = body(SprGenChunk{first, rows, slots, stride, nblk, &cands, &cand_of}))) return rc;
 		first += rows;
 	}
 	return PHYAMD_OK;
+}
+
+// lnl [count][N] (host): every row walked from the resident lowers into its own planes, every candidate of the chunk in one launch.
+// Writes only the batch scratch beyond the evaluation that made the partials resident
+int run_spr_general(Shard *e, int flags, int32_t count, const int32_t *prune, double *lnl, phyamd_spr_profile &prof) {
+	static const GeneralQueryCall call{"phyamd_spr_log_likelihoods_general", "the kernels are", "phyamd_spr_log_likelihoods", "64-wide products are",
+	                                   "which have no half-length counterpart", "the half-length matrices are", "kernels do"};
+	int rc;
+	std::vector<int32_t> live;
+	if ((rc = check_spr_general_call(e, call, flags, count, prune, live))) return rc;
+	const int N = e->N, C = e->C, P = e->P;
+	std::fill(lnl, lnl + (size_t)count * N, NAN);
+	prof.prunes = count;
+	if (live.empty()) return PHYAMD_OK;
+	std::vector<double> out;
+	return for_spr_gen_row_chunks(
+	    e, call.name, "the pruned tree's upper of every internal node and the path messages", live, prune, true,
+	    [e](size_t slots, size_t nblk) { return spr_gen_plan(e, slots, nblk); },
+	    [&](const SprGenChunk &k) -> int {
+		    const std::vector<ClassSprCand> &cands = *k.cands;
+		    const int nblk = k.nblk;
+		    for (size_t c0 = 0; c0 < cands.size(); c0 += BATCH_MAX_CHUNK) {  // (gridDim.y)
+			    const size_t n = std::min<size_t>(cands.size() - c0, BATCH_MAX_CHUNK);
+			    const ClassSprArgs a{e->d_sprg_cands.get() + c0, P, e->Pp, C, e->d_tipmask, e->d_tipsets, e->d_freqs, e->d_props, e->d_weights, e->d_imgs, e->d_placeg_imgs,
+			                         e->d_spr_slab.get() + c0 * nblk};
+			    hipLaunchKernelGGL(k_classspr, dim3((unsigned)nblk, (unsigned)n), dim3(GenGeo<2>::WAVES * 64), 0, e->stream, a);
+		    }
+		    const size_t cells = k.rows * N;
+		    hipLaunchKernelGGL(k_spr_finish, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, e->stream, cells, nblk, e->d_spr_cand_of.get(), e->d_spr_slab.get(),
+		                       e->d_spr_out.get());
+		    HIP_TRY(hipGetLastError());
+		    out.resize(cells);
+		    HIP_TRY(hipMemcpyAsync(out.data(), e->d_spr_out, sizeof(double) * cells, hipMemcpyDeviceToHost, e->stream));
+		    HIP_TRY(hipStreamSynchronize(e->stream));  // (also covers the lists, which the next chunk builds anew)
+		    for (size_t r = 0; r < k.rows; r++) std::copy(out.begin() + r * N, out.begin() + (r + 1) * N, lnl + (size_t)live[k.first + r] * N);
+		    prof.chunks++;
+		    prof.candidates += (int64_t)cands.size();
+		    return PHYAMD_OK;
+	    });
 }
 
 int shard_spr_general(Shard *e, int flags, int32_t count, const int32_t *prune, double *lnl) {
@@ -1591,6 +1623,151 @@ int run_spr_optimize(Shard *e, int flags, const SprOptimizeArgs &o, phyamd_spr_o
 int shard_spr_optimize(Shard *e, int flags, const SprOptimizeArgs &o) {
 	CHECK_ENGINE(e);
 	return profiled_call(e, &Shard::tripod_prof, phyamd_spr_optimize_profile{}, [&](phyamd_spr_optimize_profile &prof) { return run_spr_optimize(e, flags, o, prof); });
+}
+
+// ---- the three graft branches of every SPR regraft of a 20-state engine's tree, optimised (phyamd_spr_optimize_general) --------------
+
+// (phyamd_place_calls.inc, behind this file: what k_classplace_own forms a node's own partial from, and its launch)
+int place_own_of(Shard *e, const char *name, int node, double *out, PlaceGenOwn *own);
+
+// an item is a ROW: the scoring call's planes, ops, candidates and index by cell (spr_gen_plan's, without the slab, the result and
+// the half lengths); `slots` own partials of the path nodes above u and their records; and per candidate (at most N): its record,
+// its start, pi o U and the coefficients of the branch being visited -- a node's partial each --, the result and the status words;
+// per cell the scattered results and counts.  Whatever the row count: every internal node's own partial and its record.
+//   bytes = rows * [8 npd (T - 1 + 2 slots + 2 N) + lists] + 8 npd (T - 1) + records,   npd = C * 20 * Pp
+ScratchPlan classgraft_plan(Shard *e, size_t slots) {
+	const size_t D = sizeof(double), N = (size_t)e->N, internal = (size_t)(e->T - 1), ops = internal + slots, npd = node_partial_doubles(e);
+	ScratchPlan p;
+	p.add(e->d_sprg_work, D * ops * npd);
+	p.add(e->d_sprg_ops, sizeof(ClassSprOp) * ops);
+	p.add(e->d_sprg_nops, sizeof(int32_t));
+	p.add(e->d_sprg_cands, sizeof(ClassSprCand) * N);
+	p.add(e->d_spr_cand_of, sizeof(int32_t) * N);
+	p.add(e->d_graft_own, D * slots * npd, D * internal * npd);
+	p.add(e->d_placeg_owns, sizeof(PlaceGenOwn) * slots, sizeof(PlaceGenOwn) * internal);
+	p.add(e->d_graft_cands, sizeof(ClassGraftCand) * N);
+	p.add(e->d_qopt_start, D * N * 3);
+	p.add(e->d_graft_F, D * N * npd);
+	p.add(e->d_graft_K, D * N * npd);
+	p.add(e->d_tripod_res, D * N * 5);
+	p.add(e->d_tripod_status, sizeof(int32_t) * N * TRIPOD_STATUS);
+	p.add(e->d_tripod_out, D * N * 5);
+	p.add(e->d_tripod_counts, sizeof(int32_t) * N * 3);
+	return p;
+}
+
+// lengths [count][N][3], lnl, initial_lnl, passes [count][N] (host): the 20-state scoring call's rows and walk, then per chunk of rows
+// the own partials, pi o U of every candidate and one workgroup per candidate that runs its whole rule.  Writes only the batch
+// scratch beyond the evaluation that made the partials resident
+int run_spr_optimize_general(Shard *e, int flags, const SprOptimizeArgs &o, phyamd_spr_optimize_profile &prof) {
+	static const GeneralQueryCall call{"phyamd_spr_optimize_general", "the kernels are", "phyamd_spr_optimize", "64-wide products are",
+	                                   "which the solve cannot form at another length", "the likelihood in a branch length is", "solve does"};
+	int rc;
+	std::vector<int32_t> live;
+	if ((rc = check_spr_general_call(e, call, flags, o.count, o.prune, live))) return rc;
+	const int T = e->T, N = e->N, C = e->C, P = e->P, root = e->root, nops = T - 1;
+	const size_t all = (size_t)o.count * N, npd = node_partial_doubles(e);
+	std::fill(o.lengths, o.lengths + all * 3, NAN);
+	std::fill(o.lnl, o.lnl + all, NAN);
+	if (o.initial_lnl) std::fill(o.initial_lnl, o.initial_lnl + all, NAN);
+	if (o.passes) std::fill(o.passes, o.passes + all, 0);
+	prof.prunes = o.count;
+	if (live.empty()) return PHYAMD_OK;
+	std::vector<PlaceGenOwn> owns;
+	std::vector<ClassGraftCand> cands;
+	std::vector<double> start, out;
+	std::vector<int32_t> counts;
+	std::vector<const double *> own_on_path(N, nullptr);
+	return for_spr_gen_row_chunks(
+	    e, call.name, "the pruned tree's upper of every internal node, the path messages and own partials, and two planes per candidate", live, o.prune, false,
+	    [e](size_t slots, size_t) { return classgraft_plan(e, slots); },
+	    [&](const SprGenChunk &k) -> int {
+		    const std::vector<ClassSprCand> &scands = *k.cands;
+		    double *const own_all = e->d_graft_own.get(), *const own_rows = own_all + (size_t)nops * npd;
+		    const auto own_of = [&](int n) { return n < T ? (const double *)nullptr : own_all + (size_t)(n - T) * npd; };
+		    owns.clear(), cands.clear(), start.clear();
+		    for (int n = T; n < N; n++) {  // every internal node's own partial in the engine's tree (the root's is not read)
+			    if (n == root) continue;
+			    PlaceGenOwn own;
+			    if (int rc = place_own_of(e, call.name, n, own_all + (size_t)(n - T) * npd, &own)) return rc;
+			    owns.push_back(own);
+		    }
+		    for (size_t r = 0; r < k.rows; r++) {
+			    const int32_t i = live[k.first + r];
+			    const int p = o.prune ? o.prune[i] : i, u = e->sched.parent[p];
+			    // the path nodes above u: their own partial is the path message of the child below them times the other child's message
+			    const double *work = e->d_sprg_work.get() + r * k.stride * npd;
+			    std::vector<int> on_path;
+			    size_t slot = 0;
+			    for (int child = u, n = e->sched.parent[u]; n != root; child = n, n = e->sched.parent[n], slot++) {
+				    double *dst = own_rows + (r * k.slots + slot) * npd;
+				    PlaceGenOwn own;
+				    if (int rc = place_own_of(e, call.name, n, dst, &own)) return rc;
+				    const double *msg = work + ((size_t)nops + slot) * npd;  // build_spr_gen_row: the message of the path's slot-th node
+				    if (e->left[n] == child) own.src_l = msg, own.row_l = nullptr;
+				    else own.src_r = msg, own.row_r = nullptr;
+				    owns.push_back(own);
+				    own_on_path[n] = dst;
+				    on_path.push_back(n);
+			    }
+			    for (int w = 0; w < N; w++) {
+				    const int32_t ci = (*k.cand_of)[r * N + w];
+				    if (ci < 0) continue;
+				    if ((size_t)ci != cands.size() || scands[ci].w != w || scands[ci].p != p) return fail(PHYAMD_EDEVICE, "%s: the candidate lists are out of order", call.name);
+				    cands.push_back(ClassGraftCand{own_of(p), own_on_path[w] ? own_on_path[w] : own_of(w), p, w, e->left[u] == p ? 1 : 0, 0});
+				    start.push_back(e->lengths[p]);
+				    start.push_back(0.5 * e->lengths[w]);
+				    start.push_back(0.5 * e->lengths[w]);
+			    }
+			    for (const int n : on_path) own_on_path[n] = nullptr;
+		    }
+		    if (!owns.empty()) {
+			    HIP_TRY(hipMemcpyAsync(e->d_placeg_owns, owns.data(), sizeof(PlaceGenOwn) * owns.size(), hipMemcpyHostToDevice, e->stream));
+			    hipLaunchKernelGGL(k_classplace_own, dim3((unsigned)((P + 255) / 256), (unsigned)owns.size(), (unsigned)C), dim3(256), 0, e->stream, e->d_placeg_owns.get(), P, e->Pp,
+			                       e->d_tipsets.get());
+		    }
+		    HIP_TRY(hipMemcpyAsync(e->d_graft_cands, cands.data(), sizeof(ClassGraftCand) * cands.size(), hipMemcpyHostToDevice, e->stream));
+		    HIP_TRY(hipMemcpyAsync(e->d_qopt_start, start.data(), sizeof(double) * start.size(), hipMemcpyHostToDevice, e->stream));
+		    for (size_t c0 = 0; c0 < cands.size(); c0 += BATCH_MAX_CHUNK) {  // (gridDim.y)
+			    const size_t n = std::min<size_t>(cands.size() - c0, BATCH_MAX_CHUNK);
+			    const ClassGraftUpperArgs a{e->d_sprg_cands.get() + c0, P, e->Pp, C, e->d_tipmask, e->d_tipsets, e->d_freqs, e->d_imgs, e->d_graft_F.get() + c0 * npd};
+			    hipLaunchKernelGGL(k_classgraft_upper, dim3((unsigned)k.nblk, (unsigned)n), dim3(GenGeo<2>::WAVES * 64), 0, e->stream, a);
+		    }
+		    ClassGraftArgs s{};
+		    s.cands = e->d_graft_cands, s.P = P, s.Pp = e->Pp, s.C = C, s.max_iterations = o.max_iterations, s.max_passes = o.max_passes;
+		    s.lower = o.lower, s.upper = o.upper, s.tolerance = o.tolerance, s.lnl_tolerance = o.lnl_tolerance;
+		    s.tipcode = e->d_tipmask, s.tipsets = e->d_tipsets, s.props = e->d_props, s.model = e->d_model, s.rates = e->d_rates, s.weights = e->d_weights;
+		    s.start = e->d_qopt_start, s.F = e->d_graft_F, s.K = e->d_graft_K, s.out = e->d_tripod_res, s.status = e->d_tripod_status;
+		    if (!cands.empty()) hipLaunchKernelGGL(k_classgraft_solve, dim3((unsigned)cands.size()), dim3(CLASSOPT_THREADS), 0, e->stream, s);
+		    const size_t cells = k.rows * N;
+		    hipLaunchKernelGGL(k_tripod_finish, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, e->stream, cells, e->d_spr_cand_of.get(), e->d_tripod_res.get(),
+		                       e->d_tripod_status.get(), e->d_tripod_out.get(), e->d_tripod_counts.get());
+		    HIP_TRY(hipGetLastError());
+		    out.resize(cells * 5);
+		    counts.resize(cells * 3);
+		    HIP_TRY(hipMemcpyAsync(out.data(), e->d_tripod_out, sizeof(double) * out.size(), hipMemcpyDeviceToHost, e->stream));
+		    HIP_TRY(hipMemcpyAsync(counts.data(), e->d_tripod_counts, sizeof(int32_t) * counts.size(), hipMemcpyDeviceToHost, e->stream));
+		    HIP_TRY(hipStreamSynchronize(e->stream));  // (also covers the lists, which the next chunk builds anew)
+		    for (size_t r = 0; r < k.rows; r++)
+			    for (size_t w = 0; w < (size_t)N; w++) {
+				    const size_t from = r * N + w, to = (size_t)live[k.first + r] * N + w;
+				    const double *v = &out[from * 5];
+				    std::copy(v, v + 3, o.lengths + to * 3);
+				    o.lnl[to] = v[3];
+				    if (o.initial_lnl) o.initial_lnl[to] = v[4];
+				    if (o.passes) o.passes[to] = counts[from * 3];
+				    prof.visits += counts[from * 3 + 1];
+				    prof.iterations += counts[from * 3 + 2];
+			    }
+		    prof.chunks++;
+		    prof.candidates += (int64_t)cands.size();
+		    return PHYAMD_OK;
+	    });
+}
+
+int shard_spr_optimize_general(Shard *e, int flags, const SprOptimizeArgs &o) {
+	CHECK_ENGINE(e);
+	return profiled_call(e, &Shard::tripod_prof, phyamd_spr_optimize_profile{}, [&](phyamd_spr_optimize_profile &prof) { return run_spr_optimize_general(e, flags, o, prof); });
 }
 
 // ---- the ML distance of pairs of taxa (phyamd_pairwise_distances) ---------------------------------------------------------------

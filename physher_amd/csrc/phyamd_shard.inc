@@ -223,7 +223,7 @@ struct Shard {
 	DeviceArray<BatchOp> d_batch_item_ops{&batch_mem};  // [item][post-order T - 1 | pre-order T - 1]
 	DeviceArray<int32_t> d_batch_roots{&batch_mem};     // [item]
 	// what the scratch holds: every call describes what it needs as a ScratchPlan (phyamd_queries.inc: batch_plan, reweight_plan,
-	// nni_base_plan with nni_plan and cbopt_plan, nni_gen_plan, classcb_plan, blopt_plan, spr_plan with tripod_plan, spr_gen_plan, pairdist_plan, bhess_plan, sitelnl_plan; phyamd_place_calls.inc: place_plan,
+	// nni_base_plan with nni_plan and cbopt_plan, nni_gen_plan, classcb_plan, blopt_plan, spr_plan with tripod_plan, spr_gen_plan with classgraft_plan, pairdist_plan, bhess_plan, sitelnl_plan; phyamd_place_calls.inc: place_plan,
 	// place_gen_plan, qopt_plan, qopt_gen_plan) and gets at least that, so a call of one kind
 	// never runs in the scratch of another with too few upper slots or without its lists.  batch_held: the plan the arrays were last
 	// allocated by, for batch_items items (the Hessian's arrays, grown beside it, are judged by their sizes alone)
@@ -351,6 +351,15 @@ struct Shard {
 	DeviceArray<int32_t> d_sprg_nops{&batch_mem};         // [row]
 	DeviceArray<ClassSprCand> d_sprg_cands{&batch_mem};   // [row][at most N], the rows' candidates one after the other
 	DeviceArray<double> d_sprg_work{&batch_mem};          // [row][T - 1 uppers by internal node | path slots][C][20][Pp]
+	// phyamd_spr_optimize_general (phyamd_graft_gen.inc) runs the same walk of the same rows with the same lists and shares the own-partial
+	// records of the placement calls (d_placeg_owns), the starts of the placement optimiser (d_qopt_start: here t_p, t_w, t_u) and the
+	// 4-state SPR optimiser's results, status words and scattered cells (d_tripod_res, _status, _out, _counts); it adds the own
+	// partials, and per candidate of a row its record, pi o U and the coefficients of the branch being visited.  tripod_prof keeps
+	// the last SPR optimise call of either kind
+	DeviceArray<double> d_graft_own{&batch_mem};          // [T - 1 by internal node | row][path slots]: planes [C][20][Pp]
+	DeviceArray<ClassGraftCand> d_graft_cands{&batch_mem};  // [row][at most N], the rows' candidates one after the other
+	DeviceArray<double> d_graft_F{&batch_mem};            // [candidate][C][20][Pp]
+	DeviceArray<double> d_graft_K{&batch_mem};            // [candidate][C][20][Pp]
 	// phyamd_state_posteriors / phyamd_site_rate_posteriors (phyamd_post.inc): the rows of a chunk, their staged results -- [rows][P][S]
 	// posteriors and [rows][P] states, or [P][C] + [P] site rates -- and, 20 / 60 / 61 states, each row's own partial p_n (true_lower_gen).
 	// On demand, like d_branch: the calls read what the keep-partials gradient left and have no entry in the record above

@@ -423,6 +423,22 @@ class Engine:
         stops when a pass gains no more than lnl_tolerance (passes > 0) or after max_passes (passes = -max_passes); a lnL that is
         not finite ends it in band with passes negative.  NaN (passes 0) wherever spr_log_likelihoods has NaN.  The engine's tree,
         lengths and partials stay.  No fallback: EngineError where spr_log_likelihoods refuses, and on a sharded engine."""
+        return self._spr_optimize(self._lib.phyamd_spr_optimize, prune, lower, upper, tolerance, max_iterations, lnl_tolerance, max_passes, want_initial_lnl,
+                                  want_passes, flags)
+
+    def spr_optimize_general(self, prune=None, lower=1e-8, upper=10.0, tolerance=1e-8, max_iterations=100, lnl_tolerance=1e-6, max_passes=50,
+                             want_initial_lnl=True, want_passes=True, flags=0):
+        """spr_optimize for an engine of 20 states: the same tuple, in spr_log_likelihoods_general's rows, columns and rearranged
+        trees, by spr_optimize's start, pass order, visit rule and stop test; all three branches are always visited.  The two
+        branches a visit holds enter through the engine's own matrix arithmetic, the visited one through the eigen sum.  The rows
+        are walked from the resident lower partials: afterwards the engine is one with set_keep_partials(True) that has run
+        gradient(); its tree, lengths and models stay.  A lnL that is not finite ends an entry in band with passes negative.  No
+        fallback: EngineError for a state count other than 20, more than 8 categories, flags, tiled patterns, explicit matrices, a
+        rescaling or a sharded engine, and a row whose scratch does not fit the memory cap."""
+        return self._spr_optimize(self._lib.phyamd_spr_optimize_general, prune, lower, upper, tolerance, max_iterations, lnl_tolerance, max_passes,
+                                  want_initial_lnl, want_passes, flags)
+
+    def _spr_optimize(self, call, prune, lower, upper, tolerance, max_iterations, lnl_tolerance, max_passes, want_initial_lnl, want_passes, flags):
         pr = None
         if prune is not None:
             pr = np.ascontiguousarray(prune, dtype=np.int32)
@@ -433,12 +449,12 @@ class Engine:
         lnl0 = np.empty((count, self.N)) if want_initial_lnl else None
         passes = np.empty((count, self.N), dtype=np.int32) if want_passes else None
         opt = lambda a: None if a is None else _ptr(a)
-        self._check(self._lib.phyamd_spr_optimize(self._h, flags, count, opt(pr), lower, upper, tolerance, max_iterations, lnl_tolerance, max_passes,
-                                                  _ptr(lengths), _ptr(lnl), opt(lnl0), opt(passes)))
+        self._check(call(self._h, flags, count, opt(pr), lower, upper, tolerance, max_iterations, lnl_tolerance, max_passes, _ptr(lengths), _ptr(lnl), opt(lnl0),
+                         opt(passes)))
         return lengths, lnl, lnl0, passes
 
     def spr_optimize_profile(self):
-        """Of the last spr_optimize: prunes (rows), chunks (of rows), candidates, visits and iterations (over all candidates),
+        """Of the last spr_optimize or spr_optimize_general: prunes (rows), chunks (of rows), candidates, visits and iterations (over all candidates),
         scratch_bytes, ms."""
         p = _lib.SprOptimizeProfile()
         self._check(self._lib.phyamd_get_spr_optimize_profile(self._h, C.byref(p)))
